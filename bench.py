@@ -2,7 +2,7 @@
 """bench.py -- the headline benchmark of BASELINE.json: query-intervals/s of the overlap
 search (igd search -q, hits-only) on a roadmap-scale synthetic .igd, on N MI355X of one node.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of Q device-resident queries per GPU
 (k_query_bounds -> igd_scan_sorted -> k_reduce_slabs; the bucket kernels and igd_scan_tiles when the
@@ -18,9 +18,14 @@ RANK/WORLD_SIZE/MASTER_* in the environment; started as plain `python bench.py -
 process spawns the N ranks itself -- BEFORE it touches the GPU or imports torch -- and relays
 rank 0's JSON line.
 
-Prints ONE compact JSON line on rank 0 (contract in the task statement; at most LINE_CAP = 8 KB -- the driver keeps the last ~8 KB of
-stdout -- asserted here and in tests/test_gpu_bench_line.py) and writes the whole record, every side measurement in full, to
-bench_extra.json (--extra-out).  Both carry
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: metric, value (query-intervals/s),
+unit, higher_is_better, dtype, ms_per_step (one timed step), the workload's config and the per-file counts' total and checksum.
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step goes to DIR/hits.npy (float64[nFiles],
+the per-file overlap counts of one batch); the inputs are seeded, so two builds run with the same arguments compare array for array.
+
+--full adds every side measurement and check below.  It prints ONE compact JSON line on rank 0 (at most LINE_CAP = 8 KB -- the
+driver keeps the last ~8 KB of stdout -- asserted here and in tests/test_gpu_bench_line.py) and writes the whole record, every
+side measurement in full, to bench_extra.json (--extra-out).  Both carry
   roofline     : dominant kernel (igd_scan_sorted; igd_scan_tiles on the bucket path).  `achieved` / `frac` price its HIP-event time
                  against the COMPULSORY bytes of the batch, computed in this run by the engine
                  (igd_hip_batch_traffic: every visited unit's records once in the bytes of the image
@@ -70,11 +75,18 @@ def parse_args(argv=None):
     ap.add_argument("--shuffled", action="store_true", help="queries in generation order, not position-sorted (N=1)")
     ap.add_argument("--v", type=int, default=0, help="`-v N` signal filter (config 3)")
     ap.add_argument("--dir", default="/tmp/igdb")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--extra-out", default="", help="where the whole record goes (default: bench_extra.json beside bench.py); stdout carries "
-                                                     "ONE compact line of at most 8 KB")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs runs")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold-cache runs of the headline batch (profiling runs: their launches would be averaged in)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement and check: roofline, device list, cold-cache runs, CPU baselines, the command line "
+                         "end to end, extra_configs, the oracle's committed counts, the N > 1 anchor; the whole record goes to --extra-out. "
+                         "Without it the run sets up, warms up, times the K steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(hits.npy: float64[nFiles], the per-file overlap counts of one batch)")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the CPU baselines and the command line runs")
+    ap.add_argument("--extra-out", default="", help="(--full) where the whole record goes (default: bench_extra.json beside bench.py); "
+                                                     "stdout carries ONE compact line of at most 8 KB")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the extra_configs runs")
+    ap.add_argument("--no-cold", action="store_true", help="(--full) skip the cold-cache runs of the headline batch (profiling runs: their launches would be averaged in)")
     ap.add_argument("--slab-of", type=int, default=0, metavar="G",
                     help="N=1 only: this GPU's step is slab 0 of a G-GPU config-4 job (G x --queries position-sorted queries) -- "
                          "what one of G GPUs would run, measured without the other G-1")
@@ -860,6 +872,25 @@ def write_extra(full, path):
     return None
 
 
+DUMP_CAP = 60 << 20  # --dump-outputs: bytes in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (the counts are below 2^53: exact).  An array that would
+    take the total past `cap` is replaced by a fixed sample (seed 0, indices ascending) of as many elements as still fit."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = cap
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.nbytes > left:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, left // a.itemsize, replace=False))
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    return cap - left
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -939,23 +970,28 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
 
-    # who took part: world size as the process group saw it, and each rank's device (ordinal, PCI bus id, name)
-    try:
-        props = torch.cuda.get_device_properties(local)
-        me = "rank %d: cuda:%d %s pci %s" % (rank, local, props.name, getattr(props, "pci_bus_id", "?"))
-    except Exception as e:
-        me = "rank %d: cuda:%d (%s)" % (rank, local, e)
-    devices = gather_strings(me)
     mode = "v" if (args.v > 0 and db.gtype == 1) else "hits"
     hits_job = job.d_hits.cpu().numpy()      # K identical batches per rank, summed over ranks
     assert args.steps > 0 and (hits_job % args.steps == 0).all(), "hits[] is not K times one batch"
     hits_one = hits_job // args.steps        # one batch per rank, summed over ranks
-    tkey = "%s/%s/q%d%s%s" % (mode, "shuffled" if args.shuffled else "sorted", Q, "/exact" if args.exact_arrays else "",
-                              "/slab0of%d" % args.slab_of if (world == 1 and args.slab_of > 1) else "")
-    rl = job.roofline(prof, tkey if world == 1 else None)     # outside the timed region
+    if rank == 0 and args.dump_outputs:
+        nbytes = dump_outputs(args.dump_outputs, {"hits": hits_one})
+        log("[bench] outputs of the last step (%d bytes) written to %s" % (nbytes, args.dump_outputs))
+
+    if args.full:
+        # who took part: world size as the process group saw it, and each rank's device (ordinal, PCI bus id, name)
+        try:
+            props = torch.cuda.get_device_properties(local)
+            me = "rank %d: cuda:%d %s pci %s" % (rank, local, props.name, getattr(props, "pci_bus_id", "?"))
+        except Exception as e:
+            me = "rank %d: cuda:%d (%s)" % (rank, local, e)
+        devices = gather_strings(me)
+        tkey = "%s/%s/q%d%s%s" % (mode, "shuffled" if args.shuffled else "sorted", Q, "/exact" if args.exact_arrays else "",
+                                  "/slab0of%d" % args.slab_of if (world == 1 and args.slab_of > 1) else "")
+        rl = job.roofline(prof, tkey if world == 1 else None)     # outside the timed region
 
     anchor = None
-    if rank == 0 and world > 1:
+    if args.full and rank == 0 and world > 1:
         try:                                                # the N = 1 anchor of the weak-scaling curve: the same per-GPU batch size, unsharded
             a_q = synth.make_queries_slab(Q, 0, Q, seed=7, genome=synth.HG38)
             a_job = Job(db, dev, stream, a_q[0], a_q[1], a_q[2], args.v, gflags, args.query_layout)
@@ -967,14 +1003,6 @@ def main():
         except Exception as e:
             anchor = {"error": str(e)}
     if rank == 0:
-        box = measure_rates(local)
-        # what `frac` is a fraction of, three ways: compulsory bytes over the kernel's time (frac), the bytes the PMC counters saw
-        # over the same time (frac_pmc), and compulsory bytes over the whole step -- all three kernels and their launch gaps
-        rl["frac_of"] = "compulsory bytes of the launch (igd_hip_batch_traffic) / kernel_ms / 8 TB/s"
-        rl["frac_pmc"] = (rl["traffic"] / (rl["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if (rl.get("traffic") and rl["kernel_ms"] > 0) else None
-        rl["step_frac"] = rl["bytes_per_launch"] / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS
-        rl["box"] = dict(box, note="measured in this run by igd_hip_measure_rates: float4 copy kernel (read+write bytes), "
-                                   "float4 read-only kernel, pinned D2H / H2D copies")
         value = world * Q * args.steps / elapsed
         line = {
             "metric": "query-intervals/sec (igd search -q, hits-only) on roadmap-scale synthetic .igd",
@@ -992,85 +1020,96 @@ def main():
                                         else "contig numbers + starts + ends (12 B/query; igd_hip_search_dev)"),
                        "collective": ("ONE sum all-reduce of int64[%d] per job (after the %d batches), inside the timed region"
                                       % (db.nfiles, args.steps)) if grouped else "none"},
-            "roofline": rl,
-            "n_ranks_seen": ranks_seen(), "devices": devices,
-            "dist_backend": (dist.get_backend() if dist.is_initialized() else None),
             "hits_per_step_total": int(hits_one.sum()),
             "hits_checksum": hits_checksum(hits_one),
-            "db_open_s": open_s,
         }
-        # the oracle's counts of the same workload (committed fixture): a fast kernel with other counts is not a result
-        gkey = None
-        if args.files == 1900 and args.per_file == 26316 and not args.queries:
-            if world == 1 and args.slab_of == 8:
-                gkey = "config4_slab0_of_8_v%d" % (args.v if mode == "v" else 0)
-            elif world == 1 and args.slab_of <= 1:
-                gkey = "config2_sorted_q1000000_v%d" % (args.v if mode == "v" else 0)
-        elif args.files == 1900 and args.per_file == 26316 and world == 1 and args.queries == CONFIG4_PER_GPU and not args.shuffled and args.slab_of <= 1:
-            gkey = "config4_share_q12500000_v%d" % (args.v if mode == "v" else 0)
-        g = golden_counts(gkey) if gkey else None
-        if g:
-            line["matches_oracle"] = (line["hits_per_step_total"], line["hits_checksum"]) == g
-            if not line["matches_oracle"]:
-                raise SystemExit("bench.py: per-file counts differ from the oracle's (tests/golden/bench_checksums.json[%s]): %s vs %s"
-                                 % (gkey, (line["hits_per_step_total"], line["hits_checksum"]), g))
-        if world == 1 and not args.no_cold:
-            try:                                            # the headline batch with the last-level cache emptied before every launch
-                cold = job.run_cold()
-                rl["cold"] = {"kernel_ms": cold["scan_ms"], "pipeline_ms": cold["pipeline_ms"], "launches_timed": cold["launches"],
-                              "achieved": rl["bytes_per_launch"] / (cold["scan_ms"] * 1e-3) / 1e9 if cold["scan_ms"] > 0 else None,
-                              "frac": rl["bytes_per_launch"] / (cold["scan_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if cold["scan_ms"] > 0 else None,
-                              "how": "512 MiB of other memory read (not written: clean lines) on the same stream between two launches, outside "
-                                     "the kernel's HIP-event pair: no launch finds the image in the 256 MiB Infinity Cache"}
-                cd = job.run_cold(dirty=True)
-                rl["cold_after_writes"] = {"kernel_ms": cd["scan_ms"], "pipeline_ms": cd["pipeline_ms"], "launches_timed": cd["launches"],
-                                           "frac": rl["bytes_per_launch"] / (cd["scan_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if cd["scan_ms"] > 0 else None,
-                                           "how": "as `cold`, but the 512 MiB are read AND written (what a memset would leave): the "
-                                                  "cache is full of dirty lines and their write-back competes with the kernel's reads"}
-            except Exception as e:
-                rl["cold"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu:
-            bed = os.path.join(args.dir, "q%d_%s.bed" % (Q, "shuf" if args.shuffled else "sorted"))
-            if not os.path.exists(bed):
-                synth.write_bed(bed, synth.HG38, ichr, qs, qe)
-            extra = ["-v", str(args.v)] if mode == "v" else []
-            line["cpu_baseline"] = cpu_baseline(igd_path, bed, Q, int(hits_one.sum()), extra=extra)
-            try:
-                line["cli_end_to_end"] = cli_end_to_end(igd_path, bed, int(hits_one.sum()))
-                line["cli_end_to_end"]["reference_q_seconds"] = line["cpu_baseline"].get("seconds") if not extra else None
-            except Exception as e:
-                line["cli_end_to_end"] = {"error": str(e)}
-            if args.files == 1900 and args.per_file == 26316 and not args.no_extra and line["cpu_baseline"].get("kind") == "reference":
-                try:
-                    g = golden_counts("config4_share_q12500000_v0")
-                    line["cpu_baseline"]["all_cores_large"] = cpu_baseline_allcores_large(
-                        line["cpu_baseline"]["exe"], igd_path, synth.HG38,
-                        synth.make_queries_slab(CONFIG4_PER_GPU, 0, CONFIG4_PER_GPU, seed=7, genome=synth.HG38), g[0] if g else -1, args.dir)
+        if not args.full:
+            text = json.dumps(line, separators=(",", ":"))
+            assert len(text) <= LINE_CAP and "\n" not in text, len(text)
+            print(text, flush=True)
+        else:
+            box = measure_rates(local)
+            # what `frac` is a fraction of, three ways: compulsory bytes over the kernel's time (frac), the bytes the PMC counters saw
+            # over the same time (frac_pmc), and compulsory bytes over the whole step -- all three kernels and their launch gaps
+            rl["frac_of"] = "compulsory bytes of the launch (igd_hip_batch_traffic) / kernel_ms / 8 TB/s"
+            rl["frac_pmc"] = (rl["traffic"] / (rl["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if (rl.get("traffic") and rl["kernel_ms"] > 0) else None
+            rl["step_frac"] = rl["bytes_per_launch"] / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS
+            rl["box"] = dict(box, note="measured in this run by igd_hip_measure_rates: float4 copy kernel (read+write bytes), "
+                                       "float4 read-only kernel, pinned D2H / H2D copies")
+            line.update({"roofline": rl, "n_ranks_seen": ranks_seen(), "devices": devices,
+                         "dist_backend": (dist.get_backend() if dist.is_initialized() else None), "db_open_s": open_s})
+            # the oracle's counts of the same workload (committed fixture): a fast kernel with other counts is not a result
+            gkey = None
+            if args.files == 1900 and args.per_file == 26316 and not args.queries:
+                if world == 1 and args.slab_of == 8:
+                    gkey = "config4_slab0_of_8_v%d" % (args.v if mode == "v" else 0)
+                elif world == 1 and args.slab_of <= 1:
+                    gkey = "config2_sorted_q1000000_v%d" % (args.v if mode == "v" else 0)
+            elif args.files == 1900 and args.per_file == 26316 and world == 1 and args.queries == CONFIG4_PER_GPU and not args.shuffled and args.slab_of <= 1:
+                gkey = "config4_share_q12500000_v%d" % (args.v if mode == "v" else 0)
+            g = golden_counts(gkey) if gkey else None
+            if g:
+                line["matches_oracle"] = (line["hits_per_step_total"], line["hits_checksum"]) == g
+                if not line["matches_oracle"]:
+                    raise SystemExit("bench.py: per-file counts differ from the oracle's (tests/golden/bench_checksums.json[%s]): %s vs %s"
+                                     % (gkey, (line["hits_per_step_total"], line["hits_checksum"]), g))
+            if world == 1 and not args.no_cold:
+                try:                                            # the headline batch with the last-level cache emptied before every launch
+                    cold = job.run_cold()
+                    rl["cold"] = {"kernel_ms": cold["scan_ms"], "pipeline_ms": cold["pipeline_ms"], "launches_timed": cold["launches"],
+                                  "achieved": rl["bytes_per_launch"] / (cold["scan_ms"] * 1e-3) / 1e9 if cold["scan_ms"] > 0 else None,
+                                  "frac": rl["bytes_per_launch"] / (cold["scan_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if cold["scan_ms"] > 0 else None,
+                                  "how": "512 MiB of other memory read (not written: clean lines) on the same stream between two launches, outside "
+                                         "the kernel's HIP-event pair: no launch finds the image in the 256 MiB Infinity Cache"}
+                    cd = job.run_cold(dirty=True)
+                    rl["cold_after_writes"] = {"kernel_ms": cd["scan_ms"], "pipeline_ms": cd["pipeline_ms"], "launches_timed": cd["launches"],
+                                               "frac": rl["bytes_per_launch"] / (cd["scan_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if cd["scan_ms"] > 0 else None,
+                                               "how": "as `cold`, but the 512 MiB are read AND written (what a memset would leave): the "
+                                                      "cache is full of dirty lines and their write-back competes with the kernel's reads"}
                 except Exception as e:
-                    line["cpu_baseline"]["all_cores_large"] = {"error": str(e)}
-        if world == 1 and not args.no_extra:
-            line["extra_configs"] = extra_configs(db, dev, stream, args, box)
-            line["scale_anchor"] = scale_anchor(line["extra_configs"])
-        if world > 1 and anchor is not None:
-            # like for like: N ranks x 1.25e7 queries against ONE GPU running 1.25e7 queries of the same generator (measured by rank 0
-            # right after the job, outside its timed region) -- the N = 1 line of bench.py runs BASELINE config 2 (10^6 queries per
-            # step), another workload, so a ratio of the two lines' `value` says nothing about scaling
-            line["scale_anchor"] = anchor
-            line["efficiency_vs_anchor"] = value / (world * anchor["value"]) if anchor.get("value") else None
-            # what one GPU measured for a rank's step of an N-GPU job (slab 0 of N, committed with its source): the curve a
-            # measured SCALE file can be checked against -- a rank's step gets SHORTER as N grows (fewer tiles per slab)
-            try:
-                line["scale_prediction"] = json.load(open(os.path.join(ROOT, "profiles", "scale_prediction.json")))
-                pm = line["scale_prediction"]["step_ms"].get(str(world))
-                if pm and Q == CONFIG4_PER_GPU:
-                    line["scale_prediction"]["this_run_vs_predicted_step"] = (1e3 * elapsed / args.steps) / pm
-            except Exception as e:
-                line["scale_prediction"] = {"error": str(e)}
-        extra_path = write_extra(line, args.extra_out or os.path.join(ROOT, "bench_extra.json"))
-        log("[bench] the whole record (%d bytes as one JSON line) is in %s" % (len(json.dumps(line)), extra_path))
-        text = compact_line(line, os.path.relpath(extra_path, ROOT) if extra_path and extra_path.startswith(ROOT) else extra_path)
-        assert len(text) <= LINE_CAP and "\n" not in text, len(text)
-        print(text, flush=True)
+                    rl["cold"] = {"error": str(e)}
+            if world == 1 and not args.no_cpu:
+                bed = os.path.join(args.dir, "q%d_%s.bed" % (Q, "shuf" if args.shuffled else "sorted"))
+                if not os.path.exists(bed):
+                    synth.write_bed(bed, synth.HG38, ichr, qs, qe)
+                extra = ["-v", str(args.v)] if mode == "v" else []
+                line["cpu_baseline"] = cpu_baseline(igd_path, bed, Q, int(hits_one.sum()), extra=extra)
+                try:
+                    line["cli_end_to_end"] = cli_end_to_end(igd_path, bed, int(hits_one.sum()))
+                    line["cli_end_to_end"]["reference_q_seconds"] = line["cpu_baseline"].get("seconds") if not extra else None
+                except Exception as e:
+                    line["cli_end_to_end"] = {"error": str(e)}
+                if args.files == 1900 and args.per_file == 26316 and not args.no_extra and line["cpu_baseline"].get("kind") == "reference":
+                    try:
+                        g = golden_counts("config4_share_q12500000_v0")
+                        line["cpu_baseline"]["all_cores_large"] = cpu_baseline_allcores_large(
+                            line["cpu_baseline"]["exe"], igd_path, synth.HG38,
+                            synth.make_queries_slab(CONFIG4_PER_GPU, 0, CONFIG4_PER_GPU, seed=7, genome=synth.HG38), g[0] if g else -1, args.dir)
+                    except Exception as e:
+                        line["cpu_baseline"]["all_cores_large"] = {"error": str(e)}
+            if world == 1 and not args.no_extra:
+                line["extra_configs"] = extra_configs(db, dev, stream, args, box)
+                line["scale_anchor"] = scale_anchor(line["extra_configs"])
+            if world > 1 and anchor is not None:
+                # like for like: N ranks x 1.25e7 queries against ONE GPU running 1.25e7 queries of the same generator (measured by rank 0
+                # right after the job, outside its timed region) -- the N = 1 line of bench.py runs BASELINE config 2 (10^6 queries per
+                # step), another workload, so a ratio of the two lines' `value` says nothing about scaling
+                line["scale_anchor"] = anchor
+                line["efficiency_vs_anchor"] = value / (world * anchor["value"]) if anchor.get("value") else None
+                # what one GPU measured for a rank's step of an N-GPU job (slab 0 of N, committed with its source): the curve a
+                # measured SCALE file can be checked against -- a rank's step gets SHORTER as N grows (fewer tiles per slab)
+                try:
+                    line["scale_prediction"] = json.load(open(os.path.join(ROOT, "profiles", "scale_prediction.json")))
+                    pm = line["scale_prediction"]["step_ms"].get(str(world))
+                    if pm and Q == CONFIG4_PER_GPU:
+                        line["scale_prediction"]["this_run_vs_predicted_step"] = (1e3 * elapsed / args.steps) / pm
+                except Exception as e:
+                    line["scale_prediction"] = {"error": str(e)}
+            extra_path = write_extra(line, args.extra_out or os.path.join(ROOT, "bench_extra.json"))
+            log("[bench] the whole record (%d bytes as one JSON line) is in %s" % (len(json.dumps(line)), extra_path))
+            text = compact_line(line, os.path.relpath(extra_path, ROOT) if extra_path and extra_path.startswith(ROOT) else extra_path)
+            assert len(text) <= LINE_CAP and "\n" not in text, len(text)
+            print(text, flush=True)
     del job
     db.close()
     if grouped:

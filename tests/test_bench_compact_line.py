@@ -1,6 +1,7 @@
-"""bench.py's stdout contract without a GPU: the compact line built from a full record -- the real one of round 6
-(profiles/r06/bench_extra.json) and one blown up far beyond it -- stays within the 8 KB the driver's stdout tail holds, keeps the
-contract keys, and sheds its optional parts (never the contract keys) when it would not fit."""
+"""bench.py's stdout contract without a GPU: the compact line built from a full record -- a real one of the round 6 build
+(tests/golden/bench_extra_full.json: `bench.py --gpus 1 --steps 20 --warmup 5 --full` on an MI355X, the reference binary's path made
+relative) and one blown up far beyond it -- stays within the 8 KB the driver's stdout tail holds, keeps the contract keys, and sheds
+its optional parts (never the contract keys) when it would not fit."""
 import json
 import os
 import sys
@@ -15,7 +16,7 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def _full():
-    return json.load(open(os.path.join(ROOT, "profiles", "r06", "bench_extra.json")))
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "bench_extra_full.json")))
 
 
 def test_the_recorded_round_6_line_is_compact_and_complete():

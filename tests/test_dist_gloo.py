@@ -63,11 +63,18 @@ def test_bench_spawns_its_ranks_before_touching_the_gpu(tmp_path, monkeypatch):
     import importlib
     import bench
     importlib.reload(bench)
+    # each rank writes its file whole (rename); rank 1 fails only after rank 0's file is there -- the launcher stops the
+    # other ranks at once when one fails, and rank 0 may well start later than rank 1
     stub = tmp_path / "stub.py"
-    stub.write_text("import os, sys\n"
-                    "open(os.path.join(%r, 'r' + os.environ['RANK']), 'w').write(' '.join([os.environ['WORLD_SIZE'], "
+    stub.write_text("import os, sys, time\n"
+                    "d, r = %r, os.environ['RANK']\n"
+                    "open(os.path.join(d, 'r' + r + '.tmp'), 'w').write(' '.join([os.environ['WORLD_SIZE'], "
                     "os.environ['LOCAL_RANK'], os.environ['MASTER_ADDR'], os.environ['MASTER_PORT']] + sys.argv[1:]))\n"
-                    "sys.exit(3 if os.environ['RANK'] == '1' else 0)\n" % str(tmp_path))
+                    "os.replace(os.path.join(d, 'r' + r + '.tmp'), os.path.join(d, 'r' + r))\n"
+                    "t = time.time()\n"
+                    "while r == '1' and not os.path.exists(os.path.join(d, 'r0')) and time.time() - t < 120:\n"
+                    "    time.sleep(0.01)\n"
+                    "sys.exit(3 if r == '1' else 0)\n" % str(tmp_path))
     monkeypatch.setattr(bench, "__file__", str(stub))
     mods = set(sys.modules)
     rc = bench.spawn_ranks(2, ["--gpus", "2", "--steps", "4"])

@@ -19,7 +19,7 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     d = short_tmpdir("igb")
     try:
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--files", "40", "--per-file", "3000", "--queries", "20000",
-                            "--steps", "3", "--warmup", "1", "--dir", d, "--extra-out", os.path.join(d, "bench_extra.json")],
+                            "--steps", "3", "--warmup", "1", "--dir", d, "--full", "--extra-out", os.path.join(d, "bench_extra.json")],
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
         assert p.returncode == 0, p.stderr.decode()[-800:]
         lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
@@ -122,7 +122,7 @@ def test_bench_two_ranks_config4_slabs_and_allreduce(launcher):
         env.pop("WORLD_SIZE", None)
         env.pop("RANK", None)
         tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--files", str(files), "--per-file", str(per_file),
-                "--queries", str(q), "--steps", "3", "--warmup", "1", "--dir", d, "--extra-out", os.path.join(d, "bench_extra.json")]
+                "--queries", str(q), "--steps", "3", "--warmup", "1", "--dir", d, "--full", "--extra-out", os.path.join(d, "bench_extra.json")]
         if launcher == "self-spawn":
             cmd = [sys.executable] + tail
         else:
@@ -202,7 +202,7 @@ def test_bench_one_rank_forced_through_the_collective_path():
                    MASTER_PORT=str(29900 + os.getpid() % 40), HSA_ENABLE_IPC_MODE_LEGACY="0")
         env.pop("IGD_DIST_BACKEND", None)
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--files", "40", "--per-file", "3000", "--queries", "20000",
-                            "--steps", "3", "--warmup", "1", "--dir", d, "--no-extra", "--no-cpu", "--extra-out", os.path.join(d, "bench_extra.json")],
+                            "--steps", "3", "--warmup", "1", "--dir", d, "--full", "--no-extra", "--no-cpu", "--extra-out", os.path.join(d, "bench_extra.json")],
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
         assert p.returncode == 0, p.stderr.decode()[-1500:]
         j = json.loads([l for l in p.stdout.decode().splitlines() if l.strip().startswith("{")][0])
@@ -261,7 +261,7 @@ def test_bench_eight_ranks_control_flow_on_one_gpu():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                "--master-addr", "127.0.0.1", "--master-port", str(29300 + os.getpid() % 250),
                os.path.join(ROOT, "bench.py"), "--gpus", "8", "--files", str(files), "--per-file", str(per_file),
-               "--queries", str(q), "--steps", "3", "--warmup", "1", "--dir", d, "--extra-out", os.path.join(d, "bench_extra.json")]
+               "--queries", str(q), "--steps", "3", "--warmup", "1", "--dir", d, "--full", "--extra-out", os.path.join(d, "bench_extra.json")]
         t = time.time()
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
         wall = time.time() - t
@@ -282,5 +282,43 @@ def test_bench_eight_ranks_control_flow_on_one_gpu():
         total, chk = _expected_whole(d, files, per_file, 8 * q)
         assert j["hits_per_step_total"] == total and j["hits_checksum"] == chk
         assert wall < 600, wall
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_last_step():
+    """Without --full: the headline keys only, no side file, --steps sets the timed steps; --dump-outputs writes the last
+    step's per-file counts (float64[nFiles]), the same array from run to run, equal to a search of the same queries."""
+    import numpy as np
+    from igd_amd import Database, synth
+    d = short_tmpdir("igb")
+    try:
+        dumps = []
+        for steps in (4, 7):
+            out = os.path.join(d, "out%d" % steps)
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--files", "40", "--per-file", "3000", "--queries", "20000",
+                                "--steps", str(steps), "--warmup", "1", "--dir", d, "--dump-outputs", out,
+                                "--extra-out", os.path.join(d, "bench_extra.json")],
+                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+            assert p.returncode == 0, p.stderr.decode()[-800:]
+            lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+            assert len(lines) == 1
+            c = json.loads(lines[0])
+            for k, t in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str), ("ms_per_step", float)):
+                assert isinstance(c[k], t), k
+            assert c["steps"] == steps and c["warmup"] == 1 and c["higher_is_better"] is True and c["unit"] == "query-intervals/s"
+            assert abs(c["value"] - 20000 * steps / (c["ms_per_step"] * steps * 1e-3)) / c["value"] < 1e-6
+            assert not {"roofline", "cpu_baseline", "extra_configs", "cli_end_to_end", "devices", "extra_file"} & set(c)
+            assert not os.path.exists(os.path.join(d, "bench_extra.json"))
+            assert os.listdir(out) == ["hits.npy"]
+            h = np.load(os.path.join(out, "hits.npy"))
+            assert h.dtype == np.float64 and h.shape == (40,) and int(h.sum()) == c["hits_per_step_total"]
+            dumps.append(h)
+        assert np.array_equal(dumps[0], dumps[1])
+        db = Database(os.path.join(d, "rm40x3000.igd"))
+        ichr, qs, qe = synth.make_queries(20000, seed=7, genome=synth.HG38, sorted_=True)
+        want, _ = db.search(ichr, qs, qe)
+        db.close()
+        assert np.array_equal(dumps[0], want.astype(np.float64))
     finally:
         shutil.rmtree(d, ignore_errors=True)

@@ -13,7 +13,7 @@ tag=$1; shift
 root=$PWD
 out=$root/gpurun_out/profile_$tag
 mkdir -p $out
-python3 bench.py --no-extra "$@" > $out/bench.json 2> $out/bench.err || true
+python3 bench.py --full --no-extra "$@" > $out/bench.json 2> $out/bench.err || true
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py --no-cpu --no-extra --no-cold "$@" > $out/stats.log 2>&1 || true
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python3 $root/bench.py --no-cpu --no-extra --no-cold --steps 10 --warmup 2 "$@" > $out/fetch.log 2>&1 || true

@@ -7,7 +7,7 @@ python tools/prep.py > /dev/null 2>&1
 for d in igd_amd/lib igd_amd/libv_*; do
   [ -f $d/libigd_hip.so ] || continue
   tag=$(basename $d)
-  IGD_AMD_LIBDIR=$PWD/$d python bench.py --no-cpu --no-extra "$@" > $out/$tag.json 2> $out/$tag.err
+  IGD_AMD_LIBDIR=$PWD/$d python bench.py --full --no-cpu --no-extra "$@" > $out/$tag.json 2> $out/$tag.err
   python3 - $out/$tag.json $tag <<'PY'
 import json, sys
 try:
