@@ -1,0 +1,99 @@
+// engine/sets_dev.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
+// igd_sets_count: many small query sets in one launch (igd_hip_search_sets), one hits[] row per set
+// ------------------------------------------------------------------------------------------
+// The batch pipeline of igd_hip_search_dev adds a whole batch into ONE int64[nFiles] row.  A caller with a thousand sets of
+// a thousand queries each would pay that pipeline's launches, copies and sync once per set; here the sets share one launch.
+// Work item = slice: (row k, queries [a, b)) of at most one set, cut on the host (host_sets.hpp).  Persistent workgroups of
+// four waves stride over the slice table; the waves of a workgroup own different queries of its slice.  Per query its tiles
+// come from query_span (the rule word as the grouping kernels get it, re-tiled gate bit included), and each tile is walked
+// FORWARD from its first record, 64 records per lane-step, two steps per iteration (all loads of both issued together):
+//       lob <= start < qe  &&  end > qs  [&& value >= v]
+// with lob = INT_MIN in the query's first tile and the tile's start coordinate in the later ones (the reference's prefix
+// skip of records counted in an earlier tile, src/igd_search.c:510-511).  The records of a tile are ordered by start, so
+// the walk ends after the first step whose largest start is >= qe -- no bisection, hence no chain of dependent loads.
+// Counters: LDS, one 64-bit counter per file (ds_add_u64; cannot overflow), flushed at the end of each slice with device-
+// scope atomic adds of the non-zero ones into row k (slices of one set may run on several CUs at once).  A database with
+// more files than IGD_SETS_LDS_FILES adds straight into the row with global atomics instead (LDS = false).
+struct SetSlice { int32_t row, a, b, pad; };         // 16 bytes: one scalar load per slice
+
+#define IGD_SETS_WG 256                              // threads per workgroup (4 waves)
+#define IGD_SETS_LDS_FILES 8192                      // 64-bit counters in 64 KiB of LDS
+#define IGD_SETS_GRID 2048                           // persistent workgroups (8 per CU of the MI355X's 256)
+
+template <bool USE_V, bool LDS>
+__global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_count(DbView db, const int32_t *__restrict__ q_ichr,
+                                                             const int32_t *__restrict__ q_qs, const int32_t *__restrict__ q_qe,
+                                                             const SetSlice *__restrict__ slices, int nSlices, int rule, int v,
+                                                             u64 *__restrict__ rows, u64 *__restrict__ totals)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    igd_lds_u64 *cnt = (igd_lds_u64 *)smem;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nF = db.nFiles;
+    if (LDS) {
+        for (int f = threadIdx.x; f < nF; f += IGD_SETS_WG) cnt[f] = 0;
+        __syncthreads();
+    }
+    for (int s = blockIdx.x; s < nSlices; s += gridDim.x) {
+        const SetSlice sl = slices[s];
+        u64 *row = rows + (size_t)sl.row * (size_t)nF;
+        u64 found = 0;
+        for (int q = sl.a + wave; q < sl.b; q += IGD_SETS_WG / IGD_WAVE) {
+            const int qs = __builtin_amdgcn_readfirstlane(q_qs[q]);
+            const int qe = __builtin_amdgcn_readfirstlane(q_qe[q]);
+            const int cc = __builtin_amdgcn_readfirstlane(q_ichr[q]);
+            int gt0, ntl;
+            if (!query_span(db, cc, qs, qe, rule, gt0, ntl)) continue;
+            gt0 = __builtin_amdgcn_readfirstlane(gt0);
+            ntl = __builtin_amdgcn_readfirstlane(ntl);
+            for (int k = 0; k < ntl; k++) {
+                const int t = gt0 + k;
+                const int tcnt = __builtin_amdgcn_readfirstlane(db.tileCnt[t]);
+                if (tcnt == 0) continue;
+                const int lob = (k == 0) ? INT_MIN : __builtin_amdgcn_readfirstlane(db.tileBd[t]);
+                const int64_t toff = db.tileOff[t];
+                for (int i0 = 0; i0 < tcnt; i0 += 2 * IGD_WAVE) {
+                    const int i = i0 + lane, j = i + IGD_WAVE;
+                    const bool ok0 = i < tcnt, ok1 = j < tcnt;
+                    const int s0 = ok0 ? db.start[toff + i] : INT_MAX;
+                    const int e0 = ok0 ? db.end[toff + i] : INT_MIN;
+                    const int x0 = ok0 ? db.idx[toff + i] : -1;
+                    const int s1 = ok1 ? db.start[toff + j] : INT_MAX;
+                    const int e1 = ok1 ? db.end[toff + j] : INT_MIN;
+                    const int x1 = ok1 ? db.idx[toff + j] : -1;
+                    bool h0 = (s0 >= lob) & (s0 < qe) & (e0 > qs) & ((unsigned)x0 < (unsigned)nF);
+                    bool h1 = (s1 >= lob) & (s1 < qe) & (e1 > qs) & ((unsigned)x1 < (unsigned)nF);
+                    if (USE_V) {
+                        const int v0 = ok0 ? db.value[toff + i] : INT_MIN;
+                        const int v1 = ok1 ? db.value[toff + j] : INT_MIN;
+                        h0 = h0 & (v0 >= v);
+                        h1 = h1 & (v1 >= v);
+                    }
+                    if (LDS) {
+                        if (h0) (void)__hip_atomic_fetch_add(cnt + x0, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (h1) (void)__hip_atomic_fetch_add(cnt + x1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    } else {
+                        if (h0) (void)__hip_atomic_fetch_add(row + x0, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (h1) (void)__hip_atomic_fetch_add(row + x1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    found += (u64)__popcll(__ballot(h0)) + (u64)__popcll(__ballot(h1));
+                    // records are ordered by start: a step whose largest start is >= qe ends the tile
+                    if (__builtin_amdgcn_readlane(s1, 63) >= qe) break;
+                }
+            }
+        }
+        if (lane == 0 && found) (void)__hip_atomic_fetch_add(totals + sl.row, found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (LDS) {
+            __syncthreads();
+            for (int f = threadIdx.x; f < nF; f += IGD_SETS_WG) {
+                const u64 c = cnt[f];
+                if (c) {
+                    (void)__hip_atomic_fetch_add(row + f, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    cnt[f] = 0;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}

@@ -770,6 +770,90 @@ static int64_t hit_map(uint32_t **hitmap, int use_v, int32_t v)
 int64_t getMap(uint32_t **hitmap) { return hit_map(hitmap, 0, 0); }                  /* :772-826 */
 int64_t getMap_v(uint32_t **hitmap, int32_t v) { return hit_map(hitmap, 1, v); }      /* :829-886 */
 
+/* ------------------------------- `igd search -Q <list>` ------------------------------- */
+/* One query set per line of `list` (blank lines skipped, a trailing CR stripped).  For each set in list order: the line
+ * "Query set <k>: <path>" and then exactly what `igd search <db> -q <path> [-v N]` prints for that file.  When all the sets
+ * together hold at most igdc_host_limit() queries every file takes the `-q` route in turn (the host's for small files);
+ * otherwise all of them are counted by ONE engine call (igd_hip_search_sets) on one device. */
+static void print_hits_table(const int64_t *hits)
+{
+    printf("index\t number of regions\t number of hits\t File_name\n");
+    int64_t total = 0;
+    for (int32_t i = 0; i < IGD->nFiles; i++) {
+        if (hits[i] > 0)
+            printf("%i\t%i\t%lld\t%s\n", i, IGD->finfo[i].nr, (long long)hits[i], IGD->finfo[i].fileName);
+        total += hits[i];
+    }
+    printf("Total: %lld\n", (long long)total);
+}
+
+static void search_sets(const char *listName, int32_t v, int64_t *hits)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles;
+    char **paths = NULL;
+    int32_t n = 0, cap = 0;
+    igdc_lines *r = igdc_lines_open(listName);
+    if (!r) { printf("Cannot open query list %s\n", listName); return; }
+    char *line;
+    int64_t len;
+    while ((line = igdc_lines_next(r, &len)) != NULL) {
+        size_t L = strlen(line);
+        while (L > 0 && (line[L - 1] == '\r' || line[L - 1] == '\n')) line[--L] = '\0';
+        if (L == 0) continue;
+        if (n == cap) { cap = cap ? 2 * cap : 64; paths = (char **)realloc(paths, sizeof(char *) * (size_t)cap); }
+        paths[n++] = strdup(line);
+    }
+    igdc_lines_close(r);
+    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` (:1023-1030) */
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    if (nq <= igdc_host_limit()) {
+        /* every file through the `-q` route (it reads the file again: one code path for the text of a block) */
+        for (int32_t k = 0; k < n && !g_fail_rc; k++) {
+            memset(hits, 0, sizeof(int64_t) * (size_t)nfiles);
+            printf("Query set %d: %s\n", (int)k, paths[k]);
+            if (IGD->gType == 0) getOverlaps0(paths[k], hits);
+            else if (v > 0) getOverlaps_v(paths[k], hits, v);
+            else getOverlaps(paths[k], hits);
+            if (!g_fail_rc) print_hits_table(hits);     /* (as `-q`: no table after an engine failure) */
+        }
+    } else {
+        int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq);
+        int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq);
+        int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+        int64_t *rows = (int64_t *)calloc((size_t)n * (size_t)nfiles + 1, sizeof(int64_t));
+        off[0] = 0;
+        for (int32_t k = 0; k < n; k++) {
+            if (q[k].n) {
+                memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+                memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+                memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+            }
+            off[k + 1] = off[k] + q[k].n;
+        }
+        double t0 = now_s();
+        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one; -Q is one device) */
+        if (dev) {
+            const int rc = igd_hip_search_sets(dev, ichr, qs, qe, off, n, ev, rule, 0, rows, NULL);
+            if (rc != IGD_HIP_OK) engine_failed("search", rc);
+            phase("search of the query sets (H2D + kernels + D2H)", &t0);
+        }
+        for (int32_t k = 0; k < n && !g_fail_rc; k++) {
+            printf("Query set %d: %s\n", (int)k, paths[k]);
+            print_hits_table(rows + (size_t)k * (size_t)nfiles);
+        }
+        free(ichr); free(qs); free(qe); free(off); free(rows);
+    }
+    for (int32_t k = 0; k < n; k++) { igdc_queries_free(&q[k]); free(paths[k]); }
+    free(q); free(paths);
+}
+
 /* ------------------------------- `igd search` ----------------------------------------- */
 static int usage_search(void)
 {
@@ -823,11 +907,13 @@ int igd_search(int argc, char **argv)                                        /* 
 
     int32_t v = 0, qs = 1, qe = 2;
     int mode = -1, full = 0;
-    char *chrm = NULL, *qfName = (char *)"";
+    char *chrm = NULL, *qfName = (char *)"", *listName = NULL;
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
         const char *a = argv[i];
-        if (strcmp(a, "-q") == 0) {
+        if (strcmp(a, "-Q") == 0) {                   /* (not the reference's: a list of query files, see search_sets) */
+            if (i + 1 < argc) listName = argv[i + 1];
+        } else if (strcmp(a, "-q") == 0) {
             if (i + 1 >= argc) { printf("No query file.\n"); return EX_OK; }
             qfName = argv[i + 1];
             mode = 1;
@@ -916,6 +1002,8 @@ int igd_search(int argc, char **argv)                                        /* 
                 printf("%i\t%i\t%10.6f\t%s\n", i, IGD->finfo[i].nr, sm[i], IGD->finfo[i].fileName);
             free(sm);
         }
+    } else if (listName) {                        /* only where the reference's own parse leaves nothing to do */
+        search_sets(listName, v, hits);
     } else {
         free(hits);
         return usage_search();

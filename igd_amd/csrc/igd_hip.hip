@@ -299,6 +299,11 @@ struct igd_hip_db {
     int32_t *d_qc, *d_qs, *d_qe;
     int64_t qcap;
     int64_t *d_hits, *d_total;
+    // igd_hip_search_sets (host_sets.hpp): the rows and totals of one chunk of sets, the slice table of its small sets
+    int64_t *d_setRows, *d_setTot;
+    int64_t setRowCap, setTotCap;
+    struct SetSlice *d_setSlices;
+    int64_t setSliceCap;
     hipStream_t stream;
     // profiling
     std::vector<hipEvent_t> ev;   // 4 per launch: pipeline start, scan start, scan stop, pipeline stop
@@ -324,12 +329,14 @@ struct igd_hip_db {
 #include "engine/enumerate_dev.hpp"   // `-f` enumeration kernels
 #include "engine/hitmap_dev.hpp"      // `-m` hit map kernel
 #include "engine/batch_stats_dev.hpp" // instrumentation: terms of the algorithmic byte model
+#include "engine/sets_dev.hpp"        // igd_sets_count: many small query sets in one launch, one hits[] row per set
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
 #include "engine/host_enumerate.hpp"  // `-f` on the host side: chunked, double-buffered
 #include "engine/seqpare.hpp"         // Seqpare `-s`: kernels and host
 #include "engine/host_misc.hpp"       // igd_hip_hitmap, igd_hip_batch_stats
+#include "engine/host_sets.hpp"       // igd_hip_search_sets: chunks of sets, small ones sliced, large ones through the batch pipeline
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

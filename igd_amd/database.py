@@ -125,6 +125,41 @@ class Database:
                                        vf, rule, int(flags), hits.ctypes.data, C.byref(total)), "igd_hip_search")
         return hits[: self.nfiles], total.value
 
+    def search_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, hits=None, flags=0):
+        """Many query sets in one call (igd_hip_search_sets).  Set k is the queries [set_off[k], set_off[k + 1]) of the
+        concatenated arrays (set_off: int64[nsets + 1], monotone, set_off[0] = 0).  Returns (hits int64[nsets, nfiles],
+        totals int64[nsets]); row k is what search() returns for set k alone.  hits (int64[nsets, nfiles], C order) is added
+        to when given.  flags as search() (they steer the route of sets of 2^17 queries and more)."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+        nsets = len(set_off) - 1
+        if nsets < 0:
+            raise IgdError("search_sets: set_off needs nsets + 1 entries")
+        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("search_sets: set_off[-1] = %d, but %d / %d / %d queries given"
+                           % (set_off[-1], len(ichr), len(qs), len(qe)))
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        if hits is None:
+            hits = np.zeros((nsets, self.nfiles), np.int64)
+        elif hits.dtype != np.int64 or hits.shape != (nsets, self.nfiles) or not hits.flags.c_contiguous:
+            raise IgdError("search_sets: hits must be a C-ordered int64[%d, %d]" % (nsets, self.nfiles))
+        totals = np.zeros(max(nsets, 1), np.int64)
+        _chk(self._H.igd_hip_search_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data,
+                                         nsets, vf, rule, int(flags), hits.ctypes.data if hits.size else None,
+                                         totals.ctypes.data), "igd_hip_search_sets")
+        return hits, totals[:nsets]
+
+    def search_files(self, paths, v=0):
+        """One query set per BED file (read as `igd search -q` reads it): (hits int64[len(paths), nfiles], totals)."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.search_sets(cat[0], cat[1], cat[2], set_off, v)
+
     def search_dev(self, d_ichr, d_qs, d_qe, nq, d_hits, d_total=None, v=0, rule=None,
                    value_filter=None, stream=None, flags=0):
         """Resident batch: arguments are device pointers (ints).  Asynchronous.

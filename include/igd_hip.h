@@ -126,6 +126,15 @@ int igd_hip_search(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const
 int igd_hip_search_ex(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                       int64_t nq, int32_t v, int rule, int flags, int64_t *hits, int64_t *total);
 
+/* Many query sets in one call.  Set k = queries [set_off[k], set_off[k+1]) (host int64[nsets+1], monotone, set_off[0]=0);
+ * hits (host int64[nsets * nFiles], row-major) and totals (host int64[nsets], may be NULL) are ADDED to.  Row k equals
+ * igd_hip_search_ex on set k alone.  flags as igd_hip_search_ex (they steer the large-set route only).  Blocking.
+ * Sets of fewer than 2^17 queries are counted together by one kernel (a row of LDS counters per workgroup); larger ones go
+ * through the batch pipeline of igd_hip_search_dev, one row each.  A bad set_off is IGD_HIP_ERR_ARG before any launch. */
+int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                        const int64_t *set_off, int32_t nsets, int32_t v, int rule, int flags,
+                        int64_t *hits, int64_t *totals);
+
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
  * `stream` (a hipStream_t; NULL = the engine's own stream) and returns without waiting.
