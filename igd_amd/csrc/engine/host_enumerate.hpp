@@ -116,7 +116,6 @@ static int enumerate_core(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
         whole = (igd_hip_hit *)((char *)hdr + 64);
         ENUM_PHASE("pinned result buffer");
     }
-    static const bool zeroCopy = getenv("IGD_ENUM_ZEROCOPY") != nullptr;   // A/B: the fill kernel stores straight into pinned host memory
     const int64_t cap = db->enumChunkCap * (p8 ? 2 : 1);   // overlaps per chunk buffer
     const size_t hitBytes = p8 ? sizeof(igd_hip_hit8) : sizeof(igd_hip_hit);
     int64_t qa = 0, prevA = 0, prevB = 0;
@@ -141,13 +140,13 @@ static int enumerate_core(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
             if (e != hipSuccess) break;
             if (p8)
                 igd_enum_queries<true, false, true><<<egrid, 256, 0, st>>>(db->v, db->d_qc, db->d_qs, db->d_qe, (int)qa, (int)qb, nullptr,
-                                                                           db->d_qoff, qoff[qa], zeroCopy ? hostDst : db->d_enumOut[b], idxBits);
+                                                                           db->d_qoff, qoff[qa], db->d_enumOut[b], idxBits);
             else
             igd_enum_queries<true><<<egrid, 256, 0, st>>>(db->v, db->d_qc, db->d_qs, db->d_qe, (int)qa, (int)qb, nullptr,
-                                                          db->d_qoff, qoff[qa], zeroCopy ? hostDst : db->d_enumOut[b]);
+                                                          db->d_qoff, qoff[qa], db->d_enumOut[b]);
             e = hipEventRecord(db->evFill[b], st);
             if (e == hipSuccess) e = hipStreamWaitEvent(db->copyStream, db->evFill[b], 0);
-            if (e == hipSuccess && !zeroCopy)
+            if (e == hipSuccess)
                 e = hipMemcpyAsync(hostDst, db->d_enumOut[b], (size_t)nh * hitBytes, hipMemcpyDeviceToHost, db->copyStream);
             if (e == hipSuccess) e = hipEventRecord(db->evCopy[b], db->copyStream);
             if (e != hipSuccess) break;

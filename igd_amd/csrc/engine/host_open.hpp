@@ -230,9 +230,11 @@ extern "C" int igd_hip_open(const igd_hip_desc *d, int device, igd_hip_db **out)
         db->forceRank = fr && *fr ? atoi(fr) : -1;
         const char *fb = getenv("IGD_HIP_BIG");
         db->bigImage = fb && *fb == '1';                 // (|| the record count, once it is known)
-        db->qbVec1 = getenv("IGD_HIP_QB_VEC1") != nullptr;
         const char *fd = getenv("IGD_HIP_DIRECT");
         db->forceDirect = fd && *fd ? atoi(fd) : -1;
+        db->splitNoStage = getenv("IGD_HIP_SPLIT_NOSTAGE") != nullptr;
+        db->splitNoBits = getenv("IGD_HIP_SPLIT_NOBITS") != nullptr;
+        db->splitNoRegion = getenv("IGD_HIP_SPLIT_NOREGION") != nullptr;
         db->timing = tim;
     }
     db->nbp = d->nbp; db->gType = d->gType; db->nCtg = d->nCtg; db->nFiles = d->nFiles;

@@ -52,7 +52,8 @@ static int ensure_workspace(igd_hip_db *db, int64_t nq, int pairBytes)
     return IGD_HIP_OK;
 }
 
-// The bucket step (count -> scan -> scatter).  gate != 0: every kernel returns at once unless
+// The bucket step (count -> scan -> scatter) with global atomics: only for a database too large for the split path
+// (spShift < 0: more than 2^22 tiles).  gate != 0: every kernel returns at once unless
 // k_query_bounds marked this batch unsorted (ctl[CTL_UNSORTED] == gate).  Leaves the pair
 // counts in d_pairN, the range ends in d_pairPos, and d_pairCnt zeroed again.
 static int launch_bucket(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe,
@@ -74,51 +75,38 @@ static int launch_bucket(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d
     return IGD_HIP_OK;
 }
 
-// The same grouping without global atomics (k_split_*); (qs,qe) pairs only.
+// The same grouping without global atomics (k_split_*); (qs,qe) pairs only.  spShift >= 0: ensure_workspace allocated d_spSub.
 static int launch_split(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe,
                         int nq, int rule, int gate, int packed, hipStream_t st, u64 *zeroHits, u64 *zeroTotal)
 {
     const int nWG = (nq + SP_Q - 1) / SP_Q;
-    static const bool oneWG = getenv("IGD_HIP_SPLIT_ONE") != nullptr;      // A/B: one workgroup per coarse bucket, whatever the batch (until round 4)
-    const bool shared = !oneWG && db->d_spSub != nullptr;
-    uint32_t *bases = shared ? db->d_spSub + (((size_t)db->spCoarse * SPF_S) << db->spShift) : nullptr;
-    int32_t *blong = shared ? (int32_t *)(bases + db->spCoarse) : nullptr;
+    uint32_t *bases = db->d_spSub + (((size_t)db->spCoarse * SPF_S) << db->spShift);
+    int32_t *blong = (int32_t *)(bases + db->spCoarse);
     // (one bit per tile in LDS when they fit 40 KiB -- up to 327 680 tiles: hg38 in 16 kbp tiles has 188 505)
-    static const bool noBits = getenv("IGD_HIP_SPLIT_NOBITS") != nullptr;            // A/B: tileCnt[] gathers (until round 5)
-    const int bitsWords = (!noBits && db->v.tileBits && db->nT <= 40 * 1024 * 8) ? (db->nT + 31) / 32 + 1 : 0;   // (+ the array's word of slack)
-    const int ctgStaged = (!noBits && db->nCtg <= 1024) ? db->nCtg : 0;                // ... and the two contig tables (8 KiB at most)
+    const int bitsWords = (!db->splitNoBits && db->v.tileBits && db->nT <= 40 * 1024 * 8) ? (db->nT + 31) / 32 + 1 : 0;   // (+ the array's word of slack)
+    const int ctgStaged = (!db->splitNoBits && db->nCtg <= 1024) ? db->nCtg : 0;       // ... and the two contig tables (8 KiB at most)
     // ... and the workgroup's region of tuples, put together in the same LDS before it is written out (SP_Q queries + 1/8 for
     // second tiles: 54 KiB; with the kernel's 8.3 KiB of counters within the 64 KiB a launch gets without asking)
-    static const bool noRegion = getenv("IGD_HIP_SPLIT_NOREGION") != nullptr;       // A/B: tuples stored one by one (until round 5)
-    const int stageCap = (noBits || noRegion) ? 0 : SP_Q + SP_Q / 8;
+    const int stageCap = (db->splitNoBits || db->splitNoRegion) ? 0 : SP_Q + SP_Q / 8;
     size_t ldsLocal = (size_t)bitsWords * 4 + (size_t)ctgStaged * 8;
     if (ldsLocal < (size_t)stageCap * 12 + 16) ldsLocal = (size_t)stageCap * 12 + 16;
-    static const bool noFast = getenv("IGD_HIP_SPLIT_NOFAST") != nullptr;           // A/B: the general per-query code for every database
-    if (!noFast && bitsWords && ctgStaged && db->v.vshift < 0 && db->v.shift >= 0 && db->spShift >= 2)
+    if (bitsWords && ctgStaged && db->v.vshift < 0 && db->v.shift >= 0 && db->spShift >= 2)
     k_split_local<true><<<nWG, SP_WG, ldsLocal, st>>>(db->v, d_ichr, d_qs, d_qe, nq, rule, packed, db->spShift, db->spCoarse, db->d_spTable,
                                          db->d_spT, db->d_long, db->d_ctl, gate, db->epoch, zeroHits, zeroTotal, blong, bitsWords, ctgStaged, stageCap);
     else
     k_split_local<false><<<nWG, SP_WG, ldsLocal, st>>>(db->v, d_ichr, d_qs, d_qe, nq, rule, packed, db->spShift, db->spCoarse, db->d_spTable,
                                          db->d_spT, db->d_long, db->d_ctl, gate, db->epoch, zeroHits, zeroTotal, blong, bitsWords, ctgStaged, stageCap);
     // staging area of the usual bucket (split_fine_whole): twice the bucket's share of an evenly spread batch, within 64 KiB of LDS
-    static const bool noStage = getenv("IGD_HIP_SPLIT_NOSTAGE") != nullptr;       // A/B: segments walked from memory, twice (until round 5)
     const size_t ldsCnt = (size_t)2 * 4 << db->spShift;
     int64_t cap = 2 * (((int64_t)nq + nq / 8) / db->spCoarse) + 256;
     if (cap < 1024) cap = 1024;
     if (cap > (int64_t)((65536 - 256 - ldsCnt) / 12)) cap = (int64_t)((65536 - 256 - ldsCnt) / 12);
-    if (noStage || cap < 256) cap = 0;
-    if (!shared)
-    k_split_fine<<<db->spCoarse, SPF_WG, ldsCnt + (size_t)cap * 12, st>>>(db->nT, db->spShift, db->spCoarse, nWG, db->d_spTable,
-                                                                          db->d_spT,
-                                                                          db->d_pairN, db->d_pairPos, (int2 *)db->d_pairs,
-                                                                          db->d_ctl, gate, db->d_ctl, db->epoch, packed ? db->d_heavy : nullptr, (int)cap);
-    else {
-        k_split_fine_a<<<db->spCoarse * SPF_S, SPF_WG, ldsCnt + (size_t)cap * 12, st>>>(db->nT, db->spShift, db->spCoarse, nWG, db->d_spTable, db->d_spT,
-            db->d_spSub, bases, blong, db->d_pairN, db->d_pairPos, (int2 *)db->d_pairs, db->d_ctl, gate, db->d_ctl, db->epoch, packed ? db->d_heavy : nullptr, (int)cap);
-        // (an empty launch when no bucket is piled up: 4.5 us, with 96 workgroups as with 512)
-        k_split_fine_b<<<db->spCoarse * SPF_S < 512 ? db->spCoarse * SPF_S : 512, SPF_WG, (size_t)4 << db->spShift, st>>>(db->nT, db->spShift, db->spCoarse, nWG, db->d_spTable, db->d_spT,
-            db->d_spSub, bases, blong, db->d_pairN, db->d_pairPos, (int2 *)db->d_pairs, db->d_ctl, gate, db->d_ctl, db->epoch, packed ? db->d_heavy : nullptr);
-    }
+    if (db->splitNoStage || cap < 256) cap = 0;
+    k_split_fine_a<<<db->spCoarse * SPF_S, SPF_WG, ldsCnt + (size_t)cap * 12, st>>>(db->nT, db->spShift, db->spCoarse, nWG, db->d_spTable, db->d_spT,
+        db->d_spSub, bases, blong, db->d_pairN, db->d_pairPos, (int2 *)db->d_pairs, db->d_ctl, gate, db->d_ctl, db->epoch, packed ? db->d_heavy : nullptr, (int)cap);
+    // (an empty launch when no bucket is piled up: 4.5 us, with 96 workgroups as with 512)
+    k_split_fine_b<<<db->spCoarse * SPF_S < 512 ? db->spCoarse * SPF_S : 512, SPF_WG, (size_t)4 << db->spShift, st>>>(db->nT, db->spShift, db->spCoarse, nWG, db->d_spTable, db->d_spT,
+        db->d_spSub, bases, blong, db->d_pairN, db->d_pairPos, (int2 *)db->d_pairs, db->d_ctl, gate, db->d_ctl, db->epoch, packed ? db->d_heavy : nullptr);
     HIPCHK(hipGetLastError());
     return IGD_HIP_OK;
 }
@@ -305,7 +293,6 @@ static int search_dev_impl(igd_hip_db *db, const int32_t *d_ichr, const int32_t 
     db->lastDirect = direct ? 1 : 0;
     if (mode != 2) {
         bool vec = ((((uintptr_t)d_ichr) | ((uintptr_t)d_qs) | ((uintptr_t)d_qe)) & 15) == 0;   // our own word arrays are aligned
-        if (db->qbVec1) vec = false;                  // A/B (IGD_HIP_QB_VEC1, read at open)
         const bool fast = packed && db->v.shift >= 0 && db->nCtg <= QB_CTG;
         // a small batch: one query per thread (more waves share the gaps between its queries), and enough workgroups for
         // the head and tail of firstQ[] -- 10^3 queries left 190 000 entries to ONE workgroup: 90 us
@@ -347,20 +334,16 @@ static int search_dev_impl(igd_hip_db *db, const int32_t *d_ichr, const int32_t 
     k_query_bounds<VEC_, FAST_, WGT_><<<QB_GRID(WGT_ * VEC_), WGT_, 0, st>>>(db->v, d_ichr, d_qs, d_qe, (int)nq, krule,               \
         packed ? 1 : 0, db->d_firstQ, db->d_lpos, db->d_fix, db->d_ctl, db->epoch, zh, zt, db->d_qw, db->d_later, db->d_spill,         \
         (int2 *)db->d_laterHdr, mode == 1 ? 1 : 0)
-#ifndef IGD_QB_WIDE
-#define IGD_QB_WIDE 1024
-#endif
         // (the bounds alone need no later blocks: workgroups of 256 -- more of them in flight, no barrier across 16 waves)
-        if (wide && !(direct && !getenv("IGD_HIP_BONLY_WIDE"))) { if (fast) QB_LAUNCH(4, true, IGD_QB_WIDE); else QB_LAUNCH(4, false, IGD_QB_WIDE); }
+        if (wide && !direct) { if (fast) QB_LAUNCH(4, true, 1024); else QB_LAUNCH(4, false, 1024); }
         else if (vec) { if (fast) QB_LAUNCH(4, true, 256); else QB_LAUNCH(4, false, 256); }
         else { if (fast) QB_LAUNCH(1, true, 256); else QB_LAUNCH(1, false, 256); }
 #undef QB_LAUNCH
 #undef QB_GRID
-        db->lbShift = wide ? (IGD_QB_WIDE == 1024 ? 12 : IGD_QB_WIDE == 512 ? 11 : 10) : vec ? 10 : 8;
+        db->lbShift = wide ? 12 : vec ? 10 : 8;
     }
     if (mode != 1) {
-        static const bool oldBucket = getenv("IGD_HIP_ATOMIC_BUCKETS") != nullptr;   // A/B: the counting sort with global atomics
-        if (db->spShift >= 0 && !oldBucket)
+        if (db->spShift >= 0)
             rc = launch_split(db, d_ichr, d_qs, d_qe, (int)nq, krule, mode == 2 ? 0 : db->epoch, packed ? 1 : 0, st,
                               mode == 2 ? zh : nullptr, mode == 2 ? zt : nullptr);
         else

@@ -25,9 +25,6 @@
 #ifndef IGD_DENSE_MIN
 #define IGD_DENSE_MIN 32
 #endif
-#ifndef IGD_LEAN_SMALL
-#define IGD_LEAN_SMALL 1        // the lean build's units of <= 64 / <= 192 records take the pairwise path over one / three slots
-#endif
 
 #define IGD_WLDS_S 512                                  // u16 entries per wave: the unit's sorted s' (+ sentinels)
 #define IGD_WLDS_H 328                                  // u32 entries per wave: histogram over record positions 0..320
@@ -117,15 +114,15 @@ __device__ __forceinline__ void s_issue(const DbView &db, const SortArgs &a, con
             const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void *)(db.pxv + off), 0, n * 4, 0x00020000);
 #pragma unroll
             for (int r = 0; r < IGD_SLOTS; r++) {
-                R.a[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsA, vo4, r * 256, IGD_NT_AUX);
-                R.x[r] = (int)__builtin_amdgcn_raw_buffer_load_b32(rsX, vo4, r * 256, IGD_NT_AUX);
+                R.a[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsA, vo4, r * 256, 0);
+                R.x[r] = (int)__builtin_amdgcn_raw_buffer_load_b32(rsX, vo4, r * 256, 0);
             }
         } else {
             const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void *)(db.px + off), 0, n * 2, 0x00020000);
 #pragma unroll
             for (int r = 0; r < IGD_SLOTS; r++) {
-                R.a[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsA, vo4, r * 256, IGD_NT_AUX);
-                R.x[r] = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsX, vo2, r * 128, IGD_NT_AUX);
+                R.a[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsA, vo4, r * 256, 0);
+                R.x[r] = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsX, vo2, r * 128, 0);
             }
         }
     } else {
@@ -135,8 +132,8 @@ __device__ __forceinline__ void s_issue(const DbView &db, const SortArgs &a, con
             const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void *)db.pxv, 0, n ? (int)((unsigned)(end + IGD_CHUNK) * 4u) : 0, 0x00020000);   // (see below)
 #pragma unroll
             for (int r = 0; r < IGD_SLOTS; r++) {
-                R.a[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsA, vo4 + r * 256, (int)(offLo * 4u), IGD_NT_AUX);
-                R.x[r] = (int)__builtin_amdgcn_raw_buffer_load_b32(rsX, vo4 + r * 256, (int)(offLo * 4u), IGD_NT_AUX);
+                R.a[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsA, vo4 + r * 256, (int)(offLo * 4u), 0);
+                R.x[r] = (int)__builtin_amdgcn_raw_buffer_load_b32(rsX, vo4 + r * 256, (int)(offLo * 4u), 0);
             }
         } else {
             // (the dataset numbers are NOT cut off at the unit's end: the lanes past it -- whose record words are 0, so they
@@ -147,8 +144,8 @@ __device__ __forceinline__ void s_issue(const DbView &db, const SortArgs &a, con
             const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void *)db.px, 0, n ? (int)((unsigned)(end + IGD_CHUNK) * 2u) : 0, 0x00020000);
 #pragma unroll
             for (int r = 0; r < IGD_SLOTS; r++) {
-                R.a[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsA, vo4 + r * 256, (int)(offLo * 4u), IGD_NT_AUX);
-                R.x[r] = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsX, vo2 + r * 128, (int)(offLo * 2u), IGD_NT_AUX);
+                R.a[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsA, vo4 + r * 256, (int)(offLo * 4u), 0);
+                R.x[r] = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsX, vo2 + r * 128, (int)(offLo * 2u), 0);
             }
         }
     }
@@ -181,17 +178,13 @@ __device__ __forceinline__ void s_issue(const DbView &db, const SortArgs &a, con
 // The queries of one batch of <= 64 candidates (word `P0` per lane, IGD_NEVER where there is none) against the
 // unit: per slot, the summary word picks the queries that can hit it at all (one compare for all 64), and only
 // those are broadcast and compared.  cnt[r] += hit; no exec masking, no LDS.
-template <bool ASM>
 __device__ __forceinline__ void match_words(const Raw2 &R, int (&cnt)[IGD_SLOTS], const uint32_t (&W)[IGD_SLOTS], int P0)
 {
-#if IGD_ASM_MATCH && !(IGD_EXP & 2)
-    if (ASM) {                                           // (match_slot_asm, scan_tiles.hpp: the loop written out)
+#if !(IGD_EXP & 2)
 #pragma unroll
-        for (int r = 0; r < IGD_SLOTS; r++) match_slot_asm<false>(cnt[r], W[r], P0, R.a[r], 0ull);
-        return;
-    }
-#endif
-    igd_u16x2 qv;
+    for (int r = 0; r < IGD_SLOTS; r++) match_slot_asm<false>(cnt[r], W[r], P0, R.a[r], 0ull);   // (scan_tiles.hpp: the loop written out)
+#else
+    igd_u16x2 qv;                                        // measurement build: the summary compares only
     __builtin_memcpy(&qv, &P0, 4);
 #pragma unroll
     for (int r = 0; r < IGD_SLOTS; r++) {
@@ -200,24 +193,10 @@ __device__ __forceinline__ void match_words(const Raw2 &R, int (&cnt)[IGD_SLOTS]
         const igd_u16x2 mw = __builtin_elementwise_max(wv, qv);
         uint32_t mww;
         __builtin_memcpy(&mww, &mw, 4);
-        unsigned long long m = __ballot(mww == W[r]);
-#if IGD_EXP & 2
+        const unsigned long long m = __ballot(mww == W[r]);
         asm volatile("" ::"v"(R.a[r]), "s"(m));
-        m = 0;
-#endif
-        while (m) {
-            const int src = __builtin_ctzll(m);
-            m &= ~(1ull << src);                         // s_bitset0_b64
-            const int q = __builtin_amdgcn_readlane(P0, src);
-            igd_u16x2 rec, qw;
-            __builtin_memcpy(&rec, &R.a[r], 4);
-            __builtin_memcpy(&qw, &q, 4);
-            const igd_u16x2 mx = __builtin_elementwise_max(rec, qw);   // v_pk_max_u16
-            uint32_t mxw;
-            __builtin_memcpy(&mxw, &mx, 4);
-            cnt[r] += mxw == R.a[r] ? 1 : 0;             // both halves already >= the query's
-        }
     }
+#endif
 }
 
 // later-tile word (k_query_bounds: later[]) -> compare word for this tile (IGD_NEVER when the query does not reach it)
@@ -371,19 +350,19 @@ __device__ __forceinline__ void s_compute(const DbView &db, const SortArgs &a, c
         // them, each on its way while the one before it is compared
         if (nE > IGD_WAVE) {
             int wn = (IGD_WAVE + lane < nE) ? ~a.qw0[f0 + IGD_WAVE + lane - nl] : (int)IGD_NEVER;
-            match_words<IGD_ASM_MATCH == 1 || !RANK>(R, cnt, W, w);
+            match_words(R, cnt, W, w);
             for (int p = IGD_WAVE; p < nE; p += IGD_WAVE) {
                 w = wn;
                 wn = (p + IGD_WAVE + lane < nE) ? ~a.qw0[f0 + p + IGD_WAVE + lane - nl] : (int)IGD_NEVER;
-                match_words<IGD_ASM_MATCH == 1 || !RANK>(R, cnt, W, w);
+                match_words(R, cnt, W, w);
             }
-        } else if (nE > 0) match_words<IGD_ASM_MATCH == 1 || !RANK>(R, cnt, W, w);
+        } else if (nE > 0) match_words(R, cnt, W, w);
         if (far)
             far_later<RANK>(a, __builtin_amdgcn_readlane(L.la, kk), ln, f0, lane, [&](int e) {
                 bool covers;
                 const int lw = later_word(db.nbp, e, g2, deadk, true, covers);
                 nLater += __popcll(__ballot(covers));
-                match_words<IGD_ASM_MATCH == 1 || !RANK>(R, cnt, W, lw);
+                match_words(R, cnt, W, lw);
             });
         // records that start before the tile (s' = 0, low half 65535) were matched by every "later tile"
         // query, none of which may count them (the reference's tS skip, :510-511)
@@ -742,7 +721,7 @@ __device__ __forceinline__ void s_compute_lean(const DbView &db, const SortArgs 
                                                u64 *hits, unsigned short *sl, unsigned int *hist, unsigned short *sb, bool rankOK,
                                                unsigned *spent, unsigned budget)
 {
-#if IGD_LEAN_SMALL && IGD_ASM_MATCH && IGD_EXP == 0 && !IGD_EXP_NOMATCH
+#if IGD_EXP == 0 && !IGD_EXP_NOMATCH
     if (CNT32 && LDS_HITS && FEW == 0) {
         const int un = R.n;
         if (un == 0) return;
@@ -761,12 +740,6 @@ __device__ __forceinline__ void s_compute_lean(const DbView &db, const SortArgs 
 #ifndef IGD_WG_RANK
 #define IGD_WG_RANK 768         // threads per workgroup / waves per SIMD of the full (rank method) build
 #define IGD_WPE_RANK 6
-#endif
-#ifndef IGD_XCD_REMAP
-#define IGD_XCD_REMAP 0         // 1: an XCD (blockIdx & 7) takes a contiguous eighth of every round of units
-#endif
-#ifndef IGD_LEAN_SKIP
-#define IGD_LEAN_SKIP 1         // the lean build steps through the visited units only when a round has many others
 #endif
 #define IGD_ROUND 62            // units whose descriptors a wave of the lean build reads at once, one per lane; the last two lanes stay empty (s_issue, PLAIN)
 #ifndef IGD_WG_LEAN
@@ -811,12 +784,7 @@ __attribute__((amdgpu_waves_per_eu(RANK ? IGD_WPE_RANK : IGD_WPE_LEAN, RANK ? IG
     }
     if (LDS_HITS) __syncthreads();
     const int wavesPerWG = WGT / IGD_WAVE;
-#if IGD_XCD_REMAP
-    const int lblk = (gridDim.x & 7) == 0 ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-#else
-    const int lblk = (int)blockIdx.x;
-#endif
-    const int gwave = lblk * wavesPerWG + wid;
+    const int gwave = (int)blockIdx.x * wavesPerWG + wid;
     const int nwaves = gridDim.x * wavesPerWG;
     Raw2 A, B;
     unsigned spent = 0u;                                 // CNT32: what this wave's units may have added to any one LDS counter
@@ -824,13 +792,12 @@ __attribute__((amdgpu_waves_per_eu(RANK ? IGD_WPE_RANK : IGD_WPE_LEAN, RANK ? IG
     // Issue slots go to the OLDEST wave of a SIMD first: left alone, the eight waves of a SIMD finish their equal
     // shares one after the other (the first in 63 % of the last one's time, measured) and the SIMD runs ever emptier
     // towards the end.  Every wave therefore lowers its own priority as it gets through its share -- a wave that is
-    // behind outranks one that is ahead -- and they finish together.
+    // behind outranks one that is ahead -- and they finish together.  (The four copies of this schedule stay written
+    // out: folded into one helper, the same steps compile to different register assignments in both scan kernels.)
     const int myUnits = (db.nUnits - gwave + nwaves - 1) / nwaves;
     const int quarter = (myUnits + 3) >> 2;
     int prioAt = quarter, prioLevel = 3, done = 0;
-#if IGD_OPT_PRIO
     __builtin_amdgcn_s_setprio(3);
-#endif
 
     for (int ub = gwave; ub < db.nUnits; ub += nwaves * IGD_ROUND) {
         SRegs L;
@@ -888,16 +855,14 @@ __attribute__((amdgpu_waves_per_eu(RANK ? IGD_WPE_RANK : IGD_WPE_LEAN, RANK ? IG
 #define IGD_UNIT(kk_, R_) do { if (RANK) s_compute<USE_V, CNT32, RANK, LDS_HITS, FEW>(db, a, L, kk_, lane, R_, hits, sl, hist, sb, rankOK, nullptr, &spent, budget); \
                                else s_compute_lean<USE_V, CNT32, LDS_HITS, FEW>(db, a, L, kk_, lane, R_, hits, sl, hist, sb, rankOK, &spent, budget); } while (0)
         const unsigned long long mVis = __ballot((L.c0 | L.ln) != 0 && L.n > 0);
-        if (RANK || (IGD_LEAN_SKIP && __popcll(mVis) * 4 < cntU * 3)) {
+        if (RANK || __popcll(mVis) * 4 < cntU * 3) {
             // The full build also serves batches that visit a fraction of the units (one GPU's slab of config 4: one unit
             // in eight): the wave steps through the units somebody asks about only -- an unvisited one still cost its
             // dozen zero-size loads, which queue up behind everybody's real ones.
             unsigned long long m = mVis;
             const int visited = __popcll(m);
             int qd = (visited + 3) >> 2, at = qd, level = 3, nd = 0;
-#if IGD_OPT_PRIO
             __builtin_amdgcn_s_setprio(3);
-#endif
             int ka = -1, kb = -1;
             if (m) { ka = __builtin_ctzll(m); m &= m - 1; }
             if (m) { kb = __builtin_ctzll(m); m &= m - 1; }
@@ -911,7 +876,6 @@ __attribute__((amdgpu_waves_per_eu(RANK ? IGD_WPE_RANK : IGD_WPE_LEAN, RANK ? IG
                 if (kb >= 0) s_compute<USE_V, CNT32, RANK, LDS_HITS, FEW>(db, a, L, kb, lane, B, hits, sl, hist, sb, rankOK, nullptr, &spent, budget);
                 kb = -1;
                 if (m) { kb = __builtin_ctzll(m); m &= m - 1; }
-#if IGD_OPT_PRIO
                 nd += 2;
                 if (nd >= at) {
                     at += qd;
@@ -920,7 +884,6 @@ __attribute__((amdgpu_waves_per_eu(RANK ? IGD_WPE_RANK : IGD_WPE_LEAN, RANK ? IG
                     else if (level == 1) __builtin_amdgcn_s_setprio(1);
                     else __builtin_amdgcn_s_setprio(0);
                 }
-#endif
             }
             continue;
         }
@@ -932,7 +895,6 @@ __attribute__((amdgpu_waves_per_eu(RANK ? IGD_WPE_RANK : IGD_WPE_LEAN, RANK ? IG
             IGD_UNIT(kk, A);
             s_issue<USE_V, BIG, !RANK>(db, a, L, kk + 2, kk + 2 < cntU, lane, A);
             if (kk + 1 < cntU) IGD_UNIT(kk + 1, B);
-#if IGD_OPT_PRIO
             done += 2;
             if (done >= prioAt) {
                 prioAt += quarter;
@@ -941,7 +903,6 @@ __attribute__((amdgpu_waves_per_eu(RANK ? IGD_WPE_RANK : IGD_WPE_LEAN, RANK ? IG
                 else if (prioLevel == 1) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
             }
-#endif
         }
     }
     if (LDS_HITS) {

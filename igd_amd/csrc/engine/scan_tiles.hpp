@@ -70,7 +70,6 @@ __device__ __forceinline__ void issue_unit(const DbView &db, const ScanArgs &a, 
     const int64_t off = (int64_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane(L.offHi, kk) << 32) |
                                   (unsigned)__builtin_amdgcn_readlane(L.offLo, kk));
     const int64_t base = active ? off : 0;
-#if IGD_BUFFER_LOADS
     if (PACKED) {
         // Buffer loads with a per-unit descriptor: hardware bounds checking returns 0 for lanes past
         // the unit's last record (0 is the "never matches" word) and for unvisited units (n = 0) no
@@ -92,30 +91,18 @@ __device__ __forceinline__ void issue_unit(const DbView &db, const ScanArgs &a, 
                 R.x[r] = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsX, vo2, r * 128, 0);
             }
         }
-    } else
-#endif
-    {
-    // uniform base pointers + (slot*64 + lane): the loads need no per-lane address arithmetic.
-    // Lanes past the unit's last record read the next unit's records (the arrays are padded by
-    // one chunk); compute_unit discards them.
-    const uint32_t *pa = db.pse + base;
-    const uint16_t *pxx = db.px + base;
-    const uint32_t *pvv = USE_V ? db.pxv + base : nullptr;
+    } else {
+        // exact arrays: uniform base pointers + (slot*64 + lane); lanes past the unit's last record read its first
+        // (compute_unit discards them)
 #pragma unroll
-    for (int r = 0; r < IGD_SLOTS; r++) {
-        const int i = r * IGD_WAVE + lane;
-        const int64_t at = base + (i < n ? i : 0);
-        if (PACKED) {
-            R.a[r] = pa[i];
-            if (USE_V) R.x[r] = (int)pvv[i];             // idx | value << 16: one word, one register
-            else R.x[r] = (int)pxx[i];
-        } else {
+        for (int r = 0; r < IGD_SLOTS; r++) {
+            const int i = r * IGD_WAVE + lane;
+            const int64_t at = base + (i < n ? i : 0);
             R.a[r] = (uint32_t)db.start[at];
             R.b[r] = db.end[at];
             R.x[r] = db.idx[at];
             if (USE_V) R.w[r] = db.value[at];
         }
-    }
     }
     if (SORTED) {
         int i = r0 + lane;
@@ -229,37 +216,13 @@ __device__ __forceinline__ void match_slot_asm(int &cnt, uint32_t W, int P0, uin
 __device__ __forceinline__ void match_slots(const Raw &R, int (&cnt)[IGD_SLOTS], const uint32_t (&W)[IGD_SLOTS], int P0,
                                             unsigned long long live)
 {
-#if IGD_ASM_MATCH && !IGD_EXP_NOMATCH
-#pragma unroll
-    for (int r = 0; r < IGD_SLOTS; r++) match_slot_asm<true>(cnt[r], W[r], P0, R.a[r], live);
-    return;
-#endif
-    igd_u16x2 qv;
-    __builtin_memcpy(&qv, &P0, 4);
 #pragma unroll
     for (int r = 0; r < IGD_SLOTS; r++) {
-        igd_u16x2 wv;
-        __builtin_memcpy(&wv, &W[r], 4);
-        const igd_u16x2 mw = __builtin_elementwise_max(wv, qv);
-        uint32_t mww;
-        __builtin_memcpy(&mww, &mw, 4);
-        unsigned long long m = __ballot(mww == W[r]) & live;
 #if IGD_EXP_NOMATCH
         asm volatile("" ::"v"(R.a[r]), "v"(R.x[r]));
-        continue;
+#else
+        match_slot_asm<true>(cnt[r], W[r], P0, R.a[r], live);
 #endif
-        while (m) {
-            const int src = __builtin_ctzll(m);
-            m &= m - 1;
-            const int q = __builtin_amdgcn_readlane(P0, src);
-            igd_u16x2 rec, qw;
-            __builtin_memcpy(&rec, &R.a[r], 4);
-            __builtin_memcpy(&qw, &q, 4);
-            const igd_u16x2 mx = __builtin_elementwise_max(rec, qw);   // v_pk_max_u16
-            uint32_t mxw;
-            __builtin_memcpy(&mxw, &mx, 4);
-            cnt[r] += mxw == R.a[r] ? 1 : 0;             // both halves already >= the query's
-        }
     }
 }
 
@@ -288,7 +251,7 @@ __device__ __forceinline__ void compute_unit(const DbView &db, const ScanArgs &a
         cnt[r] = 0;
         // lanes past the unit's last record hold someone else's data: make them unmatchable;
         // (compact image) so are records that fail the value filter -- v is fixed for the batch
-        bool drop = (IGD_BUFFER_LOADS && PACKED) ? false : (r * IGD_WAVE + lane >= un);
+        bool drop = PACKED ? false : (r * IGD_WAVE + lane >= un);
         if (PACKED && USE_V) {
             drop = drop || (R.x[r] >> 16) < a.v;         // arithmetic shift: the signed 16-bit value
             R.x[r] &= 0xFFFF;
@@ -419,9 +382,7 @@ __global__ __launch_bounds__(IGD_WG, IGD_WPE) void igd_scan_tiles(DbView db, Sca
     const int myUnits = (db.nUnits - gwave + nwaves - 1) / nwaves;
     const int quarter = (myUnits + 3) >> 2;
     int prioAt = quarter, prioLevel = 3, done = 0;
-#if IGD_OPT_PRIO
     __builtin_amdgcn_s_setprio(3);
-#endif
 
     for (int ub = gwave; ub < db.nUnits; ub += nwaves * IGD_WAVE) {
         UnitRegs L;
@@ -453,7 +414,6 @@ __global__ __launch_bounds__(IGD_WG, IGD_WPE) void igd_scan_tiles(DbView db, Sca
                 compute_unit<SORTED, USE_V, PACKED, WIN>(db, a, L, Lr0, Lr1, kk, lane, A, hits);
                 if (kk + 2 < cntU) issue_unit<SORTED, USE_V, PACKED>(db, a, L, Lr0, Lr1, kk + 2, lane, A);
                 if (kk + 1 < cntU) compute_unit<SORTED, USE_V, PACKED, WIN>(db, a, L, Lr0, Lr1, kk + 1, lane, B, hits);
-#if IGD_OPT_PRIO
                 done += 2;
                 if (done >= prioAt) {
                     prioAt += quarter;
@@ -462,13 +422,11 @@ __global__ __launch_bounds__(IGD_WG, IGD_WPE) void igd_scan_tiles(DbView db, Sca
                     else if (prioLevel == 1) __builtin_amdgcn_s_setprio(1);
                     else __builtin_amdgcn_s_setprio(0);
                 }
-#endif
             }
         } else {
             for (int kk = 0; kk < cntU; kk++) {
                 issue_unit<SORTED, USE_V, PACKED>(db, a, L, Lr0, Lr1, kk, lane, A);
                 compute_unit<SORTED, USE_V, PACKED, WIN>(db, a, L, Lr0, Lr1, kk, lane, A, hits);
-#if IGD_OPT_PRIO
                 done += 1;
                 if (done >= prioAt) {
                     prioAt += quarter;
@@ -477,7 +435,6 @@ __global__ __launch_bounds__(IGD_WG, IGD_WPE) void igd_scan_tiles(DbView db, Sca
                     else if (prioLevel == 1) __builtin_amdgcn_s_setprio(1);
                     else __builtin_amdgcn_s_setprio(0);
                 }
-#endif
             }
         }
     }
@@ -515,7 +472,7 @@ __device__ __forceinline__ void deal_items(int nH, int gwave, int nwaves, int la
 // ------------------------------------------------------------------------------------------
 // heavy_bucket_body: the bucket path's skew valve.  The tile chunk is the unit of work, so a batch whose queries pile
 // up in a few tiles (10^6 unordered queries in ONE tile: 62 ms) would be serialised on the waves that own them.
-// k_split_fine lists the tiles with more than IGD_HEAVY_PAIRS pairs and hides them from igd_scan_tiles (negative
+// k_split_fine_a / _b list the tiles with more than IGD_HEAVY_PAIRS pairs and hide them from igd_scan_tiles (negative
 // pair count); here every (unit of the tile, slice of IGD_HEAVY_PAIRS pairs) is one work item, dealt round-robin to
 // all waves of the hosting launch (the batch's last kernel: k_reduce_slabs / k_exact_walk -- a launch of its own would
 // cost every batch 4 us), compared exactly like any other unit (compute_unit) and added to hits[] and the batch

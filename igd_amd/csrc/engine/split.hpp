@@ -7,14 +7,15 @@
 //   k_split_local   a workgroup takes 4096 queries, counts their pairs per COARSE bucket (tile >> shift,
 //                   <= 1024 buckets) in LDS, and writes them, grouped by bucket, into its own region
 //                   + one table row (offset | count << 16 per bucket);
-//   k_split_fine    one workgroup per bucket collects the bucket's segments from all regions, counts per
+//   k_split_fine_a  one workgroup per bucket collects the bucket's segments from all regions, counts per
 //                   tile in LDS (the bucket spans 2^shift tiles), writes pairN/pairPos of its tiles and
-//                   the pairs, tile by tile, into `pairs`.
+//                   the pairs, tile by tile, into `pairs` (a piled-up bucket: several workgroups, and k_split_fine_b).
 // Output = exactly what count/scan/scatter leave (pairN, pairPos = END of each tile's range, pairs).
 // Round 5 (LABNOTES R5-11): neither kernel gathers from memory any more -- k_split_local keeps one bit per tile ("holds
 // records") and the contig tables in LDS, puts its region together in LDS and writes it out side by side; the fine kernel
 // lays a bucket's segments out flat, fetches every tuple once (eight loads in flight per thread, none behind a branch) and
-// places the pairs from LDS.  Each stage has the older form behind it for what does not fit (IGD_HIP_SPLIT_NO* switches).
+// places the pairs from LDS.  Each stage falls back to the older form for what does not fit LDS; tests reach those forms
+// with small fixtures through IGD_HIP_SPLIT_NOSTAGE / _NOBITS / _NOREGION (read at open).
 #ifndef SP_WG
 #define SP_WG 1024
 #endif
@@ -23,7 +24,7 @@
 #endif
 #define SP_Q (SP_WG * SP_PER) // queries per workgroup of k_split_local: more queries = longer segments per (workgroup, bucket)
 #ifndef SPF_WG
-#define SPF_WG 256           // threads of k_split_fine
+#define SPF_WG 256           // threads of k_split_fine_a / _b
 #endif
 #define SP_CAP (SP_Q * IGD_SHORT_TILES)
 #define SP_LONG (SP_Q / 4)     // pairs of one k_split_local workgroup in one coarse bucket from which the bucket counts as piled up
@@ -226,7 +227,7 @@ __device__ __forceinline__ void split_fine_whole(int b, int nT, int shift, int n
                                                       const SpTuple *__restrict__ reg,
                                                       int32_t *__restrict__ pairN, int32_t *__restrict__ pairPos,
                                                       int2 *__restrict__ pairs, const int32_t *__restrict__ ctl, int gate,
-                                                      int32_t *__restrict__ ctlw, int epoch, int32_t *__restrict__ heavy, int cap = 0)
+                                                      int32_t *__restrict__ ctlw, int epoch, int32_t *__restrict__ heavy, int cap)
 {
     extern __shared__ uint32_t sp_lds[];
     const int F = 1 << shift;
@@ -372,16 +373,6 @@ __device__ __forceinline__ void split_fine_whole(int b, int nT, int shift, int n
         const uint32_t pos = atomicAdd(&start[tu.t - t0], 1u);
         pairs[pos] = make_int2(tu.s, tu.e);
     });
-}
-
-__global__ __launch_bounds__(SPF_WG) void k_split_fine(int nT, int shift, int nCoarse, int nWG, const uint32_t *__restrict__ table,
-                                                      const SpTuple *__restrict__ reg,
-                                                      int32_t *__restrict__ pairN, int32_t *__restrict__ pairPos,
-                                                      int2 *__restrict__ pairs, const int32_t *__restrict__ ctl, int gate,
-                                                      int32_t *__restrict__ ctlw, int epoch, int32_t *__restrict__ heavy, int cap)
-{
-    if (gate != 0 && __builtin_amdgcn_readfirstlane(ctl[CTL_UNSORTED]) != gate) return;
-    split_fine_whole((int)blockIdx.x, nT, shift, nCoarse, nWG, table, reg, pairN, pairPos, pairs, ctl, gate, ctlw, epoch, heavy, cap);
 }
 
 // Several workgroups per coarse bucket for the buckets of a PILED-UP batch (round 4).  One workgroup per bucket walks ALL pairs

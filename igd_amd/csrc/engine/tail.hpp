@@ -229,9 +229,6 @@ __device__ __forceinline__ void coverage_reset(const DbView &db, int epoch, int 
     }
 }
 
-#ifndef IGD_COV_CHUNK
-#define IGD_COV_CHUNK 0       // units a wave takes at a time; 0: every wave's share in as few chunks as a wave holds descriptors for (<= 64 units each)
-#endif
 template <bool USE_V>
 __device__ __forceinline__ void coverage_body(const DbView &db, const ScanArgs &a, u64 *__restrict__ d_hits,
                                               u64 *__restrict__ d_total, int gwave, int nwaves, int ctlv, const TailHist hist)
@@ -247,11 +244,9 @@ __device__ __forceinline__ void coverage_body(const DbView &db, const ScanArgs &
     // coverage count at its first tile), so a wave's share comes in as few chunks as possible: one, of nUnits / nwaves units,
     // for the benchmark's 190 000 units on 4096 waves (16 at a time -- three chunks for most waves, two for the rest -- took as long
     // as the longer chain: the launch's 4 waves per SIMD neither ran out of instructions to issue nor waited for the LDS).
-    int chunk = IGD_COV_CHUNK;
-    if (chunk == 0) {
-        chunk = (db.nUnits + nwaves - 1) / nwaves;
-        chunk = chunk < 16 ? 16 : (chunk > IGD_WAVE ? IGD_WAVE : chunk);
-    }
+    // (units a wave takes at a time: its share, within 16 .. the 64 a wave holds descriptors for)
+    int chunk = (db.nUnits + nwaves - 1) / nwaves;
+    chunk = chunk < 16 ? 16 : (chunk > IGD_WAVE ? IGD_WAVE : chunk);
     for (int u0 = gwave * chunk; u0 < db.nUnits; u0 += nwaves * chunk) {
         const int cnt = db.nUnits - u0 < chunk ? db.nUnits - u0 : chunk;
         // one unit per lane: its tile, and the number of long queries that cover that tile from end to end = (coarse +
@@ -479,13 +474,8 @@ __global__ __launch_bounds__(256) void k_exact_walk(SortK K, ScanArgs a, const i
 }
 
 // slab rows -> int64 hits[] (+ batch total).  grid = (ceil(nFiles/IGD_TAIL_WG), IGD_REDUCE_GROUPS)
-#ifndef IGD_TAIL_OCC
-#define IGD_TAIL_ATTR
-#else
-#define IGD_TAIL_ATTR __attribute__((amdgpu_waves_per_eu(IGD_TAIL_OCC, IGD_TAIL_OCC)))   // A/B: registers cut to what IGD_TAIL_OCC waves per SIMD leave each
-#endif
 template <bool USE_V>
-__global__ __launch_bounds__(IGD_TAIL_WG) IGD_TAIL_ATTR void k_reduce_slabs(SortK K, const u64 *__restrict__ slab, int rows, int nFiles,
+__global__ __launch_bounds__(IGD_TAIL_WG) void k_reduce_slabs(SortK K, const u64 *__restrict__ slab, int rows, int nFiles,
                                                       u64 *__restrict__ hits, u64 *__restrict__ total,
                                                       const int32_t *__restrict__ ctl, int brokenIf,
                                                       ScanArgs wa, const int2 *__restrict__ fixList,

@@ -19,7 +19,7 @@
 //         queries, and of those of the up-to-3 tiles before it that reach it, with the tile's
 //         records (a merge join: both sides stream, nothing is computed per candidate);
 //      b. any other order: every (query, visited tile) pair is grouped by tile id without global
-//         atomics (k_split_local -> k_split_fine: LDS counting in two levels);
+//         atomics (k_split_local -> k_split_fine_a/_b: LDS counting in two levels);
 //         these kernels return at once when (a) holds.
 //      The NEST/FLAT visiting rule and the "first tile" notion live entirely in this step.
 //   2. scan:   igd_scan_sorted (a) / igd_scan_tiles (b) -- one wavefront owns one <=320-record chunk
@@ -95,10 +95,8 @@
 
 typedef unsigned long long u64;
 
-// tuning / experiment knobs (defaults are the shipped configuration)
-#ifndef IGD_BUFFER_LOADS
-#define IGD_BUFFER_LOADS 1    // compact image read with bounds-checked buffer loads (descriptor per unit)
-#endif
+// measurement builds (-D...; also IGD_D_EXP, scan_direct.hpp): section costing, WRONG counts (igd_hip_open refuses them
+// unless IGD_HIP_ALLOW_EXP_BUILD=1).  The forms of the kernels that lost an A/B are gone; LABNOTES.md keeps their figures.
 #ifndef IGD_EXP_NOMATCH
 #define IGD_EXP_NOMATCH 0     // measurement only: load everything, compare nothing (wrong results)
 #endif
@@ -112,15 +110,6 @@ typedef unsigned long long u64;
                        // 0x100000 / 0x200000 the last launch without the exact walks / the coverage sums, 0x800000 k_query_bounds
                        // without the lpos[] stores of short gaps (all WRONG counts).  (The time-stamp builds of rounds 2-5 -- bits 32,
                        // 1024, 0x400000, 0x1000000 -- left the source in round 6; their results are in LABNOTES.md.)
-#endif
-#ifndef IGD_ASM_MATCH
-#define IGD_ASM_MATCH 1 // igd_scan_sorted's pairwise compare loop written out in assembly (0: the compiler's everywhere, 2: written out in the lean build only)
-#endif
-#ifndef IGD_NT_AUX
-#define IGD_NT_AUX 0   // cache policy of igd_scan_sorted's record loads (measured: 2 = nt is 6 % slower -- consecutive batches find part of the image in the Infinity Cache)
-#endif
-#ifndef IGD_OPT_PRIO
-#define IGD_OPT_PRIO 1 // igd_scan_sorted: waves lower their issue priority as they get through their share
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -266,7 +255,10 @@ struct igd_hip_db {
     int ldsDirect;                // dynamic LDS of igd_scan_direct
     int lastDirect;               // the last batch took the DIRECT step (igd_hip_last_scan_kernel)
     bool bigImage;                // the compact image is addressed with per-unit 64-bit bases (>= 2^30 tile records; IGD_HIP_BIG=1 at open: tests)
-    bool qbVec1, timing;          // IGD_HIP_QB_VEC1 (A/B), IGD_TIMING at open: no getenv on the per-batch path
+    bool timing;                  // IGD_TIMING at open: no getenv on the per-batch path
+    // IGD_HIP_SPLIT_NOSTAGE / _NOBITS / _NOREGION at open (tests): the split path's fallbacks for what does not fit LDS, taken
+    // by small fixtures too -- the unstaged fine walk, tileCnt[] gathers (bits or contig tables too large), tuples stored one by one
+    bool splitNoStage, splitNoBits, splitNoRegion;
     uint32_t *d_spTable;          // split path: [nWG][nCoarse] offset | count << 16
     SpTuple *d_spT;               // regions: the pairs of each k_split_local workgroup, grouped by coarse bucket
     uint32_t *d_spSub;            // piled-up buckets: [nCoarse][SPF_S][2^spShift] pairs per (bucket, share, tile), then bucketBase[nCoarse], bucketLong[nCoarse]

@@ -331,7 +331,7 @@ def test_unordered_batches_through_every_form_of_the_grouping_kernels(switch, wo
     short queries (everything staged), one where 40 % of the queries span 2-4 tiles (regions overflow), one with half of its
     queries on chr1 (buckets overflow) -- under
     IGD_HIP_FLAG_BUCKET, compact image and exact arrays, with and without a value filter, must give the oracle's counts in the
-    shipped form and with each stage switched off (the switches are read once per process: child processes)."""
+    shipped form and with each stage switched off (the switches are read when the database is opened: child processes)."""
     import os, subprocess, sys
     from igd_amd import synth
     from helpers import ROOT
