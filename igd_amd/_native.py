@@ -143,6 +143,8 @@ def hip():
                                         C.c_int32, C.c_int, C.c_int, C.c_void_p, i64p]
         L.igd_hip_search_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.igd_hip_support_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
         L.igd_hip_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_search_runs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -219,6 +221,12 @@ def _bind_core(L):
     L.igdc_parse_bed.argtypes = [C.c_char_p, i32p, i32p, C.c_int]
     L.igdc_read_queries.argtypes = [C.POINTER(CoreDb), C.c_char_p, C.c_int, C.POINTER(CoreQueries)]
     L.igdc_queries_free.argtypes = [C.POINTER(CoreQueries)]
+    # support counts on the host (igd_hostpath.c): db, map (igdc_map_open), ichr, qs, qe, nq, v, rule, support, nhit
+    L.igdc_map_open.restype = C.c_void_p
+    L.igdc_map_open.argtypes = [C.c_void_p, C.c_int]
+    L.igdc_map_close.argtypes = [C.c_void_p]
+    L.igdc_support_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                    C.c_void_p, C.POINTER(C.c_int64)]
     return L
 
 

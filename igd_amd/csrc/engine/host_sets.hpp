@@ -11,7 +11,8 @@
 #define IGD_SETS_BIG_MIN_DEFAULT ((int64_t)1 << 17)
 #define IGD_SETS_SLICES 4096                      // slices the small sets of a chunk are cut into, about (16 per CU) ...
 #define IGD_SETS_SLICE_MIN 64                     // ... within these bounds of queries per slice
-#define IGD_SETS_SLICE_MAX 4096
+#define IGD_SETS_SLICE_MAX 4096                    // (igd_sets_support keeps 32-bit LDS counters that a query raises by at most 1 and that are
+                                                  // flushed per slice: they hold because a slice has at most this many queries -- support_dev.hpp)
 
 // Sets with at least this many queries take the batch pipeline.  The TEST-ONLY variable IGD_SETS_BIG_MIN (read per call)
 // moves the boundary so that both routes, and a mix of them in one call, are reached by small fixtures.

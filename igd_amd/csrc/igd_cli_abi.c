@@ -854,6 +854,102 @@ static void search_sets(const char *listName, int32_t v, int64_t *hits)
     free(q); free(paths);
 }
 
+/* ------------------------------- `igd search -q F -u` / `-Q <list> -u` ----------------- */
+/* Support counts: per database file the number of QUERY REGIONS that overlap at least one of its records, where the table
+ * of `-q` counts (query, record) pairs -- the count a region-set enrichment table is made of.  The table keeps the shape
+ * of `-q`'s (third column: the support; last line: the query regions with any hit, of the accepted query lines).  Rule and
+ * filter are `-q`'s dispatch for -v.  Routing as the counting commands: at most igdc_host_limit() queries in all are
+ * counted on the host (igdc_support_host), more by ONE igd_hip_support_sets call on one device.  `paths` holds one query
+ * file (`-q`, no "Query set" lines) or the files of a list (`-Q`). */
+static void print_support_table(const int64_t *sup, int64_t nhit, int64_t nq)
+{
+    printf("index\t number of regions\t number of query regions\t File_name\n");
+    for (int32_t i = 0; i < IGD->nFiles; i++)
+        if (sup[i] > 0) printf("%i\t%i\t%lld\t%s\n", i, IGD->finfo[i].nr, (long long)sup[i], IGD->finfo[i].fileName);
+    printf("Query regions with a hit: %lld of %lld\n", (long long)nhit, (long long)nq);
+}
+
+static char **read_list(const char *listName, int32_t *n_out)
+{
+    char **paths = NULL;
+    int32_t n = 0, cap = 0;
+    *n_out = -1;
+    igdc_lines *r = igdc_lines_open(listName);
+    if (!r) { printf("Cannot open query list %s\n", listName); return NULL; }
+    char *line;
+    int64_t len;
+    while ((line = igdc_lines_next(r, &len)) != NULL) {
+        size_t L = strlen(line);
+        while (L > 0 && (line[L - 1] == '\r' || line[L - 1] == '\n')) line[--L] = '\0';
+        if (L == 0) continue;
+        if (n == cap) { cap = cap ? 2 * cap : 64; paths = (char **)realloc(paths, sizeof(char *) * (size_t)cap); }
+        paths[n++] = strdup(line);
+    }
+    igdc_lines_close(r);
+    *n_out = n;
+    return paths;
+}
+
+static void support_files(char **paths, int32_t n, int32_t v, int setLines)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles;
+    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` (:1023-1030) */
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    int64_t *rows = (int64_t *)calloc((size_t)n * (size_t)nfiles + 1, sizeof(int64_t));
+    int64_t *nhit = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t));
+    int onHost = 0;
+    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
+    if (hm) {
+        double t0 = now_s();
+        onHost = 1;
+        for (int32_t k = 0; k < n && onHost; k++)
+            if (q[k].n > 0)
+                onHost = igdc_support_host(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
+                                           &nhit[k]) == 0;
+        igdc_map_close(hm);
+        if (onHost) phase("support counts on the host (small files)", &t0);
+        else {                                        /* (a read error: the engine reads the file its own way) */
+            memset(rows, 0, sizeof(int64_t) * (size_t)n * (size_t)nfiles);
+            memset(nhit, 0, sizeof(int64_t) * (size_t)n);
+        }
+    }
+    if (!onHost && nq > 0) {
+        int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq);
+        int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq);
+        int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+        off[0] = 0;
+        for (int32_t k = 0; k < n; k++) {
+            if (q[k].n) {
+                memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+                memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+                memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+            }
+            off[k + 1] = off[k] + q[k].n;
+        }
+        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
+        double t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_support_sets(dev, ichr, qs, qe, off, n, ev, rule, rows, nhit);
+            if (rc != IGD_HIP_OK) engine_failed("support", rc);
+            phase("support counts of the query sets (H2D + kernel + D2H)", &t0);
+        }
+        free(ichr); free(qs); free(qe); free(off);
+    }
+    for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
+        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        print_support_table(rows + (size_t)k * (size_t)nfiles, nhit[k], q[k].n);
+    }
+    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    free(q); free(rows); free(nhit);
+}
+
 /* ------------------------------- `igd search` ----------------------------------------- */
 static int usage_search(void)
 {
@@ -867,6 +963,8 @@ static int usage_search(void)
             "    -m                         dataset x dataset hit map, written to -o <name> (default Hitsmap)\n"
             "    -c                         accepted, no effect\n"
             "    -s                         Seqpare similarity of the query file with every dataset\n"
+            "    -Q <list file>             one query file per line: the table of -q for each of them\n"
+            "    -u                         with -q or -Q: count query regions with a hit, once per dataset (support)\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
             "               several GPUs (database replicated, contiguous query slabs, per-dataset counts summed)\n");
     return EX_OK;
@@ -906,7 +1004,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
 
     int32_t v = 0, qs = 1, qe = 2;
-    int mode = -1, full = 0;
+    int mode = -1, full = 0, uniq = 0;
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL;
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -932,6 +1030,8 @@ int igd_search(int argc, char **argv)                                        /* 
             mode = 3;
         } else if (strcmp(a, "-f") == 0) {
             full = 1;
+        } else if (strcmp(a, "-u") == 0) {            /* (not the reference's: support counts, see support_files) */
+            uniq = 1;
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
@@ -949,6 +1049,8 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported -f option\n");
             return EX_OK;
         }
+    } else if (mode == 1 && uniq) {
+        support_files(&qfName, 1, v, 0);
     } else if (mode == 1) {                                                   /* :1023-1040 */
         if (IGD->gType == 0) getOverlaps0(qfName, hits);
         else if (v > 0) getOverlaps_v(qfName, hits, v);
@@ -1002,6 +1104,12 @@ int igd_search(int argc, char **argv)                                        /* 
                 printf("%i\t%i\t%10.6f\t%s\n", i, IGD->finfo[i].nr, sm[i], IGD->finfo[i].fileName);
             free(sm);
         }
+    } else if (listName && uniq) {
+        int32_t n = 0;
+        char **paths = read_list(listName, &n);
+        if (n >= 0) support_files(paths, n, v, 1);
+        for (int32_t k = 0; k < n; k++) free(paths[k]);
+        free(paths);
     } else if (listName) {                        /* only where the reference's own parse leaves nothing to do */
         search_sets(listName, v, hits);
     } else {

@@ -111,6 +111,11 @@ void      igdc_map_close(igdc_map *m);
 /* hits[] is ADDED to; *total = overlaps of the batch.  v = IGD_HIP_NO_VALUE_FILTER: no filter.  0 on success. */
 int igdc_search_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                      int64_t nq, int32_t v, int rule, int64_t *hits, int64_t *total);
+/* Support counts: support[f] += the queries that overlap at least one record of file f (igdc_search_host adds every
+ * overlapping record), *nhit (may be NULL) += the queries that overlap any record.  Same threading, rule and filter as
+ * igdc_search_host; added to the caller's only if every tile could be read.  0 on success. */
+int igdc_support_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                      int64_t nq, int32_t v, int rule, int64_t *support, int64_t *nhit);
 /* `-f` (rule NEST, the reference's order): qoff[0..nq] offsets, *out malloc'd (free()), entries as igd_hip_enumerate's */
 int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                         int64_t nq, int64_t *qoff, igd_hip_hit **out, int64_t *total);

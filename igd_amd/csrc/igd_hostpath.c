@@ -194,6 +194,41 @@ static inline int64_t one_query(const igdc_db *db, const igdc_map *m, tilebuf *t
     return total;
 }
 
+/* one query for the support counts (igdc_support_host): the walk of one_query, but a file counts once per query.  last[f]
+ * holds the stamp of the last query that counted file f (stamp = query number + 1; 0 = none yet).  Returns 1 if the query
+ * overlaps any record. */
+static inline int one_query_support(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int32_t v,
+                                    int use_v, int rule, int64_t *support, int64_t *last, int64_t stamp)
+{
+    if (ichr < 0 || ichr >= db->nCtg) return 0;
+    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
+    const int32_t n1 = qs / nbp;
+    int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;
+    if (n1 < 0 || n1 > mT) return 0;
+    if (n2 > mT) n2 = mT;
+    if (rule == IGD_HIP_RULE_NEST && db->nCnt[ichr][n1] == 0) return 0;
+    const int w = db->gType == 0 ? 3 : 4;
+    const int32_t nf = db->nFiles;
+    int any = 0;
+    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
+        const int32_t cnt = db->nCnt[ichr][j];
+        if (cnt <= 0) continue;
+        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
+        if (!rec) return any;
+        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
+        for (int32_t i = below(rec, w, cnt, qe) - 1; i >= 0; i--) {
+            const int32_t *r = rec + (size_t)i * (size_t)w;
+            if ((int64_t)r[1] < lob) break;
+            if (r[2] > qs && (!use_v || r[3] >= v)) {
+                if (r[0] < 0 || r[0] >= nf) continue;
+                any = 1;
+                if (last[r[0]] != stamp) { last[r[0]] = stamp; support[r[0]]++; }
+            }
+        }
+    }
+    return any;
+}
+
 typedef struct {
     const igdc_db *db; const igdc_map *m;
     const int32_t *ichr, *qs, *qe;
@@ -203,6 +238,7 @@ typedef struct {
     int64_t *qcnt;          /* enumeration: per-query counts (may be NULL) */
     hitvec out; int want_out;
     int io_failed;
+    int64_t *last;          /* support counts: the stamp array of one_query_support (NULL: pair counts) */
 } host_job;
 
 static void *host_run(void *arg)
@@ -212,7 +248,9 @@ static void *host_run(void *arg)
     tilebuf tb;
     memset(&tb, 0, sizeof tb);
     tb.ichr = -1;
-    for (int64_t i = J->lo; i < J->hi; i++) {
+    for (int64_t i = J->lo; J->last && i < J->hi; i++)      /* support counts: hits = support[], total = queries with a hit */
+        tot += one_query_support(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, i + 1);
+    for (int64_t i = J->lo; !J->last && i < J->hi; i++) {
         const int64_t n = one_query(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits,
                                     J->want_out ? &J->out : NULL, (int32_t)i);
         if (J->qcnt) J->qcnt[i] = n;
@@ -279,6 +317,39 @@ int igdc_search_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, 
     free(priv);
     if (bad) return -1;
     if (total) *total = tot;
+    return 0;
+}
+
+int igdc_support_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                      int64_t nq, int32_t v, int rule, int64_t *support, int64_t *nhit)
+{
+    if (!db || !m || !support || nq < 0) return -1;
+    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+    const int T = host_threads(nq);
+    host_job job[64];
+    /* per thread a private support vector and its stamp array; added to the caller's only if every tile could be read */
+    const size_t nf1 = (size_t)(db->nFiles + 1);
+    int64_t *priv = (int64_t *)calloc((size_t)T * 2 * nf1, sizeof(int64_t));
+    if (!priv) return -1;
+    for (int k = 0; k < T; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
+        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
+        job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
+        job[k].hits = priv + (size_t)k * 2 * nf1;
+        job[k].last = job[k].hits + nf1;
+    }
+    run_jobs(job, T);
+    int64_t tot = 0;
+    int bad = 0;
+    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
+    for (int k = 0; k < T; k++) {
+        tot += job[k].total;
+        if (!bad) for (int32_t f = 0; f < db->nFiles; f++) support[f] += job[k].hits[f];
+    }
+    free(priv);
+    if (bad) return -1;
+    if (nhit) *nhit += tot;
     return 0;
 }
 

@@ -160,6 +160,47 @@ class Database:
         cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
         return self.search_sets(cat[0], cat[1], cat[2], set_off, v)
 
+    def support_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, support=None):
+        """Support counts of many query sets in one call (igd_hip_support_sets).  Sets as search_sets().  Returns (support
+        int64[nsets, nfiles], nhit int64[nsets]): support[k, f] = the queries of set k that overlap at least one record of
+        file f (search_sets counts every overlapping record), nhit[k] = the queries of set k that overlap any record.
+        support (int64[nsets, nfiles], C order) is added to when given."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+        nsets = len(set_off) - 1
+        if nsets < 0:
+            raise IgdError("support_sets: set_off needs nsets + 1 entries")
+        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("support_sets: set_off[-1] = %d, but %d / %d / %d queries given"
+                           % (set_off[-1], len(ichr), len(qs), len(qe)))
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        if support is None:
+            support = np.zeros((nsets, self.nfiles), np.int64)
+        elif support.dtype != np.int64 or support.shape != (nsets, self.nfiles) or not support.flags.c_contiguous:
+            raise IgdError("support_sets: support must be a C-ordered int64[%d, %d]" % (nsets, self.nfiles))
+        nhit = np.zeros(max(nsets, 1), np.int64)
+        _chk(self._H.igd_hip_support_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data,
+                                          nsets, vf, rule, support.ctypes.data if support.size else None,
+                                          nhit.ctypes.data), "igd_hip_support_sets")
+        return support, nhit[:nsets]
+
+    def support(self, ichr, qs, qe, v=0, rule=None, value_filter=None):
+        """Support counts of one query set: (int64[nfiles], nhit) -- per file the queries that overlap at least one of its
+        records, and the queries that overlap any record.  Row 0 of support_sets() with one set."""
+        sup, nhit = self.support_sets(ichr, qs, qe, np.array([0, len(_i32(qs))], np.int64), v, rule, value_filter)
+        return sup[0], int(nhit[0])
+
+    def support_files(self, paths, v=0):
+        """One query set per BED file (read as `igd search -q` reads it): (support int64[len(paths), nfiles], nhit)."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.support_sets(cat[0], cat[1], cat[2], set_off, v)
+
     def search_dev(self, d_ichr, d_qs, d_qe, nq, d_hits, d_total=None, v=0, rule=None,
                    value_filter=None, stream=None, flags=0):
         """Resident batch: arguments are device pointers (ints).  Asynchronous.

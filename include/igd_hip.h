@@ -135,6 +135,17 @@ int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, 
                         const int64_t *set_off, int32_t nsets, int32_t v, int rule, int flags,
                         int64_t *hits, int64_t *totals);
 
+/* Support counts of many query sets in one call.  Sets as igd_hip_search_sets.  With hits_q[] = what igd_hip_search_ex
+ * adds for the batch that holds query q alone (same rule and v):
+ *     support[k * nFiles + f] += the queries q of set k with hits_q[f] > 0
+ *     nhit[k]                 += the queries q of set k with hits_q[f] > 0 for some f      (nhit may be NULL)
+ * -- the "regions of the set that overlap at least one region of file f" of a region-set enrichment table, where
+ * igd_hip_search_sets counts (query, record) pairs.  Two identical queries are two queries; support <= min(|set|, hits).
+ * One kernel counts all sets, whatever their sizes (igd_sets_support: a wave owns a whole query and keeps one bit per
+ * file); there is no batch-pipeline route.  Blocking.  A bad set_off is IGD_HIP_ERR_ARG before any launch. */
+int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                         const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *support, int64_t *nhit);
+
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
  * `stream` (a hipStream_t; NULL = the engine's own stream) and returns without waiting.
