@@ -1,0 +1,133 @@
+"""No GPU: the fixtures of tests/test_gpu_sets_scale.py are sound (tests/sets_fixtures.py).
+
+igdc_support_host -- the expectation of the scale tests at v > 0 -- is held against the oracle at file counts that are new for
+it (2 081 and 8 193: its stamp array has nFiles entries), the non-vacuity conditions hold on such a database, and plan()
+gives the hand-computed decomposition of known shapes, two of them the measured shapes of DESIGN section 4.4.  The numpy
+writer, the oracle and igdc_support_host take the 300 000-file database of case f."""
+import random
+import shutil
+
+import numpy as np
+import pytest
+
+import sets_fixtures as F
+from helpers import Oracle, short_tmpdir
+from test_support_host import HostDb, cli_rule, oracle_support, oracle_support_enum
+
+
+@pytest.fixture
+def tmp():
+    d = short_tmpdir("isf")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.mark.parametrize("nfiles", [2081, 8193])
+def test_host_support_and_the_fixture_on_wide_databases(nfiles, tmp, monkeypatch):
+    nbp = 1 << 14
+    path, span, window, edge = F.wide_db(random.Random(nfiles), tmp, "w", nfiles, nbp, max(40, nfiles * 3 // 10))
+    assert edge == F.boundary_files(nfiles) and {0, 31, 32, 63, 64, 2047, 2048, nfiles - 1} <= set(edge)
+    sizes = [0, 1, 65, 700, 1500, 734]
+    (ichr, qs, qe), off = F.make_sets(np.random.default_rng(nfiles), 1, nbp, span, sizes, window)
+    assert off[-1] == 3000
+    orc, H = Oracle(path), HostDb(path)
+    try:
+        assert H.nfiles == orc.nfiles == nfiles
+        for v in (0, 500):
+            rule, ev = cli_rule(orc.gtype, v)
+            W = F.Witness(edge)
+            rows = F.expected_rows(orc, H, ichr, qs, qe, off, v)
+            for k, (hits, total, sup, nhit) in enumerate(rows):
+                a, b = off[k], off[k + 1]
+                want, wnhit, whits = oracle_support(orc, ichr[a:b], qs[a:b], qe[a:b], v)
+                assert np.array_equal(sup, want) and nhit == wnhit and np.array_equal(hits, whits), (v, k)
+                if v == 0:
+                    e_sup, e_nhit = oracle_support_enum(orc, ichr[a:b], qs[a:b], qe[a:b])
+                    assert np.array_equal(e_sup, want) and e_nhit == wnhit
+                for threads in ("1", "3"):
+                    monkeypatch.setenv("IGD_HOST_THREADS", threads)
+                    got, gnhit = H.support(ichr[a:b], qs[a:b], qe[a:b], ev, rule)
+                    assert np.array_equal(got, want) and gnhit == wnhit, (v, k, threads)
+                W.add(b - a, hits, total, sup, nhit)
+            W.check()
+    finally:
+        H.close()
+        orc.close()
+
+
+def test_consts_are_the_values_the_cases_were_sized_for():
+    c = F.consts()
+    assert (c["IGD_SETS_SLICES"], c["IGD_SETS_SLICE_MIN"], c["IGD_SETS_SLICE_MAX"], c["IGD_SETS_GRID"]) == (4096, 64, 4096, 2048)
+    assert c["IGD_SETS_LDS_FILES"] == c["IGD_SUPPORT_LDS_FILES"] == 8192
+    assert c["IGD_SETS_ROW_BYTES"] == c["IGD_SUPPORT_BITS_BYTES"] == 256 << 20
+    assert c["IGD_SETS_BIG_MIN_DEFAULT"] == 1 << 17 and c["IGD_HIP_MAX_BATCH_DEFAULT"] == 1 << 24
+    assert c["IGD_SETS_WG"] // c["IGD_WAVE"] == 4
+
+
+def test_plan_gives_the_hand_computed_decomposition():
+    # DESIGN 4.4, 1 000 sets of 1 000 queries at 1 900 files: ceil(10^6 / 4096) = 245, ceil(1000 / 245) = 5 slices per set
+    p = F.plan([1000] * 1000, 1900)
+    for e in ("search", "support"):
+        assert p[e]["sliceLen"] == 245 and p[e]["lds"]
+        assert p[e]["chunks"] == [dict(first=0, rows=1000, nq=1000000, slices=5000, bigs=0, grid=2048)]
+    # DESIGN 4.4, 10 000 sets of 100: the same sliceLen, one slice per set
+    p = F.plan([100] * 10000, 1900)
+    for e in ("search", "support"):
+        assert p[e]["sliceLen"] == 245
+        assert p[e]["chunks"] == [dict(first=0, rows=10000, nq=1000000, slices=10000, bigs=0, grid=2048)]
+    # the suite's small shapes: sliceLen at its lower bound, as many workgroups as slices (1 + 0 + ceil(400 / 64) + 1)
+    p = F.plan([10, 0, 400, 3], 6)
+    assert p["search"]["sliceLen"] == 64 and p["search"]["chunks"] == [dict(first=0, rows=4, nq=413, slices=9, bigs=0, grid=9)]
+    assert p["support"]["chunks"] == p["search"]["chunks"]
+    # a set on the batch pipeline: search slices the small one only (and sizes its slices by the small queries alone);
+    # support slices every set: ceil(5010 / 4096) = 2 -> 64, ceil(5000 / 64) + 1 = 80
+    p = F.plan([5000, 10], 9, big_min=64)
+    assert p["search"]["chunks"] == [dict(first=0, rows=2, nq=5010, slices=1, bigs=1, grid=1)]
+    assert p["support"]["sliceLen"] == 64 and p["support"]["chunks"] == [dict(first=0, rows=2, nq=5010, slices=80, bigs=0, grid=80)]
+    # the row cap: 2^28 / (20 000 * 8) = 1 677 rows per chunk
+    p = F.plan([1] * 1717, 20000)
+    assert p["rowCap"] == 1677 and not p["search"]["lds"] and not p["support"]["lds"]
+    assert [(c["first"], c["rows"]) for c in p["support"]["chunks"]] == [(0, 1677), (1677, 40)]
+    assert p["support"]["maxGrid"] == 2048                 # 625 words x 4 waves x 4 bytes x 2 048 = 20 MB of stripes
+    # the batch seam: 140 sets of 120 001; 2^24 = 139 * 120 001 + 97 077; ceil(120001 / 4096) = 30, ceil(97077 / 4096) = 24,
+    # the rest of set 139 (22 924 queries) opens the second chunk with ceil(22924 / 4096) = 6 slices
+    p = F.plan([120001] * 140, 9)
+    for e in ("search", "support"):
+        assert p[e]["sliceLen"] == 4096
+        assert p[e]["chunks"] == [dict(first=0, rows=140, nq=1 << 24, slices=139 * 30 + 24, bigs=0, grid=2048),
+                                  dict(first=139, rows=1, nq=22924, slices=6, bigs=0, grid=6)]
+    # a lowered seam as in test_sets_straddle_engine_batches (a chunk that is full when a set begins still holds its empty row)
+    p = F.plan([0, 1, 96, 97, 98], 9, max_batch=97)
+    assert [(c["first"], c["rows"], c["nq"]) for c in p["support"]["chunks"]] == [(0, 4, 97), (3, 2, 97), (4, 1, 97), (4, 1, 1)]
+    # the cut grid: 300 000 files are 9 375 words; 2^28 / (9 375 * 16) = 1 789.57
+    p = F.plan([4096] * 40, 300000)
+    assert p["nW"] == 9375 and p["support"]["maxGrid"] == 1789 and p["search"]["maxGrid"] == 2048
+    assert p["rowCap"] == 111 and p["support"]["chunks"] == [dict(first=0, rows=40, nq=163840, slices=2560, bigs=0, grid=1789)]
+    # 8 192 files are still the LDS forms, 8 193 are not
+    assert F.plan([1], 8192)["search"]["lds"] and F.plan([1], 8192)["support"]["lds"]
+    assert not F.plan([1], 8193)["search"]["lds"] and not F.plan([1], 8193)["support"]["lds"]
+
+
+def test_writer_and_oracle_take_the_300000_file_database(tmp):
+    """Case f's database and sets (sets_fixtures.f_db, f_sets) before any GPU sees them: the numpy writer writes 300 000 files,
+    the oracle and igdc_support_host open them, and the expectation of a 4 096-query set and of the small set (anchored
+    per query against the oracle) is non-vacuous: the first and the last file have support, below their pair counts."""
+    path = F.f_db(tmp)
+    sizes, (ichr, qs, qe), off = F.f_sets()
+    assert sizes[0] == 4096 and 0 < sizes[-1] <= F.ANCHOR_MAX
+    keep = np.r_[off[0]:off[1], off[-2]:off[-1]]                        # the first large set and the small one
+    sub = np.array([0, sizes[0], sizes[0] + sizes[-1]], np.int64)
+    assert len(keep) == sub[-1]
+    orc, H = Oracle(path), HostDb(path)
+    try:
+        assert H.nfiles == orc.nfiles == F.F_FILES
+        for v in (0, 500):
+            W = F.Witness((0, F.F_FILES - 1))
+            for k, (hits, total, sup, nhit) in enumerate(F.expected_rows(orc, H, ichr[keep], qs[keep], qe[keep], sub, v)):
+                W.add(int(sub[k + 1] - sub[k]), hits, total, sup, nhit)
+                assert 100 < np.count_nonzero(sup) < 1000, "the window should meet a few hundred files"
+                assert 0 < sup[0] < hits[0] and 0 < sup[-1] < hits[-1]
+            W.check()
+    finally:
+        H.close()
+        orc.close()
