@@ -145,6 +145,8 @@ def hip():
                                           C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.igd_hip_support_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
+        L.igd_hip_coverage_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
         L.igd_hip_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_search_runs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -227,6 +229,9 @@ def _bind_core(L):
     L.igdc_map_close.argtypes = [C.c_void_p]
     L.igdc_support_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                     C.c_void_p, C.POINTER(C.c_int64)]
+    # covered base pairs on the host: the same arguments, coverage and covered in place of support and nhit
+    L.igdc_coverage_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                     C.c_void_p, C.POINTER(C.c_int64)]
     return L
 
 

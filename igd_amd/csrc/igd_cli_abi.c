@@ -869,6 +869,17 @@ static void print_support_table(const int64_t *sup, int64_t nhit, int64_t nq)
     printf("Query regions with a hit: %lld of %lld\n", (long long)nhit, (long long)nq);
 }
 
+/* `-b`: the same table with the covered base pairs in the third column (igdc_coverage_host / igd_hip_coverage_sets): per
+ * database file the bp of the query regions that lie under its records, an interval union per query region.  Last line:
+ * the bp under the records of any file, of the bp of the accepted query lines with end > start. */
+static void print_coverage_table(const int64_t *cov, int64_t covered, int64_t qbp)
+{
+    printf("index\t number of regions\t covered bp\t File_name\n");
+    for (int32_t i = 0; i < IGD->nFiles; i++)
+        if (cov[i] > 0) printf("%i\t%i\t%lld\t%s\n", i, IGD->finfo[i].nr, (long long)cov[i], IGD->finfo[i].fileName);
+    printf("Query bp with a hit: %lld of %lld\n", (long long)covered, (long long)qbp);
+}
+
 static char **read_list(const char *listName, int32_t *n_out)
 {
     char **paths = NULL;
@@ -890,7 +901,7 @@ static char **read_list(const char *listName, int32_t *n_out)
     return paths;
 }
 
-static void support_files(char **paths, int32_t n, int32_t v, int setLines)
+static void support_files(char **paths, int32_t n, int32_t v, int setLines, int bp)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles;
@@ -911,10 +922,10 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines)
         onHost = 1;
         for (int32_t k = 0; k < n && onHost; k++)
             if (q[k].n > 0)
-                onHost = igdc_support_host(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
-                                           &nhit[k]) == 0;
+                onHost = (bp ? igdc_coverage_host : igdc_support_host)(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
+                                                                       rows + (size_t)k * (size_t)nfiles, &nhit[k]) == 0;
         igdc_map_close(hm);
-        if (onHost) phase("support counts on the host (small files)", &t0);
+        if (onHost) phase(bp ? "covered base pairs on the host (small files)" : "support counts on the host (small files)", &t0);
         else {                                        /* (a read error: the engine reads the file its own way) */
             memset(rows, 0, sizeof(int64_t) * (size_t)n * (size_t)nfiles);
             memset(nhit, 0, sizeof(int64_t) * (size_t)n);
@@ -936,15 +947,21 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines)
         igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
         double t0 = now_s();
         if (dev) {
-            const int rc = igd_hip_support_sets(dev, ichr, qs, qe, off, n, ev, rule, rows, nhit);
-            if (rc != IGD_HIP_OK) engine_failed("support", rc);
-            phase("support counts of the query sets (H2D + kernel + D2H)", &t0);
+            const int rc = (bp ? igd_hip_coverage_sets : igd_hip_support_sets)(dev, ichr, qs, qe, off, n, ev, rule, rows, nhit);
+            if (rc != IGD_HIP_OK) engine_failed(bp ? "coverage" : "support", rc);
+            phase(bp ? "covered base pairs of the query sets (H2D + kernel + D2H)" : "support counts of the query sets (H2D + kernel + D2H)", &t0);
         }
         free(ichr); free(qs); free(qe); free(off);
     }
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
         if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
-        print_support_table(rows + (size_t)k * (size_t)nfiles, nhit[k], q[k].n);
+        if (bp) {
+            int64_t qbp = 0;                          /* (64 bits: a line may span 2^32 - 1 bp) */
+            for (int64_t i = 0; i < q[k].n; i++)
+                if (q[k].qe[i] > q[k].qs[i]) qbp += (int64_t)q[k].qe[i] - (int64_t)q[k].qs[i];
+            print_coverage_table(rows + (size_t)k * (size_t)nfiles, nhit[k], qbp);
+        } else
+            print_support_table(rows + (size_t)k * (size_t)nfiles, nhit[k], q[k].n);
     }
     for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
     free(q); free(rows); free(nhit);
@@ -965,6 +982,7 @@ static int usage_search(void)
             "    -s                         Seqpare similarity of the query file with every dataset\n"
             "    -Q <list file>             one query file per line: the table of -q for each of them\n"
             "    -u                         with -q or -Q: count query regions with a hit, once per dataset (support)\n"
+            "    -b                         with -q or -Q: base pairs of the query regions covered by each dataset\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
             "               several GPUs (database replicated, contiguous query slabs, per-dataset counts summed)\n");
     return EX_OK;
@@ -1004,7 +1022,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
 
     int32_t v = 0, qs = 1, qe = 2;
-    int mode = -1, full = 0, uniq = 0;
+    int mode = -1, full = 0, uniq = 0, bp = 0;
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL;
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -1032,6 +1050,8 @@ int igd_search(int argc, char **argv)                                        /* 
             full = 1;
         } else if (strcmp(a, "-u") == 0) {            /* (not the reference's: support counts, see support_files) */
             uniq = 1;
+        } else if (strcmp(a, "-b") == 0) {            /* (not the reference's: covered base pairs, see support_files) */
+            bp = 1;
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
@@ -1049,8 +1069,11 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported -f option\n");
             return EX_OK;
         }
-    } else if (mode == 1 && uniq) {
-        support_files(&qfName, 1, v, 0);
+    } else if ((mode == 1 || (mode < 0 && listName)) && uniq && bp) {
+        printf("Not supported: -b together with -u\n");
+        return EX_OK;
+    } else if (mode == 1 && (uniq || bp)) {
+        support_files(&qfName, 1, v, 0, bp);
     } else if (mode == 1) {                                                   /* :1023-1040 */
         if (IGD->gType == 0) getOverlaps0(qfName, hits);
         else if (v > 0) getOverlaps_v(qfName, hits, v);
@@ -1104,10 +1127,10 @@ int igd_search(int argc, char **argv)                                        /* 
                 printf("%i\t%i\t%10.6f\t%s\n", i, IGD->finfo[i].nr, sm[i], IGD->finfo[i].fileName);
             free(sm);
         }
-    } else if (listName && uniq) {
+    } else if (listName && (uniq || bp)) {
         int32_t n = 0;
         char **paths = read_list(listName, &n);
-        if (n >= 0) support_files(paths, n, v, 1);
+        if (n >= 0) support_files(paths, n, v, 1, bp);
         for (int32_t k = 0; k < n; k++) free(paths[k]);
         free(paths);
     } else if (listName) {                        /* only where the reference's own parse leaves nothing to do */

@@ -116,6 +116,12 @@ int igdc_search_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, 
  * igdc_search_host; added to the caller's only if every tile could be read.  0 on success. */
 int igdc_support_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                       int64_t nq, int32_t v, int rule, int64_t *support, int64_t *nhit);
+/* Covered base pairs: coverage[f] += over the queries, the bp of [qs, qe) that lie under the union of file f's counted
+ * records (an interval union per query, not a sum over records), *covered (may be NULL) += the same for the union over all
+ * files.  Same records, threading, rule and filter as igdc_support_host; added to the caller's only if every tile could be
+ * read.  0 on success. */
+int igdc_coverage_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                       int64_t nq, int32_t v, int rule, int64_t *coverage, int64_t *covered);
 /* `-f` (rule NEST, the reference's order): qoff[0..nq] offsets, *out malloc'd (free()), entries as igd_hip_enumerate's */
 int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                         int64_t nq, int64_t *qoff, igd_hip_hit **out, int64_t *total);

@@ -299,6 +299,11 @@ struct igd_hip_db {
     // igd_hip_support_sets (host_support.hpp), databases too wide for the LDS form: the waves' bitmap stripes (words)
     unsigned *d_supBits;
     int64_t supBitsCap;
+    // igd_hip_coverage_sets (host_coverage.hpp), databases too wide for the LDS form: the waves' frontier stripes (64-bit
+    // words) and the last tag a launch has handed out
+    unsigned long long *d_covFront;
+    int64_t covFrontCap;
+    unsigned long long covTag;
     hipStream_t stream;
     // profiling
     std::vector<hipEvent_t> ev;   // 4 per launch: pipeline start, scan start, scan stop, pipeline stop
@@ -326,6 +331,7 @@ struct igd_hip_db {
 #include "engine/batch_stats_dev.hpp" // instrumentation: terms of the algorithmic byte model
 #include "engine/sets_dev.hpp"        // igd_sets_count: many small query sets in one launch, one hits[] row per set
 #include "engine/support_dev.hpp"     // igd_sets_support: the same walk, counting each (query, file) pair once
+#include "engine/coverage_dev.hpp"    // igd_sets_coverage: the same walk, one frontier per (query, file): covered base pairs
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -334,6 +340,7 @@ struct igd_hip_db {
 #include "engine/host_misc.hpp"       // igd_hip_hitmap, igd_hip_batch_stats
 #include "engine/host_sets.hpp"       // igd_hip_search_sets: chunks of sets, small ones sliced, large ones through the batch pipeline
 #include "engine/host_support.hpp"    // igd_hip_support_sets: chunks of sets, all of them sliced
+#include "engine/host_coverage.hpp"   // igd_hip_coverage_sets: chunks of sets, all of them sliced
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

@@ -144,6 +144,15 @@ int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
     return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, support, nhit) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                          int32_t v, int rule, int64_t *coverage, int64_t *covered)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int32_t, int,
+                        int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_coverage_sets");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, coverage, covered) : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

@@ -229,6 +229,50 @@ static inline int one_query_support(const igdc_db *db, const igdc_map *m, tilebu
     return any;
 }
 
+/* one query for the covered base pairs (igdc_coverage_host): the tiles of one_query, each walked FORWARD, so the counted
+ * records come in non-decreasing start order (a tile is sorted by start, a later tile skips start < lob, every record of an
+ * earlier tile starts before lob).  front[f] = file f is covered up to here under this query; last[f] = the stamp of the
+ * last query that met file f, as in one_query_support (another stamp: the frontier is the query's start).  A record adds
+ * what it covers beyond the frontier: coverage[f] += | [qs, qe) n union of f's counted records |.  Returns the same for
+ * the union over all files. */
+static inline int64_t one_query_coverage(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                         int32_t v, int use_v, int rule, int64_t *coverage, int64_t *last, int64_t *front, int64_t stamp)
+{
+    if (ichr < 0 || ichr >= db->nCtg) return 0;
+    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
+    const int32_t n1 = qs / nbp;
+    int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;
+    if (n1 < 0 || n1 > mT) return 0;
+    if (n2 > mT) n2 = mT;
+    if (rule == IGD_HIP_RULE_NEST && db->nCnt[ichr][n1] == 0) return 0;
+    const int w = db->gType == 0 ? 3 : 4;
+    const int32_t nf = db->nFiles;
+    int64_t all = qs, covered = 0;                                          /* the frontier over all files (64 bits: no wrap) */
+    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
+        const int32_t cnt = db->nCnt[ichr][j];
+        if (cnt <= 0) continue;
+        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
+        if (!rec) return covered;
+        const int32_t first = j == n1 ? 0 : below(rec, w, cnt, (int32_t)((uint32_t)nbp * (uint32_t)j));
+        const int32_t stop = below(rec, w, cnt, qe);
+        for (int32_t i = first; i < stop; i++) {
+            const int32_t *r = rec + (size_t)i * (size_t)w;
+            if (r[2] > qs && (!use_v || r[3] >= v)) {
+                if (r[0] < 0 || r[0] >= nf) continue;
+                const int64_t lo = r[1] > qs ? r[1] : qs, hi = r[2] < qe ? r[2] : qe;
+                if (last[r[0]] != stamp) { last[r[0]] = stamp; front[r[0]] = qs; }
+                const int64_t from = lo > front[r[0]] ? lo : front[r[0]];
+                if (hi > from) coverage[r[0]] += hi - from;
+                if (hi > front[r[0]]) front[r[0]] = hi;
+                const int64_t afrom = lo > all ? lo : all;
+                if (hi > afrom) covered += hi - afrom;
+                if (hi > all) all = hi;
+            }
+        }
+    }
+    return covered;
+}
+
 typedef struct {
     const igdc_db *db; const igdc_map *m;
     const int32_t *ichr, *qs, *qe;
@@ -239,6 +283,7 @@ typedef struct {
     hitvec out; int want_out;
     int io_failed;
     int64_t *last;          /* support counts: the stamp array of one_query_support (NULL: pair counts) */
+    int64_t *front;         /* covered base pairs: the frontiers of one_query_coverage, beside last[] (NULL: not those) */
 } host_job;
 
 static void *host_run(void *arg)
@@ -248,7 +293,9 @@ static void *host_run(void *arg)
     tilebuf tb;
     memset(&tb, 0, sizeof tb);
     tb.ichr = -1;
-    for (int64_t i = J->lo; J->last && i < J->hi; i++)      /* support counts: hits = support[], total = queries with a hit */
+    for (int64_t i = J->lo; J->front && i < J->hi; i++)     /* covered base pairs: hits = coverage[], total = bp under any file */
+        tot += one_query_coverage(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, J->front, i + 1);
+    for (int64_t i = J->lo; J->last && !J->front && i < J->hi; i++)      /* support counts: hits = support[], total = queries with a hit */
         tot += one_query_support(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, i + 1);
     for (int64_t i = J->lo; !J->last && i < J->hi; i++) {
         const int64_t n = one_query(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits,
@@ -350,6 +397,40 @@ int igdc_support_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
     free(priv);
     if (bad) return -1;
     if (nhit) *nhit += tot;
+    return 0;
+}
+
+int igdc_coverage_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                       int64_t nq, int32_t v, int rule, int64_t *coverage, int64_t *covered)
+{
+    if (!db || !m || !coverage || nq < 0) return -1;
+    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+    const int T = host_threads(nq);
+    host_job job[64];
+    /* per thread a private coverage vector, its stamps and its frontiers; added to the caller's only if every tile could be read */
+    const size_t nf1 = (size_t)(db->nFiles + 1);
+    int64_t *priv = (int64_t *)calloc((size_t)T * 3 * nf1, sizeof(int64_t));
+    if (!priv) return -1;
+    for (int k = 0; k < T; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
+        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
+        job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
+        job[k].hits = priv + (size_t)k * 3 * nf1;
+        job[k].last = job[k].hits + nf1;
+        job[k].front = job[k].last + nf1;
+    }
+    run_jobs(job, T);
+    int64_t tot = 0;
+    int bad = 0;
+    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
+    for (int k = 0; k < T; k++) {
+        tot += job[k].total;
+        if (!bad) for (int32_t f = 0; f < db->nFiles; f++) coverage[f] += job[k].hits[f];
+    }
+    free(priv);
+    if (bad) return -1;
+    if (covered) *covered += tot;
     return 0;
 }
 

@@ -201,6 +201,49 @@ class Database:
         cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
         return self.support_sets(cat[0], cat[1], cat[2], set_off, v)
 
+    def coverage_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, coverage=None):
+        """Covered base pairs of many query sets in one call (igd_hip_coverage_sets).  Sets as search_sets().  Returns
+        (coverage int64[nsets, nfiles], covered int64[nsets]): coverage[k, f] = summed over the queries of set k, the bp of
+        the query that lie under at least one record of file f that the query counts (an interval union per query, not a
+        sum over records), covered[k] = the same under the records of any file.  The sum runs over queries: two identical
+        queries count twice and overlapping queries of one set are not merged -- merge the BED first for the set-level
+        intersection.  coverage (int64[nsets, nfiles], C order) is added to when given."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+        nsets = len(set_off) - 1
+        if nsets < 0:
+            raise IgdError("coverage_sets: set_off needs nsets + 1 entries")
+        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("coverage_sets: set_off[-1] = %d, but %d / %d / %d queries given"
+                           % (set_off[-1], len(ichr), len(qs), len(qe)))
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        if coverage is None:
+            coverage = np.zeros((nsets, self.nfiles), np.int64)
+        elif coverage.dtype != np.int64 or coverage.shape != (nsets, self.nfiles) or not coverage.flags.c_contiguous:
+            raise IgdError("coverage_sets: coverage must be a C-ordered int64[%d, %d]" % (nsets, self.nfiles))
+        covered = np.zeros(max(nsets, 1), np.int64)
+        _chk(self._H.igd_hip_coverage_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data,
+                                           nsets, vf, rule, coverage.ctypes.data if coverage.size else None,
+                                           covered.ctypes.data), "igd_hip_coverage_sets")
+        return coverage, covered[:nsets]
+
+    def coverage(self, ichr, qs, qe, v=0, rule=None, value_filter=None):
+        """Covered base pairs of one query set: (int64[nfiles], covered) -- per file the bp of the queries under its
+        records, and the bp under the records of any file.  Row 0 of coverage_sets() with one set."""
+        cov, covered = self.coverage_sets(ichr, qs, qe, np.array([0, len(_i32(qs))], np.int64), v, rule, value_filter)
+        return cov[0], int(covered[0])
+
+    def coverage_files(self, paths, v=0):
+        """One query set per BED file (read as `igd search -q` reads it): (coverage int64[len(paths), nfiles], covered)."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.coverage_sets(cat[0], cat[1], cat[2], set_off, v)
+
     def search_dev(self, d_ichr, d_qs, d_qe, nq, d_hits, d_total=None, v=0, rule=None,
                    value_filter=None, stream=None, flags=0):
         """Resident batch: arguments are device pointers (ints).  Asynchronous.

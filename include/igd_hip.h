@@ -146,6 +146,18 @@ int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, 
 int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                          const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *support, int64_t *nhit);
 
+/* Covered base pairs of many query sets in one call.  Sets as igd_hip_search_sets.  With R_q(f) = the records of file f
+ * that igd_hip_search_ex counts for the batch that holds query q = (contig, qs, qe) alone (same rule and v):
+ *     coverage[k * nFiles + f] += sum over the queries q of set k of | [qs, qe) n union of [start, end) over R_q(f) |
+ *     covered[k]               += the same with the union taken over the records of ALL files     (covered may be NULL)
+ * in base pairs: an interval union per query, not a sum over records.  The sum runs over queries: two identical queries
+ * count twice and overlapping queries of one set are not merged (merge the BED first for the set-level intersection).
+ * coverage > 0 exactly where igd_hip_support_sets' support > 0.  One kernel counts all sets, whatever their sizes
+ * (igd_sets_coverage: a wave owns a whole query and keeps one frontier per file); there is no batch-pipeline route.
+ * Blocking.  A bad set_off is IGD_HIP_ERR_ARG before any launch. */
+int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                          const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *coverage, int64_t *covered);
+
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
  * `stream` (a hipStream_t; NULL = the engine's own stream) and returns without waiting.
