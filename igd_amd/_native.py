@@ -147,6 +147,14 @@ def hip():
                                            C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
         L.igd_hip_coverage_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
+        L.igd_hip_member_words.argtypes = [C.c_void_p]
+        L.igd_hip_member_words.restype = C.c_int64
+        L.igd_hip_member_grid.argtypes = [C.c_int64]
+        L.igd_hip_member_grid.restype = C.c_int32
+        L.igd_hip_membership.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_search_runs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -232,6 +240,9 @@ def _bind_core(L):
     # covered base pairs on the host: the same arguments, coverage and covered in place of support and nhit
     L.igdc_coverage_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                      C.c_void_p, C.POINTER(C.c_int64)]
+    # per-query membership rows on the host: ..., rule, bits (uint32[nq, nW]), nfiles_hit (int32[nq] or NULL), nhit
+    L.igdc_membership_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L
 
 

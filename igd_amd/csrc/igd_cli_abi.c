@@ -967,6 +967,125 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
     free(q); free(rows); free(nhit);
 }
 
+/* ------------------------------- `igd search -q F -w` / `-Q <list> -w` ----------------- */
+/* Per-query membership: one line per accepted query line, in input order,
+ *     contig \t start \t end \t n \t list
+ * with the database's name of the contig (`.`: it has no such contig), the number n of datasets the region overlaps and
+ * their indices, ascending and comma-separated (`.` when n is 0) -- the rows of the matrix whose column sums `-u` prints;
+ * then `-u`'s last line.  Rule and filter are `-q`'s dispatch for -v.  Routing as `-u`: at most igdc_host_limit() queries in
+ * all go through igdc_membership_host, more through igd_hip_membership on one device.  The queries are taken in chunks of
+ * at most MEMBER_CHUNK_QUERIES queries and MEMBER_CHUNK_BYTES of rows, and the text leaves in pieces of about
+ * MEMBER_TEXT_BYTES: a file of 10^6 lines never holds the whole matrix or the whole text. */
+#define MEMBER_CHUNK_QUERIES ((int64_t)1 << 16)
+#define MEMBER_CHUNK_BYTES ((int64_t)64 << 20)
+#define MEMBER_TEXT_BYTES ((size_t)1 << 20)
+
+typedef struct { char *s; size_t n, cap; } textbuf;
+
+static int text_room(textbuf *t, size_t more)
+{
+    if (t->n + more <= t->cap) return 1;
+    size_t nc = t->cap ? t->cap : (size_t)1 << 16;
+    while (nc < t->n + more) nc *= 2;
+    char *ns = (char *)realloc(t->s, nc);
+    if (!ns) return 0;
+    t->s = ns; t->cap = nc;
+    return 1;
+}
+
+static void text_flush(textbuf *t)
+{
+    if (t->n) fwrite(t->s, 1, t->n, stdout);
+    t->n = 0;
+}
+
+static size_t put_uint(char *p, uint32_t x)
+{
+    char d[12];
+    size_t k = 0;
+    do { d[k++] = (char)('0' + x % 10); x /= 10; } while (x);
+    for (size_t i = 0; i < k; i++) p[i] = d[k - 1 - i];
+    return k;
+}
+
+/* the lines of the queries [a, b) of one file from their rows */
+static int member_lines(textbuf *t, const igdc_queries *q, int64_t a, int64_t b, const uint32_t *bits, const int32_t *nfh, int32_t nW)
+{
+    for (int64_t i = a; i < b; i++) {
+        const uint32_t *row = bits + (size_t)(i - a) * (size_t)nW;
+        const int32_t c = q->ichr[i], n = nfh[i - a];
+        const char *name = (c >= 0 && c < IGD->nCtg) ? IGD->cName[c] : ".";
+        if (!text_room(t, strlen(name) + 64 + (size_t)n * 11)) return 0;
+        t->n += (size_t)sprintf(t->s + t->n, "%s\t%d\t%d\t%d\t", name, (int)q->qs[i], (int)q->qe[i], (int)n);
+        if (n == 0) t->s[t->n++] = '.';
+        int first = 1;
+        for (int32_t w = 0; w < nW; w++)
+            for (uint32_t x = row[w]; x; x &= x - 1) {
+                if (!first) t->s[t->n++] = ',';
+                first = 0;
+                t->n += put_uint(t->s + t->n, (uint32_t)w * 32u + (uint32_t)__builtin_ctz(x));
+            }
+        t->s[t->n++] = '\n';
+        if (t->n >= MEMBER_TEXT_BYTES) text_flush(t);
+    }
+    return 1;
+}
+
+static void membership_files(char **paths, int32_t n, int32_t v, int setLines)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles, nW = (nfiles + 31) / 32;
+    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` */
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    int64_t step = MEMBER_CHUNK_BYTES / ((int64_t)(nW ? nW : 1) * 4);
+    step = step < 1 ? 1 : step > MEMBER_CHUNK_QUERIES ? MEMBER_CHUNK_QUERIES : step;
+    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
+    igd_hip_db *dev = NULL;
+    if (!hm && nq > 0 && !(dev = engine())) {         /* no device: nothing of the table is printed */
+        for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+        free(q);
+        return;
+    }
+    uint32_t *bits = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)step * (size_t)(nW ? nW : 1));
+    int32_t *nfh = (int32_t *)malloc(sizeof(int32_t) * (size_t)step);
+    textbuf t = {NULL, 0, 0};
+    double t0 = now_s();
+    for (int32_t k = 0; k < n && !g_fail_rc; k++) {
+        if (setLines) {
+            if (text_room(&t, strlen(paths[k]) + 64)) t.n += (size_t)sprintf(t.s + t.n, "Query set %d: %s\n", (int)k, paths[k]);
+        }
+        int64_t nhit = 0;
+        for (int64_t a = 0; a < q[k].n && !g_fail_rc; a += step) {
+            const int64_t b = a + step < q[k].n ? a + step : q[k].n;
+            int done = 0;
+            if (hm) {
+                done = igdc_membership_host(g_core, hm, q[k].ichr + a, q[k].qs + a, q[k].qe + a, b - a, ev, rule, bits, nfh, &nhit) == 0;
+                if (!done) { igdc_map_close(hm); hm = NULL; }     /* (a read error: the engine reads the file its own way) */
+            }
+            if (!done) {
+                if (!dev) dev = engine();
+                if (!dev) break;
+                const int rc = igd_hip_membership(dev, q[k].ichr + a, q[k].qs + a, q[k].qe + a, b - a, ev, rule, bits, nfh, &nhit);
+                if (rc != IGD_HIP_OK) { engine_failed("membership", rc); break; }
+            }
+            if (!member_lines(&t, &q[k], a, b, bits, nfh, nW)) { fprintf(stderr, "igd: out of memory\n"); break; }
+        }
+        if (!g_fail_rc && text_room(&t, 96))
+            t.n += (size_t)sprintf(t.s + t.n, "Query regions with a hit: %lld of %lld\n", (long long)nhit, (long long)q[k].n);
+    }
+    text_flush(&t);
+    phase(hm ? "membership rows on the host (small files)" : "membership rows of the query files (H2D + kernel + D2H + text)", &t0);
+    if (hm) igdc_map_close(hm);
+    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    free(q); free(bits); free(nfh); free(t.s);
+}
+
 /* ------------------------------- `igd search` ----------------------------------------- */
 static int usage_search(void)
 {
@@ -983,6 +1102,7 @@ static int usage_search(void)
             "    -Q <list file>             one query file per line: the table of -q for each of them\n"
             "    -u                         with -q or -Q: count query regions with a hit, once per dataset (support)\n"
             "    -b                         with -q or -Q: base pairs of the query regions covered by each dataset\n"
+            "    -w                         with -q or -Q: per query region, the datasets it overlaps (membership)\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
             "               several GPUs (database replicated, contiguous query slabs, per-dataset counts summed)\n");
     return EX_OK;
@@ -1022,7 +1142,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
 
     int32_t v = 0, qs = 1, qe = 2;
-    int mode = -1, full = 0, uniq = 0, bp = 0;
+    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0;
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL;
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -1052,6 +1172,8 @@ int igd_search(int argc, char **argv)                                        /* 
             uniq = 1;
         } else if (strcmp(a, "-b") == 0) {            /* (not the reference's: covered base pairs, see support_files) */
             bp = 1;
+        } else if (strcmp(a, "-w") == 0) {            /* (not the reference's: per-query membership, see membership_files) */
+            memb = 1;
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
@@ -1069,6 +1191,11 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported -f option\n");
             return EX_OK;
         }
+    } else if ((mode == 1 || (mode < 0 && listName)) && memb && (uniq || bp)) {
+        printf("Not supported: -w together with -u or -b\n");
+        return EX_OK;
+    } else if (mode == 1 && memb) {
+        membership_files(&qfName, 1, v, 0);
     } else if ((mode == 1 || (mode < 0 && listName)) && uniq && bp) {
         printf("Not supported: -b together with -u\n");
         return EX_OK;
@@ -1127,6 +1254,12 @@ int igd_search(int argc, char **argv)                                        /* 
                 printf("%i\t%i\t%10.6f\t%s\n", i, IGD->finfo[i].nr, sm[i], IGD->finfo[i].fileName);
             free(sm);
         }
+    } else if (listName && memb) {
+        int32_t n = 0;
+        char **paths = read_list(listName, &n);
+        if (n >= 0) membership_files(paths, n, v, 1);
+        for (int32_t k = 0; k < n; k++) free(paths[k]);
+        free(paths);
     } else if (listName && (uniq || bp)) {
         int32_t n = 0;
         char **paths = read_list(listName, &n);

@@ -122,6 +122,12 @@ int igdc_support_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
  * read.  0 on success. */
 int igdc_coverage_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                        int64_t nq, int32_t v, int rule, int64_t *coverage, int64_t *covered);
+/* Per-query membership: row q of bits (ceil(nFiles / 32) uint32 words; file f = bit f & 31 of word f >> 5) says which
+ * files query q overlaps, nfiles_hit[q] (may be NULL) = their number, *nhit (may be NULL) += the queries with any file.  Rows
+ * and nfiles_hit are OVERWRITTEN, every word of them (the threads write disjoint rows straight into the caller's).  Same
+ * records, threading, rule and filter as igdc_support_host.  0 on success, -1 if a tile could not be read (rows undefined). */
+int igdc_membership_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                         int64_t nq, int32_t v, int rule, uint32_t *bits, int32_t *nfiles_hit, int64_t *nhit);
 /* `-f` (rule NEST, the reference's order): qoff[0..nq] offsets, *out malloc'd (free()), entries as igd_hip_enumerate's */
 int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                         int64_t nq, int64_t *qoff, igd_hip_hit **out, int64_t *total);

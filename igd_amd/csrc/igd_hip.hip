@@ -304,6 +304,11 @@ struct igd_hip_db {
     unsigned long long *d_covFront;
     int64_t covFrontCap;
     unsigned long long covTag;
+    // igd_hip_membership (host_member.hpp): the bit rows, nfiles_hit[] and the hit counter of one chunk of queries
+    unsigned *d_memBits;
+    int32_t *d_memNf;
+    unsigned long long *d_memHit;
+    int64_t memBitsCap, memNfCap;
     hipStream_t stream;
     // profiling
     std::vector<hipEvent_t> ev;   // 4 per launch: pipeline start, scan start, scan stop, pipeline stop
@@ -332,6 +337,7 @@ struct igd_hip_db {
 #include "engine/sets_dev.hpp"        // igd_sets_count: many small query sets in one launch, one hits[] row per set
 #include "engine/support_dev.hpp"     // igd_sets_support: the same walk, counting each (query, file) pair once
 #include "engine/coverage_dev.hpp"    // igd_sets_coverage: the same walk, one frontier per (query, file): covered base pairs
+#include "engine/member_dev.hpp"      // igd_member_rows: the same walk, one bit row per query: which files it overlaps
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -341,6 +347,7 @@ struct igd_hip_db {
 #include "engine/host_sets.hpp"       // igd_hip_search_sets: chunks of sets, small ones sliced, large ones through the batch pipeline
 #include "engine/host_support.hpp"    // igd_hip_support_sets: chunks of sets, all of them sliced
 #include "engine/host_coverage.hpp"   // igd_hip_coverage_sets: chunks of sets, all of them sliced
+#include "engine/host_member.hpp"     // igd_hip_membership / _dev: chunks of queries within a row budget, one launch each
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

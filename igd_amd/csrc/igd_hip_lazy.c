@@ -153,6 +153,39 @@ int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
     return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, coverage, covered) : IGD_HIP_ERR_DEVICE;
 }
 
+int64_t igd_hip_member_words(const igd_hip_db *db)
+{
+    typedef int64_t (*fn_t)(const igd_hip_db *);
+    if (!db) return 0;
+    RESOLVE(fn_t, "igd_hip_member_words");
+    return fn ? fn(db) : 0;
+}
+
+int32_t igd_hip_member_grid(int64_t nq)
+{
+    typedef int32_t (*fn_t)(int64_t);
+    RESOLVE(fn_t, "igd_hip_member_grid");
+    return fn ? fn(nq) : 0;
+}
+
+int igd_hip_membership(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t v, int rule,
+                       uint32_t *bits, int32_t *nfiles_hit, int64_t *nhit)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, int32_t, int, uint32_t *, int32_t *,
+                        int64_t *);
+    RESOLVE(fn_t, "igd_hip_membership");
+    return fn ? fn(db, ichr, qs, qe, nq, v, rule, bits, nfiles_hit, nhit) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq, int32_t v,
+                           int rule, uint32_t *d_bits, int32_t *d_nfiles_hit, int64_t *d_nhit, void *stream)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, int32_t, int, uint32_t *, int32_t *,
+                        int64_t *, void *);
+    RESOLVE(fn_t, "igd_hip_membership_dev");
+    return fn ? fn(db, d_ichr, d_qs, d_qe, nq, v, rule, d_bits, d_nfiles_hit, d_nhit, stream) : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

@@ -229,6 +229,41 @@ static inline int one_query_support(const igdc_db *db, const igdc_map *m, tilebu
     return any;
 }
 
+/* one query for the membership rows (igdc_membership_host): the walk of one_query_support; a counted record sets its file's
+ * bit in the query's row (zeroed here first).  Returns the number of files met. */
+static inline int one_query_member(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int32_t v,
+                                   int use_v, int rule, uint32_t *row, int32_t nW)
+{
+    memset(row, 0, sizeof(uint32_t) * (size_t)nW);
+    if (ichr < 0 || ichr >= db->nCtg) return 0;
+    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
+    const int32_t n1 = qs / nbp;
+    int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;
+    if (n1 < 0 || n1 > mT) return 0;
+    if (n2 > mT) n2 = mT;
+    if (rule == IGD_HIP_RULE_NEST && db->nCnt[ichr][n1] == 0) return 0;
+    const int w = db->gType == 0 ? 3 : 4;
+    const int32_t nf = db->nFiles;
+    int n = 0;
+    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
+        const int32_t cnt = db->nCnt[ichr][j];
+        if (cnt <= 0) continue;
+        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
+        if (!rec) return n;
+        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
+        for (int32_t i = below(rec, w, cnt, qe) - 1; i >= 0; i--) {
+            const int32_t *r = rec + (size_t)i * (size_t)w;
+            if ((int64_t)r[1] < lob) break;
+            if (r[2] > qs && (!use_v || r[3] >= v)) {
+                if (r[0] < 0 || r[0] >= nf) continue;
+                const uint32_t bit = 1u << (r[0] & 31);
+                if (!(row[r[0] >> 5] & bit)) { row[r[0] >> 5] |= bit; n++; }
+            }
+        }
+    }
+    return n;
+}
+
 /* one query for the covered base pairs (igdc_coverage_host): the tiles of one_query, each walked FORWARD, so the counted
  * records come in non-decreasing start order (a tile is sorted by start, a later tile skips start < lob, every record of an
  * earlier tile starts before lob).  front[f] = file f is covered up to here under this query; last[f] = the stamp of the
@@ -284,6 +319,8 @@ typedef struct {
     int io_failed;
     int64_t *last;          /* support counts: the stamp array of one_query_support (NULL: pair counts) */
     int64_t *front;         /* covered base pairs: the frontiers of one_query_coverage, beside last[] (NULL: not those) */
+    uint32_t *bits;         /* membership rows: the caller's rows (NULL: not those), nW words each; nfh: its nfiles_hit[] or NULL */
+    int32_t *nfh, nW;
 } host_job;
 
 static void *host_run(void *arg)
@@ -293,11 +330,17 @@ static void *host_run(void *arg)
     tilebuf tb;
     memset(&tb, 0, sizeof tb);
     tb.ichr = -1;
+    for (int64_t i = J->lo; J->bits && i < J->hi; i++) {    /* membership rows: total = queries with a hit */
+        const int n = one_query_member(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule,
+                                       J->bits + (size_t)i * (size_t)J->nW, J->nW);
+        if (J->nfh) J->nfh[i] = n;
+        tot += n > 0;
+    }
     for (int64_t i = J->lo; J->front && i < J->hi; i++)     /* covered base pairs: hits = coverage[], total = bp under any file */
         tot += one_query_coverage(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, J->front, i + 1);
     for (int64_t i = J->lo; J->last && !J->front && i < J->hi; i++)      /* support counts: hits = support[], total = queries with a hit */
         tot += one_query_support(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, i + 1);
-    for (int64_t i = J->lo; !J->last && i < J->hi; i++) {
+    for (int64_t i = J->lo; !J->last && !J->bits && i < J->hi; i++) {
         const int64_t n = one_query(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits,
                                     J->want_out ? &J->out : NULL, (int32_t)i);
         if (J->qcnt) J->qcnt[i] = n;
@@ -431,6 +474,31 @@ int igdc_coverage_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr
     free(priv);
     if (bad) return -1;
     if (covered) *covered += tot;
+    return 0;
+}
+
+int igdc_membership_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                         int64_t nq, int32_t v, int rule, uint32_t *bits, int32_t *nfiles_hit, int64_t *nhit)
+{
+    if (!db || !m || nq < 0 || (nq > 0 && !bits)) return -1;
+    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+    const int T = host_threads(nq);
+    host_job job[64];
+    uint32_t none = 0;                       /* (a database without files: rows of no words) */
+    /* rows are disjoint per query: every thread writes its queries' rows straight into the caller's */
+    for (int k = 0; k < T; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
+        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
+        job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
+        job[k].bits = bits ? bits : &none; job[k].nfh = nfiles_hit; job[k].nW = (db->nFiles + 31) / 32;
+    }
+    run_jobs(job, T);
+    int64_t tot = 0;
+    int bad = 0;
+    for (int k = 0; k < T; k++) { bad |= job[k].io_failed; tot += job[k].total; }
+    if (bad) return -1;
+    if (nhit) *nhit += tot;
     return 0;
 }
 

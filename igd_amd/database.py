@@ -244,6 +244,69 @@ class Database:
         cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
         return self.coverage_sets(cat[0], cat[1], cat[2], set_off, v)
 
+    @property
+    def member_words(self):
+        """uint32 words of one membership row: ceil(nfiles / 32)"""
+        return int(self._H.igd_hip_member_words(self.dev))
+
+    def membership(self, ichr, qs, qe, v=0, rule=None, value_filter=None, bits=None):
+        """Per-query dataset membership (igd_hip_membership).  Returns (bits uint32[nq, member_words], nfiles_hit int32[nq],
+        nhit): file f is bit f & 31 of bits[q, f >> 5] and is set iff query q overlaps at least one record of file f (bits at
+        positions >= nfiles are 0), nfiles_hit[q] = the files query q overlaps, nhit = the queries that overlap any -- the
+        matrix whose column sums are support().  bits (uint32[nq, member_words], C order), when given, is overwritten:
+        every word of it, so it need not be cleared."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        nq, nW = len(qs), self.member_words
+        if len(ichr) != nq or len(qe) != nq:
+            raise IgdError("membership: %d / %d / %d queries given" % (len(ichr), nq, len(qe)))
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        if bits is None:
+            bits = np.empty((nq, nW), np.uint32)
+        elif bits.dtype != np.uint32 or bits.shape != (nq, nW) or not bits.flags.c_contiguous:
+            raise IgdError("membership: bits must be a C-ordered uint32[%d, %d]" % (nq, nW))
+        nfh = np.empty(nq, np.int32)
+        nhit = C.c_int64(0)
+        _chk(self._H.igd_hip_membership(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, nq, vf, rule,
+                                        bits.ctypes.data if bits.size else None, nfh.ctypes.data if nq else None,
+                                        C.byref(nhit)), "igd_hip_membership")
+        return bits, nfh, nhit.value
+
+    def membership_files(self, paths, v=0):
+        """The rows of several BED files (read as `igd search -q` reads them), concatenated: (bits, nfiles_hit, nhit
+        int64[len(paths)], set_off int64[len(paths) + 1]); file k owns the rows [set_off[k], set_off[k + 1])."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        bits, nfh, _ = self.membership(cat[0], cat[1], cat[2], v)
+        any_hit = np.concatenate([[0], np.cumsum(nfh > 0)]).astype(np.int64)
+        return bits, nfh, any_hit[set_off[1:]] - any_hit[set_off[:-1]], set_off
+
+    def membership_dev(self, d_ichr, d_qs, d_qe, nq, d_bits, d_nfiles_hit=None, d_nhit=None, v=0, rule=None,
+                       value_filter=None, stream=None):
+        """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_bits (uint32[nq * member_words]) and
+        d_nfiles_hit (int32[nq], may be None) are overwritten, d_nhit (int64[1], may be None) is added to.  nq above
+        igd_hip_max_batch() is refused: split the batch, rows are per query."""
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        _chk(self._H.igd_hip_membership_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), vf, rule, d_bits, d_nfiles_hit, d_nhit,
+                                            stream), "igd_hip_membership_dev")
+
+    @staticmethod
+    def unpack_membership(bits, nfiles):
+        """bool[nq, nfiles] from the rows of membership()"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        nq = bits.shape[0]
+        if nfiles == 0 or nq == 0:
+            return np.zeros((nq, nfiles), bool)
+        b = np.unpackbits(bits.astype("<u4").view(np.uint8).reshape(nq, -1), axis=1, bitorder="little")
+        return b[:, :nfiles].astype(bool)
+
     def search_dev(self, d_ichr, d_qs, d_qe, nq, d_hits, d_total=None, v=0, rule=None,
                    value_filter=None, stream=None, flags=0):
         """Resident batch: arguments are device pointers (ints).  Asynchronous.

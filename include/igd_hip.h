@@ -158,6 +158,29 @@ int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
 int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                           const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *coverage, int64_t *covered);
 
+/* Per-query dataset membership: which files each query overlaps.  With hits_q[] as above (the batch that holds query q
+ * alone, same rule and v), row q of `bits` is igd_hip_member_words(db) = ceil(nFiles / 32) uint32 words:
+ *     bit (f & 31) of bits[q * nW + (f >> 5)] = hits_q[f] > 0;      bits at positions >= nFiles are 0
+ *     nfiles_hit[q] = the files f with hits_q[f] > 0 (the popcount of row q)               (nfiles_hit may be NULL)
+ *     nhit         += the queries with any bit set (what igd_hip_support_sets adds to nhit)  (nhit may be NULL)
+ * -- the region x dataset matrix whose column sums are the support counts.  Every word of every row and every
+ * nfiles_hit[q] is DEFINED by the call (overwritten, not OR-ed or added to): the caller need not clear them.  A query on an
+ * unknown contig, out of range or ended by rule NEST's empty first tile has an all-zero row; two identical queries have two
+ * identical rows.  Queries go through the engine in chunks of at most igd_hip_max_batch() queries and a budget of device
+ * bytes for the rows.  Blocking.  A bad argument is IGD_HIP_ERR_ARG before any launch, the caller's arrays untouched. */
+int64_t igd_hip_member_words(const igd_hip_db *db);
+int igd_hip_membership(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                       int32_t v, int rule, uint32_t *bits, int32_t *nfiles_hit, int64_t *nhit);
+/* The same with device pointers on db's GPU, for a caller that keeps the matrix resident: enqueues on `stream` (a
+ * hipStream_t; NULL = the engine's own stream) and returns without waiting.  d_bits (uint32[nq * nW]) and d_nfiles_hit
+ * (int32[nq], may be NULL) are overwritten; d_nhit (int64[1], may be NULL) is ADDED to.  nq above igd_hip_max_batch() is
+ * IGD_HIP_ERR_ARG: the caller splits the batch (rows are per query). */
+int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq,
+                           int32_t v, int rule, uint32_t *d_bits, int32_t *d_nfiles_hit, int64_t *d_nhit, void *stream);
+/* Workgroups (of four waves) the membership kernel is launched with for nq queries: a wave takes a second query only when
+ * nq exceeds four times this number (tests). */
+int32_t igd_hip_member_grid(int64_t nq);
+
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
  * `stream` (a hipStream_t; NULL = the engine's own stream) and returns without waiting.
