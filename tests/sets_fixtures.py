@@ -1,14 +1,18 @@
-"""Fixtures for the sets / support kernels (igd_sets_count, igd_sets_support) beyond one slice per workgroup.  A plain module:
-no pytest hooks.  tests/test_sets_fixtures.py checks it without a GPU; tests/test_gpu_sets_scale.py uses it on one.
+"""Fixtures for the sets / support / coverage kernels (igd_sets_count, igd_sets_support, igd_sets_coverage) beyond one slice
+per workgroup.  A plain module: no pytest hooks.  tests/test_sets_fixtures.py checks it without a GPU;
+tests/test_gpu_sets_scale.py and tests/test_gpu_coverage_scale.py use it on one.
 
     consts()         the constants of the work decomposition, read out of the sources
-    plan()           the host's chunk and slice arithmetic (host_sets.hpp, host_support.hpp), restated: every test asserts
-                     through it that its fixture is in the regime it claims
+    plan()           the host's chunk and slice arithmetic (host_sets.hpp, host_support.hpp, host_coverage.hpp), restated:
+                     every test asserts through it that its fixture is in the regime it claims
     wide_db()        a database of many files whose boundary files (bit 0 and bit 31 of the first, 64th, 65th and last
                      bitmap word) lie inside a window that a known share of the queries covers
     scale_queries()  the query kinds of test_gpu_sets._queries, drawn with numpy (cases of 10^6 and more queries)
     expected_rows()  per set (hits, total, support, nhit), none of it from the kernels under test
-    Witness          the non-vacuity conditions, asserted on the expectation alone"""
+    Witness          the non-vacuity conditions, asserted on the expectation alone
+    expected_cov_rows()  per set (coverage, covered, pair sums), none of it from the kernel under test
+    CovWitness       the same for covered base pairs
+    bigbp_db(), bigbp_sets()  more than 2^32 bp under one file in one slice"""
 import os
 import random
 import re
@@ -16,11 +20,13 @@ import re
 import numpy as np
 
 from helpers import ROOT, write_igd_numpy
+from test_coverage_host import coverage_brute, coverage_from_enumeration, read_rows
 from test_support_host import cli_rule, oracle_support, oracle_support_enum
 
 ENGINE = os.path.join(ROOT, "igd_amd", "csrc", "engine")
 NBP = 1 << 14
 ANCHOR_MAX = 1500          # sets of at most this many queries: igdc_support_host is held against the oracle in place
+COV_ANCHORS = 40           # igdc_coverage_host is held in place against the brute force on this many non-empty sets at least
 
 
 # ---- the constants and the host's arithmetic --------------------------------------------------------------------------------
@@ -39,12 +45,16 @@ def consts():
     src = {n: open(p).read() for n, p in (
         ("sets_dev", os.path.join(ENGINE, "sets_dev.hpp")), ("support_dev", os.path.join(ENGINE, "support_dev.hpp")),
         ("host_sets", os.path.join(ENGINE, "host_sets.hpp")), ("host_support", os.path.join(ENGINE, "host_support.hpp")),
+        ("coverage_dev", os.path.join(ENGINE, "coverage_dev.hpp")), ("host_coverage", os.path.join(ENGINE, "host_coverage.hpp")),
+        ("member_dev", os.path.join(ENGINE, "member_dev.hpp")),
         ("hip", os.path.join(ROOT, "igd_amd", "csrc", "igd_hip.hip")), ("api", os.path.join(ROOT, "include", "igd_hip.h")))}
     c = {}
     for name, where in (("IGD_SETS_SLICES", "host_sets"), ("IGD_SETS_SLICE_MIN", "host_sets"), ("IGD_SETS_SLICE_MAX", "host_sets"),
                         ("IGD_SETS_ROW_BYTES", "host_sets"), ("IGD_SETS_BIG_MIN_DEFAULT", "host_sets"),
                         ("IGD_SETS_GRID", "sets_dev"), ("IGD_SETS_LDS_FILES", "sets_dev"), ("IGD_SETS_WG", "sets_dev"),
                         ("IGD_SUPPORT_LDS_FILES", "support_dev"), ("IGD_SUPPORT_BITS_BYTES", "host_support"),
+                        ("IGD_COVERAGE_LDS_FILES", "coverage_dev"), ("IGD_COVERAGE_FRONT_BYTES", "host_coverage"),
+                        ("IGD_MEMBER_LDS_FILES", "member_dev"),
                         ("IGD_WAVE", "hip"), ("IGD_HIP_MAX_BATCH_DEFAULT", "api")):
         c[name] = _define(src[where], name)
     return c
@@ -55,8 +65,9 @@ def _clamp(x, lo, hi):
 
 
 def plan(set_sizes, nfiles, big_min=None, max_batch=None):
-    """What igd_hip_search_sets ("search") and igd_hip_support_sets ("support") make of these sets: sliceLen, and per chunk
-    its first set, rows, queries, slices, sets on the batch pipeline (search only) and the grid of the slice kernel."""
+    """What igd_hip_search_sets ("search"), igd_hip_support_sets ("support") and igd_hip_coverage_sets ("coverage") make of
+    these sets: sliceLen, and per chunk its first set, rows, queries, slices, sets on the batch pipeline (search only) and the
+    grid of the slice kernel."""
     c = consts()
     big_min = c["IGD_SETS_BIG_MIN_DEFAULT"] if big_min is None else big_min
     step = c["IGD_HIP_MAX_BATCH_DEFAULT"] if max_batch is None else max_batch
@@ -94,13 +105,16 @@ def plan(set_sizes, nfiles, big_min=None, max_batch=None):
     max_grid = c["IGD_SETS_GRID"]
     if nfiles > c["IGD_SUPPORT_LDS_FILES"]:
         max_grid = _clamp(c["IGD_SUPPORT_BITS_BYTES"] // (nw * 4 * waves), 1, c["IGD_SETS_GRID"])
+    cov_lds = nfiles <= c["IGD_COVERAGE_LDS_FILES"]          # (one stripe of nfiles 64-bit words per wave otherwise)
+    cov_grid = c["IGD_SETS_GRID"] if cov_lds else _clamp(c["IGD_COVERAGE_FRONT_BYTES"] // (nfiles * 8 * waves), 1, c["IGD_SETS_GRID"])
     s_len = slice_len(sum(n for n in sizes if n < big_min))
     u_len = slice_len(off[-1])
     return dict(rowCap=row_cap, nW=nw,
                 search=dict(sliceLen=s_len, lds=nfiles <= c["IGD_SETS_LDS_FILES"], maxGrid=c["IGD_SETS_GRID"],
                             chunks=chunks(s_len, c["IGD_SETS_GRID"], True)),
                 support=dict(sliceLen=u_len, lds=nfiles <= c["IGD_SUPPORT_LDS_FILES"], maxGrid=max_grid,
-                             chunks=chunks(u_len, max_grid, False)))
+                             chunks=chunks(u_len, max_grid, False)),
+                coverage=dict(sliceLen=u_len, lds=cov_lds, maxGrid=cov_grid, chunks=chunks(u_len, cov_grid, False)))
 
 
 # ---- databases and queries --------------------------------------------------------------------------------------------------
@@ -246,3 +260,142 @@ class Witness:
         assert self.anchored, "no set of at most %d queries: igdc_support_host was not held against the oracle" % ANCHOR_MAX
         few = {f: n for f, n in self.sets_with.items() if n < 2}
         assert not few, "boundary files with support in fewer than two sets: %r" % few
+
+
+# ---- covered base pairs: the expectation --------------------------------------------------------------------------------------
+_rows_cache = {}
+
+
+def cached_rows(path):
+    """(read_rows(path), the same per contig sorted by start with its longest record): read once per database file"""
+    st = os.stat(path)
+    key = (path, st.st_mtime_ns, st.st_size)
+    if key not in _rows_cache:
+        rows = {c: np.asfortranarray(r) for c, r in read_rows(path).items()}     # (column slices are contiguous)
+        srt = {}
+        for c, r in rows.items():
+            r = r[np.argsort(r[:, 1], kind="stable")]
+            srt[c] = (r, int((r[:, 2] - r[:, 1]).max(initial=0)))
+        _rows_cache[key] = (rows, srt)
+    return _rows_cache[key]
+
+
+def pair_sums(path, orc, ichr, qs, qe, v):
+    """int64[nfiles]: the clipped lengths of all counted (query, record) pairs under rule FLAT with `value >= v`, summed per
+    file -- what a kernel that added every record's overlap would return.  The candidates of a query are the records that
+    start in [qs - longest record, qe), found by bisection; as in coverage_brute the result is only trusted where the
+    same pairs reproduce the oracle's hits."""
+    _, srt = cached_rows(path)
+    ichr = np.asarray(ichr)
+    qs, qe = np.asarray(qs, np.int64), np.asarray(qe, np.int64)
+    pairs = np.zeros(orc.nfiles, np.int64)
+    hits = np.zeros(orc.nfiles, np.int64)
+    use = (ichr >= 0) & (ichr < orc.nctg) & (qs > -orc.nbp) & (qe > qs)
+    for c in np.unique(ichr[use]):
+        r, longest = srt[int(c)]
+        s, e = qs[use & (ichr == c)], qe[use & (ichr == c)]
+        a = np.searchsorted(r[:, 1], s - longest, "left")
+        n = np.maximum(np.searchsorted(r[:, 1], e, "left") - a, 0)
+        qi = np.repeat(np.arange(len(n)), n)
+        ri = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n) + np.repeat(a, n)
+        rr = r[ri]
+        ok = (rr[:, 2] > s[qi]) & (rr[:, 3] >= v) & (rr[:, 0] >= 0) & (rr[:, 0] < orc.nfiles)
+        rr, qi = rr[ok], qi[ok]
+        np.add.at(pairs, rr[:, 0], np.minimum(rr[:, 2], e[qi]) - np.maximum(rr[:, 1], s[qi]))
+        hits += np.bincount(rr[:, 0], minlength=orc.nfiles)
+    want, _ = orc.search(ichr[use], qs[use], qe[use], v)
+    assert np.array_equal(hits, want), "INVALID TEST: the pair sums do not reproduce the oracle's hits at v = %d" % v
+    return pairs
+
+
+def expected_cov_rows(path, orc, hostcov, ichr, qs, qe, off, v, named=(), tally=None):
+    """Yields per set (coverage int64[nfiles], covered, pair sums int64[nfiles]), one set at a time: the numpy union of
+    test_coverage_host allocates queries x files words, so a whole call's queries never go in at once.
+    v = 0 (or gType 0): the oracle's enumeration, clipped and united in numpy (coverage_from_enumeration).
+    v > 0: igdc_coverage_host (`hostcov`, a test_coverage_host.HostCov) with the command line's rule -- product host code,
+    not the kernel under test -- held IN PLACE against coverage_brute on the first COV_ANCHORS non-empty sets, on the first
+    set of every distinct size and on every set in `named`; the pair sums come from pair_sums() and, on the anchored sets,
+    must equal the brute force's.  tally (a dict) counts the non-empty and the anchored sets for CovWitness.check()."""
+    rule, ev = cli_rule(orc.gtype, v)
+    flat = orc.gtype != 0 and v > 0
+    rows = cached_rows(path)[0] if flat else None
+    sizes_seen, anchored, nonempty = set(), 0, 0
+    for k in range(len(off) - 1):
+        a, b = int(off[k]), int(off[k + 1])
+        c, s, e = ichr[a:b], qs[a:b], qe[a:b]
+        if not flat:
+            cov, covered, pairs = coverage_from_enumeration(orc, c, s, e)
+        else:
+            cov, covered = hostcov.coverage(c, s, e, ev, rule)
+            pairs = pair_sums(path, orc, c, s, e, v)
+            nonempty += b > a
+            if b > a and (anchored < COV_ANCHORS or (b - a) not in sizes_seen or k in named):
+                w_cov, w_covered, w_pairs = coverage_brute(path, orc, c, s, e, v, rows=rows)
+                assert np.array_equal(cov, w_cov) and covered == w_covered and np.array_equal(pairs, w_pairs), (v, k, b - a)
+                anchored += 1
+            sizes_seen.add(b - a)
+        yield cov, int(covered), pairs
+    if tally is not None and flat:
+        tally["nonempty"] = tally.get("nonempty", 0) + nonempty
+        tally["anchored"] = tally.get("anchored", 0) + anchored
+
+
+class CovWitness:
+    """Non-vacuity of a coverage fixture, from the expectation alone.  Everywhere: coverage <= the pair sum and <= the set's
+    bp, max coverage <= covered <= sum of coverage.  Somewhere: coverage < pair sum (a kernel that summed pairs fails),
+    covered > the largest file's coverage (one that took the best file fails), covered < the sum over the files,
+    0 < covered < the set's bp; every boundary file has coverage in at least two sets.  With a tally of
+    expected_cov_rows (v > 0): at least COV_ANCHORS sets -- or every non-empty set of a fixture that has fewer -- were
+    held against the brute force; this is a condition of the test's validity, not a figure."""
+
+    def __init__(self, boundary=()):
+        self.below = self.above = self.under = self.partial = False
+        self.sets_with = {int(f): 0 for f in boundary}
+
+    def add(self, cov, covered, pairs, bp):
+        assert (cov >= 0).all() and (cov <= pairs).all() and (cov <= bp).all()
+        assert cov.max(initial=0) <= covered <= min(int(cov.sum()), bp)
+        self.below |= bool((cov < pairs).any())
+        self.above |= covered > cov.max(initial=0)
+        self.under |= covered < cov.sum()
+        self.partial |= 0 < covered < bp
+        for f in self.sets_with:
+            self.sets_with[f] += int(cov[f] > 0)
+
+    def check(self, tally=None):
+        assert self.below, "fixture is vacuous: coverage equals the pair sum in every set"
+        assert self.above, "fixture is vacuous: covered equals the largest file's coverage in every set"
+        assert self.under, "fixture is vacuous: covered equals the sum over the files in every set"
+        assert self.partial, "fixture is vacuous: no set has 0 < covered < its bp"
+        few = {f: n for f, n in self.sets_with.items() if n < 2}
+        assert not few, "boundary files with coverage in fewer than two sets: %r" % few
+        if tally is not None:
+            need = min(COV_ANCHORS, tally["nonempty"])
+            assert need > 0 and tally["anchored"] >= need, \
+                "INVALID TEST: igdc_coverage_host was held against the brute force on %d sets, not %d" % (tally["anchored"], need)
+
+
+# ---- case g: more than 2^32 bp under one file in one slice ------------------------------------------------------------------
+BIGBP_Q = (0, 69000000)
+BIGBP_HAND = 64 * (69000000 - 1000)            # coverage[0][0] = covered[0] = 4 415 936 000 > 2^32
+
+
+def bigbp_db(d):
+    """One contig, nbp = 2^14, three files.  File 0: one record over [1000, 70 000 000).  File 1: a short record inside it
+    and one that starts behind the long query.  File 2: one record behind everything asked."""
+    files = [[("chr1", 1000, 70000000, 1000)],
+             [("chr1", 10000000, 10000500, 1000), ("chr1", 69500000, 71000000, 1000)],
+             [("chr1", 72000000, 72000100, 1000)]]
+    path = os.path.join(d, "bigbp.igd")
+    write_igd_numpy(path, files, nbp=NBP, gtype=1)
+    return path
+
+
+def bigbp_sets():
+    """64 copies of [0, 69 000 000) -- one slice of sliceLen = 64, so one LDS counter gathers 64 x 68 999 000 bp --, then
+    one copy, then 64 copies of a 100 bp query: ((ichr, qs, qe), off)"""
+    short = (20000000, 20000100)
+    qs = np.array([BIGBP_Q[0]] * 65 + [short[0]] * 64, np.int32)
+    qe = np.array([BIGBP_Q[1]] * 65 + [short[1]] * 64, np.int32)
+    assert BIGBP_HAND == 4415936000 > 1 << 32
+    return (np.zeros(129, np.int32), qs, qe), np.array([0, 64, 65, 129], np.int64)

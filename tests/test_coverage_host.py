@@ -100,9 +100,9 @@ def read_rows(path):
     return rows
 
 
-def coverage_brute(path, orc, ichr, qs, qe, v):
-    """source 2: rule FLAT with the filter `value >= v` on gType 1"""
-    rows = read_rows(path)
+def coverage_brute(path, orc, ichr, qs, qe, v, rows=None):
+    """source 2: rule FLAT with the filter `value >= v` on gType 1  (rows: read_rows(path), for callers that keep it)"""
+    rows = read_rows(path) if rows is None else rows
     qs, qe = np.asarray(qs, np.int64), np.asarray(qe, np.int64)
     use = [i for i in range(len(qs)) if 0 <= ichr[i] < orc.nctg and qs[i] > -orc.nbp and qe[i] > qs[i]]
     qno, idx, lo, hi = [], [], [], []

@@ -18,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 
+import sets_fixtures as F
 from helpers import GOLDEN, ROOT, Oracle, short_tmpdir, write_bed, write_igd_numpy
 from test_gpu_sets import DBS, SIZES, _db, _sets
 from test_membership_host import MemberHost, assert_not_vacuous, check_rows, oracle_member, oracle_member_enum, pack_rows
@@ -150,6 +151,46 @@ def test_word_boundaries(nfiles, workdir):
                 assert not (bits[:, -1] >> np.uint32(nfiles % 32)).any()
         member, _ = oracle_member(orc, ichr, qs, qe, 0)
         assert member[0, last] and member[0].sum() == 1 and member[1].all() and member[2].all() and not member[3].any()
+    finally:
+        db.close()
+        orc.close()
+
+
+@pytest.mark.parametrize("nfiles", [2081, 16383, 16384, 16385])
+def test_file_count_edges(nfiles, workdir):
+    """igd_member_rows at the edges of its LDS form: IGD_MEMBER_LDS_FILES = 16 384 files are 512 words, eight full steps of
+    the stream-and-clear loop, with 16 383 below it and 16 385, the first wide form, above; 2 081 files are 66 words, no
+    multiple of 64, with nfiles % 32 = 1.  The boundary files of sets_fixtures.wide_db (bit 0 and bit 31 of the first, 64th,
+    65th and last word) lie under the window that an eighth of the queries covers."""
+    from igd_amd import Database
+    c = F.consts()
+    assert c["IGD_MEMBER_LDS_FILES"] == 16384 and c["IGD_WAVE"] == 64
+    nW = (nfiles + 31) // 32
+    assert {2081: (66, 1), 16383: (512, 31), 16384: (512, 0), 16385: (513, 1)}[nfiles] == (nW, nfiles % 32)
+    path, span, window, edge = F.wide_db(random.Random(8000 + nfiles), workdir, "e%d" % nfiles, nfiles, F.NBP,
+                                         max(40, nfiles * 3 // 10))
+    (ichr, qs, qe), off = F.make_sets(np.random.default_rng(nfiles), 1, F.NBP, span, [0, 1, 65, 234], window)
+    assert len(qs) == 300 and edge == F.boundary_files(nfiles) and edge[-1] == nfiles - 1
+    orc, db = Oracle(path), Database(path)
+    try:
+        assert db.member_words == nW
+        for v in (0, 500):
+            member, pairs = oracle_member(orc, ichr, qs, qe, v)
+            if v == 0:
+                assert_not_vacuous(member, pairs)
+            assert member[:, edge].any(axis=0).all(), "a boundary file is in no row of the expectation"
+            bits, nfh, nhit = db.membership(ichr, qs, qe, v, bits=ones(db, len(qs)))
+            check_rows(bits, nfh, nhit, member, (nfiles, v))
+            if nfiles % 32:
+                assert not (bits[:, -1] >> np.uint32(nfiles % 32)).any()         # nfiles - 1 is the highest valid bit
+            got = db.unpack_membership(bits, nfiles)
+            assert got[:, edge].any(axis=0).all()
+            sup, snhit = db.support_sets(ichr, qs, qe, off, v)
+            for k in range(len(off) - 1):
+                a, b = off[k], off[k + 1]
+                assert np.array_equal(got[a:b].sum(axis=0), sup[k]) and int((nfh[a:b] > 0).sum()) == snhit[k], (nfiles, v, k)
+            again, nfh2, nhit2 = db.membership(ichr, qs, qe, v, bits=ones(db, len(qs)))
+            assert np.array_equal(again, bits) and np.array_equal(nfh2, nfh) and nhit2 == nhit
     finally:
         db.close()
         orc.close()

@@ -3,7 +3,12 @@
 igdc_support_host -- the expectation of the scale tests at v > 0 -- is held against the oracle at file counts that are new for
 it (2 081 and 8 193: its stamp array has nFiles entries), the non-vacuity conditions hold on such a database, and plan()
 gives the hand-computed decomposition of known shapes, two of them the measured shapes of DESIGN section 4.4.  The numpy
-writer, the oracle and igdc_support_host take the 300 000-file database of case f."""
+writer, the oracle and igdc_support_host take the 300 000-file database of case f.
+
+The same for tests/test_gpu_coverage_scale.py: igdc_coverage_host -- its expectation at v > 0 -- is held against both sources of
+tests/test_coverage_host.py at 2 041 and 8 193 files (its front[] and last[] arrays have nFiles entries), CovWitness passes
+there, plan()["coverage"] gives the hand-computed shapes, and the oracle and igdc_coverage_host take the fixture of more than
+2^32 bp in one slice, whose hand values hold."""
 import random
 import shutil
 
@@ -12,6 +17,7 @@ import pytest
 
 import sets_fixtures as F
 from helpers import Oracle, short_tmpdir
+from test_coverage_host import HostCov, coverage_brute, coverage_from_enumeration, query_bp
 from test_support_host import HostDb, cli_rule, oracle_support, oracle_support_enum
 
 
@@ -62,6 +68,7 @@ def test_consts_are_the_values_the_cases_were_sized_for():
     assert c["IGD_SETS_ROW_BYTES"] == c["IGD_SUPPORT_BITS_BYTES"] == 256 << 20
     assert c["IGD_SETS_BIG_MIN_DEFAULT"] == 1 << 17 and c["IGD_HIP_MAX_BATCH_DEFAULT"] == 1 << 24
     assert c["IGD_SETS_WG"] // c["IGD_WAVE"] == 4
+    assert c["IGD_COVERAGE_LDS_FILES"] == 2040 and c["IGD_COVERAGE_FRONT_BYTES"] == 256 << 20 and c["IGD_MEMBER_LDS_FILES"] == 16384
 
 
 def test_plan_gives_the_hand_computed_decomposition():
@@ -128,6 +135,90 @@ def test_writer_and_oracle_take_the_300000_file_database(tmp):
                 assert 100 < np.count_nonzero(sup) < 1000, "the window should meet a few hundred files"
                 assert 0 < sup[0] < hits[0] and 0 < sup[-1] < hits[-1]
             W.check()
+    finally:
+        H.close()
+        orc.close()
+
+
+# ---- covered base pairs -----------------------------------------------------------------------------------------------------
+def test_plan_gives_the_hand_computed_decomposition_of_coverage():
+    # DESIGN 4.6's measured shape, 1 000 sets of 1 000 queries at 1 900 files: as support, in the LDS form
+    p = F.plan([1000] * 1000, 1900)["coverage"]
+    assert p["sliceLen"] == 245 and p["lds"] and p["maxGrid"] == 2048
+    assert p["chunks"] == [dict(first=0, rows=1000, nq=1000000, slices=5000, bigs=0, grid=2048)]
+    # 2 040 files are the LDS form, 2 041 are not; the cut grid: 2^28 / (2 041 * 32) = 4 110 -> 2 048,
+    # 2^28 / (20 000 * 32) = 419.4, 2^28 / (10^6 * 32) = 8.4
+    assert F.plan([1], 2040)["coverage"]["lds"] and not F.plan([1], 2041)["coverage"]["lds"]
+    assert F.plan([1], 2040)["coverage"]["maxGrid"] == F.plan([1], 2041)["coverage"]["maxGrid"] == 2048
+    assert F.plan([1], 20000)["coverage"]["maxGrid"] == 419 and F.plan([1], 1000000)["coverage"]["maxGrid"] == 8
+    # the row cap: 1 677 rows per chunk at 20 000 files
+    p = F.plan([1] * 1717, 20000)
+    assert [(c["first"], c["rows"]) for c in p["coverage"]["chunks"]] == [(0, 1677), (1677, 40)]
+    # case a of test_gpu_coverage_scale: (1 + 1 + 1 + 2 + 2 + 3) * 300 = 3 000 slices of 117 900 queries, one chunk
+    sizes = [0, 1, 63, 64, 65, 70, 130] * 300
+    for nfiles in (9, 1900, 2040):
+        p = F.plan(sizes, nfiles)["coverage"]
+        assert p["sliceLen"] == 64 and p["lds"]
+        assert p["chunks"] == [dict(first=0, rows=2100, nq=117900, slices=3000, bigs=0, grid=2048)]
+    # case w: 90 repeats are 900 slices against the 419 workgroups of 20 000 files
+    p = F.plan([0, 1, 63, 64, 65, 70, 130] * 90, 20000)["coverage"]
+    assert p["sliceLen"] == 64 and not p["lds"]
+    assert p["chunks"] == [dict(first=0, rows=630, nq=35370, slices=900, bigs=0, grid=419)]
+
+
+@pytest.mark.parametrize("nfiles", [2041, 8193])
+def test_host_coverage_and_the_fixture_on_wide_databases(nfiles, tmp, monkeypatch):
+    nbp = 1 << 14
+    path, span, window, edge = F.wide_db(random.Random(nfiles), tmp, "w", nfiles, nbp, max(40, nfiles * 3 // 10))
+    sizes = [0, 1, 65, 700, 1500, 734]
+    (ichr, qs, qe), off = F.make_sets(np.random.default_rng(nfiles), 1, nbp, span, sizes, window)
+    orc, H = Oracle(path), HostCov(path)
+    try:
+        assert H.nfiles == orc.nfiles == nfiles
+        for v in (0, 500):
+            rule, ev = cli_rule(orc.gtype, v)
+            W, tally = F.CovWitness(edge), {}
+            for k, (cov, covered, pairs) in enumerate(F.expected_cov_rows(path, orc, H, ichr, qs, qe, off, v, tally=tally)):
+                a, b = off[k], off[k + 1]
+                c, s, e = ichr[a:b], qs[a:b], qe[a:b]
+                # the two sources of test_coverage_host, each where it applies: the enumeration at v = 0 (rule NEST), the
+                # brute force at v > 0 (rule FLAT) -- here for every set, not only the ones expected_cov_rows anchors
+                want =coverage_brute(path, orc, c, s, e, v) if v else coverage_from_enumeration(orc, c, s, e)
+                assert np.array_equal(cov, want[0]) and covered == want[1] and np.array_equal(pairs, want[2]), (v, k)
+                for threads in ("1", "3"):
+                    monkeypatch.setenv("IGD_HOST_THREADS", threads)
+                    got, gcovered = H.coverage(c, s, e, ev, rule)
+                    assert np.array_equal(got, want[0]) and gcovered == want[1], (v, k, threads)
+                W.add(cov, covered, pairs, query_bp(s, e))
+            W.check(tally if v else None)
+            if v:
+                assert tally == dict(nonempty=5, anchored=5)
+    finally:
+        H.close()
+        orc.close()
+
+
+def test_oracle_and_host_take_more_than_2_32_bp_in_one_slice(tmp):
+    path = F.bigbp_db(tmp)
+    (ichr, qs, qe), off = F.bigbp_sets()
+    p = F.plan(np.diff(off), 3)["coverage"]
+    assert p["sliceLen"] == 64 and p["lds"] and p["chunks"][0]["slices"] == 3       # set 0 is one slice: one LDS counter
+    orc, H = Oracle(path), HostCov(path)
+    try:
+        assert orc.nfiles == 3 and orc.gtype == 1
+        for v in (0, 500):
+            tally = {}
+            rows = list(F.expected_cov_rows(path, orc, H, ichr, qs, qe, off, v, tally=tally))
+            assert not v or tally == dict(nonempty=3, anchored=3)
+            assert rows[0][0].tolist() == [F.BIGBP_HAND, 64 * 500, 0] and rows[0][1] == F.BIGBP_HAND > 1 << 32
+            assert rows[1][0].tolist() == [68999000, 500, 0] and rows[1][1] == 68999000
+            assert rows[2][0].tolist() == [6400, 0, 0] and rows[2][1] == 6400
+            rule, ev = cli_rule(orc.gtype, v)
+            for k, (cov, covered, pairs) in enumerate(rows):
+                got, gcovered = H.coverage(ichr[off[k]:off[k + 1]], qs[off[k]:off[k + 1]], qe[off[k]:off[k + 1]], ev, rule)
+                assert np.array_equal(got, cov) and gcovered == covered and np.array_equal(pairs, cov), (v, k)
+            got, gcovered = H.coverage(ichr, qs, qe, ev, rule)
+            assert got.tolist() == [65 * 68999000 + 6400, 65 * 500, 0] and gcovered == 65 * 68999000 + 6400
     finally:
         H.close()
         orc.close()
