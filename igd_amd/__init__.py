@@ -2,7 +2,7 @@
 path), behind the reference's own C ABI.  See DESIGN.md / INTEGRATION.md."""
 from ._native import NativeMissing, build  # noqa: F401
 
-__all__ = ["Database", "NativeMissing", "build"]
+__all__ = ["Database", "NativeMissing", "build", "fisher_host"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -10,4 +10,7 @@ def __getattr__(name):
     if name == "Database":
         from .database import Database
         return Database
+    if name == "fisher_host":
+        from .database import fisher_host
+        return fisher_host
     raise AttributeError(name)

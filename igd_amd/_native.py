@@ -151,6 +151,12 @@ def hip():
         L.igd_hip_member_words.restype = C.c_int64
         L.igd_hip_member_grid.argtypes = [C.c_int64]
         L.igd_hip_member_grid.restype = C.c_int32
+        L.igd_hip_fisher_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.igd_hip_enrich_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_fisher_grid.argtypes = [C.c_int64]
+        L.igd_hip_fisher_grid.restype = C.c_int32
         L.igd_hip_membership.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
@@ -243,6 +249,8 @@ def _bind_core(L):
     # per-query membership rows on the host: ..., rule, bits (uint32[nq, nW]), nfiles_hit (int32[nq] or NULL), nhit
     L.igdc_membership_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    # Fisher's exact test on the host: a, b, c, d (int64[ncell]), ncell, pvalue_log, odds_ratio (double[ncell], may be NULL)
+    L.igdc_fisher_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     return L
 
 

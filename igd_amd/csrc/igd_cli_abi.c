@@ -967,6 +967,119 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
     free(q); free(rows); free(nhit);
 }
 
+/* ------------------------------- `igd search -q F -U <universe>` / `-Q <list> -U <universe>` ----------------- */
+/* Region-set enrichment: per query set and database file the 2x2 table of a one-sided Fisher exact test against a
+ * background universe, the LOLA table.  With the supports of `-u` (same rule and -v filter for sets and universe), n_k
+ * accepted lines in the set and n_U in the universe:
+ *     a = support of the set      b = u - a  (u = support of the universe)      c = n_k - a      d = n_U - a - b - c
+ * a negative b or d is printed and tested as 0 and counted in "clamped cells" (a set region outside the universe, or a
+ * universe region under several set regions: the sets are NOT restricted to the universe).  oddsRatio = (a d) / (b c), the
+ * sample odds ratio; pValueLog = -log10 P(X >= a), X ~ Hypergeometric(a+b+c+d, a+b, a+c).  One row per file with a > 0.
+ * Routing as `-u`, the universe's lines counted with the sets': at most igdc_host_limit() queries in all take
+ * igdc_support_host and igdc_fisher_host, more ONE igd_hip_enrich_sets_nhit call on one device. */
+/* b, c, d and the clamp count of every cell from the definitions (printed on both routes; the host route tests them) */
+static void enrich_tables(const int64_t *rows, const int64_t *urow, const igdc_queries *q, int64_t nU, int32_t n, int32_t nfiles,
+                          int64_t *tb, int64_t *tc, int64_t *td, int64_t *clamped)
+{
+    for (int32_t k = 0; k < n; k++) {
+        clamped[k] = 0;
+        for (int32_t f = 0; f < nfiles; f++) {
+            const size_t i = (size_t)k * (size_t)nfiles + (size_t)f;
+            const int64_t b = urow[f] - rows[i], c = q[k].n - rows[i], d = nU - rows[i] - b - c;
+            if (b < 0 || d < 0) clamped[k]++;
+            tb[i] = b < 0 ? 0 : b; tc[i] = c; td[i] = d < 0 ? 0 : d;
+        }
+    }
+}
+
+static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v, int setLines)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles;
+    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` (:1023-1030) */
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries uq;
+    memset(&uq, 0, sizeof uq);
+    if (igdc_read_queries(g_core, uniName, 1, &uq) != 0 || uq.n == 0) {
+        printf("Cannot read universe file %s, or it holds no region\n", uniName);
+        igdc_queries_free(&uq);
+        return;
+    }
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    const size_t cells = (size_t)n * (size_t)nfiles;
+    int64_t *rows = (int64_t *)calloc(cells + 1, sizeof(int64_t)), *urow = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
+    int64_t *nhit = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t)), unhit = 0;
+    int64_t *tb = (int64_t *)calloc(3 * cells + 1, sizeof(int64_t)), *tc = tb + cells, *td = tc + cells;
+    int64_t *clamped = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t));
+    double *plog = (double *)calloc(2 * cells + 1, sizeof(double)), *odds = plog + cells;
+    int onHost = 0;
+    igdc_map *hm = host_map_lim(nq + uq.n, igdc_host_limit());
+    if (hm) {
+        double t0 = now_s();
+        onHost = igdc_support_host(g_core, hm, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, urow, &unhit) == 0;
+        for (int32_t k = 0; k < n && onHost; k++)
+            if (q[k].n > 0)
+                onHost = igdc_support_host(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
+                                           &nhit[k]) == 0;
+        igdc_map_close(hm);
+        if (onHost) {
+            enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
+            onHost = igdc_fisher_host(rows, tb, tc, td, (int64_t)cells, plog, odds) == 0;
+        }
+        if (onHost) phase("support counts and Fisher tests on the host (small files)", &t0);
+        else {                                        /* (a read error: the engine reads the file its own way) */
+            memset(rows, 0, sizeof(int64_t) * cells);
+            memset(urow, 0, sizeof(int64_t) * (size_t)nfiles);
+            memset(nhit, 0, sizeof(int64_t) * (size_t)n);
+            unhit = 0;
+        }
+    }
+    if (!onHost) {
+        int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+        int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+        int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+        off[0] = 0;
+        for (int32_t k = 0; k < n; k++) {
+            if (q[k].n) {
+                memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+                memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+                memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+            }
+            off[k + 1] = off[k] + q[k].n;
+        }
+        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
+        double t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_enrich_sets_nhit(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, plog, odds,
+                                                    NULL, nhit, &unhit);
+            if (rc != IGD_HIP_OK) engine_failed("enrichment", rc);
+            else enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
+            phase("enrichment of the query sets (H2D + support kernel + Fisher kernel + D2H)", &t0);
+        }
+        free(ichr); free(qs); free(qe); free(off);
+    }
+    for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
+        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        printf("index\t number of regions\t support\t b\t c\t d\t oddsRatio\t pValueLog\t File_name\n");
+        for (int32_t f = 0; f < nfiles; f++) {
+            const size_t i = (size_t)k * (size_t)nfiles + (size_t)f;
+            if (rows[i] > 0)
+                printf("%i\t%i\t%lld\t%lld\t%lld\t%lld\t%.4f\t%.4f\t%s\n", f, IGD->finfo[f].nr, (long long)rows[i], (long long)tb[i],
+                       (long long)tc[i], (long long)td[i], odds[i], plog[i], IGD->finfo[f].fileName);
+        }
+        printf("Query regions with a hit: %lld of %lld; universe regions: %lld; clamped cells: %lld\n", (long long)nhit[k],
+               (long long)q[k].n, (long long)uq.n, (long long)clamped[k]);
+    }
+    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    igdc_queries_free(&uq);
+    free(q); free(rows); free(urow); free(nhit); free(tb); free(clamped); free(plog);
+}
+
 /* ------------------------------- `igd search -q F -w` / `-Q <list> -w` ----------------- */
 /* Per-query membership: one line per accepted query line, in input order,
  *     contig \t start \t end \t n \t list
@@ -1103,6 +1216,9 @@ static int usage_search(void)
             "    -u                         with -q or -Q: count query regions with a hit, once per dataset (support)\n"
             "    -b                         with -q or -Q: base pairs of the query regions covered by each dataset\n"
             "    -w                         with -q or -Q: per query region, the datasets it overlaps (membership)\n"
+            "    -U <universe file>         with -q or -Q: enrichment of each query set against the universe, per dataset the\n"
+            "                               2x2 table of the supports, the sample odds ratio and -log10 p of a one-sided\n"
+            "                               Fisher exact test (the sets are not restricted to the universe)\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
             "               several GPUs (database replicated, contiguous query slabs, per-dataset counts summed)\n");
     return EX_OK;
@@ -1142,8 +1258,8 @@ int igd_search(int argc, char **argv)                                        /* 
     int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
 
     int32_t v = 0, qs = 1, qe = 2;
-    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0;
-    char *chrm = NULL, *qfName = (char *)"", *listName = NULL;
+    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
+    char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
         const char *a = argv[i];
@@ -1174,13 +1290,28 @@ int igd_search(int argc, char **argv)                                        /* 
             bp = 1;
         } else if (strcmp(a, "-w") == 0) {            /* (not the reference's: per-query membership, see membership_files) */
             memb = 1;
+        } else if (strcmp(a, "-U") == 0) {            /* (not the reference's: enrichment against a universe, see enrich_files) */
+            if (i + 1 >= argc) { printf("No universe file.\n"); return EX_OK; }
+            uniName = argv[i + 1];
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
+        if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
     fP = fopen(igdName, "rb");                                                /* :974 */
-    if (full) {                                                               /* :975-995 */
+    if (uniName && (bp || memb || full || other)) {
+        printf("Not supported: -U together with -b, -w, -f, -m, -s or -r\n");
+        return EX_OK;
+    } else if (uniName && mode == 1) {
+        enrich_files(&qfName, 1, uniName, v, 0);
+    } else if (uniName && listName) {
+        int32_t n = 0;
+        char **paths = read_list(listName, &n);
+        if (n >= 0) enrich_files(paths, n, uniName, v, 1);
+        for (int32_t k = 0; k < n; k++) free(paths[k]);
+        free(paths);
+    } else if (full) {                                                        /* :975-995 */
         if (mode == 1) {
             int64_t total = IGD->gType == 0 ? getOverlaps_f0(qfName) : getOverlaps_f1(qfName);
             if (!g_fail_rc) printf("Total overlaps: %lld\n", (long long)total);

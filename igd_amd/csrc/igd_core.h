@@ -128,6 +128,13 @@ int igdc_coverage_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr
  * records, threading, rule and filter as igdc_support_host.  0 on success, -1 if a tile could not be read (rows undefined). */
 int igdc_membership_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                          int64_t nq, int32_t v, int rule, uint32_t *bits, int32_t *nfiles_hit, int64_t *nhit);
+/* Fisher's exact test, one-sided ("greater"), of ncell tables a b / c d: pvalue_log = -log10 P(X >= a) for X ~
+ * Hypergeometric(a+b+c+d, a+b, a+c), in log space (finite however small p is; +0.0 at the support minimum and for N = 0), and
+ * odds_ratio (may be NULL) = (a d) / (b c), the sample odds ratio (+inf when b c = 0 < a d, NaN when both are 0) -- what
+ * igd_hip_fisher_tables computes, on the calling thread with lgamma.  Outputs are OVERWRITTEN.  0 on success; -1, the
+ * outputs untouched, for a negative entry or N >= 2^31. */
+int igdc_fisher_host(const int64_t *a, const int64_t *b, const int64_t *c, const int64_t *d, int64_t ncell, double *pvalue_log,
+                     double *odds_ratio);
 /* `-f` (rule NEST, the reference's order): qoff[0..nq] offsets, *out malloc'd (free()), entries as igd_hip_enumerate's */
 int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                         int64_t nq, int64_t *qoff, igd_hip_hit **out, int64_t *total);

@@ -186,6 +186,20 @@ int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t 
     return fn ? fn(db, d_ichr, d_qs, d_qe, nq, v, rule, d_bits, d_nfiles_hit, d_nhit, stream) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                             int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, int32_t v, int rule,
+                             int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio, int64_t *clamped, int64_t *nhit,
+                             int64_t *unhit)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, const int32_t *,
+                        const int32_t *, const int32_t *, int64_t, int32_t, int, int64_t *, int64_t *, double *, double *, int64_t *,
+                        int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_enrich_sets_nhit");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, v, rule, support, usupport, pvalue_log, odds_ratio, clamped,
+                   nhit, unhit)
+              : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

@@ -26,6 +26,7 @@
 #include "igd_core.h"
 
 #include <fcntl.h>
+#include <math.h>
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
@@ -535,6 +536,77 @@ int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ich
     qoff[nq] = run;
     *out = all;
     if (total) *total = tot;
+    return 0;
+}
+
+/* Fisher's exact test of 2x2 tables on the host: what igd_fisher_cells (engine/fisher_dev.hpp) computes, by the same scheme
+ * -- log space, nine log-factorials per term added in the same pairs, the tail summed from the side on which it decays in
+ * steps of 64 terms until a step's first term is below the first one by 45 -- with the C library's lgamma, on the calling
+ * thread.  The statistics of `-U` when the supports were counted on the host. */
+/* libm by weak reference: the libraries link -lm (Makefile), but this file is also compiled into test harnesses whose
+ * link lines are fixed and do not name it.  Every process that reaches here has libm mapped (the HIP engine and the
+ * sanitizer runtimes need it); a process that has not is answered with -1, not with a crash. */
+#pragma weak exp
+#pragma weak log
+#pragma weak log1p
+#pragma weak lgamma_r
+#define FISHER_STOP 45.0
+#define FISHER_LN10 2.302585092994045684
+static double lfact(int64_t x)
+{
+    int sign;
+    return lgamma_r((double)x + 1.0, &sign);
+}
+static double fisher_plog(int64_t a, int64_t b, int64_t c, int64_t d)
+{
+    const int64_t N = a + b + c + d, K = a + b, n = a + c;
+    const int64_t lo = a - d > 0 ? a - d : 0, hi = n < K ? n : K;
+    if (N == 0 || a <= lo) return 0.0;
+    const int64_t mode = ((n + 1) * (K + 1)) / (N + 2);
+    const int up = a > mode;
+    const double lfK = lfact(K), lfNK = lfact(N - K), lfn = lfact(n), tail5 = lfact(N - n) - lfact(N);
+    const int64_t k0 = up ? a : a - 1, rest = N - K - n;
+    double tFirst = 0.0, S = 0.0;
+    for (int64_t base = 0;; base += 64) {
+        double t0 = 0.0, acc = 0.0;
+        for (int j = 0; j < 64; j++) {
+            const int64_t k = up ? k0 + base + j : k0 - base - j;
+            if (up ? k > hi : k < lo) break;
+            const double t = ((lfK - lfact(K - k)) + (lfNK - lfact(rest + k))) + (((lfn - lfact(n - k)) - lfact(k)) + tail5);
+            if (j == 0) { t0 = t; if (base == 0) tFirst = t; }
+            acc += exp(t - tFirst);
+        }
+        S += acc;
+        if (t0 < tFirst - FISHER_STOP) break;
+        if (up ? k0 + base + 64 > hi : k0 - base - 64 < lo) break;
+    }
+    double lp = tFirst + log(S);
+    if (!up) {
+        double L = exp(lp);
+        if (!(L < 1.0)) L = 0x1.fffffffffffffp-1;
+        lp = log1p(-L);
+    }
+    const double r = -lp / FISHER_LN10;
+    return r > 0.0 ? r : 0.0;
+}
+
+int igdc_fisher_host(const int64_t *a, const int64_t *b, const int64_t *c, const int64_t *d, int64_t ncell, double *pvalue_log,
+                     double *odds_ratio)
+{
+    if (ncell < 0 || (ncell > 0 && (!a || !b || !c || !d || !pvalue_log))) return -1;
+    if (!exp || !log || !log1p || !lgamma_r) return -1;
+    const int64_t lim = (int64_t)1 << 31;
+    for (int64_t i = 0; i < ncell; i++)
+        if (a[i] < 0 || b[i] < 0 || c[i] < 0 || d[i] < 0 || a[i] >= lim || b[i] >= lim || c[i] >= lim || d[i] >= lim ||
+            a[i] + b[i] + c[i] + d[i] >= lim)
+            return -1;
+    for (int64_t i = 0; i < ncell; i++) {
+        pvalue_log[i] = fisher_plog(a[i], b[i], c[i], d[i]);
+        if (odds_ratio) {
+            const double ad = (double)a[i] * (double)d[i], bc = (double)b[i] * (double)c[i];
+            odds_ratio[i] = bc == 0.0 ? (ad > 0.0 ? INFINITY : NAN) : ad / bc;
+        }
+    }
     return 0;
 }
 

@@ -4,6 +4,7 @@ Mirrors what the reference's front-ends do around the hot path -- load header + 
 (get_igdinfo / get_fileinfo), map contig names (get_id), read query files (parse_bed loop) --
 and hands every search to the HIP engine (include/igd_hip.h).  numpy arrays for host
 batches; raw device pointers (e.g. torch tensors' data_ptr()) for resident batches."""
+import collections
 import ctypes as C
 import os
 
@@ -23,6 +24,27 @@ def _chk(rc, what):
 
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+Enrichment = collections.namedtuple("Enrichment", "support usupport b c d pvalue_log odds_ratio clamped")
+
+
+def _tables(a, b, c, d, what):
+    t = [np.ascontiguousarray(x, dtype=np.int64) for x in (a, b, c, d)]
+    if any(x.ndim != 1 or len(x) != len(t[0]) for x in t):
+        raise IgdError("%s: a, b, c, d must be four one-dimensional arrays of one length" % what)
+    return t
+
+
+def fisher_host(a, b, c, d):
+    """Fisher's exact test of the tables a b / c d on the host (igdc_fisher_host; no device is touched): (pvalue_log,
+    odds_ratio), two float64 arrays, as Database.fisher() defines them."""
+    a, b, c, d = _tables(a, b, c, d, "fisher_host")
+    n = len(a)
+    p, o = np.empty(n, np.float64), np.empty(n, np.float64)
+    if N.cli().igdc_fisher_host(a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, n, p.ctypes.data, o.ctypes.data) != 0:
+        raise IgdError("fisher_host: a table has a negative entry or N >= 2^31")
+    return p, o
 
 
 class Database:
@@ -243,6 +265,68 @@ class Database:
         set_off[1:] = np.cumsum([len(s[1]) for s in sets])
         cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
         return self.coverage_sets(cat[0], cat[1], cat[2], set_off, v)
+
+    def fisher(self, a, b, c, d, pvalue_log=None, odds_ratio=None):
+        """Fisher's exact test, one-sided ("greater"), of the 2x2 tables a b / c d on the GPU (igd_hip_fisher_tables).
+        Returns (pvalue_log, odds_ratio), two float64 arrays: pvalue_log = -log10 P(X >= a) for X ~ Hypergeometric(a+b+c+d,
+        a+b, a+c), computed in log space (finite however small p is, +0.0 where a is the support minimum), odds_ratio =
+        (a d) / (b c), the sample odds ratio (inf when b c = 0 < a d, NaN when both are 0).  The output arrays, when given,
+        are overwritten.  A negative entry or N >= 2^31 raises IgdError and leaves them untouched."""
+        a, b, c, d = _tables(a, b, c, d, "fisher")
+        n = len(a)
+        for name, x in (("pvalue_log", pvalue_log), ("odds_ratio", odds_ratio)):
+            if x is not None and (x.dtype != np.float64 or x.shape != (n,) or not x.flags.c_contiguous):
+                raise IgdError("fisher: %s must be a contiguous float64[%d]" % (name, n))
+        p = np.empty(n, np.float64) if pvalue_log is None else pvalue_log
+        o = np.empty(n, np.float64) if odds_ratio is None else odds_ratio
+        _chk(self._H.igd_hip_fisher_tables(self.dev, a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, n,
+                                           p.ctypes.data, o.ctypes.data), "igd_hip_fisher_tables")
+        return p, o
+
+    def enrichment_sets(self, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, v=0, rule=None, value_filter=None):
+        """Region-set enrichment of many query sets against a universe in one call (igd_hip_enrich_sets).  Sets as
+        search_sets(); the universe is one more set of regions.  Returns Enrichment(support, usupport, b, c, d, pvalue_log,
+        odds_ratio, clamped): per set k and file f the table a = support[k, f] (support_sets()), b = usupport[f] - a,
+        c = |set k| - a, d = |universe| - a - b - c, where a negative b or d is then 0 and clamped[k] counts the cells of
+        set k where that happened (the sets are not restricted to the universe); pvalue_log and odds_ratio as fisher()
+        on these tables.  Arrays are [nsets, nfiles], usupport [nfiles], clamped [nsets].  No q-values."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        u_ichr, u_qs, u_qe = _i32(u_ichr), _i32(u_qs), _i32(u_qe)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+        nsets, nu, nf = len(set_off) - 1, len(u_qs), self.nfiles
+        if nsets < 0:
+            raise IgdError("enrichment_sets: set_off needs nsets + 1 entries")
+        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs) or len(u_ichr) != nu or len(u_qe) != nu:
+            raise IgdError("enrichment_sets: set_off[-1] = %d, but %d / %d / %d queries and %d / %d / %d universe regions given"
+                           % (set_off[-1], len(ichr), len(qs), len(qe), len(u_ichr), nu, len(u_qe)))
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        sup, usup = np.empty((nsets, nf), np.int64), np.empty(max(nf, 1), np.int64)
+        plog, odds = np.empty((nsets, nf), np.float64), np.empty((nsets, nf), np.float64)
+        clamped = np.empty(max(nsets, 1), np.int64)
+        _chk(self._H.igd_hip_enrich_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
+                                         u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu, vf, rule,
+                                         sup.ctypes.data if sup.size else None, usup.ctypes.data,
+                                         plog.ctypes.data if plog.size else None, odds.ctypes.data if odds.size else None,
+                                         clamped.ctypes.data), "igd_hip_enrich_sets")
+        usup = usup[:nf]
+        nk = np.diff(set_off)[:, None]
+        b = usup[None, :] - sup
+        c = nk - sup
+        d = nu - sup - b - c
+        return Enrichment(sup, usup, np.maximum(b, 0), c, np.maximum(d, 0), plog, odds, clamped[:nsets])
+
+    def enrichment_files(self, paths, universe_path, v=0):
+        """One query set per BED file and the universe from a BED file (read as `igd search -q` reads them): what
+        `igd search -Q list -U universe` prints, as enrichment_sets() returns it."""
+        sets = [self.read_queries(p) for p in paths]
+        uni = self.read_queries(universe_path)
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.enrichment_sets(cat[0], cat[1], cat[2], set_off, uni[0], uni[1], uni[2], v)
 
     @property
     def member_words(self):

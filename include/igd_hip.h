@@ -181,6 +181,43 @@ int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t 
  * nq exceeds four times this number (tests). */
 int32_t igd_hip_member_grid(int64_t nq);
 
+/* Fisher's exact test, one-sided ("greater"), of many 2x2 tables  a b / c d  in one call (kernel igd_fisher_cells).  With
+ * N = a+b+c+d, K = a+b, n = a+c and X ~ Hypergeometric(N, K, n):
+ *     pvalue_log[i] = -log10 P(X >= a)   a double >= 0, computed in log space: finite however small p is (a p of 10^-4609
+ *                                        is 4609.06), exactly +0.0 when a is the support minimum max(0, n - (N - K)) or N = 0
+ *     odds_ratio[i] = (a d) / (b c)      in double: the SAMPLE odds ratio (not the conditional maximum-likelihood estimate
+ *                                        R's fisher.test reports); +inf when b c = 0 < a d, NaN when both products are 0
+ * Both are DEFINED by the call (overwritten); odds_ratio may be NULL.  Blocking.  A table with a negative entry or with
+ * N >= 2^31 is IGD_HIP_ERR_ARG before any launch, the caller's outputs untouched. */
+int igd_hip_fisher_tables(igd_hip_db *db, const int64_t *a, const int64_t *b, const int64_t *c, const int64_t *d,
+                          int64_t ncell, double *pvalue_log, double *odds_ratio);
+/* Region-set enrichment of many query sets against a universe, in one call.  Sets as igd_hip_search_sets; the universe is
+ * the nu regions u_ichr / u_qs / u_qe.  With support as igd_hip_support_sets defines it (same rule and v for the sets and
+ * the universe), n_k = |set k| and n_U = nu, the table of set k and file f is
+ *     a = support[k * nFiles + f]      b = usupport[f] - a      c = n_k - a      d = n_U - a - b - c  (= n_U - usupport[f] - c)
+ * where a negative b or d is then set to 0 and clamped[k] counts the cells of set k where that happened (a set region
+ * outside the universe, or a universe region under several set regions: the sets are NOT restricted to the universe).
+ *     support[nsets * nFiles], usupport[nFiles]                     the counts (the universe is counted once)
+ *     pvalue_log[nsets * nFiles], odds_ratio[nsets * nFiles]        as igd_hip_fisher_tables on these tables, bit for bit
+ *     clamped[nsets]
+ * All are DEFINED by the call, not added to; odds_ratio and clamped may be NULL.  One igd_hip_support_sets call over the
+ * nsets + 1 sets, then the cell kernel on the resident counts.  Blocking.  The argument checks of igd_hip_support_sets
+ * apply; a set that with the universe holds 2^31 regions or more is IGD_HIP_ERR_ARG.  On an error nothing of the caller's
+ * is written.  No q-values, one device. */
+int igd_hip_enrich_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                        int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
+                        int32_t v, int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
+                        int64_t *clamped);
+/* The same, and the regions with a hit in any file: nhit[nsets] for the sets, *unhit for the universe (what
+ * igd_hip_support_sets adds to nhit; here DEFINED; both may be NULL) -- the last line of `igd search -U`. */
+int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                             int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
+                             int32_t v, int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
+                             int64_t *clamped, int64_t *nhit, int64_t *unhit);
+/* Workgroups (of four waves, one cell per wave at a time) the cell kernel is launched with for ncell cells: a wave takes a
+ * second cell only when ncell exceeds four times this number (tests). */
+int32_t igd_hip_fisher_grid(int64_t ncell);
+
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
  * `stream` (a hipStream_t; NULL = the engine's own stream) and returns without waiting.
