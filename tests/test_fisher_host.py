@@ -94,3 +94,60 @@ def test_bad_tables_are_refused_and_outputs_untouched():
     p = np.zeros(1)
     assert N.cli().igdc_fisher_host(a.ctypes.data, z.ctypes.data, z.ctypes.data, a.ctypes.data, 1, p.ctypes.data, None) == 0
     assert abs(p[0] - math.log10(252)) < 1e-13
+
+
+def wide_golden():
+    G = [g for g in R.golden() if g[5] == "wide"]
+    assert len(G) == 20
+    margins = {(sum(g[:4]), g[0] + g[1], g[0] + g[2]) for g in G}
+    assert margins == {(2 ** 31 - 2, 2 ** 30, 2 ** 30), (2 ** 31 - 2, 2 ** 30, 10 ** 6), (10 ** 8, 5 * 10 ** 7, 10 ** 7),
+                       (4 * 10 ** 6, 2 * 10 ** 6, 2 * 10 ** 6)}
+    ways = [R.branch(*g[:4]) for g in G]
+    assert ways.count("down") == 8 and ways.count("up") == 12      # a = mode and mode - 3 sd are summed downward
+    return G
+
+
+def test_wide_tables_run_for_hundreds_of_steps():
+    """N up to 2^31 - 2 with a standard deviation of up to 16 384: the tail is summed over 27 to about 1 700 steps of 64
+    terms, with lgamma arguments near 2^30, where 1e-6 is one ulp of a log-factorial.  The recorded values come from mpmath
+    (tools/make_fisher_golden.py); the bound is the same as everywhere."""
+    G = wide_golden()
+    tables = [g[:4] for g in G]
+    p, o = host(tables)
+    worst = R.check(tables, [g[4] for g in G], p, o, "wide")
+    print("wide: worst |x - y| / bound = %.3g" % worst)
+    assert max(g[4] for g in G) > 30 and min(g[4] for g in G) < 1e-3     # 12 sd above the mode, 3 sd below it
+
+
+def test_support_end_edges():
+    """The number of summed terms at 1, 2, 63, 64, 65, 127, 128, 129 and 192 in both directions (fisher_ref.edge_tables).
+    The fixture's condition, in exact arithmetic: wherever the last step of 64 is not full, one more copy of the first
+    term -- what an unmasked lane past the end would add -- moves the exact value by more than ten times the bound."""
+    E = R.edge_tables()
+    assert sorted((w, T) for w, T, _ in E) == sorted((w, T) for w in ("up", "down") for T in R.EDGE_COUNTS)
+    tables = [t for _, _, t in E]
+    want = [R.exact_plog(*t) for t in tables]
+    for (way, T, t), y in zip(E, want):
+        assert sum(t) <= 2000
+        if T % 64:
+            moved = abs(R.one_more_first_term(*t) - y)
+            assert moved > 10 * R.tol(*t, y), (way, T, t, moved)
+    p, o = host(tables)
+    print("edges: worst |x - y| / bound = %.3g" % R.check(tables, want, p, o, "edges"))
+
+
+def test_pool_tables_cover_the_four_branches():
+    T, want = R.pool_expected()
+    assert len(T) == len(set(T)) == R.POOL == 1009 and max(sum(t) for t in T) <= 300
+    ways = [R.branch(*t) for t in T]
+    assert ways.count("zero") == 1 and min(ways.count(w) for w in ("lo", "up", "down")) >= 100
+    assert all(T[i] != T[i + 1] for i in range(len(T) - 1))
+    idx = np.arange(3 * R.POOL + 5) % R.POOL
+    a, b, c, d = (np.array(x, np.int64)[idx] for x in zip(*T))
+    import igd_amd
+    p, o = igd_amd.fisher_host(a, b, c, d)
+    print("pool: worst |x - y| / bound = %.3g" % R.check_many(T, want, idx, p, o, "pool"))
+    bad = p.copy()
+    bad[R.POOL + 1] += 1e-9                                      # the vectorised check sees one wrong cell
+    with pytest.raises(AssertionError):
+        R.check_many(T, want, idx, bad, o, "pool")

@@ -12,6 +12,7 @@ import pytest
 
 import fisher_ref as R
 from helpers import Oracle, short_tmpdir
+import test_enrich_host as EH
 from test_enrich_host import HEADER, enrich_fixture, tables_from_supports
 from test_sets_cli import _write_list
 from test_support_host import FLAT, HOST, NEST, NOV, _run, oracle_support
@@ -176,3 +177,121 @@ def test_bad_arguments_leave_nothing_written(fx):
                                    p.ctypes.data, o.ctypes.data, cl.ctypes.data)
         assert rc != 0
         assert (sup == -5).all() and (usup == -5).all() and (p == -5.0).all() and (o == -5.0).all() and (cl == -5).all()
+
+
+# ---- the cell kernel beyond one cell per wave and beyond one launch (fixtures and their conditions: test_enrich_host.py) ----
+def _open(path):
+    from igd_amd import Database
+    return Oracle(path), Database(path)
+
+
+def test_waves_take_a_second_cell_in_the_enrichment_form():
+    """267 sets x 40 files = 10 680 cells, more than the waves of the full grid: a wave's second cell g = cell0 + i has its
+    own k = g / nF and f = g - k nF, so B[f] and C[k] follow the cell.  The last set, reached only as a second cell, is
+    the one with clamped cells."""
+    from igd_amd import _native as N
+    d = short_tmpdir("igr")
+    try:
+        path, cat, off, uni = EH.recut_fixture(d)
+        orc, db = _open(path)
+        try:
+            W = EH.expected_matrix(orc, cat, off, uni)
+            nsets = len(off) - 1
+            grid = int(N.hip().igd_hip_fisher_grid(nsets * NFILES))
+            assert grid == int(N.hip().igd_hip_fisher_grid(1 << 40)) and nsets * NFILES > 4 * grid
+            EH.second_cell_conditions(W, grid)
+            res = db.enrichment_sets(*cat, off, *uni)
+            want = (W["usupport"], [(W["support"][k], W["b"][k], W["c"][k], W["d"][k], int(W["clamped"][k]),
+                                     [W["tables"][i] for i in W["idx"][k * NFILES:(k + 1) * NFILES]],
+                                     [W["plog"][i] for i in W["idx"][k * NFILES:(k + 1) * NFILES]]) for k in range(nsets)])
+            check_result(dict(db=db), res, want, "recut")
+            late = np.arange(nsets * NFILES) >= 4 * grid
+            assert (res.support.ravel()[late] > 0).any() and (res.pvalue_log.ravel()[late] > 0).any() and res.clamped[-1] > 0
+        finally:
+            db.close()
+            orc.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def test_enrichment_form_across_the_chunk_seam():
+    """2 081 files x 505 sets = 2^20 + 2 329 cells: the second launch has cell0 = 2^20 = 503 * 2081 + 1833, so its first cell
+    is file 1833 of set 503; it reads rows + 2^20, writes pvalue_log + 2^20 / odds_ratio + 2^20 from a workspace laid out
+    for 2^20 cells, and adds to clamped[503], which the first launch has already counted into.  Then the same tables go
+    through the generic form, which crosses its own seam, and must give the same bits."""
+    import time
+    d = short_tmpdir("igm")
+    try:
+        t0 = time.perf_counter()
+        path, cat, off, uni = EH.seam_fixture(d)
+        orc, db = _open(path)
+        try:
+            W = EH.expected_matrix(orc, cat, off, uni)
+            EH.seam_conditions(W, R.chunk_cells())
+            t1 = time.perf_counter()
+            res = db.enrichment_sets(*cat, off, *uni)
+            t2 = time.perf_counter()
+            worst = EH.check_matrix(W, res.usupport, res.support, res.clamped, res.pvalue_log, res.odds_ratio, "seam", res.b, res.c, res.d)
+            k, f = divmod(R.chunk_cells(), EH.SEAM_FILES)
+            for kk, ff in ((k, f - 1), (k, f), (EH.SEAM_SETS - 1, EH.SEAM_FILES - 1)):          # by name: the seam and the last cell
+                i = kk * EH.SEAM_FILES + ff
+                t, y = W["tables"][W["idx"][i]], W["plog"][W["idx"][i]]
+                assert abs(res.pvalue_log[kk, ff] - y) <= R.tol(*t, y), (kk, ff, t)
+            n = res.support.size
+            p, o = db.fisher(res.support.ravel(), res.b.ravel(), res.c.ravel(), res.d.ravel(), pvalue_log=np.full(n, -7.0),
+                             odds_ratio=np.full(n, -7.0))
+            t3 = time.perf_counter()
+            assert np.array_equal(p.view(np.int64), res.pvalue_log.ravel().view(np.int64))
+            assert np.array_equal(o.view(np.int64), res.odds_ratio.ravel().view(np.int64))
+            print("seam: worst |x - y| / bound = %.3g; preparation (database, oracle, exact values) %.2f s, enrichment_sets %.3f s, "
+                  "generic form of the same tables %.3f s" % (worst, t1 - t0, t2 - t1, t3 - t2))
+        finally:
+            db.close()
+            orc.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def test_without_odds_ratios_the_rest_is_unchanged(fx):
+    """odds_ratio = NULL in the enrichment form: the same p-values, supports and clamp counts, nothing written around them"""
+    from igd_amd import _native as N
+    db = fx["db"]
+    ichr, qs, qe = fx["cat"]
+    off, u = fx["off"], fx["uni"]
+    res = db.enrichment_sets(ichr, qs, qe, off, *u)
+    assert res.clamped.sum() > 0
+    n = 3 * NFILES
+    sup, usup, cl = np.full(n + 8, -5, np.int64), np.full(NFILES + 8, -5, np.int64), np.full(3 + 8, -5, np.int64)
+    p = np.full(n + 16, -5.0)
+    rc = N.hip().igd_hip_enrich_sets(db.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, off.ctypes.data, 3, u[0].ctypes.data,
+                                     u[1].ctypes.data, u[2].ctypes.data, len(u[1]), NOV, NEST, sup[4:].ctypes.data, usup[4:].ctypes.data,
+                                     p[8:].ctypes.data, None, cl[4:].ctypes.data)
+    assert rc == 0
+    assert np.array_equal(p[8:8 + n].view(np.int64), res.pvalue_log.ravel().view(np.int64))
+    assert np.array_equal(sup[4:4 + n], res.support.ravel()) and np.array_equal(usup[4:4 + NFILES], res.usupport)
+    assert np.array_equal(cl[4:7], res.clamped)
+    for a, lo, hi in ((p, 8, 8 + n), (sup, 4, 4 + n), (usup, 4, 4 + NFILES), (cl, 4, 7)):
+        assert (a[:lo] == -5).all() and (a[hi:] == -5).all()
+
+
+def test_one_file_database():
+    """nF = 1: the matrix is one column, k = g / 1 = g and f = 0 for every cell"""
+    d = short_tmpdir("ig1")
+    try:
+        path, cat, off, uni = EH.one_file_fixture(d)
+        orc, db = _open(path)
+        try:
+            assert orc.nfiles == 1
+            W = EH.expected_matrix(orc, cat, off, uni)
+            EH.one_file_conditions(W)
+            res = db.enrichment_sets(*cat, off, *uni)
+            assert res.support.shape == (6, 1)
+            EH.check_matrix(W, res.usupport, res.support, res.clamped, res.pvalue_log, res.odds_ratio, "one file", res.b, res.c, res.d)
+            p, o = db.fisher(res.support.ravel(), res.b.ravel(), res.c.ravel(), res.d.ravel())
+            assert np.array_equal(p.view(np.int64), res.pvalue_log.ravel().view(np.int64))
+            assert np.array_equal(o.view(np.int64), res.odds_ratio.ravel().view(np.int64))
+        finally:
+            db.close()
+            orc.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)

@@ -102,3 +102,55 @@ def test_bad_tables_raise_and_leave_the_outputs_untouched(db):
         assert (p == 7.5).all() and (o == -3.25).all()
     p, o = db.fisher([2 ** 31 - 4], [1], [1], [1])             # N = 2^31 - 1 is the largest accepted
     assert p[0] >= 0 and o[0] == float(2 ** 31 - 4)
+
+
+def test_wide_tables_run_for_hundreds_of_steps(db):
+    """tails of 27 to about 1 700 steps of 64 terms in one wave each, lgamma arguments near 2^30 (test_fisher_host.py)"""
+    import time
+    from test_fisher_host import wide_golden
+    G = wide_golden()
+    t0 = time.perf_counter()
+    both(db, [g[:4] for g in G], "wide", [g[4] for g in G])
+    print("wide: %.3f s for the device and the host call together" % (time.perf_counter() - t0))
+
+
+def test_support_end_edges(db):
+    """1, 2, 63, 64, 65, 127, 128, 129 and 192 summed terms in both directions: the lanes past the end of the support
+    compute a term and must not add it (test_fisher_host.py holds the fixture's condition in exact arithmetic)"""
+    E = R.edge_tables()
+    tables = [t for _, _, t in E]
+    both(db, tables, "edges", [R.exact_plog(*t) for t in tables])
+
+
+def test_generic_form_across_the_chunk_seam(db):
+    """2^20 + 77 cells: two launches, the second with cell0 = 2^20, 77 cells and a grid of 20 workgroups, its inputs taken
+    from a + 2^20 .. and its results copied to pvalue_log + 2^20 / odds_ratio + 2^20.  The tables cycle fisher_ref's pool
+    of 1 009 distinct ones (all four branches), so what belongs at 2^20 + j differs from what belongs at j."""
+    import time
+    import igd_amd
+    from igd_amd import _native as N
+    chunk = R.chunk_cells()
+    T, want = R.pool_expected()
+    n = chunk + 77
+    grid = int(N.hip().igd_hip_fisher_grid(chunk))
+    assert R.POOL % 2 == 1 and math.gcd(R.POOL, 4 * grid) == 1 and 4 * grid < chunk
+    idx = np.arange(n) % R.POOL
+    a, b, c, d = (np.ascontiguousarray(np.array(x, np.int64)[idx]) for x in zip(*T))
+    y = np.array(want)[idx]
+    ways = np.array([R.branch(*t) for t in T])[idx]
+    # the two sides of the seam hold different values, and no cell behind it expects what the cell 2^20 before it does
+    assert y[chunk - 1] != y[chunk] and y[chunk] != y[0] and y[n - 1] != y[76] and y[chunk - 1] > 0 and y[chunk] > 0 and y[n - 1] > 0
+    assert (y[chunk:] != y[:77]).sum() >= 60 and {"lo", "up", "down"} <= set(ways[chunk:])
+    t0 = time.perf_counter()
+    p, o = db.fisher(a, b, c, d, pvalue_log=np.full(n, -7.0), odds_ratio=np.full(n, -7.0))
+    t1 = time.perf_counter()
+    worst = R.check_many(T, want, idx, p, o, "seam")
+    for i in (0, chunk - 1, chunk, n - 1):
+        t = T[idx[i]]
+        assert abs(p[i] - want[idx[i]]) <= R.tol(*t, want[idx[i]]) and R.ulps(float(o[i]), R.odds(*t)) <= 4, (i, t, p[i], o[i])
+    hp, ho = igd_amd.fisher_host(a, b, c, d)
+    t2 = time.perf_counter()
+    bound2 = np.array([2 * R.tol(*t, w) for t, w in zip(T, want)])[idx]
+    assert (np.abs(p - hp) <= bound2).all()
+    assert np.array_equal(np.isnan(o), np.isnan(ho)) and np.array_equal(np.isinf(o), np.isinf(ho))
+    print("seam: %d cells, worst |x - y| / bound = %.3g; GPU call %.3f s, host call %.3f s" % (n, worst, t1 - t0, t2 - t1))
