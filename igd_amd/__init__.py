@@ -2,7 +2,7 @@
 path), behind the reference's own C ABI.  See DESIGN.md / INTEGRATION.md."""
 from ._native import NativeMissing, build  # noqa: F401
 
-__all__ = ["Database", "NativeMissing", "build", "fisher_host"]
+__all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == "fisher_host":
         from .database import fisher_host
         return fisher_host
+    if name == "rank_host":
+        from .database import rank_host
+        return rank_host
     raise AttributeError(name)

@@ -157,6 +157,12 @@ def hip():
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_fisher_grid.argtypes = [C.c_int64]
         L.igd_hip_fisher_grid.restype = C.c_int32
+        L.igd_hip_enrich_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_rank_grid.argtypes = [C.c_int64]
+        L.igd_hip_rank_grid.restype = C.c_int32
+        L.igd_hip_rank_lds_cols.argtypes = []
+        L.igd_hip_rank_lds_cols.restype = C.c_int32
         L.igd_hip_membership.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
@@ -251,6 +257,10 @@ def _bind_core(L):
                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     # Fisher's exact test on the host: a, b, c, d (int64[ncell]), ncell, pvalue_log, odds_ratio (double[ncell], may be NULL)
     L.igdc_fisher_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    # ranks and q-values on the host: support, pvalue_log, odds_ratio ([nrows, ncols], may be NULL), nrows, ncols, qvalue_log,
+    # rnk_sup, rnk_pv, rnk_or, max_rnk, mean_rnk (may be NULL)
+    L.igdc_rank_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 

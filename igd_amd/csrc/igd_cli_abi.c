@@ -976,7 +976,12 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
  * universe region under several set regions: the sets are NOT restricted to the universe).  oddsRatio = (a d) / (b c), the
  * sample odds ratio; pValueLog = -log10 P(X >= a), X ~ Hypergeometric(a+b+c+d, a+b, a+c).  One row per file with a > 0.
  * Routing as `-u`, the universe's lines counted with the sets': at most igdc_host_limit() queries in all take
- * igdc_support_host and igdc_fisher_host, more ONE igd_hip_enrich_sets_nhit call on one device. */
+ * igdc_support_host and igdc_fisher_host, more ONE igd_hip_enrich_sets_nhit call on one device.
+ * With `-R` six more columns follow the file name: rnkSup, rnkPV, rnkOR -- the file's rank among ALL files of the set, those
+ * with a = 0 included, by support, pValueLog and oddsRatio (ties take the minimum rank) -- maxRnk, meanRnk and qValueLog,
+ * -log10 of the Benjamini-Hochberg adjusted p over the set's nFiles tests (include/igd_hip.h: igd_hip_enrich_ranks).  They come
+ * from igdc_rank_host where the supports came from the host, otherwise from igd_hip_enrich_ranks.  Lines and their order are
+ * those without `-R`. */
 /* b, c, d and the clamp count of every cell from the definitions (printed on both routes; the host route tests them) */
 static void enrich_tables(const int64_t *rows, const int64_t *urow, const igdc_queries *q, int64_t nU, int32_t n, int32_t nfiles,
                           int64_t *tb, int64_t *tc, int64_t *td, int64_t *clamped)
@@ -992,7 +997,7 @@ static void enrich_tables(const int64_t *rows, const int64_t *urow, const igdc_q
     }
 }
 
-static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v, int setLines)
+static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v, int setLines, int ranks)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles;
@@ -1017,6 +1022,10 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
     int64_t *tb = (int64_t *)calloc(3 * cells + 1, sizeof(int64_t)), *tc = tb + cells, *td = tc + cells;
     int64_t *clamped = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t));
     double *plog = (double *)calloc(2 * cells + 1, sizeof(double)), *odds = plog + cells;
+    /* -R: q and mean, then the four int32 columns */
+    double *qlog = ranks ? (double *)calloc(4 * cells + 1, sizeof(double)) : NULL, *rmean = ranks ? qlog + cells : NULL;
+    int32_t *rsup = ranks ? (int32_t *)(rmean + cells) : NULL, *rpv = ranks ? rsup + cells : NULL, *ror = ranks ? rpv + cells : NULL;
+    int32_t *rmax = ranks ? ror + cells : NULL;
     int onHost = 0;
     igdc_map *hm = host_map_lim(nq + uq.n, igdc_host_limit());
     if (hm) {
@@ -1031,6 +1040,7 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
             enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
             onHost = igdc_fisher_host(rows, tb, tc, td, (int64_t)cells, plog, odds) == 0;
         }
+        if (onHost && ranks) onHost = igdc_rank_host(rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean) == 0;
         if (onHost) phase("support counts and Fisher tests on the host (small files)", &t0);
         else {                                        /* (a read error: the engine reads the file its own way) */
             memset(rows, 0, sizeof(int64_t) * cells);
@@ -1060,24 +1070,32 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
             if (rc != IGD_HIP_OK) engine_failed("enrichment", rc);
             else enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
             phase("enrichment of the query sets (H2D + support kernel + Fisher kernel + D2H)", &t0);
+            if (ranks && rc == IGD_HIP_OK) {
+                const int rr = igd_hip_enrich_ranks(dev, rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean);
+                if (rr != IGD_HIP_OK) engine_failed("enrichment ranks", rr);
+                phase("ranks and q-values of the enrichment table (H2D + rank kernel + D2H)", &t0);
+            }
         }
         free(ichr); free(qs); free(qe); free(off);
     }
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
         if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
-        printf("index\t number of regions\t support\t b\t c\t d\t oddsRatio\t pValueLog\t File_name\n");
+        printf("index\t number of regions\t support\t b\t c\t d\t oddsRatio\t pValueLog\t File_name%s\n",
+               ranks ? "\t rnkSup\t rnkPV\t rnkOR\t maxRnk\t meanRnk\t qValueLog" : "");
         for (int32_t f = 0; f < nfiles; f++) {
             const size_t i = (size_t)k * (size_t)nfiles + (size_t)f;
-            if (rows[i] > 0)
-                printf("%i\t%i\t%lld\t%lld\t%lld\t%lld\t%.4f\t%.4f\t%s\n", f, IGD->finfo[f].nr, (long long)rows[i], (long long)tb[i],
-                       (long long)tc[i], (long long)td[i], odds[i], plog[i], IGD->finfo[f].fileName);
+            if (rows[i] <= 0) continue;
+            printf("%i\t%i\t%lld\t%lld\t%lld\t%lld\t%.4f\t%.4f\t%s", f, IGD->finfo[f].nr, (long long)rows[i], (long long)tb[i],
+                   (long long)tc[i], (long long)td[i], odds[i], plog[i], IGD->finfo[f].fileName);
+            if (ranks) printf("\t%d\t%d\t%d\t%d\t%.2f\t%.4f", (int)rsup[i], (int)rpv[i], (int)ror[i], (int)rmax[i], rmean[i], qlog[i]);
+            printf("\n");
         }
         printf("Query regions with a hit: %lld of %lld; universe regions: %lld; clamped cells: %lld\n", (long long)nhit[k],
                (long long)q[k].n, (long long)uq.n, (long long)clamped[k]);
     }
     for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
     igdc_queries_free(&uq);
-    free(q); free(rows); free(urow); free(nhit); free(tb); free(clamped); free(plog);
+    free(q); free(rows); free(urow); free(nhit); free(tb); free(clamped); free(plog); free(qlog);
 }
 
 /* ------------------------------- `igd search -q F -w` / `-Q <list> -w` ----------------- */
@@ -1219,6 +1237,8 @@ static int usage_search(void)
             "    -U <universe file>         with -q or -Q: enrichment of each query set against the universe, per dataset the\n"
             "                               2x2 table of the supports, the sample odds ratio and -log10 p of a one-sided\n"
             "                               Fisher exact test (the sets are not restricted to the universe)\n"
+            "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
+            "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
             "               several GPUs (database replicated, contiguous query slabs, per-dataset counts summed)\n");
     return EX_OK;
@@ -1258,7 +1278,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
 
     int32_t v = 0, qs = 1, qe = 2;
-    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
+    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -1293,6 +1313,8 @@ int igd_search(int argc, char **argv)                                        /* 
         } else if (strcmp(a, "-U") == 0) {            /* (not the reference's: enrichment against a universe, see enrich_files) */
             if (i + 1 >= argc) { printf("No universe file.\n"); return EX_OK; }
             uniName = argv[i + 1];
+        } else if (strcmp(a, "-R") == 0) {            /* (not the reference's: rank and q-value columns of -U, see enrich_files) */
+            ranks = 1;
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
@@ -1300,15 +1322,18 @@ int igd_search(int argc, char **argv)                                        /* 
     }
 
     fP = fopen(igdName, "rb");                                                /* :974 */
-    if (uniName && (bp || memb || full || other)) {
+    if (ranks && !uniName) {
+        printf("Not supported: -R without -U\n");
+        return EX_OK;
+    } else if (uniName && (bp || memb || full || other)) {
         printf("Not supported: -U together with -b, -w, -f, -m, -s or -r\n");
         return EX_OK;
     } else if (uniName && mode == 1) {
-        enrich_files(&qfName, 1, uniName, v, 0);
+        enrich_files(&qfName, 1, uniName, v, 0, ranks);
     } else if (uniName && listName) {
         int32_t n = 0;
         char **paths = read_list(listName, &n);
-        if (n >= 0) enrich_files(paths, n, uniName, v, 1);
+        if (n >= 0) enrich_files(paths, n, uniName, v, 1, ranks);
         for (int32_t k = 0; k < n; k++) free(paths[k]);
         free(paths);
     } else if (full) {                                                        /* :975-995 */

@@ -135,6 +135,13 @@ int igdc_membership_host(const igdc_db *db, const igdc_map *m, const int32_t *ic
  * outputs untouched, for a negative entry or N >= 2^31. */
 int igdc_fisher_host(const int64_t *a, const int64_t *b, const int64_t *c, const int64_t *d, int64_t ncell, double *pvalue_log,
                      double *odds_ratio);
+/* Rank columns and Benjamini-Hochberg q-values of an enrichment table, row by row (a row = the ncols cells of one query
+ * set = one family of tests): what igd_hip_enrich_ranks computes (include/igd_hip.h has the definitions), on the calling
+ * thread with qsort and log10.  Any output may be NULL, and an input that no requested output needs; max_rnk and mean_rnk
+ * need all three.  Outputs are OVERWRITTEN.  0 on success; -1, the outputs untouched, for a missing input, ncols > 2^20 or
+ * a pvalue_log that is negative or NaN. */
+int igdc_rank_host(const int64_t *support, const double *pvalue_log, const double *odds_ratio, int64_t nrows, int64_t ncols,
+                   double *qvalue_log, int32_t *rnk_sup, int32_t *rnk_pv, int32_t *rnk_or, int32_t *max_rnk, double *mean_rnk);
 /* `-f` (rule NEST, the reference's order): qoff[0..nq] offsets, *out malloc'd (free()), entries as igd_hip_enumerate's */
 int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                         int64_t nq, int64_t *qoff, igd_hip_hit **out, int64_t *total);

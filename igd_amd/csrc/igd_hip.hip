@@ -309,7 +309,8 @@ struct igd_hip_db {
     int32_t *d_memNf;
     unsigned long long *d_memHit;
     int64_t memBitsCap, memNfCap;
-    // igd_hip_fisher_tables / igd_hip_enrich_sets (host_enrich.hpp): the tables and results of one chunk of cells (64-bit words)
+    // igd_hip_fisher_tables / igd_hip_enrich_sets (host_enrich.hpp): the tables and results of one chunk of cells (64-bit words);
+    // igd_hip_enrich_ranks (host_rank.hpp) uses the same words for its chunk of rows
     int64_t *d_fisher;
     int64_t fisherCap;
     hipStream_t stream;
@@ -342,6 +343,7 @@ struct igd_hip_db {
 #include "engine/coverage_dev.hpp"    // igd_sets_coverage: the same walk, one frontier per (query, file): covered base pairs
 #include "engine/member_dev.hpp"      // igd_member_rows: the same walk, one bit row per query: which files it overlaps
 #include "engine/fisher_dev.hpp"      // igd_fisher_cells: one wave per 2x2 table, the hypergeometric tail in log space
+#include "engine/rank_dev.hpp"        // igd_rank_rows: one workgroup per table row, bitonic sort per column: ranks and BH q-values
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -353,6 +355,7 @@ struct igd_hip_db {
 #include "engine/host_coverage.hpp"   // igd_hip_coverage_sets: chunks of sets, all of them sliced
 #include "engine/host_member.hpp"     // igd_hip_membership / _dev: chunks of queries within a row budget, one launch each
 #include "engine/host_enrich.hpp"     // igd_hip_fisher_tables / igd_hip_enrich_sets: chunks of cells, one launch each
+#include "engine/host_rank.hpp"       // igd_hip_enrich_ranks: chunks of whole rows, one launch each
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

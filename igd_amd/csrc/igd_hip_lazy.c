@@ -200,6 +200,31 @@ int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t 
               : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_enrich_ranks(igd_hip_db *db, const int64_t *support, const double *pvalue_log, const double *odds_ratio, int64_t nrows,
+                         int64_t ncols, double *qvalue_log, int32_t *rnk_sup, int32_t *rnk_pv, int32_t *rnk_or, int32_t *max_rnk,
+                         double *mean_rnk)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int64_t *, const double *, const double *, int64_t, int64_t, double *, int32_t *, int32_t *,
+                        int32_t *, int32_t *, double *);
+    RESOLVE(fn_t, "igd_hip_enrich_ranks");
+    return fn ? fn(db, support, pvalue_log, odds_ratio, nrows, ncols, qvalue_log, rnk_sup, rnk_pv, rnk_or, max_rnk, mean_rnk)
+              : IGD_HIP_ERR_DEVICE;
+}
+
+int32_t igd_hip_rank_grid(int64_t nrows)
+{
+    typedef int32_t (*fn_t)(int64_t);
+    RESOLVE(fn_t, "igd_hip_rank_grid");
+    return fn ? fn(nrows) : 0;
+}
+
+int32_t igd_hip_rank_lds_cols(void)
+{
+    typedef int32_t (*fn_t)(void);
+    RESOLVE(fn_t, "igd_hip_rank_lds_cols");
+    return fn ? fn() : 0;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

@@ -610,6 +610,99 @@ int igdc_fisher_host(const int64_t *a, const int64_t *b, const int64_t *c, const
     return 0;
 }
 
+/* Ranks and Benjamini-Hochberg q-values of an enrichment table on the host: what igd_rank_rows (engine/rank_dev.hpp)
+ * computes, by the same scheme -- per row and column a 64-bit key whose unsigned order is the column's, the cells sorted by
+ * descending key (equal keys by column), the start of a cell's tie run its rank - 1, the end of the run r, and q the maximum
+ * of adj = p + (log10 r - log10 m) from the small end, clamped at +0.0 -- on the calling thread.  The ranks and q of `-U -R`
+ * when the supports were counted on the host.  log10 by weak reference, as the Fisher test's functions above. */
+#pragma weak log10
+typedef struct { uint64_t key; uint32_t idx; } rank_cell;
+static int rank_cell_cmp(const void *x, const void *y)
+{
+    const rank_cell *a = (const rank_cell *)x, *b = (const rank_cell *)y;
+    if (a->key != b->key) return a->key > b->key ? -1 : 1;
+    return a->idx < b->idx ? -1 : a->idx > b->idx;
+}
+static uint64_t rank_bits(double x)
+{
+    uint64_t b;
+    memcpy(&b, &x, sizeof b);
+    return b;
+}
+static uint64_t rank_key_or(double x)
+{
+    if (x != x) return 0;                                 /* NaN: below -inf */
+    const uint64_t b = x == 0.0 ? 0 : rank_bits(x);
+    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+/* sorts cell[0..m) and stores rank[idx]; with q also the q-values (the keys are then the bits of pvalue_log >= +0.0) */
+static void rank_row(rank_cell *cell, int64_t m, int32_t *rank, double *q)
+{
+    qsort(cell, (size_t)m, sizeof *cell, rank_cell_cmp);
+    if (rank) {
+        int64_t start = 0;
+        for (int64_t j = 0; j < m; j++) {
+            if (j > 0 && cell[j].key != cell[j - 1].key) start = j;
+            rank[cell[j].idx] = (int32_t)(start + 1);
+        }
+    }
+    if (q) {
+        const double log10m = log10((double)m);
+        double adj = 0.0, best = -INFINITY;
+        for (int64_t j = m - 1; j >= 0; j--) {
+            if (j == m - 1 || cell[j + 1].key != cell[j].key) {      /* the end of a tie run: r = j + 1 */
+                double p;
+                memcpy(&p, &cell[j].key, sizeof p);
+                adj = p + (log10((double)(j + 1)) - log10m);
+            }
+            if (adj > best) best = adj;
+            q[cell[j].idx] = best > 0.0 ? best : 0.0;
+        }
+    }
+}
+
+int igdc_rank_host(const int64_t *support, const double *pvalue_log, const double *odds_ratio, int64_t nrows, int64_t ncols,
+                   double *qvalue_log, int32_t *rnk_sup, int32_t *rnk_pv, int32_t *rnk_or, int32_t *max_rnk, double *mean_rnk)
+{
+    const int mm = max_rnk || mean_rnk;
+    const int doSup = rnk_sup || mm, doPv = rnk_pv || qvalue_log || mm, doOr = rnk_or || mm;
+    if (nrows < 0 || ncols < 0 || ncols > ((int64_t)1 << 20)) return -1;
+    if (nrows == 0 || ncols == 0 || (!doSup && !doPv && !doOr)) return 0;
+    if ((doSup && !support) || (doPv && !pvalue_log) || (doOr && !odds_ratio) || nrows > INT64_MAX / ncols) return -1;
+    if (qvalue_log && !log10) return -1;
+    if (doPv)
+        for (int64_t i = 0; i < nrows * ncols; i++)
+            if (!(pvalue_log[i] >= 0.0)) return -1;
+    const int64_t m = ncols;
+    rank_cell *cell = (rank_cell *)malloc(sizeof(rank_cell) * (size_t)m);
+    int32_t *tmp = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)m);     /* the row's three ranks, for max and mean */
+    if (!cell || !tmp) { free(cell); free(tmp); return -1; }
+    for (int64_t r = 0; r < nrows; r++) {
+        const int64_t o = r * m;
+        int32_t *rs = rnk_sup ? rnk_sup + o : tmp, *rp = rnk_pv ? rnk_pv + o : tmp + m, *ro = rnk_or ? rnk_or + o : tmp + 2 * m;
+        if (doSup) {
+            for (int64_t c = 0; c < m; c++) { cell[c].key = (uint64_t)support[o + c] ^ 0x8000000000000000ull; cell[c].idx = (uint32_t)c; }
+            rank_row(cell, m, rs, NULL);
+        }
+        if (doOr) {
+            for (int64_t c = 0; c < m; c++) { cell[c].key = rank_key_or(odds_ratio[o + c]); cell[c].idx = (uint32_t)c; }
+            rank_row(cell, m, ro, NULL);
+        }
+        if (doPv) {
+            for (int64_t c = 0; c < m; c++) { cell[c].key = pvalue_log[o + c] == 0.0 ? 0 : rank_bits(pvalue_log[o + c]); cell[c].idx = (uint32_t)c; }
+            rank_row(cell, m, rp, qvalue_log ? qvalue_log + o : NULL);
+        }
+        if (mm)
+            for (int64_t c = 0; c < m; c++) {
+                const int32_t a = rs[c], b = rp[c], d = ro[c];
+                if (max_rnk) max_rnk[o + c] = a > b ? (a > d ? a : d) : (b > d ? b : d);
+                if (mean_rnk) mean_rnk[o + c] = (double)(a + b + d) / 3.0;
+            }
+    }
+    free(cell); free(tmp);
+    return 0;
+}
+
 /* The handle flavours' batches (Python search_n / search_1, R search_nr / getOverlaps): on the host while the batch is
  * small and no engine is resident, otherwise on the engine, which is attached at the first batch that needs it -- the
  * moment the reference would do its first fseek/fread (src/igd_search.c:469-476); open_iGD reads the header only, like

@@ -27,6 +27,7 @@ def _i32(a):
 
 
 Enrichment = collections.namedtuple("Enrichment", "support usupport b c d pvalue_log odds_ratio clamped")
+EnrichmentRanks = collections.namedtuple("EnrichmentRanks", "qvalue_log rnk_sup rnk_pv rnk_or max_rnk mean_rnk")
 
 
 def _tables(a, b, c, d, what):
@@ -45,6 +46,36 @@ def fisher_host(a, b, c, d):
     if N.cli().igdc_fisher_host(a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, n, p.ctypes.data, o.ctypes.data) != 0:
         raise IgdError("fisher_host: a table has a negative entry or N >= 2^31")
     return p, o
+
+
+def _rank_inputs(support, pvalue_log, odds_ratio, what):
+    if pvalue_log is None and odds_ratio is None and isinstance(support, Enrichment):
+        support, pvalue_log, odds_ratio = support.support, support.pvalue_log, support.odds_ratio
+    if pvalue_log is None or odds_ratio is None:
+        raise IgdError("%s: give support, pvalue_log and odds_ratio, or one Enrichment" % what)
+    s = np.ascontiguousarray(support, dtype=np.int64)
+    p = np.ascontiguousarray(pvalue_log, dtype=np.float64)
+    o = np.ascontiguousarray(odds_ratio, dtype=np.float64)
+    if s.ndim != 2 or p.shape != s.shape or o.shape != s.shape:
+        raise IgdError("%s: support, pvalue_log and odds_ratio must be three two-dimensional arrays of one shape" % what)
+    return s, p, o
+
+
+def _rank_outputs(shape):
+    return EnrichmentRanks(np.empty(shape, np.float64), np.empty(shape, np.int32), np.empty(shape, np.int32),
+                           np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape, np.float64))
+
+
+def rank_host(support, pvalue_log=None, odds_ratio=None):
+    """Rank columns and Benjamini-Hochberg q-values of an enrichment table on the host (igdc_rank_host; no device is
+    touched): EnrichmentRanks as Database.enrichment_ranks() defines it, from three [nsets, ncols] arrays or one Enrichment."""
+    s, p, o = _rank_inputs(support, pvalue_log, odds_ratio, "rank_host")
+    r = _rank_outputs(s.shape)
+    if N.cli().igdc_rank_host(s.ctypes.data, p.ctypes.data, o.ctypes.data, s.shape[0], s.shape[1], r.qvalue_log.ctypes.data,
+                              r.rnk_sup.ctypes.data, r.rnk_pv.ctypes.data, r.rnk_or.ctypes.data, r.max_rnk.ctypes.data,
+                              r.mean_rnk.ctypes.data) != 0:
+        raise IgdError("rank_host: more than 2^20 columns, or a pvalue_log is negative or NaN")
+    return r
 
 
 class Database:
@@ -289,7 +320,7 @@ class Database:
         odds_ratio, clamped): per set k and file f the table a = support[k, f] (support_sets()), b = usupport[f] - a,
         c = |set k| - a, d = |universe| - a - b - c, where a negative b or d is then 0 and clamped[k] counts the cells of
         set k where that happened (the sets are not restricted to the universe); pvalue_log and odds_ratio as fisher()
-        on these tables.  Arrays are [nsets, nfiles], usupport [nfiles], clamped [nsets].  No q-values."""
+        on these tables.  Arrays are [nsets, nfiles], usupport [nfiles], clamped [nsets].  Ranks and q-values: enrichment_ranks()."""
         ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
         u_ichr, u_qs, u_qe = _i32(u_ichr), _i32(u_qs), _i32(u_qe)
         set_off = np.ascontiguousarray(set_off, dtype=np.int64)
@@ -317,6 +348,22 @@ class Database:
         c = nk - sup
         d = nu - sup - b - c
         return Enrichment(sup, usup, np.maximum(b, 0), c, np.maximum(d, 0), plog, odds, clamped[:nsets])
+
+    def enrichment_ranks(self, support, pvalue_log=None, odds_ratio=None):
+        """Rank columns and q-values of an enrichment table on the GPU (igd_hip_enrich_ranks): three [nsets, ncols] arrays,
+        or one Enrichment.  Per row (query set) and within it: rnk_sup, rnk_pv, rnk_or = 1 + the cells of the row with a
+        larger support / pvalue_log / odds_ratio (ties take the minimum rank; +inf is the largest odds ratio, NaN ranks
+        below every number), max_rnk their maximum, mean_rnk their mean (float64, not rounded), and qvalue_log = -log10 of
+        the Benjamini-Hochberg adjusted p over the row's ncols tests, computed in log10 (no underflow), >= +0.0.  The
+        number of columns is free (at most 2^20).  Returns EnrichmentRanks(qvalue_log, rnk_sup, rnk_pv, rnk_or, max_rnk,
+        mean_rnk), arrays of the inputs' shape.  The family is the row: no whole-table correction, no Storey q-value."""
+        s, p, o = _rank_inputs(support, pvalue_log, odds_ratio, "enrichment_ranks")
+        r = _rank_outputs(s.shape)
+        _chk(self._H.igd_hip_enrich_ranks(self.dev, s.ctypes.data, p.ctypes.data, o.ctypes.data, s.shape[0], s.shape[1],
+                                          r.qvalue_log.ctypes.data, r.rnk_sup.ctypes.data, r.rnk_pv.ctypes.data,
+                                          r.rnk_or.ctypes.data, r.max_rnk.ctypes.data, r.mean_rnk.ctypes.data),
+             "igd_hip_enrich_ranks")
+        return r
 
     def enrichment_files(self, paths, universe_path, v=0):
         """One query set per BED file and the universe from a BED file (read as `igd search -q` reads them): what

@@ -203,7 +203,7 @@ int igd_hip_fisher_tables(igd_hip_db *db, const int64_t *a, const int64_t *b, co
  * All are DEFINED by the call, not added to; odds_ratio and clamped may be NULL.  One igd_hip_support_sets call over the
  * nsets + 1 sets, then the cell kernel on the resident counts.  Blocking.  The argument checks of igd_hip_support_sets
  * apply; a set that with the universe holds 2^31 regions or more is IGD_HIP_ERR_ARG.  On an error nothing of the caller's
- * is written.  No q-values, one device. */
+ * is written.  One device.  Ranks and q-values of the table: igd_hip_enrich_ranks. */
 int igd_hip_enrich_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
                         int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
                         int32_t v, int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
@@ -217,6 +217,33 @@ int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t 
 /* Workgroups (of four waves, one cell per wave at a time) the cell kernel is launched with for ncell cells: a wave takes a
  * second cell only when ncell exceeds four times this number (tests). */
 int32_t igd_hip_fisher_grid(int64_t ncell);
+/* Rank columns and Benjamini-Hochberg q-values of an enrichment table (kernel igd_rank_rows): the columns of a LOLA table
+ * that igd_hip_enrich_sets leaves out.  The three inputs are matrices [nrows x ncols], row-major; a ROW is the ncols cells of
+ * one query set and the unit of all work: ranks are taken, and the m = ncols tests corrected, within a row.  ncols is the
+ * caller's and not tied to the database (at most IGD_HIP_RANK_MAX_COLS).
+ *     rank[f] = 1 + #{g : x[g] > x[f]}     int32; ties take the MINIMUM rank (R: rank(-x, ties.method = "min"))
+ *     rnk_sup ranks support (compared as 64-bit integers), rnk_pv pvalue_log, rnk_or odds_ratio, where +inf is the largest
+ *     value, NaN ranks below every number and all NaN of a row tie (rank 1 + the number of non-NaN cells)
+ *     max_rnk = the largest of the three (int32), mean_rnk = (rnk_sup + rnk_pv + rnk_or) / 3.0 (double, not rounded)
+ *     qvalue_log: with r[f] = #{g : pvalue_log[g] >= pvalue_log[f]} and adj[f] = pvalue_log[f] + (log10 r[f] - log10 m),
+ *                 qvalue_log[f] = max(+0.0, max{adj[g] : pvalue_log[g] <= pvalue_log[f]})
+ *                 = -log10 of the Benjamini-Hochberg adjusted p, min(1, min over j >= i of m p_(j) / j), computed in log10
+ *                 throughout: a pvalue_log of 4609.06 keeps a finite q.  It is a function of the cell's value alone (equal
+ *                 pvalue_log give bit-equal q), never negative and never -0.0.
+ * Any output may be NULL; an input may be NULL when no requested output needs it (max_rnk and mean_rnk need all three).
+ * Every requested output is DEFINED by the call (overwritten).  Blocking, on the engine's stream, in chunks of whole rows of
+ * at most 2^20 cells.  IGD_HIP_ERR_ARG, before anything of the caller's is written: a needed input is NULL, ncols >
+ * IGD_HIP_RANK_MAX_COLS, a pvalue_log that is needed is negative or NaN.  nrows == 0 or ncols == 0 is IGD_HIP_OK and writes nothing.
+ * The family is the row: no whole-table correction, no Storey q-value, no two-sided test. */
+#define IGD_HIP_RANK_MAX_COLS (1 << 20)
+int igd_hip_enrich_ranks(igd_hip_db *db, const int64_t *support, const double *pvalue_log, const double *odds_ratio,
+                         int64_t nrows, int64_t ncols, double *qvalue_log, int32_t *rnk_sup, int32_t *rnk_pv,
+                         int32_t *rnk_or, int32_t *max_rnk, double *mean_rnk);
+/* Workgroups (one row per workgroup at a time) the rank kernel is launched with for nrows rows: a workgroup takes a second
+ * row only when nrows exceeds this number; and the widest row whose sort the kernel keeps in LDS -- wider rows are sorted in
+ * a global workspace (tests). */
+int32_t igd_hip_rank_grid(int64_t nrows);
+int32_t igd_hip_rank_lds_cols(void);
 
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
