@@ -2,7 +2,7 @@
 path), behind the reference's own C ABI.  See DESIGN.md / INTEGRATION.md."""
 from ._native import NativeMissing, build  # noqa: F401
 
-__all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host"]
+__all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "restrict_host", "enrich_restricted_host"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -16,4 +16,10 @@ def __getattr__(name):
     if name == "rank_host":
         from .database import rank_host
         return rank_host
+    if name == "restrict_host":
+        from .database import restrict_host
+        return restrict_host
+    if name == "enrich_restricted_host":
+        from .database import enrich_restricted_host
+        return enrich_restricted_host
     raise AttributeError(name)

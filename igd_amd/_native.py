@@ -155,6 +155,16 @@ def hip():
         L.igd_hip_enrich_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # sets restricted to the universe: db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, bits, size
+        L.igd_hip_restrict_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        # ..., nu, v, rule, support, usupport, size, pvalue_log, odds_ratio, bits, nhit, unhit
+        L.igd_hip_enrich_restricted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+        L.igd_hip_restrict_grid.argtypes = [C.c_int64]
+        L.igd_hip_restrict_grid.restype = C.c_int32
         L.igd_hip_fisher_grid.argtypes = [C.c_int64]
         L.igd_hip_fisher_grid.restype = C.c_int32
         L.igd_hip_enrich_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
@@ -261,6 +271,14 @@ def _bind_core(L):
     # rnk_sup, rnk_pv, rnk_or, max_rnk, mean_rnk (may be NULL)
     L.igdc_rank_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # sets restricted to a universe on the host: ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, bits, size
+    L.igdc_restrict_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_void_p]
+    # db, map, the same, v, rule, support, usupport, size, pvalue_log, odds_ratio, bits, nhit, unhit
+    L.igdc_enrich_restricted_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
     return L
 
 

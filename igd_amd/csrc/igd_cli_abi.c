@@ -973,7 +973,7 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
  * accepted lines in the set and n_U in the universe:
  *     a = support of the set      b = u - a  (u = support of the universe)      c = n_k - a      d = n_U - a - b - c
  * a negative b or d is printed and tested as 0 and counted in "clamped cells" (a set region outside the universe, or a
- * universe region under several set regions: the sets are NOT restricted to the universe).  oddsRatio = (a d) / (b c), the
+ * universe region under several set regions; `-X` below restricts the sets to the universe first).  oddsRatio = (a d) / (b c), the
  * sample odds ratio; pValueLog = -log10 P(X >= a), X ~ Hypergeometric(a+b+c+d, a+b, a+c).  One row per file with a > 0.
  * Routing as `-u`, the universe's lines counted with the sets': at most igdc_host_limit() queries in all take
  * igdc_support_host and igdc_fisher_host, more ONE igd_hip_enrich_sets_nhit call on one device.
@@ -981,7 +981,14 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
  * with a = 0 included, by support, pValueLog and oddsRatio (ties take the minimum rank) -- maxRnk, meanRnk and qValueLog,
  * -log10 of the Benjamini-Hochberg adjusted p over the set's nFiles tests (include/igd_hip.h: igd_hip_enrich_ranks).  They come
  * from igdc_rank_host where the supports came from the host, otherwise from igd_hip_enrich_ranks.  Lines and their order are
- * those without `-R`. */
+ * those without `-R`.
+ * With `-X` every set is first replaced by the universe regions it overlaps (igd_hip_restrict_sets has the definition; LOLA's
+ * redefineUserSets): n_k becomes size[k] = the number of those regions, the supports are sums over them, every table is a
+ * partition of the universe (b = u - a, c = size[k] - a, d = n_U - u - c, nothing to clamp), and the last line reads
+ *     Restricted regions with a hit: <nhit> of <size> (from <n> query regions); universe regions: <n_U>
+ * Lines of the set or the universe whose contig the database does not know are dropped by the reader, as everywhere: they
+ * are in no restricted set and not in n_U.  Routing as without `-X`: the host route is igdc_enrich_restricted_host, the engine
+ * route ONE igd_hip_enrich_restricted call on the first device.  `-X` without `-U` is refused. */
 /* b, c, d and the clamp count of every cell from the definitions (printed on both routes; the host route tests them) */
 static void enrich_tables(const int64_t *rows, const int64_t *urow, const igdc_queries *q, int64_t nU, int32_t n, int32_t nfiles,
                           int64_t *tb, int64_t *tc, int64_t *td, int64_t *clamped)
@@ -997,7 +1004,38 @@ static void enrich_tables(const int64_t *rows, const int64_t *urow, const igdc_q
     }
 }
 
-static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v, int setLines, int ranks)
+/* the sets' accepted lines, concatenated, and their offsets (free the four) */
+static void enrich_cat(const igdc_queries *q, int32_t n, int64_t nq, int32_t **ichr, int32_t **qs, int32_t **qe, int64_t **off)
+{
+    *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    (*off)[0] = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (q[k].n) {
+            memcpy(*ichr + (*off)[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(*qs + (*off)[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(*qe + (*off)[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+        }
+        (*off)[k + 1] = (*off)[k] + q[k].n;
+    }
+}
+
+/* -X: b, c, d of every cell from the restricted supports and sizes; nothing is clamped */
+static void enrich_tables_restricted(const int64_t *rows, const int64_t *urow, const int64_t *size, int64_t nU, int32_t n, int32_t nfiles,
+                                     int64_t *tb, int64_t *tc, int64_t *td)
+{
+    for (int32_t k = 0; k < n; k++)
+        for (int32_t f = 0; f < nfiles; f++) {
+            const size_t i = (size_t)k * (size_t)nfiles + (size_t)f;
+            tb[i] = urow[f] - rows[i];
+            tc[i] = size[k] - rows[i];
+            td[i] = nU - urow[f] - tc[i];
+        }
+}
+
+static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v, int setLines, int ranks, int restricted)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles;
@@ -1020,7 +1058,7 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
     int64_t *rows = (int64_t *)calloc(cells + 1, sizeof(int64_t)), *urow = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
     int64_t *nhit = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t)), unhit = 0;
     int64_t *tb = (int64_t *)calloc(3 * cells + 1, sizeof(int64_t)), *tc = tb + cells, *td = tc + cells;
-    int64_t *clamped = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t));
+    int64_t *clamped = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t)), *size = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t));
     double *plog = (double *)calloc(2 * cells + 1, sizeof(double)), *odds = plog + cells;
     /* -R: q and mean, then the four int32 columns */
     double *qlog = ranks ? (double *)calloc(4 * cells + 1, sizeof(double)) : NULL, *rmean = ranks ? qlog + cells : NULL;
@@ -1028,7 +1066,25 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
     int32_t *rmax = ranks ? ror + cells : NULL;
     int onHost = 0;
     igdc_map *hm = host_map_lim(nq + uq.n, igdc_host_limit());
-    if (hm) {
+    if (hm && restricted) {
+        int32_t *ichr, *qs, *qe;
+        int64_t *off;
+        double t0 = now_s();
+        enrich_cat(q, n, nq, &ichr, &qs, &qe, &off);
+        onHost = igdc_enrich_restricted_host(g_core, hm, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, size, plog,
+                                             odds, NULL, nhit, &unhit) == 0;
+        igdc_map_close(hm);
+        free(ichr); free(qs); free(qe); free(off);
+        if (onHost) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
+        if (onHost && ranks) onHost = igdc_rank_host(rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean) == 0;
+        if (onHost) phase("restricted sets, membership of the universe and Fisher tests on the host (small files)", &t0);
+        else {                                        /* (a read error: the engine reads the file its own way) */
+            memset(rows, 0, sizeof(int64_t) * cells);
+            memset(urow, 0, sizeof(int64_t) * (size_t)nfiles);
+            memset(nhit, 0, sizeof(int64_t) * (size_t)n);
+            unhit = 0;
+        }
+    } else if (hm) {
         double t0 = now_s();
         onHost = igdc_support_host(g_core, hm, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, urow, &unhit) == 0;
         for (int32_t k = 0; k < n && onHost; k++)
@@ -1050,26 +1106,22 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
         }
     }
     if (!onHost) {
-        int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-        int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-        int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
-        off[0] = 0;
-        for (int32_t k = 0; k < n; k++) {
-            if (q[k].n) {
-                memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-                memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-                memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-            }
-            off[k + 1] = off[k] + q[k].n;
-        }
+        int32_t *ichr, *qs, *qe;
+        int64_t *off;
+        enrich_cat(q, n, nq, &ichr, &qs, &qe, &off);
         igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
         double t0 = now_s();
         if (dev) {
-            const int rc = igd_hip_enrich_sets_nhit(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, plog, odds,
-                                                    NULL, nhit, &unhit);
+            const int rc = restricted
+                               ? igd_hip_enrich_restricted(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, size,
+                                                           plog, odds, NULL, nhit, &unhit)
+                               : igd_hip_enrich_sets_nhit(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, plog,
+                                                          odds, NULL, nhit, &unhit);
             if (rc != IGD_HIP_OK) engine_failed("enrichment", rc);
+            else if (restricted) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
             else enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
-            phase("enrichment of the query sets (H2D + support kernel + Fisher kernel + D2H)", &t0);
+            phase(restricted ? "enrichment of the restricted sets (join + membership of the universe + gather + Fisher kernel)"
+                             : "enrichment of the query sets (H2D + support kernel + Fisher kernel + D2H)", &t0);
             if (ranks && rc == IGD_HIP_OK) {
                 const int rr = igd_hip_enrich_ranks(dev, rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean);
                 if (rr != IGD_HIP_OK) engine_failed("enrichment ranks", rr);
@@ -1090,12 +1142,16 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
             if (ranks) printf("\t%d\t%d\t%d\t%d\t%.2f\t%.4f", (int)rsup[i], (int)rpv[i], (int)ror[i], (int)rmax[i], rmean[i], qlog[i]);
             printf("\n");
         }
-        printf("Query regions with a hit: %lld of %lld; universe regions: %lld; clamped cells: %lld\n", (long long)nhit[k],
-               (long long)q[k].n, (long long)uq.n, (long long)clamped[k]);
+        if (restricted)
+            printf("Restricted regions with a hit: %lld of %lld (from %lld query regions); universe regions: %lld\n", (long long)nhit[k],
+                   (long long)size[k], (long long)q[k].n, (long long)uq.n);
+        else
+            printf("Query regions with a hit: %lld of %lld; universe regions: %lld; clamped cells: %lld\n", (long long)nhit[k],
+                   (long long)q[k].n, (long long)uq.n, (long long)clamped[k]);
     }
     for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
     igdc_queries_free(&uq);
-    free(q); free(rows); free(urow); free(nhit); free(tb); free(clamped); free(plog); free(qlog);
+    free(q); free(rows); free(urow); free(nhit); free(tb); free(clamped); free(size); free(plog); free(qlog);
 }
 
 /* ------------------------------- `igd search -q F -w` / `-Q <list> -w` ----------------- */
@@ -1236,7 +1292,9 @@ static int usage_search(void)
             "    -w                         with -q or -Q: per query region, the datasets it overlaps (membership)\n"
             "    -U <universe file>         with -q or -Q: enrichment of each query set against the universe, per dataset the\n"
             "                               2x2 table of the supports, the sample odds ratio and -log10 p of a one-sided\n"
-            "                               Fisher exact test (the sets are not restricted to the universe)\n"
+            "                               Fisher exact test (the sets as given; -X restricts them to the universe)\n"
+            "    -X                         with -U: each set is first replaced by the universe regions it overlaps, so every\n"
+            "                               table is a partition of the universe (number of regions of the set = their number)\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -1278,7 +1336,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
 
     int32_t v = 0, qs = 1, qe = 2;
-    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
+    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, restricted = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -1315,6 +1373,8 @@ int igd_search(int argc, char **argv)                                        /* 
             uniName = argv[i + 1];
         } else if (strcmp(a, "-R") == 0) {            /* (not the reference's: rank and q-value columns of -U, see enrich_files) */
             ranks = 1;
+        } else if (strcmp(a, "-X") == 0) {            /* (not the reference's: -U on the sets restricted to the universe, see enrich_files) */
+            restricted = 1;
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
@@ -1325,15 +1385,18 @@ int igd_search(int argc, char **argv)                                        /* 
     if (ranks && !uniName) {
         printf("Not supported: -R without -U\n");
         return EX_OK;
+    } else if (restricted && !uniName) {
+        printf("Not supported: -X without -U\n");
+        return EX_OK;
     } else if (uniName && (bp || memb || full || other)) {
         printf("Not supported: -U together with -b, -w, -f, -m, -s or -r\n");
         return EX_OK;
     } else if (uniName && mode == 1) {
-        enrich_files(&qfName, 1, uniName, v, 0, ranks);
+        enrich_files(&qfName, 1, uniName, v, 0, ranks, restricted);
     } else if (uniName && listName) {
         int32_t n = 0;
         char **paths = read_list(listName, &n);
-        if (n >= 0) enrich_files(paths, n, uniName, v, 1, ranks);
+        if (n >= 0) enrich_files(paths, n, uniName, v, 1, ranks, restricted);
         for (int32_t k = 0; k < n; k++) free(paths[k]);
         free(paths);
     } else if (full) {                                                        /* :975-995 */

@@ -142,6 +142,20 @@ int igdc_fisher_host(const int64_t *a, const int64_t *b, const int64_t *c, const
  * a pvalue_log that is negative or NaN. */
 int igdc_rank_host(const int64_t *support, const double *pvalue_log, const double *odds_ratio, int64_t nrows, int64_t ncols,
                    double *qvalue_log, int32_t *rnk_sup, int32_t *rnk_pv, int32_t *rnk_or, int32_t *max_rnk, double *mean_rnk);
+/* Query sets restricted to a universe (what igd_hip_restrict_sets computes; include/igd_hip.h has the definitions): row k of
+ * bits (ceil(nu / 32) uint32 words; universe region u, the caller's numbering, = bit u & 31 of word u >> 5) holds the universe
+ * regions that some region of set k overlaps, size[k] their number.  Needs no database.  Outputs are OVERWRITTEN.  0 on
+ * success; -1, the outputs untouched, for a bad set_off, a missing array or nu + 1 >= 2^31. */
+int igdc_restrict_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                       const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, uint32_t *bits, int64_t *size);
+/* Enrichment of the restricted sets (what igd_hip_enrich_restricted computes): igdc_restrict_host, igdc_membership_host over
+ * the universe, the gather over the member rows of each set's bits, igdc_fisher_host on a = support, b = usupport - a,
+ * c = size - a, d = nu - usupport - c.  Outputs are OVERWRITTEN; odds_ratio, bits, nhit and unhit may be NULL.  0 on success;
+ * -1 for a bad argument (nothing written) or when a tile could not be read (outputs undefined). */
+int igdc_enrich_restricted_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                                const int64_t *set_off, int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe,
+                                int64_t nu, int32_t v, int rule, int64_t *support, int64_t *usupport, int64_t *size, double *pvalue_log,
+                                double *odds_ratio, uint32_t *bits, int64_t *nhit, int64_t *unhit);
 /* `-f` (rule NEST, the reference's order): qoff[0..nq] offsets, *out malloc'd (free()), entries as igd_hip_enumerate's */
 int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                         int64_t nq, int64_t *qoff, igd_hip_hit **out, int64_t *total);

@@ -53,6 +53,7 @@
 #include <string.h>
 #include <limits.h>
 #include <vector>
+#include <algorithm>
 #include <thread>
 #include <mutex>
 #include <time.h>
@@ -313,6 +314,11 @@ struct igd_hip_db {
     // igd_hip_enrich_ranks (host_rank.hpp) uses the same words for its chunk of rows
     int64_t *d_fisher;
     int64_t fisherCap;
+    // igd_hip_restrict_sets / igd_hip_enrich_restricted (host_restrict.hpp): the ordered universe (ustart, uend, pmax, perm), the
+    // contig table and set offsets, the bit rows of one chunk of sets and their popcounts
+    int32_t *d_rsUni, *d_rsTab, *d_rsSize;
+    unsigned *d_rsBits;
+    int64_t rsUniCap, rsTabCap, rsSizeCap, rsBitsCap;
     hipStream_t stream;
     // profiling
     std::vector<hipEvent_t> ev;   // 4 per launch: pipeline start, scan start, scan stop, pipeline stop
@@ -344,6 +350,7 @@ struct igd_hip_db {
 #include "engine/member_dev.hpp"      // igd_member_rows: the same walk, one bit row per query: which files it overlaps
 #include "engine/fisher_dev.hpp"      // igd_fisher_cells: one wave per 2x2 table, the hypergeometric tail in log space
 #include "engine/rank_dev.hpp"        // igd_rank_rows: one workgroup per table row, bitonic sort per column: ranks and BH q-values
+#include "engine/restrict_dev.hpp"    // igd_restrict_bits, igd_bits_support: sets restricted to a universe -- the interval join and the gather over member rows
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -356,6 +363,7 @@ struct igd_hip_db {
 #include "engine/host_member.hpp"     // igd_hip_membership / _dev: chunks of queries within a row budget, one launch each
 #include "engine/host_enrich.hpp"     // igd_hip_fisher_tables / igd_hip_enrich_sets: chunks of cells, one launch each
 #include "engine/host_rank.hpp"       // igd_hip_enrich_ranks: chunks of whole rows, one launch each
+#include "engine/host_restrict.hpp"   // igd_hip_restrict_sets / igd_hip_enrich_restricted: chunks of sets x chunks of the universe
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

@@ -200,6 +200,37 @@ int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t 
               : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_restrict_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                          int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, uint32_t *bits,
+                          int64_t *size)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, const int32_t *,
+                        const int32_t *, const int32_t *, int64_t, uint32_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_restrict_sets");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, bits, size) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_enrich_restricted(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                              int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, int32_t v, int rule,
+                              int64_t *support, int64_t *usupport, int64_t *size, double *pvalue_log, double *odds_ratio, uint32_t *bits,
+                              int64_t *nhit, int64_t *unhit)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, const int32_t *,
+                        const int32_t *, const int32_t *, int64_t, int32_t, int, int64_t *, int64_t *, int64_t *, double *, double *,
+                        uint32_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_enrich_restricted");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, v, rule, support, usupport, size, pvalue_log, odds_ratio,
+                   bits, nhit, unhit)
+              : IGD_HIP_ERR_DEVICE;
+}
+
+int32_t igd_hip_restrict_grid(int64_t nregions)
+{
+    typedef int32_t (*fn_t)(int64_t);
+    RESOLVE(fn_t, "igd_hip_restrict_grid");
+    return fn ? fn(nregions) : 0;
+}
+
 int igd_hip_enrich_ranks(igd_hip_db *db, const int64_t *support, const double *pvalue_log, const double *odds_ratio, int64_t nrows,
                          int64_t ncols, double *qvalue_log, int32_t *rnk_sup, int32_t *rnk_pv, int32_t *rnk_or, int32_t *max_rnk,
                          double *mean_rnk)

@@ -703,6 +703,138 @@ int igdc_rank_host(const int64_t *support, const double *pvalue_log, const doubl
     return 0;
 }
 
+/* Query sets restricted to the universe on the host: what igd_restrict_bits (engine/restrict_dev.hpp) computes, by the same
+ * scheme -- the universe regions with ichr >= 0 ordered by (ichr, start) unless they come that way, per contig the prefix
+ * maximum of the ends, per set region a bisection for the first start >= qe and a walk back while the prefix maximum is above
+ * qs -- on the calling thread.  The restricted sets of `-U -X` when the supports are counted on the host. */
+typedef struct { uint64_t key; int32_t idx; } restrict_ent;
+static int restrict_ent_cmp(const void *x, const void *y)
+{
+    const restrict_ent *a = (const restrict_ent *)x, *b = (const restrict_ent *)y;
+    if (a->key != b->key) return a->key < b->key ? -1 : 1;
+    return a->idx < b->idx ? -1 : a->idx > b->idx;
+}
+static int restrict_args_bad(const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                             const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu)
+{
+    if (nsets < 0 || nsets == INT32_MAX || nu < 0 || nu + 1 >= ((int64_t)1 << 31) || (nu > 0 && (!u_ichr || !u_qs || !u_qe)) ||
+        (nsets > 0 && (!set_off || set_off[0] != 0)))
+        return 1;
+    for (int32_t k = 0; k < nsets; k++)
+        if (set_off[k + 1] < set_off[k]) return 1;
+    return nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe);
+}
+
+int igdc_restrict_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                       const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, uint32_t *bits, int64_t *size)
+{
+    if (restrict_args_bad(ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu)) return -1;
+    const int64_t nUW = (nu + 31) / 32;
+    if (nsets > 0 && (!size || (nUW > 0 && !bits))) return -1;
+    if (nsets == 0) return 0;
+    /* the universe regions with a contig, by (ichr, start), ties in the caller's order */
+    restrict_ent *ent = (restrict_ent *)malloc(sizeof(restrict_ent) * (size_t)(nu + 1));
+    int32_t *us = (int32_t *)malloc(sizeof(int32_t) * 5 * (size_t)(nu + 1));
+    if (!ent || !us) { free(ent); free(us); return -1; }
+    int32_t *ue = us + nu, *pm = ue + nu, *cval = pm + nu, *cbeg = cval + nu;      /* (cbeg: at most nv + 1 <= nu + 1 entries) */
+    int64_t nv = 0;
+    int sorted = 1;
+    for (int64_t u = 0; u < nu; u++) {
+        if (u_ichr[u] < 0) continue;
+        ent[nv].key = ((uint64_t)(uint32_t)u_ichr[u] << 32) | (uint64_t)((uint32_t)u_qs[u] ^ 0x80000000u);
+        ent[nv].idx = (int32_t)u;
+        if (nv > 0 && ent[nv].key < ent[nv - 1].key) sorted = 0;
+        nv++;
+    }
+    if (!sorted) qsort(ent, (size_t)nv, sizeof *ent, restrict_ent_cmp);
+    int32_t nc = 0;
+    for (int64_t p = 0; p < nv; p++) {
+        const int32_t u = ent[p].idx;
+        const int first = p == 0 || u_ichr[ent[p - 1].idx] != u_ichr[u];
+        if (first) { cval[nc] = u_ichr[u]; cbeg[nc] = (int32_t)p; nc++; }
+        us[p] = u_qs[u]; ue[p] = u_qe[u];
+        pm[p] = first || u_qe[u] > pm[p - 1] ? u_qe[u] : pm[p - 1];
+    }
+    cbeg[nc] = (int32_t)nv;
+    if (nUW) memset(bits, 0, sizeof(uint32_t) * (size_t)nsets * (size_t)nUW);
+    for (int32_t k = 0; k < nsets; k++) {
+        uint32_t *row = bits + (size_t)k * (size_t)nUW;
+        int64_t n = 0;
+        for (int64_t i = set_off[k]; i < set_off[k + 1]; i++) {
+            const int32_t c = ichr[i], s = qs[i], e = qe[i];
+            if (c < 0) continue;
+            int32_t lo = 0, hi = nc;
+            while (lo < hi) { const int32_t m = (lo + hi) >> 1; if (cval[m] < c) lo = m + 1; else hi = m; }
+            if (lo >= nc || cval[lo] != c) continue;
+            const int32_t s0 = cbeg[lo];
+            int32_t a = s0, b = cbeg[lo + 1];
+            while (a < b) { const int32_t m = a + ((b - a) >> 1); if (us[m] < e) a = m + 1; else b = m; }
+            for (int32_t p = a - 1; p >= s0 && pm[p] > s; p--)
+                if (ue[p] > s) {
+                    const int32_t u = ent[p].idx;
+                    const uint32_t bit = 1u << (u & 31);
+                    if (!(row[u >> 5] & bit)) { row[u >> 5] |= bit; n++; }
+                }
+        }
+        size[k] = n;
+    }
+    free(ent); free(us);
+    return 0;
+}
+
+/* Enrichment of the restricted sets on the host: igdc_restrict_host, igdc_membership_host over the universe (in the caller's
+ * order), the gather support[k][f] = sum over u in R_k of member[u][f], then igdc_fisher_host on a = support, b = usupport - a,
+ * c = size - a, d = nu - usupport - c -- what igd_hip_enrich_restricted computes (include/igd_hip.h has the definitions).
+ * Outputs are OVERWRITTEN; odds_ratio, bits, nhit and unhit may be NULL.  0 on success; -1 for a bad argument (nothing written)
+ * or when a tile could not be read (outputs undefined). */
+int igdc_enrich_restricted_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                                const int64_t *set_off, int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe,
+                                int64_t nu, int32_t v, int rule, int64_t *support, int64_t *usupport, int64_t *size, double *pvalue_log,
+                                double *odds_ratio, uint32_t *bits, int64_t *nhit, int64_t *unhit)
+{
+    if (!db || !m || restrict_args_bad(ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu)) return -1;
+    const int64_t nF = db->nFiles, nW = (nF + 31) / 32, nUW = (nu + 31) / 32;
+    const size_t cells = (size_t)nsets * (size_t)nF;
+    if ((nF > 0 && !usupport) || (nsets > 0 && (!size || (nF > 0 && (!support || !pvalue_log))))) return -1;
+    uint32_t *own = bits ? NULL : (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)nsets * (size_t)nUW + 1));
+    uint32_t *rb = bits ? bits : own;
+    uint32_t *member = (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)nu * (size_t)nW + 1));
+    int32_t *nfh = (int32_t *)malloc(sizeof(int32_t) * ((size_t)nu + 1));
+    int64_t *tb = (int64_t *)malloc(sizeof(int64_t) * (3 * cells + 1)), *tc = tb ? tb + cells : NULL, *td = tb ? tc + cells : NULL;
+    int rc = rb && member && nfh && tb ? 0 : -1;
+    int64_t uh = 0;
+    if (rc == 0) rc = igdc_restrict_host(ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, rb, size);
+    if (rc == 0 && nu > 0) rc = igdc_membership_host(db, m, u_ichr, u_qs, u_qe, nu, v, rule, member, nfh, &uh);
+    if (rc == 0) {
+        for (int64_t f = 0; f < nF; f++) usupport[f] = 0;
+        for (int64_t u = 0; u < nu; u++)
+            for (int64_t w = 0; w < nW; w++)
+                for (uint32_t x = member[u * nW + w]; x; x &= x - 1) usupport[w * 32 + __builtin_ctz(x)]++;
+        if (cells) memset(support, 0, sizeof(int64_t) * cells);
+        for (int32_t k = 0; k < nsets; k++) {
+            int64_t *row = support + (size_t)k * (size_t)nF, h = 0;
+            for (int64_t uw = 0; uw < nUW; uw++)
+                for (uint32_t y = rb[(size_t)k * (size_t)nUW + (size_t)uw]; y; y &= y - 1) {
+                    const int64_t u = uw * 32 + __builtin_ctz(y);
+                    h += nfh[u] > 0;
+                    for (int64_t w = 0; w < nW; w++)
+                        for (uint32_t x = member[u * nW + w]; x; x &= x - 1) row[w * 32 + __builtin_ctz(x)]++;
+                }
+            if (nhit) nhit[k] = h;
+            for (int64_t f = 0; f < nF; f++) {
+                const size_t i = (size_t)k * (size_t)nF + (size_t)f;
+                tb[i] = usupport[f] - row[f];
+                tc[i] = size[k] - row[f];
+                td[i] = nu - usupport[f] - tc[i];
+            }
+        }
+        if (unhit) *unhit = uh;
+        if (cells) rc = igdc_fisher_host(support, tb, tc, td, (int64_t)cells, pvalue_log, odds_ratio);
+    }
+    free(own); free(member); free(nfh); free(tb);
+    return rc;
+}
+
 /* The handle flavours' batches (Python search_n / search_1, R search_nr / getOverlaps): on the host while the batch is
  * small and no engine is resident, otherwise on the engine, which is attached at the first batch that needs it -- the
  * moment the reference would do its first fseek/fread (src/igd_search.c:469-476); open_iGD reads the header only, like

@@ -27,6 +27,7 @@ def _i32(a):
 
 
 Enrichment = collections.namedtuple("Enrichment", "support usupport b c d pvalue_log odds_ratio clamped")
+RestrictedEnrichment = collections.namedtuple("RestrictedEnrichment", "support usupport b c d pvalue_log odds_ratio size bits")
 EnrichmentRanks = collections.namedtuple("EnrichmentRanks", "qvalue_log rnk_sup rnk_pv rnk_or max_rnk mean_rnk")
 
 
@@ -49,10 +50,10 @@ def fisher_host(a, b, c, d):
 
 
 def _rank_inputs(support, pvalue_log, odds_ratio, what):
-    if pvalue_log is None and odds_ratio is None and isinstance(support, Enrichment):
+    if pvalue_log is None and odds_ratio is None and isinstance(support, (Enrichment, RestrictedEnrichment)):
         support, pvalue_log, odds_ratio = support.support, support.pvalue_log, support.odds_ratio
     if pvalue_log is None or odds_ratio is None:
-        raise IgdError("%s: give support, pvalue_log and odds_ratio, or one Enrichment" % what)
+        raise IgdError("%s: give support, pvalue_log and odds_ratio, or one Enrichment / RestrictedEnrichment" % what)
     s = np.ascontiguousarray(support, dtype=np.int64)
     p = np.ascontiguousarray(pvalue_log, dtype=np.float64)
     o = np.ascontiguousarray(odds_ratio, dtype=np.float64)
@@ -76,6 +77,85 @@ def rank_host(support, pvalue_log=None, odds_ratio=None):
                               r.mean_rnk.ctypes.data) != 0:
         raise IgdError("rank_host: more than 2^20 columns, or a pvalue_log is negative or NaN")
     return r
+
+
+def _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, what):
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    u_ichr, u_qs, u_qe = _i32(u_ichr), _i32(u_qs), _i32(u_qe)
+    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+    nsets, nu = len(set_off) - 1, len(u_qs)
+    if nsets < 0:
+        raise IgdError("%s: set_off needs nsets + 1 entries" % what)
+    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs) or len(u_ichr) != nu or len(u_qe) != nu:
+        raise IgdError("%s: set_off[-1] = %d, but %d / %d / %d queries and %d / %d / %d universe regions given"
+                       % (what, set_off[-1], len(ichr), len(qs), len(qe), len(u_ichr), nu, len(u_qe)))
+    return ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu
+
+
+def _restricted_result(sup, usup, size, plog, odds, bits, nu):
+    b = usup[None, :] - sup
+    c = size[:, None] - sup
+    d = nu - usup[None, :] - c
+    return RestrictedEnrichment(sup, usup, b, c, d, plog, odds, size, bits)
+
+
+def restrict_host(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe):
+    """Query sets restricted to a universe on the host (igdc_restrict_host; no device and no database is touched): (bits
+    uint32[nsets, ceil(nu / 32)], size int64[nsets]) as Database.restrict_sets() defines them."""
+    ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, "restrict_host")
+    bits, size = np.empty((nsets, (nu + 31) // 32), np.uint32), np.empty(max(nsets, 1), np.int64)
+    if N.cli().igdc_restrict_host(ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets, u_ichr.ctypes.data,
+                                  u_qs.ctypes.data, u_qe.ctypes.data, nu, bits.ctypes.data if bits.size else None,
+                                  size.ctypes.data) != 0:
+        raise IgdError("restrict_host: set_off is not monotone from 0, or the universe holds 2^31 - 1 regions or more")
+    return bits, size[:nsets]
+
+
+def enrich_restricted_host(igd_path, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, v=0, rule=None, value_filter=None, with_nhit=False):
+    """Enrichment of the restricted sets on the host (igdc_enrich_restricted_host: pread on the .igd; no device is touched):
+    RestrictedEnrichment as Database.enrichment_restricted() defines it; with_nhit adds (nhit int64[nsets], unhit)."""
+    ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe,
+                                                                          "enrich_restricted_host")
+    L = N.cli()
+    core = L.igdc_open(igd_path.encode())
+    if not core:
+        raise IgdError("cannot read .igd header of %s" % igd_path)
+    fd = -1
+    m = None
+    try:
+        tsv = L.igdc_index_path(igd_path.encode())
+        rc = L.igdc_load_index(core, C.cast(tsv, C.c_char_p))
+        N.free(tsv)
+        if rc != 0:
+            raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
+        nf, gtype = core.contents.nFiles, core.contents.gType
+        if rule is None:
+            rule, vf = Database.cli_dispatch(gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        fd = os.open(igd_path, os.O_RDONLY)
+        m = L.igdc_map_open(core, fd)
+        if not m:
+            raise IgdError("cannot map %s" % igd_path)
+        sup, usup = np.empty((nsets, nf), np.int64), np.empty(max(nf, 1), np.int64)
+        plog, odds = np.empty((nsets, nf), np.float64), np.empty((nsets, nf), np.float64)
+        size, nhit, unhit = np.empty(max(nsets, 1), np.int64), np.empty(max(nsets, 1), np.int64), C.c_int64(0)
+        bits = np.empty((nsets, (nu + 31) // 32), np.uint32)
+        if L.igdc_enrich_restricted_host(core, m, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
+                                         u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu, vf, rule,
+                                         sup.ctypes.data if sup.size else None, usup.ctypes.data,
+                                         size.ctypes.data, plog.ctypes.data if plog.size else None,
+                                         odds.ctypes.data if odds.size else None, bits.ctypes.data if bits.size else None,
+                                         nhit.ctypes.data, C.byref(unhit)) != 0:
+            raise IgdError("enrich_restricted_host: bad set_off or universe, or a tile of %s could not be read" % igd_path)
+    finally:
+        if m:
+            L.igdc_map_close(m)
+        if fd >= 0:
+            os.close(fd)
+        L.igdc_close(core)
+    res = _restricted_result(sup, usup[:nf], size[:nsets], plog, odds, bits, nu)
+    return (res, nhit[:nsets], unhit.value) if with_nhit else res
 
 
 class Database:
@@ -319,7 +399,7 @@ class Database:
         search_sets(); the universe is one more set of regions.  Returns Enrichment(support, usupport, b, c, d, pvalue_log,
         odds_ratio, clamped): per set k and file f the table a = support[k, f] (support_sets()), b = usupport[f] - a,
         c = |set k| - a, d = |universe| - a - b - c, where a negative b or d is then 0 and clamped[k] counts the cells of
-        set k where that happened (the sets are not restricted to the universe); pvalue_log and odds_ratio as fisher()
+        set k where that happened (enrichment_restricted() restricts the sets to the universe first); pvalue_log and odds_ratio as fisher()
         on these tables.  Arrays are [nsets, nfiles], usupport [nfiles], clamped [nsets].  Ranks and q-values: enrichment_ranks()."""
         ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
         u_ichr, u_qs, u_qe = _i32(u_ichr), _i32(u_qs), _i32(u_qe)
@@ -349,9 +429,66 @@ class Database:
         d = nu - sup - b - c
         return Enrichment(sup, usup, np.maximum(b, 0), c, np.maximum(d, 0), plog, odds, clamped[:nsets])
 
+    def restrict_sets(self, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe):
+        """Query sets restricted to a universe (igd_hip_restrict_sets; LOLA's redefineUserSets).  Sets as search_sets(); the
+        universe in any order.  Returns (bits uint32[nsets, ceil(nu / 32)], size int64[nsets]): universe region u (the
+        caller's numbering) is bit u & 31 of bits[k, u >> 5] and is set iff some region q of set k has the same contig number
+        >= 0, u_qs[u] < qe[q] and u_qe[u] > qs[q] -- the plain predicate: empty and inverted regions are not special-cased,
+        regions that touch do not overlap, a contig number < 0 overlaps nothing.  size[k] = the set bits of row k."""
+        ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, "restrict_sets")
+        bits, size = np.empty((nsets, (nu + 31) // 32), np.uint32), np.empty(max(nsets, 1), np.int64)
+        _chk(self._H.igd_hip_restrict_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
+                                           u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu,
+                                           bits.ctypes.data if bits.size else None, size.ctypes.data), "igd_hip_restrict_sets")
+        return bits, size[:nsets]
+
+    def enrichment_restricted(self, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, v=0, rule=None, value_filter=None, with_nhit=False):
+        """Region-set enrichment with every set first restricted to the universe (igd_hip_enrich_restricted): set k is replaced
+        by R_k, the universe regions it overlaps (restrict_sets()), so each table is a true partition of the universe.  Returns
+        RestrictedEnrichment(support, usupport, b, c, d, pvalue_log, odds_ratio, size, bits): with member = membership() of the
+        universe regions, usupport[f] = its column sums, support[k, f] = the sum over R_k, a = support, b = usupport - a,
+        c = size[k] - a, d = |universe| - usupport - c, all >= 0 (nothing is clamped); pvalue_log and odds_ratio as fisher() on
+        these tables -- bit for bit what enrichment_sets() returns for R_k given as explicit regions.  Regions whose contig
+        number is < 0 (read_queries() drops lines on contigs the database does not know) are in no restricted set.
+        with_nhit adds (nhit int64[nsets], unhit): the regions of R_k / of the universe with a hit in any file."""
+        ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe,
+                                                                              "enrichment_restricted")
+        nf = self.nfiles
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        sup, usup = np.empty((nsets, nf), np.int64), np.empty(max(nf, 1), np.int64)
+        plog, odds = np.empty((nsets, nf), np.float64), np.empty((nsets, nf), np.float64)
+        size, nhit, unhit = np.empty(max(nsets, 1), np.int64), np.empty(max(nsets, 1), np.int64), C.c_int64(0)
+        bits = np.empty((nsets, (nu + 31) // 32), np.uint32)
+        _chk(self._H.igd_hip_enrich_restricted(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
+                                               u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu, vf, rule,
+                                               sup.ctypes.data if sup.size else None, usup.ctypes.data, size.ctypes.data,
+                                               plog.ctypes.data if plog.size else None, odds.ctypes.data if odds.size else None,
+                                               bits.ctypes.data if bits.size else None, nhit.ctypes.data, C.byref(unhit)),
+             "igd_hip_enrich_restricted")
+        res = _restricted_result(sup, usup[:nf], size[:nsets], plog, odds, bits, nu)
+        return (res, nhit[:nsets], unhit.value) if with_nhit else res
+
+    def enrichment_restricted_files(self, paths, universe_path, v=0):
+        """One query set per BED file and the universe from a BED file (read as `igd search -q` reads them): what
+        `igd search -Q list -U universe -X` prints, as enrichment_restricted() returns it."""
+        sets = [self.read_queries(p) for p in paths]
+        uni = self.read_queries(universe_path)
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.enrichment_restricted(cat[0], cat[1], cat[2], set_off, uni[0], uni[1], uni[2], v)
+
+    @staticmethod
+    def unpack_restricted(bits, nu):
+        """bool[nsets, nu] from the rows of restrict_sets() / RestrictedEnrichment.bits"""
+        return Database.unpack_membership(bits, nu)
+
     def enrichment_ranks(self, support, pvalue_log=None, odds_ratio=None):
         """Rank columns and q-values of an enrichment table on the GPU (igd_hip_enrich_ranks): three [nsets, ncols] arrays,
-        or one Enrichment.  Per row (query set) and within it: rnk_sup, rnk_pv, rnk_or = 1 + the cells of the row with a
+        or one Enrichment / RestrictedEnrichment.  Per row (query set) and within it: rnk_sup, rnk_pv, rnk_or = 1 + the cells of the row with a
         larger support / pvalue_log / odds_ratio (ties take the minimum rank; +inf is the largest odds ratio, NaN ranks
         below every number), max_rnk their maximum, mean_rnk their mean (float64, not rounded), and qvalue_log = -log10 of
         the Benjamini-Hochberg adjusted p over the row's ncols tests, computed in log10 (no underflow), >= +0.0.  The

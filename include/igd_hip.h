@@ -196,7 +196,8 @@ int igd_hip_fisher_tables(igd_hip_db *db, const int64_t *a, const int64_t *b, co
  * the universe), n_k = |set k| and n_U = nu, the table of set k and file f is
  *     a = support[k * nFiles + f]      b = usupport[f] - a      c = n_k - a      d = n_U - a - b - c  (= n_U - usupport[f] - c)
  * where a negative b or d is then set to 0 and clamped[k] counts the cells of set k where that happened (a set region
- * outside the universe, or a universe region under several set regions: the sets are NOT restricted to the universe).
+ * outside the universe, or a universe region under several set regions).  igd_hip_enrich_restricted restricts the sets to the
+ * universe first; its tables are partitions of the universe and need no clamp.
  *     support[nsets * nFiles], usupport[nFiles]                     the counts (the universe is counted once)
  *     pvalue_log[nsets * nFiles], odds_ratio[nsets * nFiles]        as igd_hip_fisher_tables on these tables, bit for bit
  *     clamped[nsets]
@@ -214,6 +215,43 @@ int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t 
                              int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
                              int32_t v, int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
                              int64_t *clamped, int64_t *nhit, int64_t *unhit);
+/* Query sets RESTRICTED to the universe (LOLA's redefineUserSets): each set is replaced by the universe regions it overlaps
+ * before anything is counted, so every table is a true 2x2 partition of the universe.  Sets as igd_hip_enrich_sets; the
+ * universe is the nu regions u_ichr / u_qs / u_qe in ANY order.
+ *     R_k = { u : some region q of set k has ichr_q == u_ichr_u >= 0, u_qs_u < qe_q and u_qe_u > qs_q }
+ * -- the plain predicate on the raw int32 numbers, the one the database search uses on records: empty and inverted regions on
+ * either side are not special-cased ([5,5) lies "in" [0,10)), regions that touch do not overlap.  A region with ichr < 0
+ * overlaps nothing: such a set region is dropped, such a universe region stays in n_U = nu and is in no R_k.  (A caller that
+ * maps contig names the database does not know to -1, or drops such lines as the command line tool's reader does, therefore
+ * never has a region on such a contig in a restricted set, although the join itself needs no database.)  Duplicate universe
+ * regions are distinct members; duplicate set regions add nothing.
+ *     bits[nsets * nUW], nUW = ceil(nu / 32)    region u (the caller's numbering) is bit u & 31 of word u >> 5 of row k;
+ *                                               bits at positions >= nu are 0
+ *     size[k] = |R_k|
+ * Both are DEFINED by the call.  Kernel igd_restrict_bits (an interval join over the universe ordered by (ichr, start) with a
+ * prefix maximum of the ends), in chunks of sets within a row budget.  Blocking.  The argument checks of igd_hip_enrich_sets
+ * apply, and nu + 1 >= 2^31 is IGD_HIP_ERR_ARG; on an error nothing of the caller's is written. */
+int igd_hip_restrict_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                          int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
+                          uint32_t *bits, int64_t *size);
+/* Region-set enrichment of the restricted sets.  With member[u][f] as igd_hip_membership defines it for the universe regions
+ * (rule and v of this call):
+ *     usupport[f]  = sum over u of member[u][f]               support[k * nFiles + f] = sum over u in R_k of member[u][f]
+ *     nhit[k]      = the u in R_k with any file               *unhit = the same over the whole universe
+ *     a = support   b = usupport[f] - a   c = size[k] - a   d = nu - usupport[f] - c
+ * all four >= 0 by construction (d = nu - |R_k u H_f|): there is no clamp and no `clamped`.  pvalue_log and odds_ratio are
+ * igd_fisher_cells' on these tables: passing R_k as explicit region lists (the universe's own triples) to igd_hip_enrich_sets
+ * gives the same supports, tables and, bit for bit, statistics, with clamped == 0.
+ * All outputs are DEFINED by the call; odds_ratio, bits, nhit and unhit may be NULL.  The database is walked once per universe
+ * region however many sets there are (igd_hip_membership_dev in chunks; kernel igd_bits_support gathers the member rows of the
+ * set bits).  Blocking, one device.  Checks as igd_hip_restrict_sets, before anything of the caller's is written. */
+int igd_hip_enrich_restricted(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                              int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
+                              int32_t v, int rule, int64_t *support, int64_t *usupport, int64_t *size, double *pvalue_log,
+                              double *odds_ratio, uint32_t *bits, int64_t *nhit, int64_t *unhit);
+/* Workgroups (of 256 lanes, one set region per lane at a time) the join kernel is launched with for nregions set regions: a
+ * lane takes a second region only when nregions exceeds 256 times this number (tests). */
+int32_t igd_hip_restrict_grid(int64_t nregions);
 /* Workgroups (of four waves, one cell per wave at a time) the cell kernel is launched with for ncell cells: a wave takes a
  * second cell only when ncell exceeds four times this number (tests). */
 int32_t igd_hip_fisher_grid(int64_t ncell);
