@@ -69,9 +69,9 @@ def member_of(fx, mode):
     return fx["member"][mode]
 
 
-def check_restricted(db, res, nhit, unhit, R, member, nu, what):
+def check_restricted(db, res, nhit, unhit, R, member, nu, what, gather=RR.gather):
     """every integer output against the brute force, exactly"""
-    sup, usup, wnhit, wunhit = RR.gather(R, member)
+    sup, usup, wnhit, wunhit = gather(R, member)
     size = R.sum(axis=1)
     print(what, "size", size.tolist(), "support max", int(sup.max(initial=0)), "nhit", wnhit.tolist(), "unhit", wunhit)
     assert np.array_equal(res.bits, RR.pack(R)), what

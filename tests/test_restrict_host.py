@@ -5,6 +5,7 @@ The join is held against restrict_ref.join, a numpy broadcast of the predicate; 
 per-query membership (test_membership_host.oracle_member: Oracle.search one universe region at a time); all integer outputs
 must be EQUAL.  The statistics must be the bits igd_amd.fisher_host returns for the same tables and lie within fisher_ref's
 bound of exact arithmetic.  Every fixture's stated conditions are asserted on the expectation, so none is vacuous."""
+import os
 import shutil
 
 import numpy as np
@@ -12,9 +13,10 @@ import pytest
 
 import fisher_ref as FR
 import restrict_ref as RR
+import sets_fixtures as F
 from helpers import Oracle, short_tmpdir
 from test_enrich_host import enrich_fixture
-from test_membership_host import oracle_member
+from test_membership_host import oracle_member, oracle_member_enum
 from test_support_host import FLAT, NEST
 
 CASES = RR.join_cases()
@@ -135,3 +137,87 @@ def test_whole_universe_and_a_set_that_hits_nothing(fx):
     assert not res.b[0].any() and np.array_equal(res.c[0], res.size[0] - res.support[0]) and nhit[0] == unhit > 0
     assert res.size[1] == 0 and not res.support[1].any() and nhit[1] == 0 and not res.bits[1].any()
     assert not res.pvalue_log[1].any() and not np.signbit(res.pvalue_log[1]).any()
+
+
+# ---- the fixtures of tests/test_gpu_restrict_scale.py, proven without a GPU ----------------------------------------------------
+SPAN = (1 << 11) * 200                                     # chr1 of enrich_fixture: 200 tiles of 2 048 bp
+SEAM_SETS = (5, 6, 11, 100, 700)                           # of scale_b: the whole of chr1 twice, an empty set, two others
+
+
+def scale_consts():
+    """the work decomposition of igd_bits_support, read out of the sources"""
+    c = F.consts()
+    text = open(os.path.join(F.ENGINE, "restrict_dev.hpp")).read()
+    return dict(grid=c["IGD_SETS_GRID"], wg=c["IGD_SETS_WG"], wave=c["IGD_WAVE"], block_words=F._define(text, "IGD_RESTRICT_BLOCK_WORDS"),
+                lds_files=F._define(text, "IGD_RESTRICT_LDS_FILES"))
+
+
+def scale_fixture_a(orc, uni):
+    """restrict_ref.scale_a on the 40-file enrich_fixture: the anchors are the universe regions of the first twentieth of
+    chr1 that file 0 meets with a value of at least 400 (the oracle, one region at a time)"""
+    head = np.flatnonzero((uni[0] == 0) & (uni[1] < SPAN // 20))
+    member, _ = oracle_member(orc, uni[0][head], uni[1][head], uni[2][head], 400)
+    return RR.scale_a(uni, head[member[:, 0]], scale_consts()["grid"], SPAN)
+
+
+@pytest.fixture(scope="module")
+def fx40():
+    """the 40-file database of tests/test_gpu_restrict.py"""
+    d = short_tmpdir("irs")
+    path, upath, _, _ = enrich_fixture(d, nfiles=40, name="gx")
+    orc = Oracle(path)
+    yield dict(path=path, orc=orc, uni=orc.read_queries(upath))
+    orc.close()
+    shutil.rmtree(d, ignore_errors=True)
+
+
+def hold_host_route(path, cat, off, uni, R, want, v):
+    import igd_amd
+    sup, usup, wnhit, wunhit = want
+    res, nhit, unhit = igd_amd.enrich_restricted_host(path, *cat, off, *uni, v=v, with_nhit=True)
+    size = R.sum(axis=1)
+    assert np.array_equal(res.bits, RR.pack(R)) and np.array_equal(res.size, size)
+    assert np.array_equal(res.usupport, usup) and np.array_equal(res.support, sup)
+    assert np.array_equal(nhit, wnhit) and unhit == wunhit
+    b, c, d = RR.tables(sup, usup, size, R.shape[1])
+    assert (b >= 0).all() and (c >= 0).all() and (d >= 0).all()
+    assert np.array_equal(res.b, b) and np.array_equal(res.c, c) and np.array_equal(res.d, d)
+    bits, size2 = igd_amd.restrict_host(*cat, off, *uni)
+    assert np.array_equal(bits, res.bits) and np.array_equal(size2, size)
+
+
+@pytest.mark.parametrize("v", [0, 400])
+def test_scale_fixture_a_second_items(fx40, v):
+    """case A of tests/test_gpu_restrict_scale.py: IGD_SETS_GRID + 300 sets over one block.  The conditions hold on the brute
+    force, the two forms of the gather agree, and the host route returns the brute force."""
+    k = scale_consts()
+    a = scale_fixture_a(fx40["orc"], fx40["uni"])
+    assert len(a["off"]) - 1 == k["grid"] + 300 and (len(a["uni"][1]) + 31) // 32 <= k["block_words"]
+    n = np.diff(a["off"])
+    assert n.max() <= 30 and n[n > 0].min() >= 3
+    R = RR.join(*a["cat"], a["off"], *a["uni"])
+    member, _ = oracle_member(fx40["orc"], *a["uni"], v)
+    want = RR.gather_rows(R, member)
+    for x, y in zip(want, RR.gather(R, member)):
+        assert np.array_equal(x, y)
+    print(RR.second_item_conditions(R, member, want[0], want[1], k["grid"], "A v=%d" % v))
+    hold_host_route(fx40["path"], a["cat"], a["off"], a["uni"], R, want, v)
+
+
+def test_scale_fixture_b_blocks_and_waves(fx40):
+    """cases B and C: a universe of three blocks whose last word lies in wave 1, 900 sets, and the five sets of the seam
+    child.  The membership is the oracle's enumeration."""
+    k = scale_consts()
+    b = RR.scale_b(SPAN, k["block_words"])
+    uni = b["uni"]
+    assert (uni[0] == 1).sum() == 40 and (uni[0] < 0).sum() == 12 and not np.array_equal(np.lexsort((uni[1], uni[0])), np.arange(len(uni[1])))
+    R = RR.join(*b["cat"], b["off"], *uni)
+    member = oracle_member_enum(fx40["orc"], *uni)
+    reach = int(np.concatenate([fx40["uni"][2], [SPAN + 4 * 2048]]).max())
+    assert (uni[1] > reach).sum() == 1500 and not member[uni[1] > reach].any() and not member[uni[0] < 0].any()
+    want = RR.gather_rows(R, member)
+    for x, y in zip(want, RR.gather(R, member)):
+        assert np.array_equal(x, y)
+    print(RR.block_conditions(R, member, k["grid"], k["block_words"], k["wg"] // k["wave"], "B"))
+    print(RR.seam_conditions(R[list(SEAM_SETS)], member, 9001, k["block_words"], "C"))
+    hold_host_route(fx40["path"], b["cat"], b["off"], uni, R, want, 0)
