@@ -173,6 +173,18 @@ def hip():
         L.igd_hip_rank_grid.restype = C.c_int32
         L.igd_hip_rank_lds_cols.argtypes = []
         L.igd_hip_rank_lds_cols.restype = C.c_int32
+        # dataset co-occurrence: db, ichr, qs, qe, nq, v, rule, cooc, nhit
+        L.igd_hip_cooccur.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                      C.c_void_p, C.c_void_p]
+        # db, bits, nrows, nW, cols / db, a, m, b, n, nwords32, out
+        L.igd_hip_bits_transpose.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.igd_hip_bitrows_gram.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.igd_hip_gram_tile.argtypes = []
+        L.igd_hip_gram_tile.restype = C.c_int32
+        L.igd_hip_gram_kstep.argtypes = []
+        L.igd_hip_gram_kstep.restype = C.c_int32
+        L.igd_hip_gram_slices.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+        L.igd_hip_gram_slices.restype = C.c_int64
         L.igd_hip_membership.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
@@ -279,6 +291,11 @@ def _bind_core(L):
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+    # dataset co-occurrence on the host: db, map, ichr, qs, qe, nq, v, rule, cooc (int64[nfiles, nfiles]), nhit
+    L.igdc_cooccur_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
+                                    C.c_void_p, C.POINTER(C.c_int64)]
+    # a (uint32[m, nwords32]), m, b (uint32[n, nwords32] or NULL: symmetric), n, nwords32, out (int64[m, n])
+    L.igdc_bitrows_gram_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     return L
 
 

@@ -1273,6 +1273,75 @@ static void membership_files(char **paths, int32_t n, int32_t v, int setLines)
     free(q); free(bits); free(nfh); free(t.s);
 }
 
+/* ------------------------------- `igd search -q F -C` ----------------------------------- */
+/* Dataset co-occurrence over the regions of one query file: the header
+ *     index_a \t index_b \t support_a \t support_b \t both \t jaccard \t File_a \t File_b
+ * and one line per pair of datasets a < b that at least one region overlaps both of, in ascending (a, b): the regions that
+ * overlap a, that overlap b, that overlap both, and the Jaccard index both / (support_a + support_b - both) as %.6f; then
+ * `-u`'s last line.  Rule and filter are `-q`'s dispatch for -v.  Routing as `-w`: at most igdc_host_limit() queries go through
+ * igdc_cooccur_host, more through igd_hip_cooccur on one device.  The text leaves in pieces of about MEMBER_TEXT_BYTES. */
+static void cooccur_file(char *path, int32_t v)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles;
+    if (nfiles > IGD_COOCCUR_MAX_FILES) {
+        printf("Not supported: -C with more than %d datasets\n", (int)IGD_COOCCUR_MAX_FILES);
+        return;
+    }
+    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` */
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries q;
+    if (igdc_read_queries(g_core, path, 1, &q) != 0) memset(&q, 0, sizeof q);                  /* unreadable: an empty set */
+    int64_t *cooc = (int64_t *)calloc((size_t)nfiles * (size_t)nfiles + 1, sizeof(int64_t));
+    int64_t nhit = 0;
+    if (!cooc) { fprintf(stderr, "igd: out of memory\n"); igdc_queries_free(&q); return; }
+    double t0 = now_s();
+    int done = 0;
+    igdc_map *hm = host_map_lim(q.n, igdc_host_limit());
+    if (hm) {
+        done = igdc_cooccur_host(g_core, hm, q.ichr, q.qs, q.qe, q.n, ev, rule, cooc, &nhit) == 0;
+        igdc_map_close(hm);
+        if (done) phase("co-occurrence on the host (small files)", &t0);
+    }
+    if (!done && q.n > 0) {                           /* (after a read error too: the engine reads the file its own way) */
+        igd_hip_db *dev = engine();
+        t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_cooccur(dev, q.ichr, q.qs, q.qe, q.n, ev, rule, cooc, &nhit);
+            if (rc != IGD_HIP_OK) engine_failed("co-occurrence", rc);
+            phase("co-occurrence of the query file (H2D + membership + transpose + Gram kernels + D2H)", &t0);
+        }
+    }
+    if (!g_fail_rc) {
+        textbuf t = {NULL, 0, 0};
+        int ok = text_room(&t, 128);
+        if (ok) t.n += (size_t)sprintf(t.s + t.n, "index_a\tindex_b\tsupport_a\tsupport_b\tboth\tjaccard\tFile_a\tFile_b\n");
+        for (int32_t a = 0; a < nfiles && ok; a++) {
+            const int64_t sa = cooc[(size_t)a * (size_t)nfiles + (size_t)a];
+            if (sa == 0) continue;
+            const char *na = IGD->finfo[a].fileName;
+            for (int32_t b = a + 1; b < nfiles && ok; b++) {
+                const int64_t both = cooc[(size_t)a * (size_t)nfiles + (size_t)b];
+                if (both <= 0) continue;
+                const int64_t sb = cooc[(size_t)b * (size_t)nfiles + (size_t)b];
+                const char *nb = IGD->finfo[b].fileName;
+                ok = text_room(&t, strlen(na) + strlen(nb) + 160);
+                if (!ok) break;
+                t.n += (size_t)sprintf(t.s + t.n, "%d\t%d\t%lld\t%lld\t%lld\t%.6f\t%s\t%s\n", (int)a, (int)b, (long long)sa, (long long)sb,
+                                       (long long)both, (double)both / (double)(sa + sb - both), na, nb);
+                if (t.n >= MEMBER_TEXT_BYTES) text_flush(&t);
+            }
+        }
+        if (ok && text_room(&t, 96))
+            t.n += (size_t)sprintf(t.s + t.n, "Query regions with a hit: %lld of %lld\n", (long long)nhit, (long long)q.n);
+        else fprintf(stderr, "igd: out of memory\n");
+        text_flush(&t);
+        free(t.s);
+    }
+    igdc_queries_free(&q);
+    free(cooc);
+}
+
 /* ------------------------------- `igd search` ----------------------------------------- */
 static int usage_search(void)
 {
@@ -1295,6 +1364,8 @@ static int usage_search(void)
             "                               Fisher exact test (the sets as given; -X restricts them to the universe)\n"
             "    -X                         with -U: each set is first replaced by the universe regions it overlaps, so every\n"
             "                               table is a partition of the universe (number of regions of the set = their number)\n"
+            "    -C                         with -q: dataset x dataset co-occurrence over the query regions, per pair of datasets\n"
+            "                               the regions that overlap each, both, and the Jaccard index\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -1336,7 +1407,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
 
     int32_t v = 0, qs = 1, qe = 2;
-    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, restricted = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
+    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, restricted = 0, cooc = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -1375,6 +1446,8 @@ int igd_search(int argc, char **argv)                                        /* 
             ranks = 1;
         } else if (strcmp(a, "-X") == 0) {            /* (not the reference's: -U on the sets restricted to the universe, see enrich_files) */
             restricted = 1;
+        } else if (strcmp(a, "-C") == 0) {            /* (not the reference's: dataset co-occurrence, see cooccur_file) */
+            cooc = 1;
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
@@ -1382,7 +1455,15 @@ int igd_search(int argc, char **argv)                                        /* 
     }
 
     fP = fopen(igdName, "rb");                                                /* :974 */
-    if (ranks && !uniName) {
+    if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
+        printf("Not supported: -C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r\n");
+        return EX_OK;
+    } else if (cooc && mode != 1) {
+        printf("Not supported: -C without -q\n");
+        return EX_OK;
+    } else if (cooc) {
+        cooccur_file(qfName, v);
+    } else if (ranks && !uniName) {
         printf("Not supported: -R without -U\n");
         return EX_OK;
     } else if (restricted && !uniName) {

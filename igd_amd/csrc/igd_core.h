@@ -156,6 +156,17 @@ int igdc_enrich_restricted_host(const igdc_db *db, const igdc_map *m, const int3
                                 const int64_t *set_off, int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe,
                                 int64_t nu, int32_t v, int rule, int64_t *support, int64_t *usupport, int64_t *size, double *pvalue_log,
                                 double *odds_ratio, uint32_t *bits, int64_t *nhit, int64_t *unhit);
+/* Dataset x dataset co-occurrence over one region list (what igd_hip_cooccur computes; include/igd_hip.h has the definitions):
+ * cooc[f * nFiles + g] = the regions that overlap a record of file f and one of file g, *nhit (may be NULL) = the regions with
+ * any file.  Both are DEFINED by the call.  igdc_membership_host in chunks, a transpose into bit columns, popcounts of the
+ * column pairs with threads over the rows.  0 on success; -1 for a bad argument or more than IGD_COOCCUR_MAX_FILES files
+ * (nothing written), or when a tile could not be read (outputs undefined). */
+int igdc_cooccur_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                      int32_t v, int rule, int64_t *cooc, int64_t *nhit);
+/* out[i * n + j] = popcount(a_i AND b_j) over rows of nwords32 uint32 words (what igd_hip_bitrows_gram computes): a = m rows,
+ * b = n rows, b == NULL: the symmetric form (b = a, n = m).  out is DEFINED.  Needs no database.  0, or -1 (nothing written)
+ * for a missing array, a negative size or more than 2^28 cells. */
+int igdc_bitrows_gram_host(const uint32_t *a, int64_t m, const uint32_t *b, int64_t n, int64_t nwords32, int64_t *out);
 /* `-f` (rule NEST, the reference's order): qoff[0..nq] offsets, *out malloc'd (free()), entries as igd_hip_enumerate's */
 int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                         int64_t nq, int64_t *qoff, igd_hip_hit **out, int64_t *total);

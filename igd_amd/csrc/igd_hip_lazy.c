@@ -256,6 +256,49 @@ int32_t igd_hip_rank_lds_cols(void)
     return fn ? fn() : 0;
 }
 
+int igd_hip_cooccur(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t v, int rule,
+                    int64_t *cooc, int64_t *nhit)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, int32_t, int, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_cooccur");
+    return fn ? fn(db, ichr, qs, qe, nq, v, rule, cooc, nhit) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_bits_transpose(igd_hip_db *db, const uint32_t *bits, int64_t nrows, int64_t nW, uint64_t *cols)
+{
+    typedef int (*fn_t)(igd_hip_db *, const uint32_t *, int64_t, int64_t, uint64_t *);
+    RESOLVE(fn_t, "igd_hip_bits_transpose");
+    return fn ? fn(db, bits, nrows, nW, cols) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_bitrows_gram(igd_hip_db *db, const uint32_t *a, int64_t m, const uint32_t *b, int64_t n, int64_t nwords32, int64_t *out)
+{
+    typedef int (*fn_t)(igd_hip_db *, const uint32_t *, int64_t, const uint32_t *, int64_t, int64_t, int64_t *);
+    RESOLVE(fn_t, "igd_hip_bitrows_gram");
+    return fn ? fn(db, a, m, b, n, nwords32, out) : IGD_HIP_ERR_DEVICE;
+}
+
+int32_t igd_hip_gram_tile(void)
+{
+    typedef int32_t (*fn_t)(void);
+    RESOLVE(fn_t, "igd_hip_gram_tile");
+    return fn ? fn() : 0;
+}
+
+int32_t igd_hip_gram_kstep(void)
+{
+    typedef int32_t (*fn_t)(void);
+    RESOLVE(fn_t, "igd_hip_gram_kstep");
+    return fn ? fn() : 0;
+}
+
+int64_t igd_hip_gram_slices(int64_t m, int64_t n, int64_t nwords32)
+{
+    typedef int64_t (*fn_t)(int64_t, int64_t, int64_t);
+    RESOLVE(fn_t, "igd_hip_gram_slices");
+    return fn ? fn(m, n, nwords32) : 0;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

@@ -835,6 +835,103 @@ int igdc_enrich_restricted_host(const igdc_db *db, const igdc_map *m, const int3
     return rc;
 }
 
+/* Popcount Gram product of bit rows on the host: what igd_bitrows_gram (engine/cooccur_dev.hpp) computes.  Rows of nwords32
+ * uint32 words `stride` words apart; b == a selects the symmetric form: the cells on and above the diagonal are counted and
+ * mirrored.  out (leading dimension ldo) is ADDED to.  Threads take the rows of a interleaved (row i, i + T, ..: the triangle
+ * of the symmetric form is shared out evenly); the mirror cell (j, i) of a pair i < j is written by the owner of row i alone. */
+typedef struct { const uint32_t *a, *b; int64_t m, n, stride, nw, ldo; int64_t *out; int k, T; } gram_job;
+static inline int64_t and_popc(const uint32_t *x, const uint32_t *y, int64_t nw)
+{
+    int64_t c = 0, w = 0;
+    for (; w + 2 <= nw; w += 2) {
+        uint64_t p, q;
+        memcpy(&p, x + w, 8); memcpy(&q, y + w, 8);
+        c += __builtin_popcountll(p & q);
+    }
+    if (w < nw) c += __builtin_popcount(x[w] & y[w]);
+    return c;
+}
+static void *gram_run(void *p)
+{
+    const gram_job *J = (const gram_job *)p;
+    const int sym = J->a == J->b;
+    for (int64_t i = J->k; i < J->m; i += J->T)
+        for (int64_t j = sym ? i : 0; j < J->n; j++) {
+            const int64_t c = and_popc(J->a + i * J->stride, J->b + j * J->stride, J->nw);
+            J->out[i * J->ldo + j] += c;
+            if (sym && j != i) J->out[j * J->ldo + i] += c;
+        }
+    return NULL;
+}
+static void gram_host(const uint32_t *a, int64_t m, const uint32_t *b, int64_t n, int64_t stride, int64_t nw, int64_t *out, int64_t ldo)
+{
+    if (m <= 0 || n <= 0) return;
+    const double work = (double)m * (double)n * (double)(nw + 1) / 1024.0;     /* a thread per ~2 x 10^6 word pairs */
+    const int T = host_threads(work > 1e15 ? (int64_t)1e15 : (int64_t)work);
+    gram_job job[64];
+    pthread_t th[64];
+    int started[64];
+    for (int k = 0; k < T; k++) {
+        job[k].a = a; job[k].b = b; job[k].m = m; job[k].n = n; job[k].stride = stride; job[k].nw = nw; job[k].ldo = ldo;
+        job[k].out = out; job[k].k = k; job[k].T = T;
+    }
+    for (int k = 1; k < T; k++) {
+        started[k] = pthread_create(&th[k], NULL, gram_run, &job[k]) == 0;
+        if (!started[k]) gram_run(&job[k]);
+    }
+    gram_run(&job[0]);
+    for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
+}
+
+int igdc_bitrows_gram_host(const uint32_t *a, int64_t m, const uint32_t *b, int64_t n, int64_t nwords32, int64_t *out)
+{
+    if (!b) n = m;
+    if (m < 0 || n < 0 || nwords32 < 0 || (m > 0 && n > 0 && !out) || (m > 0 && nwords32 > 0 && !a) ||
+        (m > 0 && n > ((int64_t)1 << 28) / m))
+        return -1;
+    if (m == 0 || n == 0) return 0;
+    memset(out, 0, sizeof(int64_t) * (size_t)m * (size_t)n);
+    if (nwords32 > 0) gram_host(a, m, b ? b : a, n, nwords32, nwords32, out, n);
+    return 0;
+}
+
+/* Dataset x dataset co-occurrence on the host: what igd_hip_cooccur computes (include/igd_hip.h has the definitions) --
+ * igdc_membership_host in chunks of COOCCUR_CHUNK regions, the chunk's rows transposed word-wise into one bit column per
+ * file (region r of the chunk = bit r & 31 of word r >> 5), and the popcounts of the column pairs on and above the diagonal
+ * added to the matrix and its mirror.  cooc and *nhit are DEFINED by the call.  0 on success; -1 for a bad argument (nothing
+ * written) or when a tile could not be read (outputs undefined). */
+#define COOCCUR_CHUNK ((int64_t)1 << 16)
+int igdc_cooccur_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                      int32_t v, int rule, int64_t *cooc, int64_t *nhit)
+{
+    if (!db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (db->nFiles > 0 && !cooc) || db->nFiles > IGD_COOCCUR_MAX_FILES ||
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT))
+        return -1;
+    const int64_t nF = db->nFiles, nW = (nF + 31) / 32;
+    if (nF > 0) memset(cooc, 0, sizeof(int64_t) * (size_t)nF * (size_t)nF);
+    if (nhit) *nhit = 0;
+    if (nF == 0 || nq == 0) return 0;
+    const int64_t step = nq < COOCCUR_CHUNK ? nq : COOCCUR_CHUNK, cw = 2 * ((step + 63) / 64);
+    uint32_t *bits = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)step * (size_t)nW);
+    uint32_t *cols = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)nF * (size_t)cw);
+    int rc = bits && cols ? 0 : -1;
+    int64_t hit = 0;
+    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += step) {
+        const int64_t n = nq - c0 < step ? nq - c0 : step;
+        rc = igdc_membership_host(db, m, ichr + c0, qs + c0, qe + c0, n, v, rule, bits, NULL, &hit);
+        if (rc != 0) break;
+        memset(cols, 0, sizeof(uint32_t) * (size_t)nF * (size_t)cw);
+        for (int64_t r = 0; r < n; r++)
+            for (int64_t w = 0; w < nW; w++)
+                for (uint32_t x = bits[r * nW + w]; x; x &= x - 1)
+                    cols[(w * 32 + __builtin_ctz(x)) * cw + (r >> 5)] |= 1u << (r & 31);
+        gram_host(cols, nF, cols, nF, cw, (n + 31) / 32, cooc, nF);
+    }
+    free(bits); free(cols);
+    if (rc == 0 && nhit) *nhit = hit;
+    return rc;
+}
+
 /* The handle flavours' batches (Python search_n / search_1, R search_nr / getOverlaps): on the host while the batch is
  * small and no engine is resident, otherwise on the engine, which is attached at the first batch that needs it -- the
  * moment the reference would do its first fseek/fread (src/igd_search.c:469-476); open_iGD reads the header only, like

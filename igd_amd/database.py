@@ -158,6 +158,80 @@ def enrich_restricted_host(igd_path, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, 
     return (res, nhit[:nsets], unhit.value) if with_nhit else res
 
 
+def _bitrows(x, name, what):
+    x = np.ascontiguousarray(x, dtype=np.uint32)
+    if x.ndim != 2:
+        raise IgdError("%s: %s must be a two-dimensional uint32 array of bit rows" % (what, name))
+    return x
+
+
+def bitrows_gram_host(a, b=None):
+    """Popcount Gram product of bit rows on the host (igdc_bitrows_gram_host; no device is touched): int64[m, n] with
+    out[i, j] = popcount(a[i] & b[j]) as Database.bitrows_gram() defines it; b=None is the symmetric form."""
+    a = _bitrows(a, "a", "bitrows_gram_host")
+    b = None if b is None else _bitrows(b, "b", "bitrows_gram_host")
+    if b is not None and b.shape[1] != a.shape[1]:
+        raise IgdError("bitrows_gram_host: rows of %d and of %d words" % (a.shape[1], b.shape[1]))
+    m, n = a.shape[0], a.shape[0] if b is None else b.shape[0]
+    out = np.empty((m, n), np.int64)
+    if N.cli().igdc_bitrows_gram_host(a.ctypes.data if a.size else None, m, None if b is None else (b.ctypes.data if b.size else a.ctypes.data),
+                                      n, a.shape[1], out.ctypes.data if out.size else None) != 0:
+        raise IgdError("bitrows_gram_host: more than 2^28 cells")
+    return out
+
+
+def jaccard(cooc):
+    """Jaccard index of a co-occurrence matrix (pure numpy): J[f, g] = cooc[f, g] / (cooc[f, f] + cooc[g, g] - cooc[f, g]) in
+    float64, NaN where the denominator is 0."""
+    c = np.asarray(cooc)
+    if c.ndim != 2 or c.shape[0] != c.shape[1]:
+        raise IgdError("jaccard: cooc must be a square matrix")
+    d = np.diagonal(c)
+    den = (d[:, None] + d[None, :] - c).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den == 0, np.nan, c.astype(np.float64) / den)
+
+
+def cooccur_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None):
+    """Dataset co-occurrence over a region list on the host (igdc_cooccur_host: pread on the .igd; no device is touched):
+    (cooc int64[nfiles, nfiles], nhit) as Database.cooccurrence() defines them."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    if len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("cooccur_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    L = N.cli()
+    core = L.igdc_open(igd_path.encode())
+    if not core:
+        raise IgdError("cannot read .igd header of %s" % igd_path)
+    fd = -1
+    m = None
+    try:
+        tsv = L.igdc_index_path(igd_path.encode())
+        rc = L.igdc_load_index(core, C.cast(tsv, C.c_char_p))
+        N.free(tsv)
+        if rc != 0:
+            raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
+        nf, gtype = core.contents.nFiles, core.contents.gType
+        if rule is None:
+            rule, vf = Database.cli_dispatch(gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        fd = os.open(igd_path, os.O_RDONLY)
+        m = L.igdc_map_open(core, fd)
+        if not m:
+            raise IgdError("cannot map %s" % igd_path)
+        cooc, nhit = np.empty((nf, nf), np.int64), C.c_int64(0)
+        if L.igdc_cooccur_host(core, m, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, len(qs), vf, rule,
+                               cooc.ctypes.data if cooc.size else None, C.byref(nhit)) != 0:
+            raise IgdError("cooccur_host: more than 16384 files, or a tile of %s could not be read" % igd_path)
+    finally:
+        if m:
+            L.igdc_map_close(m)
+        if fd >= 0:
+            os.close(fd)
+        L.igdc_close(core)
+    return cooc, nhit.value
+
+
 class Database:
     def __init__(self, igd_path, device=0):
         self._L = N.cli()
@@ -541,6 +615,69 @@ class Database:
                                         bits.ctypes.data if bits.size else None, nfh.ctypes.data if nq else None,
                                         C.byref(nhit)), "igd_hip_membership")
         return bits, nfh, nhit.value
+
+    def cooccurrence(self, ichr, qs, qe, v=0, rule=None, value_filter=None, cooc=None):
+        """Dataset x dataset co-occurrence over one region list (igd_hip_cooccur).  Returns (cooc int64[nfiles, nfiles], nhit):
+        with member = unpack_membership(membership(...)), cooc[f, g] = the regions q with member[q, f] and member[q, g] --
+        symmetric, its diagonal is support() -- and nhit = the regions that overlap any file.  Two identical regions count
+        twice; no region gives a zero matrix.  cooc (int64[nfiles, nfiles], C order), when given, is overwritten: every cell
+        of it.  The membership rows never leave the device.  More than 16 384 files raise IgdError.  jaccard() turns the
+        matrix into the Jaccard index."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        nq, nf = len(qs), self.nfiles
+        if len(ichr) != nq or len(qe) != nq:
+            raise IgdError("cooccurrence: %d / %d / %d regions given" % (len(ichr), nq, len(qe)))
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        if cooc is None:
+            cooc = np.empty((nf, nf), np.int64)
+        elif cooc.dtype != np.int64 or cooc.shape != (nf, nf) or not cooc.flags.c_contiguous:
+            raise IgdError("cooccurrence: cooc must be a C-ordered int64[%d, %d]" % (nf, nf))
+        nhit = C.c_int64(0)
+        _chk(self._H.igd_hip_cooccur(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, nq, vf, rule,
+                                     cooc.ctypes.data if cooc.size else None, C.byref(nhit)), "igd_hip_cooccur")
+        return cooc, nhit.value
+
+    def cooccurrence_files(self, path, v=0):
+        """The co-occurrence over the regions of one BED file (read as `igd search -q` reads it): what `igd search -q path -C`
+        prints, as cooccurrence() returns it."""
+        return self.cooccurrence(*self.read_queries(path), v)
+
+    def transpose_bits(self, bits, cols=None):
+        """Bit rows into bit columns on the GPU (igd_hip_bits_transpose): bits is uint32[nrows, nW] in the layout of
+        membership(); returns uint64[32 * nW, ceil(nrows / 64)] where row r is bit r & 63 of cols[c, r >> 6], c = 32 * w + the
+        bit's position in word w.  Every word is defined; bits at positions >= nrows are 0.  cols, when given, is overwritten."""
+        bits = _bitrows(bits, "bits", "transpose_bits")
+        nrows, nW = bits.shape
+        shape = (32 * nW, (nrows + 63) // 64)
+        if cols is None:
+            cols = np.empty(shape, np.uint64)
+        elif cols.dtype != np.uint64 or cols.shape != shape or not cols.flags.c_contiguous:
+            raise IgdError("transpose_bits: cols must be a C-ordered uint64[%d, %d]" % shape)
+        _chk(self._H.igd_hip_bits_transpose(self.dev, bits.ctypes.data if bits.size else None, nrows, nW,
+                                            cols.ctypes.data if cols.size else None), "igd_hip_bits_transpose")
+        return cols
+
+    def bitrows_gram(self, a, b=None, out=None):
+        """Popcount Gram product of bit rows on the GPU (igd_hip_bitrows_gram): a is uint32[m, nwords], b uint32[n, nwords];
+        returns int64[m, n] with out[i, j] = popcount(a[i] & b[j]).  b=None is the symmetric form (b = a): only the tiles on
+        and above the diagonal are computed.  With the bits of restrict_sets() it is the set x set overlap matrix.  out,
+        when given, is overwritten: every cell of it."""
+        a = _bitrows(a, "a", "bitrows_gram")
+        b = None if b is None else _bitrows(b, "b", "bitrows_gram")
+        if b is not None and b.shape[1] != a.shape[1]:
+            raise IgdError("bitrows_gram: rows of %d and of %d words" % (a.shape[1], b.shape[1]))
+        m, n = a.shape[0], a.shape[0] if b is None else b.shape[0]
+        if out is None:
+            out = np.empty((m, n), np.int64)
+        elif out.dtype != np.int64 or out.shape != (m, n) or not out.flags.c_contiguous:
+            raise IgdError("bitrows_gram: out must be a C-ordered int64[%d, %d]" % (m, n))
+        pb = None if b is None else (b.ctypes.data if b.size else a.ctypes.data)
+        _chk(self._H.igd_hip_bitrows_gram(self.dev, a.ctypes.data if a.size else None, m, pb, n, a.shape[1],
+                                          out.ctypes.data if out.size else None), "igd_hip_bitrows_gram")
+        return out
 
     def membership_files(self, paths, v=0):
         """The rows of several BED files (read as `igd search -q` reads them), concatenated: (bits, nfiles_hit, nhit

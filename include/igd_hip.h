@@ -282,6 +282,37 @@ int igd_hip_enrich_ranks(igd_hip_db *db, const int64_t *support, const double *p
  * a global workspace (tests). */
 int32_t igd_hip_rank_grid(int64_t nrows);
 int32_t igd_hip_rank_lds_cols(void);
+/* Dataset x dataset co-occurrence over one region list.  With member[q][f] as igd_hip_membership defines it for the nq regions
+ * (rule and v of this call):
+ *     cooc[f * nFiles + g] = #{ q : member[q][f] and member[q][g] }       int64, nFiles x nFiles, row-major
+ *     *nhit                = the regions with any file (may be NULL)
+ * The matrix is symmetric and its diagonal is the support of the region list (igd_hip_support_sets with one set).  Two
+ * identical regions count twice.  Both outputs are DEFINED by the call, never added to; nq == 0 gives a zero matrix.  The
+ * Jaccard index cooc[f][g] / (cooc[f][f] + cooc[g][g] - cooc[f][g]) is the caller's (igd_amd.jaccard).
+ * The regions go through in the chunks of igd_hip_membership; per chunk igd_hip_membership_dev, kernel igd_bits_transpose (the
+ * bit rows into bit columns) and kernel igd_bitrows_gram (popcounts of column pairs, symmetric form) adding into a resident
+ * matrix: the rows never leave the device, the matrix is copied out once.  Blocking, one device.  IGD_HIP_ERR_ARG, before
+ * anything of the caller's is written: a missing array, no such rule, more than IGD_COOCCUR_MAX_FILES files (the matrix
+ * would be 2 GiB).  Not done: several sets in one call, weighted counts, several devices. */
+#define IGD_COOCCUR_MAX_FILES 16384
+int igd_hip_cooccur(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t v, int rule,
+                    int64_t *cooc, int64_t *nhit);
+/* The two kernels on host arrays (db names the device and owns the workspaces; its records are not read).
+ * igd_hip_bits_transpose: bits is nrows rows of nW uint32 words (the layout of igd_hip_membership); cols receives 32 * nW
+ * columns of ceil(nrows / 64) uint64 words, column c at cols + c * ceil(nrows / 64): row r is bit r & 63 of word r >> 6 of
+ * column c = 32 * w + (the bit's position in word w).  Every word of cols is DEFINED; bits at positions >= nrows are 0.
+ * igd_hip_bitrows_gram: out[i * n + j] = popcount(a_i AND b_j) over rows of nwords32 uint32 words, a = m rows, b = n rows;
+ * b == NULL selects the symmetric form (b = a, n = m: only the tiles on and above the diagonal are computed and mirrored).
+ * out[m * n] is DEFINED.  The rows are those of igd_hip_restrict_sets' bits: igd_hip_bitrows_gram(bits, nsets, NULL, ..) is the
+ * set x set overlap matrix |R_j n R_k|.  IGD_HIP_ERR_ARG for a missing array, a negative size or more than 2^28 cells. */
+int igd_hip_bits_transpose(igd_hip_db *db, const uint32_t *bits, int64_t nrows, int64_t nW, uint64_t *cols);
+int igd_hip_bitrows_gram(igd_hip_db *db, const uint32_t *a, int64_t m, const uint32_t *b, int64_t n, int64_t nwords32, int64_t *out);
+/* The decomposition of igd_bitrows_gram (tests): the edge of an output tile (one workgroup), the 64-bit words of a row that
+ * one K-step stages, and the slices the word range of a launch is cut into for a = m rows, b = n rows (n == 0: the symmetric
+ * form) of nwords32 uint32 words -- every slice is a multiple of the K-step long and adds into out with atomics. */
+int32_t igd_hip_gram_tile(void);
+int32_t igd_hip_gram_kstep(void);
+int64_t igd_hip_gram_slices(int64_t m, int64_t n, int64_t nwords32);
 
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
