@@ -185,6 +185,15 @@ def hip():
         L.igd_hip_gram_kstep.restype = C.c_int32
         L.igd_hip_gram_slices.argtypes = [C.c_int64, C.c_int64, C.c_int64]
         L.igd_hip_gram_slices.restype = C.c_int64
+        # permutation null: db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, min, max
+        L.igd_hip_permute_support.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
+                                              C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 7
+        # db, ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe / db, rows, nrows, ncols, observed, 6 outputs
+        L.igd_hip_permute_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int,
+                                              C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        L.igd_hip_perm_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p] + [C.c_void_p] * 6
+        L.igd_hip_permute_grid.argtypes = [C.c_int64]
+        L.igd_hip_permute_grid.restype = C.c_int32
         L.igd_hip_membership.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
@@ -296,6 +305,18 @@ def _bind_core(L):
                                     C.c_void_p, C.POINTER(C.c_int64)]
     # a (uint32[m, nwords32]), m, b (uint32[n, nwords32] or NULL: symmetric), n, nwords32, out (int64[m, n])
     L.igdc_bitrows_gram_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    # permutation null on the host: ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe
+    L.igdc_permute_regions_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int, C.c_uint64,
+                                            C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    L.igdc_permute_first_bad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
+    L.igdc_permute_first_bad.restype = C.c_int64
+    # db, map, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, min, max
+    L.igdc_permute_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
+                                    C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 7
+    # observed, sum, sumsq, n_ge, n_le, nperm, n, mean, sd, z, nlog10_p_upper, nlog10_p_lower
+    L.igdc_perm_summary.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int64] + [C.c_void_p] * 5
+    # db, path, len (int32[nCtg]), bad_line
+    L.igdc_read_genome.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L
 
 

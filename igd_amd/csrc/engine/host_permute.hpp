@@ -1,0 +1,257 @@
+// engine/host_permute.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
+// igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: the permutation null of region-set support
+// ------------------------------------------------------------------------------------------
+// The set's regions and the contig lengths go to the device once (db->d_pmReg).  The set as given is counted first: one row
+// through igd_sets_support, copied on the device into `observed` (db->d_pmStat holds observed and the six statistics, nFiles + 1
+// words each; word nFiles is the any-dataset column, the kernel's nhit total).  Then the permutations in CHUNKS of pc, where
+// pc * nq <= igd_hip_max_batch() (the staging arrays of igd_hip_search) and pc * nFiles * 8 <= perm_row_bytes() (the rows of
+// igd_hip_search_sets): igd_permute_regions fills the staging arrays, the slice table -- one row per permutation, each row cut
+// as igd_hip_support_sets cuts a set; built and uploaded once, a shorter last chunk uses a prefix of it -- drives ONE launch of
+// igd_sets_support, and igd_perm_stats folds the chunk's rows and totals into the statistics.  Everything is enqueued on the
+// engine's stream without a wait in between; 7 x (nFiles + 1) words come back at the end.
+// Everything is computed into a buffer of this file and copied to the caller's at the end: on an error nothing is written.
+
+// The TEST-ONLY variable IGD_HIP_PERM_ROW_BYTES (read once per process, as IGD_HIP_RESTRICT_ROW_BYTES) lowers the row budget of
+// a chunk so that small fixtures cross the seam between two chunks.
+static int64_t perm_row_bytes(void)
+{
+    static const int64_t m = []() -> int64_t {
+        const char *e = getenv("IGD_HIP_PERM_ROW_BYTES");
+        const long long x = e && *e ? atoll(e) : 0;
+        return x > 0 ? (int64_t)x : IGD_SETS_ROW_BYTES;
+    }();
+    return m;
+}
+
+// workgroups igd_permute_regions is launched with for n outputs: a lane takes a second one only when n exceeds the grid's lanes
+extern "C" int32_t igd_hip_permute_grid(int64_t n)
+{
+    const int64_t g = (n + IGD_SETS_WG - 1) / IGD_SETS_WG;
+    return (int32_t)(g < 1 ? 1 : g < IGD_SETS_GRID ? g : IGD_SETS_GRID);
+}
+
+// igd_perm_stats over nrows rows (device) into the six arrays at d_st; d_tot: see permute_dev.hpp
+static int perm_stats_launch(igd_hip_db *db, const int64_t *d_rows, const int64_t *d_tot, int64_t nrows, int64_t ncols,
+                             const long long *d_obs, long long *d_st)
+{
+    const int64_t gx = (ncols + IGD_WAVE - 1) / IGD_WAVE, waves = IGD_SETS_WG / IGD_WAVE;
+    int64_t gy = (nrows + waves - 1) / waves;
+    const int64_t room = IGD_SETS_GRID / gx > 1 ? IGD_SETS_GRID / gx : 1;
+    if (gy > room) gy = room;
+    if (gy > IGD_PERM_STATS_ROWS_Y) gy = IGD_PERM_STATS_ROWS_Y;
+    igd_perm_stats<<<dim3((unsigned)gx, (unsigned)gy), IGD_SETS_WG, 0, db->stream>>>((const long long *)d_rows, (const long long *)d_tot, nrows,
+                                                                                  ncols, d_obs, d_st);
+    HIPCHK(hipGetLastError());
+    return IGD_HIP_OK;
+}
+
+static int perm_stats_init(igd_hip_db *db, long long *d_st, int64_t ncols)
+{
+    const int64_t g = (6 * ncols + IGD_SETS_WG - 1) / IGD_SETS_WG;
+    igd_perm_stats_init<<<(unsigned)(g < IGD_SETS_GRID ? g : IGD_SETS_GRID), IGD_SETS_WG, 0, db->stream>>>(d_st, ncols);
+    HIPCHK(hipGetLastError());
+    return IGD_HIP_OK;
+}
+
+// the six statistics of a call whose every permuted value is 0 against observed 0 (no region, or no file)
+static void perm_all_zero(int64_t *res, int64_t nC, int64_t nperm)
+{
+    for (int64_t f = 0; f < nC; f++) {
+        res[f] = res[nC + f] = res[2 * nC + f] = res[5 * nC + f] = res[6 * nC + f] = 0;
+        res[3 * nC + f] = res[4 * nC + f] = nperm;
+    }
+}
+
+// res = observed, sum, sumsq, n_ge, n_le, min, max, nC words each -> the caller's arrays
+static void perm_copy_out(const int64_t *res, int64_t nC, int64_t *const out[7])
+{
+    for (int a = 0; a < 7; a++)
+        if (out[a]) memcpy(out[a], res + a * nC, (size_t)nC * 8);
+}
+
+extern "C" int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule,
+                                       int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
+                                       int64_t *pmax)
+{
+    if (!db || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nperm < 1 || nperm > IGD_HIP_PERM_MAX) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: %lld permutations, not 1 .. %lld", (long long)nperm, (long long)IGD_HIP_PERM_MAX);
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nq > max_batch()) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: %lld regions, more than %lld", (long long)nq, (long long)max_batch());
+        return IGD_HIP_ERR_ARG;
+    }
+    if ((unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: %lld permutations of %lld regions: the sum of squares may pass 2^63",
+                 (long long)nperm, (long long)nq);
+        return IGD_HIP_ERR_ARG;
+    }
+    for (int64_t i = 0; i < nq; i++) {
+        const int32_t c = ichr[i];
+        if (c < 0 || c >= db->nCtg) continue;
+        const int64_t L = ctg_len[c];
+        if (L < 1 || qs[i] < 0 || qe[i] < qs[i] || (int64_t)qe[i] > L) {
+            snprintf(g_err, sizeof g_err, "igd_hip_permute_support: region %lld = (%d, %d, %d) does not lie on its contig of length %lld",
+                     (long long)i, (int)c, (int)qs[i], (int)qe[i], (long long)L);
+            return IGD_HIP_ERR_ARG;
+        }
+    }
+    const int64_t nF = db->nFiles, nC = nF + 1, nW = (nF + 31) / 32;
+    int64_t *const out[7] = {observed, sum, sumsq, n_ge, n_le, pmin, pmax};
+    std::vector<int64_t> res((size_t)(7 * nC));
+    if (nq == 0 || nF == 0) {
+        perm_all_zero(res.data(), nC, nperm);
+        perm_copy_out(res.data(), nC, out);
+        return IGD_HIP_OK;
+    }
+
+    // the image and the rule word as igd_hip_support_sets gives them to igd_sets_support
+    igd_hip_db *img = db->inner ? db->inner : db;
+    const int krule = db->inner ? (IGD_HIP_RULE_FLAT | (rule == IGD_HIP_RULE_NEST ? 0x100 : 0)) : rule;
+    const bool useV = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+    const bool lds = nF <= IGD_SUPPORT_LDS_FILES;
+    int64_t pc = max_batch() / nq;
+    const int64_t byRows = perm_row_bytes() / (nF * 8);
+    if (byRows < pc) pc = byRows < 1 ? 1 : byRows;
+    if (nperm < pc) pc = nperm;
+    int64_t sliceLen = (pc * nq + IGD_SETS_SLICES - 1) / IGD_SETS_SLICES;
+    sliceLen = sliceLen < IGD_SETS_SLICE_MIN ? IGD_SETS_SLICE_MIN : sliceLen > IGD_SETS_SLICE_MAX ? IGD_SETS_SLICE_MAX : sliceLen;
+    const int64_t perRow = (nq + sliceLen - 1) / sliceLen;                // slices of one permutation
+    int64_t maxGrid = IGD_SETS_GRID;
+    if (!lds) {
+        const int64_t g = IGD_SUPPORT_BITS_BYTES / (nW * 4 * (IGD_SETS_WG / IGD_WAVE));
+        maxGrid = g < 1 ? 1 : g < IGD_SETS_GRID ? g : IGD_SETS_GRID;
+    }
+    std::vector<SetSlice> slices;
+    slices.reserve((size_t)(pc * perRow));
+    for (int64_t r = 0; r < pc; r++)
+        for (int64_t a = 0; a < nq; a += sliceLen)
+            slices.push_back(SetSlice{(int32_t)r, (int32_t)(r * nq + a), (int32_t)(r * nq + (a + sliceLen < nq ? a + sliceLen : nq)), 0});
+
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    int rc = restrict_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + db->nCtg);
+    if (rc == IGD_HIP_OK) rc = restrict_grow(db, &db->d_pmStat, &db->pmStatCap, 7 * nC);
+    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
+    if (rc == IGD_HIP_OK) rc = ensure_sets_ws(db, pc * nF, pc, pc * perRow);
+    if (rc == IGD_HIP_OK && !lds) rc = ensure_support_bits(db, maxGrid * (IGD_SETS_WG / IGD_WAVE) * nW);
+    if (rc != IGD_HIP_OK) return rc;
+    int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
+    long long *dObs = db->d_pmStat, *dSt = dObs + nC;
+    HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)db->nCtg * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(db->d_setSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+
+    const size_t ldsB = lds ? (size_t)(4 + nF + (IGD_SETS_WG / IGD_WAVE) * nW) * 4 : 0;
+    u64 *R = (u64 *)db->d_setRows, *T = (u64 *)db->d_setTot;
+    unsigned *B = (unsigned *)db->d_supBits;
+    // `rows` zeroed rows counted from the query arrays (c, s, e): rows * perRow slices, a prefix of the table
+    auto count = [&](const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows) -> int {
+        const int ns = (int)(rows * perRow);
+        const int grid = ns < maxGrid ? ns : (int)maxGrid;
+        HIPCHK(hipMemsetAsync(db->d_setRows, 0, (size_t)(rows * nF) * 8, st));
+        HIPCHK(hipMemsetAsync(db->d_setTot, 0, (size_t)rows * 8, st));
+        if (useV && lds) igd_sets_support<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
+        else if (useV) igd_sets_support<true, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
+        else if (lds) igd_sets_support<false, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
+        else igd_sets_support<false, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
+        HIPCHK(hipGetLastError());
+        return IGD_HIP_OK;
+    };
+
+    // the set as given
+    if ((rc = count(rC, rS, rE, 1)) != IGD_HIP_OK) return rc;
+    HIPCHK(hipMemcpyAsync(dObs, db->d_setRows, (size_t)nF * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(dObs + nF, db->d_setTot, 8, hipMemcpyDeviceToDevice, st));
+    if ((rc = perm_stats_init(db, dSt, nC)) != IGD_HIP_OK) return rc;
+    for (int64_t p0 = 0; p0 < nperm; p0 += pc) {
+        const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
+        igd_permute_regions<<<igd_hip_permute_grid(n * nq), IGD_SETS_WG, 0, st>>>(rC, rS, rE, (unsigned)nq, rL, db->nCtg, mode, (u64)seed, (u64)p0,
+                                                                               (unsigned)(n * nq), db->d_qc, db->d_qs, db->d_qe);
+        HIPCHK(hipGetLastError());
+        if ((rc = count(db->d_qc, db->d_qs, db->d_qe, n)) != IGD_HIP_OK) return rc;
+        if ((rc = perm_stats_launch(db, db->d_setRows, db->d_setTot, n, nC, dObs, dSt)) != IGD_HIP_OK) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(res.data(), db->d_pmStat, (size_t)(7 * nC) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    perm_copy_out(res.data(), nC, out);
+    return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                       const int32_t *ctg_len, int32_t nctg, int mode, uint64_t seed, int64_t p0, int64_t np,
+                                       int32_t *out_qs, int32_t *out_qe)
+{
+    if (!db || nq < 0 || np < 0 || p0 < 0 || nctg < 0 || (nctg > 0 && !ctg_len) || (nq > 0 && (!ichr || !qs || !qe)) ||
+        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) ||
+        nq > max_batch() || (nq > 0 && np > (int64_t)INT32_MAX / nq)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_regions: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nq == 0 || np == 0) return IGD_HIP_OK;
+    const int64_t pc = max_batch() / nq < np ? max_batch() / nq : np;
+    std::vector<int32_t> hs((size_t)(np * nq)), he((size_t)(np * nq));
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    int rc = restrict_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg);
+    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
+    if (rc != IGD_HIP_OK) return rc;
+    int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
+    HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    if (nctg) HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)nctg * 4, hipMemcpyHostToDevice, st));
+    for (int64_t a = 0; a < np; a += pc) {
+        const int64_t n = np - a < pc ? np - a : pc;
+        igd_permute_regions<<<igd_hip_permute_grid(n * nq), IGD_SETS_WG, 0, st>>>(rC, rS, rE, (unsigned)nq, rL, nctg, mode, (u64)seed, (u64)(p0 + a),
+                                                                               (unsigned)(n * nq), nullptr, db->d_qs, db->d_qe);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hs.data() + a * nq, db->d_qs, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(he.data() + a * nq, db->d_qe, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    memcpy(out_qs, hs.data(), (size_t)(np * nq) * 4);
+    memcpy(out_qe, he.data(), (size_t)(np * nq) * 4);
+    return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t nrows, int64_t ncols, const int64_t *observed,
+                                  int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax)
+{
+    if (!db || !rows || !observed || nrows < 1 || ncols < 1 || ncols > ((int64_t)1 << 40) / nrows) {
+        snprintf(g_err, sizeof g_err, "igd_hip_perm_stats: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    int64_t rc_ = perm_row_bytes() / (ncols * 8);
+    const int64_t step = rc_ < 1 ? 1 : rc_ < nrows ? rc_ : nrows;
+    std::vector<int64_t> res((size_t)(7 * ncols));
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    int rc = restrict_grow(db, &db->d_pmStat, &db->pmStatCap, 7 * ncols);
+    if (rc == IGD_HIP_OK) rc = ensure_sets_ws(db, step * ncols, step, 0);
+    if (rc != IGD_HIP_OK) return rc;
+    long long *dObs = db->d_pmStat, *dSt = dObs + ncols;
+    HIPCHK(hipMemcpyAsync(dObs, observed, (size_t)ncols * 8, hipMemcpyHostToDevice, st));
+    if ((rc = perm_stats_init(db, dSt, ncols)) != IGD_HIP_OK) return rc;
+    for (int64_t r0 = 0; r0 < nrows; r0 += step) {
+        const int64_t n = nrows - r0 < step ? nrows - r0 : step;
+        HIPCHK(hipMemcpyAsync(db->d_setRows, rows + r0 * ncols, (size_t)(n * ncols) * 8, hipMemcpyHostToDevice, st));
+        if ((rc = perm_stats_launch(db, db->d_setRows, nullptr, n, ncols, dObs, dSt)) != IGD_HIP_OK) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(res.data(), db->d_pmStat, (size_t)(7 * ncols) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    int64_t *const out[7] = {nullptr, sum, sumsq, n_ge, n_le, pmin, pmax};
+    perm_copy_out(res.data(), ncols, out);
+    return IGD_HIP_OK;
+}

@@ -1342,6 +1342,99 @@ static void cooccur_file(char *path, int32_t v)
     free(cooc);
 }
 
+/* ------------------------------- `igd search -q F -P N -g genome` ------------------------ */
+/* Permutation null of the support counts of one query file: the regions are shifted along their contigs (-M circular, the
+ * default: one offset per permutation and contig) or placed anew on them (-M shuffle) N times, seed -S (default 0); the
+ * contig lengths come from the genome file (`name<TAB>length`).  The header
+ *     index \t observed \t mean \t sd \t z \t n_ge \t n_le \t nlog10_p_upper \t nlog10_p_lower \t File
+ * and one line per dataset: the support of the file as given, mean and standard deviation of the permuted supports, the
+ * z-score, the permutations with a support >= / <= the observed one and -log10 of (n + 1) / (N + 1) for both (floats as
+ * %.6f); then `-u`'s last line followed by the same seven statistics of the regions with a hit in any dataset.  Rule and
+ * filter are `-q`'s dispatch for -v.  Routing as `-u`, decided on regions x (N + 1): at most igdc_host_limit() go through
+ * igdc_permute_host, more through igd_hip_permute_support on one device.  A region outside its contig's length, or on a contig
+ * the genome file lacks, ends the run with a message that names the line. */
+static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t seed, int pmode, int32_t v)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
+    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` */
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    int32_t *len = (int32_t *)calloc((size_t)g_core->nCtg + 1, sizeof(int32_t));
+    int64_t bad = 0;
+    const int grc = len ? igdc_read_genome(g_core, genome, len, &bad) : -1;
+    if (grc == -1) { printf("Cannot open genome file %s\n", genome); free(len); return; }
+    if (grc != 0) {
+        printf("Genome file %s, line %lld: not a name, a tab and a length of at most 2147483647\n", genome, (long long)bad);
+        free(len);
+        return;
+    }
+    /* the accepted lines as igdc_read_queries accepts them, read here so that a refusal can name its line */
+    igdc_queries q;
+    memset(&q, 0, sizeof q);
+    int64_t no = 0;
+    igdc_lines *r = igdc_lines_open(path);
+    char *line;
+    while (r && (line = igdc_lines_next(r, NULL)) != NULL) {
+        int32_t st, en;
+        no++;
+        char *chrm = igdc_parse_bed(line, &st, &en, 1);
+        if (!chrm) continue;
+        const int32_t id = igdc_get_id(g_core, chrm);
+        if (id < 0) continue;
+        if (len[id] < 1) {
+            printf("%s, line %lld: contig %s is not in the genome file %s\n", path, (long long)no, g_core->cName[id], genome);
+            goto done;
+        }
+        if (st < 0 || en < st || en > len[id]) {
+            printf("%s, line %lld: region %s:%d-%d does not lie on its contig of length %d\n", path, (long long)no, g_core->cName[id],
+                   (int)st, (int)en, (int)len[id]);
+            goto done;
+        }
+        if (igdc_queries_push(&q, id, st, en) != 0) { fprintf(stderr, "igd: out of memory\n"); goto done; }
+    }
+    if (q.n > igd_hip_max_batch() || (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63) {
+        printf("Not supported: -P %lld with %lld regions\n", (long long)nperm, (long long)q.n);
+        goto done;
+    }
+    {
+        int64_t *st7 = (int64_t *)calloc(7 * (size_t)nC, sizeof(int64_t));
+        double *fl = (double *)calloc(5 * (size_t)nC, sizeof(double));
+        if (!st7 || !fl) { fprintf(stderr, "igd: out of memory\n"); free(st7); free(fl); goto done; }
+        int64_t *obs = st7, *sum = obs + nC, *ssq = sum + nC, *nge = ssq + nC, *nle = nge + nC, *mn = nle + nC, *mx = mn + nC;
+        double t0 = now_s();
+        int ok = 0;
+        igdc_map *hm = host_map_lim(q.n * (nperm + 1), igdc_host_limit());
+        if (hm) {
+            ok = igdc_permute_host(g_core, hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx) == 0;
+            igdc_map_close(hm);
+            if (ok) phase("permutation null on the host (small files)", &t0);
+        }
+        if (!ok) {                                    /* (after a read error too: the engine reads the file its own way) */
+            igd_hip_db *dev = engine();
+            t0 = now_s();
+            if (dev) {
+                const int rc = igd_hip_permute_support(dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx);
+                if (rc != IGD_HIP_OK) engine_failed("permutation null", rc);
+                phase("permutation null of the query file (H2D + permute, support and statistics kernels + D2H)", &t0);
+            }
+        }
+        if (!g_fail_rc && igdc_perm_summary(obs, sum, ssq, nge, nle, nperm, nC, fl, fl + nC, fl + 2 * nC, fl + 3 * nC, fl + 4 * nC) == 0) {
+            printf("index\tobserved\tmean\tsd\tz\tn_ge\tn_le\tnlog10_p_upper\tnlog10_p_lower\tFile\n");
+            for (int32_t i = 0; i < nfiles; i++)
+                printf("%d\t%lld\t%.6f\t%.6f\t%.6f\t%lld\t%lld\t%.6f\t%.6f\t%s\n", (int)i, (long long)obs[i], fl[i], fl[nC + i], fl[2 * nC + i],
+                       (long long)nge[i], (long long)nle[i], fl[3 * nC + i], fl[4 * nC + i], IGD->finfo[i].fileName);
+            const int32_t a = nfiles;
+            printf("Query regions with a hit: %lld of %lld\t%.6f\t%.6f\t%.6f\t%lld\t%lld\t%.6f\t%.6f\n", (long long)obs[a], (long long)q.n, fl[a],
+                   fl[nC + a], fl[2 * nC + a], (long long)nge[a], (long long)nle[a], fl[3 * nC + a], fl[4 * nC + a]);
+        }
+        free(st7); free(fl);
+    }
+done:
+    if (r) igdc_lines_close(r);
+    igdc_queries_free(&q);
+    free(len);
+}
+
 /* ------------------------------- `igd search` ----------------------------------------- */
 static int usage_search(void)
 {
@@ -1366,6 +1459,11 @@ static int usage_search(void)
             "                               table is a partition of the universe (number of regions of the set = their number)\n"
             "    -C                         with -q: dataset x dataset co-occurrence over the query regions, per pair of datasets\n"
             "                               the regions that overlap each, both, and the Jaccard index\n"
+            "    -P <permutations>          with -q and -g: permutation null of the support counts -- the regions are moved along\n"
+            "                               their contigs N times; per dataset observed, mean, sd, z and both one-sided p\n"
+            "    -g <genome file>           with -P: the contig lengths, one name<TAB>length per line\n"
+            "    -S <seed>  -M <mode>       with -P: the seed (default 0); circular (default: one rigid shift per contig) or\n"
+            "                               shuffle (every region placed anew on its contig)\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -1409,6 +1507,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int32_t v = 0, qs = 1, qe = 2;
     int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, restricted = 0, cooc = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
+    char *permArg = NULL, *genomeName = NULL, *seedArg = NULL, *pmodeArg = NULL;      /* -P, -g, -S, -M (see permute_file) */
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
         const char *a = argv[i];
@@ -1448,6 +1547,18 @@ int igd_search(int argc, char **argv)                                        /* 
             restricted = 1;
         } else if (strcmp(a, "-C") == 0) {            /* (not the reference's: dataset co-occurrence, see cooccur_file) */
             cooc = 1;
+        } else if (strcmp(a, "-P") == 0) {            /* (not the reference's: permutation null of the support, see permute_file) */
+            if (i + 1 >= argc) { printf("No number of permutations.\n"); return EX_OK; }
+            permArg = argv[i + 1];
+        } else if (strcmp(a, "-g") == 0) {
+            if (i + 1 >= argc) { printf("No genome file.\n"); return EX_OK; }
+            genomeName = argv[i + 1];
+        } else if (strcmp(a, "-S") == 0) {
+            if (i + 1 >= argc) { printf("No seed.\n"); return EX_OK; }
+            seedArg = argv[i + 1];
+        } else if (strcmp(a, "-M") == 0) {
+            if (i + 1 >= argc) { printf("No mode.\n"); return EX_OK; }
+            pmodeArg = argv[i + 1];
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
@@ -1455,7 +1566,33 @@ int igd_search(int argc, char **argv)                                        /* 
     }
 
     fP = fopen(igdName, "rb");                                                /* :974 */
-    if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
+    if (!permArg && (genomeName || seedArg || pmodeArg)) {
+        printf("Not supported: -g, -S or -M without -P\n");
+        return EX_OK;
+    } else if (permArg && (listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)) {
+        printf("Not supported: -P together with -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r\n");
+        return EX_OK;
+    } else if (permArg && !genomeName) {
+        printf("Not supported: -P without -g\n");
+        return EX_OK;
+    } else if (permArg && mode != 1) {
+        printf("Not supported: -P without -q\n");
+        return EX_OK;
+    } else if (permArg) {
+        char *end = NULL;
+        const long long np = strtoll(permArg, &end, 10);
+        const int pmode = !pmodeArg || strcmp(pmodeArg, "circular") == 0 ? IGD_HIP_PERM_CIRCULAR
+                          : strcmp(pmodeArg, "shuffle") == 0 ? IGD_HIP_PERM_SHUFFLE : -1;
+        if (end == permArg || *end || np < 1 || np > (long long)IGD_HIP_PERM_MAX) {
+            printf("Not supported: -P %s (1 to %lld permutations)\n", permArg, (long long)IGD_HIP_PERM_MAX);
+            return EX_OK;
+        }
+        if (pmode < 0) {
+            printf("Not supported: -M %s (circular or shuffle)\n", pmodeArg);
+            return EX_OK;
+        }
+        permute_file(qfName, genomeName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v);
+    } else if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
         printf("Not supported: -C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r\n");
         return EX_OK;
     } else if (cooc && mode != 1) {

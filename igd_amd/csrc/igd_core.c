@@ -689,3 +689,39 @@ int igdc_read_queries(const igdc_db *db, const char *qfile, int require_chr, igd
     igdc_lines_close(r);
     return 0;
 }
+
+int igdc_read_genome(const igdc_db *db, const char *path, int32_t *len, int64_t *bad_line)
+{
+    if (!db || !path || (db->nCtg > 0 && !len)) return -1;
+    igdc_lines *r = igdc_lines_open(path);
+    if (!r) return -1;
+    for (int32_t c = 0; c < db->nCtg; c++) len[c] = 0;
+    char *line;
+    int64_t no = 0;
+    int rc = 0;
+    while ((line = igdc_lines_next(r, NULL)) != NULL) {
+        no++;
+        size_t L = strlen(line);
+        while (L > 0 && (line[L - 1] == '\r' || line[L - 1] == '\n')) line[--L] = '\0';
+        if (L == 0) continue;
+        char *tab = strchr(line, '\t');
+        if (tab) *tab = '\0';
+        const int32_t id = igdc_get_id(db, line);
+        if (id < 0) continue;                                  /* a contig the database does not know: the whole line is ignored */
+        char *end = NULL;
+        long long x = -1;
+        if (tab) {
+            errno = 0;
+            x = strtoll(tab + 1, &end, 10);
+            if (end == tab + 1 || errno != 0) x = -1;
+        }
+        if (x < 0 || x > 0x7fffffffLL) {
+            if (bad_line) *bad_line = no;
+            rc = -2;
+            break;
+        }
+        len[id] = (int32_t)x;
+    }
+    igdc_lines_close(r);
+    return rc;
+}

@@ -167,6 +167,31 @@ int igdc_cooccur_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
  * b = n rows, b == NULL: the symmetric form (b = a, n = m).  out is DEFINED.  Needs no database.  0, or -1 (nothing written)
  * for a missing array, a negative size or more than 2^28 cells. */
 int igdc_bitrows_gram_host(const uint32_t *a, int64_t m, const uint32_t *b, int64_t n, int64_t nwords32, int64_t *out);
+/* Permutation null of region-set support on the host (what igd_hip_permute_support computes; include/igd_hip.h has the generator,
+ * the outputs -- nFiles + 1 words each, all but observed may be NULL, all DEFINED -- and the refusals).  igdc_permute_regions_host
+ * is kernel igd_permute_regions: permutations [p0, p0 + np) of nq regions into out_qs, out_qe (int32[np * nq]); nctg is the
+ * caller's.  igdc_permute_host counts the set with igdc_support_host and every permuted set with the same per-query walk,
+ * threads over the permutations.  0 on success; -1 for a refused argument (nothing written) or when a tile could not be
+ * read (nothing written).  igdc_permute_first_bad: the first region on a known contig that breaks 0 <= s <= e <= L, L >= 1,
+ * or -1. */
+int igdc_permute_regions_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                              int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe);
+int64_t igdc_permute_first_bad(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg);
+int igdc_permute_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                      const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                      int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax);
+/* Per column f of n, with P = nperm permutations:
+ *     mean = sum / P          sd = sqrt((P * sumsq - sum^2) / (P * (P - 1)))   (the numerator exact in 128 bits; NaN when P = 1)
+ *     z = (observed - mean) / sd   (NaN when sd is 0 or NaN)
+ *     p_upper = (n_ge + 1) / (P + 1),  p_lower = (n_le + 1) / (P + 1), reported as -log10
+ * Every output may be NULL.  Needs no database.  0, or -1 for a missing input or nperm < 1. */
+int igdc_perm_summary(const int64_t *observed, const int64_t *sum, const int64_t *sumsq, const int64_t *n_ge, const int64_t *n_le,
+                      int64_t nperm, int64_t n, double *mean, double *sd, double *z, double *nlog10_p_upper, double *nlog10_p_lower);
+/* A genome file, lines `name<TAB>length`: len[c] = the length of contig c of the database (int32[nCtg]); lines of contigs the
+ * database does not know are ignored, contigs the file does not name get 0.  0; -1 when the file cannot be opened; -2 for a
+ * line of a known contig without a length or with one that is negative or above 2^31 - 1 (*bad_line, may be NULL, = its
+ * number from 1). */
+int igdc_read_genome(const igdc_db *db, const char *path, int32_t *len, int64_t *bad_line);
 /* `-f` (rule NEST, the reference's order): qoff[0..nq] offsets, *out malloc'd (free()), entries as igd_hip_enumerate's */
 int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                         int64_t nq, int64_t *qoff, igd_hip_hit **out, int64_t *total);

@@ -323,6 +323,11 @@ struct igd_hip_db {
     // the matrix, and the generic entries' resident copies of the caller's rows (64-bit words)
     u64 *d_coCols, *d_coMat, *d_coA, *d_coB;
     int64_t coColsCap, coMatCap, coACap, coBCap;
+    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats (host_permute.hpp): the set's regions and the contig
+    // lengths (ichr, qs, qe, ctg_len), and observed with the six statistics (64-bit words)
+    int32_t *d_pmReg;
+    long long *d_pmStat;
+    int64_t pmRegCap, pmStatCap;
     hipStream_t stream;
     // profiling
     std::vector<hipEvent_t> ev;   // 4 per launch: pipeline start, scan start, scan stop, pipeline stop
@@ -356,6 +361,7 @@ struct igd_hip_db {
 #include "engine/rank_dev.hpp"        // igd_rank_rows: one workgroup per table row, bitonic sort per column: ranks and BH q-values
 #include "engine/restrict_dev.hpp"    // igd_restrict_bits, igd_bits_support: sets restricted to a universe -- the interval join and the gather over member rows
 #include "engine/cooccur_dev.hpp"     // igd_bits_transpose, igd_bitrows_gram: bit rows into bit columns, popcount Gram product -- dataset co-occurrence
+#include "engine/permute_dev.hpp"     // igd_permute_regions, igd_perm_stats: shifted / shuffled region sets, column statistics of a row matrix -- permutation null
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -370,6 +376,7 @@ struct igd_hip_db {
 #include "engine/host_rank.hpp"       // igd_hip_enrich_ranks: chunks of whole rows, one launch each
 #include "engine/host_restrict.hpp"   // igd_hip_restrict_sets / igd_hip_enrich_restricted: chunks of sets x chunks of the universe
 #include "engine/host_cooccur.hpp"    // igd_hip_cooccur / igd_hip_bits_transpose / igd_hip_bitrows_gram: chunks of regions, rows stay resident
+#include "engine/host_permute.hpp"    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: chunks of permutations, rows stay resident
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

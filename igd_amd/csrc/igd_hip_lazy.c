@@ -299,6 +299,41 @@ int64_t igd_hip_gram_slices(int64_t m, int64_t n, int64_t nwords32)
     return fn ? fn(m, n, nwords32) : 0;
 }
 
+int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                            int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
+                            int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int, uint64_t, int64_t,
+                        int32_t, int, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_permute_support");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                            int32_t nctg, int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int32_t, int, uint64_t,
+                        int64_t, int64_t, int32_t *, int32_t *);
+    RESOLVE(fn_t, "igd_hip_permute_regions");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t nrows, int64_t ncols, const int64_t *observed, int64_t *sum,
+                       int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int64_t *, int64_t, int64_t, const int64_t *, int64_t *, int64_t *, int64_t *, int64_t *,
+                        int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_perm_stats");
+    return fn ? fn(db, rows, nrows, ncols, observed, sum, sumsq, n_ge, n_le, pmin, pmax) : IGD_HIP_ERR_DEVICE;
+}
+
+int32_t igd_hip_permute_grid(int64_t n)
+{
+    typedef int32_t (*fn_t)(int64_t);
+    RESOLVE(fn_t, "igd_hip_permute_grid");
+    return fn ? fn(n) : 0;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

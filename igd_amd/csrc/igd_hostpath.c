@@ -932,6 +932,165 @@ int igdc_cooccur_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
     return rc;
 }
 
+/* Permutation null of region-set support on the host: what igd_hip_permute_support computes (include/igd_hip.h has the
+ * generator and the definitions).  igdc_permute_regions_host is kernel igd_permute_regions, igdc_permute_host the whole test:
+ * the set as given through igdc_support_host, then threads over the permutations (thread k takes p = k, k + T, ..), each with
+ * its own permuted arrays, row and stamp array, walking a permuted set with the per-query code of igdc_support_host and
+ * folding the row into its own statistics; the threads' statistics are combined at the end.  All outputs are DEFINED. */
+int igdc_permute_regions_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                              int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe)
+{
+    if (nq < 0 || np < 0 || p0 < 0 || nctg < 0 || (nctg > 0 && !ctg_len) || (nq > 0 && (!ichr || !qs || !qe)) ||
+        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE))
+        return -1;
+    for (int64_t p = 0; p < np; p++) {
+        const uint64_t base = igd_hip_perm_base(seed, (uint64_t)(p0 + p));
+        int32_t *os = out_qs + p * nq, *oe = out_qe + p * nq;
+        for (int64_t i = 0; i < nq; i++) {
+            os[i] = qs[i]; oe[i] = qe[i];
+            igd_hip_perm_place(mode, base, ichr[i], i, ctg_len, nctg, &os[i], &oe[i]);
+        }
+    }
+    return 0;
+}
+
+/* the first region on a known contig that breaks 0 <= s <= e <= L, L >= 1; -1: none */
+int64_t igdc_permute_first_bad(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg)
+{
+    for (int64_t i = 0; i < nq; i++) {
+        const int32_t c = ichr[i];
+        if (c < 0 || c >= nctg) continue;
+        if (ctg_len[c] < 1 || qs[i] < 0 || qe[i] < qs[i] || qe[i] > ctg_len[c]) return i;
+    }
+    return -1;
+}
+
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe, *ctg_len;
+    int64_t nq, nperm;
+    int mode; uint64_t seed;
+    int32_t v; int use_v, rule;
+    const int64_t *observed;
+    int64_t *acc;           /* sum, sumsq, n_ge, n_le, min, max: nFiles + 1 words each */
+    int32_t *ps, *pe;       /* the permuted set */
+    int64_t *row, *last;
+    int k, T, io_failed;
+} perm_job;
+
+static void *perm_run(void *arg)
+{
+    perm_job *P = (perm_job *)arg;
+    const int64_t nF = P->db->nFiles, nC = nF + 1;
+    for (int64_t p = P->k; p < P->nperm && !P->io_failed; p += P->T) {
+        (void)igdc_permute_regions_host(P->ichr, P->qs, P->qe, P->nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, p, 1, P->ps, P->pe);
+        memset(P->row, 0, sizeof(int64_t) * (size_t)nC);
+        memset(P->last, 0, sizeof(int64_t) * (size_t)nC);
+        host_job J;
+        memset(&J, 0, sizeof J);
+        J.db = P->db; J.m = P->m; J.ichr = P->ichr; J.qs = P->ps; J.qe = P->pe;
+        J.lo = 0; J.hi = P->nq; J.v = P->v; J.use_v = P->use_v; J.rule = P->rule;
+        J.hits = P->row; J.last = P->last;
+        host_run(&J);
+        if (J.io_failed) { P->io_failed = 1; break; }
+        P->row[nF] = J.total;
+        for (int64_t f = 0; f < nC; f++) {
+            const int64_t x = P->row[f];
+            P->acc[f] += x;
+            P->acc[nC + f] += x * x;
+            P->acc[2 * nC + f] += x >= P->observed[f];
+            P->acc[3 * nC + f] += x <= P->observed[f];
+            if (x < P->acc[4 * nC + f]) P->acc[4 * nC + f] = x;
+            if (x > P->acc[5 * nC + f]) P->acc[5 * nC + f] = x;
+        }
+    }
+    return NULL;
+}
+
+int igdc_permute_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                      const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                      int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax)
+{
+    if (!db || !m || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) ||
+        nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() ||
+        (unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63 ||
+        igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0)
+        return -1;
+    const int64_t nF = db->nFiles, nC = nF + 1;
+    int T = host_threads(nq * nperm > 0 ? nq * nperm : 1);
+    if (T > nperm) T = (int)nperm;
+    /* per thread: 6 statistics, row and stamps (8 nC words), the permuted set (2 nq int32); + the observed row */
+    int64_t *w = (int64_t *)calloc((size_t)T * 8 * (size_t)nC + (size_t)nC, sizeof(int64_t));
+    int32_t *pq = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 2 * (size_t)nq + 1));
+    int rc = w && pq ? 0 : -1;
+    int64_t *obs = w ? w + (size_t)T * 8 * (size_t)nC : NULL;
+    if (rc == 0 && nq > 0) rc = igdc_support_host(db, m, ichr, qs, qe, nq, v, rule, obs, &obs[nF]);
+    perm_job job[64];
+    pthread_t th[64];
+    int started[64];
+    for (int k = 0; k < T && rc == 0; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe; job[k].ctg_len = ctg_len;
+        job[k].nq = nq; job[k].nperm = nperm; job[k].mode = mode; job[k].seed = seed;
+        job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1; job[k].rule = rule;
+        job[k].observed = obs;
+        job[k].acc = w + (size_t)k * 8 * (size_t)nC;
+        job[k].row = job[k].acc + 6 * nC; job[k].last = job[k].row + nC;
+        job[k].ps = pq + (size_t)k * 2 * (size_t)nq; job[k].pe = job[k].ps + nq;
+        job[k].k = k; job[k].T = T;
+        for (int64_t f = 0; f < nC; f++) { job[k].acc[4 * nC + f] = INT64_MAX; job[k].acc[5 * nC + f] = INT64_MIN; }
+    }
+    if (rc == 0) {
+        for (int k = 1; k < T; k++) {
+            started[k] = pthread_create(&th[k], NULL, perm_run, &job[k]) == 0;
+            if (!started[k]) perm_run(&job[k]);
+        }
+        perm_run(&job[0]);
+        for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
+        for (int k = 0; k < T; k++) if (job[k].io_failed) rc = -1;
+    }
+    if (rc == 0) {
+        int64_t *a0 = job[0].acc;
+        for (int k = 1; k < T; k++)
+            for (int64_t f = 0; f < nC; f++) {
+                const int64_t *a = job[k].acc;
+                for (int s = 0; s < 4; s++) a0[s * nC + f] += a[s * nC + f];
+                if (a[4 * nC + f] < a0[4 * nC + f]) a0[4 * nC + f] = a[4 * nC + f];
+                if (a[5 * nC + f] > a0[5 * nC + f]) a0[5 * nC + f] = a[5 * nC + f];
+            }
+        int64_t *const out[6] = {sum, sumsq, n_ge, n_le, pmin, pmax};
+        memcpy(observed, obs, sizeof(int64_t) * (size_t)nC);
+        for (int s = 0; s < 6; s++) if (out[s]) memcpy(out[s], a0 + s * nC, sizeof(int64_t) * (size_t)nC);
+    }
+    free(w); free(pq);
+    return rc;
+}
+
+/* mean, sd, z and the two one-sided permutation p-values (as -log10) of n columns; igd_core.h has the formulas.  sqrt by
+ * weak reference, as log10 above.  0, or -1 without a C math library. */
+#pragma weak sqrt
+int igdc_perm_summary(const int64_t *observed, const int64_t *sum, const int64_t *sumsq, const int64_t *n_ge, const int64_t *n_le,
+                       int64_t nperm, int64_t n, double *mean, double *sd, double *z, double *nlog10_p_upper, double *nlog10_p_lower)
+{
+    const double P = (double)nperm, nan = __builtin_nan("");
+    if (!sqrt || !log10 || nperm < 1 || n < 0 || (n > 0 && (!observed || !sum || !sumsq || !n_ge || !n_le))) return -1;
+    for (int64_t f = 0; f < n; f++) {
+        const double mu = (double)sum[f] / P;
+        double s = nan;
+        if (nperm > 1) {
+            const __int128 num = (__int128)nperm * (__int128)sumsq[f] - (__int128)sum[f] * (__int128)sum[f];
+            s = sqrt((double)num / (P * (P - 1.0)));
+        }
+        if (mean) mean[f] = mu;
+        if (sd) sd[f] = s;
+        if (z) z[f] = (s != s || s == 0.0) ? nan : ((double)observed[f] - mu) / s;
+        if (nlog10_p_upper) nlog10_p_upper[f] = 0.0 - log10((double)(n_ge[f] + 1) / (P + 1.0));
+        if (nlog10_p_lower) nlog10_p_lower[f] = 0.0 - log10((double)(n_le[f] + 1) / (P + 1.0));
+    }
+    return 0;
+}
+
 /* The handle flavours' batches (Python search_n / search_1, R search_nr / getOverlaps): on the host while the batch is
  * small and no engine is resident, otherwise on the engine, which is attached at the first batch that needs it -- the
  * moment the reference would do its first fseek/fread (src/igd_search.c:469-476); open_iGD reads the header only, like

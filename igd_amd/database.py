@@ -29,6 +29,9 @@ def _i32(a):
 Enrichment = collections.namedtuple("Enrichment", "support usupport b c d pvalue_log odds_ratio clamped")
 RestrictedEnrichment = collections.namedtuple("RestrictedEnrichment", "support usupport b c d pvalue_log odds_ratio size bits")
 EnrichmentRanks = collections.namedtuple("EnrichmentRanks", "qvalue_log rnk_sup rnk_pv rnk_or max_rnk mean_rnk")
+PermutationSupport = collections.namedtuple("PermutationSupport", "observed sum sumsq n_ge n_le min max nperm")
+PermutationSummary = collections.namedtuple("PermutationSummary", "mean sd z nlog10_p_upper nlog10_p_lower")
+PERM_MODES = {"circular": 0, "shuffle": 1}           # IGD_HIP_PERM_CIRCULAR, IGD_HIP_PERM_SHUFFLE
 
 
 def _tables(a, b, c, d, what):
@@ -230,6 +233,91 @@ def cooccur_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None):
             os.close(fd)
         L.igdc_close(core)
     return cooc, nhit.value
+
+
+def _perm_mode(mode, what):
+    if mode not in PERM_MODES:
+        raise IgdError("%s: mode must be 'circular' or 'shuffle', not %r" % (what, mode))
+    return PERM_MODES[mode]
+
+
+def _perm_regions(ichr, qs, qe, ctg_len, what):
+    ichr, qs, qe, ctg_len = _i32(ichr), _i32(qs), _i32(qe), _i32(ctg_len)
+    if len(ichr) != len(qs) or len(qe) != len(qs) or ctg_len.ndim != 1:
+        raise IgdError("%s: %d / %d / %d regions given" % (what, len(ichr), len(qs), len(qe)))
+    return ichr, qs, qe, ctg_len
+
+
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+def permute_regions_host(ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"):
+    """Permutations [p0, p0 + np_) of a region list on the host (igdc_permute_regions_host; no device is touched):
+    (qs, qe) int32[np_, nq] as Database.permute_regions() defines them."""
+    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_regions_host")
+    oqs, oqe = np.empty((int(np_), len(qs)), np.int32), np.empty((int(np_), len(qs)), np.int32)
+    if N.cli().igdc_permute_regions_host(_ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len),
+                                         _perm_mode(mode, "permute_regions_host"), int(seed) & (2 ** 64 - 1), int(p0), int(np_),
+                                         _ptr(oqs), _ptr(oqe)) != 0:
+        raise IgdError("permute_regions_host: bad argument")
+    return oqs, oqe
+
+
+def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
+    """The permutation null of the support counts on the host (igdc_permute_host: pread on the .igd, threads over the
+    permutations; no device is touched): a PermutationSupport as Database.permutation_support() defines it."""
+    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_host")
+    pm = _perm_mode(mode, "permute_host")
+    L = N.cli()
+    core = L.igdc_open(igd_path.encode())
+    if not core:
+        raise IgdError("cannot read .igd header of %s" % igd_path)
+    fd = -1
+    m = None
+    try:
+        tsv = L.igdc_index_path(igd_path.encode())
+        rc = L.igdc_load_index(core, C.cast(tsv, C.c_char_p))
+        N.free(tsv)
+        if rc != 0:
+            raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
+        nf, gtype, nctg = core.contents.nFiles, core.contents.gType, core.contents.nCtg
+        if len(ctg_len) != nctg:
+            raise IgdError("permute_host: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), nctg))
+        if rule is None:
+            rule, vf = Database.cli_dispatch(gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        fd = os.open(igd_path, os.O_RDONLY)
+        m = L.igdc_map_open(core, fd)
+        if not m:
+            raise IgdError("cannot map %s" % igd_path)
+        out = [np.empty(nf + 1, np.int64) for _ in range(7)]
+        if L.igdc_permute_host(core, m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, int(seed) & (2 ** 64 - 1), int(nperm),
+                               vf, rule, *[a.ctypes.data for a in out]) != 0:
+            raise IgdError("permute_host: a refused argument (number of permutations, a region outside its contig), or a tile of %s "
+                           "could not be read" % igd_path)
+    finally:
+        if m:
+            L.igdc_map_close(m)
+        if fd >= 0:
+            os.close(fd)
+        L.igdc_close(core)
+    return PermutationSupport(*out, int(nperm))
+
+
+def perm_summary(ps):
+    """mean, standard deviation (ddof = 1), z-score and -log10 of the one-sided permutation p-values (n_ge + 1) / (P + 1) and
+    (n_le + 1) / (P + 1) of a PermutationSupport (igdc_perm_summary: the variance's numerator is exact): a PermutationSummary
+    of float64 arrays.  sd is NaN for one permutation, z is NaN where sd is 0 or NaN."""
+    a = [np.ascontiguousarray(x, dtype=np.int64) for x in (ps.observed, ps.sum, ps.sumsq, ps.n_ge, ps.n_le)]
+    n = len(a[0])
+    if any(x.shape != (n,) for x in a):
+        raise IgdError("perm_summary: arrays of different lengths")
+    out = [np.empty(n, np.float64) for _ in range(5)]
+    if N.cli().igdc_perm_summary(*[_ptr(x) for x in a], int(ps.nperm), n, *[_ptr(x) for x in out]) != 0:
+        raise IgdError("perm_summary: bad argument")
+    return PermutationSummary(*out)
 
 
 class Database:
@@ -678,6 +766,73 @@ class Database:
         _chk(self._H.igd_hip_bitrows_gram(self.dev, a.ctypes.data if a.size else None, m, pb, n, a.shape[1],
                                           out.ctypes.data if out.size else None), "igd_hip_bitrows_gram")
         return out
+
+    def permutation_support(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
+        """Permutation null of the support counts of one region set (igd_hip_permute_support).  The set is moved nperm times
+        -- mode "circular": one rigid shift per permutation and contig, a region that would cross the contig's end is pushed
+        back against it; "shuffle": every region placed anew on its contig -- with the generator of include/igd_hip.h; every
+        permuted set is counted as support() counts.  ctg_len: int32[nctg], the contig lengths in the database's contig
+        order (read_genome()).  Returns PermutationSupport(observed, sum, sumsq, n_ge, n_le, min, max, nperm), int64[nfiles + 1]
+        each: the support as given, and over the permuted supports x their sum, sum of squares, the permutations with
+        x >= observed and x <= observed, the smallest and the largest; index nfiles is the regions with a hit in any file.
+        The permuted regions and the permutations x files matrix never leave the device.  perm_summary() gives mean, sd, z
+        and p.  A region on a known contig that does not lie within its length raises IgdError."""
+        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_support")
+        if len(ctg_len) != self.nctg:
+            raise IgdError("permutation_support: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), self.nctg))
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        out = [np.empty(self.nfiles + 1, np.int64) for _ in range(7)]
+        _chk(self._H.igd_hip_permute_support(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len),
+                                             _perm_mode(mode, "permutation_support"), int(seed) & (2 ** 64 - 1), int(nperm), vf, rule,
+                                             *[a.ctypes.data for a in out]), "igd_hip_permute_support")
+        return PermutationSupport(*out, int(nperm))
+
+    def read_genome(self, path):
+        """int32[nctg]: the contig lengths of a genome file (`name<TAB>length` per line) in the database's contig order; 0 for
+        a contig the file does not name."""
+        ln = np.zeros(max(self.nctg, 1), np.int32)
+        bad = C.c_int64(0)
+        rc = self._L.igdc_read_genome(self._core, path.encode(), ln.ctypes.data, C.byref(bad))
+        if rc == -1:
+            raise IOError("cannot open genome file %s" % path)
+        if rc != 0:
+            raise IgdError("genome file %s, line %d: not a name, a tab and a length of at most 2147483647" % (path, bad.value))
+        return ln[:self.nctg]
+
+    def permutation_support_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0):
+        """The permutation null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the
+        integers behind what `igd search -q path -P nperm -g genome_path` prints."""
+        return self.permutation_support(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v)
+
+    def permute_regions(self, ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"):
+        """Kernel igd_permute_regions on host arrays (igd_hip_permute_regions): (qs, qe) int32[np_, nq], row k the regions
+        under permutation p0 + k.  ctg_len is the caller's: len(ctg_len) contigs, not tied to the database; a region with
+        ichr outside [0, len(ctg_len)) passes through unchanged."""
+        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_regions")
+        oqs, oqe = np.empty((int(np_), len(qs)), np.int32), np.empty((int(np_), len(qs)), np.int32)
+        _chk(self._H.igd_hip_permute_regions(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len),
+                                             _perm_mode(mode, "permute_regions"), int(seed) & (2 ** 64 - 1), int(p0), int(np_),
+                                             _ptr(oqs), _ptr(oqe)), "igd_hip_permute_regions")
+        return oqs, oqe
+
+    def perm_stats(self, rows, observed, out=None):
+        """Kernel igd_perm_stats on host arrays (igd_hip_perm_stats): rows int64[nrows, ncols], observed int64[ncols]; returns
+        (sum, sumsq, n_ge, n_le, min, max), int64[ncols] each, over the rows of every column.  out, when given, is a list of
+        six int64[ncols] arrays that are overwritten."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        observed = np.ascontiguousarray(observed, dtype=np.int64)
+        if rows.ndim != 2 or observed.shape != (rows.shape[1],):
+            raise IgdError("perm_stats: rows must be int64[nrows, ncols] and observed int64[ncols]")
+        if out is None:
+            out = [np.empty(rows.shape[1], np.int64) for _ in range(6)]
+        elif len(out) != 6 or any(a.dtype != np.int64 or a.shape != (rows.shape[1],) or not a.flags.c_contiguous for a in out):
+            raise IgdError("perm_stats: out must be six C-ordered int64[%d]" % rows.shape[1])
+        _chk(self._H.igd_hip_perm_stats(self.dev, _ptr(rows), rows.shape[0], rows.shape[1], _ptr(observed),
+                                        *[_ptr(a) for a in out]), "igd_hip_perm_stats")
+        return tuple(out)
 
     def membership_files(self, paths, v=0):
         """The rows of several BED files (read as `igd search -q` reads them), concatenated: (bits, nfiles_hit, nhit

@@ -314,6 +314,94 @@ int32_t igd_hip_gram_tile(void);
 int32_t igd_hip_gram_kstep(void);
 int64_t igd_hip_gram_slices(int64_t m, int64_t n, int64_t nwords32);
 
+/* Permutation null for region-set support: the set is moved around the genome nperm times, every permuted set is counted as
+ * igd_hip_support_sets counts a set, and per file the observed support is placed among the permuted ones.  No universe.
+ *
+ * THE GENERATOR (the one definition: kernel igd_permute_regions, igdc_permute_regions_host and the tests' numpy reference
+ * agree bit for bit).  All arithmetic is unsigned 64-bit modulo 2^64.
+ *     G        = 0x9E3779B97F4A7C15
+ *     mix64(z) : z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  return z ^ z >> 31
+ *     r(p, k)  = mix64( mix64( mix64(seed + G) + (p + 1) * G ) + (k + 1) * G )        p = permutation number, k = key
+ * A region (c, s, e) with 0 <= c < nctg, len = e - s, L = ctg_len[c]; valid input has 0 <= s <= e <= L and L >= 1.
+ *     IGD_HIP_PERM_CIRCULAR  a rigid shift, one offset per permutation and contig: k = c;  s' = (s + r(p, c) mod L) mod L in 64
+ *                            bits;  len == L: s' = 0;  otherwise s' + len > L: s' = L - len -- a region that would cross the
+ *                            contig's end is pushed back against it: its width is kept, it is never split;  e' = s' + len.
+ *     IGD_HIP_PERM_SHUFFLE   independent placement on the same contig: k = i, the region's position in the call's arrays;
+ *                            s' = r(p, i) mod (L - len + 1);  e' = s' + len.
+ * A region with c < 0 or c >= nctg overlaps nothing: it passes through unchanged and is not validated.  (So does, in the
+ * kernels' generic entry alone, an invalid region on a known contig; igd_hip_permute_support refuses those.)  `mod` is biased
+ * towards small offsets by at most 2^-32 (L < 2^31 against a 64-bit draw); nothing is done about it. */
+#define IGD_HIP_PERM_CIRCULAR 0
+#define IGD_HIP_PERM_SHUFFLE  1
+#define IGD_HIP_PERM_MAX ((int64_t)1 << 20)          /* permutations of one call */
+#if defined(__HIPCC__)
+#define IGD_HIP_HD_ __host__ __device__
+#else
+#define IGD_HIP_HD_
+#endif
+static inline IGD_HIP_HD_ uint64_t igd_hip_perm_mix64(uint64_t z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+/* mix64(mix64(seed + G) + (p + 1) * G): what r(p, k) shares between the keys of permutation p */
+static inline IGD_HIP_HD_ uint64_t igd_hip_perm_base(uint64_t seed, uint64_t p)
+{
+    const uint64_t a = igd_hip_perm_mix64(seed + 0x9E3779B97F4A7C15ull);
+    const uint64_t b = igd_hip_perm_mix64(a + (p + 1) * 0x9E3779B97F4A7C15ull);
+    return b;
+}
+/* region i = (c, *s, *e) under permutation p (base = igd_hip_perm_base(seed, p)), in place */
+static inline IGD_HIP_HD_ void igd_hip_perm_place(int mode, uint64_t base, int32_t c, int64_t i, const int32_t *ctg_len, int32_t nctg,
+                                                  int32_t *s, int32_t *e)
+{
+    if (c < 0 || c >= nctg) return;
+    const int64_t L = ctg_len[c], s0 = *s, len = (int64_t)*e - s0;
+    if (L < 1 || s0 < 0 || len < 0 || s0 + len > L) return;
+    const uint64_t k = mode == IGD_HIP_PERM_SHUFFLE ? (uint64_t)i : (uint64_t)c;
+    const uint64_t r = igd_hip_perm_mix64(base + (k + 1) * 0x9E3779B97F4A7C15ull);
+    int64_t t;
+    if (mode == IGD_HIP_PERM_SHUFFLE) t = (int64_t)(r % (uint64_t)(L - len + 1));
+    else {
+        t = (int64_t)(((uint64_t)s0 + r % (uint64_t)L) % (uint64_t)L);
+        if (len == L) t = 0;
+        else if (t + len > L) t = L - len;
+    }
+    *s = (int32_t)t;
+    *e = (int32_t)(t + len);
+}
+/* The whole test on one device.  ctg_len is int32[number of contigs of db], in the database's contig order.  Index nFiles of
+ * every output is the "any dataset" column: the regions with a hit in any file, what igd_hip_support_sets adds to nhit.
+ *     observed[f] = support of the set as given                          sum[f], sumsq[f] = over the permutations, of x and x^2
+ *     n_ge[f], n_le[f] = permutations with x >= observed[f], x <= observed[f]      pmin[f], pmax[f] = smallest, largest x
+ * with x = the support of file f in one permuted set.  Each array is int64[nFiles + 1]; all but observed may be NULL; all are
+ * DEFINED by the call.  The regions are uploaded once; the permutations go through in chunks of pc permutations with
+ * pc * nq <= igd_hip_max_batch() and pc * nFiles * 8 <= the row budget of igd_hip_support_sets (TEST-ONLY: IGD_HIP_PERM_ROW_BYTES
+ * lowers it): kernel igd_permute_regions into the staging arrays, one row per permutation through igd_sets_support (both
+ * forms), kernel igd_perm_stats over the chunk's rows and totals into resident statistics.  The permuted regions and the
+ * rows never leave the device.  Blocking.  IGD_HIP_ERR_ARG, before any launch and with nothing of the caller's written: a
+ * missing array, no such rule or mode, nperm < 1 or > IGD_HIP_PERM_MAX, nq > igd_hip_max_batch(), nperm * nq^2 >= 2^63 (sumsq),
+ * a region on a known contig that breaks 0 <= s <= e <= L, L >= 1 (igd_hip_last_error names the first one).
+ * Not done: several sets in one call, a universe-restricted shuffle, regions split at the contig's end, several devices. */
+int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                            int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
+                            int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax);
+/* The two kernels on host arrays (db names the device and owns the workspaces; its records are not read).
+ * igd_hip_permute_regions: permutations [p0, p0 + np) of nq regions into out_qs, out_qe (int32[np * nq], permutation-major);
+ * nctg is the caller's, not tied to the database.  IGD_HIP_ERR_ARG for a missing array, no such mode, a negative size,
+ * nq > igd_hip_max_batch() or more than 2^31 - 1 outputs.
+ * igd_hip_perm_stats: rows is int64[nrows * ncols]; sum .. pmax (int64[ncols], each may be NULL) are DEFINED as above with
+ * x = rows[r][col]; sums wrap modulo 2^64.  The rows go through in chunks of the same row budget, the statistics stay
+ * resident between them.  IGD_HIP_ERR_ARG for a missing array or nrows < 1 or ncols < 1.
+ * igd_hip_permute_grid: workgroups igd_permute_regions is launched with for n outputs (tests: a lane takes a second output
+ * only when n exceeds the grid's lanes). */
+int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                            int32_t nctg, int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe);
+int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t nrows, int64_t ncols, const int64_t *observed, int64_t *sum,
+                       int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax);
+int32_t igd_hip_permute_grid(int64_t n);
+
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
  * `stream` (a hipStream_t; NULL = the engine's own stream) and returns without waiting.
