@@ -104,6 +104,10 @@ def orc():
                                             C.POINTER(OrcHit), C.c_int64]
         lib.orc_getMap.restype = C.c_int64
         lib.orc_getMap.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.orc_seq_overlaps.restype = C.c_int64
+        lib.orc_seq_overlaps.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, i32p, C.c_int64]
+        lib.orc_seqOverlaps.restype = C.c_int
+        lib.orc_seqOverlaps.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
         lib.free = C.CDLL(None).free
         lib.free.argtypes = [C.c_void_p]
         _orc = lib
@@ -195,6 +199,28 @@ class Oracle:
         else:
             ret = self.lib.orc_getOverlaps(self.h, qfile.encode(), _p64(hits))
         return hits[: self.nfiles], ret
+
+    def file_nr(self):
+        """regions per dataset (the index file's third column)"""
+        return np.array([self.lib.orc_file_nr(self.h, m) for m in range(self.nfiles)], np.int64)
+
+    def seq_overlaps(self, chrom, qs, qe):
+        """orc_seq_overlaps for one interval: int32[n, 4] = (idx_t, idx_g, idx_f, bits of the float similarity) per overlap,
+        in discovery order."""
+        cap = getattr(self, "_seq_cap", 4096)
+        while True:
+            buf = np.empty((cap, 4), np.int32)
+            n = self.lib.orc_seq_overlaps(self.h, chrom.encode(), int(qs), int(qe), _p32(buf), cap)
+            if n <= cap:
+                return buf[:n].copy()
+            cap = self._seq_cap = 2 * int(n)
+
+    def seqpare_file(self, qfile):
+        """orc_seqOverlaps: the raw double sm[nFiles] of `search -q qfile -s`."""
+        sm = np.full(max(self.nfiles, 1), np.nan, np.float64)
+        if self.lib.orc_seqOverlaps(self.h, qfile.encode(), sm.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+            raise IOError(qfile)
+        return sm[: self.nfiles]
 
 
 # --------------------------------------------------------------------------------------
