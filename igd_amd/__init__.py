@@ -3,7 +3,8 @@ path), behind the reference's own C ABI.  See DESIGN.md / INTEGRATION.md."""
 from ._native import NativeMissing, build  # noqa: F401
 
 __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "restrict_host", "enrich_restricted_host",
-           "cooccur_host", "bitrows_gram_host", "jaccard", "perm_summary", "permute_regions_host", "permute_host"]
+           "cooccur_host", "bitrows_gram_host", "jaccard", "perm_summary", "permute_regions_host", "permute_host", "MinOverlap",
+           "search_host", "support_host"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -23,7 +24,8 @@ def __getattr__(name):
     if name == "enrich_restricted_host":
         from .database import enrich_restricted_host
         return enrich_restricted_host
-    if name in ("cooccur_host", "bitrows_gram_host", "jaccard", "perm_summary", "permute_regions_host", "permute_host"):
+    if name in ("cooccur_host", "bitrows_gram_host", "jaccard", "perm_summary", "permute_regions_host", "permute_host", "MinOverlap",
+                "search_host", "support_host"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

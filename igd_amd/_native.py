@@ -145,6 +145,9 @@ def hip():
                                           C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.igd_hip_support_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
+        # the `_ov` forms: the same arguments, then a pointer to an igd_hip_min_overlap (three int32; NULL: no threshold)
+        L.igd_hip_search_sets_ov.argtypes = L.igd_hip_search_sets.argtypes + [C.c_void_p]
+        L.igd_hip_support_sets_ov.argtypes = L.igd_hip_support_sets.argtypes + [C.c_void_p]
         L.igd_hip_coverage_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
         L.igd_hip_member_words.argtypes = [C.c_void_p]
@@ -155,6 +158,8 @@ def hip():
         L.igd_hip_enrich_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # igd_hip_enrich_sets' arguments, nhit, unhit, min_overlap
+        L.igd_hip_enrich_sets_ov.argtypes = L.igd_hip_enrich_sets.argtypes + [C.c_void_p] * 3
         # sets restricted to the universe: db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, bits, size
         L.igd_hip_restrict_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -188,6 +193,7 @@ def hip():
         # permutation null: db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, min, max
         L.igd_hip_permute_support.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
                                               C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 7
+        L.igd_hip_permute_support_ov.argtypes = L.igd_hip_permute_support.argtypes + [C.c_void_p]
         # db, ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe / db, rows, nrows, ncols, observed, 6 outputs
         L.igd_hip_permute_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int,
                                               C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
@@ -280,6 +286,11 @@ def _bind_core(L):
     L.igdc_map_close.argtypes = [C.c_void_p]
     L.igdc_support_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                     C.c_void_p, C.POINTER(C.c_int64)]
+    # pair counts on the host: db, map, ichr, qs, qe, nq, v, rule, hits, total; the `_ov` twins take a pointer to an
+    # igd_hip_min_overlap (NULL: no threshold) after the plain function's arguments
+    L.igdc_search_host.argtypes = L.igdc_support_host.argtypes
+    L.igdc_search_host_ov.argtypes = L.igdc_search_host.argtypes + [C.c_void_p]
+    L.igdc_support_host_ov.argtypes = L.igdc_support_host.argtypes + [C.c_void_p]
     # covered base pairs on the host: the same arguments, coverage and covered in place of support and nhit
     L.igdc_coverage_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                      C.c_void_p, C.POINTER(C.c_int64)]
@@ -313,6 +324,7 @@ def _bind_core(L):
     # db, map, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, min, max
     L.igdc_permute_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
                                     C.c_int64, C.c_int32, C.c_int] + [C.c_void_p] * 7
+    L.igdc_permute_host_ov.argtypes = L.igdc_permute_host.argtypes + [C.c_void_p]
     # observed, sum, sumsq, n_ge, n_le, nperm, n, mean, sd, z, nlog10_p_upper, nlog10_p_lower
     L.igdc_perm_summary.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int64] + [C.c_void_p] * 5
     # db, path, len (int32[nCtg]), bad_line

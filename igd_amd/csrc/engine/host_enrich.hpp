@@ -74,11 +74,17 @@ extern "C" int igd_hip_fisher_tables(igd_hip_db *db, const int64_t *a, const int
 
 // igd_hip_enrich_sets and, for a caller that also prints them (the command line tool), the regions with any hit: nhit[nsets]
 // and *unhit, DEFINED like the rest (both may be NULL)
-extern "C" int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
-                                        int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, int32_t v,
-                                        int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
-                                        int64_t *clamped, int64_t *nhit, int64_t *unhit)
+// min_overlap: the sets' and the universe's supports are both taken under it (igd_hip_support_sets_ov); NULL: no threshold
+extern "C" int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                                      int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, int32_t v,
+                                      int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
+                                      int64_t *clamped, int64_t *nhit, int64_t *unhit, const igd_hip_min_overlap *min_overlap)
 {
+    if (!igd_hip_min_overlap_valid(min_overlap)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_enrich_sets: min_overlap (%d bp, %d ppm, %d ppm) out of range", (int)min_overlap->min_bp,
+                 (int)min_overlap->ppm_query, (int)min_overlap->ppm_record);
+        return IGD_HIP_ERR_ARG;
+    }
     if (!db || nsets < 0 || nsets == INT32_MAX || nu < 0 || (nu > 0 && (!u_ichr || !u_qs || !u_qe)) || (db->nFiles > 0 && !usupport) ||
         (nsets > 0 && (!set_off || (db->nFiles > 0 && (!support || !pvalue_log)))) ||
         (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)) {
@@ -123,7 +129,7 @@ extern "C" int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, con
         off[0] = 0;
         for (int32_t k = 0; k < nsets; k++) { off[(size_t)k + 1] = set_off[k + 1]; nk[(size_t)k] = set_off[k + 1] - set_off[k]; }
         off[(size_t)nsets + 1] = tot;
-        const int rc = igd_hip_support_sets(db, cc.data(), cs.data(), ce.data(), off.data(), nsets + 1, v, rule, rows.data(), hit.data());
+        const int rc = igd_hip_support_sets_ov(db, cc.data(), cs.data(), ce.data(), off.data(), nsets + 1, v, rule, rows.data(), hit.data(), min_overlap);
         if (rc != IGD_HIP_OK) return rc;
     }
     if (nF) memcpy(usupport, rows.data() + (size_t)ncell, (size_t)nF * 8);
@@ -159,6 +165,15 @@ extern "C" int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, con
         HIPCHK(hipStreamSynchronize(st));
     }
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                                        int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, int32_t v,
+                                        int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
+                                        int64_t *clamped, int64_t *nhit, int64_t *unhit)
+{
+    return igd_hip_enrich_sets_ov(db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, v, rule, support, usupport, pvalue_log, odds_ratio,
+                                  clamped, nhit, unhit, nullptr);
 }
 
 extern "C" int igd_hip_enrich_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,

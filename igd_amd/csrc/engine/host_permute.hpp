@@ -69,11 +69,18 @@ static void perm_copy_out(const int64_t *res, int64_t nC, int64_t *const out[7])
         if (out[a]) memcpy(out[a], res + a * nC, (size_t)nC * 8);
 }
 
-extern "C" int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule,
-                                       int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
-                                       int64_t *pmax)
+extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule,
+                                          int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
+                                          int64_t *pmax, const igd_hip_min_overlap *min_overlap)
 {
+    if (!igd_hip_min_overlap_valid(min_overlap)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: min_overlap (%d bp, %d ppm, %d ppm) out of range", (int)min_overlap->min_bp,
+                 (int)min_overlap->ppm_query, (int)min_overlap->ppm_record);
+        return IGD_HIP_ERR_ARG;
+    }
+    const bool ov = igd_hip_min_overlap_active(min_overlap);
+    const MinOv mo = min_ov_of(min_overlap);
     if (!db || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
         (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE)) {
         snprintf(g_err, sizeof g_err, "igd_hip_permute_support: bad argument");
@@ -150,21 +157,13 @@ extern "C" int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, cons
     HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)db->nCtg * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(db->d_setSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
 
-    const size_t ldsB = lds ? (size_t)(4 + nF + (IGD_SETS_WG / IGD_WAVE) * nW) * 4 : 0;
-    u64 *R = (u64 *)db->d_setRows, *T = (u64 *)db->d_setTot;
-    unsigned *B = (unsigned *)db->d_supBits;
     // `rows` zeroed rows counted from the query arrays (c, s, e): rows * perRow slices, a prefix of the table
     auto count = [&](const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows) -> int {
         const int ns = (int)(rows * perRow);
         const int grid = ns < maxGrid ? ns : (int)maxGrid;
         HIPCHK(hipMemsetAsync(db->d_setRows, 0, (size_t)(rows * nF) * 8, st));
         HIPCHK(hipMemsetAsync(db->d_setTot, 0, (size_t)rows * 8, st));
-        if (useV && lds) igd_sets_support<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
-        else if (useV) igd_sets_support<true, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
-        else if (lds) igd_sets_support<false, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
-        else igd_sets_support<false, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
-        HIPCHK(hipGetLastError());
-        return IGD_HIP_OK;
+        return support_launch(db, img->v, c, s, e, ns, grid, krule, v, useV, lds, ov, mo);
     };
 
     // the set as given
@@ -185,6 +184,15 @@ extern "C" int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, cons
     HIPCHK(hipGetLastError());
     perm_copy_out(res.data(), nC, out);
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule,
+                                       int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
+                                       int64_t *pmax)
+{
+    return igd_hip_permute_support_ov(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax,
+                                      nullptr);
 }
 
 extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,

@@ -46,10 +46,24 @@ static int ensure_sets_ws(igd_hip_db *db, int64_t rowWords, int64_t rows, int64_
     return IGD_HIP_OK;
 }
 
-extern "C" int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
-                                   const int64_t *set_off, int32_t nsets, int32_t v, int rule, int flags,
-                                   int64_t *hits, int64_t *totals)
+// the kernel's copy of a caller's threshold (NULL or all zero: inactive -- the plain kernels are launched)
+static inline MinOv min_ov_of(const igd_hip_min_overlap *t)
 {
+    return igd_hip_min_overlap_active(t) ? MinOv{t->min_bp, t->ppm_query, t->ppm_record} : MinOv{0, 0, 0};
+}
+
+// With an active threshold EVERY set is cut into slices for igd_sets_count_ov: the batch pipeline takes no threshold.
+extern "C" int igd_hip_search_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                                      const int64_t *set_off, int32_t nsets, int32_t v, int rule, int flags,
+                                      int64_t *hits, int64_t *totals, const igd_hip_min_overlap *min_overlap)
+{
+    if (!igd_hip_min_overlap_valid(min_overlap)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_search_sets: min_overlap (%d bp, %d ppm, %d ppm) out of range", (int)min_overlap->min_bp,
+                 (int)min_overlap->ppm_query, (int)min_overlap->ppm_record);
+        return IGD_HIP_ERR_ARG;
+    }
+    const bool ov = igd_hip_min_overlap_active(min_overlap);
+    const MinOv mo = min_ov_of(min_overlap);
     if (!db || nsets < 0 || (nsets > 0 && (!set_off || !hits)) || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) ||
         ((flags & IGD_HIP_FLAG_SORTED) && (flags & IGD_HIP_FLAG_BUCKET))) {
         snprintf(g_err, sizeof g_err, "igd_hip_search_sets: bad argument");
@@ -81,7 +95,7 @@ extern "C" int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const in
     const int64_t nF = db->nFiles;
     const int64_t step = max_batch();
     const int64_t rowCap = IGD_SETS_ROW_BYTES / (nF * 8) > 0 ? IGD_SETS_ROW_BYTES / (nF * 8) : 1;
-    const int64_t bigMin = sets_big_min();
+    const int64_t bigMin = ov ? INT64_MAX : sets_big_min();
     const int bigFlags = flags & ~IGD_HIP_FLAG_ZERO_FIRST;
     int64_t nSmall = 0;
     for (int32_t k = 0; k < nsets; k++)
@@ -133,7 +147,11 @@ extern "C" int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const in
             const int grid = ns < IGD_SETS_GRID ? ns : IGD_SETS_GRID;
             const size_t ldsB = lds ? (size_t)nF * 8 : 0;
             u64 *R = (u64 *)db->d_setRows, *T = (u64 *)db->d_setTot;
-            if (useV && lds) igd_sets_count<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T);
+            if (ov && useV && lds) igd_sets_count_ov<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T, mo);
+            else if (ov && useV) igd_sets_count_ov<true, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T, mo);
+            else if (ov && lds) igd_sets_count_ov<false, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T, mo);
+            else if (ov) igd_sets_count_ov<false, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T, mo);
+            else if (useV && lds) igd_sets_count<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T);
             else if (useV) igd_sets_count<true, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T);
             else if (lds) igd_sets_count<false, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T);
             else igd_sets_count<false, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T);
@@ -166,4 +184,11 @@ extern "C" int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const in
         }
     }
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                                   const int64_t *set_off, int32_t nsets, int32_t v, int rule, int flags,
+                                   int64_t *hits, int64_t *totals)
+{
+    return igd_hip_search_sets_ov(db, ichr, qs, qe, set_off, nsets, v, rule, flags, hits, totals, nullptr);
 }

@@ -26,9 +26,38 @@ static int ensure_support_bits(igd_hip_db *db, int64_t words)
     return IGD_HIP_OK;
 }
 
-extern "C" int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
-                                    const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *support, int64_t *nhit)
+// igd_sets_support, or igd_sets_support_ov under an active threshold (mo), on `ns` slices of the table at db->d_setSlices
+static int support_launch(igd_hip_db *db, const DbView &view, const int32_t *c, const int32_t *s, const int32_t *e, int ns, int grid,
+                          int krule, int v, bool useV, bool lds, bool ov, MinOv mo)
 {
+    const int64_t nF = db->nFiles, nW = (nF + 31) / 32;
+    const size_t ldsB = lds ? (size_t)(4 + nF + (IGD_SETS_WG / IGD_WAVE) * nW) * 4 : 0;
+    hipStream_t st = db->stream;
+    u64 *R = (u64 *)db->d_setRows, *T = (u64 *)db->d_setTot;
+    unsigned *B = (unsigned *)db->d_supBits;
+    if (ov && useV && lds) igd_sets_support_ov<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(view, c, s, e, db->d_setSlices, ns, krule, v, R, T, B, mo);
+    else if (ov && useV) igd_sets_support_ov<true, false><<<grid, IGD_SETS_WG, ldsB, st>>>(view, c, s, e, db->d_setSlices, ns, krule, v, R, T, B, mo);
+    else if (ov && lds) igd_sets_support_ov<false, true><<<grid, IGD_SETS_WG, ldsB, st>>>(view, c, s, e, db->d_setSlices, ns, krule, v, R, T, B, mo);
+    else if (ov) igd_sets_support_ov<false, false><<<grid, IGD_SETS_WG, ldsB, st>>>(view, c, s, e, db->d_setSlices, ns, krule, v, R, T, B, mo);
+    else if (useV && lds) igd_sets_support<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(view, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
+    else if (useV) igd_sets_support<true, false><<<grid, IGD_SETS_WG, ldsB, st>>>(view, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
+    else if (lds) igd_sets_support<false, true><<<grid, IGD_SETS_WG, ldsB, st>>>(view, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
+    else igd_sets_support<false, false><<<grid, IGD_SETS_WG, ldsB, st>>>(view, c, s, e, db->d_setSlices, ns, krule, v, R, T, B);
+    HIPCHK(hipGetLastError());
+    return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_support_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                                       const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *support, int64_t *nhit,
+                                       const igd_hip_min_overlap *min_overlap)
+{
+    if (!igd_hip_min_overlap_valid(min_overlap)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_support_sets: min_overlap (%d bp, %d ppm, %d ppm) out of range", (int)min_overlap->min_bp,
+                 (int)min_overlap->ppm_query, (int)min_overlap->ppm_record);
+        return IGD_HIP_ERR_ARG;
+    }
+    const bool ov = igd_hip_min_overlap_active(min_overlap);
+    const MinOv mo = min_ov_of(min_overlap);
     if (!db || nsets < 0 || (nsets > 0 && (!set_off || !support)) || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)) {
         snprintf(g_err, sizeof g_err, "igd_hip_support_sets: bad argument");
         return IGD_HIP_ERR_ARG;
@@ -103,16 +132,7 @@ extern "C" int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const i
         HIPCHK(hipMemsetAsync(db->d_setRows, 0, (size_t)(rows * nF) * 8, st));
         HIPCHK(hipMemsetAsync(db->d_setTot, 0, (size_t)rows * 8, st));
         HIPCHK(hipMemcpyAsync(db->d_setSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-        {
-            const size_t ldsB = lds ? (size_t)(4 + nF + (IGD_SETS_WG / IGD_WAVE) * nW) * 4 : 0;
-            u64 *R = (u64 *)db->d_setRows, *T = (u64 *)db->d_setTot;
-            unsigned *B = (unsigned *)db->d_supBits;
-            if (useV && lds) igd_sets_support<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T, B);
-            else if (useV) igd_sets_support<true, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T, B);
-            else if (lds) igd_sets_support<false, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T, B);
-            else igd_sets_support<false, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, krule, v, R, T, B);
-            HIPCHK(hipGetLastError());
-        }
+        if ((rc = support_launch(db, img->v, db->d_qc, db->d_qs, db->d_qe, ns, grid, krule, v, useV, lds, ov, mo)) != IGD_HIP_OK) return rc;
         hrows.resize((size_t)(rows * nF));
         htot.resize((size_t)rows);
         HIPCHK(hipMemcpyAsync(hrows.data(), db->d_setRows, (size_t)(rows * nF) * 8, hipMemcpyDeviceToHost, st));
@@ -127,4 +147,10 @@ extern "C" int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const i
         }
     }
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                                    const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *support, int64_t *nhit)
+{
+    return igd_hip_support_sets_ov(db, ichr, qs, qe, set_off, nsets, v, rule, support, nhit, nullptr);
 }

@@ -20,11 +20,26 @@ struct SetSlice { int32_t row, a, b, pad; };         // 16 bytes: one scalar loa
 #define IGD_SETS_LDS_FILES 8192                      // 64-bit counters in 64 KiB of LDS
 #define IGD_SETS_GRID 2048                           // persistent workgroups (8 per CU of the MI355X's 256)
 
-template <bool USE_V, bool LDS>
-__global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_count(DbView db, const int32_t *__restrict__ q_ichr,
-                                                             const int32_t *__restrict__ q_qs, const int32_t *__restrict__ q_qe,
-                                                             const SetSlice *__restrict__ slices, int nSlices, int rule, int v,
-                                                             u64 *__restrict__ rows, u64 *__restrict__ totals)
+// The minimum overlap of the `_ov` kernels (include/igd_hip.h: igd_hip_min_overlap), by value in the kernel arguments.
+// OV = false: the fields are never read and the body below is the plain kernel's, instruction for instruction.
+// OV = true, per query and wave-uniform: need = igd_hip_min_overlap_need_q -- max(min_bp, 1, ceil(lenq * ppm_query / 10^6)), the
+// one 64-bit division of the test -- and a query that no record can satisfy (qe <= qs) is left before its tiles are looked up.
+// Per lane: ov = min(qe, end) - max(qs, start) as a 32-bit difference (records have 0 <= start < end), one compare against
+// need, and, behind a wave-uniform branch on ppm_record, ov * 10^6 >= (end - start) * ppm_record as two 64-bit products.
+struct MinOv { int32_t min_bp, ppm_query, ppm_record; };
+
+__device__ __forceinline__ bool min_ov_pair(int need, int ppmR, int qs, int qe, int s, int e)
+{
+    const int ov = (int)((unsigned)(qe < e ? qe : e) - (unsigned)(qs > s ? qs : s));
+    bool ok = ov >= need;
+    if (ppmR) ok = ok & ((int64_t)ov * IGD_HIP_PPM >= (int64_t)(int)((unsigned)e - (unsigned)s) * (int64_t)ppmR);
+    return ok;
+}
+
+template <bool USE_V, bool LDS, bool OV>
+__device__ __forceinline__ void sets_count_body(const DbView &db, const int32_t *__restrict__ q_ichr, const int32_t *__restrict__ q_qs,
+                                                const int32_t *__restrict__ q_qe, const SetSlice *__restrict__ slices, int nSlices,
+                                                int rule, int v, u64 *__restrict__ rows, u64 *__restrict__ totals, const MinOv mo)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     igd_lds_u64 *cnt = (igd_lds_u64 *)smem;
@@ -43,6 +58,11 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_count(DbView db, const i
             const int qs = __builtin_amdgcn_readfirstlane(q_qs[q]);
             const int qe = __builtin_amdgcn_readfirstlane(q_qe[q]);
             const int cc = __builtin_amdgcn_readfirstlane(q_ichr[q]);
+            int need = 0;
+            if (OV) {
+                need = __builtin_amdgcn_readfirstlane(igd_hip_min_overlap_need_q(mo.min_bp, mo.ppm_query, qs, qe));
+                if (need < 0) continue;
+            }
             int gt0, ntl;
             if (!query_span(db, cc, qs, qe, rule, gt0, ntl)) continue;
             gt0 = __builtin_amdgcn_readfirstlane(gt0);
@@ -70,6 +90,10 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_count(DbView db, const i
                         h0 = h0 & (v0 >= v);
                         h1 = h1 & (v1 >= v);
                     }
+                    if (OV) {
+                        h0 = h0 & min_ov_pair(need, mo.ppm_record, qs, qe, s0, e0);
+                        h1 = h1 & min_ov_pair(need, mo.ppm_record, qs, qe, s1, e1);
+                    }
                     if (LDS) {
                         if (h0) (void)__hip_atomic_fetch_add(cnt + x0, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         if (h1) (void)__hip_atomic_fetch_add(cnt + x1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -96,4 +120,25 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_count(DbView db, const i
             __syncthreads();
         }
     }
+}
+
+template <bool USE_V, bool LDS>
+__global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_count(DbView db, const int32_t *__restrict__ q_ichr,
+                                                             const int32_t *__restrict__ q_qs, const int32_t *__restrict__ q_qe,
+                                                             const SetSlice *__restrict__ slices, int nSlices, int rule, int v,
+                                                             u64 *__restrict__ rows, u64 *__restrict__ totals)
+{
+    sets_count_body<USE_V, LDS, false>(db, q_ichr, q_qs, q_qe, slices, nSlices, rule, v, rows, totals, MinOv{0, 0, 0});
+}
+
+// the same walk under a minimum overlap per pair (igd_hip_search_sets_ov with an active threshold).  amdgpu_num_sgpr: the threshold's
+// four scalars push the allocation past the 100 SGPRs that eight waves per SIMD leave each wave (the plain kernels use 94 .. 100);
+// capped there, two to six of them live in VGPR lanes (v_writelane / v_readlane, no scratch) and the occupancy stays the twins'.
+template <bool USE_V, bool LDS>
+__global__ __launch_bounds__(IGD_SETS_WG) __attribute__((amdgpu_num_sgpr(102))) void igd_sets_count_ov(DbView db, const int32_t *__restrict__ q_ichr,
+                                                                const int32_t *__restrict__ q_qs, const int32_t *__restrict__ q_qe,
+                                                                const SetSlice *__restrict__ slices, int nSlices, int rule, int v,
+                                                                u64 *__restrict__ rows, u64 *__restrict__ totals, MinOv mo)
+{
+    sets_count_body<USE_V, LDS, true>(db, q_ichr, q_qs, q_qe, slices, nSlices, rule, v, rows, totals, mo);
 }

@@ -46,11 +46,12 @@ __device__ __forceinline__ void support_mark(igd_lds_u32 *bits, igd_lds_u32 *cnt
     }
 }
 
-template <bool USE_V, bool LDS>
-__global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_support(DbView db, const int32_t *__restrict__ q_ichr,
-                                                               const int32_t *__restrict__ q_qs, const int32_t *__restrict__ q_qe,
-                                                               const SetSlice *__restrict__ slices, int nSlices, int rule, int v,
-                                                               u64 *__restrict__ rows, u64 *__restrict__ nhit, unsigned *__restrict__ gbits)
+// OV: the minimum overlap per pair of igd_sets_support_ov, as in sets_count_body (sets_dev.hpp); OV = false is the plain kernel
+template <bool USE_V, bool LDS, bool OV>
+__device__ __forceinline__ void sets_support_body(const DbView &db, const int32_t *__restrict__ q_ichr, const int32_t *__restrict__ q_qs,
+                                                  const int32_t *__restrict__ q_qe, const SetSlice *__restrict__ slices, int nSlices,
+                                                  int rule, int v, u64 *__restrict__ rows, u64 *__restrict__ nhit,
+                                                  unsigned *__restrict__ gbits, const MinOv mo)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -74,6 +75,11 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_support(DbView db, const
             const int qs = __builtin_amdgcn_readfirstlane(q_qs[q]);
             const int qe = __builtin_amdgcn_readfirstlane(q_qe[q]);
             const int cc = __builtin_amdgcn_readfirstlane(q_ichr[q]);
+            int need = 0;
+            if (OV) {
+                need = __builtin_amdgcn_readfirstlane(igd_hip_min_overlap_need_q(mo.min_bp, mo.ppm_query, qs, qe));
+                if (need < 0) continue;
+            }
             int gt0, ntl;
             if (!query_span(db, cc, qs, qe, rule, gt0, ntl)) continue;
             gt0 = __builtin_amdgcn_readfirstlane(gt0);
@@ -101,6 +107,10 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_support(DbView db, const
                         const int v1 = ok1 ? db.value[toff + j] : INT_MIN;
                         h0 = h0 & (v0 >= v);
                         h1 = h1 & (v1 >= v);
+                    }
+                    if (OV) {
+                        h0 = h0 & min_ov_pair(need, mo.ppm_record, qs, qe, s0, e0);
+                        h1 = h1 & min_ov_pair(need, mo.ppm_record, qs, qe, s1, e1);
                     }
                     if (h0) support_mark<LDS>(bits, cnt, gb, row, x0);
                     if (h1) support_mark<LDS>(bits, cnt, gb, row, x1);
@@ -143,4 +153,24 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_support(DbView db, const
             (void)__hip_atomic_fetch_add(nhit + sl.row, (u64)hitq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+
+template <bool USE_V, bool LDS>
+__global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_support(DbView db, const int32_t *__restrict__ q_ichr,
+                                                               const int32_t *__restrict__ q_qs, const int32_t *__restrict__ q_qe,
+                                                               const SetSlice *__restrict__ slices, int nSlices, int rule, int v,
+                                                               u64 *__restrict__ rows, u64 *__restrict__ nhit, unsigned *__restrict__ gbits)
+{
+    sets_support_body<USE_V, LDS, false>(db, q_ichr, q_qs, q_qe, slices, nSlices, rule, v, rows, nhit, gbits, MinOv{0, 0, 0});
+}
+
+// the same walk under a minimum overlap per pair (igd_hip_support_sets_ov, igd_hip_permute_support_ov with an active threshold)
+template <bool USE_V, bool LDS>
+__global__ __launch_bounds__(IGD_SETS_WG) __attribute__((amdgpu_num_sgpr(102))) void igd_sets_support_ov(DbView db, const int32_t *__restrict__ q_ichr,
+                                                                  const int32_t *__restrict__ q_qs, const int32_t *__restrict__ q_qe,
+                                                                  const SetSlice *__restrict__ slices, int nSlices, int rule, int v,
+                                                                  u64 *__restrict__ rows, u64 *__restrict__ nhit,
+                                                                  unsigned *__restrict__ gbits, MinOv mo)
+{
+    sets_support_body<USE_V, LDS, true>(db, q_ichr, q_qs, q_qe, slices, nSlices, rule, v, rows, nhit, gbits, mo);
 }

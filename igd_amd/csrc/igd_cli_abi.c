@@ -255,6 +255,34 @@ static void *parse_run(void *arg)
     return NULL;
 }
 
+/* `-O N -A F -B F`: a minimum overlap per (query region, record) pair (include/igd_hip.h: igd_hip_min_overlap), for the plain
+ * `-q` / `-Q` counts, `-u`, `-U` [-R] and `-P`.  g_mo is NULL without them; the routines below hand it to the `_ov` entry points,
+ * which take NULL as "no threshold". */
+static igd_hip_min_overlap g_mo_val = {0, 0, 0};
+static const igd_hip_min_overlap *g_mo = NULL;
+
+/* a decimal fraction in [0, 1] with at most six places -> parts per million, exactly (digits only: no strtod); -1: refused */
+static int32_t parse_ppm(const char *a)
+{
+    int32_t whole = 0, frac = 0;
+    int nw = 0, nf = 0;
+    for (; *a >= '0' && *a <= '9'; a++, nw++) {
+        if (nw >= 1) return -1;                       /* one digit before the point: 0 or 1 */
+        whole = *a - '0';
+    }
+    if (*a == '.') {
+        for (a++; *a >= '0' && *a <= '9'; a++, nf++) {
+            if (nf >= 6) return -1;
+            frac = frac * 10 + (*a - '0');
+        }
+        if (nf == 0 && nw == 0) return -1;
+    } else if (nw == 0) return -1;
+    if (*a) return -1;
+    for (; nf < 6; nf++) frac *= 10;
+    if (whole > 1 || (whole == 1 && frac != 0)) return -1;
+    return whole * IGD_HIP_PPM + frac;
+}
+
 /* a file of at most igdc_host_limit() queries, while no engine is resident: counted on the host (igd_hostpath.c) */
 static igdc_map *host_map_lim(int64_t nq, int64_t lim)
 {
@@ -289,7 +317,7 @@ static int64_t file_query(const char *qFile, int32_t v, int rule, int64_t *hits)
     igdc_map *hm = q.n > 0 ? host_map_lim(q.n, igdc_host_limit()) : NULL;
     int onHost = 0;
     if (hm) {
-        onHost = igdc_search_host(g_core, hm, q.ichr, q.qs, q.qe, q.n, v, rule, hits, &total) == 0;   // (fails only on a read error: hits[] untouched)
+        onHost = igdc_search_host_ov(g_core, hm, q.ichr, q.qs, q.qe, q.n, v, rule, hits, &total, g_mo) == 0;   // (fails only on a read error: hits[] untouched)
         igdc_map_close(hm);
         if (onHost) phase("search on the host (small file)", &t0);
         else total = 0;
@@ -298,7 +326,10 @@ static int64_t file_query(const char *qFile, int32_t v, int rule, int64_t *hits)
         igd_hip_db *dev = engine();
         t0 = now_s();
         /* position-sorted BED (the common case): tell the engine, it verifies on the device */
+        /* under a minimum overlap the file is ONE set of the sets route (the batch pipeline takes no threshold; first device) */
+        const int64_t one[2] = {0, q.n};
         int rc = !dev ? IGD_HIP_OK
+               : g_mo ? igd_hip_search_sets_ov(dev, q.ichr, q.qs, q.qe, one, 1, v, rule, 0, hits, &total, g_mo)
                : g_core->grp ? igdc_search_multi(g_core, q.ichr, q.qs, q.qe, q.n, v, rule, igdc_queries_flags(&q, g_core->nbp), hits, &total)
                : igd_hip_search_ex(dev, q.ichr, q.qs, q.qe, q.n, v, rule, igdc_queries_flags(&q, g_core->nbp), hits, &total);
         if (rc != IGD_HIP_OK) { engine_failed("search", rc); total = 0; }
@@ -840,7 +871,7 @@ static void search_sets(const char *listName, int32_t v, int64_t *hits)
         double t0 = now_s();
         igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one; -Q is one device) */
         if (dev) {
-            const int rc = igd_hip_search_sets(dev, ichr, qs, qe, off, n, ev, rule, 0, rows, NULL);
+            const int rc = igd_hip_search_sets_ov(dev, ichr, qs, qe, off, n, ev, rule, 0, rows, NULL, g_mo);
             if (rc != IGD_HIP_OK) engine_failed("search", rc);
             phase("search of the query sets (H2D + kernels + D2H)", &t0);
         }
@@ -922,8 +953,10 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
         onHost = 1;
         for (int32_t k = 0; k < n && onHost; k++)
             if (q[k].n > 0)
-                onHost = (bp ? igdc_coverage_host : igdc_support_host)(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
-                                                                       rows + (size_t)k * (size_t)nfiles, &nhit[k]) == 0;
+                onHost = (bp ? igdc_coverage_host(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
+                                                  rows + (size_t)k * (size_t)nfiles, &nhit[k])
+                             : igdc_support_host_ov(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
+                                                    rows + (size_t)k * (size_t)nfiles, &nhit[k], g_mo)) == 0;
         igdc_map_close(hm);
         if (onHost) phase(bp ? "covered base pairs on the host (small files)" : "support counts on the host (small files)", &t0);
         else {                                        /* (a read error: the engine reads the file its own way) */
@@ -947,7 +980,8 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
         igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
         double t0 = now_s();
         if (dev) {
-            const int rc = (bp ? igd_hip_coverage_sets : igd_hip_support_sets)(dev, ichr, qs, qe, off, n, ev, rule, rows, nhit);
+            const int rc = bp ? igd_hip_coverage_sets(dev, ichr, qs, qe, off, n, ev, rule, rows, nhit)
+                              : igd_hip_support_sets_ov(dev, ichr, qs, qe, off, n, ev, rule, rows, nhit, g_mo);
             if (rc != IGD_HIP_OK) engine_failed(bp ? "coverage" : "support", rc);
             phase(bp ? "covered base pairs of the query sets (H2D + kernel + D2H)" : "support counts of the query sets (H2D + kernel + D2H)", &t0);
         }
@@ -1086,11 +1120,11 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
         }
     } else if (hm) {
         double t0 = now_s();
-        onHost = igdc_support_host(g_core, hm, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, urow, &unhit) == 0;
+        onHost = igdc_support_host_ov(g_core, hm, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, urow, &unhit, g_mo) == 0;
         for (int32_t k = 0; k < n && onHost; k++)
             if (q[k].n > 0)
-                onHost = igdc_support_host(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
-                                           &nhit[k]) == 0;
+                onHost = igdc_support_host_ov(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
+                                              &nhit[k], g_mo) == 0;
         igdc_map_close(hm);
         if (onHost) {
             enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
@@ -1115,8 +1149,8 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
             const int rc = restricted
                                ? igd_hip_enrich_restricted(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, size,
                                                            plog, odds, NULL, nhit, &unhit)
-                               : igd_hip_enrich_sets_nhit(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, plog,
-                                                          odds, NULL, nhit, &unhit);
+                               : igd_hip_enrich_sets_ov(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, plog,
+                                                        odds, NULL, nhit, &unhit, g_mo);
             if (rc != IGD_HIP_OK) engine_failed("enrichment", rc);
             else if (restricted) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
             else enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
@@ -1405,7 +1439,7 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
         int ok = 0;
         igdc_map *hm = host_map_lim(q.n * (nperm + 1), igdc_host_limit());
         if (hm) {
-            ok = igdc_permute_host(g_core, hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx) == 0;
+            ok = igdc_permute_host_ov(g_core, hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo) == 0;
             igdc_map_close(hm);
             if (ok) phase("permutation null on the host (small files)", &t0);
         }
@@ -1413,7 +1447,7 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
             igd_hip_db *dev = engine();
             t0 = now_s();
             if (dev) {
-                const int rc = igd_hip_permute_support(dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx);
+                const int rc = igd_hip_permute_support_ov(dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo);
                 if (rc != IGD_HIP_OK) engine_failed("permutation null", rc);
                 phase("permutation null of the query file (H2D + permute, support and statistics kernels + D2H)", &t0);
             }
@@ -1464,6 +1498,9 @@ static int usage_search(void)
             "    -g <genome file>           with -P: the contig lengths, one name<TAB>length per line\n"
             "    -S <seed>  -M <mode>       with -P: the seed (default 0); circular (default: one rigid shift per contig) or\n"
             "                               shuffle (every region placed anew on its contig)\n"
+            "    -O <bp>  -A <F>  -B <F>    minimum overlap of a counted (query region, record) pair: at least <bp> base pairs,\n"
+            "                               the fraction F of the query region (-A), of the record (-B); F is a decimal in [0, 1]\n"
+            "                               with at most six places.  With -q or -Q alone, -u, -U [-R] and -P\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -1505,7 +1542,9 @@ int igd_search(int argc, char **argv)                                        /* 
     int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
 
     int32_t v = 0, qs = 1, qe = 2;
-    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, restricted = 0, cooc = 0, other = 0;      /* other: -m, -s or -r was given (-U refuses them) */
+    g_mo_val.min_bp = g_mo_val.ppm_query = g_mo_val.ppm_record = 0;
+    g_mo = NULL;
+    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, restricted = 0, cooc = 0, other = 0, minov = 0;      /* other: -m, -s or -r was given (-U refuses them) */
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
     char *permArg = NULL, *genomeName = NULL, *seedArg = NULL, *pmodeArg = NULL;      /* -P, -g, -S, -M (see permute_file) */
     char out[64] = "";
@@ -1559,12 +1598,32 @@ int igd_search(int argc, char **argv)                                        /* 
         } else if (strcmp(a, "-M") == 0) {
             if (i + 1 >= argc) { printf("No mode.\n"); return EX_OK; }
             pmodeArg = argv[i + 1];
+        } else if (strcmp(a, "-O") == 0 || strcmp(a, "-A") == 0 || strcmp(a, "-B") == 0) {
+            /* (not the reference's: a minimum overlap per pair, see g_mo) */
+            char *end = NULL;
+            const long long bpv = a[1] == 'O' && i + 1 < argc ? strtoll(argv[i + 1], &end, 10) : -1;
+            const int32_t ppm = a[1] != 'O' && i + 1 < argc ? parse_ppm(argv[i + 1]) : -1;
+            if (a[1] == 'O' ? (!end || end == argv[i + 1] || *end || bpv < 0 || bpv > INT32_MAX) : ppm < 0) {
+                printf("Not supported: %s %s (%s)\n", a, i + 1 < argc ? argv[i + 1] : "",
+                       a[1] == 'O' ? "a number of base pairs, 0 to 2147483647" : "a decimal fraction in [0, 1] with at most six places");
+                return EX_USAGE;
+            }
+            if (a[1] == 'O') g_mo_val.min_bp = (int32_t)bpv;
+            else if (a[1] == 'A') g_mo_val.ppm_query = ppm;
+            else g_mo_val.ppm_record = ppm;
+            minov = 1;
+            i++;
         } else if (strcmp(a, "-o") == 0) {
             if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
         }
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    if (minov && (bp || memb || restricted || cooc || full || other || (mode != 1 && !listName))) {
+        printf("Not supported: -O, -A or -B together with -b, -w, -X, -C, -f, -m, -s or -r, or without -q or -Q\n");
+        return EX_USAGE;
+    }
+    if (minov && igd_hip_min_overlap_active(&g_mo_val)) g_mo = &g_mo_val;      /* (all three zero: no threshold) */
     fP = fopen(igdName, "rb");                                                /* :974 */
     if (!permArg && (genomeName || seedArg || pmodeArg)) {
         printf("Not supported: -g, -S or -M without -P\n");

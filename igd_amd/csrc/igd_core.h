@@ -120,6 +120,17 @@ int igdc_support_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
  * records (an interval union per query, not a sum over records), *covered (may be NULL) += the same for the union over all
  * files.  Same records, threading, rule and filter as igdc_support_host; added to the caller's only if every tile could be
  * read.  0 on success. */
+/* The two above and igdc_permute_host below under a minimum overlap per pair (include/igd_hip.h: igd_hip_min_overlap -- the same
+ * inline predicate as the kernels'; NULL or all zero: inactive, the plain function; a field out of range: -1, nothing written).
+ * The enrichment of `-U` on the host is these supports through igdc_fisher_host, so it needs no twin of its own. */
+int igdc_search_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                        int64_t nq, int32_t v, int rule, int64_t *hits, int64_t *total, const igd_hip_min_overlap *min_overlap);
+int igdc_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                         int64_t nq, int32_t v, int rule, int64_t *support, int64_t *nhit, const igd_hip_min_overlap *min_overlap);
+int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                         int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
+                         const igd_hip_min_overlap *min_overlap);
 int igdc_coverage_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                        int64_t nq, int32_t v, int rule, int64_t *coverage, int64_t *covered);
 /* Per-query membership: row q of bits (ceil(nFiles / 32) uint32 words; file f = bit f & 31 of word f >> 5) says which

@@ -144,6 +144,24 @@ int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
     return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, support, nhit) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_search_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                           int32_t v, int rule, int flags, int64_t *hits, int64_t *totals, const igd_hip_min_overlap *min_overlap)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int32_t, int, int,
+                        int64_t *, int64_t *, const igd_hip_min_overlap *);
+    RESOLVE(fn_t, "igd_hip_search_sets_ov");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, flags, hits, totals, min_overlap) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_support_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                            int32_t v, int rule, int64_t *support, int64_t *nhit, const igd_hip_min_overlap *min_overlap)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int32_t, int,
+                        int64_t *, int64_t *, const igd_hip_min_overlap *);
+    RESOLVE(fn_t, "igd_hip_support_sets_ov");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, support, nhit, min_overlap) : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
                           int32_t v, int rule, int64_t *coverage, int64_t *covered)
 {
@@ -197,6 +215,20 @@ int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t 
     RESOLVE(fn_t, "igd_hip_enrich_sets_nhit");
     return fn ? fn(db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, v, rule, support, usupport, pvalue_log, odds_ratio, clamped,
                    nhit, unhit)
+              : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                           int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, int32_t v, int rule,
+                           int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio, int64_t *clamped, int64_t *nhit,
+                           int64_t *unhit, const igd_hip_min_overlap *min_overlap)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, const int32_t *,
+                        const int32_t *, const int32_t *, int64_t, int32_t, int, int64_t *, int64_t *, double *, double *, int64_t *,
+                        int64_t *, int64_t *, const igd_hip_min_overlap *);
+    RESOLVE(fn_t, "igd_hip_enrich_sets_ov");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, v, rule, support, usupport, pvalue_log, odds_ratio, clamped,
+                   nhit, unhit, min_overlap)
               : IGD_HIP_ERR_DEVICE;
 }
 
@@ -307,6 +339,17 @@ int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *
                         int32_t, int, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *);
     RESOLVE(fn_t, "igd_hip_permute_support");
     return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                               int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
+                               int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int, uint64_t, int64_t,
+                        int32_t, int, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, const igd_hip_min_overlap *);
+    RESOLVE(fn_t, "igd_hip_permute_support_ov");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax, min_overlap)
+              : IGD_HIP_ERR_DEVICE;
 }
 
 int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,

@@ -162,10 +162,14 @@ static inline void hv_push(hitvec *o, int32_t q, const int32_t *r)
     h->q = q; h->idx = r[0]; h->start = r[1]; h->end = r[2];
 }
 
+/* mo: an ACTIVE minimum overlap per pair (include/igd_hip.h: igd_hip_min_overlap; the host flavours pass NULL for an inactive
+ * one), the same inline predicate as the kernels': need_q once per query, the pair test on every record the walk counts */
 static inline int64_t one_query(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int32_t v,
-                                int use_v, int rule, int64_t *hits, hitvec *emit, int32_t qno)
+                                int use_v, int rule, int64_t *hits, hitvec *emit, int32_t qno, const igd_hip_min_overlap *mo)
 {
     if (ichr < 0 || ichr >= db->nCtg) return 0;                            /* :456-457 */
+    const int32_t need = mo ? igd_hip_min_overlap_need_q(mo->min_bp, mo->ppm_query, qs, qe) : 0;
+    if (need < 0) return 0;                                                /* qe <= qs: no record qualifies */
     const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
     const int32_t n1 = qs / nbp;                                           /* C division, as :459 */
     int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;                       /* (qe-1)/nbp with the reference's wrap */
@@ -184,7 +188,7 @@ static inline int64_t one_query(const igdc_db *db, const igdc_map *m, tilebuf *t
         for (int32_t i = below(rec, w, cnt, qe) - 1; i >= 0; i--) {        /* the reverse scans of :489-493, :522-526 */
             const int32_t *r = rec + (size_t)i * (size_t)w;
             if ((int64_t)r[1] < lob) break;                                /* met in an earlier tile (:510-511) */
-            if (r[2] > qs && (!use_v || r[3] >= v)) {
+            if (r[2] > qs && (!use_v || r[3] >= v) && (!mo || igd_hip_min_overlap_pair(need, mo->ppm_record, qs, qe, r[1], r[2]))) {
                 if (r[0] < 0 || r[0] >= nf) continue;                      /* the reference indexes hits[] unchecked (:491) */
                 if (hits) hits[r[0]]++;
                 if (emit) hv_push(emit, qno, r);
@@ -199,9 +203,11 @@ static inline int64_t one_query(const igdc_db *db, const igdc_map *m, tilebuf *t
  * holds the stamp of the last query that counted file f (stamp = query number + 1; 0 = none yet).  Returns 1 if the query
  * overlaps any record. */
 static inline int one_query_support(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int32_t v,
-                                    int use_v, int rule, int64_t *support, int64_t *last, int64_t stamp)
+                                    int use_v, int rule, int64_t *support, int64_t *last, int64_t stamp, const igd_hip_min_overlap *mo)
 {
     if (ichr < 0 || ichr >= db->nCtg) return 0;
+    const int32_t need = mo ? igd_hip_min_overlap_need_q(mo->min_bp, mo->ppm_query, qs, qe) : 0;
+    if (need < 0) return 0;
     const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
     const int32_t n1 = qs / nbp;
     int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;
@@ -220,7 +226,7 @@ static inline int one_query_support(const igdc_db *db, const igdc_map *m, tilebu
         for (int32_t i = below(rec, w, cnt, qe) - 1; i >= 0; i--) {
             const int32_t *r = rec + (size_t)i * (size_t)w;
             if ((int64_t)r[1] < lob) break;
-            if (r[2] > qs && (!use_v || r[3] >= v)) {
+            if (r[2] > qs && (!use_v || r[3] >= v) && (!mo || igd_hip_min_overlap_pair(need, mo->ppm_record, qs, qe, r[1], r[2]))) {
                 if (r[0] < 0 || r[0] >= nf) continue;
                 any = 1;
                 if (last[r[0]] != stamp) { last[r[0]] = stamp; support[r[0]]++; }
@@ -322,6 +328,7 @@ typedef struct {
     int64_t *front;         /* covered base pairs: the frontiers of one_query_coverage, beside last[] (NULL: not those) */
     uint32_t *bits;         /* membership rows: the caller's rows (NULL: not those), nW words each; nfh: its nfiles_hit[] or NULL */
     int32_t *nfh, nW;
+    const igd_hip_min_overlap *mo;      /* pair counts and support counts: an active minimum overlap, or NULL */
 } host_job;
 
 static void *host_run(void *arg)
@@ -340,10 +347,10 @@ static void *host_run(void *arg)
     for (int64_t i = J->lo; J->front && i < J->hi; i++)     /* covered base pairs: hits = coverage[], total = bp under any file */
         tot += one_query_coverage(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, J->front, i + 1);
     for (int64_t i = J->lo; J->last && !J->front && i < J->hi; i++)      /* support counts: hits = support[], total = queries with a hit */
-        tot += one_query_support(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, i + 1);
+        tot += one_query_support(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, i + 1, J->mo);
     for (int64_t i = J->lo; !J->last && !J->bits && i < J->hi; i++) {
         const int64_t n = one_query(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits,
-                                    J->want_out ? &J->out : NULL, (int32_t)i);
+                                    J->want_out ? &J->out : NULL, (int32_t)i, J->mo);
         if (J->qcnt) J->qcnt[i] = n;
         tot += n;
     }
@@ -383,7 +390,14 @@ static int run_jobs(host_job *job, int T)
 int igdc_search_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                      int64_t nq, int32_t v, int rule, int64_t *hits, int64_t *total)
 {
-    if (!db || !m || !hits || nq < 0) return -1;
+    return igdc_search_host_ov(db, m, ichr, qs, qe, nq, v, rule, hits, total, NULL);
+}
+
+int igdc_search_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                        int64_t nq, int32_t v, int rule, int64_t *hits, int64_t *total, const igd_hip_min_overlap *min_overlap)
+{
+    if (!db || !m || !hits || nq < 0 || !igd_hip_min_overlap_valid(min_overlap)) return -1;
+    const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
     const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;      /* gType 0 stores no value (:1024-1025) */
     const int T = host_threads(nq);
     host_job job[64];
@@ -396,6 +410,7 @@ int igdc_search_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, 
         job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
         job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
         job[k].hits = priv + (size_t)k * (size_t)(db->nFiles + 1);
+        job[k].mo = mo;
     }
     run_jobs(job, T);
     int64_t tot = 0;
@@ -414,7 +429,14 @@ int igdc_search_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, 
 int igdc_support_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                       int64_t nq, int32_t v, int rule, int64_t *support, int64_t *nhit)
 {
-    if (!db || !m || !support || nq < 0) return -1;
+    return igdc_support_host_ov(db, m, ichr, qs, qe, nq, v, rule, support, nhit, NULL);
+}
+
+int igdc_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                         int64_t nq, int32_t v, int rule, int64_t *support, int64_t *nhit, const igd_hip_min_overlap *min_overlap)
+{
+    if (!db || !m || !support || nq < 0 || !igd_hip_min_overlap_valid(min_overlap)) return -1;
+    const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
     const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
     const int T = host_threads(nq);
     host_job job[64];
@@ -429,6 +451,7 @@ int igdc_support_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
         job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
         job[k].hits = priv + (size_t)k * 2 * nf1;
         job[k].last = job[k].hits + nf1;
+        job[k].mo = mo;
     }
     run_jobs(job, T);
     int64_t tot = 0;
@@ -976,6 +999,7 @@ typedef struct {
     int32_t *ps, *pe;       /* the permuted set */
     int64_t *row, *last;
     int k, T, io_failed;
+    const igd_hip_min_overlap *mo;      /* an active minimum overlap, or NULL */
 } perm_job;
 
 static void *perm_run(void *arg)
@@ -990,7 +1014,7 @@ static void *perm_run(void *arg)
         memset(&J, 0, sizeof J);
         J.db = P->db; J.m = P->m; J.ichr = P->ichr; J.qs = P->ps; J.qe = P->pe;
         J.lo = 0; J.hi = P->nq; J.v = P->v; J.use_v = P->use_v; J.rule = P->rule;
-        J.hits = P->row; J.last = P->last;
+        J.hits = P->row; J.last = P->last; J.mo = P->mo;
         host_run(&J);
         if (J.io_failed) { P->io_failed = 1; break; }
         P->row[nF] = J.total;
@@ -1011,7 +1035,16 @@ int igdc_permute_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
                       int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax)
 {
-    if (!db || !m || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
+    return igdc_permute_host_ov(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax, NULL);
+}
+
+int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                         int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
+                         const igd_hip_min_overlap *min_overlap)
+{
+    const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
+    if (!igd_hip_min_overlap_valid(min_overlap) || !db || !m || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
         (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) ||
         nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() ||
         (unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63 ||
@@ -1025,7 +1058,7 @@ int igdc_permute_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
     int32_t *pq = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 2 * (size_t)nq + 1));
     int rc = w && pq ? 0 : -1;
     int64_t *obs = w ? w + (size_t)T * 8 * (size_t)nC : NULL;
-    if (rc == 0 && nq > 0) rc = igdc_support_host(db, m, ichr, qs, qe, nq, v, rule, obs, &obs[nF]);
+    if (rc == 0 && nq > 0) rc = igdc_support_host_ov(db, m, ichr, qs, qe, nq, v, rule, obs, &obs[nF], mo);
     perm_job job[64];
     pthread_t th[64];
     int started[64];
@@ -1038,7 +1071,7 @@ int igdc_permute_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
         job[k].acc = w + (size_t)k * 8 * (size_t)nC;
         job[k].row = job[k].acc + 6 * nC; job[k].last = job[k].row + nC;
         job[k].ps = pq + (size_t)k * 2 * (size_t)nq; job[k].pe = job[k].ps + nq;
-        job[k].k = k; job[k].T = T;
+        job[k].k = k; job[k].T = T; job[k].mo = mo;
         for (int64_t f = 0; f < nC; f++) { job[k].acc[4 * nC + f] = INT64_MAX; job[k].acc[5 * nC + f] = INT64_MIN; }
     }
     if (rc == 0) {

@@ -34,6 +34,49 @@ PermutationSummary = collections.namedtuple("PermutationSummary", "mean sd z nlo
 PERM_MODES = {"circular": 0, "shuffle": 1}           # IGD_HIP_PERM_CIRCULAR, IGD_HIP_PERM_SHUFFLE
 
 
+class MinOverlap(C.Structure):
+    """A minimum overlap per (query region, record) pair -- igd_hip_min_overlap of include/igd_hip.h: LOLA's minOverlap,
+    GenomicRanges' minoverlap, bedtools' -f / -F.  A pair the search counts keeps counting only if its overlap
+    ov = min(qe, end) - max(qs, start) has ov >= max(bp, 1), ov * 10^6 >= (qe - qs) * query_ppm and
+    ov * 10^6 >= (end - start) * record_ppm (integers; equality qualifies).  The fractions are parts per million, 0 .. 10^6;
+    from_fractions() takes them as numbers in [0, 1].  All three zero is no threshold at all.  With any of them set a
+    zero-length or inverted query (qe <= qs) is never counted -- the plain search counts one under a record that spans it.
+    Accepted as `min_overlap=` by search_sets, support_sets, enrichment_sets, permutation_support, their one-set and file
+    forms and the host functions; a bare int there means MinOverlap(bp=that)."""
+    _fields_ = [("bp", C.c_int32), ("query_ppm", C.c_int32), ("record_ppm", C.c_int32)]
+    PPM = 1000000
+
+    def __init__(self, bp=0, query_ppm=0, record_ppm=0):
+        for name, x, hi in (("bp", bp, 2 ** 31 - 1), ("query_ppm", query_ppm, self.PPM), ("record_ppm", record_ppm, self.PPM)):
+            if isinstance(x, bool) or int(x) != x or not 0 <= int(x) <= hi:
+                raise IgdError("MinOverlap: %s = %r, not an integer in 0 .. %d" % (name, x, hi))
+        super().__init__(int(bp), int(query_ppm), int(record_ppm))
+
+    @classmethod
+    def from_fractions(cls, bp=0, query=0.0, record=0.0):
+        """bp and the two fractions as numbers in [0, 1], rounded to the nearest part per million"""
+        for name, x in (("query", query), ("record", record)):
+            if not 0 <= x <= 1:                                   # (NaN fails both comparisons)
+                raise IgdError("MinOverlap.from_fractions: %s = %r, not in [0, 1]" % (name, x))
+        return cls(bp, int(round(query * cls.PPM)), int(round(record * cls.PPM)))
+
+    @property
+    def active(self):
+        return bool(self.bp or self.query_ppm or self.record_ppm)
+
+    def __repr__(self):
+        return "MinOverlap(bp=%d, query_ppm=%d, record_ppm=%d)" % (self.bp, self.query_ppm, self.record_ppm)
+
+
+def _min_overlap(mo, what):
+    """None (no `_ov` call at all), or a MinOverlap from a MinOverlap or a bare int of base pairs"""
+    if mo is None or isinstance(mo, MinOverlap):
+        return mo
+    if isinstance(mo, (int, np.integer)) and not isinstance(mo, bool):
+        return MinOverlap(bp=int(mo))
+    raise IgdError("%s: min_overlap must be None, an int (base pairs) or a MinOverlap, not %r" % (what, mo))
+
+
 def _tables(a, b, c, d, what):
     t = [np.ascontiguousarray(x, dtype=np.int64) for x in (a, b, c, d)]
     if any(x.ndim != 1 or len(x) != len(t[0]) for x in t):
@@ -235,6 +278,80 @@ def cooccur_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None):
     return cooc, nhit.value
 
 
+class _HostDb:
+    """header, index and tile reader of a .igd for the igdc_*_host functions (no device is touched)"""
+
+    def __init__(self, igd_path, what):
+        self.L = L = N.cli()
+        self.core = L.igdc_open(igd_path.encode())
+        if not self.core:
+            raise IgdError("cannot read .igd header of %s" % igd_path)
+        self.m = None
+        try:
+            tsv = L.igdc_index_path(igd_path.encode())
+            rc = L.igdc_load_index(self.core, C.cast(tsv, C.c_char_p))
+            N.free(tsv)
+            if rc != 0:
+                raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
+            fd = os.open(igd_path, os.O_RDONLY)
+            try:
+                self.m = L.igdc_map_open(self.core, fd)
+            finally:
+                os.close(fd)
+            if not self.m:
+                raise IgdError("%s: cannot map %s" % (what, igd_path))
+        except Exception:
+            self.close()
+            raise
+        self.nfiles, self.gtype, self.nctg = self.core.contents.nFiles, self.core.contents.gType, self.core.contents.nCtg
+
+    def dispatch(self, v, rule, value_filter):
+        if rule is None:
+            return Database.cli_dispatch(self.gtype, v)
+        return rule, N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+
+    def close(self):
+        if self.m:
+            self.L.igdc_map_close(self.m)
+        self.L.igdc_close(self.core)
+        self.m = self.core = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def search_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None, min_overlap=None):
+    """Pair counts of one query set on the host (igdc_search_host / igdc_search_host_ov: pread on the .igd, threads over the
+    queries; no device is touched): (hits int64[nfiles], total) as Database.search() defines them, under min_overlap
+    (MinOverlap, or an int of base pairs) as Database.search_sets() does."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    mo = _min_overlap(min_overlap, "search_host")
+    with _HostDb(igd_path, "search_host") as h:
+        rule, vf = h.dispatch(v, rule, value_filter)
+        hits, total = np.zeros(max(h.nfiles, 1), np.int64), C.c_int64(0)
+        a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), vf, rule, hits.ctypes.data, C.byref(total))
+        if (h.L.igdc_search_host(*a) if mo is None else h.L.igdc_search_host_ov(*a, C.byref(mo))) != 0:
+            raise IgdError("search_host: a tile of %s could not be read" % igd_path)
+        return hits[:h.nfiles], total.value
+
+
+def support_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None, min_overlap=None):
+    """Support counts of one query set on the host (igdc_support_host / igdc_support_host_ov; no device is touched):
+    (support int64[nfiles], nhit) as Database.support() defines them, min_overlap included."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    mo = _min_overlap(min_overlap, "support_host")
+    with _HostDb(igd_path, "support_host") as h:
+        rule, vf = h.dispatch(v, rule, value_filter)
+        sup, nhit = np.zeros(max(h.nfiles, 1), np.int64), C.c_int64(0)
+        a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), vf, rule, sup.ctypes.data, C.byref(nhit))
+        if (h.L.igdc_support_host(*a) if mo is None else h.L.igdc_support_host_ov(*a, C.byref(mo))) != 0:
+            raise IgdError("support_host: a tile of %s could not be read" % igd_path)
+        return sup[:h.nfiles], nhit.value
+
+
 def _perm_mode(mode, what):
     if mode not in PERM_MODES:
         raise IgdError("%s: mode must be 'circular' or 'shuffle', not %r" % (what, mode))
@@ -264,11 +381,13 @@ def permute_regions_host(ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"
     return oqs, oqe
 
 
-def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
+def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, min_overlap=None):
     """The permutation null of the support counts on the host (igdc_permute_host: pread on the .igd, threads over the
-    permutations; no device is touched): a PermutationSupport as Database.permutation_support() defines it."""
+    permutations; no device is touched): a PermutationSupport as Database.permutation_support() defines it, min_overlap
+    included (igdc_permute_host_ov)."""
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_host")
     pm = _perm_mode(mode, "permute_host")
+    mo = _min_overlap(min_overlap, "permute_host")
     L = N.cli()
     core = L.igdc_open(igd_path.encode())
     if not core:
@@ -293,8 +412,9 @@ def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular"
         if not m:
             raise IgdError("cannot map %s" % igd_path)
         out = [np.empty(nf + 1, np.int64) for _ in range(7)]
-        if L.igdc_permute_host(core, m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, int(seed) & (2 ** 64 - 1), int(nperm),
-                               vf, rule, *[a.ctypes.data for a in out]) != 0:
+        a = (core, m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, int(seed) & (2 ** 64 - 1), int(nperm), vf, rule,
+             *[x.ctypes.data for x in out])
+        if (L.igdc_permute_host(*a) if mo is None else L.igdc_permute_host_ov(*a, C.byref(mo))) != 0:
             raise IgdError("permute_host: a refused argument (number of permutations, a region outside its contig), or a tile of %s "
                            "could not be read" % igd_path)
     finally:
@@ -420,11 +540,13 @@ class Database:
                                        vf, rule, int(flags), hits.ctypes.data, C.byref(total)), "igd_hip_search")
         return hits[: self.nfiles], total.value
 
-    def search_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, hits=None, flags=0):
+    def search_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, hits=None, flags=0, min_overlap=None):
         """Many query sets in one call (igd_hip_search_sets).  Set k is the queries [set_off[k], set_off[k + 1]) of the
         concatenated arrays (set_off: int64[nsets + 1], monotone, set_off[0] = 0).  Returns (hits int64[nsets, nfiles],
         totals int64[nsets]); row k is what search() returns for set k alone.  hits (int64[nsets, nfiles], C order) is added
-        to when given.  flags as search() (they steer the route of sets of 2^17 queries and more)."""
+        to when given.  flags as search() (they steer the route of sets of 2^17 queries and more).
+        min_overlap (a MinOverlap, or an int of base pairs; igd_hip_search_sets_ov): only the pairs that reach it are counted,
+        and every set, whatever its size, is counted by the slice kernel."""
         ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
         set_off = np.ascontiguousarray(set_off, dtype=np.int64)
         nsets = len(set_off) - 1
@@ -442,24 +564,26 @@ class Database:
         elif hits.dtype != np.int64 or hits.shape != (nsets, self.nfiles) or not hits.flags.c_contiguous:
             raise IgdError("search_sets: hits must be a C-ordered int64[%d, %d]" % (nsets, self.nfiles))
         totals = np.zeros(max(nsets, 1), np.int64)
-        _chk(self._H.igd_hip_search_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data,
-                                         nsets, vf, rule, int(flags), hits.ctypes.data if hits.size else None,
-                                         totals.ctypes.data), "igd_hip_search_sets")
+        mo = _min_overlap(min_overlap, "search_sets")
+        a = (self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets, vf, rule, int(flags),
+             hits.ctypes.data if hits.size else None, totals.ctypes.data)
+        _chk(self._H.igd_hip_search_sets(*a) if mo is None else self._H.igd_hip_search_sets_ov(*a, C.byref(mo)), "igd_hip_search_sets")
         return hits, totals[:nsets]
 
-    def search_files(self, paths, v=0):
+    def search_files(self, paths, v=0, min_overlap=None):
         """One query set per BED file (read as `igd search -q` reads it): (hits int64[len(paths), nfiles], totals)."""
         sets = [self.read_queries(p) for p in paths]
         set_off = np.zeros(len(sets) + 1, np.int64)
         set_off[1:] = np.cumsum([len(s[1]) for s in sets])
         cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.search_sets(cat[0], cat[1], cat[2], set_off, v)
+        return self.search_sets(cat[0], cat[1], cat[2], set_off, v, min_overlap=min_overlap)
 
-    def support_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, support=None):
+    def support_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, support=None, min_overlap=None):
         """Support counts of many query sets in one call (igd_hip_support_sets).  Sets as search_sets().  Returns (support
         int64[nsets, nfiles], nhit int64[nsets]): support[k, f] = the queries of set k that overlap at least one record of
         file f (search_sets counts every overlapping record), nhit[k] = the queries of set k that overlap any record.
-        support (int64[nsets, nfiles], C order) is added to when given."""
+        support (int64[nsets, nfiles], C order) is added to when given.  min_overlap (a MinOverlap, or an int of base pairs;
+        igd_hip_support_sets_ov): "overlap" then means at least one PAIR that reaches it, as LOLA and bedtools test it."""
         ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
         set_off = np.ascontiguousarray(set_off, dtype=np.int64)
         nsets = len(set_off) - 1
@@ -477,24 +601,25 @@ class Database:
         elif support.dtype != np.int64 or support.shape != (nsets, self.nfiles) or not support.flags.c_contiguous:
             raise IgdError("support_sets: support must be a C-ordered int64[%d, %d]" % (nsets, self.nfiles))
         nhit = np.zeros(max(nsets, 1), np.int64)
-        _chk(self._H.igd_hip_support_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data,
-                                          nsets, vf, rule, support.ctypes.data if support.size else None,
-                                          nhit.ctypes.data), "igd_hip_support_sets")
+        mo = _min_overlap(min_overlap, "support_sets")
+        a = (self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets, vf, rule,
+             support.ctypes.data if support.size else None, nhit.ctypes.data)
+        _chk(self._H.igd_hip_support_sets(*a) if mo is None else self._H.igd_hip_support_sets_ov(*a, C.byref(mo)), "igd_hip_support_sets")
         return support, nhit[:nsets]
 
-    def support(self, ichr, qs, qe, v=0, rule=None, value_filter=None):
+    def support(self, ichr, qs, qe, v=0, rule=None, value_filter=None, min_overlap=None):
         """Support counts of one query set: (int64[nfiles], nhit) -- per file the queries that overlap at least one of its
         records, and the queries that overlap any record.  Row 0 of support_sets() with one set."""
-        sup, nhit = self.support_sets(ichr, qs, qe, np.array([0, len(_i32(qs))], np.int64), v, rule, value_filter)
+        sup, nhit = self.support_sets(ichr, qs, qe, np.array([0, len(_i32(qs))], np.int64), v, rule, value_filter, min_overlap=min_overlap)
         return sup[0], int(nhit[0])
 
-    def support_files(self, paths, v=0):
+    def support_files(self, paths, v=0, min_overlap=None):
         """One query set per BED file (read as `igd search -q` reads it): (support int64[len(paths), nfiles], nhit)."""
         sets = [self.read_queries(p) for p in paths]
         set_off = np.zeros(len(sets) + 1, np.int64)
         set_off[1:] = np.cumsum([len(s[1]) for s in sets])
         cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.support_sets(cat[0], cat[1], cat[2], set_off, v)
+        return self.support_sets(cat[0], cat[1], cat[2], set_off, v, min_overlap=min_overlap)
 
     def coverage_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, coverage=None):
         """Covered base pairs of many query sets in one call (igd_hip_coverage_sets).  Sets as search_sets().  Returns
@@ -556,13 +681,15 @@ class Database:
                                            p.ctypes.data, o.ctypes.data), "igd_hip_fisher_tables")
         return p, o
 
-    def enrichment_sets(self, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, v=0, rule=None, value_filter=None):
+    def enrichment_sets(self, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, v=0, rule=None, value_filter=None, min_overlap=None):
         """Region-set enrichment of many query sets against a universe in one call (igd_hip_enrich_sets).  Sets as
         search_sets(); the universe is one more set of regions.  Returns Enrichment(support, usupport, b, c, d, pvalue_log,
         odds_ratio, clamped): per set k and file f the table a = support[k, f] (support_sets()), b = usupport[f] - a,
         c = |set k| - a, d = |universe| - a - b - c, where a negative b or d is then 0 and clamped[k] counts the cells of
         set k where that happened (enrichment_restricted() restricts the sets to the universe first); pvalue_log and odds_ratio as fisher()
-        on these tables.  Arrays are [nsets, nfiles], usupport [nfiles], clamped [nsets].  Ranks and q-values: enrichment_ranks()."""
+        on these tables.  Arrays are [nsets, nfiles], usupport [nfiles], clamped [nsets].  Ranks and q-values: enrichment_ranks().
+        min_overlap (a MinOverlap, or an int of base pairs; igd_hip_enrich_sets_ov): the supports of the sets AND of the
+        universe are taken under it, as LOLA's runLOLA(minOverlap=) does."""
         ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
         u_ichr, u_qs, u_qe = _i32(u_ichr), _i32(u_qs), _i32(u_qe)
         set_off = np.ascontiguousarray(set_off, dtype=np.int64)
@@ -579,11 +706,12 @@ class Database:
         sup, usup = np.empty((nsets, nf), np.int64), np.empty(max(nf, 1), np.int64)
         plog, odds = np.empty((nsets, nf), np.float64), np.empty((nsets, nf), np.float64)
         clamped = np.empty(max(nsets, 1), np.int64)
-        _chk(self._H.igd_hip_enrich_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
-                                         u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu, vf, rule,
-                                         sup.ctypes.data if sup.size else None, usup.ctypes.data,
-                                         plog.ctypes.data if plog.size else None, odds.ctypes.data if odds.size else None,
-                                         clamped.ctypes.data), "igd_hip_enrich_sets")
+        mo = _min_overlap(min_overlap, "enrichment_sets")
+        a = (self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
+             u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu, vf, rule, sup.ctypes.data if sup.size else None, usup.ctypes.data,
+             plog.ctypes.data if plog.size else None, odds.ctypes.data if odds.size else None, clamped.ctypes.data)
+        _chk(self._H.igd_hip_enrich_sets(*a) if mo is None else self._H.igd_hip_enrich_sets_ov(*a, None, None, C.byref(mo)),
+             "igd_hip_enrich_sets")
         usup = usup[:nf]
         nk = np.diff(set_off)[:, None]
         b = usup[None, :] - sup
@@ -664,7 +792,7 @@ class Database:
              "igd_hip_enrich_ranks")
         return r
 
-    def enrichment_files(self, paths, universe_path, v=0):
+    def enrichment_files(self, paths, universe_path, v=0, min_overlap=None):
         """One query set per BED file and the universe from a BED file (read as `igd search -q` reads them): what
         `igd search -Q list -U universe` prints, as enrichment_sets() returns it."""
         sets = [self.read_queries(p) for p in paths]
@@ -672,7 +800,7 @@ class Database:
         set_off = np.zeros(len(sets) + 1, np.int64)
         set_off[1:] = np.cumsum([len(s[1]) for s in sets])
         cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.enrichment_sets(cat[0], cat[1], cat[2], set_off, uni[0], uni[1], uni[2], v)
+        return self.enrichment_sets(cat[0], cat[1], cat[2], set_off, uni[0], uni[1], uni[2], v, min_overlap=min_overlap)
 
     @property
     def member_words(self):
@@ -767,7 +895,8 @@ class Database:
                                           out.ctypes.data if out.size else None), "igd_hip_bitrows_gram")
         return out
 
-    def permutation_support(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
+    def permutation_support(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None,
+                            min_overlap=None):
         """Permutation null of the support counts of one region set (igd_hip_permute_support).  The set is moved nperm times
         -- mode "circular": one rigid shift per permutation and contig, a region that would cross the contig's end is pushed
         back against it; "shuffle": every region placed anew on its contig -- with the generator of include/igd_hip.h; every
@@ -776,7 +905,8 @@ class Database:
         each: the support as given, and over the permuted supports x their sum, sum of squares, the permutations with
         x >= observed and x <= observed, the smallest and the largest; index nfiles is the regions with a hit in any file.
         The permuted regions and the permutations x files matrix never leave the device.  perm_summary() gives mean, sd, z
-        and p.  A region on a known contig that does not lie within its length raises IgdError."""
+        and p.  A region on a known contig that does not lie within its length raises IgdError.  min_overlap (a MinOverlap, or
+        an int of base pairs; igd_hip_permute_support_ov): the observed row and every permuted row are counted under it."""
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_support")
         if len(ctg_len) != self.nctg:
             raise IgdError("permutation_support: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), self.nctg))
@@ -785,9 +915,11 @@ class Database:
         else:
             vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
         out = [np.empty(self.nfiles + 1, np.int64) for _ in range(7)]
-        _chk(self._H.igd_hip_permute_support(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len),
-                                             _perm_mode(mode, "permutation_support"), int(seed) & (2 ** 64 - 1), int(nperm), vf, rule,
-                                             *[a.ctypes.data for a in out]), "igd_hip_permute_support")
+        mo = _min_overlap(min_overlap, "permutation_support")
+        a = (self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), _perm_mode(mode, "permutation_support"),
+             int(seed) & (2 ** 64 - 1), int(nperm), vf, rule, *[x.ctypes.data for x in out])
+        _chk(self._H.igd_hip_permute_support(*a) if mo is None else self._H.igd_hip_permute_support_ov(*a, C.byref(mo)),
+             "igd_hip_permute_support")
         return PermutationSupport(*out, int(nperm))
 
     def read_genome(self, path):
@@ -802,10 +934,10 @@ class Database:
             raise IgdError("genome file %s, line %d: not a name, a tab and a length of at most 2147483647" % (path, bad.value))
         return ln[:self.nctg]
 
-    def permutation_support_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0):
+    def permutation_support_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0, min_overlap=None):
         """The permutation null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the
         integers behind what `igd search -q path -P nperm -g genome_path` prints."""
-        return self.permutation_support(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v)
+        return self.permutation_support(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v, min_overlap=min_overlap)
 
     def permute_regions(self, ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"):
         """Kernel igd_permute_regions on host arrays (igd_hip_permute_regions): (qs, qe) int32[np_, nq], row k the regions

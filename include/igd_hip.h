@@ -146,6 +146,64 @@ int igd_hip_search_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, 
 int igd_hip_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                          const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *support, int64_t *nhit);
 
+/* MINIMUM OVERLAP PER PAIR (LOLA's minOverlap, GenomicRanges' minoverlap, bedtools' -f / -F): a threshold on every (query,
+ * record) pair, taken by the `_ov` forms of the set counts, the support counts, the enrichment and the permutation null.
+ *     min_bp       base pairs, >= 0
+ *     ppm_query    fraction of the QUERY's length, in parts per million, 0 .. 1 000 000
+ *     ppm_record   fraction of the RECORD's length, in parts per million, 0 .. 1 000 000
+ * Anything outside these ranges is IGD_HIP_ERR_ARG.  A NULL pointer or {0, 0, 0} is INACTIVE: the `_ov` form then IS the
+ * plain entry point -- the same kernels, the same results.  With any field non-zero the threshold is ACTIVE and narrows the
+ * pairs the search counts (rule word, the skip of a record met in an earlier tile, value filter and idx < nFiles unchanged)
+ * to those with
+ *     ov = min(qe, end) - max(qs, start)                      (the record's own coordinates, in whichever tile it is met)
+ *     ov >= max(min_bp, 1)  &&  ov * 10^6 >= (qe - qs) * ppm_query  &&  ov * 10^6 >= (end - start) * ppm_record
+ * in 64-bit integers; equality qualifies.  ppm_query = 10^6: the query lies inside the record; ppm_record = 10^6: the record
+ * lies inside the query; both: equal intervals.  A ZERO-LENGTH OR INVERTED QUERY (qe <= qs) has ov <= 0 with every record
+ * and is never counted under an active threshold, although the plain predicate  start < qe && end > qs  counts it under a
+ * record that spans both its ends.  The test is per pair: support is "at least one qualifying pair in the file", not a sum
+ * of covered base pairs over a file's records.
+ * igd_hip_min_overlap_need_q is the part of the test that depends on the query alone, max(min_bp, 1, ceil(lenq * ppm_query /
+ * 10^6)), or -1 when no record can qualify (qe <= qs; a bound above 2^31 - 1): the kernels evaluate it once per query.
+ * Records are taken to satisfy 0 <= start < end (every writer of the format drops the others). */
+typedef struct { int32_t min_bp, ppm_query, ppm_record; } igd_hip_min_overlap;
+#define IGD_HIP_PPM 1000000
+#if defined(__HIPCC__)
+#define IGD_HIP_OV_HD_ __host__ __device__
+#else
+#define IGD_HIP_OV_HD_
+#endif
+static inline int igd_hip_min_overlap_valid(const igd_hip_min_overlap *t)
+{
+    return !t || (t->min_bp >= 0 && t->ppm_query >= 0 && t->ppm_query <= IGD_HIP_PPM && t->ppm_record >= 0 && t->ppm_record <= IGD_HIP_PPM);
+}
+static inline int igd_hip_min_overlap_active(const igd_hip_min_overlap *t)
+{
+    return t && (t->min_bp | t->ppm_query | t->ppm_record) != 0;
+}
+static inline IGD_HIP_OV_HD_ int32_t igd_hip_min_overlap_need_q(int32_t min_bp, int32_t ppm_query, int32_t qs, int32_t qe)
+{
+    const int64_t lenq = (int64_t)qe - (int64_t)qs;
+    if (lenq <= 0) return -1;
+    int64_t need = (lenq * (int64_t)ppm_query + (IGD_HIP_PPM - 1)) / IGD_HIP_PPM;
+    if (need < min_bp) need = min_bp;
+    if (need < 1) need = 1;
+    return need > (int64_t)INT32_MAX ? -1 : (int32_t)need;
+}
+/* the pair (qs, qe) x (start, end), already counted by the plain predicate, under need_q >= 1 and ppm_record */
+static inline IGD_HIP_OV_HD_ int igd_hip_min_overlap_pair(int32_t need_q, int32_t ppm_record, int32_t qs, int32_t qe, int32_t start, int32_t end)
+{
+    const int64_t ov = (int64_t)(qe < end ? qe : end) - (int64_t)(qs > start ? qs : start);
+    return ov >= need_q && ov * IGD_HIP_PPM >= ((int64_t)end - (int64_t)start) * (int64_t)ppm_record;
+}
+int igd_hip_search_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                           const int64_t *set_off, int32_t nsets, int32_t v, int rule, int flags,
+                           int64_t *hits, int64_t *totals, const igd_hip_min_overlap *min_overlap);
+int igd_hip_support_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                            const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *support, int64_t *nhit,
+                            const igd_hip_min_overlap *min_overlap);
+/* igd_hip_search_sets_ov under an active threshold cuts EVERY set into slices for the kernel (as the support counts do):
+ * the batch pipeline takes no threshold, so `flags` and the 2^17 boundary have no effect then. */
+
 /* Covered base pairs of many query sets in one call.  Sets as igd_hip_search_sets.  With R_q(f) = the records of file f
  * that igd_hip_search_ex counts for the batch that holds query q = (contig, qs, qe) alone (same rule and v):
  *     coverage[k * nFiles + f] += sum over the queries q of set k of | [qs, qe) n union of [start, end) over R_q(f) |
@@ -215,6 +273,12 @@ int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t 
                              int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
                              int32_t v, int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
                              int64_t *clamped, int64_t *nhit, int64_t *unhit);
+/* The same under a minimum overlap (igd_hip_min_overlap above): the supports of the sets AND of the universe are taken under
+ * the threshold, as LOLA's runLOLA(minOverlap=) does; the tables, the Fisher cells and the clamp are formed as before. */
+int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                           int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
+                           int32_t v, int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
+                           int64_t *clamped, int64_t *nhit, int64_t *unhit, const igd_hip_min_overlap *min_overlap);
 /* Query sets RESTRICTED to the universe (LOLA's redefineUserSets): each set is replaced by the universe regions it overlaps
  * before anything is counted, so every table is a true 2x2 partition of the universe.  Sets as igd_hip_enrich_sets; the
  * universe is the nu regions u_ichr / u_qs / u_qe in ANY order.
@@ -387,6 +451,10 @@ static inline IGD_HIP_HD_ void igd_hip_perm_place(int mode, uint64_t base, int32
 int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
                             int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
                             int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax);
+/* The same under a minimum overlap (igd_hip_min_overlap above): the observed row and every permuted row are counted under it. */
+int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                               int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
+                               int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap);
 /* The two kernels on host arrays (db names the device and owns the workspaces; its records are not read).
  * igd_hip_permute_regions: permutations [p0, p0 + np) of nq regions into out_qs, out_qe (int32[np * nq], permutation-major);
  * nctg is the caller's, not tied to the database.  IGD_HIP_ERR_ARG for a missing array, no such mode, a negative size,
