@@ -137,112 +137,87 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_sets_coverage(DbView db, cons
             ntl = __builtin_amdgcn_readfirstlane(ntl);
             tag++;
             int allFront = INT_MIN;                                      // covered up to here under this query, any file
-            for (int k = 0; k < ntl; k++) {
-                const int t = gt0 + k;
-                const int tcnt = __builtin_amdgcn_readfirstlane(db.tileCnt[t]);
-                if (tcnt == 0) continue;
-                const int lob = (k == 0) ? INT_MIN : __builtin_amdgcn_readfirstlane(db.tileBd[t]);
-                const int64_t toff = db.tileOff[t];
-                for (int i0 = 0; i0 < tcnt; i0 += 2 * IGD_WAVE) {
-                    const int i = i0 + lane, j = i + IGD_WAVE;
-                    const bool ok0 = i < tcnt, ok1 = j < tcnt;
-                    const int s0 = ok0 ? db.start[toff + i] : INT_MAX;
-                    const int e0 = ok0 ? db.end[toff + i] : INT_MIN;
-                    const int x0 = ok0 ? db.idx[toff + i] : -1;
-                    const int s1 = ok1 ? db.start[toff + j] : INT_MAX;
-                    const int e1 = ok1 ? db.end[toff + j] : INT_MIN;
-                    const int x1 = ok1 ? db.idx[toff + j] : -1;
-                    bool h0 = (s0 >= lob) & (s0 < qe) & (e0 > qs) & ((unsigned)x0 < (unsigned)nF);
-                    bool h1 = (s1 >= lob) & (s1 < qe) & (e1 > qs) & ((unsigned)x1 < (unsigned)nF);
-                    if (USE_V) {
-                        const int v0 = ok0 ? db.value[toff + i] : INT_MIN;
-                        const int v1 = ok1 ? db.value[toff + j] : INT_MIN;
-                        h0 = h0 & (v0 >= v);
-                        h1 = h1 & (v1 >= v);
-                    }
-                    const u64 b0 = __ballot(h0), b1 = __ballot(h1);
-                    if (b0 | b1) {                                       // (wave-uniform: every lane goes the same way below)
-                        const int lo0 = s0 > qs ? s0 : qs, hi0 = e0 < qe ? e0 : qe;
-                        const int lo1 = s1 > qs ? s1 : qs, hi1 = e1 < qe ? e1 : qe;
-                        // any file: exclusive prefix maximum of hi in lane order, first half before second
-                        {
-                            const int in0 = wave_inclusive_max(h0 ? hi0 : INT_MIN);
-                            const int ex0 = wave_prev_lane(in0, lane);
-                            if (h0) mine += cov_beyond(lo0, hi0, ex0 > allFront ? ex0 : allFront);
-                            const int top0 = __builtin_amdgcn_readlane(in0, 63);
-                            allFront = top0 > allFront ? top0 : allFront;
-                            if (b1) {
-                                const int in1 = wave_inclusive_max(h1 ? hi1 : INT_MIN);
-                                const int ex1 = wave_prev_lane(in1, lane);
-                                if (h1) mine += cov_beyond(lo1, hi1, ex1 > allFront ? ex1 : allFront);
-                                const int top1 = __builtin_amdgcn_readlane(in1, 63);
-                                allFront = top1 > allFront ? top1 : allFront;
-                            }
-                        }
-                        // per file: the words as they are, then who else is here
-                        u64 w0 = 0, w1 = 0;
-                        unsigned r0 = (unsigned)lane, r1 = (unsigned)lane + 64u;
-                        if (h0) w0 = cov_word<LDS>(fl, fg, x0);
-                        if (h1) w1 = cov_word<LDS>(fl, fg, x1);
-                        if (h0) cov_mark<LDS>(fl, fg, x0, (unsigned)lane);
-                        if (h1) cov_mark<LDS>(fl, fg, x1, (unsigned)lane + 64u);
-                        if (h0) r0 = cov_marked<LDS>(fl, fg, x0);
-                        if (h1) r1 = cov_marked<LDS>(fl, fg, x1);
-                        // a word of another query is no frontier
-                        const int f0 = (unsigned)(w0 >> 32) == tag ? (int)(unsigned)w0 : INT_MIN;
-                        const int f1 = (unsigned)(w1 >> 32) == tag ? (int)(unsigned)w1 : INT_MIN;
-                        u64 p0 = __ballot(h0 & (r0 != (unsigned)lane)), p1 = __ballot(h1 & (r1 != (unsigned)lane + 64u));
-                        bool d0 = false, d1 = false;                     // applied by the ordered path
-#ifdef IGD_COVERAGE_PROBE
-                        if (lane == 0) {
-                            atomicAdd(&g_covProbe[0], 1ull);
-                            if (p0 | p1) atomicAdd(&g_covProbe[1], 1ull);
-                        }
-#endif
-                        while (p0 | p1) {                                // ordered path: one file with company per turn
-                            const int xf = p0 ? __builtin_amdgcn_readlane(x0, (int)__builtin_ctzll(p0))
-                                              : __builtin_amdgcn_readlane(x1, (int)__builtin_ctzll(p1));
-                            const bool m0 = h0 & (x0 == xf), m1 = h1 & (x1 == xf);
-                            const u64 mb0 = __ballot(m0), mb1 = __ballot(m1);
-                            // the file's frontier as any of its lanes read it (all of them before the first store)
-                            const int fx = mb0 ? __builtin_amdgcn_readlane(f0, (int)__builtin_ctzll(mb0))
-                                               : __builtin_amdgcn_readlane(f1, (int)__builtin_ctzll(mb1));
-                            const int in0 = wave_inclusive_max(m0 ? hi0 : INT_MIN);
-                            const int ex0 = wave_prev_lane(in0, lane);
-                            int top = __builtin_amdgcn_readlane(in0, 63);
-                            top = top > fx ? top : fx;
-                            const int in1 = wave_inclusive_max(m1 ? hi1 : INT_MIN);
+            walk_query_tiles<USE_V, false>(db, lane, nF, qs, qe, gt0, ntl, v, 0, MinOv{0, 0, 0}, [&](int s0, int e0, int x0, bool h0, int s1, int e1, int x1, bool h1) {
+                const u64 b0 = __ballot(h0), b1 = __ballot(h1);
+                if (b0 | b1) {                                       // (wave-uniform: every lane goes the same way below)
+                    const int lo0 = s0 > qs ? s0 : qs, hi0 = e0 < qe ? e0 : qe;
+                    const int lo1 = s1 > qs ? s1 : qs, hi1 = e1 < qe ? e1 : qe;
+                    // any file: exclusive prefix maximum of hi in lane order, first half before second
+                    {
+                        const int in0 = wave_inclusive_max(h0 ? hi0 : INT_MIN);
+                        const int ex0 = wave_prev_lane(in0, lane);
+                        mine += h0 ? cov_beyond(lo0, hi0, ex0 > allFront ? ex0 : allFront) : 0u;
+                        const int top0 = __builtin_amdgcn_readlane(in0, 63);
+                        allFront = top0 > allFront ? top0 : allFront;
+                        if (b1) {
+                            const int in1 = wave_inclusive_max(h1 ? hi1 : INT_MIN);
                             const int ex1 = wave_prev_lane(in1, lane);
-                            int end = __builtin_amdgcn_readlane(in1, 63);
-                            end = end > top ? end : top;
-                            if (m0) {
-                                const unsigned bp = cov_beyond(lo0, hi0, ex0 > fx ? ex0 : fx);
-                                if (bp) cov_add<LDS>(cnt, row, x0, bp);
-                                cov_set_word<LDS>(fl, fg, x0, tag, end);   // (every lane of the file stores the same word)
-                            }
-                            if (m1) {
-                                const unsigned bp = cov_beyond(lo1, hi1, ex1 > top ? ex1 : top);
-                                if (bp) cov_add<LDS>(cnt, row, x1, bp);
-                                cov_set_word<LDS>(fl, fg, x1, tag, end);
-                            }
-                            d0 |= m0; d1 |= m1;
-                            p0 &= ~mb0; p1 &= ~mb1;
-                        }
-                        if (h0 & !d0) {                                  // alone on its file: plain read-modify-write
-                            const unsigned bp = cov_beyond(lo0, hi0, f0);
-                            if (bp) cov_add<LDS>(cnt, row, x0, bp);
-                            cov_set_word<LDS>(fl, fg, x0, tag, hi0 > f0 ? hi0 : f0);
-                        }
-                        if (h1 & !d1) {
-                            const unsigned bp = cov_beyond(lo1, hi1, f1);
-                            if (bp) cov_add<LDS>(cnt, row, x1, bp);
-                            cov_set_word<LDS>(fl, fg, x1, tag, hi1 > f1 ? hi1 : f1);
+                            mine += h1 ? cov_beyond(lo1, hi1, ex1 > allFront ? ex1 : allFront) : 0u;
+                            const int top1 = __builtin_amdgcn_readlane(in1, 63);
+                            allFront = top1 > allFront ? top1 : allFront;
                         }
                     }
-                    // records are ordered by start: a step whose largest start is >= qe ends the tile
-                    if (__builtin_amdgcn_readlane(s1, 63) >= qe) break;
+                    // per file: the words as they are, then who else is here
+                    u64 w0 = 0, w1 = 0;
+                    unsigned r0 = (unsigned)lane, r1 = (unsigned)lane + 64u;
+                    if (h0) w0 = cov_word<LDS>(fl, fg, x0);
+                    if (h1) w1 = cov_word<LDS>(fl, fg, x1);
+                    if (h0) cov_mark<LDS>(fl, fg, x0, (unsigned)lane);
+                    if (h1) cov_mark<LDS>(fl, fg, x1, (unsigned)lane + 64u);
+                    if (h0) r0 = cov_marked<LDS>(fl, fg, x0);
+                    if (h1) r1 = cov_marked<LDS>(fl, fg, x1);
+                    // a word of another query is no frontier
+                    const int f0 = (unsigned)(w0 >> 32) == tag ? (int)(unsigned)w0 : INT_MIN;
+                    const int f1 = (unsigned)(w1 >> 32) == tag ? (int)(unsigned)w1 : INT_MIN;
+                    u64 p0 = __ballot(r0 != (unsigned)lane), p1 = __ballot(r1 != (unsigned)lane + 64u);   // (a lane without a hit kept its own number)
+                    bool d0 = false, d1 = false;                     // applied by the ordered path
+#ifdef IGD_COVERAGE_PROBE
+                    if (lane == 0) {
+                        atomicAdd(&g_covProbe[0], 1ull);
+                        if (p0 | p1) atomicAdd(&g_covProbe[1], 1ull);
+                    }
+#endif
+                    while (p0 | p1) {                                // ordered path: one file with company per turn
+                        const int xf = p0 ? __builtin_amdgcn_readlane(x0, (int)__builtin_ctzll(p0))
+                                          : __builtin_amdgcn_readlane(x1, (int)__builtin_ctzll(p1));
+                        const bool m0 = h0 & (x0 == xf), m1 = h1 & (x1 == xf);
+                        const u64 mb0 = __ballot(m0), mb1 = __ballot(m1);
+                        // the file's frontier as any of its lanes read it (all of them before the first store)
+                        const int fx = mb0 ? __builtin_amdgcn_readlane(f0, (int)__builtin_ctzll(mb0))
+                                           : __builtin_amdgcn_readlane(f1, (int)__builtin_ctzll(mb1));
+                        const int in0 = wave_inclusive_max(m0 ? hi0 : INT_MIN);
+                        const int ex0 = wave_prev_lane(in0, lane);
+                        int top = __builtin_amdgcn_readlane(in0, 63);
+                        top = top > fx ? top : fx;
+                        const int in1 = wave_inclusive_max(m1 ? hi1 : INT_MIN);
+                        const int ex1 = wave_prev_lane(in1, lane);
+                        int end = __builtin_amdgcn_readlane(in1, 63);
+                        end = end > top ? end : top;
+                        if (m0) {
+                            const unsigned bp = cov_beyond(lo0, hi0, ex0 > fx ? ex0 : fx);
+                            if (bp) cov_add<LDS>(cnt, row, x0, bp);
+                            cov_set_word<LDS>(fl, fg, x0, tag, end);   // (every lane of the file stores the same word)
+                        }
+                        if (m1) {
+                            const unsigned bp = cov_beyond(lo1, hi1, ex1 > top ? ex1 : top);
+                            if (bp) cov_add<LDS>(cnt, row, x1, bp);
+                            cov_set_word<LDS>(fl, fg, x1, tag, end);
+                        }
+                        d0 |= m0; d1 |= m1;
+                        p0 &= ~mb0; p1 &= ~mb1;
+                    }
+                    if (h0 & !d0) {                                  // alone on its file: plain read-modify-write
+                        const unsigned bp = cov_beyond(lo0, hi0, f0);
+                        if (bp) cov_add<LDS>(cnt, row, x0, bp);
+                        cov_set_word<LDS>(fl, fg, x0, tag, hi0 > f0 ? hi0 : f0);
+                    }
+                    if (h1 & !d1) {
+                        const unsigned bp = cov_beyond(lo1, hi1, f1);
+                        if (bp) cov_add<LDS>(cnt, row, x1, bp);
+                        cov_set_word<LDS>(fl, fg, x1, tag, hi1 > f1 ? hi1 : f1);
+                    }
                 }
-            }
+            });
         }
         // the slice's bp under any file: the lanes' sums meet in lane 0
         for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d, IGD_WAVE);

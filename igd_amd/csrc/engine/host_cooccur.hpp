@@ -16,11 +16,7 @@
 // that the refusal is met by a small fixture.
 static int64_t cooccur_max_files(void)
 {
-    static const int64_t m = []() -> int64_t {
-        const char *e = getenv("IGD_HIP_COOCCUR_MAX_FILES");
-        const long long x = e && *e ? atoll(e) : 0;
-        return x > 0 && x < IGD_COOCCUR_MAX_FILES ? (int64_t)x : IGD_COOCCUR_MAX_FILES;
-    }();
+    static const int64_t m = std::min(env_positive("IGD_HIP_COOCCUR_MAX_FILES", IGD_COOCCUR_MAX_FILES), (int64_t)IGD_COOCCUR_MAX_FILES);
     return m;
 }
 
@@ -102,8 +98,8 @@ extern "C" int igd_hip_bits_transpose(igd_hip_db *db, const uint32_t *bits, int6
     if (nrows == 0 || nW == 0) return IGD_HIP_OK;
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = restrict_grow(db, &db->d_coA, &db->coACap, (nrows * nW + 1) / 2);
-    if (rc == IGD_HIP_OK) rc = restrict_grow(db, &db->d_coCols, &db->coColsCap, 32 * nW * cw);
+    int rc = dev_grow(db, &db->d_coA, &db->coACap, (nrows * nW + 1) / 2);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_coCols, &db->coColsCap, 32 * nW * cw);
     if (rc != IGD_HIP_OK) return rc;
     HIPCHK(hipMemcpyAsync(db->d_coA, bits, (size_t)(nrows * nW) * 4, hipMemcpyHostToDevice, st));
     rc = transpose_launch((const unsigned *)db->d_coA, nrows, nW, db->d_coCols, st);
@@ -117,7 +113,7 @@ extern "C" int igd_hip_bits_transpose(igd_hip_db *db, const uint32_t *bits, int6
 // host rows of nwords32 uint32 words into resident rows of nw64 uint64 words (an odd nwords32: the pad word is zero)
 static int gram_upload(igd_hip_db *db, u64 **d, int64_t *cap, const uint32_t *h, int64_t rows, int64_t nwords32, int64_t nw64, hipStream_t st)
 {
-    int rc = restrict_grow(db, d, cap, rows * nw64);
+    int rc = dev_grow(db, d, cap, rows * nw64);
     if (rc != IGD_HIP_OK) return rc;
     if (nwords32 & 1) {
         HIPCHK(hipMemsetAsync(*d, 0, (size_t)(rows * nw64) * 8, st));
@@ -148,7 +144,7 @@ extern "C" int igd_hip_bitrows_gram(igd_hip_db *db, const uint32_t *a, int64_t m
     hipStream_t st = db->stream;
     int rc = gram_upload(db, &db->d_coA, &db->coACap, a, m, nwords32, nw64, st);
     if (rc == IGD_HIP_OK && !sym) rc = gram_upload(db, &db->d_coB, &db->coBCap, b, n, nwords32, nw64, st);
-    if (rc == IGD_HIP_OK) rc = restrict_grow(db, &db->d_coMat, &db->coMatCap, m * n);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_coMat, &db->coMatCap, m * n);
     if (rc != IGD_HIP_OK) return rc;
     HIPCHK(hipMemsetAsync(db->d_coMat, 0, (size_t)(m * n) * 8, st));
     rc = gram_launch(db->d_coA, m, sym ? nullptr : db->d_coB, n, nw64, nw64, db->d_coMat, st);
@@ -184,19 +180,17 @@ extern "C" int igd_hip_cooccur(igd_hip_db *db, const int32_t *ichr, const int32_
 
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = restrict_grow(db, &db->d_coMat, &db->coMatCap, nF * nF);
-    if (rc == IGD_HIP_OK) rc = restrict_grow(db, &db->d_coCols, &db->coColsCap, 32 * nW * ((step + 63) / 64));
-    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, step);
+    int rc = dev_grow(db, &db->d_coMat, &db->coMatCap, nF * nF);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_coCols, &db->coColsCap, 32 * nW * ((step + 63) / 64));
+    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, step);       // (the first chunk is the largest: stage_queries never grows them)
     if (rc == IGD_HIP_OK) rc = ensure_member_ws(db, step * nW, step);
     if (rc != IGD_HIP_OK) return rc;
     HIPCHK(hipMemsetAsync(db->d_coMat, 0, (size_t)(nF * nF) * 8, st));
     HIPCHK(hipMemsetAsync(db->d_memHit, 0, 8, st));
     for (int64_t c0 = 0; c0 < nq; c0 += step) {
         const int64_t m = nq - c0 < step ? nq - c0 : step, cw = (m + 63) / 64;
-        HIPCHK(hipMemcpyAsync(db->d_qc, ichr + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(db->d_qs, qs + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(db->d_qe, qe + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-        rc = igd_hip_membership_dev(db, db->d_qc, db->d_qs, db->d_qe, m, v, rule, db->d_memBits, nullptr, (int64_t *)db->d_memHit, st);
+        rc = stage_queries(db, ichr, qs, qe, c0, m);
+        if (rc == IGD_HIP_OK) rc = igd_hip_membership_dev(db, db->d_qc, db->d_qs, db->d_qe, m, v, rule, db->d_memBits, nullptr, (int64_t *)db->d_memHit, st);
         if (rc == IGD_HIP_OK) rc = transpose_launch(db->d_memBits, m, nW, db->d_coCols, st);
         if (rc == IGD_HIP_OK) rc = gram_launch(db->d_coCols, nF, nullptr, nF, cw, cw, db->d_coMat, st);
         if (rc != IGD_HIP_OK) return rc;

@@ -12,25 +12,9 @@
 #define IGD_FISHER_CHUNK ((int64_t)1 << 20)
 #define IGD_FISHER_MAX_N ((int64_t)1 << 31)              // a table's N stays below this
 
-static int ensure_fisher_ws(igd_hip_db *db, int64_t words)
-{
-    if (words <= db->fisherCap) return IGD_HIP_OK;
-    int rc;
-    HIPCHK(hipStreamSynchronize(db->stream));
-    if (db->d_fisher) (void)hipFree(db->d_fisher);
-    db->d_fisher = nullptr; db->fisherCap = 0;
-    if ((rc = dalloc(&db->d_fisher, (size_t)words, nullptr)) != IGD_HIP_OK) return rc;
-    db->fisherCap = words;
-    return IGD_HIP_OK;
-}
-
 // workgroups (of IGD_SETS_WG / IGD_WAVE waves) igd_fisher_cells is launched with for ncell cells: a wave takes a second cell
 // only when ncell exceeds the grid's waves
-extern "C" int32_t igd_hip_fisher_grid(int64_t ncell)
-{
-    const int64_t g = (ncell + (IGD_SETS_WG / IGD_WAVE) - 1) / (IGD_SETS_WG / IGD_WAVE);
-    return (int32_t)(g < 1 ? 1 : g < IGD_SETS_GRID ? g : IGD_SETS_GRID);
-}
+extern "C" int32_t igd_hip_fisher_grid(int64_t ncell) { return items_grid(ncell, IGD_SETS_WG / IGD_WAVE); }
 
 extern "C" int igd_hip_fisher_tables(igd_hip_db *db, const int64_t *a, const int64_t *b, const int64_t *c, const int64_t *d,
                                      int64_t ncell, double *pvalue_log, double *odds_ratio)
@@ -52,7 +36,7 @@ extern "C" int igd_hip_fisher_tables(igd_hip_db *db, const int64_t *a, const int
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
     const int64_t step = ncell < IGD_FISHER_CHUNK ? ncell : IGD_FISHER_CHUNK;
-    int rc = ensure_fisher_ws(db, 6 * step);
+    int rc = dev_grow(db, &db->d_fisher, &db->fisherCap, 6 * step);
     if (rc != IGD_HIP_OK) return rc;
     int64_t *dA = db->d_fisher, *dB = dA + step, *dC = dB + step, *dD = dC + step;
     double *dP = (double *)(dD + step), *dO = dP + step;
@@ -68,6 +52,42 @@ extern "C" int igd_hip_fisher_tables(igd_hip_db *db, const int64_t *a, const int
         if (odds_ratio) HIPCHK(hipMemcpyAsync(odds_ratio + c0, dO, (size_t)m * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
+    }
+    return IGD_HIP_OK;
+}
+
+// igd_fisher_cells<true> over nsets x nFiles cells: rows = the sets' support (host), usupport[nFiles], nk[nsets] = the sets'
+// sizes, nu = the universe's; b, c, d and the clamp flag are formed on the device.  pvalue_log / odds_ratio (may be NULL)
+// [nsets x nFiles] and clamped[nsets] (may be NULL) are the host's.
+static int fisher_enrich_cells(igd_hip_db *db, const int64_t *rows, const int64_t *usupport, const int64_t *nk, int32_t nsets, int64_t nu,
+                               double *pvalue_log, double *odds_ratio, int64_t *clamped)
+{
+    const int64_t nF = db->nFiles, ncell = (int64_t)nsets * nF;
+    if (ncell == 0) return IGD_HIP_OK;
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    const int64_t step = ncell < IGD_FISHER_CHUNK ? ncell : IGD_FISHER_CHUNK;
+    int rc = dev_grow(db, &db->d_fisher, &db->fisherCap, 3 * step + nF + 2 * (int64_t)nsets);
+    if (rc != IGD_HIP_OK) return rc;
+    int64_t *dA = db->d_fisher, *dU = dA + step, *dN = dU + nF;
+    u64 *dCl = (u64 *)(dN + nsets);
+    double *dP = (double *)(dCl + nsets), *dO = dP + step;
+    HIPCHK(hipMemcpyAsync(dU, usupport, (size_t)nF * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dN, nk, (size_t)nsets * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dCl, 0, (size_t)nsets * 8, st));
+    for (int64_t c0 = 0; c0 < ncell; c0 += step) {
+        const int64_t m = ncell - c0 < step ? ncell - c0 : step;
+        HIPCHK(hipMemcpyAsync(dA, rows + c0, (size_t)m * 8, hipMemcpyHostToDevice, st));
+        igd_fisher_cells<true><<<igd_hip_fisher_grid(m), IGD_SETS_WG, 0, st>>>(dA, dU, dN, nullptr, nu, nF, c0, m, dP, odds_ratio ? dO : nullptr, dCl);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(pvalue_log + c0, dP, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+        if (odds_ratio) HIPCHK(hipMemcpyAsync(odds_ratio + c0, dO, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+    }
+    if (clamped) {
+        HIPCHK(hipMemcpyAsync(clamped, dCl, (size_t)nsets * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
     return IGD_HIP_OK;
 }
@@ -92,20 +112,9 @@ extern "C" int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const
         return IGD_HIP_ERR_ARG;
     }
     // (the checks of igd_hip_support_sets, made here so that nothing of the caller's is written before them)
-    if (nsets > 0 && set_off[0] != 0) {
-        snprintf(g_err, sizeof g_err, "igd_hip_enrich_sets: set_off[0] = %lld, not 0", (long long)set_off[0]);
-        return IGD_HIP_ERR_ARG;
-    }
-    for (int32_t k = 0; k < nsets; k++)
-        if (set_off[k + 1] < set_off[k]) {
-            snprintf(g_err, sizeof g_err, "igd_hip_enrich_sets: set_off decreases at set %d", (int)k);
-            return IGD_HIP_ERR_ARG;
-        }
+    int rc = sets_check("igd_hip_enrich_sets", ichr, qs, qe, set_off, nsets);
+    if (rc != IGD_HIP_OK) return rc;
     const int64_t nq = nsets > 0 ? set_off[nsets] : 0;
-    if (nq > 0 && (!ichr || !qs || !qe)) {
-        snprintf(g_err, sizeof g_err, "igd_hip_enrich_sets: bad argument");
-        return IGD_HIP_ERR_ARG;
-    }
     for (int32_t k = 0; k < nsets; k++)
         if (set_off[k + 1] - set_off[k] + nu >= IGD_FISHER_MAX_N) {      // N <= n_k + n_U whatever is clamped
             snprintf(g_err, sizeof g_err, "igd_hip_enrich_sets: set %d and the universe hold 2^31 regions or more", (int)k);
@@ -129,7 +138,7 @@ extern "C" int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const
         off[0] = 0;
         for (int32_t k = 0; k < nsets; k++) { off[(size_t)k + 1] = set_off[k + 1]; nk[(size_t)k] = set_off[k + 1] - set_off[k]; }
         off[(size_t)nsets + 1] = tot;
-        const int rc = igd_hip_support_sets_ov(db, cc.data(), cs.data(), ce.data(), off.data(), nsets + 1, v, rule, rows.data(), hit.data(), min_overlap);
+        rc = igd_hip_support_sets_ov(db, cc.data(), cs.data(), ce.data(), off.data(), nsets + 1, v, rule, rows.data(), hit.data(), min_overlap);
         if (rc != IGD_HIP_OK) return rc;
     }
     if (nF) memcpy(usupport, rows.data() + (size_t)ncell, (size_t)nF * 8);
@@ -137,34 +146,7 @@ extern "C" int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const
     if (nhit && nsets) memcpy(nhit, hit.data(), (size_t)nsets * 8);
     if (unhit) *unhit = hit[(size_t)nsets];
     if (clamped && nsets) memset(clamped, 0, (size_t)nsets * 8);
-    if (ncell == 0) return IGD_HIP_OK;
-
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
-    const int64_t step = ncell < IGD_FISHER_CHUNK ? ncell : IGD_FISHER_CHUNK;
-    int rc = ensure_fisher_ws(db, 3 * step + nF + 2 * (int64_t)nsets);
-    if (rc != IGD_HIP_OK) return rc;
-    int64_t *dA = db->d_fisher, *dU = dA + step, *dN = dU + nF;
-    u64 *dCl = (u64 *)(dN + nsets);
-    double *dP = (double *)(dCl + nsets), *dO = dP + step;
-    HIPCHK(hipMemcpyAsync(dU, usupport, (size_t)nF * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dN, nk.data(), (size_t)nsets * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(dCl, 0, (size_t)nsets * 8, st));
-    for (int64_t c0 = 0; c0 < ncell; c0 += step) {
-        const int64_t m = ncell - c0 < step ? ncell - c0 : step;
-        HIPCHK(hipMemcpyAsync(dA, rows.data() + c0, (size_t)m * 8, hipMemcpyHostToDevice, st));
-        igd_fisher_cells<true><<<igd_hip_fisher_grid(m), IGD_SETS_WG, 0, st>>>(dA, dU, dN, nullptr, nu, nF, c0, m, dP, odds_ratio ? dO : nullptr, dCl);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(pvalue_log + c0, dP, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-        if (odds_ratio) HIPCHK(hipMemcpyAsync(odds_ratio + c0, dO, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-    }
-    if (clamped) {
-        HIPCHK(hipMemcpyAsync(clamped, dCl, (size_t)nsets * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGD_HIP_OK;
+    return fisher_enrich_cells(db, rows.data(), usupport, nk.data(), nsets, nu, pvalue_log, odds_ratio, clamped);
 }
 
 extern "C" int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,

@@ -7,18 +7,14 @@
 // device rows (a database of 10^6 files has 125 KB rows: 2^24 of them would be 2 TB); per chunk the queries go to the
 // device through the staging buffers of igd_hip_search (ensure_qstage), the device form runs on the engine's stream and the
 // rows come back into the caller's array at their place -- rows are per query, so chunks need no merging.
-// The image and the rule word are igd_hip_support_sets's (re-tiled copy, its gate bit).
+// The image and the rule word are igd_hip_support_sets's (slice_image, host_common.hpp).
 #define IGD_MEMBER_ROW_BYTES ((int64_t)256 << 20)    // device rows of one chunk (of the order of IGD_SETS_ROW_BYTES)
 
 // The TEST-ONLY variable IGD_HIP_MEMBER_ROW_BYTES (read once per process, as IGD_HIP_MAX_BATCH) lowers the budget so that
 // small fixtures cross the row seam.
 static int64_t member_row_bytes(void)
 {
-    static const int64_t m = []() -> int64_t {
-        const char *e = getenv("IGD_HIP_MEMBER_ROW_BYTES");
-        const long long x = e && *e ? atoll(e) : 0;
-        return x > 0 ? (int64_t)x : IGD_MEMBER_ROW_BYTES;
-    }();
+    static const int64_t m = env_positive("IGD_HIP_MEMBER_ROW_BYTES", IGD_MEMBER_ROW_BYTES);
     return m;
 }
 
@@ -26,11 +22,7 @@ extern "C" int64_t igd_hip_member_words(const igd_hip_db *db) { return db ? ((in
 
 // workgroups igd_member_rows is launched with for nq queries (each of IGD_SETS_WG / IGD_WAVE waves; a wave meets a second
 // query only when nq exceeds the grid's waves)
-extern "C" int32_t igd_hip_member_grid(int64_t nq)
-{
-    const int64_t g = (nq + (IGD_SETS_WG / IGD_WAVE) - 1) / (IGD_SETS_WG / IGD_WAVE);
-    return (int32_t)(g < 1 ? 1 : g < IGD_SETS_GRID ? g : IGD_SETS_GRID);
-}
+extern "C" int32_t igd_hip_member_grid(int64_t nq) { return items_grid(nq, IGD_SETS_WG / IGD_WAVE); }
 
 extern "C" int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq,
                                       int32_t v, int rule, uint32_t *d_bits, int32_t *d_nfiles_hit, int64_t *d_nhit, void *stream)
@@ -48,20 +40,15 @@ extern "C" int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, con
         if (d_nfiles_hit) HIPCHK(hipMemsetAsync(d_nfiles_hit, 0, (size_t)nq * 4, st));
         return IGD_HIP_OK;
     }
-    // the image and the rule word as igd_hip_support_sets gives them to igd_sets_support (re-tiled copy, its gate bit)
-    igd_hip_db *img = db->inner ? db->inner : db;
-    const int krule = db->inner ? (IGD_HIP_RULE_FLAT | (rule == IGD_HIP_RULE_NEST ? 0x100 : 0)) : rule;
-    const bool useV = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;     // gType 0 has no value field
+    const SliceImage im = slice_image(db, rule, v);
     const bool lds = nF <= IGD_MEMBER_LDS_FILES;
     const int grid = igd_hip_member_grid(nq);
     const size_t ldsB = (size_t)(4 + (lds ? (IGD_SETS_WG / IGD_WAVE) * nW : 0)) * 4;
-    u64 *T = (u64 *)d_nhit;
     const int n = (int)nq;
     if (!lds) HIPCHK(hipMemsetAsync(d_bits, 0, (size_t)(nq * nW) * 4, st));        // the wide form ORs into zeroed rows
-    if (useV && lds) igd_member_rows<true, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, d_ichr, d_qs, d_qe, n, krule, v, d_bits, d_nfiles_hit, T);
-    else if (useV) igd_member_rows<true, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, d_ichr, d_qs, d_qe, n, krule, v, d_bits, d_nfiles_hit, T);
-    else if (lds) igd_member_rows<false, true><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, d_ichr, d_qs, d_qe, n, krule, v, d_bits, d_nfiles_hit, T);
-    else igd_member_rows<false, false><<<grid, IGD_SETS_WG, ldsB, st>>>(img->v, d_ichr, d_qs, d_qe, n, krule, v, d_bits, d_nfiles_hit, T);
+    with_flags(im.useV, lds, [&](auto V, auto L) {
+        igd_member_rows<V(), L()><<<grid, IGD_SETS_WG, ldsB, st>>>(im.view, d_ichr, d_qs, d_qe, n, im.krule, v, d_bits, d_nfiles_hit, (u64 *)d_nhit);
+    });
     HIPCHK(hipGetLastError());
     if (!lds && d_nfiles_hit) {
         igd_member_popc<<<grid, IGD_SETS_WG, 0, st>>>(d_bits, n, (int)nW, d_nfiles_hit);
@@ -72,22 +59,10 @@ extern "C" int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, con
 
 static int ensure_member_ws(igd_hip_db *db, int64_t words, int64_t rows)
 {
-    int rc;
-    if (words > db->memBitsCap || rows > db->memNfCap) HIPCHK(hipStreamSynchronize(db->stream));
-    if (words > db->memBitsCap) {
-        if (db->d_memBits) (void)hipFree(db->d_memBits);
-        db->d_memBits = nullptr; db->memBitsCap = 0;
-        if ((rc = dalloc(&db->d_memBits, (size_t)words, nullptr)) != IGD_HIP_OK) return rc;
-        db->memBitsCap = words;
-    }
-    if (rows > db->memNfCap) {
-        if (db->d_memNf) (void)hipFree(db->d_memNf);
-        db->d_memNf = nullptr; db->memNfCap = 0;
-        if ((rc = dalloc(&db->d_memNf, (size_t)rows, nullptr)) != IGD_HIP_OK) return rc;
-        db->memNfCap = rows;
-    }
-    if (!db->d_memHit && (rc = dalloc(&db->d_memHit, (size_t)1, nullptr)) != IGD_HIP_OK) return rc;
-    return IGD_HIP_OK;
+    int rc = dev_grow(db, &db->d_memBits, &db->memBitsCap, words);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_memNf, &db->memNfCap, rows);
+    if (rc == IGD_HIP_OK && !db->d_memHit) rc = dalloc(&db->d_memHit, (size_t)1, nullptr);
+    return rc;
 }
 
 extern "C" int igd_hip_membership(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -112,12 +87,9 @@ extern "C" int igd_hip_membership(igd_hip_db *db, const int32_t *ichr, const int
     int64_t hit = 0;
     for (int64_t c0 = 0; c0 < nq; c0 += step) {
         const int64_t m = nq - c0 < step ? nq - c0 : step;
-        int rc = ensure_qstage(db, m);
-        if (rc == IGD_HIP_OK) rc = ensure_member_ws(db, m * nW, m);
+        int rc = ensure_member_ws(db, m * nW, m);
+        if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
         if (rc != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemcpyAsync(db->d_qc, ichr + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(db->d_qs, qs + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(db->d_qe, qe + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(db->d_memHit, 0, 8, st));
         rc = igd_hip_membership_dev(db, db->d_qc, db->d_qs, db->d_qe, m, v, rule, db->d_memBits, nfiles_hit ? db->d_memNf : nullptr,
                                     (int64_t *)db->d_memHit, st);

@@ -15,20 +15,12 @@
 // a chunk so that small fixtures cross the seam between two chunks.
 static int64_t perm_row_bytes(void)
 {
-    static const int64_t m = []() -> int64_t {
-        const char *e = getenv("IGD_HIP_PERM_ROW_BYTES");
-        const long long x = e && *e ? atoll(e) : 0;
-        return x > 0 ? (int64_t)x : IGD_SETS_ROW_BYTES;
-    }();
+    static const int64_t m = env_positive("IGD_HIP_PERM_ROW_BYTES", sets_row_bytes());
     return m;
 }
 
 // workgroups igd_permute_regions is launched with for n outputs: a lane takes a second one only when n exceeds the grid's lanes
-extern "C" int32_t igd_hip_permute_grid(int64_t n)
-{
-    const int64_t g = (n + IGD_SETS_WG - 1) / IGD_SETS_WG;
-    return (int32_t)(g < 1 ? 1 : g < IGD_SETS_GRID ? g : IGD_SETS_GRID);
-}
+extern "C" int32_t igd_hip_permute_grid(int64_t n) { return items_grid(n, IGD_SETS_WG); }
 
 // igd_perm_stats over nrows rows (device) into the six arrays at d_st; d_tot: see permute_dev.hpp
 static int perm_stats_launch(igd_hip_db *db, const int64_t *d_rows, const int64_t *d_tot, int64_t nrows, int64_t ncols,
@@ -109,7 +101,7 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
             return IGD_HIP_ERR_ARG;
         }
     }
-    const int64_t nF = db->nFiles, nC = nF + 1, nW = (nF + 31) / 32;
+    const int64_t nF = db->nFiles, nC = nF + 1;
     int64_t *const out[7] = {observed, sum, sumsq, n_ge, n_le, pmin, pmax};
     std::vector<int64_t> res((size_t)(7 * nC));
     if (nq == 0 || nF == 0) {
@@ -118,23 +110,14 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
         return IGD_HIP_OK;
     }
 
-    // the image and the rule word as igd_hip_support_sets gives them to igd_sets_support
-    igd_hip_db *img = db->inner ? db->inner : db;
-    const int krule = db->inner ? (IGD_HIP_RULE_FLAT | (rule == IGD_HIP_RULE_NEST ? 0x100 : 0)) : rule;
-    const bool useV = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
-    const bool lds = nF <= IGD_SUPPORT_LDS_FILES;
+    const SliceImage im = slice_image(db, rule, v);
     int64_t pc = max_batch() / nq;
     const int64_t byRows = perm_row_bytes() / (nF * 8);
     if (byRows < pc) pc = byRows < 1 ? 1 : byRows;
     if (nperm < pc) pc = nperm;
-    int64_t sliceLen = (pc * nq + IGD_SETS_SLICES - 1) / IGD_SETS_SLICES;
-    sliceLen = sliceLen < IGD_SETS_SLICE_MIN ? IGD_SETS_SLICE_MIN : sliceLen > IGD_SETS_SLICE_MAX ? IGD_SETS_SLICE_MAX : sliceLen;
+    const int64_t sliceLen = sets_slice_len(pc * nq);
     const int64_t perRow = (nq + sliceLen - 1) / sliceLen;                // slices of one permutation
-    int64_t maxGrid = IGD_SETS_GRID;
-    if (!lds) {
-        const int64_t g = IGD_SUPPORT_BITS_BYTES / (nW * 4 * (IGD_SETS_WG / IGD_WAVE));
-        maxGrid = g < 1 ? 1 : g < IGD_SETS_GRID ? g : IGD_SETS_GRID;
-    }
+    const int64_t maxGrid = support_max_grid(db);
     std::vector<SetSlice> slices;
     slices.reserve((size_t)(pc * perRow));
     for (int64_t r = 0; r < pc; r++)
@@ -143,11 +126,11 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
 
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = restrict_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + db->nCtg);
-    if (rc == IGD_HIP_OK) rc = restrict_grow(db, &db->d_pmStat, &db->pmStatCap, 7 * nC);
+    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + db->nCtg);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_pmStat, &db->pmStatCap, 7 * nC);
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
-    if (rc == IGD_HIP_OK) rc = ensure_sets_ws(db, pc * nF, pc, pc * perRow);
-    if (rc == IGD_HIP_OK && !lds) rc = ensure_support_bits(db, maxGrid * (IGD_SETS_WG / IGD_WAVE) * nW);
+    if (rc == IGD_HIP_OK) rc = sets_ws(db, pc * nF, pc, pc * perRow);
+    if (rc == IGD_HIP_OK) rc = ensure_support_bits(db, maxGrid);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
     long long *dObs = db->d_pmStat, *dSt = dObs + nC;
@@ -163,7 +146,7 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
         const int grid = ns < maxGrid ? ns : (int)maxGrid;
         HIPCHK(hipMemsetAsync(db->d_setRows, 0, (size_t)(rows * nF) * 8, st));
         HIPCHK(hipMemsetAsync(db->d_setTot, 0, (size_t)rows * 8, st));
-        return support_launch(db, img->v, c, s, e, ns, grid, krule, v, useV, lds, ov, mo);
+        return support_launch(db, im, c, s, e, ns, grid, v, ov, mo);
     };
 
     // the set as given
@@ -210,7 +193,7 @@ extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, cons
     std::vector<int32_t> hs((size_t)(np * nq)), he((size_t)(np * nq));
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = restrict_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg);
+    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg);
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
@@ -245,8 +228,8 @@ extern "C" int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t n
     std::vector<int64_t> res((size_t)(7 * ncols));
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = restrict_grow(db, &db->d_pmStat, &db->pmStatCap, 7 * ncols);
-    if (rc == IGD_HIP_OK) rc = ensure_sets_ws(db, step * ncols, step, 0);
+    int rc = dev_grow(db, &db->d_pmStat, &db->pmStatCap, 7 * ncols);
+    if (rc == IGD_HIP_OK) rc = sets_ws(db, step * ncols, step, 0);
     if (rc != IGD_HIP_OK) return rc;
     long long *dObs = db->d_pmStat, *dSt = dObs + ncols;
     HIPCHK(hipMemcpyAsync(dObs, observed, (size_t)ncols * 8, hipMemcpyHostToDevice, st));

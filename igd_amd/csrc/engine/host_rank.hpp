@@ -4,7 +4,7 @@
 // The table comes as three host matrices [nrows x ncols]; ncols is the caller's, not the database's.  Rows go through the
 // kernel in CHUNKS of whole rows of at most IGD_RANK_CHUNK cells (a wider row alone), one launch per chunk on the engine's
 // stream: the needed inputs up, the requested outputs straight into the caller's arrays at their place.  The workspace
-// is the handle's enrichment workspace (d_fisher, ensure_fisher_ws): per cell of a chunk 7 words -- three inputs, q, mean and
+// is the handle's enrichment workspace (d_fisher, dev_grow): per cell of a chunk 7 words -- three inputs, q, mean and
 // four int32 rank rows -- and, for rows wider than IGD_RANK_LDS_COLS, the workgroups' sort slices (1.5 words per padded cell).
 #define IGD_RANK_CHUNK ((int64_t)1 << 20)
 
@@ -56,7 +56,7 @@ extern "C" int igd_hip_enrich_ranks(igd_hip_db *db, const int64_t *support, cons
     const int64_t step = nrows < rowsPer ? nrows : rowsPer, cells = step * ncols;
     const int32_t maxGrid = igd_hip_rank_grid(step);
     const int64_t sortWords = lds ? 0 : (int64_t)maxGrid * n + ((int64_t)maxGrid * n + 1) / 2;
-    int rc = ensure_fisher_ws(db, 7 * cells + sortWords);
+    int rc = dev_grow(db, &db->d_fisher, &db->fisherCap, 7 * cells + sortWords);
     if (rc != IGD_HIP_OK) return rc;
     int64_t *dS = db->d_fisher;
     double *dP = (double *)(dS + cells), *dO = dP + cells, *dQ = dO + cells, *dMean = dQ + cells;

@@ -4,7 +4,7 @@
 // The join.  The host orders the universe regions with ichr >= 0 by (ichr, start) -- the sort is skipped when they come that
 // way --, builds per contig the prefix maximum of the ends and uploads them with the permutation back to the caller's order
 // and the contig range table.  The sets go through igd_restrict_bits in CHUNKS of whole sets whose rows (nUW words each) stay
-// within restrict_row_bytes() (IGD_SETS_ROW_BYTES) and, in the enrichment form, whose support rows do too; inside a chunk the
+// within restrict_row_bytes() (sets_row_bytes()) and, in the enrichment form, whose support rows do too; inside a chunk the
 // regions are uploaded in batches of at most igd_hip_max_batch() (a set may be cut between two batches: its row is an OR).
 // The rows are zeroed on the stream before the first batch; igd_member_popc behind the last one gives |R_k|.
 // The enrichment.  The join of all chunks first (rows to the host, or left on the device when one chunk holds all sets); then
@@ -19,56 +19,24 @@ static_assert((unsigned long long)IGD_RESTRICT_BLOCK_WORDS * 32ull <= 0xffffffff
 // a set chunk so that small fixtures cross the seam between two chunks.
 static int64_t restrict_row_bytes(void)
 {
-    static const int64_t m = []() -> int64_t {
-        const char *e = getenv("IGD_HIP_RESTRICT_ROW_BYTES");
-        const long long x = e && *e ? atoll(e) : 0;
-        return x > 0 ? (int64_t)x : IGD_SETS_ROW_BYTES;
-    }();
+    static const int64_t m = env_positive("IGD_HIP_RESTRICT_ROW_BYTES", sets_row_bytes());
     return m;
 }
 
 // workgroups igd_restrict_bits is launched with for nregions set regions: a lane takes a second region only when nregions
 // exceeds the grid's lanes
-extern "C" int32_t igd_hip_restrict_grid(int64_t nregions)
-{
-    const int64_t g = (nregions + IGD_SETS_WG - 1) / IGD_SETS_WG;
-    return (int32_t)(g < 1 ? 1 : g < IGD_SETS_GRID ? g : IGD_SETS_GRID);
-}
-
-template <typename T>
-static int restrict_grow(igd_hip_db *db, T **p, int64_t *cap, int64_t need)
-{
-    if (need <= *cap) return IGD_HIP_OK;
-    int rc;
-    HIPCHK(hipStreamSynchronize(db->stream));
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    if ((rc = dalloc(p, (size_t)need, nullptr)) != IGD_HIP_OK) return rc;
-    *cap = need;
-    return IGD_HIP_OK;
-}
+extern "C" int32_t igd_hip_restrict_grid(int64_t nregions) { return items_grid(nregions, IGD_SETS_WG); }
 
 // the checks of igd_hip_enrich_sets that both entry points share
 static int restrict_check(const char *who, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
                           const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu)
 {
-    if (nsets < 0 || nsets == INT32_MAX || nu < 0 || (nu > 0 && (!u_ichr || !u_qs || !u_qe)) || (nsets > 0 && !set_off)) {
+    if (nsets == INT32_MAX || nu < 0 || (nu > 0 && (!u_ichr || !u_qs || !u_qe))) {
         snprintf(g_err, sizeof g_err, "%s: bad argument", who);
         return IGD_HIP_ERR_ARG;
     }
-    if (nsets > 0 && set_off[0] != 0) {
-        snprintf(g_err, sizeof g_err, "%s: set_off[0] = %lld, not 0", who, (long long)set_off[0]);
-        return IGD_HIP_ERR_ARG;
-    }
-    for (int32_t k = 0; k < nsets; k++)
-        if (set_off[k + 1] < set_off[k]) {
-            snprintf(g_err, sizeof g_err, "%s: set_off decreases at set %d", who, (int)k);
-            return IGD_HIP_ERR_ARG;
-        }
-    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) {
-        snprintf(g_err, sizeof g_err, "%s: bad argument", who);
-        return IGD_HIP_ERR_ARG;
-    }
+    const int rc = sets_check(who, ichr, qs, qe, set_off, nsets);
+    if (rc != IGD_HIP_OK) return rc;
     if (nu + 1 >= IGD_FISHER_MAX_N) {
         snprintf(g_err, sizeof g_err, "%s: the universe holds 2^31 - 1 regions or more", who);
         return IGD_HIP_ERR_ARG;
@@ -130,8 +98,8 @@ static int restrict_join(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
 
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = restrict_grow(db, &db->d_rsUni, &db->rsUniCap, 4 * nv + 1);
-    if (rc == IGD_HIP_OK) rc = restrict_grow(db, &db->d_rsTab, &db->rsTabCap, (int64_t)(2 * nc + 1) + (nsets < rowCap ? nsets : rowCap) + 1);
+    int rc = dev_grow(db, &db->d_rsUni, &db->rsUniCap, 4 * nv + 1);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_rsTab, &db->rsTabCap, (int64_t)(2 * nc + 1) + (nsets < rowCap ? nsets : rowCap) + 1);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *dS = db->d_rsUni, *dE = dS + nv, *dM = dE + nv, *dP = dM + nv;
     int32_t *dCv = db->d_rsTab, *dCb = dCv + nc, *dOff = dCb + nc + 1;
@@ -143,8 +111,8 @@ static int restrict_join(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
     std::vector<int32_t> hoff, hsize;
     for (int32_t k0 = 0; k0 < nsets; k0 += (int32_t)rowCap) {
         const int32_t rows = (int32_t)(nsets - k0 < rowCap ? nsets - k0 : rowCap);
-        rc = restrict_grow(db, &db->d_rsBits, &db->rsBitsCap, (int64_t)rows * nUW);
-        if (rc == IGD_HIP_OK) rc = restrict_grow(db, &db->d_rsSize, &db->rsSizeCap, (int64_t)rows);
+        rc = dev_grow(db, &db->d_rsBits, &db->rsBitsCap, (int64_t)rows * nUW);
+        if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_rsSize, &db->rsSizeCap, (int64_t)rows);
         if (rc != IGD_HIP_OK) return rc;
         HIPCHK(hipMemsetAsync(db->d_rsBits, 0, (size_t)((int64_t)rows * nUW) * 4, st));
         hoff.resize((size_t)rows + 1);
@@ -154,11 +122,7 @@ static int restrict_join(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
                 const int64_t o = set_off[k0 + k] - c0;
                 hoff[(size_t)k] = (int32_t)(o < 0 ? 0 : o > m ? m : o);
             }
-            rc = ensure_qstage(db, m);
-            if (rc != IGD_HIP_OK) return rc;
-            HIPCHK(hipMemcpyAsync(db->d_qc, ichr + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(db->d_qs, qs + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(db->d_qe, qe + c0, (size_t)m * 4, hipMemcpyHostToDevice, st));
+            if ((rc = stage_queries(db, ichr, qs, qe, c0, m)) != IGD_HIP_OK) return rc;
             HIPCHK(hipMemcpyAsync(dOff, hoff.data(), (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, st));
             igd_restrict_bits<<<igd_hip_restrict_grid(m), IGD_SETS_WG, 0, st>>>(db->d_qc, db->d_qs, db->d_qe, (int)m, dOff, rows, dCv, dCb, nc,
                                                                                  dS, dE, dM, dP, nUW, db->d_rsBits);
@@ -234,12 +198,9 @@ extern "C" int igd_hip_enrich_restricted(igd_hip_db *db, const int32_t *ichr, co
         std::vector<int64_t> hrows, htot;
         for (int64_t u0 = 0; u0 < nu; u0 += ustep) {
             const int64_t um = nu - u0 < ustep ? nu - u0 : ustep, u1 = u0 + um;
-            rc = ensure_qstage(db, um);
-            if (rc == IGD_HIP_OK) rc = ensure_member_ws(db, um * nW, um);
+            rc = ensure_member_ws(db, um * nW, um);
+            if (rc == IGD_HIP_OK) rc = stage_queries(db, u_ichr, u_qs, u_qe, u0, um);
             if (rc != IGD_HIP_OK) return rc;
-            HIPCHK(hipMemcpyAsync(db->d_qc, u_ichr + u0, (size_t)um * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(db->d_qs, u_qs + u0, (size_t)um * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(db->d_qe, u_qe + u0, (size_t)um * 4, hipMemcpyHostToDevice, st));
             rc = igd_hip_membership_dev(db, db->d_qc, db->d_qs, db->d_qe, um, v, rule, db->d_memBits, db->d_memNf, nullptr, st);
             if (rc != IGD_HIP_OK) return rc;
             const int64_t w0 = u0 >> 5, w1 = (u1 + 31) >> 5, nblk = (w1 - w0 + IGD_RESTRICT_BLOCK_WORDS - 1) / IGD_RESTRICT_BLOCK_WORDS;
@@ -248,12 +209,12 @@ extern "C" int igd_hip_enrich_restricted(igd_hip_db *db, const int32_t *ichr, co
                 const int32_t r = srows + (k0 == 0 ? 1 : 0);             // the first chunk carries the ones row
                 const int ones = k0 == 0 ? srows : -1;
                 if (srows > 0 && !one) {
-                    rc = restrict_grow(db, &db->d_rsBits, &db->rsBitsCap, (int64_t)srows * nUW);
+                    rc = dev_grow(db, &db->d_rsBits, &db->rsBitsCap, (int64_t)srows * nUW);
                     if (rc != IGD_HIP_OK) return rc;
                     HIPCHK(hipMemcpyAsync(db->d_rsBits, hb.data() + (size_t)k0 * (size_t)nUW, (size_t)((int64_t)srows * nUW) * 4,
                                           hipMemcpyHostToDevice, st));
                 }
-                rc = ensure_sets_ws(db, (int64_t)r * nF, r, 0);
+                rc = sets_ws(db, (int64_t)r * nF, r, 0);
                 if (rc != IGD_HIP_OK) return rc;
                 HIPCHK(hipMemsetAsync(db->d_setRows, 0, (size_t)((int64_t)r * nF) * 8, st));
                 HIPCHK(hipMemsetAsync(db->d_setTot, 0, (size_t)r * 8, st));
@@ -286,27 +247,8 @@ extern "C" int igd_hip_enrich_restricted(igd_hip_db *db, const int32_t *ichr, co
 
     // the statistics: igd_fisher_cells<true> on the restricted supports, n_k := |R_k| (nothing can be clamped)
     std::vector<double> hp((size_t)ncell + 1), ho((size_t)ncell + 1);
-    if (ncell > 0) {
-        const int64_t step = ncell < IGD_FISHER_CHUNK ? ncell : IGD_FISHER_CHUNK;
-        rc = ensure_fisher_ws(db, 3 * step + nF + 2 * (int64_t)nsets);
-        if (rc != IGD_HIP_OK) return rc;
-        int64_t *dA = db->d_fisher, *dU = dA + step, *dN = dU + nF;
-        u64 *dCl = (u64 *)(dN + nsets);
-        double *dP = (double *)(dCl + nsets), *dO = dP + step;
-        HIPCHK(hipMemcpyAsync(dU, urow.data(), (size_t)nF * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dN, hz.data(), (size_t)nsets * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(dCl, 0, (size_t)nsets * 8, st));
-        for (int64_t c0 = 0; c0 < ncell; c0 += step) {
-            const int64_t m = ncell - c0 < step ? ncell - c0 : step;
-            HIPCHK(hipMemcpyAsync(dA, rows.data() + c0, (size_t)m * 8, hipMemcpyHostToDevice, st));
-            igd_fisher_cells<true><<<igd_hip_fisher_grid(m), IGD_SETS_WG, 0, st>>>(dA, dU, dN, nullptr, nu, nF, c0, m, dP, odds_ratio ? dO : nullptr, dCl);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(hp.data() + c0, dP, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-            if (odds_ratio) HIPCHK(hipMemcpyAsync(ho.data() + c0, dO, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            HIPCHK(hipGetLastError());
-        }
-    }
+    rc = fisher_enrich_cells(db, rows.data(), urow.data(), hz.data(), nsets, nu, hp.data(), odds_ratio ? ho.data() : nullptr, nullptr);
+    if (rc != IGD_HIP_OK) return rc;
 
     if (nF) memcpy(usupport, urow.data(), (size_t)nF * 8);
     if (ncell) {

@@ -68,41 +68,16 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_member_rows(DbView db, const 
         gt0 = __builtin_amdgcn_readfirstlane(gt0);
         ntl = __builtin_amdgcn_readfirstlane(ntl);
         u64 any = 0;
-        for (int k = 0; k < ntl; k++) {
-            const int t = gt0 + k;
-            const int tcnt = __builtin_amdgcn_readfirstlane(db.tileCnt[t]);
-            if (tcnt == 0) continue;
-            const int lob = (k == 0) ? INT_MIN : __builtin_amdgcn_readfirstlane(db.tileBd[t]);
-            const int64_t toff = db.tileOff[t];
-            for (int i0 = 0; i0 < tcnt; i0 += 2 * IGD_WAVE) {
-                const int i = i0 + lane, j = i + IGD_WAVE;
-                const bool ok0 = i < tcnt, ok1 = j < tcnt;
-                const int s0 = ok0 ? db.start[toff + i] : INT_MAX;
-                const int e0 = ok0 ? db.end[toff + i] : INT_MIN;
-                const int x0 = ok0 ? db.idx[toff + i] : -1;
-                const int s1 = ok1 ? db.start[toff + j] : INT_MAX;
-                const int e1 = ok1 ? db.end[toff + j] : INT_MIN;
-                const int x1 = ok1 ? db.idx[toff + j] : -1;
-                bool h0 = (s0 >= lob) & (s0 < qe) & (e0 > qs) & ((unsigned)x0 < (unsigned)nF);
-                bool h1 = (s1 >= lob) & (s1 < qe) & (e1 > qs) & ((unsigned)x1 < (unsigned)nF);
-                if (USE_V) {
-                    const int v0 = ok0 ? db.value[toff + i] : INT_MIN;
-                    const int v1 = ok1 ? db.value[toff + j] : INT_MIN;
-                    h0 = h0 & (v0 >= v);
-                    h1 = h1 & (v1 >= v);
-                }
-                if (LDS) {
-                    if (h0) (void)__hip_atomic_fetch_or(bm + (x0 >> 5), 1u << (x0 & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (h1) (void)__hip_atomic_fetch_or(bm + (x1 >> 5), 1u << (x1 & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                } else {
-                    if (h0) (void)__hip_atomic_fetch_or(row + (x0 >> 5), 1u << (x0 & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (h1) (void)__hip_atomic_fetch_or(row + (x1 >> 5), 1u << (x1 & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                any |= __ballot(h0) | __ballot(h1);
-                // records are ordered by start: a step whose largest start is >= qe ends the tile
-                if (__builtin_amdgcn_readlane(s1, 63) >= qe) break;
+        walk_query_tiles<USE_V, false>(db, lane, nF, qs, qe, gt0, ntl, v, 0, MinOv{0, 0, 0}, [&](int, int, int x0, bool h0, int, int, int x1, bool h1) {
+            if (LDS) {
+                if (h0) (void)__hip_atomic_fetch_or(bm + (x0 >> 5), 1u << (x0 & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (h1) (void)__hip_atomic_fetch_or(bm + (x1 >> 5), 1u << (x1 & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else {
+                if (h0) (void)__hip_atomic_fetch_or(row + (x0 >> 5), 1u << (x0 & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (h1) (void)__hip_atomic_fetch_or(row + (x1 >> 5), 1u << (x1 & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-        }
+            any |= __ballot(h0) | __ballot(h1);
+        });
         if (any) hitq++;
         if (LDS) {
             if (any) {

@@ -36,6 +36,49 @@ __device__ __forceinline__ bool min_ov_pair(int need, int ppmR, int qs, int qe, 
     return ok;
 }
 
+// The forward walk over one query's tiles that igd_sets_count, igd_sets_support, igd_sets_coverage and igd_member_rows share:
+// tiles gt0 .. gt0 + ntl - 1 (query_span), each from its first record, 2 x 64 records per iteration with all loads issued
+// together, the predicate above with its USE_V (value >= v) and OV (min_ov_pair under `need`, `mo`) terms, then
+// step(s0, e0, x0, h0, s1, e1, x1, h1) -- start, end, idx and "counted" of this lane's two records; a lane past the tile's end
+// has h = false -- and the early exit.  Everything but `lane` and what step() does per lane is wave-uniform.
+template <bool USE_V, bool OV, typename F>
+__device__ __forceinline__ void walk_query_tiles(const DbView &db, int lane, int nF, int qs, int qe, int gt0, int ntl, int v, int need,
+                                                 const MinOv &mo, F &&step)
+{
+    for (int k = 0; k < ntl; k++) {
+        const int t = gt0 + k;
+        const int tcnt = __builtin_amdgcn_readfirstlane(db.tileCnt[t]);
+        if (tcnt == 0) continue;
+        const int lob = (k == 0) ? INT_MIN : __builtin_amdgcn_readfirstlane(db.tileBd[t]);
+        const int64_t toff = db.tileOff[t];
+        for (int i0 = 0; i0 < tcnt; i0 += 2 * IGD_WAVE) {
+            const int i = i0 + lane, j = i + IGD_WAVE;
+            const bool ok0 = i < tcnt, ok1 = j < tcnt;
+            const int s0 = ok0 ? db.start[toff + i] : INT_MAX;
+            const int e0 = ok0 ? db.end[toff + i] : INT_MIN;
+            const int x0 = ok0 ? db.idx[toff + i] : -1;
+            const int s1 = ok1 ? db.start[toff + j] : INT_MAX;
+            const int e1 = ok1 ? db.end[toff + j] : INT_MIN;
+            const int x1 = ok1 ? db.idx[toff + j] : -1;
+            bool h0 = (s0 >= lob) & (s0 < qe) & (e0 > qs) & ((unsigned)x0 < (unsigned)nF);
+            bool h1 = (s1 >= lob) & (s1 < qe) & (e1 > qs) & ((unsigned)x1 < (unsigned)nF);
+            if (USE_V) {
+                const int v0 = ok0 ? db.value[toff + i] : INT_MIN;
+                const int v1 = ok1 ? db.value[toff + j] : INT_MIN;
+                h0 = h0 & (v0 >= v);
+                h1 = h1 & (v1 >= v);
+            }
+            if (OV) {
+                h0 = h0 & min_ov_pair(need, mo.ppm_record, qs, qe, s0, e0);
+                h1 = h1 & min_ov_pair(need, mo.ppm_record, qs, qe, s1, e1);
+            }
+            step(s0, e0, x0, h0, s1, e1, x1, h1);
+            // records are ordered by start: a step whose largest start is >= qe ends the tile
+            if (__builtin_amdgcn_readlane(s1, 63) >= qe) break;
+        }
+    }
+}
+
 template <bool USE_V, bool LDS, bool OV>
 __device__ __forceinline__ void sets_count_body(const DbView &db, const int32_t *__restrict__ q_ichr, const int32_t *__restrict__ q_qs,
                                                 const int32_t *__restrict__ q_qe, const SetSlice *__restrict__ slices, int nSlices,
@@ -67,45 +110,16 @@ __device__ __forceinline__ void sets_count_body(const DbView &db, const int32_t 
             if (!query_span(db, cc, qs, qe, rule, gt0, ntl)) continue;
             gt0 = __builtin_amdgcn_readfirstlane(gt0);
             ntl = __builtin_amdgcn_readfirstlane(ntl);
-            for (int k = 0; k < ntl; k++) {
-                const int t = gt0 + k;
-                const int tcnt = __builtin_amdgcn_readfirstlane(db.tileCnt[t]);
-                if (tcnt == 0) continue;
-                const int lob = (k == 0) ? INT_MIN : __builtin_amdgcn_readfirstlane(db.tileBd[t]);
-                const int64_t toff = db.tileOff[t];
-                for (int i0 = 0; i0 < tcnt; i0 += 2 * IGD_WAVE) {
-                    const int i = i0 + lane, j = i + IGD_WAVE;
-                    const bool ok0 = i < tcnt, ok1 = j < tcnt;
-                    const int s0 = ok0 ? db.start[toff + i] : INT_MAX;
-                    const int e0 = ok0 ? db.end[toff + i] : INT_MIN;
-                    const int x0 = ok0 ? db.idx[toff + i] : -1;
-                    const int s1 = ok1 ? db.start[toff + j] : INT_MAX;
-                    const int e1 = ok1 ? db.end[toff + j] : INT_MIN;
-                    const int x1 = ok1 ? db.idx[toff + j] : -1;
-                    bool h0 = (s0 >= lob) & (s0 < qe) & (e0 > qs) & ((unsigned)x0 < (unsigned)nF);
-                    bool h1 = (s1 >= lob) & (s1 < qe) & (e1 > qs) & ((unsigned)x1 < (unsigned)nF);
-                    if (USE_V) {
-                        const int v0 = ok0 ? db.value[toff + i] : INT_MIN;
-                        const int v1 = ok1 ? db.value[toff + j] : INT_MIN;
-                        h0 = h0 & (v0 >= v);
-                        h1 = h1 & (v1 >= v);
-                    }
-                    if (OV) {
-                        h0 = h0 & min_ov_pair(need, mo.ppm_record, qs, qe, s0, e0);
-                        h1 = h1 & min_ov_pair(need, mo.ppm_record, qs, qe, s1, e1);
-                    }
-                    if (LDS) {
-                        if (h0) (void)__hip_atomic_fetch_add(cnt + x0, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (h1) (void)__hip_atomic_fetch_add(cnt + x1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    } else {
-                        if (h0) (void)__hip_atomic_fetch_add(row + x0, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (h1) (void)__hip_atomic_fetch_add(row + x1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    found += (u64)__popcll(__ballot(h0)) + (u64)__popcll(__ballot(h1));
-                    // records are ordered by start: a step whose largest start is >= qe ends the tile
-                    if (__builtin_amdgcn_readlane(s1, 63) >= qe) break;
+            walk_query_tiles<USE_V, OV>(db, lane, nF, qs, qe, gt0, ntl, v, need, mo, [&](int, int, int x0, bool h0, int, int, int x1, bool h1) {
+                if (LDS) {
+                    if (h0) (void)__hip_atomic_fetch_add(cnt + x0, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (h1) (void)__hip_atomic_fetch_add(cnt + x1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                } else {
+                    if (h0) (void)__hip_atomic_fetch_add(row + x0, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (h1) (void)__hip_atomic_fetch_add(row + x1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-            }
+                found += (u64)__popcll(__ballot(h0)) + (u64)__popcll(__ballot(h1));
+            });
         }
         if (lane == 0 && found) (void)__hip_atomic_fetch_add(totals + sl.row, found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (LDS) {

@@ -85,40 +85,11 @@ __device__ __forceinline__ void sets_support_body(const DbView &db, const int32_
             gt0 = __builtin_amdgcn_readfirstlane(gt0);
             ntl = __builtin_amdgcn_readfirstlane(ntl);
             u64 any = 0;
-            for (int k = 0; k < ntl; k++) {
-                const int t = gt0 + k;
-                const int tcnt = __builtin_amdgcn_readfirstlane(db.tileCnt[t]);
-                if (tcnt == 0) continue;
-                const int lob = (k == 0) ? INT_MIN : __builtin_amdgcn_readfirstlane(db.tileBd[t]);
-                const int64_t toff = db.tileOff[t];
-                for (int i0 = 0; i0 < tcnt; i0 += 2 * IGD_WAVE) {
-                    const int i = i0 + lane, j = i + IGD_WAVE;
-                    const bool ok0 = i < tcnt, ok1 = j < tcnt;
-                    const int s0 = ok0 ? db.start[toff + i] : INT_MAX;
-                    const int e0 = ok0 ? db.end[toff + i] : INT_MIN;
-                    const int x0 = ok0 ? db.idx[toff + i] : -1;
-                    const int s1 = ok1 ? db.start[toff + j] : INT_MAX;
-                    const int e1 = ok1 ? db.end[toff + j] : INT_MIN;
-                    const int x1 = ok1 ? db.idx[toff + j] : -1;
-                    bool h0 = (s0 >= lob) & (s0 < qe) & (e0 > qs) & ((unsigned)x0 < (unsigned)nF);
-                    bool h1 = (s1 >= lob) & (s1 < qe) & (e1 > qs) & ((unsigned)x1 < (unsigned)nF);
-                    if (USE_V) {
-                        const int v0 = ok0 ? db.value[toff + i] : INT_MIN;
-                        const int v1 = ok1 ? db.value[toff + j] : INT_MIN;
-                        h0 = h0 & (v0 >= v);
-                        h1 = h1 & (v1 >= v);
-                    }
-                    if (OV) {
-                        h0 = h0 & min_ov_pair(need, mo.ppm_record, qs, qe, s0, e0);
-                        h1 = h1 & min_ov_pair(need, mo.ppm_record, qs, qe, s1, e1);
-                    }
-                    if (h0) support_mark<LDS>(bits, cnt, gb, row, x0);
-                    if (h1) support_mark<LDS>(bits, cnt, gb, row, x1);
-                    any |= __ballot(h0) | __ballot(h1);
-                    // records are ordered by start: a step whose largest start is >= qe ends the tile
-                    if (__builtin_amdgcn_readlane(s1, 63) >= qe) break;
-                }
-            }
+            walk_query_tiles<USE_V, OV>(db, lane, nF, qs, qe, gt0, ntl, v, need, mo, [&](int, int, int x0, bool h0, int, int, int x1, bool h1) {
+                if (h0) support_mark<LDS>(bits, cnt, gb, row, x0);
+                if (h1) support_mark<LDS>(bits, cnt, gb, row, x1);
+                any |= __ballot(h0) | __ballot(h1);
+            });
             if (any) {
                 // the next query starts from an empty bitmap.  (The ORs above have returned: their values were used.  The
                 // stores below and the next query's ORs are the same wave's accesses to the same unit, executed in order.)

@@ -292,7 +292,8 @@ struct igd_hip_db {
     int32_t *d_qc, *d_qs, *d_qe;
     int64_t qcap;
     int64_t *d_hits, *d_total;
-    // igd_hip_search_sets (host_sets.hpp): the rows and totals of one chunk of sets, the slice table of its small sets
+    // igd_hip_search_sets (host_sets.hpp): the rows and totals of one chunk of sets, the slice table of its small sets.  These and
+    // the workspaces below only grow: dev_grow (host_common.hpp)
     int64_t *d_setRows, *d_setTot;
     int64_t setRowCap, setTotCap;
     struct SetSlice *d_setSlices;
@@ -368,6 +369,7 @@ struct igd_hip_db {
 #include "engine/host_enumerate.hpp"  // `-f` on the host side: chunked, double-buffered
 #include "engine/seqpare.hpp"         // Seqpare `-s`: kernels and host
 #include "engine/host_misc.hpp"       // igd_hip_hitmap, igd_hip_batch_stats
+#include "engine/host_common.hpp"     // shared by the parts below: dev_grow, stage_queries, slice_image, sets_check, with_flags, run_set_chunks
 #include "engine/host_sets.hpp"       // igd_hip_search_sets: chunks of sets, small ones sliced, large ones through the batch pipeline
 #include "engine/host_support.hpp"    // igd_hip_support_sets: chunks of sets, all of them sliced
 #include "engine/host_coverage.hpp"   // igd_hip_coverage_sets: chunks of sets, all of them sliced

@@ -3,7 +3,7 @@ per workgroup.  A plain module: no pytest hooks.  tests/test_sets_fixtures.py ch
 tests/test_gpu_sets_scale.py and tests/test_gpu_coverage_scale.py use it on one.
 
     consts()         the constants of the work decomposition, read out of the sources
-    plan()           the host's chunk and slice arithmetic (host_sets.hpp, host_support.hpp, host_coverage.hpp), restated:
+    plan()           the host's chunk and slice arithmetic (run_set_chunks, host_common.hpp, and its three callers), restated:
                      every test asserts through it that its fixture is in the regime it claims
     wide_db()        a database of many files whose boundary files (bit 0 and bit 31 of the first, 64th, 65th and last
                      bitmap word) lie inside a window that a known share of the queries covers
@@ -64,10 +64,11 @@ def _clamp(x, lo, hi):
     return lo if x < lo else hi if x > hi else x
 
 
-def plan(set_sizes, nfiles, big_min=None, max_batch=None):
+def plan(set_sizes, nfiles, big_min=None, max_batch=None, row_bytes=None):
     """What igd_hip_search_sets ("search"), igd_hip_support_sets ("support") and igd_hip_coverage_sets ("coverage") make of
     these sets: sliceLen, and per chunk its first set, rows, queries, slices, sets on the batch pipeline (search only) and the
-    grid of the slice kernel."""
+    grid of the slice kernel.  big_min, max_batch, row_bytes: what IGD_SETS_BIG_MIN, IGD_HIP_MAX_BATCH and
+    IGD_HIP_SETS_ROW_BYTES are set to (None: the engine's defaults)."""
     c = consts()
     big_min = c["IGD_SETS_BIG_MIN_DEFAULT"] if big_min is None else big_min
     step = c["IGD_HIP_MAX_BATCH_DEFAULT"] if max_batch is None else max_batch
@@ -75,7 +76,7 @@ def plan(set_sizes, nfiles, big_min=None, max_batch=None):
     off = [0]
     for n in sizes:
         off.append(off[-1] + n)
-    row_cap = max(c["IGD_SETS_ROW_BYTES"] // (nfiles * 8), 1)
+    row_cap = max((c["IGD_SETS_ROW_BYTES"] if row_bytes is None else row_bytes) // (nfiles * 8), 1)
     waves = c["IGD_SETS_WG"] // c["IGD_WAVE"]
     nw = (nfiles + 31) // 32
 
