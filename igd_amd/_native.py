@@ -204,6 +204,15 @@ def hip():
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # nearest record per dataset: db, ichr, qs, qe, nq, window, v, dist, dmin / ..., set_off, nsets, window, v, n_within,
+        # n_overlap, sum_dist / device pointers, ..., d_dist, d_dmin, stream
+        L.igd_hip_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.igd_hip_nearest_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_nearest_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+        L.igd_hip_nearest_grid.argtypes = [C.c_int64]
+        L.igd_hip_nearest_grid.restype = C.c_int32
         L.igd_hip_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_search_runs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -327,6 +336,13 @@ def _bind_core(L):
     L.igdc_permute_host_ov.argtypes = L.igdc_permute_host.argtypes + [C.c_void_p]
     # observed, sum, sumsq, n_ge, n_le, nperm, n, mean, sd, z, nlog10_p_upper, nlog10_p_lower
     L.igdc_perm_summary.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int64] + [C.c_void_p] * 5
+    # nearest record per dataset on the host: db, map, ichr, qs, qe, nq, window, v, dist, dmin / ..., set_off, nsets, window, v,
+    # n_within, n_overlap, sum_dist / n_within, sum_dist, n, mean
+    L.igdc_nearest_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_void_p]
+    L.igdc_nearest_sets_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.igdc_nearest_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     # db, path, len (int32[nCtg]), bad_line
     L.igdc_read_genome.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L

@@ -1,0 +1,179 @@
+// engine/host_nearest.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
+// igd_hip_nearest / igd_hip_nearest_dev / igd_hip_nearest_sets: the nearest record per dataset within a window (nearest_dev.hpp)
+// ------------------------------------------------------------------------------------------
+// The device form takes one engine batch of resident regions and writes resident rows: one launch (the wide form: a fill of
+// the rows with 0xff before it and, when dmin is wanted, igd_nearest_rowmin behind it), asynchronous on the caller's stream.
+// The host form takes host arrays in CHUNKS of at most igd_hip_max_batch() regions AND at most IGD_NEAREST_ROW_BYTES of device
+// rows (4 nFiles bytes per region: 7.6 KB at 1 900 files, 35 000 regions per chunk); per chunk the regions go to the device
+// through the staging buffers of igd_hip_search, the device form runs on the engine's stream and the rows come back into the
+// caller's arrays at their place.
+// The sets form takes GROUPS of whole sets whose three result rows (3 x (nFiles + 1) x 8 bytes per set) fit sets_row_bytes();
+// the regions of a group go through in the same chunks -- a set may be cut by a chunk, its statistics are sums over regions --
+// and per chunk igd_nearest_reduce adds the rows into the group's three resident matrices, by a slice table cut here: a slice
+// is at most IGD_NEAREST_SLICE regions of one set.  The rows never leave the device; the matrices are copied out once per group.
+// The image is slice_image(db, IGD_HIP_RULE_FLAT, v): the re-tiled copy when there is one, visited under rule FLAT.
+#define IGD_NEAREST_ROW_BYTES ((int64_t)256 << 20)   // device rows of one chunk (of the order of IGD_MEMBER_ROW_BYTES)
+#define IGD_NEAREST_SLICE 256                        // regions per slice of igd_nearest_reduce: 64 per wave
+#define IGD_NEAREST_REDUCE_WGS 16384                 // igd_nearest_reduce: about this many workgroups per launch (64 per CU)
+
+// The TEST-ONLY variable IGD_HIP_NEAREST_ROW_BYTES (read once per process, as IGD_HIP_MAX_BATCH) lowers the budget so that
+// small fixtures cross the row seam.
+static int64_t nearest_row_bytes(void)
+{
+    static const int64_t m = env_positive("IGD_HIP_NEAREST_ROW_BYTES", IGD_NEAREST_ROW_BYTES);
+    return m;
+}
+
+// workgroups igd_nearest_rows is launched with for nq regions (each of IGD_SETS_WG / IGD_WAVE waves; a wave meets a second
+// region only when nq exceeds the grid's waves)
+extern "C" int32_t igd_hip_nearest_grid(int64_t nq) { return items_grid(nq, IGD_SETS_WG / IGD_WAVE); }
+
+// regions per chunk of the host forms
+static int64_t nearest_step(int64_t nF)
+{
+    const int64_t byRows = nearest_row_bytes() / ((nF > 0 ? nF : 1) * 4);
+    const int64_t step = max_batch();
+    return byRows < step ? (byRows < 1 ? 1 : byRows) : step;
+}
+
+static int nearest_window_bad(const char *who, int32_t window)
+{
+    if (igd_hip_nearest_window_valid(window)) return 0;
+    snprintf(g_err, sizeof g_err, "%s: window %d outside 0 .. %d", who, (int)window, (int)IGD_HIP_NEAREST_MAX_WINDOW);
+    return 1;
+}
+
+extern "C" int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq,
+                                   int32_t window, int32_t v, int32_t *d_dist, int32_t *d_dmin, void *stream)
+{
+    if (nearest_window_bad("igd_hip_nearest_dev", window)) return IGD_HIP_ERR_ARG;
+    if (!db || nq < 0 || nq > max_batch() || (nq > 0 && (!d_ichr || !d_qs || !d_qe || (!d_dist && db->nFiles > 0)))) {
+        snprintf(g_err, sizeof g_err, "igd_hip_nearest_dev: bad argument (batch limit %lld regions)", (long long)max_batch());
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nq == 0) return IGD_HIP_OK;
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = stream ? (hipStream_t)stream : db->stream;
+    const int64_t nF = db->nFiles;
+    if (nF == 0) {                                       // rows of no words; no region has a dataset near it
+        if (d_dmin) HIPCHK(hipMemsetAsync(d_dmin, 0xff, (size_t)nq * 4, st));
+        return IGD_HIP_OK;
+    }
+    const SliceImage im = slice_image(db, IGD_HIP_RULE_FLAT, v);
+    const bool lds = nF <= IGD_NEAREST_LDS_FILES;
+    const int grid = igd_hip_nearest_grid(nq);
+    const size_t ldsB = lds ? (size_t)((IGD_SETS_WG / IGD_WAVE) * nF) * 4 : 0;
+    const int n = (int)nq;
+    if (!lds) HIPCHK(hipMemsetAsync(d_dist, 0xff, (size_t)(nq * nF) * 4, st));       // the wide form minimises into rows of "none"
+    with_flags(im.useV, lds, [&](auto V, auto L) {
+        igd_nearest_rows<V(), L()><<<grid, IGD_SETS_WG, ldsB, st>>>(im.view, d_ichr, d_qs, d_qe, n, window, im.krule, v, d_dist, d_dmin);
+    });
+    HIPCHK(hipGetLastError());
+    if (!lds && d_dmin) {
+        igd_nearest_rowmin<<<grid, IGD_SETS_WG, 0, st>>>(d_dist, n, (int)nF, d_dmin);
+        HIPCHK(hipGetLastError());
+    }
+    return IGD_HIP_OK;
+}
+
+// the rows and dmin[] of one chunk of regions
+static int ensure_nearest_ws(igd_hip_db *db, int64_t words, int64_t rows)
+{
+    int rc = dev_grow(db, &db->d_nrDist, &db->nrDistCap, words);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrMin, &db->nrMinCap, rows);
+    return rc;
+}
+
+extern "C" int igd_hip_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window,
+                               int32_t v, int32_t *dist, int32_t *dmin)
+{
+    if (nearest_window_bad("igd_hip_nearest", window)) return IGD_HIP_ERR_ARG;
+    if (!db || nq < 0 || (nq > 0 && (!ichr || !qs || !qe || (!dist && db->nFiles > 0)))) {
+        snprintf(g_err, sizeof g_err, "igd_hip_nearest: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nq == 0) return IGD_HIP_OK;
+    const int64_t nF = db->nFiles;
+    if (nF == 0) {
+        if (dmin) memset(dmin, 0xff, (size_t)nq * 4);
+        return IGD_HIP_OK;
+    }
+    const int64_t step = nearest_step(nF);
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    for (int64_t c0 = 0; c0 < nq; c0 += step) {
+        const int64_t m = nq - c0 < step ? nq - c0 : step;
+        int rc = ensure_nearest_ws(db, m * nF, m);
+        if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
+        if (rc == IGD_HIP_OK) rc = igd_hip_nearest_dev(db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, dmin ? db->d_nrMin : nullptr, st);
+        if (rc != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemcpyAsync(dist + c0 * nF, db->d_nrDist, (size_t)(m * nF) * 4, hipMemcpyDeviceToHost, st));
+        if (dmin) HIPCHK(hipMemcpyAsync(dmin + c0, db->d_nrMin, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+    }
+    return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_nearest_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                                    int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    if (nearest_window_bad("igd_hip_nearest_sets", window)) return IGD_HIP_ERR_ARG;
+    if (!db || nsets < 0 || (nsets > 0 && !set_off)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_nearest_sets: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nsets == 0) return IGD_HIP_OK;
+    int rc = sets_check("igd_hip_nearest_sets", ichr, qs, qe, set_off, nsets);
+    if (rc != IGD_HIP_OK) return rc;
+    const int64_t nF = db->nFiles, nC = nF + 1;
+    int64_t *outs[3] = {n_within, n_overlap, sum_dist};
+    if (set_off[nsets] == 0 || nF == 0) {                // every statistic is 0: no region, or no dataset to be near
+        for (int64_t *o : outs) if (o) memset(o, 0, (size_t)nsets * (size_t)nC * 8);
+        return IGD_HIP_OK;
+    }
+    const int64_t step = nearest_step(nF);
+    const int64_t rowCap = sets_row_bytes() / (3 * nC * 8) > 0 ? sets_row_bytes() / (3 * nC * 8) : 1;
+    const int gx = (int)((nC + IGD_WAVE - 1) / IGD_WAVE);
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    std::vector<SetSlice> slices;
+    for (int32_t k0 = 0; k0 < nsets;) {
+        // one group: sets [k0, k1), regions [set_off[k0], set_off[k1])
+        const int32_t k1 = (int32_t)(nsets - k0 < rowCap ? nsets : k0 + rowCap);
+        const int64_t rows = k1 - k0, matWords = rows * nC;
+        if ((rc = dev_grow(db, &db->d_nrStat, &db->nrStatCap, 3 * matWords)) != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemsetAsync(db->d_nrStat, 0, (size_t)(3 * matWords) * 8, st));
+        int32_t k = k0;
+        for (int64_t c0 = set_off[k0]; c0 < set_off[k1]; c0 += step) {
+            const int64_t m = set_off[k1] - c0 < step ? set_off[k1] - c0 : step;
+            // the chunk's part of every set it meets, in slices of at most IGD_NEAREST_SLICE regions
+            slices.clear();
+            while (set_off[k + 1] <= c0) k++;
+            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++) {
+                const int64_t a0 = set_off[j] > c0 ? set_off[j] : c0, b0 = set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m;
+                for (int64_t a = a0; a < b0; a += IGD_NEAREST_SLICE)
+                    slices.push_back(SetSlice{j - k0, (int32_t)(a - c0), (int32_t)((a + IGD_NEAREST_SLICE < b0 ? a + IGD_NEAREST_SLICE : b0) - c0), 0});
+            }
+            const int ns = (int)slices.size();
+            rc = ensure_nearest_ws(db, m * nF, m);
+            if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
+            if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
+            if (rc == IGD_HIP_OK) rc = igd_hip_nearest_dev(db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
+            if (rc != IGD_HIP_OK) return rc;
+            HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+            int gy = IGD_NEAREST_REDUCE_WGS / gx;
+            gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
+            igd_nearest_reduce<<<dim3((unsigned)gx, (unsigned)gy), IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns,
+                                                                                      (u64 *)db->d_nrStat, matWords);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
+        }
+        for (int i = 0; i < 3; i++)
+            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * nC, db->d_nrStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        k0 = k1;
+    }
+    return IGD_HIP_OK;
+}

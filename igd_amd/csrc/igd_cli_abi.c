@@ -1469,6 +1469,81 @@ done:
     free(len);
 }
 
+/* ------------------------------- `igd search -q F -N <bp>` / `-Q <list> -N <bp>` ------- */
+/* Nearest record per dataset within a window (include/igd_hip.h has the definitions): per database file the query regions
+ * with a record of the file within W bp (n_within), those that overlap one (n_overlap) and the mean distance of the former
+ * (mean_dist, `NA` where there is none); one line per dataset, then the same for "any dataset".  -v keeps the records with
+ * value >= v, as everywhere; there is no tile rule.  Routing as `-u`: at most igdc_host_limit() regions in all are answered on
+ * the host (igdc_nearest_sets_host), more by ONE igd_hip_nearest_sets call on one device.  `paths` holds one query file (`-q`,
+ * no "Query set" lines) or the files of a list (`-Q`). */
+static void print_mean(const char *before, int64_t n_within, double mean, const char *after)
+{
+    if (n_within > 0) printf("%s%.2f%s", before, mean, after);
+    else printf("%sNA%s", before, after);
+}
+
+static void nearest_files(char **paths, int32_t n, int32_t v, int setLines, int32_t window)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles;
+    const size_t nC = (size_t)nfiles + 1;
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    int64_t *st3 = (int64_t *)calloc(3 * (size_t)(n ? n : 1) * nC, sizeof(int64_t));
+    double *mean = (double *)malloc(sizeof(double) * (size_t)(n ? n : 1) * nC);
+    int64_t *nw = st3, *no = st3 + (size_t)n * nC, *sd = st3 + 2 * (size_t)n * nC;
+    off[0] = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (q[k].n) {
+            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+        }
+        off[k + 1] = off[k] + q[k].n;
+    }
+    int onHost = 0;
+    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
+    if (hm) {
+        double t0 = now_s();
+        onHost = igdc_nearest_sets_host(g_core, hm, ichr, qs, qe, off, n, window, ev, nw, no, sd) == 0;
+        igdc_map_close(hm);
+        if (onHost) phase("nearest records on the host (small files)", &t0);
+    }
+    if (!onHost && nq > 0) {                          /* (after a read error too: the engine reads the file its own way) */
+        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
+        double t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_nearest_sets(dev, ichr, qs, qe, off, n, window, ev, nw, no, sd);
+            if (rc != IGD_HIP_OK) engine_failed("nearest", rc);
+            phase("nearest records of the query sets (H2D + kernels + D2H)", &t0);
+        }
+    }
+    if (!g_fail_rc) igdc_nearest_summary(nw, sd, (int64_t)n * (int64_t)nC, mean);
+    for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
+        const size_t o = (size_t)k * nC;
+        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        printf("index\tn_within\tn_overlap\tmean_dist\tFile\n");
+        for (int32_t i = 0; i < nfiles; i++) {
+            printf("%d\t%lld\t%lld", (int)i, (long long)nw[o + i], (long long)no[o + i]);
+            print_mean("\t", nw[o + i], mean[o + i], "\t");
+            printf("%s\n", IGD->finfo[i].fileName);
+        }
+        printf("Regions with a dataset within %d bp: %lld of %lld; overlapping: %lld", (int)window, (long long)nw[o + nfiles], (long long)q[k].n,
+               (long long)no[o + nfiles]);
+        print_mean("; mean distance ", nw[o + nfiles], mean[o + nfiles], "\n");
+    }
+    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    free(q); free(ichr); free(qs); free(qe); free(off); free(st3); free(mean);
+}
+
 /* ------------------------------- `igd search` ----------------------------------------- */
 static int usage_search(void)
 {
@@ -1501,6 +1576,8 @@ static int usage_search(void)
             "    -O <bp>  -A <F>  -B <F>    minimum overlap of a counted (query region, record) pair: at least <bp> base pairs,\n"
             "                               the fraction F of the query region (-A), of the record (-B); F is a decimal in [0, 1]\n"
             "                               with at most six places.  With -q or -Q alone, -u, -U [-R] and -P\n"
+            "    -N <bp>                    with -q or -Q: per dataset, the query regions with a record within <bp> base pairs (0 to\n"
+            "                               1073741824), those that overlap one, and the mean distance to the nearest record\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -1547,6 +1624,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, restricted = 0, cooc = 0, other = 0, minov = 0;      /* other: -m, -s or -r was given (-U refuses them) */
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
     char *permArg = NULL, *genomeName = NULL, *seedArg = NULL, *pmodeArg = NULL;      /* -P, -g, -S, -M (see permute_file) */
+    char *nearArg = NULL;                                                             /* -N (see nearest_files) */
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
         const char *a = argv[i];
@@ -1589,6 +1667,10 @@ int igd_search(int argc, char **argv)                                        /* 
         } else if (strcmp(a, "-P") == 0) {            /* (not the reference's: permutation null of the support, see permute_file) */
             if (i + 1 >= argc) { printf("No number of permutations.\n"); return EX_OK; }
             permArg = argv[i + 1];
+        } else if (strcmp(a, "-N") == 0) {            /* (not the reference's: nearest record per dataset within a window, see nearest_files) */
+            if (i + 1 >= argc) { printf("No window.\n"); return EX_OK; }
+            nearArg = argv[i + 1];
+            i++;                                      /* (the window is not an option: "-N -5" is a refused window) */
         } else if (strcmp(a, "-g") == 0) {
             if (i + 1 >= argc) { printf("No genome file.\n"); return EX_OK; }
             genomeName = argv[i + 1];
@@ -1619,6 +1701,22 @@ int igd_search(int argc, char **argv)                                        /* 
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    if (nearArg) {
+        char *end = NULL;
+        const long long w = strtoll(nearArg, &end, 10);
+        if (uniq || bp || memb || uniName || ranks || restricted || cooc || permArg || full || other || minov) {
+            printf("Not supported: -N together with -u, -b, -w, -U, -R, -X, -C, -P, -f, -m, -s, -r, -O, -A or -B\n");
+            return EX_OK;
+        }
+        if (mode != 1 && !listName) {
+            printf("Not supported: -N without -q or -Q\n");
+            return EX_OK;
+        }
+        if (end == nearArg || *end || w < 0 || w > (long long)IGD_HIP_NEAREST_MAX_WINDOW) {
+            printf("Not supported: -N %s (a window of 0 to %lld base pairs)\n", nearArg, (long long)IGD_HIP_NEAREST_MAX_WINDOW);
+            return EX_OK;
+        }
+    }
     if (minov && (bp || memb || restricted || cooc || full || other || (mode != 1 && !listName))) {
         printf("Not supported: -O, -A or -B together with -b, -w, -X, -C, -f, -m, -s or -r, or without -q or -Q\n");
         return EX_USAGE;
@@ -1628,6 +1726,14 @@ int igd_search(int argc, char **argv)                                        /* 
     if (!permArg && (genomeName || seedArg || pmodeArg)) {
         printf("Not supported: -g, -S or -M without -P\n");
         return EX_OK;
+    } else if (nearArg && mode == 1) {
+        nearest_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10));
+    } else if (nearArg) {
+        int32_t n = 0;
+        char **paths = read_list(listName, &n);
+        if (n >= 0) nearest_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10));
+        for (int32_t k = 0; k < n; k++) free(paths[k]);
+        free(paths);
     } else if (permArg && (listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)) {
         printf("Not supported: -P together with -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r\n");
         return EX_OK;

@@ -198,6 +198,19 @@ int igdc_permute_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
  * Every output may be NULL.  Needs no database.  0, or -1 for a missing input or nperm < 1. */
 int igdc_perm_summary(const int64_t *observed, const int64_t *sum, const int64_t *sumsq, const int64_t *n_ge, const int64_t *n_le,
                       int64_t nperm, int64_t n, double *mean, double *sd, double *z, double *nlog10_p_upper, double *nlog10_p_lower);
+/* Nearest record per dataset within a window (what igd_hip_nearest and igd_hip_nearest_sets compute; include/igd_hip.h has the
+ * definitions): dist (int32[nq * nFiles]) and dmin (int32[nq], may be NULL); n_within, n_overlap, sum_dist (int64[nsets *
+ * (nFiles + 1)], each may be NULL; column nFiles from dmin).  Every output is OVERWRITTEN, every word of it.  Each region is
+ * widened by the window, visits its tiles under rule FLAT with the prefix skip and keeps one minimum per file; threads run
+ * over the regions.  0 on success; -1 for a missing array, a bad set_off or a window outside 0 .. 2^30 (nothing written), or
+ * when a tile could not be read (outputs undefined). */
+int igdc_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                      int32_t window, int32_t v, int32_t *dist, int32_t *dmin);
+int igdc_nearest_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                           const int64_t *set_off, int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
+                           int64_t *sum_dist);
+/* mean[i] = sum_dist[i] / n_within[i] as a double, NaN where n_within[i] = 0.  Needs no database.  0, or -1 for a missing array. */
+int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t n, double *mean);
 /* A genome file, lines `name<TAB>length`: len[c] = the length of contig c of the database (int32[nCtg]); lines of contigs the
  * database does not know are ignored, contigs the file does not name get 0.  0; -1 when the file cannot be opened; -2 for a
  * line of a known contig without a length or with one that is negative or above 2^31 - 1 (*bad_line, may be NULL, = its

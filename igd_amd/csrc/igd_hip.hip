@@ -329,6 +329,12 @@ struct igd_hip_db {
     int32_t *d_pmReg;
     long long *d_pmStat;
     int64_t pmRegCap, pmStatCap;
+    // igd_hip_nearest / igd_hip_nearest_sets (host_nearest.hpp): the distance rows and dmin[] of one chunk of regions, the three
+    // matrices of one group of sets (64-bit words) and the slice table of igd_nearest_reduce
+    int32_t *d_nrDist, *d_nrMin;
+    int64_t *d_nrStat;
+    struct SetSlice *d_nrSlices;
+    int64_t nrDistCap, nrMinCap, nrStatCap, nrSliceCap;
     hipStream_t stream;
     // profiling
     std::vector<hipEvent_t> ev;   // 4 per launch: pipeline start, scan start, scan stop, pipeline stop
@@ -363,6 +369,7 @@ struct igd_hip_db {
 #include "engine/restrict_dev.hpp"    // igd_restrict_bits, igd_bits_support: sets restricted to a universe -- the interval join and the gather over member rows
 #include "engine/cooccur_dev.hpp"     // igd_bits_transpose, igd_bitrows_gram: bit rows into bit columns, popcount Gram product -- dataset co-occurrence
 #include "engine/permute_dev.hpp"     // igd_permute_regions, igd_perm_stats: shifted / shuffled region sets, column statistics of a row matrix -- permutation null
+#include "engine/nearest_dev.hpp"     // igd_nearest_rows, igd_nearest_reduce: the same walk over a widened interval, one distance row per region -- nearest record per dataset
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -379,6 +386,7 @@ struct igd_hip_db {
 #include "engine/host_restrict.hpp"   // igd_hip_restrict_sets / igd_hip_enrich_restricted: chunks of sets x chunks of the universe
 #include "engine/host_cooccur.hpp"    // igd_hip_cooccur / igd_hip_bits_transpose / igd_hip_bitrows_gram: chunks of regions, rows stay resident
 #include "engine/host_permute.hpp"    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: chunks of permutations, rows stay resident
+#include "engine/host_nearest.hpp"    // igd_hip_nearest / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

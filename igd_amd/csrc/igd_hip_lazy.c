@@ -204,6 +204,23 @@ int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t 
     return fn ? fn(db, d_ichr, d_qs, d_qe, nq, v, rule, d_bits, d_nfiles_hit, d_nhit, stream) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window, int32_t v,
+                    int32_t *dist, int32_t *dmin)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, int32_t, int32_t, int32_t *, int32_t *);
+    RESOLVE(fn_t, "igd_hip_nearest");
+    return fn ? fn(db, ichr, qs, qe, nq, window, v, dist, dmin) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_nearest_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                         int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int32_t, int32_t,
+                        int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_nearest_sets");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, window, v, n_within, n_overlap, sum_dist) : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
                              int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, int32_t v, int rule,
                              int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio, int64_t *clamped, int64_t *nhit,

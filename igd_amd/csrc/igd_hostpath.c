@@ -1124,6 +1124,144 @@ int igdc_perm_summary(const int64_t *observed, const int64_t *sum, const int64_t
     return 0;
 }
 
+/* ---- nearest record per dataset within a window (include/igd_hip.h has the definitions) ----------------------------------
+ * One region: its row is set to -1, the interval is widened by the window (igd_hip_nearest_widen), the tiles of the widened
+ * interval are visited as one_query visits them under rule FLAT -- bisection for the last start < we, backwards while
+ * end > ws, in later tiles only down to the tile's start (the prefix skip) -- and every counted record lowers row[idx] to
+ * its d, computed from the region as given (igd_hip_nearest_dist).  Returns the minimum over the files, or -1. */
+static inline int32_t one_region_nearest(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                         int32_t window, int32_t v, int use_v, int32_t *row)
+{
+    const int32_t nf = db->nFiles;
+    for (int32_t f = 0; f < nf; f++) row[f] = -1;
+    if (ichr < 0 || ichr >= db->nCtg) return -1;
+    int32_t ws, we;
+    igd_hip_nearest_widen(qs, qe, window, &ws, &we);
+    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
+    const int32_t n1 = ws / nbp;
+    int32_t n2 = (int32_t)((uint32_t)we - 1u) / nbp;
+    if (n1 < 0 || n1 > mT) return -1;                                      /* (no record ends behind the contig's last tile) */
+    if (n2 > mT) n2 = mT;
+    const int w = db->gType == 0 ? 3 : 4;
+    int64_t best = -1;
+    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
+        const int32_t cnt = db->nCnt[ichr][j];
+        if (cnt <= 0) continue;
+        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
+        if (!rec) return -1;
+        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
+        for (int32_t i = below(rec, w, cnt, we) - 1; i >= 0; i--) {
+            const int32_t *r = rec + (size_t)i * (size_t)w;
+            if ((int64_t)r[1] < lob) break;
+            if (r[2] > ws && (!use_v || r[3] >= v)) {
+                if (r[0] < 0 || r[0] >= nf) continue;
+                const int64_t d = igd_hip_nearest_dist(qs, qe, r[1], r[2]);
+                if (row[r[0]] < 0 || d < row[r[0]]) row[r[0]] = (int32_t)d;
+                if (best < 0 || d < best) best = d;
+            }
+        }
+    }
+    return (int32_t)best;
+}
+
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe;
+    int64_t lo, hi;
+    int32_t window, v; int use_v;
+    int32_t *dist, *dmin;
+    int io_failed;
+} nearest_job;
+
+static void *nearest_run(void *arg)
+{
+    nearest_job *J = (nearest_job *)arg;
+    tilebuf tb;
+    memset(&tb, 0, sizeof tb);
+    tb.ichr = -1;
+    const size_t nf = (size_t)J->db->nFiles;
+    for (int64_t i = J->lo; i < J->hi; i++) {
+        const int32_t d = one_region_nearest(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->window, J->v, J->use_v, J->dist + (size_t)i * nf);
+        if (J->dmin) J->dmin[i] = d;
+    }
+    J->io_failed = tb.failed;
+    free(tb.buf);
+    return NULL;
+}
+
+int igdc_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                      int32_t window, int32_t v, int32_t *dist, int32_t *dmin)
+{
+    if (!db || !m || nq < 0 || !igd_hip_nearest_window_valid(window) || (nq > 0 && (!ichr || !qs || !qe || (!dist && db->nFiles > 0)))) return -1;
+    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+    const int T = host_threads(nq);
+    nearest_job job[64];
+    pthread_t th[64];
+    int started[64];
+    int32_t none = 0;                        /* (a database without files: rows of no words) */
+    /* rows are disjoint per region: every thread writes its regions' rows straight into the caller's */
+    for (int k = 0; k < T; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
+        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
+        job[k].window = window; job[k].v = v; job[k].use_v = use_v;
+        job[k].dist = dist ? dist : &none; job[k].dmin = dmin;
+    }
+    for (int k = 1; k < T; k++) {
+        started[k] = pthread_create(&th[k], NULL, nearest_run, &job[k]) == 0;
+        if (!started[k]) nearest_run(&job[k]);
+    }
+    nearest_run(&job[0]);
+    for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
+    int bad = 0;
+    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
+    return bad ? -1 : 0;
+}
+
+#define NEAREST_HOST_ROW_BYTES ((int64_t)32 << 20)   /* igdc_nearest_sets_host: distance rows of one chunk of regions */
+int igdc_nearest_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                           const int64_t *set_off, int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
+                           int64_t *sum_dist)
+{
+    if (!db || !m || nsets < 0 || !igd_hip_nearest_window_valid(window) || (nsets > 0 && (!set_off || set_off[0] != 0))) return -1;
+    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
+    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) return -1;
+    const int64_t nf = db->nFiles, nC = nf + 1, nq = nsets > 0 ? set_off[nsets] : 0;
+    int64_t chunk = NEAREST_HOST_ROW_BYTES / (4 * (nf > 0 ? nf : 1));
+    chunk = chunk < 1 ? 1 : chunk > nq ? nq : chunk;
+    int32_t *dist = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk * nf + 1)), *dmin = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk + 1));
+    if (!dist || !dmin) { free(dist); free(dmin); return -1; }
+    int64_t *outs[3] = {n_within, n_overlap, sum_dist};
+    for (int i = 0; i < 3; i++) if (outs[i]) memset(outs[i], 0, sizeof(int64_t) * (size_t)nsets * (size_t)nC);
+    int rc = 0;
+    int32_t k = 0;
+    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += chunk) {
+        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
+        rc = igdc_nearest_host(db, m, ichr + c0, qs + c0, qe + c0, n, window, v, dist, dmin);
+        for (int64_t i = 0; i < n && rc == 0; i++) {
+            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
+            const int32_t *row = dist + (size_t)i * (size_t)nf;
+            const size_t o = (size_t)k * (size_t)nC;
+            for (int64_t f = 0; f < nC; f++) {
+                const int32_t d = f < nf ? row[f] : dmin[i];
+                if (d < 0) continue;
+                if (n_within) n_within[o + f]++;
+                if (n_overlap && d == 0) n_overlap[o + f]++;
+                if (sum_dist) sum_dist[o + f] += d;
+            }
+        }
+    }
+    free(dist); free(dmin);
+    return rc;
+}
+
+int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t n, double *mean)
+{
+    if (n < 0 || (n > 0 && (!n_within || !sum_dist || !mean))) return -1;
+    for (int64_t i = 0; i < n; i++) mean[i] = n_within[i] > 0 ? (double)sum_dist[i] / (double)n_within[i] : __builtin_nan("");
+    return 0;
+}
+
 /* The handle flavours' batches (Python search_n / search_1, R search_nr / getOverlaps): on the host while the batch is
  * small and no engine is resident, otherwise on the engine, which is attached at the first batch that needs it -- the
  * moment the reference would do its first fseek/fread (src/igd_search.c:469-476); open_iGD reads the header only, like

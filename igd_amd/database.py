@@ -32,6 +32,8 @@ EnrichmentRanks = collections.namedtuple("EnrichmentRanks", "qvalue_log rnk_sup 
 PermutationSupport = collections.namedtuple("PermutationSupport", "observed sum sumsq n_ge n_le min max nperm")
 PermutationSummary = collections.namedtuple("PermutationSummary", "mean sd z nlog10_p_upper nlog10_p_lower")
 PERM_MODES = {"circular": 0, "shuffle": 1}           # IGD_HIP_PERM_CIRCULAR, IGD_HIP_PERM_SHUFFLE
+NearestSets = collections.namedtuple("NearestSets", "n_within n_overlap sum_dist window")
+NEAREST_MAX_WINDOW = 1 << 30                         # IGD_HIP_NEAREST_MAX_WINDOW
 
 
 class MinOverlap(C.Structure):
@@ -438,6 +440,61 @@ def perm_summary(ps):
     if N.cli().igdc_perm_summary(*[_ptr(x) for x in a], int(ps.nperm), n, *[_ptr(x) for x in out]) != 0:
         raise IgdError("perm_summary: bad argument")
     return PermutationSummary(*out)
+
+
+def _window(window, what):
+    w = int(window)
+    if not -2 ** 31 <= w < 2 ** 31:                      # (inside int32 the native call decides: 0 .. 2^30)
+        raise IgdError("%s: window %d outside 0 .. %d" % (what, w, NEAREST_MAX_WINDOW))
+    return w
+
+
+def _value_filter(value_filter):
+    return N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+
+
+def nearest_host(igd_path, ichr, qs, qe, window, value_filter=None):
+    """Database.nearest() on the host (igdc_nearest_host: pread on the .igd, threads over the regions; no device is touched):
+    (dist int32[nq, nfiles], dmin int32[nq])."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    if len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("nearest_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    with _HostDb(igd_path, "nearest_host") as h:
+        dist, dmin = np.empty((len(qs), h.nfiles), np.int32), np.empty(len(qs), np.int32)
+        if h.L.igdc_nearest_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _window(window, "nearest_host"),
+                                 _value_filter(value_filter), _ptr(dist), _ptr(dmin)) != 0:
+            raise IgdError("nearest_host: a window outside 0 .. %d, or a tile of %s could not be read" % (NEAREST_MAX_WINDOW, igd_path))
+        return dist, dmin
+
+
+def nearest_sets_host(igd_path, ichr, qs, qe, set_off, window, value_filter=None):
+    """Database.nearest_sets() on the host (igdc_nearest_sets_host; no device is touched): a NearestSets."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+    nsets = len(set_off) - 1
+    if nsets < 0:
+        raise IgdError("nearest_sets_host: set_off needs nsets + 1 entries")
+    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("nearest_sets_host: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
+    with _HostDb(igd_path, "nearest_sets_host") as h:
+        out = [np.empty((nsets, h.nfiles + 1), np.int64) for _ in range(3)]
+        if h.L.igdc_nearest_sets_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets,
+                                      _window(window, "nearest_sets_host"), _value_filter(value_filter), *[_ptr(a) for a in out]) != 0:
+            raise IgdError("nearest_sets_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
+                           % (NEAREST_MAX_WINDOW, igd_path))
+        return NearestSets(*out, int(window))
+
+
+def nearest_summary(ns):
+    """mean distance = sum_dist / n_within of a NearestSets as float64[nsets, nfiles + 1], NaN where n_within is 0
+    (igdc_nearest_summary)."""
+    nw, sd = (np.ascontiguousarray(x, dtype=np.int64) for x in (ns.n_within, ns.sum_dist))
+    if nw.shape != sd.shape:
+        raise IgdError("nearest_summary: arrays of different shapes")
+    mean = np.empty(nw.shape, np.float64)
+    if N.cli().igdc_nearest_summary(_ptr(nw), _ptr(sd), nw.size, _ptr(mean)) != 0:
+        raise IgdError("nearest_summary: bad argument")
+    return mean
 
 
 class Database:
@@ -976,6 +1033,58 @@ class Database:
         bits, nfh, _ = self.membership(cat[0], cat[1], cat[2], v)
         any_hit = np.concatenate([[0], np.cumsum(nfh > 0)]).astype(np.int64)
         return bits, nfh, any_hit[set_off[1:]] - any_hit[set_off[:-1]], set_off
+
+    # ---- nearest record per dataset within a window ---------------------------------------
+    def nearest(self, ichr, qs, qe, window, value_filter=None, dist=None):
+        """How far each region lies from the nearest record of every dataset within `window` bp (igd_hip_nearest; the
+        definitions are in include/igd_hip.h): (dist int32[nq, nfiles], dmin int32[nq]).  dist[q, f] is 0 where region q
+        overlaps a record of file f, the gap + 1 otherwise (book-ended intervals are 1 bp apart), -1 where file f has no record
+        within the window; dmin[q] is the smallest of the row's distances, or -1.  value_filter: only records with value >=
+        it count (the nearest passing record).  There is no tile rule.  dist (int32[nq, nfiles], C order), when given, is
+        overwritten: every word is defined by the call."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        if len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("nearest: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+        nq = len(qs)
+        if dist is None:
+            dist = np.empty((nq, self.nfiles), np.int32)
+        elif dist.dtype != np.int32 or dist.shape != (nq, self.nfiles) or not dist.flags.c_contiguous:
+            raise IgdError("nearest: dist must be a C-ordered int32[%d, %d]" % (nq, self.nfiles))
+        dmin = np.empty(nq, np.int32)
+        _chk(self._H.igd_hip_nearest(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, _window(window, "nearest"), _value_filter(value_filter),
+                                     _ptr(dist), _ptr(dmin)), "igd_hip_nearest")
+        return dist, dmin
+
+    def nearest_sets(self, ichr, qs, qe, set_off, window, value_filter=None):
+        """The distances of nearest() summed up per region set (igd_hip_nearest_sets; sets as search_sets()): a NearestSets of
+        three int64[nsets, nfiles + 1] -- n_within (the regions of the set with a record of the file within the window),
+        n_overlap (those that overlap one: the support under rule FLAT) and sum_dist (the sum of the former's distances) --
+        whose last column is the any-dataset column, built from dmin.  The distance rows never leave the device."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+        nsets = len(set_off) - 1
+        if nsets < 0:
+            raise IgdError("nearest_sets: set_off needs nsets + 1 entries")
+        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("nearest_sets: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
+        out = [np.empty((nsets, self.nfiles + 1), np.int64) for _ in range(3)]
+        _chk(self._H.igd_hip_nearest_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, _window(window, "nearest_sets"),
+                                          _value_filter(value_filter), *[_ptr(a) for a in out]), "igd_hip_nearest_sets")
+        return NearestSets(*out, int(window))
+
+    def nearest_files(self, paths, window, value_filter=None):
+        """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets()."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.nearest_sets(cat[0], cat[1], cat[2], set_off, window, value_filter)
+
+    def nearest_dev(self, d_ichr, d_qs, d_qe, nq, window, d_dist, d_dmin=None, value_filter=None, stream=None):
+        """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_dist (int32[nq * nfiles]) and d_dmin
+        (int32[nq], may be None) are overwritten.  nq above igd_hip_max_batch() is refused: split the batch."""
+        _chk(self._H.igd_hip_nearest_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), _window(window, "nearest_dev"), _value_filter(value_filter),
+                                         d_dist, d_dmin, stream), "igd_hip_nearest_dev")
 
     def membership_dev(self, d_ichr, d_qs, d_qe, nq, d_bits, d_nfiles_hit=None, d_nhit=None, v=0, rule=None,
                        value_filter=None, stream=None):

@@ -239,6 +239,69 @@ int igd_hip_membership_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t 
  * nq exceeds four times this number (tests). */
 int32_t igd_hip_member_grid(int64_t nq);
 
+/* Nearest record per dataset within a window: how far each region lies from the nearest record of every file, as
+ * `bedtools closest -d` / `window` and GenomicRanges' distanceToNearest measure it.  THE DEFINITIONS (the one place: kernel
+ * igd_nearest_rows, igdc_nearest_host and the tests' numpy reference agree on every integer).  For a region (c, qs, qe) and a
+ * record (c, s, e, value) on the same contig
+ *     d = 0                          if s < qe && e > qs       (the plain predicate, on the raw int32 coordinates)
+ *     d = max(s - qe, qs - e) + 1    otherwise                 (book-ended intervals are 1 bp apart: bedtools' convention)
+ * in 64-bit integers; d >= 1 in the second case, whatever the region looks like.
+ *     window       W, 0 <= W <= IGD_HIP_NEAREST_MAX_WINDOW = 2^30; anything else is IGD_HIP_ERR_ARG.  A record is WITHIN THE
+ *                  WINDOW iff d <= W, which is  s < qe + W && e > qs - W  in 64-bit arithmetic.
+ *     dist[q][f]   min d over the records of file f within the window -- with a value filter v on a database that has
+ *                  values, over those with value >= v: the nearest PASSING record -- or -1 when there is none.  int32.
+ *     dmin[q]      the minimum over f of the dist[q][f] that are not -1, else -1.
+ *     no rule      A distance is a property of the intervals, not of the reference's loop: there is no `rule` argument.  The
+ *                  widened interval [max(qs - W, 0), min(qe + W, 2^31 - 1)) is walked under rule FLAT on the image
+ *                  igd_hip_support_sets walks (the re-tiled copy when there is one); neither clamp changes which records are
+ *                  within the window, records having 0 <= start < end.
+ *     degenerate   A region on an unknown contig (c < 0 or c >= nCtg) has a row of -1.  Zero-length and inverted regions are
+ *                  not special-cased: the formula is applied literally.
+ *     sets         For set k = regions [set_off[k], set_off[k + 1]) each statistic is int64[nsets][nFiles + 1]; column nFiles is
+ *                  the any-dataset column, built from dmin (as index nFiles of igd_hip_permute_support's arrays):
+ *                      n_within[k][f]  = #{q : dist[q][f] >= 0}        n_overlap[k][f] = #{q : dist[q][f] == 0}
+ *                      sum_dist[k][f]  = the sum of the non-negative dist[q][f]
+ *     identities   n_overlap is the support of igd_hip_support_sets(..., IGD_HIP_RULE_FLAT) for every W, its last column that
+ *                  call's nhit; with W = 0, n_within == n_overlap.
+ * Every output is DEFINED by the call, as igd_hip_membership defines its rows: every word is written, nothing is added to.
+ * igd_hip_nearest: dist is int32[nq * nFiles], dmin int32[nq] (may be NULL).  The regions go through in chunks of at most
+ * igd_hip_max_batch() regions and 256 MiB of device rows (TEST-ONLY: IGD_HIP_NEAREST_ROW_BYTES lowers it).
+ * igd_hip_nearest_sets: whole sets are taken while their three result rows fit the row budget of igd_hip_support_sets, their
+ * regions go through in the chunks above (a set may be cut by a chunk), kernel igd_nearest_reduce adds every chunk's rows
+ * into the three resident matrices; the rows never leave the device and the matrices are copied out once.  Any of the three
+ * may be NULL.
+ * igd_hip_nearest_dev: device pointers, one engine batch (nq above igd_hip_max_batch() is IGD_HIP_ERR_ARG), enqueued on
+ * `stream` (NULL: the engine's own) without waiting; d_dist and d_dmin (may be NULL) are overwritten.
+ * Blocking (but for _dev), one device.  IGD_HIP_ERR_ARG -- a missing array, a bad set_off, W out of range -- comes before
+ * anything of the caller's is written.
+ * Not done: an unbounded nearest, signed or upstream/downstream distances, distance histograms, a minimum overlap, several
+ * devices, the permutation null of a distance statistic. */
+#define IGD_HIP_NEAREST_MAX_WINDOW ((int32_t)1 << 30)
+static inline IGD_HIP_OV_HD_ int igd_hip_nearest_window_valid(int64_t window) { return window >= 0 && window <= IGD_HIP_NEAREST_MAX_WINDOW; }
+/* d of one (region, record) pair */
+static inline IGD_HIP_OV_HD_ int64_t igd_hip_nearest_dist(int32_t qs, int32_t qe, int32_t start, int32_t end)
+{
+    if (start < qe && end > qs) return 0;
+    const int64_t a = (int64_t)start - (int64_t)qe, b = (int64_t)qs - (int64_t)end;
+    return (a > b ? a : b) + 1;
+}
+/* the widened interval the tiles are visited for: [max(qs - W, 0), min(qe + W, 2^31 - 1)) */
+static inline IGD_HIP_OV_HD_ void igd_hip_nearest_widen(int32_t qs, int32_t qe, int32_t window, int32_t *ws, int32_t *we)
+{
+    const int64_t a = (int64_t)qs - (int64_t)window, b = (int64_t)qe + (int64_t)window;
+    *ws = (int32_t)(a < 0 ? 0 : a);
+    *we = (int32_t)(b > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : b);
+}
+int igd_hip_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window, int32_t v,
+                    int32_t *dist, int32_t *dmin);
+int igd_hip_nearest_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                         int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist);
+int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq, int32_t window,
+                        int32_t v, int32_t *d_dist, int32_t *d_dmin, void *stream);
+/* Workgroups (of four waves) igd_nearest_rows is launched with for nq regions: a wave meets a second region only when nq
+ * exceeds four times this number (tests). */
+int32_t igd_hip_nearest_grid(int64_t nq);
+
 /* Fisher's exact test, one-sided ("greater"), of many 2x2 tables  a b / c d  in one call (kernel igd_fisher_cells).  With
  * N = a+b+c+d, K = a+b, n = a+c and X ~ Hypergeometric(N, K, n):
  *     pvalue_log[i] = -log10 P(X >= a)   a double >= 0, computed in log space: finite however small p is (a p of 10^-4609
