@@ -4,7 +4,8 @@ from ._native import NativeMissing, build  # noqa: F401
 
 __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "restrict_host", "enrich_restricted_host",
            "cooccur_host", "bitrows_gram_host", "jaccard", "perm_summary", "permute_regions_host", "permute_host", "MinOverlap",
-           "search_host", "support_host", "nearest_host", "nearest_sets_host", "nearest_summary", "NearestSets"]
+           "search_host", "support_host", "nearest_host", "nearest_sets_host", "nearest_summary", "NearestSets", "permute_nearest_host",
+           "perm_nearest_summary", "PermutationNearest"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -25,7 +26,8 @@ def __getattr__(name):
         from .database import enrich_restricted_host
         return enrich_restricted_host
     if name in ("cooccur_host", "bitrows_gram_host", "jaccard", "perm_summary", "permute_regions_host", "permute_host", "MinOverlap",
-                "search_host", "support_host", "nearest_host", "nearest_sets_host", "nearest_summary", "NearestSets"):
+                "search_host", "support_host", "nearest_host", "nearest_sets_host", "nearest_summary", "NearestSets", "permute_nearest_host",
+                "perm_nearest_summary", "PermutationNearest"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

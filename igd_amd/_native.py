@@ -211,6 +211,16 @@ def hip():
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_nearest_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
+        # the fused route and the permutation null of the distances: as igd_hip_nearest_sets / db, ichr, qs, qe, nq, ctg_len, mode,
+        # seed, nperm, window, v, n_within, n_overlap, sum_dist
+        L.igd_hip_nearest_sets_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_permute_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
+                                              C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_nearest_fused_max_files.argtypes = []
+        L.igd_hip_nearest_fused_max_files.restype = C.c_int32
+        L.igd_hip_nearest_fused_grid.argtypes = [C.c_int64]
+        L.igd_hip_nearest_fused_grid.restype = C.c_int32
         L.igd_hip_nearest_grid.argtypes = [C.c_int64]
         L.igd_hip_nearest_grid.restype = C.c_int32
         L.igd_hip_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -343,6 +353,11 @@ def _bind_core(L):
     L.igdc_nearest_sets_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.igdc_nearest_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    # permutation null of the distances on the host: db, map, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within,
+    # n_overlap, sum_dist / n_within, sum_dist, nperm, ncols, the twelve outputs
+    L.igdc_permute_nearest_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                            C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.igdc_perm_nearest_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 12
     # db, path, len (int32[nCtg]), bad_line
     L.igdc_read_genome.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L

@@ -1,0 +1,229 @@
+// engine/host_permute_nearest.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
+// igd_hip_nearest_sets_fused / igd_hip_permute_nearest: the set statistics of the nearest record per dataset through
+// igd_nearest_slices (nearest_fused_dev.hpp), and their permutation null
+// ------------------------------------------------------------------------------------------
+// igd_hip_nearest_sets_fused has igd_hip_nearest_sets' contract (host_nearest.hpp): GROUPS of whole sets whose three result rows
+// fit sets_row_bytes(), their regions in chunks of igd_hip_max_batch() -- there are no distance rows, so no row budget --
+// every chunk's part of every set cut into slices of sets_slice_len(chunk) regions, ONE launch per chunk with
+// support_launch's grid rule, the three matrices copied out once per group.
+// igd_hip_permute_nearest is igd_hip_permute_support_ov's driver (host_permute.hpp) with the three matrices as its rows: the
+// regions and ctg_len go up once (db->d_pmReg); the slice table has one row per permutation of a chunk, is built and
+// uploaded once, and a shorter last chunk uses its prefix; a chunk holds pc permutations with pc * nq <= igd_hip_max_batch()
+// and 3 * pc * (nFiles + 1) * 8 <= perm_row_bytes(); per chunk, on the engine's stream and without a wait: igd_permute_regions
+// into the staging arrays, a memset of the chunk's three matrices, the fused kernel, an asynchronous copy of the chunk's rows
+// into a buffer of this file.  Row 0 -- the set as given -- is one more launch over the regions themselves.  The null
+// distribution itself comes back, int64[nperm + 1][nFiles + 1] three times: the statistic of interest is a ratio of two of
+// them per permutation.  On an error nothing of the caller's is written.
+// Databases with more files than IGD_NEAREST_FUSED_LDS_FILES: the first calls igd_hip_nearest_sets; the second runs
+// igd_hip_nearest_dev + igd_nearest_reduce over the same staged regions (nearest_rows_reduce below), in pieces within the
+// row budget of igd_hip_nearest, with a wait per piece.  The results are the same integers.
+// The matrices and slice tables are igd_hip_nearest_sets' workspaces (db->d_nrStat, d_nrSlices).
+static_assert(IGD_SETS_SLICE_MAX < 65536, "igd_nearest_slices packs n_within and n_overlap of one slice into 16 bits each");
+
+extern "C" int32_t igd_hip_nearest_fused_max_files(void) { return IGD_NEAREST_FUSED_LDS_FILES; }
+
+// workgroups igd_nearest_slices is launched with for nslices slices: a workgroup takes a second slice only past IGD_SETS_GRID
+extern "C" int32_t igd_hip_nearest_fused_grid(int64_t nslices) { return items_grid(nslices, 1); }
+
+// igd_nearest_slices over `ns` slices of the table at db->d_nrSlices into the matrices at db->d_nrStat
+static int nearest_fused_launch(igd_hip_db *db, const SliceImage &im, const int32_t *c, const int32_t *s, const int32_t *e, int ns,
+                                int32_t window, int32_t v, int64_t matWords)
+{
+    const size_t ldsB = IGD_NEAREST_FUSED_LDS_BYTES(db->nFiles);
+    const int grid = igd_hip_nearest_fused_grid(ns);
+    auto go = [&](auto V) {
+        if (ldsB > (size_t)65536)                        // (more dynamic LDS than a launch gets unasked)
+            (void)hipFuncSetAttribute((const void *)igd_nearest_slices<V()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsB);
+        igd_nearest_slices<V()><<<grid, IGD_SETS_WG, ldsB, db->stream>>>(im.view, c, s, e, db->d_nrSlices, ns, window, im.krule, v,
+                                                                        (u64 *)db->d_nrStat, matWords);
+    };
+    if (im.useV) go(std::true_type{});
+    else go(std::false_type{});
+    HIPCHK(hipGetLastError());
+    return IGD_HIP_OK;
+}
+
+// [a0, b0) of a staged array cut into slices of row `row`, at most `len` regions each, positions relative to `base`
+static void push_slices(std::vector<SetSlice> &slices, int32_t row, int64_t a0, int64_t b0, int64_t len, int64_t base)
+{
+    for (int64_t a = a0; a < b0; a += len)
+        slices.push_back(SetSlice{row, (int32_t)(a - base), (int32_t)((a + len < b0 ? a + len : b0) - base), 0});
+}
+
+extern "C" int igd_hip_nearest_sets_fused(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                                          int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    if (nearest_window_bad("igd_hip_nearest_sets_fused", window)) return IGD_HIP_ERR_ARG;
+    if (!db || nsets < 0 || (nsets > 0 && !set_off)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_nearest_sets_fused: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nsets == 0) return IGD_HIP_OK;
+    int rc = sets_check("igd_hip_nearest_sets_fused", ichr, qs, qe, set_off, nsets);
+    if (rc != IGD_HIP_OK) return rc;
+    const int64_t nF = db->nFiles, nC = nF + 1;
+    if (nF > IGD_NEAREST_FUSED_LDS_FILES)                 // no wide form: the rows route
+        return igd_hip_nearest_sets(db, ichr, qs, qe, set_off, nsets, window, v, n_within, n_overlap, sum_dist);
+    int64_t *outs[3] = {n_within, n_overlap, sum_dist};
+    if (set_off[nsets] == 0 || nF == 0) {                // every statistic is 0: no region, or no dataset to be near
+        for (int64_t *o : outs) if (o) memset(o, 0, (size_t)nsets * (size_t)nC * 8);
+        return IGD_HIP_OK;
+    }
+    const SliceImage im = slice_image(db, IGD_HIP_RULE_FLAT, v);
+    const int64_t step = max_batch();
+    const int64_t rowCap = sets_row_bytes() / (3 * nC * 8) > 0 ? sets_row_bytes() / (3 * nC * 8) : 1;
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    std::vector<SetSlice> slices;
+    for (int32_t k0 = 0; k0 < nsets;) {
+        // one group: sets [k0, k1), regions [set_off[k0], set_off[k1])
+        const int32_t k1 = (int32_t)(nsets - k0 < rowCap ? nsets : k0 + rowCap);
+        const int64_t rows = k1 - k0, matWords = rows * nC;
+        if ((rc = dev_grow(db, &db->d_nrStat, &db->nrStatCap, 3 * matWords)) != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemsetAsync(db->d_nrStat, 0, (size_t)(3 * matWords) * 8, st));
+        int32_t k = k0;
+        for (int64_t c0 = set_off[k0]; c0 < set_off[k1]; c0 += step) {
+            const int64_t m = set_off[k1] - c0 < step ? set_off[k1] - c0 : step;
+            const int64_t sliceLen = sets_slice_len(m);
+            slices.clear();
+            while (set_off[k + 1] <= c0) k++;
+            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++)
+                push_slices(slices, j - k0, set_off[j] > c0 ? set_off[j] : c0, set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m, sliceLen, c0);
+            const int ns = (int)slices.size();
+            rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
+            if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
+            if (rc != IGD_HIP_OK) return rc;
+            HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+            if ((rc = nearest_fused_launch(db, im, db->d_qc, db->d_qs, db->d_qe, ns, window, v, matWords)) != IGD_HIP_OK) return rc;
+            HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
+        }
+        for (int i = 0; i < 3; i++)
+            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * nC, db->d_nrStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        k0 = k1;
+    }
+    return IGD_HIP_OK;
+}
+
+// Databases too wide for igd_nearest_slices: `rows` rows of nq resident regions each (c, s, e; row r = regions [r nq, (r + 1) nq))
+// through igd_hip_nearest_dev and igd_nearest_reduce into the matrices at db->d_nrStat, in pieces of nearest_step() regions --
+// a piece may cut a row, the statistics are sums over regions -- with slices of IGD_NEAREST_SLICE and a wait per piece.
+static int nearest_rows_reduce(igd_hip_db *db, const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows, int64_t nq,
+                               int32_t window, int32_t v, int64_t matWords)
+{
+    const int64_t nF = db->nFiles, nC = nF + 1, total = rows * nq, step = nearest_step(nF);
+    const int gx = (int)((nC + IGD_WAVE - 1) / IGD_WAVE);
+    hipStream_t st = db->stream;
+    std::vector<SetSlice> slices;
+    for (int64_t c0 = 0; c0 < total; c0 += step) {
+        const int64_t m = total - c0 < step ? total - c0 : step;
+        slices.clear();
+        for (int64_t r = c0 / nq; r < rows && r * nq < c0 + m; r++)
+            push_slices(slices, (int32_t)r, r * nq > c0 ? r * nq : c0, (r + 1) * nq < c0 + m ? (r + 1) * nq : c0 + m, IGD_NEAREST_SLICE, c0);
+        const int ns = (int)slices.size();
+        int rc = ensure_nearest_ws(db, m * nF, m);
+        if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
+        if (rc == IGD_HIP_OK) rc = igd_hip_nearest_dev(db, c + c0, s + c0, e + c0, m, window, v, db->d_nrDist, db->d_nrMin, st);
+        if (rc != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+        int gy = IGD_NEAREST_REDUCE_WGS / gx;
+        gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
+        igd_nearest_reduce<<<dim3((unsigned)gx, (unsigned)gy), IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns,
+                                                                                  (u64 *)db->d_nrStat, matWords);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));                // (the slice table is the host's vector)
+    }
+    return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                                       int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    if (nearest_window_bad("igd_hip_permute_nearest", window)) return IGD_HIP_ERR_ARG;
+    if (!db || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
+        (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nperm < 1 || nperm > IGD_HIP_PERM_MAX) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: %lld permutations, not 1 .. %lld", (long long)nperm, (long long)IGD_HIP_PERM_MAX);
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nq > max_batch()) {
+        snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: %lld regions, more than %lld", (long long)nq, (long long)max_batch());
+        return IGD_HIP_ERR_ARG;
+    }
+    for (int64_t i = 0; i < nq; i++) {
+        const int32_t c = ichr[i];
+        if (c < 0 || c >= db->nCtg) continue;
+        const int64_t L = ctg_len[c];
+        if (L < 1 || qs[i] < 0 || qe[i] < qs[i] || (int64_t)qe[i] > L) {
+            snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: region %lld = (%d, %d, %d) does not lie on its contig of length %lld",
+                     (long long)i, (int)c, (int)qs[i], (int)qe[i], (long long)L);
+            return IGD_HIP_ERR_ARG;
+        }
+    }
+    const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
+    int64_t *const outs[3] = {n_within, n_overlap, sum_dist};
+    if (nq == 0 || nF == 0) {                            // every statistic is 0: no region, or no dataset to be near
+        for (int64_t *o : outs) if (o) memset(o, 0, (size_t)R * (size_t)nC * 8);
+        return IGD_HIP_OK;
+    }
+
+    const SliceImage im = slice_image(db, IGD_HIP_RULE_FLAT, v);
+    const bool fused = nF <= IGD_NEAREST_FUSED_LDS_FILES;
+    int64_t pc = max_batch() / nq;
+    const int64_t byRows = perm_row_bytes() / (3 * nC * 8);
+    if (byRows < pc) pc = byRows < 1 ? 1 : byRows;
+    if (nperm < pc) pc = nperm;
+    const int64_t sliceLen = sets_slice_len(pc * nq);
+    const int64_t perRow = (nq + sliceLen - 1) / sliceLen;                // slices of one permutation
+    std::vector<SetSlice> slices;
+    if (fused) {
+        slices.reserve((size_t)(pc * perRow));
+        for (int64_t r = 0; r < pc; r++) push_slices(slices, (int32_t)r, r * nq, (r + 1) * nq, sliceLen, 0);
+    }
+    std::vector<int64_t> res((size_t)(3 * R * nC));
+
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + db->nCtg);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrStat, &db->nrStatCap, 3 * pc * nC);
+    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
+    if (rc == IGD_HIP_OK && fused) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, pc * perRow);
+    if (rc != IGD_HIP_OK) return rc;
+    int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
+    HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)db->nCtg * 4, hipMemcpyHostToDevice, st));
+    if (fused) HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+
+    // `rows` rows counted from the region arrays (c, s, e) into zeroed matrices, which go to rows [r0, r0 + rows) of res
+    auto count = [&](const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows, int64_t r0) -> int {
+        const int64_t matWords = rows * nC;
+        HIPCHK(hipMemsetAsync(db->d_nrStat, 0, (size_t)(3 * matWords) * 8, st));
+        const int rc2 = fused ? nearest_fused_launch(db, im, c, s, e, (int)(rows * perRow), window, v, matWords)
+                              : nearest_rows_reduce(db, c, s, e, rows, nq, window, v, matWords);
+        if (rc2 != IGD_HIP_OK) return rc2;
+        for (int i = 0; i < 3; i++)
+            HIPCHK(hipMemcpyAsync(res.data() + (i * R + r0) * nC, db->d_nrStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
+        return IGD_HIP_OK;
+    };
+
+    if ((rc = count(rC, rS, rE, 1, 0)) != IGD_HIP_OK) return rc;         // the set as given
+    for (int64_t p0 = 0; p0 < nperm; p0 += pc) {
+        const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
+        igd_permute_regions<<<igd_hip_permute_grid(n * nq), IGD_SETS_WG, 0, st>>>(rC, rS, rE, (unsigned)nq, rL, db->nCtg, mode, (u64)seed, (u64)p0,
+                                                                               (unsigned)(n * nq), db->d_qc, db->d_qs, db->d_qe);
+        HIPCHK(hipGetLastError());
+        if ((rc = count(db->d_qc, db->d_qs, db->d_qe, n, 1 + p0)) != IGD_HIP_OK) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < 3; i++)
+        if (outs[i]) memcpy(outs[i], res.data() + (size_t)i * (size_t)(R * nC), (size_t)(R * nC) * 8);
+    return IGD_HIP_OK;
+}

@@ -1387,7 +1387,9 @@ static void cooccur_file(char *path, int32_t v)
  * filter are `-q`'s dispatch for -v.  Routing as `-u`, decided on regions x (N + 1): at most igdc_host_limit() go through
  * igdc_permute_host, more through igd_hip_permute_support on one device.  A region outside its contig's length, or on a contig
  * the genome file lacks, ends the run with a message that names the line. */
-static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t seed, int pmode, int32_t v)
+/* `-D W` switches the statistic from support to distance (permute_nearest_table below); window < 0: the support. */
+static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int32_t window);
+static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t seed, int pmode, int32_t v, int32_t window)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
@@ -1426,11 +1428,13 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
         }
         if (igdc_queries_push(&q, id, st, en) != 0) { fprintf(stderr, "igd: out of memory\n"); goto done; }
     }
-    if (q.n > igd_hip_max_batch() || (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63) {
+    if (q.n > igd_hip_max_batch() ||
+        (window < 0 && (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63)) {
         printf("Not supported: -P %lld with %lld regions\n", (long long)nperm, (long long)q.n);
         goto done;
     }
-    {
+    if (window >= 0) permute_nearest_table(&q, len, nperm, seed, pmode, ev, window);
+    else {
         int64_t *st7 = (int64_t *)calloc(7 * (size_t)nC, sizeof(int64_t));
         double *fl = (double *)calloc(5 * (size_t)nC, sizeof(double));
         if (!st7 || !fl) { fprintf(stderr, "igd: out of memory\n"); free(st7); free(fl); goto done; }
@@ -1544,6 +1548,68 @@ static void nearest_files(char **paths, int32_t n, int32_t v, int setLines, int3
     free(q); free(ichr); free(qs); free(qe); free(off); free(st3); free(mean);
 }
 
+/* ------------------------------- `igd search -q F -P N -g genome -D <bp>` --------------- */
+/* Permutation null of the nearest-record distances (include/igd_hip.h: igd_hip_permute_nearest; igd_core.h:
+ * igdc_perm_nearest_summary has the columns): "are my regions closer to dataset f than chance".  The header
+ *     index n_within mean_dist within_mean within_sd within_z nlog10_p_within_upper dist_mean dist_sd dist_z n_def dist_n_le
+ *     nlog10_p_dist_lower File                                                                       (tab-separated)
+ * and one line per dataset; floats as %.6f, mean_dist and dist_mean as %.2f as under -N, NaN as NA; then -N's last line for
+ * the set as given, followed by the same statistics (within_mean .. nlog10_p_dist_lower) of the any-dataset column.  Routing
+ * as -P: regions x (N + 1) against igdc_host_limit(). */
+static void print_na(const char *fmt, double x, const char *after)
+{
+    if (x != x) printf("NA%s", after);
+    else { printf(fmt, x); printf("%s", after); }
+}
+
+static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int32_t window)
+{
+    const int32_t nfiles = IGD->nFiles;
+    const size_t nC = (size_t)nfiles + 1, R = (size_t)nperm + 1;
+    int64_t *st3 = (int64_t *)calloc(3 * R * nC + 3 * nC, sizeof(int64_t));
+    double *fl = (double *)calloc(9 * nC, sizeof(double));
+    if (!st3 || !fl) { fprintf(stderr, "igd: out of memory\n"); free(st3); free(fl); return; }
+    int64_t *nw = st3, *no = nw + R * nC, *sd = no + R * nC, *nge = sd + R * nC, *ndef = nge + nC, *nle = ndef + nC;
+    double *wm = fl, *ws = wm + nC, *wz = ws + nC, *pu = wz + nC, *md = pu + nC, *dm = md + nC, *ds = dm + nC, *dz = ds + nC, *pl = dz + nC;
+    double t0 = now_s();
+    int ok = 0;
+    igdc_map *hm = host_map_lim(q->n * (nperm + 1), igdc_host_limit());
+    if (hm) {
+        ok = igdc_permute_nearest_host(g_core, hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd) == 0;
+        igdc_map_close(hm);
+        if (ok) phase("permutation null of the distances on the host (small files)", &t0);
+    }
+    if (!ok) {                                        /* (after a read error too: the engine reads the file its own way) */
+        igd_hip_db *dev = engine();
+        t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_permute_nearest(dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd);
+            if (rc != IGD_HIP_OK) engine_failed("permutation null of the distances", rc);
+            phase("permutation null of the distances (H2D + permute and fused nearest kernels + D2H)", &t0);
+        }
+    }
+    if (!g_fail_rc && igdc_perm_nearest_summary(nw, sd, nperm, (int64_t)nC, wm, ws, wz, nge, pu, md, dm, ds, dz, ndef, nle, pl) == 0) {
+        printf("index\tn_within\tmean_dist\twithin_mean\twithin_sd\twithin_z\tnlog10_p_within_upper\tdist_mean\tdist_sd\tdist_z\tn_def\tdist_n_le\t"
+               "nlog10_p_dist_lower\tFile\n");
+        for (int32_t i = 0; i <= nfiles; i++) {
+            if (i < nfiles) {
+                printf("%d\t%lld\t", (int)i, (long long)nw[i]);
+                print_na("%.2f", md[i], "\t");
+            } else {
+                printf("Regions with a dataset within %d bp: %lld of %lld; overlapping: %lld", (int)window, (long long)nw[i], (long long)q->n,
+                       (long long)no[i]);
+                print_mean("; mean distance ", nw[i], md[i], "\t");
+            }
+            print_na("%.6f", wm[i], "\t"); print_na("%.6f", ws[i], "\t"); print_na("%.6f", wz[i], "\t"); print_na("%.6f", pu[i], "\t");
+            print_na("%.2f", dm[i], "\t"); print_na("%.6f", ds[i], "\t"); print_na("%.6f", dz[i], "\t");
+            printf("%lld\t%lld\t", (long long)ndef[i], (long long)nle[i]);
+            print_na("%.6f", pl[i], i < nfiles ? "\t" : "\n");
+            if (i < nfiles) printf("%s\n", IGD->finfo[i].fileName);
+        }
+    }
+    free(st3); free(fl);
+}
+
 /* ------------------------------- `igd search` ----------------------------------------- */
 static int usage_search(void)
 {
@@ -1578,6 +1644,9 @@ static int usage_search(void)
             "                               with at most six places.  With -q or -Q alone, -u, -U [-R] and -P\n"
             "    -N <bp>                    with -q or -Q: per dataset, the query regions with a record within <bp> base pairs (0 to\n"
             "                               1073741824), those that overlap one, and the mean distance to the nearest record\n"
+            "    -D <bp>                    with -P: the null of the distances instead -- per dataset the regions with a record within\n"
+            "                               <bp> base pairs (0 to 1073741824) and their mean distance to the nearest one, each\n"
+            "                               placed among the permuted sets' (mean, sd, z, one-sided p)\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -1625,6 +1694,7 @@ int igd_search(int argc, char **argv)                                        /* 
     char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
     char *permArg = NULL, *genomeName = NULL, *seedArg = NULL, *pmodeArg = NULL;      /* -P, -g, -S, -M (see permute_file) */
     char *nearArg = NULL;                                                             /* -N (see nearest_files) */
+    char *distArg = NULL;                                                             /* -D (see permute_nearest_table) */
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
         const char *a = argv[i];
@@ -1671,6 +1741,10 @@ int igd_search(int argc, char **argv)                                        /* 
             if (i + 1 >= argc) { printf("No window.\n"); return EX_OK; }
             nearArg = argv[i + 1];
             i++;                                      /* (the window is not an option: "-N -5" is a refused window) */
+        } else if (strcmp(a, "-D") == 0) {            /* (not the reference's: -P on the distances, see permute_nearest_table) */
+            if (i + 1 >= argc) { printf("Not supported: -D without a window\n"); return EX_USAGE; }
+            distArg = argv[i + 1];
+            i++;                                      /* (the window is not an option: "-D -5" is a refused window) */
         } else if (strcmp(a, "-g") == 0) {
             if (i + 1 >= argc) { printf("No genome file.\n"); return EX_OK; }
             genomeName = argv[i + 1];
@@ -1701,6 +1775,29 @@ int igd_search(int argc, char **argv)                                        /* 
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    int32_t distW = -1;                                                       /* -D: every refusal is a usage error */
+    if (distArg) {
+        char *end = NULL, *pend = NULL;
+        const long long w = strtoll(distArg, &end, 10);
+        const long long np = permArg ? strtoll(permArg, &pend, 10) : 0;
+        const char *why = NULL;
+        if (!permArg) why = "-D without -P";
+        else if (nearArg || minov || listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)
+            why = "-D together with -N, -O, -A, -B, -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r";
+        else if (!genomeName) why = "-D -P without -g";
+        else if (mode != 1) why = "-D -P without -q";
+        else if (pend == permArg || *pend || np < 1 || np > (long long)IGD_HIP_PERM_MAX) why = "-D with a number of permutations outside 1 to 1048576";
+        else if (pmodeArg && strcmp(pmodeArg, "circular") != 0 && strcmp(pmodeArg, "shuffle") != 0) why = "-D with a -M that is neither circular nor shuffle";
+        if (why) {
+            printf("Not supported: %s\n", why);
+            return EX_USAGE;
+        }
+        if (end == distArg || *end || w < 0 || w > (long long)IGD_HIP_NEAREST_MAX_WINDOW) {
+            printf("Not supported: -D %s (a window of 0 to %lld base pairs)\n", distArg, (long long)IGD_HIP_NEAREST_MAX_WINDOW);
+            return EX_USAGE;
+        }
+        distW = (int32_t)w;
+    }
     if (nearArg) {
         char *end = NULL;
         const long long w = strtoll(nearArg, &end, 10);
@@ -1756,7 +1853,7 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported: -M %s (circular or shuffle)\n", pmodeArg);
             return EX_OK;
         }
-        permute_file(qfName, genomeName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v);
+        permute_file(qfName, genomeName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW);
     } else if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
         printf("Not supported: -C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r\n");
         return EX_OK;

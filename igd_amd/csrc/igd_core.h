@@ -211,6 +211,31 @@ int igdc_nearest_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *
                            int64_t *sum_dist);
 /* mean[i] = sum_dist[i] / n_within[i] as a double, NaN where n_within[i] = 0.  Needs no database.  0, or -1 for a missing array. */
 int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t n, double *mean);
+/* Permutation null of the nearest-record distances on the host (what igd_hip_permute_nearest computes; include/igd_hip.h): each
+ * output is int64[(nperm + 1) * (nFiles + 1)] (may be NULL), row 0 the set as given, row p + 1 permutation p of
+ * igdc_permute_regions_host's generator counted as igdc_nearest_sets_host counts a set; threads run over the rows.  0; -1 for a
+ * refused argument (igdc_permute_host's but the sumsq guard, and a window outside 0 .. 2^30) or when a tile could not be read
+ * -- nothing is written then. */
+int igdc_permute_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                              const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                              int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist);
+/* The summary of such a null distribution, per column f of ncols; n_within and sum_dist are int64[(nperm + 1) * ncols].  With
+ * P = nperm, nw_0 / sd_0 the observed row and nw_p / sd_p the permuted rows:
+ *     counts      within_mean, within_sd, within_z: igdc_perm_summary's formulas over nw_p (the variance's numerator exact in 128
+ *                 bits; sd NaN when P = 1, z NaN when sd is 0 or NaN); within_n_ge = #{p : nw_p >= nw_0};
+ *                 nlog10_p_within_upper = -log10((within_n_ge + 1) / (P + 1))
+ *     distances   mean_dist = sd_0 / nw_0 (NaN when nw_0 = 0); n_def = #{p : nw_p > 0}; dist_mean and dist_sd over
+ *                 m_p = sd_p / nw_p of those permutations, in doubles, two passes in permutation order (dist_mean NaN when
+ *                 n_def = 0; dist_sd divides by n_def - 1 and is NaN when n_def < 2); dist_z = (mean_dist - dist_mean) / dist_sd,
+ *                 NaN when nw_0 = 0 or the sd is 0 or NaN; dist_n_le = #{p : nw_p > 0 and sd_p * nw_0 <= sd_0 * nw_p}, compared
+ *                 exactly in 128 bits -- a permutation with nothing within the window is not "as close" -- and 0 when nw_0 = 0;
+ *                 nlog10_p_dist_lower = -log10((dist_n_le + 1) / (P + 1))
+ * within_n_ge, n_def and dist_n_le are int64[ncols], the others double[ncols]; every output may be NULL.  Needs no database.
+ * 0, or -1 for a missing input or nperm < 1. */
+int igdc_perm_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t nperm, int64_t ncols, double *within_mean,
+                              double *within_sd, double *within_z, int64_t *within_n_ge, double *nlog10_p_within_upper, double *mean_dist,
+                              double *dist_mean, double *dist_sd, double *dist_z, int64_t *n_def, int64_t *dist_n_le,
+                              double *nlog10_p_dist_lower);
 /* A genome file, lines `name<TAB>length`: len[c] = the length of contig c of the database (int32[nCtg]); lines of contigs the
  * database does not know are ignored, contigs the file does not name get 0.  0; -1 when the file cannot be opened; -2 for a
  * line of a known contig without a length or with one that is negative or above 2^31 - 1 (*bad_line, may be NULL, = its

@@ -370,6 +370,7 @@ struct igd_hip_db {
 #include "engine/cooccur_dev.hpp"     // igd_bits_transpose, igd_bitrows_gram: bit rows into bit columns, popcount Gram product -- dataset co-occurrence
 #include "engine/permute_dev.hpp"     // igd_permute_regions, igd_perm_stats: shifted / shuffled region sets, column statistics of a row matrix -- permutation null
 #include "engine/nearest_dev.hpp"     // igd_nearest_rows, igd_nearest_reduce: the same walk over a widened interval, one distance row per region -- nearest record per dataset
+#include "engine/nearest_fused_dev.hpp" // igd_nearest_slices: the same walk and table, folded into per-slice LDS accumulators -- the set statistics without the rows
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -387,6 +388,7 @@ struct igd_hip_db {
 #include "engine/host_cooccur.hpp"    // igd_hip_cooccur / igd_hip_bits_transpose / igd_hip_bitrows_gram: chunks of regions, rows stay resident
 #include "engine/host_permute.hpp"    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: chunks of permutations, rows stay resident
 #include "engine/host_nearest.hpp"    // igd_hip_nearest / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
+#include "engine/host_permute_nearest.hpp" // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: one fused launch per chunk, the null distribution of the distance statistics
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

@@ -387,6 +387,39 @@ int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t nrows, int64
     return fn ? fn(db, rows, nrows, ncols, observed, sum, sumsq, n_ge, n_le, pmin, pmax) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_nearest_sets_fused(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                               int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int32_t, int32_t,
+                        int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_nearest_sets_fused");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, window, v, n_within, n_overlap, sum_dist) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                            int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
+                            int64_t *sum_dist)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int, uint64_t, int64_t,
+                        int32_t, int32_t, int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_permute_nearest");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap, sum_dist) : IGD_HIP_ERR_DEVICE;
+}
+
+int32_t igd_hip_nearest_fused_max_files(void)
+{
+    typedef int32_t (*fn_t)(void);
+    RESOLVE(fn_t, "igd_hip_nearest_fused_max_files");
+    return fn ? fn() : 0;
+}
+
+int32_t igd_hip_nearest_fused_grid(int64_t nslices)
+{
+    typedef int32_t (*fn_t)(int64_t);
+    RESOLVE(fn_t, "igd_hip_nearest_fused_grid");
+    return fn ? fn(nslices) : 0;
+}
+
 int32_t igd_hip_permute_grid(int64_t n)
 {
     typedef int32_t (*fn_t)(int64_t);

@@ -1262,6 +1262,156 @@ int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64
     return 0;
 }
 
+/* ---- permutation null of the nearest-record distances (what igd_hip_permute_nearest computes) ----------------------------
+ * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator; a row is igdc_nearest_sets_host's
+ * walk over its regions (one_region_nearest) summed into the three statistics.  Threads run over the rows (thread k takes
+ * rows k, k + T, ..), each with its own permuted arrays, distance row and tile buffer; the rows are disjoint.  Everything is
+ * computed into a buffer and copied out at the end: -1 (a refused argument, a tile that could not be read) writes nothing. */
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe, *ctg_len;
+    int64_t nq, nrows;
+    int mode; uint64_t seed;
+    int32_t window, v; int use_v;
+    int64_t *res;           /* three matrices of nrows x (nFiles + 1) */
+    int32_t *ps, *pe, *row; /* the permuted set, one distance row */
+    int k, T, io_failed;
+} pnear_job;
+
+static void *pnear_run(void *arg)
+{
+    pnear_job *P = (pnear_job *)arg;
+    const int64_t nF = P->db->nFiles, nC = nF + 1;
+    tilebuf tb;
+    memset(&tb, 0, sizeof tb);
+    tb.ichr = -1;
+    for (int64_t r = P->k; r < P->nrows && !tb.failed; r += P->T) {
+        const int32_t *s = P->qs, *e = P->qe;
+        if (r > 0) {
+            (void)igdc_permute_regions_host(P->ichr, P->qs, P->qe, P->nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, r - 1, 1, P->ps, P->pe);
+            s = P->ps; e = P->pe;
+        }
+        int64_t *nw = P->res + r * nC, *no = nw + P->nrows * nC, *sd = no + P->nrows * nC;
+        for (int64_t i = 0; i < P->nq && !tb.failed; i++) {
+            const int32_t dm = one_region_nearest(P->db, P->m, &tb, P->ichr[i], s[i], e[i], P->window, P->v, P->use_v, P->row);
+            if (dm < 0) continue;                                          /* (no record within the window: the row is all -1) */
+            for (int64_t f = 0; f < nC; f++) {
+                const int32_t d = f < nF ? P->row[f] : dm;
+                if (d < 0) continue;
+                nw[f]++;
+                no[f] += d == 0;
+                sd[f] += d;
+            }
+        }
+    }
+    P->io_failed = tb.failed;
+    free(tb.buf);
+    return NULL;
+}
+
+int igdc_permute_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                              const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                              int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    if (!db || !m || nq < 0 || !igd_hip_nearest_window_valid(window) || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
+        (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) || nperm < 1 || nperm > IGD_HIP_PERM_MAX ||
+        nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0)
+        return -1;
+    const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
+    int T = host_threads(nq * R > 0 ? nq * R : 1);
+    if (T > R) T = (int)R;
+    int64_t *res = (int64_t *)calloc((size_t)(3 * R * nC), sizeof(int64_t));
+    int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (2 * (size_t)nq + (size_t)nF) + 1));
+    int rc = res && w ? 0 : -1;
+    pnear_job job[64];
+    pthread_t th[64];
+    int started[64];
+    for (int k = 0; k < T && rc == 0; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe; job[k].ctg_len = ctg_len;
+        job[k].nq = nq; job[k].nrows = R; job[k].mode = mode; job[k].seed = seed;
+        job[k].window = window; job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+        job[k].res = res;
+        job[k].ps = w + (size_t)k * (2 * (size_t)nq + (size_t)nF); job[k].pe = job[k].ps + nq; job[k].row = job[k].pe + nq;
+        job[k].k = k; job[k].T = T;
+    }
+    if (rc == 0 && nq > 0 && nF > 0) {
+        for (int k = 1; k < T; k++) {
+            started[k] = pthread_create(&th[k], NULL, pnear_run, &job[k]) == 0;
+            if (!started[k]) pnear_run(&job[k]);
+        }
+        pnear_run(&job[0]);
+        for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
+        for (int k = 0; k < T; k++) if (job[k].io_failed) rc = -1;
+    }
+    if (rc == 0) {
+        int64_t *const out[3] = {n_within, n_overlap, sum_dist};
+        for (int s = 0; s < 3; s++) if (out[s]) memcpy(out[s], res + (size_t)s * (size_t)(R * nC), sizeof(int64_t) * (size_t)(R * nC));
+    }
+    free(res); free(w);
+    return rc;
+}
+
+/* the summary of a null distribution of distance statistics; igd_core.h has the formulas */
+int igdc_perm_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t nperm, int64_t ncols, double *within_mean,
+                              double *within_sd, double *within_z, int64_t *within_n_ge, double *nlog10_p_within_upper, double *mean_dist,
+                              double *dist_mean, double *dist_sd, double *dist_z, int64_t *n_def, int64_t *dist_n_le,
+                              double *nlog10_p_dist_lower)
+{
+    const double P = (double)nperm, nan = __builtin_nan("");
+    if (!sqrt || !log10 || nperm < 1 || ncols < 0 || (ncols > 0 && (!n_within || !sum_dist))) return -1;
+    for (int64_t f = 0; f < ncols; f++) {
+        const int64_t nw0 = n_within[f], sd0 = sum_dist[f];
+        /* counts: igdc_perm_summary's formulas */
+        __int128 sum = 0, sumsq = 0;
+        int64_t nge = 0, ndef = 0, nle = 0;
+        for (int64_t p = 1; p <= nperm; p++) {
+            const int64_t x = n_within[p * ncols + f];
+            sum += x;
+            sumsq += (__int128)x * (__int128)x;
+            nge += x >= nw0;
+        }
+        const double mu = (double)sum / P;
+        double s = nan;
+        if (nperm > 1) s = sqrt((double)((__int128)nperm * sumsq - sum * sum) / (P * (P - 1.0)));
+        if (within_mean) within_mean[f] = mu;
+        if (within_sd) within_sd[f] = s;
+        if (within_z) within_z[f] = (s != s || s == 0.0) ? nan : ((double)nw0 - mu) / s;
+        if (within_n_ge) within_n_ge[f] = nge;
+        if (nlog10_p_within_upper) nlog10_p_within_upper[f] = 0.0 - log10((double)(nge + 1) / (P + 1.0));
+        /* distances: m_p = sd_p / nw_p over the permutations with nw_p > 0, two passes in permutation order */
+        const double md = nw0 > 0 ? (double)sd0 / (double)nw0 : nan;
+        double acc = 0.0;
+        for (int64_t p = 1; p <= nperm; p++) {
+            const int64_t nwp = n_within[p * ncols + f], sdp = sum_dist[p * ncols + f];
+            if (nwp <= 0) continue;
+            ndef++;
+            acc += (double)sdp / (double)nwp;
+            if (nw0 > 0 && (__int128)sdp * (__int128)nw0 <= (__int128)sd0 * (__int128)nwp) nle++;
+        }
+        const double dmu = ndef > 0 ? acc / (double)ndef : nan;
+        double ds = nan;
+        if (ndef > 1) {
+            double ss = 0.0;
+            for (int64_t p = 1; p <= nperm; p++) {
+                const int64_t nwp = n_within[p * ncols + f];
+                if (nwp <= 0) continue;
+                const double t = (double)sum_dist[p * ncols + f] / (double)nwp - dmu;
+                ss += t * t;
+            }
+            ds = sqrt(ss / (double)(ndef - 1));
+        }
+        if (mean_dist) mean_dist[f] = md;
+        if (dist_mean) dist_mean[f] = dmu;
+        if (dist_sd) dist_sd[f] = ds;
+        if (dist_z) dist_z[f] = (nw0 <= 0 || ds != ds || ds == 0.0) ? nan : (md - dmu) / ds;
+        if (n_def) n_def[f] = ndef;
+        if (dist_n_le) dist_n_le[f] = nle;
+        if (nlog10_p_dist_lower) nlog10_p_dist_lower[f] = 0.0 - log10((double)(nle + 1) / (P + 1.0));
+    }
+    return 0;
+}
+
 /* The handle flavours' batches (Python search_n / search_1, R search_nr / getOverlaps): on the host while the batch is
  * small and no engine is resident, otherwise on the engine, which is attached at the first batch that needs it -- the
  * moment the reference would do its first fseek/fread (src/igd_search.c:469-476); open_iGD reads the header only, like

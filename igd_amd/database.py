@@ -33,6 +33,10 @@ PermutationSupport = collections.namedtuple("PermutationSupport", "observed sum 
 PermutationSummary = collections.namedtuple("PermutationSummary", "mean sd z nlog10_p_upper nlog10_p_lower")
 PERM_MODES = {"circular": 0, "shuffle": 1}           # IGD_HIP_PERM_CIRCULAR, IGD_HIP_PERM_SHUFFLE
 NearestSets = collections.namedtuple("NearestSets", "n_within n_overlap sum_dist window")
+PermutationNearest = collections.namedtuple("PermutationNearest", "n_within n_overlap sum_dist window nperm")
+PermutationNearestSummary = collections.namedtuple(
+    "PermutationNearestSummary", "within_mean within_sd within_z within_n_ge nlog10_p_within_upper mean_dist dist_mean dist_sd dist_z n_def "
+    "dist_n_le nlog10_p_dist_lower")
 NEAREST_MAX_WINDOW = 1 << 30                         # IGD_HIP_NEAREST_MAX_WINDOW
 
 
@@ -440,6 +444,51 @@ def perm_summary(ps):
     if N.cli().igdc_perm_summary(*[_ptr(x) for x in a], int(ps.nperm), n, *[_ptr(x) for x in out]) != 0:
         raise IgdError("perm_summary: bad argument")
     return PermutationSummary(*out)
+
+
+def _three_out(out, shape, what):
+    """three C-ordered int64 arrays of `shape`: the caller's (overwritten) or new ones"""
+    if out is None:
+        return [np.empty(shape, np.int64) for _ in range(3)]
+    if len(out) != 3 or any(a.dtype != np.int64 or a.shape != shape or not a.flags.c_contiguous for a in out):
+        raise IgdError("%s: out must be three C-ordered int64%s" % (what, list(shape)))
+    return list(out)
+
+
+def permute_nearest_host(igd_path, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None):
+    """Database.permutation_nearest() on the host (igdc_permute_nearest_host: pread on the .igd, threads over the permutations;
+    no device is touched): a PermutationNearest."""
+    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_nearest_host")
+    pm = _perm_mode(mode, "permute_nearest_host")
+    with _HostDb(igd_path, "permute_nearest_host") as h:
+        nctg = h.core.contents.nCtg
+        if len(ctg_len) != nctg:
+            raise IgdError("permute_nearest_host: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), nctg))
+        out = [np.empty((max(int(nperm), 0) + 1, h.nfiles + 1), np.int64) for _ in range(3)]
+        if h.L.igdc_permute_nearest_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, int(seed) & (2 ** 64 - 1),
+                                         int(nperm), _window(window, "permute_nearest_host"), _value_filter(value_filter),
+                                         *[_ptr(a) for a in out]) != 0:
+            raise IgdError("permute_nearest_host: a refused argument (number of permutations, window, a region outside its contig), or a "
+                           "tile of %s could not be read" % igd_path)
+        return PermutationNearest(*out, int(window), int(nperm))
+
+
+def perm_nearest_summary(pn):
+    """The summary of a PermutationNearest (igdc_perm_nearest_summary; igd_core.h has the formulas): a
+    PermutationNearestSummary of arrays [nfiles + 1] -- float64, but within_n_ge, n_def and dist_n_le, which are int64.  Of the
+    counts: mean, sd, z of the permuted n_within, the permutations with n_within >= the observed one and -log10 of the upper
+    p-value.  Of the distances: the observed mean distance, mean and sd (ddof = 1) of the permuted mean distances over the
+    n_def permutations that have one, z, the permutations at least as close as observed (compared exactly) and -log10 of the
+    lower p-value."""
+    nw, sd = (np.ascontiguousarray(x, dtype=np.int64) for x in (pn.n_within, pn.sum_dist))
+    if nw.ndim != 2 or nw.shape != sd.shape or nw.shape[0] != int(pn.nperm) + 1:
+        raise IgdError("perm_nearest_summary: n_within and sum_dist must be int64[nperm + 1, ncols]")
+    n = nw.shape[1]
+    kinds = [np.float64] * 3 + [np.int64] + [np.float64] * 5 + [np.int64] * 2 + [np.float64]
+    out = [np.empty(n, k) for k in kinds]
+    if N.cli().igdc_perm_nearest_summary(_ptr(nw), _ptr(sd), int(pn.nperm), n, *[_ptr(x) for x in out]) != 0:
+        raise IgdError("perm_nearest_summary: bad argument")
+    return PermutationNearestSummary(*out)
 
 
 def _window(window, what):
@@ -1071,6 +1120,56 @@ class Database:
         _chk(self._H.igd_hip_nearest_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, _window(window, "nearest_sets"),
                                           _value_filter(value_filter), *[_ptr(a) for a in out]), "igd_hip_nearest_sets")
         return NearestSets(*out, int(window))
+
+    def nearest_sets_fused(self, ichr, qs, qe, set_off, window, value_filter=None, out=None):
+        """nearest_sets() through the fused kernel (igd_hip_nearest_sets_fused, kernel igd_nearest_slices): the same NearestSets,
+        every integer, without distance rows in device memory.  Databases with more files than igd_hip_nearest_fused_max_files()
+        take nearest_sets()'s route.  out, when given, is a list of three C-ordered int64[nsets, nfiles + 1] that are
+        overwritten."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+        nsets = len(set_off) - 1
+        if nsets < 0:
+            raise IgdError("nearest_sets_fused: set_off needs nsets + 1 entries")
+        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("nearest_sets_fused: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
+        out = _three_out(out, (nsets, self.nfiles + 1), "nearest_sets_fused")
+        _chk(self._H.igd_hip_nearest_sets_fused(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets,
+                                                _window(window, "nearest_sets_fused"), _value_filter(value_filter), *[_ptr(a) for a in out]),
+             "igd_hip_nearest_sets_fused")
+        return NearestSets(*out, int(window))
+
+    def nearest_fused_files(self, paths, window, value_filter=None):
+        """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets_fused()."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.nearest_sets_fused(cat[0], cat[1], cat[2], set_off, window, value_filter)
+
+    def permutation_nearest(self, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, out=None):
+        """Permutation null of the nearest-record distances of one region set (igd_hip_permute_nearest): "are my regions closer
+        to dataset f than chance".  The set is moved nperm times as permutation_support() moves it (same generator, mode, seed
+        and ctg_len) and every permuted set is measured as nearest_sets() measures a set.  Returns PermutationNearest(n_within,
+        n_overlap, sum_dist, window, nperm), int64[nperm + 1, nfiles + 1] each: row 0 the set as given, row p + 1 permutation
+        p, the last column the any-dataset column.  The null distribution itself comes back -- the mean distance
+        sum_dist / n_within is a ratio of two columns that both vary -- and perm_nearest_summary() places the observed row
+        in it.  Neither the permuted regions nor any distance row leave the device.  out, when given, is a list of three
+        C-ordered int64[nperm + 1, nfiles + 1] that are overwritten (untouched when the call raises)."""
+        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_nearest")
+        if len(ctg_len) != self.nctg:
+            raise IgdError("permutation_nearest: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), self.nctg))
+        out = _three_out(out, (max(int(nperm), 0) + 1, self.nfiles + 1), "permutation_nearest")
+        _chk(self._H.igd_hip_permute_nearest(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len),
+                                             _perm_mode(mode, "permutation_nearest"), int(seed) & (2 ** 64 - 1), int(nperm),
+                                             _window(window, "permutation_nearest"), _value_filter(value_filter), *[_ptr(a) for a in out]),
+             "igd_hip_permute_nearest")
+        return PermutationNearest(*out, int(window), int(nperm))
+
+    def permutation_nearest_files(self, path, genome_path, nperm, window, seed=0, mode="circular", value_filter=None):
+        """The null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the integers behind
+        what `igd search -q path -P nperm -g genome_path -D window` prints."""
+        return self.permutation_nearest(*self.read_queries(path), self.read_genome(genome_path), nperm, window, seed, mode, value_filter)
 
     def nearest_files(self, paths, window, value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets()."""

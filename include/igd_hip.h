@@ -302,6 +302,32 @@ int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_
  * exceeds four times this number (tests). */
 int32_t igd_hip_nearest_grid(int64_t nq);
 
+/* The set statistics without the distance rows, and their permutation null (kernel igd_nearest_slices: the walk and table of
+ * igd_nearest_rows, folded per region into LDS accumulators of the slice; nothing per region reaches memory).
+ * igd_hip_nearest_sets_fused: the contract, checks and outputs of igd_hip_nearest_sets, every integer the same.  Groups of
+ * whole sets within the row budget of igd_hip_support_sets, regions in chunks of igd_hip_max_batch(), one launch per chunk.
+ * igd_hip_permute_nearest: "are my regions closer to dataset f than chance" (regioneR's permTest with meanDistance).  Each
+ * output is int64[nperm + 1][nFiles + 1] (any may be NULL): row 0 the statistics of the set as given, row p + 1 those of
+ * permutation p of THE GENERATOR below (igd_hip_perm_place; mode, seed and ctg_len as igd_hip_permute_support), column nFiles
+ * the any-dataset column.  The null distribution itself comes back, not moments of it: the statistic of interest,
+ * sum_dist / n_within, is a ratio of two columns that both vary per permutation (igdc_perm_nearest_summary, igd_core.h).
+ * Chunks of pc permutations, pc * nq <= igd_hip_max_batch() and 3 * pc * (nFiles + 1) * 8 <= the row budget of
+ * igd_hip_permute_support (TEST-ONLY: IGD_HIP_PERM_ROW_BYTES); per chunk igd_permute_regions, a memset, igd_nearest_slices
+ * and a copy, enqueued without a wait.  IGD_HIP_ERR_ARG before any launch, nothing of the caller's written: W out of range, a
+ * missing array, no such mode, nperm < 1 or > IGD_HIP_PERM_MAX, nq > igd_hip_max_batch(), a region on a known contig outside
+ * 0 <= s <= e <= L.  nq == 0 or nFiles == 0: all zeros.  Blocking, one device.
+ * Databases with more than igd_hip_nearest_fused_max_files() files take igd_nearest_rows + igd_nearest_reduce instead (there
+ * is no wide form of the fused kernel); the results are the same.  igd_hip_nearest_fused_grid: workgroups the fused kernel is
+ * launched with for nslices slices (tests: a workgroup takes a second slice only past this number).
+ * Not done: several sets or a set list under the permutation, signed or unbounded distances, a minimum overlap, several devices. */
+int igd_hip_nearest_sets_fused(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                               int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist);
+int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                            int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
+                            int64_t *sum_dist);
+int32_t igd_hip_nearest_fused_max_files(void);
+int32_t igd_hip_nearest_fused_grid(int64_t nslices);
+
 /* Fisher's exact test, one-sided ("greater"), of many 2x2 tables  a b / c d  in one call (kernel igd_fisher_cells).  With
  * N = a+b+c+d, K = a+b, n = a+c and X ~ Hypergeometric(N, K, n):
  *     pvalue_log[i] = -log10 P(X >= a)   a double >= 0, computed in log space: finite however small p is (a p of 10^-4609
