@@ -397,11 +397,11 @@ static int search_dev_impl(igd_hip_db *db, const int32_t *d_ichr, const int32_t 
             w.out = (u64 *)d_hits;
             SortK Kt = K;
             Kt.a.sbCap = 0; Kt.a.wldsBytes = (int)tailWave; Kt.a.tailHistOff = tailHistOff;
-            // IGD_REDUCE_GROUPS row groups sum the slab; the launch is filled up to IGD_TAIL_WGS workgroups (8 waves per SIMD),
-            // which find out from the batch's control words that the tail has nothing for them -- or share a long
-            // exact-walk list and the coverage of long queries, whose loops are chains of dependent loads
-            const int gx = (fileN + IGD_TAIL_WG - 1) / IGD_TAIL_WG;
-            dim3 rg(gx, (!last || IGD_REDUCE_GROUPS * gx >= IGD_TAIL_WGS) ? IGD_REDUCE_GROUPS : (IGD_TAIL_WGS + gx - 1) / gx);
+            // one workgroup per (column block of 64 files, row share) sums the slab; the last pass's launch is filled up to
+            // IGD_TAIL_WGS workgroups, which find out from the batch's control words that the tail has nothing for them -- or
+            // share a long exact-walk list and the coverage of long queries, whose loops are chains of dependent loads
+            const int sumWgs = (fileN + IGD_WAVE - 1) / IGD_WAVE * IGD_REDUCE_SPLIT;
+            dim3 rg(last && sumWgs < IGD_TAIL_WGS ? IGD_TAIL_WGS : sumWgs);
             const int rows32 = (mode != 2 && packed) ? db->epoch : 0;      // the merge join's kernel leaves 32-bit rows (CNT32)
             if (useV)
                 k_reduce_slabs<true><<<rg, IGD_TAIL_WG, last ? tailLds : 0, st>>>(Kt, db->d_slab, db->grid, fileN, (u64 *)d_hits + fileLo, (u64 *)d_total,

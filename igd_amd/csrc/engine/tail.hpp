@@ -473,7 +473,31 @@ __global__ __launch_bounds__(256) void k_exact_walk(SortK K, ScanArgs a, const i
     batch_tail<USE_V>(K, a, fixList, longList, heavyB, valves, a.out, nullptr, smem, gwave, gridDim.x * (blockDim.x >> 6), ctlv);
 }
 
-// slab rows -> int64 hits[] (+ batch total).  grid = (ceil(nFiles/IGD_TAIL_WG), IGD_REDUCE_GROUPS)
+// column_share: one wave's share of a column block of the slab -- rows first, first + step, ... of 64 consecutive files,
+// a file per lane, so that a row's segment is one coalesced wave load.  IGD_REDUCE_DEPTH rows are asked for before the
+// first is added (a row past the end is asked for as the round's first row and masked: a load behind a branch is a round
+// trip of its own, LABNOTES R5-12); 512 rows over IGD_REDUCE_SPLIT row shares of 16 waves are one such round.
+template <typename T>
+__device__ __forceinline__ u64 column_share(const T *__restrict__ slab, int rows, int nFiles, int file, int first, int step)
+{
+    u64 s = 0;
+    for (int g0 = first; g0 < rows; g0 += IGD_REDUCE_DEPTH * step) {
+        T v[IGD_REDUCE_DEPTH];
+#pragma unroll
+        for (int k = 0; k < IGD_REDUCE_DEPTH; k++) {
+            const int g = g0 + k * step;
+            v[k] = slab[(size_t)(g < rows ? g : g0) * nFiles + file];
+        }
+#pragma unroll
+        for (int k = 0; k < IGD_REDUCE_DEPTH; k++) s += g0 + k * step < rows ? (u64)v[k] : 0;
+    }
+    return s;
+}
+
+// slab rows -> int64 hits[] (+ batch total).  The first ceil(nFiles / 64) x IGD_REDUCE_SPLIT workgroups of the launch (in
+// the flat numbering the tail uses) each sum one row share of one column block of 64 files: 16 waves' partial sums meet
+// in LDS, after the tail, and every hits[f] gets IGD_REDUCE_SPLIT additions per batch.  The workgroups beyond are there
+// for the batch's tail only (see the launch).
 template <bool USE_V>
 __global__ __launch_bounds__(IGD_TAIL_WG) void k_reduce_slabs(SortK K, const u64 *__restrict__ slab, int rows, int nFiles,
                                                       u64 *__restrict__ hits, u64 *__restrict__ total,
@@ -483,47 +507,54 @@ __global__ __launch_bounds__(IGD_TAIL_WG) void k_reduce_slabs(SortK K, const u64
                                                       int rows32 /* != 0: igd_scan_sorted of epoch `rows32` wrote 32-bit rows (unless the batch went to the bucket path) */)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ u64 red[IGD_TAIL_WG / IGD_WAVE];
     constexpr int WPB = IGD_TAIL_WG / IGD_WAVE;           // waves per workgroup
+    __shared__ u64 part[WPB * IGD_WAVE];
     // the batch's control words, word i in lane i: one load, in flight together with the slab rows
     const int ctlv = (threadIdx.x & 63) < IGD_CTL_WORDS ? ctl[threadIdx.x & 63] : 0;
-    int f = blockIdx.x * IGD_TAIL_WG + threadIdx.x;
-    u64 s = 0;
-    if (f < nFiles && blockIdx.y < IGD_REDUCE_GROUPS) {  // (the workgroups beyond are there for the batch's tail only, see the launch)
-        // (both kinds of rows are read before the control words say which kind this batch left: the loads are in flight
-        // together, and a row of either kind lies inside the slab)
-        u64 s64 = 0;
-        unsigned long long s32 = 0;
-        if (rows32) {
-            const unsigned int *slab32 = (const unsigned int *)slab;
-            for (int g = blockIdx.y; g < rows; g += IGD_REDUCE_GROUPS) s32 += slab32[(size_t)g * nFiles + f];
-            if (__builtin_amdgcn_readlane(ctlv, CTL_UNSORTED) == rows32)   // the bucket path's batch: 64-bit rows
-                for (int g = blockIdx.y; g < rows; g += IGD_REDUCE_GROUPS) s64 += slab[(size_t)g * nFiles + f];
-            s = __builtin_amdgcn_readlane(ctlv, CTL_UNSORTED) == rows32 ? s64 : s32;
-        } else
-            for (int g = blockIdx.y; g < rows; g += IGD_REDUCE_GROUPS) s += slab[(size_t)g * nFiles + f];
-    }
-    // brokenIf != 0: the batch ran under IGD_HIP_FLAG_SORTED; if the device found it unsorted the
-    // scan kernel wrote no slab, so nothing may be added
-    if (valves >= 0) coverage_reset(K.db, wa.epoch, (blockIdx.y * gridDim.x + blockIdx.x) * WPB + (int)(threadIdx.x >> 6), gridDim.x * gridDim.y * WPB, ctlv);
-    if (brokenIf != 0 && __builtin_amdgcn_readlane(ctlv, CTL_UNSORTED) == brokenIf) return;
-    if (s) atomicAdd(&hits[f], s);
-    if (total) {
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            u64 t = 0;
-            for (int k = 0; k < WPB; k++) t += red[k];
-            if (t) atomicAdd(total, t);
-        }
-    }
-    if (valves < 0) return;                              // an earlier pass of a windowed batch: the tail rides in the last pass's launch
-    // ... and the batch's exact-walk list and skew valves (normally empty) ride in the same launch
     const int nb = gridDim.x * gridDim.y;
     const int bid = blockIdx.y * gridDim.x + blockIdx.x;
-    const int gwave = bid * WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    batch_tail<USE_V>(K, wa, fixList, longList, heavyB, valves, wa.out, total, smem, gwave, nb * WPB, ctlv);   // (wa.out: the caller's hits[]; `hits` is a window of it in a windowed batch)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const bool summing = bid < (nFiles + IGD_WAVE - 1) / IGD_WAVE * IGD_REDUCE_SPLIT;   // (the same in every wave of the workgroup)
+    const int f = bid / IGD_REDUCE_SPLIT * IGD_WAVE + lane;
+    if (summing) {
+        const int fc = f < nFiles ? f : nFiles - 1;      // (a lane past the files reads the last file's column and adds nothing)
+        const int first = bid % IGD_REDUCE_SPLIT + IGD_REDUCE_SPLIT * wave, step = IGD_REDUCE_SPLIT * WPB;
+        // (the 32-bit rows are read before the control words say which kind this batch left: the loads are in flight
+        // together, and a row of either kind lies inside the slab)
+        u64 s;
+        if (rows32) {
+            s = column_share((const unsigned int *)slab, rows, nFiles, fc, first, step);
+            if (__builtin_amdgcn_readlane(ctlv, CTL_UNSORTED) == rows32)   // the bucket path's batch: 64-bit rows
+                s = column_share(slab, rows, nFiles, fc, first, step);
+        } else
+            s = column_share(slab, rows, nFiles, fc, first, step);
+        part[wave * IGD_WAVE + lane] = f < nFiles ? s : 0;
+    }
+    if (valves >= 0) coverage_reset(K.db, wa.epoch, bid * WPB + wave, nb * WPB, ctlv);
+    // brokenIf != 0: the batch ran under IGD_HIP_FLAG_SORTED; if the device found it unsorted the
+    // scan kernel wrote no slab, so nothing may be added
+    const bool broken = brokenIf != 0 && __builtin_amdgcn_readlane(ctlv, CTL_UNSORTED) == brokenIf;
+    if (broken) return;                                  // (the same in every wave of the launch)
+    // ... and the batch's exact-walk list and skew valves (normally empty) ride in the same launch; an earlier pass of a
+    // windowed batch has none: the tail rides in the last pass's launch
+    if (valves >= 0)
+        batch_tail<USE_V>(K, wa, fixList, longList, heavyB, valves, wa.out, total, smem, bid * WPB + wave, nb * WPB, ctlv);   // (wa.out: the caller's hits[]; `hits` is a window of it in a windowed batch)
+    // The partial sums are added up LAST: the tail shares its work out over all waves of the launch in fixed shares, so a
+    // barrier in front of it that holds the 16 waves of every summing workgroup until the slowest has its rows makes the whole
+    // launch wait (10^6 queries inside 10 tiles: 74 -> 78 us); here every wave goes on as soon as its own rows are in.
+    if (summing) {
+        __syncthreads();
+        if (wave == 0) {
+            u64 t = 0;
+#pragma unroll
+            for (int k = 0; k < WPB; k++) t += part[k * IGD_WAVE + lane];
+            if (t) atomicAdd(&hits[f], t);               // (atomic: the other row shares, the exact walks and the valves add here too)
+            if (total) {
+                for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o);
+                if (lane == 0 && t) atomicAdd(total, t);
+            }
+        }
+    }
 }
 
 // without LDS counters the batch total is the growth of sum(hits): measured around the launch

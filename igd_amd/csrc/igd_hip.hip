@@ -86,9 +86,15 @@
 #define IGD_TAIL_WG 1024                     // ... in workgroups of 16 waves: what the long queries' work counts in a workgroup's LDS
                                              // leaves it as one global atomic per dataset, and 2048 workgroups of 4 waves made 3.9 x 10^6 of those
 #endif
-#ifndef IGD_REDUCE_GROUPS
-#define IGD_REDUCE_GROUPS 64                 // (32-bit slab rows: 6.2 us with 128 groups, 5.4 with 64, 6.4 with 32, 10.1 with 16)
+#ifndef IGD_REDUCE_SPLIT
+#define IGD_REDUCE_SPLIT 4                   // row shares per column block of 64 files in k_reduce_slabs = additions per hits[f] and batch
+                                             // (1900 files, 32-bit rows, the kernel by rocprofv3: 7.3 us with 1 share, 5.3 with 2, 4.8 with 4, 4.6 with 8,
+                                             // taken with the partial sums added up before the tail; 4 and 8 are within the run-to-run spread of each
+                                             // other and give the same step; adding up after the tail: 5.2 with 4)
 #endif
+static_assert(IGD_REDUCE_SPLIT >= 1 && IGD_REDUCE_SPLIT <= 32 && (IGD_REDUCE_SPLIT & (IGD_REDUCE_SPLIT - 1)) == 0, "IGD_REDUCE_SPLIT: a power of two, 1 .. 32");
+#define IGD_REDUCE_DEPTH (512 / (IGD_REDUCE_SPLIT * (IGD_TAIL_WG / IGD_WAVE)))   // rows a lane asks for at a time: all of a wave's, of a slab of 512
+static_assert(IGD_REDUCE_DEPTH >= 1, "IGD_REDUCE_DEPTH: column_share's loop would not advance");
 #define IGD_PIPE_EVENTS 16                   // profiling: launches whose whole pipeline (not just the scan kernel) is timed
 #define IGD_WINDOW_FILES 10240
 #define IGD_MAX_WINDOWS 16                   // passes over the files of a database with more files than LDS counters
