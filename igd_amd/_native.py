@@ -223,6 +223,15 @@ def hip():
         L.igd_hip_nearest_fused_grid.restype = C.c_int32
         L.igd_hip_nearest_grid.argtypes = [C.c_int64]
         L.igd_hip_nearest_grid.restype = C.c_int32
+        # values of the overlapping records: db, ichr, qs, qe, nq, op, v, count, agg / ..., set_off, nsets, op, v, n_hit, pairs,
+        # agg_sum / device pointers, ..., d_count, d_agg, stream
+        L.igd_hip_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]
+        L.igd_hip_map_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_map_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
+        L.igd_hip_map_grid.argtypes = [C.c_int64]
+        L.igd_hip_map_grid.restype = C.c_int32
         L.igd_hip_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_search_runs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -353,6 +362,13 @@ def _bind_core(L):
     L.igdc_nearest_sets_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.igdc_nearest_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    # values of the overlapping records on the host: db, map, ichr, qs, qe, nq, op, v, count, agg / ..., set_off, nsets, op, v,
+    # n_hit, pairs, agg_sum / n_hit, pairs, agg_sum, n, op, mean_region, mean_pair
+    L.igdc_map_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_void_p,
+                                C.c_void_p]
+    L.igdc_map_sets_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
+    L.igdc_map_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
     # permutation null of the distances on the host: db, map, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within,
     # n_overlap, sum_dist / n_within, sum_dist, nperm, ncols, the twelve outputs
     L.igdc_permute_nearest_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,

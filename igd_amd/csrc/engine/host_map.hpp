@@ -1,0 +1,199 @@
+// engine/host_map.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
+// igd_hip_map / igd_hip_map_dev / igd_hip_map_sets: the values of the overlapping records per region and dataset (map_dev.hpp)
+// ------------------------------------------------------------------------------------------
+// The shape of host_nearest.hpp.  The device form takes one engine batch of resident regions and writes resident rows: one
+// launch (the wide form: fills of the rows before it and, but for SUM, igd_map_rowfix behind it), asynchronous on the caller's
+// stream.  The host form takes host arrays in CHUNKS of at most igd_hip_max_batch() regions AND at most IGD_MAP_ROW_BYTES of
+// device rows (4 nFiles bytes per region under COUNT, 12 nFiles otherwise: 22.8 KB at 1 900 files, 11 700 regions per chunk);
+// per chunk the regions go to the device through the staging buffers of igd_hip_search, the device form runs on the engine's
+// stream and the rows come back into the caller's arrays at their place.
+// The sets form takes GROUPS of whole sets whose three result rows (3 x nFiles x 8 bytes per set) fit sets_row_bytes(); the
+// regions of a group go through in the same chunks -- a set may be cut by a chunk, its statistics are sums over regions -- and
+// per chunk igd_map_reduce adds the rows into the group's three resident matrices, by a slice table cut here: a slice is at
+// most IGD_MAP_SLICE regions of one set.  The rows never leave the device; the matrices are copied out once per group.  Under
+// COUNT there are no agg rows at all: agg_sum is summed from the counts.
+// The image is slice_image(db, IGD_HIP_RULE_FLAT, v): the re-tiled copy when there is one, visited under rule FLAT.
+#define IGD_MAP_ROW_BYTES ((int64_t)256 << 20)       // device rows of one chunk (IGD_NEAREST_ROW_BYTES)
+#define IGD_MAP_SLICE 256                            // regions per slice of igd_map_reduce: 64 per wave
+#define IGD_MAP_REDUCE_WGS 16384                     // igd_map_reduce: about this many workgroups per launch (64 per CU)
+
+// The TEST-ONLY variable IGD_HIP_MAP_ROW_BYTES (read once per process, as IGD_HIP_MAX_BATCH) lowers the budget so that small
+// fixtures cross the row seam.
+static int64_t map_row_bytes(void)
+{
+    static const int64_t m = env_positive("IGD_HIP_MAP_ROW_BYTES", IGD_MAP_ROW_BYTES);
+    return m;
+}
+
+// workgroups igd_map_rows is launched with for nq regions (each of IGD_SETS_WG / IGD_WAVE waves; a wave meets a second region
+// only when nq exceeds the grid's waves)
+extern "C" int32_t igd_hip_map_grid(int64_t nq) { return items_grid(nq, IGD_SETS_WG / IGD_WAVE); }
+
+// regions per chunk of the host forms
+static int64_t map_step(int64_t nF, bool withAgg)
+{
+    const int64_t byRows = map_row_bytes() / ((nF > 0 ? nF : 1) * (withAgg ? 12 : 4));
+    const int64_t step = max_batch();
+    return byRows < step ? (byRows < 1 ? 1 : byRows) : step;
+}
+
+// an unknown op, or an op that reads values on a database without them
+static int map_op_bad(const char *who, const igd_hip_db *db, int op)
+{
+    if (!igd_hip_map_op_valid(op)) {
+        snprintf(g_err, sizeof g_err, "%s: no such op %d", who, op);
+        return 1;
+    }
+    if (db && op != IGD_HIP_MAP_COUNT && db->gType != 1) {
+        snprintf(g_err, sizeof g_err, "%s: sum, min and max need a database with values (gType 1)", who);
+        return 1;
+    }
+    return 0;
+}
+
+template <bool V, bool L>
+static void map_launch(int op, int grid, size_t ldsB, hipStream_t st, const DbView &view, const int32_t *d_ichr, const int32_t *d_qs,
+                       const int32_t *d_qe, int n, int krule, int v, int32_t *d_count, int64_t *d_agg)
+{
+    switch (op) {
+    case IGD_HIP_MAP_COUNT: igd_map_rows<V, IGD_HIP_MAP_COUNT, L><<<grid, IGD_SETS_WG, ldsB, st>>>(view, d_ichr, d_qs, d_qe, n, krule, v, d_count, d_agg); break;
+    case IGD_HIP_MAP_SUM: igd_map_rows<V, IGD_HIP_MAP_SUM, L><<<grid, IGD_SETS_WG, ldsB, st>>>(view, d_ichr, d_qs, d_qe, n, krule, v, d_count, d_agg); break;
+    case IGD_HIP_MAP_MIN: igd_map_rows<V, IGD_HIP_MAP_MIN, L><<<grid, IGD_SETS_WG, ldsB, st>>>(view, d_ichr, d_qs, d_qe, n, krule, v, d_count, d_agg); break;
+    default: igd_map_rows<V, IGD_HIP_MAP_MAX, L><<<grid, IGD_SETS_WG, ldsB, st>>>(view, d_ichr, d_qs, d_qe, n, krule, v, d_count, d_agg); break;
+    }
+}
+
+extern "C" int igd_hip_map_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq, int op, int32_t v,
+                               int32_t *d_count, int64_t *d_agg, void *stream)
+{
+    if (map_op_bad("igd_hip_map_dev", db, op)) return IGD_HIP_ERR_ARG;
+    if (!db || nq < 0 || nq > max_batch() ||
+        (nq > 0 && (!d_ichr || !d_qs || !d_qe || (db->nFiles > 0 && (!d_count || (!d_agg && op != IGD_HIP_MAP_COUNT)))))) {
+        snprintf(g_err, sizeof g_err, "igd_hip_map_dev: bad argument (batch limit %lld regions)", (long long)max_batch());
+        return IGD_HIP_ERR_ARG;
+    }
+    const int64_t nF = db->nFiles;
+    if (nq == 0 || nF == 0) return IGD_HIP_OK;           // (rows of no words)
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = stream ? (hipStream_t)stream : db->stream;
+    const SliceImage im = slice_image(db, IGD_HIP_RULE_FLAT, v);
+    const bool lds = nF <= map_lds_files(op);
+    const int grid = igd_hip_map_grid(nq);
+    const size_t ldsB = lds ? (size_t)((IGD_SETS_WG / IGD_WAVE) * nF) * (size_t)map_lds_file_bytes(op) : 0;
+    const size_t cells = (size_t)(nq * nF);
+    if (!lds) {                                          // the wide form folds into rows of "nothing yet"
+        HIPCHK(hipMemsetAsync(d_count, 0, cells * 4, st));
+        if (op != IGD_HIP_MAP_COUNT) HIPCHK(hipMemsetAsync(d_agg, op == IGD_HIP_MAP_MIN ? 0x7f : op == IGD_HIP_MAP_MAX ? 0x80 : 0, cells * 8, st));
+    }
+    with_flags(im.useV, lds, [&](auto V, auto L) {
+        map_launch<V(), L()>(op, grid, ldsB, st, im.view, d_ichr, d_qs, d_qe, (int)nq, im.krule, v, d_count, d_agg);
+    });
+    HIPCHK(hipGetLastError());
+    if (!lds && d_agg && op != IGD_HIP_MAP_SUM) {
+        const int fg = (int)items_grid((int64_t)cells, 4 * IGD_SETS_WG);
+        if (op == IGD_HIP_MAP_COUNT) igd_map_rowfix<IGD_HIP_MAP_COUNT><<<fg, IGD_SETS_WG, 0, st>>>(d_count, d_agg, cells);
+        else igd_map_rowfix<IGD_HIP_MAP_MIN><<<fg, IGD_SETS_WG, 0, st>>>(d_count, d_agg, cells);
+        HIPCHK(hipGetLastError());
+    }
+    return IGD_HIP_OK;
+}
+
+// the count and agg rows of one chunk of regions
+static int ensure_map_ws(igd_hip_db *db, int64_t cells, bool withAgg)
+{
+    int rc = dev_grow(db, &db->d_mpCount, &db->mpCountCap, cells);
+    if (rc == IGD_HIP_OK && withAgg) rc = dev_grow(db, &db->d_mpAgg, &db->mpAggCap, cells);
+    return rc;
+}
+
+extern "C" int igd_hip_map(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int op, int32_t v,
+                           int32_t *count, int64_t *agg)
+{
+    if (map_op_bad("igd_hip_map", db, op)) return IGD_HIP_ERR_ARG;
+    if (!db || nq < 0 || (nq > 0 && (!ichr || !qs || !qe || (db->nFiles > 0 && (!count || (!agg && op != IGD_HIP_MAP_COUNT)))))) {
+        snprintf(g_err, sizeof g_err, "igd_hip_map: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    const int64_t nF = db->nFiles;
+    if (nq == 0 || nF == 0) return IGD_HIP_OK;
+    const bool withAgg = agg != nullptr;
+    const int64_t step = map_step(nF, withAgg);
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    for (int64_t c0 = 0; c0 < nq; c0 += step) {
+        const int64_t m = nq - c0 < step ? nq - c0 : step;
+        int rc = ensure_map_ws(db, m * nF, withAgg);
+        if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
+        if (rc == IGD_HIP_OK) rc = igd_hip_map_dev(db, db->d_qc, db->d_qs, db->d_qe, m, op, v, db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, st);
+        if (rc != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemcpyAsync(count + c0 * nF, db->d_mpCount, (size_t)(m * nF) * 4, hipMemcpyDeviceToHost, st));
+        if (withAgg) HIPCHK(hipMemcpyAsync(agg + c0 * nF, db->d_mpAgg, (size_t)(m * nF) * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+    }
+    return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_map_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                                int32_t nsets, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
+{
+    if (map_op_bad("igd_hip_map_sets", db, op)) return IGD_HIP_ERR_ARG;
+    if (!db || nsets < 0 || (nsets > 0 && !set_off)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_map_sets: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nsets == 0) return IGD_HIP_OK;
+    int rc = sets_check("igd_hip_map_sets", ichr, qs, qe, set_off, nsets);
+    if (rc != IGD_HIP_OK) return rc;
+    const int64_t nF = db->nFiles;
+    int64_t *outs[3] = {n_hit, pairs, agg_sum};
+    if (set_off[nsets] == 0 || nF == 0) {                // every statistic is 0: no region, or no dataset
+        for (int64_t *o : outs) if (o) memset(o, 0, (size_t)nsets * (size_t)nF * 8);
+        return IGD_HIP_OK;
+    }
+    const bool withAgg = op != IGD_HIP_MAP_COUNT;
+    const int64_t step = map_step(nF, withAgg);
+    const int64_t rowCap = sets_row_bytes() / (3 * nF * 8) > 0 ? sets_row_bytes() / (3 * nF * 8) : 1;
+    const int gx = (int)((nF + IGD_WAVE - 1) / IGD_WAVE);
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    std::vector<SetSlice> slices;
+    for (int32_t k0 = 0; k0 < nsets;) {
+        // one group: sets [k0, k1), regions [set_off[k0], set_off[k1])
+        const int32_t k1 = (int32_t)(nsets - k0 < rowCap ? nsets : k0 + rowCap);
+        const int64_t rows = k1 - k0, matWords = rows * nF;
+        if ((rc = dev_grow(db, &db->d_mpStat, &db->mpStatCap, 3 * matWords)) != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemsetAsync(db->d_mpStat, 0, (size_t)(3 * matWords) * 8, st));
+        int32_t k = k0;
+        for (int64_t c0 = set_off[k0]; c0 < set_off[k1]; c0 += step) {
+            const int64_t m = set_off[k1] - c0 < step ? set_off[k1] - c0 : step;
+            // the chunk's part of every set it meets, in slices of at most IGD_MAP_SLICE regions
+            slices.clear();
+            while (set_off[k + 1] <= c0) k++;
+            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++) {
+                const int64_t a0 = set_off[j] > c0 ? set_off[j] : c0, b0 = set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m;
+                for (int64_t a = a0; a < b0; a += IGD_MAP_SLICE)
+                    slices.push_back(SetSlice{j - k0, (int32_t)(a - c0), (int32_t)((a + IGD_MAP_SLICE < b0 ? a + IGD_MAP_SLICE : b0) - c0), 0});
+            }
+            const int ns = (int)slices.size();
+            rc = ensure_map_ws(db, m * nF, withAgg);
+            if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_mpSlices, &db->mpSliceCap, (int64_t)ns);
+            if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
+            if (rc == IGD_HIP_OK) rc = igd_hip_map_dev(db, db->d_qc, db->d_qs, db->d_qe, m, op, v, db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, st);
+            if (rc != IGD_HIP_OK) return rc;
+            HIPCHK(hipMemcpyAsync(db->d_mpSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+            int gy = IGD_MAP_REDUCE_WGS / gx;
+            gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
+            igd_map_reduce<<<dim3((unsigned)gx, (unsigned)gy), IGD_SETS_WG, 0, st>>>(db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, (int)nF, db->d_mpSlices,
+                                                                                  ns, (u64 *)db->d_mpStat, matWords);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
+        }
+        for (int i = 0; i < 3; i++)
+            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * nF, db->d_mpStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        k0 = k1;
+    }
+    return IGD_HIP_OK;
+}

@@ -41,7 +41,9 @@ __device__ __forceinline__ bool min_ov_pair(int need, int ppmR, int qs, int qe, 
 // together, the predicate above with its USE_V (value >= v) and OV (min_ov_pair under `need`, `mo`) terms, then
 // step(s0, e0, x0, h0, s1, e1, x1, h1) -- start, end, idx and "counted" of this lane's two records; a lane past the tile's end
 // has h = false -- and the early exit.  Everything but `lane` and what step() does per lane is wave-uniform.
-template <bool USE_V, bool OV, typename F>
+// VAL (igd_map_rows): step(s0, e0, x0, h0, v0, s1, e1, x1, h1, v1) also receives the lane's two value words; they are loaded when
+// USE_V or LOADV is set and are 0 otherwise.  VAL = LOADV = false is the walk as it was, instruction for instruction.
+template <bool USE_V, bool OV, bool VAL = false, bool LOADV = false, typename F>
 __device__ __forceinline__ void walk_query_tiles(const DbView &db, int lane, int nF, int qs, int qe, int gt0, int ntl, int v, int need,
                                                  const MinOv &mo, F &&step)
 {
@@ -62,9 +64,12 @@ __device__ __forceinline__ void walk_query_tiles(const DbView &db, int lane, int
             const int x1 = ok1 ? db.idx[toff + j] : -1;
             bool h0 = (s0 >= lob) & (s0 < qe) & (e0 > qs) & ((unsigned)x0 < (unsigned)nF);
             bool h1 = (s1 >= lob) & (s1 < qe) & (e1 > qs) & ((unsigned)x1 < (unsigned)nF);
+            int v0 = 0, v1 = 0;
+            if (USE_V || LOADV) {
+                v0 = ok0 ? db.value[toff + i] : INT_MIN;
+                v1 = ok1 ? db.value[toff + j] : INT_MIN;
+            }
             if (USE_V) {
-                const int v0 = ok0 ? db.value[toff + i] : INT_MIN;
-                const int v1 = ok1 ? db.value[toff + j] : INT_MIN;
                 h0 = h0 & (v0 >= v);
                 h1 = h1 & (v1 >= v);
             }
@@ -72,7 +77,8 @@ __device__ __forceinline__ void walk_query_tiles(const DbView &db, int lane, int
                 h0 = h0 & min_ov_pair(need, mo.ppm_record, qs, qe, s0, e0);
                 h1 = h1 & min_ov_pair(need, mo.ppm_record, qs, qe, s1, e1);
             }
-            step(s0, e0, x0, h0, s1, e1, x1, h1);
+            if constexpr (VAL) step(s0, e0, x0, h0, v0, s1, e1, x1, h1, v1);
+            else step(s0, e0, x0, h0, s1, e1, x1, h1);
             // records are ordered by start: a step whose largest start is >= qe ends the tile
             if (__builtin_amdgcn_readlane(s1, 63) >= qe) break;
         }

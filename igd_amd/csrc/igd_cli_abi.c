@@ -1548,6 +1548,82 @@ static void nearest_files(char **paths, int32_t n, int32_t v, int setLines, int3
     free(q); free(ichr); free(qs); free(qe); free(off); free(st3); free(mean);
 }
 
+/* ------------------------------- `igd search -q F -V <op>` / `-Q <list> -V <op>` ------- */
+/* Values of the overlapping records per dataset (include/igd_hip.h has the definitions): per database file the query regions
+ * with a counted record (n_hit), the counted (region, record) pairs (pairs) and a mean -- of the per-region count, sum, minimum
+ * or maximum over the regions with a hit (mean_region) or, for `mean`, of the values over the pairs (op SUM, mean_pair); `NA`
+ * where the divisor is 0.  One line per dataset, then the pairs of all datasets and the datasets with a hit.  -v keeps the
+ * records with value >= v, as everywhere; there is no tile rule.  Routing as `-u` and `-N`: at most igdc_host_limit() regions
+ * in all are answered on the host (igdc_map_sets_host), more by ONE igd_hip_map_sets call on one device.  `paths` holds one
+ * query file (`-q`, no "Query set" lines) or the files of a list (`-Q`). */
+static const char *const MAP_OPS[] = {"count", "sum", "min", "max", "mean"};
+static const int MAP_OP_OF[] = {IGD_HIP_MAP_COUNT, IGD_HIP_MAP_SUM, IGD_HIP_MAP_MIN, IGD_HIP_MAP_MAX, IGD_HIP_MAP_SUM};
+
+static void map_files(char **paths, int32_t n, int32_t v, int setLines, int opName)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int op = MAP_OP_OF[opName], perPair = opName == 4;
+    const int32_t nfiles = IGD->nFiles;
+    const size_t nC = (size_t)nfiles;
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    int64_t *st3 = (int64_t *)calloc(3 * (size_t)(n ? n : 1) * nC + 1, sizeof(int64_t));
+    double *mean = (double *)malloc(sizeof(double) * (2 * (size_t)(n ? n : 1) * nC + 1));
+    int64_t *nh = st3, *np = st3 + (size_t)n * nC, *sa = st3 + 2 * (size_t)n * nC;
+    double *meanPair = mean + (size_t)n * nC;
+    off[0] = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (q[k].n) {
+            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+        }
+        off[k + 1] = off[k] + q[k].n;
+    }
+    int onHost = 0;
+    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
+    if (hm) {
+        double t0 = now_s();
+        onHost = igdc_map_sets_host(g_core, hm, ichr, qs, qe, off, n, op, ev, nh, np, sa) == 0;
+        igdc_map_close(hm);
+        if (onHost) phase("values of the overlapping records on the host (small files)", &t0);
+    }
+    if (!onHost && nq > 0) {                          /* (after a read error too: the engine reads the file its own way) */
+        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
+        double t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_map_sets(dev, ichr, qs, qe, off, n, op, ev, nh, np, sa);
+            if (rc != IGD_HIP_OK) engine_failed("map", rc);
+            phase("values of the overlapping records of the query sets (H2D + kernels + D2H)", &t0);
+        }
+    }
+    if (!g_fail_rc) igdc_map_summary(nh, np, sa, (int64_t)n * (int64_t)nC, op, mean, meanPair);
+    for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
+        const size_t o = (size_t)k * nC;
+        int64_t all = 0, withHit = 0;
+        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        printf("index\tn_hit\tpairs\tmean_%s\tFile\n", MAP_OPS[opName]);
+        for (int32_t i = 0; i < nfiles; i++) {
+            printf("%d\t%lld\t%lld", (int)i, (long long)nh[o + i], (long long)np[o + i]);
+            print_mean("\t", perPair ? np[o + i] : nh[o + i], perPair ? meanPair[o + i] : mean[o + i], "\t");
+            printf("%s\n", IGD->finfo[i].fileName);
+            all += np[o + i];
+            withHit += nh[o + i] > 0;
+        }
+        printf("Pairs: %lld; datasets with a hit: %lld of %d\n", (long long)all, (long long)withHit, (int)nfiles);
+    }
+    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    free(q); free(ichr); free(qs); free(qe); free(off); free(st3); free(mean);
+}
+
 /* ------------------------------- `igd search -q F -P N -g genome -D <bp>` --------------- */
 /* Permutation null of the nearest-record distances (include/igd_hip.h: igd_hip_permute_nearest; igd_core.h:
  * igdc_perm_nearest_summary has the columns): "are my regions closer to dataset f than chance".  The header
@@ -1644,6 +1720,9 @@ static int usage_search(void)
             "                               with at most six places.  With -q or -Q alone, -u, -U [-R] and -P\n"
             "    -N <bp>                    with -q or -Q: per dataset, the query regions with a record within <bp> base pairs (0 to\n"
             "                               1073741824), those that overlap one, and the mean distance to the nearest record\n"
+            "    -V <op>                    with -q or -Q: per dataset, the query regions with an overlapping record, the overlapping\n"
+            "                               (region, record) pairs and the mean over those regions of the records' count, sum, min\n"
+            "                               or max of the value column; mean: the mean value over the pairs\n"
             "    -D <bp>                    with -P: the null of the distances instead -- per dataset the regions with a record within\n"
             "                               <bp> base pairs (0 to 1073741824) and their mean distance to the nearest one, each\n"
             "                               placed among the permuted sets' (mean, sd, z, one-sided p)\n"
@@ -1695,6 +1774,7 @@ int igd_search(int argc, char **argv)                                        /* 
     char *permArg = NULL, *genomeName = NULL, *seedArg = NULL, *pmodeArg = NULL;      /* -P, -g, -S, -M (see permute_file) */
     char *nearArg = NULL;                                                             /* -N (see nearest_files) */
     char *distArg = NULL;                                                             /* -D (see permute_nearest_table) */
+    char *mapArg = NULL;                                                              /* -V (see map_files) */
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
         const char *a = argv[i];
@@ -1741,6 +1821,10 @@ int igd_search(int argc, char **argv)                                        /* 
             if (i + 1 >= argc) { printf("No window.\n"); return EX_OK; }
             nearArg = argv[i + 1];
             i++;                                      /* (the window is not an option: "-N -5" is a refused window) */
+        } else if (strcmp(a, "-V") == 0) {            /* (not the reference's: values of the overlapping records, see map_files) */
+            if (i + 1 >= argc) { printf("Not supported: -V without an op (count, sum, min, max or mean)\n"); return EX_USAGE; }
+            mapArg = argv[i + 1];
+            i++;                                      /* (the op is not an option) */
         } else if (strcmp(a, "-D") == 0) {            /* (not the reference's: -P on the distances, see permute_nearest_table) */
             if (i + 1 >= argc) { printf("Not supported: -D without a window\n"); return EX_USAGE; }
             distArg = argv[i + 1];
@@ -1775,6 +1859,26 @@ int igd_search(int argc, char **argv)                                        /* 
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    int mapOp = -1;                                                           /* -V: every refusal is a usage error */
+    if (mapArg) {
+        for (int k = 0; k < 5; k++) if (strcmp(mapArg, MAP_OPS[k]) == 0) mapOp = k;
+        const char *why = NULL;
+        if (uniq || bp || memb || uniName || ranks || restricted || cooc || permArg || distArg || nearArg || full || other || minov)
+            why = "-V together with -u, -b, -w, -U, -R, -X, -C, -P, -D, -N, -f, -m, -s, -r, -O, -A or -B";
+        else if (mode != 1 && !listName) why = "-V without -q or -Q";
+        if (why) {
+            printf("Not supported: %s\n", why);
+            return EX_USAGE;
+        }
+        if (mapOp < 0) {
+            printf("Not supported: -V %s (count, sum, min, max or mean)\n", mapArg);
+            return EX_USAGE;
+        }
+        if (mapOp != 0 && IGD->gType == 0) {
+            printf("Not supported: -V %s on a database without values (gType 0); -V count works there\n", mapArg);
+            return EX_USAGE;
+        }
+    }
     int32_t distW = -1;                                                       /* -D: every refusal is a usage error */
     if (distArg) {
         char *end = NULL, *pend = NULL;
@@ -1823,6 +1927,14 @@ int igd_search(int argc, char **argv)                                        /* 
     if (!permArg && (genomeName || seedArg || pmodeArg)) {
         printf("Not supported: -g, -S or -M without -P\n");
         return EX_OK;
+    } else if (mapArg && mode == 1) {
+        map_files(&qfName, 1, v, 0, mapOp);
+    } else if (mapArg) {
+        int32_t n = 0;
+        char **paths = read_list(listName, &n);
+        if (n >= 0) map_files(paths, n, v, 1, mapOp);
+        for (int32_t k = 0; k < n; k++) free(paths[k]);
+        free(paths);
     } else if (nearArg && mode == 1) {
         nearest_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10));
     } else if (nearArg) {

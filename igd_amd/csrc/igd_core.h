@@ -211,6 +211,21 @@ int igdc_nearest_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *
                            int64_t *sum_dist);
 /* mean[i] = sum_dist[i] / n_within[i] as a double, NaN where n_within[i] = 0.  Needs no database.  0, or -1 for a missing array. */
 int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t n, double *mean);
+/* Values of the overlapping records per region and dataset (what igd_hip_map and igd_hip_map_sets compute; include/igd_hip.h has
+ * the definitions and the ops): count (int32[nq * nFiles]) and agg (int64[nq * nFiles]; under op COUNT it may be NULL and
+ * receives the counts when it is not); n_hit, pairs, agg_sum (int64[nsets * nFiles], each may be NULL).  Every output is
+ * OVERWRITTEN, every word of it.  Each region visits its tiles under rule FLAT with the prefix skip, as igdc_nearest_host at
+ * W = 0; threads run over the regions.  0 on success; -1 for a missing array, a bad set_off, an unknown op or a value op on a
+ * gType 0 database (nothing written), or when a tile could not be read (outputs undefined). */
+int igdc_map_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int op,
+                  int32_t v, int32_t *count, int64_t *agg);
+int igdc_map_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                       const int64_t *set_off, int32_t nsets, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum);
+/* mean_region[i] = agg_sum[i] / n_hit[i] and, under op SUM, mean_pair[i] = agg_sum[i] / pairs[i] (the mean value of a counted
+ * record; NaN under the other ops), as doubles, NaN where the divisor is 0.  mean_pair may be NULL.  Needs no database.  0, or
+ * -1 for a missing array or an unknown op. */
+int igdc_map_summary(const int64_t *n_hit, const int64_t *pairs, const int64_t *agg_sum, int64_t n, int op, double *mean_region,
+                     double *mean_pair);
 /* Permutation null of the nearest-record distances on the host (what igd_hip_permute_nearest computes; include/igd_hip.h): each
  * output is int64[(nperm + 1) * (nFiles + 1)] (may be NULL), row 0 the set as given, row p + 1 permutation p of
  * igdc_permute_regions_host's generator counted as igdc_nearest_sets_host counts a set; threads run over the rows.  0; -1 for a

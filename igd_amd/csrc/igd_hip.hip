@@ -341,6 +341,12 @@ struct igd_hip_db {
     int64_t *d_nrStat;
     struct SetSlice *d_nrSlices;
     int64_t nrDistCap, nrMinCap, nrStatCap, nrSliceCap;
+    // igd_hip_map / igd_hip_map_sets (host_map.hpp): the count and agg rows of one chunk of regions, the three matrices of one
+    // group of sets (64-bit words) and the slice table of igd_map_reduce
+    int32_t *d_mpCount;
+    int64_t *d_mpAgg, *d_mpStat;
+    struct SetSlice *d_mpSlices;
+    int64_t mpCountCap, mpAggCap, mpStatCap, mpSliceCap;
     hipStream_t stream;
     // profiling
     std::vector<hipEvent_t> ev;   // 4 per launch: pipeline start, scan start, scan stop, pipeline stop
@@ -377,6 +383,7 @@ struct igd_hip_db {
 #include "engine/permute_dev.hpp"     // igd_permute_regions, igd_perm_stats: shifted / shuffled region sets, column statistics of a row matrix -- permutation null
 #include "engine/nearest_dev.hpp"     // igd_nearest_rows, igd_nearest_reduce: the same walk over a widened interval, one distance row per region -- nearest record per dataset
 #include "engine/nearest_fused_dev.hpp" // igd_nearest_slices: the same walk and table, folded into per-slice LDS accumulators -- the set statistics without the rows
+#include "engine/map_dev.hpp"         // igd_map_rows, igd_map_reduce: the same walk with the value words, count and sum / min / max rows per region -- values of the overlapping records
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -395,6 +402,7 @@ struct igd_hip_db {
 #include "engine/host_permute.hpp"    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: chunks of permutations, rows stay resident
 #include "engine/host_nearest.hpp"    // igd_hip_nearest / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
 #include "engine/host_permute_nearest.hpp" // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: one fused launch per chunk, the null distribution of the distance statistics
+#include "engine/host_map.hpp"        // igd_hip_map / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

@@ -221,6 +221,23 @@ int igd_hip_nearest_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
     return fn ? fn(db, ichr, qs, qe, set_off, nsets, window, v, n_within, n_overlap, sum_dist) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_map(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int op, int32_t v, int32_t *count,
+                int64_t *agg)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, int, int32_t, int32_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_map");
+    return fn ? fn(db, ichr, qs, qe, nq, op, v, count, agg) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_map_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                     int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int, int32_t, int64_t *,
+                        int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_map_sets");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, op, v, n_hit, pairs, agg_sum) : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
                              int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, int32_t v, int rule,
                              int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio, int64_t *clamped, int64_t *nhit,

@@ -1262,6 +1262,151 @@ int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64
     return 0;
 }
 
+/* ---- values of the overlapping records per region and dataset (include/igd_hip.h has the definitions) --------------------
+ * One region: its rows are set to 0 and the tiles of igd_hip_nearest_widen(qs, qe, 0) are visited as one_region_nearest visits
+ * them -- bisection for the last start < qe, backwards while end > qs, in later tiles only down to the tile's start (the prefix
+ * skip) -- and every counted record adds 1 to count[idx] and folds its value into agg[idx] (NULL under COUNT: nothing). */
+static inline void one_region_map(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int op,
+                                  int32_t v, int use_v, int32_t *count, int64_t *agg)
+{
+    const int32_t nf = db->nFiles;
+    for (int32_t f = 0; f < nf; f++) count[f] = 0;
+    if (agg) for (int32_t f = 0; f < nf; f++) agg[f] = 0;
+    if (ichr < 0 || ichr >= db->nCtg) return;
+    int32_t ws, we;
+    igd_hip_nearest_widen(qs, qe, 0, &ws, &we);
+    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
+    const int32_t n1 = ws / nbp;
+    int32_t n2 = (int32_t)((uint32_t)we - 1u) / nbp;
+    if (n1 < 0 || n1 > mT) return;                                         /* (no record ends behind the contig's last tile) */
+    if (n2 > mT) n2 = mT;
+    const int w = db->gType == 0 ? 3 : 4;
+    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
+        const int32_t cnt = db->nCnt[ichr][j];
+        if (cnt <= 0) continue;
+        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
+        if (!rec) return;
+        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
+        for (int32_t i = below(rec, w, cnt, we) - 1; i >= 0; i--) {
+            const int32_t *r = rec + (size_t)i * (size_t)w;
+            if ((int64_t)r[1] < lob) break;
+            if (r[2] > ws && (!use_v || r[3] >= v)) {
+                if (r[0] < 0 || r[0] >= nf) continue;
+                const int32_t f = r[0];
+                if (op != IGD_HIP_MAP_COUNT) {
+                    const int64_t val = r[3];
+                    if (op == IGD_HIP_MAP_SUM) agg[f] = (int64_t)((uint64_t)agg[f] + (uint64_t)val);
+                    else if (count[f] == 0 || (op == IGD_HIP_MAP_MIN ? val < agg[f] : val > agg[f])) agg[f] = val;
+                }
+                count[f]++;
+            }
+        }
+    }
+    if (agg && op == IGD_HIP_MAP_COUNT) for (int32_t f = 0; f < nf; f++) agg[f] = count[f];
+}
+
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe;
+    int64_t lo, hi;
+    int op; int32_t v; int use_v;
+    int32_t *count; int64_t *agg;
+    int io_failed;
+} map_job;
+
+static void *map_run(void *arg)
+{
+    map_job *J = (map_job *)arg;
+    tilebuf tb;
+    memset(&tb, 0, sizeof tb);
+    tb.ichr = -1;
+    const size_t nf = (size_t)J->db->nFiles;
+    for (int64_t i = J->lo; i < J->hi; i++)
+        one_region_map(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->op, J->v, J->use_v, J->count + (size_t)i * nf,
+                       J->agg ? J->agg + (size_t)i * nf : NULL);
+    J->io_failed = tb.failed;
+    free(tb.buf);
+    return NULL;
+}
+
+static int map_op_ok(const igdc_db *db, int op) { return igd_hip_map_op_valid(op) && (op == IGD_HIP_MAP_COUNT || db->gType == 1); }
+
+int igdc_map_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int op,
+                  int32_t v, int32_t *count, int64_t *agg)
+{
+    if (!db || !m || nq < 0 || !map_op_ok(db, op)) return -1;
+    if (nq > 0 && (!ichr || !qs || !qe || (db->nFiles > 0 && (!count || (!agg && op != IGD_HIP_MAP_COUNT))))) return -1;
+    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+    const int T = host_threads(nq);
+    map_job job[64];
+    pthread_t th[64];
+    int started[64];
+    int32_t none = 0;                        /* (a database without files: rows of no words) */
+    /* rows are disjoint per region: every thread writes its regions' rows straight into the caller's */
+    for (int k = 0; k < T; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
+        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
+        job[k].op = op; job[k].v = v; job[k].use_v = use_v;
+        job[k].count = count ? count : &none; job[k].agg = db->nFiles > 0 ? agg : NULL;
+    }
+    for (int k = 1; k < T; k++) {
+        started[k] = pthread_create(&th[k], NULL, map_run, &job[k]) == 0;
+        if (!started[k]) map_run(&job[k]);
+    }
+    map_run(&job[0]);
+    for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
+    int bad = 0;
+    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
+    return bad ? -1 : 0;
+}
+
+#define MAP_HOST_ROW_BYTES ((int64_t)32 << 20)       /* igdc_map_sets_host: count and agg rows of one chunk of regions */
+int igdc_map_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                       const int64_t *set_off, int32_t nsets, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
+{
+    if (!db || !m || nsets < 0 || !map_op_ok(db, op) || (nsets > 0 && (!set_off || set_off[0] != 0))) return -1;
+    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
+    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) return -1;
+    const int64_t nf = db->nFiles, nq = nsets > 0 ? set_off[nsets] : 0;
+    int64_t chunk = MAP_HOST_ROW_BYTES / (12 * (nf > 0 ? nf : 1));
+    chunk = chunk < 1 ? 1 : chunk > nq ? nq : chunk;
+    int32_t *count = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk * nf + 1));
+    int64_t *agg = (int64_t *)malloc(sizeof(int64_t) * (size_t)(chunk * nf + 1));
+    if (!count || !agg) { free(count); free(agg); return -1; }
+    int64_t *outs[3] = {n_hit, pairs, agg_sum};
+    for (int i = 0; i < 3; i++) if (outs[i]) memset(outs[i], 0, sizeof(int64_t) * (size_t)nsets * (size_t)nf);
+    int rc = 0;
+    int32_t k = 0;
+    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += chunk) {
+        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
+        rc = igdc_map_host(db, m, ichr + c0, qs + c0, qe + c0, n, op, v, count, agg);
+        for (int64_t i = 0; i < n && rc == 0; i++) {
+            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
+            const size_t r = (size_t)i * (size_t)nf, o = (size_t)k * (size_t)nf;
+            for (int64_t f = 0; f < nf; f++) {
+                if (count[r + f] == 0) continue;
+                if (n_hit) n_hit[o + f]++;
+                if (pairs) pairs[o + f] += count[r + f];
+                if (agg_sum) agg_sum[o + f] = (int64_t)((uint64_t)agg_sum[o + f] + (uint64_t)agg[r + f]);
+            }
+        }
+    }
+    free(count); free(agg);
+    return rc;
+}
+
+int igdc_map_summary(const int64_t *n_hit, const int64_t *pairs, const int64_t *agg_sum, int64_t n, int op, double *mean_region,
+                     double *mean_pair)
+{
+    if (n < 0 || !igd_hip_map_op_valid(op) || (n > 0 && (!n_hit || !pairs || !agg_sum || !mean_region))) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        mean_region[i] = n_hit[i] > 0 ? (double)agg_sum[i] / (double)n_hit[i] : __builtin_nan("");
+        if (mean_pair) mean_pair[i] = op == IGD_HIP_MAP_SUM && pairs[i] > 0 ? (double)agg_sum[i] / (double)pairs[i] : __builtin_nan("");
+    }
+    return 0;
+}
+
 /* ---- permutation null of the nearest-record distances (what igd_hip_permute_nearest computes) ----------------------------
  * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator; a row is igdc_nearest_sets_host's
  * walk over its regions (one_region_nearest) summed into the three statistics.  Threads run over the rows (thread k takes

@@ -34,6 +34,8 @@ PermutationSummary = collections.namedtuple("PermutationSummary", "mean sd z nlo
 PERM_MODES = {"circular": 0, "shuffle": 1}           # IGD_HIP_PERM_CIRCULAR, IGD_HIP_PERM_SHUFFLE
 NearestSets = collections.namedtuple("NearestSets", "n_within n_overlap sum_dist window")
 PermutationNearest = collections.namedtuple("PermutationNearest", "n_within n_overlap sum_dist window nperm")
+MapSets = collections.namedtuple("MapSets", "n_hit pairs agg_sum op")
+MAP_OPS = {"count": 0, "sum": 1, "min": 2, "max": 3}             # IGD_HIP_MAP_COUNT, _SUM, _MIN, _MAX
 PermutationNearestSummary = collections.namedtuple(
     "PermutationNearestSummary", "within_mean within_sd within_z within_n_ge nlog10_p_within_upper mean_dist dist_mean dist_sd dist_z n_def "
     "dist_n_le nlog10_p_dist_lower")
@@ -544,6 +546,62 @@ def nearest_summary(ns):
     if N.cli().igdc_nearest_summary(_ptr(nw), _ptr(sd), nw.size, _ptr(mean)) != 0:
         raise IgdError("nearest_summary: bad argument")
     return mean
+
+
+def _map_op(op, what):
+    if op not in MAP_OPS:
+        raise IgdError("%s: op %r is none of count, sum, min, max" % (what, op))
+    return MAP_OPS[op]
+
+
+def _map_sets_args(ichr, qs, qe, set_off, what):
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+    if len(set_off) < 1:
+        raise IgdError("%s: set_off needs nsets + 1 entries" % what)
+    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("%s: set_off[-1] = %d, but %d / %d / %d regions given" % (what, set_off[-1], len(ichr), len(qs), len(qe)))
+    return ichr, qs, qe, set_off
+
+
+def map_host(igd_path, ichr, qs, qe, op="sum", value_filter=None):
+    """Database.map_values() on the host (igdc_map_host: pread on the .igd, threads over the regions; no device is touched):
+    (count int32[nq, nfiles], agg int64[nq, nfiles]); under op "count" agg holds the counts."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    if len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("map_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    o = _map_op(op, "map_host")
+    with _HostDb(igd_path, "map_host") as h:
+        count, agg = np.empty((len(qs), h.nfiles), np.int32), np.empty((len(qs), h.nfiles), np.int64)
+        if h.L.igdc_map_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), o, _value_filter(value_filter), _ptr(count), _ptr(agg)) != 0:
+            raise IgdError("map_host: op %s on a database without values, or a tile of %s could not be read" % (op, igd_path))
+        return count, agg
+
+
+def map_sets_host(igd_path, ichr, qs, qe, set_off, op="sum", value_filter=None):
+    """Database.map_sets() on the host (igdc_map_sets_host; no device is touched): a MapSets."""
+    ichr, qs, qe, set_off = _map_sets_args(ichr, qs, qe, set_off, "map_sets_host")
+    o = _map_op(op, "map_sets_host")
+    nsets = len(set_off) - 1
+    with _HostDb(igd_path, "map_sets_host") as h:
+        out = [np.empty((nsets, h.nfiles), np.int64) for _ in range(3)]
+        if h.L.igdc_map_sets_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, o, _value_filter(value_filter),
+                                  *[_ptr(a) for a in out]) != 0:
+            raise IgdError("map_sets_host: a bad set_off, op %s on a database without values, or a tile of %s could not be read"
+                           % (op, igd_path))
+        return MapSets(*out, op)
+
+
+def map_summary(ms):
+    """(mean_region, mean_pair) of a MapSets as float64[nsets, nfiles] (igdc_map_summary): agg_sum / n_hit, and for op "sum"
+    agg_sum / pairs (NaN under the other ops); NaN where the divisor is 0."""
+    nh, npairs, sa = (np.ascontiguousarray(x, dtype=np.int64) for x in (ms.n_hit, ms.pairs, ms.agg_sum))
+    if nh.shape != npairs.shape or nh.shape != sa.shape:
+        raise IgdError("map_summary: arrays of different shapes")
+    mean_region, mean_pair = np.empty(nh.shape, np.float64), np.empty(nh.shape, np.float64)
+    if N.cli().igdc_map_summary(_ptr(nh), _ptr(npairs), _ptr(sa), nh.size, _map_op(ms.op, "map_summary"), _ptr(mean_region), _ptr(mean_pair)) != 0:
+        raise IgdError("map_summary: bad argument")
+    return mean_region, mean_pair
 
 
 class Database:
@@ -1184,6 +1242,57 @@ class Database:
         (int32[nq], may be None) are overwritten.  nq above igd_hip_max_batch() is refused: split the batch."""
         _chk(self._H.igd_hip_nearest_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), _window(window, "nearest_dev"), _value_filter(value_filter),
                                          d_dist, d_dmin, stream), "igd_hip_nearest_dev")
+
+    # ---- values of the overlapping records per region and dataset -------------------------
+    def map_values(self, ichr, qs, qe, op="sum", value_filter=None, count=None, agg=None):
+        """How many records of every dataset overlap each region and what they are worth (igd_hip_map; the definitions are in
+        include/igd_hip.h): (count int32[nq, nfiles], agg int64[nq, nfiles]).  op is "count", "sum", "min" or "max" of the
+        records' value column; agg is 0 where count is 0 and, under "count", holds the counts.  value_filter: only records with
+        value >= it are counted.  There is no tile rule.  count and agg (C order), when given, are overwritten: every word is
+        defined by the call.  "sum", "min" and "max" on a database without values raise."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        if len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("map_values: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+        nq, o = len(qs), _map_op(op, "map_values")
+        if count is None:
+            count = np.empty((nq, self.nfiles), np.int32)
+        elif count.dtype != np.int32 or count.shape != (nq, self.nfiles) or not count.flags.c_contiguous:
+            raise IgdError("map_values: count must be a C-ordered int32[%d, %d]" % (nq, self.nfiles))
+        if agg is None:
+            agg = np.empty((nq, self.nfiles), np.int64)
+        elif agg.dtype != np.int64 or agg.shape != (nq, self.nfiles) or not agg.flags.c_contiguous:
+            raise IgdError("map_values: agg must be a C-ordered int64[%d, %d]" % (nq, self.nfiles))
+        _chk(self._H.igd_hip_map(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, o, _value_filter(value_filter), _ptr(count), _ptr(agg)),
+             "igd_hip_map")
+        return count, agg
+
+    def map_sets(self, ichr, qs, qe, set_off, op="sum", value_filter=None, out=None):
+        """map_values() summed up per region set (igd_hip_map_sets; sets as search_sets()): MapSets(n_hit, pairs, agg_sum, op),
+        three int64[nsets, nfiles] -- the regions of the set with a counted record of the file, the counted (region, record)
+        pairs, and the sum of the regions' agg (under "count": the pairs).  The rows never leave the device.  out, when given,
+        is a list of three C-ordered int64[nsets, nfiles] that are overwritten."""
+        ichr, qs, qe, set_off = _map_sets_args(ichr, qs, qe, set_off, "map_sets")
+        o = _map_op(op, "map_sets")
+        nsets = len(set_off) - 1
+        out = _three_out(out, (nsets, self.nfiles), "map_sets")
+        _chk(self._H.igd_hip_map_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, o, _value_filter(value_filter),
+                                      *[_ptr(a) for a in out]), "igd_hip_map_sets")
+        return MapSets(*out, op)
+
+    def map_files(self, paths, op, value_filter=None):
+        """One region set per BED file (read as `igd search -q` reads it): the MapSets of map_sets()."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.map_sets(cat[0], cat[1], cat[2], set_off, op, value_filter)
+
+    def map_dev(self, d_ichr, d_qs, d_qe, nq, d_count, d_agg=None, op="sum", value_filter=None, stream=None):
+        """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_count (int32[nq * nfiles]) and d_agg
+        (int64[nq * nfiles]; may be None under op "count") are overwritten.  nq above igd_hip_max_batch() is refused: split the
+        batch."""
+        _chk(self._H.igd_hip_map_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), _map_op(op, "map_dev"), _value_filter(value_filter), d_count, d_agg,
+                                     stream), "igd_hip_map_dev")
 
     def membership_dev(self, d_ichr, d_qs, d_qe, nq, d_bits, d_nfiles_hit=None, d_nhit=None, v=0, rule=None,
                        value_filter=None, stream=None):

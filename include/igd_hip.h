@@ -302,6 +302,55 @@ int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_
  * exceeds four times this number (tests). */
 int32_t igd_hip_nearest_grid(int64_t nq);
 
+/* Values of the overlapping records per region and dataset: how many records of every file lie under each region and what they
+ * are worth -- `bedtools map -c 5 -o count,sum,min,max,mean`, the regions x datasets feature matrix.  THE DEFINITIONS (the one
+ * place: kernel igd_map_rows, igdc_map_host and the tests' numpy reference agree on every integer).
+ *     counted      A record (idx = f, s, e, val) is counted for region (c, qs, qe) iff it lies on contig c, s < qe && e > qs and,
+ *                  with a value filter v on a database that has values (gType 1), val >= v.  Each record is counted once,
+ *                  however many tiles hold a copy of it.  This is "distance 0" of igd_hip_nearest_dist.
+ *     no rule      As igd_hip_nearest at W = 0: igd_hip_nearest_widen(qs, qe, 0), walked under rule FLAT on the image
+ *                  igd_hip_support_sets walks.  An unknown contig has an empty row; zero-length and inverted regions are not
+ *                  special-cased, the predicate decides.
+ *     op           IGD_HIP_MAP_COUNT, _SUM, _MIN, _MAX; anything else is IGD_HIP_ERR_ARG.  SUM, MIN and MAX on a gType 0
+ *                  database (no values) are IGD_HIP_ERR_ARG; COUNT works on both types.
+ *     count[q][f]  the number of counted records, int32.
+ *     agg[q][f]    the sum, minimum or maximum of val over the counted records, sign-extended to int64; the sum is exact in
+ *                  64-bit two's complement.  0 where count is 0.  Under op COUNT agg may be NULL; when it is given it receives
+ *                  the counts (agg_sum below is defined the same way).
+ *     sets         For set k = regions [set_off[k], set_off[k + 1]) each statistic is int64[nsets][nFiles]:
+ *                      n_hit[k][f] = #{q : count[q][f] > 0}      pairs[k][f] = the sum of count[q][f]
+ *                      agg_sum[k][f] = the sum of agg[q][f]      (COUNT: equal to pairs)
+ *                  igdc_map_summary (igd_core.h) derives mean_region = agg_sum / n_hit and, for SUM, mean_pair = agg_sum / pairs.
+ *     identities   count > 0 iff igd_hip_nearest(W = 0).dist == 0; n_hit is igd_hip_nearest_sets(W = 0).n_overlap without its
+ *                  last column; over regions with 0 <= qs that start inside the contig's tiles the column sums of count are the
+ *                  hits of igd_hip_search under rule FLAT.
+ * Every output is DEFINED by the call: every word is written, nothing is added to.
+ * igd_hip_map: count is int32[nq * nFiles], agg int64[nq * nFiles].  The regions go through in chunks of at most
+ * igd_hip_max_batch() regions and 256 MiB of device rows (TEST-ONLY: IGD_HIP_MAP_ROW_BYTES lowers it).
+ * igd_hip_map_sets: whole sets are taken while their three result rows fit the row budget of igd_hip_support_sets, their regions
+ * go through in the chunks above (a set may be cut by a chunk), kernel igd_map_reduce adds every chunk's rows into the three
+ * resident matrices; the rows never leave the device and the matrices are copied out once per group.  Any of the three may be NULL.
+ * igd_hip_map_dev: device pointers, one engine batch (nq above igd_hip_max_batch() is IGD_HIP_ERR_ARG), enqueued on `stream`
+ * (NULL: the engine's own) without waiting; d_count and d_agg are overwritten.
+ * Blocking (but for _dev), one device.  IGD_HIP_ERR_ARG -- a missing array, a bad set_off, an unknown op, a value op on gType 0
+ * -- comes before anything of the caller's is written.  nFiles == 0: rows of no words.
+ * Not done: an any-dataset column, a per-region mean array (it is agg / count on the caller's side), a minimum overlap, a
+ * window, median and other order statistics, several devices. */
+#define IGD_HIP_MAP_COUNT 0
+#define IGD_HIP_MAP_SUM 1
+#define IGD_HIP_MAP_MIN 2
+#define IGD_HIP_MAP_MAX 3
+static inline IGD_HIP_OV_HD_ int igd_hip_map_op_valid(int op) { return op >= IGD_HIP_MAP_COUNT && op <= IGD_HIP_MAP_MAX; }
+int igd_hip_map(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int op, int32_t v, int32_t *count,
+                int64_t *agg);
+int igd_hip_map_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                     int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum);
+int igd_hip_map_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq, int op, int32_t v,
+                    int32_t *d_count, int64_t *d_agg, void *stream);
+/* Workgroups (of four waves) igd_map_rows is launched with for nq regions: a wave meets a second region only when nq exceeds four
+ * times this number (tests). */
+int32_t igd_hip_map_grid(int64_t nq);
+
 /* The set statistics without the distance rows, and their permutation null (kernel igd_nearest_slices: the walk and table of
  * igd_nearest_rows, folded per region into LDS accumulators of the slice; nothing per region reaches memory).
  * igd_hip_nearest_sets_fused: the contract, checks and outputs of igd_hip_nearest_sets, every integer the same.  Groups of
