@@ -5,7 +5,8 @@ from ._native import NativeMissing, build  # noqa: F401
 __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "restrict_host", "enrich_restricted_host",
            "cooccur_host", "bitrows_gram_host", "jaccard", "perm_summary", "permute_regions_host", "permute_host", "MinOverlap",
            "search_host", "support_host", "nearest_host", "nearest_sets_host", "nearest_summary", "NearestSets", "permute_nearest_host",
-           "perm_nearest_summary", "PermutationNearest", "map_host", "map_sets_host", "map_summary", "MapSets"]
+           "perm_nearest_summary", "PermutationNearest", "map_host", "map_sets_host", "map_summary", "MapSets",
+           "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -27,7 +28,8 @@ def __getattr__(name):
         return enrich_restricted_host
     if name in ("cooccur_host", "bitrows_gram_host", "jaccard", "perm_summary", "permute_regions_host", "permute_host", "MinOverlap",
                 "search_host", "support_host", "nearest_host", "nearest_sets_host", "nearest_summary", "NearestSets", "permute_nearest_host",
-                "perm_nearest_summary", "PermutationNearest", "map_host", "map_sets_host", "map_summary", "MapSets"):
+                "perm_nearest_summary", "PermutationNearest", "map_host", "map_sets_host", "map_summary", "MapSets",
+                "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

@@ -211,6 +211,11 @@ def hip():
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_nearest_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
+        # the signed forms: as igd_hip_nearest / igd_hip_nearest_dev; the histogram: ..., set_off, nsets, window, v, edges, ne, hist
+        L.igd_hip_nearest_signed.argtypes = L.igd_hip_nearest.argtypes
+        L.igd_hip_nearest_signed_dev.argtypes = L.igd_hip_nearest_dev.argtypes
+        L.igd_hip_nearest_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_int32, C.c_void_p]
         # the fused route and the permutation null of the distances: as igd_hip_nearest_sets / db, ichr, qs, qe, nq, ctg_len, mode,
         # seed, nperm, window, v, n_within, n_overlap, sum_dist
         L.igd_hip_nearest_sets_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -362,6 +367,10 @@ def _bind_core(L):
     L.igdc_nearest_sets_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.igdc_nearest_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    # the signed rows: as igdc_nearest_host; the histogram: db, map, ichr, qs, qe, set_off, nsets, window, v, edges, ne, hist
+    L.igdc_nearest_signed_host.argtypes = L.igdc_nearest_host.argtypes
+    L.igdc_nearest_hist_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     # values of the overlapping records on the host: db, map, ichr, qs, qe, nq, op, v, count, agg / ..., set_off, nsets, op, v,
     # n_hit, pairs, agg_sum / n_hit, pairs, agg_sum, n, op, mean_region, mean_pair
     L.igdc_map_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_void_p,

@@ -1,5 +1,7 @@
 // engine/host_nearest.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
 // igd_hip_nearest / igd_hip_nearest_dev / igd_hip_nearest_sets: the nearest record per dataset within a window (nearest_dev.hpp)
+// igd_hip_nearest_signed / igd_hip_nearest_signed_dev / igd_hip_nearest_hist: the same with a side, and the histogram of the
+// signed distances per set and dataset
 // ------------------------------------------------------------------------------------------
 // The device form takes one engine batch of resident regions and writes resident rows: one launch (the wide form: a fill of
 // the rows with 0xff before it and, when dmin is wanted, igd_nearest_rowmin behind it), asynchronous on the caller's stream.
@@ -11,6 +13,10 @@
 // the regions of a group go through in the same chunks -- a set may be cut by a chunk, its statistics are sums over regions --
 // and per chunk igd_nearest_reduce adds the rows into the group's three resident matrices, by a slice table cut here: a slice
 // is at most IGD_NEAREST_SLICE regions of one set.  The rows never leave the device; the matrices are copied out once per group.
+// The signed forms are the same three bodies (nearest_rows_dev, nearest_rows_host, nearest_set_groups) with SIGNED = true:
+// the rows hold signed distances, the wide form's second kernel is igd_nearest_rowdecode and always runs, and the group driver's
+// reduction is igd_nearest_hist into ONE resident matrix of (ne + 1) x (nFiles + 1) words per set, with the slices cut as for
+// igd_nearest_reduce: at most IGD_NEAREST_SLICE = 256 regions, so the kernel's u32 LDS counters hold at most 256.
 // The image is slice_image(db, IGD_HIP_RULE_FLAT, v): the re-tiled copy when there is one, visited under rule FLAT.
 #define IGD_NEAREST_ROW_BYTES ((int64_t)256 << 20)   // device rows of one chunk (of the order of IGD_MEMBER_ROW_BYTES)
 #define IGD_NEAREST_SLICE 256                        // regions per slice of igd_nearest_reduce: 64 per wave
@@ -43,12 +49,14 @@ static int nearest_window_bad(const char *who, int32_t window)
     return 1;
 }
 
-extern "C" int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq,
-                                   int32_t window, int32_t v, int32_t *d_dist, int32_t *d_dmin, void *stream)
+// one engine batch of resident regions into resident rows (igd_hip_nearest_dev; SIGNED: igd_hip_nearest_signed_dev)
+template <bool SIGNED>
+static int nearest_rows_dev(const char *who, igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq,
+                            int32_t window, int32_t v, int32_t *d_dist, int32_t *d_dmin, void *stream)
 {
-    if (nearest_window_bad("igd_hip_nearest_dev", window)) return IGD_HIP_ERR_ARG;
+    if (nearest_window_bad(who, window)) return IGD_HIP_ERR_ARG;
     if (!db || nq < 0 || nq > max_batch() || (nq > 0 && (!d_ichr || !d_qs || !d_qe || (!d_dist && db->nFiles > 0)))) {
-        snprintf(g_err, sizeof g_err, "igd_hip_nearest_dev: bad argument (batch limit %lld regions)", (long long)max_batch());
+        snprintf(g_err, sizeof g_err, "%s: bad argument (batch limit %lld regions)", who, (long long)max_batch());
         return IGD_HIP_ERR_ARG;
     }
     if (nq == 0) return IGD_HIP_OK;
@@ -56,7 +64,8 @@ extern "C" int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const 
     hipStream_t st = stream ? (hipStream_t)stream : db->stream;
     const int64_t nF = db->nFiles;
     if (nF == 0) {                                       // rows of no words; no region has a dataset near it
-        if (d_dmin) HIPCHK(hipMemsetAsync(d_dmin, 0xff, (size_t)nq * 4, st));
+        if (d_dmin && !SIGNED) HIPCHK(hipMemsetAsync(d_dmin, 0xff, (size_t)nq * 4, st));
+        if (d_dmin && SIGNED) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_dmin, IGD_HIP_NEAREST_NO_RECORD, (size_t)nq, st));
         return IGD_HIP_OK;
     }
     const SliceImage im = slice_image(db, IGD_HIP_RULE_FLAT, v);
@@ -66,14 +75,29 @@ extern "C" int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const 
     const int n = (int)nq;
     if (!lds) HIPCHK(hipMemsetAsync(d_dist, 0xff, (size_t)(nq * nF) * 4, st));       // the wide form minimises into rows of "none"
     with_flags(im.useV, lds, [&](auto V, auto L) {
-        igd_nearest_rows<V(), L()><<<grid, IGD_SETS_WG, ldsB, st>>>(im.view, d_ichr, d_qs, d_qe, n, window, im.krule, v, d_dist, d_dmin);
+        igd_nearest_rows<V(), L(), SIGNED><<<grid, IGD_SETS_WG, ldsB, st>>>(im.view, d_ichr, d_qs, d_qe, n, window, im.krule, v, d_dist, d_dmin);
     });
     HIPCHK(hipGetLastError());
-    if (!lds && d_dmin) {
+    if (!lds && SIGNED) {                                // (the rows hold keys: decoded whether sdmin is wanted or not)
+        igd_nearest_rowdecode<<<grid, IGD_SETS_WG, 0, st>>>(d_dist, n, (int)nF, d_dmin);
+        HIPCHK(hipGetLastError());
+    } else if (!lds && d_dmin) {
         igd_nearest_rowmin<<<grid, IGD_SETS_WG, 0, st>>>(d_dist, n, (int)nF, d_dmin);
         HIPCHK(hipGetLastError());
     }
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq,
+                                   int32_t window, int32_t v, int32_t *d_dist, int32_t *d_dmin, void *stream)
+{
+    return nearest_rows_dev<false>("igd_hip_nearest_dev", db, d_ichr, d_qs, d_qe, nq, window, v, d_dist, d_dmin, stream);
+}
+
+extern "C" int igd_hip_nearest_signed_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq,
+                                          int32_t window, int32_t v, int32_t *d_sdist, int32_t *d_sdmin, void *stream)
+{
+    return nearest_rows_dev<true>("igd_hip_nearest_signed_dev", db, d_ichr, d_qs, d_qe, nq, window, v, d_sdist, d_sdmin, stream);
 }
 
 // the rows and dmin[] of one chunk of regions
@@ -84,18 +108,21 @@ static int ensure_nearest_ws(igd_hip_db *db, int64_t words, int64_t rows)
     return rc;
 }
 
-extern "C" int igd_hip_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window,
-                               int32_t v, int32_t *dist, int32_t *dmin)
+// host arrays in chunks (igd_hip_nearest; SIGNED: igd_hip_nearest_signed)
+template <bool SIGNED>
+static int nearest_rows_host(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                             int32_t window, int32_t v, int32_t *dist, int32_t *dmin)
 {
-    if (nearest_window_bad("igd_hip_nearest", window)) return IGD_HIP_ERR_ARG;
+    if (nearest_window_bad(who, window)) return IGD_HIP_ERR_ARG;
     if (!db || nq < 0 || (nq > 0 && (!ichr || !qs || !qe || (!dist && db->nFiles > 0)))) {
-        snprintf(g_err, sizeof g_err, "igd_hip_nearest: bad argument");
+        snprintf(g_err, sizeof g_err, "%s: bad argument", who);
         return IGD_HIP_ERR_ARG;
     }
     if (nq == 0) return IGD_HIP_OK;
     const int64_t nF = db->nFiles;
     if (nF == 0) {
-        if (dmin) memset(dmin, 0xff, (size_t)nq * 4);
+        if (dmin && !SIGNED) memset(dmin, 0xff, (size_t)nq * 4);
+        if (dmin && SIGNED) for (int64_t i = 0; i < nq; i++) dmin[i] = IGD_HIP_NEAREST_NO_RECORD;
         return IGD_HIP_OK;
     }
     const int64_t step = nearest_step(nF);
@@ -105,12 +132,81 @@ extern "C" int igd_hip_nearest(igd_hip_db *db, const int32_t *ichr, const int32_
         const int64_t m = nq - c0 < step ? nq - c0 : step;
         int rc = ensure_nearest_ws(db, m * nF, m);
         if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
-        if (rc == IGD_HIP_OK) rc = igd_hip_nearest_dev(db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, dmin ? db->d_nrMin : nullptr, st);
+        if (rc == IGD_HIP_OK) rc = nearest_rows_dev<SIGNED>(who, db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, dmin ? db->d_nrMin : nullptr, st);
         if (rc != IGD_HIP_OK) return rc;
         HIPCHK(hipMemcpyAsync(dist + c0 * nF, db->d_nrDist, (size_t)(m * nF) * 4, hipMemcpyDeviceToHost, st));
         if (dmin) HIPCHK(hipMemcpyAsync(dmin + c0, db->d_nrMin, (size_t)m * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
+    }
+    return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window,
+                               int32_t v, int32_t *dist, int32_t *dmin)
+{
+    return nearest_rows_host<false>("igd_hip_nearest", db, ichr, qs, qe, nq, window, v, dist, dmin);
+}
+
+extern "C" int igd_hip_nearest_signed(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window,
+                                      int32_t v, int32_t *sdist, int32_t *sdmin)
+{
+    return nearest_rows_host<true>("igd_hip_nearest_signed", db, ichr, qs, qe, nq, window, v, sdist, sdmin);
+}
+
+// The group and chunk driver of igd_hip_nearest_sets and igd_hip_nearest_hist (the arguments are checked, there are regions
+// and files).  Per set there are nMat result rows of matRow 64-bit words, kept in d_nrStat as nMat matrices of rows x matRow
+// words: whole sets are taken while they fit sets_row_bytes(); their regions go through in chunks of nearest_step() -- the
+// (SIGNED) rows and dmin[] of a chunk stay in d_nrDist / d_nrMin -- and reduce(gx, gy, ns, rows, st) launches the kernel that
+// adds the chunk's rows into the matrices by the slice table in d_nrSlices; matrix i is copied out to outs[i] (may be NULL)
+// once per group.
+template <bool SIGNED, typename Reduce>
+static int nearest_set_groups(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                              int32_t nsets, int32_t window, int32_t v, int nMat, int64_t matRow, int64_t *const *outs, Reduce &&reduce)
+{
+    int rc;
+    const int64_t nF = db->nFiles, nC = nF + 1;
+    const int64_t step = nearest_step(nF);
+    const int64_t rowCap = sets_row_bytes() / (nMat * matRow * 8) > 0 ? sets_row_bytes() / (nMat * matRow * 8) : 1;
+    const int gx = (int)((nC + IGD_WAVE - 1) / IGD_WAVE);
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    std::vector<SetSlice> slices;
+    for (int32_t k0 = 0; k0 < nsets;) {
+        // one group: sets [k0, k1), regions [set_off[k0], set_off[k1])
+        const int32_t k1 = (int32_t)(nsets - k0 < rowCap ? nsets : k0 + rowCap);
+        const int64_t rows = k1 - k0, matWords = rows * matRow;
+        if ((rc = dev_grow(db, &db->d_nrStat, &db->nrStatCap, nMat * matWords)) != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemsetAsync(db->d_nrStat, 0, (size_t)(nMat * matWords) * 8, st));
+        int32_t k = k0;
+        for (int64_t c0 = set_off[k0]; c0 < set_off[k1]; c0 += step) {
+            const int64_t m = set_off[k1] - c0 < step ? set_off[k1] - c0 : step;
+            // the chunk's part of every set it meets, in slices of at most IGD_NEAREST_SLICE regions
+            slices.clear();
+            while (set_off[k + 1] <= c0) k++;
+            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++) {
+                const int64_t a0 = set_off[j] > c0 ? set_off[j] : c0, b0 = set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m;
+                for (int64_t a = a0; a < b0; a += IGD_NEAREST_SLICE)
+                    slices.push_back(SetSlice{j - k0, (int32_t)(a - c0), (int32_t)((a + IGD_NEAREST_SLICE < b0 ? a + IGD_NEAREST_SLICE : b0) - c0), 0});
+            }
+            const int ns = (int)slices.size();
+            rc = ensure_nearest_ws(db, m * nF, m);
+            if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
+            if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
+            if (rc == IGD_HIP_OK) rc = nearest_rows_dev<SIGNED>(who, db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
+            if (rc != IGD_HIP_OK) return rc;
+            HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+            int gy = IGD_NEAREST_REDUCE_WGS / gx;
+            gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
+            reduce(dim3((unsigned)gx, (unsigned)gy), ns, rows, st);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
+        }
+        for (int i = 0; i < nMat; i++)
+            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * matRow, db->d_nrStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        k0 = k1;
     }
     return IGD_HIP_OK;
 }
@@ -132,48 +228,38 @@ extern "C" int igd_hip_nearest_sets(igd_hip_db *db, const int32_t *ichr, const i
         for (int64_t *o : outs) if (o) memset(o, 0, (size_t)nsets * (size_t)nC * 8);
         return IGD_HIP_OK;
     }
-    const int64_t step = nearest_step(nF);
-    const int64_t rowCap = sets_row_bytes() / (3 * nC * 8) > 0 ? sets_row_bytes() / (3 * nC * 8) : 1;
-    const int gx = (int)((nC + IGD_WAVE - 1) / IGD_WAVE);
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
-    std::vector<SetSlice> slices;
-    for (int32_t k0 = 0; k0 < nsets;) {
-        // one group: sets [k0, k1), regions [set_off[k0], set_off[k1])
-        const int32_t k1 = (int32_t)(nsets - k0 < rowCap ? nsets : k0 + rowCap);
-        const int64_t rows = k1 - k0, matWords = rows * nC;
-        if ((rc = dev_grow(db, &db->d_nrStat, &db->nrStatCap, 3 * matWords)) != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemsetAsync(db->d_nrStat, 0, (size_t)(3 * matWords) * 8, st));
-        int32_t k = k0;
-        for (int64_t c0 = set_off[k0]; c0 < set_off[k1]; c0 += step) {
-            const int64_t m = set_off[k1] - c0 < step ? set_off[k1] - c0 : step;
-            // the chunk's part of every set it meets, in slices of at most IGD_NEAREST_SLICE regions
-            slices.clear();
-            while (set_off[k + 1] <= c0) k++;
-            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++) {
-                const int64_t a0 = set_off[j] > c0 ? set_off[j] : c0, b0 = set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m;
-                for (int64_t a = a0; a < b0; a += IGD_NEAREST_SLICE)
-                    slices.push_back(SetSlice{j - k0, (int32_t)(a - c0), (int32_t)((a + IGD_NEAREST_SLICE < b0 ? a + IGD_NEAREST_SLICE : b0) - c0), 0});
-            }
-            const int ns = (int)slices.size();
-            rc = ensure_nearest_ws(db, m * nF, m);
-            if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
-            if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
-            if (rc == IGD_HIP_OK) rc = igd_hip_nearest_dev(db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
-            if (rc != IGD_HIP_OK) return rc;
-            HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-            int gy = IGD_NEAREST_REDUCE_WGS / gx;
-            gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
-            igd_nearest_reduce<<<dim3((unsigned)gx, (unsigned)gy), IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns,
-                                                                                      (u64 *)db->d_nrStat, matWords);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
-        }
-        for (int i = 0; i < 3; i++)
-            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * nC, db->d_nrStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        k0 = k1;
+    return nearest_set_groups<false>("igd_hip_nearest_sets", db, ichr, qs, qe, set_off, nsets, window, v, 3, nC, outs,
+                                     [&](dim3 grid, int ns, int64_t rows, hipStream_t st) {
+        igd_nearest_reduce<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns, (u64 *)db->d_nrStat, rows * nC);
+    });
+}
+
+extern "C" int igd_hip_nearest_hist(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                                    int32_t nsets, int32_t window, int32_t v, const int32_t *edges, int32_t ne, int64_t *hist)
+{
+    if (nearest_window_bad("igd_hip_nearest_hist", window)) return IGD_HIP_ERR_ARG;
+    if (!igd_hip_nearest_edges_valid(edges, ne)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_nearest_hist: edges must be 1 .. %d strictly ascending int32", (int)IGD_HIP_NEAREST_MAX_EDGES);
+        return IGD_HIP_ERR_ARG;
     }
-    return IGD_HIP_OK;
+    if (!db || nsets < 0 || (nsets > 0 && (!set_off || !hist))) {
+        snprintf(g_err, sizeof g_err, "igd_hip_nearest_hist: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nsets == 0) return IGD_HIP_OK;
+    int rc = sets_check("igd_hip_nearest_hist", ichr, qs, qe, set_off, nsets);
+    if (rc != IGD_HIP_OK) return rc;
+    const int64_t nF = db->nFiles, nC = nF + 1, matRow = (int64_t)(ne + 1) * nC;
+    if (set_off[nsets] == 0 || nF == 0) {                // no region, or no dataset to be near: no region is in a bin
+        memset(hist, 0, (size_t)nsets * (size_t)matRow * 8);
+        return IGD_HIP_OK;
+    }
+    HIPCHK(hipSetDevice(db->device));
+    if ((rc = dev_grow(db, &db->d_nrEdges, &db->nrEdgesCap, (int64_t)IGD_HIP_NEAREST_MAX_EDGES)) != IGD_HIP_OK) return rc;
+    HIPCHK(hipMemcpyAsync(db->d_nrEdges, edges, (size_t)ne * 4, hipMemcpyHostToDevice, db->stream));
+    int64_t *outs[1] = {hist};
+    return nearest_set_groups<true>("igd_hip_nearest_hist", db, ichr, qs, qe, set_off, nsets, window, v, 1, matRow, outs,
+                                    [&](dim3 grid, int ns, int64_t, hipStream_t st) {
+        igd_nearest_hist<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns, db->d_nrEdges, (int)ne, (u64 *)db->d_nrStat);
+    });
 }

@@ -33,11 +33,19 @@
 //   belongs to one wave during the launch.  dmin comes from igd_nearest_rowmin, a small kernel launched behind this one
 //   (the pattern of igd_member_popc); it is not launched when the caller wants no dmin.
 // igd_nearest_reduce adds the rows of a chunk into the three resident matrices of igd_hip_nearest_sets; see there.
+// SIGNED (igd_hip_nearest_signed / _signed_dev / igd_hip_nearest_hist): the step minimises igd_hip_nearest_key -- 2 d + (d > 0
+//   && downstream) -- instead of d: the same table, the same 0xffffffff "none", the same atomics that return nothing (a minimum
+//   does not depend on the order of the records).  The stream-out decodes the key on its way to the row
+//   (igd_hip_nearest_key_decode: INT32_MIN = none), dmin is decoded after the wave's min-reduction of the KEYS, and a region
+//   without a counted record stores INT32_MIN words.  Wide form: the minimum goes into the row as a key and
+//   igd_nearest_rowdecode, launched behind (igd_nearest_rowmin's role), takes the row's minimum and decodes the row in place;
+//   it runs in every signed call, whether the caller wants sdmin or not.  The unsigned instantiations are what they were.
+// igd_nearest_hist counts the signed rows of a chunk into the resident histogram of igd_hip_nearest_hist; see there.
 // All stores to memory are vector stores or vector atomics.
 #define IGD_NEAREST_LDS_FILES 4096                   // 64 KiB of tables per workgroup: two workgroups per CU stay resident
 #define IGD_NEAREST_NONE 0xffffffffu
 
-template <bool USE_V, bool LDS>
+template <bool USE_V, bool LDS, bool SIGNED = false>
 __global__ __launch_bounds__(IGD_SETS_WG) void igd_nearest_rows(DbView db, const int32_t *__restrict__ q_ichr,
                                                                const int32_t *__restrict__ q_qs, const int32_t *__restrict__ q_qe,
                                                                int nq, int window, int krule, int v, int32_t *__restrict__ dist,
@@ -67,7 +75,8 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_nearest_rows(DbView db, const
         u64 any = 0;
         walk_query_tiles<USE_V, false>(db, lane, nF, ws, we, gt0, ntl, v, 0, MinOv{0, 0, 0}, [&](int s0, int e0, int x0, bool h0, int s1, int e1, int x1, bool h1) {
             // (a lane without a counted record computes a d nobody reads)
-            const unsigned d0 = (unsigned)igd_hip_nearest_dist(qs, qe, s0, e0), d1 = (unsigned)igd_hip_nearest_dist(qs, qe, s1, e1);
+            const unsigned d0 = SIGNED ? igd_hip_nearest_key(qs, qe, s0, e0) : (unsigned)igd_hip_nearest_dist(qs, qe, s0, e0);
+            const unsigned d1 = SIGNED ? igd_hip_nearest_key(qs, qe, s1, e1) : (unsigned)igd_hip_nearest_dist(qs, qe, s1, e1);
             if (LDS) {
                 if (h0) (void)__hip_atomic_fetch_min(tb + x0, d0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (h1) (void)__hip_atomic_fetch_min(tb + x1, d1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -86,7 +95,7 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_nearest_rows(DbView db, const
                 for (int w = lane; w < nF; w += IGD_WAVE) {
                     const unsigned x = __hip_atomic_load(tb + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     __hip_atomic_store(tb + w, IGD_NEAREST_NONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    row[w] = x;
+                    row[w] = SIGNED ? (unsigned)igd_hip_nearest_key_decode(x) : x;
                     m = x < m ? x : m;
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -95,11 +104,11 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_nearest_rows(DbView db, const
                         const unsigned y = (unsigned)__shfl_xor((int)m, o);
                         m = y < m ? y : m;
                     }
-                    if (lane == 0) dmin[q] = (int32_t)m;
+                    if (lane == 0) dmin[q] = SIGNED ? igd_hip_nearest_key_decode(m) : (int32_t)m;
                 }
             } else {
-                for (int w = lane; w < nF; w += IGD_WAVE) row[w] = IGD_NEAREST_NONE;
-                if (dmin && lane == 0) dmin[q] = -1;
+                for (int w = lane; w < nF; w += IGD_WAVE) row[w] = SIGNED ? (unsigned)IGD_HIP_NEAREST_NO_RECORD : IGD_NEAREST_NONE;
+                if (dmin && lane == 0) dmin[q] = SIGNED ? IGD_HIP_NEAREST_NO_RECORD : -1;
             }
         }
     }
@@ -124,6 +133,31 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_nearest_rowmin(const int32_t 
             m = y < m ? y : m;
         }
         if (lane == 0) dmin[q] = (int32_t)m;
+    }
+}
+
+// wide form, SIGNED: row q holds minimum keys (0xffffffff = none); the wave takes their minimum, decodes the row IN PLACE
+// (every word is read and then written by the same lane) and one lane stores the decoded minimum when dmin is wanted
+__global__ __launch_bounds__(IGD_SETS_WG) void igd_nearest_rowdecode(int32_t *__restrict__ dist, int nq, int nF, int32_t *__restrict__ dmin)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int waves = (int)gridDim.x * (IGD_SETS_WG / IGD_WAVE);
+    for (int q = (int)blockIdx.x * (IGD_SETS_WG / IGD_WAVE) + wave; q < nq; q += waves) {
+        unsigned *row = (unsigned *)dist + (size_t)q * (size_t)nF;
+        unsigned m = IGD_NEAREST_NONE;
+        for (int w = lane; w < nF; w += IGD_WAVE) {
+            const unsigned x = row[w];
+            row[w] = (unsigned)igd_hip_nearest_key_decode(x);
+            m = x < m ? x : m;
+        }
+        if (dmin) {
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned y = (unsigned)__shfl_xor((int)m, o);
+                m = y < m ? y : m;
+            }
+            if (lane == 0) dmin[q] = igd_hip_nearest_key_decode(m);
+        }
     }
 }
 
@@ -169,5 +203,56 @@ __global__ __launch_bounds__(IGD_SETS_WG) void igd_nearest_reduce(const int32_t 
             if (sd) (void)__hip_atomic_fetch_add(dst + 2 * matWords, sd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();                                                  // (wave 0 has read part[] before the next slice's writes)
+    }
+}
+
+// igd_nearest_hist.  The SIGNED rows of one chunk of regions (sdist: nF words each; sdmin: one word each, read as column nF),
+// igd_nearest_reduce's slice table, and ne strictly ascending edges.  hist is u64[rows][ne + 1][nF + 1].  The shape of
+// igd_nearest_reduce: workgroup (x, y) owns the 64 columns [64 x, 64 x + 64), one per lane, and the slices y, y + gridDim.y,
+// ..; the rows of a slice are strided over the four waves.  LDS: u32 h[64][64] addressed bin * 64 + lane (16 KiB; the lanes of
+// a wave hit distinct banks, and a lane only ever touches its own column's counters, which the four waves share) and the
+// edges as 64 words padded with INT32_MAX -- no sdist is INT32_MAX (|sdist| <= 2^30, or INT32_MIN, which is skipped), so the
+// padding is never counted.  Per element: a branch-free six-step bisection, pos += s if edges[pos + s - 1] <= x for s = 32 ..
+// 1 (pos + s - 1 <= 62: the 64th word is never read as an edge; pos ends as bin(x) <= ne), then one LDS add that returns
+// nothing (ds_add_u32).  Per slice: bins 0 .. ne are zeroed, the slice is counted, and behind a barrier wave w issues for the
+// bins w, w + 4, .. one device-scope 64-bit atomic add (nothing returned) per NON-ZERO (bin, column) into hist[row][bin][col],
+// coalesced across the lanes.  A slice holds at most IGD_NEAREST_SLICE = 256 regions, so a u32 counter holds at most 256.
+// Only integers are added: no order matters.
+#define IGD_NEAREST_HIST_BINS 64                     // IGD_HIP_NEAREST_MAX_EDGES + 1
+__global__ __launch_bounds__(IGD_SETS_WG) void igd_nearest_hist(const int32_t *__restrict__ sdist, const int32_t *__restrict__ sdmin,
+                                                               int nF, const SetSlice *__restrict__ slices, int nSlices,
+                                                               const int32_t *__restrict__ edges, int ne, u64 *__restrict__ hist)
+{
+    __shared__ unsigned h[IGD_NEAREST_HIST_BINS * IGD_WAVE];
+    __shared__ int32_t edg[IGD_NEAREST_HIST_BINS];
+    const int lane = threadIdx.x & 63;
+    const int wave = (int)(threadIdx.x >> 6);
+    const int col = (int)blockIdx.x * IGD_WAVE + lane;
+    const bool live = col <= nF;
+    const bool fromMin = col == nF;
+    const int nb = ne + 1;
+    if (threadIdx.x < IGD_NEAREST_HIST_BINS) edg[threadIdx.x] = (int)threadIdx.x < ne ? edges[threadIdx.x] : INT32_MAX;
+    for (int s = blockIdx.y; s < nSlices; s += gridDim.y) {
+        const SetSlice sl = slices[s];
+        for (int i = threadIdx.x; i < nb * IGD_WAVE; i += IGD_SETS_WG) h[i] = 0;
+        __syncthreads();                                                  // (the first slice: the edges are in place too)
+        if (live)
+            for (int r = sl.a + wave; r < sl.b; r += IGD_SETS_WG / IGD_WAVE) {
+                const int x = fromMin ? sdmin[r] : sdist[(size_t)r * (size_t)nF + (size_t)col];
+                if (x == IGD_HIP_NEAREST_NO_RECORD) continue;
+                int pos = 0;
+#pragma unroll
+                for (int st = 32; st > 0; st >>= 1) pos += edg[pos + st - 1] <= x ? st : 0;
+                (void)__hip_atomic_fetch_add(&h[pos * IGD_WAVE + lane], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        __syncthreads();
+        if (live) {
+            u64 *dst = hist + (size_t)sl.row * (size_t)nb * (size_t)(nF + 1) + (size_t)col;
+            for (int b = wave; b < nb; b += IGD_SETS_WG / IGD_WAVE) {
+                const unsigned c = h[b * IGD_WAVE + lane];
+                if (c) (void)__hip_atomic_fetch_add(dst + (size_t)b * (size_t)(nF + 1), (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __syncthreads();                                                  // (h[] has been read before the next slice's zeroes)
     }
 }

@@ -1548,6 +1548,89 @@ static void nearest_files(char **paths, int32_t n, int32_t v, int setLines, int3
     free(q); free(ichr); free(qs); free(qe); free(off); free(st3); free(mean);
 }
 
+/* ------------------------------- `igd search -q F -N <bp> -H e1,e2,..` / `-Q <list> -N <bp> -H ..` ------- */
+/* Histogram of the signed nearest distances (include/igd_hip.h has the definitions): per database file the query regions with
+ * a record of the file within W bp (n_within) and their number per bin of the signed distance -- negative: the nearest record
+ * lies upstream -- under the columns `<e1`, `[e1,e2)`, .., `>=e_ne`; one line per dataset, then the same for "any dataset".
+ * -v, routing and the layout of -Q blocks as -N: the host answers with igdc_nearest_hist_host, the engine with ONE
+ * igd_hip_nearest_hist call. */
+static int parse_edges(const char *arg, int32_t *edges)                     /* the number of edges, or -1 for a refused list */
+{
+    int ne = 0;
+    for (const char *p = arg;;) {
+        char *end = NULL;
+        if (p[0] != '-' && (p[0] < '0' || p[0] > '9')) return -1;           /* (strtoll's leading blanks and '+' are not the list's) */
+        const long long x = strtoll(p, &end, 10);                           /* (out of range: LLONG_MIN / LLONG_MAX, refused below) */
+        if (end == p || (*end != ',' && *end != '\0') || x < (long long)INT32_MIN || x > (long long)INT32_MAX) return -1;
+        if (ne == IGD_HIP_NEAREST_MAX_EDGES || (ne > 0 && (int32_t)x <= edges[ne - 1])) return -1;
+        edges[ne++] = (int32_t)x;
+        if (*end == '\0') return ne;
+        p = end + 1;
+    }
+}
+
+static void nearest_hist_files(char **paths, int32_t n, int32_t v, int setLines, int32_t window, const int32_t *edges, int ne)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles;
+    const size_t nC = (size_t)nfiles + 1, nB = (size_t)ne + 1;
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    int64_t *hist = (int64_t *)calloc((size_t)(n ? n : 1) * nB * nC, sizeof(int64_t));
+    off[0] = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (q[k].n) {
+            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+        }
+        off[k + 1] = off[k] + q[k].n;
+    }
+    int onHost = 0;
+    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
+    if (hm) {
+        double t0 = now_s();
+        onHost = igdc_nearest_hist_host(g_core, hm, ichr, qs, qe, off, n, window, ev, edges, ne, hist) == 0;
+        igdc_map_close(hm);
+        if (onHost) phase("histogram of the nearest distances on the host (small files)", &t0);
+    }
+    if (!onHost && nq > 0) {                          /* (after a read error too: the engine reads the file its own way) */
+        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
+        double t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_nearest_hist(dev, ichr, qs, qe, off, n, window, ev, edges, ne, hist);
+            if (rc != IGD_HIP_OK) engine_failed("nearest histogram", rc);
+            phase("histogram of the nearest distances of the query sets (H2D + kernels + D2H)", &t0);
+        }
+    }
+    for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
+        const int64_t *h = hist + (size_t)k * nB * nC;
+        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        printf("index\tn_within\t<%d", (int)edges[0]);
+        for (int b = 1; b < ne; b++) printf("\t[%d,%d)", (int)edges[b - 1], (int)edges[b]);
+        printf("\t>=%d\tFile\n", (int)edges[ne - 1]);
+        for (int32_t i = 0; i <= nfiles; i++) {       /* (i = nfiles: the any-dataset column) */
+            int64_t nw = 0;
+            for (size_t b = 0; b < nB; b++) nw += h[b * nC + (size_t)i];
+            if (i < nfiles) printf("%d\t%lld", (int)i, (long long)nw);
+            else printf("Any dataset within %d bp: %lld of %lld", (int)window, (long long)nw, (long long)q[k].n);
+            for (size_t b = 0; b < nB; b++) printf("\t%lld", (long long)h[b * nC + (size_t)i]);
+            if (i < nfiles) printf("\t%s\n", IGD->finfo[i].fileName);
+            else printf("\n");
+        }
+    }
+    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    free(q); free(ichr); free(qs); free(qe); free(off); free(hist);
+}
+
 /* ------------------------------- `igd search -q F -V <op>` / `-Q <list> -V <op>` ------- */
 /* Values of the overlapping records per dataset (include/igd_hip.h has the definitions): per database file the query regions
  * with a counted record (n_hit), the counted (region, record) pairs (pairs) and a mean -- of the per-region count, sum, minimum
@@ -1720,6 +1803,9 @@ static int usage_search(void)
             "                               with at most six places.  With -q or -Q alone, -u, -U [-R] and -P\n"
             "    -N <bp>                    with -q or -Q: per dataset, the query regions with a record within <bp> base pairs (0 to\n"
             "                               1073741824), those that overlap one, and the mean distance to the nearest record\n"
+            "    -H <e1,e2,...>             with -N: instead, per dataset the regions with a record within <bp> and their number per\n"
+            "                               bin of the SIGNED distance to the nearest record (negative: it lies upstream); 1 to 63\n"
+            "                               ascending integer edges, bins <e1, [e1,e2), .., >=e_last\n"
             "    -V <op>                    with -q or -Q: per dataset, the query regions with an overlapping record, the overlapping\n"
             "                               (region, record) pairs and the mean over those regions of the records' count, sum, min\n"
             "                               or max of the value column; mean: the mean value over the pairs\n"
@@ -1774,6 +1860,7 @@ int igd_search(int argc, char **argv)                                        /* 
     char *permArg = NULL, *genomeName = NULL, *seedArg = NULL, *pmodeArg = NULL;      /* -P, -g, -S, -M (see permute_file) */
     char *nearArg = NULL;                                                             /* -N (see nearest_files) */
     char *distArg = NULL;                                                             /* -D (see permute_nearest_table) */
+    char *histArg = NULL;                                                             /* -H (see nearest_hist_files) */
     char *mapArg = NULL;                                                              /* -V (see map_files) */
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -1821,6 +1908,10 @@ int igd_search(int argc, char **argv)                                        /* 
             if (i + 1 >= argc) { printf("No window.\n"); return EX_OK; }
             nearArg = argv[i + 1];
             i++;                                      /* (the window is not an option: "-N -5" is a refused window) */
+        } else if (strcmp(a, "-H") == 0) {            /* (not the reference's: histogram of the signed distances of -N, see nearest_hist_files) */
+            if (i + 1 >= argc) { printf("Not supported: -H without a list of edges\n"); return EX_USAGE; }
+            histArg = argv[i + 1];
+            i++;                                      /* (the list is not an option: "-H -500,0,500" is a list) */
         } else if (strcmp(a, "-V") == 0) {            /* (not the reference's: values of the overlapping records, see map_files) */
             if (i + 1 >= argc) { printf("Not supported: -V without an op (count, sum, min, max or mean)\n"); return EX_USAGE; }
             mapArg = argv[i + 1];
@@ -1876,6 +1967,22 @@ int igd_search(int argc, char **argv)                                        /* 
         }
         if (mapOp != 0 && IGD->gType == 0) {
             printf("Not supported: -V %s on a database without values (gType 0); -V count works there\n", mapArg);
+            return EX_USAGE;
+        }
+    }
+    int32_t histEdges[IGD_HIP_NEAREST_MAX_EDGES];                             /* -H: every refusal is a usage error */
+    int histNe = 0;
+    if (histArg) {
+        const char *why = NULL;
+        if (!nearArg) why = "-H without -N";
+        else if (permArg || distArg) why = "-H together with -P or -D";
+        if (why) {
+            printf("Not supported: %s\n", why);
+            return EX_USAGE;
+        }
+        if ((histNe = parse_edges(histArg, histEdges)) < 1) {
+            printf("Not supported: -H %s (1 to %d ascending integer edges, each within int32, separated by commas)\n", histArg,
+                   (int)IGD_HIP_NEAREST_MAX_EDGES);
             return EX_USAGE;
         }
     }
@@ -1936,11 +2043,13 @@ int igd_search(int argc, char **argv)                                        /* 
         for (int32_t k = 0; k < n; k++) free(paths[k]);
         free(paths);
     } else if (nearArg && mode == 1) {
-        nearest_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10));
+        if (histArg) nearest_hist_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10), histEdges, histNe);
+        else nearest_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10));
     } else if (nearArg) {
         int32_t n = 0;
         char **paths = read_list(listName, &n);
-        if (n >= 0) nearest_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10));
+        if (n >= 0 && histArg) nearest_hist_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10), histEdges, histNe);
+        else if (n >= 0) nearest_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10));
         for (int32_t k = 0; k < n; k++) free(paths[k]);
         free(paths);
     } else if (permArg && (listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)) {

@@ -209,6 +209,16 @@ int igdc_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
 int igdc_nearest_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                            const int64_t *set_off, int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
                            int64_t *sum_dist);
+/* Signed nearest distances and their histogram (what igd_hip_nearest_signed and igd_hip_nearest_hist compute; include/igd_hip.h
+ * has the definitions): sdist (int32[nq * nFiles]) and sdmin (int32[nq], may be NULL), IGD_HIP_NEAREST_NO_RECORD where there is
+ * no record; hist (int64[nsets * (ne + 1) * (nFiles + 1)], column nFiles from sdmin).  The walk of igdc_nearest_host with
+ * igd_hip_nearest_key minimised instead of d, threads over the regions.  0 on success; -1 as above, and for edges that are not
+ * 1 .. IGD_HIP_NEAREST_MAX_EDGES strictly ascending values (nothing written). */
+int igdc_nearest_signed_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                             int32_t window, int32_t v, int32_t *sdist, int32_t *sdmin);
+int igdc_nearest_hist_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                           const int64_t *set_off, int32_t nsets, int32_t window, int32_t v, const int32_t *edges, int32_t ne,
+                           int64_t *hist);
 /* mean[i] = sum_dist[i] / n_within[i] as a double, NaN where n_within[i] = 0.  Needs no database.  0, or -1 for a missing array. */
 int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t n, double *mean);
 /* Values of the overlapping records per region and dataset (what igd_hip_map and igd_hip_map_sets compute; include/igd_hip.h has

@@ -341,6 +341,9 @@ struct igd_hip_db {
     int64_t *d_nrStat;
     struct SetSlice *d_nrSlices;
     int64_t nrDistCap, nrMinCap, nrStatCap, nrSliceCap;
+    // igd_hip_nearest_hist: the edges on the device (the resident histogram of one group of sets lives in d_nrStat)
+    int32_t *d_nrEdges;
+    int64_t nrEdgesCap;
     // igd_hip_map / igd_hip_map_sets (host_map.hpp): the count and agg rows of one chunk of regions, the three matrices of one
     // group of sets (64-bit words) and the slice table of igd_map_reduce
     int32_t *d_mpCount;
@@ -381,7 +384,7 @@ struct igd_hip_db {
 #include "engine/restrict_dev.hpp"    // igd_restrict_bits, igd_bits_support: sets restricted to a universe -- the interval join and the gather over member rows
 #include "engine/cooccur_dev.hpp"     // igd_bits_transpose, igd_bitrows_gram: bit rows into bit columns, popcount Gram product -- dataset co-occurrence
 #include "engine/permute_dev.hpp"     // igd_permute_regions, igd_perm_stats: shifted / shuffled region sets, column statistics of a row matrix -- permutation null
-#include "engine/nearest_dev.hpp"     // igd_nearest_rows, igd_nearest_reduce: the same walk over a widened interval, one distance row per region -- nearest record per dataset
+#include "engine/nearest_dev.hpp"     // igd_nearest_rows, igd_nearest_reduce, igd_nearest_hist: the same walk over a widened interval, one (signed) distance row per region -- nearest record per dataset
 #include "engine/nearest_fused_dev.hpp" // igd_nearest_slices: the same walk and table, folded into per-slice LDS accumulators -- the set statistics without the rows
 #include "engine/map_dev.hpp"         // igd_map_rows, igd_map_reduce: the same walk with the value words, count and sum / min / max rows per region -- values of the overlapping records
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
@@ -400,7 +403,7 @@ struct igd_hip_db {
 #include "engine/host_restrict.hpp"   // igd_hip_restrict_sets / igd_hip_enrich_restricted: chunks of sets x chunks of the universe
 #include "engine/host_cooccur.hpp"    // igd_hip_cooccur / igd_hip_bits_transpose / igd_hip_bitrows_gram: chunks of regions, rows stay resident
 #include "engine/host_permute.hpp"    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: chunks of permutations, rows stay resident
-#include "engine/host_nearest.hpp"    // igd_hip_nearest / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
+#include "engine/host_nearest.hpp"    // igd_hip_nearest / _dev / _sets, _signed / _signed_dev / _hist: chunks of regions within a row budget, the set statistics stay resident
 #include "engine/host_permute_nearest.hpp" // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: one fused launch per chunk, the null distribution of the distance statistics
 #include "engine/host_map.hpp"        // igd_hip_map / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile

@@ -1128,47 +1128,63 @@ int igdc_perm_summary(const int64_t *observed, const int64_t *sum, const int64_t
  * One region: its row is set to -1, the interval is widened by the window (igd_hip_nearest_widen), the tiles of the widened
  * interval are visited as one_query visits them under rule FLAT -- bisection for the last start < we, backwards while
  * end > ws, in later tiles only down to the tile's start (the prefix skip) -- and every counted record lowers row[idx] to
- * its d, computed from the region as given (igd_hip_nearest_dist).  Returns the minimum over the files, or -1. */
-static inline int32_t one_region_nearest(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
-                                         int32_t window, int32_t v, int use_v, int32_t *row)
+ * its d, computed from the region as given (igd_hip_nearest_dist).  Returns the minimum over the files, or -1.
+ * one_region_keys is that walk on unsigned words, 0xffffffff (= -1) for "none": with sgn it minimises igd_hip_nearest_key
+ * instead of d, and one_region_nearest_signed decodes the row and the minimum (igd_hip_nearest_key_decode). */
+static inline uint32_t one_region_keys(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                       int32_t window, int32_t v, int use_v, int sgn, uint32_t *row)
 {
     const int32_t nf = db->nFiles;
-    for (int32_t f = 0; f < nf; f++) row[f] = -1;
-    if (ichr < 0 || ichr >= db->nCtg) return -1;
+    for (int32_t f = 0; f < nf; f++) row[f] = 0xffffffffu;
+    if (ichr < 0 || ichr >= db->nCtg) return 0xffffffffu;
     int32_t ws, we;
     igd_hip_nearest_widen(qs, qe, window, &ws, &we);
     const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
     const int32_t n1 = ws / nbp;
     int32_t n2 = (int32_t)((uint32_t)we - 1u) / nbp;
-    if (n1 < 0 || n1 > mT) return -1;                                      /* (no record ends behind the contig's last tile) */
+    if (n1 < 0 || n1 > mT) return 0xffffffffu;                             /* (no record ends behind the contig's last tile) */
     if (n2 > mT) n2 = mT;
     const int w = db->gType == 0 ? 3 : 4;
-    int64_t best = -1;
+    uint32_t best = 0xffffffffu;
     for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
         const int32_t cnt = db->nCnt[ichr][j];
         if (cnt <= 0) continue;
         const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
-        if (!rec) return -1;
+        if (!rec) return best;
         const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
         for (int32_t i = below(rec, w, cnt, we) - 1; i >= 0; i--) {
             const int32_t *r = rec + (size_t)i * (size_t)w;
             if ((int64_t)r[1] < lob) break;
             if (r[2] > ws && (!use_v || r[3] >= v)) {
                 if (r[0] < 0 || r[0] >= nf) continue;
-                const int64_t d = igd_hip_nearest_dist(qs, qe, r[1], r[2]);
-                if (row[r[0]] < 0 || d < row[r[0]]) row[r[0]] = (int32_t)d;
-                if (best < 0 || d < best) best = d;
+                const uint32_t d = sgn ? igd_hip_nearest_key(qs, qe, r[1], r[2]) : (uint32_t)igd_hip_nearest_dist(qs, qe, r[1], r[2]);
+                if (d < row[r[0]]) row[r[0]] = d;
+                if (d < best) best = d;
             }
         }
     }
-    return (int32_t)best;
+    return best;
+}
+
+static inline int32_t one_region_nearest(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                         int32_t window, int32_t v, int use_v, int32_t *row)
+{
+    return (int32_t)one_region_keys(db, m, tb, ichr, qs, qe, window, v, use_v, 0, (uint32_t *)row);
+}
+
+static inline int32_t one_region_nearest_signed(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                                int32_t window, int32_t v, int use_v, int32_t *row)
+{
+    const uint32_t best = one_region_keys(db, m, tb, ichr, qs, qe, window, v, use_v, 1, (uint32_t *)row);
+    for (int32_t f = 0; f < db->nFiles; f++) row[f] = igd_hip_nearest_key_decode((uint32_t)row[f]);
+    return igd_hip_nearest_key_decode(best);
 }
 
 typedef struct {
     const igdc_db *db; const igdc_map *m;
     const int32_t *ichr, *qs, *qe;
     int64_t lo, hi;
-    int32_t window, v; int use_v;
+    int32_t window, v; int use_v, sgn;
     int32_t *dist, *dmin;
     int io_failed;
 } nearest_job;
@@ -1181,7 +1197,9 @@ static void *nearest_run(void *arg)
     tb.ichr = -1;
     const size_t nf = (size_t)J->db->nFiles;
     for (int64_t i = J->lo; i < J->hi; i++) {
-        const int32_t d = one_region_nearest(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->window, J->v, J->use_v, J->dist + (size_t)i * nf);
+        int32_t *row = J->dist + (size_t)i * nf;
+        const int32_t d = J->sgn ? one_region_nearest_signed(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->window, J->v, J->use_v, row)
+                                 : one_region_nearest(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->window, J->v, J->use_v, row);
         if (J->dmin) J->dmin[i] = d;
     }
     J->io_failed = tb.failed;
@@ -1189,8 +1207,8 @@ static void *nearest_run(void *arg)
     return NULL;
 }
 
-int igdc_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                      int32_t window, int32_t v, int32_t *dist, int32_t *dmin)
+static int nearest_rows_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                             int32_t window, int32_t v, int sgn, int32_t *dist, int32_t *dmin)
 {
     if (!db || !m || nq < 0 || !igd_hip_nearest_window_valid(window) || (nq > 0 && (!ichr || !qs || !qe || (!dist && db->nFiles > 0)))) return -1;
     const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
@@ -1204,7 +1222,7 @@ int igdc_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
         memset(&job[k], 0, sizeof job[k]);
         job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
         job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].window = window; job[k].v = v; job[k].use_v = use_v;
+        job[k].window = window; job[k].v = v; job[k].use_v = use_v; job[k].sgn = sgn;
         job[k].dist = dist ? dist : &none; job[k].dmin = dmin;
     }
     for (int k = 1; k < T; k++) {
@@ -1216,6 +1234,18 @@ int igdc_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
     int bad = 0;
     for (int k = 0; k < T; k++) bad |= job[k].io_failed;
     return bad ? -1 : 0;
+}
+
+int igdc_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                      int32_t window, int32_t v, int32_t *dist, int32_t *dmin)
+{
+    return nearest_rows_host(db, m, ichr, qs, qe, nq, window, v, 0, dist, dmin);
+}
+
+int igdc_nearest_signed_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                             int32_t window, int32_t v, int32_t *sdist, int32_t *sdmin)
+{
+    return nearest_rows_host(db, m, ichr, qs, qe, nq, window, v, 1, sdist, sdmin);
 }
 
 #define NEAREST_HOST_ROW_BYTES ((int64_t)32 << 20)   /* igdc_nearest_sets_host: distance rows of one chunk of regions */
@@ -1248,6 +1278,41 @@ int igdc_nearest_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *
                 if (n_within) n_within[o + f]++;
                 if (n_overlap && d == 0) n_overlap[o + f]++;
                 if (sum_dist) sum_dist[o + f] += d;
+            }
+        }
+    }
+    free(dist); free(dmin);
+    return rc;
+}
+
+/* the signed rows of a chunk of regions (igdc_nearest_signed_host), each word counted into its bin of its set's histogram */
+int igdc_nearest_hist_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                           const int64_t *set_off, int32_t nsets, int32_t window, int32_t v, const int32_t *edges, int32_t ne,
+                           int64_t *hist)
+{
+    if (!db || !m || nsets < 0 || !igd_hip_nearest_window_valid(window) || !igd_hip_nearest_edges_valid(edges, ne) ||
+        (nsets > 0 && (!set_off || set_off[0] != 0 || !hist))) return -1;
+    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
+    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) return -1;
+    const int64_t nf = db->nFiles, nC = nf + 1, nq = nsets > 0 ? set_off[nsets] : 0;
+    const size_t setWords = (size_t)(ne + 1) * (size_t)nC;
+    int64_t chunk = NEAREST_HOST_ROW_BYTES / (4 * (nf > 0 ? nf : 1));
+    chunk = chunk < 1 ? 1 : chunk > nq ? nq : chunk;
+    int32_t *dist = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk * nf + 1)), *dmin = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk + 1));
+    if (!dist || !dmin) { free(dist); free(dmin); return -1; }
+    if (nsets > 0) memset(hist, 0, sizeof(int64_t) * (size_t)nsets * setWords);
+    int rc = 0;
+    int32_t k = 0;
+    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += chunk) {
+        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
+        rc = igdc_nearest_signed_host(db, m, ichr + c0, qs + c0, qe + c0, n, window, v, dist, dmin);
+        for (int64_t i = 0; i < n && rc == 0; i++) {
+            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
+            const int32_t *row = dist + (size_t)i * (size_t)nf;
+            int64_t *h = hist + (size_t)k * setWords;
+            for (int64_t f = 0; f < nC; f++) {
+                const int32_t x = f < nf ? row[f] : dmin[i];
+                if (x != IGD_HIP_NEAREST_NO_RECORD) h[(size_t)igd_hip_nearest_bin(edges, ne, x) * (size_t)nC + (size_t)f]++;
             }
         }
     }

@@ -40,6 +40,9 @@ PermutationNearestSummary = collections.namedtuple(
     "PermutationNearestSummary", "within_mean within_sd within_z within_n_ge nlog10_p_within_upper mean_dist dist_mean dist_sd dist_z n_def "
     "dist_n_le nlog10_p_dist_lower")
 NEAREST_MAX_WINDOW = 1 << 30                         # IGD_HIP_NEAREST_MAX_WINDOW
+NEAREST_NO_RECORD = -2 ** 31                         # IGD_HIP_NEAREST_NO_RECORD: a signed distance where there is no record
+NEAREST_MAX_EDGES = 63                               # IGD_HIP_NEAREST_MAX_EDGES
+NearestHist = collections.namedtuple("NearestHist", "hist edges window")
 
 
 class MinOverlap(C.Structure):
@@ -534,6 +537,51 @@ def nearest_sets_host(igd_path, ichr, qs, qe, set_off, window, value_filter=None
             raise IgdError("nearest_sets_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
                            % (NEAREST_MAX_WINDOW, igd_path))
         return NearestSets(*out, int(window))
+
+
+def _edges(edges, what):
+    """1 .. 63 strictly ascending int32 edges (the native call refuses the same lists)"""
+    e = np.asarray(edges)
+    if e.ndim != 1 or not 1 <= len(e) <= NEAREST_MAX_EDGES or e.dtype.kind not in "iu":
+        raise IgdError("%s: edges must be 1 to %d integers" % (what, NEAREST_MAX_EDGES))
+    e = e.astype(np.int64)
+    if (e < -2 ** 31).any() or (e >= 2 ** 31).any() or (np.diff(e) <= 0).any():
+        raise IgdError("%s: edges must be strictly ascending int32 values" % what)
+    return np.ascontiguousarray(e, dtype=np.int32)
+
+
+def nearest_signed_host(igd_path, ichr, qs, qe, window, value_filter=None):
+    """Database.nearest_signed() on the host (igdc_nearest_signed_host; no device is touched):
+    (sdist int32[nq, nfiles], sdmin int32[nq])."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    if len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("nearest_signed_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    with _HostDb(igd_path, "nearest_signed_host") as h:
+        sdist, sdmin = np.empty((len(qs), h.nfiles), np.int32), np.empty(len(qs), np.int32)
+        if h.L.igdc_nearest_signed_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _window(window, "nearest_signed_host"),
+                                        _value_filter(value_filter), _ptr(sdist), _ptr(sdmin)) != 0:
+            raise IgdError("nearest_signed_host: a window outside 0 .. %d, or a tile of %s could not be read" % (NEAREST_MAX_WINDOW, igd_path))
+        return sdist, sdmin
+
+
+def nearest_hist_host(igd_path, ichr, qs, qe, set_off, window, edges, value_filter=None):
+    """Database.nearest_hist() on the host (igdc_nearest_hist_host; no device is touched): a NearestHist."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+    edges = _edges(edges, "nearest_hist_host")
+    nsets = len(set_off) - 1
+    if nsets < 0:
+        raise IgdError("nearest_hist_host: set_off needs nsets + 1 entries")
+    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("nearest_hist_host: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
+    with _HostDb(igd_path, "nearest_hist_host") as h:
+        hist = np.empty((nsets, len(edges) + 1, h.nfiles + 1), np.int64)
+        if h.L.igdc_nearest_hist_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets,
+                                      _window(window, "nearest_hist_host"), _value_filter(value_filter), _ptr(edges), len(edges),
+                                      _ptr(hist)) != 0:
+            raise IgdError("nearest_hist_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
+                           % (NEAREST_MAX_WINDOW, igd_path))
+        return NearestHist(hist, edges, int(window))
 
 
 def nearest_summary(ns):
@@ -1242,6 +1290,64 @@ class Database:
         (int32[nq], may be None) are overwritten.  nq above igd_hip_max_batch() is refused: split the batch."""
         _chk(self._H.igd_hip_nearest_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), _window(window, "nearest_dev"), _value_filter(value_filter),
                                          d_dist, d_dmin, stream), "igd_hip_nearest_dev")
+
+    # ---- signed nearest distances and their histogram -------------------------------------
+    def nearest_signed(self, ichr, qs, qe, window, value_filter=None, sdist=None):
+        """nearest() with a side (igd_hip_nearest_signed; the definitions are in include/igd_hip.h): (sdist int32[nq, nfiles],
+        sdmin int32[nq]).  sdist[q, f] is 0 where region q overlaps a record of file f, -d where the nearest record within the
+        window lies upstream (at lower coordinates) and +d where it lies downstream, d being nearest()'s distance; at equal d on
+        both sides upstream wins; NEAREST_NO_RECORD (-2^31) where file f has no record within the window.  sdmin[q] is the
+        row's entry of smallest d, decided the same way.  sdist (int32[nq, nfiles], C order), when given, is overwritten."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        if len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("nearest_signed: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+        nq = len(qs)
+        if sdist is None:
+            sdist = np.empty((nq, self.nfiles), np.int32)
+        elif sdist.dtype != np.int32 or sdist.shape != (nq, self.nfiles) or not sdist.flags.c_contiguous:
+            raise IgdError("nearest_signed: sdist must be a C-ordered int32[%d, %d]" % (nq, self.nfiles))
+        sdmin = np.empty(nq, np.int32)
+        _chk(self._H.igd_hip_nearest_signed(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, _window(window, "nearest_signed"),
+                                            _value_filter(value_filter), _ptr(sdist), _ptr(sdmin)), "igd_hip_nearest_signed")
+        return sdist, sdmin
+
+    def nearest_hist(self, ichr, qs, qe, set_off, window, edges, value_filter=None, hist=None):
+        """The histogram of nearest_signed()'s distances per region set and dataset (igd_hip_nearest_hist; sets as
+        search_sets()): NearestHist(hist, edges, window) with hist int64[nsets, len(edges) + 1, nfiles + 1].  edges are 1 to
+        63 strictly ascending int32 values; bin b counts the regions whose signed distance x has exactly b edges <= x (bin 0:
+        below edges[0], the last bin: at or above edges[-1]); the last column is the any-dataset column, built from sdmin.
+        Regions without a record within the window are in no bin: hist.sum(axis=1) is nearest_sets().n_within.  The distance
+        rows never leave the device.  hist, when given (C order), is overwritten."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+        edges = _edges(edges, "nearest_hist")
+        nsets = len(set_off) - 1
+        if nsets < 0:
+            raise IgdError("nearest_hist: set_off needs nsets + 1 entries")
+        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("nearest_hist: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
+        shape = (nsets, len(edges) + 1, self.nfiles + 1)
+        if hist is None:
+            hist = np.empty(shape, np.int64)
+        elif hist.dtype != np.int64 or hist.shape != shape or not hist.flags.c_contiguous:
+            raise IgdError("nearest_hist: hist must be a C-ordered int64[%d, %d, %d]" % shape)
+        _chk(self._H.igd_hip_nearest_hist(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, _window(window, "nearest_hist"),
+                                          _value_filter(value_filter), _ptr(edges), len(edges), _ptr(hist)), "igd_hip_nearest_hist")
+        return NearestHist(hist, edges, int(window))
+
+    def nearest_hist_files(self, paths, window, edges, value_filter=None):
+        """One region set per BED file (read as `igd search -q` reads it): the NearestHist of nearest_hist()."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.nearest_hist(cat[0], cat[1], cat[2], set_off, window, edges, value_filter)
+
+    def nearest_signed_dev(self, d_ichr, d_qs, d_qe, nq, window, d_sdist, d_sdmin=None, value_filter=None, stream=None):
+        """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_sdist (int32[nq * nfiles]) and d_sdmin
+        (int32[nq], may be None) are overwritten.  nq above igd_hip_max_batch() is refused: split the batch."""
+        _chk(self._H.igd_hip_nearest_signed_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), _window(window, "nearest_signed_dev"),
+                                                _value_filter(value_filter), d_sdist, d_sdmin, stream), "igd_hip_nearest_signed_dev")
 
     # ---- values of the overlapping records per region and dataset -------------------------
     def map_values(self, ichr, qs, qe, op="sum", value_filter=None, count=None, agg=None):

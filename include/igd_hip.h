@@ -274,8 +274,7 @@ int32_t igd_hip_member_grid(int64_t nq);
  * `stream` (NULL: the engine's own) without waiting; d_dist and d_dmin (may be NULL) are overwritten.
  * Blocking (but for _dev), one device.  IGD_HIP_ERR_ARG -- a missing array, a bad set_off, W out of range -- comes before
  * anything of the caller's is written.
- * Not done: an unbounded nearest, signed or upstream/downstream distances, distance histograms, a minimum overlap, several
- * devices, the permutation null of a distance statistic. */
+ * Not done: an unbounded nearest, a minimum overlap, several devices, the permutation null of a distance statistic. */
 #define IGD_HIP_NEAREST_MAX_WINDOW ((int32_t)1 << 30)
 static inline IGD_HIP_OV_HD_ int igd_hip_nearest_window_valid(int64_t window) { return window >= 0 && window <= IGD_HIP_NEAREST_MAX_WINDOW; }
 /* d of one (region, record) pair */
@@ -301,6 +300,70 @@ int igd_hip_nearest_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_
 /* Workgroups (of four waves) igd_nearest_rows is launched with for nq regions: a wave meets a second region only when nq
  * exceeds four times this number (tests). */
 int32_t igd_hip_nearest_grid(int64_t nq);
+
+/* Signed nearest distances and their histogram per set and dataset: on which side the nearest record lies
+ * (`bedtools closest -D ref`) and how the distances are distributed (GenomicDistributions' calcFeatureDist).  THE DEFINITIONS
+ * (the one place: kernels igd_nearest_rows<., ., true> and igd_nearest_hist, igdc_nearest_signed_host / igdc_nearest_hist_host
+ * and the tests' numpy reference agree on every integer).  With d = igd_hip_nearest_dist(qs, qe, s, e) as above:
+ *     side         with a = s - qe and b = qs - e in 64 bits, a record with d > 0 lies DOWNSTREAM if a >= b, else UPSTREAM.  The
+ *                  formula is applied literally to zero-length and inverted regions.  There is no strand: upstream means lower
+ *                  coordinates.
+ *     key          2 d + (d > 0 && downstream), unsigned 32-bit (igd_hip_nearest_key).  d <= 2^30, so key <= 2^31 + 1 <
+ *                  0xffffffff, which stays "none".  The nearest record of file f is the one of MINIMUM KEY over the records
+ *                  within the window (d <= W; with a value filter the passing ones): at equal d on both sides upstream wins.
+ *                  The minimum of a key does not depend on the order of the records.
+ *     sdist[q][f]  int32: IGD_HIP_NEAREST_NO_RECORD = INT32_MIN when there is none; otherwise -(key >> 1) for an even non-zero
+ *                  key, +(key >> 1) for an odd key, 0 for key 0 (igd_hip_nearest_key_decode).
+ *     sdmin[q]     the same decoding of the minimum key over the files.
+ *     identities   abs(sdist) == dist wherever dist >= 0, and sdist == NO_RECORD iff dist == -1; the same pair for sdmin, dmin.
+ *     edges        int32[ne], strictly ascending, 1 <= ne <= IGD_HIP_NEAREST_MAX_EDGES = 63; anything else is IGD_HIP_ERR_ARG.
+ *     bin(x)       #{k : edges[k] <= x}, in 0 .. ne: bin 0 is "below edges[0]", bin ne "at or above the last edge".
+ *     hist         int64[nsets][ne + 1][nFiles + 1]: hist[k][b][f] = the regions q of set k with sdist[q][f] != NO_RECORD and
+ *                  bin(sdist[q][f]) == b; column nFiles is built from sdmin.  Regions with no record within the window are in
+ *                  no bin: hist.sum(axis = 1) == igd_hip_nearest_sets' n_within, and with edges = (0, 1) bin 1 is n_overlap.
+ * igd_hip_nearest_signed / _signed_dev: the chunks, checks and "a call defines every word" of igd_hip_nearest / _dev; sdmin may
+ * be NULL.  igd_hip_nearest_hist: the groups and chunks of igd_hip_nearest_sets -- whole sets are taken while (ne + 1) x
+ * (nFiles + 1) words per set fit the row budget of igd_hip_support_sets, a set may be cut by a chunk, kernel igd_nearest_hist adds
+ * every chunk's rows into the resident histogram; the rows never leave the device and hist is copied out once per group.
+ * nsets == 0 writes nothing; without regions or without files every word of hist is 0.  IGD_HIP_ERR_ARG comes before anything
+ * of the caller's is written.
+ * Not done: an unbounded nearest, both-sides rows (the nearest record upstream AND downstream), the permutation null of a
+ * bin, several devices. */
+#define IGD_HIP_NEAREST_NO_RECORD INT32_MIN
+#define IGD_HIP_NEAREST_MAX_EDGES 63
+/* key of one (region, record) pair */
+static inline IGD_HIP_OV_HD_ uint32_t igd_hip_nearest_key(int32_t qs, int32_t qe, int32_t start, int32_t end)
+{
+    if (start < qe && end > qs) return 0;
+    const int64_t a = (int64_t)start - (int64_t)qe, b = (int64_t)qs - (int64_t)end;
+    return a >= b ? (uint32_t)(2 * (a + 1) + 1) : (uint32_t)(2 * (b + 1));
+}
+/* sdist of a minimum key (0xffffffff: none) */
+static inline IGD_HIP_OV_HD_ int32_t igd_hip_nearest_key_decode(uint32_t key)
+{
+    const int32_t d = (int32_t)(key >> 1);
+    return key == 0xffffffffu ? IGD_HIP_NEAREST_NO_RECORD : (key & 1u) ? d : -d;
+}
+/* bin of x: the number of edges <= x */
+static inline IGD_HIP_OV_HD_ int igd_hip_nearest_bin(const int32_t *edges, int ne, int32_t x)
+{
+    int b = 0;
+    while (b < ne && edges[b] <= x) b++;
+    return b;
+}
+/* 1 <= ne <= IGD_HIP_NEAREST_MAX_EDGES strictly ascending edges */
+static inline int igd_hip_nearest_edges_valid(const int32_t *edges, int64_t ne)
+{
+    if (!edges || ne < 1 || ne > IGD_HIP_NEAREST_MAX_EDGES) return 0;
+    for (int64_t k = 1; k < ne; k++) if (edges[k] <= edges[k - 1]) return 0;
+    return 1;
+}
+int igd_hip_nearest_signed(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window,
+                           int32_t v, int32_t *sdist, int32_t *sdmin);
+int igd_hip_nearest_signed_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq,
+                               int32_t window, int32_t v, int32_t *d_sdist, int32_t *d_sdmin, void *stream);
+int igd_hip_nearest_hist(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                         int32_t nsets, int32_t window, int32_t v, const int32_t *edges, int32_t ne, int64_t *hist);
 
 /* Values of the overlapping records per region and dataset: how many records of every file lie under each region and what they
  * are worth -- `bedtools map -c 5 -o count,sum,min,max,mean`, the regions x datasets feature matrix.  THE DEFINITIONS (the one
