@@ -216,6 +216,13 @@ def hip():
         L.igd_hip_nearest_signed_dev.argtypes = L.igd_hip_nearest_dev.argtypes
         L.igd_hip_nearest_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_void_p, C.c_int32, C.c_void_p]
+        # the flanks: db, ichr, qs, qe, nq, window, measure, v, up, down, upmin, downmin [, stream]; the relative-distance
+        # histogram: ..., set_off, nsets, window, measure, v, nbins, hist
+        L.igd_hip_flank.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_flank_dev.argtypes = L.igd_hip_flank.argtypes + [C.c_void_p]
+        L.igd_hip_flank_reldist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int,
+                                            C.c_int32, C.c_int32, C.c_void_p]
         # the fused route and the permutation null of the distances: as igd_hip_nearest_sets / db, ichr, qs, qe, nq, ctg_len, mode,
         # seed, nperm, window, v, n_within, n_overlap, sum_dist
         L.igd_hip_nearest_sets_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -371,6 +378,12 @@ def _bind_core(L):
     L.igdc_nearest_signed_host.argtypes = L.igdc_nearest_host.argtypes
     L.igdc_nearest_hist_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    # the flanks: db, map, ichr, qs, qe, nq, window, measure, v, up, down, upmin, downmin; the relative-distance histogram: db,
+    # map, ichr, qs, qe, set_off, nsets, window, measure, v, nbins, hist
+    L.igdc_flank_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.igdc_flank_reldist_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_int, C.c_int32, C.c_int32, C.c_void_p]
     # values of the overlapping records on the host: db, map, ichr, qs, qe, nq, op, v, count, agg / ..., set_off, nsets, op, v,
     # n_hit, pairs, agg_sum / n_hit, pairs, agg_sum, n, op, mean_region, mean_pair
     L.igdc_map_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_void_p,

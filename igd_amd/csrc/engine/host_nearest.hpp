@@ -13,7 +13,7 @@
 // the regions of a group go through in the same chunks -- a set may be cut by a chunk, its statistics are sums over regions --
 // and per chunk igd_nearest_reduce adds the rows into the group's three resident matrices, by a slice table cut here: a slice
 // is at most IGD_NEAREST_SLICE regions of one set.  The rows never leave the device; the matrices are copied out once per group.
-// The signed forms are the same three bodies (nearest_rows_dev, nearest_rows_host, nearest_set_groups) with SIGNED = true:
+// The signed forms are the same bodies (nearest_rows_dev, nearest_rows_host; nearest_set_groups with its row kernel) with SIGNED = true:
 // the rows hold signed distances, the wide form's second kernel is igd_nearest_rowdecode and always runs, and the group driver's
 // reduction is igd_nearest_hist into ONE resident matrix of (ne + 1) x (nFiles + 1) words per set, with the slices cut as for
 // igd_nearest_reduce: at most IGD_NEAREST_SLICE = 256 regions, so the kernel's u32 LDS counters hold at most 256.
@@ -34,10 +34,10 @@ static int64_t nearest_row_bytes(void)
 // region only when nq exceeds the grid's waves)
 extern "C" int32_t igd_hip_nearest_grid(int64_t nq) { return items_grid(nq, IGD_SETS_WG / IGD_WAVE); }
 
-// regions per chunk of the host forms
-static int64_t nearest_step(int64_t nF)
+// regions per chunk of the host forms (nRows rows of nF words per region: two in host_flank.hpp)
+static int64_t nearest_step(int64_t nF, int nRows = 1)
 {
-    const int64_t byRows = nearest_row_bytes() / ((nF > 0 ? nF : 1) * 4);
+    const int64_t byRows = nearest_row_bytes() / ((nF > 0 ? nF : 1) * 4 * nRows);
     const int64_t step = max_batch();
     return byRows < step ? (byRows < 1 ? 1 : byRows) : step;
 }
@@ -154,19 +154,20 @@ extern "C" int igd_hip_nearest_signed(igd_hip_db *db, const int32_t *ichr, const
     return nearest_rows_host<true>("igd_hip_nearest_signed", db, ichr, qs, qe, nq, window, v, sdist, sdmin);
 }
 
-// The group and chunk driver of igd_hip_nearest_sets and igd_hip_nearest_hist (the arguments are checked, there are regions
-// and files).  Per set there are nMat result rows of matRow 64-bit words, kept in d_nrStat as nMat matrices of rows x matRow
-// words: whole sets are taken while they fit sets_row_bytes(); their regions go through in chunks of nearest_step() -- the
-// (SIGNED) rows and dmin[] of a chunk stay in d_nrDist / d_nrMin -- and reduce(gx, gy, ns, rows, st) launches the kernel that
-// adds the chunk's rows into the matrices by the slice table in d_nrSlices; matrix i is copied out to outs[i] (may be NULL)
-// once per group.
-template <bool SIGNED, typename Reduce>
-static int nearest_set_groups(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
-                              int32_t nsets, int32_t window, int32_t v, int nMat, int64_t matRow, int64_t *const *outs, Reduce &&reduce)
+// The group and chunk driver of igd_hip_nearest_sets, igd_hip_nearest_hist and igd_hip_flank_reldist (the arguments are
+// checked, there are regions and files).  Per set there are nMat result rows of matRow 64-bit words, kept in d_nrStat as nMat
+// matrices of rows x matRow words: whole sets are taken while they fit sets_row_bytes(); their regions go through in chunks of
+// `step` regions -- fill(m, st) launches the row kernel over the m staged regions of a chunk, whose nRows rows per region (one:
+// the (signed) distances; two: the flanks) and as many minima stay in d_nrDist / d_nrMin, row after row -- and reduce(grid, ns,
+// rows, m, st) launches the kernel that adds the chunk's rows into the matrices by the slice table in d_nrSlices; matrix i is
+// copied out to outs[i] (may be NULL) once per group.
+template <typename Fill, typename Reduce>
+static int nearest_set_groups(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                              int32_t nsets, int64_t step, int nRows, int nMat, int64_t matRow, int64_t *const *outs, Fill &&fill,
+                              Reduce &&reduce)
 {
     int rc;
     const int64_t nF = db->nFiles, nC = nF + 1;
-    const int64_t step = nearest_step(nF);
     const int64_t rowCap = sets_row_bytes() / (nMat * matRow * 8) > 0 ? sets_row_bytes() / (nMat * matRow * 8) : 1;
     const int gx = (int)((nC + IGD_WAVE - 1) / IGD_WAVE);
     HIPCHK(hipSetDevice(db->device));
@@ -190,15 +191,15 @@ static int nearest_set_groups(const char *who, igd_hip_db *db, const int32_t *ic
                     slices.push_back(SetSlice{j - k0, (int32_t)(a - c0), (int32_t)((a + IGD_NEAREST_SLICE < b0 ? a + IGD_NEAREST_SLICE : b0) - c0), 0});
             }
             const int ns = (int)slices.size();
-            rc = ensure_nearest_ws(db, m * nF, m);
+            rc = ensure_nearest_ws(db, nRows * m * nF, nRows * m);
             if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
             if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
-            if (rc == IGD_HIP_OK) rc = nearest_rows_dev<SIGNED>(who, db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
+            if (rc == IGD_HIP_OK) rc = fill(m, st);
             if (rc != IGD_HIP_OK) return rc;
             HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
             int gy = IGD_NEAREST_REDUCE_WGS / gx;
             gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
-            reduce(dim3((unsigned)gx, (unsigned)gy), ns, rows, st);
+            reduce(dim3((unsigned)gx, (unsigned)gy), ns, rows, m, st);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
         }
@@ -228,8 +229,9 @@ extern "C" int igd_hip_nearest_sets(igd_hip_db *db, const int32_t *ichr, const i
         for (int64_t *o : outs) if (o) memset(o, 0, (size_t)nsets * (size_t)nC * 8);
         return IGD_HIP_OK;
     }
-    return nearest_set_groups<false>("igd_hip_nearest_sets", db, ichr, qs, qe, set_off, nsets, window, v, 3, nC, outs,
-                                     [&](dim3 grid, int ns, int64_t rows, hipStream_t st) {
+    return nearest_set_groups(db, ichr, qs, qe, set_off, nsets, nearest_step(nF), 1, 3, nC, outs, [&](int64_t m, hipStream_t st) {
+        return nearest_rows_dev<false>("igd_hip_nearest_sets", db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
+    }, [&](dim3 grid, int ns, int64_t rows, int64_t, hipStream_t st) {
         igd_nearest_reduce<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns, (u64 *)db->d_nrStat, rows * nC);
     });
 }
@@ -258,8 +260,9 @@ extern "C" int igd_hip_nearest_hist(igd_hip_db *db, const int32_t *ichr, const i
     if ((rc = dev_grow(db, &db->d_nrEdges, &db->nrEdgesCap, (int64_t)IGD_HIP_NEAREST_MAX_EDGES)) != IGD_HIP_OK) return rc;
     HIPCHK(hipMemcpyAsync(db->d_nrEdges, edges, (size_t)ne * 4, hipMemcpyHostToDevice, db->stream));
     int64_t *outs[1] = {hist};
-    return nearest_set_groups<true>("igd_hip_nearest_hist", db, ichr, qs, qe, set_off, nsets, window, v, 1, matRow, outs,
-                                    [&](dim3 grid, int ns, int64_t, hipStream_t st) {
+    return nearest_set_groups(db, ichr, qs, qe, set_off, nsets, nearest_step(nF), 1, 1, matRow, outs, [&](int64_t m, hipStream_t st) {
+        return nearest_rows_dev<true>("igd_hip_nearest_hist", db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
+    }, [&](dim3 grid, int ns, int64_t, int64_t, hipStream_t st) {
         igd_nearest_hist<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns, db->d_nrEdges, (int)ne, (u64 *)db->d_nrStat);
     });
 }

@@ -1631,6 +1631,74 @@ static void nearest_hist_files(char **paths, int32_t n, int32_t v, int setLines,
     free(q); free(ichr); free(qs); free(qe); free(off); free(hist);
 }
 
+/* ------------------------------- `igd search -q F -N <bp> -L <bins> [-E]` / `-Q <list> -N <bp> -L ..` ------- */
+/* Histogram of the relative distance (include/igd_hip.h has the definitions; `bedtools reldist`): per database file the query
+ * regions that have a record of the file on BOTH sides within W bp (n_flanked) and their number per bin of min(up, down) /
+ * (up + down), under the bins' lower bounds k / (2 B); one line per dataset, then the same for "any dataset".  The distances
+ * are measured between midpoints, with -E between edges.  -v, routing and the layout of -Q blocks as -N: the host answers with
+ * igdc_flank_reldist_host, the engine with ONE igd_hip_flank_reldist call. */
+static void flank_reldist_files(char **paths, int32_t n, int32_t v, int setLines, int32_t window, int measure, int32_t nbins)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const int32_t nfiles = IGD->nFiles;
+    const size_t nC = (size_t)nfiles + 1, nB = (size_t)nbins;
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
+    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    int64_t *hist = (int64_t *)calloc((size_t)(n ? n : 1) * nB * nC, sizeof(int64_t));
+    off[0] = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (q[k].n) {
+            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+        }
+        off[k + 1] = off[k] + q[k].n;
+    }
+    int onHost = 0;
+    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
+    if (hm) {
+        double t0 = now_s();
+        onHost = igdc_flank_reldist_host(g_core, hm, ichr, qs, qe, off, n, window, measure, ev, nbins, hist) == 0;
+        igdc_map_close(hm);
+        if (onHost) phase("histogram of the relative distances on the host (small files)", &t0);
+    }
+    if (!onHost && nq > 0) {                          /* (after a read error too: the engine reads the file its own way) */
+        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
+        double t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_flank_reldist(dev, ichr, qs, qe, off, n, window, measure, ev, nbins, hist);
+            if (rc != IGD_HIP_OK) engine_failed("relative-distance histogram", rc);
+            phase("histogram of the relative distances of the query sets (H2D + kernels + D2H)", &t0);
+        }
+    }
+    for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
+        const int64_t *h = hist + (size_t)k * nB * nC;
+        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        printf("index\tn_flanked");
+        for (int b = 0; b < nbins; b++) printf("\t%.4f", (double)b / (double)(2 * nbins));
+        printf("\tFile\n");
+        for (int32_t i = 0; i <= nfiles; i++) {       /* (i = nfiles: the any-dataset column) */
+            int64_t nfl = 0;
+            for (size_t b = 0; b < nB; b++) nfl += h[b * nC + (size_t)i];
+            if (i < nfiles) printf("%d\t%lld", (int)i, (long long)nfl);
+            else printf("Any dataset within %d bp: %lld of %lld", (int)window, (long long)nfl, (long long)q[k].n);
+            for (size_t b = 0; b < nB; b++) printf("\t%lld", (long long)h[b * nC + (size_t)i]);
+            if (i < nfiles) printf("\t%s\n", IGD->finfo[i].fileName);
+            else printf("\n");
+        }
+    }
+    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    free(q); free(ichr); free(qs); free(qe); free(off); free(hist);
+}
+
 /* ------------------------------- `igd search -q F -V <op>` / `-Q <list> -V <op>` ------- */
 /* Values of the overlapping records per dataset (include/igd_hip.h has the definitions): per database file the query regions
  * with a counted record (n_hit), the counted (region, record) pairs (pairs) and a mean -- of the per-region count, sum, minimum
@@ -1806,6 +1874,10 @@ static int usage_search(void)
             "    -H <e1,e2,...>             with -N: instead, per dataset the regions with a record within <bp> and their number per\n"
             "                               bin of the SIGNED distance to the nearest record (negative: it lies upstream); 1 to 63\n"
             "                               ascending integer edges, bins <e1, [e1,e2), .., >=e_last\n"
+            "    -L <bins> [-E]             with -N: instead, per dataset the regions with a record on BOTH sides within <bp> and their\n"
+            "                               number per bin of the relative distance min(up, down) / (up + down) in [0, 0.5], as\n"
+            "                               bedtools reldist (1 to 64 bins; 50: its bins of 0.01); distances between midpoints,\n"
+            "                               with -E between edges\n"
             "    -V <op>                    with -q or -Q: per dataset, the query regions with an overlapping record, the overlapping\n"
             "                               (region, record) pairs and the mean over those regions of the records' count, sum, min\n"
             "                               or max of the value column; mean: the mean value over the pairs\n"
@@ -1861,6 +1933,8 @@ int igd_search(int argc, char **argv)                                        /* 
     char *nearArg = NULL;                                                             /* -N (see nearest_files) */
     char *distArg = NULL;                                                             /* -D (see permute_nearest_table) */
     char *histArg = NULL;                                                             /* -H (see nearest_hist_files) */
+    char *binsArg = NULL;                                                             /* -L (see flank_reldist_files) */
+    int flankL = 0, flankEdges = 0;                                                   /* -L, -E given */
     char *mapArg = NULL;                                                              /* -V (see map_files) */
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -1912,6 +1986,11 @@ int igd_search(int argc, char **argv)                                        /* 
             if (i + 1 >= argc) { printf("Not supported: -H without a list of edges\n"); return EX_USAGE; }
             histArg = argv[i + 1];
             i++;                                      /* (the list is not an option: "-H -500,0,500" is a list) */
+        } else if (strcmp(a, "-L") == 0) {            /* (not the reference's: histogram of the relative distances of -N, see flank_reldist_files) */
+            flankL = 1;
+            if (i + 1 < argc) { binsArg = argv[i + 1]; i++; }
+        } else if (strcmp(a, "-E") == 0) {            /* (not the reference's: -L between edges) */
+            flankEdges = 1;
         } else if (strcmp(a, "-V") == 0) {            /* (not the reference's: values of the overlapping records, see map_files) */
             if (i + 1 >= argc) { printf("Not supported: -V without an op (count, sum, min, max or mean)\n"); return EX_USAGE; }
             mapArg = argv[i + 1];
@@ -1969,6 +2048,25 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported: -V %s on a database without values (gType 0); -V count works there\n", mapArg);
             return EX_USAGE;
         }
+    }
+    int32_t flankBins = 0;                                                    /* -L, -E: every refusal is a usage error */
+    if (flankL || flankEdges) {
+        char *end = NULL;
+        const long long nb = binsArg ? strtoll(binsArg, &end, 10) : 0;
+        const char *why = NULL;
+        if (!flankL) why = "-E without -L";
+        else if (!nearArg) why = "-L without -N";
+        else if (histArg || permArg || distArg || minov) why = "-L together with -H, -P, -D, -O, -A or -B";
+        else if (!binsArg) why = "-L without a number of bins";
+        if (why) {
+            printf("Not supported: %s\n", why);
+            return EX_USAGE;
+        }
+        if (binsArg[0] < '0' || binsArg[0] > '9' || *end || !igd_hip_flank_bins_valid(nb)) {
+            printf("Not supported: -L %s (1 to %d bins)\n", binsArg, (int)IGD_HIP_FLANK_MAX_BINS);
+            return EX_USAGE;
+        }
+        flankBins = (int32_t)nb;
     }
     int32_t histEdges[IGD_HIP_NEAREST_MAX_EDGES];                             /* -H: every refusal is a usage error */
     int histNe = 0;
@@ -2043,12 +2141,14 @@ int igd_search(int argc, char **argv)                                        /* 
         for (int32_t k = 0; k < n; k++) free(paths[k]);
         free(paths);
     } else if (nearArg && mode == 1) {
-        if (histArg) nearest_hist_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10), histEdges, histNe);
+        if (flankL) flank_reldist_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10), flankEdges ? IGD_HIP_FLANK_EDGES : IGD_HIP_FLANK_MIDPOINTS, flankBins);
+        else if (histArg) nearest_hist_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10), histEdges, histNe);
         else nearest_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10));
     } else if (nearArg) {
         int32_t n = 0;
         char **paths = read_list(listName, &n);
-        if (n >= 0 && histArg) nearest_hist_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10), histEdges, histNe);
+        if (n >= 0 && flankL) flank_reldist_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10), flankEdges ? IGD_HIP_FLANK_EDGES : IGD_HIP_FLANK_MIDPOINTS, flankBins);
+        else if (n >= 0 && histArg) nearest_hist_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10), histEdges, histNe);
         else if (n >= 0) nearest_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10));
         for (int32_t k = 0; k < n; k++) free(paths[k]);
         free(paths);

@@ -219,6 +219,16 @@ int igdc_nearest_signed_host(const igdc_db *db, const igdc_map *m, const int32_t
 int igdc_nearest_hist_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                            const int64_t *set_off, int32_t nsets, int32_t window, int32_t v, const int32_t *edges, int32_t ne,
                            int64_t *hist);
+/* Flanking records per dataset and the relative-distance histogram (what igd_hip_flank and igd_hip_flank_reldist compute;
+ * include/igd_hip.h has the definitions): up and down (int32[nq * nFiles] each, both required when there are files), upmin and
+ * downmin (int32[nq], each may be NULL), -1 where there is none; hist (int64[nsets * nbins * (nFiles + 1)], column nFiles from
+ * upmin / downmin).  The walk of igdc_nearest_host with two words per file, threads over the regions.  0 on success; -1 as
+ * above, and for a measure that is neither IGD_HIP_FLANK_EDGES nor IGD_HIP_FLANK_MIDPOINTS or nbins outside 1 ..
+ * IGD_HIP_FLANK_MAX_BINS (nothing written). */
+int igdc_flank_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                    int32_t window, int measure, int32_t v, int32_t *up, int32_t *down, int32_t *upmin, int32_t *downmin);
+int igdc_flank_reldist_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                            const int64_t *set_off, int32_t nsets, int32_t window, int measure, int32_t v, int32_t nbins, int64_t *hist);
 /* mean[i] = sum_dist[i] / n_within[i] as a double, NaN where n_within[i] = 0.  Needs no database.  0, or -1 for a missing array. */
 int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t n, double *mean);
 /* Values of the overlapping records per region and dataset (what igd_hip_map and igd_hip_map_sets compute; include/igd_hip.h has

@@ -385,6 +385,7 @@ struct igd_hip_db {
 #include "engine/cooccur_dev.hpp"     // igd_bits_transpose, igd_bitrows_gram: bit rows into bit columns, popcount Gram product -- dataset co-occurrence
 #include "engine/permute_dev.hpp"     // igd_permute_regions, igd_perm_stats: shifted / shuffled region sets, column statistics of a row matrix -- permutation null
 #include "engine/nearest_dev.hpp"     // igd_nearest_rows, igd_nearest_reduce, igd_nearest_hist: the same walk over a widened interval, one (signed) distance row per region -- nearest record per dataset
+#include "engine/flank_dev.hpp"       // igd_flank_rows, igd_flank_reldist: the same walk with two minima per region and dataset -- the nearest record on each side, the relative-distance histogram
 #include "engine/nearest_fused_dev.hpp" // igd_nearest_slices: the same walk and table, folded into per-slice LDS accumulators -- the set statistics without the rows
 #include "engine/map_dev.hpp"         // igd_map_rows, igd_map_reduce: the same walk with the value words, count and sum / min / max rows per region -- values of the overlapping records
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
@@ -404,6 +405,7 @@ struct igd_hip_db {
 #include "engine/host_cooccur.hpp"    // igd_hip_cooccur / igd_hip_bits_transpose / igd_hip_bitrows_gram: chunks of regions, rows stay resident
 #include "engine/host_permute.hpp"    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: chunks of permutations, rows stay resident
 #include "engine/host_nearest.hpp"    // igd_hip_nearest / _dev / _sets, _signed / _signed_dev / _hist: chunks of regions within a row budget, the set statistics stay resident
+#include "engine/host_flank.hpp"      // igd_hip_flank / _dev / _reldist: the chunks and groups of host_nearest.hpp with two rows per region
 #include "engine/host_permute_nearest.hpp" // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: one fused launch per chunk, the null distribution of the distance statistics
 #include "engine/host_map.hpp"        // igd_hip_map / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile

@@ -230,6 +230,15 @@ int igd_hip_nearest_hist(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
     return fn ? fn(db, ichr, qs, qe, set_off, nsets, window, v, edges, ne, hist) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_flank_reldist(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                          int32_t nsets, int32_t window, int measure, int32_t v, int32_t nbins, int64_t *hist)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int32_t, int, int32_t,
+                        int32_t, int64_t *);
+    RESOLVE(fn_t, "igd_hip_flank_reldist");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, window, measure, v, nbins, hist) : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_map(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int op, int32_t v, int32_t *count,
                 int64_t *agg)
 {

@@ -1320,6 +1320,141 @@ int igdc_nearest_hist_host(const igdc_db *db, const igdc_map *m, const int32_t *
     return rc;
 }
 
+/* ---- flanking records per dataset and the relative-distance histogram (include/igd_hip.h has the definitions) -----------
+ * One region: one_region_keys' walk -- the same tiles, the same counted records -- with two unsigned words per file, 0xffffffff
+ * (= -1) for "none": igd_hip_flank_pair says on which side a counted record lies and how far, and it lowers that side's word.
+ * The minima over the files go to *upmin and *downmin. */
+static inline void one_region_flanks(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                     int32_t window, int measure, int32_t v, int use_v, uint32_t *up, uint32_t *down, uint32_t *upmin,
+                                     uint32_t *downmin)
+{
+    const int32_t nf = db->nFiles;
+    for (int32_t f = 0; f < nf; f++) up[f] = down[f] = 0xffffffffu;
+    *upmin = *downmin = 0xffffffffu;
+    if (ichr < 0 || ichr >= db->nCtg) return;
+    int32_t ws, we;
+    igd_hip_nearest_widen(qs, qe, window, &ws, &we);
+    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
+    const int32_t n1 = ws / nbp;
+    int32_t n2 = (int32_t)((uint32_t)we - 1u) / nbp;
+    if (n1 < 0 || n1 > mT) return;                                         /* (no record ends behind the contig's last tile) */
+    if (n2 > mT) n2 = mT;
+    const int w = db->gType == 0 ? 3 : 4;
+    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
+        const int32_t cnt = db->nCnt[ichr][j];
+        if (cnt <= 0) continue;
+        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
+        if (!rec) return;
+        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
+        for (int32_t i = below(rec, w, cnt, we) - 1; i >= 0; i--) {
+            const int32_t *r = rec + (size_t)i * (size_t)w;
+            if ((int64_t)r[1] < lob) break;
+            if (r[2] > ws && (!use_v || r[3] >= v)) {
+                if (r[0] < 0 || r[0] >= nf) continue;
+                uint32_t d = 0;
+                const int side = igd_hip_flank_pair(measure, window, qs, qe, r[1], r[2], &d);
+                if (side == IGD_HIP_FLANK_NEITHER) continue;
+                uint32_t *row = side == IGD_HIP_FLANK_UP ? up : down, *best = side == IGD_HIP_FLANK_UP ? upmin : downmin;
+                if (d < row[r[0]]) row[r[0]] = d;
+                if (d < *best) *best = d;
+            }
+        }
+    }
+}
+
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe;
+    int64_t lo, hi;
+    int32_t window, v; int use_v, measure;
+    int32_t *up, *down, *upmin, *downmin;
+    int io_failed;
+} flank_job;
+
+static void *flank_run(void *arg)
+{
+    flank_job *J = (flank_job *)arg;
+    tilebuf tb;
+    memset(&tb, 0, sizeof tb);
+    tb.ichr = -1;
+    const size_t nf = (size_t)J->db->nFiles;
+    for (int64_t i = J->lo; i < J->hi; i++) {
+        uint32_t um, dm;
+        one_region_flanks(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->window, J->measure, J->v, J->use_v,
+                          (uint32_t *)J->up + (size_t)i * nf, (uint32_t *)J->down + (size_t)i * nf, &um, &dm);
+        if (J->upmin) J->upmin[i] = (int32_t)um;
+        if (J->downmin) J->downmin[i] = (int32_t)dm;
+    }
+    J->io_failed = tb.failed;
+    free(tb.buf);
+    return NULL;
+}
+
+int igdc_flank_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                    int32_t window, int measure, int32_t v, int32_t *up, int32_t *down, int32_t *upmin, int32_t *downmin)
+{
+    if (!db || !m || nq < 0 || !igd_hip_nearest_window_valid(window) || !igd_hip_flank_measure_valid(measure) ||
+        (nq > 0 && (!ichr || !qs || !qe || ((!up || !down) && db->nFiles > 0)))) return -1;
+    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+    const int T = host_threads(nq);
+    flank_job job[64];
+    pthread_t th[64];
+    int started[64];
+    int32_t none[2] = {0, 0};                /* (a database without files: rows of no words) */
+    /* rows are disjoint per region: every thread writes its regions' rows straight into the caller's */
+    for (int k = 0; k < T; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
+        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
+        job[k].window = window; job[k].v = v; job[k].use_v = use_v; job[k].measure = measure;
+        job[k].up = up ? up : &none[0]; job[k].down = down ? down : &none[1]; job[k].upmin = upmin; job[k].downmin = downmin;
+    }
+    for (int k = 1; k < T; k++) {
+        started[k] = pthread_create(&th[k], NULL, flank_run, &job[k]) == 0;
+        if (!started[k]) flank_run(&job[k]);
+    }
+    flank_run(&job[0]);
+    for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
+    int bad = 0;
+    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
+    return bad ? -1 : 0;
+}
+
+/* the two rows of a chunk of regions (igdc_flank_host), each flanked pair counted into its bin of its set's histogram */
+int igdc_flank_reldist_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                            const int64_t *set_off, int32_t nsets, int32_t window, int measure, int32_t v, int32_t nbins, int64_t *hist)
+{
+    if (!db || !m || nsets < 0 || !igd_hip_nearest_window_valid(window) || !igd_hip_flank_measure_valid(measure) ||
+        !igd_hip_flank_bins_valid(nbins) || (nsets > 0 && (!set_off || set_off[0] != 0 || !hist))) return -1;
+    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
+    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) return -1;
+    const int64_t nf = db->nFiles, nC = nf + 1, nq = nsets > 0 ? set_off[nsets] : 0;
+    const size_t setWords = (size_t)nbins * (size_t)nC;
+    int64_t chunk = NEAREST_HOST_ROW_BYTES / (8 * (nf > 0 ? nf : 1));
+    chunk = chunk < 1 ? 1 : chunk > nq ? nq : chunk;
+    int32_t *rows = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * chunk * nf + 1)), *mins = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * chunk + 1));
+    if (!rows || !mins) { free(rows); free(mins); return -1; }
+    int32_t *up = rows, *down = rows + chunk * nf, *upmin = mins, *downmin = mins + chunk;
+    if (nsets > 0) memset(hist, 0, sizeof(int64_t) * (size_t)nsets * setWords);
+    int rc = 0;
+    int32_t k = 0;
+    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += chunk) {
+        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
+        rc = igdc_flank_host(db, m, ichr + c0, qs + c0, qe + c0, n, window, measure, v, up, down, upmin, downmin);
+        for (int64_t i = 0; i < n && rc == 0; i++) {
+            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
+            int64_t *h = hist + (size_t)k * setWords;
+            for (int64_t f = 0; f < nC; f++) {
+                const int32_t u = f < nf ? up[(size_t)i * (size_t)nf + (size_t)f] : upmin[i];
+                const int32_t d = f < nf ? down[(size_t)i * (size_t)nf + (size_t)f] : downmin[i];
+                if (igd_hip_flank_flanked(u, d)) h[(size_t)igd_hip_flank_bin(nbins, u, d) * (size_t)nC + (size_t)f]++;
+            }
+        }
+    }
+    free(rows); free(mins);
+    return rc;
+}
+
 int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t n, double *mean)
 {
     if (n < 0 || (n > 0 && (!n_within || !sum_dist || !mean))) return -1;

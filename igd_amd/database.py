@@ -43,6 +43,10 @@ NEAREST_MAX_WINDOW = 1 << 30                         # IGD_HIP_NEAREST_MAX_WINDO
 NEAREST_NO_RECORD = -2 ** 31                         # IGD_HIP_NEAREST_NO_RECORD: a signed distance where there is no record
 NEAREST_MAX_EDGES = 63                               # IGD_HIP_NEAREST_MAX_EDGES
 NearestHist = collections.namedtuple("NearestHist", "hist edges window")
+FLANK_EDGES = 0                                      # IGD_HIP_FLANK_EDGES
+FLANK_MIDPOINTS = 1                                  # IGD_HIP_FLANK_MIDPOINTS
+FLANK_MAX_BINS = 64                                  # IGD_HIP_FLANK_MAX_BINS
+FlankReldist = collections.namedtuple("FlankReldist", "hist nbins window measure")
 
 
 class MinOverlap(C.Structure):
@@ -582,6 +586,71 @@ def nearest_hist_host(igd_path, ichr, qs, qe, set_off, window, edges, value_filt
             raise IgdError("nearest_hist_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
                            % (NEAREST_MAX_WINDOW, igd_path))
         return NearestHist(hist, edges, int(window))
+
+
+def _measure(measure, what):
+    """"edges" / "midpoints" (or FLANK_EDGES / FLANK_MIDPOINTS) -> the native constant"""
+    if isinstance(measure, str) and measure in ("edges", "midpoints"):
+        return FLANK_EDGES if measure == "edges" else FLANK_MIDPOINTS
+    if not isinstance(measure, (str, bool)) and measure in (FLANK_EDGES, FLANK_MIDPOINTS):
+        return int(measure)
+    raise IgdError("%s: measure must be \"edges\" or \"midpoints\"" % what)
+
+
+def _nbins(nbins, what):
+    if isinstance(nbins, (bool, float)) or not isinstance(nbins, (int, np.integer)) or not 1 <= nbins <= FLANK_MAX_BINS:
+        raise IgdError("%s: nbins must be an integer from 1 to %d" % (what, FLANK_MAX_BINS))
+    return int(nbins)
+
+
+def _sets_args(ichr, qs, qe, set_off, what):
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+    if len(set_off) < 1:
+        raise IgdError("%s: set_off needs nsets + 1 entries" % what)
+    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("%s: set_off[-1] = %d, but %d / %d / %d regions given" % (what, set_off[-1], len(ichr), len(qs), len(qe)))
+    return ichr, qs, qe, set_off
+
+
+def flanks_host(igd_path, ichr, qs, qe, window, measure="midpoints", value_filter=None):
+    """Database.flanks() on the host (igdc_flank_host; no device is touched): (up, down int32[nq, nfiles], upmin, downmin
+    int32[nq])."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    if len(ichr) != len(qs) or len(qe) != len(qs):
+        raise IgdError("flanks_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    measure = _measure(measure, "flanks_host")
+    with _HostDb(igd_path, "flanks_host") as h:
+        up, down = np.empty((len(qs), h.nfiles), np.int32), np.empty((len(qs), h.nfiles), np.int32)
+        upmin, downmin = np.empty(len(qs), np.int32), np.empty(len(qs), np.int32)
+        if h.L.igdc_flank_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _window(window, "flanks_host"), measure,
+                               _value_filter(value_filter), _ptr(up), _ptr(down), _ptr(upmin), _ptr(downmin)) != 0:
+            raise IgdError("flanks_host: a window outside 0 .. %d, or a tile of %s could not be read" % (NEAREST_MAX_WINDOW, igd_path))
+        return up, down, upmin, downmin
+
+
+def flank_reldist_host(igd_path, ichr, qs, qe, set_off, window, nbins=50, measure="midpoints", value_filter=None):
+    """Database.flank_reldist() on the host (igdc_flank_reldist_host; no device is touched): a FlankReldist."""
+    ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "flank_reldist_host")
+    nbins, m = _nbins(nbins, "flank_reldist_host"), _measure(measure, "flank_reldist_host")
+    nsets = len(set_off) - 1
+    with _HostDb(igd_path, "flank_reldist_host") as h:
+        hist = np.empty((nsets, nbins, h.nfiles + 1), np.int64)
+        if h.L.igdc_flank_reldist_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets,
+                                       _window(window, "flank_reldist_host"), m, _value_filter(value_filter), nbins, _ptr(hist)) != 0:
+            raise IgdError("flank_reldist_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
+                           % (NEAREST_MAX_WINDOW, igd_path))
+        return FlankReldist(hist, nbins, int(window), m)
+
+
+def reldist_summary(fr):
+    """(n_flanked int64[nsets, nfiles + 1], fraction float64[nsets, nbins, nfiles + 1]) of a FlankReldist: the flanked regions per
+    set and dataset and the share of each bin among them (`bedtools reldist`'s fraction column), NaN where n_flanked is 0."""
+    hist = np.asarray(fr.hist, np.int64)
+    n = hist.sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        frac = np.where(n[:, None, :] > 0, hist / n[:, None, :].astype(np.float64), np.nan)
+    return n, frac
 
 
 def nearest_summary(ns):
@@ -1348,6 +1417,64 @@ class Database:
         (int32[nq], may be None) are overwritten.  nq above igd_hip_max_batch() is refused: split the batch."""
         _chk(self._H.igd_hip_nearest_signed_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), _window(window, "nearest_signed_dev"),
                                                 _value_filter(value_filter), d_sdist, d_sdmin, stream), "igd_hip_nearest_signed_dev")
+
+    # ---- flanking records per dataset and the relative-distance histogram ------------------
+    def flanks(self, ichr, qs, qe, window, measure="midpoints", value_filter=None, up=None, down=None):
+        """The nearest record of every dataset on EACH side of every region within `window` base pairs (igd_hip_flank; the
+        definitions are in include/igd_hip.h): (up, down int32[nq, nfiles], upmin, downmin int32[nq]), -1 where there is none.
+        measure "edges": distances as nearest()'s, between the region and the record, a record that overlaps the region is on
+        neither side (`bedtools closest -D ref -io -iu` / `-id`); "midpoints": between integer midpoints, an equal midpoint
+        counts as downstream at distance 0 (`bedtools reldist`).  Upstream means lower coordinates.  upmin / downmin are the
+        minima over the datasets.  up and down (int32[nq, nfiles], C order), when given, are overwritten."""
+        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        if len(ichr) != len(qs) or len(qe) != len(qs):
+            raise IgdError("flanks: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+        nq = len(qs)
+        rows = []
+        for name, r in (("up", up), ("down", down)):
+            if r is None:
+                r = np.empty((nq, self.nfiles), np.int32)
+            elif r.dtype != np.int32 or r.shape != (nq, self.nfiles) or not r.flags.c_contiguous:
+                raise IgdError("flanks: %s must be a C-ordered int32[%d, %d]" % (name, nq, self.nfiles))
+            rows.append(r)
+        upmin, downmin = np.empty(nq, np.int32), np.empty(nq, np.int32)
+        _chk(self._H.igd_hip_flank(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, _window(window, "flanks"), _measure(measure, "flanks"),
+                                   _value_filter(value_filter), _ptr(rows[0]), _ptr(rows[1]), _ptr(upmin), _ptr(downmin)), "igd_hip_flank")
+        return rows[0], rows[1], upmin, downmin
+
+    def flanks_dev(self, d_ichr, d_qs, d_qe, nq, window, d_up, d_down, d_upmin=None, d_downmin=None, measure="midpoints",
+                   value_filter=None, stream=None):
+        """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_up and d_down (int32[nq * nfiles]) and d_upmin,
+        d_downmin (int32[nq], each may be None) are overwritten.  nq above igd_hip_max_batch() is refused: split the batch."""
+        _chk(self._H.igd_hip_flank_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), _window(window, "flanks_dev"), _measure(measure, "flanks_dev"),
+                                       _value_filter(value_filter), d_up, d_down, d_upmin, d_downmin, stream), "igd_hip_flank_dev")
+
+    def flank_reldist(self, ichr, qs, qe, set_off, window, nbins=50, measure="midpoints", value_filter=None, hist=None):
+        """The histogram of the relative distance per region set and dataset (igd_hip_flank_reldist; sets as search_sets();
+        `bedtools reldist`): FlankReldist(hist, nbins, window, measure) with hist int64[nsets, nbins, nfiles + 1].  A region
+        that has a record of dataset f on both sides within the window (flanks(): up >= 0, down >= 0, up + down > 0) is counted
+        in bin min(nbins - 1, floor(2 nbins min(up, down) / (up + down))) of column f: flat under independence, piled at 0 under
+        association.  The last column is the any-dataset column, built from upmin / downmin.  hist.sum(axis=1) is the number
+        of flanked regions (igd_amd.reldist_summary gives the fractions).  The rows never leave the device.  hist, when given
+        (C order), is overwritten."""
+        ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "flank_reldist")
+        nbins, m = _nbins(nbins, "flank_reldist"), _measure(measure, "flank_reldist")
+        shape = (len(set_off) - 1, nbins, self.nfiles + 1)
+        if hist is None:
+            hist = np.empty(shape, np.int64)
+        elif hist.dtype != np.int64 or hist.shape != shape or not hist.flags.c_contiguous:
+            raise IgdError("flank_reldist: hist must be a C-ordered int64[%d, %d, %d]" % shape)
+        _chk(self._H.igd_hip_flank_reldist(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, shape[0], _window(window, "flank_reldist"),
+                                           m, _value_filter(value_filter), nbins, _ptr(hist)), "igd_hip_flank_reldist")
+        return FlankReldist(hist, nbins, int(window), m)
+
+    def flank_reldist_files(self, paths, window, nbins=50, measure="midpoints", value_filter=None):
+        """One region set per BED file (read as `igd search -q` reads it): the FlankReldist of flank_reldist()."""
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return self.flank_reldist(cat[0], cat[1], cat[2], set_off, window, nbins, measure, value_filter)
 
     # ---- values of the overlapping records per region and dataset -------------------------
     def map_values(self, ichr, qs, qe, op="sum", value_filter=None, count=None, agg=None):

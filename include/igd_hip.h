@@ -327,8 +327,7 @@ int32_t igd_hip_nearest_grid(int64_t nq);
  * every chunk's rows into the resident histogram; the rows never leave the device and hist is copied out once per group.
  * nsets == 0 writes nothing; without regions or without files every word of hist is 0.  IGD_HIP_ERR_ARG comes before anything
  * of the caller's is written.
- * Not done: an unbounded nearest, both-sides rows (the nearest record upstream AND downstream), the permutation null of a
- * bin, several devices. */
+ * Not done: an unbounded nearest, the permutation null of a bin, several devices. */
 #define IGD_HIP_NEAREST_NO_RECORD INT32_MIN
 #define IGD_HIP_NEAREST_MAX_EDGES 63
 /* key of one (region, record) pair */
@@ -364,6 +363,83 @@ int igd_hip_nearest_signed_dev(igd_hip_db *db, const int32_t *d_ichr, const int3
                                int32_t window, int32_t v, int32_t *d_sdist, int32_t *d_sdmin, void *stream);
 int igd_hip_nearest_hist(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
                          int32_t nsets, int32_t window, int32_t v, const int32_t *edges, int32_t ne, int64_t *hist);
+
+/* Flanking records per dataset and the relative-distance histogram: the nearest record on EACH side of every region
+ * (`bedtools closest -D ref -io -iu` / `-id`: the next gene on either side of a peak) and `bedtools reldist`, the relative-distance
+ * test of GenometriCorr.  THE DEFINITIONS (the one place: kernels igd_flank_rows and igd_flank_reldist, igdc_flank_host /
+ * igdc_flank_reldist_host and the tests' numpy reference agree on every integer).  A record (s, e) of file f is COUNTED for
+ * region (qs, qe) under window W when igd_hip_nearest counts it: igd_hip_nearest_dist(qs, qe, s, e) <= W, and with a value filter
+ * when value >= v.  Two measures, chosen per call:
+ *     IGD_HIP_FLANK_EDGES      with d, a = s - qe and b = qs - e as above, a counted record with d > 0 is DOWNSTREAM if a >= b,
+ *                              else UPSTREAM, at distance d; a record with d == 0 (overlapping) is on neither side.  W: 0 .. 2^30.
+ *     IGD_HIP_FLANK_MIDPOINTS  mid(x, y) = floor((x + y) / 2) in 64 bits (an arithmetic shift: bedtools' integer midpoint) and
+ *                              D = mid(s, e) - mid(qs, qe).  A counted record takes part only if |D| <= W (for a proper region
+ *                              and record |D| <= W implies d <= W; the conjunction keeps the formula literal for zero-length and
+ *                              inverted regions).  It is UPSTREAM at distance -D if D < 0 and DOWNSTREAM at distance D if
+ *                              D >= 0: an equal midpoint is "right", as reldist's lower_bound.
+ *     up[q][f]     int32: the minimum distance over the upstream records of file f that take part, -1 when there is none;
+ *     down[q][f]   the same over the downstream ones.  Edges: both >= 1.  Midpoints: up >= 1, down >= 0.  Every value is <= 2^30,
+ *                  so the unsigned word 0xffffffff stays "none" while minimising, as in igd_hip_nearest.
+ *     upmin[q], downmin[q]   the minima over the files (-1: none).
+ *     degenerate   the formulas are applied literally to zero-length and inverted regions; a region on an unknown contig has rows
+ *                  of -1; there is no strand (upstream means lower coordinates); a minimum does not depend on record order.
+ *     flanked      a pair (q, f) with up >= 0 && down >= 0 && up + down > 0 (igd_hip_flank_flanked).
+ *     bin          of a flanked pair, for B bins, 1 <= B <= IGD_HIP_FLANK_MAX_BINS = 64:
+ *                  min(B - 1, floor(2 B min(up, down) / (up + down))), 64-bit integer arithmetic, exact everywhere
+ *                  (igd_hip_flank_bin).  The relative distance min / (up + down) lies in [0, 0.5]; B = 50 gives reldist's bins of
+ *                  0.01, with 0.5 folded into the last.
+ *     hist         int64[nsets][B][nFiles + 1]: hist[k][b][f] = the regions q of set k whose pair (q, f) is flanked and in bin b;
+ *                  column nFiles is computed from upmin / downmin (any dataset).  hist.sum(axis = 1) is n_flanked.
+ * igd_hip_flank: up and down are int32[nq * nFiles] (both required when there are files), upmin and downmin int32[nq] (either
+ * may be NULL).  The regions go through in igd_hip_nearest's chunks with two rows per region: at most igd_hip_max_batch()
+ * regions and IGD_HIP_NEAREST_ROW_BYTES / (8 nFiles) regions.  A call defines every word.
+ * igd_hip_flank_dev: device pointers, one engine batch (nq above igd_hip_max_batch() is IGD_HIP_ERR_ARG), enqueued on `stream`
+ * (NULL: the engine's own) without waiting; d_up and d_down are overwritten, d_upmin and d_downmin may each be NULL.
+ * igd_hip_flank_reldist: the groups and chunks of igd_hip_nearest_hist -- whole sets are taken while B x (nFiles + 1) words per
+ * set fit the row budget of igd_hip_support_sets, a set may be cut by a chunk, kernel igd_flank_reldist adds every chunk's rows
+ * into the resident histogram; the rows never leave the device and hist is copied out once per group.  The histogram is built
+ * from the two rows alone, so it serves both measures.  nsets == 0 writes nothing; without regions or without files every word
+ * of hist is 0.
+ * Blocking (but for _dev), one device.  IGD_HIP_ERR_ARG -- W out of range, a measure that is neither, B outside 1 .. 64, a
+ * missing array, a bad set_off -- comes before anything of the caller's is written.
+ * Not done: unbounded flanks, the permutation null of a bin, several devices. */
+#define IGD_HIP_FLANK_EDGES 0
+#define IGD_HIP_FLANK_MIDPOINTS 1
+#define IGD_HIP_FLANK_MAX_BINS 64
+#define IGD_HIP_FLANK_NEITHER 0
+#define IGD_HIP_FLANK_UP 1
+#define IGD_HIP_FLANK_DOWN 2
+static inline IGD_HIP_OV_HD_ int igd_hip_flank_measure_valid(int measure) { return measure == IGD_HIP_FLANK_EDGES || measure == IGD_HIP_FLANK_MIDPOINTS; }
+static inline IGD_HIP_OV_HD_ int igd_hip_flank_bins_valid(int64_t nbins) { return nbins >= 1 && nbins <= IGD_HIP_FLANK_MAX_BINS; }
+static inline IGD_HIP_OV_HD_ int64_t igd_hip_flank_mid(int32_t x, int32_t y) { return ((int64_t)x + (int64_t)y) >> 1; }
+/* the side of one COUNTED (region, record) pair -- IGD_HIP_FLANK_NEITHER, _UP or _DOWN -- and, on a side, its distance in *dist */
+static inline IGD_HIP_OV_HD_ int igd_hip_flank_pair(int measure, int32_t window, int32_t qs, int32_t qe, int32_t start, int32_t end,
+                                                    uint32_t *dist)
+{
+    if (measure == IGD_HIP_FLANK_MIDPOINTS) {
+        const int64_t D = igd_hip_flank_mid(start, end) - igd_hip_flank_mid(qs, qe);
+        if (D < -(int64_t)window || D > (int64_t)window) return IGD_HIP_FLANK_NEITHER;
+        *dist = (uint32_t)(D < 0 ? -D : D);
+        return D < 0 ? IGD_HIP_FLANK_UP : IGD_HIP_FLANK_DOWN;
+    }
+    if (start < qe && end > qs) return IGD_HIP_FLANK_NEITHER;
+    const int64_t a = (int64_t)start - (int64_t)qe, b = (int64_t)qs - (int64_t)end;
+    *dist = (uint32_t)((a >= b ? a : b) + 1);
+    return a >= b ? IGD_HIP_FLANK_DOWN : IGD_HIP_FLANK_UP;
+}
+static inline IGD_HIP_OV_HD_ int igd_hip_flank_flanked(int32_t up, int32_t down) { return up >= 0 && down >= 0 && (int64_t)up + (int64_t)down > 0; }
+/* bin of a flanked pair */
+static inline IGD_HIP_OV_HD_ int igd_hip_flank_bin(int nbins, int32_t up, int32_t down)
+{
+    const int64_t m = up < down ? up : down, k = 2 * (int64_t)nbins * m / ((int64_t)up + (int64_t)down);
+    return (int)(k < nbins - 1 ? k : nbins - 1);
+}
+int igd_hip_flank(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window, int measure,
+                  int32_t v, int32_t *up, int32_t *down, int32_t *upmin, int32_t *downmin);
+int igd_hip_flank_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, int64_t nq, int32_t window,
+                      int measure, int32_t v, int32_t *d_up, int32_t *d_down, int32_t *d_upmin, int32_t *d_downmin, void *stream);
+int igd_hip_flank_reldist(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                          int32_t nsets, int32_t window, int measure, int32_t v, int32_t nbins, int64_t *hist);
 
 /* Values of the overlapping records per region and dataset: how many records of every file lie under each region and what they
  * are worth -- `bedtools map -c 5 -o count,sum,min,max,mean`, the regions x datasets feature matrix.  THE DEFINITIONS (the one
