@@ -244,6 +244,9 @@ def hip():
                                       C.c_void_p]
         L.igd_hip_map_grid.argtypes = [C.c_int64]
         L.igd_hip_map_grid.restype = C.c_int32
+        # the y of the reductions' grid: ncols (nFiles + 1 for the nearest family, nFiles for map), nslices
+        L.igd_hip_reduce_grid_y.argtypes = [C.c_int64, C.c_int64]
+        L.igd_hip_reduce_grid_y.restype = C.c_int32
         L.igd_hip_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_search_runs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -14,6 +14,26 @@ static int64_t env_positive(const char *name, int64_t dflt)
     return x > 0 ? (int64_t)x : dflt;
 }
 
+// The grid of the four reductions over a slice table (igd_nearest_reduce, igd_nearest_hist, igd_flank_reldist, igd_map_reduce):
+// gx workgroups of 64 columns across, gy down, and workgroup (x, y) takes the slices y, y + gy, ..  About IGD_REDUCE_WGS
+// workgroups per launch (64 per CU), never more rows than slices or than a grid's y may have.
+// The TEST-ONLY variable IGD_HIP_REDUCE_WGS (read once per process, as IGD_HIP_MAX_BATCH) lowers the number so that small
+// fixtures give a workgroup a second slice.
+#define IGD_REDUCE_WGS 16384
+static int reduce_grid_y(int gx, int ns)
+{
+    static const int64_t wgs = env_positive("IGD_HIP_REDUCE_WGS", IGD_REDUCE_WGS);
+    const int64_t gy = wgs / (gx > 0 ? gx : 1), top = ns < 65535 ? ns : 65535;
+    return (int)(gy > top ? (top < 1 ? 1 : top) : gy < 1 ? 1 : gy);
+}
+
+// the same for ncols columns and nslices slices (tests): ncols is nFiles + 1 for the nearest family, nFiles for igd_hip_map_sets
+extern "C" int32_t igd_hip_reduce_grid_y(int64_t ncols, int64_t nslices)
+{
+    const int64_t gx = (ncols + IGD_WAVE - 1) / IGD_WAVE;
+    return reduce_grid_y((int)(gx < INT_MAX ? gx : INT_MAX), (int)(nslices < INT_MAX ? nslices : INT_MAX));
+}
+
 // the chunk driver's two budgets, defined beside their constants in host_sets.hpp
 static int64_t sets_row_bytes(void);                 // device rows of one chunk of sets (IGD_SETS_ROW_BYTES; TEST-ONLY IGD_HIP_SETS_ROW_BYTES)
 static int64_t sets_slice_len(int64_t n);            // queries per slice when n queries are cut for one launch (IGD_SETS_SLICES, _MIN, _MAX)

@@ -15,7 +15,6 @@
 // The image is slice_image(db, IGD_HIP_RULE_FLAT, v): the re-tiled copy when there is one, visited under rule FLAT.
 #define IGD_MAP_ROW_BYTES ((int64_t)256 << 20)       // device rows of one chunk (IGD_NEAREST_ROW_BYTES)
 #define IGD_MAP_SLICE 256                            // regions per slice of igd_map_reduce: 64 per wave
-#define IGD_MAP_REDUCE_WGS 16384                     // igd_map_reduce: about this many workgroups per launch (64 per CU)
 
 // The TEST-ONLY variable IGD_HIP_MAP_ROW_BYTES (read once per process, as IGD_HIP_MAX_BATCH) lowers the budget so that small
 // fixtures cross the row seam.
@@ -182,9 +181,7 @@ extern "C" int igd_hip_map_sets(igd_hip_db *db, const int32_t *ichr, const int32
             if (rc == IGD_HIP_OK) rc = igd_hip_map_dev(db, db->d_qc, db->d_qs, db->d_qe, m, op, v, db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, st);
             if (rc != IGD_HIP_OK) return rc;
             HIPCHK(hipMemcpyAsync(db->d_mpSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-            int gy = IGD_MAP_REDUCE_WGS / gx;
-            gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
-            igd_map_reduce<<<dim3((unsigned)gx, (unsigned)gy), IGD_SETS_WG, 0, st>>>(db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, (int)nF, db->d_mpSlices,
+            igd_map_reduce<<<dim3((unsigned)gx, (unsigned)reduce_grid_y(gx, ns)), IGD_SETS_WG, 0, st>>>(db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, (int)nF, db->d_mpSlices,
                                                                                   ns, (u64 *)db->d_mpStat, matWords);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)

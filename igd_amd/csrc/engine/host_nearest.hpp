@@ -20,7 +20,6 @@
 // The image is slice_image(db, IGD_HIP_RULE_FLAT, v): the re-tiled copy when there is one, visited under rule FLAT.
 #define IGD_NEAREST_ROW_BYTES ((int64_t)256 << 20)   // device rows of one chunk (of the order of IGD_MEMBER_ROW_BYTES)
 #define IGD_NEAREST_SLICE 256                        // regions per slice of igd_nearest_reduce: 64 per wave
-#define IGD_NEAREST_REDUCE_WGS 16384                 // igd_nearest_reduce: about this many workgroups per launch (64 per CU)
 
 // The TEST-ONLY variable IGD_HIP_NEAREST_ROW_BYTES (read once per process, as IGD_HIP_MAX_BATCH) lowers the budget so that
 // small fixtures cross the row seam.
@@ -197,9 +196,7 @@ static int nearest_set_groups(igd_hip_db *db, const int32_t *ichr, const int32_t
             if (rc == IGD_HIP_OK) rc = fill(m, st);
             if (rc != IGD_HIP_OK) return rc;
             HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-            int gy = IGD_NEAREST_REDUCE_WGS / gx;
-            gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
-            reduce(dim3((unsigned)gx, (unsigned)gy), ns, rows, m, st);
+            reduce(dim3((unsigned)gx, (unsigned)reduce_grid_y(gx, ns)), ns, rows, m, st);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
         }

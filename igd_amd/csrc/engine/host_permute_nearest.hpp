@@ -127,9 +127,7 @@ static int nearest_rows_reduce(igd_hip_db *db, const int32_t *c, const int32_t *
         if (rc == IGD_HIP_OK) rc = igd_hip_nearest_dev(db, c + c0, s + c0, e + c0, m, window, v, db->d_nrDist, db->d_nrMin, st);
         if (rc != IGD_HIP_OK) return rc;
         HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-        int gy = IGD_NEAREST_REDUCE_WGS / gx;
-        gy = gy < 1 ? 1 : gy > ns ? ns : gy > 65535 ? 65535 : gy;
-        igd_nearest_reduce<<<dim3((unsigned)gx, (unsigned)gy), IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns,
+        igd_nearest_reduce<<<dim3((unsigned)gx, (unsigned)reduce_grid_y(gx, ns)), IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns,
                                                                                   (u64 *)db->d_nrStat, matWords);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));                // (the slice table is the host's vector)

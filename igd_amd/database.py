@@ -1279,11 +1279,12 @@ class Database:
                                      _ptr(dist), _ptr(dmin)), "igd_hip_nearest")
         return dist, dmin
 
-    def nearest_sets(self, ichr, qs, qe, set_off, window, value_filter=None):
+    def nearest_sets(self, ichr, qs, qe, set_off, window, value_filter=None, out=None):
         """The distances of nearest() summed up per region set (igd_hip_nearest_sets; sets as search_sets()): a NearestSets of
         three int64[nsets, nfiles + 1] -- n_within (the regions of the set with a record of the file within the window),
         n_overlap (those that overlap one: the support under rule FLAT) and sum_dist (the sum of the former's distances) --
-        whose last column is the any-dataset column, built from dmin.  The distance rows never leave the device."""
+        whose last column is the any-dataset column, built from dmin.  The distance rows never leave the device.  out, when
+        given, is a list of three C-ordered int64[nsets, nfiles + 1] that are overwritten."""
         ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
         set_off = np.ascontiguousarray(set_off, dtype=np.int64)
         nsets = len(set_off) - 1
@@ -1291,7 +1292,7 @@ class Database:
             raise IgdError("nearest_sets: set_off needs nsets + 1 entries")
         if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
             raise IgdError("nearest_sets: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
-        out = [np.empty((nsets, self.nfiles + 1), np.int64) for _ in range(3)]
+        out = _three_out(out, (nsets, self.nfiles + 1), "nearest_sets")
         _chk(self._H.igd_hip_nearest_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, _window(window, "nearest_sets"),
                                           _value_filter(value_filter), *[_ptr(a) for a in out]), "igd_hip_nearest_sets")
         return NearestSets(*out, int(window))

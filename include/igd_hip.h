@@ -489,6 +489,12 @@ int igd_hip_map_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, 
 /* Workgroups (of four waves) igd_map_rows is launched with for nq regions: a wave meets a second region only when nq exceeds four
  * times this number (tests). */
 int32_t igd_hip_map_grid(int64_t nq);
+/* Rows of workgroups (the grid's y) that the reductions over a slice table -- igd_nearest_reduce, igd_nearest_hist,
+ * igd_flank_reldist, igd_map_reduce -- are launched with for nslices slices of a matrix of ncols columns (nFiles + 1 for the
+ * nearest family, nFiles for igd_hip_map_sets): clamp(16384 / ceil(ncols / 64), 1, min(nslices, 65535)).  Workgroup (x, y) takes
+ * the slices y, y + this number, ..: it meets a second slice only when nslices exceeds it (tests; TEST-ONLY: IGD_HIP_REDUCE_WGS
+ * lowers the 16384, read once per process). */
+int32_t igd_hip_reduce_grid_y(int64_t ncols, int64_t nslices);
 
 /* The set statistics without the distance rows, and their permutation null (kernel igd_nearest_slices: the walk and table of
  * igd_nearest_rows, folded per region into LDS accumulators of the slice; nothing per region reaches memory).

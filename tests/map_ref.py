@@ -80,8 +80,48 @@ def table_text(names, n_hit, pairs, agg_sum, op):
 
 
 # ---- placed cases -----------------------------------------------------------------------------------------------------------
-def placed_db(d, nbp=1 << 14, name="mplaced"):
-    """One database for the placed cases of the issue; chrE holds the coordinates at 2^31 - 1 (its tiles run up there)."""
+CROWD_VALUES = (I32_MAX, I32_MIN, -7, I32_MAX, I32_MAX)
+CROWD_RECORDS = 300
+
+
+def crowd_base(nbp=1 << 14):
+    """where the crowd file's records start: inside tile 7 of chrA, two tiles past every other record of the contig"""
+    return 7 * nbp + 100
+
+
+def crowd_file(nbp=1 << 14):
+    """300 records of one file in one tile, record k starting at base + k: sorted by start, every 64 consecutive records -- one
+    load of a wave -- belong to this file, and under a region over all of them every lane folds into the same (region, file)
+    cell.  The values cycle through CROWD_VALUES; a record of value INT32_MAX ends 50 bp behind its start, one of INT32_MIN at
+    base + 1000 + k and one of -7 at base + 2000 + k, so that regions behind the starts select records by value."""
+    base = crowd_base(nbp)
+    tail = {I32_MAX: lambda k: base + k + 50, I32_MIN: lambda k: base + 1000 + k, -7: lambda k: base + 2000 + k}
+    recs = [("chrA", base + k, tail[CROWD_VALUES[k % 5]](k), CROWD_VALUES[k % 5]) for k in range(CROWD_RECORDS)]
+    assert (base + 2000 + CROWD_RECORDS) // nbp == base // nbp
+    return recs
+
+
+def crowd_regions(nbp=1 << 14):
+    """((ichr, qs, qe), counts): all 300 records; the first 128; the records of -7 alone; those of INT32_MIN and -7 (a sum far
+    below -2^32).  counts: the records each region overlaps, without a value filter."""
+    base = crowd_base(nbp)
+    rows = [(0, base - 10, base + 400), (0, base - 10, base + 128), (0, base + 1500, base + 1600), (0, base + 600, base + 700)]
+    a = np.array(rows, np.int64)
+    n7 = sum(1 for k in range(CROWD_RECORDS) if CROWD_VALUES[k % 5] == -7)
+    nmin = sum(1 for k in range(CROWD_RECORDS) if CROWD_VALUES[k % 5] == I32_MIN)
+    return (a[:, 0].astype(np.int32), a[:, 1].astype(np.int32), a[:, 2].astype(np.int32)), [CROWD_RECORDS, 128, n7, n7 + nmin]
+
+
+def pad_file(i, nbp=1 << 14):
+    """file i of a padded placed_db: one short record on chrB with a negative value, somewhere in the contig's first twelve
+    tiles -- under placed_regions' seven-tile region when it starts below 7 nbp + 3, clear of every other region"""
+    s = (i * 2654435761) % (12 * nbp)
+    return [("chrB", s, s + 1 + i % 50, -1 - i % 1000)]
+
+
+def placed_db(d, nbp=1 << 14, name="mplaced", pad_to=None, crowd=False):
+    """One database for the placed cases of the issue; chrE holds the coordinates at 2^31 - 1 (its tiles run up there).
+    crowd: crowd_file() follows as file 6.  pad_to = n: pad_file()s follow until there are n files (the wide forms)."""
     files = [
         # f0: a record over five tiles (under a region over seven), and a book-ended pair around region [1000, 2000)
         [("chrB", nbp + 5, 6 * nbp - 5, 321), ("chrA", 2000, 2500, 900), ("chrA", 500, 1000, 900)],
@@ -98,6 +138,10 @@ def placed_db(d, nbp=1 << 14, name="mplaced"):
         # f5: the top of int32
         [("chrE", TOP - 100, TOP, 900), ("chrE", TOP - 5 * nbp, TOP - 5 * nbp + 10, -1)],
     ]
+    if crowd:
+        files.append(crowd_file(nbp))
+    while pad_to is not None and len(files) < pad_to:
+        files.append(pad_file(len(files), nbp))
     return ListDb(d, name, files, nbp, 1, contig_order=["chrA", "chrB", "chrE"])
 
 
