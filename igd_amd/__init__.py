@@ -7,7 +7,8 @@ __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "re
            "search_host", "support_host", "nearest_host", "nearest_sets_host", "nearest_summary", "NearestSets", "permute_nearest_host",
            "perm_nearest_summary", "PermutationNearest", "map_host", "map_sets_host", "map_summary", "MapSets",
            "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD",
-           "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS"]
+           "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
+           "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -31,7 +32,8 @@ def __getattr__(name):
                 "search_host", "support_host", "nearest_host", "nearest_sets_host", "nearest_summary", "NearestSets", "permute_nearest_host",
                 "perm_nearest_summary", "PermutationNearest", "map_host", "map_sets_host", "map_summary", "MapSets",
                 "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD",
-                "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS"):
+                "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
+                "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

@@ -223,6 +223,18 @@ def hip():
         L.igd_hip_flank_dev.argtypes = L.igd_hip_flank.argtypes + [C.c_void_p]
         L.igd_hip_flank_reldist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int,
                                             C.c_int32, C.c_int32, C.c_void_p]
+        # merged region sets: db, ichr, qs, qe, set_off, nsets, gap, m_ichr, m_qs, m_qe, m_off, m_count, n_dropped / device pointers,
+        # ..., nsets, n, gap, ..., stream; merged base pairs per dataset: db, v, rule, file_bp; the table: db, ichr, qs, qe, set_off,
+        # nsets, v, rule, inter, set_bp, file_bp, n_merged, n_dropped
+        L.igd_hip_merge_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_merge_sets_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_dataset_bp.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_void_p]
+        L.igd_hip_dataset_bp_computed.argtypes = [C.c_void_p]
+        L.igd_hip_dataset_bp_computed.restype = C.c_int64
+        L.igd_hip_jaccard_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         # the fused route and the permutation null of the distances: as igd_hip_nearest_sets / db, ichr, qs, qe, nq, ctg_len, mode,
         # seed, nperm, window, v, n_within, n_overlap, sum_dist
         L.igd_hip_nearest_sets_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -387,6 +399,15 @@ def _bind_core(L):
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.igdc_flank_reldist_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                           C.c_int, C.c_int32, C.c_int32, C.c_void_p]
+    # merged region sets and the base-pair Jaccard on the host: db, ichr, qs, qe, set_off, nsets, gap, m_ichr, m_qs, m_qe, m_off,
+    # m_count, n_dropped / db, map, v, rule, file_bp / db, map, ichr, qs, qe, set_off, nsets, v, rule, inter, set_bp, file_bp,
+    # n_merged, n_dropped / inter, set_bp, file_bp, nsets, ncols, jaccard, set_fraction, file_fraction
+    L.igdc_merge_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.igdc_dataset_bp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p]
+    L.igdc_jaccard_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.igdc_jaccard_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     # values of the overlapping records on the host: db, map, ichr, qs, qe, nq, op, v, count, agg / ..., set_off, nsets, op, v,
     # n_hit, pairs, agg_sum / n_hit, pairs, agg_sum, n, op, mean_region, mean_pair
     L.igdc_map_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_void_p,

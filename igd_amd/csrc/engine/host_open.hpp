@@ -44,7 +44,7 @@ extern "C" void igd_hip_close(igd_hip_db *db)
                     db->d_memBits, db->d_memNf, db->d_memHit, db->d_fisher, db->d_rsUni, db->d_rsTab, db->d_rsSize, db->d_rsBits,
                     db->d_coCols, db->d_coMat, db->d_coA, db->d_coB, db->d_pmReg, db->d_pmStat,
                     db->d_nrDist, db->d_nrMin, db->d_nrStat, db->d_nrSlices, db->d_nrEdges,
-                    db->d_mpCount, db->d_mpAgg, db->d_mpStat, db->d_mpSlices};
+                    db->d_mpCount, db->d_mpAgg, db->d_mpStat, db->d_mpSlices, db->d_merge};
     for (void *p : ptrs)
         if (p && !(db->arena && (char *)p >= db->arena && (char *)p < db->arena + db->arenaSize)) (void)hipFree(p);
     if (db->arena) (void)hipFree(db->arena);
@@ -243,6 +243,7 @@ extern "C" int igd_hip_open(const igd_hip_desc *d, int device, igd_hip_db **out)
     }
     db->nbp = d->nbp; db->gType = d->gType; db->nCtg = d->nCtg; db->nFiles = d->nFiles;
     db->nRec = d->nRecords;
+    db->hNTile.assign(d->nTile, d->nTile + (d->nCtg > 0 ? d->nCtg : 0));
 
     // host-side tables
     int64_t nT = 0;

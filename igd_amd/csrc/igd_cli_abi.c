@@ -1001,6 +1001,89 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
     free(q); free(rows); free(nhit);
 }
 
+/* ------------------------------- `igd search -q F -J` / `-Q <list> -J` ----------------- */
+/* Base-pair Jaccard (include/igd_hip.h has the definitions): the query set is merged at gap 0, and per database file the table
+ * gives the bp of the intersection with the union of the file's records, the bp of the union of the two, the Jaccard, the
+ * fraction of the set's bp inside the file (set_fraction) and the file's merged bp; every file has a line.  Last line: the
+ * same against the records of any file.  A ratio over 0 is printed as NA.  Rule and filter are `-q`'s dispatch for -v.
+ * Routing as `-b`: at most igdc_host_limit() regions in all go through igdc_jaccard_host, more through ONE
+ * igd_hip_jaccard_sets call on one device. */
+static void print_ratio(int64_t num, int64_t den)
+{
+    if (den != 0) printf("%.6f", (double)num / (double)den);
+    else printf("NA");
+}
+
+static void print_jaccard_table(const int64_t *inter, int64_t set_bp, const int64_t *file_bp, int64_t n_merged, int64_t n_dropped)
+{
+    const int32_t nf = IGD->nFiles;
+    printf("index\tintersection\tunion\tjaccard\tset_fraction\tfile_bp\tFile\n");
+    for (int32_t i = 0; i < nf; i++) {
+        const int64_t u = set_bp + file_bp[i] - inter[i];
+        printf("%i\t%lld\t%lld\t", i, (long long)inter[i], (long long)u);
+        print_ratio(inter[i], u);
+        printf("\t");
+        print_ratio(inter[i], set_bp);
+        printf("\t%lld\t%s\n", (long long)file_bp[i], IGD->finfo[i].fileName);
+    }
+    printf("Any dataset: %lld of %lld bp in %lld merged regions (%lld dropped); jaccard ", (long long)inter[nf], (long long)set_bp,
+           (long long)n_merged, (long long)n_dropped);
+    print_ratio(inter[nf], set_bp + file_bp[nf] - inter[nf]);
+    printf("\n");
+}
+
+static void jaccard_files(char **paths, int32_t n, int32_t v, int setLines)
+{
+    if (!g_core || !cur_igd()) { engine(); return; }
+    const size_t nc = (size_t)IGD->nFiles + 1;
+    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` (:1023-1030) */
+    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
+    int64_t nq = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        nq += q[k].n;
+    }
+    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq ? nq : 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq ? nq : 1));
+    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq ? nq : 1));
+    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    off[0] = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (q[k].n) {
+            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+        }
+        off[k + 1] = off[k] + q[k].n;
+    }
+    int64_t *inter = (int64_t *)calloc((size_t)(n ? n : 1) * nc, sizeof(int64_t));
+    int64_t *file_bp = (int64_t *)calloc(nc, sizeof(int64_t));
+    int64_t *per = (int64_t *)calloc(3 * (size_t)(n ? n : 1), sizeof(int64_t)), *set_bp = per, *n_merged = per + n, *n_dropped = per + 2 * (size_t)n;
+    int onHost = 0;
+    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
+    if (hm) {
+        double t0 = now_s();
+        onHost = igdc_jaccard_host(g_core, hm, ichr, qs, qe, off, n, ev, rule, inter, set_bp, file_bp, n_merged, n_dropped) == 0;
+        igdc_map_close(hm);
+        if (onHost) phase("base-pair Jaccard on the host (small files)", &t0);
+    }
+    if (!onHost) {
+        igd_hip_db *dev = engine();                       /* (IGD_DEVICES with several devices: the first one, as -Q) */
+        double t0 = now_s();
+        if (dev) {
+            const int rc = igd_hip_jaccard_sets(dev, ichr, qs, qe, off, n, ev, rule, inter, set_bp, file_bp, n_merged, n_dropped);
+            if (rc != IGD_HIP_OK) engine_failed("jaccard", rc);
+            phase("base-pair Jaccard of the query sets (merge + coverage)", &t0);
+        }
+    }
+    for (int32_t k = 0; k < n && !g_fail_rc; k++) {       /* (as `-q`: no table after an engine failure) */
+        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        print_jaccard_table(inter + (size_t)k * nc, set_bp[k], file_bp, n_merged[k], n_dropped[k]);
+    }
+    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    free(q); free(ichr); free(qs); free(qe); free(off); free(inter); free(file_bp); free(per);
+}
+
 /* ------------------------------- `igd search -q F -U <universe>` / `-Q <list> -U <universe>` ----------------- */
 /* Region-set enrichment: per query set and database file the 2x2 table of a one-sided Fisher exact test against a
  * background universe, the LOLA table.  With the supports of `-u` (same rule and -v filter for sets and universe), n_k
@@ -1935,6 +2018,7 @@ int igd_search(int argc, char **argv)                                        /* 
     char *histArg = NULL;                                                             /* -H (see nearest_hist_files) */
     char *binsArg = NULL;                                                             /* -L (see flank_reldist_files) */
     int flankL = 0, flankEdges = 0;                                                   /* -L, -E given */
+    int jac = 0;                                                                      /* -J given (see jaccard_files) */
     char *mapArg = NULL;                                                              /* -V (see map_files) */
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -1964,6 +2048,8 @@ int igd_search(int argc, char **argv)                                        /* 
             uniq = 1;
         } else if (strcmp(a, "-b") == 0) {            /* (not the reference's: covered base pairs, see support_files) */
             bp = 1;
+        } else if (strcmp(a, "-J") == 0) {            /* (not the reference's: base-pair Jaccard, see jaccard_files) */
+            jac = 1;
         } else if (strcmp(a, "-w") == 0) {            /* (not the reference's: per-query membership, see membership_files) */
             memb = 1;
         } else if (strcmp(a, "-U") == 0) {            /* (not the reference's: enrichment against a universe, see enrich_files) */
@@ -2029,6 +2115,17 @@ int igd_search(int argc, char **argv)                                        /* 
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    if (jac) {                                                                /* -J: every refusal is a usage error */
+        const char *why = NULL;
+        if (uniq || bp || memb || uniName || ranks || restricted || cooc || permArg || distArg || nearArg || histArg || flankL || flankEdges ||
+            mapArg || full || other || minov)
+            why = "-J together with -u, -b, -w, -U, -R, -X, -C, -P, -D, -N, -H, -L, -E, -V, -f, -m, -s, -r, -O, -A or -B";
+        else if (mode != 1 && !listName) why = "-J without -q or -Q";
+        if (why) {
+            printf("Not supported: %s\n", why);
+            return EX_USAGE;
+        }
+    }
     int mapOp = -1;                                                           /* -V: every refusal is a usage error */
     if (mapArg) {
         for (int k = 0; k < 5; k++) if (strcmp(mapArg, MAP_OPS[k]) == 0) mapOp = k;
@@ -2132,6 +2229,14 @@ int igd_search(int argc, char **argv)                                        /* 
     if (!permArg && (genomeName || seedArg || pmodeArg)) {
         printf("Not supported: -g, -S or -M without -P\n");
         return EX_OK;
+    } else if (jac && mode == 1) {
+        jaccard_files(&qfName, 1, v, 0);
+    } else if (jac) {
+        int32_t n = 0;
+        char **paths = read_list(listName, &n);
+        if (n >= 0) jaccard_files(paths, n, v, 1);
+        for (int32_t k = 0; k < n; k++) free(paths[k]);
+        free(paths);
     } else if (mapArg && mode == 1) {
         map_files(&qfName, 1, v, 0, mapOp);
     } else if (mapArg) {

@@ -229,6 +229,24 @@ int igdc_flank_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, c
                     int32_t window, int measure, int32_t v, int32_t *up, int32_t *down, int32_t *upmin, int32_t *downmin);
 int igdc_flank_reldist_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                             const int64_t *set_off, int32_t nsets, int32_t window, int measure, int32_t v, int32_t nbins, int64_t *hist);
+/* Merged region sets and the base-pair Jaccard (what igd_hip_merge_sets, igd_hip_dataset_bp and igd_hip_jaccard_sets compute;
+ * include/igd_hip.h has the definitions): a sort and a sweep per set, threads over the sets; file_bp and the intersections
+ * through igdc_coverage_host, threads over the tiles and the runs.  igdc_merge_host needs the database only for its number of
+ * contigs.  Every output is OVERWRITTEN, every word of it.  0 on success; -1 for a missing array, a bad set_off, a gap outside
+ * 0 .. 2^30 (nothing written), or when a tile could not be read (outputs undefined).  The host route keeps no file_bp between
+ * calls. */
+int igdc_merge_host(const igdc_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                    int64_t gap, int32_t *m_ichr, int32_t *m_qs, int32_t *m_qe, int64_t *m_off, int32_t *m_count, int64_t *n_dropped);
+int igdc_dataset_bp_host(const igdc_db *db, const igdc_map *m, int32_t v, int rule, int64_t *file_bp);
+int igdc_jaccard_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                      const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *file_bp,
+                      int64_t *n_merged, int64_t *n_dropped);
+/* inter / (set_bp + file_bp - inter), NaN where the union is 0; and over inter[nsets][ncols], set_bp[nsets], file_bp[ncols] the
+ * Jaccard and the two containment fractions inter / set_bp and inter / file_bp (doubles, NaN where the divisor is 0; each may
+ * be NULL).  Need no database.  0, or -1 for a missing input. */
+double igdc_jaccard_value(int64_t inter, int64_t set_bp, int64_t file_bp);
+int igdc_jaccard_summary(const int64_t *inter, const int64_t *set_bp, const int64_t *file_bp, int64_t nsets, int64_t ncols, double *jaccard,
+                         double *set_fraction, double *file_fraction);
 /* mean[i] = sum_dist[i] / n_within[i] as a double, NaN where n_within[i] = 0.  Needs no database.  0, or -1 for a missing array. */
 int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64_t n, double *mean);
 /* Values of the overlapping records per region and dataset (what igd_hip_map and igd_hip_map_sets compute; include/igd_hip.h has

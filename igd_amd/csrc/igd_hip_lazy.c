@@ -171,6 +171,50 @@ int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
     return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, coverage, covered) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_merge_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                       int64_t gap, int32_t *m_ichr, int32_t *m_qs, int32_t *m_qe, int64_t *m_off, int32_t *m_count, int64_t *n_dropped)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int64_t, int32_t *,
+                        int32_t *, int32_t *, int64_t *, int32_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_merge_sets");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, gap, m_ichr, m_qs, m_qe, m_off, m_count, n_dropped) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_merge_sets_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, const int64_t *d_set_off,
+                           int32_t nsets, int64_t n, int64_t gap, int32_t *d_m_ichr, int32_t *d_m_qs, int32_t *d_m_qe, int64_t *d_m_off,
+                           int32_t *d_m_count, int64_t *d_n_dropped, void *stream)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int64_t, int64_t,
+                        int32_t *, int32_t *, int32_t *, int64_t *, int32_t *, int64_t *, void *);
+    RESOLVE(fn_t, "igd_hip_merge_sets_dev");
+    return fn ? fn(db, d_ichr, d_qs, d_qe, d_set_off, nsets, n, gap, d_m_ichr, d_m_qs, d_m_qe, d_m_off, d_m_count, d_n_dropped, stream)
+              : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_dataset_bp(igd_hip_db *db, int32_t v, int rule, int64_t *file_bp)
+{
+    typedef int (*fn_t)(igd_hip_db *, int32_t, int, int64_t *);
+    RESOLVE(fn_t, "igd_hip_dataset_bp");
+    return fn ? fn(db, v, rule, file_bp) : IGD_HIP_ERR_DEVICE;
+}
+
+int64_t igd_hip_dataset_bp_computed(const igd_hip_db *db)
+{
+    typedef int64_t (*fn_t)(const igd_hip_db *);
+    if (!db) return 0;
+    RESOLVE(fn_t, "igd_hip_dataset_bp_computed");
+    return fn ? fn(db) : 0;
+}
+
+int igd_hip_jaccard_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                         int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *file_bp, int64_t *n_merged, int64_t *n_dropped)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int32_t, int, int64_t *,
+                        int64_t *, int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_jaccard_sets");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, inter, set_bp, file_bp, n_merged, n_dropped) : IGD_HIP_ERR_DEVICE;
+}
+
 int64_t igd_hip_member_words(const igd_hip_db *db)
 {
     typedef int64_t (*fn_t)(const igd_hip_db *);

@@ -1783,3 +1783,174 @@ int igdc_search_auto(igdc_db *db, const char *path, int device, const int32_t *i
     }
     return igd_hip_search_ex(db->dev, ichr, qs, qe, nq, v, rule, flags, hits, total);
 }
+
+/* ---- merged region sets and the base-pair Jaccard (include/igd_hip.h has the definitions) -------------------------------
+ * Per set: the regions that take part, sorted by (ichr, qs, qe), one sweep with the running maximum of the ends.  The runs of
+ * set k are built at its own place [set_off[k], ..) of scratch arrays, threads over the sets; one serial pass packs them. */
+typedef struct { int32_t c, s, e; } merge_reg;
+static int merge_reg_cmp(const void *a, const void *b)
+{
+    const merge_reg *x = (const merge_reg *)a, *y = (const merge_reg *)b;
+    if (x->c != y->c) return x->c < y->c ? -1 : 1;
+    if (x->s != y->s) return x->s < y->s ? -1 : 1;
+    return x->e < y->e ? -1 : x->e > y->e;
+}
+
+typedef struct {
+    const igdc_db *db;
+    const int32_t *ichr, *qs, *qe;
+    const int64_t *set_off;
+    int32_t k0, k1;
+    int64_t gap;
+    merge_reg *regs;            /* [n] scratch: set k sorts at set_off[k] */
+    int32_t *rc, *rs, *re, *rn; /* [n] the runs of set k from set_off[k] on */
+    int64_t *nrun, *n_dropped;  /* [nsets] */
+} merge_job;
+
+static void *merge_run(void *arg)
+{
+    merge_job *J = (merge_job *)arg;
+    for (int32_t k = J->k0; k < J->k1; k++) {
+        const int64_t a = J->set_off[k], b = J->set_off[k + 1];
+        merge_reg *g = J->regs + a;
+        int64_t m = 0, r = -1;
+        for (int64_t i = a; i < b; i++)
+            if (igd_hip_merge_takes_part(J->db->nCtg, J->ichr[i], J->qs[i], J->qe[i])) {
+                g[m].c = J->ichr[i]; g[m].s = J->qs[i]; g[m].e = J->qe[i];
+                m++;
+            }
+        qsort(g, (size_t)m, sizeof *g, merge_reg_cmp);
+        for (int64_t i = 0; i < m; i++) {
+            if (r < 0 || g[i].c != J->rc[a + r] || igd_hip_merge_opens(g[i].s, J->re[a + r], J->gap)) {
+                r++;
+                J->rc[a + r] = g[i].c; J->rs[a + r] = g[i].s; J->re[a + r] = g[i].e; J->rn[a + r] = 1;
+            } else {
+                if (g[i].e > J->re[a + r]) J->re[a + r] = g[i].e;
+                J->rn[a + r]++;
+            }
+        }
+        J->nrun[k] = r + 1;
+        J->n_dropped[k] = (b - a) - m;
+    }
+    return NULL;
+}
+
+int igdc_merge_host(const igdc_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                    int64_t gap, int32_t *m_ichr, int32_t *m_qs, int32_t *m_qe, int64_t *m_off, int32_t *m_count, int64_t *n_dropped)
+{
+    if (!db || nsets < 0 || !igd_hip_merge_gap_valid(gap) || (nsets > 0 && (!set_off || set_off[0] != 0 || !m_off || !n_dropped))) return -1;
+    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
+    const int64_t n = nsets > 0 ? set_off[nsets] : 0;
+    if (n > 0 && (!ichr || !qs || !qe || !m_ichr || !m_qs || !m_qe)) return -1;
+    if (nsets == 0) return 0;
+    merge_reg *regs = (merge_reg *)malloc((size_t)(n > 0 ? n : 1) * sizeof *regs);
+    int32_t *runs = (int32_t *)malloc((size_t)(n > 0 ? n : 1) * 4 * sizeof *runs);
+    int64_t *nrun = (int64_t *)calloc((size_t)nsets, sizeof *nrun);
+    if (!regs || !runs || !nrun) { free(regs); free(runs); free(nrun); return -1; }
+    int T = host_threads(n);
+    if (T > nsets) T = nsets;
+    merge_job job[64];
+    pthread_t th[64];
+    int started[64];
+    for (int t = 0; t < T; t++) {
+        merge_job *J = &job[t];
+        J->db = db; J->ichr = ichr; J->qs = qs; J->qe = qe; J->set_off = set_off; J->gap = gap;
+        J->k0 = (int32_t)((int64_t)nsets * t / T); J->k1 = (int32_t)((int64_t)nsets * (t + 1) / T);
+        J->regs = regs; J->rc = runs; J->rs = runs + n; J->re = runs + 2 * n; J->rn = runs + 3 * n;
+        J->nrun = nrun; J->n_dropped = n_dropped;
+    }
+    for (int t = 1; t < T; t++) {
+        started[t] = pthread_create(&th[t], NULL, merge_run, &job[t]) == 0;
+        if (!started[t]) merge_run(&job[t]);
+    }
+    merge_run(&job[0]);
+    for (int t = 1; t < T; t++) if (started[t]) pthread_join(th[t], NULL);
+    int64_t at = 0;
+    for (int32_t k = 0; k < nsets; k++) {
+        const int64_t a = set_off[k];
+        m_off[k] = at;
+        for (int64_t r = 0; r < nrun[k]; r++, at++) {
+            m_ichr[at] = runs[a + r]; m_qs[at] = runs[n + a + r]; m_qe[at] = runs[2 * n + a + r];
+            if (m_count) m_count[at] = runs[3 * n + a + r];
+        }
+    }
+    m_off[nsets] = at;
+    for (; at < n; at++) {                                /* the rest of the capacity is defined too */
+        m_ichr[at] = 0; m_qs[at] = 0; m_qe[at] = 0;
+        if (m_count) m_count[at] = 0;
+    }
+    free(regs); free(runs); free(nrun);
+    return 0;
+}
+
+/* file_bp[f], f <= nFiles: igdc_coverage_host over every tile of every contig as one query (igd_hip_tile_query); nothing is
+ * kept between calls -- the host route has no handle of its own to keep it in */
+int igdc_dataset_bp_host(const igdc_db *db, const igdc_map *m, int32_t v, int rule, int64_t *file_bp)
+{
+    if (!db || !m || !file_bp || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)) return -1;
+    int64_t nq = 0;
+    for (int32_t c = 0; c < db->nCtg; c++) nq += db->nTile[c];
+    int32_t *q = (int32_t *)malloc((size_t)(nq > 0 ? nq : 1) * 3 * sizeof *q);
+    if (!q) return -1;
+    int64_t k = 0;
+    for (int32_t c = 0; c < db->nCtg; c++)
+        for (int64_t t = 0; t < db->nTile[c]; t++) {
+            int32_t ws, we;
+            if (!igd_hip_tile_query(db->nbp, t, &ws, &we)) break;
+            q[k] = c; q[nq + k] = ws; q[2 * nq + k] = we;
+            k++;
+        }
+    for (int32_t f = 0; f <= db->nFiles; f++) file_bp[f] = 0;
+    const int rc = igdc_coverage_host(db, m, q, q + nq, q + 2 * nq, k, v, rule, file_bp, file_bp + db->nFiles);
+    free(q);
+    return rc;
+}
+
+int igdc_jaccard_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                      const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *file_bp,
+                      int64_t *n_merged, int64_t *n_dropped)
+{
+    if (!db || !m || nsets < 0 || !file_bp || (nsets > 0 && (!set_off || set_off[0] != 0 || !inter || !set_bp || !n_merged || !n_dropped)) ||
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)) return -1;
+    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
+    const int64_t n = nsets > 0 ? set_off[nsets] : 0, nF = db->nFiles;
+    if (n > 0 && (!ichr || !qs || !qe)) return -1;
+    int rc = igdc_dataset_bp_host(db, m, v, rule, file_bp);
+    if (rc != 0 || nsets == 0) return rc;
+    int32_t *mr = (int32_t *)malloc((size_t)(n > 0 ? n : 1) * 3 * sizeof *mr);
+    int64_t *moff = (int64_t *)malloc(((size_t)nsets + 1) * sizeof *moff);
+    if (!mr || !moff) { free(mr); free(moff); return -1; }
+    rc = igdc_merge_host(db, ichr, qs, qe, set_off, nsets, 0, mr, mr + n, mr + 2 * n, moff, NULL, n_dropped);
+    for (int32_t k = 0; rc == 0 && k < nsets; k++) {
+        const int64_t a = moff[k], b = moff[k + 1];
+        int64_t *row = inter + (int64_t)k * (nF + 1), bp = 0;
+        for (int64_t f = 0; f <= nF; f++) row[f] = 0;
+        for (int64_t r = a; r < b; r++) bp += (int64_t)mr[2 * n + r] - (int64_t)mr[n + r];
+        set_bp[k] = bp;
+        n_merged[k] = b - a;
+        rc = igdc_coverage_host(db, m, mr + a, mr + n + a, mr + 2 * n + a, b - a, v, rule, row, row + nF);
+    }
+    free(mr); free(moff);
+    return rc;
+}
+
+/* jaccard[i] = inter / (set_bp + file_bp - inter), set_fraction[i] = inter / set_bp, file_fraction[i] = inter / file_bp, doubles, NaN
+ * where the divisor is 0; i = k * ncols + f over inter[nsets][ncols], set_bp[nsets], file_bp[ncols] */
+double igdc_jaccard_value(int64_t inter, int64_t set_bp, int64_t file_bp)
+{
+    const int64_t u = set_bp + file_bp - inter;
+    return u != 0 ? (double)inter / (double)u : NAN;
+}
+int igdc_jaccard_summary(const int64_t *inter, const int64_t *set_bp, const int64_t *file_bp, int64_t nsets, int64_t ncols, double *jaccard,
+                         double *set_fraction, double *file_fraction)
+{
+    if (nsets < 0 || ncols < 0 || (nsets > 0 && ncols > 0 && (!inter || !set_bp || !file_bp))) return -1;
+    for (int64_t k = 0; k < nsets; k++)
+        for (int64_t f = 0; f < ncols; f++) {
+            const int64_t i = k * ncols + f;
+            if (jaccard) jaccard[i] = igdc_jaccard_value(inter[i], set_bp[k], file_bp[f]);
+            if (set_fraction) set_fraction[i] = set_bp[k] != 0 ? (double)inter[i] / (double)set_bp[k] : NAN;
+            if (file_fraction) file_fraction[i] = file_bp[f] != 0 ? (double)inter[i] / (double)file_bp[f] : NAN;
+        }
+    return 0;
+}

@@ -47,6 +47,8 @@ FLANK_EDGES = 0                                      # IGD_HIP_FLANK_EDGES
 FLANK_MIDPOINTS = 1                                  # IGD_HIP_FLANK_MIDPOINTS
 FLANK_MAX_BINS = 64                                  # IGD_HIP_FLANK_MAX_BINS
 FlankReldist = collections.namedtuple("FlankReldist", "hist nbins window measure")
+JaccardSets = collections.namedtuple("JaccardSets", "inter set_bp file_bp n_merged n_dropped")
+MERGE_MAX_GAP = 1 << 30
 
 
 class MinOverlap(C.Structure):
@@ -641,6 +643,71 @@ def flank_reldist_host(igd_path, ichr, qs, qe, set_off, window, nbins=50, measur
             raise IgdError("flank_reldist_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
                            % (NEAREST_MAX_WINDOW, igd_path))
         return FlankReldist(hist, nbins, int(window), m)
+
+
+def _gap(gap, what):
+    if isinstance(gap, (bool, float)) or not isinstance(gap, (int, np.integer)) or not 0 <= gap <= MERGE_MAX_GAP:
+        raise IgdError("%s: gap must be an integer from 0 to %d" % (what, MERGE_MAX_GAP))
+    return int(gap)
+
+
+def _merge_out(n, nsets):
+    return (np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(nsets + 1, np.int64), np.empty(n, np.int32),
+            np.empty(nsets, np.int64))
+
+
+def _merge_cut(mc, ms, me, moff, cnt, dropped):
+    r = int(moff[-1])
+    return mc[:r], ms[:r], me[:r], moff, cnt[:r], dropped
+
+
+def merge_host(igd_path, ichr, qs, qe, set_off, gap=0):
+    """Database.merge_sets() on the host (igdc_merge_host; no device is touched): (ichr, qs, qe, set_off, count, n_dropped)."""
+    ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "merge_host")
+    gap, nsets = _gap(gap, "merge_host"), len(set_off) - 1
+    out = _merge_out(len(qs), nsets)
+    with _HostDb(igd_path, "merge_host") as h:
+        if h.L.igdc_merge_host(h.core, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, gap, *[_ptr(a) for a in out]) != 0:
+            raise IgdError("merge_host: a bad set_off")
+    return _merge_cut(*out)
+
+
+def dataset_bp_host(igd_path, v=0, rule=None, value_filter=None):
+    """Database.dataset_bp() on the host (igdc_dataset_bp_host; no device is touched): int64[nfiles + 1]."""
+    with _HostDb(igd_path, "dataset_bp_host") as h:
+        rule, vf = h.dispatch(v, rule, value_filter)
+        bp = np.empty(h.nfiles + 1, np.int64)
+        if h.L.igdc_dataset_bp_host(h.core, h.m, vf, rule, bp.ctypes.data) != 0:
+            raise IgdError("dataset_bp_host: a tile of %s could not be read" % igd_path)
+        return bp
+
+
+def jaccard_host(igd_path, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None):
+    """Database.jaccard_sets() on the host (igdc_jaccard_host; no device is touched): a JaccardSets."""
+    ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "jaccard_host")
+    nsets = len(set_off) - 1
+    with _HostDb(igd_path, "jaccard_host") as h:
+        rule, vf = h.dispatch(v, rule, value_filter)
+        js = JaccardSets(np.empty((nsets, h.nfiles + 1), np.int64), np.empty(nsets, np.int64), np.empty(h.nfiles + 1, np.int64),
+                         np.empty(nsets, np.int64), np.empty(nsets, np.int64))
+        if h.L.igdc_jaccard_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, vf, rule, _ptr(js.inter),
+                                 _ptr(js.set_bp), js.file_bp.ctypes.data, _ptr(js.n_merged), _ptr(js.n_dropped)) != 0:
+            raise IgdError("jaccard_host: a bad set_off, or a tile of %s could not be read" % igd_path)
+        return js
+
+
+def jaccard_summary(js):
+    """(jaccard, set_fraction, file_fraction), each float64[nsets, nfiles + 1], of a JaccardSets (igdc_jaccard_summary):
+    inter / (set_bp + file_bp - inter) and the two containment fractions inter / set_bp and inter / file_bp, NaN where the
+    divisor is 0.  (igd_amd.jaccard is about co-occurrence: the Jaccard of two datasets over the regions of a set.)"""
+    inter = np.ascontiguousarray(js.inter, np.int64)
+    set_bp, file_bp = np.ascontiguousarray(js.set_bp, np.int64), np.ascontiguousarray(js.file_bp, np.int64)
+    if inter.ndim != 2 or inter.shape != (len(set_bp), len(file_bp)):
+        raise IgdError("jaccard_summary: inter must be int64[%d, %d]" % (len(set_bp), len(file_bp)))
+    out = [np.empty(inter.shape, np.float64) for _ in range(3)]
+    if N.cli().igdc_jaccard_summary(_ptr(inter), _ptr(set_bp), _ptr(file_bp), inter.shape[0], inter.shape[1], *[_ptr(a) for a in out]) != 0:
+        raise IgdError("jaccard_summary: bad argument")
+    return tuple(out)
 
 
 def reldist_summary(fr):
@@ -1476,6 +1543,78 @@ class Database:
         set_off[1:] = np.cumsum([len(s[1]) for s in sets])
         cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
         return self.flank_reldist(cat[0], cat[1], cat[2], set_off, window, nbins, measure, value_filter)
+
+    # ---- merged region sets and the base-pair Jaccard per set and dataset -------------------
+    def merge_sets(self, ichr, qs, qe, set_off, gap=0):
+        """Region sets merged on the device as `bedtools merge -d gap` (igd_hip_merge_sets; the definitions are in
+        include/igd_hip.h; sets as search_sets()): (ichr, qs, qe, set_off, count, n_dropped) -- the runs ordered by (set, ichr, qs),
+        their offsets per set (int64[nsets + 1]), the regions each run joined (int32) and per set the regions that were dropped
+        (unknown contig, zero length, inverted; int64[nsets]).  At gap 0 book-ended regions join.  The order of the regions
+        within a set does not matter."""
+        ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "merge_sets")
+        gap, nsets = _gap(gap, "merge_sets"), len(set_off) - 1
+        out = _merge_out(len(qs), nsets)
+        _chk(self._H.igd_hip_merge_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, gap, *[_ptr(a) for a in out]),
+             "igd_hip_merge_sets")
+        return _merge_cut(*out)
+
+    def merge_sets_dev(self, d_ichr, d_qs, d_qe, d_set_off, nsets, n, d_m_ichr, d_m_qs, d_m_qe, d_m_off, d_n_dropped, d_m_count=None,
+                       gap=0, stream=None):
+        """Resident sets: arguments are device pointers (ints), n the number of regions.  Asynchronous.  d_m_ichr, d_m_qs, d_m_qe
+        and d_m_count (int32[n]; the last may be None), d_m_off (int64[nsets + 1]) and d_n_dropped (int64[nsets]) are
+        overwritten, the words behind the last run with 0; d_m_off[nsets], read back by the caller, is the number of runs.  The
+        merges of one Database share one workspace: order them with respect to each other (one stream, or an event between two
+        streams) -- two in flight on different streams race."""
+        _chk(self._H.igd_hip_merge_sets_dev(self.dev, d_ichr, d_qs, d_qe, d_set_off, int(nsets), int(n), _gap(gap, "merge_sets_dev"),
+                                            d_m_ichr, d_m_qs, d_m_qe, d_m_off, d_m_count, d_n_dropped, stream), "igd_hip_merge_sets_dev")
+
+    def _read_sets(self, paths):
+        sets = [self.read_queries(p) for p in paths]
+        set_off = np.zeros(len(sets) + 1, np.int64)
+        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
+        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
+        return cat[0], cat[1], cat[2], set_off
+
+    def merge_files(self, paths, gap=0):
+        """One region set per BED file (read as `igd search -q` reads it): merge_sets() of them."""
+        return self.merge_sets(*self._read_sets(paths), gap=gap)
+
+    def dataset_bp(self, v=0, rule=None, value_filter=None):
+        """The merged base pairs of every dataset (igd_hip_dataset_bp): int64[nfiles + 1], entry f the bp of the union of the
+        records of file f that a search under (v, rule, value_filter) counts, the last entry the union over all files.  Computed
+        once per (value filter, rule) and kept in the handle: dataset_bp_computed() counts the computations."""
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = _value_filter(value_filter)
+        bp = np.empty(self.nfiles + 1, np.int64)
+        _chk(self._H.igd_hip_dataset_bp(self.dev, vf, rule, bp.ctypes.data), "igd_hip_dataset_bp")
+        return bp
+
+    def dataset_bp_computed(self):
+        """How many times this handle has computed (not found in its cache) a dataset_bp()."""
+        return int(self._H.igd_hip_dataset_bp_computed(self.dev))
+
+    def jaccard_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None):
+        """The base-pair intersection of every region set with every dataset, `bedtools jaccard` (igd_hip_jaccard_sets; sets as
+        search_sets()): JaccardSets(inter int64[nsets, nfiles + 1], set_bp int64[nsets], file_bp int64[nfiles + 1], n_merged,
+        n_dropped int64[nsets]).  The sets are merged at gap 0 first, so inter[k, f] is |A_k n B_f| exactly; the last column is
+        "any dataset".  igd_amd.jaccard_summary() gives the Jaccard and the containment fractions."""
+        ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "jaccard_sets")
+        nsets = len(set_off) - 1
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = _value_filter(value_filter)
+        js = JaccardSets(np.empty((nsets, self.nfiles + 1), np.int64), np.empty(nsets, np.int64), np.empty(self.nfiles + 1, np.int64),
+                         np.empty(nsets, np.int64), np.empty(nsets, np.int64))
+        _chk(self._H.igd_hip_jaccard_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, vf, rule, _ptr(js.inter),
+                                          _ptr(js.set_bp), js.file_bp.ctypes.data, _ptr(js.n_merged), _ptr(js.n_dropped)), "igd_hip_jaccard_sets")
+        return js
+
+    def jaccard_files(self, paths, v=0):
+        """One region set per BED file (read as `igd search -q` reads it): the JaccardSets of jaccard_sets()."""
+        return self.jaccard_sets(*self._read_sets(paths), v=v)
 
     # ---- values of the overlapping records per region and dataset -------------------------
     def map_values(self, ichr, qs, qe, op="sum", value_filter=None, count=None, agg=None):

@@ -489,6 +489,66 @@ int igd_hip_map_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, 
 /* Workgroups (of four waves) igd_map_rows is launched with for nq regions: a wave meets a second region only when nq exceeds four
  * times this number (tests). */
 int32_t igd_hip_map_grid(int64_t nq);
+
+/* Merged region sets and the base-pair Jaccard per set and dataset: `bedtools merge -d gap` on the device, and per set k and
+ * dataset f what `bedtools jaccard` reports -- |A_k n B_f|, |A_k u B_f| -- with one extra column nFiles for "any dataset".  THE
+ * DEFINITIONS (the one place: the kernels igd_merge_*, igdc_merge_host / igdc_dataset_bp_host / igdc_jaccard_host and the
+ * tests' reference agree on every integer).
+ *     gap          0 <= gap <= IGD_HIP_MERGE_MAX_GAP = 2^30; anything else is IGD_HIP_ERR_ARG.
+ *     takes part   A region (ichr, qs, qe) takes part iff 0 <= ichr < the database's contigs and qe > qs (igd_hip_merge_takes_part).
+ *                  Regions on unknown contigs, zero-length and inverted regions are dropped; n_dropped[k] counts them per set.
+ *     runs         Within set k the regions that take part are ordered by (ichr, qs, qe).  A region OPENS A RUN iff it is the
+ *                  first of its (set, contig) or qs > E + gap in 64 bits, E being the maximum qe of all earlier regions of the
+ *                  same (set, contig) (igd_hip_merge_opens; qs and E reach INT32_MAX, the sum does not wrap).  At gap 0
+ *                  book-ended regions join, as in bedtools.  A run is (ichr, its first qs, its maximum qe).
+ *     outputs      m_ichr, m_qs, m_qe: int32, capacity n = set_off[nsets], the runs ordered by (set, ichr, qs); m_off:
+ *                  int64[nsets + 1], the runs of set k are [m_off[k], m_off[k + 1]); m_count (may be NULL): int32 per run, the
+ *                  regions it joined (`merge -c 1 -o count`); n_dropped: int64[nsets].  Words of the capacity behind the
+ *                  last run are 0.  The result does not depend on the order of the regions within a set.
+ *     set_bp[k]    the sum of qe - qs over the runs of set k AT GAP 0 (the Jaccard is always taken at gap 0).
+ *     inter[k][f]  int64[nsets][nFiles + 1]: for f < nFiles igd_hip_coverage_sets' coverage of the runs of set k, column nFiles
+ *                  its covered[].  The runs are disjoint, so this is |A_k n B_f| exactly; B_f is the union of the records of
+ *                  file f that the search counts under the rule and v given.
+ *     file_bp[f]   int64[nFiles + 1]: |B_f|, column nFiles the union over all files.  It is igd_hip_coverage_sets over ONE set
+ *                  that holds every tile of every contig of the database as one query, [t nbp, (t + 1) nbp) with the end capped
+ *                  at INT32_MAX (igd_hip_tile_query): the queries partition the contig and coverage clips to the query, so the
+ *                  sum is exact.  Kept in the handle per (v, rule) once computed; a gType-0 database has one entry per rule.
+ *     jaccard      inter / (set_bp + file_bp - inter) as a double, NaN where the union is 0.  The engine returns integers
+ *                  only; igdc_jaccard_value (igd_core.h) and igd_amd.jaccard_summary derive it.
+ * igd_hip_merge_sets: host arrays in and out, blocking.  igd_hip_merge_sets_dev: device pointers, n = the number of regions
+ * (d_set_off is resident, so the host cannot read it), enqueued on `stream` (NULL: the engine's own) without waiting; the
+ * caller reads d_m_off[nsets] back to learn the number of runs.  Every merge of a handle works in the handle's ONE workspace:
+ * calls on one handle -- both forms, and igd_hip_jaccard_sets -- must be ORDERED with respect to each other (the same stream, or an
+ * event between two streams); two merges of one handle in flight on different streams race.  igd_hip_dataset_bp: file_bp as above.
+ * igd_hip_dataset_bp_computed: how many times the handle has computed (not found) one.  igd_hip_jaccard_sets: inter, set_bp,
+ * file_bp, n_merged[k] = the runs of set k, n_dropped.
+ * Every output is DEFINED by the call.  nsets == 0 writes nothing (igd_hip_jaccard_sets: file_bp only); without regions the
+ * offsets and counts are 0; nFiles == 0 leaves the any-dataset column, 0.  IGD_HIP_ERR_ARG -- a bad gap, a bad set_off, a
+ * missing array, more than 2^30 regions -- comes before anything of the caller's is written.  One device.
+ * Not done: strand, a gap on the Jaccard, Jaccard between two query sets, a permutation null, several devices. */
+#define IGD_HIP_MERGE_MAX_GAP ((int64_t)1 << 30)
+static inline IGD_HIP_OV_HD_ int igd_hip_merge_gap_valid(int64_t gap) { return gap >= 0 && gap <= IGD_HIP_MERGE_MAX_GAP; }
+static inline IGD_HIP_OV_HD_ int igd_hip_merge_takes_part(int32_t nctg, int32_t ichr, int32_t qs, int32_t qe) { return ichr >= 0 && ichr < nctg && qe > qs; }
+/* a region that is not the first of its (set, contig): E is the maximum end before it */
+static inline IGD_HIP_OV_HD_ int igd_hip_merge_opens(int32_t qs, int32_t E, int64_t gap) { return (int64_t)qs > (int64_t)E + gap; }
+/* tile t of a contig as a query; 0 when the tile begins at or behind INT32_MAX (no region can lie there) */
+static inline IGD_HIP_OV_HD_ int igd_hip_tile_query(int32_t nbp, int64_t t, int32_t *ws, int32_t *we)
+{
+    const int64_t a = t * (int64_t)nbp, b = a + (int64_t)nbp;
+    if (a >= (int64_t)INT32_MAX) return 0;
+    *ws = (int32_t)a;
+    *we = (int32_t)(b > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : b);
+    return 1;
+}
+int igd_hip_merge_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                       int64_t gap, int32_t *m_ichr, int32_t *m_qs, int32_t *m_qe, int64_t *m_off, int32_t *m_count, int64_t *n_dropped);
+int igd_hip_merge_sets_dev(igd_hip_db *db, const int32_t *d_ichr, const int32_t *d_qs, const int32_t *d_qe, const int64_t *d_set_off,
+                           int32_t nsets, int64_t n, int64_t gap, int32_t *d_m_ichr, int32_t *d_m_qs, int32_t *d_m_qe, int64_t *d_m_off,
+                           int32_t *d_m_count, int64_t *d_n_dropped, void *stream);
+int igd_hip_dataset_bp(igd_hip_db *db, int32_t v, int rule, int64_t *file_bp);
+int64_t igd_hip_dataset_bp_computed(const igd_hip_db *db);
+int igd_hip_jaccard_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                         int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *file_bp, int64_t *n_merged, int64_t *n_dropped);
 /* Rows of workgroups (the grid's y) that the reductions over a slice table -- igd_nearest_reduce, igd_nearest_hist,
  * igd_flank_reldist, igd_map_reduce -- are launched with for nslices slices of a matrix of ncols columns (nFiles + 1 for the
  * nearest family, nFiles for igd_hip_map_sets): clamp(16384 / ceil(ncols / 64), 1, min(nslices, 65535)).  Workgroup (x, y) takes
