@@ -8,7 +8,8 @@ __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "re
            "perm_nearest_summary", "PermutationNearest", "map_host", "map_sets_host", "map_summary", "MapSets",
            "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD",
            "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
-           "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP"]
+           "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP",
+           "permute_bp_host", "perm_bp_summary", "PermutationBp"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -33,7 +34,8 @@ def __getattr__(name):
                 "perm_nearest_summary", "PermutationNearest", "map_host", "map_sets_host", "map_summary", "MapSets",
                 "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD",
                 "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
-                "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP"):
+                "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP",
+                "permute_bp_host", "perm_bp_summary", "PermutationBp"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

@@ -235,6 +235,12 @@ def hip():
         L.igd_hip_dataset_bp_computed.restype = C.c_int64
         L.igd_hip_jaccard_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # the permutation null of the base-pair overlap: db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp,
+        # n_merged, n_dropped / pc, nq
+        L.igd_hip_permute_bp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
+                                         C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_merge_slices_per_row.argtypes = [C.c_int64, C.c_int64]
+        L.igd_hip_merge_slices_per_row.restype = C.c_int64
         # the fused route and the permutation null of the distances: as igd_hip_nearest_sets / db, ichr, qs, qe, nq, ctg_len, mode,
         # seed, nperm, window, v, n_within, n_overlap, sum_dist
         L.igd_hip_nearest_sets_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -420,6 +426,11 @@ def _bind_core(L):
     L.igdc_permute_nearest_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                             C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.igdc_perm_nearest_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 12
+    # permutation null of the base-pair overlap on the host: db, map, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter,
+    # set_bp, n_merged, n_dropped / inter, set_bp, file_bp, nperm, ncols, the fourteen outputs
+    L.igdc_permute_bp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                       C.c_uint64, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.igdc_perm_bp_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 14
     # db, path, len (int32[nCtg]), bad_line
     L.igdc_read_genome.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L

@@ -41,6 +41,22 @@ extern "C" int igd_hip_coverage_probe(unsigned long long *out)
 }
 #endif
 
+// igd_sets_coverage over `ns` slices of the table at db->d_setSlices, queries (c, s, e), into db->d_setRows / d_setTot (zeroed)
+static int coverage_launch(igd_hip_db *db, const SliceImage &im, const int32_t *c, const int32_t *s, const int32_t *e, int ns, int grid,
+                           int32_t v, unsigned tag0)
+{
+    const int64_t nF = db->nFiles;
+    u64 *R = (u64 *)db->d_setRows, *T = (u64 *)db->d_setTot;
+    with_flags(im.useV, nF <= IGD_COVERAGE_LDS_FILES, [&](auto V, auto L) {
+        const size_t ldsB = L() ? (size_t)(2 + nF * (1 + IGD_SETS_WG / IGD_WAVE)) * 8 : 0;
+        if (ldsB > (size_t)65536)                        // (more dynamic LDS than a launch gets unasked)
+            (void)hipFuncSetAttribute((const void *)igd_sets_coverage<V(), L()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsB);
+        igd_sets_coverage<V(), L()><<<grid, IGD_SETS_WG, ldsB, db->stream>>>(im.view, c, s, e, db->d_setSlices, ns, im.krule, v, R, T,
+                                                                            (u64 *)db->d_covFront, tag0);
+    });
+    return IGD_HIP_OK;
+}
+
 extern "C" int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                                     const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *coverage, int64_t *covered)
 {
@@ -59,19 +75,8 @@ extern "C" int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const 
     // wide form: as many workgroups as IGD_COVERAGE_FRONT_BYTES of stripes allow (20 000 files: 156 KiB per wave, 419
     // workgroups; 10^6 files: 7.6 MiB per wave, 8 workgroups)
     const int64_t maxGrid = lds ? IGD_SETS_GRID : wide_grid(IGD_COVERAGE_FRONT_BYTES, nF * 8 * (IGD_SETS_WG / IGD_WAVE));
-    hipStream_t st = db->stream;
     unsigned tag0 = 0;
-    auto launch = [&](int ns, int grid) {
-        u64 *R = (u64 *)db->d_setRows, *T = (u64 *)db->d_setTot;
-        with_flags(im.useV, lds, [&](auto V, auto L) {
-            const size_t ldsB = L() ? (size_t)(2 + nF * (1 + IGD_SETS_WG / IGD_WAVE)) * 8 : 0;
-            if (ldsB > (size_t)65536)                    // (more dynamic LDS than a launch gets unasked)
-                (void)hipFuncSetAttribute((const void *)igd_sets_coverage<V(), L()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsB);
-            igd_sets_coverage<V(), L()><<<grid, IGD_SETS_WG, ldsB, st>>>(im.view, db->d_qc, db->d_qs, db->d_qe, db->d_setSlices, ns, im.krule, v, R, T,
-                                                                        (u64 *)db->d_covFront, tag0);
-        });
-        return IGD_HIP_OK;
-    };
+    auto launch = [&](int ns, int grid) { return coverage_launch(db, im, db->d_qc, db->d_qs, db->d_qe, ns, grid, v, tag0); };
     return run_set_chunks(db, ichr, qs, qe, set_off, nsets, sets_slice_len(set_off[nsets]), maxGrid, INT64_MAX, coverage, covered,
                           [&](int64_t m, int64_t, int) {
                               return lds ? IGD_HIP_OK : coverage_fronts(db, maxGrid * (IGD_SETS_WG / IGD_WAVE) * nF, m, &tag0);

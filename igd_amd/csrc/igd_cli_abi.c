@@ -1472,7 +1472,9 @@ static void cooccur_file(char *path, int32_t v)
  * the genome file lacks, ends the run with a message that names the line. */
 /* `-D W` switches the statistic from support to distance (permute_nearest_table below); window < 0: the support. */
 static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int32_t window);
-static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t seed, int pmode, int32_t v, int32_t window)
+/* `-G` switches it to base pairs (permute_bp_table below); it takes no sum of squares on the device, so the guard on it does not apply. */
+static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int rule);
+static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t seed, int pmode, int32_t v, int32_t window, int gbp)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
@@ -1512,11 +1514,12 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
         if (igdc_queries_push(&q, id, st, en) != 0) { fprintf(stderr, "igd: out of memory\n"); goto done; }
     }
     if (q.n > igd_hip_max_batch() ||
-        (window < 0 && (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63)) {
+        (window < 0 && !gbp && (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63)) {
         printf("Not supported: -P %lld with %lld regions\n", (long long)nperm, (long long)q.n);
         goto done;
     }
-    if (window >= 0) permute_nearest_table(&q, len, nperm, seed, pmode, ev, window);
+    if (gbp) permute_bp_table(&q, len, nperm, seed, pmode, ev, rule);
+    else if (window >= 0) permute_nearest_table(&q, len, nperm, seed, pmode, ev, window);
     else {
         int64_t *st7 = (int64_t *)calloc(7 * (size_t)nC, sizeof(int64_t));
         double *fl = (double *)calloc(5 * (size_t)nC, sizeof(double));
@@ -1920,6 +1923,57 @@ static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int
     free(st3); free(fl);
 }
 
+/* ------------------------------- `igd search -q F -P N -g genome -G` ------------------- */
+/* Permutation null of the base-pair overlap (include/igd_hip.h: igd_hip_permute_bp; igd_core.h: igdc_perm_bp_summary has the
+ * columns): "does my region set share more base pairs with dataset f than chance".  -G is to -J what -D is to -N.  The header
+ *     index observed_bp mean sd z fold n_ge n_le nlog10_p_upper nlog10_p_lower jaccard jaccard_mean File     (tab-separated)
+ * and one line per dataset; floats as %.6f, NaN as NA; then -J's last line for the set as given (without its Jaccard),
+ * followed by the same statistics (mean .. jaccard_mean) of the any-dataset column.  Rule and filter are `-q`'s dispatch for
+ * -v.  Routing as -P: regions x (N + 1) against igdc_host_limit(). */
+static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int rule)
+{
+    const int32_t nfiles = IGD->nFiles;
+    const size_t nC = (size_t)nfiles + 1, R = (size_t)nperm + 1;
+    int64_t *st = (int64_t *)calloc(R * nC + 2 * R + 1 + 4 * nC, sizeof(int64_t));
+    double *fl = (double *)calloc(9 * nC, sizeof(double));
+    if (!st || !fl) { fprintf(stderr, "igd: out of memory\n"); free(st); free(fl); return; }
+    int64_t *inter = st, *sbp = inter + R * nC, *nm = sbp + R, *nd = nm + R, *fbp = nd + 1, *obs = fbp + nC, *nge = obs + nC, *nle = nge + nC;
+    double *mu = fl, *sd = mu + nC, *z = sd + nC, *fold = z + nC, *pu = fold + nC, *pl = pu + nC, *jac = pl + nC, *jm = jac + nC, *js = jm + nC;
+    double t0 = now_s();
+    int ok = 0;
+    igdc_map *hm = host_map_lim(q->n * (nperm + 1), igdc_host_limit());
+    if (hm) {
+        ok = igdc_permute_bp_host(g_core, hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd) == 0 &&
+             igdc_dataset_bp_host(g_core, hm, ev, rule, fbp) == 0;
+        igdc_map_close(hm);
+        if (ok) phase("permutation null of the base-pair overlap on the host (small files)", &t0);
+    }
+    if (!ok) {                                        /* (after a read error too: the engine reads the file its own way) */
+        igd_hip_db *dev = engine();
+        t0 = now_s();
+        if (dev) {
+            int rc = igd_hip_permute_bp(dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd);
+            if (rc == IGD_HIP_OK) rc = igd_hip_dataset_bp(dev, ev, rule, fbp);
+            if (rc != IGD_HIP_OK) engine_failed("permutation null of the base-pair overlap", rc);
+            phase("permutation null of the base-pair overlap (H2D + permute, merge, hand-over and coverage kernels + D2H)", &t0);
+        }
+    }
+    if (!g_fail_rc && igdc_perm_bp_summary(inter, sbp, fbp, nperm, (int64_t)nC, obs, mu, sd, z, fold, nge, nle, pu, pl, jac, jm, js, NULL, NULL) == 0) {
+        printf("index\tobserved_bp\tmean\tsd\tz\tfold\tn_ge\tn_le\tnlog10_p_upper\tnlog10_p_lower\tjaccard\tjaccard_mean\tFile\n");
+        for (int32_t i = 0; i <= nfiles; i++) {
+            if (i < nfiles) printf("%d\t%lld\t", (int)i, (long long)obs[i]);
+            else printf("Any dataset: %lld of %lld bp in %lld merged regions (%lld dropped)\t", (long long)obs[i], (long long)sbp[0], (long long)nm[0],
+                        (long long)nd[0]);
+            print_na("%.6f", mu[i], "\t"); print_na("%.6f", sd[i], "\t"); print_na("%.6f", z[i], "\t"); print_na("%.6f", fold[i], "\t");
+            printf("%lld\t%lld\t", (long long)nge[i], (long long)nle[i]);
+            print_na("%.6f", pu[i], "\t"); print_na("%.6f", pl[i], "\t"); print_na("%.6f", jac[i], "\t");
+            print_na("%.6f", jm[i], i < nfiles ? "\t" : "\n");
+            if (i < nfiles) printf("%s\n", IGD->finfo[i].fileName);
+        }
+    }
+    free(st); free(fl);
+}
+
 /* ------------------------------- `igd search` ----------------------------------------- */
 static int usage_search(void)
 {
@@ -1967,6 +2021,9 @@ static int usage_search(void)
             "    -D <bp>                    with -P: the null of the distances instead -- per dataset the regions with a record within\n"
             "                               <bp> base pairs (0 to 1073741824) and their mean distance to the nearest one, each\n"
             "                               placed among the permuted sets' (mean, sd, z, one-sided p)\n"
+            "    -G                         with -P: the null of the base-pair overlap instead -- per dataset the base pairs the merged\n"
+            "                               regions share with it (as -J) placed among the permuted sets' (mean, sd, z, fold, both\n"
+            "                               one-sided p) and the Jaccard with the mean permuted one\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -2019,6 +2076,7 @@ int igd_search(int argc, char **argv)                                        /* 
     char *binsArg = NULL;                                                             /* -L (see flank_reldist_files) */
     int flankL = 0, flankEdges = 0;                                                   /* -L, -E given */
     int jac = 0;                                                                      /* -J given (see jaccard_files) */
+    int gbp = 0;                                                                      /* -G given (see permute_bp_table) */
     char *mapArg = NULL;                                                              /* -V (see map_files) */
     char out[64] = "";
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -2050,6 +2108,8 @@ int igd_search(int argc, char **argv)                                        /* 
             bp = 1;
         } else if (strcmp(a, "-J") == 0) {            /* (not the reference's: base-pair Jaccard, see jaccard_files) */
             jac = 1;
+        } else if (strcmp(a, "-G") == 0) {            /* (not the reference's: -P on the base-pair overlap, see permute_bp_table) */
+            gbp = 1;
         } else if (strcmp(a, "-w") == 0) {            /* (not the reference's: per-query membership, see membership_files) */
             memb = 1;
         } else if (strcmp(a, "-U") == 0) {            /* (not the reference's: enrichment against a universe, see enrich_files) */
@@ -2115,6 +2175,23 @@ int igd_search(int argc, char **argv)                                        /* 
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    if (gbp) {                                                                /* -G: every refusal is a usage error */
+        char *pend = NULL;
+        const long long np = permArg ? strtoll(permArg, &pend, 10) : 0;
+        const char *why = NULL;
+        if (!permArg) why = "-G without -P";
+        else if (distArg || jac || minov || nearArg || histArg || flankL || flankEdges || mapArg || listName || uniq || bp || memb || uniName ||
+                 ranks || restricted || cooc || full || other)
+            why = "-G together with -D, -J, -O, -A, -B, -N, -H, -L, -E, -V, -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r";
+        else if (!genomeName) why = "-G -P without -g";
+        else if (mode != 1) why = "-G -P without -q";
+        else if (pend == permArg || *pend || np < 1 || np > (long long)IGD_HIP_PERM_MAX) why = "-G with a number of permutations outside 1 to 1048576";
+        else if (pmodeArg && strcmp(pmodeArg, "circular") != 0 && strcmp(pmodeArg, "shuffle") != 0) why = "-G with a -M that is neither circular nor shuffle";
+        if (why) {
+            printf("Not supported: %s\n", why);
+            return EX_USAGE;
+        }
+    }
     if (jac) {                                                                /* -J: every refusal is a usage error */
         const char *why = NULL;
         if (uniq || bp || memb || uniName || ranks || restricted || cooc || permArg || distArg || nearArg || histArg || flankL || flankEdges ||
@@ -2279,7 +2356,7 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported: -M %s (circular or shuffle)\n", pmodeArg);
             return EX_OK;
         }
-        permute_file(qfName, genomeName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW);
+        permute_file(qfName, genomeName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW, gbp);
     } else if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
         printf("Not supported: -C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r\n");
         return EX_OK;

@@ -289,6 +289,31 @@ int igdc_perm_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, 
                               double *within_sd, double *within_z, int64_t *within_n_ge, double *nlog10_p_within_upper, double *mean_dist,
                               double *dist_mean, double *dist_sd, double *dist_z, int64_t *n_def, int64_t *dist_n_le,
                               double *nlog10_p_dist_lower);
+/* Permutation null of the base-pair overlap on the host (what igd_hip_permute_bp computes; include/igd_hip.h): inter is
+ * int64[(nperm + 1) * (nFiles + 1)], set_bp and n_merged int64[nperm + 1], n_dropped one word (each may be NULL); row 0 the set as
+ * given, row p + 1 permutation p of igdc_permute_regions_host's generator, every row merged by igdc_merge_host at gap 0 and its
+ * runs covered by igdc_coverage_host; threads run over the rows.  0; -1 for a refused argument (igdc_permute_host's but the
+ * sumsq guard) or when a tile could not be read -- nothing is written then. */
+int igdc_permute_bp_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
+                         int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped);
+/* The summary of such a null distribution, per column f of ncols; inter is int64[(nperm + 1) * ncols], set_bp int64[nperm + 1],
+ * file_bp int64[ncols] (igd_hip_dataset_bp).  With P = nperm, x_0 the observed row and x_p the permuted rows of column f:
+ *     base pairs  observed = x_0; mean, sd, z: igdc_perm_summary's formulas over x_p (sum and sum of squares exact in 128 bits
+ *                 -- x^2 alone passes 2^63 from 3.04 x 10^9 bp; sd NaN when P = 1, z NaN when sd is 0 or NaN);
+ *                 fold = x_0 / mean, NaN when the mean is 0; n_ge = #{p : x_p >= x_0}, n_le = #{p : x_p <= x_0};
+ *                 nlog10_p_upper = -log10((n_ge + 1) / (P + 1)), nlog10_p_lower = -log10((n_le + 1) / (P + 1))
+ *     Jaccard     u_r = set_bp[r] + file_bp[f] - x_r, the union of row r; jaccard = x_0 / u_0 (NaN when u_0 = 0);
+ *                 jaccard_n_def = #{p : u_p != 0}; jaccard_mean and jaccard_sd over j_p = x_p / u_p of those permutations, in
+ *                 doubles, two passes in permutation order (mean NaN when n_def = 0; sd divides by n_def - 1, NaN when
+ *                 n_def < 2); jaccard_n_ge = #{p : u_p != 0 and x_p * u_0 >= x_0 * u_p}, compared exactly in 128 bits (the
+ *                 products reach about 2^77) -- a ratio over 0 is not defined and counts on neither side -- and 0 when u_0 = 0
+ * observed, n_ge, n_le, jaccard_n_def and jaccard_n_ge are int64[ncols], the others double[ncols]; every output may be NULL.
+ * Needs no database.  0, or -1 for a missing input or nperm < 1. */
+int igdc_perm_bp_summary(const int64_t *inter, const int64_t *set_bp, const int64_t *file_bp, int64_t nperm, int64_t ncols,
+                         int64_t *observed, double *mean, double *sd, double *z, double *fold, int64_t *n_ge, int64_t *n_le,
+                         double *nlog10_p_upper, double *nlog10_p_lower, double *jaccard, double *jaccard_mean, double *jaccard_sd,
+                         int64_t *jaccard_n_def, int64_t *jaccard_n_ge);
 /* A genome file, lines `name<TAB>length`: len[c] = the length of contig c of the database (int32[nCtg]); lines of contigs the
  * database does not know are ignored, contigs the file does not name get 0.  0; -1 when the file cannot be opened; -2 for a
  * line of a known contig without a length or with one that is negative or above 2^31 - 1 (*bad_line, may be NULL, = its

@@ -353,6 +353,11 @@ struct igd_hip_db {
     // igd_hip_merge_sets / _dev (host_merge.hpp): every array of one merge, carved from one allocation (bytes)
     char *d_merge;
     int64_t mergeCap;
+    // igd_hip_permute_bp (host_permute_bp.hpp): the runs of one chunk of rows (m_ichr, m_qs, m_qe), and its 64-bit words: the
+    // regular set offsets, the run offsets, dropped, set_bp and n_merged per row
+    int32_t *d_pbRun;
+    int64_t *d_pbWord;
+    int64_t pbRunCap, pbWordCap;
     // igd_hip_dataset_bp: the tiles of every contig as the file has them (host copy), the merged base pairs per dataset that
     // have been computed so far, one entry per (v, rule), and how often one was computed
     struct BpEntry { int32_t v; int rule; std::vector<int64_t> bp; };
@@ -398,6 +403,7 @@ struct igd_hip_db {
 #include "engine/nearest_fused_dev.hpp" // igd_nearest_slices: the same walk and table, folded into per-slice LDS accumulators -- the set statistics without the rows
 #include "engine/map_dev.hpp"         // igd_map_rows, igd_map_reduce: the same walk with the value words, count and sum / min / max rows per region -- values of the overlapping records
 #include "engine/merge_dev.hpp"       // igd_merge_*: region sets merged as `bedtools merge` -- sort keys, segmented maximum scan of the ends, run heads and compaction
+#include "engine/permute_bp_dev.hpp"  // igd_merge_row_offsets, igd_merge_slices, igd_merge_row_bp: the merged runs handed to igd_sets_coverage on the device -- permutation null of base-pair overlap
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
 #include "engine/host_search.hpp"     // workspaces, launches, igd_hip_search_dev / _runs_dev / _search / _search_ex, sync
 #include "engine/host_group.hpp"      // device groups of one process: native RCCL all-reduce of hits[]
@@ -419,6 +425,7 @@ struct igd_hip_db {
 #include "engine/host_permute_nearest.hpp" // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: one fused launch per chunk, the null distribution of the distance statistics
 #include "engine/host_map.hpp"        // igd_hip_map / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
 #include "engine/host_merge.hpp"      // igd_hip_merge_sets / _dev, igd_hip_dataset_bp, igd_hip_jaccard_sets: device merge, merged base pairs per dataset, the intersection table
+#include "engine/host_permute_bp.hpp" // igd_hip_permute_bp: chunks of permutations, merged and covered without a host copy in between
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

@@ -215,6 +215,23 @@ int igd_hip_jaccard_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
     return fn ? fn(db, ichr, qs, qe, set_off, nsets, v, rule, inter, set_bp, file_bp, n_merged, n_dropped) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                       int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
+                       int64_t *n_dropped)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int, uint64_t, int64_t,
+                        int32_t, int, int64_t *, int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_permute_bp");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped) : IGD_HIP_ERR_DEVICE;
+}
+
+int64_t igd_hip_merge_slices_per_row(int64_t pc, int64_t nq)
+{
+    typedef int64_t (*fn_t)(int64_t, int64_t);
+    RESOLVE(fn_t, "igd_hip_merge_slices_per_row");
+    return fn ? fn(pc, nq) : 0;
+}
+
 int64_t igd_hip_member_words(const igd_hip_db *db)
 {
     typedef int64_t (*fn_t)(const igd_hip_db *);

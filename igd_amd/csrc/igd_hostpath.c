@@ -1954,3 +1954,147 @@ int igdc_jaccard_summary(const int64_t *inter, const int64_t *set_bp, const int6
         }
     return 0;
 }
+
+/* ---- permutation null of the base-pair overlap (what igd_hip_permute_bp computes; include/igd_hip.h has the definitions) --
+ * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator; a row is igdc_jaccard_host's
+ * treatment of one set: igdc_merge_host at gap 0, then igdc_coverage_host over the runs.  Threads run over the rows (thread k
+ * takes rows k, k + T, ..), each with its own permuted arrays and run arrays; the rows are disjoint.  Everything is computed
+ * into a buffer and copied out at the end: -1 (a refused argument, a tile that could not be read) writes nothing. */
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe, *ctg_len;
+    int64_t nq, nrows;
+    int mode; uint64_t seed;
+    int32_t v; int rule;
+    int64_t *inter, *set_bp, *n_merged, *dropped;   /* nrows x (nFiles + 1), nrows, nrows, nrows */
+    int32_t *ps, *pe, *mr;                          /* the permuted set; the runs (3 x nq) */
+    int k, T, failed;
+} pbp_job;
+
+static void *pbp_run(void *arg)
+{
+    pbp_job *P = (pbp_job *)arg;
+    const int64_t nF = P->db->nFiles, nq = P->nq, off[2] = {0, nq};
+    for (int64_t r = P->k; r < P->nrows && !P->failed; r += P->T) {
+        const int32_t *s = P->qs, *e = P->qe;
+        if (r > 0) {
+            (void)igdc_permute_regions_host(P->ichr, P->qs, P->qe, nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, r - 1, 1, P->ps, P->pe);
+            s = P->ps; e = P->pe;
+        }
+        int64_t moff[2], bp = 0;
+        if (igdc_merge_host(P->db, P->ichr, s, e, off, 1, 0, P->mr, P->mr + nq, P->mr + 2 * nq, moff, NULL, &P->dropped[r]) != 0) { P->failed = 1; break; }
+        for (int64_t i = 0; i < moff[1]; i++) bp += (int64_t)P->mr[2 * nq + i] - (int64_t)P->mr[nq + i];
+        P->set_bp[r] = bp;
+        P->n_merged[r] = moff[1];
+        int64_t *row = P->inter + r * (nF + 1);
+        if (igdc_coverage_host(P->db, P->m, P->mr, P->mr + nq, P->mr + 2 * nq, moff[1], P->v, P->rule, row, row + nF) != 0) P->failed = 1;
+    }
+    return NULL;
+}
+
+int igdc_permute_bp_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
+                         int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped)
+{
+    if (!db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) ||
+        nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0)
+        return -1;
+    const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
+    int T = host_threads(nq * R > 0 ? nq * R : 1);
+    if (T > R) T = (int)R;
+    int64_t *res = (int64_t *)calloc((size_t)(R * nC + 3 * R), sizeof(int64_t));
+    int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 5 * (size_t)nq + 1));
+    int rc = res && w ? 0 : -1;
+    pbp_job job[64];
+    pthread_t th[64];
+    int started[64];
+    for (int k = 0; k < T && rc == 0; k++) {
+        memset(&job[k], 0, sizeof job[k]);
+        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe; job[k].ctg_len = ctg_len;
+        job[k].nq = nq; job[k].nrows = R; job[k].mode = mode; job[k].seed = seed; job[k].v = v; job[k].rule = rule;
+        job[k].inter = res; job[k].set_bp = res + R * nC; job[k].n_merged = job[k].set_bp + R; job[k].dropped = job[k].n_merged + R;
+        job[k].ps = w + (size_t)k * 5 * (size_t)nq; job[k].pe = job[k].ps + nq; job[k].mr = job[k].pe + nq;
+        job[k].k = k; job[k].T = T;
+    }
+    if (rc == 0 && nq > 0) {
+        for (int k = 1; k < T; k++) {
+            started[k] = pthread_create(&th[k], NULL, pbp_run, &job[k]) == 0;
+            if (!started[k]) pbp_run(&job[k]);
+        }
+        pbp_run(&job[0]);
+        for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
+        for (int k = 0; k < T; k++) if (job[k].failed) rc = -1;
+    }
+    if (rc == 0) {
+        if (inter) memcpy(inter, res, sizeof(int64_t) * (size_t)(R * nC));
+        if (set_bp) memcpy(set_bp, res + R * nC, sizeof(int64_t) * (size_t)R);
+        if (n_merged) memcpy(n_merged, res + R * nC + R, sizeof(int64_t) * (size_t)R);
+        if (n_dropped) *n_dropped = res[R * nC + 2 * R];
+    }
+    free(res); free(w);
+    return rc;
+}
+
+/* the summary of a null distribution of base-pair overlaps; igd_core.h has the formulas */
+int igdc_perm_bp_summary(const int64_t *inter, const int64_t *set_bp, const int64_t *file_bp, int64_t nperm, int64_t ncols,
+                         int64_t *observed, double *mean, double *sd, double *z, double *fold, int64_t *n_ge, int64_t *n_le,
+                         double *nlog10_p_upper, double *nlog10_p_lower, double *jaccard, double *jaccard_mean, double *jaccard_sd,
+                         int64_t *jaccard_n_def, int64_t *jaccard_n_ge)
+{
+    const double P = (double)nperm, nan = __builtin_nan("");
+    if (!sqrt || !log10 || nperm < 1 || ncols < 0 || (ncols > 0 && (!inter || !set_bp || !file_bp))) return -1;
+    for (int64_t f = 0; f < ncols; f++) {
+        const int64_t x0 = inter[f], u0 = set_bp[0] + file_bp[f] - x0;
+        /* base pairs: igdc_perm_summary's formulas, the sums exact in 128 bits */
+        __int128 sum = 0, sumsq = 0;
+        int64_t nge = 0, nle = 0;
+        for (int64_t p = 1; p <= nperm; p++) {
+            const int64_t x = inter[p * ncols + f];
+            sum += x;
+            sumsq += (__int128)x * (__int128)x;
+            nge += x >= x0;
+            nle += x <= x0;
+        }
+        const double mu = (double)sum / P;
+        double s = nan;
+        if (nperm > 1) s = sqrt((double)((__int128)nperm * sumsq - sum * sum) / (P * (P - 1.0)));
+        if (observed) observed[f] = x0;
+        if (mean) mean[f] = mu;
+        if (sd) sd[f] = s;
+        if (z) z[f] = (s != s || s == 0.0) ? nan : ((double)x0 - mu) / s;
+        if (fold) fold[f] = mu != 0.0 ? (double)x0 / mu : nan;
+        if (n_ge) n_ge[f] = nge;
+        if (n_le) n_le[f] = nle;
+        if (nlog10_p_upper) nlog10_p_upper[f] = 0.0 - log10((double)(nge + 1) / (P + 1.0));
+        if (nlog10_p_lower) nlog10_p_lower[f] = 0.0 - log10((double)(nle + 1) / (P + 1.0));
+        /* Jaccards: j_p = x_p / u_p over the permutations with u_p != 0, two passes in permutation order */
+        int64_t ndef = 0, jge = 0;
+        double acc = 0.0;
+        for (int64_t p = 1; p <= nperm; p++) {
+            const int64_t xp = inter[p * ncols + f], up = set_bp[p] + file_bp[f] - xp;
+            if (up == 0) continue;
+            ndef++;
+            acc += (double)xp / (double)up;
+            if (u0 != 0 && (__int128)xp * (__int128)u0 >= (__int128)x0 * (__int128)up) jge++;
+        }
+        const double jmu = ndef > 0 ? acc / (double)ndef : nan;
+        double js = nan;
+        if (ndef > 1) {
+            double ss = 0.0;
+            for (int64_t p = 1; p <= nperm; p++) {
+                const int64_t xp = inter[p * ncols + f], up = set_bp[p] + file_bp[f] - xp;
+                if (up == 0) continue;
+                const double t = (double)xp / (double)up - jmu;
+                ss += t * t;
+            }
+            js = sqrt(ss / (double)(ndef - 1));
+        }
+        if (jaccard) jaccard[f] = igdc_jaccard_value(x0, set_bp[0], file_bp[f]);
+        if (jaccard_mean) jaccard_mean[f] = jmu;
+        if (jaccard_sd) jaccard_sd[f] = js;
+        if (jaccard_n_def) jaccard_n_def[f] = ndef;
+        if (jaccard_n_ge) jaccard_n_ge[f] = jge;
+    }
+    return 0;
+}

@@ -36,6 +36,10 @@ NearestSets = collections.namedtuple("NearestSets", "n_within n_overlap sum_dist
 PermutationNearest = collections.namedtuple("PermutationNearest", "n_within n_overlap sum_dist window nperm")
 MapSets = collections.namedtuple("MapSets", "n_hit pairs agg_sum op")
 MAP_OPS = {"count": 0, "sum": 1, "min": 2, "max": 3}             # IGD_HIP_MAP_COUNT, _SUM, _MIN, _MAX
+PermutationBp = collections.namedtuple("PermutationBp", "inter set_bp n_merged n_dropped file_bp nperm")
+PermutationBpSummary = collections.namedtuple(
+    "PermutationBpSummary", "observed mean sd z fold n_ge n_le nlog10_p_upper nlog10_p_lower jaccard jaccard_mean jaccard_sd jaccard_n_def "
+    "jaccard_n_ge")
 PermutationNearestSummary = collections.namedtuple(
     "PermutationNearestSummary", "within_mean within_sd within_z within_n_ge nlog10_p_within_upper mean_dist dist_mean dist_sd dist_z n_def "
     "dist_n_le nlog10_p_dist_lower")
@@ -659,6 +663,46 @@ def _merge_out(n, nsets):
 def _merge_cut(mc, ms, me, moff, cnt, dropped):
     r = int(moff[-1])
     return mc[:r], ms[:r], me[:r], moff, cnt[:r], dropped
+
+
+def permute_bp_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
+    """Database.permutation_bp() on the host (igdc_permute_bp_host: pread on the .igd, threads over the permutations; no device
+    is touched): a PermutationBp."""
+    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_bp_host")
+    pm = _perm_mode(mode, "permute_bp_host")
+    with _HostDb(igd_path, "permute_bp_host") as h:
+        nctg = h.core.contents.nCtg
+        if len(ctg_len) != nctg:
+            raise IgdError("permute_bp_host: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), nctg))
+        rule, vf = h.dispatch(v, rule, value_filter)
+        rows = max(int(nperm), 0) + 1
+        inter, set_bp, n_merged = np.empty((rows, h.nfiles + 1), np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
+        dropped, file_bp = np.zeros(1, np.int64), np.empty(h.nfiles + 1, np.int64)
+        if h.L.igdc_permute_bp_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, int(seed) & (2 ** 64 - 1),
+                                    int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged), _ptr(dropped)) != 0:
+            raise IgdError("permute_bp_host: a refused argument (number of permutations, a region outside its contig), or a tile of %s "
+                           "could not be read" % igd_path)
+        if h.L.igdc_dataset_bp_host(h.core, h.m, vf, rule, file_bp.ctypes.data) != 0:
+            raise IgdError("permute_bp_host: a tile of %s could not be read" % igd_path)
+        return PermutationBp(inter, set_bp, n_merged, int(dropped[0]), file_bp, int(nperm))
+
+
+def perm_bp_summary(pb):
+    """The summary of a PermutationBp (igdc_perm_bp_summary; igd_core.h has the formulas): a PermutationBpSummary of arrays
+    [nfiles + 1] -- float64, but observed, n_ge, n_le, jaccard_n_def and jaccard_n_ge, which are int64.  Of the base pairs: the
+    observed overlap, mean, sd (ddof = 1) and z of the permuted ones, fold = observed / mean, the permutations with at least
+    and at most the observed overlap and -log10 of the two p-values.  Of the Jaccards: the observed one, mean and sd of the
+    permuted ones over the jaccard_n_def permutations that have one, and the permutations whose Jaccard is at least the
+    observed one (compared exactly)."""
+    inter, set_bp, file_bp = (np.ascontiguousarray(x, dtype=np.int64) for x in (pb.inter, pb.set_bp, pb.file_bp))
+    if inter.ndim != 2 or inter.shape != (int(pb.nperm) + 1, len(file_bp)) or set_bp.shape != (inter.shape[0],):
+        raise IgdError("perm_bp_summary: inter must be int64[nperm + 1, ncols], set_bp int64[nperm + 1], file_bp int64[ncols]")
+    n = inter.shape[1]
+    kinds = [np.int64] + [np.float64] * 4 + [np.int64] * 2 + [np.float64] * 5 + [np.int64] * 2
+    out = [np.empty(n, k) for k in kinds]
+    if N.cli().igdc_perm_bp_summary(_ptr(inter), _ptr(set_bp), _ptr(file_bp), int(pb.nperm), n, *[_ptr(x) for x in out]) != 0:
+        raise IgdError("perm_bp_summary: bad argument")
+    return PermutationBpSummary(*out)
 
 
 def merge_host(igd_path, ichr, qs, qe, set_off, gap=0):
@@ -1611,6 +1655,35 @@ class Database:
         _chk(self._H.igd_hip_jaccard_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, vf, rule, _ptr(js.inter),
                                           _ptr(js.set_bp), js.file_bp.ctypes.data, _ptr(js.n_merged), _ptr(js.n_dropped)), "igd_hip_jaccard_sets")
         return js
+
+    def permutation_bp(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
+        """Permutation null of the base-pair overlap of one region set (igd_hip_permute_bp): "does my set share more base pairs
+        with dataset f than chance".  The set is moved nperm times as permutation_support() moves it (same generator, mode,
+        seed and ctg_len), and the set as given and every permuted set are treated as jaccard_sets() treats a set: merged at gap
+        0, then covered.  Returns PermutationBp(inter int64[nperm + 1, nfiles + 1], set_bp, n_merged int64[nperm + 1], n_dropped,
+        file_bp int64[nfiles + 1], nperm): row 0 the set as given, row p + 1 permutation p, the last column "any dataset";
+        file_bp is dataset_bp().  Neither the permuted regions nor the merged runs leave the device.  perm_bp_summary() places
+        the observed row in the null distribution."""
+        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_bp")
+        if len(ctg_len) != self.nctg:
+            raise IgdError("permutation_bp: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), self.nctg))
+        if rule is None:
+            rule, vf = self.cli_dispatch(self.gtype, v)
+        else:
+            vf = _value_filter(value_filter)
+        rows = max(int(nperm), 0) + 1
+        inter, set_bp, n_merged = np.empty((rows, self.nfiles + 1), np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
+        dropped, file_bp = np.zeros(1, np.int64), np.empty(self.nfiles + 1, np.int64)
+        _chk(self._H.igd_hip_permute_bp(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), _perm_mode(mode, "permutation_bp"),
+                                        int(seed) & (2 ** 64 - 1), int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged),
+                                        _ptr(dropped)), "igd_hip_permute_bp")
+        _chk(self._H.igd_hip_dataset_bp(self.dev, vf, rule, file_bp.ctypes.data), "igd_hip_dataset_bp")
+        return PermutationBp(inter, set_bp, n_merged, int(dropped[0]), file_bp, int(nperm))
+
+    def permutation_bp_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0):
+        """The null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the integers behind
+        what `igd search -q path -P nperm -g genome_path -G` prints."""
+        return self.permutation_bp(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v)
 
     def jaccard_files(self, paths, v=0):
         """One region set per BED file (read as `igd search -q` reads it): the JaccardSets of jaccard_sets()."""

@@ -549,6 +549,43 @@ int igd_hip_dataset_bp(igd_hip_db *db, int32_t v, int rule, int64_t *file_bp);
 int64_t igd_hip_dataset_bp_computed(const igd_hip_db *db);
 int igd_hip_jaccard_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
                          int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *file_bp, int64_t *n_merged, int64_t *n_dropped);
+
+/* The permutation null of the base-pair overlap: "does my region set share more base pairs with dataset f than chance" (GAT's
+ * nucleotide overlap, regioneR's permTest with numOverlaps in bp).  THE DEFINITIONS (the one place: the kernels of
+ * permute_bp_dev.hpp, igdc_permute_bp_host and the tests' reference agree on every integer).
+ *     inputs       one set of nq regions; ctg_len, mode, seed and nperm exactly as for igd_hip_permute_support (the generator is
+ *                  igd_hip_perm_place below; 0 <= s <= e <= L on known contigs; nperm 1 .. IGD_HIP_PERM_MAX; nq <=
+ *                  igd_hip_max_batch(); no sum of squares is taken, so that call's sumsq guard does not apply); v and rule
+ *                  as for igd_hip_jaccard_sets.
+ *     rows         Row 0 is the set as given, row p + 1 the set under permutation p.  Every row is treated as
+ *                  igd_hip_jaccard_sets treats a set: its regions are merged at gap 0 (igd_hip_merge_takes_part,
+ *                  igd_hip_merge_opens; zero-length regions and regions on unknown contigs are dropped), and the runs are
+ *                  covered as igd_hip_coverage_sets covers them.  Every row is merged ANEW: both modes can put a region
+ *                  over another (`circular` pushes a region that would cross the contig's end back against it).
+ *     inter        int64[nperm + 1][nFiles + 1]: column f is |row n union of the records of dataset f| in bp, column nFiles
+ *                  the same against any dataset (the coverage stage's covered[]).
+ *     set_bp       int64[nperm + 1]: the merged bp of the row; it varies per permutation, overlaps come and go.
+ *     n_merged     int64[nperm + 1]: the runs of the row.
+ *     n_dropped    one int64: the regions that take no part -- the same in every row, a permutation moves neither a
+ *                  zero-length region onto a length nor a region onto a known contig.
+ * Any output may be NULL; all are DEFINED by the call.  file_bp is igd_hip_dataset_bp and is not computed again.  The null
+ * distribution itself comes back, not moments of it: with x in base pairs x^2 passes 2^63 from x = 3.04 x 10^9, one human
+ * genome's worth; igdc_perm_bp_summary (igd_core.h) takes the summary on the host.
+ * Chunks of pc permutations, pc * nq <= igd_hip_max_batch() and pc * nFiles * 8 <= the row budget of igd_hip_permute_support
+ * (TEST-ONLY: IGD_HIP_PERM_ROW_BYTES); per chunk igd_permute_regions, the merge launches, igd_merge_slices, igd_sets_coverage,
+ * igd_merge_row_bp and the copies, enqueued without a wait or a host copy in between: the merged runs stay on the device.
+ * igd_hip_merge_slices_per_row: the slice slots every row gets when pc rows of nq regions are handed over (tests):
+ * ceil(nq / L) with L = clamp(ceil(pc nq / 4096), 64, 4096), the slice length of igd_hip_coverage_sets for pc nq queries.
+ * IGD_HIP_ERR_ARG before any launch, nothing of the caller's written: a missing array, no such rule or mode, nperm < 1 or >
+ * IGD_HIP_PERM_MAX, nq > igd_hip_max_batch(), a region on a known contig outside 0 <= s <= e <= L.  nq == 0: all zeros;
+ * nFiles == 0: inter is zeros, set_bp and n_merged are still the rows'.  Blocking, one device; ordered with the other merges
+ * of the handle as igd_hip_merge_sets is.
+ * Not done: several sets in one call, a gap other than 0, a shuffle restricted to a workspace (GAT's), regions split at a
+ * contig's end, several devices, igd_hip_jaccard_sets itself on the resident hand-over. */
+int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                       int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
+                       int64_t *n_dropped);
+int64_t igd_hip_merge_slices_per_row(int64_t pc, int64_t nq);
 /* Rows of workgroups (the grid's y) that the reductions over a slice table -- igd_nearest_reduce, igd_nearest_hist,
  * igd_flank_reldist, igd_map_reduce -- are launched with for nslices slices of a matrix of ncols columns (nFiles + 1 for the
  * nearest family, nFiles for igd_hip_map_sets): clamp(16384 / ceil(ncols / 64), 1, min(nslices, 65535)).  Workgroup (x, y) takes
