@@ -295,6 +295,148 @@ static igdc_map *host_map_lim(int64_t nq, int64_t lim)
     return m;
 }
 
+/* ------------------------------- shared by the table commands of `igd search` ---------- */
+/* the dispatch of `-q` on gType and -v (:1023-1030): returns the value filter and stores the tile rule (NULL: the command has none) */
+static int32_t q_dispatch(int32_t v, int *rule)
+{
+    const int byValue = IGD->gType != 0 && v > 0;
+    if (rule) *rule = byValue ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;
+    return byValue ? v : IGD_HIP_NO_VALUE_FILTER;
+}
+
+/* The route of a table command.  While no engine is resident and at most igdc_host_limit() regions are asked about, the host
+ * answers from the mapped database (igd_hostpath.c); otherwise, and after a read error there, the engine does (IGD_DEVICES with
+ * several devices: the first one, as -Q).  The two calls are the command's own:
+ *     cli_route R;
+ *     if (route_host(&R, regions)) route_host_end(&R, igdc_x_host(g_core, R.hm, ..) == 0, "<host label>");
+ *     if (route_engine(&R, gate)) route_engine_end(&R, "x", igd_hip_x(R.dev, ..), "<engine label>");
+ * `gate` is the command's reason to ask the engine at all (for most: regions > 0).  An engine failure is reported here and leaves
+ * g_fail_rc set: the command prints no table then, as `-q`. */
+typedef struct { igdc_map *hm; igd_hip_db *dev; int onHost; double t0; } cli_route;
+
+static int route_host(cli_route *R, int64_t regions)
+{
+    R->dev = NULL; R->onHost = 0;
+    R->hm = host_map_lim(regions, igdc_host_limit());
+    R->t0 = now_s();
+    return R->hm != NULL;
+}
+
+static int route_host_end(cli_route *R, int ok, const char *label)
+{
+    igdc_map_close(R->hm);
+    R->hm = NULL;
+    if ((R->onHost = ok)) phase(label, &R->t0);
+    return ok;
+}
+
+static int route_engine(cli_route *R, int gate)
+{
+    if (R->onHost || !gate) return 0;
+    R->dev = engine();
+    R->t0 = now_s();
+    return R->dev != NULL;
+}
+
+static void route_engine_end(cli_route *R, const char *name, int rc, const char *label)
+{
+    if (rc != IGD_HIP_OK) engine_failed(name, rc);
+    phase(label, &R->t0);
+}
+
+/* The query files of a command: the one of `-q` (no "Query set" lines), else those of the `-Q` list -- one per line, blank lines
+ * skipped, a trailing CR stripped. */
+typedef struct { char **paths; int32_t n; int setLines; char *one; } cli_paths;
+
+static char **read_list(const char *listName, int32_t *n_out)
+{
+    char **paths = NULL;
+    int32_t n = 0, cap = 0;
+    *n_out = -1;
+    igdc_lines *r = igdc_lines_open(listName);
+    if (!r) { printf("Cannot open query list %s\n", listName); return NULL; }
+    char *line;
+    int64_t len;
+    while ((line = igdc_lines_next(r, &len)) != NULL) {
+        size_t L = strlen(line);
+        while (L > 0 && (line[L - 1] == '\r' || line[L - 1] == '\n')) line[--L] = '\0';
+        if (L == 0) continue;
+        if (n == cap) { cap = cap ? 2 * cap : 64; paths = (char **)realloc(paths, sizeof(char *) * (size_t)cap); }
+        paths[n++] = strdup(line);
+    }
+    igdc_lines_close(r);
+    *n_out = n;
+    return paths;
+}
+
+static int paths_open(cli_paths *P, char *qfName, const char *listName)      /* 0: the list cannot be opened (said on stdout) */
+{
+    memset(P, 0, sizeof *P);
+    if (qfName) { P->one = qfName; P->paths = &P->one; P->n = 1; return 1; }
+    P->setLines = 1;
+    P->paths = read_list(listName, &P->n);
+    return P->n >= 0;
+}
+
+static void paths_close(cli_paths *P)
+{
+    if (!P->setLines) return;
+    for (int32_t k = 0; k < P->n; k++) free(P->paths[k]);
+    free(P->paths);
+}
+
+/* The query sets of a command: every file read by igdc_read_queries (an unreadable one is an empty set) and, once sets_cat() is
+ * asked for them, the sets' accepted lines concatenated with their offsets -- what the `_sets` entry points take. */
+typedef struct {
+    char **paths; int32_t n; int setLines;
+    igdc_queries *q; int64_t nq;                 /* per set, and the regions of all sets */
+    int32_t *ichr, *qs, *qe; int64_t *off;       /* sets_cat() */
+} cli_sets;
+
+static void sets_load(cli_sets *S, const cli_paths *P)
+{
+    char **paths = P->paths;
+    const int32_t n = P->n;
+    memset(S, 0, sizeof *S);
+    S->paths = paths; S->n = n; S->setLines = P->setLines;
+    igdc_queries *q = S->q = (igdc_queries *)calloc((size_t)n + 1, sizeof(igdc_queries));
+    for (int32_t k = 0; k < n; k++) {
+        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
+        S->nq += q[k].n;
+    }
+}
+
+static void sets_cat(cli_sets *S)
+{
+    if (S->off) return;
+    const igdc_queries *q = S->q;
+    const int32_t n = S->n;
+    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(S->nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(S->nq + 1));
+    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(S->nq + 1));
+    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    off[0] = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (q[k].n) {
+            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
+            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
+        }
+        off[k + 1] = off[k] + q[k].n;
+    }
+    S->ichr = ichr; S->qs = qs; S->qe = qe; S->off = off;
+}
+
+static void sets_free(cli_sets *S)
+{
+    for (int32_t k = 0; k < S->n; k++) igdc_queries_free(&S->q[k]);
+    free(S->q); free(S->ichr); free(S->qs); free(S->qe); free(S->off);
+}
+
+static void sets_title(const cli_sets *S, int32_t k)                         /* the line that opens the block of set k under -Q */
+{
+    if (S->setLines) printf("Query set %d: %s\n", (int)k, S->paths[k]);
+}
+
 static int64_t file_query(const char *qFile, int32_t v, int rule, int64_t *hits)
 {
     if (!g_core || !cur_igd()) { engine(); return 0; }
@@ -818,80 +960,54 @@ static void print_hits_table(const int64_t *hits)
     printf("Total: %lld\n", (long long)total);
 }
 
-static void search_sets(const char *listName, int32_t v, int64_t *hits)
+static void count_file(char *qFile, int32_t v, int64_t *hits)                /* the counts of `-q` for one file (:1023-1030) */
+{
+    if (IGD->gType == 0) getOverlaps0(qFile, hits);
+    else if (v > 0) getOverlaps_v(qFile, hits, v);
+    else getOverlaps(qFile, hits);
+}
+
+static void search_sets(const cli_paths *P, int32_t v, int64_t *hits)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles;
-    char **paths = NULL;
-    int32_t n = 0, cap = 0;
-    igdc_lines *r = igdc_lines_open(listName);
-    if (!r) { printf("Cannot open query list %s\n", listName); return; }
-    char *line;
-    int64_t len;
-    while ((line = igdc_lines_next(r, &len)) != NULL) {
-        size_t L = strlen(line);
-        while (L > 0 && (line[L - 1] == '\r' || line[L - 1] == '\n')) line[--L] = '\0';
-        if (L == 0) continue;
-        if (n == cap) { cap = cap ? 2 * cap : 64; paths = (char **)realloc(paths, sizeof(char *) * (size_t)cap); }
-        paths[n++] = strdup(line);
-    }
-    igdc_lines_close(r);
-    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` (:1023-1030) */
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
-    if (nq <= igdc_host_limit()) {
+    const int32_t nfiles = IGD->nFiles, n = P->n;
+    int rule;
+    const int32_t ev = q_dispatch(v, &rule);
+    cli_sets S;
+    sets_load(&S, P);
+    if (S.nq <= igdc_host_limit()) {
         /* every file through the `-q` route (it reads the file again: one code path for the text of a block) */
         for (int32_t k = 0; k < n && !g_fail_rc; k++) {
             memset(hits, 0, sizeof(int64_t) * (size_t)nfiles);
-            printf("Query set %d: %s\n", (int)k, paths[k]);
-            if (IGD->gType == 0) getOverlaps0(paths[k], hits);
-            else if (v > 0) getOverlaps_v(paths[k], hits, v);
-            else getOverlaps(paths[k], hits);
+            sets_title(&S, k);
+            count_file(S.paths[k], v, hits);
             if (!g_fail_rc) print_hits_table(hits);     /* (as `-q`: no table after an engine failure) */
         }
     } else {
-        int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq);
-        int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq);
-        int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
         int64_t *rows = (int64_t *)calloc((size_t)n * (size_t)nfiles + 1, sizeof(int64_t));
-        off[0] = 0;
-        for (int32_t k = 0; k < n; k++) {
-            if (q[k].n) {
-                memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-                memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-                memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-            }
-            off[k + 1] = off[k] + q[k].n;
-        }
+        sets_cat(&S);
         double t0 = now_s();
         igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one; -Q is one device) */
         if (dev) {
-            const int rc = igd_hip_search_sets_ov(dev, ichr, qs, qe, off, n, ev, rule, 0, rows, NULL, g_mo);
+            const int rc = igd_hip_search_sets_ov(dev, S.ichr, S.qs, S.qe, S.off, n, ev, rule, 0, rows, NULL, g_mo);
             if (rc != IGD_HIP_OK) engine_failed("search", rc);
             phase("search of the query sets (H2D + kernels + D2H)", &t0);
         }
         for (int32_t k = 0; k < n && !g_fail_rc; k++) {
-            printf("Query set %d: %s\n", (int)k, paths[k]);
+            sets_title(&S, k);
             print_hits_table(rows + (size_t)k * (size_t)nfiles);
         }
-        free(ichr); free(qs); free(qe); free(off); free(rows);
+        free(rows);
     }
-    for (int32_t k = 0; k < n; k++) { igdc_queries_free(&q[k]); free(paths[k]); }
-    free(q); free(paths);
+    sets_free(&S);
 }
 
 /* ------------------------------- `igd search -q F -u` / `-Q <list> -u` ----------------- */
 /* Support counts: per database file the number of QUERY REGIONS that overlap at least one of its records, where the table
  * of `-q` counts (query, record) pairs -- the count a region-set enrichment table is made of.  The table keeps the shape
  * of `-q`'s (third column: the support; last line: the query regions with any hit, of the accepted query lines).  Rule and
- * filter are `-q`'s dispatch for -v.  Routing as the counting commands: at most igdc_host_limit() queries in all are
- * counted on the host (igdc_support_host), more by ONE igd_hip_support_sets call on one device.  `paths` holds one query
- * file (`-q`, no "Query set" lines) or the files of a list (`-Q`). */
+ * filter are `-q`'s dispatch for -v.  Route (cli_route, which this and the commands below share): igdc_support_host on the
+ * host, ONE igd_hip_support_sets call on the engine. */
 static void print_support_table(const int64_t *sup, int64_t nhit, int64_t nq)
 {
     printf("index\t number of regions\t number of query regions\t File_name\n");
@@ -911,84 +1027,39 @@ static void print_coverage_table(const int64_t *cov, int64_t covered, int64_t qb
     printf("Query bp with a hit: %lld of %lld\n", (long long)covered, (long long)qbp);
 }
 
-static char **read_list(const char *listName, int32_t *n_out)
-{
-    char **paths = NULL;
-    int32_t n = 0, cap = 0;
-    *n_out = -1;
-    igdc_lines *r = igdc_lines_open(listName);
-    if (!r) { printf("Cannot open query list %s\n", listName); return NULL; }
-    char *line;
-    int64_t len;
-    while ((line = igdc_lines_next(r, &len)) != NULL) {
-        size_t L = strlen(line);
-        while (L > 0 && (line[L - 1] == '\r' || line[L - 1] == '\n')) line[--L] = '\0';
-        if (L == 0) continue;
-        if (n == cap) { cap = cap ? 2 * cap : 64; paths = (char **)realloc(paths, sizeof(char *) * (size_t)cap); }
-        paths[n++] = strdup(line);
-    }
-    igdc_lines_close(r);
-    *n_out = n;
-    return paths;
-}
-
-static void support_files(char **paths, int32_t n, int32_t v, int setLines, int bp)
+static void support_files(const cli_paths *P, int32_t v, int bp)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles;
-    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` (:1023-1030) */
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
+    const int32_t nfiles = IGD->nFiles, n = P->n;
+    int rule;
+    const int32_t ev = q_dispatch(v, &rule);
+    cli_sets S;
+    sets_load(&S, P);
+    const igdc_queries *q = S.q;
     int64_t *rows = (int64_t *)calloc((size_t)n * (size_t)nfiles + 1, sizeof(int64_t));
     int64_t *nhit = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t));
-    int onHost = 0;
-    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
-    if (hm) {
-        double t0 = now_s();
-        onHost = 1;
-        for (int32_t k = 0; k < n && onHost; k++)
+    cli_route R;
+    if (route_host(&R, S.nq)) {                       /* set by set: no concatenation on this route */
+        int ok = 1;
+        for (int32_t k = 0; k < n && ok; k++)
             if (q[k].n > 0)
-                onHost = (bp ? igdc_coverage_host(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
-                                                  rows + (size_t)k * (size_t)nfiles, &nhit[k])
-                             : igdc_support_host_ov(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
-                                                    rows + (size_t)k * (size_t)nfiles, &nhit[k], g_mo)) == 0;
-        igdc_map_close(hm);
-        if (onHost) phase(bp ? "covered base pairs on the host (small files)" : "support counts on the host (small files)", &t0);
-        else {                                        /* (a read error: the engine reads the file its own way) */
-            memset(rows, 0, sizeof(int64_t) * (size_t)n * (size_t)nfiles);
+                ok = (bp ? igdc_coverage_host(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
+                                              rows + (size_t)k * (size_t)nfiles, &nhit[k])
+                         : igdc_support_host_ov(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
+                                                rows + (size_t)k * (size_t)nfiles, &nhit[k], g_mo)) == 0;
+        if (!route_host_end(&R, ok, bp ? "covered base pairs on the host (small files)" : "support counts on the host (small files)")) {
+            memset(rows, 0, sizeof(int64_t) * (size_t)n * (size_t)nfiles);      /* (the sets before the read error were counted) */
             memset(nhit, 0, sizeof(int64_t) * (size_t)n);
         }
     }
-    if (!onHost && nq > 0) {
-        int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq);
-        int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)nq);
-        int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
-        off[0] = 0;
-        for (int32_t k = 0; k < n; k++) {
-            if (q[k].n) {
-                memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-                memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-                memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-            }
-            off[k + 1] = off[k] + q[k].n;
-        }
-        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
-        double t0 = now_s();
-        if (dev) {
-            const int rc = bp ? igd_hip_coverage_sets(dev, ichr, qs, qe, off, n, ev, rule, rows, nhit)
-                              : igd_hip_support_sets_ov(dev, ichr, qs, qe, off, n, ev, rule, rows, nhit, g_mo);
-            if (rc != IGD_HIP_OK) engine_failed(bp ? "coverage" : "support", rc);
-            phase(bp ? "covered base pairs of the query sets (H2D + kernel + D2H)" : "support counts of the query sets (H2D + kernel + D2H)", &t0);
-        }
-        free(ichr); free(qs); free(qe); free(off);
-    }
+    if (!R.onHost && S.nq > 0) sets_cat(&S);
+    if (route_engine(&R, S.nq > 0))
+        route_engine_end(&R, bp ? "coverage" : "support",
+                         bp ? igd_hip_coverage_sets(R.dev, S.ichr, S.qs, S.qe, S.off, n, ev, rule, rows, nhit)
+                            : igd_hip_support_sets_ov(R.dev, S.ichr, S.qs, S.qe, S.off, n, ev, rule, rows, nhit, g_mo),
+                         bp ? "covered base pairs of the query sets (H2D + kernel + D2H)" : "support counts of the query sets (H2D + kernel + D2H)");
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
-        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        sets_title(&S, k);
         if (bp) {
             int64_t qbp = 0;                          /* (64 bits: a line may span 2^32 - 1 bp) */
             for (int64_t i = 0; i < q[k].n; i++)
@@ -997,8 +1068,8 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
         } else
             print_support_table(rows + (size_t)k * (size_t)nfiles, nhit[k], q[k].n);
     }
-    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
-    free(q); free(rows); free(nhit);
+    sets_free(&S);
+    free(rows); free(nhit);
 }
 
 /* ------------------------------- `igd search -q F -J` / `-Q <list> -J` ----------------- */
@@ -1006,8 +1077,7 @@ static void support_files(char **paths, int32_t n, int32_t v, int setLines, int 
  * gives the bp of the intersection with the union of the file's records, the bp of the union of the two, the Jaccard, the
  * fraction of the set's bp inside the file (set_fraction) and the file's merged bp; every file has a line.  Last line: the
  * same against the records of any file.  A ratio over 0 is printed as NA.  Rule and filter are `-q`'s dispatch for -v.
- * Routing as `-b`: at most igdc_host_limit() regions in all go through igdc_jaccard_host, more through ONE
- * igd_hip_jaccard_sets call on one device. */
+ * Route: igdc_jaccard_host, or ONE igd_hip_jaccard_sets call. */
 static void print_ratio(int64_t num, int64_t den)
 {
     if (den != 0) printf("%.6f", (double)num / (double)den);
@@ -1032,56 +1102,32 @@ static void print_jaccard_table(const int64_t *inter, int64_t set_bp, const int6
     printf("\n");
 }
 
-static void jaccard_files(char **paths, int32_t n, int32_t v, int setLines)
+static void jaccard_files(const cli_paths *P, int32_t v)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const size_t nc = (size_t)IGD->nFiles + 1;
-    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` (:1023-1030) */
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
-    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq ? nq : 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq ? nq : 1));
-    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq ? nq : 1));
-    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
-    off[0] = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (q[k].n) {
-            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-        }
-        off[k + 1] = off[k] + q[k].n;
-    }
+    const int32_t n = P->n;
+    int rule;
+    const int32_t ev = q_dispatch(v, &rule);
+    cli_sets S;
+    sets_load(&S, P);
+    sets_cat(&S);
     int64_t *inter = (int64_t *)calloc((size_t)(n ? n : 1) * nc, sizeof(int64_t));
     int64_t *file_bp = (int64_t *)calloc(nc, sizeof(int64_t));
     int64_t *per = (int64_t *)calloc(3 * (size_t)(n ? n : 1), sizeof(int64_t)), *set_bp = per, *n_merged = per + n, *n_dropped = per + 2 * (size_t)n;
-    int onHost = 0;
-    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
-    if (hm) {
-        double t0 = now_s();
-        onHost = igdc_jaccard_host(g_core, hm, ichr, qs, qe, off, n, ev, rule, inter, set_bp, file_bp, n_merged, n_dropped) == 0;
-        igdc_map_close(hm);
-        if (onHost) phase("base-pair Jaccard on the host (small files)", &t0);
-    }
-    if (!onHost) {
-        igd_hip_db *dev = engine();                       /* (IGD_DEVICES with several devices: the first one, as -Q) */
-        double t0 = now_s();
-        if (dev) {
-            const int rc = igd_hip_jaccard_sets(dev, ichr, qs, qe, off, n, ev, rule, inter, set_bp, file_bp, n_merged, n_dropped);
-            if (rc != IGD_HIP_OK) engine_failed("jaccard", rc);
-            phase("base-pair Jaccard of the query sets (merge + coverage)", &t0);
-        }
-    }
+    cli_route R;
+    if (route_host(&R, S.nq))
+        route_host_end(&R, igdc_jaccard_host(g_core, R.hm, S.ichr, S.qs, S.qe, S.off, n, ev, rule, inter, set_bp, file_bp, n_merged, n_dropped) == 0,
+                       "base-pair Jaccard on the host (small files)");
+    if (route_engine(&R, 1))                              /* no gate on the regions: the table needs file_bp of every dataset, also for empty sets */
+        route_engine_end(&R, "jaccard", igd_hip_jaccard_sets(R.dev, S.ichr, S.qs, S.qe, S.off, n, ev, rule, inter, set_bp, file_bp, n_merged, n_dropped),
+                         "base-pair Jaccard of the query sets (merge + coverage)");
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {       /* (as `-q`: no table after an engine failure) */
-        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        sets_title(&S, k);
         print_jaccard_table(inter + (size_t)k * nc, set_bp[k], file_bp, n_merged[k], n_dropped[k]);
     }
-    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
-    free(q); free(ichr); free(qs); free(qe); free(off); free(inter); free(file_bp); free(per);
+    sets_free(&S);
+    free(inter); free(file_bp); free(per);
 }
 
 /* ------------------------------- `igd search -q F -U <universe>` / `-Q <list> -U <universe>` ----------------- */
@@ -1092,8 +1138,7 @@ static void jaccard_files(char **paths, int32_t n, int32_t v, int setLines)
  * a negative b or d is printed and tested as 0 and counted in "clamped cells" (a set region outside the universe, or a
  * universe region under several set regions; `-X` below restricts the sets to the universe first).  oddsRatio = (a d) / (b c), the
  * sample odds ratio; pValueLog = -log10 P(X >= a), X ~ Hypergeometric(a+b+c+d, a+b, a+c).  One row per file with a > 0.
- * Routing as `-u`, the universe's lines counted with the sets': at most igdc_host_limit() queries in all take
- * igdc_support_host and igdc_fisher_host, more ONE igd_hip_enrich_sets_nhit call on one device.
+ * Route, the universe's lines counted with the sets': igdc_support_host and igdc_fisher_host, or ONE igd_hip_enrich_sets_nhit call.
  * With `-R` six more columns follow the file name: rnkSup, rnkPV, rnkOR -- the file's rank among ALL files of the set, those
  * with a = 0 included, by support, pValueLog and oddsRatio (ties take the minimum rank) -- maxRnk, meanRnk and qValueLog,
  * -log10 of the Benjamini-Hochberg adjusted p over the set's nFiles tests (include/igd_hip.h: igd_hip_enrich_ranks).  They come
@@ -1104,8 +1149,8 @@ static void jaccard_files(char **paths, int32_t n, int32_t v, int setLines)
  * partition of the universe (b = u - a, c = size[k] - a, d = n_U - u - c, nothing to clamp), and the last line reads
  *     Restricted regions with a hit: <nhit> of <size> (from <n> query regions); universe regions: <n_U>
  * Lines of the set or the universe whose contig the database does not know are dropped by the reader, as everywhere: they
- * are in no restricted set and not in n_U.  Routing as without `-X`: the host route is igdc_enrich_restricted_host, the engine
- * route ONE igd_hip_enrich_restricted call on the first device.  `-X` without `-U` is refused. */
+ * are in no restricted set and not in n_U.  Route: igdc_enrich_restricted_host, or ONE igd_hip_enrich_restricted call.  `-X`
+ * without `-U` is refused. */
 /* b, c, d and the clamp count of every cell from the definitions (printed on both routes; the host route tests them) */
 static void enrich_tables(const int64_t *rows, const int64_t *urow, const igdc_queries *q, int64_t nU, int32_t n, int32_t nfiles,
                           int64_t *tb, int64_t *tc, int64_t *td, int64_t *clamped)
@@ -1118,24 +1163,6 @@ static void enrich_tables(const int64_t *rows, const int64_t *urow, const igdc_q
             if (b < 0 || d < 0) clamped[k]++;
             tb[i] = b < 0 ? 0 : b; tc[i] = c; td[i] = d < 0 ? 0 : d;
         }
-    }
-}
-
-/* the sets' accepted lines, concatenated, and their offsets (free the four) */
-static void enrich_cat(const igdc_queries *q, int32_t n, int64_t nq, int32_t **ichr, int32_t **qs, int32_t **qe, int64_t **off)
-{
-    *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
-    (*off)[0] = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (q[k].n) {
-            memcpy(*ichr + (*off)[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(*qs + (*off)[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(*qe + (*off)[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-        }
-        (*off)[k + 1] = (*off)[k] + q[k].n;
     }
 }
 
@@ -1152,12 +1179,12 @@ static void enrich_tables_restricted(const int64_t *rows, const int64_t *urow, c
         }
 }
 
-static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v, int setLines, int ranks, int restricted)
+static void enrich_files(const cli_paths *P, const char *uniName, int32_t v, int ranks, int restricted)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles;
-    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` (:1023-1030) */
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    const int32_t nfiles = IGD->nFiles, n = P->n;
+    int rule;
+    const int32_t ev = q_dispatch(v, &rule);
     igdc_queries uq;
     memset(&uq, 0, sizeof uq);
     if (igdc_read_queries(g_core, uniName, 1, &uq) != 0 || uq.n == 0) {
@@ -1165,12 +1192,9 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
         igdc_queries_free(&uq);
         return;
     }
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
+    cli_sets S;
+    sets_load(&S, P);
+    const igdc_queries *q = S.q;
     const size_t cells = (size_t)n * (size_t)nfiles;
     int64_t *rows = (int64_t *)calloc(cells + 1, sizeof(int64_t)), *urow = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
     int64_t *nhit = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t)), unhit = 0;
@@ -1181,74 +1205,51 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
     double *qlog = ranks ? (double *)calloc(4 * cells + 1, sizeof(double)) : NULL, *rmean = ranks ? qlog + cells : NULL;
     int32_t *rsup = ranks ? (int32_t *)(rmean + cells) : NULL, *rpv = ranks ? rsup + cells : NULL, *ror = ranks ? rpv + cells : NULL;
     int32_t *rmax = ranks ? ror + cells : NULL;
-    int onHost = 0;
-    igdc_map *hm = host_map_lim(nq + uq.n, igdc_host_limit());
-    if (hm && restricted) {
-        int32_t *ichr, *qs, *qe;
-        int64_t *off;
-        double t0 = now_s();
-        enrich_cat(q, n, nq, &ichr, &qs, &qe, &off);
-        onHost = igdc_enrich_restricted_host(g_core, hm, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, size, plog,
-                                             odds, NULL, nhit, &unhit) == 0;
-        igdc_map_close(hm);
-        free(ichr); free(qs); free(qe); free(off);
-        if (onHost) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
-        if (onHost && ranks) onHost = igdc_rank_host(rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean) == 0;
-        if (onHost) phase("restricted sets, membership of the universe and Fisher tests on the host (small files)", &t0);
-        else {                                        /* (a read error: the engine reads the file its own way) */
-            memset(rows, 0, sizeof(int64_t) * cells);
-            memset(urow, 0, sizeof(int64_t) * (size_t)nfiles);
-            memset(nhit, 0, sizeof(int64_t) * (size_t)n);
-            unhit = 0;
-        }
-    } else if (hm) {
-        double t0 = now_s();
-        onHost = igdc_support_host_ov(g_core, hm, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, urow, &unhit, g_mo) == 0;
-        for (int32_t k = 0; k < n && onHost; k++)
-            if (q[k].n > 0)
-                onHost = igdc_support_host_ov(g_core, hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
+    cli_route R;
+    if (route_host(&R, S.nq + uq.n)) {
+        int ok;
+        if (restricted) {
+            sets_cat(&S);
+            ok = igdc_enrich_restricted_host(g_core, R.hm, S.ichr, S.qs, S.qe, S.off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, size,
+                                             plog, odds, NULL, nhit, &unhit) == 0;
+            if (ok) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
+        } else {
+            ok = igdc_support_host_ov(g_core, R.hm, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, urow, &unhit, g_mo) == 0;
+            for (int32_t k = 0; k < n && ok; k++)
+                if (q[k].n > 0)
+                    ok = igdc_support_host_ov(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
                                               &nhit[k], g_mo) == 0;
-        igdc_map_close(hm);
-        if (onHost) {
-            enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
-            onHost = igdc_fisher_host(rows, tb, tc, td, (int64_t)cells, plog, odds) == 0;
-        }
-        if (onHost && ranks) onHost = igdc_rank_host(rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean) == 0;
-        if (onHost) phase("support counts and Fisher tests on the host (small files)", &t0);
-        else {                                        /* (a read error: the engine reads the file its own way) */
-            memset(rows, 0, sizeof(int64_t) * cells);
-            memset(urow, 0, sizeof(int64_t) * (size_t)nfiles);
-            memset(nhit, 0, sizeof(int64_t) * (size_t)n);
-            unhit = 0;
-        }
-    }
-    if (!onHost) {
-        int32_t *ichr, *qs, *qe;
-        int64_t *off;
-        enrich_cat(q, n, nq, &ichr, &qs, &qe, &off);
-        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
-        double t0 = now_s();
-        if (dev) {
-            const int rc = restricted
-                               ? igd_hip_enrich_restricted(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, size,
-                                                           plog, odds, NULL, nhit, &unhit)
-                               : igd_hip_enrich_sets_ov(dev, ichr, qs, qe, off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, plog,
-                                                        odds, NULL, nhit, &unhit, g_mo);
-            if (rc != IGD_HIP_OK) engine_failed("enrichment", rc);
-            else if (restricted) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
-            else enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
-            phase(restricted ? "enrichment of the restricted sets (join + membership of the universe + gather + Fisher kernel)"
-                             : "enrichment of the query sets (H2D + support kernel + Fisher kernel + D2H)", &t0);
-            if (ranks && rc == IGD_HIP_OK) {
-                const int rr = igd_hip_enrich_ranks(dev, rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean);
-                if (rr != IGD_HIP_OK) engine_failed("enrichment ranks", rr);
-                phase("ranks and q-values of the enrichment table (H2D + rank kernel + D2H)", &t0);
+            if (ok) {
+                enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
+                ok = igdc_fisher_host(rows, tb, tc, td, (int64_t)cells, plog, odds) == 0;
             }
         }
-        free(ichr); free(qs); free(qe); free(off);
+        if (ok && ranks) ok = igdc_rank_host(rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean) == 0;
+        if (!route_host_end(&R, ok, restricted ? "restricted sets, membership of the universe and Fisher tests on the host (small files)"
+                                               : "support counts and Fisher tests on the host (small files)")) {
+            memset(rows, 0, sizeof(int64_t) * cells);                           /* (what was counted before the read error) */
+            memset(urow, 0, sizeof(int64_t) * (size_t)nfiles);
+            memset(nhit, 0, sizeof(int64_t) * (size_t)n);
+            unhit = 0;
+        }
+    }
+    if (!R.onHost) sets_cat(&S);
+    if (route_engine(&R, 1)) {                        /* (no gate: the universe holds a region) */
+        const int rc = restricted
+                           ? igd_hip_enrich_restricted(R.dev, S.ichr, S.qs, S.qe, S.off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, size,
+                                                       plog, odds, NULL, nhit, &unhit)
+                           : igd_hip_enrich_sets_ov(R.dev, S.ichr, S.qs, S.qe, S.off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, plog,
+                                                    odds, NULL, nhit, &unhit, g_mo);
+        if (rc == IGD_HIP_OK && restricted) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
+        else if (rc == IGD_HIP_OK) enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
+        route_engine_end(&R, "enrichment", rc, restricted ? "enrichment of the restricted sets (join + membership of the universe + gather + Fisher kernel)"
+                                                          : "enrichment of the query sets (H2D + support kernel + Fisher kernel + D2H)");
+        if (ranks && rc == IGD_HIP_OK)
+            route_engine_end(&R, "enrichment ranks", igd_hip_enrich_ranks(R.dev, rows, plog, odds, n, nfiles, qlog, rsup, rpv, ror, rmax, rmean),
+                             "ranks and q-values of the enrichment table (H2D + rank kernel + D2H)");
     }
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
-        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        sets_title(&S, k);
         printf("index\t number of regions\t support\t b\t c\t d\t oddsRatio\t pValueLog\t File_name%s\n",
                ranks ? "\t rnkSup\t rnkPV\t rnkOR\t maxRnk\t meanRnk\t qValueLog" : "");
         for (int32_t f = 0; f < nfiles; f++) {
@@ -1266,9 +1267,9 @@ static void enrich_files(char **paths, int32_t n, const char *uniName, int32_t v
             printf("Query regions with a hit: %lld of %lld; universe regions: %lld; clamped cells: %lld\n", (long long)nhit[k],
                    (long long)q[k].n, (long long)uq.n, (long long)clamped[k]);
     }
-    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
+    sets_free(&S);
     igdc_queries_free(&uq);
-    free(q); free(rows); free(urow); free(nhit); free(tb); free(clamped); free(size); free(plog); free(qlog);
+    free(rows); free(urow); free(nhit); free(tb); free(clamped); free(size); free(plog); free(qlog);
 }
 
 /* ------------------------------- `igd search -q F -w` / `-Q <list> -w` ----------------- */
@@ -1335,25 +1336,22 @@ static int member_lines(textbuf *t, const igdc_queries *q, int64_t a, int64_t b,
     return 1;
 }
 
-static void membership_files(char **paths, int32_t n, int32_t v, int setLines)
+static void membership_files(const cli_paths *P, int32_t v)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles, nW = (nfiles + 31) / 32;
-    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` */
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
+    const int32_t nfiles = IGD->nFiles, nW = (nfiles + 31) / 32, n = P->n;
+    int rule;
+    const int32_t ev = q_dispatch(v, &rule);
+    cli_sets S;
+    sets_load(&S, P);
+    const igdc_queries *q = S.q;
     int64_t step = MEMBER_CHUNK_BYTES / ((int64_t)(nW ? nW : 1) * 4);
     step = step < 1 ? 1 : step > MEMBER_CHUNK_QUERIES ? MEMBER_CHUNK_QUERIES : step;
-    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
+    /* (not a cli_route: the rows are asked for chunk by chunk, and a read error moves the remaining chunks to the engine) */
+    igdc_map *hm = host_map_lim(S.nq, igdc_host_limit());
     igd_hip_db *dev = NULL;
-    if (!hm && nq > 0 && !(dev = engine())) {         /* no device: nothing of the table is printed */
-        for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
-        free(q);
+    if (!hm && S.nq > 0 && !(dev = engine())) {       /* no device: nothing of the table is printed */
+        sets_free(&S);
         return;
     }
     uint32_t *bits = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)step * (size_t)(nW ? nW : 1));
@@ -1361,9 +1359,8 @@ static void membership_files(char **paths, int32_t n, int32_t v, int setLines)
     textbuf t = {NULL, 0, 0};
     double t0 = now_s();
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {
-        if (setLines) {
-            if (text_room(&t, strlen(paths[k]) + 64)) t.n += (size_t)sprintf(t.s + t.n, "Query set %d: %s\n", (int)k, paths[k]);
-        }
+        if (S.setLines && text_room(&t, strlen(S.paths[k]) + 64))        /* (sets_title(), into the text buffer) */
+            t.n += (size_t)sprintf(t.s + t.n, "Query set %d: %s\n", (int)k, S.paths[k]);
         int64_t nhit = 0;
         for (int64_t a = 0; a < q[k].n && !g_fail_rc; a += step) {
             const int64_t b = a + step < q[k].n ? a + step : q[k].n;
@@ -1386,8 +1383,8 @@ static void membership_files(char **paths, int32_t n, int32_t v, int setLines)
     text_flush(&t);
     phase(hm ? "membership rows on the host (small files)" : "membership rows of the query files (H2D + kernel + D2H + text)", &t0);
     if (hm) igdc_map_close(hm);
-    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
-    free(q); free(bits); free(nfh); free(t.s);
+    sets_free(&S);
+    free(bits); free(nfh); free(t.s);
 }
 
 /* ------------------------------- `igd search -q F -C` ----------------------------------- */
@@ -1395,8 +1392,8 @@ static void membership_files(char **paths, int32_t n, int32_t v, int setLines)
  *     index_a \t index_b \t support_a \t support_b \t both \t jaccard \t File_a \t File_b
  * and one line per pair of datasets a < b that at least one region overlaps both of, in ascending (a, b): the regions that
  * overlap a, that overlap b, that overlap both, and the Jaccard index both / (support_a + support_b - both) as %.6f; then
- * `-u`'s last line.  Rule and filter are `-q`'s dispatch for -v.  Routing as `-w`: at most igdc_host_limit() queries go through
- * igdc_cooccur_host, more through igd_hip_cooccur on one device.  The text leaves in pieces of about MEMBER_TEXT_BYTES. */
+ * `-u`'s last line.  Rule and filter are `-q`'s dispatch for -v.  Route: igdc_cooccur_host, or igd_hip_cooccur.  The text leaves
+ * in pieces of about MEMBER_TEXT_BYTES. */
 static void cooccur_file(char *path, int32_t v)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
@@ -1405,30 +1402,19 @@ static void cooccur_file(char *path, int32_t v)
         printf("Not supported: -C with more than %d datasets\n", (int)IGD_COOCCUR_MAX_FILES);
         return;
     }
-    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` */
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    int rule;
+    const int32_t ev = q_dispatch(v, &rule);
     igdc_queries q;
     if (igdc_read_queries(g_core, path, 1, &q) != 0) memset(&q, 0, sizeof q);                  /* unreadable: an empty set */
     int64_t *cooc = (int64_t *)calloc((size_t)nfiles * (size_t)nfiles + 1, sizeof(int64_t));
     int64_t nhit = 0;
     if (!cooc) { fprintf(stderr, "igd: out of memory\n"); igdc_queries_free(&q); return; }
-    double t0 = now_s();
-    int done = 0;
-    igdc_map *hm = host_map_lim(q.n, igdc_host_limit());
-    if (hm) {
-        done = igdc_cooccur_host(g_core, hm, q.ichr, q.qs, q.qe, q.n, ev, rule, cooc, &nhit) == 0;
-        igdc_map_close(hm);
-        if (done) phase("co-occurrence on the host (small files)", &t0);
-    }
-    if (!done && q.n > 0) {                           /* (after a read error too: the engine reads the file its own way) */
-        igd_hip_db *dev = engine();
-        t0 = now_s();
-        if (dev) {
-            const int rc = igd_hip_cooccur(dev, q.ichr, q.qs, q.qe, q.n, ev, rule, cooc, &nhit);
-            if (rc != IGD_HIP_OK) engine_failed("co-occurrence", rc);
-            phase("co-occurrence of the query file (H2D + membership + transpose + Gram kernels + D2H)", &t0);
-        }
-    }
+    cli_route R;
+    if (route_host(&R, q.n))
+        route_host_end(&R, igdc_cooccur_host(g_core, R.hm, q.ichr, q.qs, q.qe, q.n, ev, rule, cooc, &nhit) == 0, "co-occurrence on the host (small files)");
+    if (route_engine(&R, q.n > 0))
+        route_engine_end(&R, "co-occurrence", igd_hip_cooccur(R.dev, q.ichr, q.qs, q.qe, q.n, ev, rule, cooc, &nhit),
+                         "co-occurrence of the query file (H2D + membership + transpose + Gram kernels + D2H)");
     if (!g_fail_rc) {
         textbuf t = {NULL, 0, 0};
         int ok = text_room(&t, 128);
@@ -1467,9 +1453,9 @@ static void cooccur_file(char *path, int32_t v)
  * and one line per dataset: the support of the file as given, mean and standard deviation of the permuted supports, the
  * z-score, the permutations with a support >= / <= the observed one and -log10 of (n + 1) / (N + 1) for both (floats as
  * %.6f); then `-u`'s last line followed by the same seven statistics of the regions with a hit in any dataset.  Rule and
- * filter are `-q`'s dispatch for -v.  Routing as `-u`, decided on regions x (N + 1): at most igdc_host_limit() go through
- * igdc_permute_host, more through igd_hip_permute_support on one device.  A region outside its contig's length, or on a contig
- * the genome file lacks, ends the run with a message that names the line. */
+ * filter are `-q`'s dispatch for -v.  Route, decided on regions x (N + 1) and with no gate on them: igdc_permute_host, or
+ * igd_hip_permute_support.  A region outside its contig's length, or on a contig the genome file lacks, ends the run with a
+ * message that names the line. */
 /* `-D W` switches the statistic from support to distance (permute_nearest_table below); window < 0: the support. */
 static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int32_t window);
 /* `-G` switches it to base pairs (permute_bp_table below); it takes no sum of squares on the device, so the guard on it does not apply. */
@@ -1478,8 +1464,8 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
-    const int rule = (IGD->gType != 0 && v > 0) ? IGD_HIP_RULE_FLAT : IGD_HIP_RULE_NEST;     /* the dispatch of `-q` */
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
+    int rule;
+    const int32_t ev = q_dispatch(v, &rule);
     int32_t *len = (int32_t *)calloc((size_t)g_core->nCtg + 1, sizeof(int32_t));
     int64_t bad = 0;
     const int grc = len ? igdc_read_genome(g_core, genome, len, &bad) : -1;
@@ -1525,23 +1511,14 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
         double *fl = (double *)calloc(5 * (size_t)nC, sizeof(double));
         if (!st7 || !fl) { fprintf(stderr, "igd: out of memory\n"); free(st7); free(fl); goto done; }
         int64_t *obs = st7, *sum = obs + nC, *ssq = sum + nC, *nge = ssq + nC, *nle = nge + nC, *mn = nle + nC, *mx = mn + nC;
-        double t0 = now_s();
-        int ok = 0;
-        igdc_map *hm = host_map_lim(q.n * (nperm + 1), igdc_host_limit());
-        if (hm) {
-            ok = igdc_permute_host_ov(g_core, hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo) == 0;
-            igdc_map_close(hm);
-            if (ok) phase("permutation null on the host (small files)", &t0);
-        }
-        if (!ok) {                                    /* (after a read error too: the engine reads the file its own way) */
-            igd_hip_db *dev = engine();
-            t0 = now_s();
-            if (dev) {
-                const int rc = igd_hip_permute_support_ov(dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo);
-                if (rc != IGD_HIP_OK) engine_failed("permutation null", rc);
-                phase("permutation null of the query file (H2D + permute, support and statistics kernels + D2H)", &t0);
-            }
-        }
+        cli_route R;
+        if (route_host(&R, q.n * (nperm + 1)))
+            route_host_end(&R, igdc_permute_host_ov(g_core, R.hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo) == 0,
+                           "permutation null on the host (small files)");
+        if (route_engine(&R, 1))
+            route_engine_end(&R, "permutation null",
+                             igd_hip_permute_support_ov(R.dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo),
+                             "permutation null of the query file (H2D + permute, support and statistics kernels + D2H)");
         if (!g_fail_rc && igdc_perm_summary(obs, sum, ssq, nge, nle, nperm, nC, fl, fl + nC, fl + 2 * nC, fl + 3 * nC, fl + 4 * nC) == 0) {
             printf("index\tobserved\tmean\tsd\tz\tn_ge\tn_le\tnlog10_p_upper\tnlog10_p_lower\tFile\n");
             for (int32_t i = 0; i < nfiles; i++)
@@ -1563,63 +1540,37 @@ done:
 /* Nearest record per dataset within a window (include/igd_hip.h has the definitions): per database file the query regions
  * with a record of the file within W bp (n_within), those that overlap one (n_overlap) and the mean distance of the former
  * (mean_dist, `NA` where there is none); one line per dataset, then the same for "any dataset".  -v keeps the records with
- * value >= v, as everywhere; there is no tile rule.  Routing as `-u`: at most igdc_host_limit() regions in all are answered on
- * the host (igdc_nearest_sets_host), more by ONE igd_hip_nearest_sets call on one device.  `paths` holds one query file (`-q`,
- * no "Query set" lines) or the files of a list (`-Q`). */
+ * value >= v, as everywhere; there is no tile rule.  Route: igdc_nearest_sets_host, or ONE igd_hip_nearest_sets call. */
 static void print_mean(const char *before, int64_t n_within, double mean, const char *after)
 {
     if (n_within > 0) printf("%s%.2f%s", before, mean, after);
     else printf("%sNA%s", before, after);
 }
 
-static void nearest_files(char **paths, int32_t n, int32_t v, int setLines, int32_t window)
+static void nearest_files(const cli_paths *P, int32_t v, int32_t window)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles;
+    const int32_t nfiles = IGD->nFiles, n = P->n;
     const size_t nC = (size_t)nfiles + 1;
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
-    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    const int32_t ev = q_dispatch(v, NULL);
+    cli_sets S;
+    sets_load(&S, P);
+    sets_cat(&S);
+    const igdc_queries *q = S.q;
     int64_t *st3 = (int64_t *)calloc(3 * (size_t)(n ? n : 1) * nC, sizeof(int64_t));
     double *mean = (double *)malloc(sizeof(double) * (size_t)(n ? n : 1) * nC);
     int64_t *nw = st3, *no = st3 + (size_t)n * nC, *sd = st3 + 2 * (size_t)n * nC;
-    off[0] = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (q[k].n) {
-            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-        }
-        off[k + 1] = off[k] + q[k].n;
-    }
-    int onHost = 0;
-    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
-    if (hm) {
-        double t0 = now_s();
-        onHost = igdc_nearest_sets_host(g_core, hm, ichr, qs, qe, off, n, window, ev, nw, no, sd) == 0;
-        igdc_map_close(hm);
-        if (onHost) phase("nearest records on the host (small files)", &t0);
-    }
-    if (!onHost && nq > 0) {                          /* (after a read error too: the engine reads the file its own way) */
-        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
-        double t0 = now_s();
-        if (dev) {
-            const int rc = igd_hip_nearest_sets(dev, ichr, qs, qe, off, n, window, ev, nw, no, sd);
-            if (rc != IGD_HIP_OK) engine_failed("nearest", rc);
-            phase("nearest records of the query sets (H2D + kernels + D2H)", &t0);
-        }
-    }
+    cli_route R;
+    if (route_host(&R, S.nq))
+        route_host_end(&R, igdc_nearest_sets_host(g_core, R.hm, S.ichr, S.qs, S.qe, S.off, n, window, ev, nw, no, sd) == 0,
+                       "nearest records on the host (small files)");
+    if (route_engine(&R, S.nq > 0))
+        route_engine_end(&R, "nearest", igd_hip_nearest_sets(R.dev, S.ichr, S.qs, S.qe, S.off, n, window, ev, nw, no, sd),
+                         "nearest records of the query sets (H2D + kernels + D2H)");
     if (!g_fail_rc) igdc_nearest_summary(nw, sd, (int64_t)n * (int64_t)nC, mean);
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
         const size_t o = (size_t)k * nC;
-        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        sets_title(&S, k);
         printf("index\tn_within\tn_overlap\tmean_dist\tFile\n");
         for (int32_t i = 0; i < nfiles; i++) {
             printf("%d\t%lld\t%lld", (int)i, (long long)nw[o + i], (long long)no[o + i]);
@@ -1630,8 +1581,8 @@ static void nearest_files(char **paths, int32_t n, int32_t v, int setLines, int3
                (long long)no[o + nfiles]);
         print_mean("; mean distance ", nw[o + nfiles], mean[o + nfiles], "\n");
     }
-    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
-    free(q); free(ichr); free(qs); free(qe); free(off); free(st3); free(mean);
+    sets_free(&S);
+    free(st3); free(mean);
 }
 
 /* ------------------------------- `igd search -q F -N <bp> -H e1,e2,..` / `-Q <list> -N <bp> -H ..` ------- */
@@ -1655,66 +1606,48 @@ static int parse_edges(const char *arg, int32_t *edges)                     /* t
     }
 }
 
-static void nearest_hist_files(char **paths, int32_t n, int32_t v, int setLines, int32_t window, const int32_t *edges, int ne)
+/* the lines under the header of -H's and -L's table: per dataset, and then for "any dataset", the sum of the bins and the bins */
+static void print_hist_rows(const int64_t *h, size_t nB, int32_t window, int64_t nq)
+{
+    const int32_t nfiles = IGD->nFiles;
+    const size_t nC = (size_t)nfiles + 1;
+    for (int32_t i = 0; i <= nfiles; i++) {           /* (i = nfiles: the any-dataset column) */
+        int64_t nw = 0;
+        for (size_t b = 0; b < nB; b++) nw += h[b * nC + (size_t)i];
+        if (i < nfiles) printf("%d\t%lld", (int)i, (long long)nw);
+        else printf("Any dataset within %d bp: %lld of %lld", (int)window, (long long)nw, (long long)nq);
+        for (size_t b = 0; b < nB; b++) printf("\t%lld", (long long)h[b * nC + (size_t)i]);
+        if (i < nfiles) printf("\t%s\n", IGD->finfo[i].fileName);
+        else printf("\n");
+    }
+}
+
+static void nearest_hist_files(const cli_paths *P, int32_t v, int32_t window, const int32_t *edges, int ne)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles;
-    const size_t nC = (size_t)nfiles + 1, nB = (size_t)ne + 1;
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
-    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    const int32_t n = P->n;
+    const size_t nC = (size_t)IGD->nFiles + 1, nB = (size_t)ne + 1;
+    const int32_t ev = q_dispatch(v, NULL);
+    cli_sets S;
+    sets_load(&S, P);
+    sets_cat(&S);
     int64_t *hist = (int64_t *)calloc((size_t)(n ? n : 1) * nB * nC, sizeof(int64_t));
-    off[0] = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (q[k].n) {
-            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-        }
-        off[k + 1] = off[k] + q[k].n;
-    }
-    int onHost = 0;
-    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
-    if (hm) {
-        double t0 = now_s();
-        onHost = igdc_nearest_hist_host(g_core, hm, ichr, qs, qe, off, n, window, ev, edges, ne, hist) == 0;
-        igdc_map_close(hm);
-        if (onHost) phase("histogram of the nearest distances on the host (small files)", &t0);
-    }
-    if (!onHost && nq > 0) {                          /* (after a read error too: the engine reads the file its own way) */
-        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
-        double t0 = now_s();
-        if (dev) {
-            const int rc = igd_hip_nearest_hist(dev, ichr, qs, qe, off, n, window, ev, edges, ne, hist);
-            if (rc != IGD_HIP_OK) engine_failed("nearest histogram", rc);
-            phase("histogram of the nearest distances of the query sets (H2D + kernels + D2H)", &t0);
-        }
-    }
+    cli_route R;
+    if (route_host(&R, S.nq))
+        route_host_end(&R, igdc_nearest_hist_host(g_core, R.hm, S.ichr, S.qs, S.qe, S.off, n, window, ev, edges, ne, hist) == 0,
+                       "histogram of the nearest distances on the host (small files)");
+    if (route_engine(&R, S.nq > 0))
+        route_engine_end(&R, "nearest histogram", igd_hip_nearest_hist(R.dev, S.ichr, S.qs, S.qe, S.off, n, window, ev, edges, ne, hist),
+                         "histogram of the nearest distances of the query sets (H2D + kernels + D2H)");
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
-        const int64_t *h = hist + (size_t)k * nB * nC;
-        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        sets_title(&S, k);
         printf("index\tn_within\t<%d", (int)edges[0]);
         for (int b = 1; b < ne; b++) printf("\t[%d,%d)", (int)edges[b - 1], (int)edges[b]);
         printf("\t>=%d\tFile\n", (int)edges[ne - 1]);
-        for (int32_t i = 0; i <= nfiles; i++) {       /* (i = nfiles: the any-dataset column) */
-            int64_t nw = 0;
-            for (size_t b = 0; b < nB; b++) nw += h[b * nC + (size_t)i];
-            if (i < nfiles) printf("%d\t%lld", (int)i, (long long)nw);
-            else printf("Any dataset within %d bp: %lld of %lld", (int)window, (long long)nw, (long long)q[k].n);
-            for (size_t b = 0; b < nB; b++) printf("\t%lld", (long long)h[b * nC + (size_t)i]);
-            if (i < nfiles) printf("\t%s\n", IGD->finfo[i].fileName);
-            else printf("\n");
-        }
+        print_hist_rows(hist + (size_t)k * nB * nC, nB, window, S.q[k].n);
     }
-    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
-    free(q); free(ichr); free(qs); free(qe); free(off); free(hist);
+    sets_free(&S);
+    free(hist);
 }
 
 /* ------------------------------- `igd search -q F -N <bp> -L <bins> [-E]` / `-Q <list> -N <bp> -L ..` ------- */
@@ -1723,66 +1656,32 @@ static void nearest_hist_files(char **paths, int32_t n, int32_t v, int setLines,
  * (up + down), under the bins' lower bounds k / (2 B); one line per dataset, then the same for "any dataset".  The distances
  * are measured between midpoints, with -E between edges.  -v, routing and the layout of -Q blocks as -N: the host answers with
  * igdc_flank_reldist_host, the engine with ONE igd_hip_flank_reldist call. */
-static void flank_reldist_files(char **paths, int32_t n, int32_t v, int setLines, int32_t window, int measure, int32_t nbins)
+static void flank_reldist_files(const cli_paths *P, int32_t v, int32_t window, int measure, int32_t nbins)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles;
-    const size_t nC = (size_t)nfiles + 1, nB = (size_t)nbins;
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
-    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    const int32_t n = P->n;
+    const size_t nC = (size_t)IGD->nFiles + 1, nB = (size_t)nbins;
+    const int32_t ev = q_dispatch(v, NULL);
+    cli_sets S;
+    sets_load(&S, P);
+    sets_cat(&S);
     int64_t *hist = (int64_t *)calloc((size_t)(n ? n : 1) * nB * nC, sizeof(int64_t));
-    off[0] = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (q[k].n) {
-            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-        }
-        off[k + 1] = off[k] + q[k].n;
-    }
-    int onHost = 0;
-    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
-    if (hm) {
-        double t0 = now_s();
-        onHost = igdc_flank_reldist_host(g_core, hm, ichr, qs, qe, off, n, window, measure, ev, nbins, hist) == 0;
-        igdc_map_close(hm);
-        if (onHost) phase("histogram of the relative distances on the host (small files)", &t0);
-    }
-    if (!onHost && nq > 0) {                          /* (after a read error too: the engine reads the file its own way) */
-        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
-        double t0 = now_s();
-        if (dev) {
-            const int rc = igd_hip_flank_reldist(dev, ichr, qs, qe, off, n, window, measure, ev, nbins, hist);
-            if (rc != IGD_HIP_OK) engine_failed("relative-distance histogram", rc);
-            phase("histogram of the relative distances of the query sets (H2D + kernels + D2H)", &t0);
-        }
-    }
+    cli_route R;
+    if (route_host(&R, S.nq))
+        route_host_end(&R, igdc_flank_reldist_host(g_core, R.hm, S.ichr, S.qs, S.qe, S.off, n, window, measure, ev, nbins, hist) == 0,
+                       "histogram of the relative distances on the host (small files)");
+    if (route_engine(&R, S.nq > 0))
+        route_engine_end(&R, "relative-distance histogram", igd_hip_flank_reldist(R.dev, S.ichr, S.qs, S.qe, S.off, n, window, measure, ev, nbins, hist),
+                         "histogram of the relative distances of the query sets (H2D + kernels + D2H)");
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
-        const int64_t *h = hist + (size_t)k * nB * nC;
-        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        sets_title(&S, k);
         printf("index\tn_flanked");
         for (int b = 0; b < nbins; b++) printf("\t%.4f", (double)b / (double)(2 * nbins));
         printf("\tFile\n");
-        for (int32_t i = 0; i <= nfiles; i++) {       /* (i = nfiles: the any-dataset column) */
-            int64_t nfl = 0;
-            for (size_t b = 0; b < nB; b++) nfl += h[b * nC + (size_t)i];
-            if (i < nfiles) printf("%d\t%lld", (int)i, (long long)nfl);
-            else printf("Any dataset within %d bp: %lld of %lld", (int)window, (long long)nfl, (long long)q[k].n);
-            for (size_t b = 0; b < nB; b++) printf("\t%lld", (long long)h[b * nC + (size_t)i]);
-            if (i < nfiles) printf("\t%s\n", IGD->finfo[i].fileName);
-            else printf("\n");
-        }
+        print_hist_rows(hist + (size_t)k * nB * nC, nB, window, S.q[k].n);
     }
-    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
-    free(q); free(ichr); free(qs); free(qe); free(off); free(hist);
+    sets_free(&S);
+    free(hist);
 }
 
 /* ------------------------------- `igd search -q F -V <op>` / `-Q <list> -V <op>` ------- */
@@ -1790,63 +1689,36 @@ static void flank_reldist_files(char **paths, int32_t n, int32_t v, int setLines
  * with a counted record (n_hit), the counted (region, record) pairs (pairs) and a mean -- of the per-region count, sum, minimum
  * or maximum over the regions with a hit (mean_region) or, for `mean`, of the values over the pairs (op SUM, mean_pair); `NA`
  * where the divisor is 0.  One line per dataset, then the pairs of all datasets and the datasets with a hit.  -v keeps the
- * records with value >= v, as everywhere; there is no tile rule.  Routing as `-u` and `-N`: at most igdc_host_limit() regions
- * in all are answered on the host (igdc_map_sets_host), more by ONE igd_hip_map_sets call on one device.  `paths` holds one
- * query file (`-q`, no "Query set" lines) or the files of a list (`-Q`). */
+ * records with value >= v, as everywhere; there is no tile rule.  Route: igdc_map_sets_host, or ONE igd_hip_map_sets call. */
 static const char *const MAP_OPS[] = {"count", "sum", "min", "max", "mean"};
 static const int MAP_OP_OF[] = {IGD_HIP_MAP_COUNT, IGD_HIP_MAP_SUM, IGD_HIP_MAP_MIN, IGD_HIP_MAP_MAX, IGD_HIP_MAP_SUM};
 
-static void map_files(char **paths, int32_t n, int32_t v, int setLines, int opName)
+static void map_files(const cli_paths *P, int32_t v, int opName)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int op = MAP_OP_OF[opName], perPair = opName == 4;
-    const int32_t nfiles = IGD->nFiles;
+    const int32_t nfiles = IGD->nFiles, n = P->n;
     const size_t nC = (size_t)nfiles;
-    const int32_t ev = (IGD->gType != 0 && v > 0) ? v : IGD_HIP_NO_VALUE_FILTER;
-    igdc_queries *q = (igdc_queries *)calloc((size_t)(n ? n : 1), sizeof(igdc_queries));
-    int64_t nq = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (igdc_read_queries(g_core, paths[k], 1, &q[k]) != 0) memset(&q[k], 0, sizeof q[k]);   /* unreadable: an empty set */
-        nq += q[k].n;
-    }
-    int32_t *ichr = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1)), *qs = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    int32_t *qe = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nq + 1));
-    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    const int32_t ev = q_dispatch(v, NULL);
+    cli_sets S;
+    sets_load(&S, P);
+    sets_cat(&S);
     int64_t *st3 = (int64_t *)calloc(3 * (size_t)(n ? n : 1) * nC + 1, sizeof(int64_t));
     double *mean = (double *)malloc(sizeof(double) * (2 * (size_t)(n ? n : 1) * nC + 1));
     int64_t *nh = st3, *np = st3 + (size_t)n * nC, *sa = st3 + 2 * (size_t)n * nC;
     double *meanPair = mean + (size_t)n * nC;
-    off[0] = 0;
-    for (int32_t k = 0; k < n; k++) {
-        if (q[k].n) {
-            memcpy(ichr + off[k], q[k].ichr, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qs + off[k], q[k].qs, sizeof(int32_t) * (size_t)q[k].n);
-            memcpy(qe + off[k], q[k].qe, sizeof(int32_t) * (size_t)q[k].n);
-        }
-        off[k + 1] = off[k] + q[k].n;
-    }
-    int onHost = 0;
-    igdc_map *hm = host_map_lim(nq, igdc_host_limit());
-    if (hm) {
-        double t0 = now_s();
-        onHost = igdc_map_sets_host(g_core, hm, ichr, qs, qe, off, n, op, ev, nh, np, sa) == 0;
-        igdc_map_close(hm);
-        if (onHost) phase("values of the overlapping records on the host (small files)", &t0);
-    }
-    if (!onHost && nq > 0) {                          /* (after a read error too: the engine reads the file its own way) */
-        igd_hip_db *dev = engine();                   /* (IGD_DEVICES with several devices: the first one, as -Q) */
-        double t0 = now_s();
-        if (dev) {
-            const int rc = igd_hip_map_sets(dev, ichr, qs, qe, off, n, op, ev, nh, np, sa);
-            if (rc != IGD_HIP_OK) engine_failed("map", rc);
-            phase("values of the overlapping records of the query sets (H2D + kernels + D2H)", &t0);
-        }
-    }
+    cli_route R;
+    if (route_host(&R, S.nq))
+        route_host_end(&R, igdc_map_sets_host(g_core, R.hm, S.ichr, S.qs, S.qe, S.off, n, op, ev, nh, np, sa) == 0,
+                       "values of the overlapping records on the host (small files)");
+    if (route_engine(&R, S.nq > 0))
+        route_engine_end(&R, "map", igd_hip_map_sets(R.dev, S.ichr, S.qs, S.qe, S.off, n, op, ev, nh, np, sa),
+                         "values of the overlapping records of the query sets (H2D + kernels + D2H)");
     if (!g_fail_rc) igdc_map_summary(nh, np, sa, (int64_t)n * (int64_t)nC, op, mean, meanPair);
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
         const size_t o = (size_t)k * nC;
         int64_t all = 0, withHit = 0;
-        if (setLines) printf("Query set %d: %s\n", (int)k, paths[k]);
+        sets_title(&S, k);
         printf("index\tn_hit\tpairs\tmean_%s\tFile\n", MAP_OPS[opName]);
         for (int32_t i = 0; i < nfiles; i++) {
             printf("%d\t%lld\t%lld", (int)i, (long long)nh[o + i], (long long)np[o + i]);
@@ -1857,8 +1729,8 @@ static void map_files(char **paths, int32_t n, int32_t v, int setLines, int opNa
         }
         printf("Pairs: %lld; datasets with a hit: %lld of %d\n", (long long)all, (long long)withHit, (int)nfiles);
     }
-    for (int32_t k = 0; k < n; k++) igdc_queries_free(&q[k]);
-    free(q); free(ichr); free(qs); free(qe); free(off); free(st3); free(mean);
+    sets_free(&S);
+    free(st3); free(mean);
 }
 
 /* ------------------------------- `igd search -q F -P N -g genome -D <bp>` --------------- */
@@ -1884,23 +1756,14 @@ static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int
     if (!st3 || !fl) { fprintf(stderr, "igd: out of memory\n"); free(st3); free(fl); return; }
     int64_t *nw = st3, *no = nw + R * nC, *sd = no + R * nC, *nge = sd + R * nC, *ndef = nge + nC, *nle = ndef + nC;
     double *wm = fl, *ws = wm + nC, *wz = ws + nC, *pu = wz + nC, *md = pu + nC, *dm = md + nC, *ds = dm + nC, *dz = ds + nC, *pl = dz + nC;
-    double t0 = now_s();
-    int ok = 0;
-    igdc_map *hm = host_map_lim(q->n * (nperm + 1), igdc_host_limit());
-    if (hm) {
-        ok = igdc_permute_nearest_host(g_core, hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd) == 0;
-        igdc_map_close(hm);
-        if (ok) phase("permutation null of the distances on the host (small files)", &t0);
-    }
-    if (!ok) {                                        /* (after a read error too: the engine reads the file its own way) */
-        igd_hip_db *dev = engine();
-        t0 = now_s();
-        if (dev) {
-            const int rc = igd_hip_permute_nearest(dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd);
-            if (rc != IGD_HIP_OK) engine_failed("permutation null of the distances", rc);
-            phase("permutation null of the distances (H2D + permute and fused nearest kernels + D2H)", &t0);
-        }
-    }
+    cli_route Rt;
+    if (route_host(&Rt, q->n * (nperm + 1)))
+        route_host_end(&Rt, igdc_permute_nearest_host(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd) == 0,
+                       "permutation null of the distances on the host (small files)");
+    if (route_engine(&Rt, 1))
+        route_engine_end(&Rt, "permutation null of the distances",
+                         igd_hip_permute_nearest(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd),
+                         "permutation null of the distances (H2D + permute and fused nearest kernels + D2H)");
     if (!g_fail_rc && igdc_perm_nearest_summary(nw, sd, nperm, (int64_t)nC, wm, ws, wz, nge, pu, md, dm, ds, dz, ndef, nle, pl) == 0) {
         printf("index\tn_within\tmean_dist\twithin_mean\twithin_sd\twithin_z\tnlog10_p_within_upper\tdist_mean\tdist_sd\tdist_z\tn_def\tdist_n_le\t"
                "nlog10_p_dist_lower\tFile\n");
@@ -1939,24 +1802,16 @@ static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t 
     if (!st || !fl) { fprintf(stderr, "igd: out of memory\n"); free(st); free(fl); return; }
     int64_t *inter = st, *sbp = inter + R * nC, *nm = sbp + R, *nd = nm + R, *fbp = nd + 1, *obs = fbp + nC, *nge = obs + nC, *nle = nge + nC;
     double *mu = fl, *sd = mu + nC, *z = sd + nC, *fold = z + nC, *pu = fold + nC, *pl = pu + nC, *jac = pl + nC, *jm = jac + nC, *js = jm + nC;
-    double t0 = now_s();
-    int ok = 0;
-    igdc_map *hm = host_map_lim(q->n * (nperm + 1), igdc_host_limit());
-    if (hm) {
-        ok = igdc_permute_bp_host(g_core, hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd) == 0 &&
-             igdc_dataset_bp_host(g_core, hm, ev, rule, fbp) == 0;
-        igdc_map_close(hm);
-        if (ok) phase("permutation null of the base-pair overlap on the host (small files)", &t0);
-    }
-    if (!ok) {                                        /* (after a read error too: the engine reads the file its own way) */
-        igd_hip_db *dev = engine();
-        t0 = now_s();
-        if (dev) {
-            int rc = igd_hip_permute_bp(dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd);
-            if (rc == IGD_HIP_OK) rc = igd_hip_dataset_bp(dev, ev, rule, fbp);
-            if (rc != IGD_HIP_OK) engine_failed("permutation null of the base-pair overlap", rc);
-            phase("permutation null of the base-pair overlap (H2D + permute, merge, hand-over and coverage kernels + D2H)", &t0);
-        }
+    cli_route Rt;
+    if (route_host(&Rt, q->n * (nperm + 1)))
+        route_host_end(&Rt, igdc_permute_bp_host(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd) == 0 &&
+                           igdc_dataset_bp_host(g_core, Rt.hm, ev, rule, fbp) == 0,
+                       "permutation null of the base-pair overlap on the host (small files)");
+    if (route_engine(&Rt, 1)) {
+        int rc = igd_hip_permute_bp(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd);
+        if (rc == IGD_HIP_OK) rc = igd_hip_dataset_bp(Rt.dev, ev, rule, fbp);
+        route_engine_end(&Rt, "permutation null of the base-pair overlap", rc,
+                         "permutation null of the base-pair overlap (H2D + permute, merge, hand-over and coverage kernels + D2H)");
     }
     if (!g_fail_rc && igdc_perm_bp_summary(inter, sbp, fbp, nperm, (int64_t)nC, obs, mu, sd, z, fold, nge, nle, pu, pl, jac, jm, js, NULL, NULL) == 0) {
         printf("index\tobserved_bp\tmean\tsd\tz\tfold\tn_ge\tn_le\tnlog10_p_upper\tnlog10_p_lower\tjaccard\tjaccard_mean\tFile\n");
@@ -2029,6 +1884,27 @@ static int usage_search(void)
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
             "               several GPUs (database replicated, contiguous query slabs, per-dataset counts summed)\n");
     return EX_OK;
+}
+
+/* `-P <permutations>`: 1 when the argument is a whole number in 1 .. IGD_HIP_PERM_MAX; -D, -G and plain -P word their own refusals */
+static int parse_perm_count(const char *arg, long long *np)
+{
+    char *end = NULL;
+    *np = strtoll(arg, &end, 10);
+    return end != arg && !*end && *np >= 1 && *np <= (long long)IGD_HIP_PERM_MAX;
+}
+
+/* `-M <mode>`: circular (also without -M) or shuffle; -1: neither */
+static int parse_perm_mode(const char *arg)
+{
+    if (!arg || strcmp(arg, "circular") == 0) return IGD_HIP_PERM_CIRCULAR;
+    return strcmp(arg, "shuffle") == 0 ? IGD_HIP_PERM_SHUFFLE : -1;
+}
+
+static int refused_usage(const char *why)                                    /* the refusals of the newer options */
+{
+    printf("Not supported: %s\n", why);
+    return EX_USAGE;
 }
 
 int igd_search(int argc, char **argv)                                        /* :889-1079 */
@@ -2175,9 +2051,8 @@ int igd_search(int argc, char **argv)                                        /* 
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    long long np = 0;                                                         /* -P's count, once a block below has parsed it */
     if (gbp) {                                                                /* -G: every refusal is a usage error */
-        char *pend = NULL;
-        const long long np = permArg ? strtoll(permArg, &pend, 10) : 0;
         const char *why = NULL;
         if (!permArg) why = "-G without -P";
         else if (distArg || jac || minov || nearArg || histArg || flankL || flankEdges || mapArg || listName || uniq || bp || memb || uniName ||
@@ -2185,12 +2060,9 @@ int igd_search(int argc, char **argv)                                        /* 
             why = "-G together with -D, -J, -O, -A, -B, -N, -H, -L, -E, -V, -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r";
         else if (!genomeName) why = "-G -P without -g";
         else if (mode != 1) why = "-G -P without -q";
-        else if (pend == permArg || *pend || np < 1 || np > (long long)IGD_HIP_PERM_MAX) why = "-G with a number of permutations outside 1 to 1048576";
-        else if (pmodeArg && strcmp(pmodeArg, "circular") != 0 && strcmp(pmodeArg, "shuffle") != 0) why = "-G with a -M that is neither circular nor shuffle";
-        if (why) {
-            printf("Not supported: %s\n", why);
-            return EX_USAGE;
-        }
+        else if (!parse_perm_count(permArg, &np)) why = "-G with a number of permutations outside 1 to 1048576";
+        else if (parse_perm_mode(pmodeArg) < 0) why = "-G with a -M that is neither circular nor shuffle";
+        if (why) return refused_usage(why);
     }
     if (jac) {                                                                /* -J: every refusal is a usage error */
         const char *why = NULL;
@@ -2198,10 +2070,7 @@ int igd_search(int argc, char **argv)                                        /* 
             mapArg || full || other || minov)
             why = "-J together with -u, -b, -w, -U, -R, -X, -C, -P, -D, -N, -H, -L, -E, -V, -f, -m, -s, -r, -O, -A or -B";
         else if (mode != 1 && !listName) why = "-J without -q or -Q";
-        if (why) {
-            printf("Not supported: %s\n", why);
-            return EX_USAGE;
-        }
+        if (why) return refused_usage(why);
     }
     int mapOp = -1;                                                           /* -V: every refusal is a usage error */
     if (mapArg) {
@@ -2210,10 +2079,7 @@ int igd_search(int argc, char **argv)                                        /* 
         if (uniq || bp || memb || uniName || ranks || restricted || cooc || permArg || distArg || nearArg || full || other || minov)
             why = "-V together with -u, -b, -w, -U, -R, -X, -C, -P, -D, -N, -f, -m, -s, -r, -O, -A or -B";
         else if (mode != 1 && !listName) why = "-V without -q or -Q";
-        if (why) {
-            printf("Not supported: %s\n", why);
-            return EX_USAGE;
-        }
+        if (why) return refused_usage(why);
         if (mapOp < 0) {
             printf("Not supported: -V %s (count, sum, min, max or mean)\n", mapArg);
             return EX_USAGE;
@@ -2232,10 +2098,7 @@ int igd_search(int argc, char **argv)                                        /* 
         else if (!nearArg) why = "-L without -N";
         else if (histArg || permArg || distArg || minov) why = "-L together with -H, -P, -D, -O, -A or -B";
         else if (!binsArg) why = "-L without a number of bins";
-        if (why) {
-            printf("Not supported: %s\n", why);
-            return EX_USAGE;
-        }
+        if (why) return refused_usage(why);
         if (binsArg[0] < '0' || binsArg[0] > '9' || *end || !igd_hip_flank_bins_valid(nb)) {
             printf("Not supported: -L %s (1 to %d bins)\n", binsArg, (int)IGD_HIP_FLANK_MAX_BINS);
             return EX_USAGE;
@@ -2248,10 +2111,7 @@ int igd_search(int argc, char **argv)                                        /* 
         const char *why = NULL;
         if (!nearArg) why = "-H without -N";
         else if (permArg || distArg) why = "-H together with -P or -D";
-        if (why) {
-            printf("Not supported: %s\n", why);
-            return EX_USAGE;
-        }
+        if (why) return refused_usage(why);
         if ((histNe = parse_edges(histArg, histEdges)) < 1) {
             printf("Not supported: -H %s (1 to %d ascending integer edges, each within int32, separated by commas)\n", histArg,
                    (int)IGD_HIP_NEAREST_MAX_EDGES);
@@ -2260,27 +2120,24 @@ int igd_search(int argc, char **argv)                                        /* 
     }
     int32_t distW = -1;                                                       /* -D: every refusal is a usage error */
     if (distArg) {
-        char *end = NULL, *pend = NULL;
+        char *end = NULL;
         const long long w = strtoll(distArg, &end, 10);
-        const long long np = permArg ? strtoll(permArg, &pend, 10) : 0;
         const char *why = NULL;
         if (!permArg) why = "-D without -P";
         else if (nearArg || minov || listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)
             why = "-D together with -N, -O, -A, -B, -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r";
         else if (!genomeName) why = "-D -P without -g";
         else if (mode != 1) why = "-D -P without -q";
-        else if (pend == permArg || *pend || np < 1 || np > (long long)IGD_HIP_PERM_MAX) why = "-D with a number of permutations outside 1 to 1048576";
-        else if (pmodeArg && strcmp(pmodeArg, "circular") != 0 && strcmp(pmodeArg, "shuffle") != 0) why = "-D with a -M that is neither circular nor shuffle";
-        if (why) {
-            printf("Not supported: %s\n", why);
-            return EX_USAGE;
-        }
+        else if (!parse_perm_count(permArg, &np)) why = "-D with a number of permutations outside 1 to 1048576";
+        else if (parse_perm_mode(pmodeArg) < 0) why = "-D with a -M that is neither circular nor shuffle";
+        if (why) return refused_usage(why);
         if (end == distArg || *end || w < 0 || w > (long long)IGD_HIP_NEAREST_MAX_WINDOW) {
             printf("Not supported: -D %s (a window of 0 to %lld base pairs)\n", distArg, (long long)IGD_HIP_NEAREST_MAX_WINDOW);
             return EX_USAGE;
         }
         distW = (int32_t)w;
     }
+    int32_t nearW = 0;                                                        /* -N: the older wording, and exit code 0 */
     if (nearArg) {
         char *end = NULL;
         const long long w = strtoll(nearArg, &end, 10);
@@ -2296,6 +2153,7 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported: -N %s (a window of 0 to %lld base pairs)\n", nearArg, (long long)IGD_HIP_NEAREST_MAX_WINDOW);
             return EX_OK;
         }
+        nearW = (int32_t)w;
     }
     if (minov && (bp || memb || restricted || cooc || full || other || (mode != 1 && !listName))) {
         printf("Not supported: -O, -A or -B together with -b, -w, -X, -C, -f, -m, -s or -r, or without -q or -Q\n");
@@ -2303,37 +2161,23 @@ int igd_search(int argc, char **argv)                                        /* 
     }
     if (minov && igd_hip_min_overlap_active(&g_mo_val)) g_mo = &g_mo_val;      /* (all three zero: no threshold) */
     fP = fopen(igdName, "rb");                                                /* :974 */
+    /* the query files of the per-set commands: -q's when it was given, else the -Q list's; opened by the branch that runs one */
+    char *const oneFile = mode == 1 ? qfName : NULL;
+    const int perSet = mode == 1 || (mode < 0 && listName);                   /* -u, -b and -w: -Q counts only without -m, -s and -r */
+    cli_paths P;
+    memset(&P, 0, sizeof P);
     if (!permArg && (genomeName || seedArg || pmodeArg)) {
         printf("Not supported: -g, -S or -M without -P\n");
         return EX_OK;
-    } else if (jac && mode == 1) {
-        jaccard_files(&qfName, 1, v, 0);
     } else if (jac) {
-        int32_t n = 0;
-        char **paths = read_list(listName, &n);
-        if (n >= 0) jaccard_files(paths, n, v, 1);
-        for (int32_t k = 0; k < n; k++) free(paths[k]);
-        free(paths);
-    } else if (mapArg && mode == 1) {
-        map_files(&qfName, 1, v, 0, mapOp);
+        if (paths_open(&P, oneFile, listName)) jaccard_files(&P, v);
     } else if (mapArg) {
-        int32_t n = 0;
-        char **paths = read_list(listName, &n);
-        if (n >= 0) map_files(paths, n, v, 1, mapOp);
-        for (int32_t k = 0; k < n; k++) free(paths[k]);
-        free(paths);
-    } else if (nearArg && mode == 1) {
-        if (flankL) flank_reldist_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10), flankEdges ? IGD_HIP_FLANK_EDGES : IGD_HIP_FLANK_MIDPOINTS, flankBins);
-        else if (histArg) nearest_hist_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10), histEdges, histNe);
-        else nearest_files(&qfName, 1, v, 0, (int32_t)strtoll(nearArg, NULL, 10));
+        if (paths_open(&P, oneFile, listName)) map_files(&P, v, mapOp);
     } else if (nearArg) {
-        int32_t n = 0;
-        char **paths = read_list(listName, &n);
-        if (n >= 0 && flankL) flank_reldist_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10), flankEdges ? IGD_HIP_FLANK_EDGES : IGD_HIP_FLANK_MIDPOINTS, flankBins);
-        else if (n >= 0 && histArg) nearest_hist_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10), histEdges, histNe);
-        else if (n >= 0) nearest_files(paths, n, v, 1, (int32_t)strtoll(nearArg, NULL, 10));
-        for (int32_t k = 0; k < n; k++) free(paths[k]);
-        free(paths);
+        const int ok = paths_open(&P, oneFile, listName);
+        if (ok && flankL) flank_reldist_files(&P, v, nearW, flankEdges ? IGD_HIP_FLANK_EDGES : IGD_HIP_FLANK_MIDPOINTS, flankBins);
+        else if (ok && histArg) nearest_hist_files(&P, v, nearW, histEdges, histNe);
+        else if (ok) nearest_files(&P, v, nearW);
     } else if (permArg && (listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)) {
         printf("Not supported: -P together with -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r\n");
         return EX_OK;
@@ -2344,11 +2188,8 @@ int igd_search(int argc, char **argv)                                        /* 
         printf("Not supported: -P without -q\n");
         return EX_OK;
     } else if (permArg) {
-        char *end = NULL;
-        const long long np = strtoll(permArg, &end, 10);
-        const int pmode = !pmodeArg || strcmp(pmodeArg, "circular") == 0 ? IGD_HIP_PERM_CIRCULAR
-                          : strcmp(pmodeArg, "shuffle") == 0 ? IGD_HIP_PERM_SHUFFLE : -1;
-        if (end == permArg || *end || np < 1 || np > (long long)IGD_HIP_PERM_MAX) {
+        const int pmode = parse_perm_mode(pmodeArg);
+        if (!parse_perm_count(permArg, &np)) {
             printf("Not supported: -P %s (1 to %lld permutations)\n", permArg, (long long)IGD_HIP_PERM_MAX);
             return EX_OK;
         }
@@ -2374,14 +2215,8 @@ int igd_search(int argc, char **argv)                                        /* 
     } else if (uniName && (bp || memb || full || other)) {
         printf("Not supported: -U together with -b, -w, -f, -m, -s or -r\n");
         return EX_OK;
-    } else if (uniName && mode == 1) {
-        enrich_files(&qfName, 1, uniName, v, 0, ranks, restricted);
-    } else if (uniName && listName) {
-        int32_t n = 0;
-        char **paths = read_list(listName, &n);
-        if (n >= 0) enrich_files(paths, n, uniName, v, 1, ranks, restricted);
-        for (int32_t k = 0; k < n; k++) free(paths[k]);
-        free(paths);
+    } else if (uniName && (mode == 1 || listName)) {
+        if (paths_open(&P, oneFile, listName)) enrich_files(&P, uniName, v, ranks, restricted);
     } else if (full) {                                                        /* :975-995 */
         if (mode == 1) {
             int64_t total = IGD->gType == 0 ? getOverlaps_f0(qfName) : getOverlaps_f1(qfName);
@@ -2393,28 +2228,19 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported -f option\n");
             return EX_OK;
         }
-    } else if ((mode == 1 || (mode < 0 && listName)) && memb && (uniq || bp)) {
+    } else if (perSet && memb && (uniq || bp)) {
         printf("Not supported: -w together with -u or -b\n");
         return EX_OK;
-    } else if (mode == 1 && memb) {
-        membership_files(&qfName, 1, v, 0);
-    } else if ((mode == 1 || (mode < 0 && listName)) && uniq && bp) {
+    } else if (perSet && memb) {
+        if (paths_open(&P, oneFile, listName)) membership_files(&P, v);
+    } else if (perSet && uniq && bp) {
         printf("Not supported: -b together with -u\n");
         return EX_OK;
-    } else if (mode == 1 && (uniq || bp)) {
-        support_files(&qfName, 1, v, 0, bp);
-    } else if (mode == 1) {                                                   /* :1023-1040 */
-        if (IGD->gType == 0) getOverlaps0(qfName, hits);
-        else if (v > 0) getOverlaps_v(qfName, hits, v);
-        else getOverlaps(qfName, hits);
-        if (!g_fail_rc) printf("index\t number of regions\t number of hits\t File_name\n");
-        int64_t total = 0;
-        for (int32_t i = 0; i < nfiles && !g_fail_rc; i++) {
-            if (hits[i] > 0)
-                printf("%i\t%i\t%lld\t%s\n", i, IGD->finfo[i].nr, (long long)hits[i], IGD->finfo[i].fileName);
-            total += hits[i];
-        }
-        if (!g_fail_rc) printf("Total: %lld\n", (long long)total);
+    } else if (perSet && (uniq || bp)) {
+        if (paths_open(&P, oneFile, listName)) support_files(&P, v, bp);
+    } else if (mode == 1) {                                                  /* :1023-1040 */
+        count_file(qfName, v, hits);
+        if (!g_fail_rc) print_hits_table(hits);
     } else if (mode == 2) {                                                   /* :1041-1053 */
         if (IGD->gType == 0) get_overlaps0(chrm, qs, qe, hits);
         else if (v > 0) get_overlaps_v(chrm, qs, qe, v, hits);
@@ -2456,24 +2282,13 @@ int igd_search(int argc, char **argv)                                        /* 
                 printf("%i\t%i\t%10.6f\t%s\n", i, IGD->finfo[i].nr, sm[i], IGD->finfo[i].fileName);
             free(sm);
         }
-    } else if (listName && memb) {
-        int32_t n = 0;
-        char **paths = read_list(listName, &n);
-        if (n >= 0) membership_files(paths, n, v, 1);
-        for (int32_t k = 0; k < n; k++) free(paths[k]);
-        free(paths);
-    } else if (listName && (uniq || bp)) {
-        int32_t n = 0;
-        char **paths = read_list(listName, &n);
-        if (n >= 0) support_files(paths, n, v, 1, bp);
-        for (int32_t k = 0; k < n; k++) free(paths[k]);
-        free(paths);
     } else if (listName) {                        /* only where the reference's own parse leaves nothing to do */
-        search_sets(listName, v, hits);
+        if (paths_open(&P, oneFile, listName)) search_sets(&P, v, hits);
     } else {
         free(hits);
         return usage_search();
     }
+    paths_close(&P);
 
     /* release everything, in the shape get_igdinfo/get_fileinfo handed it out (:1066-1078) */
     if (fP) { fclose(fP); fP = NULL; }
