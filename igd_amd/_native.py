@@ -265,6 +265,9 @@ def hip():
         # the y of the reductions' grid: ncols (nFiles + 1 for the nearest family, nFiles for map), nslices
         L.igd_hip_reduce_grid_y.argtypes = [C.c_int64, C.c_int64]
         L.igd_hip_reduce_grid_y.restype = C.c_int32
+        # TEST-ONLY, igd_sortscan.hpp on host arrays: device, in, n, out, total / device, keys, vals, n, bits
+        L.igd_hip_test_exclusive_scan.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.igd_hip_test_radix_sort_pairs.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         L.igd_hip_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_search_runs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -426,6 +426,7 @@ struct igd_hip_db {
 #include "engine/host_map.hpp"        // igd_hip_map / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
 #include "engine/host_merge.hpp"      // igd_hip_merge_sets / _dev, igd_hip_dataset_bp, igd_hip_jaccard_sets: device merge, merged base pairs per dataset, the intersection table
 #include "engine/host_permute_bp.hpp" // igd_hip_permute_bp: chunks of permutations, merged and covered without a host copy in between
+#include "engine/host_selftest.hpp"   // TEST-ONLY: igd_hip_test_exclusive_scan / igd_hip_test_radix_sort_pairs: igd_sortscan.hpp on host arrays, guard bytes behind every device array
 #include "engine/measure.hpp"         // instrumentation: compulsory traffic, streaming rates of the box, launch profile
 extern "C" unsigned igd_hip_build_wrong_counts(void)
 {

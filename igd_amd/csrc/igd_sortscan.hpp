@@ -184,7 +184,9 @@ static __global__ void __launch_bounds__(RS_WG) ss_rs_scatter(const uint32_t *__
 }
 
 
-// sorts (kA, vA) by the low `bits` bits of the key; kB/vB are scratch of the same size, hist holds
+// sorts (kA, vA) by the key, one whole byte per pass: the order is that of the low 8 * ceil(bits / 8) bits, not of the low
+// `bits` bits alone.  Every caller passes keys below 2^bits, for which the two are the same.  bits == 0: nothing is done.
+// kB/vB are scratch of the same size, hist holds
 // 256 * nBlocks uint32, digitBase as many int64, sums ceil(256*nBlocks / SCAN_TILE) + 1 int64.
 // On return *kA/*vA point at the sorted arrays (the buffers may have been swapped).
 static inline int64_t rs_blocks(int64_t n) { return (n + RS_BLOCK - 1) / RS_BLOCK; }

@@ -592,6 +592,17 @@ int64_t igd_hip_merge_slices_per_row(int64_t pc, int64_t nq);
  * the slices y, y + this number, ..: it meets a second slice only when nslices exceeds it (tests; TEST-ONLY: IGD_HIP_REDUCE_WGS
  * lowers the 16384, read once per process). */
 int32_t igd_hip_reduce_grid_y(int64_t ncols, int64_t nslices);
+/* TEST-ONLY: the two device primitives everything above is built on (igd_sortscan.hpp), on host arrays.  Both block, need no
+ * handle, and free what they allocate.  They run the instantiations the engine itself uses, with workspaces of exactly the
+ * promised sizes (hist 256 * nBlocks uint32, digitBase as many int64, sums ceil(len / SCAN_TILE) + 1 int64) and 256 guard
+ * bytes behind every device array: IGD_HIP_ERR_DEVICE, igd_hip_last_error naming the array, when one of them was written.
+ * igd_hip_test_exclusive_scan: out[i] = in[0] + .. + in[i - 1] and *total = the sum of all, in 64 bits.  n == 0 is IGD_HIP_OK
+ * with *total = 0 and nothing else touched.
+ * igd_hip_test_radix_sort_pairs: (keys, vals) sorted in place, stably, by the low 8 * ceil(bits / 8) bits of the key (the
+ * engine's callers pass keys below 2^bits); bits == 0 and n == 0 leave both arrays as they are.
+ * IGD_HIP_ERR_ARG with nothing written: n < 0 or n > 2^31, a null array, bits outside 0 .. 32, no such device. */
+int igd_hip_test_exclusive_scan(int device, const uint32_t *in, int64_t n, int64_t *out, int64_t *total);
+int igd_hip_test_radix_sort_pairs(int device, uint32_t *keys, uint32_t *vals, int64_t n, int bits);
 
 /* The set statistics without the distance rows, and their permutation null (kernel igd_nearest_slices: the walk and table of
  * igd_nearest_rows, folded per region into LDS accumulators of the slice; nothing per region reaches memory).

@@ -39,6 +39,32 @@ def ref_merge(nctg, ichr, qs, qe, set_off, gap=0):
             np.array(dropped, np.int64))
 
 
+def ref_merge_np(nctg, ichr, qs, qe, set_off, gap=0):
+    """ref_merge's six arrays, vectorised for millions of regions: a lexsort by (set, contig, qs, qe); the largest end so far
+    of every (set, contig) segment as ONE running maximum over end + (segment << 32) in int64, the ends moved to 0 .. 2^32 - 1
+    so that a later segment's smallest value is above an earlier one's largest; run heads, counts, dropped regions"""
+    ichr, qs, qe = (np.asarray(a).astype(np.int64) for a in (ichr, qs, qe))
+    set_off = np.asarray(set_off, np.int64)
+    nsets = len(set_off) - 1
+    setof = np.repeat(np.arange(nsets, dtype=np.int64), np.diff(set_off))
+    part = (ichr >= 0) & (ichr < nctg) & (qe > qs)
+    dropped = np.bincount(setof[~part], minlength=nsets).astype(np.int64)
+    s, c, a, b = setof[part], ichr[part], qs[part], qe[part]
+    order = np.lexsort((b, a, c, s))
+    s, c, a, b = s[order], c[order], a[order], b[order]
+    m = len(s)
+    seg_head = np.ones(m, bool)
+    seg_head[1:] = (s[1:] != s[:-1]) | (c[1:] != c[:-1])
+    seg = (np.cumsum(seg_head) - 1) << 32
+    inc = np.maximum.accumulate(b + (1 << 31) + seg) - seg - (1 << 31)
+    opens = seg_head.copy()
+    opens[1:] |= a[1:] > inc[:-1] + gap
+    heads = np.flatnonzero(opens)
+    ends = np.append(heads[1:], m)[:len(heads)]          # (no region takes part: no run)
+    m_off = np.concatenate([[0], np.cumsum(np.bincount(s[heads], minlength=nsets))]).astype(np.int64)
+    return (c[heads].astype(np.int32), a[heads].astype(np.int32), inc[ends - 1].astype(np.int32), m_off, (ends - heads).astype(np.int32), dropped)
+
+
 def _masks(db, span, v):
     """per contig: bool[nfiles + 1, span], row f the bp under the counted records of file f, the last row under any file's"""
     use_v = v is not None and v != NOV and db.gtype == 1

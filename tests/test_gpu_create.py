@@ -220,6 +220,73 @@ def test_engine_c_abi_direct_and_python_flavour():
         shutil.rmtree(d, ignore_errors=True)
 
 
+def check_created(nbp, nctg, ctg, start, end, value, file):
+    """igd_hip_create on arrays against the expectation of test_engine_c_abi_direct_and_python_flavour, vectorised: every record
+    expanded to its (tile, record) pairs, the pairs put in tile order by a stable sort, and the oracle's tile sort called on the
+    tiles that hold two records or more (a tile of one has one order) -> what igd_hip_create returned"""
+    from igd_amd import _native
+    created = _native.create_arrays(nbp, 1, nctg, ctg, start, end, value, file)
+    n, n1, n2 = len(start), start.astype(np.int64) // nbp, (end.astype(np.int64) - 1) // nbp
+    ntile = np.array([int(n2[ctg == c].max()) + 1 for c in range(nctg)], np.int64)
+    assert created["nTile"].tolist() == ntile.tolist()
+    tb = np.concatenate([[0], np.cumsum(ntile)])
+    span = n2 - n1 + 1
+    first = np.cumsum(span) - span
+    rec = np.repeat(np.arange(n), span)
+    tile = tb[ctg[rec]] + n1[rec] + (np.arange(len(rec)) - first[rec])
+    cnt = np.bincount(tile, minlength=int(tb[-1]))
+    assert len(created["records"]) == len(rec) and np.array_equal(created["nCnt"], cnt)
+    src = rec[np.argsort(tile, kind="stable")].astype(np.int32)       # input order inside every tile
+    key = start[src].astype(np.int32)
+    O = orc()
+    off = np.cumsum(cnt) - cnt
+    many = np.flatnonzero(cnt >= 2)
+    for o, m in zip(off[many].tolist(), cnt[many].tolist()):
+        O.orc_tile_sort(C.c_void_p(key.ctypes.data + 4 * o), C.c_void_p(src.ctypes.data + 4 * o), C.c_int64(m))
+    exp = np.stack([file[src], start[src], end[src], value[src]], axis=1)
+    bad = np.flatnonzero((created["records"] != exp).any(axis=1))
+    assert len(bad) == 0, (len(bad), int(bad[0]), created["records"][bad[0]].tolist(), exp[bad[0]].tolist())
+    return created, len(many)
+
+
+def scan_round():
+    from test_gpu_sortscan import ROUND, SCAN_TILE, SUMS_WG
+    return ROUND, SCAN_TILE, SUMS_WG
+
+
+def test_create_many_records_past_one_round_of_the_scan():
+    """the span scan (replica offsets) over more than ROUND records: ss_scan_of_sums takes the tile sums into a second round, and
+    the sort by tile orders more than ROUND pairs"""
+    ROUND, SCAN_TILE, SUMS_WG = scan_round()
+    rng = np.random.default_rng(31)
+    n, nbp = ROUND + 2 * SCAN_TILE + 3, 16384
+    ctg = rng.integers(0, 3, n).astype(np.int32)
+    start = rng.integers(0, 1 << 28, n).astype(np.int32)
+    end = (start + rng.choice([1, 10, 1000, nbp + 3], n)).astype(np.int32)
+    value = rng.integers(0, 1000, n).astype(np.int32)
+    file = np.sort(rng.integers(0, 40, n)).astype(np.int32)
+    created, sorted_tiles = check_created(nbp, 3, ctg, start, end, value, file)
+    assert -(-n // SCAN_TILE) > SUMS_WG and len(created["records"]) > ROUND
+    assert set(np.unique((end - 1) // nbp - start // nbp).tolist()) == {0, 1, 2} and sorted_tiles > 40000
+
+
+def test_create_many_tiles_past_one_round_of_the_scan():
+    """the tile-offset scan over more than ROUND + SCAN_TILE counts that are mostly 0 or 1"""
+    ROUND, SCAN_TILE, SUMS_WG = scan_round()
+    rng = np.random.default_rng(32)
+    n, nbp = 300000, 16
+    top = nbp * (ROUND + 2 * SCAN_TILE)
+    start = rng.integers(0, top - nbp, n).astype(np.int32)
+    end = (start + rng.integers(1, nbp + 1, n)).astype(np.int32)
+    start[n // 2], end[n // 2] = top - nbp, top                     # one record ends in the last tile
+    value = rng.integers(0, 1000, n).astype(np.int32)
+    file = np.sort(rng.integers(0, 40, n)).astype(np.int32)
+    created, sorted_tiles = check_created(nbp, 1, np.zeros(n, np.int32), start, end, value, file)
+    ntiles = int(created["nTile"][0])
+    assert ntiles + 1 > ROUND + SCAN_TILE and -(-(ntiles + 1) // SCAN_TILE) > SUMS_WG
+    assert len(created["records"]) > n and np.count_nonzero(created["nCnt"] <= 1) > 0.9 * ntiles and sorted_tiles > 1000
+
+
 def test_golden_smallrand_beds_give_the_reference_database():
     """tests/golden/smallrand holds gzip'd BED inputs AND the db.igd the reference created from them
     (-b 14): `bin/igd create` must reproduce that file (tile bytes included), and searching our file

@@ -15,7 +15,7 @@ import pytest
 import igd_amd
 import igd_amd.database
 from helpers import ROOT, short_tmpdir
-from jaccard_ref import MAX_GAP, ref_dataset_bp, ref_jaccard, ref_merge
+from jaccard_ref import MAX_GAP, ref_dataset_bp, ref_jaccard, ref_merge, ref_merge_np
 from nearest_ref import TOP, ListDb, sparse_lists
 from test_jaccard_cli import db_and_beds
 from test_jaccard_host import G32, G64, NUMPY_DBS, PLACED, JaccardHost, _p, cli_rule, cut_merge, merge_equal, placed_arrays, shape_case, two_contig_db
@@ -330,6 +330,70 @@ def test_the_carry_workgroup_hands_the_pair_from_round_to_round():
     p = subprocess.run([sys.executable, "-c", CARRY], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        env=dict(os.environ, IGD_HIP_MERGE_CARRY_WG=str(CARRY_WG)), timeout=900)
     assert p.returncode == 0 and p.stdout.strip().endswith(b"ok"), p.stderr.decode()[-2000:]
+
+
+def shipped_round():
+    """regions of one round of igd_merge_scan_carry and of ss_scan_of_sums as shipped (both 1 024 tiles of SCAN_TILE)"""
+    src = open(os.path.join(ROOT, "igd_amd", "csrc", "engine", "merge_dev.hpp")).read()
+    wg = int(re.search(r"^#define\s+IGD_MERGE_CARRY_WG\s+(\d+)", src, re.M).group(1))
+    from test_gpu_sortscan import SUMS_WG
+    assert wg == SUMS_WG and wg // 64 == 16, (wg, SUMS_WG)      # (16 waves' partials in wagg[])
+    return wg * SCAN_TILE
+
+
+def seam_case(R, what):
+    """the construction of CARRY above with R regions per round: sorted positions [0, R) ONE run that ends on the first seam;
+    the next segment (a set or a contig) begins there with [500, 600) inside that run's span, then [1000, 10^8) with R + 50
+    small regions inside it, one run ACROSS the second seam, a region behind it, and disjoint regions into the third round"""
+    rng = np.random.default_rng(9800)
+    a_in = 10 + np.cumsum(rng.integers(1, 40, R - 1))
+    b_in = 1001 + np.cumsum(rng.integers(1, 40, R + 50))
+    assert a_in[-1] < 10 ** 8 - 10 and b_in[-1] < 10 ** 8 - 10
+    a_s, a_e = np.concatenate([[0], a_in]), np.concatenate([[10 ** 8], a_in + 3])
+    b_s, b_e = np.concatenate([[500, 1000], b_in, [10 ** 8 + 7]]), np.concatenate([[600, 10 ** 8], b_in + 3, [10 ** 8 + 9]])
+    c_s = 2 * 10 ** 8 + 10 * np.arange(1500)
+    qs, qe = (np.concatenate(x).astype(np.int32) for x in ((a_s, b_s, c_s), (a_e, b_e, c_s + 9)))
+    n = len(qs)
+    if what == "sets":
+        ichr, off = np.zeros(n, np.int32), np.array([0, R, R + len(b_s), n], np.int64)
+    else:
+        ichr, off = np.concatenate([np.zeros(R, np.int32), np.ones(n - R, np.int32)]), np.array([0, n], np.int64)
+    perm = np.concatenate([int(off[k]) + np.random.RandomState(k).permutation(int(off[k + 1] - off[k])) for k in range(len(off) - 1)])
+    return ichr[perm], qs[perm], qe[perm], off
+
+
+def random_case(n):
+    """three sets on two contigs, a few regions that do not take part; about every second region joins its neighbour"""
+    rng = np.random.default_rng(9900)
+    ichr = rng.integers(0, 2, n).astype(np.int32)
+    qs = rng.integers(0, 2 * 10 ** 9, n)
+    qe = qs + rng.choice([1, 30, 400, 5000], n)
+    for k, i in enumerate(rng.integers(0, n, 40)):
+        if k % 2:
+            ichr[i] = (-1, 2)[k % 4 == 1]
+        else:
+            qe[i] = qs[i] - (k % 4)
+    return ichr, qs.astype(np.int32), qe.astype(np.int32), np.array([0, n // 5, n // 5 + n // 2, n], np.int64)
+
+
+@pytest.mark.parametrize("what", ["sets", "contigs", "random"])
+def test_the_merge_past_a_round_under_the_shipped_constants(what, placed):
+    """No test variable is set: igd_merge_scan_carry runs with its 1 024 threads and 16 waves' partials, and the run-flag scan
+    inside the merge (exclusive_scan) with ss_scan_of_sums, both into a third round of 1 024 tiles.  Every integer against
+    ref_merge_np (tests/test_jaccard_host.py pins it to the Python sweep)."""
+    assert not any(v in os.environ for v in ("IGD_HIP_MERGE_CARRY_WG", "IGD_HIP_MERGE_GRID"))
+    R = shipped_round()
+    ichr, qs, qe, off = random_case(2 * R + SCAN_TILE + 5) if what == "random" else seam_case(R, what)
+    n = len(qs)
+    assert -(-n // SCAN_TILE) > 2 * (R // SCAN_TILE), "%d regions do not reach a third round of %d tiles" % (n, R // SCAN_TILE)
+    want = ref_merge_np(2, ichr, qs, qe, off)
+    rc, got, rest = cut_merge(dev_merge(placed, ichr, qs, qe, off))
+    assert rc == 0 and merge_equal(got, want) and (rest == 0).all(), [np.flatnonzero(g != w)[:3] if g.shape == w.shape else (g.shape, w.shape)
+                                                                       for g, w in zip(got, want)]
+    if what == "random":
+        assert want[5].sum() >= 20 and (want[5] > 0).all() and 0.2 * n < len(want[0]) < 0.8 * n and want[4].max() > 3
+    else:
+        assert got[2][:4].tolist() == [10 ** 8, 600, 10 ** 8, 10 ** 8 + 9] and got[4][:4].tolist() == [R, 1, R + 51, 1]
 
 
 def test_cli_j_on_both_routes_byte_for_byte(workdir):

@@ -14,7 +14,7 @@ import pytest
 import igd_amd
 import igd_amd.database
 from helpers import short_tmpdir
-from jaccard_ref import FLAT, MAX_GAP, NEST, jaccard_regions, ref_dataset_bp, ref_jaccard, ref_merge
+from jaccard_ref import FLAT, MAX_GAP, NEST, jaccard_regions, ref_dataset_bp, ref_jaccard, ref_merge, ref_merge_np
 from nearest_ref import NOV, TOP, ListDb, clustered_lists
 from test_nearest_host import set_offsets
 from test_support_host import NUMPY_DBS
@@ -138,6 +138,23 @@ def placed_arrays(case):
 def test_the_reference_gives_the_placed_cases(case):
     (ichr, qs, qe, off, gap), want = placed_arrays(case)
     assert merge_equal(ref_merge(2, ichr, qs, qe, off, gap), want)
+
+
+def test_the_numpy_reference_equals_the_python_reference(tmp):
+    """ref_merge_np (the vectorised form the production-size device cases are checked against) gives ref_merge's six arrays, types
+    included: on the placed cases, which it must also give as written out by hand, and on the four database shapes under four gaps"""
+    for case in PLACED:
+        (ichr, qs, qe, off, gap), want = placed_arrays(case)
+        got = ref_merge_np(2, ichr, qs, qe, off, gap)
+        assert merge_equal(got, want) and merge_equal(got, ref_merge(2, ichr, qs, qe, off, gap)), case[0]
+    for case in range(len(NUMPY_DBS)):
+        db, ichr, qs, qe, off = shape_case(case, tmp)
+        for gap in (0, 1, 300, MAX_GAP):
+            want = ref_merge(len(db.ctgs), ichr, qs, qe, off, gap)
+            assert len(want[0]) > 0 and want[5].sum() > 0 and want[4].max() > 1          # (the inputs have runs, joined regions and dropped ones)
+            assert merge_equal(ref_merge_np(len(db.ctgs), ichr, qs, qe, off, gap), want), (case, gap)
+    none = ref_merge_np(2, [5, 0], [1, 9], [2, 9], [0, 0, 2, 2], 0)
+    assert merge_equal(none, ref_merge(2, [5, 0], [1, 9], [2, 9], [0, 0, 2, 2], 0)) and none[3].tolist() == [0, 0, 0, 0] and none[5].tolist() == [0, 2, 0]
 
 
 def test_placed_cases_on_the_host_route(tmp, host_threads):
