@@ -1,7 +1,10 @@
 // engine/host_common.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
 // What the host sides of the region-set entry points share: workspace growth, query staging, the image a slice kernel reads,
-// the set_off checks, slice and grid arithmetic, kernel dispatch by template flags, and the chunk driver of
-// igd_hip_search_sets / igd_hip_support_sets / igd_hip_coverage_sets.
+// the set_off checks, slice, step and grid arithmetic, kernel dispatch by template flags, and two drivers:
+//   run_region_chunks  host arrays in chunks of regions, rows back per chunk: igd_hip_nearest(_signed), igd_hip_flank,
+//                      igd_hip_map, igd_hip_membership, igd_hip_cooccur
+//   run_set_chunks     chunks of sets, rows added on the host: igd_hip_search_sets / igd_hip_support_sets / igd_hip_coverage_sets
+// (The group driver of the resident set statistics, run_set_groups, is in host_nearest.hpp.)
 // ------------------------------------------------------------------------------------------
 #include <type_traits>
 
@@ -73,6 +76,42 @@ static int stage_queries(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
     HIPCHK(hipMemcpyAsync(db->d_qs, qs + c0, (size_t)m * 4, hipMemcpyHostToDevice, db->stream));
     HIPCHK(hipMemcpyAsync(db->d_qe, qe + c0, (size_t)m * 4, hipMemcpyHostToDevice, db->stream));
     return IGD_HIP_OK;
+}
+
+// Regions per chunk of a host form whose device rows cost bytesPerRegion each: the batch limit, or as many as `budget` bytes of
+// rows hold, at least one.  (igd_hip_nearest: 4 nFiles of nearest_row_bytes(); igd_hip_flank: 8 nFiles; igd_hip_map: 4 or 12
+// nFiles of map_row_bytes(); igd_hip_membership and igd_hip_cooccur: 4 nW of member_row_bytes().)
+static int64_t chunk_step(int64_t budget, int64_t bytesPerRegion)
+{
+    const int64_t byRows = budget / bytesPerRegion, step = max_batch();
+    return byRows < step ? (byRows < 1 ? 1 : byRows) : step;
+}
+
+// The region-chunk driver of the host row forms (the arguments are checked, nq > 0).  For c0 = 0, step, ..: regions
+// [c0, c0 + m) go to the staging buffers, body(c0, m, st) grows its own workspace, runs the _dev form over the staged arrays
+// and enqueues the copies back to the caller's arrays at row c0 -- rows are per region, so chunks need no merging -- and the
+// stream is waited for: the staging buffers and the workspace are written again by the next chunk.
+template <typename Body>
+static int run_region_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t step, Body &&body)
+{
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    for (int64_t c0 = 0; c0 < nq; c0 += step) {
+        const int64_t m = nq - c0 < step ? nq - c0 : step;
+        int rc = stage_queries(db, ichr, qs, qe, c0, m);
+        if (rc == IGD_HIP_OK) rc = body(c0, m, st);
+        if (rc != IGD_HIP_OK) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+    }
+    return IGD_HIP_OK;
+}
+
+// [a0, b0) of a staged array cut into slices of row `row`, at most `len` regions each, positions relative to `base`
+static void push_slices(std::vector<SetSlice> &slices, int32_t row, int64_t a0, int64_t b0, int64_t len, int64_t base)
+{
+    for (int64_t a = a0; a < b0; a += len)
+        slices.push_back(SetSlice{row, (int32_t)(a - base), (int32_t)((a + len < b0 ? a + len : b0) - base), 0});
 }
 
 // The image a slice kernel (walk_query_tiles, sets_dev.hpp) reads: the re-tiled copy when there is one, with the rule word its
@@ -168,9 +207,7 @@ static int run_set_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
             rows = row + 1;
             if (end > pos) {
                 if (set_off[k + 1] - set_off[k] >= bigMin) bigs.push_back(BigPart{row, pos - c0, end - c0});
-                else
-                    for (int64_t a = pos; a < end; a += sliceLen)
-                        slices.push_back(SetSlice{row, (int32_t)(a - c0), (int32_t)((a + sliceLen < end ? a + sliceLen : end) - c0), 0});
+                else push_slices(slices, row, pos, end, sliceLen, c0);
             }
             pos = end;
             if (pos < set_off[k + 1]) break;             // the batch is full: the rest of set k opens the next chunk

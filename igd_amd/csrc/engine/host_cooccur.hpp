@@ -1,8 +1,9 @@
 // engine/host_cooccur.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
 // igd_hip_cooccur, igd_hip_bits_transpose, igd_hip_bitrows_gram (cooccur_dev.hpp)
 // ------------------------------------------------------------------------------------------
-// The co-occurrence.  The regions go through in the CHUNKS of igd_hip_membership: at most igd_hip_max_batch() regions and
-// member_row_bytes() of rows.  Per chunk, all on the engine's stream: the regions to the staging buffers, igd_hip_membership_dev
+// The co-occurrence.  The regions go through in the CHUNKS of igd_hip_membership (run_region_chunks, host_common.hpp): at most
+// igd_hip_max_batch() regions and member_row_bytes() of rows; the first chunk is the largest and every workspace is grown once,
+// before the loop.  Per chunk, all on the engine's stream: the regions to the staging buffers, igd_hip_membership_dev
 // into the handle's rows, igd_bits_transpose into the handle's columns (32 * nW columns of ceil(chunk / 64) words; the tail bits
 // of a chunk's last word are 0, so a chunk end that is no multiple of 64 adds nothing), igd_bitrows_gram<true> over the first
 // nFiles columns ADDING into the handle's matrix, which was zeroed once before the first chunk.  The rows never leave the
@@ -173,9 +174,7 @@ extern "C" int igd_hip_cooccur(igd_hip_db *db, const int32_t *ichr, const int32_
         if (nhit) *nhit = 0;
         return IGD_HIP_OK;
     }
-    const int64_t byRows = member_row_bytes() / (nW * 4);
-    int64_t step = max_batch();
-    if (byRows < step) step = byRows < 1 ? 1 : byRows;
+    int64_t step = chunk_step(member_row_bytes(), nW * 4);
     if (nq < step) step = nq;
 
     HIPCHK(hipSetDevice(db->device));
@@ -187,16 +186,14 @@ extern "C" int igd_hip_cooccur(igd_hip_db *db, const int32_t *ichr, const int32_
     if (rc != IGD_HIP_OK) return rc;
     HIPCHK(hipMemsetAsync(db->d_coMat, 0, (size_t)(nF * nF) * 8, st));
     HIPCHK(hipMemsetAsync(db->d_memHit, 0, 8, st));
-    for (int64_t c0 = 0; c0 < nq; c0 += step) {
-        const int64_t m = nq - c0 < step ? nq - c0 : step, cw = (m + 63) / 64;
-        rc = stage_queries(db, ichr, qs, qe, c0, m);
-        if (rc == IGD_HIP_OK) rc = igd_hip_membership_dev(db, db->d_qc, db->d_qs, db->d_qe, m, v, rule, db->d_memBits, nullptr, (int64_t *)db->d_memHit, st);
-        if (rc == IGD_HIP_OK) rc = transpose_launch(db->d_memBits, m, nW, db->d_coCols, st);
-        if (rc == IGD_HIP_OK) rc = gram_launch(db->d_coCols, nF, nullptr, nF, cw, cw, db->d_coMat, st);
-        if (rc != IGD_HIP_OK) return rc;
-        HIPCHK(hipStreamSynchronize(st));                // (the staging buffers are written again by the next chunk)
-        HIPCHK(hipGetLastError());
-    }
+    rc = run_region_chunks(db, ichr, qs, qe, nq, step, [&](int64_t, int64_t m, hipStream_t) {
+        const int64_t cw = (m + 63) / 64;
+        int rc2 = igd_hip_membership_dev(db, db->d_qc, db->d_qs, db->d_qe, m, v, rule, db->d_memBits, nullptr, (int64_t *)db->d_memHit, st);
+        if (rc2 == IGD_HIP_OK) rc2 = transpose_launch(db->d_memBits, m, nW, db->d_coCols, st);
+        if (rc2 == IGD_HIP_OK) rc2 = gram_launch(db->d_coCols, nF, nullptr, nF, cw, cw, db->d_coMat, st);
+        return rc2;
+    });
+    if (rc != IGD_HIP_OK) return rc;
     unsigned long long h = 0;
     HIPCHK(hipMemcpy(&h, db->d_memHit, 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cooc, db->d_coMat, (size_t)(nF * nF) * 8, hipMemcpyDeviceToHost));

@@ -4,11 +4,12 @@
 // ------------------------------------------------------------------------------------------
 // The three forms of host_nearest.hpp with two rows per region.  The device form: one launch of igd_flank_rows (the wide form:
 // a fill of both rows with 0xff before it and igd_nearest_rowmin behind it for each minimum that is wanted), asynchronous on the
-// caller's stream.  The host form: chunks of nearest_step(nF, 2) regions -- at most igd_hip_max_batch() regions and
-// IGD_NEAREST_ROW_BYTES / (8 nFiles) -- whose rows lie in the workspace of igd_hip_nearest, d_nrDist (the up rows of the chunk,
-// then its down rows) and d_nrMin (upmin, then downmin).  The sets form: nearest_set_groups, the driver of igd_hip_nearest_hist,
-// with igd_flank_rows as the row kernel and igd_flank_reldist as the reduction into ONE resident matrix of B x (nFiles + 1)
-// words per set in d_nrStat; slices of at most IGD_NEAREST_SLICE = 256 regions, so the kernel's u32 LDS counters hold at most 256.
+// caller's stream.  The host form: run_region_chunks (host_common.hpp) with chunks of chunk_step(nearest_row_bytes(), 8 nFiles)
+// regions -- at most igd_hip_max_batch() regions and IGD_NEAREST_ROW_BYTES / (8 nFiles) -- whose rows lie in the workspace of
+// igd_hip_nearest, d_nrDist (the up rows of the chunk, then its down rows) and d_nrMin (upmin, then downmin).  The sets form:
+// run_set_groups (host_nearest.hpp), the driver of igd_hip_nearest_hist, with a chunk functor that launches igd_flank_rows and
+// igd_flank_reldist, the reduction into ONE resident matrix of B x (nFiles + 1) words per set in d_grpStat; slices of at most
+// IGD_NEAREST_SLICE = 256 regions, so the kernel's u32 LDS counters hold at most 256.
 // The image is slice_image(db, IGD_HIP_RULE_FLAT, v), as for igd_hip_nearest.
 
 static int flank_args_bad(const char *who, int32_t window, int measure)
@@ -84,13 +85,8 @@ extern "C" int igd_hip_flank(igd_hip_db *db, const int32_t *ichr, const int32_t 
         if (downmin) memset(downmin, 0xff, (size_t)nq * 4);
         return IGD_HIP_OK;
     }
-    const int64_t step = nearest_step(nF, 2);
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
-    for (int64_t c0 = 0; c0 < nq; c0 += step) {
-        const int64_t m = nq - c0 < step ? nq - c0 : step;
+    return run_region_chunks(db, ichr, qs, qe, nq, chunk_step(nearest_row_bytes(), nF * 8), [&](int64_t c0, int64_t m, hipStream_t st) {
         int rc = ensure_nearest_ws(db, 2 * m * nF, 2 * m);
-        if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
         if (rc == IGD_HIP_OK) rc = flank_rows_dev(db, db->d_qc, db->d_qs, db->d_qe, m, window, measure, v, db->d_nrDist, db->d_nrDist + m * nF,
                                                   upmin ? db->d_nrMin : nullptr, downmin ? db->d_nrMin + m : nullptr, st);
         if (rc != IGD_HIP_OK) return rc;
@@ -98,10 +94,8 @@ extern "C" int igd_hip_flank(igd_hip_db *db, const int32_t *ichr, const int32_t 
         HIPCHK(hipMemcpyAsync(down + c0 * nF, db->d_nrDist + m * nF, (size_t)(m * nF) * 4, hipMemcpyDeviceToHost, st));
         if (upmin) HIPCHK(hipMemcpyAsync(upmin + c0, db->d_nrMin, (size_t)m * 4, hipMemcpyDeviceToHost, st));
         if (downmin) HIPCHK(hipMemcpyAsync(downmin + c0, db->d_nrMin + m, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-    }
-    return IGD_HIP_OK;
+        return IGD_HIP_OK;
+    });
 }
 
 extern "C" int igd_hip_flank_reldist(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
@@ -125,11 +119,14 @@ extern "C" int igd_hip_flank_reldist(igd_hip_db *db, const int32_t *ichr, const 
         return IGD_HIP_OK;
     }
     int64_t *outs[1] = {hist};
-    return nearest_set_groups(db, ichr, qs, qe, set_off, nsets, nearest_step(nF, 2), 2, 1, matRow, outs, [&](int64_t m, hipStream_t st) {
-        return flank_rows_dev(db, db->d_qc, db->d_qs, db->d_qe, m, window, measure, v, db->d_nrDist, db->d_nrDist + m * nF, db->d_nrMin,
-                              db->d_nrMin + m, st);
-    }, [&](dim3 grid, int ns, int64_t, int64_t m, hipStream_t st) {
-        igd_flank_reldist<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrDist + m * nF, db->d_nrMin, db->d_nrMin + m, (int)nF, db->d_nrSlices, ns,
-                                                        (int)nbins, (u64 *)db->d_nrStat);
+    return run_set_groups(db, ichr, qs, qe, set_off, nsets, chunk_step(nearest_row_bytes(), nF * 8), IGD_NEAREST_SLICE, 1, matRow, outs, nC,
+                          [&](dim3 grid, int ns, int64_t, int64_t m, hipStream_t st) {
+        int rc2 = ensure_nearest_ws(db, 2 * m * nF, 2 * m);
+        if (rc2 == IGD_HIP_OK) rc2 = flank_rows_dev(db, db->d_qc, db->d_qs, db->d_qe, m, window, measure, v, db->d_nrDist, db->d_nrDist + m * nF, db->d_nrMin,
+                                                    db->d_nrMin + m, st);
+        if (rc2 != IGD_HIP_OK) return rc2;
+        igd_flank_reldist<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrDist + m * nF, db->d_nrMin, db->d_nrMin + m, (int)nF, db->d_grpSlices, ns,
+                                                        (int)nbins, (u64 *)db->d_grpStat);
+        return IGD_HIP_OK;
     });
 }

@@ -4,14 +4,14 @@
 // The shape of host_nearest.hpp.  The device form takes one engine batch of resident regions and writes resident rows: one
 // launch (the wide form: fills of the rows before it and, but for SUM, igd_map_rowfix behind it), asynchronous on the caller's
 // stream.  The host form takes host arrays in CHUNKS of at most igd_hip_max_batch() regions AND at most IGD_MAP_ROW_BYTES of
-// device rows (4 nFiles bytes per region under COUNT, 12 nFiles otherwise: 22.8 KB at 1 900 files, 11 700 regions per chunk);
-// per chunk the regions go to the device through the staging buffers of igd_hip_search, the device form runs on the engine's
-// stream and the rows come back into the caller's arrays at their place.
-// The sets form takes GROUPS of whole sets whose three result rows (3 x nFiles x 8 bytes per set) fit sets_row_bytes(); the
-// regions of a group go through in the same chunks -- a set may be cut by a chunk, its statistics are sums over regions -- and
-// per chunk igd_map_reduce adds the rows into the group's three resident matrices, by a slice table cut here: a slice is at
-// most IGD_MAP_SLICE regions of one set.  The rows never leave the device; the matrices are copied out once per group.  Under
-// COUNT there are no agg rows at all: agg_sum is summed from the counts.
+// device rows (4 nFiles bytes per region under COUNT, 12 nFiles otherwise: 22.8 KB at 1 900 files, 11 700 regions per chunk:
+// chunk_step); run_region_chunks (host_common.hpp) stages the regions of a chunk, the body here runs the device form on the
+// engine's stream and sends the rows back into the caller's arrays at their place.
+// The sets form is run_set_groups (host_nearest.hpp): GROUPS of whole sets whose three result rows (3 x nFiles x 8 bytes per
+// set) fit sets_row_bytes(), the regions of a group in the same chunks, a slice table of at most IGD_MAP_SLICE regions of one
+// set per slice; the chunk functor here runs the device form and igd_map_reduce, which adds the rows into the group's three
+// resident matrices (the handle's d_grpStat and d_grpSlices, shared with the nearest family).  The rows never leave the
+// device.  Under COUNT there are no agg rows at all: agg_sum is summed from the counts.
 // The image is slice_image(db, IGD_HIP_RULE_FLAT, v): the re-tiled copy when there is one, visited under rule FLAT.
 #define IGD_MAP_ROW_BYTES ((int64_t)256 << 20)       // device rows of one chunk (IGD_NEAREST_ROW_BYTES)
 #define IGD_MAP_SLICE 256                            // regions per slice of igd_map_reduce: 64 per wave
@@ -27,14 +27,6 @@ static int64_t map_row_bytes(void)
 // workgroups igd_map_rows is launched with for nq regions (each of IGD_SETS_WG / IGD_WAVE waves; a wave meets a second region
 // only when nq exceeds the grid's waves)
 extern "C" int32_t igd_hip_map_grid(int64_t nq) { return items_grid(nq, IGD_SETS_WG / IGD_WAVE); }
-
-// regions per chunk of the host forms
-static int64_t map_step(int64_t nF, bool withAgg)
-{
-    const int64_t byRows = map_row_bytes() / ((nF > 0 ? nF : 1) * (withAgg ? 12 : 4));
-    const int64_t step = max_batch();
-    return byRows < step ? (byRows < 1 ? 1 : byRows) : step;
-}
 
 // an unknown op, or an op that reads values on a database without them
 static int map_op_bad(const char *who, const igd_hip_db *db, int op)
@@ -116,21 +108,14 @@ extern "C" int igd_hip_map(igd_hip_db *db, const int32_t *ichr, const int32_t *q
     const int64_t nF = db->nFiles;
     if (nq == 0 || nF == 0) return IGD_HIP_OK;
     const bool withAgg = agg != nullptr;
-    const int64_t step = map_step(nF, withAgg);
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
-    for (int64_t c0 = 0; c0 < nq; c0 += step) {
-        const int64_t m = nq - c0 < step ? nq - c0 : step;
+    return run_region_chunks(db, ichr, qs, qe, nq, chunk_step(map_row_bytes(), nF * (withAgg ? 12 : 4)), [&](int64_t c0, int64_t m, hipStream_t st) {
         int rc = ensure_map_ws(db, m * nF, withAgg);
-        if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
         if (rc == IGD_HIP_OK) rc = igd_hip_map_dev(db, db->d_qc, db->d_qs, db->d_qe, m, op, v, db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, st);
         if (rc != IGD_HIP_OK) return rc;
         HIPCHK(hipMemcpyAsync(count + c0 * nF, db->d_mpCount, (size_t)(m * nF) * 4, hipMemcpyDeviceToHost, st));
         if (withAgg) HIPCHK(hipMemcpyAsync(agg + c0 * nF, db->d_mpAgg, (size_t)(m * nF) * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-    }
-    return IGD_HIP_OK;
+        return IGD_HIP_OK;
+    });
 }
 
 extern "C" int igd_hip_map_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
@@ -151,46 +136,12 @@ extern "C" int igd_hip_map_sets(igd_hip_db *db, const int32_t *ichr, const int32
         return IGD_HIP_OK;
     }
     const bool withAgg = op != IGD_HIP_MAP_COUNT;
-    const int64_t step = map_step(nF, withAgg);
-    const int64_t rowCap = sets_row_bytes() / (3 * nF * 8) > 0 ? sets_row_bytes() / (3 * nF * 8) : 1;
-    const int gx = (int)((nF + IGD_WAVE - 1) / IGD_WAVE);
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
-    std::vector<SetSlice> slices;
-    for (int32_t k0 = 0; k0 < nsets;) {
-        // one group: sets [k0, k1), regions [set_off[k0], set_off[k1])
-        const int32_t k1 = (int32_t)(nsets - k0 < rowCap ? nsets : k0 + rowCap);
-        const int64_t rows = k1 - k0, matWords = rows * nF;
-        if ((rc = dev_grow(db, &db->d_mpStat, &db->mpStatCap, 3 * matWords)) != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemsetAsync(db->d_mpStat, 0, (size_t)(3 * matWords) * 8, st));
-        int32_t k = k0;
-        for (int64_t c0 = set_off[k0]; c0 < set_off[k1]; c0 += step) {
-            const int64_t m = set_off[k1] - c0 < step ? set_off[k1] - c0 : step;
-            // the chunk's part of every set it meets, in slices of at most IGD_MAP_SLICE regions
-            slices.clear();
-            while (set_off[k + 1] <= c0) k++;
-            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++) {
-                const int64_t a0 = set_off[j] > c0 ? set_off[j] : c0, b0 = set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m;
-                for (int64_t a = a0; a < b0; a += IGD_MAP_SLICE)
-                    slices.push_back(SetSlice{j - k0, (int32_t)(a - c0), (int32_t)((a + IGD_MAP_SLICE < b0 ? a + IGD_MAP_SLICE : b0) - c0), 0});
-            }
-            const int ns = (int)slices.size();
-            rc = ensure_map_ws(db, m * nF, withAgg);
-            if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_mpSlices, &db->mpSliceCap, (int64_t)ns);
-            if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
-            if (rc == IGD_HIP_OK) rc = igd_hip_map_dev(db, db->d_qc, db->d_qs, db->d_qe, m, op, v, db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, st);
-            if (rc != IGD_HIP_OK) return rc;
-            HIPCHK(hipMemcpyAsync(db->d_mpSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-            igd_map_reduce<<<dim3((unsigned)gx, (unsigned)reduce_grid_y(gx, ns)), IGD_SETS_WG, 0, st>>>(db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, (int)nF, db->d_mpSlices,
-                                                                                  ns, (u64 *)db->d_mpStat, matWords);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
-        }
-        for (int i = 0; i < 3; i++)
-            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * nF, db->d_mpStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        k0 = k1;
-    }
-    return IGD_HIP_OK;
+    return run_set_groups(db, ichr, qs, qe, set_off, nsets, chunk_step(map_row_bytes(), nF * (withAgg ? 12 : 4)), IGD_MAP_SLICE, 3, nF, outs, nF,
+                          [&](dim3 grid, int ns, int64_t rows, int64_t m, hipStream_t st) {
+        int rc2 = ensure_map_ws(db, m * nF, withAgg);
+        if (rc2 == IGD_HIP_OK) rc2 = igd_hip_map_dev(db, db->d_qc, db->d_qs, db->d_qe, m, op, v, db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, st);
+        if (rc2 != IGD_HIP_OK) return rc2;
+        igd_map_reduce<<<grid, IGD_SETS_WG, 0, st>>>(db->d_mpCount, withAgg ? db->d_mpAgg : nullptr, (int)nF, db->d_grpSlices, ns, (u64 *)db->d_grpStat, rows * nF);
+        return IGD_HIP_OK;
+    });
 }

@@ -4,9 +4,9 @@
 // The device form takes one engine batch of resident queries and writes resident rows: one launch (the wide form: a memset
 // of the rows before it and, when nfiles_hit is wanted, igd_member_popc behind it), asynchronous on the caller's stream.
 // The host form takes host arrays in CHUNKS of at most igd_hip_max_batch() queries AND at most IGD_MEMBER_ROW_BYTES of
-// device rows (a database of 10^6 files has 125 KB rows: 2^24 of them would be 2 TB); per chunk the queries go to the
-// device through the staging buffers of igd_hip_search (ensure_qstage), the device form runs on the engine's stream and the
-// rows come back into the caller's array at their place -- rows are per query, so chunks need no merging.
+// device rows (a database of 10^6 files has 125 KB rows: 2^24 of them would be 2 TB; chunk_step); run_region_chunks
+// (host_common.hpp) stages the queries of a chunk, the body here runs the device form on the engine's stream and sends the
+// rows back into the caller's array at their place -- rows are per query, so chunks need no merging.
 // The image and the rule word are igd_hip_support_sets's (slice_image, host_common.hpp).
 #define IGD_MEMBER_ROW_BYTES ((int64_t)256 << 20)    // device rows of one chunk (of the order of IGD_SETS_ROW_BYTES)
 
@@ -78,30 +78,23 @@ extern "C" int igd_hip_membership(igd_hip_db *db, const int32_t *ichr, const int
         if (nfiles_hit) memset(nfiles_hit, 0, (size_t)nq * 4);
         return IGD_HIP_OK;
     }
-    const int64_t byRows = member_row_bytes() / (nW * 4);
-    int64_t step = max_batch();
-    if (byRows < step) step = byRows < 1 ? 1 : byRows;
-
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
-    int64_t hit = 0;
-    for (int64_t c0 = 0; c0 < nq; c0 += step) {
-        const int64_t m = nq - c0 < step ? nq - c0 : step;
-        int rc = ensure_member_ws(db, m * nW, m);
-        if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
-        if (rc != IGD_HIP_OK) return rc;
+    // the hit counter is per chunk: zeroed before the launch, copied out behind it, and the chunks' counts are added once the
+    // driver has waited for the last of them
+    const int64_t step = chunk_step(member_row_bytes(), nW * 4);
+    std::vector<unsigned long long> hs((size_t)((nq + step - 1) / step), 0);
+    const int rc = run_region_chunks(db, ichr, qs, qe, nq, step, [&](int64_t c0, int64_t m, hipStream_t st) {
+        int rc2 = ensure_member_ws(db, m * nW, m);
+        if (rc2 != IGD_HIP_OK) return rc2;
         HIPCHK(hipMemsetAsync(db->d_memHit, 0, 8, st));
-        rc = igd_hip_membership_dev(db, db->d_qc, db->d_qs, db->d_qe, m, v, rule, db->d_memBits, nfiles_hit ? db->d_memNf : nullptr,
-                                    (int64_t *)db->d_memHit, st);
-        if (rc != IGD_HIP_OK) return rc;
-        unsigned long long h = 0;
+        rc2 = igd_hip_membership_dev(db, db->d_qc, db->d_qs, db->d_qe, m, v, rule, db->d_memBits, nfiles_hit ? db->d_memNf : nullptr,
+                                     (int64_t *)db->d_memHit, st);
+        if (rc2 != IGD_HIP_OK) return rc2;
         HIPCHK(hipMemcpyAsync(bits + c0 * nW, db->d_memBits, (size_t)(m * nW) * 4, hipMemcpyDeviceToHost, st));
         if (nfiles_hit) HIPCHK(hipMemcpyAsync(nfiles_hit + c0, db->d_memNf, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&h, db->d_memHit, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        hit += (int64_t)h;
-    }
-    if (nhit) *nhit += hit;
+        HIPCHK(hipMemcpyAsync(&hs[(size_t)(c0 / step)], db->d_memHit, 8, hipMemcpyDeviceToHost, st));
+        return IGD_HIP_OK;
+    });
+    if (rc != IGD_HIP_OK) return rc;
+    if (nhit) for (unsigned long long h : hs) *nhit += (int64_t)h;
     return IGD_HIP_OK;
 }

@@ -6,16 +6,16 @@
 // The device form takes one engine batch of resident regions and writes resident rows: one launch (the wide form: a fill of
 // the rows with 0xff before it and, when dmin is wanted, igd_nearest_rowmin behind it), asynchronous on the caller's stream.
 // The host form takes host arrays in CHUNKS of at most igd_hip_max_batch() regions AND at most IGD_NEAREST_ROW_BYTES of device
-// rows (4 nFiles bytes per region: 7.6 KB at 1 900 files, 35 000 regions per chunk); per chunk the regions go to the device
-// through the staging buffers of igd_hip_search, the device form runs on the engine's stream and the rows come back into the
-// caller's arrays at their place.
-// The sets form takes GROUPS of whole sets whose three result rows (3 x (nFiles + 1) x 8 bytes per set) fit sets_row_bytes();
-// the regions of a group go through in the same chunks -- a set may be cut by a chunk, its statistics are sums over regions --
-// and per chunk igd_nearest_reduce adds the rows into the group's three resident matrices, by a slice table cut here: a slice
-// is at most IGD_NEAREST_SLICE regions of one set.  The rows never leave the device; the matrices are copied out once per group.
-// The signed forms are the same bodies (nearest_rows_dev, nearest_rows_host; nearest_set_groups with its row kernel) with SIGNED = true:
-// the rows hold signed distances, the wide form's second kernel is igd_nearest_rowdecode and always runs, and the group driver's
-// reduction is igd_nearest_hist into ONE resident matrix of (ne + 1) x (nFiles + 1) words per set, with the slices cut as for
+// rows (4 nFiles bytes per region: 7.6 KB at 1 900 files, 35 000 regions per chunk: chunk_step); run_region_chunks
+// (host_common.hpp) stages the regions of a chunk, the body here runs the device form on the engine's stream and sends the rows
+// back into the caller's arrays at their place.
+// The sets form is run_set_groups (below; also the driver of host_flank.hpp, host_map.hpp, host_permute_nearest.hpp): GROUPS of whole sets whose three result rows (3 x (nFiles + 1) x 8 bytes
+// per set) fit sets_row_bytes(), the regions of a group in the same chunks, a slice table of at most IGD_NEAREST_SLICE regions
+// of one set per slice; the chunk functor here launches the row kernel and igd_nearest_reduce, which adds the rows into the
+// group's three resident matrices.  The rows never leave the device.
+// The signed forms are the same bodies (nearest_rows_dev, nearest_rows_host; the same chunk functor) with SIGNED = true: the
+// rows hold signed distances, the wide form's second kernel is igd_nearest_rowdecode and always runs, and the reduction is
+// igd_nearest_hist into ONE resident matrix of (ne + 1) x (nFiles + 1) words per set, with the slices cut as for
 // igd_nearest_reduce: at most IGD_NEAREST_SLICE = 256 regions, so the kernel's u32 LDS counters hold at most 256.
 // The image is slice_image(db, IGD_HIP_RULE_FLAT, v): the re-tiled copy when there is one, visited under rule FLAT.
 #define IGD_NEAREST_ROW_BYTES ((int64_t)256 << 20)   // device rows of one chunk (of the order of IGD_MEMBER_ROW_BYTES)
@@ -32,14 +32,6 @@ static int64_t nearest_row_bytes(void)
 // workgroups igd_nearest_rows is launched with for nq regions (each of IGD_SETS_WG / IGD_WAVE waves; a wave meets a second
 // region only when nq exceeds the grid's waves)
 extern "C" int32_t igd_hip_nearest_grid(int64_t nq) { return items_grid(nq, IGD_SETS_WG / IGD_WAVE); }
-
-// regions per chunk of the host forms (nRows rows of nF words per region: two in host_flank.hpp)
-static int64_t nearest_step(int64_t nF, int nRows = 1)
-{
-    const int64_t byRows = nearest_row_bytes() / ((nF > 0 ? nF : 1) * 4 * nRows);
-    const int64_t step = max_batch();
-    return byRows < step ? (byRows < 1 ? 1 : byRows) : step;
-}
 
 static int nearest_window_bad(const char *who, int32_t window)
 {
@@ -124,21 +116,14 @@ static int nearest_rows_host(const char *who, igd_hip_db *db, const int32_t *ich
         if (dmin && SIGNED) for (int64_t i = 0; i < nq; i++) dmin[i] = IGD_HIP_NEAREST_NO_RECORD;
         return IGD_HIP_OK;
     }
-    const int64_t step = nearest_step(nF);
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
-    for (int64_t c0 = 0; c0 < nq; c0 += step) {
-        const int64_t m = nq - c0 < step ? nq - c0 : step;
+    return run_region_chunks(db, ichr, qs, qe, nq, chunk_step(nearest_row_bytes(), nF * 4), [&](int64_t c0, int64_t m, hipStream_t st) {
         int rc = ensure_nearest_ws(db, m * nF, m);
-        if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
         if (rc == IGD_HIP_OK) rc = nearest_rows_dev<SIGNED>(who, db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, dmin ? db->d_nrMin : nullptr, st);
         if (rc != IGD_HIP_OK) return rc;
         HIPCHK(hipMemcpyAsync(dist + c0 * nF, db->d_nrDist, (size_t)(m * nF) * 4, hipMemcpyDeviceToHost, st));
         if (dmin) HIPCHK(hipMemcpyAsync(dmin + c0, db->d_nrMin, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-    }
-    return IGD_HIP_OK;
+        return IGD_HIP_OK;
+    });
 }
 
 extern "C" int igd_hip_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t window,
@@ -153,22 +138,23 @@ extern "C" int igd_hip_nearest_signed(igd_hip_db *db, const int32_t *ichr, const
     return nearest_rows_host<true>("igd_hip_nearest_signed", db, ichr, qs, qe, nq, window, v, sdist, sdmin);
 }
 
-// The group and chunk driver of igd_hip_nearest_sets, igd_hip_nearest_hist and igd_hip_flank_reldist (the arguments are
-// checked, there are regions and files).  Per set there are nMat result rows of matRow 64-bit words, kept in d_nrStat as nMat
-// matrices of rows x matRow words: whole sets are taken while they fit sets_row_bytes(); their regions go through in chunks of
-// `step` regions -- fill(m, st) launches the row kernel over the m staged regions of a chunk, whose nRows rows per region (one:
-// the (signed) distances; two: the flanks) and as many minima stay in d_nrDist / d_nrMin, row after row -- and reduce(grid, ns,
-// rows, m, st) launches the kernel that adds the chunk's rows into the matrices by the slice table in d_nrSlices; matrix i is
-// copied out to outs[i] (may be NULL) once per group.
-template <typename Fill, typename Reduce>
-static int nearest_set_groups(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
-                              int32_t nsets, int64_t step, int nRows, int nMat, int64_t matRow, int64_t *const *outs, Fill &&fill,
-                              Reduce &&reduce)
+// The group driver of the resident set statistics: igd_hip_nearest_sets, igd_hip_nearest_hist, igd_hip_flank_reldist,
+// igd_hip_map_sets and igd_hip_nearest_sets_fused (the arguments are checked, there are regions and files).  Per set there are
+// nMat result rows of matRow 64-bit words, kept in d_grpStat as nMat matrices of rows x matRow words: GROUPS of whole sets are
+// taken while they fit sets_row_bytes(); their regions go through in chunks of `step` regions -- a set may be cut by a chunk,
+// its statistics are sums over regions.  Per chunk the regions go to the staging buffers, the chunk's part of every set it
+// meets is cut into slices of at most sliceLen regions (0: sets_slice_len(chunk)), the table goes to d_grpSlices, and
+// chunk(grid, ns, rows, m, st) sees to its own row workspace and launches its kernels, which add the chunk into the matrices:
+// grid is that of a reduction over nCols columns and ns slices (reduce_grid_y), rows the sets of the group, m the regions of
+// the chunk.  Then the stream is waited for (the slice table is the host's vector; the staging buffers are reused).  Matrix i
+// is copied out to outs[i] (may be NULL) once per group.
+template <typename Chunk>
+static int run_set_groups(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                          int64_t step, int64_t sliceLen, int nMat, int64_t matRow, int64_t *const *outs, int64_t nCols, Chunk &&chunk)
 {
     int rc;
-    const int64_t nF = db->nFiles, nC = nF + 1;
     const int64_t rowCap = sets_row_bytes() / (nMat * matRow * 8) > 0 ? sets_row_bytes() / (nMat * matRow * 8) : 1;
-    const int gx = (int)((nC + IGD_WAVE - 1) / IGD_WAVE);
+    const int gx = (int)((nCols + IGD_WAVE - 1) / IGD_WAVE);
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
     std::vector<SetSlice> slices;
@@ -176,32 +162,27 @@ static int nearest_set_groups(igd_hip_db *db, const int32_t *ichr, const int32_t
         // one group: sets [k0, k1), regions [set_off[k0], set_off[k1])
         const int32_t k1 = (int32_t)(nsets - k0 < rowCap ? nsets : k0 + rowCap);
         const int64_t rows = k1 - k0, matWords = rows * matRow;
-        if ((rc = dev_grow(db, &db->d_nrStat, &db->nrStatCap, nMat * matWords)) != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemsetAsync(db->d_nrStat, 0, (size_t)(nMat * matWords) * 8, st));
+        if ((rc = dev_grow(db, &db->d_grpStat, &db->grpStatCap, nMat * matWords)) != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemsetAsync(db->d_grpStat, 0, (size_t)(nMat * matWords) * 8, st));
         int32_t k = k0;
         for (int64_t c0 = set_off[k0]; c0 < set_off[k1]; c0 += step) {
             const int64_t m = set_off[k1] - c0 < step ? set_off[k1] - c0 : step;
-            // the chunk's part of every set it meets, in slices of at most IGD_NEAREST_SLICE regions
+            const int64_t len = sliceLen ? sliceLen : sets_slice_len(m);
             slices.clear();
             while (set_off[k + 1] <= c0) k++;
-            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++) {
-                const int64_t a0 = set_off[j] > c0 ? set_off[j] : c0, b0 = set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m;
-                for (int64_t a = a0; a < b0; a += IGD_NEAREST_SLICE)
-                    slices.push_back(SetSlice{j - k0, (int32_t)(a - c0), (int32_t)((a + IGD_NEAREST_SLICE < b0 ? a + IGD_NEAREST_SLICE : b0) - c0), 0});
-            }
+            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++)
+                push_slices(slices, j - k0, set_off[j] > c0 ? set_off[j] : c0, set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m, len, c0);
             const int ns = (int)slices.size();
-            rc = ensure_nearest_ws(db, nRows * m * nF, nRows * m);
-            if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
+            rc = dev_grow(db, &db->d_grpSlices, &db->grpSliceCap, (int64_t)ns);
             if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
-            if (rc == IGD_HIP_OK) rc = fill(m, st);
             if (rc != IGD_HIP_OK) return rc;
-            HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-            reduce(dim3((unsigned)gx, (unsigned)reduce_grid_y(gx, ns)), ns, rows, m, st);
+            HIPCHK(hipMemcpyAsync(db->d_grpSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+            if ((rc = chunk(dim3((unsigned)gx, (unsigned)reduce_grid_y(gx, ns)), ns, rows, m, st)) != IGD_HIP_OK) return rc;
             HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
+            HIPCHK(hipStreamSynchronize(st));
         }
         for (int i = 0; i < nMat; i++)
-            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * matRow, db->d_nrStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
+            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * matRow, db->d_grpStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
         k0 = k1;
@@ -226,10 +207,13 @@ extern "C" int igd_hip_nearest_sets(igd_hip_db *db, const int32_t *ichr, const i
         for (int64_t *o : outs) if (o) memset(o, 0, (size_t)nsets * (size_t)nC * 8);
         return IGD_HIP_OK;
     }
-    return nearest_set_groups(db, ichr, qs, qe, set_off, nsets, nearest_step(nF), 1, 3, nC, outs, [&](int64_t m, hipStream_t st) {
-        return nearest_rows_dev<false>("igd_hip_nearest_sets", db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
-    }, [&](dim3 grid, int ns, int64_t rows, int64_t, hipStream_t st) {
-        igd_nearest_reduce<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns, (u64 *)db->d_nrStat, rows * nC);
+    return run_set_groups(db, ichr, qs, qe, set_off, nsets, chunk_step(nearest_row_bytes(), nF * 4), IGD_NEAREST_SLICE, 3, nC, outs, nC,
+                          [&](dim3 grid, int ns, int64_t rows, int64_t m, hipStream_t st) {
+        int rc2 = ensure_nearest_ws(db, m * nF, m);
+        if (rc2 == IGD_HIP_OK) rc2 = nearest_rows_dev<false>("igd_hip_nearest_sets", db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
+        if (rc2 != IGD_HIP_OK) return rc2;
+        igd_nearest_reduce<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_grpSlices, ns, (u64 *)db->d_grpStat, rows * nC);
+        return IGD_HIP_OK;
     });
 }
 
@@ -257,9 +241,12 @@ extern "C" int igd_hip_nearest_hist(igd_hip_db *db, const int32_t *ichr, const i
     if ((rc = dev_grow(db, &db->d_nrEdges, &db->nrEdgesCap, (int64_t)IGD_HIP_NEAREST_MAX_EDGES)) != IGD_HIP_OK) return rc;
     HIPCHK(hipMemcpyAsync(db->d_nrEdges, edges, (size_t)ne * 4, hipMemcpyHostToDevice, db->stream));
     int64_t *outs[1] = {hist};
-    return nearest_set_groups(db, ichr, qs, qe, set_off, nsets, nearest_step(nF), 1, 1, matRow, outs, [&](int64_t m, hipStream_t st) {
-        return nearest_rows_dev<true>("igd_hip_nearest_hist", db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
-    }, [&](dim3 grid, int ns, int64_t, int64_t, hipStream_t st) {
-        igd_nearest_hist<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns, db->d_nrEdges, (int)ne, (u64 *)db->d_nrStat);
+    return run_set_groups(db, ichr, qs, qe, set_off, nsets, chunk_step(nearest_row_bytes(), nF * 4), IGD_NEAREST_SLICE, 1, matRow, outs, nC,
+                          [&](dim3 grid, int ns, int64_t, int64_t m, hipStream_t st) {
+        int rc2 = ensure_nearest_ws(db, m * nF, m);
+        if (rc2 == IGD_HIP_OK) rc2 = nearest_rows_dev<true>("igd_hip_nearest_hist", db, db->d_qc, db->d_qs, db->d_qe, m, window, v, db->d_nrDist, db->d_nrMin, st);
+        if (rc2 != IGD_HIP_OK) return rc2;
+        igd_nearest_hist<<<grid, IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_grpSlices, ns, db->d_nrEdges, (int)ne, (u64 *)db->d_grpStat);
+        return IGD_HIP_OK;
     });
 }

@@ -120,9 +120,7 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
     const int64_t maxGrid = support_max_grid(db);
     std::vector<SetSlice> slices;
     slices.reserve((size_t)(pc * perRow));
-    for (int64_t r = 0; r < pc; r++)
-        for (int64_t a = 0; a < nq; a += sliceLen)
-            slices.push_back(SetSlice{(int32_t)r, (int32_t)(r * nq + a), (int32_t)(r * nq + (a + sliceLen < nq ? a + sliceLen : nq)), 0});
+    for (int64_t r = 0; r < pc; r++) push_slices(slices, (int32_t)r, r * nq, (r + 1) * nq, sliceLen, 0);
 
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;

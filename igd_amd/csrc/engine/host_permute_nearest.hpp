@@ -2,10 +2,11 @@
 // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: the set statistics of the nearest record per dataset through
 // igd_nearest_slices (nearest_fused_dev.hpp), and their permutation null
 // ------------------------------------------------------------------------------------------
-// igd_hip_nearest_sets_fused has igd_hip_nearest_sets' contract (host_nearest.hpp): GROUPS of whole sets whose three result rows
-// fit sets_row_bytes(), their regions in chunks of igd_hip_max_batch() -- there are no distance rows, so no row budget --
-// every chunk's part of every set cut into slices of sets_slice_len(chunk) regions, ONE launch per chunk with
-// support_launch's grid rule, the three matrices copied out once per group.
+// igd_hip_nearest_sets_fused has igd_hip_nearest_sets' contract (host_nearest.hpp) and its driver, run_set_groups
+// (host_common.hpp): GROUPS of whole sets whose three result rows fit sets_row_bytes(), their regions in chunks of
+// igd_hip_max_batch() -- there are no distance rows, so no row budget and no row workspace -- every chunk's part of every set
+// cut into slices of sets_slice_len(chunk) regions, ONE launch per chunk with support_launch's grid rule, the three matrices
+// copied out once per group.
 // igd_hip_permute_nearest is igd_hip_permute_support_ov's driver (host_permute.hpp) with the three matrices as its rows: the
 // regions and ctg_len go up once (db->d_pmReg); the slice table has one row per permutation of a chunk, is built and
 // uploaded once, and a shorter last chunk uses its prefix; a chunk holds pc permutations with pc * nq <= igd_hip_max_batch()
@@ -17,7 +18,7 @@
 // Databases with more files than IGD_NEAREST_FUSED_LDS_FILES: the first calls igd_hip_nearest_sets; the second runs
 // igd_hip_nearest_dev + igd_nearest_reduce over the same staged regions (nearest_rows_reduce below), in pieces within the
 // row budget of igd_hip_nearest, with a wait per piece.  The results are the same integers.
-// The matrices and slice tables are igd_hip_nearest_sets' workspaces (db->d_nrStat, d_nrSlices).
+// The matrices and slice tables are the group driver's workspaces (db->d_grpStat, d_grpSlices).
 static_assert(IGD_SETS_SLICE_MAX < 65536, "igd_nearest_slices packs n_within and n_overlap of one slice into 16 bits each");
 
 extern "C" int32_t igd_hip_nearest_fused_max_files(void) { return IGD_NEAREST_FUSED_LDS_FILES; }
@@ -25,7 +26,7 @@ extern "C" int32_t igd_hip_nearest_fused_max_files(void) { return IGD_NEAREST_FU
 // workgroups igd_nearest_slices is launched with for nslices slices: a workgroup takes a second slice only past IGD_SETS_GRID
 extern "C" int32_t igd_hip_nearest_fused_grid(int64_t nslices) { return items_grid(nslices, 1); }
 
-// igd_nearest_slices over `ns` slices of the table at db->d_nrSlices into the matrices at db->d_nrStat
+// igd_nearest_slices over `ns` slices of the table at db->d_grpSlices into the matrices at db->d_grpStat
 static int nearest_fused_launch(igd_hip_db *db, const SliceImage &im, const int32_t *c, const int32_t *s, const int32_t *e, int ns,
                                 int32_t window, int32_t v, int64_t matWords)
 {
@@ -34,20 +35,13 @@ static int nearest_fused_launch(igd_hip_db *db, const SliceImage &im, const int3
     auto go = [&](auto V) {
         if (ldsB > (size_t)65536)                        // (more dynamic LDS than a launch gets unasked)
             (void)hipFuncSetAttribute((const void *)igd_nearest_slices<V()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsB);
-        igd_nearest_slices<V()><<<grid, IGD_SETS_WG, ldsB, db->stream>>>(im.view, c, s, e, db->d_nrSlices, ns, window, im.krule, v,
-                                                                        (u64 *)db->d_nrStat, matWords);
+        igd_nearest_slices<V()><<<grid, IGD_SETS_WG, ldsB, db->stream>>>(im.view, c, s, e, db->d_grpSlices, ns, window, im.krule, v,
+                                                                        (u64 *)db->d_grpStat, matWords);
     };
     if (im.useV) go(std::true_type{});
     else go(std::false_type{});
     HIPCHK(hipGetLastError());
     return IGD_HIP_OK;
-}
-
-// [a0, b0) of a staged array cut into slices of row `row`, at most `len` regions each, positions relative to `base`
-static void push_slices(std::vector<SetSlice> &slices, int32_t row, int64_t a0, int64_t b0, int64_t len, int64_t base)
-{
-    for (int64_t a = a0; a < b0; a += len)
-        slices.push_back(SetSlice{row, (int32_t)(a - base), (int32_t)((a + len < b0 ? a + len : b0) - base), 0});
 }
 
 extern "C" int igd_hip_nearest_sets_fused(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
@@ -70,49 +64,20 @@ extern "C" int igd_hip_nearest_sets_fused(igd_hip_db *db, const int32_t *ichr, c
         return IGD_HIP_OK;
     }
     const SliceImage im = slice_image(db, IGD_HIP_RULE_FLAT, v);
-    const int64_t step = max_batch();
-    const int64_t rowCap = sets_row_bytes() / (3 * nC * 8) > 0 ? sets_row_bytes() / (3 * nC * 8) : 1;
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
-    std::vector<SetSlice> slices;
-    for (int32_t k0 = 0; k0 < nsets;) {
-        // one group: sets [k0, k1), regions [set_off[k0], set_off[k1])
-        const int32_t k1 = (int32_t)(nsets - k0 < rowCap ? nsets : k0 + rowCap);
-        const int64_t rows = k1 - k0, matWords = rows * nC;
-        if ((rc = dev_grow(db, &db->d_nrStat, &db->nrStatCap, 3 * matWords)) != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemsetAsync(db->d_nrStat, 0, (size_t)(3 * matWords) * 8, st));
-        int32_t k = k0;
-        for (int64_t c0 = set_off[k0]; c0 < set_off[k1]; c0 += step) {
-            const int64_t m = set_off[k1] - c0 < step ? set_off[k1] - c0 : step;
-            const int64_t sliceLen = sets_slice_len(m);
-            slices.clear();
-            while (set_off[k + 1] <= c0) k++;
-            for (int32_t j = k; j < k1 && set_off[j] < c0 + m; j++)
-                push_slices(slices, j - k0, set_off[j] > c0 ? set_off[j] : c0, set_off[j + 1] < c0 + m ? set_off[j + 1] : c0 + m, sliceLen, c0);
-            const int ns = (int)slices.size();
-            rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
-            if (rc == IGD_HIP_OK) rc = stage_queries(db, ichr, qs, qe, c0, m);
-            if (rc != IGD_HIP_OK) return rc;
-            HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-            if ((rc = nearest_fused_launch(db, im, db->d_qc, db->d_qs, db->d_qe, ns, window, v, matWords)) != IGD_HIP_OK) return rc;
-            HIPCHK(hipStreamSynchronize(st));            // (the slice table is the host's vector; the staging buffers are reused)
-        }
-        for (int i = 0; i < 3; i++)
-            if (outs[i]) HIPCHK(hipMemcpyAsync(outs[i] + (int64_t)k0 * nC, db->d_nrStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        k0 = k1;
-    }
-    return IGD_HIP_OK;
+    // (slice length 0: sets_slice_len(chunk); the kernel has a grid rule of its own, nearest_fused_launch)
+    return run_set_groups(db, ichr, qs, qe, set_off, nsets, max_batch(), 0, 3, nC, outs, nC, [&](dim3, int ns, int64_t rows, int64_t, hipStream_t) {
+        return nearest_fused_launch(db, im, db->d_qc, db->d_qs, db->d_qe, ns, window, v, rows * nC);
+    });
 }
 
 // Databases too wide for igd_nearest_slices: `rows` rows of nq resident regions each (c, s, e; row r = regions [r nq, (r + 1) nq))
-// through igd_hip_nearest_dev and igd_nearest_reduce into the matrices at db->d_nrStat, in pieces of nearest_step() regions --
-// a piece may cut a row, the statistics are sums over regions -- with slices of IGD_NEAREST_SLICE and a wait per piece.
+// through igd_hip_nearest_dev and igd_nearest_reduce into the matrices at db->d_grpStat, in pieces of igd_hip_nearest's chunk_step()
+// regions -- a piece may cut a row, the statistics are sums over regions -- with slices of IGD_NEAREST_SLICE and a wait per
+// piece.  (The chunk body of run_set_groups over RESIDENT regions cut by nq, not staged ones cut by set_off: it stays its own loop.)
 static int nearest_rows_reduce(igd_hip_db *db, const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows, int64_t nq,
                                int32_t window, int32_t v, int64_t matWords)
 {
-    const int64_t nF = db->nFiles, nC = nF + 1, total = rows * nq, step = nearest_step(nF);
+    const int64_t nF = db->nFiles, nC = nF + 1, total = rows * nq, step = chunk_step(nearest_row_bytes(), nF * 4);
     const int gx = (int)((nC + IGD_WAVE - 1) / IGD_WAVE);
     hipStream_t st = db->stream;
     std::vector<SetSlice> slices;
@@ -123,12 +88,12 @@ static int nearest_rows_reduce(igd_hip_db *db, const int32_t *c, const int32_t *
             push_slices(slices, (int32_t)r, r * nq > c0 ? r * nq : c0, (r + 1) * nq < c0 + m ? (r + 1) * nq : c0 + m, IGD_NEAREST_SLICE, c0);
         const int ns = (int)slices.size();
         int rc = ensure_nearest_ws(db, m * nF, m);
-        if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, (int64_t)ns);
+        if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_grpSlices, &db->grpSliceCap, (int64_t)ns);
         if (rc == IGD_HIP_OK) rc = igd_hip_nearest_dev(db, c + c0, s + c0, e + c0, m, window, v, db->d_nrDist, db->d_nrMin, st);
         if (rc != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-        igd_nearest_reduce<<<dim3((unsigned)gx, (unsigned)reduce_grid_y(gx, ns)), IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_nrSlices, ns,
-                                                                                  (u64 *)db->d_nrStat, matWords);
+        HIPCHK(hipMemcpyAsync(db->d_grpSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+        igd_nearest_reduce<<<dim3((unsigned)gx, (unsigned)reduce_grid_y(gx, ns)), IGD_SETS_WG, 0, st>>>(db->d_nrDist, db->d_nrMin, (int)nF, db->d_grpSlices, ns,
+                                                                                  (u64 *)db->d_grpStat, matWords);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));                // (the slice table is the host's vector)
     }
@@ -188,26 +153,26 @@ extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, cons
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
     int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + db->nCtg);
-    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_nrStat, &db->nrStatCap, 3 * pc * nC);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_grpStat, &db->grpStatCap, 3 * pc * nC);
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
-    if (rc == IGD_HIP_OK && fused) rc = dev_grow(db, &db->d_nrSlices, &db->nrSliceCap, pc * perRow);
+    if (rc == IGD_HIP_OK && fused) rc = dev_grow(db, &db->d_grpSlices, &db->grpSliceCap, pc * perRow);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
     HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)db->nCtg * 4, hipMemcpyHostToDevice, st));
-    if (fused) HIPCHK(hipMemcpyAsync(db->d_nrSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
+    if (fused) HIPCHK(hipMemcpyAsync(db->d_grpSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
 
     // `rows` rows counted from the region arrays (c, s, e) into zeroed matrices, which go to rows [r0, r0 + rows) of res
     auto count = [&](const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows, int64_t r0) -> int {
         const int64_t matWords = rows * nC;
-        HIPCHK(hipMemsetAsync(db->d_nrStat, 0, (size_t)(3 * matWords) * 8, st));
+        HIPCHK(hipMemsetAsync(db->d_grpStat, 0, (size_t)(3 * matWords) * 8, st));
         const int rc2 = fused ? nearest_fused_launch(db, im, c, s, e, (int)(rows * perRow), window, v, matWords)
                               : nearest_rows_reduce(db, c, s, e, rows, nq, window, v, matWords);
         if (rc2 != IGD_HIP_OK) return rc2;
         for (int i = 0; i < 3; i++)
-            HIPCHK(hipMemcpyAsync(res.data() + (i * R + r0) * nC, db->d_nrStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(res.data() + (i * R + r0) * nC, db->d_grpStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
 

@@ -335,21 +335,24 @@ struct igd_hip_db {
     int32_t *d_pmReg;
     long long *d_pmStat;
     int64_t pmRegCap, pmStatCap;
-    // igd_hip_nearest / igd_hip_nearest_sets (host_nearest.hpp): the distance rows and dmin[] of one chunk of regions, the three
-    // matrices of one group of sets (64-bit words) and the slice table of igd_nearest_reduce
+    // run_set_groups (host_nearest.hpp), the driver of igd_hip_nearest_sets(_fused), igd_hip_nearest_hist, igd_hip_flank_reldist and
+    // igd_hip_map_sets: the result matrices of one group of sets (64-bit words) and the slice table of one chunk.  One pair for
+    // all of them: every user runs on `stream` and waits before it returns.  igd_hip_permute_nearest keeps its chunk's matrices
+    // and its slice table here too
+    int64_t *d_grpStat;
+    struct SetSlice *d_grpSlices;
+    int64_t grpStatCap, grpSliceCap;
+    // igd_hip_nearest / igd_hip_nearest_sets (host_nearest.hpp), igd_hip_flank (host_flank.hpp): the distance rows and dmin[] of one
+    // chunk of regions
     int32_t *d_nrDist, *d_nrMin;
-    int64_t *d_nrStat;
-    struct SetSlice *d_nrSlices;
-    int64_t nrDistCap, nrMinCap, nrStatCap, nrSliceCap;
-    // igd_hip_nearest_hist: the edges on the device (the resident histogram of one group of sets lives in d_nrStat)
+    int64_t nrDistCap, nrMinCap;
+    // igd_hip_nearest_hist: the edges on the device
     int32_t *d_nrEdges;
     int64_t nrEdgesCap;
-    // igd_hip_map / igd_hip_map_sets (host_map.hpp): the count and agg rows of one chunk of regions, the three matrices of one
-    // group of sets (64-bit words) and the slice table of igd_map_reduce
+    // igd_hip_map / igd_hip_map_sets (host_map.hpp): the count and agg rows of one chunk of regions
     int32_t *d_mpCount;
-    int64_t *d_mpAgg, *d_mpStat;
-    struct SetSlice *d_mpSlices;
-    int64_t mpCountCap, mpAggCap, mpStatCap, mpSliceCap;
+    int64_t *d_mpAgg;
+    int64_t mpCountCap, mpAggCap;
     // igd_hip_merge_sets / _dev (host_merge.hpp): every array of one merge, carved from one allocation (bytes)
     char *d_merge;
     int64_t mergeCap;
@@ -410,20 +413,20 @@ struct igd_hip_db {
 #include "engine/host_enumerate.hpp"  // `-f` on the host side: chunked, double-buffered
 #include "engine/seqpare.hpp"         // Seqpare `-s`: kernels and host
 #include "engine/host_misc.hpp"       // igd_hip_hitmap, igd_hip_batch_stats
-#include "engine/host_common.hpp"     // shared by the parts below: dev_grow, stage_queries, slice_image, sets_check, with_flags, run_set_chunks
+#include "engine/host_common.hpp"     // shared by the parts below: dev_grow, stage_queries, chunk_step, push_slices, slice_image, sets_check, with_flags; the drivers run_region_chunks and run_set_chunks
 #include "engine/host_sets.hpp"       // igd_hip_search_sets: chunks of sets, small ones sliced, large ones through the batch pipeline
 #include "engine/host_support.hpp"    // igd_hip_support_sets: chunks of sets, all of them sliced
 #include "engine/host_coverage.hpp"   // igd_hip_coverage_sets: chunks of sets, all of them sliced
-#include "engine/host_member.hpp"     // igd_hip_membership / _dev: chunks of queries within a row budget, one launch each
+#include "engine/host_member.hpp"     // igd_hip_membership / _dev: a body of run_region_chunks, chunks of queries within a row budget, one launch each
 #include "engine/host_enrich.hpp"     // igd_hip_fisher_tables / igd_hip_enrich_sets: chunks of cells, one launch each
 #include "engine/host_rank.hpp"       // igd_hip_enrich_ranks: chunks of whole rows, one launch each
 #include "engine/host_restrict.hpp"   // igd_hip_restrict_sets / igd_hip_enrich_restricted: chunks of sets x chunks of the universe
 #include "engine/host_cooccur.hpp"    // igd_hip_cooccur / igd_hip_bits_transpose / igd_hip_bitrows_gram: chunks of regions, rows stay resident
 #include "engine/host_permute.hpp"    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: chunks of permutations, rows stay resident
-#include "engine/host_nearest.hpp"    // igd_hip_nearest / _dev / _sets, _signed / _signed_dev / _hist: chunks of regions within a row budget, the set statistics stay resident
-#include "engine/host_flank.hpp"      // igd_hip_flank / _dev / _reldist: the chunks and groups of host_nearest.hpp with two rows per region
-#include "engine/host_permute_nearest.hpp" // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: one fused launch per chunk, the null distribution of the distance statistics
-#include "engine/host_map.hpp"        // igd_hip_map / _dev / _sets: chunks of regions within a row budget, the set statistics stay resident
+#include "engine/host_nearest.hpp"    // igd_hip_nearest / _dev / _sets, _signed / _signed_dev / _hist: a body of run_region_chunks; run_set_groups, the group driver of every resident set statistic, and its chunk functors
+#include "engine/host_flank.hpp"      // igd_hip_flank / _dev / _reldist: the same two drivers with two rows per region
+#include "engine/host_permute_nearest.hpp" // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: run_set_groups with one fused launch per chunk, the null distribution of the distance statistics
+#include "engine/host_map.hpp"        // igd_hip_map / _dev / _sets: the same two drivers, the set statistics stay resident
 #include "engine/host_merge.hpp"      // igd_hip_merge_sets / _dev, igd_hip_dataset_bp, igd_hip_jaccard_sets: device merge, merged base pairs per dataset, the intersection table
 #include "engine/host_permute_bp.hpp" // igd_hip_permute_bp: chunks of permutations, merged and covered without a host copy in between
 #include "engine/host_selftest.hpp"   // TEST-ONLY: igd_hip_test_exclusive_scan / igd_hip_test_radix_sort_pairs: igd_sortscan.hpp on host arrays, guard bytes behind every device array

@@ -231,6 +231,60 @@ def test_calls_straddle_the_chunk_seams(env):
     assert p.returncode == 0 and p.stdout.strip().endswith(b"ok"), p.stderr.decode()[-2000:]
 
 
+SHARED = r"""
+import os, random, sys
+import numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from helpers import short_tmpdir
+import map_ref as R
+import nearest_ref as NR
+import flank_ref as F
+from igd_amd import Database
+d = short_tmpdir("igk")
+rng = random.Random(13)
+nbp = 1 << 12
+files, span = R.clustered_lists(rng, nbp, 40, 2, 20, min_value=-300)
+ldb = R.ListDb(d, "b", files, nbp, 1)
+db = Database(ldb.path)
+sizes = [0, 1, 5, 700, 0, 1100, 3]
+off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+ichr, qs, qe = R.mixed_regions(rng, 2, nbp, span, int(off[-1]))
+W, B, G = nbp, 7, 0x5a5a5a5a5a5a5a5a
+def garbage(*shape):
+    return np.full(shape, G, np.int64)
+def map_sets(op):
+    ms = db.map_sets(ichr, qs, qe, off, op, out=[garbage(len(sizes), 40) for _ in range(3)])
+    for got, ref in zip(ms[:3], R.ref_sets(*R.ref_rows(ldb, ichr, qs, qe, op), off)):
+        assert np.array_equal(got, ref), op
+    return [a.copy() for a in ms[:3]]
+nref = NR.ref_sets(*NR.ref_rows(ldb, ichr, qs, qe, W), off)
+first = map_sets("sum")
+ns = db.nearest_sets(ichr, qs, qe, off, W, out=[garbage(len(sizes), 41) for _ in range(3)])
+assert all(np.array_equal(got, ref) for got, ref in zip(ns[:3], nref)), "nearest_sets"
+map_sets("count")
+fr = db.flank_reldist(ichr, qs, qe, off, W, B, measure=F.EDGES, hist=garbage(len(sizes), B, 41))
+assert np.array_equal(fr.hist, F.ref_hist(*F.ref_flanks(ldb, ichr, qs, qe, W, F.EDGES), off, B)), "flank_reldist"
+nf = db.nearest_sets_fused(ichr, qs, qe, off, W, out=[garbage(len(sizes), 41) for _ in range(3)])
+assert all(np.array_equal(got, ref) for got, ref in zip(nf[:3], nref)), "nearest_sets_fused"
+last = map_sets("sum")
+assert all(np.array_equal(a, b) for a, b in zip(first, last))
+assert first[0][3].any() and first[0][5].any() and ns.n_within[5].any() and fr.hist[5].any() and not first[0][0].any()
+print("ok")
+""" % (os.path.join(ROOT, "tests"), ROOT)
+
+
+def test_set_statistics_share_their_group_workspaces():
+    """map_sets and the nearest family keep their group's matrices and their slice table in ONE pair of workspaces of the handle.
+    On one Database, in turn: map_sets (sum), nearest_sets, map_sets (count), flank_reldist with 7 bins, nearest_sets_fused,
+    map_sets (sum) again -- matrices of 40, 41 and 7 x 41 columns, slices of 256 regions and of sets_slice_len(chunk) -- each
+    against its definition, the first and the last result equal: a stale capacity, a matrix that was not zeroed again or a
+    table left over from the call before would show.  Chunks of 97 regions, groups of two sets (one for the histogram); the
+    variables are read once per process: a child process."""
+    env = dict(os.environ, IGD_HIP_MAX_BATCH="97", IGD_HIP_SETS_ROW_BYTES="2000")
+    p = subprocess.run([sys.executable, "-c", SHARED], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
+    assert p.returncode == 0 and p.stdout.strip().endswith(b"ok"), p.stderr.decode()[-2000:]
+
+
 def test_resident_rows_on_a_torch_stream(workdir):
     import torch
     from igd_amd import Database
