@@ -26,6 +26,93 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+# ---- the arguments every entry takes: regions, sets, dispatch, a caller's output arrays, a seed, the contig lengths ---------
+def _regions(ichr, qs, qe, what=None, noun="regions", ok=True):
+    """(ichr, qs, qe) as C-ordered int32.  With `what`: three arrays of one length (and whatever else `ok` stands for), or
+    IgdError; without it nothing is compared -- search(), the enumerations and the set entries, which speak for themselves."""
+    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    if what and (len(ichr) != len(qs) or len(qe) != len(qs) or not ok):
+        raise IgdError("%s: %d / %d / %d %s given" % (what, len(ichr), len(qs), len(qe), noun))
+    return ichr, qs, qe
+
+
+def _sets(ichr, qs, qe, set_off, what, noun="regions", universe=None):
+    """(ichr, qs, qe, set_off int64[nsets + 1], nsets) of concatenated sets whose last offset is the number of regions.
+    universe: the three lengths of a universe's arrays, which then have to agree too (_restrict_args)."""
+    ichr, qs, qe = _regions(ichr, qs, qe)
+    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+    if len(set_off) < 1:
+        raise IgdError("%s: set_off needs nsets + 1 entries" % what)
+    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs) or (universe and len(set(universe)) != 1):
+        given = "%d / %d / %d %s" % (len(ichr), len(qs), len(qe), noun)
+        if universe:
+            given += " and %d / %d / %d universe regions" % universe
+        raise IgdError("%s: set_off[-1] = %d, but %s given" % (what, set_off[-1], given))
+    return ichr, qs, qe, set_off, len(set_off) - 1
+
+
+def _value_filter(value_filter):
+    return N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+
+
+def _dispatch(gtype, v, rule, value_filter):
+    """(rule, engine v): the command line's choice for `-v v` unless the caller names a rule"""
+    if rule is None:
+        return Database.cli_dispatch(gtype, v)
+    return rule, _value_filter(value_filter)
+
+
+def _wrong_out(what, name, words, dtype, shape):
+    return IgdError("%s: %s must be %s %s[%s]" % (what, name, words, np.dtype(dtype).name, ", ".join("%d" % n for n in shape)))
+
+
+def _out(arr, shape, dtype, name, what, zero=False, words="a C-ordered"):
+    """the caller's output array after its dtype, shape and order are checked, or a new one (zeroed where the entry adds)"""
+    if arr is None:
+        return (np.zeros if zero else np.empty)(shape, dtype)
+    if arr.dtype != dtype or arr.shape != shape or not arr.flags.c_contiguous:
+        raise _wrong_out(what, name, words, dtype, shape)
+    return arr
+
+
+def _outs(out, count, shape, what):
+    """`count` C-ordered int64 arrays of `shape`: the caller's list (overwritten) or new ones"""
+    if out is None:
+        return [np.empty(shape, np.int64) for _ in range(count)]
+    words = {3: "three", 6: "six"}[count] + " C-ordered"
+    if len(out) != count:
+        raise _wrong_out(what, "out", words, np.int64, shape)
+    return [_out(a, shape, np.int64, "out", what, words=words) for a in out]
+
+
+def _seed(seed):
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _ctg_len_matches(ctg_len, nctg, what):
+    if len(ctg_len) != nctg:
+        raise IgdError("%s: ctg_len has %d entries, the database %d contigs" % (what, len(ctg_len), nctg))
+
+
+def _open_core(igd_path):
+    """header and index of a .igd: an igdc_db the caller closes with igdc_close"""
+    L = N.cli()
+    core = L.igdc_open(igd_path.encode())
+    if not core:
+        raise IgdError("cannot read .igd header of %s" % igd_path)
+    tsv = L.igdc_index_path(igd_path.encode())
+    rc = L.igdc_load_index(core, C.cast(tsv, C.c_char_p))
+    N.free(tsv)
+    if rc != 0:
+        L.igdc_close(core)
+        raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
+    return core
+
+
 Enrichment = collections.namedtuple("Enrichment", "support usupport b c d pvalue_log odds_ratio clamped")
 RestrictedEnrichment = collections.namedtuple("RestrictedEnrichment", "support usupport b c d pvalue_log odds_ratio size bits")
 EnrichmentRanks = collections.namedtuple("EnrichmentRanks", "qvalue_log rnk_sup rnk_pv rnk_or max_rnk mean_rnk")
@@ -111,7 +198,7 @@ def fisher_host(a, b, c, d):
     a, b, c, d = _tables(a, b, c, d, "fisher_host")
     n = len(a)
     p, o = np.empty(n, np.float64), np.empty(n, np.float64)
-    if N.cli().igdc_fisher_host(a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, n, p.ctypes.data, o.ctypes.data) != 0:
+    if N.cli().igdc_fisher_host(_ptr(a), _ptr(b), _ptr(c), _ptr(d), n, _ptr(p), _ptr(o)) != 0:
         raise IgdError("fisher_host: a table has a negative entry or N >= 2^31")
     return p, o
 
@@ -139,24 +226,15 @@ def rank_host(support, pvalue_log=None, odds_ratio=None):
     touched): EnrichmentRanks as Database.enrichment_ranks() defines it, from three [nsets, ncols] arrays or one Enrichment."""
     s, p, o = _rank_inputs(support, pvalue_log, odds_ratio, "rank_host")
     r = _rank_outputs(s.shape)
-    if N.cli().igdc_rank_host(s.ctypes.data, p.ctypes.data, o.ctypes.data, s.shape[0], s.shape[1], r.qvalue_log.ctypes.data,
-                              r.rnk_sup.ctypes.data, r.rnk_pv.ctypes.data, r.rnk_or.ctypes.data, r.max_rnk.ctypes.data,
-                              r.mean_rnk.ctypes.data) != 0:
+    if N.cli().igdc_rank_host(_ptr(s), _ptr(p), _ptr(o), s.shape[0], s.shape[1], *[_ptr(x) for x in r]) != 0:
         raise IgdError("rank_host: more than 2^20 columns, or a pvalue_log is negative or NaN")
     return r
 
 
 def _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, what):
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    u_ichr, u_qs, u_qe = _i32(u_ichr), _i32(u_qs), _i32(u_qe)
-    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-    nsets, nu = len(set_off) - 1, len(u_qs)
-    if nsets < 0:
-        raise IgdError("%s: set_off needs nsets + 1 entries" % what)
-    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs) or len(u_ichr) != nu or len(u_qe) != nu:
-        raise IgdError("%s: set_off[-1] = %d, but %d / %d / %d queries and %d / %d / %d universe regions given"
-                       % (what, set_off[-1], len(ichr), len(qs), len(qe), len(u_ichr), nu, len(u_qe)))
-    return ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu
+    u_ichr, u_qs, u_qe = _regions(u_ichr, u_qs, u_qe)
+    ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, what, "queries", (len(u_ichr), len(u_qs), len(u_qe)))
+    return ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, len(u_qs)
 
 
 def _restricted_result(sup, usup, size, plog, odds, bits, nu):
@@ -171,9 +249,8 @@ def restrict_host(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe):
     uint32[nsets, ceil(nu / 32)], size int64[nsets]) as Database.restrict_sets() defines them."""
     ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, "restrict_host")
     bits, size = np.empty((nsets, (nu + 31) // 32), np.uint32), np.empty(max(nsets, 1), np.int64)
-    if N.cli().igdc_restrict_host(ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets, u_ichr.ctypes.data,
-                                  u_qs.ctypes.data, u_qe.ctypes.data, nu, bits.ctypes.data if bits.size else None,
-                                  size.ctypes.data) != 0:
+    if N.cli().igdc_restrict_host(_ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _ptr(u_ichr), _ptr(u_qs), _ptr(u_qe), nu,
+                                  _ptr(bits), _ptr(size)) != 0:
         raise IgdError("restrict_host: set_off is not monotone from 0, or the universe holds 2^31 - 1 regions or more")
     return bits, size[:nsets]
 
@@ -183,44 +260,17 @@ def enrich_restricted_host(igd_path, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, 
     RestrictedEnrichment as Database.enrichment_restricted() defines it; with_nhit adds (nhit int64[nsets], unhit)."""
     ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe,
                                                                           "enrich_restricted_host")
-    L = N.cli()
-    core = L.igdc_open(igd_path.encode())
-    if not core:
-        raise IgdError("cannot read .igd header of %s" % igd_path)
-    fd = -1
-    m = None
-    try:
-        tsv = L.igdc_index_path(igd_path.encode())
-        rc = L.igdc_load_index(core, C.cast(tsv, C.c_char_p))
-        N.free(tsv)
-        if rc != 0:
-            raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
-        nf, gtype = core.contents.nFiles, core.contents.gType
-        if rule is None:
-            rule, vf = Database.cli_dispatch(gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-        fd = os.open(igd_path, os.O_RDONLY)
-        m = L.igdc_map_open(core, fd)
-        if not m:
-            raise IgdError("cannot map %s" % igd_path)
+    with _HostDb(igd_path, None) as h:
+        nf = h.nfiles
+        rule, vf = h.dispatch(v, rule, value_filter)
         sup, usup = np.empty((nsets, nf), np.int64), np.empty(max(nf, 1), np.int64)
         plog, odds = np.empty((nsets, nf), np.float64), np.empty((nsets, nf), np.float64)
         size, nhit, unhit = np.empty(max(nsets, 1), np.int64), np.empty(max(nsets, 1), np.int64), C.c_int64(0)
         bits = np.empty((nsets, (nu + 31) // 32), np.uint32)
-        if L.igdc_enrich_restricted_host(core, m, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
-                                         u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu, vf, rule,
-                                         sup.ctypes.data if sup.size else None, usup.ctypes.data,
-                                         size.ctypes.data, plog.ctypes.data if plog.size else None,
-                                         odds.ctypes.data if odds.size else None, bits.ctypes.data if bits.size else None,
-                                         nhit.ctypes.data, C.byref(unhit)) != 0:
+        if h.L.igdc_enrich_restricted_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _ptr(u_ichr), _ptr(u_qs),
+                                           _ptr(u_qe), nu, vf, rule, _ptr(sup), _ptr(usup), _ptr(size), _ptr(plog), _ptr(odds), _ptr(bits),
+                                           _ptr(nhit), C.byref(unhit)) != 0:
             raise IgdError("enrich_restricted_host: bad set_off or universe, or a tile of %s could not be read" % igd_path)
-    finally:
-        if m:
-            L.igdc_map_close(m)
-        if fd >= 0:
-            os.close(fd)
-        L.igdc_close(core)
     res = _restricted_result(sup, usup[:nf], size[:nsets], plog, odds, bits, nu)
     return (res, nhit[:nsets], unhit.value) if with_nhit else res
 
@@ -241,8 +291,8 @@ def bitrows_gram_host(a, b=None):
         raise IgdError("bitrows_gram_host: rows of %d and of %d words" % (a.shape[1], b.shape[1]))
     m, n = a.shape[0], a.shape[0] if b is None else b.shape[0]
     out = np.empty((m, n), np.int64)
-    if N.cli().igdc_bitrows_gram_host(a.ctypes.data if a.size else None, m, None if b is None else (b.ctypes.data if b.size else a.ctypes.data),
-                                      n, a.shape[1], out.ctypes.data if out.size else None) != 0:
+    if N.cli().igdc_bitrows_gram_host(_ptr(a), m, None if b is None else (b.ctypes.data if b.size else a.ctypes.data), n, a.shape[1],
+                                      _ptr(out)) != 0:
         raise IgdError("bitrows_gram_host: more than 2^28 cells")
     return out
 
@@ -262,40 +312,12 @@ def jaccard(cooc):
 def cooccur_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None):
     """Dataset co-occurrence over a region list on the host (igdc_cooccur_host: pread on the .igd; no device is touched):
     (cooc int64[nfiles, nfiles], nhit) as Database.cooccurrence() defines them."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    if len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("cooccur_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
-    L = N.cli()
-    core = L.igdc_open(igd_path.encode())
-    if not core:
-        raise IgdError("cannot read .igd header of %s" % igd_path)
-    fd = -1
-    m = None
-    try:
-        tsv = L.igdc_index_path(igd_path.encode())
-        rc = L.igdc_load_index(core, C.cast(tsv, C.c_char_p))
-        N.free(tsv)
-        if rc != 0:
-            raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
-        nf, gtype = core.contents.nFiles, core.contents.gType
-        if rule is None:
-            rule, vf = Database.cli_dispatch(gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-        fd = os.open(igd_path, os.O_RDONLY)
-        m = L.igdc_map_open(core, fd)
-        if not m:
-            raise IgdError("cannot map %s" % igd_path)
-        cooc, nhit = np.empty((nf, nf), np.int64), C.c_int64(0)
-        if L.igdc_cooccur_host(core, m, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, len(qs), vf, rule,
-                               cooc.ctypes.data if cooc.size else None, C.byref(nhit)) != 0:
+    ichr, qs, qe = _regions(ichr, qs, qe, "cooccur_host")
+    with _HostDb(igd_path, None) as h:
+        rule, vf = h.dispatch(v, rule, value_filter)
+        cooc, nhit = np.empty((h.nfiles, h.nfiles), np.int64), C.c_int64(0)
+        if h.L.igdc_cooccur_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), vf, rule, _ptr(cooc), C.byref(nhit)) != 0:
             raise IgdError("cooccur_host: more than 16384 files, or a tile of %s could not be read" % igd_path)
-    finally:
-        if m:
-            L.igdc_map_close(m)
-        if fd >= 0:
-            os.close(fd)
-        L.igdc_close(core)
     return cooc, nhit.value
 
 
@@ -303,33 +325,25 @@ class _HostDb:
     """header, index and tile reader of a .igd for the igdc_*_host functions (no device is touched)"""
 
     def __init__(self, igd_path, what):
+        """what: the entry's name in front of "cannot map"; None for the three oldest entries, which say it without one"""
         self.L = L = N.cli()
-        self.core = L.igdc_open(igd_path.encode())
-        if not self.core:
-            raise IgdError("cannot read .igd header of %s" % igd_path)
+        self.core = _open_core(igd_path)
         self.m = None
         try:
-            tsv = L.igdc_index_path(igd_path.encode())
-            rc = L.igdc_load_index(self.core, C.cast(tsv, C.c_char_p))
-            N.free(tsv)
-            if rc != 0:
-                raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
             fd = os.open(igd_path, os.O_RDONLY)
             try:
                 self.m = L.igdc_map_open(self.core, fd)
             finally:
                 os.close(fd)
             if not self.m:
-                raise IgdError("%s: cannot map %s" % (what, igd_path))
+                raise IgdError("%scannot map %s" % ("%s: " % what if what else "", igd_path))
         except Exception:
             self.close()
             raise
         self.nfiles, self.gtype, self.nctg = self.core.contents.nFiles, self.core.contents.gType, self.core.contents.nCtg
 
     def dispatch(self, v, rule, value_filter):
-        if rule is None:
-            return Database.cli_dispatch(self.gtype, v)
-        return rule, N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        return _dispatch(self.gtype, v, rule, value_filter)
 
     def close(self):
         if self.m:
@@ -348,12 +362,12 @@ def search_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None, min_o
     """Pair counts of one query set on the host (igdc_search_host / igdc_search_host_ov: pread on the .igd, threads over the
     queries; no device is touched): (hits int64[nfiles], total) as Database.search() defines them, under min_overlap
     (MinOverlap, or an int of base pairs) as Database.search_sets() does."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    ichr, qs, qe = _regions(ichr, qs, qe)
     mo = _min_overlap(min_overlap, "search_host")
     with _HostDb(igd_path, "search_host") as h:
         rule, vf = h.dispatch(v, rule, value_filter)
         hits, total = np.zeros(max(h.nfiles, 1), np.int64), C.c_int64(0)
-        a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), vf, rule, hits.ctypes.data, C.byref(total))
+        a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), vf, rule, _ptr(hits), C.byref(total))
         if (h.L.igdc_search_host(*a) if mo is None else h.L.igdc_search_host_ov(*a, C.byref(mo))) != 0:
             raise IgdError("search_host: a tile of %s could not be read" % igd_path)
         return hits[:h.nfiles], total.value
@@ -362,12 +376,12 @@ def search_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None, min_o
 def support_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None, min_overlap=None):
     """Support counts of one query set on the host (igdc_support_host / igdc_support_host_ov; no device is touched):
     (support int64[nfiles], nhit) as Database.support() defines them, min_overlap included."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+    ichr, qs, qe = _regions(ichr, qs, qe)
     mo = _min_overlap(min_overlap, "support_host")
     with _HostDb(igd_path, "support_host") as h:
         rule, vf = h.dispatch(v, rule, value_filter)
         sup, nhit = np.zeros(max(h.nfiles, 1), np.int64), C.c_int64(0)
-        a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), vf, rule, sup.ctypes.data, C.byref(nhit))
+        a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), vf, rule, _ptr(sup), C.byref(nhit))
         if (h.L.igdc_support_host(*a) if mo is None else h.L.igdc_support_host_ov(*a, C.byref(mo))) != 0:
             raise IgdError("support_host: a tile of %s could not be read" % igd_path)
         return sup[:h.nfiles], nhit.value
@@ -380,14 +394,8 @@ def _perm_mode(mode, what):
 
 
 def _perm_regions(ichr, qs, qe, ctg_len, what):
-    ichr, qs, qe, ctg_len = _i32(ichr), _i32(qs), _i32(qe), _i32(ctg_len)
-    if len(ichr) != len(qs) or len(qe) != len(qs) or ctg_len.ndim != 1:
-        raise IgdError("%s: %d / %d / %d regions given" % (what, len(ichr), len(qs), len(qe)))
-    return ichr, qs, qe, ctg_len
-
-
-def _ptr(a):
-    return a.ctypes.data if a.size else None
+    ctg_len = _i32(ctg_len)
+    return (*_regions(ichr, qs, qe, what, ok=ctg_len.ndim == 1), ctg_len)
 
 
 def permute_regions_host(ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"):
@@ -396,7 +404,7 @@ def permute_regions_host(ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_regions_host")
     oqs, oqe = np.empty((int(np_), len(qs)), np.int32), np.empty((int(np_), len(qs)), np.int32)
     if N.cli().igdc_permute_regions_host(_ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len),
-                                         _perm_mode(mode, "permute_regions_host"), int(seed) & (2 ** 64 - 1), int(p0), int(np_),
+                                         _perm_mode(mode, "permute_regions_host"), _seed(seed), int(p0), int(np_),
                                          _ptr(oqs), _ptr(oqe)) != 0:
         raise IgdError("permute_regions_host: bad argument")
     return oqs, oqe
@@ -409,41 +417,15 @@ def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular"
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_host")
     pm = _perm_mode(mode, "permute_host")
     mo = _min_overlap(min_overlap, "permute_host")
-    L = N.cli()
-    core = L.igdc_open(igd_path.encode())
-    if not core:
-        raise IgdError("cannot read .igd header of %s" % igd_path)
-    fd = -1
-    m = None
-    try:
-        tsv = L.igdc_index_path(igd_path.encode())
-        rc = L.igdc_load_index(core, C.cast(tsv, C.c_char_p))
-        N.free(tsv)
-        if rc != 0:
-            raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
-        nf, gtype, nctg = core.contents.nFiles, core.contents.gType, core.contents.nCtg
-        if len(ctg_len) != nctg:
-            raise IgdError("permute_host: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), nctg))
-        if rule is None:
-            rule, vf = Database.cli_dispatch(gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-        fd = os.open(igd_path, os.O_RDONLY)
-        m = L.igdc_map_open(core, fd)
-        if not m:
-            raise IgdError("cannot map %s" % igd_path)
-        out = [np.empty(nf + 1, np.int64) for _ in range(7)]
-        a = (core, m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, int(seed) & (2 ** 64 - 1), int(nperm), vf, rule,
-             *[x.ctypes.data for x in out])
-        if (L.igdc_permute_host(*a) if mo is None else L.igdc_permute_host_ov(*a, C.byref(mo))) != 0:
+    with _HostDb(igd_path, None) as h:
+        _ctg_len_matches(ctg_len, h.nctg, "permute_host")
+        rule, vf = h.dispatch(v, rule, value_filter)
+        out = [np.empty(h.nfiles + 1, np.int64) for _ in range(7)]
+        a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed), int(nperm), vf, rule,
+             *[_ptr(x) for x in out])
+        if (h.L.igdc_permute_host(*a) if mo is None else h.L.igdc_permute_host_ov(*a, C.byref(mo))) != 0:
             raise IgdError("permute_host: a refused argument (number of permutations, a region outside its contig), or a tile of %s "
                            "could not be read" % igd_path)
-    finally:
-        if m:
-            L.igdc_map_close(m)
-        if fd >= 0:
-            os.close(fd)
-        L.igdc_close(core)
     return PermutationSupport(*out, int(nperm))
 
 
@@ -461,26 +443,15 @@ def perm_summary(ps):
     return PermutationSummary(*out)
 
 
-def _three_out(out, shape, what):
-    """three C-ordered int64 arrays of `shape`: the caller's (overwritten) or new ones"""
-    if out is None:
-        return [np.empty(shape, np.int64) for _ in range(3)]
-    if len(out) != 3 or any(a.dtype != np.int64 or a.shape != shape or not a.flags.c_contiguous for a in out):
-        raise IgdError("%s: out must be three C-ordered int64%s" % (what, list(shape)))
-    return list(out)
-
-
 def permute_nearest_host(igd_path, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None):
     """Database.permutation_nearest() on the host (igdc_permute_nearest_host: pread on the .igd, threads over the permutations;
     no device is touched): a PermutationNearest."""
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_nearest_host")
     pm = _perm_mode(mode, "permute_nearest_host")
     with _HostDb(igd_path, "permute_nearest_host") as h:
-        nctg = h.core.contents.nCtg
-        if len(ctg_len) != nctg:
-            raise IgdError("permute_nearest_host: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), nctg))
+        _ctg_len_matches(ctg_len, h.nctg, "permute_nearest_host")
         out = [np.empty((max(int(nperm), 0) + 1, h.nfiles + 1), np.int64) for _ in range(3)]
-        if h.L.igdc_permute_nearest_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, int(seed) & (2 ** 64 - 1),
+        if h.L.igdc_permute_nearest_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed),
                                          int(nperm), _window(window, "permute_nearest_host"), _value_filter(value_filter),
                                          *[_ptr(a) for a in out]) != 0:
             raise IgdError("permute_nearest_host: a refused argument (number of permutations, window, a region outside its contig), or a "
@@ -513,16 +484,10 @@ def _window(window, what):
     return w
 
 
-def _value_filter(value_filter):
-    return N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-
-
 def nearest_host(igd_path, ichr, qs, qe, window, value_filter=None):
     """Database.nearest() on the host (igdc_nearest_host: pread on the .igd, threads over the regions; no device is touched):
     (dist int32[nq, nfiles], dmin int32[nq])."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    if len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("nearest_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    ichr, qs, qe = _regions(ichr, qs, qe, "nearest_host")
     with _HostDb(igd_path, "nearest_host") as h:
         dist, dmin = np.empty((len(qs), h.nfiles), np.int32), np.empty(len(qs), np.int32)
         if h.L.igdc_nearest_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _window(window, "nearest_host"),
@@ -533,16 +498,10 @@ def nearest_host(igd_path, ichr, qs, qe, window, value_filter=None):
 
 def nearest_sets_host(igd_path, ichr, qs, qe, set_off, window, value_filter=None):
     """Database.nearest_sets() on the host (igdc_nearest_sets_host; no device is touched): a NearestSets."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-    nsets = len(set_off) - 1
-    if nsets < 0:
-        raise IgdError("nearest_sets_host: set_off needs nsets + 1 entries")
-    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("nearest_sets_host: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
+    ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "nearest_sets_host")
     with _HostDb(igd_path, "nearest_sets_host") as h:
         out = [np.empty((nsets, h.nfiles + 1), np.int64) for _ in range(3)]
-        if h.L.igdc_nearest_sets_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets,
+        if h.L.igdc_nearest_sets_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets,
                                       _window(window, "nearest_sets_host"), _value_filter(value_filter), *[_ptr(a) for a in out]) != 0:
             raise IgdError("nearest_sets_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
                            % (NEAREST_MAX_WINDOW, igd_path))
@@ -563,9 +522,7 @@ def _edges(edges, what):
 def nearest_signed_host(igd_path, ichr, qs, qe, window, value_filter=None):
     """Database.nearest_signed() on the host (igdc_nearest_signed_host; no device is touched):
     (sdist int32[nq, nfiles], sdmin int32[nq])."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    if len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("nearest_signed_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    ichr, qs, qe = _regions(ichr, qs, qe, "nearest_signed_host")
     with _HostDb(igd_path, "nearest_signed_host") as h:
         sdist, sdmin = np.empty((len(qs), h.nfiles), np.int32), np.empty(len(qs), np.int32)
         if h.L.igdc_nearest_signed_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _window(window, "nearest_signed_host"),
@@ -576,17 +533,11 @@ def nearest_signed_host(igd_path, ichr, qs, qe, window, value_filter=None):
 
 def nearest_hist_host(igd_path, ichr, qs, qe, set_off, window, edges, value_filter=None):
     """Database.nearest_hist() on the host (igdc_nearest_hist_host; no device is touched): a NearestHist."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+    ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "nearest_hist_host")
     edges = _edges(edges, "nearest_hist_host")
-    nsets = len(set_off) - 1
-    if nsets < 0:
-        raise IgdError("nearest_hist_host: set_off needs nsets + 1 entries")
-    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("nearest_hist_host: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
     with _HostDb(igd_path, "nearest_hist_host") as h:
         hist = np.empty((nsets, len(edges) + 1, h.nfiles + 1), np.int64)
-        if h.L.igdc_nearest_hist_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets,
+        if h.L.igdc_nearest_hist_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets,
                                       _window(window, "nearest_hist_host"), _value_filter(value_filter), _ptr(edges), len(edges),
                                       _ptr(hist)) != 0:
             raise IgdError("nearest_hist_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
@@ -609,22 +560,10 @@ def _nbins(nbins, what):
     return int(nbins)
 
 
-def _sets_args(ichr, qs, qe, set_off, what):
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-    if len(set_off) < 1:
-        raise IgdError("%s: set_off needs nsets + 1 entries" % what)
-    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("%s: set_off[-1] = %d, but %d / %d / %d regions given" % (what, set_off[-1], len(ichr), len(qs), len(qe)))
-    return ichr, qs, qe, set_off
-
-
 def flanks_host(igd_path, ichr, qs, qe, window, measure="midpoints", value_filter=None):
     """Database.flanks() on the host (igdc_flank_host; no device is touched): (up, down int32[nq, nfiles], upmin, downmin
     int32[nq])."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    if len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("flanks_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    ichr, qs, qe = _regions(ichr, qs, qe, "flanks_host")
     measure = _measure(measure, "flanks_host")
     with _HostDb(igd_path, "flanks_host") as h:
         up, down = np.empty((len(qs), h.nfiles), np.int32), np.empty((len(qs), h.nfiles), np.int32)
@@ -637,12 +576,11 @@ def flanks_host(igd_path, ichr, qs, qe, window, measure="midpoints", value_filte
 
 def flank_reldist_host(igd_path, ichr, qs, qe, set_off, window, nbins=50, measure="midpoints", value_filter=None):
     """Database.flank_reldist() on the host (igdc_flank_reldist_host; no device is touched): a FlankReldist."""
-    ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "flank_reldist_host")
+    ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "flank_reldist_host")
     nbins, m = _nbins(nbins, "flank_reldist_host"), _measure(measure, "flank_reldist_host")
-    nsets = len(set_off) - 1
     with _HostDb(igd_path, "flank_reldist_host") as h:
         hist = np.empty((nsets, nbins, h.nfiles + 1), np.int64)
-        if h.L.igdc_flank_reldist_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets,
+        if h.L.igdc_flank_reldist_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets,
                                        _window(window, "flank_reldist_host"), m, _value_filter(value_filter), nbins, _ptr(hist)) != 0:
             raise IgdError("flank_reldist_host: a bad set_off, a window outside 0 .. %d, or a tile of %s could not be read"
                            % (NEAREST_MAX_WINDOW, igd_path))
@@ -671,18 +609,16 @@ def permute_bp_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circul
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_bp_host")
     pm = _perm_mode(mode, "permute_bp_host")
     with _HostDb(igd_path, "permute_bp_host") as h:
-        nctg = h.core.contents.nCtg
-        if len(ctg_len) != nctg:
-            raise IgdError("permute_bp_host: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), nctg))
+        _ctg_len_matches(ctg_len, h.nctg, "permute_bp_host")
         rule, vf = h.dispatch(v, rule, value_filter)
         rows = max(int(nperm), 0) + 1
         inter, set_bp, n_merged = np.empty((rows, h.nfiles + 1), np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
         dropped, file_bp = np.zeros(1, np.int64), np.empty(h.nfiles + 1, np.int64)
-        if h.L.igdc_permute_bp_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, int(seed) & (2 ** 64 - 1),
+        if h.L.igdc_permute_bp_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed),
                                     int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged), _ptr(dropped)) != 0:
             raise IgdError("permute_bp_host: a refused argument (number of permutations, a region outside its contig), or a tile of %s "
                            "could not be read" % igd_path)
-        if h.L.igdc_dataset_bp_host(h.core, h.m, vf, rule, file_bp.ctypes.data) != 0:
+        if h.L.igdc_dataset_bp_host(h.core, h.m, vf, rule, _ptr(file_bp)) != 0:
             raise IgdError("permute_bp_host: a tile of %s could not be read" % igd_path)
         return PermutationBp(inter, set_bp, n_merged, int(dropped[0]), file_bp, int(nperm))
 
@@ -707,11 +643,11 @@ def perm_bp_summary(pb):
 
 def merge_host(igd_path, ichr, qs, qe, set_off, gap=0):
     """Database.merge_sets() on the host (igdc_merge_host; no device is touched): (ichr, qs, qe, set_off, count, n_dropped)."""
-    ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "merge_host")
-    gap, nsets = _gap(gap, "merge_host"), len(set_off) - 1
+    ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "merge_host")
+    gap = _gap(gap, "merge_host")
     out = _merge_out(len(qs), nsets)
     with _HostDb(igd_path, "merge_host") as h:
-        if h.L.igdc_merge_host(h.core, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, gap, *[_ptr(a) for a in out]) != 0:
+        if h.L.igdc_merge_host(h.core, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, gap, *[_ptr(a) for a in out]) != 0:
             raise IgdError("merge_host: a bad set_off")
     return _merge_cut(*out)
 
@@ -721,21 +657,20 @@ def dataset_bp_host(igd_path, v=0, rule=None, value_filter=None):
     with _HostDb(igd_path, "dataset_bp_host") as h:
         rule, vf = h.dispatch(v, rule, value_filter)
         bp = np.empty(h.nfiles + 1, np.int64)
-        if h.L.igdc_dataset_bp_host(h.core, h.m, vf, rule, bp.ctypes.data) != 0:
+        if h.L.igdc_dataset_bp_host(h.core, h.m, vf, rule, _ptr(bp)) != 0:
             raise IgdError("dataset_bp_host: a tile of %s could not be read" % igd_path)
         return bp
 
 
 def jaccard_host(igd_path, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None):
     """Database.jaccard_sets() on the host (igdc_jaccard_host; no device is touched): a JaccardSets."""
-    ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "jaccard_host")
-    nsets = len(set_off) - 1
+    ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "jaccard_host")
     with _HostDb(igd_path, "jaccard_host") as h:
         rule, vf = h.dispatch(v, rule, value_filter)
         js = JaccardSets(np.empty((nsets, h.nfiles + 1), np.int64), np.empty(nsets, np.int64), np.empty(h.nfiles + 1, np.int64),
                          np.empty(nsets, np.int64), np.empty(nsets, np.int64))
-        if h.L.igdc_jaccard_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, vf, rule, _ptr(js.inter),
-                                 _ptr(js.set_bp), js.file_bp.ctypes.data, _ptr(js.n_merged), _ptr(js.n_dropped)) != 0:
+        if h.L.igdc_jaccard_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, vf, rule, _ptr(js.inter),
+                                 _ptr(js.set_bp), _ptr(js.file_bp), _ptr(js.n_merged), _ptr(js.n_dropped)) != 0:
             raise IgdError("jaccard_host: a bad set_off, or a tile of %s could not be read" % igd_path)
         return js
 
@@ -782,22 +717,10 @@ def _map_op(op, what):
     return MAP_OPS[op]
 
 
-def _map_sets_args(ichr, qs, qe, set_off, what):
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-    if len(set_off) < 1:
-        raise IgdError("%s: set_off needs nsets + 1 entries" % what)
-    if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("%s: set_off[-1] = %d, but %d / %d / %d regions given" % (what, set_off[-1], len(ichr), len(qs), len(qe)))
-    return ichr, qs, qe, set_off
-
-
 def map_host(igd_path, ichr, qs, qe, op="sum", value_filter=None):
     """Database.map_values() on the host (igdc_map_host: pread on the .igd, threads over the regions; no device is touched):
     (count int32[nq, nfiles], agg int64[nq, nfiles]); under op "count" agg holds the counts."""
-    ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-    if len(ichr) != len(qs) or len(qe) != len(qs):
-        raise IgdError("map_host: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+    ichr, qs, qe = _regions(ichr, qs, qe, "map_host")
     o = _map_op(op, "map_host")
     with _HostDb(igd_path, "map_host") as h:
         count, agg = np.empty((len(qs), h.nfiles), np.int32), np.empty((len(qs), h.nfiles), np.int64)
@@ -808,12 +731,11 @@ def map_host(igd_path, ichr, qs, qe, op="sum", value_filter=None):
 
 def map_sets_host(igd_path, ichr, qs, qe, set_off, op="sum", value_filter=None):
     """Database.map_sets() on the host (igdc_map_sets_host; no device is touched): a MapSets."""
-    ichr, qs, qe, set_off = _map_sets_args(ichr, qs, qe, set_off, "map_sets_host")
+    ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "map_sets_host")
     o = _map_op(op, "map_sets_host")
-    nsets = len(set_off) - 1
     with _HostDb(igd_path, "map_sets_host") as h:
         out = [np.empty((nsets, h.nfiles), np.int64) for _ in range(3)]
-        if h.L.igdc_map_sets_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, o, _value_filter(value_filter),
+        if h.L.igdc_map_sets_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, o, _value_filter(value_filter),
                                   *[_ptr(a) for a in out]) != 0:
             raise IgdError("map_sets_host: a bad set_off, op %s on a database without values, or a tile of %s could not be read"
                            % (op, igd_path))
@@ -841,16 +763,7 @@ class Database:
             raise IgdError("%s is a measurement build (IGD_EXP=0x%x) whose counts are WRONG on purpose; "
                            "IGD_HIP_ALLOW_EXP_BUILD=1 loads it anyway" % (os.path.join(N.LIBDIR, "libigd_hip.so"), self.build_flags))
         self.path = igd_path
-        self._core = self._L.igdc_open(igd_path.encode())
-        if not self._core:
-            raise IgdError("cannot read .igd header of %s" % igd_path)
-        tsv = self._L.igdc_index_path(igd_path.encode())
-        rc = self._L.igdc_load_index(self._core, C.cast(tsv, C.c_char_p))
-        N.free(tsv)
-        if rc != 0:
-            self._L.igdc_close(self._core)
-            self._core = None
-            raise IgdError("cannot read the _index.tsv next to %s" % igd_path)
+        self._core = _open_core(igd_path)
         c = self._core.contents
         self.nbp, self.gtype, self.nctg, self.nfiles = c.nbp, c.gType, c.nCtg, c.nFiles
         self.nrecords, self.ntiles = c.nRecords, c.nTileTotal
@@ -920,16 +833,13 @@ class Database:
         flags: 0 (device checks the order and picks merge-join or bucketing), IGD_HIP_FLAG_SORTED [| IGD_HIP_FLAG_SHORT] (a
         promise, verified; a broken one is repaired by a second pass) or IGD_HIP_FLAG_BUCKET (the caller knows the batch is
         unordered: no order check, ~13 us per 10^6 queries less than 0)."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        ichr, qs, qe = _regions(ichr, qs, qe)
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         if hits is None:
             hits = np.zeros(max(self.nfiles, 1), np.int64)
         total = C.c_int64(0)
-        _chk(self._H.igd_hip_search_ex(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, len(qs),
-                                       vf, rule, int(flags), hits.ctypes.data, C.byref(total)), "igd_hip_search")
+        _chk(self._H.igd_hip_search_ex(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), vf, rule, int(flags),
+                                       hits.ctypes.data, C.byref(total)), "igd_hip_search")     # (hits: the caller's, never looked at)
         return hits[: self.nfiles], total.value
 
     def search_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, hits=None, flags=0, min_overlap=None):
@@ -939,36 +849,18 @@ class Database:
         to when given.  flags as search() (they steer the route of sets of 2^17 queries and more).
         min_overlap (a MinOverlap, or an int of base pairs; igd_hip_search_sets_ov): only the pairs that reach it are counted,
         and every set, whatever its size, is counted by the slice kernel."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-        nsets = len(set_off) - 1
-        if nsets < 0:
-            raise IgdError("search_sets: set_off needs nsets + 1 entries")
-        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("search_sets: set_off[-1] = %d, but %d / %d / %d queries given"
-                           % (set_off[-1], len(ichr), len(qs), len(qe)))
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-        if hits is None:
-            hits = np.zeros((nsets, self.nfiles), np.int64)
-        elif hits.dtype != np.int64 or hits.shape != (nsets, self.nfiles) or not hits.flags.c_contiguous:
-            raise IgdError("search_sets: hits must be a C-ordered int64[%d, %d]" % (nsets, self.nfiles))
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "search_sets", "queries")
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
+        hits = _out(hits, (nsets, self.nfiles), np.int64, "hits", "search_sets", zero=True)
         totals = np.zeros(max(nsets, 1), np.int64)
         mo = _min_overlap(min_overlap, "search_sets")
-        a = (self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets, vf, rule, int(flags),
-             hits.ctypes.data if hits.size else None, totals.ctypes.data)
+        a = (self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, vf, rule, int(flags), _ptr(hits), _ptr(totals))
         _chk(self._H.igd_hip_search_sets(*a) if mo is None else self._H.igd_hip_search_sets_ov(*a, C.byref(mo)), "igd_hip_search_sets")
         return hits, totals[:nsets]
 
     def search_files(self, paths, v=0, min_overlap=None):
         """One query set per BED file (read as `igd search -q` reads it): (hits int64[len(paths), nfiles], totals)."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.search_sets(cat[0], cat[1], cat[2], set_off, v, min_overlap=min_overlap)
+        return self.search_sets(*self._read_sets(paths), v, min_overlap=min_overlap)
 
     def support_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, support=None, min_overlap=None):
         """Support counts of many query sets in one call (igd_hip_support_sets).  Sets as search_sets().  Returns (support
@@ -976,26 +868,12 @@ class Database:
         file f (search_sets counts every overlapping record), nhit[k] = the queries of set k that overlap any record.
         support (int64[nsets, nfiles], C order) is added to when given.  min_overlap (a MinOverlap, or an int of base pairs;
         igd_hip_support_sets_ov): "overlap" then means at least one PAIR that reaches it, as LOLA and bedtools test it."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-        nsets = len(set_off) - 1
-        if nsets < 0:
-            raise IgdError("support_sets: set_off needs nsets + 1 entries")
-        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("support_sets: set_off[-1] = %d, but %d / %d / %d queries given"
-                           % (set_off[-1], len(ichr), len(qs), len(qe)))
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-        if support is None:
-            support = np.zeros((nsets, self.nfiles), np.int64)
-        elif support.dtype != np.int64 or support.shape != (nsets, self.nfiles) or not support.flags.c_contiguous:
-            raise IgdError("support_sets: support must be a C-ordered int64[%d, %d]" % (nsets, self.nfiles))
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "support_sets", "queries")
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
+        support = _out(support, (nsets, self.nfiles), np.int64, "support", "support_sets", zero=True)
         nhit = np.zeros(max(nsets, 1), np.int64)
         mo = _min_overlap(min_overlap, "support_sets")
-        a = (self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets, vf, rule,
-             support.ctypes.data if support.size else None, nhit.ctypes.data)
+        a = (self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, vf, rule, _ptr(support), _ptr(nhit))
         _chk(self._H.igd_hip_support_sets(*a) if mo is None else self._H.igd_hip_support_sets_ov(*a, C.byref(mo)), "igd_hip_support_sets")
         return support, nhit[:nsets]
 
@@ -1007,11 +885,7 @@ class Database:
 
     def support_files(self, paths, v=0, min_overlap=None):
         """One query set per BED file (read as `igd search -q` reads it): (support int64[len(paths), nfiles], nhit)."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.support_sets(cat[0], cat[1], cat[2], set_off, v, min_overlap=min_overlap)
+        return self.support_sets(*self._read_sets(paths), v, min_overlap=min_overlap)
 
     def coverage_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, coverage=None):
         """Covered base pairs of many query sets in one call (igd_hip_coverage_sets).  Sets as search_sets().  Returns
@@ -1020,26 +894,12 @@ class Database:
         sum over records), covered[k] = the same under the records of any file.  The sum runs over queries: two identical
         queries count twice and overlapping queries of one set are not merged -- merge the BED first for the set-level
         intersection.  coverage (int64[nsets, nfiles], C order) is added to when given."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-        nsets = len(set_off) - 1
-        if nsets < 0:
-            raise IgdError("coverage_sets: set_off needs nsets + 1 entries")
-        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("coverage_sets: set_off[-1] = %d, but %d / %d / %d queries given"
-                           % (set_off[-1], len(ichr), len(qs), len(qe)))
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-        if coverage is None:
-            coverage = np.zeros((nsets, self.nfiles), np.int64)
-        elif coverage.dtype != np.int64 or coverage.shape != (nsets, self.nfiles) or not coverage.flags.c_contiguous:
-            raise IgdError("coverage_sets: coverage must be a C-ordered int64[%d, %d]" % (nsets, self.nfiles))
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "coverage_sets", "queries")
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
+        coverage = _out(coverage, (nsets, self.nfiles), np.int64, "coverage", "coverage_sets", zero=True)
         covered = np.zeros(max(nsets, 1), np.int64)
-        _chk(self._H.igd_hip_coverage_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data,
-                                           nsets, vf, rule, coverage.ctypes.data if coverage.size else None,
-                                           covered.ctypes.data), "igd_hip_coverage_sets")
+        _chk(self._H.igd_hip_coverage_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, vf, rule, _ptr(coverage),
+                                           _ptr(covered)), "igd_hip_coverage_sets")
         return coverage, covered[:nsets]
 
     def coverage(self, ichr, qs, qe, v=0, rule=None, value_filter=None):
@@ -1050,11 +910,7 @@ class Database:
 
     def coverage_files(self, paths, v=0):
         """One query set per BED file (read as `igd search -q` reads it): (coverage int64[len(paths), nfiles], covered)."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.coverage_sets(cat[0], cat[1], cat[2], set_off, v)
+        return self.coverage_sets(*self._read_sets(paths), v)
 
     def fisher(self, a, b, c, d, pvalue_log=None, odds_ratio=None):
         """Fisher's exact test, one-sided ("greater"), of the 2x2 tables a b / c d on the GPU (igd_hip_fisher_tables).
@@ -1064,13 +920,9 @@ class Database:
         are overwritten.  A negative entry or N >= 2^31 raises IgdError and leaves them untouched."""
         a, b, c, d = _tables(a, b, c, d, "fisher")
         n = len(a)
-        for name, x in (("pvalue_log", pvalue_log), ("odds_ratio", odds_ratio)):
-            if x is not None and (x.dtype != np.float64 or x.shape != (n,) or not x.flags.c_contiguous):
-                raise IgdError("fisher: %s must be a contiguous float64[%d]" % (name, n))
-        p = np.empty(n, np.float64) if pvalue_log is None else pvalue_log
-        o = np.empty(n, np.float64) if odds_ratio is None else odds_ratio
-        _chk(self._H.igd_hip_fisher_tables(self.dev, a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, n,
-                                           p.ctypes.data, o.ctypes.data), "igd_hip_fisher_tables")
+        p = _out(pvalue_log, (n,), np.float64, "pvalue_log", "fisher", words="a contiguous")
+        o = _out(odds_ratio, (n,), np.float64, "odds_ratio", "fisher", words="a contiguous")
+        _chk(self._H.igd_hip_fisher_tables(self.dev, _ptr(a), _ptr(b), _ptr(c), _ptr(d), n, _ptr(p), _ptr(o)), "igd_hip_fisher_tables")
         return p, o
 
     def enrichment_sets(self, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, v=0, rule=None, value_filter=None, min_overlap=None):
@@ -1082,26 +934,15 @@ class Database:
         on these tables.  Arrays are [nsets, nfiles], usupport [nfiles], clamped [nsets].  Ranks and q-values: enrichment_ranks().
         min_overlap (a MinOverlap, or an int of base pairs; igd_hip_enrich_sets_ov): the supports of the sets AND of the
         universe are taken under it, as LOLA's runLOLA(minOverlap=) does."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        u_ichr, u_qs, u_qe = _i32(u_ichr), _i32(u_qs), _i32(u_qe)
-        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-        nsets, nu, nf = len(set_off) - 1, len(u_qs), self.nfiles
-        if nsets < 0:
-            raise IgdError("enrichment_sets: set_off needs nsets + 1 entries")
-        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs) or len(u_ichr) != nu or len(u_qe) != nu:
-            raise IgdError("enrichment_sets: set_off[-1] = %d, but %d / %d / %d queries and %d / %d / %d universe regions given"
-                           % (set_off[-1], len(ichr), len(qs), len(qe), len(u_ichr), nu, len(u_qe)))
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, "enrichment_sets")
+        nf = self.nfiles
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         sup, usup = np.empty((nsets, nf), np.int64), np.empty(max(nf, 1), np.int64)
         plog, odds = np.empty((nsets, nf), np.float64), np.empty((nsets, nf), np.float64)
         clamped = np.empty(max(nsets, 1), np.int64)
         mo = _min_overlap(min_overlap, "enrichment_sets")
-        a = (self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
-             u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu, vf, rule, sup.ctypes.data if sup.size else None, usup.ctypes.data,
-             plog.ctypes.data if plog.size else None, odds.ctypes.data if odds.size else None, clamped.ctypes.data)
+        a = (self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _ptr(u_ichr), _ptr(u_qs), _ptr(u_qe), nu, vf, rule,
+             _ptr(sup), _ptr(usup), _ptr(plog), _ptr(odds), _ptr(clamped))
         _chk(self._H.igd_hip_enrich_sets(*a) if mo is None else self._H.igd_hip_enrich_sets_ov(*a, None, None, C.byref(mo)),
              "igd_hip_enrich_sets")
         usup = usup[:nf]
@@ -1119,9 +960,8 @@ class Database:
         regions that touch do not overlap, a contig number < 0 overlaps nothing.  size[k] = the set bits of row k."""
         ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, "restrict_sets")
         bits, size = np.empty((nsets, (nu + 31) // 32), np.uint32), np.empty(max(nsets, 1), np.int64)
-        _chk(self._H.igd_hip_restrict_sets(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
-                                           u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu,
-                                           bits.ctypes.data if bits.size else None, size.ctypes.data), "igd_hip_restrict_sets")
+        _chk(self._H.igd_hip_restrict_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _ptr(u_ichr), _ptr(u_qs),
+                                           _ptr(u_qe), nu, _ptr(bits), _ptr(size)), "igd_hip_restrict_sets")
         return bits, size[:nsets]
 
     def enrichment_restricted(self, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, v=0, rule=None, value_filter=None, with_nhit=False):
@@ -1136,32 +976,23 @@ class Database:
         ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe,
                                                                               "enrichment_restricted")
         nf = self.nfiles
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         sup, usup = np.empty((nsets, nf), np.int64), np.empty(max(nf, 1), np.int64)
         plog, odds = np.empty((nsets, nf), np.float64), np.empty((nsets, nf), np.float64)
         size, nhit, unhit = np.empty(max(nsets, 1), np.int64), np.empty(max(nsets, 1), np.int64), C.c_int64(0)
         bits = np.empty((nsets, (nu + 31) // 32), np.uint32)
-        _chk(self._H.igd_hip_enrich_restricted(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, set_off.ctypes.data, nsets,
-                                               u_ichr.ctypes.data, u_qs.ctypes.data, u_qe.ctypes.data, nu, vf, rule,
-                                               sup.ctypes.data if sup.size else None, usup.ctypes.data, size.ctypes.data,
-                                               plog.ctypes.data if plog.size else None, odds.ctypes.data if odds.size else None,
-                                               bits.ctypes.data if bits.size else None, nhit.ctypes.data, C.byref(unhit)),
-             "igd_hip_enrich_restricted")
+        _chk(self._H.igd_hip_enrich_restricted(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _ptr(u_ichr), _ptr(u_qs),
+                                               _ptr(u_qe), nu, vf, rule, _ptr(sup), _ptr(usup), _ptr(size), _ptr(plog), _ptr(odds),
+                                               _ptr(bits), _ptr(nhit), C.byref(unhit)), "igd_hip_enrich_restricted")
         res = _restricted_result(sup, usup[:nf], size[:nsets], plog, odds, bits, nu)
         return (res, nhit[:nsets], unhit.value) if with_nhit else res
 
     def enrichment_restricted_files(self, paths, universe_path, v=0):
         """One query set per BED file and the universe from a BED file (read as `igd search -q` reads them): what
         `igd search -Q list -U universe -X` prints, as enrichment_restricted() returns it."""
-        sets = [self.read_queries(p) for p in paths]
+        sets = self._read_sets(paths)
         uni = self.read_queries(universe_path)
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.enrichment_restricted(cat[0], cat[1], cat[2], set_off, uni[0], uni[1], uni[2], v)
+        return self.enrichment_restricted(*sets, uni[0], uni[1], uni[2], v)
 
     @staticmethod
     def unpack_restricted(bits, nu):
@@ -1178,21 +1009,16 @@ class Database:
         mean_rnk), arrays of the inputs' shape.  The family is the row: no whole-table correction, no Storey q-value."""
         s, p, o = _rank_inputs(support, pvalue_log, odds_ratio, "enrichment_ranks")
         r = _rank_outputs(s.shape)
-        _chk(self._H.igd_hip_enrich_ranks(self.dev, s.ctypes.data, p.ctypes.data, o.ctypes.data, s.shape[0], s.shape[1],
-                                          r.qvalue_log.ctypes.data, r.rnk_sup.ctypes.data, r.rnk_pv.ctypes.data,
-                                          r.rnk_or.ctypes.data, r.max_rnk.ctypes.data, r.mean_rnk.ctypes.data),
+        _chk(self._H.igd_hip_enrich_ranks(self.dev, _ptr(s), _ptr(p), _ptr(o), s.shape[0], s.shape[1], *[_ptr(x) for x in r]),
              "igd_hip_enrich_ranks")
         return r
 
     def enrichment_files(self, paths, universe_path, v=0, min_overlap=None):
         """One query set per BED file and the universe from a BED file (read as `igd search -q` reads them): what
         `igd search -Q list -U universe` prints, as enrichment_sets() returns it."""
-        sets = [self.read_queries(p) for p in paths]
+        sets = self._read_sets(paths)
         uni = self.read_queries(universe_path)
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.enrichment_sets(cat[0], cat[1], cat[2], set_off, uni[0], uni[1], uni[2], v, min_overlap=min_overlap)
+        return self.enrichment_sets(*sets, uni[0], uni[1], uni[2], v, min_overlap=min_overlap)
 
     @property
     def member_words(self):
@@ -1205,23 +1031,14 @@ class Database:
         positions >= nfiles are 0), nfiles_hit[q] = the files query q overlaps, nhit = the queries that overlap any -- the
         matrix whose column sums are support().  bits (uint32[nq, member_words], C order), when given, is overwritten:
         every word of it, so it need not be cleared."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        ichr, qs, qe = _regions(ichr, qs, qe, "membership", "queries")
         nq, nW = len(qs), self.member_words
-        if len(ichr) != nq or len(qe) != nq:
-            raise IgdError("membership: %d / %d / %d queries given" % (len(ichr), nq, len(qe)))
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-        if bits is None:
-            bits = np.empty((nq, nW), np.uint32)
-        elif bits.dtype != np.uint32 or bits.shape != (nq, nW) or not bits.flags.c_contiguous:
-            raise IgdError("membership: bits must be a C-ordered uint32[%d, %d]" % (nq, nW))
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
+        bits = _out(bits, (nq, nW), np.uint32, "bits", "membership")
         nfh = np.empty(nq, np.int32)
         nhit = C.c_int64(0)
-        _chk(self._H.igd_hip_membership(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, nq, vf, rule,
-                                        bits.ctypes.data if bits.size else None, nfh.ctypes.data if nq else None,
-                                        C.byref(nhit)), "igd_hip_membership")
+        _chk(self._H.igd_hip_membership(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, vf, rule, _ptr(bits), _ptr(nfh), C.byref(nhit)),
+             "igd_hip_membership")
         return bits, nfh, nhit.value
 
     def cooccurrence(self, ichr, qs, qe, v=0, rule=None, value_filter=None, cooc=None):
@@ -1231,21 +1048,12 @@ class Database:
         twice; no region gives a zero matrix.  cooc (int64[nfiles, nfiles], C order), when given, is overwritten: every cell
         of it.  The membership rows never leave the device.  More than 16 384 files raise IgdError.  jaccard() turns the
         matrix into the Jaccard index."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        ichr, qs, qe = _regions(ichr, qs, qe, "cooccurrence")
         nq, nf = len(qs), self.nfiles
-        if len(ichr) != nq or len(qe) != nq:
-            raise IgdError("cooccurrence: %d / %d / %d regions given" % (len(ichr), nq, len(qe)))
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
-        if cooc is None:
-            cooc = np.empty((nf, nf), np.int64)
-        elif cooc.dtype != np.int64 or cooc.shape != (nf, nf) or not cooc.flags.c_contiguous:
-            raise IgdError("cooccurrence: cooc must be a C-ordered int64[%d, %d]" % (nf, nf))
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
+        cooc = _out(cooc, (nf, nf), np.int64, "cooc", "cooccurrence")
         nhit = C.c_int64(0)
-        _chk(self._H.igd_hip_cooccur(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, nq, vf, rule,
-                                     cooc.ctypes.data if cooc.size else None, C.byref(nhit)), "igd_hip_cooccur")
+        _chk(self._H.igd_hip_cooccur(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, vf, rule, _ptr(cooc), C.byref(nhit)), "igd_hip_cooccur")
         return cooc, nhit.value
 
     def cooccurrence_files(self, path, v=0):
@@ -1260,12 +1068,8 @@ class Database:
         bits = _bitrows(bits, "bits", "transpose_bits")
         nrows, nW = bits.shape
         shape = (32 * nW, (nrows + 63) // 64)
-        if cols is None:
-            cols = np.empty(shape, np.uint64)
-        elif cols.dtype != np.uint64 or cols.shape != shape or not cols.flags.c_contiguous:
-            raise IgdError("transpose_bits: cols must be a C-ordered uint64[%d, %d]" % shape)
-        _chk(self._H.igd_hip_bits_transpose(self.dev, bits.ctypes.data if bits.size else None, nrows, nW,
-                                            cols.ctypes.data if cols.size else None), "igd_hip_bits_transpose")
+        cols = _out(cols, shape, np.uint64, "cols", "transpose_bits")
+        _chk(self._H.igd_hip_bits_transpose(self.dev, _ptr(bits), nrows, nW, _ptr(cols)), "igd_hip_bits_transpose")
         return cols
 
     def bitrows_gram(self, a, b=None, out=None):
@@ -1278,13 +1082,9 @@ class Database:
         if b is not None and b.shape[1] != a.shape[1]:
             raise IgdError("bitrows_gram: rows of %d and of %d words" % (a.shape[1], b.shape[1]))
         m, n = a.shape[0], a.shape[0] if b is None else b.shape[0]
-        if out is None:
-            out = np.empty((m, n), np.int64)
-        elif out.dtype != np.int64 or out.shape != (m, n) or not out.flags.c_contiguous:
-            raise IgdError("bitrows_gram: out must be a C-ordered int64[%d, %d]" % (m, n))
+        out = _out(out, (m, n), np.int64, "out", "bitrows_gram")
         pb = None if b is None else (b.ctypes.data if b.size else a.ctypes.data)
-        _chk(self._H.igd_hip_bitrows_gram(self.dev, a.ctypes.data if a.size else None, m, pb, n, a.shape[1],
-                                          out.ctypes.data if out.size else None), "igd_hip_bitrows_gram")
+        _chk(self._H.igd_hip_bitrows_gram(self.dev, _ptr(a), m, pb, n, a.shape[1], _ptr(out)), "igd_hip_bitrows_gram")
         return out
 
     def permutation_support(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None,
@@ -1300,16 +1100,12 @@ class Database:
         and p.  A region on a known contig that does not lie within its length raises IgdError.  min_overlap (a MinOverlap, or
         an int of base pairs; igd_hip_permute_support_ov): the observed row and every permuted row are counted under it."""
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_support")
-        if len(ctg_len) != self.nctg:
-            raise IgdError("permutation_support: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), self.nctg))
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        _ctg_len_matches(ctg_len, self.nctg, "permutation_support")
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         out = [np.empty(self.nfiles + 1, np.int64) for _ in range(7)]
         mo = _min_overlap(min_overlap, "permutation_support")
         a = (self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), _perm_mode(mode, "permutation_support"),
-             int(seed) & (2 ** 64 - 1), int(nperm), vf, rule, *[x.ctypes.data for x in out])
+             _seed(seed), int(nperm), vf, rule, *[_ptr(x) for x in out])
         _chk(self._H.igd_hip_permute_support(*a) if mo is None else self._H.igd_hip_permute_support_ov(*a, C.byref(mo)),
              "igd_hip_permute_support")
         return PermutationSupport(*out, int(nperm))
@@ -1319,7 +1115,7 @@ class Database:
         a contig the file does not name."""
         ln = np.zeros(max(self.nctg, 1), np.int32)
         bad = C.c_int64(0)
-        rc = self._L.igdc_read_genome(self._core, path.encode(), ln.ctypes.data, C.byref(bad))
+        rc = self._L.igdc_read_genome(self._core, path.encode(), _ptr(ln), C.byref(bad))
         if rc == -1:
             raise IOError("cannot open genome file %s" % path)
         if rc != 0:
@@ -1338,7 +1134,7 @@ class Database:
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_regions")
         oqs, oqe = np.empty((int(np_), len(qs)), np.int32), np.empty((int(np_), len(qs)), np.int32)
         _chk(self._H.igd_hip_permute_regions(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len),
-                                             _perm_mode(mode, "permute_regions"), int(seed) & (2 ** 64 - 1), int(p0), int(np_),
+                                             _perm_mode(mode, "permute_regions"), _seed(seed), int(p0), int(np_),
                                              _ptr(oqs), _ptr(oqe)), "igd_hip_permute_regions")
         return oqs, oqe
 
@@ -1350,10 +1146,7 @@ class Database:
         observed = np.ascontiguousarray(observed, dtype=np.int64)
         if rows.ndim != 2 or observed.shape != (rows.shape[1],):
             raise IgdError("perm_stats: rows must be int64[nrows, ncols] and observed int64[ncols]")
-        if out is None:
-            out = [np.empty(rows.shape[1], np.int64) for _ in range(6)]
-        elif len(out) != 6 or any(a.dtype != np.int64 or a.shape != (rows.shape[1],) or not a.flags.c_contiguous for a in out):
-            raise IgdError("perm_stats: out must be six C-ordered int64[%d]" % rows.shape[1])
+        out = _outs(out, 6, (rows.shape[1],), "perm_stats")
         _chk(self._H.igd_hip_perm_stats(self.dev, _ptr(rows), rows.shape[0], rows.shape[1], _ptr(observed),
                                         *[_ptr(a) for a in out]), "igd_hip_perm_stats")
         return tuple(out)
@@ -1361,11 +1154,8 @@ class Database:
     def membership_files(self, paths, v=0):
         """The rows of several BED files (read as `igd search -q` reads them), concatenated: (bits, nfiles_hit, nhit
         int64[len(paths)], set_off int64[len(paths) + 1]); file k owns the rows [set_off[k], set_off[k + 1])."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        bits, nfh, _ = self.membership(cat[0], cat[1], cat[2], v)
+        ichr, qs, qe, set_off = self._read_sets(paths)
+        bits, nfh, _ = self.membership(ichr, qs, qe, v)
         any_hit = np.concatenate([[0], np.cumsum(nfh > 0)]).astype(np.int64)
         return bits, nfh, any_hit[set_off[1:]] - any_hit[set_off[:-1]], set_off
 
@@ -1377,14 +1167,9 @@ class Database:
         within the window; dmin[q] is the smallest of the row's distances, or -1.  value_filter: only records with value >=
         it count (the nearest passing record).  There is no tile rule.  dist (int32[nq, nfiles], C order), when given, is
         overwritten: every word is defined by the call."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        if len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("nearest: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+        ichr, qs, qe = _regions(ichr, qs, qe, "nearest")
         nq = len(qs)
-        if dist is None:
-            dist = np.empty((nq, self.nfiles), np.int32)
-        elif dist.dtype != np.int32 or dist.shape != (nq, self.nfiles) or not dist.flags.c_contiguous:
-            raise IgdError("nearest: dist must be a C-ordered int32[%d, %d]" % (nq, self.nfiles))
+        dist = _out(dist, (nq, self.nfiles), np.int32, "dist", "nearest")
         dmin = np.empty(nq, np.int32)
         _chk(self._H.igd_hip_nearest(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, _window(window, "nearest"), _value_filter(value_filter),
                                      _ptr(dist), _ptr(dmin)), "igd_hip_nearest")
@@ -1396,15 +1181,9 @@ class Database:
         n_overlap (those that overlap one: the support under rule FLAT) and sum_dist (the sum of the former's distances) --
         whose last column is the any-dataset column, built from dmin.  The distance rows never leave the device.  out, when
         given, is a list of three C-ordered int64[nsets, nfiles + 1] that are overwritten."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-        nsets = len(set_off) - 1
-        if nsets < 0:
-            raise IgdError("nearest_sets: set_off needs nsets + 1 entries")
-        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("nearest_sets: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
-        out = _three_out(out, (nsets, self.nfiles + 1), "nearest_sets")
-        _chk(self._H.igd_hip_nearest_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, _window(window, "nearest_sets"),
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "nearest_sets")
+        out = _outs(out, 3, (nsets, self.nfiles + 1), "nearest_sets")
+        _chk(self._H.igd_hip_nearest_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _window(window, "nearest_sets"),
                                           _value_filter(value_filter), *[_ptr(a) for a in out]), "igd_hip_nearest_sets")
         return NearestSets(*out, int(window))
 
@@ -1413,26 +1192,16 @@ class Database:
         every integer, without distance rows in device memory.  Databases with more files than igd_hip_nearest_fused_max_files()
         take nearest_sets()'s route.  out, when given, is a list of three C-ordered int64[nsets, nfiles + 1] that are
         overwritten."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
-        nsets = len(set_off) - 1
-        if nsets < 0:
-            raise IgdError("nearest_sets_fused: set_off needs nsets + 1 entries")
-        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("nearest_sets_fused: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
-        out = _three_out(out, (nsets, self.nfiles + 1), "nearest_sets_fused")
-        _chk(self._H.igd_hip_nearest_sets_fused(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets,
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "nearest_sets_fused")
+        out = _outs(out, 3, (nsets, self.nfiles + 1), "nearest_sets_fused")
+        _chk(self._H.igd_hip_nearest_sets_fused(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets,
                                                 _window(window, "nearest_sets_fused"), _value_filter(value_filter), *[_ptr(a) for a in out]),
              "igd_hip_nearest_sets_fused")
         return NearestSets(*out, int(window))
 
     def nearest_fused_files(self, paths, window, value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets_fused()."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.nearest_sets_fused(cat[0], cat[1], cat[2], set_off, window, value_filter)
+        return self.nearest_sets_fused(*self._read_sets(paths), window, value_filter)
 
     def permutation_nearest(self, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, out=None):
         """Permutation null of the nearest-record distances of one region set (igd_hip_permute_nearest): "are my regions closer
@@ -1444,11 +1213,10 @@ class Database:
         in it.  Neither the permuted regions nor any distance row leave the device.  out, when given, is a list of three
         C-ordered int64[nperm + 1, nfiles + 1] that are overwritten (untouched when the call raises)."""
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_nearest")
-        if len(ctg_len) != self.nctg:
-            raise IgdError("permutation_nearest: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), self.nctg))
-        out = _three_out(out, (max(int(nperm), 0) + 1, self.nfiles + 1), "permutation_nearest")
+        _ctg_len_matches(ctg_len, self.nctg, "permutation_nearest")
+        out = _outs(out, 3, (max(int(nperm), 0) + 1, self.nfiles + 1), "permutation_nearest")
         _chk(self._H.igd_hip_permute_nearest(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len),
-                                             _perm_mode(mode, "permutation_nearest"), int(seed) & (2 ** 64 - 1), int(nperm),
+                                             _perm_mode(mode, "permutation_nearest"), _seed(seed), int(nperm),
                                              _window(window, "permutation_nearest"), _value_filter(value_filter), *[_ptr(a) for a in out]),
              "igd_hip_permute_nearest")
         return PermutationNearest(*out, int(window), int(nperm))
@@ -1460,11 +1228,7 @@ class Database:
 
     def nearest_files(self, paths, window, value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets()."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.nearest_sets(cat[0], cat[1], cat[2], set_off, window, value_filter)
+        return self.nearest_sets(*self._read_sets(paths), window, value_filter)
 
     def nearest_dev(self, d_ichr, d_qs, d_qe, nq, window, d_dist, d_dmin=None, value_filter=None, stream=None):
         """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_dist (int32[nq * nfiles]) and d_dmin
@@ -1479,14 +1243,9 @@ class Database:
         window lies upstream (at lower coordinates) and +d where it lies downstream, d being nearest()'s distance; at equal d on
         both sides upstream wins; NEAREST_NO_RECORD (-2^31) where file f has no record within the window.  sdmin[q] is the
         row's entry of smallest d, decided the same way.  sdist (int32[nq, nfiles], C order), when given, is overwritten."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        if len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("nearest_signed: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+        ichr, qs, qe = _regions(ichr, qs, qe, "nearest_signed")
         nq = len(qs)
-        if sdist is None:
-            sdist = np.empty((nq, self.nfiles), np.int32)
-        elif sdist.dtype != np.int32 or sdist.shape != (nq, self.nfiles) or not sdist.flags.c_contiguous:
-            raise IgdError("nearest_signed: sdist must be a C-ordered int32[%d, %d]" % (nq, self.nfiles))
+        sdist = _out(sdist, (nq, self.nfiles), np.int32, "sdist", "nearest_signed")
         sdmin = np.empty(nq, np.int32)
         _chk(self._H.igd_hip_nearest_signed(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, _window(window, "nearest_signed"),
                                             _value_filter(value_filter), _ptr(sdist), _ptr(sdmin)), "igd_hip_nearest_signed")
@@ -1499,30 +1258,17 @@ class Database:
         below edges[0], the last bin: at or above edges[-1]); the last column is the any-dataset column, built from sdmin.
         Regions without a record within the window are in no bin: hist.sum(axis=1) is nearest_sets().n_within.  The distance
         rows never leave the device.  hist, when given (C order), is overwritten."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        set_off = np.ascontiguousarray(set_off, dtype=np.int64)
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "nearest_hist")
         edges = _edges(edges, "nearest_hist")
-        nsets = len(set_off) - 1
-        if nsets < 0:
-            raise IgdError("nearest_hist: set_off needs nsets + 1 entries")
-        if set_off[-1] != len(qs) or len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("nearest_hist: set_off[-1] = %d, but %d / %d / %d regions given" % (set_off[-1], len(ichr), len(qs), len(qe)))
         shape = (nsets, len(edges) + 1, self.nfiles + 1)
-        if hist is None:
-            hist = np.empty(shape, np.int64)
-        elif hist.dtype != np.int64 or hist.shape != shape or not hist.flags.c_contiguous:
-            raise IgdError("nearest_hist: hist must be a C-ordered int64[%d, %d, %d]" % shape)
-        _chk(self._H.igd_hip_nearest_hist(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, _window(window, "nearest_hist"),
+        hist = _out(hist, shape, np.int64, "hist", "nearest_hist")
+        _chk(self._H.igd_hip_nearest_hist(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _window(window, "nearest_hist"),
                                           _value_filter(value_filter), _ptr(edges), len(edges), _ptr(hist)), "igd_hip_nearest_hist")
         return NearestHist(hist, edges, int(window))
 
     def nearest_hist_files(self, paths, window, edges, value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the NearestHist of nearest_hist()."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.nearest_hist(cat[0], cat[1], cat[2], set_off, window, edges, value_filter)
+        return self.nearest_hist(*self._read_sets(paths), window, edges, value_filter)
 
     def nearest_signed_dev(self, d_ichr, d_qs, d_qe, nq, window, d_sdist, d_sdmin=None, value_filter=None, stream=None):
         """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_sdist (int32[nq * nfiles]) and d_sdmin
@@ -1538,17 +1284,9 @@ class Database:
         neither side (`bedtools closest -D ref -io -iu` / `-id`); "midpoints": between integer midpoints, an equal midpoint
         counts as downstream at distance 0 (`bedtools reldist`).  Upstream means lower coordinates.  upmin / downmin are the
         minima over the datasets.  up and down (int32[nq, nfiles], C order), when given, are overwritten."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        if len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("flanks: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+        ichr, qs, qe = _regions(ichr, qs, qe, "flanks")
         nq = len(qs)
-        rows = []
-        for name, r in (("up", up), ("down", down)):
-            if r is None:
-                r = np.empty((nq, self.nfiles), np.int32)
-            elif r.dtype != np.int32 or r.shape != (nq, self.nfiles) or not r.flags.c_contiguous:
-                raise IgdError("flanks: %s must be a C-ordered int32[%d, %d]" % (name, nq, self.nfiles))
-            rows.append(r)
+        rows = [_out(r, (nq, self.nfiles), np.int32, name, "flanks") for name, r in (("up", up), ("down", down))]
         upmin, downmin = np.empty(nq, np.int32), np.empty(nq, np.int32)
         _chk(self._H.igd_hip_flank(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, _window(window, "flanks"), _measure(measure, "flanks"),
                                    _value_filter(value_filter), _ptr(rows[0]), _ptr(rows[1]), _ptr(upmin), _ptr(downmin)), "igd_hip_flank")
@@ -1569,24 +1307,16 @@ class Database:
         association.  The last column is the any-dataset column, built from upmin / downmin.  hist.sum(axis=1) is the number
         of flanked regions (igd_amd.reldist_summary gives the fractions).  The rows never leave the device.  hist, when given
         (C order), is overwritten."""
-        ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "flank_reldist")
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "flank_reldist")
         nbins, m = _nbins(nbins, "flank_reldist"), _measure(measure, "flank_reldist")
-        shape = (len(set_off) - 1, nbins, self.nfiles + 1)
-        if hist is None:
-            hist = np.empty(shape, np.int64)
-        elif hist.dtype != np.int64 or hist.shape != shape or not hist.flags.c_contiguous:
-            raise IgdError("flank_reldist: hist must be a C-ordered int64[%d, %d, %d]" % shape)
-        _chk(self._H.igd_hip_flank_reldist(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, shape[0], _window(window, "flank_reldist"),
+        hist = _out(hist, (nsets, nbins, self.nfiles + 1), np.int64, "hist", "flank_reldist")
+        _chk(self._H.igd_hip_flank_reldist(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _window(window, "flank_reldist"),
                                            m, _value_filter(value_filter), nbins, _ptr(hist)), "igd_hip_flank_reldist")
         return FlankReldist(hist, nbins, int(window), m)
 
     def flank_reldist_files(self, paths, window, nbins=50, measure="midpoints", value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the FlankReldist of flank_reldist()."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.flank_reldist(cat[0], cat[1], cat[2], set_off, window, nbins, measure, value_filter)
+        return self.flank_reldist(*self._read_sets(paths), window, nbins, measure, value_filter)
 
     # ---- merged region sets and the base-pair Jaccard per set and dataset -------------------
     def merge_sets(self, ichr, qs, qe, set_off, gap=0):
@@ -1595,10 +1325,10 @@ class Database:
         their offsets per set (int64[nsets + 1]), the regions each run joined (int32) and per set the regions that were dropped
         (unknown contig, zero length, inverted; int64[nsets]).  At gap 0 book-ended regions join.  The order of the regions
         within a set does not matter."""
-        ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "merge_sets")
-        gap, nsets = _gap(gap, "merge_sets"), len(set_off) - 1
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "merge_sets")
+        gap = _gap(gap, "merge_sets")
         out = _merge_out(len(qs), nsets)
-        _chk(self._H.igd_hip_merge_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, gap, *[_ptr(a) for a in out]),
+        _chk(self._H.igd_hip_merge_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, gap, *[_ptr(a) for a in out]),
              "igd_hip_merge_sets")
         return _merge_cut(*out)
 
@@ -1627,12 +1357,9 @@ class Database:
         """The merged base pairs of every dataset (igd_hip_dataset_bp): int64[nfiles + 1], entry f the bp of the union of the
         records of file f that a search under (v, rule, value_filter) counts, the last entry the union over all files.  Computed
         once per (value filter, rule) and kept in the handle: dataset_bp_computed() counts the computations."""
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = _value_filter(value_filter)
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         bp = np.empty(self.nfiles + 1, np.int64)
-        _chk(self._H.igd_hip_dataset_bp(self.dev, vf, rule, bp.ctypes.data), "igd_hip_dataset_bp")
+        _chk(self._H.igd_hip_dataset_bp(self.dev, vf, rule, _ptr(bp)), "igd_hip_dataset_bp")
         return bp
 
     def dataset_bp_computed(self):
@@ -1644,16 +1371,12 @@ class Database:
         search_sets()): JaccardSets(inter int64[nsets, nfiles + 1], set_bp int64[nsets], file_bp int64[nfiles + 1], n_merged,
         n_dropped int64[nsets]).  The sets are merged at gap 0 first, so inter[k, f] is |A_k n B_f| exactly; the last column is
         "any dataset".  igd_amd.jaccard_summary() gives the Jaccard and the containment fractions."""
-        ichr, qs, qe, set_off = _sets_args(ichr, qs, qe, set_off, "jaccard_sets")
-        nsets = len(set_off) - 1
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = _value_filter(value_filter)
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "jaccard_sets")
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         js = JaccardSets(np.empty((nsets, self.nfiles + 1), np.int64), np.empty(nsets, np.int64), np.empty(self.nfiles + 1, np.int64),
                          np.empty(nsets, np.int64), np.empty(nsets, np.int64))
-        _chk(self._H.igd_hip_jaccard_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, vf, rule, _ptr(js.inter),
-                                          _ptr(js.set_bp), js.file_bp.ctypes.data, _ptr(js.n_merged), _ptr(js.n_dropped)), "igd_hip_jaccard_sets")
+        _chk(self._H.igd_hip_jaccard_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, vf, rule, _ptr(js.inter),
+                                          _ptr(js.set_bp), _ptr(js.file_bp), _ptr(js.n_merged), _ptr(js.n_dropped)), "igd_hip_jaccard_sets")
         return js
 
     def permutation_bp(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
@@ -1665,19 +1388,15 @@ class Database:
         file_bp is dataset_bp().  Neither the permuted regions nor the merged runs leave the device.  perm_bp_summary() places
         the observed row in the null distribution."""
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_bp")
-        if len(ctg_len) != self.nctg:
-            raise IgdError("permutation_bp: ctg_len has %d entries, the database %d contigs" % (len(ctg_len), self.nctg))
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = _value_filter(value_filter)
+        _ctg_len_matches(ctg_len, self.nctg, "permutation_bp")
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         rows = max(int(nperm), 0) + 1
         inter, set_bp, n_merged = np.empty((rows, self.nfiles + 1), np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
         dropped, file_bp = np.zeros(1, np.int64), np.empty(self.nfiles + 1, np.int64)
         _chk(self._H.igd_hip_permute_bp(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), _perm_mode(mode, "permutation_bp"),
-                                        int(seed) & (2 ** 64 - 1), int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged),
+                                        _seed(seed), int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged),
                                         _ptr(dropped)), "igd_hip_permute_bp")
-        _chk(self._H.igd_hip_dataset_bp(self.dev, vf, rule, file_bp.ctypes.data), "igd_hip_dataset_bp")
+        _chk(self._H.igd_hip_dataset_bp(self.dev, vf, rule, _ptr(file_bp)), "igd_hip_dataset_bp")
         return PermutationBp(inter, set_bp, n_merged, int(dropped[0]), file_bp, int(nperm))
 
     def permutation_bp_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0):
@@ -1696,18 +1415,10 @@ class Database:
         records' value column; agg is 0 where count is 0 and, under "count", holds the counts.  value_filter: only records with
         value >= it are counted.  There is no tile rule.  count and agg (C order), when given, are overwritten: every word is
         defined by the call.  "sum", "min" and "max" on a database without values raise."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
-        if len(ichr) != len(qs) or len(qe) != len(qs):
-            raise IgdError("map_values: %d / %d / %d regions given" % (len(ichr), len(qs), len(qe)))
+        ichr, qs, qe = _regions(ichr, qs, qe, "map_values")
         nq, o = len(qs), _map_op(op, "map_values")
-        if count is None:
-            count = np.empty((nq, self.nfiles), np.int32)
-        elif count.dtype != np.int32 or count.shape != (nq, self.nfiles) or not count.flags.c_contiguous:
-            raise IgdError("map_values: count must be a C-ordered int32[%d, %d]" % (nq, self.nfiles))
-        if agg is None:
-            agg = np.empty((nq, self.nfiles), np.int64)
-        elif agg.dtype != np.int64 or agg.shape != (nq, self.nfiles) or not agg.flags.c_contiguous:
-            raise IgdError("map_values: agg must be a C-ordered int64[%d, %d]" % (nq, self.nfiles))
+        count = _out(count, (nq, self.nfiles), np.int32, "count", "map_values")
+        agg = _out(agg, (nq, self.nfiles), np.int64, "agg", "map_values")
         _chk(self._H.igd_hip_map(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq, o, _value_filter(value_filter), _ptr(count), _ptr(agg)),
              "igd_hip_map")
         return count, agg
@@ -1717,21 +1428,16 @@ class Database:
         three int64[nsets, nfiles] -- the regions of the set with a counted record of the file, the counted (region, record)
         pairs, and the sum of the regions' agg (under "count": the pairs).  The rows never leave the device.  out, when given,
         is a list of three C-ordered int64[nsets, nfiles] that are overwritten."""
-        ichr, qs, qe, set_off = _map_sets_args(ichr, qs, qe, set_off, "map_sets")
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "map_sets")
         o = _map_op(op, "map_sets")
-        nsets = len(set_off) - 1
-        out = _three_out(out, (nsets, self.nfiles), "map_sets")
-        _chk(self._H.igd_hip_map_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), set_off.ctypes.data, nsets, o, _value_filter(value_filter),
+        out = _outs(out, 3, (nsets, self.nfiles), "map_sets")
+        _chk(self._H.igd_hip_map_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, o, _value_filter(value_filter),
                                       *[_ptr(a) for a in out]), "igd_hip_map_sets")
         return MapSets(*out, op)
 
     def map_files(self, paths, op, value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the MapSets of map_sets()."""
-        sets = [self.read_queries(p) for p in paths]
-        set_off = np.zeros(len(sets) + 1, np.int64)
-        set_off[1:] = np.cumsum([len(s[1]) for s in sets])
-        cat = [np.concatenate([s[i] for s in sets]) if sets else np.zeros(0, np.int32) for i in range(3)]
-        return self.map_sets(cat[0], cat[1], cat[2], set_off, op, value_filter)
+        return self.map_sets(*self._read_sets(paths), op, value_filter)
 
     def map_dev(self, d_ichr, d_qs, d_qe, nq, d_count, d_agg=None, op="sum", value_filter=None, stream=None):
         """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_count (int32[nq * nfiles]) and d_agg
@@ -1745,10 +1451,7 @@ class Database:
         """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_bits (uint32[nq * member_words]) and
         d_nfiles_hit (int32[nq], may be None) are overwritten, d_nhit (int64[1], may be None) is added to.  nq above
         igd_hip_max_batch() is refused: split the batch, rows are per query."""
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         _chk(self._H.igd_hip_membership_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), vf, rule, d_bits, d_nfiles_hit, d_nhit,
                                             stream), "igd_hip_membership_dev")
 
@@ -1767,10 +1470,7 @@ class Database:
         """Resident batch: arguments are device pointers (ints).  Asynchronous.
         flags: 0, IGD_HIP_FLAG_SORTED (verified promise; sync() raises if broken) [| IGD_HIP_FLAG_SHORT: no query as long as a tile,
         verified too -- a dense batch then takes the DIRECT step] or IGD_HIP_FLAG_BUCKET (known to be unordered: no order check)."""
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         _chk(self._H.igd_hip_search_dev(self.dev, d_ichr, d_qs, d_qe, int(nq), vf, rule, int(flags), d_hits,
                                         d_total, stream), "igd_hip_search_dev")
 
@@ -1778,10 +1478,7 @@ class Database:
                         value_filter=None, stream=None, flags=0):
         """Resident position-sorted batch given as contig runs (device int32[nctg + 1]: queries [run[c], run[c + 1]) lie on
         contig c) instead of one contig number per query.  Asynchronous; implies the order promise."""
-        if rule is None:
-            rule, vf = self.cli_dispatch(self.gtype, v)
-        else:
-            vf = N.IGD_HIP_NO_VALUE_FILTER if value_filter is None else int(value_filter)
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         _chk(self._H.igd_hip_search_runs_dev(self.dev, d_run_start, d_qs, d_qe, int(nq), vf, rule, int(flags), d_hits,
                                              d_total, stream), "igd_hip_search_runs_dev")
 
@@ -1799,13 +1496,13 @@ class Database:
 
     def enumerate(self, ichr, qs, qe):
         """`-f`: returns (qoff int64[nq+1], records int32[n,4] = q,idx,start,end) in reference order."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        ichr, qs, qe = _regions(ichr, qs, qe)
         nq = len(qs)
         qoff = np.zeros(nq + 1, np.int64)
         out = C.POINTER(N.HipHit)()
         total = C.c_int64(0)
-        _chk(self._H.igd_hip_enumerate(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, nq,
-                                       qoff.ctypes.data, C.byref(out), C.byref(total)), "igd_hip_enumerate")
+        _chk(self._H.igd_hip_enumerate(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq,
+                                       _ptr(qoff), C.byref(out), C.byref(total)), "igd_hip_enumerate")
         n = total.value
         if n:
             rec = np.ctypeslib.as_array(C.cast(out, N.i32p), shape=(n * 4,)).reshape(n, 4).copy()
@@ -1817,7 +1514,7 @@ class Database:
     def enumerate_stream(self, ichr, qs, qe, on_chunk=None):
         """`-f`, streamed (igd_hip_enumerate_stream): on_chunk(q0, q1, qoff, rec) is called per chunk with
         rec = int32[n,4] VIEW of the pinned chunk buffer (valid during the call only).  Returns (qoff, total)."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        ichr, qs, qe = _regions(ichr, qs, qe)
         nq = len(qs)
         qoff = np.zeros(nq + 1, np.int64)
         total = C.c_int64(0)
@@ -1831,8 +1528,8 @@ class Database:
             return 0
 
         cb = N.ENUM_SINK(sink)
-        _chk(self._H.igd_hip_enumerate_stream(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, nq,
-                                              qoff.ctypes.data, cb, None, C.byref(total)), "igd_hip_enumerate_stream")
+        _chk(self._H.igd_hip_enumerate_stream(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq,
+                                              _ptr(qoff), cb, None, C.byref(total)), "igd_hip_enumerate_stream")
         return qoff, total.value
 
     def hit8_idx_bits(self):
@@ -1844,7 +1541,7 @@ class Database:
         """`-f`, streamed in 8 bytes per overlap (igd_hip_enumerate_stream8): on_chunk(q0, q1, qoff, rec, bits) is called per chunk
         with rec = uint32[n,2] VIEW of the pinned chunk buffer: rec[:,0] = start, rec[:,1] = (end - start) << bits | idx.
         Returns (qoff, total)."""
-        ichr, qs, qe = _i32(ichr), _i32(qs), _i32(qe)
+        ichr, qs, qe = _regions(ichr, qs, qe)
         nq = len(qs)
         qoff = np.zeros(nq + 1, np.int64)
         total = C.c_int64(0)
@@ -1858,8 +1555,8 @@ class Database:
             return 0
 
         cb = N.ENUM_SINK8(sink)
-        _chk(self._H.igd_hip_enumerate_stream8(self.dev, ichr.ctypes.data, qs.ctypes.data, qe.ctypes.data, nq,
-                                               qoff.ctypes.data, cb, None, C.byref(total)), "igd_hip_enumerate_stream8")
+        _chk(self._H.igd_hip_enumerate_stream8(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), nq,
+                                               _ptr(qoff), cb, None, C.byref(total)), "igd_hip_enumerate_stream8")
         return qoff, total.value
 
     @staticmethod
@@ -1885,8 +1582,8 @@ class Database:
         query lines, known contig or not) and nr (regions per dataset) the similarity S = sum/(Nq+nr-sum)."""
         a = [np.ascontiguousarray(x, dtype=np.int32) for x in (ichr, qs, qe, qgroup)]
         sums = np.zeros(max(self.nfiles, 1), np.float64)
-        _chk(self._H.igd_hip_seqpare(self.dev, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, len(a[0]),
-                                     a[3].ctypes.data, int(ngroups), sums.ctypes.data), "igd_hip_seqpare")
+        _chk(self._H.igd_hip_seqpare(self.dev, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), len(a[0]),
+                                     _ptr(a[3]), int(ngroups), _ptr(sums)), "igd_hip_seqpare")
         sums = sums[:self.nfiles]
         if n_queries_total is None or nr is None:
             return sums
