@@ -9,7 +9,7 @@ __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "re
            "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD",
            "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
            "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP",
-           "permute_bp_host", "perm_bp_summary", "PermutationBp"]
+           "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace"]
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -35,7 +35,7 @@ def __getattr__(name):
                 "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD",
                 "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
                 "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP",
-                "permute_bp_host", "perm_bp_summary", "PermutationBp"):
+                "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

@@ -98,6 +98,13 @@ class CoreQueries(C.Structure):
                 ("unsorted", C.c_int32), ("max_len", C.c_int32)]
 
 
+class HipWorkspace(C.Structure):
+    """struct igd_hip_workspace of include/igd_hip.h: the table of a workspace (w_off int64[nctg + 1], w_start and w_len
+    int32[nseg], w_pre int32[nseg + nctg])"""
+    _fields_ = [("nctg", C.c_int32), ("nseg", C.c_int64), ("w_off", C.c_void_p), ("w_start", C.c_void_p), ("w_len", C.c_void_p),
+                ("w_pre", C.c_void_p)]
+
+
 IGD_HIP_RULE_NEST = 0
 IGD_HIP_RULE_FLAT = 1
 class HipTraffic(C.Structure):
@@ -200,6 +207,9 @@ def hip():
         L.igd_hip_perm_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p] + [C.c_void_p] * 6
         L.igd_hip_permute_grid.argtypes = [C.c_int64]
         L.igd_hip_permute_grid.restype = C.c_int32
+        # the same inside a workspace: the last argument is a const igd_hip_workspace * (NULL: the entry above)
+        L.igd_hip_permute_support_ws.argtypes = L.igd_hip_permute_support_ov.argtypes + [C.c_void_p]
+        L.igd_hip_permute_regions_ws.argtypes = L.igd_hip_permute_regions.argtypes + [C.c_void_p]
         L.igd_hip_membership.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
@@ -239,6 +249,7 @@ def hip():
         # n_merged, n_dropped / pc, nq
         L.igd_hip_permute_bp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
                                          C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_permute_bp_ws.argtypes = L.igd_hip_permute_bp.argtypes + [C.c_void_p]
         L.igd_hip_merge_slices_per_row.argtypes = [C.c_int64, C.c_int64]
         L.igd_hip_merge_slices_per_row.restype = C.c_int64
         # the fused route and the permutation null of the distances: as igd_hip_nearest_sets / db, ichr, qs, qe, nq, ctg_len, mode,
@@ -247,6 +258,7 @@ def hip():
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_permute_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
                                               C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_permute_nearest_ws.argtypes = L.igd_hip_permute_nearest.argtypes + [C.c_void_p]
         L.igd_hip_nearest_fused_max_files.argtypes = []
         L.igd_hip_nearest_fused_max_files.restype = C.c_int32
         L.igd_hip_nearest_fused_grid.argtypes = [C.c_int64]
@@ -434,6 +446,21 @@ def _bind_core(L):
     L.igdc_permute_bp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                        C.c_uint64, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.igdc_perm_bp_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 14
+    # the workspace of the permutation nulls: ichr, a, b, n, ctg_len, nctg, out / table / table, ctg_len, nctg / table, ctg_len,
+    # ichr, qs, qe, nq / table, ichr, qs, qe, nq / db, path, ctg_len, out; and the four host routes with the table behind them
+    L.igdc_workspace_build.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.POINTER(HipWorkspace))]
+    L.igdc_workspace_free.argtypes = [C.c_void_p]
+    L.igdc_workspace_free.restype = None
+    L.igdc_workspace_valid.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.igdc_workspace_first_unplaceable.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.igdc_workspace_first_unplaceable.restype = C.c_int64
+    L.igdc_workspace_outside.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.igdc_workspace_outside.restype = C.c_int64
+    L.igdc_read_workspace.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.POINTER(HipWorkspace))]
+    L.igdc_permute_regions_host_ws.argtypes = L.igdc_permute_regions_host.argtypes + [C.c_void_p]
+    L.igdc_permute_host_ws.argtypes = L.igdc_permute_host_ov.argtypes + [C.c_void_p]
+    L.igdc_permute_nearest_host_ws.argtypes = L.igdc_permute_nearest_host.argtypes + [C.c_void_p]
+    L.igdc_permute_bp_host_ws.argtypes = L.igdc_permute_bp_host.argtypes + [C.c_void_p]
     # db, path, len (int32[nCtg]), bad_line
     L.igdc_read_genome.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L

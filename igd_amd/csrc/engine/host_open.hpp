@@ -42,7 +42,7 @@ extern "C" void igd_hip_close(igd_hip_db *db)
                     db->d_slab, db->d_qc, db->d_qs, db->d_qe, db->d_hits, db->d_total, db->d_qw, db->d_later, db->d_spill, db->d_laterHdr, db->d_lpos, db->d_cov,
                     db->d_spTable, db->d_spT, db->d_runIchr, db->d_spSub, db->d_setRows, db->d_setTot, db->d_setSlices, db->d_supBits, db->d_covFront,
                     db->d_memBits, db->d_memNf, db->d_memHit, db->d_fisher, db->d_rsUni, db->d_rsTab, db->d_rsSize, db->d_rsBits,
-                    db->d_coCols, db->d_coMat, db->d_coA, db->d_coB, db->d_pmReg, db->d_pmStat,
+                    db->d_coCols, db->d_coMat, db->d_coA, db->d_coB, db->d_pmReg, db->d_pmStat, db->d_pmWs,
                     db->d_grpStat, db->d_grpSlices, db->d_nrDist, db->d_nrMin, db->d_nrEdges,
                     db->d_mpCount, db->d_mpAgg, db->d_merge, db->d_pbRun, db->d_pbWord};
     for (void *p : ptrs)

@@ -22,6 +22,75 @@ static int64_t perm_row_bytes(void)
 // workgroups igd_permute_regions is launched with for n outputs: a lane takes a second one only when n exceeds the grid's lanes
 extern "C" int32_t igd_hip_permute_grid(int64_t n) { return items_grid(n, IGD_SETS_WG); }
 
+// THE PLACEMENT OF ONE CALL, written once for the four launch sites (here twice, host_permute_nearest.hpp, host_permute_bp.hpp):
+// the mode and, under IGD_HIP_PERM_WORKSPACE, the table on the device (db->d_pmWs).
+struct PermPlace {
+    int mode;
+    const int64_t *wOff;
+    const int32_t *wStart, *wLen, *wPre;
+};
+
+// a mode the call can run: the two free placements without a workspace, IGD_HIP_PERM_WORKSPACE with one
+static bool perm_mode_ok(int mode, const igd_hip_workspace *ws)
+{
+    return ws ? mode == IGD_HIP_PERM_WORKSPACE : (mode == IGD_HIP_PERM_CIRCULAR || mode == IGD_HIP_PERM_SHUFFLE);
+}
+
+// true, g_err set: the table is not valid for these contigs or -- drivers only, behind their own check of the regions -- a
+// region on a known contig fits in no segment
+static bool perm_ws_refused(const char *who, const igd_hip_workspace *ws, const int32_t *ctg_len, int32_t nctg, const int32_t *ichr,
+                            const int32_t *qs, const int32_t *qe, int64_t nq, bool mustFit)
+{
+    if (!ws) return false;
+    if (!igd_hip_workspace_valid(ws, ctg_len, nctg)) {
+        snprintf(g_err, sizeof g_err, "%s: the workspace table is not valid for the %d contigs of the call", who, (int)nctg);
+        return true;
+    }
+    for (int64_t i = 0; mustFit && i < nq; i++) {
+        int32_t s = qs[i], e = qe[i];
+        if (igd_hip_perm_place_ws(0, ichr[i], i, ctg_len, nctg, ws->w_off, ws->w_start, ws->w_len, ws->w_pre, &s, &e)) {
+            snprintf(g_err, sizeof g_err, "%s: region %lld = (%d, %d, %d) fits in no segment of the workspace on its contig", who, (long long)i,
+                     (int)ichr[i], (int)qs[i], (int)qe[i]);
+            return true;
+        }
+    }
+    return false;
+}
+
+// the table of a checked workspace into db->d_pmWs, on the engine's stream; without one only the mode is kept
+static int perm_place_upload(igd_hip_db *db, int mode, const igd_hip_workspace *ws, PermPlace *pl)
+{
+    *pl = PermPlace{mode, nullptr, nullptr, nullptr, nullptr};
+    if (!ws) return IGD_HIP_OK;
+    const int64_t nc = ws->nctg, ns = ws->nseg;
+    const int rc = dev_grow(db, &db->d_pmWs, &db->pmWsCap, 2 * (nc + 1) + 3 * ns + nc + 1);
+    if (rc != IGD_HIP_OK) return rc;
+    int64_t *dOff = (int64_t *)db->d_pmWs;
+    int32_t *dStart = db->d_pmWs + 2 * (nc + 1), *dLen = dStart + ns, *dPre = dLen + ns;
+    HIPCHK(hipMemcpyAsync(dOff, ws->w_off, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, db->stream));
+    if (ns > 0) {
+        HIPCHK(hipMemcpyAsync(dStart, ws->w_start, (size_t)ns * 4, hipMemcpyHostToDevice, db->stream));
+        HIPCHK(hipMemcpyAsync(dLen, ws->w_len, (size_t)ns * 4, hipMemcpyHostToDevice, db->stream));
+    }
+    if (ns + nc > 0) HIPCHK(hipMemcpyAsync(dPre, ws->w_pre, (size_t)(ns + nc) * 4, hipMemcpyHostToDevice, db->stream));
+    *pl = PermPlace{mode, dOff, dStart, dLen, dPre};
+    return IGD_HIP_OK;
+}
+
+// `total` outputs (permutations from p0 on, nq regions each) by the kernel of the call's placement
+static int permute_launch(igd_hip_db *db, const PermPlace &pl, const int32_t *rC, const int32_t *rS, const int32_t *rE, int64_t nq,
+                          const int32_t *rL, int32_t nctg, u64 seed, u64 p0, int64_t total, int32_t *oC, int32_t *oS, int32_t *oE)
+{
+    const unsigned grid = (unsigned)igd_hip_permute_grid(total);
+    if (pl.mode == IGD_HIP_PERM_WORKSPACE)
+        igd_permute_workspace<<<grid, IGD_SETS_WG, 0, db->stream>>>(rC, rS, rE, (unsigned)nq, rL, nctg, pl.wOff, pl.wStart, pl.wLen, pl.wPre, seed,
+                                                                  p0, (unsigned)total, oC, oS, oE);
+    else
+        igd_permute_regions<<<grid, IGD_SETS_WG, 0, db->stream>>>(rC, rS, rE, (unsigned)nq, rL, nctg, pl.mode, seed, p0, (unsigned)total, oC, oS, oE);
+    HIPCHK(hipGetLastError());
+    return IGD_HIP_OK;
+}
+
 // igd_perm_stats over nrows rows (device) into the six arrays at d_st; d_tot: see permute_dev.hpp
 static int perm_stats_launch(igd_hip_db *db, const int64_t *d_rows, const int64_t *d_tot, int64_t nrows, int64_t ncols,
                              const long long *d_obs, long long *d_st)
@@ -61,10 +130,10 @@ static void perm_copy_out(const int64_t *res, int64_t nC, int64_t *const out[7])
         if (out[a]) memcpy(out[a], res + a * nC, (size_t)nC * 8);
 }
 
-extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+extern "C" int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                                           const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule,
                                           int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
-                                          int64_t *pmax, const igd_hip_min_overlap *min_overlap)
+                                          int64_t *pmax, const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
 {
     if (!igd_hip_min_overlap_valid(min_overlap)) {
         snprintf(g_err, sizeof g_err, "igd_hip_permute_support: min_overlap (%d bp, %d ppm, %d ppm) out of range", (int)min_overlap->min_bp,
@@ -74,7 +143,7 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
     const bool ov = igd_hip_min_overlap_active(min_overlap);
     const MinOv mo = min_ov_of(min_overlap);
     if (!db || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE)) {
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || !perm_mode_ok(mode, ws)) {
         snprintf(g_err, sizeof g_err, "igd_hip_permute_support: bad argument");
         return IGD_HIP_ERR_ARG;
     }
@@ -101,6 +170,7 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
             return IGD_HIP_ERR_ARG;
         }
     }
+    if (perm_ws_refused("igd_hip_permute_support", ws, ctg_len, db->nCtg, ichr, qs, qe, nq, true)) return IGD_HIP_ERR_ARG;
     const int64_t nF = db->nFiles, nC = nF + 1;
     int64_t *const out[7] = {observed, sum, sumsq, n_ge, n_le, pmin, pmax};
     std::vector<int64_t> res((size_t)(7 * nC));
@@ -129,6 +199,8 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
     if (rc == IGD_HIP_OK) rc = sets_ws(db, pc * nF, pc, pc * perRow);
     if (rc == IGD_HIP_OK) rc = ensure_support_bits(db, maxGrid);
+    PermPlace pl;
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, mode, ws, &pl);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
     long long *dObs = db->d_pmStat, *dSt = dObs + nC;
@@ -154,9 +226,7 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
     if ((rc = perm_stats_init(db, dSt, nC)) != IGD_HIP_OK) return rc;
     for (int64_t p0 = 0; p0 < nperm; p0 += pc) {
         const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
-        igd_permute_regions<<<igd_hip_permute_grid(n * nq), IGD_SETS_WG, 0, st>>>(rC, rS, rE, (unsigned)nq, rL, db->nCtg, mode, (u64)seed, (u64)p0,
-                                                                               (unsigned)(n * nq), db->d_qc, db->d_qs, db->d_qe);
-        HIPCHK(hipGetLastError());
+        if ((rc = permute_launch(db, pl, rC, rS, rE, nq, rL, db->nCtg, (u64)seed, (u64)p0, n * nq, db->d_qc, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
         if ((rc = count(db->d_qc, db->d_qs, db->d_qe, n)) != IGD_HIP_OK) return rc;
         if ((rc = perm_stats_launch(db, db->d_setRows, db->d_setTot, n, nC, dObs, dSt)) != IGD_HIP_OK) return rc;
     }
@@ -165,6 +235,15 @@ extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, c
     HIPCHK(hipGetLastError());
     perm_copy_out(res.data(), nC, out);
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule,
+                                          int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
+                                          int64_t *pmax, const igd_hip_min_overlap *min_overlap)
+{
+    return igd_hip_permute_support_ws(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax,
+                                      min_overlap, nullptr);
 }
 
 extern "C" int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -176,16 +255,17 @@ extern "C" int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, cons
                                       nullptr);
 }
 
-extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                                       const int32_t *ctg_len, int32_t nctg, int mode, uint64_t seed, int64_t p0, int64_t np,
-                                       int32_t *out_qs, int32_t *out_qe)
+extern "C" int igd_hip_permute_regions_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                          const int32_t *ctg_len, int32_t nctg, int mode, uint64_t seed, int64_t p0, int64_t np,
+                                          int32_t *out_qs, int32_t *out_qe, const igd_hip_workspace *ws)
 {
     if (!db || nq < 0 || np < 0 || p0 < 0 || nctg < 0 || (nctg > 0 && !ctg_len) || (nq > 0 && (!ichr || !qs || !qe)) ||
-        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) ||
+        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || !perm_mode_ok(mode, ws) ||
         nq > max_batch() || (nq > 0 && np > (int64_t)INT32_MAX / nq)) {
         snprintf(g_err, sizeof g_err, "igd_hip_permute_regions: bad argument");
         return IGD_HIP_ERR_ARG;
     }
+    if (perm_ws_refused("igd_hip_permute_regions", ws, ctg_len, nctg, ichr, qs, qe, nq, false)) return IGD_HIP_ERR_ARG;
     if (nq == 0 || np == 0) return IGD_HIP_OK;
     const int64_t pc = max_batch() / nq < np ? max_batch() / nq : np;
     std::vector<int32_t> hs((size_t)(np * nq)), he((size_t)(np * nq));
@@ -193,6 +273,8 @@ extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, cons
     hipStream_t st = db->stream;
     int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg);
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
+    PermPlace pl;
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, mode, ws, &pl);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
     HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
@@ -201,9 +283,7 @@ extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, cons
     if (nctg) HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)nctg * 4, hipMemcpyHostToDevice, st));
     for (int64_t a = 0; a < np; a += pc) {
         const int64_t n = np - a < pc ? np - a : pc;
-        igd_permute_regions<<<igd_hip_permute_grid(n * nq), IGD_SETS_WG, 0, st>>>(rC, rS, rE, (unsigned)nq, rL, nctg, mode, (u64)seed, (u64)(p0 + a),
-                                                                               (unsigned)(n * nq), nullptr, db->d_qs, db->d_qe);
-        HIPCHK(hipGetLastError());
+        if ((rc = permute_launch(db, pl, rC, rS, rE, nq, rL, nctg, (u64)seed, (u64)(p0 + a), n * nq, nullptr, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
         HIPCHK(hipMemcpyAsync(hs.data() + a * nq, db->d_qs, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(he.data() + a * nq, db->d_qe, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
     }
@@ -212,6 +292,13 @@ extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, cons
     memcpy(out_qs, hs.data(), (size_t)(np * nq) * 4);
     memcpy(out_qe, he.data(), (size_t)(np * nq) * 4);
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                       const int32_t *ctg_len, int32_t nctg, int mode, uint64_t seed, int64_t p0, int64_t np,
+                                       int32_t *out_qs, int32_t *out_qe)
+{
+    return igd_hip_permute_regions_ws(db, ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe, nullptr);
 }
 
 extern "C" int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t nrows, int64_t ncols, const int64_t *observed,

@@ -23,12 +23,12 @@ extern "C" int64_t igd_hip_merge_slices_per_row(int64_t pc, int64_t nq)
     return (nq + sliceLen - 1) / sliceLen;
 }
 
-extern "C" int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
-                                  int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp,
-                                  int64_t *n_merged, int64_t *n_dropped)
+extern "C" int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                                     int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp,
+                                     int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
 {
     if (!db || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE)) {
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || !perm_mode_ok(mode, ws)) {
         snprintf(g_err, sizeof g_err, "igd_hip_permute_bp: bad argument");
         return IGD_HIP_ERR_ARG;
     }
@@ -50,6 +50,7 @@ extern "C" int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int
             return IGD_HIP_ERR_ARG;
         }
     }
+    if (perm_ws_refused("igd_hip_permute_bp", ws, ctg_len, db->nCtg, ichr, qs, qe, nq, true)) return IGD_HIP_ERR_ARG;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     if (nq == 0) {                                       // no region: no run, no base pair
         if (inter) memset(inter, 0, (size_t)R * (size_t)nC * 8);
@@ -86,6 +87,8 @@ extern "C" int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
     if (rc == IGD_HIP_OK) rc = sets_ws(db, pc * nF, pc, pc * perRow);
     if (rc == IGD_HIP_OK) rc = merge_ws(db, pc * nq, (int32_t)pc, false, &w);       // (the largest chunk: carved per chunk below)
+    PermPlace pl;
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, mode, ws, &pl);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
     int32_t *mC = db->d_pbRun, *mS = mC + pc * nq, *mE = mS + pc * nq;
@@ -127,9 +130,7 @@ extern "C" int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int
     HIPCHK(hipMemcpyAsync(hDrop, dDrop, 8, hipMemcpyDeviceToHost, st));
     for (int64_t p0 = 0; p0 < nperm; p0 += pc) {
         const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
-        igd_permute_regions<<<igd_hip_permute_grid(n * nq), IGD_SETS_WG, 0, st>>>(rC, rS, rE, (unsigned)nq, rL, db->nCtg, mode, (u64)seed, (u64)p0,
-                                                                               (unsigned)(n * nq), db->d_qc, db->d_qs, db->d_qe);
-        HIPCHK(hipGetLastError());
+        if ((rc = permute_launch(db, pl, rC, rS, rE, nq, rL, db->nCtg, (u64)seed, (u64)p0, n * nq, db->d_qc, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
         if ((rc = count(db->d_qc, db->d_qs, db->d_qe, n, 1 + p0)) != IGD_HIP_OK) return rc;
     }
     HIPCHK(hipStreamSynchronize(st));
@@ -143,4 +144,11 @@ extern "C" int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int
     if (n_merged) memcpy(n_merged, hRuns, (size_t)R * 8);
     if (n_dropped) *n_dropped = *hDrop;
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                                  int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp,
+                                  int64_t *n_merged, int64_t *n_dropped)
+{
+    return igd_hip_permute_bp_ws(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, nullptr);
 }

@@ -100,13 +100,13 @@ static int nearest_rows_reduce(igd_hip_db *db, const int32_t *c, const int32_t *
     return IGD_HIP_OK;
 }
 
-extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
-                                       int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+extern "C" int igd_hip_permute_nearest_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                                          int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws)
 {
     if (nearest_window_bad("igd_hip_permute_nearest", window)) return IGD_HIP_ERR_ARG;
     if (!db || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE)) {
+        !perm_mode_ok(mode, ws)) {
         snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: bad argument");
         return IGD_HIP_ERR_ARG;
     }
@@ -128,6 +128,7 @@ extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, cons
             return IGD_HIP_ERR_ARG;
         }
     }
+    if (perm_ws_refused("igd_hip_permute_nearest", ws, ctg_len, db->nCtg, ichr, qs, qe, nq, true)) return IGD_HIP_ERR_ARG;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     int64_t *const outs[3] = {n_within, n_overlap, sum_dist};
     if (nq == 0 || nF == 0) {                            // every statistic is 0: no region, or no dataset to be near
@@ -156,6 +157,8 @@ extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, cons
     if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_grpStat, &db->grpStatCap, 3 * pc * nC);
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
     if (rc == IGD_HIP_OK && fused) rc = dev_grow(db, &db->d_grpSlices, &db->grpSliceCap, pc * perRow);
+    PermPlace pl;
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, mode, ws, &pl);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
     HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
@@ -179,9 +182,7 @@ extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, cons
     if ((rc = count(rC, rS, rE, 1, 0)) != IGD_HIP_OK) return rc;         // the set as given
     for (int64_t p0 = 0; p0 < nperm; p0 += pc) {
         const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
-        igd_permute_regions<<<igd_hip_permute_grid(n * nq), IGD_SETS_WG, 0, st>>>(rC, rS, rE, (unsigned)nq, rL, db->nCtg, mode, (u64)seed, (u64)p0,
-                                                                               (unsigned)(n * nq), db->d_qc, db->d_qs, db->d_qe);
-        HIPCHK(hipGetLastError());
+        if ((rc = permute_launch(db, pl, rC, rS, rE, nq, rL, db->nCtg, (u64)seed, (u64)p0, n * nq, db->d_qc, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
         if ((rc = count(db->d_qc, db->d_qs, db->d_qe, n, 1 + p0)) != IGD_HIP_OK) return rc;
     }
     HIPCHK(hipStreamSynchronize(st));
@@ -189,4 +190,11 @@ extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, cons
     for (int i = 0; i < 3; i++)
         if (outs[i]) memcpy(outs[i], res.data() + (size_t)i * (size_t)(R * nC), (size_t)(R * nC) * 8);
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                                       int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    return igd_hip_permute_nearest_ws(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap, sum_dist, nullptr);
 }

@@ -72,6 +72,7 @@ static int device_from_env(void)
 }
 
 static int g_fail_rc = 0;            /* code of the first engine failure of this process (0: none) */
+static int g_usage_rc = 0;           /* a refusal found in the input files of `-P .. -W` (exit code EX_USAGE; 0: none) */
 
 int igd_engine_status(void) { return g_fail_rc; }
 
@@ -1458,9 +1459,16 @@ static void cooccur_file(char *path, int32_t v)
  * message that names the line. */
 /* `-D W` switches the statistic from support to distance (permute_nearest_table below); window < 0: the support. */
 static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int32_t window);
+/* `-W workspace.bed` places the regions inside a workspace (include/igd_hip.h: THE WORKSPACE; pmode is IGD_HIP_PERM_WORKSPACE then
+ * and -M is refused): the file is read as a query file is, built into the table once (igdc_read_workspace) and handed to the _ws
+ * form of the statistic's route; the three tables keep their layout.  A workspace without a usable segment and a region that
+ * fits in no segment of its contig end the run with a message (the latter names the line) and exit code EX_USAGE; regions that
+ * do not lie inside the workspace as given are counted on stderr and the run goes on.  g_ws: the table of the run, or NULL. */
+static const igd_hip_workspace *g_ws = NULL;
 /* `-G` switches it to base pairs (permute_bp_table below); it takes no sum of squares on the device, so the guard on it does not apply. */
 static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int rule);
-static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t seed, int pmode, int32_t v, int32_t window, int gbp)
+static void permute_file(char *path, const char *genome, const char *wsName, int64_t nperm, uint64_t seed, int pmode, int32_t v, int32_t window,
+                         int gbp)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
@@ -1478,7 +1486,8 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
     /* the accepted lines as igdc_read_queries accepts them, read here so that a refusal can name its line */
     igdc_queries q;
     memset(&q, 0, sizeof q);
-    int64_t no = 0;
+    int64_t no = 0, *lineOf = NULL, lineCap = 0;                             /* -W: the line of every accepted region */
+    igd_hip_workspace *ws = NULL;
     igdc_lines *r = igdc_lines_open(path);
     char *line;
     while (r && (line = igdc_lines_next(r, NULL)) != NULL) {
@@ -1497,7 +1506,33 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
                    (int)st, (int)en, (int)len[id]);
             goto done;
         }
+        if (wsName && q.n == lineCap) {
+            int64_t *grown = (int64_t *)realloc(lineOf, sizeof(int64_t) * (size_t)(lineCap ? 2 * lineCap : 1024));
+            if (!grown) { fprintf(stderr, "igd: out of memory\n"); goto done; }
+            lineOf = grown; lineCap = lineCap ? 2 * lineCap : 1024;
+        }
         if (igdc_queries_push(&q, id, st, en) != 0) { fprintf(stderr, "igd: out of memory\n"); goto done; }
+        if (wsName) lineOf[q.n - 1] = no;
+    }
+    if (wsName) {
+        const int wrc = igdc_read_workspace(g_core, wsName, len, &ws);
+        if (wrc == -1) { printf("Cannot open workspace file %s\n", wsName); goto done; }
+        if (wrc != 0) { fprintf(stderr, "igd: out of memory\n"); goto done; }
+        if (ws->nseg == 0) {
+            printf("Workspace file %s: no usable segment on a contig of the database\n", wsName);
+            g_usage_rc = 1;
+            goto done;
+        }
+        const int64_t bad_i = igdc_workspace_first_unplaceable(ws, len, q.ichr, q.qs, q.qe, q.n);
+        if (bad_i >= 0) {
+            printf("%s, line %lld: region %s:%d-%d fits in no segment of the workspace %s on its contig\n", path, (long long)lineOf[bad_i],
+                   g_core->cName[q.ichr[bad_i]], (int)q.qs[bad_i], (int)q.qe[bad_i], wsName);
+            g_usage_rc = 1;
+            goto done;
+        }
+        const int64_t outside = igdc_workspace_outside(ws, q.ichr, q.qs, q.qe, q.n);
+        if (outside > 0) fprintf(stderr, "%lld of %lld regions do not lie inside the workspace\n", (long long)outside, (long long)q.n);
+        g_ws = ws;
     }
     if (q.n > igd_hip_max_batch() ||
         (window < 0 && !gbp && (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63)) {
@@ -1513,11 +1548,11 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
         int64_t *obs = st7, *sum = obs + nC, *ssq = sum + nC, *nge = ssq + nC, *nle = nge + nC, *mn = nle + nC, *mx = mn + nC;
         cli_route R;
         if (route_host(&R, q.n * (nperm + 1)))
-            route_host_end(&R, igdc_permute_host_ov(g_core, R.hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo) == 0,
+            route_host_end(&R, igdc_permute_host_ws(g_core, R.hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo, g_ws) == 0,
                            "permutation null on the host (small files)");
         if (route_engine(&R, 1))
             route_engine_end(&R, "permutation null",
-                             igd_hip_permute_support_ov(R.dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo),
+                             igd_hip_permute_support_ws(R.dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo, g_ws),
                              "permutation null of the query file (H2D + permute, support and statistics kernels + D2H)");
         if (!g_fail_rc && igdc_perm_summary(obs, sum, ssq, nge, nle, nperm, nC, fl, fl + nC, fl + 2 * nC, fl + 3 * nC, fl + 4 * nC) == 0) {
             printf("index\tobserved\tmean\tsd\tz\tn_ge\tn_le\tnlog10_p_upper\tnlog10_p_lower\tFile\n");
@@ -1533,6 +1568,9 @@ static void permute_file(char *path, const char *genome, int64_t nperm, uint64_t
 done:
     if (r) igdc_lines_close(r);
     igdc_queries_free(&q);
+    g_ws = NULL;
+    igdc_workspace_free(ws);
+    free(lineOf);
     free(len);
 }
 
@@ -1758,11 +1796,11 @@ static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int
     double *wm = fl, *ws = wm + nC, *wz = ws + nC, *pu = wz + nC, *md = pu + nC, *dm = md + nC, *ds = dm + nC, *dz = ds + nC, *pl = dz + nC;
     cli_route Rt;
     if (route_host(&Rt, q->n * (nperm + 1)))
-        route_host_end(&Rt, igdc_permute_nearest_host(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd) == 0,
+        route_host_end(&Rt, igdc_permute_nearest_host_ws(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd, g_ws) == 0,
                        "permutation null of the distances on the host (small files)");
     if (route_engine(&Rt, 1))
         route_engine_end(&Rt, "permutation null of the distances",
-                         igd_hip_permute_nearest(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd),
+                         igd_hip_permute_nearest_ws(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd, g_ws),
                          "permutation null of the distances (H2D + permute and fused nearest kernels + D2H)");
     if (!g_fail_rc && igdc_perm_nearest_summary(nw, sd, nperm, (int64_t)nC, wm, ws, wz, nge, pu, md, dm, ds, dz, ndef, nle, pl) == 0) {
         printf("index\tn_within\tmean_dist\twithin_mean\twithin_sd\twithin_z\tnlog10_p_within_upper\tdist_mean\tdist_sd\tdist_z\tn_def\tdist_n_le\t"
@@ -1804,11 +1842,11 @@ static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t 
     double *mu = fl, *sd = mu + nC, *z = sd + nC, *fold = z + nC, *pu = fold + nC, *pl = pu + nC, *jac = pl + nC, *jm = jac + nC, *js = jm + nC;
     cli_route Rt;
     if (route_host(&Rt, q->n * (nperm + 1)))
-        route_host_end(&Rt, igdc_permute_bp_host(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd) == 0 &&
+        route_host_end(&Rt, igdc_permute_bp_host_ws(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd, g_ws) == 0 &&
                            igdc_dataset_bp_host(g_core, Rt.hm, ev, rule, fbp) == 0,
                        "permutation null of the base-pair overlap on the host (small files)");
     if (route_engine(&Rt, 1)) {
-        int rc = igd_hip_permute_bp(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd);
+        int rc = igd_hip_permute_bp_ws(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd, g_ws);
         if (rc == IGD_HIP_OK) rc = igd_hip_dataset_bp(Rt.dev, ev, rule, fbp);
         route_engine_end(&Rt, "permutation null of the base-pair overlap", rc,
                          "permutation null of the base-pair overlap (H2D + permute, merge, hand-over and coverage kernels + D2H)");
@@ -1879,6 +1917,8 @@ static int usage_search(void)
             "    -G                         with -P: the null of the base-pair overlap instead -- per dataset the base pairs the merged\n"
             "                               regions share with it (as -J) placed among the permuted sets' (mean, sd, z, fold, both\n"
             "                               one-sided p) and the Jaccard with the mean permuted one\n"
+            "    -W <workspace file>        with -P: the regions are placed inside the segments of this BED file (centromeres, gaps and\n"
+            "                               blacklisted stretches left out), every fitting start equally likely; instead of -M\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -1948,6 +1988,7 @@ int igd_search(int argc, char **argv)                                        /* 
     char *permArg = NULL, *genomeName = NULL, *seedArg = NULL, *pmodeArg = NULL;      /* -P, -g, -S, -M (see permute_file) */
     char *nearArg = NULL;                                                             /* -N (see nearest_files) */
     char *distArg = NULL;                                                             /* -D (see permute_nearest_table) */
+    char *wsName = NULL;                                                              /* -W (see g_ws) */
     char *histArg = NULL;                                                             /* -H (see nearest_hist_files) */
     char *binsArg = NULL;                                                             /* -L (see flank_reldist_files) */
     int flankL = 0, flankEdges = 0;                                                   /* -L, -E given */
@@ -2021,6 +2062,9 @@ int igd_search(int argc, char **argv)                                        /* 
             if (i + 1 >= argc) { printf("Not supported: -D without a window\n"); return EX_USAGE; }
             distArg = argv[i + 1];
             i++;                                      /* (the window is not an option: "-D -5" is a refused window) */
+        } else if (strcmp(a, "-W") == 0) {            /* (not the reference's: -P inside a workspace, see g_ws) */
+            if (i + 1 >= argc) { printf("Not supported: -W without a workspace file\n"); return EX_USAGE; }
+            wsName = argv[i + 1];
         } else if (strcmp(a, "-g") == 0) {
             if (i + 1 >= argc) { printf("No genome file.\n"); return EX_OK; }
             genomeName = argv[i + 1];
@@ -2052,6 +2096,10 @@ int igd_search(int argc, char **argv)                                        /* 
     }
 
     long long np = 0;                                                         /* -P's count, once a block below has parsed it */
+    if (wsName) {                                                             /* -W: every refusal is a usage error */
+        if (!permArg) return refused_usage("-W without -P");
+        if (pmodeArg) return refused_usage("-W together with -M (the workspace is the placement)");
+    }
     if (gbp) {                                                                /* -G: every refusal is a usage error */
         const char *why = NULL;
         if (!permArg) why = "-G without -P";
@@ -2188,7 +2236,7 @@ int igd_search(int argc, char **argv)                                        /* 
         printf("Not supported: -P without -q\n");
         return EX_OK;
     } else if (permArg) {
-        const int pmode = parse_perm_mode(pmodeArg);
+        const int pmode = wsName ? IGD_HIP_PERM_WORKSPACE : parse_perm_mode(pmodeArg);
         if (!parse_perm_count(permArg, &np)) {
             printf("Not supported: -P %s (1 to %lld permutations)\n", permArg, (long long)IGD_HIP_PERM_MAX);
             return EX_OK;
@@ -2197,7 +2245,7 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported: -M %s (circular or shuffle)\n", pmodeArg);
             return EX_OK;
         }
-        permute_file(qfName, genomeName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW, gbp);
+        permute_file(qfName, genomeName, wsName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW, gbp);
     } else if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
         printf("Not supported: -C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r\n");
         return EX_OK;
@@ -2305,7 +2353,7 @@ int igd_search(int argc, char **argv)                                        /* 
     free(g_core_path); g_core_path = NULL;
     /* the reference's exit code is always 0; an engine failure (message already on stderr) is the one
      * thing this tool reports through it, instead of printing a table of zeros */
-    return g_fail_rc ? EX_UNAVAILABLE : EX_OK;
+    return g_fail_rc ? EX_UNAVAILABLE : g_usage_rc ? EX_USAGE : EX_OK;
 }
 
 /* ---- create_igd*, src/igd_create.h:10-14 --------------------------------------------------- */

@@ -314,6 +314,43 @@ int igdc_perm_bp_summary(const int64_t *inter, const int64_t *set_bp, const int6
                          int64_t *observed, double *mean, double *sd, double *z, double *fold, int64_t *n_ge, int64_t *n_le,
                          double *nlog10_p_upper, double *nlog10_p_lower, double *jaccard, double *jaccard_mean, double *jaccard_sd,
                          int64_t *jaccard_n_def, int64_t *jaccard_n_ge);
+/* The workspace of the permutation nulls (include/igd_hip.h: THE WORKSPACE has the definition of the table), shared by the
+ * host route and the engine's callers.
+ * igdc_workspace_build: the table of the n segments (ichr, a, b) on nctg contigs of lengths ctg_len: merged at gap 0 through
+ * igdc_merge_host, clipped to the contigs, ordered and summed; *out is one allocation, freed by igdc_workspace_free.  0; -1 for
+ * a missing array, a negative length or no memory (nothing allocated).  A workspace without a segment is a table like any other.
+ * igdc_workspace_valid: igd_hip_workspace_valid as a symbol of the library.
+ * igdc_workspace_first_unplaceable: the first valid region on a known contig that fits in no segment of its contig (T == 0),
+ * or -1; the table must be valid for ctg_len.
+ * igdc_workspace_outside: the regions on known contigs that do not lie inside one segment (s >= a and e <= b; an inverted
+ * region lies in none), or -1 without memory.  Information only: nothing refuses on it.
+ * igdc_read_workspace: a BED file through igdc_read_queries (the command line's rule for `-q`; lines on contigs the
+ * database lacks are dropped), built for the database's contigs.  0; -1 when the file cannot be opened; -2 when the table
+ * could not be built.
+ * The _ws routes are the four host routes above with the table as their last argument: NULL is the route above; with a table
+ * the mode must be IGD_HIP_PERM_WORKSPACE, and -1 (nothing written) is also an invalid table and, in the three drivers, a region
+ * on a known contig that fits in no segment. */
+int igdc_workspace_build(const int32_t *ichr, const int32_t *a, const int32_t *b, int64_t n, const int32_t *ctg_len, int32_t nctg,
+                         igd_hip_workspace **out);
+void igdc_workspace_free(igd_hip_workspace *ws);
+int igdc_workspace_valid(const igd_hip_workspace *ws, const int32_t *ctg_len, int32_t nctg);
+int64_t igdc_workspace_first_unplaceable(const igd_hip_workspace *ws, const int32_t *ctg_len, const int32_t *ichr, const int32_t *qs,
+                                         const int32_t *qe, int64_t nq);
+int64_t igdc_workspace_outside(const igd_hip_workspace *ws, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq);
+int igdc_read_workspace(const igdc_db *db, const char *path, const int32_t *ctg_len, igd_hip_workspace **out);
+int igdc_permute_regions_host_ws(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                                 int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe,
+                                 const igd_hip_workspace *ws);
+int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                         int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
+                         const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws);
+int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                 const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                                 int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws);
+int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                            const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
+                            int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws);
 /* A genome file, lines `name<TAB>length`: len[c] = the length of contig c of the database (int32[nCtg]); lines of contigs the
  * database does not know are ignored, contigs the file does not name get 0.  0; -1 when the file cannot be opened; -2 for a
  * line of a known contig without a length or with one that is negative or above 2^31 - 1 (*bad_line, may be NULL, = its

@@ -335,6 +335,10 @@ struct igd_hip_db {
     int32_t *d_pmReg;
     long long *d_pmStat;
     int64_t pmRegCap, pmStatCap;
+    // the _ws entries of the three permutation nulls (host_permute.hpp): the workspace table of one call, as 32-bit words --
+    // w_off (int64[nctg + 1], in front: 8-byte aligned), then w_start, w_len and w_pre
+    int32_t *d_pmWs;
+    int64_t pmWsCap;
     // run_set_groups (host_nearest.hpp), the driver of igd_hip_nearest_sets(_fused), igd_hip_nearest_hist, igd_hip_flank_reldist and
     // igd_hip_map_sets: the result matrices of one group of sets (64-bit words) and the slice table of one chunk.  One pair for
     // all of them: every user runs on `stream` and waits before it returns.  igd_hip_permute_nearest keeps its chunk's matrices
@@ -401,6 +405,7 @@ struct igd_hip_db {
 #include "engine/restrict_dev.hpp"    // igd_restrict_bits, igd_bits_support: sets restricted to a universe -- the interval join and the gather over member rows
 #include "engine/cooccur_dev.hpp"     // igd_bits_transpose, igd_bitrows_gram: bit rows into bit columns, popcount Gram product -- dataset co-occurrence
 #include "engine/permute_dev.hpp"     // igd_permute_regions, igd_perm_stats: shifted / shuffled region sets, column statistics of a row matrix -- permutation null
+#include "engine/permute_ws_dev.hpp"  // igd_permute_workspace: the same launch, regions placed inside a workspace by two binary searches in a resident table
 #include "engine/nearest_dev.hpp"     // igd_nearest_rows, igd_nearest_reduce, igd_nearest_hist: the same walk over a widened interval, one (signed) distance row per region -- nearest record per dataset
 #include "engine/flank_dev.hpp"       // igd_flank_rows, igd_flank_reldist: the same walk with two minima per region and dataset -- the nearest record on each side, the relative-distance histogram
 #include "engine/nearest_fused_dev.hpp" // igd_nearest_slices: the same walk and table, folded into per-slice LDS accumulators -- the set statistics without the rows

@@ -523,6 +523,49 @@ int32_t igd_hip_permute_grid(int64_t n)
     return fn ? fn(n) : 0;
 }
 
+int igd_hip_permute_regions_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                               int32_t nctg, int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe,
+                               const igd_hip_workspace *ws)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int32_t, int, uint64_t,
+                        int64_t, int64_t, int32_t *, int32_t *, const igd_hip_workspace *);
+    RESOLVE(fn_t, "igd_hip_permute_regions_ws");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe, ws) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                               int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
+                               int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap,
+                               const igd_hip_workspace *ws)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int, uint64_t, int64_t,
+                        int32_t, int, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *, const igd_hip_min_overlap *,
+                        const igd_hip_workspace *);
+    RESOLVE(fn_t, "igd_hip_permute_support_ws");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax, min_overlap, ws)
+              : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_nearest_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                               int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
+                               int64_t *sum_dist, const igd_hip_workspace *ws)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int, uint64_t, int64_t,
+                        int32_t, int32_t, int64_t *, int64_t *, int64_t *, const igd_hip_workspace *);
+    RESOLVE(fn_t, "igd_hip_permute_nearest_ws");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap, sum_dist, ws) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                          int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
+                          int64_t *n_dropped, const igd_hip_workspace *ws)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int, uint64_t, int64_t,
+                        int32_t, int, int64_t *, int64_t *, int64_t *, int64_t *, const igd_hip_workspace *);
+    RESOLVE(fn_t, "igd_hip_permute_bp_ws");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, ws) : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

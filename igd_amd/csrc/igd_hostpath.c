@@ -960,21 +960,156 @@ int igdc_cooccur_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
  * the set as given through igdc_support_host, then threads over the permutations (thread k takes p = k, k + T, ..), each with
  * its own permuted arrays, row and stamp array, walking a permuted set with the per-query code of igdc_support_host and
  * folding the row into its own statistics; the threads' statistics are combined at the end.  All outputs are DEFINED. */
-int igdc_permute_regions_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
-                              int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe)
+/* a mode the call can run: the two free placements without a workspace, IGD_HIP_PERM_WORKSPACE with one (a checked table) */
+static int perm_mode_ok(int mode, const igd_hip_workspace *ws)
 {
-    if (nq < 0 || np < 0 || p0 < 0 || nctg < 0 || (nctg > 0 && !ctg_len) || (nq > 0 && (!ichr || !qs || !qe)) ||
-        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE))
-        return -1;
+    return ws ? mode == IGD_HIP_PERM_WORKSPACE : (mode == IGD_HIP_PERM_CIRCULAR || mode == IGD_HIP_PERM_SHUFFLE);
+}
+
+/* the placement itself, on checked arguments: what the threads of the three drivers call per permutation */
+static void perm_regions_fill(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                              int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe, const igd_hip_workspace *ws)
+{
     for (int64_t p = 0; p < np; p++) {
         const uint64_t base = igd_hip_perm_base(seed, (uint64_t)(p0 + p));
         int32_t *os = out_qs + p * nq, *oe = out_qe + p * nq;
         for (int64_t i = 0; i < nq; i++) {
             os[i] = qs[i]; oe[i] = qe[i];
-            igd_hip_perm_place(mode, base, ichr[i], i, ctg_len, nctg, &os[i], &oe[i]);
+            if (ws) (void)igd_hip_perm_place_ws(base, ichr[i], i, ctg_len, nctg, ws->w_off, ws->w_start, ws->w_len, ws->w_pre, &os[i], &oe[i]);
+            else igd_hip_perm_place(mode, base, ichr[i], i, ctg_len, nctg, &os[i], &oe[i]);
         }
     }
+}
+
+int igdc_permute_regions_host_ws(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                                 int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe,
+                                 const igd_hip_workspace *ws)
+{
+    if (nq < 0 || np < 0 || p0 < 0 || nctg < 0 || (nctg > 0 && !ctg_len) || (nq > 0 && (!ichr || !qs || !qe)) ||
+        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || !perm_mode_ok(mode, ws) || (ws && !igd_hip_workspace_valid(ws, ctg_len, nctg)))
+        return -1;
+    perm_regions_fill(ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe, ws);
     return 0;
+}
+
+int igdc_permute_regions_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                              int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe)
+{
+    return igdc_permute_regions_host_ws(ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe, NULL);
+}
+
+/* ---- the workspace table (include/igd_hip.h: THE WORKSPACE) ---------------------------------------------------------------
+ * igdc_workspace_build: the segments through igdc_merge_host at gap 0 (one set; it needs a database only for the number of
+ * contigs), the runs clipped to [0, ctg_len[c]], per contig ordered by length descending then start ascending, and summed.  The
+ * table and its four arrays are ONE allocation (igdc_workspace_free). */
+typedef struct { int32_t c, a, l; } ws_seg;
+static int ws_seg_cmp(const void *x, const void *y)
+{
+    const ws_seg *p = (const ws_seg *)x, *q = (const ws_seg *)y;
+    if (p->c != q->c) return p->c < q->c ? -1 : 1;
+    if (p->l != q->l) return p->l > q->l ? -1 : 1;
+    return p->a < q->a ? -1 : p->a > q->a;
+}
+
+int igdc_workspace_build(const int32_t *ichr, const int32_t *a, const int32_t *b, int64_t n, const int32_t *ctg_len, int32_t nctg,
+                         igd_hip_workspace **out)
+{
+    if (!out || n < 0 || nctg < 0 || (nctg > 0 && !ctg_len) || (n > 0 && (!ichr || !a || !b))) return -1;
+    for (int32_t c = 0; c < nctg; c++) if (ctg_len[c] < 0) return -1;
+    igdc_db d;
+    memset(&d, 0, sizeof d);
+    d.nCtg = nctg;
+    const int64_t off[2] = {0, n};
+    int64_t moff[2] = {0, 0}, dropped = 0, m = 0;
+    int32_t *mr = (int32_t *)malloc((size_t)(n > 0 ? n : 1) * 3 * sizeof *mr);
+    ws_seg *g = (ws_seg *)malloc((size_t)(n > 0 ? n : 1) * sizeof *g);
+    if (!mr || !g || igdc_merge_host(&d, ichr, a, b, off, 1, 0, mr, mr + n, mr + 2 * n, moff, NULL, &dropped) != 0) { free(mr); free(g); return -1; }
+    for (int64_t r = 0; r < moff[1]; r++) {
+        const int32_t c = mr[r];
+        const int64_t L = ctg_len[c], lo = mr[n + r] < 0 ? 0 : mr[n + r], hi = mr[2 * n + r] > L ? L : mr[2 * n + r];
+        if (hi - lo < 1) continue;
+        g[m].c = c; g[m].a = (int32_t)lo; g[m].l = (int32_t)(hi - lo);
+        m++;
+    }
+    free(mr);
+    qsort(g, (size_t)m, sizeof *g, ws_seg_cmp);
+    /* the struct, then w_off (8-byte words), then the three 32-bit arrays */
+    const size_t bytes = sizeof(igd_hip_workspace) + ((size_t)nctg + 1) * 8 + ((size_t)m * 3 + (size_t)nctg + 1) * 4;
+    char *blk = (char *)malloc(bytes);
+    if (!blk) { free(g); return -1; }
+    igd_hip_workspace *ws = (igd_hip_workspace *)blk;
+    int64_t *w_off = (int64_t *)(blk + sizeof(igd_hip_workspace));
+    int32_t *w_start = (int32_t *)(w_off + nctg + 1), *w_len = w_start + m, *w_pre = w_len + m;
+    int64_t at = 0;
+    for (int32_t c = 0; c < nctg; c++) {
+        int64_t sum = 0;
+        w_off[c] = at;
+        w_pre[at + c] = 0;
+        for (; at < m && g[at].c == c; at++) {
+            w_start[at] = g[at].a; w_len[at] = g[at].l;
+            sum += g[at].l;
+            w_pre[at + c + 1] = (int32_t)sum;
+        }
+    }
+    w_off[nctg] = m;
+    free(g);
+    ws->nctg = nctg; ws->nseg = m; ws->w_off = w_off; ws->w_start = w_start; ws->w_len = w_len; ws->w_pre = w_pre;
+    *out = ws;
+    return 0;
+}
+
+void igdc_workspace_free(igd_hip_workspace *ws) { free(ws); }
+
+int igdc_workspace_valid(const igd_hip_workspace *ws, const int32_t *ctg_len, int32_t nctg) { return igd_hip_workspace_valid(ws, ctg_len, nctg); }
+
+int64_t igdc_workspace_first_unplaceable(const igd_hip_workspace *ws, const int32_t *ctg_len, const int32_t *ichr, const int32_t *qs,
+                                         const int32_t *qe, int64_t nq)
+{
+    for (int64_t i = 0; i < nq; i++) {
+        int32_t s = qs[i], e = qe[i];
+        if (igd_hip_perm_place_ws(0, ichr[i], i, ctg_len, ws->nctg, ws->w_off, ws->w_start, ws->w_len, ws->w_pre, &s, &e)) return i;
+    }
+    return -1;
+}
+
+static int ws_span_cmp(const void *x, const void *y)
+{
+    const int32_t *p = (const int32_t *)x, *q = (const int32_t *)y;
+    return p[0] < q[0] ? -1 : p[0] > q[0];
+}
+
+int64_t igdc_workspace_outside(const igd_hip_workspace *ws, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq)
+{
+    if (!ws || nq < 0 || (nq > 0 && (!ichr || !qs || !qe))) return -1;
+    /* per contig the segments as (start, end) ordered by start: they are disjoint, so the one that can hold a region is the
+     * last that starts at or before it */
+    int32_t *sp = (int32_t *)malloc(((size_t)ws->nseg + 1) * 2 * sizeof *sp);
+    if (!sp) return -1;
+    for (int64_t j = 0; j < ws->nseg; j++) { sp[2 * j] = ws->w_start[j]; sp[2 * j + 1] = ws->w_start[j] + ws->w_len[j]; }
+    for (int32_t c = 0; c < ws->nctg; c++) qsort(sp + 2 * ws->w_off[c], (size_t)(ws->w_off[c + 1] - ws->w_off[c]), 2 * sizeof *sp, ws_span_cmp);
+    int64_t out = 0;
+    for (int64_t i = 0; i < nq; i++) {
+        const int32_t c = ichr[i];
+        if (c < 0 || c >= ws->nctg) continue;
+        int64_t lo = ws->w_off[c], hi = ws->w_off[c + 1];          /* the first segment that starts behind qs[i] */
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (sp[2 * mid] <= qs[i]) lo = mid + 1; else hi = mid;
+        }
+        out += !(lo > ws->w_off[c] && qe[i] >= qs[i] && qe[i] <= sp[2 * (lo - 1) + 1]);
+    }
+    free(sp);
+    return out;
+}
+
+int igdc_read_workspace(const igdc_db *db, const char *path, const int32_t *ctg_len, igd_hip_workspace **out)
+{
+    igdc_queries q;
+    if (!db || !path || !out) return -1;
+    if (igdc_read_queries(db, path, 1, &q) != 0) return -1;
+    const int rc = igdc_workspace_build(q.ichr, q.qs, q.qe, q.n, ctg_len, db->nCtg, out);
+    igdc_queries_free(&q);
+    return rc == 0 ? 0 : -2;
 }
 
 /* the first region on a known contig that breaks 0 <= s <= e <= L, L >= 1; -1: none */
@@ -1000,6 +1135,7 @@ typedef struct {
     int64_t *row, *last;
     int k, T, io_failed;
     const igd_hip_min_overlap *mo;      /* an active minimum overlap, or NULL */
+    const igd_hip_workspace *ws;        /* the checked table of mode IGD_HIP_PERM_WORKSPACE, or NULL */
 } perm_job;
 
 static void *perm_run(void *arg)
@@ -1007,7 +1143,7 @@ static void *perm_run(void *arg)
     perm_job *P = (perm_job *)arg;
     const int64_t nF = P->db->nFiles, nC = nF + 1;
     for (int64_t p = P->k; p < P->nperm && !P->io_failed; p += P->T) {
-        (void)igdc_permute_regions_host(P->ichr, P->qs, P->qe, P->nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, p, 1, P->ps, P->pe);
+        perm_regions_fill(P->ichr, P->qs, P->qe, P->nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, p, 1, P->ps, P->pe, P->ws);
         memset(P->row, 0, sizeof(int64_t) * (size_t)nC);
         memset(P->last, 0, sizeof(int64_t) * (size_t)nC);
         host_job J;
@@ -1035,7 +1171,7 @@ int igdc_permute_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
                       int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax)
 {
-    return igdc_permute_host_ov(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax, NULL);
+    return igdc_permute_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax, NULL, NULL);
 }
 
 int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -1043,12 +1179,29 @@ int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ic
                          int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
                          const igd_hip_min_overlap *min_overlap)
 {
+    return igdc_permute_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax,
+                                min_overlap, NULL);
+}
+
+/* the refusals the three drivers add under a workspace, behind their own: a table that is not valid for the database's contigs,
+ * a region on a known contig that fits in no segment */
+static int perm_ws_refused(const igdc_db *db, const igd_hip_workspace *ws, const int32_t *ctg_len, const int32_t *ichr, const int32_t *qs,
+                           const int32_t *qe, int64_t nq)
+{
+    return ws && (!igd_hip_workspace_valid(ws, ctg_len, db->nCtg) || igdc_workspace_first_unplaceable(ws, ctg_len, ichr, qs, qe, nq) >= 0);
+}
+
+int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                         int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
+                         const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
+{
     const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
     if (!igd_hip_min_overlap_valid(min_overlap) || !db || !m || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) ||
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || !perm_mode_ok(mode, ws) ||
         nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() ||
         (unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63 ||
-        igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0)
+        igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 || perm_ws_refused(db, ws, ctg_len, ichr, qs, qe, nq))
         return -1;
     const int64_t nF = db->nFiles, nC = nF + 1;
     int T = host_threads(nq * nperm > 0 ? nq * nperm : 1);
@@ -1071,7 +1224,7 @@ int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ic
         job[k].acc = w + (size_t)k * 8 * (size_t)nC;
         job[k].row = job[k].acc + 6 * nC; job[k].last = job[k].row + nC;
         job[k].ps = pq + (size_t)k * 2 * (size_t)nq; job[k].pe = job[k].ps + nq;
-        job[k].k = k; job[k].T = T; job[k].mo = mo;
+        job[k].k = k; job[k].T = T; job[k].mo = mo; job[k].ws = ws;
         for (int64_t f = 0; f < nC; f++) { job[k].acc[4 * nC + f] = INT64_MAX; job[k].acc[5 * nC + f] = INT64_MIN; }
     }
     if (rc == 0) {
@@ -1621,6 +1774,7 @@ typedef struct {
     int64_t *res;           /* three matrices of nrows x (nFiles + 1) */
     int32_t *ps, *pe, *row; /* the permuted set, one distance row */
     int k, T, io_failed;
+    const igd_hip_workspace *ws;
 } pnear_job;
 
 static void *pnear_run(void *arg)
@@ -1633,7 +1787,7 @@ static void *pnear_run(void *arg)
     for (int64_t r = P->k; r < P->nrows && !tb.failed; r += P->T) {
         const int32_t *s = P->qs, *e = P->qe;
         if (r > 0) {
-            (void)igdc_permute_regions_host(P->ichr, P->qs, P->qe, P->nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, r - 1, 1, P->ps, P->pe);
+            perm_regions_fill(P->ichr, P->qs, P->qe, P->nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, r - 1, 1, P->ps, P->pe, P->ws);
             s = P->ps; e = P->pe;
         }
         int64_t *nw = P->res + r * nC, *no = nw + P->nrows * nC, *sd = no + P->nrows * nC;
@@ -1658,9 +1812,17 @@ int igdc_permute_nearest_host(const igdc_db *db, const igdc_map *m, const int32_
                               const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
                               int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
 {
+    return igdc_permute_nearest_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap, sum_dist, NULL);
+}
+
+int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                 const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                                 int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws)
+{
     if (!db || !m || nq < 0 || !igd_hip_nearest_window_valid(window) || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) || nperm < 1 || nperm > IGD_HIP_PERM_MAX ||
-        nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0)
+        !perm_mode_ok(mode, ws) || nperm < 1 || nperm > IGD_HIP_PERM_MAX ||
+        nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 ||
+        perm_ws_refused(db, ws, ctg_len, ichr, qs, qe, nq))
         return -1;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     int T = host_threads(nq * R > 0 ? nq * R : 1);
@@ -1678,7 +1840,7 @@ int igdc_permute_nearest_host(const igdc_db *db, const igdc_map *m, const int32_
         job[k].window = window; job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
         job[k].res = res;
         job[k].ps = w + (size_t)k * (2 * (size_t)nq + (size_t)nF); job[k].pe = job[k].ps + nq; job[k].row = job[k].pe + nq;
-        job[k].k = k; job[k].T = T;
+        job[k].k = k; job[k].T = T; job[k].ws = ws;
     }
     if (rc == 0 && nq > 0 && nF > 0) {
         for (int k = 1; k < T; k++) {
@@ -1969,6 +2131,7 @@ typedef struct {
     int64_t *inter, *set_bp, *n_merged, *dropped;   /* nrows x (nFiles + 1), nrows, nrows, nrows */
     int32_t *ps, *pe, *mr;                          /* the permuted set; the runs (3 x nq) */
     int k, T, failed;
+    const igd_hip_workspace *ws;
 } pbp_job;
 
 static void *pbp_run(void *arg)
@@ -1978,7 +2141,7 @@ static void *pbp_run(void *arg)
     for (int64_t r = P->k; r < P->nrows && !P->failed; r += P->T) {
         const int32_t *s = P->qs, *e = P->qe;
         if (r > 0) {
-            (void)igdc_permute_regions_host(P->ichr, P->qs, P->qe, nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, r - 1, 1, P->ps, P->pe);
+            perm_regions_fill(P->ichr, P->qs, P->qe, nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, r - 1, 1, P->ps, P->pe, P->ws);
             s = P->ps; e = P->pe;
         }
         int64_t moff[2], bp = 0;
@@ -1996,9 +2159,17 @@ int igdc_permute_bp_host(const igdc_db *db, const igdc_map *m, const int32_t *ic
                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
                          int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped)
 {
+    return igdc_permute_bp_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, NULL);
+}
+
+int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                            const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
+                            int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
+{
     if (!db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || (mode != IGD_HIP_PERM_CIRCULAR && mode != IGD_HIP_PERM_SHUFFLE) ||
-        nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0)
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || !perm_mode_ok(mode, ws) ||
+        nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 ||
+        perm_ws_refused(db, ws, ctg_len, ichr, qs, qe, nq))
         return -1;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     int T = host_threads(nq * R > 0 ? nq * R : 1);
@@ -2015,7 +2186,7 @@ int igdc_permute_bp_host(const igdc_db *db, const igdc_map *m, const int32_t *ic
         job[k].nq = nq; job[k].nrows = R; job[k].mode = mode; job[k].seed = seed; job[k].v = v; job[k].rule = rule;
         job[k].inter = res; job[k].set_bp = res + R * nC; job[k].n_merged = job[k].set_bp + R; job[k].dropped = job[k].n_merged + R;
         job[k].ps = w + (size_t)k * 5 * (size_t)nq; job[k].pe = job[k].ps + nq; job[k].mr = job[k].pe + nq;
-        job[k].k = k; job[k].T = T;
+        job[k].k = k; job[k].T = T; job[k].ws = ws;
     }
     if (rc == 0 && nq > 0) {
         for (int k = 1; k < T; k++) {

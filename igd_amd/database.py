@@ -119,6 +119,7 @@ EnrichmentRanks = collections.namedtuple("EnrichmentRanks", "qvalue_log rnk_sup 
 PermutationSupport = collections.namedtuple("PermutationSupport", "observed sum sumsq n_ge n_le min max nperm")
 PermutationSummary = collections.namedtuple("PermutationSummary", "mean sd z nlog10_p_upper nlog10_p_lower")
 PERM_MODES = {"circular": 0, "shuffle": 1}           # IGD_HIP_PERM_CIRCULAR, IGD_HIP_PERM_SHUFFLE
+PERM_WORKSPACE = 2                                   # IGD_HIP_PERM_WORKSPACE: mode="workspace" together with workspace=
 NearestSets = collections.namedtuple("NearestSets", "n_within n_overlap sum_dist window")
 PermutationNearest = collections.namedtuple("PermutationNearest", "n_within n_overlap sum_dist window nperm")
 MapSets = collections.namedtuple("MapSets", "n_hit pairs agg_sum op")
@@ -387,10 +388,68 @@ def support_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None, min_
         return sup[:h.nfiles], nhit.value
 
 
-def _perm_mode(mode, what):
+class Workspace:
+    """The table of a workspace (include/igd_hip.h: THE WORKSPACE): the stretches of the contigs a permutation may place a
+    region in.  Built by build_workspace() or Database.read_workspace(); handed as workspace= together with mode="workspace".
+    nctg, nseg; w_off int64[nctg + 1], w_start, w_len int32[nseg], w_pre int32[nseg + nctg] (copies); ctg_len as it was built.
+    first_unplaceable(ichr, qs, qe): the first region on a known contig that fits in no segment, or -1.  outside(ichr, qs,
+    qe): the regions on known contigs that do not lie inside one segment."""
+
+    def __init__(self, table, ctg_len):
+        self._t, self.ctg_len = table, ctg_len
+        t = table.contents
+        self.nctg, self.nseg = int(t.nctg), int(t.nseg)
+
+        def arr(p, n, ct, dt):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).astype(dt) if n > 0 else np.zeros(0, dt)
+        self.w_off = arr(t.w_off, self.nctg + 1, C.c_int64, np.int64)
+        self.w_start = arr(t.w_start, self.nseg, C.c_int32, np.int32)
+        self.w_len = arr(t.w_len, self.nseg, C.c_int32, np.int32)
+        self.w_pre = arr(t.w_pre, self.nseg + self.nctg, C.c_int32, np.int32)
+
+    @property
+    def ptr(self):
+        return C.cast(self._t, C.c_void_p)
+
+    def first_unplaceable(self, ichr, qs, qe):
+        ichr, qs, qe = _regions(ichr, qs, qe)
+        return int(N.cli().igdc_workspace_first_unplaceable(self.ptr, _ptr(self.ctg_len), _ptr(ichr), _ptr(qs), _ptr(qe), len(qs)))
+
+    def outside(self, ichr, qs, qe):
+        ichr, qs, qe = _regions(ichr, qs, qe)
+        return int(N.cli().igdc_workspace_outside(self.ptr, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs)))
+
+    def __del__(self):
+        if getattr(self, "_t", None):
+            N.cli().igdc_workspace_free(self._t)
+            self._t = None
+
+
+def build_workspace(ichr, a, b, ctg_len):
+    """The Workspace of the segments (ichr, a, b) on contigs of lengths ctg_len (igdc_workspace_build): merged at gap 0,
+    clipped to the contigs, per contig ordered by length descending, then start ascending."""
+    ichr, a, b, ctg_len = _perm_regions(ichr, a, b, ctg_len, "build_workspace")
+    t = C.POINTER(N.HipWorkspace)()
+    if N.cli().igdc_workspace_build(_ptr(ichr), _ptr(a), _ptr(b), len(a), _ptr(ctg_len), len(ctg_len), C.byref(t)) != 0:
+        raise IgdError("build_workspace: bad argument (a negative contig length), or out of memory")
+    return Workspace(t, ctg_len)
+
+
+def _perm_mode(mode, what, workspace=None):
+    """the mode number of a call; mode="workspace" and workspace= come together or not at all (ValueError)"""
+    if (mode == "workspace") != (workspace is not None):
+        raise ValueError("%s: mode='workspace' and workspace= go together, not one without the other" % what)
+    if workspace is not None:
+        if not isinstance(workspace, Workspace):
+            raise ValueError("%s: workspace must be a Workspace (build_workspace(), Database.read_workspace())" % what)
+        return PERM_WORKSPACE
     if mode not in PERM_MODES:
         raise IgdError("%s: mode must be 'circular' or 'shuffle', not %r" % (what, mode))
     return PERM_MODES[mode]
+
+
+def _ws_ptr(workspace):
+    return None if workspace is None else workspace.ptr
 
 
 def _perm_regions(ichr, qs, qe, ctg_len, what):
@@ -398,24 +457,25 @@ def _perm_regions(ichr, qs, qe, ctg_len, what):
     return (*_regions(ichr, qs, qe, what, ok=ctg_len.ndim == 1), ctg_len)
 
 
-def permute_regions_host(ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"):
-    """Permutations [p0, p0 + np_) of a region list on the host (igdc_permute_regions_host; no device is touched):
+def permute_regions_host(ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular", workspace=None):
+    """Permutations [p0, p0 + np_) of a region list on the host (igdc_permute_regions_host_ws; no device is touched):
     (qs, qe) int32[np_, nq] as Database.permute_regions() defines them."""
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_regions_host")
+    pm = _perm_mode(mode, "permute_regions_host", workspace)
     oqs, oqe = np.empty((int(np_), len(qs)), np.int32), np.empty((int(np_), len(qs)), np.int32)
-    if N.cli().igdc_permute_regions_host(_ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len),
-                                         _perm_mode(mode, "permute_regions_host"), _seed(seed), int(p0), int(np_),
-                                         _ptr(oqs), _ptr(oqe)) != 0:
+    if N.cli().igdc_permute_regions_host_ws(_ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len),
+                                            pm, _seed(seed), int(p0), int(np_), _ptr(oqs), _ptr(oqe), _ws_ptr(workspace)) != 0:
         raise IgdError("permute_regions_host: bad argument")
     return oqs, oqe
 
 
-def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, min_overlap=None):
+def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, min_overlap=None,
+                 workspace=None):
     """The permutation null of the support counts on the host (igdc_permute_host: pread on the .igd, threads over the
     permutations; no device is touched): a PermutationSupport as Database.permutation_support() defines it, min_overlap
     included (igdc_permute_host_ov)."""
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_host")
-    pm = _perm_mode(mode, "permute_host")
+    pm = _perm_mode(mode, "permute_host", workspace)
     mo = _min_overlap(min_overlap, "permute_host")
     with _HostDb(igd_path, None) as h:
         _ctg_len_matches(ctg_len, h.nctg, "permute_host")
@@ -423,8 +483,8 @@ def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular"
         out = [np.empty(h.nfiles + 1, np.int64) for _ in range(7)]
         a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed), int(nperm), vf, rule,
              *[_ptr(x) for x in out])
-        if (h.L.igdc_permute_host(*a) if mo is None else h.L.igdc_permute_host_ov(*a, C.byref(mo))) != 0:
-            raise IgdError("permute_host: a refused argument (number of permutations, a region outside its contig), or a tile of %s "
+        if h.L.igdc_permute_host_ws(*a, None if mo is None else C.byref(mo), _ws_ptr(workspace)) != 0:
+            raise IgdError("permute_host: a refused argument (number of permutations, a region outside its contig or its workspace), or a tile of %s "
                            "could not be read" % igd_path)
     return PermutationSupport(*out, int(nperm))
 
@@ -443,18 +503,18 @@ def perm_summary(ps):
     return PermutationSummary(*out)
 
 
-def permute_nearest_host(igd_path, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None):
+def permute_nearest_host(igd_path, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, workspace=None):
     """Database.permutation_nearest() on the host (igdc_permute_nearest_host: pread on the .igd, threads over the permutations;
     no device is touched): a PermutationNearest."""
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_nearest_host")
-    pm = _perm_mode(mode, "permute_nearest_host")
+    pm = _perm_mode(mode, "permute_nearest_host", workspace)
     with _HostDb(igd_path, "permute_nearest_host") as h:
         _ctg_len_matches(ctg_len, h.nctg, "permute_nearest_host")
         out = [np.empty((max(int(nperm), 0) + 1, h.nfiles + 1), np.int64) for _ in range(3)]
-        if h.L.igdc_permute_nearest_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed),
-                                         int(nperm), _window(window, "permute_nearest_host"), _value_filter(value_filter),
-                                         *[_ptr(a) for a in out]) != 0:
-            raise IgdError("permute_nearest_host: a refused argument (number of permutations, window, a region outside its contig), or a "
+        if h.L.igdc_permute_nearest_host_ws(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed),
+                                            int(nperm), _window(window, "permute_nearest_host"), _value_filter(value_filter),
+                                            *[_ptr(a) for a in out], _ws_ptr(workspace)) != 0:
+            raise IgdError("permute_nearest_host: a refused argument (number of permutations, window, a region outside its contig or its workspace), or a "
                            "tile of %s could not be read" % igd_path)
         return PermutationNearest(*out, int(window), int(nperm))
 
@@ -603,20 +663,20 @@ def _merge_cut(mc, ms, me, moff, cnt, dropped):
     return mc[:r], ms[:r], me[:r], moff, cnt[:r], dropped
 
 
-def permute_bp_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
+def permute_bp_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, workspace=None):
     """Database.permutation_bp() on the host (igdc_permute_bp_host: pread on the .igd, threads over the permutations; no device
     is touched): a PermutationBp."""
     ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_bp_host")
-    pm = _perm_mode(mode, "permute_bp_host")
+    pm = _perm_mode(mode, "permute_bp_host", workspace)
     with _HostDb(igd_path, "permute_bp_host") as h:
         _ctg_len_matches(ctg_len, h.nctg, "permute_bp_host")
         rule, vf = h.dispatch(v, rule, value_filter)
         rows = max(int(nperm), 0) + 1
         inter, set_bp, n_merged = np.empty((rows, h.nfiles + 1), np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
         dropped, file_bp = np.zeros(1, np.int64), np.empty(h.nfiles + 1, np.int64)
-        if h.L.igdc_permute_bp_host(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed),
-                                    int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged), _ptr(dropped)) != 0:
-            raise IgdError("permute_bp_host: a refused argument (number of permutations, a region outside its contig), or a tile of %s "
+        if h.L.igdc_permute_bp_host_ws(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed),
+                                       int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged), _ptr(dropped), _ws_ptr(workspace)) != 0:
+            raise IgdError("permute_bp_host: a refused argument (number of permutations, a region outside its contig or its workspace), or a tile of %s "
                            "could not be read" % igd_path)
         if h.L.igdc_dataset_bp_host(h.core, h.m, vf, rule, _ptr(file_bp)) != 0:
             raise IgdError("permute_bp_host: a tile of %s could not be read" % igd_path)
@@ -1088,7 +1148,7 @@ class Database:
         return out
 
     def permutation_support(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None,
-                            min_overlap=None):
+                            min_overlap=None, workspace=None):
         """Permutation null of the support counts of one region set (igd_hip_permute_support).  The set is moved nperm times
         -- mode "circular": one rigid shift per permutation and contig, a region that would cross the contig's end is pushed
         back against it; "shuffle": every region placed anew on its contig -- with the generator of include/igd_hip.h; every
@@ -1098,16 +1158,19 @@ class Database:
         x >= observed and x <= observed, the smallest and the largest; index nfiles is the regions with a hit in any file.
         The permuted regions and the permutations x files matrix never leave the device.  perm_summary() gives mean, sd, z
         and p.  A region on a known contig that does not lie within its length raises IgdError.  min_overlap (a MinOverlap, or
-        an int of base pairs; igd_hip_permute_support_ov): the observed row and every permuted row are counted under it."""
+        an int of base pairs; igd_hip_permute_support_ov): the observed row and every permuted row are counted under it.
+        mode "workspace" together with workspace= (a Workspace): every region is placed anew inside the segments of the
+        workspace on its contig, every fitting start equally likely (igd_hip_permute_support_ws); a region that fits in no
+        segment raises IgdError.  The same pair of arguments serves permutation_nearest(), permutation_bp() and
+        permute_regions()."""
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_support")
+        pm = _perm_mode(mode, "permutation_support", workspace)
         _ctg_len_matches(ctg_len, self.nctg, "permutation_support")
         rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         out = [np.empty(self.nfiles + 1, np.int64) for _ in range(7)]
         mo = _min_overlap(min_overlap, "permutation_support")
-        a = (self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), _perm_mode(mode, "permutation_support"),
-             _seed(seed), int(nperm), vf, rule, *[_ptr(x) for x in out])
-        _chk(self._H.igd_hip_permute_support(*a) if mo is None else self._H.igd_hip_permute_support_ov(*a, C.byref(mo)),
-             "igd_hip_permute_support")
+        a = (self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed), int(nperm), vf, rule, *[_ptr(x) for x in out])
+        _chk(self._H.igd_hip_permute_support_ws(*a, None if mo is None else C.byref(mo), _ws_ptr(workspace)), "igd_hip_permute_support")
         return PermutationSupport(*out, int(nperm))
 
     def read_genome(self, path):
@@ -1122,20 +1185,35 @@ class Database:
             raise IgdError("genome file %s, line %d: not a name, a tab and a length of at most 2147483647" % (path, bad.value))
         return ln[:self.nctg]
 
-    def permutation_support_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0, min_overlap=None):
-        """The permutation null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the
-        integers behind what `igd search -q path -P nperm -g genome_path` prints."""
-        return self.permutation_support(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v, min_overlap=min_overlap)
+    def read_workspace(self, path, ctg_len):
+        """The Workspace of a BED file (read as `igd search -q` reads a query file; lines on contigs the database lacks are
+        skipped) on the database's contigs of lengths ctg_len (read_genome()): igdc_read_workspace."""
+        ctg_len = _i32(ctg_len)
+        _ctg_len_matches(ctg_len, self.nctg, "read_workspace")
+        t = C.POINTER(N.HipWorkspace)()
+        rc = self._L.igdc_read_workspace(self._core, path.encode(), _ptr(ctg_len), C.byref(t))
+        if rc == -1:
+            raise IOError("cannot open workspace file %s" % path)
+        if rc != 0:
+            raise IgdError("read_workspace: the table of %s could not be built" % path)
+        return Workspace(t, ctg_len)
 
-    def permute_regions(self, ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"):
+    def permutation_support_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0, min_overlap=None, workspace=None):
+        """The permutation null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the
+        integers behind what `igd search -q path -P nperm -g genome_path` prints (with -W: mode="workspace" and workspace=)."""
+        return self.permutation_support(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v, min_overlap=min_overlap,
+                                        workspace=workspace)
+
+    def permute_regions(self, ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular", workspace=None):
         """Kernel igd_permute_regions on host arrays (igd_hip_permute_regions): (qs, qe) int32[np_, nq], row k the regions
         under permutation p0 + k.  ctg_len is the caller's: len(ctg_len) contigs, not tied to the database; a region with
         ichr outside [0, len(ctg_len)) passes through unchanged."""
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_regions")
+        pm = _perm_mode(mode, "permute_regions", workspace)
         oqs, oqe = np.empty((int(np_), len(qs)), np.int32), np.empty((int(np_), len(qs)), np.int32)
-        _chk(self._H.igd_hip_permute_regions(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len),
-                                             _perm_mode(mode, "permute_regions"), _seed(seed), int(p0), int(np_),
-                                             _ptr(oqs), _ptr(oqe)), "igd_hip_permute_regions")
+        _chk(self._H.igd_hip_permute_regions_ws(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len),
+                                                pm, _seed(seed), int(p0), int(np_), _ptr(oqs), _ptr(oqe), _ws_ptr(workspace)),
+             "igd_hip_permute_regions")
         return oqs, oqe
 
     def perm_stats(self, rows, observed, out=None):
@@ -1203,7 +1281,7 @@ class Database:
         """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets_fused()."""
         return self.nearest_sets_fused(*self._read_sets(paths), window, value_filter)
 
-    def permutation_nearest(self, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, out=None):
+    def permutation_nearest(self, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, out=None, workspace=None):
         """Permutation null of the nearest-record distances of one region set (igd_hip_permute_nearest): "are my regions closer
         to dataset f than chance".  The set is moved nperm times as permutation_support() moves it (same generator, mode, seed
         and ctg_len) and every permuted set is measured as nearest_sets() measures a set.  Returns PermutationNearest(n_within,
@@ -1213,18 +1291,20 @@ class Database:
         in it.  Neither the permuted regions nor any distance row leave the device.  out, when given, is a list of three
         C-ordered int64[nperm + 1, nfiles + 1] that are overwritten (untouched when the call raises)."""
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_nearest")
+        pm = _perm_mode(mode, "permutation_nearest", workspace)
         _ctg_len_matches(ctg_len, self.nctg, "permutation_nearest")
         out = _outs(out, 3, (max(int(nperm), 0) + 1, self.nfiles + 1), "permutation_nearest")
-        _chk(self._H.igd_hip_permute_nearest(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len),
-                                             _perm_mode(mode, "permutation_nearest"), _seed(seed), int(nperm),
-                                             _window(window, "permutation_nearest"), _value_filter(value_filter), *[_ptr(a) for a in out]),
+        _chk(self._H.igd_hip_permute_nearest_ws(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed), int(nperm),
+                                                _window(window, "permutation_nearest"), _value_filter(value_filter), *[_ptr(a) for a in out],
+                                                _ws_ptr(workspace)),
              "igd_hip_permute_nearest")
         return PermutationNearest(*out, int(window), int(nperm))
 
-    def permutation_nearest_files(self, path, genome_path, nperm, window, seed=0, mode="circular", value_filter=None):
+    def permutation_nearest_files(self, path, genome_path, nperm, window, seed=0, mode="circular", value_filter=None, workspace=None):
         """The null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the integers behind
         what `igd search -q path -P nperm -g genome_path -D window` prints."""
-        return self.permutation_nearest(*self.read_queries(path), self.read_genome(genome_path), nperm, window, seed, mode, value_filter)
+        return self.permutation_nearest(*self.read_queries(path), self.read_genome(genome_path), nperm, window, seed, mode, value_filter,
+                                        workspace=workspace)
 
     def nearest_files(self, paths, window, value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets()."""
@@ -1379,7 +1459,7 @@ class Database:
                                           _ptr(js.set_bp), _ptr(js.file_bp), _ptr(js.n_merged), _ptr(js.n_dropped)), "igd_hip_jaccard_sets")
         return js
 
-    def permutation_bp(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None):
+    def permutation_bp(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, workspace=None):
         """Permutation null of the base-pair overlap of one region set (igd_hip_permute_bp): "does my set share more base pairs
         with dataset f than chance".  The set is moved nperm times as permutation_support() moves it (same generator, mode,
         seed and ctg_len), and the set as given and every permuted set are treated as jaccard_sets() treats a set: merged at gap
@@ -1388,21 +1468,22 @@ class Database:
         file_bp is dataset_bp().  Neither the permuted regions nor the merged runs leave the device.  perm_bp_summary() places
         the observed row in the null distribution."""
         ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_bp")
+        pm = _perm_mode(mode, "permutation_bp", workspace)
         _ctg_len_matches(ctg_len, self.nctg, "permutation_bp")
         rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         rows = max(int(nperm), 0) + 1
         inter, set_bp, n_merged = np.empty((rows, self.nfiles + 1), np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
         dropped, file_bp = np.zeros(1, np.int64), np.empty(self.nfiles + 1, np.int64)
-        _chk(self._H.igd_hip_permute_bp(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), _perm_mode(mode, "permutation_bp"),
-                                        _seed(seed), int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged),
-                                        _ptr(dropped)), "igd_hip_permute_bp")
+        _chk(self._H.igd_hip_permute_bp_ws(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm,
+                                           _seed(seed), int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged),
+                                           _ptr(dropped), _ws_ptr(workspace)), "igd_hip_permute_bp")
         _chk(self._H.igd_hip_dataset_bp(self.dev, vf, rule, _ptr(file_bp)), "igd_hip_dataset_bp")
         return PermutationBp(inter, set_bp, n_merged, int(dropped[0]), file_bp, int(nperm))
 
-    def permutation_bp_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0):
+    def permutation_bp_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0, workspace=None):
         """The null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the integers behind
         what `igd search -q path -P nperm -g genome_path -G` prints."""
-        return self.permutation_bp(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v)
+        return self.permutation_bp(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v, workspace=workspace)
 
     def jaccard_files(self, paths, v=0):
         """One region set per BED file (read as `igd search -q` reads it): the JaccardSets of jaccard_sets()."""

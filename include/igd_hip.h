@@ -580,8 +580,8 @@ int igd_hip_jaccard_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs,
  * IGD_HIP_PERM_MAX, nq > igd_hip_max_batch(), a region on a known contig outside 0 <= s <= e <= L.  nq == 0: all zeros;
  * nFiles == 0: inter is zeros, set_bp and n_merged are still the rows'.  Blocking, one device; ordered with the other merges
  * of the handle as igd_hip_merge_sets is.
- * Not done: several sets in one call, a gap other than 0, a shuffle restricted to a workspace (GAT's), regions split at a
- * contig's end, several devices, igd_hip_jaccard_sets itself on the resident hand-over. */
+ * Not done: several sets in one call, a gap other than 0, regions split at a contig's end, several devices,
+ * igd_hip_jaccard_sets itself on the resident hand-over. */
 int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
                        int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
                        int64_t *n_dropped);
@@ -826,6 +826,88 @@ static inline IGD_HIP_HD_ void igd_hip_perm_place(int mode, uint64_t base, int32
     *s = (int32_t)t;
     *e = (int32_t)(t + len);
 }
+/* THE WORKSPACE (the one definition: kernel igd_permute_workspace, igdc_permute_regions_host_ws and the tests' numpy reference
+ * agree bit for bit).  A workspace is a list of segments (c, a, b) on the contigs of the call: the stretches a region may be
+ * placed in (GAT's workspace, regioneR's mask inverted, `bedtools shuffle -incl`).  It is merged at gap 0 by the rules of
+ * igd_hip_merge_sets (igd_hip_merge_takes_part, igd_hip_merge_opens: touching segments join, zero-length and inverted ones
+ * and those on unknown contigs are dropped) and then clipped to [0, ctg_len[c]]; what is left of a segment has length >= 1.
+ * Per contig the merged segments are ordered by length descending, then start ascending.  THE TABLE of nseg segments:
+ *     w_off[nctg + 1]        int64: the segments of contig c are w_off[c] .. w_off[c + 1] - 1; w_off[0] = 0, w_off[nctg] = nseg
+ *     w_start[nseg], w_len[nseg]   int32, in that order
+ *     w_pre[nseg + nctg]     int32, n + 1 entries per contig: w_pre[w_off[c] + c + j] = the sum of the first j lengths of contig
+ *                            c, 0 <= j <= n = w_off[c + 1] - w_off[c].  Disjoint segments of one contig sum to at most
+ *                            ctg_len[c] <= 2^31 - 1.
+ * IGD_HIP_PERM_WORKSPACE places region i = (c, s, e), len = e - s, valid as above, with k = i and r = r(p, i) as SHUFFLE:
+ *     kk   = the number of segments of contig c with w_len >= len (binary search in the descending lengths)
+ *     F(j) = w_pre[w_off[c] + c + j] - j * (len - 1) in signed 64 bits, 0 <= j <= kk: the valid starts in the first j segments
+ *            (each gives w_len - len + 1 >= 1, so F is strictly increasing);  T = F(kk)
+ *     T == 0: the region fits nowhere and passes through unchanged (the three drivers refuse such a call)
+ *     u = r mod T;  j = the one index with F(j) <= u < F(j + 1) (a second binary search);
+ *     s' = w_start[w_off[c] + j] + (u - F(j));  e' = s' + len.
+ * Every fitting start is equally likely up to the bias of `mod`, at most 2^-31 (T <= 2^32).  Regions on unknown contigs and
+ * invalid regions pass through as under the other modes.  Two identities: a workspace of the one segment [0, L) per contig
+ * gives SHUFFLE's output bit for bit, and every placed region lies inside one segment.
+ * igd_hip_workspace_valid: 1 when a table can be trusted -- nctg as given, offsets from 0 to nseg and monotone, per contig
+ * fewer than 2^31 segments, every length >= 1 and not above the one before it, 0 <= start and start + len <= ctg_len[c], w_pre
+ * the sums just defined and never above ctg_len[c].  O(nseg).  With such a table igd_hip_perm_place_ws reads inside the four
+ * arrays and returns a region on its contig whatever else the table holds; both searches take at most 32 steps. */
+#define IGD_HIP_PERM_WORKSPACE 2
+typedef struct igd_hip_workspace {
+    int32_t nctg;
+    int64_t nseg;
+    const int64_t *w_off;
+    const int32_t *w_start, *w_len, *w_pre;
+} igd_hip_workspace;
+static inline int igd_hip_workspace_valid(const igd_hip_workspace *ws, const int32_t *ctg_len, int32_t nctg)
+{
+    if (!ws || ws->nctg != nctg || nctg < 0 || ws->nseg < 0 || !ws->w_off || (nctg > 0 && (!ctg_len || !ws->w_pre)) ||
+        (ws->nseg > 0 && (!ws->w_start || !ws->w_len)) || ws->w_off[0] != 0 || ws->w_off[nctg] != ws->nseg)
+        return 0;
+    for (int32_t c = 0; c < nctg; c++) {
+        const int64_t o = ws->w_off[c], n = ws->w_off[c + 1] - o, L = ctg_len[c];
+        if (n < 0 || n > (int64_t)INT32_MAX || o + n > ws->nseg) return 0;
+        const int32_t *pre = ws->w_pre + o + c;
+        int64_t sum = 0;
+        if (pre[0] != 0) return 0;
+        for (int64_t j = 0; j < n; j++) {
+            const int64_t a = ws->w_start[o + j], l = ws->w_len[o + j];
+            if (l < 1 || (j > 0 && l > (int64_t)ws->w_len[o + j - 1]) || a < 0 || a + l > L) return 0;
+            sum += l;
+            if (sum > L || (int64_t)pre[j + 1] != sum) return 0;
+        }
+    }
+    return 1;
+}
+/* region i = (c, *s, *e) under permutation p (base = igd_hip_perm_base(seed, p)) inside the workspace, in place; 1 when the
+ * region is on a known contig, valid, and fits in no segment (it is left as it was), 0 otherwise */
+static inline IGD_HIP_HD_ int igd_hip_perm_place_ws(uint64_t base, int32_t c, int64_t i, const int32_t *ctg_len, int32_t nctg,
+                                                    const int64_t *w_off, const int32_t *w_start, const int32_t *w_len, const int32_t *w_pre,
+                                                    int32_t *s, int32_t *e)
+{
+    if (c < 0 || c >= nctg) return 0;
+    const int64_t L = ctg_len[c], s0 = *s, len = (int64_t)*e - s0;
+    if (L < 1 || s0 < 0 || len < 0 || s0 + len > L) return 0;
+    const int64_t o = w_off[c], n = w_off[c + 1] - o;
+    const int32_t *pre = w_pre + o + c;
+    int64_t lo = 0, hi = n;                               /* kk: the first j with w_len[j] < len */
+    for (int step = 0; step < 32 && lo < hi; step++) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)w_len[o + mid] >= len) lo = mid + 1; else hi = mid;
+    }
+    const int64_t kk = lo, T = (int64_t)pre[kk] - kk * (len - 1);
+    if (T <= 0) return 1;
+    const uint64_t r = igd_hip_perm_mix64(base + ((uint64_t)i + 1) * 0x9E3779B97F4A7C15ull);
+    const int64_t u = (int64_t)(r % (uint64_t)T);
+    lo = 0; hi = kk;                                      /* F(lo) <= u < F(hi) */
+    for (int step = 0; step < 32 && hi - lo > 1; step++) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)pre[mid] - mid * (len - 1) <= u) lo = mid; else hi = mid;
+    }
+    const int64_t t = (int64_t)w_start[o + lo] + (u - ((int64_t)pre[lo] - lo * (len - 1)));
+    *s = (int32_t)t;
+    *e = (int32_t)(t + len);
+    return 0;
+}
 /* The whole test on one device.  ctg_len is int32[number of contigs of db], in the database's contig order.  Index nFiles of
  * every output is the "any dataset" column: the regions with a hit in any file, what igd_hip_support_sets adds to nhit.
  *     observed[f] = support of the set as given                          sum[f], sumsq[f] = over the permutations, of x and x^2
@@ -838,7 +920,7 @@ static inline IGD_HIP_HD_ void igd_hip_perm_place(int mode, uint64_t base, int32
  * rows never leave the device.  Blocking.  IGD_HIP_ERR_ARG, before any launch and with nothing of the caller's written: a
  * missing array, no such rule or mode, nperm < 1 or > IGD_HIP_PERM_MAX, nq > igd_hip_max_batch(), nperm * nq^2 >= 2^63 (sumsq),
  * a region on a known contig that breaks 0 <= s <= e <= L, L >= 1 (igd_hip_last_error names the first one).
- * Not done: several sets in one call, a universe-restricted shuffle, regions split at the contig's end, several devices. */
+ * Not done: several sets in one call, regions split at the contig's end, several devices. */
 int igd_hip_permute_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
                             int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
                             int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax);
@@ -860,6 +942,29 @@ int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *
 int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t nrows, int64_t ncols, const int64_t *observed, int64_t *sum,
                        int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax);
 int32_t igd_hip_permute_grid(int64_t n);
+/* The four entries above inside a workspace (THE WORKSPACE above; kernel igd_permute_workspace, the launch shape of
+ * igd_permute_regions with the table read from device memory).  ws == NULL is the entry above, every refusal included: mode
+ * IGD_HIP_PERM_WORKSPACE without a workspace stays IGD_HIP_ERR_ARG.  With a workspace the mode must be IGD_HIP_PERM_WORKSPACE;
+ * the table is checked by igd_hip_workspace_valid against the call's ctg_len (the database's contigs for the three drivers)
+ * and uploaded once per call into a buffer of the handle; everything behind the placement is the entry's own chain, unchanged.
+ * IGD_HIP_ERR_ARG before any launch, nothing of the caller's written: an invalid table, a mode / workspace mismatch and, in the
+ * three drivers, a valid region on a known contig that fits in no segment (igd_hip_last_error names the first one; the generic
+ * entry passes it through unchanged).
+ * Not done: a circular shift inside a workspace, segments weighted other than by length (isochores), truncating datasets to
+ * the workspace, several sets in one call, several devices. */
+int igd_hip_permute_regions_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                               int32_t nctg, int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe,
+                               const igd_hip_workspace *ws);
+int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                               int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
+                               int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap,
+                               const igd_hip_workspace *ws);
+int igd_hip_permute_nearest_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                               int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
+                               int64_t *sum_dist, const igd_hip_workspace *ws);
+int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                          int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
+                          int64_t *n_dropped, const igd_hip_workspace *ws);
 
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
