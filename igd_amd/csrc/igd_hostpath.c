@@ -41,8 +41,8 @@
  * (engine F + n * 7 ns against host 0.03 s + n * 0.55 us / T, crossing at ~280 000 * T) assumed the engine route's BEST start-up
  * and threads that scale; on a host where they do not (1.4 us per query whatever T) it sent 2e6-query files to a 2.8 s host
  * route.  With this limit the worst case of the model's error is ~0.1 s either way, and a 10^6-query file -- BASELINE config 2
- * -- is counted by the MI355X.  IGD_HOST_MAX_QUERIES overrides it (0: every file goes to the GPU).  This file is frozen:
- * bench.py times every size on BOTH routes and labels who counted. */
+ * -- is counted by the MI355X.  IGD_HOST_MAX_QUERIES overrides it (0: every file goes to the GPU).  The LIMIT is frozen
+ * (the code of this file is not): bench.py times every size on BOTH routes and labels who counted. */
 static int64_t host_threads_usable(void)
 {
     long t = sysconf(_SC_NPROCESSORS_ONLN);
@@ -65,11 +65,7 @@ int64_t igdc_host_limit(void)
     if (e >= 0) return e;
     return 25000 * host_threads_usable();
 }
-int64_t igdc_host_limit_enum(void)
-{
-    const int64_t e = host_limit_env();
-    return e >= 0 ? e : 25000 * host_threads_usable();
-}
+int64_t igdc_host_limit_enum(void) { return igdc_host_limit(); }
 
 /* a query file of `bytes` bytes can be expected to hold at most the limit's number of lines (a BED3 line of a human
  * genome is 18-26 bytes; gzip shrinks it about four times): parse it BEFORE the engine is started, then decide */
@@ -148,7 +144,78 @@ static inline int32_t below(const int32_t *rec, int w, int32_t cnt, int32_t qe)
     return lo;
 }
 
-/* one query; hits may be NULL (count only); emit appends (idx,start,end) triples in the reference's -f order */
+/* a worker's tile buffer: opened empty; closing frees it and reports whether a tile could not be read */
+static void tb_open(tilebuf *tb)
+{
+    memset(tb, 0, sizeof *tb);
+    tb->ichr = -1;
+}
+static int tb_close(tilebuf *tb)
+{
+    free(tb->buf);
+    tb->buf = NULL;
+    return tb->failed;
+}
+
+/* ---- THE tile walk: the one place that knows how the reference visits the tiles of an interval -----------------------------
+ * The tiles of [lo, hi) on contig ichr, and in each the COUNTED records: start < hi (the bisection), end > lo, value >= v under
+ * a filter, a dataset number the database has (the reference indexes hits[] unchecked, :491), and in a tile after the first
+ * only records that start inside the tile (the prefix skip, :510-511: the others were met in an earlier tile).  WALK_BACK
+ * scans each tile down from the bisection, as the reference does (:489-493, :522-526); WALK_FORWARD scans the same records
+ * up from the prefix skip, so that they come in non-decreasing start order over the whole walk.  nest is rule NEST's exit on
+ * an empty first tile (:468).  On a tile that cannot be read the walk stops with tb->failed set and answers 0; otherwise 1.
+ * What is done with a counted record is the visitor's business.  The walker is forced inline and every caller passes a
+ * function by name, so the visitor is a constant where the walk is expanded and is inlined into the scan loop (LABNOTES has
+ * the check of the object code): a new host twin writes a visitor, not an eighth copy of this. */
+typedef void (*walk_visit)(void *ctx, const int32_t *r);
+enum { WALK_BACK = 0, WALK_FORWARD = 1 };
+
+static inline int counted(const int32_t *r, int32_t lo, int32_t v, int use_v, int32_t nf)
+{
+    return r[2] > lo && (!use_v || r[3] >= v) && r[0] >= 0 && r[0] < nf;
+}
+
+static inline __attribute__((always_inline)) int walk_tiles(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t lo,
+                                                            int32_t hi, int32_t v, int use_v, int nest, int dir, walk_visit visit, void *ctx)
+{
+    if (ichr < 0 || ichr >= db->nCtg) return 1;                            /* :456-457 */
+    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
+    const int32_t n1 = lo / nbp;                                           /* C division, as :459 */
+    int32_t n2 = (int32_t)((uint32_t)hi - 1u) / nbp;                       /* (hi-1)/nbp with the reference's wrap */
+    if (n1 < 0 || n1 > mT) return 1;                                       /* (no record ends behind the contig's last tile) */
+    if (n2 > mT) n2 = mT;
+    if (nest && db->nCnt[ichr][n1] == 0) return 1;                         /* :468 */
+    const int w = db->gType == 0 ? 3 : 4;
+    const int32_t nf = db->nFiles;
+    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
+        const int32_t cnt = db->nCnt[ichr][j];
+        if (cnt <= 0) continue;
+        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
+        if (!rec) return 0;
+        const int32_t tile0 = (int32_t)((uint32_t)nbp * (uint32_t)j), stop = below(rec, w, cnt, hi);
+        if (dir == WALK_FORWARD) {
+            for (int32_t i = j == n1 ? 0 : below(rec, w, cnt, tile0); i < stop; i++) {
+                const int32_t *r = rec + (size_t)i * (size_t)w;
+                if (counted(r, lo, v, use_v, nf)) visit(ctx, r);
+            }
+        } else {
+            const int64_t lob = j == n1 ? INT64_MIN : (int64_t)tile0;
+            for (int32_t i = stop - 1; i >= 0; i--) {
+                const int32_t *r = rec + (size_t)i * (size_t)w;
+                if ((int64_t)r[1] < lob) break;                            /* met in an earlier tile (:510-511) */
+                if (counted(r, lo, v, use_v, nf)) visit(ctx, r);
+            }
+        }
+    }
+    return 1;
+}
+
+/* ---- the visitors: one per kind of answer.  Each one_* function sets up its row BEFORE the walk (an unknown contig still
+ * gives a defined row) and returns what the walk had when it stopped. */
+
+/* pair counts: hits may be NULL (count only); emit appends (idx,start,end) triples in the reference's -f order.
+ * mo: an ACTIVE minimum overlap per pair (include/igd_hip.h: igd_hip_min_overlap; the host flavours pass NULL for an inactive
+ * one), the same inline predicate as the kernels': need_q once per query, the pair test on every record the walk counts */
 typedef struct { igd_hip_hit *v; int64_t n, cap; int failed; } hitvec;
 static inline void hv_push(hitvec *o, int32_t q, const int32_t *r)
 {
@@ -162,204 +229,183 @@ static inline void hv_push(hitvec *o, int32_t q, const int32_t *r)
     h->q = q; h->idx = r[0]; h->start = r[1]; h->end = r[2];
 }
 
-/* mo: an ACTIVE minimum overlap per pair (include/igd_hip.h: igd_hip_min_overlap; the host flavours pass NULL for an inactive
- * one), the same inline predicate as the kernels': need_q once per query, the pair test on every record the walk counts */
+typedef struct { int32_t qs, qe, need, qno; const igd_hip_min_overlap *mo; int64_t *hits; hitvec *emit; int64_t total; } pairs_ctx;
+static inline void visit_pairs(void *ctx, const int32_t *r)
+{
+    pairs_ctx *c = (pairs_ctx *)ctx;
+    if (c->mo && !igd_hip_min_overlap_pair(c->need, c->mo->ppm_record, c->qs, c->qe, r[1], r[2])) return;
+    if (c->hits) c->hits[r[0]]++;
+    if (c->emit) hv_push(c->emit, c->qno, r);
+    c->total++;
+}
 static inline int64_t one_query(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int32_t v,
                                 int use_v, int rule, int64_t *hits, hitvec *emit, int32_t qno, const igd_hip_min_overlap *mo)
 {
-    if (ichr < 0 || ichr >= db->nCtg) return 0;                            /* :456-457 */
-    const int32_t need = mo ? igd_hip_min_overlap_need_q(mo->min_bp, mo->ppm_query, qs, qe) : 0;
-    if (need < 0) return 0;                                                /* qe <= qs: no record qualifies */
-    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
-    const int32_t n1 = qs / nbp;                                           /* C division, as :459 */
-    int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;                       /* (qe-1)/nbp with the reference's wrap */
-    if (n1 < 0 || n1 > mT) return 0;
-    if (n2 > mT) n2 = mT;
-    if (rule == IGD_HIP_RULE_NEST && db->nCnt[ichr][n1] == 0) return 0;    /* :468 */
-    const int w = db->gType == 0 ? 3 : 4;
-    const int32_t nf = db->nFiles;
-    int64_t total = 0;
-    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
-        const int32_t cnt = db->nCnt[ichr][j];
-        if (cnt <= 0) continue;
-        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
-        if (!rec) return total;
-        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
-        for (int32_t i = below(rec, w, cnt, qe) - 1; i >= 0; i--) {        /* the reverse scans of :489-493, :522-526 */
-            const int32_t *r = rec + (size_t)i * (size_t)w;
-            if ((int64_t)r[1] < lob) break;                                /* met in an earlier tile (:510-511) */
-            if (r[2] > qs && (!use_v || r[3] >= v) && (!mo || igd_hip_min_overlap_pair(need, mo->ppm_record, qs, qe, r[1], r[2]))) {
-                if (r[0] < 0 || r[0] >= nf) continue;                      /* the reference indexes hits[] unchecked (:491) */
-                if (hits) hits[r[0]]++;
-                if (emit) hv_push(emit, qno, r);
-                total++;
-            }
-        }
-    }
-    return total;
+    pairs_ctx c = {qs, qe, mo ? igd_hip_min_overlap_need_q(mo->min_bp, mo->ppm_query, qs, qe) : 0, qno, mo, hits, emit, 0};
+    if (c.need < 0) return 0;                                              /* qe <= qs: no record qualifies */
+    walk_tiles(db, m, tb, ichr, qs, qe, v, use_v, rule == IGD_HIP_RULE_NEST, WALK_BACK, visit_pairs, &c);
+    return c.total;
 }
 
-/* one query for the support counts (igdc_support_host): the walk of one_query, but a file counts once per query.  last[f]
- * holds the stamp of the last query that counted file f (stamp = query number + 1; 0 = none yet).  Returns 1 if the query
- * overlaps any record. */
+/* support counts (igdc_support_host): a file counts once per query.  last[f] holds the stamp of the last query that counted
+ * file f (stamp = query number + 1; 0 = none yet).  Returns 1 if the query overlaps any record. */
+typedef struct { int32_t qs, qe, need; const igd_hip_min_overlap *mo; int64_t *support, *last, stamp; int any; } support_ctx;
+static inline void visit_support(void *ctx, const int32_t *r)
+{
+    support_ctx *c = (support_ctx *)ctx;
+    if (c->mo && !igd_hip_min_overlap_pair(c->need, c->mo->ppm_record, c->qs, c->qe, r[1], r[2])) return;
+    c->any = 1;
+    if (c->last[r[0]] != c->stamp) { c->last[r[0]] = c->stamp; c->support[r[0]]++; }
+}
 static inline int one_query_support(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int32_t v,
                                     int use_v, int rule, int64_t *support, int64_t *last, int64_t stamp, const igd_hip_min_overlap *mo)
 {
-    if (ichr < 0 || ichr >= db->nCtg) return 0;
-    const int32_t need = mo ? igd_hip_min_overlap_need_q(mo->min_bp, mo->ppm_query, qs, qe) : 0;
-    if (need < 0) return 0;
-    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
-    const int32_t n1 = qs / nbp;
-    int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;
-    if (n1 < 0 || n1 > mT) return 0;
-    if (n2 > mT) n2 = mT;
-    if (rule == IGD_HIP_RULE_NEST && db->nCnt[ichr][n1] == 0) return 0;
-    const int w = db->gType == 0 ? 3 : 4;
-    const int32_t nf = db->nFiles;
-    int any = 0;
-    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
-        const int32_t cnt = db->nCnt[ichr][j];
-        if (cnt <= 0) continue;
-        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
-        if (!rec) return any;
-        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
-        for (int32_t i = below(rec, w, cnt, qe) - 1; i >= 0; i--) {
-            const int32_t *r = rec + (size_t)i * (size_t)w;
-            if ((int64_t)r[1] < lob) break;
-            if (r[2] > qs && (!use_v || r[3] >= v) && (!mo || igd_hip_min_overlap_pair(need, mo->ppm_record, qs, qe, r[1], r[2]))) {
-                if (r[0] < 0 || r[0] >= nf) continue;
-                any = 1;
-                if (last[r[0]] != stamp) { last[r[0]] = stamp; support[r[0]]++; }
-            }
-        }
-    }
-    return any;
+    support_ctx c = {qs, qe, mo ? igd_hip_min_overlap_need_q(mo->min_bp, mo->ppm_query, qs, qe) : 0, mo, support, last, stamp, 0};
+    if (c.need < 0) return 0;
+    walk_tiles(db, m, tb, ichr, qs, qe, v, use_v, rule == IGD_HIP_RULE_NEST, WALK_BACK, visit_support, &c);
+    return c.any;
 }
 
-/* one query for the membership rows (igdc_membership_host): the walk of one_query_support; a counted record sets its file's
- * bit in the query's row (zeroed here first).  Returns the number of files met. */
+/* membership rows (igdc_membership_host): a counted record sets its file's bit in the query's row (zeroed here first).
+ * Returns the number of files met. */
+typedef struct { uint32_t *row; int n; } member_ctx;
+static inline void visit_member(void *ctx, const int32_t *r)
+{
+    member_ctx *c = (member_ctx *)ctx;
+    const uint32_t bit = 1u << (r[0] & 31);
+    if (!(c->row[r[0] >> 5] & bit)) { c->row[r[0] >> 5] |= bit; c->n++; }
+}
 static inline int one_query_member(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int32_t v,
                                    int use_v, int rule, uint32_t *row, int32_t nW)
 {
+    member_ctx c = {row, 0};
     memset(row, 0, sizeof(uint32_t) * (size_t)nW);
-    if (ichr < 0 || ichr >= db->nCtg) return 0;
-    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
-    const int32_t n1 = qs / nbp;
-    int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;
-    if (n1 < 0 || n1 > mT) return 0;
-    if (n2 > mT) n2 = mT;
-    if (rule == IGD_HIP_RULE_NEST && db->nCnt[ichr][n1] == 0) return 0;
-    const int w = db->gType == 0 ? 3 : 4;
-    const int32_t nf = db->nFiles;
-    int n = 0;
-    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
-        const int32_t cnt = db->nCnt[ichr][j];
-        if (cnt <= 0) continue;
-        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
-        if (!rec) return n;
-        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
-        for (int32_t i = below(rec, w, cnt, qe) - 1; i >= 0; i--) {
-            const int32_t *r = rec + (size_t)i * (size_t)w;
-            if ((int64_t)r[1] < lob) break;
-            if (r[2] > qs && (!use_v || r[3] >= v)) {
-                if (r[0] < 0 || r[0] >= nf) continue;
-                const uint32_t bit = 1u << (r[0] & 31);
-                if (!(row[r[0] >> 5] & bit)) { row[r[0] >> 5] |= bit; n++; }
-            }
-        }
-    }
-    return n;
+    walk_tiles(db, m, tb, ichr, qs, qe, v, use_v, rule == IGD_HIP_RULE_NEST, WALK_BACK, visit_member, &c);
+    return c.n;
 }
 
-/* one query for the covered base pairs (igdc_coverage_host): the tiles of one_query, each walked FORWARD, so the counted
- * records come in non-decreasing start order (a tile is sorted by start, a later tile skips start < lob, every record of an
- * earlier tile starts before lob).  front[f] = file f is covered up to here under this query; last[f] = the stamp of the
- * last query that met file f, as in one_query_support (another stamp: the frontier is the query's start).  A record adds
- * what it covers beyond the frontier: coverage[f] += | [qs, qe) n union of f's counted records |.  Returns the same for
- * the union over all files. */
+/* covered base pairs (igdc_coverage_host): the walk FORWARD, so the counted records come in non-decreasing start order (a tile
+ * is sorted by start, a later tile skips start < its own, every record of an earlier tile starts before it).  front[f] = file f
+ * is covered up to here under this query; last[f] = the stamp of the last query that met file f, as in one_query_support
+ * (another stamp: the frontier is the query's start).  A record adds what it covers beyond the frontier: coverage[f] +=
+ * | [qs, qe) n union of f's counted records |.  Returns the same for the union over all files. */
+typedef struct { int32_t qs, qe; int64_t *coverage, *last, *front, stamp, all, covered; } coverage_ctx;
+static inline void visit_coverage(void *ctx, const int32_t *r)
+{
+    coverage_ctx *c = (coverage_ctx *)ctx;
+    const int64_t lo = r[1] > c->qs ? r[1] : c->qs, hi = r[2] < c->qe ? r[2] : c->qe;
+    if (c->last[r[0]] != c->stamp) { c->last[r[0]] = c->stamp; c->front[r[0]] = c->qs; }
+    const int64_t from = lo > c->front[r[0]] ? lo : c->front[r[0]];
+    if (hi > from) c->coverage[r[0]] += hi - from;
+    if (hi > c->front[r[0]]) c->front[r[0]] = hi;
+    const int64_t afrom = lo > c->all ? lo : c->all;
+    if (hi > afrom) c->covered += hi - afrom;
+    if (hi > c->all) c->all = hi;
+}
 static inline int64_t one_query_coverage(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
                                          int32_t v, int use_v, int rule, int64_t *coverage, int64_t *last, int64_t *front, int64_t stamp)
 {
-    if (ichr < 0 || ichr >= db->nCtg) return 0;
-    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
-    const int32_t n1 = qs / nbp;
-    int32_t n2 = (int32_t)((uint32_t)qe - 1u) / nbp;
-    if (n1 < 0 || n1 > mT) return 0;
-    if (n2 > mT) n2 = mT;
-    if (rule == IGD_HIP_RULE_NEST && db->nCnt[ichr][n1] == 0) return 0;
-    const int w = db->gType == 0 ? 3 : 4;
-    const int32_t nf = db->nFiles;
-    int64_t all = qs, covered = 0;                                          /* the frontier over all files (64 bits: no wrap) */
-    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
-        const int32_t cnt = db->nCnt[ichr][j];
-        if (cnt <= 0) continue;
-        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
-        if (!rec) return covered;
-        const int32_t first = j == n1 ? 0 : below(rec, w, cnt, (int32_t)((uint32_t)nbp * (uint32_t)j));
-        const int32_t stop = below(rec, w, cnt, qe);
-        for (int32_t i = first; i < stop; i++) {
-            const int32_t *r = rec + (size_t)i * (size_t)w;
-            if (r[2] > qs && (!use_v || r[3] >= v)) {
-                if (r[0] < 0 || r[0] >= nf) continue;
-                const int64_t lo = r[1] > qs ? r[1] : qs, hi = r[2] < qe ? r[2] : qe;
-                if (last[r[0]] != stamp) { last[r[0]] = stamp; front[r[0]] = qs; }
-                const int64_t from = lo > front[r[0]] ? lo : front[r[0]];
-                if (hi > from) coverage[r[0]] += hi - from;
-                if (hi > front[r[0]]) front[r[0]] = hi;
-                const int64_t afrom = lo > all ? lo : all;
-                if (hi > afrom) covered += hi - afrom;
-                if (hi > all) all = hi;
-            }
-        }
-    }
-    return covered;
+    coverage_ctx c = {qs, qe, coverage, last, front, stamp, qs, 0};        /* all: the frontier over all files (64 bits: no wrap) */
+    walk_tiles(db, m, tb, ichr, qs, qe, v, use_v, rule == IGD_HIP_RULE_NEST, WALK_FORWARD, visit_coverage, &c);
+    return c.covered;
 }
 
-typedef struct {
-    const igdc_db *db; const igdc_map *m;
-    const int32_t *ichr, *qs, *qe;
-    int64_t lo, hi;
-    int32_t v; int use_v, rule;
-    int64_t *hits, total;
-    int64_t *qcnt;          /* enumeration: per-query counts (may be NULL) */
-    hitvec out; int want_out;
-    int io_failed;
-    int64_t *last;          /* support counts: the stamp array of one_query_support (NULL: pair counts) */
-    int64_t *front;         /* covered base pairs: the frontiers of one_query_coverage, beside last[] (NULL: not those) */
-    uint32_t *bits;         /* membership rows: the caller's rows (NULL: not those), nW words each; nfh: its nfiles_hit[] or NULL */
-    int32_t *nfh, nW;
-    const igd_hip_min_overlap *mo;      /* pair counts and support counts: an active minimum overlap, or NULL */
-} host_job;
-
-static void *host_run(void *arg)
+/* nearest record per dataset within a window (include/igd_hip.h has the definitions).  One region: its row is set to -1, the
+ * interval is widened by the window (igd_hip_nearest_widen), the tiles of the widened interval are walked without rule NEST's
+ * exit, and every counted record lowers row[idx] to its d, computed from the region as given (igd_hip_nearest_dist).  Returns
+ * the minimum over the files, or -1.  one_region_keys is that on unsigned words, 0xffffffff (= -1) for "none": with sgn it
+ * minimises igd_hip_nearest_key instead of d, and one_region_nearest_signed decodes the row and the minimum
+ * (igd_hip_nearest_key_decode). */
+typedef struct { int32_t qs, qe; int sgn; uint32_t *row, best; } keys_ctx;
+static inline void visit_keys(void *ctx, const int32_t *r)
 {
-    host_job *J = (host_job *)arg;
-    int64_t tot = 0;
-    tilebuf tb;
-    memset(&tb, 0, sizeof tb);
-    tb.ichr = -1;
-    for (int64_t i = J->lo; J->bits && i < J->hi; i++) {    /* membership rows: total = queries with a hit */
-        const int n = one_query_member(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule,
-                                       J->bits + (size_t)i * (size_t)J->nW, J->nW);
-        if (J->nfh) J->nfh[i] = n;
-        tot += n > 0;
-    }
-    for (int64_t i = J->lo; J->front && i < J->hi; i++)     /* covered base pairs: hits = coverage[], total = bp under any file */
-        tot += one_query_coverage(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, J->front, i + 1);
-    for (int64_t i = J->lo; J->last && !J->front && i < J->hi; i++)      /* support counts: hits = support[], total = queries with a hit */
-        tot += one_query_support(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits, J->last, i + 1, J->mo);
-    for (int64_t i = J->lo; !J->last && !J->bits && i < J->hi; i++) {
-        const int64_t n = one_query(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->v, J->use_v, J->rule, J->hits,
-                                    J->want_out ? &J->out : NULL, (int32_t)i, J->mo);
-        if (J->qcnt) J->qcnt[i] = n;
-        tot += n;
-    }
-    J->total = tot;
-    J->io_failed = tb.failed;
-    free(tb.buf);
-    return NULL;
+    keys_ctx *c = (keys_ctx *)ctx;
+    const uint32_t d = c->sgn ? igd_hip_nearest_key(c->qs, c->qe, r[1], r[2]) : (uint32_t)igd_hip_nearest_dist(c->qs, c->qe, r[1], r[2]);
+    if (d < c->row[r[0]]) c->row[r[0]] = d;
+    if (d < c->best) c->best = d;
+}
+static inline uint32_t one_region_keys(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                       int32_t window, int32_t v, int use_v, int sgn, uint32_t *row)
+{
+    keys_ctx c = {qs, qe, sgn, row, 0xffffffffu};
+    int32_t ws, we;
+    for (int32_t f = 0; f < db->nFiles; f++) row[f] = 0xffffffffu;
+    igd_hip_nearest_widen(qs, qe, window, &ws, &we);
+    walk_tiles(db, m, tb, ichr, ws, we, v, use_v, 0, WALK_BACK, visit_keys, &c);
+    return c.best;
+}
+static inline int32_t one_region_nearest(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                         int32_t window, int32_t v, int use_v, int32_t *row)
+{
+    return (int32_t)one_region_keys(db, m, tb, ichr, qs, qe, window, v, use_v, 0, (uint32_t *)row);
+}
+static inline int32_t one_region_nearest_signed(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                                int32_t window, int32_t v, int use_v, int32_t *row)
+{
+    const uint32_t best = one_region_keys(db, m, tb, ichr, qs, qe, window, v, use_v, 1, (uint32_t *)row);
+    for (int32_t f = 0; f < db->nFiles; f++) row[f] = igd_hip_nearest_key_decode((uint32_t)row[f]);
+    return igd_hip_nearest_key_decode(best);
 }
 
+/* flanking records per dataset (include/igd_hip.h has the definitions).  One region: one_region_keys' walk -- the same tiles,
+ * the same counted records -- with two unsigned words per file, 0xffffffff (= -1) for "none": igd_hip_flank_pair says on which
+ * side a counted record lies and how far, and it lowers that side's word.  The minima over the files go to *upmin, *downmin. */
+typedef struct { int32_t qs, qe, window; int measure; uint32_t *up, *down, upmin, downmin; } flank_ctx;
+static inline void visit_flanks(void *ctx, const int32_t *r)
+{
+    flank_ctx *c = (flank_ctx *)ctx;
+    uint32_t d = 0;
+    const int side = igd_hip_flank_pair(c->measure, c->window, c->qs, c->qe, r[1], r[2], &d);
+    if (side == IGD_HIP_FLANK_NEITHER) return;
+    uint32_t *row = side == IGD_HIP_FLANK_UP ? c->up : c->down, *best = side == IGD_HIP_FLANK_UP ? &c->upmin : &c->downmin;
+    if (d < row[r[0]]) row[r[0]] = d;
+    if (d < *best) *best = d;
+}
+static inline void one_region_flanks(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
+                                     int32_t window, int measure, int32_t v, int use_v, uint32_t *up, uint32_t *down, uint32_t *upmin,
+                                     uint32_t *downmin)
+{
+    flank_ctx c = {qs, qe, window, measure, up, down, 0xffffffffu, 0xffffffffu};
+    int32_t ws, we;
+    for (int32_t f = 0; f < db->nFiles; f++) up[f] = down[f] = 0xffffffffu;
+    igd_hip_nearest_widen(qs, qe, window, &ws, &we);
+    walk_tiles(db, m, tb, ichr, ws, we, v, use_v, 0, WALK_BACK, visit_flanks, &c);
+    *upmin = c.upmin; *downmin = c.downmin;
+}
+
+/* values of the overlapping records per region and dataset (include/igd_hip.h has the definitions).  One region: its rows are
+ * set to 0, the tiles of igd_hip_nearest_widen(qs, qe, 0) are walked as one_region_keys walks them, and every counted record
+ * adds 1 to count[idx] and folds its value into agg[idx] (NULL under COUNT: nothing). */
+typedef struct { int op; int32_t *count; int64_t *agg; } map_ctx;
+static inline void visit_map(void *ctx, const int32_t *r)
+{
+    map_ctx *c = (map_ctx *)ctx;
+    const int32_t f = r[0];
+    if (c->op != IGD_HIP_MAP_COUNT) {
+        const int64_t val = r[3];
+        if (c->op == IGD_HIP_MAP_SUM) c->agg[f] = (int64_t)((uint64_t)c->agg[f] + (uint64_t)val);
+        else if (c->count[f] == 0 || (c->op == IGD_HIP_MAP_MIN ? val < c->agg[f] : val > c->agg[f])) c->agg[f] = val;
+    }
+    c->count[f]++;
+}
+static inline void one_region_map(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int op,
+                                  int32_t v, int use_v, int32_t *count, int64_t *agg)
+{
+    map_ctx c = {op, count, agg};
+    const int32_t nf = db->nFiles;
+    int32_t ws, we;
+    for (int32_t f = 0; f < nf; f++) count[f] = 0;
+    if (agg) for (int32_t f = 0; f < nf; f++) agg[f] = 0;
+    igd_hip_nearest_widen(qs, qe, 0, &ws, &we);
+    if (!walk_tiles(db, m, tb, ichr, ws, we, v, use_v, 0, WALK_BACK, visit_map, &c)) return;
+    if (agg && op == IGD_HIP_MAP_COUNT) for (int32_t f = 0; f < nf; f++) agg[f] = count[f];
+}
+
+/* ---- threads ---------------------------------------------------------------------------------------------------------------
+ * run_threads: T jobs of one type, `size` bytes apart: jobs 1 .. T-1 on new threads, job 0 on the caller; a thread that could
+ * not be created has its job run here, inline.  Returns when all are done.  How many threads a call is worth is the caller's
+ * rule (host_threads, capped by what there is to share out). */
+#define HOST_MAX_THREADS 64
 static int host_threads(int64_t nq)
 {
     const char *e = getenv("IGD_HOST_THREADS");
@@ -370,21 +416,157 @@ static int host_threads(int64_t nq)
     }
     const int64_t byWork = (nq + 2047) / 2048;      /* a thread is worth starting for ~2000 queries (~3 ms of counting) */
     if (t > byWork) t = (long)byWork;
-    if (t > 64) t = 64;
+    if (t > HOST_MAX_THREADS) t = HOST_MAX_THREADS;
     return t < 1 ? 1 : (int)t;
 }
 
-static int run_jobs(host_job *job, int T)
+static void run_threads(void *(*run)(void *), void *jobs, size_t size, int T)
 {
-    pthread_t th[64];
-    int started[64];
+    pthread_t th[HOST_MAX_THREADS];
+    int started[HOST_MAX_THREADS];
     for (int k = 1; k < T; k++) {
-        started[k] = pthread_create(&th[k], NULL, host_run, &job[k]) == 0;
-        if (!started[k]) host_run(&job[k]);
+        void *job = (char *)jobs + (size_t)k * size;
+        started[k] = pthread_create(&th[k], NULL, run, job) == 0;
+        if (!started[k]) run(job);
     }
-    host_run(&job[0]);
+    run(jobs);
     for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
-    return 0;
+}
+
+/* ---- the job of one thread of a query-split entry: queries [lo, hi) of the caller's arrays, answered as `kind` says --------- */
+enum { JOB_PAIRS, JOB_SUPPORT, JOB_COVERAGE, JOB_MEMBER, JOB_NEAREST, JOB_FLANK, JOB_MAP };
+typedef struct {
+    int kind;
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe;
+    int64_t lo, hi;
+    int32_t v; int use_v, rule;
+    int64_t total;          /* out: PAIRS pairs, SUPPORT and MEMBER queries with a hit, COVERAGE base pairs under any file */
+    int io_failed;          /* out: a tile could not be read */
+    int64_t *hits;          /* PAIRS hits[] (may be NULL), SUPPORT support[], COVERAGE coverage[] */
+    int64_t *last, *front;  /* SUPPORT, COVERAGE: the stamps; COVERAGE: the frontiers */
+    const igd_hip_min_overlap *mo;      /* PAIRS, SUPPORT: an active minimum overlap, or NULL */
+    int64_t *qcnt;          /* PAIRS: per-query counts (enumeration; may be NULL) */
+    hitvec out; int want_out;
+    uint32_t *bits;         /* MEMBER: the caller's rows, nW words each; nfh: its nfiles_hit[] or NULL */
+    int32_t *nfh, nW;
+    int32_t window; int sgn, measure, op;           /* NEAREST window, sgn; FLANK window, measure; MAP op */
+    int32_t *rowa, *rowb, *mina, *minb;             /* NEAREST dist, -, dmin, -; FLANK up, down, upmin, downmin; MAP count; */
+    int64_t *agg;                                   /* MAP agg or NULL; rows of nFiles words per query, mins may be NULL */
+} host_job;
+
+static void job_init(host_job *J, int kind, const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                     int64_t lo, int64_t hi, int32_t v, int rule)
+{
+    memset(J, 0, sizeof *J);
+    J->kind = kind; J->db = db; J->m = m; J->ichr = ichr; J->qs = qs; J->qe = qe;
+    J->lo = lo; J->hi = hi;
+    J->v = v; J->use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;   /* gType 0 stores no value (:1024-1025) */
+    J->rule = rule;
+}
+
+/* T jobs over nq queries in contiguous ranges; the caller adds what its kind needs */
+static void jobs_split(host_job *job, int T, int kind, const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs,
+                       const int32_t *qe, int64_t nq, int32_t v, int rule)
+{
+    for (int k = 0; k < T; k++) job_init(&job[k], kind, db, m, ichr, qs, qe, nq * k / T, nq * (k + 1) / T, v, rule);
+}
+
+static void *host_run(void *arg)
+{
+    host_job *J = (host_job *)arg;
+    const igdc_db *db = J->db;
+    const igdc_map *m = J->m;
+    const int32_t *ichr = J->ichr, *qs = J->qs, *qe = J->qe, v = J->v;
+    const int use_v = J->use_v, rule = J->rule;
+    const size_t nf = (size_t)db->nFiles;
+    int64_t tot = 0;
+    tilebuf tb;
+    tb_open(&tb);
+    switch (J->kind) {
+    case JOB_PAIRS:
+        for (int64_t i = J->lo; i < J->hi; i++) {
+            const int64_t n = one_query(db, m, &tb, ichr[i], qs[i], qe[i], v, use_v, rule, J->hits, J->want_out ? &J->out : NULL, (int32_t)i, J->mo);
+            if (J->qcnt) J->qcnt[i] = n;
+            tot += n;
+        }
+        break;
+    case JOB_SUPPORT:
+        for (int64_t i = J->lo; i < J->hi; i++)
+            tot += one_query_support(db, m, &tb, ichr[i], qs[i], qe[i], v, use_v, rule, J->hits, J->last, i + 1, J->mo);
+        break;
+    case JOB_COVERAGE:
+        for (int64_t i = J->lo; i < J->hi; i++)
+            tot += one_query_coverage(db, m, &tb, ichr[i], qs[i], qe[i], v, use_v, rule, J->hits, J->last, J->front, i + 1);
+        break;
+    case JOB_MEMBER:
+        for (int64_t i = J->lo; i < J->hi; i++) {
+            const int n = one_query_member(db, m, &tb, ichr[i], qs[i], qe[i], v, use_v, rule, J->bits + (size_t)i * (size_t)J->nW, J->nW);
+            if (J->nfh) J->nfh[i] = n;
+            tot += n > 0;
+        }
+        break;
+    case JOB_NEAREST:
+        for (int64_t i = J->lo; i < J->hi; i++) {
+            int32_t *row = J->rowa + (size_t)i * nf;
+            const int32_t d = J->sgn ? one_region_nearest_signed(db, m, &tb, ichr[i], qs[i], qe[i], J->window, v, use_v, row)
+                                     : one_region_nearest(db, m, &tb, ichr[i], qs[i], qe[i], J->window, v, use_v, row);
+            if (J->mina) J->mina[i] = d;
+        }
+        break;
+    case JOB_FLANK:
+        for (int64_t i = J->lo; i < J->hi; i++) {
+            uint32_t um, dm;
+            one_region_flanks(db, m, &tb, ichr[i], qs[i], qe[i], J->window, J->measure, v, use_v, (uint32_t *)J->rowa + (size_t)i * nf,
+                              (uint32_t *)J->rowb + (size_t)i * nf, &um, &dm);
+            if (J->mina) J->mina[i] = (int32_t)um;
+            if (J->minb) J->minb[i] = (int32_t)dm;
+        }
+        break;
+    case JOB_MAP:
+        for (int64_t i = J->lo; i < J->hi; i++)
+            one_region_map(db, m, &tb, ichr[i], qs[i], qe[i], J->op, v, use_v, J->rowa + (size_t)i * nf, J->agg ? J->agg + (size_t)i * nf : NULL);
+        break;
+    }
+    J->total = tot;
+    J->io_failed = tb_close(&tb);
+    return NULL;
+}
+
+/* runs the jobs; nonzero if a tile could not be read; *tot (may be NULL) = the sum of the jobs' totals */
+static int jobs_run(host_job *job, int T, int64_t *tot)
+{
+    int bad = 0;
+    int64_t sum = 0;
+    run_threads(host_run, job, sizeof *job, T);
+    for (int k = 0; k < T; k++) { bad |= job[k].io_failed; sum += job[k].total; }
+    if (tot) *tot = sum;
+    return bad;
+}
+
+/* the entries whose answer is a sum over queries (pair counts, support counts, covered base pairs): every thread counts into
+ * nvec private vectors of nFiles + 1 words -- the answer, then the stamps, then the frontiers -- and the answers are ADDED to
+ * out[] only if every tile could be read.  0 and *tot = the sum of the threads' totals, or -1 with out[] as it was. */
+static int run_private(int kind, int nvec, const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                       int64_t nq, int32_t v, int rule, const igd_hip_min_overlap *mo, int64_t *out, int64_t *tot)
+{
+    const int T = host_threads(nq);
+    const size_t nf1 = (size_t)(db->nFiles + 1);
+    host_job job[HOST_MAX_THREADS];
+    int64_t *priv = (int64_t *)calloc((size_t)T * (size_t)nvec * nf1, sizeof(int64_t));
+    if (!priv) return -1;
+    jobs_split(job, T, kind, db, m, ichr, qs, qe, nq, v, rule);
+    for (int k = 0; k < T; k++) {
+        job[k].hits = priv + (size_t)k * (size_t)nvec * nf1;
+        if (nvec > 1) job[k].last = job[k].hits + nf1;
+        if (nvec > 2) job[k].front = job[k].last + nf1;
+        job[k].mo = mo;
+    }
+    const int bad = jobs_run(job, T, tot);
+    for (int k = 0; k < T && !bad; k++)
+        for (int32_t f = 0; f < db->nFiles; f++) out[f] += job[k].hits[f];
+    free(priv);
+    return bad ? -1 : 0;
 }
 
 int igdc_search_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
@@ -397,31 +579,9 @@ int igdc_search_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ich
                         int64_t nq, int32_t v, int rule, int64_t *hits, int64_t *total, const igd_hip_min_overlap *min_overlap)
 {
     if (!db || !m || !hits || nq < 0 || !igd_hip_min_overlap_valid(min_overlap)) return -1;
-    const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
-    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;      /* gType 0 stores no value (:1024-1025) */
-    const int T = host_threads(nq);
-    host_job job[64];
-    /* every thread counts into a private vector; they are added to the caller's hits[] only if every tile could be read */
-    int64_t *priv = (int64_t *)calloc((size_t)T * (size_t)(db->nFiles + 1), sizeof(int64_t));
-    if (!priv) return -1;
-    for (int k = 0; k < T; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
-        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
-        job[k].hits = priv + (size_t)k * (size_t)(db->nFiles + 1);
-        job[k].mo = mo;
-    }
-    run_jobs(job, T);
     int64_t tot = 0;
-    int bad = 0;
-    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
-    for (int k = 0; k < T; k++) {
-        tot += job[k].total;
-        if (!bad) for (int32_t f = 0; f < db->nFiles; f++) hits[f] += job[k].hits[f];
-    }
-    free(priv);
-    if (bad) return -1;
+    if (run_private(JOB_PAIRS, 1, db, m, ichr, qs, qe, nq, v, rule, igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL, hits, &tot) != 0)
+        return -1;
     if (total) *total = tot;
     return 0;
 }
@@ -436,33 +596,9 @@ int igdc_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ic
                          int64_t nq, int32_t v, int rule, int64_t *support, int64_t *nhit, const igd_hip_min_overlap *min_overlap)
 {
     if (!db || !m || !support || nq < 0 || !igd_hip_min_overlap_valid(min_overlap)) return -1;
-    const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
-    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
-    const int T = host_threads(nq);
-    host_job job[64];
-    /* per thread a private support vector and its stamp array; added to the caller's only if every tile could be read */
-    const size_t nf1 = (size_t)(db->nFiles + 1);
-    int64_t *priv = (int64_t *)calloc((size_t)T * 2 * nf1, sizeof(int64_t));
-    if (!priv) return -1;
-    for (int k = 0; k < T; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
-        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
-        job[k].hits = priv + (size_t)k * 2 * nf1;
-        job[k].last = job[k].hits + nf1;
-        job[k].mo = mo;
-    }
-    run_jobs(job, T);
     int64_t tot = 0;
-    int bad = 0;
-    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
-    for (int k = 0; k < T; k++) {
-        tot += job[k].total;
-        if (!bad) for (int32_t f = 0; f < db->nFiles; f++) support[f] += job[k].hits[f];
-    }
-    free(priv);
-    if (bad) return -1;
+    if (run_private(JOB_SUPPORT, 2, db, m, ichr, qs, qe, nq, v, rule, igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL, support, &tot) != 0)
+        return -1;
     if (nhit) *nhit += tot;
     return 0;
 }
@@ -471,32 +607,8 @@ int igdc_coverage_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr
                        int64_t nq, int32_t v, int rule, int64_t *coverage, int64_t *covered)
 {
     if (!db || !m || !coverage || nq < 0) return -1;
-    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
-    const int T = host_threads(nq);
-    host_job job[64];
-    /* per thread a private coverage vector, its stamps and its frontiers; added to the caller's only if every tile could be read */
-    const size_t nf1 = (size_t)(db->nFiles + 1);
-    int64_t *priv = (int64_t *)calloc((size_t)T * 3 * nf1, sizeof(int64_t));
-    if (!priv) return -1;
-    for (int k = 0; k < T; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
-        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
-        job[k].hits = priv + (size_t)k * 3 * nf1;
-        job[k].last = job[k].hits + nf1;
-        job[k].front = job[k].last + nf1;
-    }
-    run_jobs(job, T);
     int64_t tot = 0;
-    int bad = 0;
-    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
-    for (int k = 0; k < T; k++) {
-        tot += job[k].total;
-        if (!bad) for (int32_t f = 0; f < db->nFiles; f++) coverage[f] += job[k].hits[f];
-    }
-    free(priv);
-    if (bad) return -1;
+    if (run_private(JOB_COVERAGE, 3, db, m, ichr, qs, qe, nq, v, rule, NULL, coverage, &tot) != 0) return -1;
     if (covered) *covered += tot;
     return 0;
 }
@@ -505,23 +617,14 @@ int igdc_membership_host(const igdc_db *db, const igdc_map *m, const int32_t *ic
                          int64_t nq, int32_t v, int rule, uint32_t *bits, int32_t *nfiles_hit, int64_t *nhit)
 {
     if (!db || !m || nq < 0 || (nq > 0 && !bits)) return -1;
-    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
     const int T = host_threads(nq);
-    host_job job[64];
+    host_job job[HOST_MAX_THREADS];
     uint32_t none = 0;                       /* (a database without files: rows of no words) */
     /* rows are disjoint per query: every thread writes its queries' rows straight into the caller's */
-    for (int k = 0; k < T; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
-        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].v = v; job[k].use_v = use_v; job[k].rule = rule;
-        job[k].bits = bits ? bits : &none; job[k].nfh = nfiles_hit; job[k].nW = (db->nFiles + 31) / 32;
-    }
-    run_jobs(job, T);
+    jobs_split(job, T, JOB_MEMBER, db, m, ichr, qs, qe, nq, v, rule);
+    for (int k = 0; k < T; k++) { job[k].bits = bits ? bits : &none; job[k].nfh = nfiles_hit; job[k].nW = (db->nFiles + 31) / 32; }
     int64_t tot = 0;
-    int bad = 0;
-    for (int k = 0; k < T; k++) { bad |= job[k].io_failed; tot += job[k].total; }
-    if (bad) return -1;
+    if (jobs_run(job, T, &tot)) return -1;
     if (nhit) *nhit += tot;
     return 0;
 }
@@ -532,19 +635,12 @@ int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ich
     if (!db || !m || !qoff || !out || nq < 0 || nq > INT32_MAX) return -1;
     *out = NULL;
     const int T = host_threads(nq);
-    host_job job[64];
-    for (int k = 0; k < T; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
-        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].v = IGD_HIP_NO_VALUE_FILTER; job[k].use_v = 0; job[k].rule = IGD_HIP_RULE_NEST;    /* -f: rule NEST, no filter */
-        job[k].qcnt = qoff;                 /* counts first, turned into offsets below */
-        job[k].want_out = 1;
-    }
-    run_jobs(job, T);
+    host_job job[HOST_MAX_THREADS];
+    jobs_split(job, T, JOB_PAIRS, db, m, ichr, qs, qe, nq, IGD_HIP_NO_VALUE_FILTER, IGD_HIP_RULE_NEST);      /* -f: rule NEST, no filter */
+    for (int k = 0; k < T; k++) { job[k].qcnt = qoff; job[k].want_out = 1; }       /* counts first, turned into offsets below */
+    int failed = jobs_run(job, T, NULL);
     int64_t tot = 0;
-    int failed = 0;
-    for (int k = 0; k < T; k++) { tot += job[k].out.n; failed |= job[k].out.failed | job[k].io_failed; }
+    for (int k = 0; k < T; k++) { tot += job[k].out.n; failed |= job[k].out.failed; }
     igd_hip_hit *all = failed ? NULL : (igd_hip_hit *)malloc(sizeof(igd_hip_hit) * (size_t)(tot ? tot : 1));
     if (!all) failed = 1;
     int64_t at = 0;
@@ -561,6 +657,17 @@ int igdc_enumerate_host(const igdc_db *db, const igdc_map *m, const int32_t *ich
     if (total) *total = tot;
     return 0;
 }
+
+/* ---- region sets: the offsets' check and the loop over chunks of regions ---------------------------------------------------
+ * set_off_bad: nsets >= 0 offsets from 0 that never fall, and the region arrays if there is a region. */
+static int set_off_bad(const int64_t *set_off, int32_t nsets, const int32_t *ichr, const int32_t *qs, const int32_t *qe)
+{
+    if (nsets < 0 || (nsets > 0 && (!set_off || set_off[0] != 0))) return 1;
+    for (int32_t k = 0; k < nsets; k++)
+        if (set_off[k + 1] < set_off[k]) return 1;
+    return nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe);
+}
+
 
 /* Fisher's exact test of 2x2 tables on the host: what igd_fisher_cells (engine/fisher_dev.hpp) computes, by the same scheme
  * -- log space, nine log-factorials per term added in the same pairs, the tail summed from the side on which it decays in
@@ -740,12 +847,8 @@ static int restrict_ent_cmp(const void *x, const void *y)
 static int restrict_args_bad(const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
                              const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu)
 {
-    if (nsets < 0 || nsets == INT32_MAX || nu < 0 || nu + 1 >= ((int64_t)1 << 31) || (nu > 0 && (!u_ichr || !u_qs || !u_qe)) ||
-        (nsets > 0 && (!set_off || set_off[0] != 0)))
-        return 1;
-    for (int32_t k = 0; k < nsets; k++)
-        if (set_off[k + 1] < set_off[k]) return 1;
-    return nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe);
+    return nsets == INT32_MAX || nu < 0 || nu + 1 >= ((int64_t)1 << 31) || (nu > 0 && (!u_ichr || !u_qs || !u_qe)) ||
+           set_off_bad(set_off, nsets, ichr, qs, qe);
 }
 
 int igdc_restrict_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
@@ -891,19 +994,12 @@ static void gram_host(const uint32_t *a, int64_t m, const uint32_t *b, int64_t n
     if (m <= 0 || n <= 0) return;
     const double work = (double)m * (double)n * (double)(nw + 1) / 1024.0;     /* a thread per ~2 x 10^6 word pairs */
     const int T = host_threads(work > 1e15 ? (int64_t)1e15 : (int64_t)work);
-    gram_job job[64];
-    pthread_t th[64];
-    int started[64];
+    gram_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T; k++) {
         job[k].a = a; job[k].b = b; job[k].m = m; job[k].n = n; job[k].stride = stride; job[k].nw = nw; job[k].ldo = ldo;
         job[k].out = out; job[k].k = k; job[k].T = T;
     }
-    for (int k = 1; k < T; k++) {
-        started[k] = pthread_create(&th[k], NULL, gram_run, &job[k]) == 0;
-        if (!started[k]) gram_run(&job[k]);
-    }
-    gram_run(&job[0]);
-    for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
+    run_threads(gram_run, job, sizeof job[0], T);
 }
 
 int igdc_bitrows_gram_host(const uint32_t *a, int64_t m, const uint32_t *b, int64_t n, int64_t nwords32, int64_t *out)
@@ -1123,47 +1219,92 @@ int64_t igdc_permute_first_bad(const int32_t *ichr, const int32_t *qs, const int
     return -1;
 }
 
+/* the refusals the three drivers share (each adds its own in front): the set and the contig lengths, a mode the call can run, the
+ * number of permutations, the generator's bounds on the regions, and under a workspace a table that is valid for the database's
+ * contigs and has a segment for every region on a known contig */
+static int perm_args_bad(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *ctg_len, int mode, int64_t nperm, const igd_hip_workspace *ws)
+{
+    return !db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) || !perm_mode_ok(mode, ws) ||
+           nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 ||
+           (ws && (!igd_hip_workspace_valid(ws, ctg_len, db->nCtg) || igdc_workspace_first_unplaceable(ws, ctg_len, ichr, qs, qe, nq) >= 0));
+}
+
+/* What a thread of the three drivers knows about the rows.  Row 0 is the set as given, row r > 0 permutation r - 1 of the
+ * generator, filled into the thread's own arrays; thread k of T takes the rows first + k, first + k + T, .. below nrows and
+ * hands each, with its arrays, to the driver's row function, until one answers nonzero (a tile that could not be read). */
 typedef struct {
     const igdc_db *db; const igdc_map *m;
     const int32_t *ichr, *qs, *qe, *ctg_len;
-    int64_t nq, nperm;
+    int64_t nq, first, nrows;
     int mode; uint64_t seed;
-    int32_t v; int use_v, rule;
+    const igd_hip_workspace *ws;        /* the checked table of mode IGD_HIP_PERM_WORKSPACE, or NULL */
+    int32_t *ps, *pe;                   /* the permuted set */
+    int k, T, failed;
+} perm_stripe;
+typedef int (*perm_row_fn)(void *job, int64_t r, const int32_t *s, const int32_t *e);
+
+static void stripe_init(perm_stripe *S, const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                        int64_t nq, const int32_t *ctg_len, int mode, uint64_t seed, const igd_hip_workspace *ws, int64_t first, int64_t nrows,
+                        int32_t *ps, int k, int T)
+{
+    S->db = db; S->m = m; S->ichr = ichr; S->qs = qs; S->qe = qe; S->ctg_len = ctg_len;
+    S->nq = nq; S->first = first; S->nrows = nrows; S->mode = mode; S->seed = seed; S->ws = ws;
+    S->ps = ps; S->pe = ps + nq;
+    S->k = k; S->T = T; S->failed = 0;
+}
+
+static void perm_rows(perm_stripe *S, perm_row_fn row, void *job)
+{
+    for (int64_t r = S->first + S->k; r < S->nrows && !S->failed; r += S->T) {
+        const int32_t *s = S->qs, *e = S->qe;
+        if (r > 0) {
+            perm_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->mode, S->seed, r - 1, 1, S->ps, S->pe, S->ws);
+            s = S->ps; e = S->pe;
+        }
+        if (row(job, r, s, e)) S->failed = 1;
+    }
+}
+
+/* igdc_permute_host's thread: rows 1 .. nperm, each walked with the per-query code of igdc_support_host and folded into the
+ * thread's own statistics */
+typedef struct {
+    perm_stripe s;
+    int32_t v; int rule;
     const int64_t *observed;
     int64_t *acc;           /* sum, sumsq, n_ge, n_le, min, max: nFiles + 1 words each */
-    int32_t *ps, *pe;       /* the permuted set */
     int64_t *row, *last;
-    int k, T, io_failed;
     const igd_hip_min_overlap *mo;      /* an active minimum overlap, or NULL */
-    const igd_hip_workspace *ws;        /* the checked table of mode IGD_HIP_PERM_WORKSPACE, or NULL */
 } perm_job;
 
+static int perm_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
+{
+    perm_job *P = (perm_job *)job;
+    const int64_t nF = P->s.db->nFiles, nC = nF + 1;
+    (void)r;
+    memset(P->row, 0, sizeof(int64_t) * (size_t)nC);
+    memset(P->last, 0, sizeof(int64_t) * (size_t)nC);
+    host_job J;
+    job_init(&J, JOB_SUPPORT, P->s.db, P->s.m, P->s.ichr, s, e, 0, P->s.nq, P->v, P->rule);
+    J.hits = P->row; J.last = P->last; J.mo = P->mo;
+    host_run(&J);
+    if (J.io_failed) return 1;
+    P->row[nF] = J.total;
+    for (int64_t f = 0; f < nC; f++) {
+        const int64_t x = P->row[f];
+        P->acc[f] += x;
+        P->acc[nC + f] += x * x;
+        P->acc[2 * nC + f] += x >= P->observed[f];
+        P->acc[3 * nC + f] += x <= P->observed[f];
+        if (x < P->acc[4 * nC + f]) P->acc[4 * nC + f] = x;
+        if (x > P->acc[5 * nC + f]) P->acc[5 * nC + f] = x;
+    }
+    return 0;
+}
 static void *perm_run(void *arg)
 {
     perm_job *P = (perm_job *)arg;
-    const int64_t nF = P->db->nFiles, nC = nF + 1;
-    for (int64_t p = P->k; p < P->nperm && !P->io_failed; p += P->T) {
-        perm_regions_fill(P->ichr, P->qs, P->qe, P->nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, p, 1, P->ps, P->pe, P->ws);
-        memset(P->row, 0, sizeof(int64_t) * (size_t)nC);
-        memset(P->last, 0, sizeof(int64_t) * (size_t)nC);
-        host_job J;
-        memset(&J, 0, sizeof J);
-        J.db = P->db; J.m = P->m; J.ichr = P->ichr; J.qs = P->ps; J.qe = P->pe;
-        J.lo = 0; J.hi = P->nq; J.v = P->v; J.use_v = P->use_v; J.rule = P->rule;
-        J.hits = P->row; J.last = P->last; J.mo = P->mo;
-        host_run(&J);
-        if (J.io_failed) { P->io_failed = 1; break; }
-        P->row[nF] = J.total;
-        for (int64_t f = 0; f < nC; f++) {
-            const int64_t x = P->row[f];
-            P->acc[f] += x;
-            P->acc[nC + f] += x * x;
-            P->acc[2 * nC + f] += x >= P->observed[f];
-            P->acc[3 * nC + f] += x <= P->observed[f];
-            if (x < P->acc[4 * nC + f]) P->acc[4 * nC + f] = x;
-            if (x > P->acc[5 * nC + f]) P->acc[5 * nC + f] = x;
-        }
-    }
+    perm_rows(&P->s, perm_row, P);
     return NULL;
 }
 
@@ -1183,25 +1324,15 @@ int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ic
                                 min_overlap, NULL);
 }
 
-/* the refusals the three drivers add under a workspace, behind their own: a table that is not valid for the database's contigs,
- * a region on a known contig that fits in no segment */
-static int perm_ws_refused(const igdc_db *db, const igd_hip_workspace *ws, const int32_t *ctg_len, const int32_t *ichr, const int32_t *qs,
-                           const int32_t *qe, int64_t nq)
-{
-    return ws && (!igd_hip_workspace_valid(ws, ctg_len, db->nCtg) || igdc_workspace_first_unplaceable(ws, ctg_len, ichr, qs, qe, nq) >= 0);
-}
-
 int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
                          int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
                          const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
 {
     const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
-    if (!igd_hip_min_overlap_valid(min_overlap) || !db || !m || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || !perm_mode_ok(mode, ws) ||
-        nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() ||
-        (unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63 ||
-        igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 || perm_ws_refused(db, ws, ctg_len, ichr, qs, qe, nq))
+    if (!igd_hip_min_overlap_valid(min_overlap) || !observed || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) ||
+        perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws) ||
+        (unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63)
         return -1;
     const int64_t nF = db->nFiles, nC = nF + 1;
     int T = host_threads(nq * nperm > 0 ? nq * nperm : 1);
@@ -1212,29 +1343,17 @@ int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ic
     int rc = w && pq ? 0 : -1;
     int64_t *obs = w ? w + (size_t)T * 8 * (size_t)nC : NULL;
     if (rc == 0 && nq > 0) rc = igdc_support_host_ov(db, m, ichr, qs, qe, nq, v, rule, obs, &obs[nF], mo);
-    perm_job job[64];
-    pthread_t th[64];
-    int started[64];
+    perm_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe; job[k].ctg_len = ctg_len;
-        job[k].nq = nq; job[k].nperm = nperm; job[k].mode = mode; job[k].seed = seed;
-        job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1; job[k].rule = rule;
-        job[k].observed = obs;
+        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 1, nperm + 1, pq + (size_t)k * 2 * (size_t)nq, k, T);
+        job[k].v = v; job[k].rule = rule; job[k].observed = obs; job[k].mo = mo;
         job[k].acc = w + (size_t)k * 8 * (size_t)nC;
         job[k].row = job[k].acc + 6 * nC; job[k].last = job[k].row + nC;
-        job[k].ps = pq + (size_t)k * 2 * (size_t)nq; job[k].pe = job[k].ps + nq;
-        job[k].k = k; job[k].T = T; job[k].mo = mo; job[k].ws = ws;
         for (int64_t f = 0; f < nC; f++) { job[k].acc[4 * nC + f] = INT64_MAX; job[k].acc[5 * nC + f] = INT64_MIN; }
     }
     if (rc == 0) {
-        for (int k = 1; k < T; k++) {
-            started[k] = pthread_create(&th[k], NULL, perm_run, &job[k]) == 0;
-            if (!started[k]) perm_run(&job[k]);
-        }
-        perm_run(&job[0]);
-        for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
-        for (int k = 0; k < T; k++) if (job[k].io_failed) rc = -1;
+        run_threads(perm_run, job, sizeof job[0], T);
+        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
     }
     if (rc == 0) {
         int64_t *a0 = job[0].acc;
@@ -1277,116 +1396,18 @@ int igdc_perm_summary(const int64_t *observed, const int64_t *sum, const int64_t
     return 0;
 }
 
-/* ---- nearest record per dataset within a window (include/igd_hip.h has the definitions) ----------------------------------
- * One region: its row is set to -1, the interval is widened by the window (igd_hip_nearest_widen), the tiles of the widened
- * interval are visited as one_query visits them under rule FLAT -- bisection for the last start < we, backwards while
- * end > ws, in later tiles only down to the tile's start (the prefix skip) -- and every counted record lowers row[idx] to
- * its d, computed from the region as given (igd_hip_nearest_dist).  Returns the minimum over the files, or -1.
- * one_region_keys is that walk on unsigned words, 0xffffffff (= -1) for "none": with sgn it minimises igd_hip_nearest_key
- * instead of d, and one_region_nearest_signed decodes the row and the minimum (igd_hip_nearest_key_decode). */
-static inline uint32_t one_region_keys(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
-                                       int32_t window, int32_t v, int use_v, int sgn, uint32_t *row)
-{
-    const int32_t nf = db->nFiles;
-    for (int32_t f = 0; f < nf; f++) row[f] = 0xffffffffu;
-    if (ichr < 0 || ichr >= db->nCtg) return 0xffffffffu;
-    int32_t ws, we;
-    igd_hip_nearest_widen(qs, qe, window, &ws, &we);
-    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
-    const int32_t n1 = ws / nbp;
-    int32_t n2 = (int32_t)((uint32_t)we - 1u) / nbp;
-    if (n1 < 0 || n1 > mT) return 0xffffffffu;                             /* (no record ends behind the contig's last tile) */
-    if (n2 > mT) n2 = mT;
-    const int w = db->gType == 0 ? 3 : 4;
-    uint32_t best = 0xffffffffu;
-    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
-        const int32_t cnt = db->nCnt[ichr][j];
-        if (cnt <= 0) continue;
-        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
-        if (!rec) return best;
-        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
-        for (int32_t i = below(rec, w, cnt, we) - 1; i >= 0; i--) {
-            const int32_t *r = rec + (size_t)i * (size_t)w;
-            if ((int64_t)r[1] < lob) break;
-            if (r[2] > ws && (!use_v || r[3] >= v)) {
-                if (r[0] < 0 || r[0] >= nf) continue;
-                const uint32_t d = sgn ? igd_hip_nearest_key(qs, qe, r[1], r[2]) : (uint32_t)igd_hip_nearest_dist(qs, qe, r[1], r[2]);
-                if (d < row[r[0]]) row[r[0]] = d;
-                if (d < best) best = d;
-            }
-        }
-    }
-    return best;
-}
-
-static inline int32_t one_region_nearest(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
-                                         int32_t window, int32_t v, int use_v, int32_t *row)
-{
-    return (int32_t)one_region_keys(db, m, tb, ichr, qs, qe, window, v, use_v, 0, (uint32_t *)row);
-}
-
-static inline int32_t one_region_nearest_signed(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
-                                                int32_t window, int32_t v, int use_v, int32_t *row)
-{
-    const uint32_t best = one_region_keys(db, m, tb, ichr, qs, qe, window, v, use_v, 1, (uint32_t *)row);
-    for (int32_t f = 0; f < db->nFiles; f++) row[f] = igd_hip_nearest_key_decode((uint32_t)row[f]);
-    return igd_hip_nearest_key_decode(best);
-}
-
-typedef struct {
-    const igdc_db *db; const igdc_map *m;
-    const int32_t *ichr, *qs, *qe;
-    int64_t lo, hi;
-    int32_t window, v; int use_v, sgn;
-    int32_t *dist, *dmin;
-    int io_failed;
-} nearest_job;
-
-static void *nearest_run(void *arg)
-{
-    nearest_job *J = (nearest_job *)arg;
-    tilebuf tb;
-    memset(&tb, 0, sizeof tb);
-    tb.ichr = -1;
-    const size_t nf = (size_t)J->db->nFiles;
-    for (int64_t i = J->lo; i < J->hi; i++) {
-        int32_t *row = J->dist + (size_t)i * nf;
-        const int32_t d = J->sgn ? one_region_nearest_signed(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->window, J->v, J->use_v, row)
-                                 : one_region_nearest(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->window, J->v, J->use_v, row);
-        if (J->dmin) J->dmin[i] = d;
-    }
-    J->io_failed = tb.failed;
-    free(tb.buf);
-    return NULL;
-}
-
+/* ---- nearest record per dataset within a window: the entries (one_region_keys has the walk) ------------------------------ */
 static int nearest_rows_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                              int32_t window, int32_t v, int sgn, int32_t *dist, int32_t *dmin)
 {
     if (!db || !m || nq < 0 || !igd_hip_nearest_window_valid(window) || (nq > 0 && (!ichr || !qs || !qe || (!dist && db->nFiles > 0)))) return -1;
-    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
     const int T = host_threads(nq);
-    nearest_job job[64];
-    pthread_t th[64];
-    int started[64];
+    host_job job[HOST_MAX_THREADS];
     int32_t none = 0;                        /* (a database without files: rows of no words) */
     /* rows are disjoint per region: every thread writes its regions' rows straight into the caller's */
-    for (int k = 0; k < T; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
-        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].window = window; job[k].v = v; job[k].use_v = use_v; job[k].sgn = sgn;
-        job[k].dist = dist ? dist : &none; job[k].dmin = dmin;
-    }
-    for (int k = 1; k < T; k++) {
-        started[k] = pthread_create(&th[k], NULL, nearest_run, &job[k]) == 0;
-        if (!started[k]) nearest_run(&job[k]);
-    }
-    nearest_run(&job[0]);
-    for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
-    int bad = 0;
-    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
-    return bad ? -1 : 0;
+    jobs_split(job, T, JOB_NEAREST, db, m, ichr, qs, qe, nq, v, 0);
+    for (int k = 0; k < T; k++) { job[k].window = window; job[k].sgn = sgn; job[k].rowa = dist ? dist : &none; job[k].mina = dmin; }
+    return jobs_run(job, T, NULL) ? -1 : 0;
 }
 
 int igdc_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -1401,209 +1422,168 @@ int igdc_nearest_signed_host(const igdc_db *db, const igdc_map *m, const int32_t
     return nearest_rows_host(db, m, ichr, qs, qe, nq, window, v, 1, sdist, sdmin);
 }
 
-#define NEAREST_HOST_ROW_BYTES ((int64_t)32 << 20)   /* igdc_nearest_sets_host: distance rows of one chunk of regions */
+/* ---- per-set statistics of per-region rows: the loop over chunks of regions ----------------------------------------------
+ * The rows of a whole set list need not fit in memory, so they are computed for chunks of regions -- as many as HOST_ROW_BYTES
+ * hold (IGD_HOST_ROW_BYTES overrides it: for tests of the seam) -- by the entry's row computer, and every region of the chunk
+ * is handed with its set to the entry's fold.  The set index runs along with the regions; empty sets are passed over.  A *_sets
+ * entry is its refusals, a row computer and a fold. */
+#define HOST_ROW_BYTES ((int64_t)32 << 20)
+typedef int (*chunk_rows_fn)(void *ctx, int64_t c0, int64_t n);        /* the rows of regions [c0, c0 + n); 0 or -1 */
+typedef void (*chunk_fold_fn)(void *ctx, int32_t set, int64_t i);       /* region i of the chunk belongs to `set` */
+
+static int64_t chunk_regions(int64_t bytes_per_region, int64_t nq)
+{
+    const char *e = getenv("IGD_HOST_ROW_BYTES");
+    const long long x = e && *e ? atoll(e) : 0;
+    const int64_t chunk = (x > 0 ? (int64_t)x : HOST_ROW_BYTES) / bytes_per_region;
+    return chunk < 1 ? 1 : chunk > nq ? nq : chunk;
+}
+
+static int set_chunks(const int64_t *set_off, int32_t nsets, int64_t chunk, chunk_rows_fn rows, chunk_fold_fn fold, void *ctx)
+{
+    const int64_t nq = nsets > 0 ? set_off[nsets] : 0;
+    int32_t k = 0;
+    for (int64_t c0 = 0; c0 < nq; c0 += chunk) {
+        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
+        const int rc = rows(ctx, c0, n);
+        if (rc != 0) return rc;
+        for (int64_t i = 0; i < n; i++) {
+            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
+            fold(ctx, k, i);
+        }
+    }
+    return 0;
+}
+
+/* igdc_nearest_sets_host and igdc_nearest_hist_host: the (signed) distance rows of a chunk, each word counted into its set's
+ * three statistics, or into its bin of its set's histogram */
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe;
+    int32_t window, v; int sgn;
+    int32_t *dist, *dmin;                           /* the chunk's rows */
+    int64_t *n_within, *n_overlap, *sum_dist;       /* nearest_sets' outputs (each may be NULL) */
+    const int32_t *edges; int32_t ne; int64_t *hist;
+} nearest_sets_ctx;
+
+static int nearest_sets_rows(void *ctx, int64_t c0, int64_t n)
+{
+    nearest_sets_ctx *c = (nearest_sets_ctx *)ctx;
+    return nearest_rows_host(c->db, c->m, c->ichr + c0, c->qs + c0, c->qe + c0, n, c->window, c->v, c->sgn, c->dist, c->dmin);
+}
+static void nearest_sets_fold(void *ctx, int32_t k, int64_t i)
+{
+    nearest_sets_ctx *c = (nearest_sets_ctx *)ctx;
+    const int64_t nf = c->db->nFiles, nC = nf + 1;
+    const int32_t *row = c->dist + (size_t)i * (size_t)nf;
+    const size_t o = (size_t)k * (size_t)nC;
+    for (int64_t f = 0; f < nC; f++) {
+        const int32_t d = f < nf ? row[f] : c->dmin[i];
+        if (d < 0) continue;
+        if (c->n_within) c->n_within[o + f]++;
+        if (c->n_overlap && d == 0) c->n_overlap[o + f]++;
+        if (c->sum_dist) c->sum_dist[o + f] += d;
+    }
+}
+static void nearest_hist_fold(void *ctx, int32_t k, int64_t i)
+{
+    nearest_sets_ctx *c = (nearest_sets_ctx *)ctx;
+    const int64_t nf = c->db->nFiles, nC = nf + 1;
+    const int32_t *row = c->dist + (size_t)i * (size_t)nf;
+    int64_t *h = c->hist + (size_t)k * (size_t)(c->ne + 1) * (size_t)nC;
+    for (int64_t f = 0; f < nC; f++) {
+        const int32_t x = f < nf ? row[f] : c->dmin[i];
+        if (x != IGD_HIP_NEAREST_NO_RECORD) h[(size_t)igd_hip_nearest_bin(c->edges, c->ne, x) * (size_t)nC + (size_t)f]++;
+    }
+}
+/* allocates the chunk's rows, runs the chunks with `fold`, frees */
+static int nearest_sets_run(nearest_sets_ctx *c, const int64_t *set_off, int32_t nsets, chunk_fold_fn fold)
+{
+    const int64_t nf = c->db->nFiles, chunk = chunk_regions(4 * (nf > 0 ? nf : 1), nsets > 0 ? set_off[nsets] : 0);
+    c->dist = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk * nf + 1));
+    c->dmin = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk + 1));
+    const int rc = c->dist && c->dmin ? set_chunks(set_off, nsets, chunk, nearest_sets_rows, fold, c) : -1;
+    free(c->dist); free(c->dmin);
+    return rc;
+}
+
 int igdc_nearest_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                            const int64_t *set_off, int32_t nsets, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
                            int64_t *sum_dist)
 {
-    if (!db || !m || nsets < 0 || !igd_hip_nearest_window_valid(window) || (nsets > 0 && (!set_off || set_off[0] != 0))) return -1;
-    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
-    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) return -1;
-    const int64_t nf = db->nFiles, nC = nf + 1, nq = nsets > 0 ? set_off[nsets] : 0;
-    int64_t chunk = NEAREST_HOST_ROW_BYTES / (4 * (nf > 0 ? nf : 1));
-    chunk = chunk < 1 ? 1 : chunk > nq ? nq : chunk;
-    int32_t *dist = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk * nf + 1)), *dmin = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk + 1));
-    if (!dist || !dmin) { free(dist); free(dmin); return -1; }
+    if (!db || !m || !igd_hip_nearest_window_valid(window) || set_off_bad(set_off, nsets, ichr, qs, qe)) return -1;
+    nearest_sets_ctx c = {db, m, ichr, qs, qe, window, v, 0, NULL, NULL, n_within, n_overlap, sum_dist, NULL, 0, NULL};
     int64_t *outs[3] = {n_within, n_overlap, sum_dist};
-    for (int i = 0; i < 3; i++) if (outs[i]) memset(outs[i], 0, sizeof(int64_t) * (size_t)nsets * (size_t)nC);
-    int rc = 0;
-    int32_t k = 0;
-    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += chunk) {
-        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
-        rc = igdc_nearest_host(db, m, ichr + c0, qs + c0, qe + c0, n, window, v, dist, dmin);
-        for (int64_t i = 0; i < n && rc == 0; i++) {
-            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
-            const int32_t *row = dist + (size_t)i * (size_t)nf;
-            const size_t o = (size_t)k * (size_t)nC;
-            for (int64_t f = 0; f < nC; f++) {
-                const int32_t d = f < nf ? row[f] : dmin[i];
-                if (d < 0) continue;
-                if (n_within) n_within[o + f]++;
-                if (n_overlap && d == 0) n_overlap[o + f]++;
-                if (sum_dist) sum_dist[o + f] += d;
-            }
-        }
-    }
-    free(dist); free(dmin);
-    return rc;
+    for (int i = 0; i < 3; i++) if (outs[i]) memset(outs[i], 0, sizeof(int64_t) * (size_t)nsets * (size_t)(db->nFiles + 1));
+    return nearest_sets_run(&c, set_off, nsets, nearest_sets_fold);
 }
 
-/* the signed rows of a chunk of regions (igdc_nearest_signed_host), each word counted into its bin of its set's histogram */
 int igdc_nearest_hist_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                            const int64_t *set_off, int32_t nsets, int32_t window, int32_t v, const int32_t *edges, int32_t ne,
                            int64_t *hist)
 {
-    if (!db || !m || nsets < 0 || !igd_hip_nearest_window_valid(window) || !igd_hip_nearest_edges_valid(edges, ne) ||
-        (nsets > 0 && (!set_off || set_off[0] != 0 || !hist))) return -1;
-    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
-    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) return -1;
-    const int64_t nf = db->nFiles, nC = nf + 1, nq = nsets > 0 ? set_off[nsets] : 0;
-    const size_t setWords = (size_t)(ne + 1) * (size_t)nC;
-    int64_t chunk = NEAREST_HOST_ROW_BYTES / (4 * (nf > 0 ? nf : 1));
-    chunk = chunk < 1 ? 1 : chunk > nq ? nq : chunk;
-    int32_t *dist = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk * nf + 1)), *dmin = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk + 1));
-    if (!dist || !dmin) { free(dist); free(dmin); return -1; }
-    if (nsets > 0) memset(hist, 0, sizeof(int64_t) * (size_t)nsets * setWords);
-    int rc = 0;
-    int32_t k = 0;
-    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += chunk) {
-        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
-        rc = igdc_nearest_signed_host(db, m, ichr + c0, qs + c0, qe + c0, n, window, v, dist, dmin);
-        for (int64_t i = 0; i < n && rc == 0; i++) {
-            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
-            const int32_t *row = dist + (size_t)i * (size_t)nf;
-            int64_t *h = hist + (size_t)k * setWords;
-            for (int64_t f = 0; f < nC; f++) {
-                const int32_t x = f < nf ? row[f] : dmin[i];
-                if (x != IGD_HIP_NEAREST_NO_RECORD) h[(size_t)igd_hip_nearest_bin(edges, ne, x) * (size_t)nC + (size_t)f]++;
-            }
-        }
-    }
-    free(dist); free(dmin);
-    return rc;
+    if (!db || !m || !igd_hip_nearest_window_valid(window) || !igd_hip_nearest_edges_valid(edges, ne) || (nsets > 0 && !hist) ||
+        set_off_bad(set_off, nsets, ichr, qs, qe)) return -1;
+    nearest_sets_ctx c = {db, m, ichr, qs, qe, window, v, 1, NULL, NULL, NULL, NULL, NULL, edges, ne, hist};
+    if (nsets > 0) memset(hist, 0, sizeof(int64_t) * (size_t)nsets * (size_t)(ne + 1) * (size_t)(db->nFiles + 1));
+    return nearest_sets_run(&c, set_off, nsets, nearest_hist_fold);
 }
 
-/* ---- flanking records per dataset and the relative-distance histogram (include/igd_hip.h has the definitions) -----------
- * One region: one_region_keys' walk -- the same tiles, the same counted records -- with two unsigned words per file, 0xffffffff
- * (= -1) for "none": igd_hip_flank_pair says on which side a counted record lies and how far, and it lowers that side's word.
- * The minima over the files go to *upmin and *downmin. */
-static inline void one_region_flanks(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe,
-                                     int32_t window, int measure, int32_t v, int use_v, uint32_t *up, uint32_t *down, uint32_t *upmin,
-                                     uint32_t *downmin)
-{
-    const int32_t nf = db->nFiles;
-    for (int32_t f = 0; f < nf; f++) up[f] = down[f] = 0xffffffffu;
-    *upmin = *downmin = 0xffffffffu;
-    if (ichr < 0 || ichr >= db->nCtg) return;
-    int32_t ws, we;
-    igd_hip_nearest_widen(qs, qe, window, &ws, &we);
-    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
-    const int32_t n1 = ws / nbp;
-    int32_t n2 = (int32_t)((uint32_t)we - 1u) / nbp;
-    if (n1 < 0 || n1 > mT) return;                                         /* (no record ends behind the contig's last tile) */
-    if (n2 > mT) n2 = mT;
-    const int w = db->gType == 0 ? 3 : 4;
-    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
-        const int32_t cnt = db->nCnt[ichr][j];
-        if (cnt <= 0) continue;
-        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
-        if (!rec) return;
-        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
-        for (int32_t i = below(rec, w, cnt, we) - 1; i >= 0; i--) {
-            const int32_t *r = rec + (size_t)i * (size_t)w;
-            if ((int64_t)r[1] < lob) break;
-            if (r[2] > ws && (!use_v || r[3] >= v)) {
-                if (r[0] < 0 || r[0] >= nf) continue;
-                uint32_t d = 0;
-                const int side = igd_hip_flank_pair(measure, window, qs, qe, r[1], r[2], &d);
-                if (side == IGD_HIP_FLANK_NEITHER) continue;
-                uint32_t *row = side == IGD_HIP_FLANK_UP ? up : down, *best = side == IGD_HIP_FLANK_UP ? upmin : downmin;
-                if (d < row[r[0]]) row[r[0]] = d;
-                if (d < *best) *best = d;
-            }
-        }
-    }
-}
-
-typedef struct {
-    const igdc_db *db; const igdc_map *m;
-    const int32_t *ichr, *qs, *qe;
-    int64_t lo, hi;
-    int32_t window, v; int use_v, measure;
-    int32_t *up, *down, *upmin, *downmin;
-    int io_failed;
-} flank_job;
-
-static void *flank_run(void *arg)
-{
-    flank_job *J = (flank_job *)arg;
-    tilebuf tb;
-    memset(&tb, 0, sizeof tb);
-    tb.ichr = -1;
-    const size_t nf = (size_t)J->db->nFiles;
-    for (int64_t i = J->lo; i < J->hi; i++) {
-        uint32_t um, dm;
-        one_region_flanks(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->window, J->measure, J->v, J->use_v,
-                          (uint32_t *)J->up + (size_t)i * nf, (uint32_t *)J->down + (size_t)i * nf, &um, &dm);
-        if (J->upmin) J->upmin[i] = (int32_t)um;
-        if (J->downmin) J->downmin[i] = (int32_t)dm;
-    }
-    J->io_failed = tb.failed;
-    free(tb.buf);
-    return NULL;
-}
-
+/* ---- flanking records per dataset and the relative-distance histogram: the entries (one_region_flanks has the walk) ------ */
 int igdc_flank_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                     int32_t window, int measure, int32_t v, int32_t *up, int32_t *down, int32_t *upmin, int32_t *downmin)
 {
     if (!db || !m || nq < 0 || !igd_hip_nearest_window_valid(window) || !igd_hip_flank_measure_valid(measure) ||
         (nq > 0 && (!ichr || !qs || !qe || ((!up || !down) && db->nFiles > 0)))) return -1;
-    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
     const int T = host_threads(nq);
-    flank_job job[64];
-    pthread_t th[64];
-    int started[64];
+    host_job job[HOST_MAX_THREADS];
     int32_t none[2] = {0, 0};                /* (a database without files: rows of no words) */
     /* rows are disjoint per region: every thread writes its regions' rows straight into the caller's */
+    jobs_split(job, T, JOB_FLANK, db, m, ichr, qs, qe, nq, v, 0);
     for (int k = 0; k < T; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
-        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].window = window; job[k].v = v; job[k].use_v = use_v; job[k].measure = measure;
-        job[k].up = up ? up : &none[0]; job[k].down = down ? down : &none[1]; job[k].upmin = upmin; job[k].downmin = downmin;
+        job[k].window = window; job[k].measure = measure;
+        job[k].rowa = up ? up : &none[0]; job[k].rowb = down ? down : &none[1]; job[k].mina = upmin; job[k].minb = downmin;
     }
-    for (int k = 1; k < T; k++) {
-        started[k] = pthread_create(&th[k], NULL, flank_run, &job[k]) == 0;
-        if (!started[k]) flank_run(&job[k]);
-    }
-    flank_run(&job[0]);
-    for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
-    int bad = 0;
-    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
-    return bad ? -1 : 0;
+    return jobs_run(job, T, NULL) ? -1 : 0;
 }
 
 /* the two rows of a chunk of regions (igdc_flank_host), each flanked pair counted into its bin of its set's histogram */
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe;
+    int32_t window, v, nbins; int measure;
+    int32_t *up, *down, *upmin, *downmin;           /* the chunk's rows */
+    int64_t *hist;
+} reldist_ctx;
+
+static int reldist_rows(void *ctx, int64_t c0, int64_t n)
+{
+    reldist_ctx *c = (reldist_ctx *)ctx;
+    return igdc_flank_host(c->db, c->m, c->ichr + c0, c->qs + c0, c->qe + c0, n, c->window, c->measure, c->v, c->up, c->down, c->upmin, c->downmin);
+}
+static void reldist_fold(void *ctx, int32_t k, int64_t i)
+{
+    reldist_ctx *c = (reldist_ctx *)ctx;
+    const int64_t nf = c->db->nFiles, nC = nf + 1;
+    int64_t *h = c->hist + (size_t)k * (size_t)c->nbins * (size_t)nC;
+    for (int64_t f = 0; f < nC; f++) {
+        const int32_t u = f < nf ? c->up[(size_t)i * (size_t)nf + (size_t)f] : c->upmin[i];
+        const int32_t d = f < nf ? c->down[(size_t)i * (size_t)nf + (size_t)f] : c->downmin[i];
+        if (igd_hip_flank_flanked(u, d)) h[(size_t)igd_hip_flank_bin(c->nbins, u, d) * (size_t)nC + (size_t)f]++;
+    }
+}
+
 int igdc_flank_reldist_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                             const int64_t *set_off, int32_t nsets, int32_t window, int measure, int32_t v, int32_t nbins, int64_t *hist)
 {
-    if (!db || !m || nsets < 0 || !igd_hip_nearest_window_valid(window) || !igd_hip_flank_measure_valid(measure) ||
-        !igd_hip_flank_bins_valid(nbins) || (nsets > 0 && (!set_off || set_off[0] != 0 || !hist))) return -1;
-    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
-    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) return -1;
-    const int64_t nf = db->nFiles, nC = nf + 1, nq = nsets > 0 ? set_off[nsets] : 0;
-    const size_t setWords = (size_t)nbins * (size_t)nC;
-    int64_t chunk = NEAREST_HOST_ROW_BYTES / (8 * (nf > 0 ? nf : 1));
-    chunk = chunk < 1 ? 1 : chunk > nq ? nq : chunk;
+    if (!db || !m || !igd_hip_nearest_window_valid(window) || !igd_hip_flank_measure_valid(measure) || !igd_hip_flank_bins_valid(nbins) ||
+        (nsets > 0 && !hist) || set_off_bad(set_off, nsets, ichr, qs, qe)) return -1;
+    const int64_t nf = db->nFiles, chunk = chunk_regions(8 * (nf > 0 ? nf : 1), nsets > 0 ? set_off[nsets] : 0);
     int32_t *rows = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * chunk * nf + 1)), *mins = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * chunk + 1));
     if (!rows || !mins) { free(rows); free(mins); return -1; }
-    int32_t *up = rows, *down = rows + chunk * nf, *upmin = mins, *downmin = mins + chunk;
-    if (nsets > 0) memset(hist, 0, sizeof(int64_t) * (size_t)nsets * setWords);
-    int rc = 0;
-    int32_t k = 0;
-    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += chunk) {
-        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
-        rc = igdc_flank_host(db, m, ichr + c0, qs + c0, qe + c0, n, window, measure, v, up, down, upmin, downmin);
-        for (int64_t i = 0; i < n && rc == 0; i++) {
-            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
-            int64_t *h = hist + (size_t)k * setWords;
-            for (int64_t f = 0; f < nC; f++) {
-                const int32_t u = f < nf ? up[(size_t)i * (size_t)nf + (size_t)f] : upmin[i];
-                const int32_t d = f < nf ? down[(size_t)i * (size_t)nf + (size_t)f] : downmin[i];
-                if (igd_hip_flank_flanked(u, d)) h[(size_t)igd_hip_flank_bin(nbins, u, d) * (size_t)nC + (size_t)f]++;
-            }
-        }
-    }
+    reldist_ctx c = {db, m, ichr, qs, qe, window, v, nbins, measure, rows, rows + chunk * nf, mins, mins + chunk, hist};
+    if (nsets > 0) memset(hist, 0, sizeof(int64_t) * (size_t)nsets * (size_t)nbins * (size_t)(nf + 1));
+    const int rc = set_chunks(set_off, nsets, chunk, reldist_rows, reldist_fold, &c);
     free(rows); free(mins);
     return rc;
 }
@@ -1615,73 +1595,7 @@ int igdc_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, int64
     return 0;
 }
 
-/* ---- values of the overlapping records per region and dataset (include/igd_hip.h has the definitions) --------------------
- * One region: its rows are set to 0 and the tiles of igd_hip_nearest_widen(qs, qe, 0) are visited as one_region_nearest visits
- * them -- bisection for the last start < qe, backwards while end > qs, in later tiles only down to the tile's start (the prefix
- * skip) -- and every counted record adds 1 to count[idx] and folds its value into agg[idx] (NULL under COUNT: nothing). */
-static inline void one_region_map(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int op,
-                                  int32_t v, int use_v, int32_t *count, int64_t *agg)
-{
-    const int32_t nf = db->nFiles;
-    for (int32_t f = 0; f < nf; f++) count[f] = 0;
-    if (agg) for (int32_t f = 0; f < nf; f++) agg[f] = 0;
-    if (ichr < 0 || ichr >= db->nCtg) return;
-    int32_t ws, we;
-    igd_hip_nearest_widen(qs, qe, 0, &ws, &we);
-    const int32_t nbp = db->nbp, mT = db->nTile[ichr] - 1;
-    const int32_t n1 = ws / nbp;
-    int32_t n2 = (int32_t)((uint32_t)we - 1u) / nbp;
-    if (n1 < 0 || n1 > mT) return;                                         /* (no record ends behind the contig's last tile) */
-    if (n2 > mT) n2 = mT;
-    const int w = db->gType == 0 ? 3 : 4;
-    for (int32_t j = n1; j <= (n2 > n1 ? n2 : n1); j++) {
-        const int32_t cnt = db->nCnt[ichr][j];
-        if (cnt <= 0) continue;
-        const int32_t *rec = tile_records(db, m, tb, ichr, j, cnt);
-        if (!rec) return;
-        const int64_t lob = j == n1 ? INT64_MIN : (int64_t)(int32_t)((uint32_t)nbp * (uint32_t)j);
-        for (int32_t i = below(rec, w, cnt, we) - 1; i >= 0; i--) {
-            const int32_t *r = rec + (size_t)i * (size_t)w;
-            if ((int64_t)r[1] < lob) break;
-            if (r[2] > ws && (!use_v || r[3] >= v)) {
-                if (r[0] < 0 || r[0] >= nf) continue;
-                const int32_t f = r[0];
-                if (op != IGD_HIP_MAP_COUNT) {
-                    const int64_t val = r[3];
-                    if (op == IGD_HIP_MAP_SUM) agg[f] = (int64_t)((uint64_t)agg[f] + (uint64_t)val);
-                    else if (count[f] == 0 || (op == IGD_HIP_MAP_MIN ? val < agg[f] : val > agg[f])) agg[f] = val;
-                }
-                count[f]++;
-            }
-        }
-    }
-    if (agg && op == IGD_HIP_MAP_COUNT) for (int32_t f = 0; f < nf; f++) agg[f] = count[f];
-}
-
-typedef struct {
-    const igdc_db *db; const igdc_map *m;
-    const int32_t *ichr, *qs, *qe;
-    int64_t lo, hi;
-    int op; int32_t v; int use_v;
-    int32_t *count; int64_t *agg;
-    int io_failed;
-} map_job;
-
-static void *map_run(void *arg)
-{
-    map_job *J = (map_job *)arg;
-    tilebuf tb;
-    memset(&tb, 0, sizeof tb);
-    tb.ichr = -1;
-    const size_t nf = (size_t)J->db->nFiles;
-    for (int64_t i = J->lo; i < J->hi; i++)
-        one_region_map(J->db, J->m, &tb, J->ichr[i], J->qs[i], J->qe[i], J->op, J->v, J->use_v, J->count + (size_t)i * nf,
-                       J->agg ? J->agg + (size_t)i * nf : NULL);
-    J->io_failed = tb.failed;
-    free(tb.buf);
-    return NULL;
-}
-
+/* ---- values of the overlapping records per region and dataset: the entries (one_region_map has the walk) ----------------- */
 static int map_op_ok(const igdc_db *db, int op) { return igd_hip_map_op_valid(op) && (op == IGD_HIP_MAP_COUNT || db->gType == 1); }
 
 int igdc_map_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int op,
@@ -1689,62 +1603,54 @@ int igdc_map_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, con
 {
     if (!db || !m || nq < 0 || !map_op_ok(db, op)) return -1;
     if (nq > 0 && (!ichr || !qs || !qe || (db->nFiles > 0 && (!count || (!agg && op != IGD_HIP_MAP_COUNT))))) return -1;
-    const int use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
     const int T = host_threads(nq);
-    map_job job[64];
-    pthread_t th[64];
-    int started[64];
+    host_job job[HOST_MAX_THREADS];
     int32_t none = 0;                        /* (a database without files: rows of no words) */
     /* rows are disjoint per region: every thread writes its regions' rows straight into the caller's */
-    for (int k = 0; k < T; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe;
-        job[k].lo = nq * k / T; job[k].hi = nq * (k + 1) / T;
-        job[k].op = op; job[k].v = v; job[k].use_v = use_v;
-        job[k].count = count ? count : &none; job[k].agg = db->nFiles > 0 ? agg : NULL;
-    }
-    for (int k = 1; k < T; k++) {
-        started[k] = pthread_create(&th[k], NULL, map_run, &job[k]) == 0;
-        if (!started[k]) map_run(&job[k]);
-    }
-    map_run(&job[0]);
-    for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
-    int bad = 0;
-    for (int k = 0; k < T; k++) bad |= job[k].io_failed;
-    return bad ? -1 : 0;
+    jobs_split(job, T, JOB_MAP, db, m, ichr, qs, qe, nq, v, 0);
+    for (int k = 0; k < T; k++) { job[k].op = op; job[k].rowa = count ? count : &none; job[k].agg = db->nFiles > 0 ? agg : NULL; }
+    return jobs_run(job, T, NULL) ? -1 : 0;
 }
 
-#define MAP_HOST_ROW_BYTES ((int64_t)32 << 20)       /* igdc_map_sets_host: count and agg rows of one chunk of regions */
+/* the count and agg rows of a chunk of regions (igdc_map_host), each region with a record counted into its set's sums */
+typedef struct {
+    const igdc_db *db; const igdc_map *m;
+    const int32_t *ichr, *qs, *qe;
+    int op; int32_t v;
+    int32_t *count; int64_t *agg;                   /* the chunk's rows */
+    int64_t *n_hit, *pairs, *agg_sum;               /* (each may be NULL) */
+} map_sets_ctx;
+
+static int map_sets_rows(void *ctx, int64_t c0, int64_t n)
+{
+    map_sets_ctx *c = (map_sets_ctx *)ctx;
+    return igdc_map_host(c->db, c->m, c->ichr + c0, c->qs + c0, c->qe + c0, n, c->op, c->v, c->count, c->agg);
+}
+static void map_sets_fold(void *ctx, int32_t k, int64_t i)
+{
+    map_sets_ctx *c = (map_sets_ctx *)ctx;
+    const int64_t nf = c->db->nFiles;
+    const size_t r = (size_t)i * (size_t)nf, o = (size_t)k * (size_t)nf;
+    for (int64_t f = 0; f < nf; f++) {
+        if (c->count[r + f] == 0) continue;
+        if (c->n_hit) c->n_hit[o + f]++;
+        if (c->pairs) c->pairs[o + f] += c->count[r + f];
+        if (c->agg_sum) c->agg_sum[o + f] = (int64_t)((uint64_t)c->agg_sum[o + f] + (uint64_t)c->agg[r + f]);
+    }
+}
+
 int igdc_map_sets_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                        const int64_t *set_off, int32_t nsets, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
 {
-    if (!db || !m || nsets < 0 || !map_op_ok(db, op) || (nsets > 0 && (!set_off || set_off[0] != 0))) return -1;
-    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
-    if (nsets > 0 && set_off[nsets] > 0 && (!ichr || !qs || !qe)) return -1;
-    const int64_t nf = db->nFiles, nq = nsets > 0 ? set_off[nsets] : 0;
-    int64_t chunk = MAP_HOST_ROW_BYTES / (12 * (nf > 0 ? nf : 1));
-    chunk = chunk < 1 ? 1 : chunk > nq ? nq : chunk;
+    if (!db || !m || nsets < 0 || !map_op_ok(db, op) || set_off_bad(set_off, nsets, ichr, qs, qe)) return -1;
+    const int64_t nf = db->nFiles, chunk = chunk_regions(12 * (nf > 0 ? nf : 1), nsets > 0 ? set_off[nsets] : 0);
     int32_t *count = (int32_t *)malloc(sizeof(int32_t) * (size_t)(chunk * nf + 1));
     int64_t *agg = (int64_t *)malloc(sizeof(int64_t) * (size_t)(chunk * nf + 1));
     if (!count || !agg) { free(count); free(agg); return -1; }
+    map_sets_ctx c = {db, m, ichr, qs, qe, op, v, count, agg, n_hit, pairs, agg_sum};
     int64_t *outs[3] = {n_hit, pairs, agg_sum};
     for (int i = 0; i < 3; i++) if (outs[i]) memset(outs[i], 0, sizeof(int64_t) * (size_t)nsets * (size_t)nf);
-    int rc = 0;
-    int32_t k = 0;
-    for (int64_t c0 = 0; c0 < nq && rc == 0; c0 += chunk) {
-        const int64_t n = nq - c0 < chunk ? nq - c0 : chunk;
-        rc = igdc_map_host(db, m, ichr + c0, qs + c0, qe + c0, n, op, v, count, agg);
-        for (int64_t i = 0; i < n && rc == 0; i++) {
-            while (set_off[k + 1] <= c0 + i) k++;                          /* (empty sets are passed over) */
-            const size_t r = (size_t)i * (size_t)nf, o = (size_t)k * (size_t)nf;
-            for (int64_t f = 0; f < nf; f++) {
-                if (count[r + f] == 0) continue;
-                if (n_hit) n_hit[o + f]++;
-                if (pairs) pairs[o + f] += count[r + f];
-                if (agg_sum) agg_sum[o + f] = (int64_t)((uint64_t)agg_sum[o + f] + (uint64_t)agg[r + f]);
-            }
-        }
-    }
+    const int rc = set_chunks(set_off, nsets, chunk, map_sets_rows, map_sets_fold, &c);
     free(count); free(agg);
     return rc;
 }
@@ -1761,50 +1667,42 @@ int igdc_map_summary(const int64_t *n_hit, const int64_t *pairs, const int64_t *
 }
 
 /* ---- permutation null of the nearest-record distances (what igd_hip_permute_nearest computes) ----------------------------
- * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator; a row is igdc_nearest_sets_host's
- * walk over its regions (one_region_nearest) summed into the three statistics.  Threads run over the rows (thread k takes
- * rows k, k + T, ..), each with its own permuted arrays, distance row and tile buffer; the rows are disjoint.  Everything is
- * computed into a buffer and copied out at the end: -1 (a refused argument, a tile that could not be read) writes nothing. */
+ * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator (perm_rows); a row is
+ * igdc_nearest_sets_host's walk over its regions (one_region_nearest) summed into the three statistics.  Each thread has its
+ * own permuted arrays, distance row and tile buffer; the rows are disjoint.  Everything is computed into a buffer and copied out
+ * at the end: -1 (a refused argument, a tile that could not be read) writes nothing. */
 typedef struct {
-    const igdc_db *db; const igdc_map *m;
-    const int32_t *ichr, *qs, *qe, *ctg_len;
-    int64_t nq, nrows;
-    int mode; uint64_t seed;
+    perm_stripe s;
     int32_t window, v; int use_v;
     int64_t *res;           /* three matrices of nrows x (nFiles + 1) */
-    int32_t *ps, *pe, *row; /* the permuted set, one distance row */
-    int k, T, io_failed;
-    const igd_hip_workspace *ws;
+    int32_t *row;           /* one distance row */
+    tilebuf tb;
 } pnear_job;
 
+static int pnear_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
+{
+    pnear_job *P = (pnear_job *)job;
+    const int64_t nF = P->s.db->nFiles, nC = nF + 1;
+    int64_t *nw = P->res + r * nC, *no = nw + P->s.nrows * nC, *sd = no + P->s.nrows * nC;
+    for (int64_t i = 0; i < P->s.nq && !P->tb.failed; i++) {
+        const int32_t dm = one_region_nearest(P->s.db, P->s.m, &P->tb, P->s.ichr[i], s[i], e[i], P->window, P->v, P->use_v, P->row);
+        if (dm < 0) continue;                                          /* (no record within the window: the row is all -1) */
+        for (int64_t f = 0; f < nC; f++) {
+            const int32_t d = f < nF ? P->row[f] : dm;
+            if (d < 0) continue;
+            nw[f]++;
+            no[f] += d == 0;
+            sd[f] += d;
+        }
+    }
+    return P->tb.failed;
+}
 static void *pnear_run(void *arg)
 {
     pnear_job *P = (pnear_job *)arg;
-    const int64_t nF = P->db->nFiles, nC = nF + 1;
-    tilebuf tb;
-    memset(&tb, 0, sizeof tb);
-    tb.ichr = -1;
-    for (int64_t r = P->k; r < P->nrows && !tb.failed; r += P->T) {
-        const int32_t *s = P->qs, *e = P->qe;
-        if (r > 0) {
-            perm_regions_fill(P->ichr, P->qs, P->qe, P->nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, r - 1, 1, P->ps, P->pe, P->ws);
-            s = P->ps; e = P->pe;
-        }
-        int64_t *nw = P->res + r * nC, *no = nw + P->nrows * nC, *sd = no + P->nrows * nC;
-        for (int64_t i = 0; i < P->nq && !tb.failed; i++) {
-            const int32_t dm = one_region_nearest(P->db, P->m, &tb, P->ichr[i], s[i], e[i], P->window, P->v, P->use_v, P->row);
-            if (dm < 0) continue;                                          /* (no record within the window: the row is all -1) */
-            for (int64_t f = 0; f < nC; f++) {
-                const int32_t d = f < nF ? P->row[f] : dm;
-                if (d < 0) continue;
-                nw[f]++;
-                no[f] += d == 0;
-                sd[f] += d;
-            }
-        }
-    }
-    P->io_failed = tb.failed;
-    free(tb.buf);
+    tb_open(&P->tb);
+    perm_rows(&P->s, pnear_row, P);
+    tb_close(&P->tb);
     return NULL;
 }
 
@@ -1819,37 +1717,23 @@ int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int
                                  const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
                                  int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws)
 {
-    if (!db || !m || nq < 0 || !igd_hip_nearest_window_valid(window) || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        !perm_mode_ok(mode, ws) || nperm < 1 || nperm > IGD_HIP_PERM_MAX ||
-        nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 ||
-        perm_ws_refused(db, ws, ctg_len, ichr, qs, qe, nq))
-        return -1;
+    if (!igd_hip_nearest_window_valid(window) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws)) return -1;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     int T = host_threads(nq * R > 0 ? nq * R : 1);
     if (T > R) T = (int)R;
     int64_t *res = (int64_t *)calloc((size_t)(3 * R * nC), sizeof(int64_t));
     int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (2 * (size_t)nq + (size_t)nF) + 1));
     int rc = res && w ? 0 : -1;
-    pnear_job job[64];
-    pthread_t th[64];
-    int started[64];
+    pnear_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe; job[k].ctg_len = ctg_len;
-        job[k].nq = nq; job[k].nrows = R; job[k].mode = mode; job[k].seed = seed;
+        int32_t *mine = w + (size_t)k * (2 * (size_t)nq + (size_t)nF);
+        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 0, R, mine, k, T);
         job[k].window = window; job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
-        job[k].res = res;
-        job[k].ps = w + (size_t)k * (2 * (size_t)nq + (size_t)nF); job[k].pe = job[k].ps + nq; job[k].row = job[k].pe + nq;
-        job[k].k = k; job[k].T = T; job[k].ws = ws;
+        job[k].res = res; job[k].row = mine + 2 * nq;
     }
     if (rc == 0 && nq > 0 && nF > 0) {
-        for (int k = 1; k < T; k++) {
-            started[k] = pthread_create(&th[k], NULL, pnear_run, &job[k]) == 0;
-            if (!started[k]) pnear_run(&job[k]);
-        }
-        pnear_run(&job[0]);
-        for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
-        for (int k = 0; k < T; k++) if (job[k].io_failed) rc = -1;
+        run_threads(pnear_run, job, sizeof job[0], T);
+        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
     }
     if (rc == 0) {
         int64_t *const out[3] = {n_within, n_overlap, sum_dist};
@@ -2000,10 +1884,9 @@ static void *merge_run(void *arg)
 int igdc_merge_host(const igdc_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
                     int64_t gap, int32_t *m_ichr, int32_t *m_qs, int32_t *m_qe, int64_t *m_off, int32_t *m_count, int64_t *n_dropped)
 {
-    if (!db || nsets < 0 || !igd_hip_merge_gap_valid(gap) || (nsets > 0 && (!set_off || set_off[0] != 0 || !m_off || !n_dropped))) return -1;
-    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
+    if (!db || !igd_hip_merge_gap_valid(gap) || (nsets > 0 && (!m_off || !n_dropped)) || set_off_bad(set_off, nsets, ichr, qs, qe)) return -1;
     const int64_t n = nsets > 0 ? set_off[nsets] : 0;
-    if (n > 0 && (!ichr || !qs || !qe || !m_ichr || !m_qs || !m_qe)) return -1;
+    if (n > 0 && (!m_ichr || !m_qs || !m_qe)) return -1;
     if (nsets == 0) return 0;
     merge_reg *regs = (merge_reg *)malloc((size_t)(n > 0 ? n : 1) * sizeof *regs);
     int32_t *runs = (int32_t *)malloc((size_t)(n > 0 ? n : 1) * 4 * sizeof *runs);
@@ -2011,9 +1894,7 @@ int igdc_merge_host(const igdc_db *db, const int32_t *ichr, const int32_t *qs, c
     if (!regs || !runs || !nrun) { free(regs); free(runs); free(nrun); return -1; }
     int T = host_threads(n);
     if (T > nsets) T = nsets;
-    merge_job job[64];
-    pthread_t th[64];
-    int started[64];
+    merge_job job[HOST_MAX_THREADS];
     for (int t = 0; t < T; t++) {
         merge_job *J = &job[t];
         J->db = db; J->ichr = ichr; J->qs = qs; J->qe = qe; J->set_off = set_off; J->gap = gap;
@@ -2021,12 +1902,7 @@ int igdc_merge_host(const igdc_db *db, const int32_t *ichr, const int32_t *qs, c
         J->regs = regs; J->rc = runs; J->rs = runs + n; J->re = runs + 2 * n; J->rn = runs + 3 * n;
         J->nrun = nrun; J->n_dropped = n_dropped;
     }
-    for (int t = 1; t < T; t++) {
-        started[t] = pthread_create(&th[t], NULL, merge_run, &job[t]) == 0;
-        if (!started[t]) merge_run(&job[t]);
-    }
-    merge_run(&job[0]);
-    for (int t = 1; t < T; t++) if (started[t]) pthread_join(th[t], NULL);
+    run_threads(merge_run, job, sizeof job[0], T);
     int64_t at = 0;
     for (int32_t k = 0; k < nsets; k++) {
         const int64_t a = set_off[k];
@@ -2072,11 +1948,9 @@ int igdc_jaccard_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
                       const int64_t *set_off, int32_t nsets, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *file_bp,
                       int64_t *n_merged, int64_t *n_dropped)
 {
-    if (!db || !m || nsets < 0 || !file_bp || (nsets > 0 && (!set_off || set_off[0] != 0 || !inter || !set_bp || !n_merged || !n_dropped)) ||
-        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)) return -1;
-    for (int32_t k = 0; k < nsets; k++) if (set_off[k + 1] < set_off[k]) return -1;
+    if (!db || !m || !file_bp || (nsets > 0 && (!inter || !set_bp || !n_merged || !n_dropped)) ||
+        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || set_off_bad(set_off, nsets, ichr, qs, qe)) return -1;
     const int64_t n = nsets > 0 ? set_off[nsets] : 0, nF = db->nFiles;
-    if (n > 0 && (!ichr || !qs || !qe)) return -1;
     int rc = igdc_dataset_bp_host(db, m, v, rule, file_bp);
     if (rc != 0 || nsets == 0) return rc;
     int32_t *mr = (int32_t *)malloc((size_t)(n > 0 ? n : 1) * 3 * sizeof *mr);
@@ -2118,40 +1992,34 @@ int igdc_jaccard_summary(const int64_t *inter, const int64_t *set_bp, const int6
 }
 
 /* ---- permutation null of the base-pair overlap (what igd_hip_permute_bp computes; include/igd_hip.h has the definitions) --
- * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator; a row is igdc_jaccard_host's
- * treatment of one set: igdc_merge_host at gap 0, then igdc_coverage_host over the runs.  Threads run over the rows (thread k
- * takes rows k, k + T, ..), each with its own permuted arrays and run arrays; the rows are disjoint.  Everything is computed
- * into a buffer and copied out at the end: -1 (a refused argument, a tile that could not be read) writes nothing. */
+ * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator (perm_rows); a row is
+ * igdc_jaccard_host's treatment of one set: igdc_merge_host at gap 0, then igdc_coverage_host over the runs.  Each thread has
+ * its own permuted arrays and run arrays; the rows are disjoint.  Everything is computed into a buffer and copied out at the
+ * end: -1 (a refused argument, a tile that could not be read) writes nothing. */
 typedef struct {
-    const igdc_db *db; const igdc_map *m;
-    const int32_t *ichr, *qs, *qe, *ctg_len;
-    int64_t nq, nrows;
-    int mode; uint64_t seed;
+    perm_stripe s;
     int32_t v; int rule;
     int64_t *inter, *set_bp, *n_merged, *dropped;   /* nrows x (nFiles + 1), nrows, nrows, nrows */
-    int32_t *ps, *pe, *mr;                          /* the permuted set; the runs (3 x nq) */
-    int k, T, failed;
-    const igd_hip_workspace *ws;
+    int32_t *mr;                                    /* the runs (3 x nq) */
 } pbp_job;
 
+static int pbp_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
+{
+    pbp_job *P = (pbp_job *)job;
+    const igdc_db *db = P->s.db;
+    const int64_t nF = db->nFiles, nq = P->s.nq, off[2] = {0, nq};
+    int64_t moff[2], bp = 0;
+    if (igdc_merge_host(db, P->s.ichr, s, e, off, 1, 0, P->mr, P->mr + nq, P->mr + 2 * nq, moff, NULL, &P->dropped[r]) != 0) return 1;
+    for (int64_t i = 0; i < moff[1]; i++) bp += (int64_t)P->mr[2 * nq + i] - (int64_t)P->mr[nq + i];
+    P->set_bp[r] = bp;
+    P->n_merged[r] = moff[1];
+    int64_t *row = P->inter + r * (nF + 1);
+    return igdc_coverage_host(db, P->s.m, P->mr, P->mr + nq, P->mr + 2 * nq, moff[1], P->v, P->rule, row, row + nF) != 0;
+}
 static void *pbp_run(void *arg)
 {
     pbp_job *P = (pbp_job *)arg;
-    const int64_t nF = P->db->nFiles, nq = P->nq, off[2] = {0, nq};
-    for (int64_t r = P->k; r < P->nrows && !P->failed; r += P->T) {
-        const int32_t *s = P->qs, *e = P->qe;
-        if (r > 0) {
-            perm_regions_fill(P->ichr, P->qs, P->qe, nq, P->ctg_len, P->db->nCtg, P->mode, P->seed, r - 1, 1, P->ps, P->pe, P->ws);
-            s = P->ps; e = P->pe;
-        }
-        int64_t moff[2], bp = 0;
-        if (igdc_merge_host(P->db, P->ichr, s, e, off, 1, 0, P->mr, P->mr + nq, P->mr + 2 * nq, moff, NULL, &P->dropped[r]) != 0) { P->failed = 1; break; }
-        for (int64_t i = 0; i < moff[1]; i++) bp += (int64_t)P->mr[2 * nq + i] - (int64_t)P->mr[nq + i];
-        P->set_bp[r] = bp;
-        P->n_merged[r] = moff[1];
-        int64_t *row = P->inter + r * (nF + 1);
-        if (igdc_coverage_host(P->db, P->m, P->mr, P->mr + nq, P->mr + 2 * nq, moff[1], P->v, P->rule, row, row + nF) != 0) P->failed = 1;
-    }
+    perm_rows(&P->s, pbp_row, P);
     return NULL;
 }
 
@@ -2166,36 +2034,23 @@ int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t 
                             const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
                             int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
 {
-    if (!db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || !perm_mode_ok(mode, ws) ||
-        nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 ||
-        perm_ws_refused(db, ws, ctg_len, ichr, qs, qe, nq))
-        return -1;
+    if ((rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws)) return -1;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     int T = host_threads(nq * R > 0 ? nq * R : 1);
     if (T > R) T = (int)R;
     int64_t *res = (int64_t *)calloc((size_t)(R * nC + 3 * R), sizeof(int64_t));
     int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 5 * (size_t)nq + 1));
     int rc = res && w ? 0 : -1;
-    pbp_job job[64];
-    pthread_t th[64];
-    int started[64];
+    pbp_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
-        memset(&job[k], 0, sizeof job[k]);
-        job[k].db = db; job[k].m = m; job[k].ichr = ichr; job[k].qs = qs; job[k].qe = qe; job[k].ctg_len = ctg_len;
-        job[k].nq = nq; job[k].nrows = R; job[k].mode = mode; job[k].seed = seed; job[k].v = v; job[k].rule = rule;
+        int32_t *mine = w + (size_t)k * 5 * (size_t)nq;
+        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 0, R, mine, k, T);
+        job[k].v = v; job[k].rule = rule; job[k].mr = mine + 2 * nq;
         job[k].inter = res; job[k].set_bp = res + R * nC; job[k].n_merged = job[k].set_bp + R; job[k].dropped = job[k].n_merged + R;
-        job[k].ps = w + (size_t)k * 5 * (size_t)nq; job[k].pe = job[k].ps + nq; job[k].mr = job[k].pe + nq;
-        job[k].k = k; job[k].T = T; job[k].ws = ws;
     }
     if (rc == 0 && nq > 0) {
-        for (int k = 1; k < T; k++) {
-            started[k] = pthread_create(&th[k], NULL, pbp_run, &job[k]) == 0;
-            if (!started[k]) pbp_run(&job[k]);
-        }
-        pbp_run(&job[0]);
-        for (int k = 1; k < T; k++) if (started[k]) pthread_join(th[k], NULL);
-        for (int k = 0; k < T; k++) if (job[k].failed) rc = -1;
+        run_threads(pbp_run, job, sizeof job[0], T);
+        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
     }
     if (rc == 0) {
         if (inter) memcpy(inter, res, sizeof(int64_t) * (size_t)(R * nC));
