@@ -4,7 +4,8 @@
 //   run_region_chunks  host arrays in chunks of regions, rows back per chunk: igd_hip_nearest(_signed), igd_hip_flank,
 //                      igd_hip_map, igd_hip_membership, igd_hip_cooccur
 //   run_set_chunks     chunks of sets, rows added on the host: igd_hip_search_sets / igd_hip_support_sets / igd_hip_coverage_sets
-// (The group driver of the resident set statistics, run_set_groups, is in host_nearest.hpp.)
+// (The group driver of the resident set statistics, run_set_groups, is in host_nearest.hpp; the chunk driver of the three
+// permutation nulls, run_perm_chunks, in host_permute.hpp.)
 // ------------------------------------------------------------------------------------------
 #include <type_traits>
 

@@ -1,15 +1,17 @@
 // engine/host_permute.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
 // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: the permutation null of region-set support
 // ------------------------------------------------------------------------------------------
-// The set's regions and the contig lengths go to the device once (db->d_pmReg).  The set as given is counted first: one row
-// through igd_sets_support, copied on the device into `observed` (db->d_pmStat holds observed and the six statistics, nFiles + 1
-// words each; word nFiles is the any-dataset column, the kernel's nhit total).  Then the permutations in CHUNKS of pc, where
-// pc * nq <= igd_hip_max_batch() (the staging arrays of igd_hip_search) and pc * nFiles * 8 <= perm_row_bytes() (the rows of
-// igd_hip_search_sets): igd_permute_regions fills the staging arrays, the slice table -- one row per permutation, each row cut
-// as igd_hip_support_sets cuts a set; built and uploaded once, a shorter last chunk uses a prefix of it -- drives ONE launch of
-// igd_sets_support, and igd_perm_stats folds the chunk's rows and totals into the statistics.  Everything is enqueued on the
-// engine's stream without a wait in between; 7 x (nFiles + 1) words come back at the end.
-// Everything is computed into a buffer of this file and copied to the caller's at the end: on an error nothing is written.
+// What the three nulls (here, host_permute_nearest.hpp, host_permute_bp.hpp) share is written once, here: the refusals
+// (perm_args_refused), the upload of the call's regions, contig lengths and workspace table (perm_place_upload), the generator's
+// launch (permute_launch) and the chunk driver (run_perm_chunks).  A statistic adds the bytes of device rows one permutation
+// costs, the workspaces it grows, and what it counts from a chunk of rows.
+// The support: the set as given is counted first, one row through igd_sets_support, copied on the device into `observed`
+// (db->d_pmStat holds observed and the six statistics, nFiles + 1 words each; word nFiles is the any-dataset column, the
+// kernel's nhit total).  Then the permutations in the driver's chunks, pc * nFiles * 8 <= perm_row_bytes() (the rows of
+// igd_hip_search_sets): the slice table -- one row per permutation, each row cut as igd_hip_support_sets cuts a set; built and
+// uploaded once, a shorter last chunk uses a prefix of it -- drives ONE launch of igd_sets_support, and igd_perm_stats folds the
+// chunk's rows and totals into the statistics.  7 x (nFiles + 1) words come back behind the last chunk, into a buffer of this
+// file that is copied to the caller's behind the driver's wait: on an error nothing is written.
 
 // The TEST-ONLY variable IGD_HIP_PERM_ROW_BYTES (read once per process, as IGD_HIP_RESTRICT_ROW_BYTES) lowers the row budget of
 // a chunk so that small fixtures cross the seam between two chunks.
@@ -21,14 +23,6 @@ static int64_t perm_row_bytes(void)
 
 // workgroups igd_permute_regions is launched with for n outputs: a lane takes a second one only when n exceeds the grid's lanes
 extern "C" int32_t igd_hip_permute_grid(int64_t n) { return items_grid(n, IGD_SETS_WG); }
-
-// THE PLACEMENT OF ONE CALL, written once for the four launch sites (here twice, host_permute_nearest.hpp, host_permute_bp.hpp):
-// the mode and, under IGD_HIP_PERM_WORKSPACE, the table on the device (db->d_pmWs).
-struct PermPlace {
-    int mode;
-    const int64_t *wOff;
-    const int32_t *wStart, *wLen, *wPre;
-};
 
 // a mode the call can run: the two free placements without a workspace, IGD_HIP_PERM_WORKSPACE with one
 static bool perm_mode_ok(int mode, const igd_hip_workspace *ws)
@@ -46,47 +40,142 @@ static bool perm_ws_refused(const char *who, const igd_hip_workspace *ws, const 
         snprintf(g_err, sizeof g_err, "%s: the workspace table is not valid for the %d contigs of the call", who, (int)nctg);
         return true;
     }
-    for (int64_t i = 0; mustFit && i < nq; i++) {
-        int32_t s = qs[i], e = qe[i];
-        if (igd_hip_perm_place_ws(0, ichr[i], i, ctg_len, nctg, ws->w_off, ws->w_start, ws->w_len, ws->w_pre, &s, &e)) {
-            snprintf(g_err, sizeof g_err, "%s: region %lld = (%d, %d, %d) fits in no segment of the workspace on its contig", who, (long long)i,
-                     (int)ichr[i], (int)qs[i], (int)qe[i]);
-            return true;
-        }
-    }
-    return false;
+    const int64_t i = mustFit ? igd_hip_perm_first_unplaceable(ws, ctg_len, ichr, qs, qe, nq) : -1;
+    if (i >= 0)
+        snprintf(g_err, sizeof g_err, "%s: region %lld = (%d, %d, %d) fits in no segment of the workspace on its contig", who, (long long)i,
+                 (int)ichr[i], (int)qs[i], (int)qe[i]);
+    return i >= 0;
 }
 
-// the table of a checked workspace into db->d_pmWs, on the engine's stream; without one only the mode is kept
-static int perm_place_upload(igd_hip_db *db, int mode, const igd_hip_workspace *ws, PermPlace *pl)
+// THE REFUSALS OF THE THREE DRIVERS, in this order: a missing argument (extraBad: what else the driver calls one -- a missing
+// output, no such rule), a mode the call cannot run, the number of permutations, more regions than a batch, the first region
+// off its contig, a workspace table that is not valid for the database's contigs, the first region in no segment.  true, g_err
+// set, prefixed with `who`.  Each driver has its own check in front (min_overlap, the window); the support's bound on the sum of
+// squares runs BEHIND this function, so a call that also has one of the last three faults is now told of that fault instead.
+static bool perm_args_refused(const char *who, const igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                              const int32_t *ctg_len, int mode, int64_t nperm, const igd_hip_workspace *ws, bool extraBad)
 {
-    *pl = PermPlace{mode, nullptr, nullptr, nullptr, nullptr};
-    if (!ws) return IGD_HIP_OK;
-    const int64_t nc = ws->nctg, ns = ws->nseg;
-    const int rc = dev_grow(db, &db->d_pmWs, &db->pmWsCap, 2 * (nc + 1) + 3 * ns + nc + 1);
-    if (rc != IGD_HIP_OK) return rc;
-    int64_t *dOff = (int64_t *)db->d_pmWs;
-    int32_t *dStart = db->d_pmWs + 2 * (nc + 1), *dLen = dStart + ns, *dPre = dLen + ns;
-    HIPCHK(hipMemcpyAsync(dOff, ws->w_off, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, db->stream));
-    if (ns > 0) {
-        HIPCHK(hipMemcpyAsync(dStart, ws->w_start, (size_t)ns * 4, hipMemcpyHostToDevice, db->stream));
-        HIPCHK(hipMemcpyAsync(dLen, ws->w_len, (size_t)ns * 4, hipMemcpyHostToDevice, db->stream));
+    if (!db || nq < 0 || extraBad || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) || !perm_mode_ok(mode, ws)) {
+        snprintf(g_err, sizeof g_err, "%s: bad argument", who);
+        return true;
     }
-    if (ns + nc > 0) HIPCHK(hipMemcpyAsync(dPre, ws->w_pre, (size_t)(ns + nc) * 4, hipMemcpyHostToDevice, db->stream));
-    *pl = PermPlace{mode, dOff, dStart, dLen, dPre};
+    if (nperm < 1 || nperm > IGD_HIP_PERM_MAX) {
+        snprintf(g_err, sizeof g_err, "%s: %lld permutations, not 1 .. %lld", who, (long long)nperm, (long long)IGD_HIP_PERM_MAX);
+        return true;
+    }
+    if (nq > max_batch()) {
+        snprintf(g_err, sizeof g_err, "%s: %lld regions, more than %lld", who, (long long)nq, (long long)max_batch());
+        return true;
+    }
+    const int64_t i = igd_hip_perm_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg);
+    if (i >= 0) {
+        snprintf(g_err, sizeof g_err, "%s: region %lld = (%d, %d, %d) does not lie on its contig of length %lld", who, (long long)i,
+                 (int)ichr[i], (int)qs[i], (int)qe[i], (long long)ctg_len[ichr[i]]);
+        return true;
+    }
+    return perm_ws_refused(who, ws, ctg_len, db->nCtg, ichr, qs, qe, nq, true);
+}
+
+// THE PLACEMENT OF ONE CALL, written once for the two launch sites (run_perm_chunks, igd_hip_permute_regions_ws): the call's nq
+// regions and nctg contig lengths on the device (db->d_pmReg), the mode and, under IGD_HIP_PERM_WORKSPACE, the table (db->d_pmWs).
+struct PermPlace {
+    const int32_t *rC, *rS, *rE, *rL;
+    int64_t nq;
+    int32_t nctg;
+    int mode;
+    const int64_t *wOff;
+    const int32_t *wStart, *wLen, *wPre;
+};
+
+// both buffers grown, then on the engine's stream the table of a checked workspace (without one only the mode is kept) and the
+// regions with the contig lengths
+static int perm_place_upload(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                             int32_t nctg, int mode, const igd_hip_workspace *ws, PermPlace *pl)
+{
+    const int64_t nc = ws ? ws->nctg : 0, ns = ws ? ws->nseg : 0;
+    hipStream_t st = db->stream;
+    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg);
+    if (rc == IGD_HIP_OK && ws) rc = dev_grow(db, &db->d_pmWs, &db->pmWsCap, 2 * (nc + 1) + 3 * ns + nc + 1);
+    if (rc != IGD_HIP_OK) return rc;
+    int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
+    *pl = PermPlace{rC, rS, rE, rL, nq, nctg, mode, nullptr, nullptr, nullptr, nullptr};
+    if (ws) {
+        int64_t *dOff = (int64_t *)db->d_pmWs;
+        int32_t *dStart = db->d_pmWs + 2 * (nc + 1), *dLen = dStart + ns, *dPre = dLen + ns;
+        HIPCHK(hipMemcpyAsync(dOff, ws->w_off, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, st));
+        if (ns > 0) {
+            HIPCHK(hipMemcpyAsync(dStart, ws->w_start, (size_t)ns * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(dLen, ws->w_len, (size_t)ns * 4, hipMemcpyHostToDevice, st));
+        }
+        if (ns + nc > 0) HIPCHK(hipMemcpyAsync(dPre, ws->w_pre, (size_t)(ns + nc) * 4, hipMemcpyHostToDevice, st));
+        pl->wOff = dOff; pl->wStart = dStart; pl->wLen = dLen; pl->wPre = dPre;
+    }
+    HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    if (nctg > 0) HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)nctg * 4, hipMemcpyHostToDevice, st));
     return IGD_HIP_OK;
 }
 
 // `total` outputs (permutations from p0 on, nq regions each) by the kernel of the call's placement
-static int permute_launch(igd_hip_db *db, const PermPlace &pl, const int32_t *rC, const int32_t *rS, const int32_t *rE, int64_t nq,
-                          const int32_t *rL, int32_t nctg, u64 seed, u64 p0, int64_t total, int32_t *oC, int32_t *oS, int32_t *oE)
+static int permute_launch(igd_hip_db *db, const PermPlace &pl, u64 seed, u64 p0, int64_t total, int32_t *oC, int32_t *oS, int32_t *oE)
 {
     const unsigned grid = (unsigned)igd_hip_permute_grid(total);
     if (pl.mode == IGD_HIP_PERM_WORKSPACE)
-        igd_permute_workspace<<<grid, IGD_SETS_WG, 0, db->stream>>>(rC, rS, rE, (unsigned)nq, rL, nctg, pl.wOff, pl.wStart, pl.wLen, pl.wPre, seed,
-                                                                  p0, (unsigned)total, oC, oS, oE);
+        igd_permute_workspace<<<grid, IGD_SETS_WG, 0, db->stream>>>(pl.rC, pl.rS, pl.rE, (unsigned)pl.nq, pl.rL, pl.nctg, pl.wOff, pl.wStart, pl.wLen,
+                                                                  pl.wPre, seed, p0, (unsigned)total, oC, oS, oE);
     else
-        igd_permute_regions<<<grid, IGD_SETS_WG, 0, db->stream>>>(rC, rS, rE, (unsigned)nq, rL, nctg, pl.mode, seed, p0, (unsigned)total, oC, oS, oE);
+        igd_permute_regions<<<grid, IGD_SETS_WG, 0, db->stream>>>(pl.rC, pl.rS, pl.rE, (unsigned)pl.nq, pl.rL, pl.nctg, pl.mode, seed, p0,
+                                                                (unsigned)total, oC, oS, oE);
+    HIPCHK(hipGetLastError());
+    return IGD_HIP_OK;
+}
+
+// the host slice table of a chunk of pc rows of nq staged regions: row r cut as igd_hip_support_sets cuts a set (the support, the
+// fused nearest kernel); a shorter chunk uses a prefix of it
+static std::vector<SetSlice> perm_row_slices(int64_t pc, int64_t nq, int64_t sliceLen)
+{
+    std::vector<SetSlice> slices;
+    slices.reserve((size_t)(pc * ((nq + sliceLen - 1) / sliceLen)));
+    for (int64_t r = 0; r < pc; r++) push_slices(slices, (int32_t)r, r * nq, (r + 1) * nq, sliceLen, 0);
+    return slices;
+}
+
+// The chunk driver of the three nulls (the arguments are checked, nq > 0).  A chunk holds pc permutations: pc * nq <=
+// igd_hip_max_batch() (the staging arrays of igd_hip_search) and, unless rowBytes is 0, pc * rowBytes <= perm_row_bytes(); at
+// least one, at most nperm.  prepare(pc, sliceLen, perRow) grows the statistic's own workspaces for such a chunk, cut into
+// slices of sliceLen = sets_slice_len(pc * nq) regions, perRow of them per row; it enqueues nothing.  Then the staging arrays and
+// the placement's two buffers are grown -- every dev_grow of the call is over before its first upload -- and the regions, the
+// contig lengths and the table go up once.  count(c, s, e, rows, r0) enqueues what the statistic does with `rows` rows of nq
+// resident regions each, rows [r0, r0 + rows) of the null: first the set as given (r0 == 0, one row: the regions themselves;
+// this call also uploads what every chunk reads, and adds what the statistic does once behind row 0), then per chunk the
+// generator's output in the staging arrays (r0 = 1 + p0); the call with r0 + rows == nperm + 1 is the last.  Everything is on the
+// engine's stream without a wait in between, unless count waits itself; ONE wait at the end, behind which the callers write
+// their results.
+template <typename Prepare, typename Count>
+static int run_perm_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                           int mode, uint64_t seed, int64_t nperm, const igd_hip_workspace *ws, int64_t rowBytes, Prepare &&prepare,
+                           Count &&count)
+{
+    HIPCHK(hipSetDevice(db->device));
+    int64_t pc = max_batch() / nq;
+    const int64_t byRows = rowBytes > 0 ? perm_row_bytes() / rowBytes : pc;
+    if (byRows < pc) pc = byRows < 1 ? 1 : byRows;
+    if (nperm < pc) pc = nperm;
+    const int64_t sliceLen = sets_slice_len(pc * nq);
+    const int64_t perRow = (nq + sliceLen - 1) / sliceLen;                // slices of one permutation
+    int rc = prepare(pc, sliceLen, perRow);
+    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
+    PermPlace pl;
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, db->nCtg, mode, ws, &pl);
+    if (rc == IGD_HIP_OK) rc = count(pl.rC, pl.rS, pl.rE, (int64_t)1, (int64_t)0);      // the set as given
+    for (int64_t p0 = 0; rc == IGD_HIP_OK && p0 < nperm; p0 += pc) {
+        const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
+        rc = permute_launch(db, pl, (u64)seed, (u64)p0, n * nq, db->d_qc, db->d_qs, db->d_qe);
+        if (rc == IGD_HIP_OK) rc = count(db->d_qc, db->d_qs, db->d_qe, n, 1 + p0);
+    }
+    if (rc != IGD_HIP_OK) return rc;
+    HIPCHK(hipStreamSynchronize(db->stream));
     HIPCHK(hipGetLastError());
     return IGD_HIP_OK;
 }
@@ -142,35 +231,14 @@ extern "C" int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, c
     }
     const bool ov = igd_hip_min_overlap_active(min_overlap);
     const MinOv mo = min_ov_of(min_overlap);
-    if (!db || nq < 0 || !observed || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || !perm_mode_ok(mode, ws)) {
-        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: bad argument");
+    if (perm_args_refused("igd_hip_permute_support", db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws,
+                          !observed || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)))
         return IGD_HIP_ERR_ARG;
-    }
-    if (nperm < 1 || nperm > IGD_HIP_PERM_MAX) {
-        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: %lld permutations, not 1 .. %lld", (long long)nperm, (long long)IGD_HIP_PERM_MAX);
-        return IGD_HIP_ERR_ARG;
-    }
-    if (nq > max_batch()) {
-        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: %lld regions, more than %lld", (long long)nq, (long long)max_batch());
-        return IGD_HIP_ERR_ARG;
-    }
     if ((unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63) {
         snprintf(g_err, sizeof g_err, "igd_hip_permute_support: %lld permutations of %lld regions: the sum of squares may pass 2^63",
                  (long long)nperm, (long long)nq);
         return IGD_HIP_ERR_ARG;
     }
-    for (int64_t i = 0; i < nq; i++) {
-        const int32_t c = ichr[i];
-        if (c < 0 || c >= db->nCtg) continue;
-        const int64_t L = ctg_len[c];
-        if (L < 1 || qs[i] < 0 || qe[i] < qs[i] || (int64_t)qe[i] > L) {
-            snprintf(g_err, sizeof g_err, "igd_hip_permute_support: region %lld = (%d, %d, %d) does not lie on its contig of length %lld",
-                     (long long)i, (int)c, (int)qs[i], (int)qe[i], (long long)L);
-            return IGD_HIP_ERR_ARG;
-        }
-    }
-    if (perm_ws_refused("igd_hip_permute_support", ws, ctg_len, db->nCtg, ichr, qs, qe, nq, true)) return IGD_HIP_ERR_ARG;
     const int64_t nF = db->nFiles, nC = nF + 1;
     int64_t *const out[7] = {observed, sum, sumsq, n_ge, n_le, pmin, pmax};
     std::vector<int64_t> res((size_t)(7 * nC));
@@ -181,58 +249,40 @@ extern "C" int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, c
     }
 
     const SliceImage im = slice_image(db, rule, v);
-    int64_t pc = max_batch() / nq;
-    const int64_t byRows = perm_row_bytes() / (nF * 8);
-    if (byRows < pc) pc = byRows < 1 ? 1 : byRows;
-    if (nperm < pc) pc = nperm;
-    const int64_t sliceLen = sets_slice_len(pc * nq);
-    const int64_t perRow = (nq + sliceLen - 1) / sliceLen;                // slices of one permutation
     const int64_t maxGrid = support_max_grid(db);
-    std::vector<SetSlice> slices;
-    slices.reserve((size_t)(pc * perRow));
-    for (int64_t r = 0; r < pc; r++) push_slices(slices, (int32_t)r, r * nq, (r + 1) * nq, sliceLen, 0);
-
-    HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + db->nCtg);
-    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_pmStat, &db->pmStatCap, 7 * nC);
-    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
-    if (rc == IGD_HIP_OK) rc = sets_ws(db, pc * nF, pc, pc * perRow);
-    if (rc == IGD_HIP_OK) rc = ensure_support_bits(db, maxGrid);
-    PermPlace pl;
-    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, mode, ws, &pl);
-    if (rc != IGD_HIP_OK) return rc;
-    int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
-    long long *dObs = db->d_pmStat, *dSt = dObs + nC;
-    HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)db->nCtg * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(db->d_setSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-
-    // `rows` zeroed rows counted from the query arrays (c, s, e): rows * perRow slices, a prefix of the table
-    auto count = [&](const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows) -> int {
+    std::vector<SetSlice> slices;
+    int64_t perRow = 0;
+    auto prepare = [&](int64_t pc, int64_t sliceLen, int64_t perRow_) -> int {
+        perRow = perRow_;
+        slices = perm_row_slices(pc, nq, sliceLen);
+        int rc = dev_grow(db, &db->d_pmStat, &db->pmStatCap, 7 * nC);
+        if (rc == IGD_HIP_OK) rc = sets_ws(db, pc * nF, pc, pc * perRow);
+        if (rc == IGD_HIP_OK) rc = ensure_support_bits(db, maxGrid);
+        return rc;
+    };
+    // `rows` zeroed rows counted from the query arrays (c, s, e): rows * perRow slices, a prefix of the table.  Row 0 becomes
+    // `observed` and opens the statistics; a chunk is folded into them, and the last one sends them home.
+    auto count = [&](const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows, int64_t r0) -> int {
         const int ns = (int)(rows * perRow);
         const int grid = ns < maxGrid ? ns : (int)maxGrid;
+        long long *dObs = db->d_pmStat, *dSt = dObs + nC;
+        if (r0 == 0) HIPCHK(hipMemcpyAsync(db->d_setSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(db->d_setRows, 0, (size_t)(rows * nF) * 8, st));
         HIPCHK(hipMemsetAsync(db->d_setTot, 0, (size_t)rows * 8, st));
-        return support_launch(db, im, c, s, e, ns, grid, v, ov, mo);
+        int rc = support_launch(db, im, c, s, e, ns, grid, v, ov, mo);
+        if (rc != IGD_HIP_OK) return rc;
+        if (r0 == 0) {
+            HIPCHK(hipMemcpyAsync(dObs, db->d_setRows, (size_t)nF * 8, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(dObs + nF, db->d_setTot, 8, hipMemcpyDeviceToDevice, st));
+            return perm_stats_init(db, dSt, nC);
+        }
+        if ((rc = perm_stats_launch(db, db->d_setRows, db->d_setTot, rows, nC, dObs, dSt)) != IGD_HIP_OK) return rc;
+        if (r0 + rows == nperm + 1) HIPCHK(hipMemcpyAsync(res.data(), db->d_pmStat, (size_t)(7 * nC) * 8, hipMemcpyDeviceToHost, st));
+        return IGD_HIP_OK;
     };
-
-    // the set as given
-    if ((rc = count(rC, rS, rE, 1)) != IGD_HIP_OK) return rc;
-    HIPCHK(hipMemcpyAsync(dObs, db->d_setRows, (size_t)nF * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(dObs + nF, db->d_setTot, 8, hipMemcpyDeviceToDevice, st));
-    if ((rc = perm_stats_init(db, dSt, nC)) != IGD_HIP_OK) return rc;
-    for (int64_t p0 = 0; p0 < nperm; p0 += pc) {
-        const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
-        if ((rc = permute_launch(db, pl, rC, rS, rE, nq, rL, db->nCtg, (u64)seed, (u64)p0, n * nq, db->d_qc, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
-        if ((rc = count(db->d_qc, db->d_qs, db->d_qe, n)) != IGD_HIP_OK) return rc;
-        if ((rc = perm_stats_launch(db, db->d_setRows, db->d_setTot, n, nC, dObs, dSt)) != IGD_HIP_OK) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(res.data(), db->d_pmStat, (size_t)(7 * nC) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, nF * 8, prepare, count);
+    if (rc != IGD_HIP_OK) return rc;
     perm_copy_out(res.data(), nC, out);
     return IGD_HIP_OK;
 }
@@ -271,19 +321,13 @@ extern "C" int igd_hip_permute_regions_ws(igd_hip_db *db, const int32_t *ichr, c
     std::vector<int32_t> hs((size_t)(np * nq)), he((size_t)(np * nq));
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg);
-    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
+    int rc = ensure_qstage(db, pc * nq);
     PermPlace pl;
-    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, mode, ws, &pl);
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, nctg, mode, ws, &pl);
     if (rc != IGD_HIP_OK) return rc;
-    int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
-    HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    if (nctg) HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)nctg * 4, hipMemcpyHostToDevice, st));
     for (int64_t a = 0; a < np; a += pc) {
         const int64_t n = np - a < pc ? np - a : pc;
-        if ((rc = permute_launch(db, pl, rC, rS, rE, nq, rL, nctg, (u64)seed, (u64)(p0 + a), n * nq, nullptr, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
+        if ((rc = permute_launch(db, pl, (u64)seed, (u64)(p0 + a), n * nq, nullptr, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
         HIPCHK(hipMemcpyAsync(hs.data() + a * nq, db->d_qs, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(he.data() + a * nq, db->d_qe, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
     }

@@ -7,14 +7,12 @@
 // igd_hip_max_batch() -- there are no distance rows, so no row budget and no row workspace -- every chunk's part of every set
 // cut into slices of sets_slice_len(chunk) regions, ONE launch per chunk with support_launch's grid rule, the three matrices
 // copied out once per group.
-// igd_hip_permute_nearest is igd_hip_permute_support_ov's driver (host_permute.hpp) with the three matrices as its rows: the
-// regions and ctg_len go up once (db->d_pmReg); the slice table has one row per permutation of a chunk, is built and
-// uploaded once, and a shorter last chunk uses its prefix; a chunk holds pc permutations with pc * nq <= igd_hip_max_batch()
-// and 3 * pc * (nFiles + 1) * 8 <= perm_row_bytes(); per chunk, on the engine's stream and without a wait: igd_permute_regions
-// into the staging arrays, a memset of the chunk's three matrices, the fused kernel, an asynchronous copy of the chunk's rows
-// into a buffer of this file.  Row 0 -- the set as given -- is one more launch over the regions themselves.  The null
-// distribution itself comes back, int64[nperm + 1][nFiles + 1] three times: the statistic of interest is a ratio of two of
-// them per permutation.  On an error nothing of the caller's is written.
+// igd_hip_permute_nearest runs in run_perm_chunks (host_permute.hpp: refusals, upload, chunks, the wait) with the three
+// matrices as its rows, 3 * (nFiles + 1) * 8 bytes per permutation: the slice table has one row per permutation of a chunk, is
+// built and uploaded once, and a shorter last chunk uses its prefix; per chunk a memset of the chunk's three matrices, the
+// fused kernel, an asynchronous copy of the chunk's rows into a buffer of this file.  The null distribution itself comes back,
+// int64[nperm + 1][nFiles + 1] three times: the statistic of interest is a ratio of two of them per permutation.  On an error
+// nothing of the caller's is written.
 // Databases with more files than IGD_NEAREST_FUSED_LDS_FILES: the first calls igd_hip_nearest_sets; the second runs
 // igd_hip_nearest_dev + igd_nearest_reduce over the same staged regions (nearest_rows_reduce below), in pieces within the
 // row budget of igd_hip_nearest, with a wait per piece.  The results are the same integers.
@@ -105,30 +103,7 @@ extern "C" int igd_hip_permute_nearest_ws(igd_hip_db *db, const int32_t *ichr, c
                                           int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws)
 {
     if (nearest_window_bad("igd_hip_permute_nearest", window)) return IGD_HIP_ERR_ARG;
-    if (!db || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) ||
-        !perm_mode_ok(mode, ws)) {
-        snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: bad argument");
-        return IGD_HIP_ERR_ARG;
-    }
-    if (nperm < 1 || nperm > IGD_HIP_PERM_MAX) {
-        snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: %lld permutations, not 1 .. %lld", (long long)nperm, (long long)IGD_HIP_PERM_MAX);
-        return IGD_HIP_ERR_ARG;
-    }
-    if (nq > max_batch()) {
-        snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: %lld regions, more than %lld", (long long)nq, (long long)max_batch());
-        return IGD_HIP_ERR_ARG;
-    }
-    for (int64_t i = 0; i < nq; i++) {
-        const int32_t c = ichr[i];
-        if (c < 0 || c >= db->nCtg) continue;
-        const int64_t L = ctg_len[c];
-        if (L < 1 || qs[i] < 0 || qe[i] < qs[i] || (int64_t)qe[i] > L) {
-            snprintf(g_err, sizeof g_err, "igd_hip_permute_nearest: region %lld = (%d, %d, %d) does not lie on its contig of length %lld",
-                     (long long)i, (int)c, (int)qs[i], (int)qe[i], (long long)L);
-            return IGD_HIP_ERR_ARG;
-        }
-    }
-    if (perm_ws_refused("igd_hip_permute_nearest", ws, ctg_len, db->nCtg, ichr, qs, qe, nq, true)) return IGD_HIP_ERR_ARG;
+    if (perm_args_refused("igd_hip_permute_nearest", db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, false)) return IGD_HIP_ERR_ARG;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     int64_t *const outs[3] = {n_within, n_overlap, sum_dist};
     if (nq == 0 || nF == 0) {                            // every statistic is 0: no region, or no dataset to be near
@@ -138,55 +113,31 @@ extern "C" int igd_hip_permute_nearest_ws(igd_hip_db *db, const int32_t *ichr, c
 
     const SliceImage im = slice_image(db, IGD_HIP_RULE_FLAT, v);
     const bool fused = nF <= IGD_NEAREST_FUSED_LDS_FILES;
-    int64_t pc = max_batch() / nq;
-    const int64_t byRows = perm_row_bytes() / (3 * nC * 8);
-    if (byRows < pc) pc = byRows < 1 ? 1 : byRows;
-    if (nperm < pc) pc = nperm;
-    const int64_t sliceLen = sets_slice_len(pc * nq);
-    const int64_t perRow = (nq + sliceLen - 1) / sliceLen;                // slices of one permutation
-    std::vector<SetSlice> slices;
-    if (fused) {
-        slices.reserve((size_t)(pc * perRow));
-        for (int64_t r = 0; r < pc; r++) push_slices(slices, (int32_t)r, r * nq, (r + 1) * nq, sliceLen, 0);
-    }
-    std::vector<int64_t> res((size_t)(3 * R * nC));
-
-    HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
-    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + db->nCtg);
-    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_grpStat, &db->grpStatCap, 3 * pc * nC);
-    if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
-    if (rc == IGD_HIP_OK && fused) rc = dev_grow(db, &db->d_grpSlices, &db->grpSliceCap, pc * perRow);
-    PermPlace pl;
-    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, mode, ws, &pl);
-    if (rc != IGD_HIP_OK) return rc;
-    int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
-    HIPCHK(hipMemcpyAsync(rC, ichr, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)db->nCtg * 4, hipMemcpyHostToDevice, st));
-    if (fused) HIPCHK(hipMemcpyAsync(db->d_grpSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
-
+    std::vector<SetSlice> slices;
+    std::vector<int64_t> res((size_t)(3 * R * nC));
+    int64_t perRow = 0;
+    auto prepare = [&](int64_t pc, int64_t sliceLen, int64_t perRow_) -> int {
+        perRow = perRow_;
+        if (fused) slices = perm_row_slices(pc, nq, sliceLen);
+        int rc = dev_grow(db, &db->d_grpStat, &db->grpStatCap, 3 * pc * nC);
+        if (rc == IGD_HIP_OK && fused) rc = dev_grow(db, &db->d_grpSlices, &db->grpSliceCap, pc * perRow);
+        return rc;
+    };
     // `rows` rows counted from the region arrays (c, s, e) into zeroed matrices, which go to rows [r0, r0 + rows) of res
     auto count = [&](const int32_t *c, const int32_t *s, const int32_t *e, int64_t rows, int64_t r0) -> int {
         const int64_t matWords = rows * nC;
+        if (r0 == 0 && fused) HIPCHK(hipMemcpyAsync(db->d_grpSlices, slices.data(), slices.size() * sizeof(SetSlice), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(db->d_grpStat, 0, (size_t)(3 * matWords) * 8, st));
-        const int rc2 = fused ? nearest_fused_launch(db, im, c, s, e, (int)(rows * perRow), window, v, matWords)
-                              : nearest_rows_reduce(db, c, s, e, rows, nq, window, v, matWords);
-        if (rc2 != IGD_HIP_OK) return rc2;
+        const int rc = fused ? nearest_fused_launch(db, im, c, s, e, (int)(rows * perRow), window, v, matWords)
+                             : nearest_rows_reduce(db, c, s, e, rows, nq, window, v, matWords);
+        if (rc != IGD_HIP_OK) return rc;
         for (int i = 0; i < 3; i++)
             HIPCHK(hipMemcpyAsync(res.data() + (i * R + r0) * nC, db->d_grpStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
-
-    if ((rc = count(rC, rS, rE, 1, 0)) != IGD_HIP_OK) return rc;         // the set as given
-    for (int64_t p0 = 0; p0 < nperm; p0 += pc) {
-        const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
-        if ((rc = permute_launch(db, pl, rC, rS, rE, nq, rL, db->nCtg, (u64)seed, (u64)p0, n * nq, db->d_qc, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
-        if ((rc = count(db->d_qc, db->d_qs, db->d_qe, n, 1 + p0)) != IGD_HIP_OK) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, 3 * nC * 8, prepare, count);
+    if (rc != IGD_HIP_OK) return rc;
     for (int i = 0; i < 3; i++)
         if (outs[i]) memcpy(outs[i], res.data() + (size_t)i * (size_t)(R * nC), (size_t)(R * nC) * 8);
     return IGD_HIP_OK;

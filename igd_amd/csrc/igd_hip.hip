@@ -330,13 +330,14 @@ struct igd_hip_db {
     // the matrix, and the generic entries' resident copies of the caller's rows (64-bit words)
     u64 *d_coCols, *d_coMat, *d_coA, *d_coB;
     int64_t coColsCap, coMatCap, coACap, coBCap;
-    // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats (host_permute.hpp): the set's regions and the contig
-    // lengths (ichr, qs, qe, ctg_len), and observed with the six statistics (64-bit words)
+    // perm_place_upload (host_permute.hpp), for run_perm_chunks -- the three permutation nulls -- and igd_hip_permute_regions: the
+    // call's regions and contig lengths (ichr, qs, qe, ctg_len).  igd_hip_permute_support / igd_hip_perm_stats: observed with the
+    // six statistics (64-bit words)
     int32_t *d_pmReg;
     long long *d_pmStat;
     int64_t pmRegCap, pmStatCap;
-    // the _ws entries of the three permutation nulls (host_permute.hpp): the workspace table of one call, as 32-bit words --
-    // w_off (int64[nctg + 1], in front: 8-byte aligned), then w_start, w_len and w_pre
+    // perm_place_upload under a workspace (the _ws entries): the table of one call, as 32-bit words -- w_off (int64[nctg + 1], in
+    // front: 8-byte aligned), then w_start, w_len and w_pre
     int32_t *d_pmWs;
     int64_t pmWsCap;
     // run_set_groups (host_nearest.hpp), the driver of igd_hip_nearest_sets(_fused), igd_hip_nearest_hist, igd_hip_flank_reldist and
@@ -360,8 +361,8 @@ struct igd_hip_db {
     // igd_hip_merge_sets / _dev (host_merge.hpp): every array of one merge, carved from one allocation (bytes)
     char *d_merge;
     int64_t mergeCap;
-    // igd_hip_permute_bp (host_permute_bp.hpp): the runs of one chunk of rows (m_ichr, m_qs, m_qe), and its 64-bit words: the
-    // regular set offsets, the run offsets, dropped, set_bp and n_merged per row
+    // igd_hip_permute_bp (host_permute_bp.hpp; grown in its prepare, carved in its count): the runs of one chunk of rows (m_ichr,
+    // m_qs, m_qe), and its 64-bit words: the regular set offsets, the run offsets, dropped, set_bp and n_merged per row
     int32_t *d_pbRun;
     int64_t *d_pbWord;
     int64_t pbRunCap, pbWordCap;

@@ -1161,11 +1161,7 @@ int igdc_workspace_valid(const igd_hip_workspace *ws, const int32_t *ctg_len, in
 int64_t igdc_workspace_first_unplaceable(const igd_hip_workspace *ws, const int32_t *ctg_len, const int32_t *ichr, const int32_t *qs,
                                          const int32_t *qe, int64_t nq)
 {
-    for (int64_t i = 0; i < nq; i++) {
-        int32_t s = qs[i], e = qe[i];
-        if (igd_hip_perm_place_ws(0, ichr[i], i, ctg_len, ws->nctg, ws->w_off, ws->w_start, ws->w_len, ws->w_pre, &s, &e)) return i;
-    }
-    return -1;
+    return igd_hip_perm_first_unplaceable(ws, ctg_len, ichr, qs, qe, nq);
 }
 
 static int ws_span_cmp(const void *x, const void *y)
@@ -1208,15 +1204,10 @@ int igdc_read_workspace(const igdc_db *db, const char *path, const int32_t *ctg_
     return rc == 0 ? 0 : -2;
 }
 
-/* the first region on a known contig that breaks 0 <= s <= e <= L, L >= 1; -1: none */
+/* igd_hip_perm_first_bad (include/igd_hip.h) as a symbol of the library */
 int64_t igdc_permute_first_bad(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg)
 {
-    for (int64_t i = 0; i < nq; i++) {
-        const int32_t c = ichr[i];
-        if (c < 0 || c >= nctg) continue;
-        if (ctg_len[c] < 1 || qs[i] < 0 || qe[i] < qs[i] || qe[i] > ctg_len[c]) return i;
-    }
-    return -1;
+    return igd_hip_perm_first_bad(ichr, qs, qe, nq, ctg_len, nctg);
 }
 
 /* the refusals the three drivers share (each adds its own in front): the set and the contig lengths, a mode the call can run, the

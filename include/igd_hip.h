@@ -908,6 +908,29 @@ static inline IGD_HIP_HD_ int igd_hip_perm_place_ws(uint64_t base, int32_t c, in
     *e = (int32_t)(t + len);
     return 0;
 }
+/* The two questions every driver asks of a call's regions before it runs, the engine's and the host route's alike (host only).
+ * igd_hip_perm_first_bad: the first region on a known contig that breaks L >= 1, 0 <= s <= e <= L; -1: none.
+ * igd_hip_perm_first_unplaceable: the first such valid region that fits in no segment of its contig (T == 0 above) in a table
+ * igd_hip_workspace_valid has passed for these contigs; -1: none. */
+static inline int64_t igd_hip_perm_first_bad(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                                             int32_t nctg)
+{
+    for (int64_t i = 0; i < nq; i++) {
+        const int32_t c = ichr[i];
+        if (c < 0 || c >= nctg) continue;
+        if (ctg_len[c] < 1 || qs[i] < 0 || qe[i] < qs[i] || qe[i] > ctg_len[c]) return i;
+    }
+    return -1;
+}
+static inline int64_t igd_hip_perm_first_unplaceable(const igd_hip_workspace *ws, const int32_t *ctg_len, const int32_t *ichr,
+                                                     const int32_t *qs, const int32_t *qe, int64_t nq)
+{
+    for (int64_t i = 0; i < nq; i++) {
+        int32_t s = qs[i], e = qe[i];
+        if (igd_hip_perm_place_ws(0, ichr[i], i, ctg_len, ws->nctg, ws->w_off, ws->w_start, ws->w_len, ws->w_pre, &s, &e)) return i;
+    }
+    return -1;
+}
 /* The whole test on one device.  ctg_len is int32[number of contigs of db], in the database's contig order.  Index nFiles of
  * every output is the "any dataset" column: the regions with a hit in any file, what igd_hip_support_sets adds to nhit.
  *     observed[f] = support of the set as given                          sum[f], sumsq[f] = over the permutations, of x and x^2

@@ -338,6 +338,45 @@ def test_refusals_leave_the_callers_arrays_untouched(dbfx):
             f()
 
 
+def test_the_shared_refusals_word_for_word_in_all_three_drivers(dbfx):
+    """The faults the three drivers refuse alike, each alone, 3 regions and 2 permutations, with the workspace (mode 2) and without
+    (mode 1): every entry answers IGD_HIP_ERR_ARG, its message opens with its own name and carries the same key text, and every
+    output array keeps its fill."""
+    L_ = H()
+    db, L, ws, tab = dbfx["db"], dbfx["ctg_len"], dbfx["ws"], dbfx["tab"]
+    nC, R = db.nfiles + 1, 3
+    longest = int(WR.contig(tab, 0)[1][0])
+    c, s, e = np.zeros(3, np.int32), np.array([0, 5, 9], np.int32), np.array([10, 5 + longest, 9], np.int32)
+    assert longest >= 10 and 5 + longest <= L[0]
+    zero_len = L.copy()
+    zero_len[0] = 0
+    perm_max = 1 << 20                                                            # IGD_HIP_PERM_MAX
+    put = lambda a, v: np.concatenate([a[:1], np.array([v], np.int32), a[2:]])   # noqa: E731  (region 1 changed)
+    faults = [(dict(c=None), b"bad argument"), (dict(L=None), b"bad argument"), (dict(mode=3), b"bad argument"),
+              (dict(nperm=0), b"permutations"), (dict(nperm=perm_max + 1), b"permutations"), (dict(e=put(e, 4)), b"region 1 "),
+              (dict(s=put(s, -1), e=put(e, 3)), b"region 1 "), (dict(e=put(e, int(L[0]) + 1)), b"region 1 "), (dict(L=zero_len), b"region 0 ")]
+    st = [np.full(nC, G64, np.int64) for _ in range(7)]
+    mats = [np.full(R * nC, G64, np.int64) for _ in range(3)]
+    small = [np.full(R, G64, np.int64), np.full(R, G64, np.int64), np.full(1, G64, np.int64)]
+    opt = lambda a: None if a is None else ptr(a)                                 # noqa: E731
+    rows = 0
+    for fault, key in faults:
+        for mode, w in ((2, ws.ptr), (1, None)):
+            a = dict(dict(c=c, s=s, e=e, L=L, mode=mode, nperm=2), **fault)
+            head = (db.dev, opt(a["c"]), ptr(a["s"]), ptr(a["e"]), 3, opt(a["L"]), a["mode"], 0, a["nperm"])
+            calls = (("igd_hip_permute_support", lambda: L_.igd_hip_permute_support_ws(*head, NOV, NEST, *[ptr(x) for x in st], None, w)),
+                     ("igd_hip_permute_nearest", lambda: L_.igd_hip_permute_nearest_ws(*head, 100, NOV, *[ptr(x) for x in mats], w)),
+                     ("igd_hip_permute_bp", lambda: L_.igd_hip_permute_bp_ws(*head, NOV, NEST, ptr(mats[0]), ptr(small[0]), ptr(small[1]),
+                                                                             ptr(small[2]), w)))
+            for name, call in calls:
+                assert call() == -2, (name, fault, mode)
+                msg = L_.igd_hip_last_error()
+                assert msg.startswith(name.encode() + b":") and key in msg, (msg, fault, mode)
+            assert all((x == G64).all() for x in st + mats + small), (fault, mode)
+            rows += 1
+    assert rows == 2 * len(faults)
+
+
 # ---- the command line ---------------------------------------------------------------------------------------------------------
 def test_cli_W_on_the_engine_route_equals_the_host_route(wfx):  # noqa: F811
     for stat in ([], ["-D", "700"], ["-G"], ["-v", "500"], ["-O", "40"]):
