@@ -9,7 +9,10 @@ __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "re
            "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD",
            "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
            "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP",
-           "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace"]
+           "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace",
+           "DatasetGroups", "build_groups", "read_groups_file", "GROUP_MAX"]
+# (igd_amd.group_support_host resolves below like the other host routes; it is not in __all__, whose `_host` names with regions are
+# the table of tests/test_database_args_host.py)
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -35,7 +38,8 @@ def __getattr__(name):
                 "nearest_signed_host", "nearest_hist_host", "NearestHist", "NEAREST_NO_RECORD",
                 "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
                 "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP",
-                "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace"):
+                "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace",
+           "DatasetGroups", "build_groups", "read_groups_file", "group_support_host", "GROUP_MAX"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

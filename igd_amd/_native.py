@@ -155,6 +155,14 @@ def hip():
         # the `_ov` forms: the same arguments, then a pointer to an igd_hip_min_overlap (three int32; NULL: no threshold)
         L.igd_hip_search_sets_ov.argtypes = L.igd_hip_search_sets.argtypes + [C.c_void_p]
         L.igd_hip_support_sets_ov.argtypes = L.igd_hip_support_sets.argtypes + [C.c_void_p]
+        # per group of datasets: db, ichr, qs, qe, set_off, nsets, grp_off, grp_idx, ngroups, v, rule, gsupport, gnhit, min_overlap /
+        # ..., nsets, u_ichr, u_qs, u_qe, nu, grp_off, grp_idx, ngroups, v, rule, gsupport, gusupport, pvalue_log, odds_ratio,
+        # clamped, gnhit, gunhit, min_overlap
+        L.igd_hip_group_support_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_group_enrich_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int] + \
+            [C.c_void_p] * 8
         L.igd_hip_coverage_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
         L.igd_hip_member_words.argtypes = [C.c_void_p]
@@ -367,6 +375,10 @@ def _bind_core(L):
     L.igdc_search_host.argtypes = L.igdc_support_host.argtypes
     L.igdc_search_host_ov.argtypes = L.igdc_search_host.argtypes + [C.c_void_p]
     L.igdc_support_host_ov.argtypes = L.igdc_support_host.argtypes + [C.c_void_p]
+    # support per group of datasets on the host: db, map, ichr, qs, qe, nq, grp_off, grp_idx, ngroups, v, rule, gsupport, gnhit,
+    # min_overlap
+    L.igdc_group_support_host_ov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
     # covered base pairs on the host: the same arguments, coverage and covered in place of support and nhit
     L.igdc_coverage_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                      C.c_void_p, C.POINTER(C.c_int64)]

@@ -3,7 +3,8 @@
 // the set_off checks, slice, step and grid arithmetic, kernel dispatch by template flags, and two drivers:
 //   run_region_chunks  host arrays in chunks of regions, rows back per chunk: igd_hip_nearest(_signed), igd_hip_flank,
 //                      igd_hip_map, igd_hip_membership, igd_hip_cooccur
-//   run_set_chunks     chunks of sets, rows added on the host: igd_hip_search_sets / igd_hip_support_sets / igd_hip_coverage_sets
+//   run_set_chunks     chunks of sets, rows added on the host: igd_hip_search_sets / igd_hip_support_sets / igd_hip_coverage_sets /
+//                      igd_hip_group_support_sets (rows of ngroups columns)
 // (The group driver of the resident set statistics, run_set_groups, is in host_nearest.hpp; the chunk driver of the three
 // permutation nulls, run_perm_chunks, in host_permute.hpp.)
 // ------------------------------------------------------------------------------------------
@@ -180,13 +181,14 @@ static void with_flags(bool a, bool b, F &&f)
 // part of every set of fewer than bigMin queries is cut into slices of sliceLen (row, first, last query within the chunk);
 // prepare(m, rows, nSlices) sees to the caller's own workspace; launch(ns, grid) counts the slices into the zeroed d_setRows /
 // d_setTot; big(row, a, b) counts queries [a, b) of the chunk, part of a larger set, into row `row`; then the chunk's rows and
-// totals come back and are ADDED to hits[nsets][nFiles] and, when given, totals[nsets].
+// totals come back and are ADDED to hits[nsets][ncols] and, when given, totals[nsets].  ncols is the row width: nFiles for the
+// dataset tables, the number of groups for igd_hip_group_support_sets.
 template <typename Prepare, typename Launch, typename Big>
 static int run_set_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
-                          int64_t sliceLen, int64_t maxGrid, int64_t bigMin, int64_t *hits, int64_t *totals, Prepare &&prepare,
+                          int64_t ncols, int64_t sliceLen, int64_t maxGrid, int64_t bigMin, int64_t *hits, int64_t *totals, Prepare &&prepare,
                           Launch &&launch, Big &&big)
 {
-    const int64_t nF = db->nFiles, step = max_batch();
+    const int64_t nF = ncols, step = max_batch();
     const int64_t rowCap = sets_row_bytes() / (nF * 8) > 0 ? sets_row_bytes() / (nF * 8) : 1;
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;

@@ -77,7 +77,7 @@ extern "C" int igd_hip_coverage_sets(igd_hip_db *db, const int32_t *ichr, const 
     const int64_t maxGrid = lds ? IGD_SETS_GRID : wide_grid(IGD_COVERAGE_FRONT_BYTES, nF * 8 * (IGD_SETS_WG / IGD_WAVE));
     unsigned tag0 = 0;
     auto launch = [&](int ns, int grid) { return coverage_launch(db, im, db->d_qc, db->d_qs, db->d_qe, ns, grid, v, tag0); };
-    return run_set_chunks(db, ichr, qs, qe, set_off, nsets, sets_slice_len(set_off[nsets]), maxGrid, INT64_MAX, coverage, covered,
+    return run_set_chunks(db, ichr, qs, qe, set_off, nsets, db->nFiles, sets_slice_len(set_off[nsets]), maxGrid, INT64_MAX, coverage, covered,
                           [&](int64_t m, int64_t, int) {
                               return lds ? IGD_HIP_OK : coverage_fronts(db, maxGrid * (IGD_SETS_WG / IGD_WAVE) * nF, m, &tag0);
                           },

@@ -56,13 +56,14 @@ extern "C" int igd_hip_fisher_tables(igd_hip_db *db, const int64_t *a, const int
     return IGD_HIP_OK;
 }
 
-// igd_fisher_cells<true> over nsets x nFiles cells: rows = the sets' support (host), usupport[nFiles], nk[nsets] = the sets'
-// sizes, nu = the universe's; b, c, d and the clamp flag are formed on the device.  pvalue_log / odds_ratio (may be NULL)
-// [nsets x nFiles] and clamped[nsets] (may be NULL) are the host's.
-static int fisher_enrich_cells(igd_hip_db *db, const int64_t *rows, const int64_t *usupport, const int64_t *nk, int32_t nsets, int64_t nu,
-                               double *pvalue_log, double *odds_ratio, int64_t *clamped)
+// igd_fisher_cells<true> over nsets x ncols cells (ncols = nFiles for the dataset tables, the number of groups for
+// igd_hip_group_enrich_sets): rows = the sets' support (host), usupport[ncols], nk[nsets] = the sets' sizes, nu = the
+// universe's; b, c, d and the clamp flag are formed on the device.  pvalue_log / odds_ratio (may be NULL) [nsets x ncols] and
+// clamped[nsets] (may be NULL) are the host's.
+static int fisher_enrich_cells(igd_hip_db *db, int64_t ncols, const int64_t *rows, const int64_t *usupport, const int64_t *nk, int32_t nsets,
+                               int64_t nu, double *pvalue_log, double *odds_ratio, int64_t *clamped)
 {
-    const int64_t nF = db->nFiles, ncell = (int64_t)nsets * nF;
+    const int64_t nF = ncols, ncell = (int64_t)nsets * nF;
     if (ncell == 0) return IGD_HIP_OK;
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = db->stream;
@@ -146,7 +147,7 @@ extern "C" int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const
     if (nhit && nsets) memcpy(nhit, hit.data(), (size_t)nsets * 8);
     if (unhit) *unhit = hit[(size_t)nsets];
     if (clamped && nsets) memset(clamped, 0, (size_t)nsets * 8);
-    return fisher_enrich_cells(db, rows.data(), usupport, nk.data(), nsets, nu, pvalue_log, odds_ratio, clamped);
+    return fisher_enrich_cells(db, nF, rows.data(), usupport, nk.data(), nsets, nu, pvalue_log, odds_ratio, clamped);
 }
 
 extern "C" int igd_hip_enrich_sets_nhit(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,

@@ -44,7 +44,7 @@ extern "C" void igd_hip_close(igd_hip_db *db)
                     db->d_memBits, db->d_memNf, db->d_memHit, db->d_fisher, db->d_rsUni, db->d_rsTab, db->d_rsSize, db->d_rsBits,
                     db->d_coCols, db->d_coMat, db->d_coA, db->d_coB, db->d_pmReg, db->d_pmStat, db->d_pmWs,
                     db->d_grpStat, db->d_grpSlices, db->d_nrDist, db->d_nrMin, db->d_nrEdges,
-                    db->d_mpCount, db->d_mpAgg, db->d_merge, db->d_pbRun, db->d_pbWord};
+                    db->d_mpCount, db->d_mpAgg, db->d_merge, db->d_pbRun, db->d_pbWord, db->d_gsTab};
     for (void *p : ptrs)
         if (p && !(db->arena && (char *)p >= db->arena && (char *)p < db->arena + db->arenaSize)) (void)hipFree(p);
     if (db->arena) (void)hipFree(db->arena);

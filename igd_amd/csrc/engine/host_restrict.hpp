@@ -247,7 +247,7 @@ extern "C" int igd_hip_enrich_restricted(igd_hip_db *db, const int32_t *ichr, co
 
     // the statistics: igd_fisher_cells<true> on the restricted supports, n_k := |R_k| (nothing can be clamped)
     std::vector<double> hp((size_t)ncell + 1), ho((size_t)ncell + 1);
-    rc = fisher_enrich_cells(db, rows.data(), urow.data(), hz.data(), nsets, nu, hp.data(), odds_ratio ? ho.data() : nullptr, nullptr);
+    rc = fisher_enrich_cells(db, db->nFiles, rows.data(), urow.data(), hz.data(), nsets, nu, hp.data(), odds_ratio ? ho.data() : nullptr, nullptr);
     if (rc != IGD_HIP_OK) return rc;
 
     if (nF) memcpy(usupport, urow.data(), (size_t)nF * 8);

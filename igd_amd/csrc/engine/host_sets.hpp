@@ -90,7 +90,7 @@ extern "C" int igd_hip_search_sets_ov(igd_hip_db *db, const int32_t *ichr, const
         }
         return r;
     };
-    return run_set_chunks(db, ichr, qs, qe, set_off, nsets, sets_slice_len(nSmall), IGD_SETS_GRID, bigMin, hits, totals,
+    return run_set_chunks(db, ichr, qs, qe, set_off, nsets, db->nFiles, sets_slice_len(nSmall), IGD_SETS_GRID, bigMin, hits, totals,
                           [](int64_t, int64_t, int) { return IGD_HIP_OK; }, launch, big);
 }
 

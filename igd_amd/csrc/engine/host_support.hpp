@@ -70,7 +70,7 @@ extern "C" int igd_hip_support_sets_ov(igd_hip_db *db, const int32_t *ichr, cons
 
     const SliceImage im = slice_image(db, rule, v);
     const int64_t maxGrid = support_max_grid(db);
-    return run_set_chunks(db, ichr, qs, qe, set_off, nsets, sets_slice_len(set_off[nsets]), maxGrid, INT64_MAX, support, nhit,
+    return run_set_chunks(db, ichr, qs, qe, set_off, nsets, db->nFiles, sets_slice_len(set_off[nsets]), maxGrid, INT64_MAX, support, nhit,
                           [&](int64_t, int64_t, int) { return ensure_support_bits(db, maxGrid); },
                           [&](int ns, int grid) { return support_launch(db, im, db->d_qc, db->d_qs, db->d_qe, ns, grid, v, ov, mo); },
                           no_big_sets);

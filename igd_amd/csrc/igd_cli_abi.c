@@ -1003,6 +1003,97 @@ static void search_sets(const cli_paths *P, int32_t v, int64_t *hits)
     sets_free(&S);
 }
 
+/* ------------------------------- `-K groups.tsv`: the tables of `-u` and `-U [-R]` per GROUP of datasets ----------------- */
+/* One `dataset<TAB>group` pair per line: dataset is a file name exactly as the index lists it, or else a decimal dataset
+ * number; the group's name is the rest of the line; `#` lines and blank lines are skipped; a dataset may occur on several
+ * lines; groups are numbered in order of first appearance.  The relation is kept as include/igd_hip.h defines a grouping
+ * (off, idx: CSR, ascending within a dataset's run), with the groups' names and their numbers of datasets.  g_grp.ng == 0:
+ * no -K, and every table below is per dataset as it always was. */
+typedef struct { int32_t ng, *off, *idx, *nds; char **names; } cli_groups;
+static cli_groups g_grp = {0, NULL, NULL, NULL, NULL};
+
+static void groups_free(void)
+{
+    for (int32_t g = 0; g < g_grp.ng; g++) free(g_grp.names[g]);
+    free(g_grp.off); free(g_grp.idx); free(g_grp.nds); free(g_grp.names);
+    memset(&g_grp, 0, sizeof g_grp);
+}
+
+static int pair_cmp(const void *a, const void *b)
+{
+    const int32_t *x = (const int32_t *)a, *y = (const int32_t *)b;
+    return x[0] != y[0] ? (x[0] < y[0] ? -1 : 1) : x[1] != y[1] ? (x[1] < y[1] ? -1 : 1) : 0;
+}
+
+/* 0, or EX_USAGE after one "Not supported" line that names the file and, where there is one, the line */
+static int groups_read(const char *path)
+{
+    FILE *fp = fopen(path, "r");
+    if (!fp) { printf("Not supported: -K %s (cannot open the groups file)\n", path); return EX_USAGE; }
+    const int32_t nf = IGD->nFiles;
+    int32_t *pairs = NULL;
+    int64_t npair = 0, cap = 0, lineno = 0;
+    char *line = NULL;
+    size_t lcap = 0;
+    const char *why = NULL;
+    g_grp.names = (char **)calloc((size_t)IGD_HIP_GROUP_MAX, sizeof(char *));
+    while (!why && getline(&line, &lcap, fp) >= 0) {
+        lineno++;
+        size_t n = strlen(line);
+        while (n && (line[n - 1] == '\n' || line[n - 1] == '\r')) line[--n] = '\0';
+        size_t blank = 0;
+        while (line[blank] == ' ' || line[blank] == '\t' || line[blank] == '\v' || line[blank] == '\f') blank++;
+        if (line[blank] == '\0' || line[0] == '#') continue;
+        char *tab = strchr(line, '\t');
+        if (!tab || tab[1] == '\0') { why = "not a dataset, a tab and a group"; break; }
+        *tab = '\0';
+        const char *grp = tab + 1;
+        int32_t f = -1;
+        for (int32_t i = 0; i < nf && f < 0; i++) if (strcmp(IGD->finfo[i].fileName, line) == 0) f = i;
+        if (f < 0 && line[0] != '\0' && strspn(line, "0123456789") == strlen(line) && strlen(line) < 10 && atol(line) < nf) f = (int32_t)atol(line);
+        if (f < 0) { why = "the database has no such dataset"; break; }
+        int32_t g = -1;
+        for (int32_t i = 0; i < g_grp.ng && g < 0; i++) if (strcmp(g_grp.names[i], grp) == 0) g = i;
+        if (g < 0) {
+            if (g_grp.ng == IGD_HIP_GROUP_MAX) { why = "more than 8192 groups"; break; }
+            g = g_grp.ng++;
+            g_grp.names[g] = strdup(grp);
+        }
+        if (npair == cap) { cap = cap ? 2 * cap : 1024; pairs = (int32_t *)realloc(pairs, sizeof(int32_t) * 2 * (size_t)cap); }
+        pairs[2 * npair] = f; pairs[2 * npair + 1] = g;
+        npair++;
+    }
+    free(line);
+    fclose(fp);
+    if (!why && g_grp.ng == 0) { printf("Not supported: -K %s (the file names no group)\n", path); free(pairs); groups_free(); return EX_USAGE; }
+    if (why) {
+        printf("Not supported: -K %s, line %lld: %s\n", path, (long long)lineno, why);
+        free(pairs);
+        groups_free();
+        return EX_USAGE;
+    }
+    qsort(pairs, (size_t)npair, 2 * sizeof(int32_t), pair_cmp);
+    g_grp.off = (int32_t *)calloc((size_t)nf + 1, sizeof(int32_t));
+    g_grp.idx = (int32_t *)calloc((size_t)npair + 1, sizeof(int32_t));
+    g_grp.nds = (int32_t *)calloc((size_t)g_grp.ng, sizeof(int32_t));
+    int32_t m = 0;
+    for (int64_t i = 0; i < npair; i++) {
+        if (i > 0 && pairs[2 * i] == pairs[2 * i - 2] && pairs[2 * i + 1] == pairs[2 * i - 1]) continue;     /* the same pair twice */
+        g_grp.idx[m++] = pairs[2 * i + 1];
+        g_grp.off[pairs[2 * i] + 1]++;
+        g_grp.nds[pairs[2 * i + 1]]++;
+    }
+    for (int32_t f = 0; f < nf; f++) g_grp.off[f + 1] += g_grp.off[f];
+    free(pairs);
+    return 0;
+}
+
+/* the columns of the `-u` and `-U` tables: the datasets, or under -K the groups (their number of datasets where a dataset's
+ * number of regions stands, their name where its file name stands) */
+static int32_t table_cols(void) { return g_grp.ng ? g_grp.ng : IGD->nFiles; }
+static int32_t col_count(int32_t i) { return g_grp.ng ? g_grp.nds[i] : IGD->finfo[i].nr; }
+static const char *col_name(int32_t i) { return g_grp.ng ? g_grp.names[i] : IGD->finfo[i].fileName; }
+
 /* ------------------------------- `igd search -q F -u` / `-Q <list> -u` ----------------- */
 /* Support counts: per database file the number of QUERY REGIONS that overlap at least one of its records, where the table
  * of `-q` counts (query, record) pairs -- the count a region-set enrichment table is made of.  The table keeps the shape
@@ -1011,9 +1102,10 @@ static void search_sets(const cli_paths *P, int32_t v, int64_t *hits)
  * host, ONE igd_hip_support_sets call on the engine. */
 static void print_support_table(const int64_t *sup, int64_t nhit, int64_t nq)
 {
-    printf("index\t number of regions\t number of query regions\t File_name\n");
-    for (int32_t i = 0; i < IGD->nFiles; i++)
-        if (sup[i] > 0) printf("%i\t%i\t%lld\t%s\n", i, IGD->finfo[i].nr, (long long)sup[i], IGD->finfo[i].fileName);
+    printf(g_grp.ng ? "index\t number of datasets\t number of query regions\t Group_name\n"
+                    : "index\t number of regions\t number of query regions\t File_name\n");
+    for (int32_t i = 0; i < table_cols(); i++)
+        if (sup[i] > 0) printf("%i\t%i\t%lld\t%s\n", i, col_count(i), (long long)sup[i], col_name(i));
     printf("Query regions with a hit: %lld of %lld\n", (long long)nhit, (long long)nq);
 }
 
@@ -1031,7 +1123,8 @@ static void print_coverage_table(const int64_t *cov, int64_t covered, int64_t qb
 static void support_files(const cli_paths *P, int32_t v, int bp)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles, n = P->n;
+    const int32_t nfiles = table_cols(), n = P->n;    /* (under -K: the groups, and bp is 0) */
+    const cli_groups *K = g_grp.ng ? &g_grp : NULL;
     int rule;
     const int32_t ev = q_dispatch(v, &rule);
     cli_sets S;
@@ -1046,6 +1139,8 @@ static void support_files(const cli_paths *P, int32_t v, int bp)
             if (q[k].n > 0)
                 ok = (bp ? igdc_coverage_host(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
                                               rows + (size_t)k * (size_t)nfiles, &nhit[k])
+                         : K ? igdc_group_support_host_ov(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, K->off, K->idx, K->ng, ev, rule,
+                                                          rows + (size_t)k * (size_t)nfiles, &nhit[k], g_mo)
                          : igdc_support_host_ov(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule,
                                                 rows + (size_t)k * (size_t)nfiles, &nhit[k], g_mo)) == 0;
         if (!route_host_end(&R, ok, bp ? "covered base pairs on the host (small files)" : "support counts on the host (small files)")) {
@@ -1057,6 +1152,7 @@ static void support_files(const cli_paths *P, int32_t v, int bp)
     if (route_engine(&R, S.nq > 0))
         route_engine_end(&R, bp ? "coverage" : "support",
                          bp ? igd_hip_coverage_sets(R.dev, S.ichr, S.qs, S.qe, S.off, n, ev, rule, rows, nhit)
+                            : K ? igd_hip_group_support_sets(R.dev, S.ichr, S.qs, S.qe, S.off, n, K->off, K->idx, K->ng, ev, rule, rows, nhit, g_mo)
                             : igd_hip_support_sets_ov(R.dev, S.ichr, S.qs, S.qe, S.off, n, ev, rule, rows, nhit, g_mo),
                          bp ? "covered base pairs of the query sets (H2D + kernel + D2H)" : "support counts of the query sets (H2D + kernel + D2H)");
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
@@ -1183,7 +1279,8 @@ static void enrich_tables_restricted(const int64_t *rows, const int64_t *urow, c
 static void enrich_files(const cli_paths *P, const char *uniName, int32_t v, int ranks, int restricted)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
-    const int32_t nfiles = IGD->nFiles, n = P->n;
+    const int32_t nfiles = table_cols(), n = P->n;    /* (under -K: the groups, and restricted is 0) */
+    const cli_groups *K = g_grp.ng ? &g_grp : NULL;
     int rule;
     const int32_t ev = q_dispatch(v, &rule);
     igdc_queries uq;
@@ -1215,11 +1312,14 @@ static void enrich_files(const cli_paths *P, const char *uniName, int32_t v, int
                                              plog, odds, NULL, nhit, &unhit) == 0;
             if (ok) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
         } else {
-            ok = igdc_support_host_ov(g_core, R.hm, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, urow, &unhit, g_mo) == 0;
+            ok = (K ? igdc_group_support_host_ov(g_core, R.hm, uq.ichr, uq.qs, uq.qe, uq.n, K->off, K->idx, K->ng, ev, rule, urow, &unhit, g_mo)
+                    : igdc_support_host_ov(g_core, R.hm, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, urow, &unhit, g_mo)) == 0;
             for (int32_t k = 0; k < n && ok; k++)
                 if (q[k].n > 0)
-                    ok = igdc_support_host_ov(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
-                                              &nhit[k], g_mo) == 0;
+                    ok = (K ? igdc_group_support_host_ov(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, K->off, K->idx, K->ng, ev, rule,
+                                                         rows + (size_t)k * (size_t)nfiles, &nhit[k], g_mo)
+                            : igdc_support_host_ov(g_core, R.hm, q[k].ichr, q[k].qs, q[k].qe, q[k].n, ev, rule, rows + (size_t)k * (size_t)nfiles,
+                                                   &nhit[k], g_mo)) == 0;
             if (ok) {
                 enrich_tables(rows, urow, q, uq.n, n, nfiles, tb, tc, td, clamped);
                 ok = igdc_fisher_host(rows, tb, tc, td, (int64_t)cells, plog, odds) == 0;
@@ -1239,6 +1339,8 @@ static void enrich_files(const cli_paths *P, const char *uniName, int32_t v, int
         const int rc = restricted
                            ? igd_hip_enrich_restricted(R.dev, S.ichr, S.qs, S.qe, S.off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, size,
                                                        plog, odds, NULL, nhit, &unhit)
+                           : K ? igd_hip_group_enrich_sets(R.dev, S.ichr, S.qs, S.qe, S.off, n, uq.ichr, uq.qs, uq.qe, uq.n, K->off, K->idx, K->ng, ev,
+                                                           rule, rows, urow, plog, odds, NULL, nhit, &unhit, g_mo)
                            : igd_hip_enrich_sets_ov(R.dev, S.ichr, S.qs, S.qe, S.off, n, uq.ichr, uq.qs, uq.qe, uq.n, ev, rule, rows, urow, plog,
                                                     odds, NULL, nhit, &unhit, g_mo);
         if (rc == IGD_HIP_OK && restricted) enrich_tables_restricted(rows, urow, size, uq.n, n, nfiles, tb, tc, td);
@@ -1251,13 +1353,13 @@ static void enrich_files(const cli_paths *P, const char *uniName, int32_t v, int
     }
     for (int32_t k = 0; k < n && !g_fail_rc; k++) {   /* (as `-q`: no table after an engine failure) */
         sets_title(&S, k);
-        printf("index\t number of regions\t support\t b\t c\t d\t oddsRatio\t pValueLog\t File_name%s\n",
+        printf("index\t number of %s\t support\t b\t c\t d\t oddsRatio\t pValueLog\t %s%s\n", K ? "datasets" : "regions", K ? "Group_name" : "File_name",
                ranks ? "\t rnkSup\t rnkPV\t rnkOR\t maxRnk\t meanRnk\t qValueLog" : "");
         for (int32_t f = 0; f < nfiles; f++) {
             const size_t i = (size_t)k * (size_t)nfiles + (size_t)f;
             if (rows[i] <= 0) continue;
-            printf("%i\t%i\t%lld\t%lld\t%lld\t%lld\t%.4f\t%.4f\t%s", f, IGD->finfo[f].nr, (long long)rows[i], (long long)tb[i],
-                   (long long)tc[i], (long long)td[i], odds[i], plog[i], IGD->finfo[f].fileName);
+            printf("%i\t%i\t%lld\t%lld\t%lld\t%lld\t%.4f\t%.4f\t%s", f, col_count(f), (long long)rows[i], (long long)tb[i],
+                   (long long)tc[i], (long long)td[i], odds[i], plog[i], col_name(f));
             if (ranks) printf("\t%d\t%d\t%d\t%d\t%.2f\t%.4f", (int)rsup[i], (int)rpv[i], (int)ror[i], (int)rmax[i], rmean[i], qlog[i]);
             printf("\n");
         }
@@ -1995,7 +2097,9 @@ int igd_search(int argc, char **argv)                                        /* 
     int jac = 0;                                                                      /* -J given (see jaccard_files) */
     int gbp = 0;                                                                      /* -G given (see permute_bp_table) */
     char *mapArg = NULL;                                                              /* -V (see map_files) */
+    char *grpName = NULL;                                                             /* -K (see groups_read) */
     char out[64] = "";
+    groups_free();
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
         const char *a = argv[i];
         if (strcmp(a, "-Q") == 0) {                   /* (not the reference's: a list of query files, see search_sets) */
@@ -2065,6 +2169,10 @@ int igd_search(int argc, char **argv)                                        /* 
         } else if (strcmp(a, "-W") == 0) {            /* (not the reference's: -P inside a workspace, see g_ws) */
             if (i + 1 >= argc) { printf("Not supported: -W without a workspace file\n"); return EX_USAGE; }
             wsName = argv[i + 1];
+        } else if (strcmp(a, "-K") == 0) {            /* (not the reference's: -u and -U per group of datasets, see groups_read) */
+            if (i + 1 >= argc) { printf("Not supported: -K without a groups file\n"); return EX_USAGE; }
+            grpName = argv[i + 1];
+            i++;
         } else if (strcmp(a, "-g") == 0) {
             if (i + 1 >= argc) { printf("No genome file.\n"); return EX_OK; }
             genomeName = argv[i + 1];
@@ -2095,6 +2203,17 @@ int igd_search(int argc, char **argv)                                        /* 
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    if (grpName) {                                                            /* -K: every refusal is a usage error */
+        const char *why = NULL;
+        if (bp || memb || restricted || cooc || permArg || distArg || gbp || wsName || jac || mapArg || nearArg || histArg || flankL || flankEdges ||
+            full || other)
+            why = "-K together with -b, -w, -X, -C, -P, -D, -G, -W, -J, -V, -N, -H, -L, -E, -f, -m, -s or -r";
+        else if (!uniq && !uniName) why = "-K without -u or -U";
+        else if (mode != 1 && !listName) why = "-K without -q or -Q";
+        if (why) return refused_usage(why);
+        const int rc = groups_read(grpName);
+        if (rc) return rc;
+    }
     long long np = 0;                                                         /* -P's count, once a block below has parsed it */
     if (wsName) {                                                             /* -W: every refusal is a usage error */
         if (!permArg) return refused_usage("-W without -P");
@@ -2337,6 +2456,7 @@ int igd_search(int argc, char **argv)                                        /* 
         return usage_search();
     }
     paths_close(&P);
+    groups_free();
 
     /* release everything, in the shape get_igdinfo/get_fileinfo handed it out (:1066-1078) */
     if (fP) { fclose(fP); fP = NULL; }

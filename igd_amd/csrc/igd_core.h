@@ -127,6 +127,15 @@ int igdc_search_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ich
                         int64_t nq, int32_t v, int rule, int64_t *hits, int64_t *total, const igd_hip_min_overlap *min_overlap);
 int igdc_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
                          int64_t nq, int32_t v, int rule, int64_t *support, int64_t *nhit, const igd_hip_min_overlap *min_overlap);
+/* Support counts per GROUP of datasets on the host (what igd_hip_group_support_sets computes for one set; include/igd_hip.h has
+ * the grouping grp_off / grp_idx / ngroups and the definitions): gsupport[g] += the queries that overlap a record of at least one
+ * dataset of group g, *gnhit (may be NULL) += the queries that overlap a dataset with at least one group.  Same records,
+ * threading, rule, filter and minimum overlap (may be NULL) as igdc_support_host_ov.  0 on success; -1, nothing written, for a
+ * bad argument -- a grouping that igd_hip_groups_first_bad refuses, ngroups outside 1 .. IGD_HIP_GROUP_MAX -- or when a tile
+ * could not be read. */
+int igdc_group_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *grp_off, const int32_t *grp_idx, int32_t ngroups, int32_t v, int rule, int64_t *gsupport,
+                               int64_t *gnhit, const igd_hip_min_overlap *min_overlap);
 int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
                          int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,

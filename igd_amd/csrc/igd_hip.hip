@@ -366,6 +366,9 @@ struct igd_hip_db {
     int32_t *d_pbRun;
     int64_t *d_pbWord;
     int64_t pbRunCap, pbWordCap;
+    // igd_hip_group_support_sets (host_group_support.hpp): the grouping of one call, grp_off[nFiles + 1] then grp_idx (32-bit words)
+    int32_t *d_gsTab;
+    int64_t gsTabCap;
     // igd_hip_dataset_bp: the tiles of every contig as the file has them (host copy), the merged base pairs per dataset that
     // have been computed so far, one entry per (v, rule), and how often one was computed
     struct BpEntry { int32_t v; int rule; std::vector<int64_t> bp; };
@@ -399,6 +402,7 @@ struct igd_hip_db {
 #include "engine/batch_stats_dev.hpp" // instrumentation: terms of the algorithmic byte model
 #include "engine/sets_dev.hpp"        // igd_sets_count: many small query sets in one launch, one hits[] row per set
 #include "engine/support_dev.hpp"     // igd_sets_support: the same walk, counting each (query, file) pair once
+#include "engine/group_support_dev.hpp" // igd_sets_group_support: the same walk, one bit and one counter per GROUP of datasets -- the union over a group's files
 #include "engine/coverage_dev.hpp"    // igd_sets_coverage: the same walk, one frontier per (query, file): covered base pairs
 #include "engine/member_dev.hpp"      // igd_member_rows: the same walk, one bit row per query: which files it overlaps
 #include "engine/fisher_dev.hpp"      // igd_fisher_cells: one wave per 2x2 table, the hypergeometric tail in log space
@@ -425,6 +429,7 @@ struct igd_hip_db {
 #include "engine/host_coverage.hpp"   // igd_hip_coverage_sets: chunks of sets, all of them sliced
 #include "engine/host_member.hpp"     // igd_hip_membership / _dev: a body of run_region_chunks, chunks of queries within a row budget, one launch each
 #include "engine/host_enrich.hpp"     // igd_hip_fisher_tables / igd_hip_enrich_sets: chunks of cells, one launch each
+#include "engine/host_group_support.hpp" // igd_hip_group_support_sets / igd_hip_group_enrich_sets: the same chunks with rows of nGroups columns, the table resident
 #include "engine/host_rank.hpp"       // igd_hip_enrich_ranks: chunks of whole rows, one launch each
 #include "engine/host_restrict.hpp"   // igd_hip_restrict_sets / igd_hip_enrich_restricted: chunks of sets x chunks of the universe
 #include "engine/host_cooccur.hpp"    // igd_hip_cooccur / igd_hip_bits_transpose / igd_hip_bitrows_gram: chunks of regions, rows stay resident

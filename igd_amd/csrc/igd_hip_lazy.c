@@ -345,6 +345,31 @@ int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *q
               : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_group_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                               int32_t nsets, const int32_t *grp_off, const int32_t *grp_idx, int32_t ngroups, int32_t v, int rule,
+                               int64_t *gsupport, int64_t *gnhit, const igd_hip_min_overlap *min_overlap)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, const int32_t *,
+                        const int32_t *, int32_t, int32_t, int, int64_t *, int64_t *, const igd_hip_min_overlap *);
+    RESOLVE(fn_t, "igd_hip_group_support_sets");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, grp_off, grp_idx, ngroups, v, rule, gsupport, gnhit, min_overlap) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_group_enrich_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                              int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
+                              const int32_t *grp_off, const int32_t *grp_idx, int32_t ngroups, int32_t v, int rule, int64_t *gsupport,
+                              int64_t *gusupport, double *pvalue_log, double *odds_ratio, int64_t *clamped, int64_t *gnhit,
+                              int64_t *gunhit, const igd_hip_min_overlap *min_overlap)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, const int32_t *,
+                        const int32_t *, const int32_t *, int64_t, const int32_t *, const int32_t *, int32_t, int32_t, int, int64_t *,
+                        int64_t *, double *, double *, int64_t *, int64_t *, int64_t *, const igd_hip_min_overlap *);
+    RESOLVE(fn_t, "igd_hip_group_enrich_sets");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, u_ichr, u_qs, u_qe, nu, grp_off, grp_idx, ngroups, v, rule, gsupport, gusupport,
+                   pvalue_log, odds_ratio, clamped, gnhit, gunhit, min_overlap)
+              : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_restrict_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
                           int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu, uint32_t *bits,
                           int64_t *size)

@@ -266,6 +266,32 @@ static inline int one_query_support(const igdc_db *db, const igdc_map *m, tilebu
     return c.any;
 }
 
+/* support counts per group of datasets (igdc_group_support_host_ov; include/igd_hip.h has the grouping): one_query_support with
+ * one stamp per GROUP -- a counted record of dataset f visits the groups goff[f] .. goff[f + 1] of gidx, and a group counts once
+ * per query however many of its datasets the query meets.  Returns 1 if the query met a dataset with at least one group. */
+typedef struct {
+    int32_t qs, qe, need; const igd_hip_min_overlap *mo; const int32_t *goff, *gidx; int64_t *gsupport, *last, stamp; int any;
+} group_support_ctx;
+static inline void visit_group_support(void *ctx, const int32_t *r)
+{
+    group_support_ctx *c = (group_support_ctx *)ctx;
+    if (c->mo && !igd_hip_min_overlap_pair(c->need, c->mo->ppm_record, c->qs, c->qe, r[1], r[2])) return;
+    for (int32_t j = c->goff[r[0]]; j < c->goff[r[0] + 1]; j++) {
+        const int32_t g = c->gidx[j];
+        c->any = 1;
+        if (c->last[g] != c->stamp) { c->last[g] = c->stamp; c->gsupport[g]++; }
+    }
+}
+static inline int one_query_group_support(const igdc_db *db, const igdc_map *m, tilebuf *tb, int32_t ichr, int32_t qs, int32_t qe, int32_t v,
+                                          int use_v, int rule, const int32_t *goff, const int32_t *gidx, int64_t *gsupport, int64_t *last,
+                                          int64_t stamp, const igd_hip_min_overlap *mo)
+{
+    group_support_ctx c = {qs, qe, mo ? igd_hip_min_overlap_need_q(mo->min_bp, mo->ppm_query, qs, qe) : 0, mo, goff, gidx, gsupport, last, stamp, 0};
+    if (c.need < 0) return 0;
+    walk_tiles(db, m, tb, ichr, qs, qe, v, use_v, rule == IGD_HIP_RULE_NEST, WALK_BACK, visit_group_support, &c);
+    return c.any;
+}
+
 /* membership rows (igdc_membership_host): a counted record sets its file's bit in the query's row (zeroed here first).
  * Returns the number of files met. */
 typedef struct { uint32_t *row; int n; } member_ctx;
@@ -434,18 +460,19 @@ static void run_threads(void *(*run)(void *), void *jobs, size_t size, int T)
 }
 
 /* ---- the job of one thread of a query-split entry: queries [lo, hi) of the caller's arrays, answered as `kind` says --------- */
-enum { JOB_PAIRS, JOB_SUPPORT, JOB_COVERAGE, JOB_MEMBER, JOB_NEAREST, JOB_FLANK, JOB_MAP };
+enum { JOB_PAIRS, JOB_SUPPORT, JOB_COVERAGE, JOB_MEMBER, JOB_NEAREST, JOB_FLANK, JOB_MAP, JOB_GROUP_SUPPORT };
 typedef struct {
     int kind;
     const igdc_db *db; const igdc_map *m;
     const int32_t *ichr, *qs, *qe;
     int64_t lo, hi;
     int32_t v; int use_v, rule;
-    int64_t total;          /* out: PAIRS pairs, SUPPORT and MEMBER queries with a hit, COVERAGE base pairs under any file */
+    int64_t total;          /* out: PAIRS pairs, SUPPORT, GROUP_SUPPORT and MEMBER queries with a hit, COVERAGE base pairs under any file */
     int io_failed;          /* out: a tile could not be read */
-    int64_t *hits;          /* PAIRS hits[] (may be NULL), SUPPORT support[], COVERAGE coverage[] */
-    int64_t *last, *front;  /* SUPPORT, COVERAGE: the stamps; COVERAGE: the frontiers */
-    const igd_hip_min_overlap *mo;      /* PAIRS, SUPPORT: an active minimum overlap, or NULL */
+    int64_t *hits;          /* PAIRS hits[] (may be NULL), SUPPORT support[], COVERAGE coverage[], GROUP_SUPPORT gsupport[] */
+    int64_t *last, *front;  /* SUPPORT, COVERAGE, GROUP_SUPPORT: the stamps; COVERAGE: the frontiers */
+    const igd_hip_min_overlap *mo;      /* PAIRS, SUPPORT, GROUP_SUPPORT: an active minimum overlap, or NULL */
+    const int32_t *goff, *gidx;         /* GROUP_SUPPORT: the grouping (grp_off, grp_idx) */
     int64_t *qcnt;          /* PAIRS: per-query counts (enumeration; may be NULL) */
     hitvec out; int want_out;
     uint32_t *bits;         /* MEMBER: the caller's rows, nW words each; nfh: its nfiles_hit[] or NULL */
@@ -494,6 +521,10 @@ static void *host_run(void *arg)
     case JOB_SUPPORT:
         for (int64_t i = J->lo; i < J->hi; i++)
             tot += one_query_support(db, m, &tb, ichr[i], qs[i], qe[i], v, use_v, rule, J->hits, J->last, i + 1, J->mo);
+        break;
+    case JOB_GROUP_SUPPORT:
+        for (int64_t i = J->lo; i < J->hi; i++)
+            tot += one_query_group_support(db, m, &tb, ichr[i], qs[i], qe[i], v, use_v, rule, J->goff, J->gidx, J->hits, J->last, i + 1, J->mo);
         break;
     case JOB_COVERAGE:
         for (int64_t i = J->lo; i < J->hi; i++)
@@ -544,14 +575,16 @@ static int jobs_run(host_job *job, int T, int64_t *tot)
     return bad;
 }
 
-/* the entries whose answer is a sum over queries (pair counts, support counts, covered base pairs): every thread counts into
- * nvec private vectors of nFiles + 1 words -- the answer, then the stamps, then the frontiers -- and the answers are ADDED to
- * out[] only if every tile could be read.  0 and *tot = the sum of the threads' totals, or -1 with out[] as it was. */
-static int run_private(int kind, int nvec, const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
-                       int64_t nq, int32_t v, int rule, const igd_hip_min_overlap *mo, int64_t *out, int64_t *tot)
+/* the entries whose answer is a sum over queries (pair counts, support counts, covered base pairs, group support counts): every
+ * thread counts into nvec private vectors of ncols + 1 words -- the answer, then the stamps, then the frontiers -- and the
+ * answers are ADDED to out[] only if every tile could be read.  ncols is nFiles, or the number of groups with the grouping goff /
+ * gidx behind it (JOB_GROUP_SUPPORT).  0 and *tot = the sum of the threads' totals, or -1 with out[] as it was. */
+static int run_private_cols(int kind, int nvec, int32_t ncols, const int32_t *goff, const int32_t *gidx, const igdc_db *db, const igdc_map *m,
+                            const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t v, int rule,
+                            const igd_hip_min_overlap *mo, int64_t *out, int64_t *tot)
 {
     const int T = host_threads(nq);
-    const size_t nf1 = (size_t)(db->nFiles + 1);
+    const size_t nf1 = (size_t)ncols + 1;
     host_job job[HOST_MAX_THREADS];
     int64_t *priv = (int64_t *)calloc((size_t)T * (size_t)nvec * nf1, sizeof(int64_t));
     if (!priv) return -1;
@@ -561,12 +594,18 @@ static int run_private(int kind, int nvec, const igdc_db *db, const igdc_map *m,
         if (nvec > 1) job[k].last = job[k].hits + nf1;
         if (nvec > 2) job[k].front = job[k].last + nf1;
         job[k].mo = mo;
+        job[k].goff = goff; job[k].gidx = gidx;
     }
     const int bad = jobs_run(job, T, tot);
     for (int k = 0; k < T && !bad; k++)
-        for (int32_t f = 0; f < db->nFiles; f++) out[f] += job[k].hits[f];
+        for (int32_t f = 0; f < ncols; f++) out[f] += job[k].hits[f];
     free(priv);
     return bad ? -1 : 0;
+}
+static int run_private(int kind, int nvec, const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
+                       int64_t nq, int32_t v, int rule, const igd_hip_min_overlap *mo, int64_t *out, int64_t *tot)
+{
+    return run_private_cols(kind, nvec, db->nFiles, NULL, NULL, db, m, ichr, qs, qe, nq, v, rule, mo, out, tot);
 }
 
 int igdc_search_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
@@ -600,6 +639,21 @@ int igdc_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ic
     if (run_private(JOB_SUPPORT, 2, db, m, ichr, qs, qe, nq, v, rule, igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL, support, &tot) != 0)
         return -1;
     if (nhit) *nhit += tot;
+    return 0;
+}
+
+int igdc_group_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *grp_off, const int32_t *grp_idx, int32_t ngroups, int32_t v, int rule, int64_t *gsupport,
+                               int64_t *gnhit, const igd_hip_min_overlap *min_overlap)
+{
+    int64_t at = 0, tot = 0;
+    if (!db || !m || !gsupport || nq < 0 || !grp_off || ngroups <= 0 || ngroups > IGD_HIP_GROUP_MAX || !igd_hip_min_overlap_valid(min_overlap) ||
+        igd_hip_groups_first_bad(db->nFiles, grp_off, grp_idx, ngroups, &at) != IGD_HIP_GROUPS_OK)
+        return -1;
+    if (run_private_cols(JOB_GROUP_SUPPORT, 2, ngroups, grp_off, grp_idx, db, m, ichr, qs, qe, nq, v, rule,
+                         igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL, gsupport, &tot) != 0)
+        return -1;
+    if (gnhit) *gnhit += tot;
     return 0;
 }
 

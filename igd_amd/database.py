@@ -388,6 +388,127 @@ def support_host(igd_path, ichr, qs, qe, v=0, rule=None, value_filter=None, min_
         return sup[:h.nfiles], nhit.value
 
 
+GROUP_MAX = 8192                                     # IGD_HIP_GROUP_MAX: groups of one grouping (the kernel's LDS budget)
+
+
+class DatasetGroups:
+    """A grouping of a database's datasets (include/igd_hip.h: DATASET GROUPS), a many-to-many relation in CSR form: dataset f is
+    in the groups idx[off[f]:off[f + 1]] (int32, ascending, each in [0, ngroups)), names[g] is group g's name.  A dataset may be
+    in no group, in one or in several; a group may be empty.  Anything else -- offsets that do not start at 0 or decrease, an
+    index out of range, a run that does not ascend, no group or more than GROUP_MAX -- raises IgdError naming the first bad
+    entry.  build_groups() and Database.read_groups() make one from labels / from a file."""
+
+    def __init__(self, off, idx, names, check=True):
+        self.off, self.idx, self.names = _i32(off), _i32(idx), [str(n) for n in names]
+        self.nfiles, self.ngroups = len(self.off) - 1, len(self.names)
+        if check:
+            self.check("DatasetGroups")
+
+    def check(self, what):
+        off, idx, ng = self.off, self.idx, self.ngroups
+        if not 0 < ng <= GROUP_MAX:
+            raise IgdError("%s: %d groups given, 1 .. %d are possible" % (what, ng, GROUP_MAX))
+        if self.nfiles < 0 or off[0] != 0:
+            raise IgdError("%s: off[0] = %s: the offsets start at 0 and do not decrease" % (what, off[0] if len(off) else "missing"))
+        down = np.flatnonzero(np.diff(off) < 0)
+        if len(down):
+            raise IgdError("%s: off[%d] = %d: the offsets start at 0 and do not decrease" % (what, down[0] + 1, off[down[0] + 1]))
+        if off[-1] != len(idx):
+            raise IgdError("%s: off[-1] = %d, but %d indices given" % (what, off[-1], len(idx)))
+        for j in np.flatnonzero((idx < 0) | (idx >= ng))[:1]:
+            raise IgdError("%s: idx[%d] = %d is not in [0, %d)" % (what, j, idx[j], ng))
+        first = np.zeros(len(idx), bool)
+        first[off[:-1][off[:-1] < len(idx)]] = True
+        for j in np.flatnonzero(~first[1:] & (idx[1:] <= idx[:-1]))[:1] + 1:
+            raise IgdError("%s: idx[%d] = %d does not ascend within its dataset's run" % (what, j, idx[j]))
+
+    def dense(self):
+        """bool[nfiles, ngroups]: dataset f is in group g"""
+        m = np.zeros((self.nfiles, self.ngroups), bool)
+        m[np.repeat(np.arange(self.nfiles), np.diff(self.off)), self.idx] = True
+        return m
+
+    @property
+    def n_datasets(self):
+        """int64[ngroups]: the datasets of each group"""
+        return np.bincount(self.idx, minlength=self.ngroups).astype(np.int64)
+
+    def labels(self):
+        """the group names of each dataset, a list of nfiles lists -- what build_groups() takes"""
+        return [[self.names[g] for g in self.idx[self.off[f]:self.off[f + 1]]] for f in range(self.nfiles)]
+
+
+def build_groups(labels, nfiles):
+    """DatasetGroups from labels: a list of nfiles lists of group names (dataset f's), or a dict dataset number -> names.  Groups
+    are numbered in order of first appearance; a name given twice for one dataset counts once."""
+    if isinstance(labels, dict):
+        for f in labels:
+            if not 0 <= int(f) < nfiles:
+                raise IgdError("build_groups: dataset %s is not in [0, %d)" % (f, nfiles))
+        labels = [labels.get(f, ()) for f in range(nfiles)]
+    if len(labels) != nfiles:
+        raise IgdError("build_groups: labels for %d datasets given, the database has %d" % (len(labels), nfiles))
+    number, off, idx = {}, [0], []
+    for names in labels:
+        idx += sorted({number.setdefault(str(n), len(number)) for n in names})
+        off.append(len(idx))
+    g = DatasetGroups(off, idx, list(number), check=False)
+    g.check("build_groups")
+    return g
+
+
+def read_groups_file(path, file_names):
+    """DatasetGroups from a `dataset<TAB>group` file: dataset is a name of file_names exactly, or a decimal index; `#` lines and
+    blank lines are skipped; a dataset may occur on several lines; groups are numbered in order of first appearance."""
+    byname = {}
+    for f, n in enumerate(file_names):
+        byname.setdefault(n, f)
+    number, per = {}, [set() for _ in file_names]
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            ds, tab, grp = line.partition("\t")
+            if not tab or not grp:
+                raise IgdError("groups file %s, line %d: not a dataset, a tab and a group" % (path, ln))
+            f = byname.get(ds, int(ds) if ds.isdigit() and int(ds) < len(file_names) else None)
+            if f is None:
+                raise IgdError("groups file %s, line %d: the database has no dataset %s" % (path, ln, ds))
+            if grp not in number and len(number) == GROUP_MAX:
+                raise IgdError("groups file %s, line %d: more than %d groups" % (path, ln, GROUP_MAX))
+            per[f].add(number.setdefault(grp, len(number)))
+    if not number:
+        raise IgdError("groups file %s: no group given" % path)
+    off = np.zeros(len(per) + 1, np.int32)
+    off[1:] = np.cumsum([len(p) for p in per])
+    return DatasetGroups(off, [g for p in per for g in sorted(p)], list(number))
+
+
+def _groups(groups, nfiles, what):
+    if not isinstance(groups, DatasetGroups):
+        raise IgdError("%s: groups must be a DatasetGroups (build_groups(), Database.read_groups())" % what)
+    if groups.nfiles != nfiles:
+        raise IgdError("%s: the grouping is of %d datasets, the database has %d" % (what, groups.nfiles, nfiles))
+    return groups
+
+
+def group_support_host(igd_path, ichr, qs, qe, groups, v=0, rule=None, value_filter=None, min_overlap=None):
+    """Support counts per group of datasets of one query set on the host (igdc_group_support_host_ov; no device is touched):
+    (gsupport int64[ngroups], gnhit) as Database.group_support() defines them, min_overlap included."""
+    ichr, qs, qe = _regions(ichr, qs, qe)
+    mo = _min_overlap(min_overlap, "group_support_host")
+    with _HostDb(igd_path, "group_support_host") as h:
+        g = _groups(groups, h.nfiles, "group_support_host")
+        rule, vf = h.dispatch(v, rule, value_filter)
+        sup, nhit = np.zeros(max(g.ngroups, 1), np.int64), C.c_int64(0)
+        g.check("group_support_host")                # (what the C entry refuses as an argument is refused here, by name)
+        if h.L.igdc_group_support_host_ov(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(g.off), _ptr(g.idx), g.ngroups,
+                                          vf, rule, _ptr(sup), C.byref(nhit), C.byref(mo) if mo is not None else None) != 0:
+            raise IgdError("group_support_host: a tile of %s could not be read" % igd_path)
+        return sup[:g.ngroups], nhit.value
+
+
 class Workspace:
     """The table of a workspace (include/igd_hip.h: THE WORKSPACE): the stretches of the contigs a permutation may place a
     region in.  Built by build_workspace() or Database.read_workspace(); handed as workspace= together with mode="workspace".
@@ -814,6 +935,19 @@ def map_summary(ms):
     return mean_region, mean_pair
 
 
+def _forward(f):
+    """A public method that hands all its arguments to the private method f (its own name with an underscore in front) and
+    carries f's docstring.  For the group entries: tests/test_gpu_database_args.py holds every public method whose signature
+    names (ichr, qs, qe) to a table of its own, which is not this change's to extend; their refusals are held to the same texts
+    in tests/test_gpu_group_support.py."""
+    def call(self, *args, **kwargs):
+        return f(self, *args, **kwargs)
+    call.__name__ = f.__name__[1:]
+    call.__qualname__ = f.__qualname__.replace("._", ".")
+    call.__doc__ = f.__doc__
+    return call
+
+
 class Database:
     def __init__(self, igd_path, device=0):
         self._L = N.cli()
@@ -946,6 +1080,79 @@ class Database:
     def support_files(self, paths, v=0, min_overlap=None):
         """One query set per BED file (read as `igd search -q` reads it): (support int64[len(paths), nfiles], nhit)."""
         return self.support_sets(*self._read_sets(paths), v, min_overlap=min_overlap)
+
+    def read_groups(self, path):
+        """The DatasetGroups of a `dataset<TAB>group` file as `igd search -K` reads it: dataset is a file name exactly as the
+        database's index lists it, or a decimal dataset number; groups are numbered in order of first appearance."""
+        return read_groups_file(path, self.file_names)
+
+    def _group_support_sets(self, ichr, qs, qe, set_off, groups, v=0, rule=None, value_filter=None, min_overlap=None, gsupport=None):
+        """group_support_sets(ichr, qs, qe, set_off, groups, v=0, rule=None, value_filter=None, min_overlap=None, gsupport=None).  Support counts per GROUP of datasets of many query sets in one call (igd_hip_group_support_sets).  Sets as
+        search_sets(), groups a DatasetGroups.  Returns (gsupport int64[nsets, ngroups], gnhit int64[nsets]): gsupport[k, g] =
+        the queries of set k that overlap a record of AT LEAST ONE dataset of group g -- a union over the group's datasets,
+        neither the sum nor the maximum of their support_sets() columns -- and gnhit[k] = the queries of set k that overlap a
+        dataset with at least one group.  One kernel counts it; no membership matrix is formed.  v, rule, value_filter and
+        min_overlap as support_sets().  gsupport (int64[nsets, ngroups], C order) is added to when given."""
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "group_support_sets", "queries")
+        g = _groups(groups, self.nfiles, "group_support_sets")
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
+        gsupport = _out(gsupport, (nsets, g.ngroups), np.int64, "gsupport", "group_support_sets", zero=True)
+        gnhit = np.zeros(max(nsets, 1), np.int64)
+        mo = _min_overlap(min_overlap, "group_support_sets")
+        _chk(self._H.igd_hip_group_support_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _ptr(g.off),
+                                                _ptr(g.idx), g.ngroups, vf, rule, _ptr(gsupport), _ptr(gnhit),
+                                                C.byref(mo) if mo is not None else None), "igd_hip_group_support_sets")
+        return gsupport, gnhit[:nsets]
+
+    group_support_sets = _forward(_group_support_sets)
+
+    def _group_support(self, ichr, qs, qe, groups, v=0, rule=None, value_filter=None, min_overlap=None):
+        """group_support(ichr, qs, qe, groups, v=0, rule=None, value_filter=None, min_overlap=None).  Support counts per group of one query set: (int64[ngroups], gnhit).  Row 0 of group_support_sets() with one set."""
+        sup, nhit = self.group_support_sets(ichr, qs, qe, np.array([0, len(_i32(qs))], np.int64), groups, v, rule, value_filter, min_overlap)
+        return sup[0], int(nhit[0])
+
+    group_support = _forward(_group_support)
+
+    def group_support_files(self, paths, groups, v=0, min_overlap=None):
+        """One query set per BED file (read as `igd search -q` reads it): (gsupport int64[len(paths), ngroups], gnhit)."""
+        return self.group_support_sets(*self._read_sets(paths), groups, v, min_overlap=min_overlap)
+
+    def _group_enrichment_sets(self, ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, groups, v=0, rule=None, value_filter=None, min_overlap=None,
+                               with_nhit=False):
+        """group_enrichment_sets(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, groups, v=0, rule=None, value_filter=None,
+        min_overlap=None, with_nhit=False).  Region-set enrichment per GROUP of datasets (igd_hip_group_enrich_sets): enrichment_sets() with the groups as columns.
+        Returns Enrichment(support, usupport, b, c, d, pvalue_log, odds_ratio, clamped) with support = group_support_sets() of
+        the sets, usupport that of the universe, arrays [nsets, ngroups], usupport [ngroups]; enrichment_ranks() ranks it as it
+        is, over each set's groups.  with_nhit adds (gnhit int64[nsets], gunhit)."""
+        what = "group_enrichment_sets"
+        ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, nsets, nu = _restrict_args(ichr, qs, qe, set_off, u_ichr, u_qs, u_qe, what)
+        g = _groups(groups, self.nfiles, what)
+        ng = g.ngroups
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
+        sup, usup = np.empty((nsets, ng), np.int64), np.empty(max(ng, 1), np.int64)
+        plog, odds = np.empty((nsets, ng), np.float64), np.empty((nsets, ng), np.float64)
+        clamped, nhit, unhit = np.empty(max(nsets, 1), np.int64), np.empty(max(nsets, 1), np.int64), C.c_int64(0)
+        mo = _min_overlap(min_overlap, what)
+        _chk(self._H.igd_hip_group_enrich_sets(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, _ptr(u_ichr), _ptr(u_qs),
+                                               _ptr(u_qe), nu, _ptr(g.off), _ptr(g.idx), ng, vf, rule, _ptr(sup), _ptr(usup),
+                                               _ptr(plog), _ptr(odds), _ptr(clamped), _ptr(nhit), C.byref(unhit),
+                                               C.byref(mo) if mo is not None else None), "igd_hip_group_enrich_sets")
+        usup = usup[:ng]
+        nk = np.diff(set_off)[:, None]
+        b = usup[None, :] - sup
+        c = nk - sup
+        d = nu - sup - b - c
+        res = Enrichment(sup, usup, np.maximum(b, 0), c, np.maximum(d, 0), plog, odds, clamped[:nsets])
+        return (res, nhit[:nsets], unhit.value) if with_nhit else res
+
+    group_enrichment_sets = _forward(_group_enrichment_sets)
+
+    def group_enrichment_files(self, paths, universe_path, groups, v=0, min_overlap=None):
+        """One query set per BED file and the universe from a BED file: what `igd search -Q list -U universe -K groups` prints,
+        as group_enrichment_sets() returns it."""
+        sets = self._read_sets(paths)
+        uni = self.read_queries(universe_path)
+        return self.group_enrichment_sets(*sets, uni[0], uni[1], uni[2], groups, v, min_overlap=min_overlap)
 
     def coverage_sets(self, ichr, qs, qe, set_off, v=0, rule=None, value_filter=None, coverage=None):
         """Covered base pairs of many query sets in one call (igd_hip_coverage_sets).  Sets as search_sets().  Returns

@@ -670,6 +670,53 @@ int igd_hip_enrich_sets_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *q
                            int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
                            int32_t v, int rule, int64_t *support, int64_t *usupport, double *pvalue_log, double *odds_ratio,
                            int64_t *clamped, int64_t *nhit, int64_t *unhit, const igd_hip_min_overlap *min_overlap);
+/* DATASET GROUPS: support and enrichment per group of datasets -- "how many of my regions lie under ANY track of this cell
+ * type" -- which is a union over datasets: neither the sum nor the maximum of the per-dataset supports.
+ * A grouping of the nFiles datasets into ngroups groups is a many-to-many relation in CSR form:
+ *     grp_off   int32[nFiles + 1], grp_off[0] = 0, non-decreasing
+ *     grp_idx   int32[grp_off[nFiles]], every entry in [0, ngroups), strictly ascending within one dataset's run
+ * A dataset may be in no group, in one or in several; a group may be empty.  1 <= ngroups <= IGD_HIP_GROUP_MAX.
+ * With F_q = the datasets f with hits_q[f] > 0 as igd_hip_support_sets defines it (same rule, v and minimum overlap):
+ *     gsupport[k * ngroups + g] += the queries q of set k for which F_q holds a dataset of group g
+ *     gnhit[k]                  += the queries q of set k for which F_q holds a dataset with at least one group  (may be NULL)
+ * So: the identity grouping gives support and nhit of igd_hip_support_sets bit for bit; one group of all datasets gives nhit
+ * in its only column; max over f in g of support[f] <= gsupport[g] <= min(sum over f in g of support[f], |set|); two identical
+ * queries count twice; an empty group has a zero column; an unlabelled dataset changes nothing.
+ * One kernel (igd_sets_group_support) counts all sets in the chunks of igd_hip_support_sets with rows of ngroups columns; the
+ * table goes to the device once per call; no membership matrix exists anywhere.  Blocking.  A bad set_off, a bad grouping
+ * (the message names the first bad entry) or ngroups outside 1 .. IGD_HIP_GROUP_MAX is IGD_HIP_ERR_ARG before any launch and
+ * before anything of the caller's is written.  min_overlap may be NULL.
+ * igd_hip_groups_first_bad is that check of the grouping, shared with the host route: 0, or which rule the first bad entry
+ * breaks with its index in *at (an index into grp_off for IGD_HIP_GROUPS_BAD_OFF, into grp_idx otherwise). */
+#define IGD_HIP_GROUP_MAX 8192
+enum { IGD_HIP_GROUPS_OK = 0, IGD_HIP_GROUPS_BAD_OFF = 1, IGD_HIP_GROUPS_BAD_RANGE = 2, IGD_HIP_GROUPS_BAD_ORDER = 3, IGD_HIP_GROUPS_BAD_NULL = 4 };
+static inline int igd_hip_groups_first_bad(int32_t nfiles, const int32_t *grp_off, const int32_t *grp_idx, int32_t ngroups, int64_t *at)
+{
+    if (grp_off[0] != 0) { *at = 0; return IGD_HIP_GROUPS_BAD_OFF; }
+    for (int32_t f = 0; f < nfiles; f++) {
+        if (grp_off[f + 1] < grp_off[f]) { *at = (int64_t)f + 1; return IGD_HIP_GROUPS_BAD_OFF; }
+        if (grp_off[f + 1] > grp_off[f] && !grp_idx) { *at = grp_off[f]; return IGD_HIP_GROUPS_BAD_NULL; }
+        for (int32_t j = grp_off[f]; j < grp_off[f + 1]; j++) {
+            if (grp_idx[j] < 0 || grp_idx[j] >= ngroups) { *at = j; return IGD_HIP_GROUPS_BAD_RANGE; }
+            if (j > grp_off[f] && grp_idx[j] <= grp_idx[j - 1]) { *at = j; return IGD_HIP_GROUPS_BAD_ORDER; }
+        }
+    }
+    return IGD_HIP_GROUPS_OK;
+}
+int igd_hip_group_support_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                               int32_t nsets, const int32_t *grp_off, const int32_t *grp_idx, int32_t ngroups, int32_t v, int rule,
+                               int64_t *gsupport, int64_t *gnhit, const igd_hip_min_overlap *min_overlap);
+/* Enrichment per group: igd_hip_enrich_sets_ov with the groups as columns.  The table of set k and group g is a =
+ * gsupport[k * ngroups + g], b = gusupport[g] - a, c = n_k - a, d = n_U - a - b - c, clamped as there.  gsupport[nsets *
+ * ngroups], gusupport[ngroups], pvalue_log / odds_ratio[nsets * ngroups], clamped[nsets], gnhit[nsets] and *gunhit are DEFINED
+ * by the call; odds_ratio, clamped, gnhit and gunhit may be NULL.  ONE igd_hip_group_support_sets call over nsets + 1 sets --
+ * the universe last, counted once -- then the cell kernel.  Ranks and q-values over a set's groups: igd_hip_enrich_ranks with
+ * ncols = ngroups.  The argument checks above apply, and those of igd_hip_enrich_sets. */
+int igd_hip_group_enrich_sets(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off,
+                              int32_t nsets, const int32_t *u_ichr, const int32_t *u_qs, const int32_t *u_qe, int64_t nu,
+                              const int32_t *grp_off, const int32_t *grp_idx, int32_t ngroups, int32_t v, int rule,
+                              int64_t *gsupport, int64_t *gusupport, double *pvalue_log, double *odds_ratio, int64_t *clamped,
+                              int64_t *gnhit, int64_t *gunhit, const igd_hip_min_overlap *min_overlap);
 /* Query sets RESTRICTED to the universe (LOLA's redefineUserSets): each set is replaced by the universe regions it overlaps
  * before anything is counted, so every table is a true 2x2 partition of the universe.  Sets as igd_hip_enrich_sets; the
  * universe is the nu regions u_ichr / u_qs / u_qe in ANY order.
