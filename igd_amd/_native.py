@@ -319,6 +319,9 @@ def hip():
         L.igd_hip_scan_kernel_name.restype = C.c_char_p
         L.igd_hip_last_scan_kernel.restype = C.c_char_p
         L.igd_hip_last_scan_kernel.argtypes = [C.c_void_p]
+        # TEST-ONLY: db, out int64[n], n -> words filled
+        L.igd_hip_last_batch_routes.argtypes = [C.c_void_p, i64p, C.c_int]
+        L.igd_hip_route_constants.argtypes = [C.c_void_p, i64p, C.c_int]
         L.igd_hip_seqpare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
         L.igd_hip_create.argtypes = [C.POINTER(HipCreateDesc), C.c_int, C.POINTER(HipCreated)]
         L.igd_hip_created_free.argtypes = [C.POINTER(HipCreated)]

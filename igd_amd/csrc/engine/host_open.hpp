@@ -117,6 +117,61 @@ extern "C" const char *igd_hip_last_scan_kernel(igd_hip_db *db)
     return db->lastPacked ? "igd_scan_sorted" : "igd_scan_tiles";
 }
 
+// TEST-ONLY: which routes the last batch of `db` took (include/igd_hip.h: IGD_HIP_ROUTE_*), from the handle and the control
+// words of the batch's parity.  Waits for the batch, like igd_hip_last_scan_kernel.  The list counters of a batch's parity are
+// zeroed by the batch BEFORE it and only read by its own last launch, so they stand until the next batch starts.
+extern "C" int igd_hip_last_batch_routes(igd_hip_db *db, int64_t *out, int n)
+{
+    if (db && db->inner) return igd_hip_last_batch_routes(db->inner, out, n);
+    if (!db || !out || n <= 0 || db->epoch == 0) return 0;
+    // the kernel is the one igd_hip_last_scan_kernel names (which also waits for the batch): one rule, kept there
+    const char *name = igd_hip_last_scan_kernel(db);
+    const int kernel = !strcmp(name, "igd_scan_sorted") ? 1 : !strcmp(name, "igd_scan_tiles") ? 2 : !strcmp(name, "igd_scan_direct") ? 3 : 0;
+    int32_t ctl[IGD_CTL_WORDS];
+    if (kernel == 0 || hipMemcpy(ctl, db->d_ctl, sizeof ctl, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    const int par = db->epoch & 1;
+    const bool uns = db->lastMode != 2 && ctl[CTL_UNSORTED] == db->epoch;
+    int64_t w[IGD_HIP_ROUTE_WORDS];
+    w[IGD_HIP_ROUTE_KERNEL] = kernel;
+    w[IGD_HIP_ROUTE_FULL] = kernel == 1 ? db->lastRank : -1;
+    w[IGD_HIP_ROUTE_PACKED] = db->lastPacked;
+    w[IGD_HIP_ROUTE_LBSHIFT] = db->lastMode != 2 ? db->lbShift : 0;
+    w[IGD_HIP_ROUTE_NFIX] = ctl[CTL_NFIX + par];
+    w[IGD_HIP_ROUTE_NLONG] = ctl[CTL_NLONG + par];
+    w[IGD_HIP_ROUTE_NHEAVYS] = ctl[CTL_NHEAVYS + par];
+    w[IGD_HIP_ROUTE_NHEAVY] = ctl[CTL_NHEAVY + par];
+    w[IGD_HIP_ROUTE_NFAR] = ctl[CTL_NFAR + par];
+    w[IGD_HIP_ROUTE_COV_SORTED] = ctl[CTL_COV + 0 * 2 + par] == db->epoch ? 1 : 0;
+    w[IGD_HIP_ROUTE_COV_BUCKET] = ctl[CTL_COV + 1 * 2 + par] == db->epoch ? 1 : 0;
+    w[IGD_HIP_ROUTE_UNSORTED] = uns ? 1 : 0;
+    w[IGD_HIP_ROUTE_NOTSTART] = db->lastMode != 2 && ctl[CTL_NOTSTART] == db->epoch ? 1 : 0;
+    const int m = n < IGD_HIP_ROUTE_WORDS ? n : IGD_HIP_ROUTE_WORDS;
+    for (int k = 0; k < m; k++) out[k] = w[k];
+    return m;
+}
+
+// TEST-ONLY: the constants the route tests derive their shapes from (include/igd_hip.h: IGD_HIP_RCONST_*).  No device access.
+extern "C" int igd_hip_route_constants(igd_hip_db *db, int64_t *out, int n)
+{
+    if (db && db->inner) return igd_hip_route_constants(db->inner, out, n);
+    if (!db || !out || n <= 0) return 0;
+    int64_t w[IGD_HIP_RCONST_WORDS];
+    w[IGD_HIP_RCONST_UNIT] = IGD_CHUNK;
+    w[IGD_HIP_RCONST_ROUND] = IGD_ROUND;
+    w[IGD_HIP_RCONST_SHORT_TILES] = IGD_SHORT_TILES;
+    w[IGD_HIP_RCONST_DENSE_MIN] = IGD_DENSE_MIN;
+    w[IGD_HIP_RCONST_LEAN_FIRST] = IGD_LEAN_FIRST;
+    w[IGD_HIP_RCONST_HEAVY_FIRST] = IGD_HEAVY_FIRST;
+    w[IGD_HIP_RCONST_HEAVY_SLICE] = IGD_HEAVY_SLICE;
+    w[IGD_HIP_RCONST_FAR_WIDE] = IGD_FAR_WIDE;
+    w[IGD_HIP_RCONST_LATER_MAX] = IGD_WAVE;               // later_range: more candidates than this do not come with the records
+    w[IGD_HIP_RCONST_SBCAP] = db->sbCap;
+    w[IGD_HIP_RCONST_LEAN_WAVES] = (int64_t)db->grid * (IGD_WG_LEAN / IGD_WAVE);
+    const int m = n < IGD_HIP_RCONST_WORDS ? n : IGD_HIP_RCONST_WORDS;
+    for (int k = 0; k < m; k++) out[k] = w[k];
+    return m;
+}
+
 static double wall_s(void)
 {
     struct timespec t;

@@ -255,6 +255,7 @@ struct igd_hip_db {
     int32_t *d_laterHdr;         // laterHdr[]: int2 per later block (entries, last tile covered as a later tile)
     int lbShift;                  // log2(queries per later block) of the batch in flight
     int lastMode, lastPacked;     // of the last batch (igd_hip_last_scan_kernel)
+    int lastRank;                 // build of igd_scan_sorted the last batch launched: 0 lean, 1 full (igd_hip_last_batch_routes)
     int forceRank;                // IGD_HIP_RANK at open (tests): 0 lean build, 1 full build, -1 the engine decides
     int forceDirect;              // IGD_HIP_DIRECT at open (tests): 1 every batch under IGD_HIP_FLAG_SORTED that can takes the DIRECT step, 0 none, -1 the engine decides
     int4 *d_tileD;                // DbView::tileD

@@ -680,3 +680,20 @@ int igd_hip_group_search(igd_hip_group *g, const int32_t *ichr, const int32_t *q
     RESOLVE(fn_t, "igd_hip_group_search");
     return fn ? fn(g, ichr, qs, qe, nq, v, rule, flags, hits, total) : IGD_HIP_ERR_DEVICE;
 }
+
+/* TEST-ONLY accessors (include/igd_hip.h): a caller that links a host flavour reads the last batch's routes through these */
+int igd_hip_last_batch_routes(igd_hip_db *db, int64_t *out, int n)
+{
+    typedef int (*fn_t)(igd_hip_db *, int64_t *, int);
+    if (!db) return 0;
+    RESOLVE(fn_t, "igd_hip_last_batch_routes");
+    return fn ? fn(db, out, n) : 0;
+}
+
+int igd_hip_route_constants(igd_hip_db *db, int64_t *out, int n)
+{
+    typedef int (*fn_t)(igd_hip_db *, int64_t *, int);
+    if (!db) return 0;
+    RESOLVE(fn_t, "igd_hip_route_constants");
+    return fn ? fn(db, out, n) : 0;
+}

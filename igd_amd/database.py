@@ -1915,6 +1915,32 @@ class Database:
         """Name of the scan kernel the last batch ran on ("igd_scan_sorted" / "igd_scan_tiles"); waits for it."""
         return (self._H.igd_hip_last_scan_kernel(self.dev) or b"").decode()
 
+    ROUTE_WORDS = ("kernel", "full", "packed", "lb_shift", "nfix", "nlong", "nheavys", "nheavy", "nfar", "cov_sorted",
+                   "cov_bucket", "unsorted", "notstart")
+    ROUTE_CONSTANTS = ("unit", "round", "short_tiles", "dense_min", "lean_first", "heavy_first", "heavy_slice", "far_wide",
+                       "later_max", "sbcap", "lean_waves")
+
+    def last_batch_routes(self):
+        """TEST-ONLY (igd_hip_last_batch_routes): dict of the route words of the last batch, {} before the first; waits for it.
+        kernel is the name last_scan_kernel() gives."""
+        w = (C.c_int64 * len(self.ROUTE_WORDS))()
+        n = self._H.igd_hip_last_batch_routes(self.dev, w, len(w))
+        if n == 0:
+            return {}
+        if n != len(w):
+            raise IgdError("igd_hip_last_batch_routes: %d words, not %d" % (n, len(w)))
+        out = dict(zip(self.ROUTE_WORDS, (int(x) for x in w)))
+        out["kernel"] = {1: "igd_scan_sorted", 2: "igd_scan_tiles", 3: "igd_scan_direct"}[out["kernel"]]
+        return out
+
+    def route_constants(self):
+        """TEST-ONLY (igd_hip_route_constants): dict of the constants the merge join's routes are decided by."""
+        w = (C.c_int64 * len(self.ROUTE_CONSTANTS))()
+        n = self._H.igd_hip_route_constants(self.dev, w, len(w))
+        if n != len(w):
+            raise IgdError("igd_hip_route_constants: %d words, not %d" % (n, len(w)))
+        return dict(zip(self.ROUTE_CONSTANTS, (int(x) for x in w)))
+
 
 def measure_rates(device=0):
     """GB/s of this box, measured now: HBM float4 copy (read+write), HBM float4 read, pinned D2H, pinned H2D."""

@@ -1219,6 +1219,43 @@ const char *igd_hip_scan_kernel_name(void);
 /* ... and the one the last batch of `db` actually ran on: "igd_scan_sorted" (merge join over the compact image) or
  * "igd_scan_tiles" (bucket path, exact arrays).  Waits for the batch. */
 const char *igd_hip_last_scan_kernel(igd_hip_db *db);
+/* TEST-ONLY: which routes the last batch of `db` took.  Fills out[0 .. min(n, IGD_HIP_ROUTE_WORDS) - 1] and returns the number
+ * of words filled; 0 before the first batch (or when the device cannot be read).  Waits for the batch.  The list counters are
+ * those of the batch's own control words: they stand until the handle's next batch.  Word k of out[]: */
+enum {
+    IGD_HIP_ROUTE_KERNEL = 0,     /* scan kernel igd_hip_last_scan_kernel names: 1 igd_scan_sorted, 2 igd_scan_tiles, 3 igd_scan_direct */
+    IGD_HIP_ROUTE_FULL,           /* igd_scan_sorted: 0 the lean (pairwise-only) build, 1 the full (rank method) build; -1 another kernel */
+    IGD_HIP_ROUTE_PACKED,         /* 1: the compact image, 0: the exact arrays                                              */
+    IGD_HIP_ROUTE_LBSHIFT,        /* log2(queries per later block) of the bounds pass: 8, 10 or 12; 0 when it did not run     */
+    IGD_HIP_ROUTE_NFIX,           /* entries of the merge join's exact-walk list (WALK_FIRST, WALK_LAST)                   */
+    IGD_HIP_ROUTE_NLONG,          /* entries of the bucket path's exact-walk list (WALK_FIRST, WALK_ALL)                   */
+    IGD_HIP_ROUTE_NHEAVYS,        /* tiles listed for heavy_sorted_body (merge join's skew valve)                          */
+    IGD_HIP_ROUTE_NHEAVY,         /* tiles listed for heavy_bucket_body (bucket path's skew valve)                         */
+    IGD_HIP_ROUTE_NFAR,           /* units listed for far_units_body                                                       */
+    IGD_HIP_ROUTE_COV_SORTED,     /* 1: long queries of the merge join wrote coverage differences (set 0)                  */
+    IGD_HIP_ROUTE_COV_BUCKET,     /* 1: long queries of the bucket path wrote coverage differences (set 1)                 */
+    IGD_HIP_ROUTE_UNSORTED,       /* 1: the bounds pass found the batch not ordered by tile                                */
+    IGD_HIP_ROUTE_NOTSTART,       /* 1: ordered by tile, but not by start inside a tile (rank method off)                  */
+    IGD_HIP_ROUTE_WORDS
+};
+int igd_hip_last_batch_routes(igd_hip_db *db, int64_t *out, int n);
+/* TEST-ONLY: the constants the route tests derive their shapes from, filled and counted like the words above (no device access;
+ * valid from igd_hip_open on).  Word k of out[]: */
+enum {
+    IGD_HIP_RCONST_UNIT = 0,      /* records per unit (register slots per lane x 64 lanes)                                 */
+    IGD_HIP_RCONST_ROUND,         /* units a wave of the lean build reads the descriptors of at once                       */
+    IGD_HIP_RCONST_SHORT_TILES,   /* a query over more tiles than this has its last tile walked exactly (WALK_LAST)        */
+    IGD_HIP_RCONST_DENSE_MIN,     /* full build: first-tile queries of a tile from which the rank method counts            */
+    IGD_HIP_RCONST_LEAN_FIRST,    /* lean build: more first-tile queries than this list the tile for heavy_sorted_body     */
+    IGD_HIP_RCONST_HEAVY_FIRST,   /* full build: the same                                                                  */
+    IGD_HIP_RCONST_HEAVY_SLICE,   /* queries per slice of a listed tile                                                    */
+    IGD_HIP_RCONST_FAR_WIDE,      /* full build: a far unit whose candidates span this many later blocks is listed         */
+    IGD_HIP_RCONST_LATER_MAX,     /* later-tile candidates that come with a unit's records; one more makes the unit far    */
+    IGD_HIP_RCONST_SBCAP,         /* this handle: query starts of one tile a wave of the full build keeps in LDS           */
+    IGD_HIP_RCONST_LEAN_WAVES,    /* this handle: waves of one launch of the lean build (units beyond ROUND x this: a second round) */
+    IGD_HIP_RCONST_WORDS
+};
+int igd_hip_route_constants(igd_hip_db *db, int64_t *out, int n);
 
 #ifdef __cplusplus
 }

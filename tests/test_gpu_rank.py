@@ -3,7 +3,14 @@ bisections per record/query instead of pairwise compares) against the oracle: de
 small databases with every awkward query kind -- inverted (qe < qs), zero-length, negative starts, unknown contigs,
 starts beyond the contig's last tile, queries over many tiles -- with and without the value filter, on multi-chunk
 tiles and on gType 0; and a batch ordered by tile but NOT by start inside a tile, which must fall back to pairwise
-compares (CTL_NOTSTART) and still be exact."""
+compares (CTL_NOTSTART) and still be exact.
+
+What the route words (Database.last_batch_routes) show: a batch sorted by (contig, start) whose queries name contigs the
+database does not have is ordered by tile but NOT by start -- those queries share the key of tile 0 (contig < 0) or of the
+last tile (contig >= nctg) with starts of their own -- so the device switches the rank method off for it (notstart = 1).
+The dense test therefore runs every case a second time with those queries' starts moved below / above every other start
+(_rank_ordered: they count nothing wherever they start), asserts notstart = 0 on the full build -- the rank method runs --
+and notstart = 1 for the batch as it was."""
 import random
 import shutil
 
@@ -35,11 +42,24 @@ def _dense_queries(rng, nctg, nbp, span, n):
     return ichr[order], qs[order], qe[order]
 
 
+def _rank_ordered(ichr, qs, qe, nctg):
+    """the same batch with the queries of unknown contigs in start order inside the keys they share: contig < 0 (key: tile 0)
+    below every start, contig >= nctg (key: the last tile) above every start; lengths kept"""
+    qs, ln = qs.astype(np.int64), qe.astype(np.int64) - qs.astype(np.int64)
+    lo, hi = ichr < 0, ichr >= nctg
+    qs = np.where(lo, -(1 << 30) + np.cumsum(lo), np.where(hi, (1 << 30) + np.cumsum(hi), qs))
+    order = np.lexsort((qs, ichr))
+    return ichr[order], qs[order].astype(np.int32), (qs + ln)[order].astype(np.int32)
+
+
 @pytest.mark.parametrize("build", ["auto", "lean", "full"])
 @pytest.mark.parametrize("case", [1, 2, 3, 5, 6])
 def test_dense_sorted_batches_take_the_rank_path_and_match_the_oracle(case, build, workdir, monkeypatch):
     """build: which igd_scan_sorted the engine launches -- auto (by queries per tile: the full build here), lean
-    (pairwise only; tiles with > 512 first-tile queries go to the skew valve, heavy_sorted_body) or full (rank method from 32 on)."""
+    (pairwise only; tiles with > 512 first-tile queries go to the skew valve, heavy_sorted_body: nheavys > 0 is asserted)
+    or full (rank method from 32 on).  The batch as generated is ordered by tile but not by start (unknown contigs: see the
+    module's docstring) and is counted pairwise -- notstart = 1 is asserted; the same batch in rank order (_rank_ordered)
+    has notstart = 0, and the full build counts its dense tiles by rank."""
     from igd_amd import Database
     if build != "auto":
         monkeypatch.setenv("IGD_HIP_RANK", "0" if build == "lean" else "1")
@@ -57,7 +77,32 @@ def test_dense_sorted_batches_take_the_rank_path_and_match_the_oracle(case, buil
             for flags in (0, FLAG_SORTED, FLAG_BUCKET, FLAG_EXACT):
                 got, gtot = db.search(ichr, qs, qe, v, flags=flags)
                 assert gtot == wtot, (case, v, flags)
+                routes = db.last_batch_routes()
+                print(case, build, v, flags, routes)
+                if flags == FLAG_SORTED and routes["packed"]:      # the merge join's kernel, in the build asked for, fed four queries per thread
+                    assert routes["kernel"] == "igd_scan_sorted" and routes["lb_shift"] == 10 and routes["unsorted"] == 0
+                    assert routes["full"] == (0 if build == "lean" else 1)      # (auto: dense on average, the full build)
+                    assert routes["notstart"] == 1             # unknown contigs inside the keys of tile 0 / the last tile: rank method off
+                    if build == "lean":
+                        assert routes["nheavys"] > 0           # tiles with > 512 first-tile queries: the skew valve
+                if flags in (FLAG_BUCKET, FLAG_EXACT):
+                    assert routes["kernel"] == "igd_scan_tiles"
                 np.testing.assert_array_equal(got, want, err_msg="case %d v %d flags %d" % (case, v, flags))
+        # the same queries in rank order: the rank method stays on (full build: every tile with >= 32 first-tile queries)
+        a, b, c = _rank_ordered(ichr, qs, qe, nctg)
+        for v in (0, 300):
+            want, wtot = orc.search(a, b, c, v)
+            for flags in (FLAG_SORTED, 0):
+                got, gtot = db.search(a, b, c, v, flags=flags)
+                assert gtot == wtot, (case, v, flags)
+                np.testing.assert_array_equal(got, want, err_msg="rank order: case %d v %d flags %d" % (case, v, flags))
+                routes = db.last_batch_routes()
+                print(case, build, v, flags, "rank order", routes)
+                assert (routes["unsorted"], routes["notstart"]) == (0, 0), routes
+                if routes["packed"]:
+                    assert routes["kernel"] == "igd_scan_sorted" and routes["full"] == (0 if build == "lean" else 1)
+                    if build == "lean":
+                        assert routes["nheavys"] > 0
         # rule FLAT without a value filter (every tile visited, also behind an empty first tile)
         want = orc.search_rule(ichr, qs, qe, 1) if hasattr(orc, "search_rule") else None
         got_flat = db.search(ichr, qs, qe, rule=1)[0]
@@ -89,9 +134,12 @@ def test_tile_ordered_but_start_unordered_batch_falls_back_to_pairwise(workdir):
         assert (np.diff(b)[np.diff(a * 10**6 + b // nbp) == 0] < 0).any()
         for v in (0, 300):
             want, wtot = orc.search(a, b, c, v)
-            got, gtot = db.search(a, b, c, v, flags=FLAG_SORTED)      # the promise (tile order) holds
+            got, gtot = db.search(a, b, c, v, flags=FLAG_SORTED)      # (contig, start) is what is promised: reported, and redone unpromised
             assert gtot == wtot
             np.testing.assert_array_equal(got, want)
+            routes = db.last_batch_routes()                          # of the batch that counted: ordered by tile, not by start
+            assert (routes["unsorted"], routes["notstart"]) == (0, 1), routes
+            assert not routes["packed"] or routes["kernel"] == "igd_scan_sorted"
     finally:
         db.close(); orc.close()
 
@@ -120,6 +168,10 @@ def test_every_query_reaching_into_later_tiles(build, workdir, monkeypatch):
             got, gtot = db.search(ichr, qs, qe, 0, flags=FLAG_SORTED)
             assert gtot == wtot
             np.testing.assert_array_equal(got, want)
+            routes = db.last_batch_routes()
+            print(build, n, routes)
+            assert routes["lb_shift"] == (10 if n >= 65536 else 8) and routes["full"] == (0 if build == "lean" else 1)
+            assert routes["kernel"] == "igd_scan_sorted" and routes["unsorted"] == 0
             # the same batch from device arrays that start 4 bytes off a 16-byte boundary (k_query_bounds<1>)
             dev = torch.device("cuda:0")
             buf = [torch.empty(n + 1, dtype=torch.int32, device=dev) for _ in range(3)]
@@ -133,5 +185,6 @@ def test_every_query_reaching_into_later_tiles(build, workdir, monkeypatch):
             db.sync()
             np.testing.assert_array_equal(d_hits.cpu().numpy(), want)
             assert int(d_tot.item()) == wtot
+            assert db.last_batch_routes()["lb_shift"] == 8
     finally:
         db.close(); orc.close()

@@ -161,10 +161,13 @@ def test_dense_batches_whole_against_the_oracle(workload):
 
 
 def test_mid_size_batch_lean_build_long_queries(workdir):
-    """Between one and eight queries per tile on a database of tens of thousands of tiles: the lean build of
-    igd_scan_sorted fed by k_query_bounds with four queries per thread (>= 65536 queries), with queries up to six tiles
-    long -- later-tile words for one, two and three tiles, full later blocks, queries left to the exact walk -- and
-    unknown contigs; every count against the oracle, in the promised-order, device-decides and bucket modes."""
+    """Between one and eight queries per tile of the FILE, a database of tens of thousands of tiles of 2^9 bp, at least 65536
+    queries up to six of those tiles long, unknown contigs; every count against the oracle, in the promised-order,
+    device-decides and bucket modes.  The counting runs on the re-tiled 2^14 bp copy, and there the batch is another one than
+    the test's name says (asserted through the route words): dense on average -- the FULL build of igd_scan_sorted, fed by
+    k_query_bounds with four queries per thread (later blocks of 2^10 queries) -- and no query is long enough for the exact
+    walk (an empty list).  The lean build, the exact walk and the coverage are reached on purpose by
+    tests/test_gpu_mergejoin_routes.py."""
     from igd_amd import Database, synth
     path = os.path.join(workdir, "mid.igd")
     nbp_log = 9
@@ -183,5 +186,9 @@ def test_mid_size_batch_lean_build_long_queries(workdir):
                 got, gtot = db.search(ichr, qs, qe, v, flags=flags)
                 assert gtot == wtot, (v, flags)
                 np.testing.assert_array_equal(got, want, err_msg="v=%d flags=%d" % (v, flags))
+                routes = db.last_batch_routes()
+                print(v, flags, routes)
+                assert routes["kernel"] == ("igd_scan_tiles" if flags == 2 else "igd_scan_sorted")
+                assert flags == 2 or (routes["lb_shift"], routes["unsorted"], routes["full"], routes["nfix"]) == (10, 0, 1, 0)
     finally:
         db.close(); orc.close()
