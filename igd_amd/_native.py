@@ -218,6 +218,12 @@ def hip():
         # the same inside a workspace: the last argument is a const igd_hip_workspace * (NULL: the entry above)
         L.igd_hip_permute_support_ws.argtypes = L.igd_hip_permute_support_ov.argtypes + [C.c_void_p]
         L.igd_hip_permute_regions_ws.argtypes = L.igd_hip_permute_regions.argtypes + [C.c_void_p]
+        # support under rigid shifts: db, ichr, qs, qe, nq, ctg_len, nctg, offsets, nshift, out_qs, out_qe / db, ichr, qs, qe, nq,
+        # ctg_len, offsets, nshift, v, rule, shifted, min_overlap
+        L.igd_hip_shift_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_int64, C.c_void_p, C.c_void_p]
+        L.igd_hip_shift_support.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
         L.igd_hip_membership.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
@@ -476,6 +482,12 @@ def _bind_core(L):
     L.igdc_permute_host_ws.argtypes = L.igdc_permute_host_ov.argtypes + [C.c_void_p]
     L.igdc_permute_nearest_host_ws.argtypes = L.igdc_permute_nearest_host.argtypes + [C.c_void_p]
     L.igdc_permute_bp_host_ws.argtypes = L.igdc_permute_bp_host.argtypes + [C.c_void_p]
+    # support under rigid shifts on the host: ichr, qs, qe, nq, ctg_len, nctg, offsets, nshift, out_qs, out_qe / db, map, ichr, qs,
+    # qe, nq, ctg_len, offsets, nshift, v, rule, shifted, min_overlap
+    L.igdc_shift_regions_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p]
+    L.igdc_shift_support_host_ov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
     # db, path, len (int32[nCtg]), bad_line
     L.igdc_read_genome.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L

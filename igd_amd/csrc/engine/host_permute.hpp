@@ -24,6 +24,10 @@ static int64_t perm_row_bytes(void)
 // workgroups igd_permute_regions is launched with for n outputs: a lane takes a second one only when n exceeds the grid's lanes
 extern "C" int32_t igd_hip_permute_grid(int64_t n) { return items_grid(n, IGD_SETS_WG); }
 
+// The third placement kind, internal to the engine: the set moved rigidly by offsets[p] (igd_hip_shift_place; host_shift.hpp drives
+// it through run_perm_chunks with its offset table).  No public mode: perm_mode_ok refuses it for the three nulls.
+#define IGD_PERM_PLACE_SHIFT 3
+
 // a mode the call can run: the two free placements without a workspace, IGD_HIP_PERM_WORKSPACE with one
 static bool perm_mode_ok(int mode, const igd_hip_workspace *ws)
 {
@@ -77,7 +81,8 @@ static bool perm_args_refused(const char *who, const igd_hip_db *db, const int32
 }
 
 // THE PLACEMENT OF ONE CALL, written once for the two launch sites (run_perm_chunks, igd_hip_permute_regions_ws): the call's nq
-// regions and nctg contig lengths on the device (db->d_pmReg), the mode and, under IGD_HIP_PERM_WORKSPACE, the table (db->d_pmWs).
+// regions and nctg contig lengths on the device (db->d_pmReg), the mode and, under IGD_HIP_PERM_WORKSPACE, the table (db->d_pmWs);
+// under IGD_PERM_PLACE_SHIFT the offsets, behind the contig lengths in db->d_pmReg.
 struct PermPlace {
     const int32_t *rC, *rS, *rE, *rL;
     int64_t nq;
@@ -85,20 +90,22 @@ struct PermPlace {
     int mode;
     const int64_t *wOff;
     const int32_t *wStart, *wLen, *wPre;
+    const int32_t *offs;
 };
 
 // both buffers grown, then on the engine's stream the table of a checked workspace (without one only the mode is kept) and the
-// regions with the contig lengths
+// regions with the contig lengths; offsets (nshift of them; NULL, 0 for the nulls) go up last
 static int perm_place_upload(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
-                             int32_t nctg, int mode, const igd_hip_workspace *ws, PermPlace *pl)
+                             int32_t nctg, int mode, const igd_hip_workspace *ws, PermPlace *pl, const int32_t *offsets = nullptr,
+                             int64_t nshift = 0)
 {
     const int64_t nc = ws ? ws->nctg : 0, ns = ws ? ws->nseg : 0;
     hipStream_t st = db->stream;
-    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg);
+    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg + nshift);
     if (rc == IGD_HIP_OK && ws) rc = dev_grow(db, &db->d_pmWs, &db->pmWsCap, 2 * (nc + 1) + 3 * ns + nc + 1);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
-    *pl = PermPlace{rC, rS, rE, rL, nq, nctg, mode, nullptr, nullptr, nullptr, nullptr};
+    *pl = PermPlace{rC, rS, rE, rL, nq, nctg, mode, nullptr, nullptr, nullptr, nullptr, nshift > 0 ? rL + nctg : nullptr};
     if (ws) {
         int64_t *dOff = (int64_t *)db->d_pmWs;
         int32_t *dStart = db->d_pmWs + 2 * (nc + 1), *dLen = dStart + ns, *dPre = dLen + ns;
@@ -114,14 +121,19 @@ static int perm_place_upload(igd_hip_db *db, const int32_t *ichr, const int32_t 
     HIPCHK(hipMemcpyAsync(rS, qs, (size_t)nq * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
     if (nctg > 0) HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)nctg * 4, hipMemcpyHostToDevice, st));
+    if (nshift > 0) HIPCHK(hipMemcpyAsync(rL + nctg, offsets, (size_t)nshift * 4, hipMemcpyHostToDevice, st));
     return IGD_HIP_OK;
 }
 
-// `total` outputs (permutations from p0 on, nq regions each) by the kernel of the call's placement
+// `total` outputs (permutations from p0 on, nq regions each) by the kernel of the call's placement; under IGD_PERM_PLACE_SHIFT
+// permutation p is the shift by offsets[p] and the seed is not read
 static int permute_launch(igd_hip_db *db, const PermPlace &pl, u64 seed, u64 p0, int64_t total, int32_t *oC, int32_t *oS, int32_t *oE)
 {
     const unsigned grid = (unsigned)igd_hip_permute_grid(total);
-    if (pl.mode == IGD_HIP_PERM_WORKSPACE)
+    if (pl.mode == IGD_PERM_PLACE_SHIFT)
+        igd_shift_regions<<<grid, IGD_SETS_WG, 0, db->stream>>>(pl.rC, pl.rS, pl.rE, (unsigned)pl.nq, pl.rL, pl.nctg, pl.offs, (unsigned)p0,
+                                                              (unsigned)total, oC, oS, oE);
+    else if (pl.mode == IGD_HIP_PERM_WORKSPACE)
         igd_permute_workspace<<<grid, IGD_SETS_WG, 0, db->stream>>>(pl.rC, pl.rS, pl.rE, (unsigned)pl.nq, pl.rL, pl.nctg, pl.wOff, pl.wStart, pl.wLen,
                                                                   pl.wPre, seed, p0, (unsigned)total, oC, oS, oE);
     else
@@ -151,11 +163,12 @@ static std::vector<SetSlice> perm_row_slices(int64_t pc, int64_t nq, int64_t sli
 // this call also uploads what every chunk reads, and adds what the statistic does once behind row 0), then per chunk the
 // generator's output in the staging arrays (r0 = 1 + p0); the call with r0 + rows == nperm + 1 is the last.  Everything is on the
 // engine's stream without a wait in between, unless count waits itself; ONE wait at the end, behind which the callers write
-// their results.
+// their results.  offsets (NULL for the three nulls): the table of mode IGD_PERM_PLACE_SHIFT, nperm entries -- "permutation" p
+// is then the set shifted by offsets[p], and the caller's count has nothing to do with the set as given.
 template <typename Prepare, typename Count>
 static int run_perm_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
                            int mode, uint64_t seed, int64_t nperm, const igd_hip_workspace *ws, int64_t rowBytes, Prepare &&prepare,
-                           Count &&count)
+                           Count &&count, const int32_t *offsets = nullptr)
 {
     HIPCHK(hipSetDevice(db->device));
     int64_t pc = max_batch() / nq;
@@ -167,7 +180,7 @@ static int run_perm_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *q
     int rc = prepare(pc, sliceLen, perRow);
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
     PermPlace pl;
-    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, db->nCtg, mode, ws, &pl);
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, db->nCtg, mode, ws, &pl, offsets, offsets ? nperm : 0);
     if (rc == IGD_HIP_OK) rc = count(pl.rC, pl.rS, pl.rE, (int64_t)1, (int64_t)0);      // the set as given
     for (int64_t p0 = 0; rc == IGD_HIP_OK && p0 < nperm; p0 += pc) {
         const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;

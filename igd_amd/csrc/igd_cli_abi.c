@@ -1569,8 +1569,11 @@ static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int
 static const igd_hip_workspace *g_ws = NULL;
 /* `-G` switches it to base pairs (permute_bp_table below); it takes no sum of squares on the device, so the guard on it does not apply. */
 static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int rule);
+/* `-Z W,STEP` prints the shift profile of the support instead (shift_table below): nshift > 0 offsets; nperm may be 0 then. */
+static void shift_table(const igdc_queries *q, const int32_t *len, const int32_t *offsets, int nshift, int64_t nperm, uint64_t seed, int pmode,
+                        int32_t ev, int rule);
 static void permute_file(char *path, const char *genome, const char *wsName, int64_t nperm, uint64_t seed, int pmode, int32_t v, int32_t window,
-                         int gbp)
+                         int gbp, const int32_t *offsets, int nshift)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
@@ -1641,7 +1644,8 @@ static void permute_file(char *path, const char *genome, const char *wsName, int
         printf("Not supported: -P %lld with %lld regions\n", (long long)nperm, (long long)q.n);
         goto done;
     }
-    if (gbp) permute_bp_table(&q, len, nperm, seed, pmode, ev, rule);
+    if (nshift > 0) shift_table(&q, len, offsets, nshift, nperm, seed, pmode, ev, rule);
+    else if (gbp) permute_bp_table(&q, len, nperm, seed, pmode, ev, rule);
     else if (window >= 0) permute_nearest_table(&q, len, nperm, seed, pmode, ev, window);
     else {
         int64_t *st7 = (int64_t *)calloc(7 * (size_t)nC, sizeof(int64_t));
@@ -1674,6 +1678,85 @@ done:
     igdc_workspace_free(ws);
     free(lineOf);
     free(len);
+}
+
+/* ------------------------------- `igd search -q F -g genome -Z W,STEP [-P N]` ---------- */
+/* Local z-score: the support of every dataset with the whole query file moved rigidly by each offset (include/igd_hip.h: THE
+ * SHIFT).  Without -P the header `index \t File \t shift_<d> ..` and one line per dataset with the integer supports, then a line
+ * `any \t -` with the regions that have a hit in any dataset.  With -P N the columns observed, mean and sd (%.6f; `NA` for the sd
+ * of one permutation) of -P's null stand in front, and every shift is printed as z = (support - mean) / sd, %.4f, `NA` where sd
+ * is 0 or undefined.  The file, the genome file and the workspace are read and checked by permute_file.  Route, decided on
+ * regions x (shifts + N + 1): igdc_shift_support_host_ov and igdc_permute_host_ws, or igd_hip_shift_support and
+ * igd_hip_permute_support_ws. */
+static void shift_table(const igdc_queries *q, const int32_t *len, const int32_t *offsets, int nshift, int64_t nperm, uint64_t seed, int pmode,
+                        int32_t ev, int rule)
+{
+    const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
+    int64_t *sh = (int64_t *)calloc((size_t)nshift * (size_t)nC, sizeof(int64_t));
+    int64_t *st7 = (int64_t *)calloc(7 * (size_t)nC, sizeof(int64_t));
+    double *fl = (double *)calloc(2 * (size_t)nC, sizeof(double));
+    if (!sh || !st7 || !fl) { fprintf(stderr, "igd: out of memory\n"); free(sh); free(st7); free(fl); return; }
+    int64_t *obs = st7, *sum = obs + nC, *ssq = sum + nC, *nge = ssq + nC, *nle = nge + nC, *mn = nle + nC, *mx = mn + nC;
+    cli_route R;
+    if (route_host(&R, q->n * ((int64_t)nshift + (nperm > 0 ? nperm + 1 : 0))))
+        route_host_end(&R, igdc_shift_support_host_ov(g_core, R.hm, q->ichr, q->qs, q->qe, q->n, len, offsets, nshift, ev, rule, sh, g_mo) == 0 &&
+                               (nperm < 1 || igdc_permute_host_ws(g_core, R.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, obs, sum,
+                                                                  ssq, nge, nle, mn, mx, g_mo, g_ws) == 0),
+                       "shift profile on the host (small files)");
+    if (route_engine(&R, 1)) {
+        int rc = igd_hip_shift_support(R.dev, q->ichr, q->qs, q->qe, q->n, len, offsets, nshift, ev, rule, sh, g_mo);
+        if (rc == IGD_HIP_OK && nperm > 0)
+            rc = igd_hip_permute_support_ws(R.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo, g_ws);
+        route_engine_end(&R, "shift profile", rc, "shift profile of the query file (H2D + shift and support kernels + D2H)");
+    }
+    if (!g_fail_rc && (nperm < 1 || igdc_perm_summary(obs, sum, ssq, nge, nle, nperm, nC, fl, fl + nC, NULL, NULL, NULL) == 0)) {
+        printf("index\tFile%s", nperm > 0 ? "\tobserved\tmean\tsd" : "");
+        for (int j = 0; j < nshift; j++) printf("\tshift_%d", (int)offsets[j]);
+        printf("\n");
+        for (int32_t i = 0; i <= nfiles; i++) {               /* (i = nfiles: the any-dataset column) */
+            const double mean = fl[i], sd = fl[nC + i];
+            if (i < nfiles) printf("%d\t%s", (int)i, IGD->finfo[i].fileName);
+            else printf("any\t-");
+            if (nperm > 0) {
+                printf("\t%lld\t%.6f", (long long)obs[i], mean);
+                if (sd == sd) printf("\t%.6f", sd); else printf("\tNA");
+            }
+            for (int j = 0; j < nshift; j++) {
+                const int64_t x = sh[(size_t)j * (size_t)nC + (size_t)i];
+                if (nperm < 1) printf("\t%lld", (long long)x);
+                else if (sd != sd || sd == 0.0) printf("\tNA");
+                else printf("\t%.4f", ((double)x - mean) / sd);
+            }
+            printf("\n");
+        }
+    }
+    free(sh); free(st7); free(fl);
+}
+
+/* `-Z W,STEP`: the offsets -k STEP .. k STEP, k = W / STEP, into a malloc'd array; 0 for anything but two whole numbers with
+ * 0 <= W <= 2^30, STEP >= 1 and at most IGD_HIP_SHIFT_MAX shifts */
+static int parse_shifts(const char *arg, int32_t **offsets)
+{
+    char *end = NULL;
+    if (arg[0] < '0' || arg[0] > '9') return 0;
+    const long long w = strtoll(arg, &end, 10);
+    if (*end != ',' || end[1] < '0' || end[1] > '9' || w > (long long)IGD_HIP_SHIFT_MAX_OFFSET) return 0;
+    const char *p = end + 1;
+    const long long step = strtoll(p, &end, 10);
+    if (*end || step < 1) return 0;
+    const long long k = w / step;
+    if (2 * k + 1 > IGD_HIP_SHIFT_MAX) return 0;
+    int32_t *o = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * k + 1));
+    if (!o) return 0;
+    for (long long j = -k; j <= k; j++) o[j + k] = (int32_t)(j * step);
+    *offsets = o;
+    return (int)(2 * k + 1);
+}
+
+static int refused_shift(const char *why, const char *arg)                   /* -Z's refusals: stderr, nothing on stdout */
+{
+    fprintf(stderr, "Not supported: %s%s\n", why, arg ? arg : "");
+    return EX_USAGE;
 }
 
 /* ------------------------------- `igd search -q F -N <bp>` / `-Q <list> -N <bp>` ------- */
@@ -2021,6 +2104,9 @@ static int usage_search(void)
             "                               one-sided p) and the Jaccard with the mean permuted one\n"
             "    -W <workspace file>        with -P: the regions are placed inside the segments of this BED file (centromeres, gaps and\n"
             "                               blacklisted stretches left out), every fitting start equally likely; instead of -M\n"
+            "    -Z <W>,<STEP>              local z-score, with -q and -g: the support of every dataset with the whole file moved by\n"
+            "                               -k STEP .. k STEP base pairs (k = W / STEP, at most 4096 shifts; a region is pushed back\n"
+            "                               against its contig's ends); with -P each count as a z-score in the null of -P\n"
             "    -R                         with -U: six more columns, the dataset's rank within the set by support, p and odds\n"
             "                               ratio, their maximum and mean, and -log10 of the Benjamini-Hochberg q-value\n"
             "  environment: IGD_DEVICE=<n> selects the GPU (default 0); IGD_DEVICES=0,1,.. searches a query file on\n"
@@ -2098,6 +2184,7 @@ int igd_search(int argc, char **argv)                                        /* 
     int gbp = 0;                                                                      /* -G given (see permute_bp_table) */
     char *mapArg = NULL;                                                              /* -V (see map_files) */
     char *grpName = NULL;                                                             /* -K (see groups_read) */
+    char *shiftArg = NULL;                                                            /* -Z (see shift_table) */
     char out[64] = "";
     groups_free();
     for (int i = 3; i < argc; i++) {                                          /* :931-971 */
@@ -2173,6 +2260,10 @@ int igd_search(int argc, char **argv)                                        /* 
             if (i + 1 >= argc) { printf("Not supported: -K without a groups file\n"); return EX_USAGE; }
             grpName = argv[i + 1];
             i++;
+        } else if (strcmp(a, "-Z") == 0) {            /* (not the reference's: support under rigid shifts, see shift_table) */
+            if (i + 1 >= argc) return refused_shift("-Z without W,STEP", NULL);
+            shiftArg = argv[i + 1];
+            i++;
         } else if (strcmp(a, "-g") == 0) {
             if (i + 1 >= argc) { printf("No genome file.\n"); return EX_OK; }
             genomeName = argv[i + 1];
@@ -2203,6 +2294,26 @@ int igd_search(int argc, char **argv)                                        /* 
         if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
     }
 
+    long long np = 0;                                                         /* -P's count, once a block below has parsed it */
+    int32_t *shiftOff = NULL;                                                 /* -Z: every refusal is a usage error, worded on stderr */
+    int nShift = 0;
+    if (shiftArg) {
+        const char *why = NULL;
+        if (listName) why = "-Z together with -Q";
+        else if (uniq || uniName || bp || jac || memb || cooc || nearArg || mapArg || grpName || full || other || ranks || restricted || histArg ||
+                 flankL || flankEdges)
+            why = "-Z together with -u, -U, -b, -J, -w, -C, -N, -V, -K, -m, -s, -r, -f, -R, -X, -H, -L or -E";
+        else if (distArg || gbp) why = "-Z together with -D or -G (the shift profile is the support's)";
+        else if (!genomeName) why = "-Z without -g";
+        else if (mode != 1) why = "-Z without -q";
+        else if (!permArg && (seedArg || pmodeArg || wsName)) why = "-Z with -S, -M or -W but without -P";
+        else if (wsName && pmodeArg) why = "-W together with -M (the workspace is the placement)";
+        else if (permArg && !parse_perm_count(permArg, &np)) why = "-Z with a number of permutations outside 1 to 1048576";
+        else if (permArg && parse_perm_mode(pmodeArg) < 0) why = "-Z with a -M that is neither circular nor shuffle";
+        if (why) return refused_shift(why, NULL);
+        if ((nShift = parse_shifts(shiftArg, &shiftOff)) < 1)
+            return refused_shift("-Z W,STEP needs 0 <= W <= 1073741824, STEP >= 1 and at most 4096 shifts, not ", shiftArg);
+    }
     if (grpName) {                                                            /* -K: every refusal is a usage error */
         const char *why = NULL;
         if (bp || memb || restricted || cooc || permArg || distArg || gbp || wsName || jac || mapArg || nearArg || histArg || flankL || flankEdges ||
@@ -2214,7 +2325,6 @@ int igd_search(int argc, char **argv)                                        /* 
         const int rc = groups_read(grpName);
         if (rc) return rc;
     }
-    long long np = 0;                                                         /* -P's count, once a block below has parsed it */
     if (wsName) {                                                             /* -W: every refusal is a usage error */
         if (!permArg) return refused_usage("-W without -P");
         if (pmodeArg) return refused_usage("-W together with -M (the workspace is the placement)");
@@ -2333,7 +2443,11 @@ int igd_search(int argc, char **argv)                                        /* 
     const int perSet = mode == 1 || (mode < 0 && listName);                   /* -u, -b and -w: -Q counts only without -m, -s and -r */
     cli_paths P;
     memset(&P, 0, sizeof P);
-    if (!permArg && (genomeName || seedArg || pmodeArg)) {
+    if (shiftArg) {
+        permute_file(qfName, genomeName, wsName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0,
+                     wsName ? IGD_HIP_PERM_WORKSPACE : parse_perm_mode(pmodeArg), v, -1, 0, shiftOff, nShift);
+        free(shiftOff);
+    } else if (!permArg && (genomeName || seedArg || pmodeArg)) {
         printf("Not supported: -g, -S or -M without -P\n");
         return EX_OK;
     } else if (jac) {
@@ -2364,7 +2478,7 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported: -M %s (circular or shuffle)\n", pmodeArg);
             return EX_OK;
         }
-        permute_file(qfName, genomeName, wsName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW, gbp);
+        permute_file(qfName, genomeName, wsName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW, gbp, NULL, 0);
     } else if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
         printf("Not supported: -C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r\n");
         return EX_OK;

@@ -360,6 +360,17 @@ int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int
 int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                             const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
                             int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws);
+/* The support of a region set under rigid shifts on the host (what igd_hip_shift_regions and igd_hip_shift_support compute;
+ * include/igd_hip.h has THE SHIFT, the outputs and the refusals).  igdc_shift_regions_host is kernel igd_shift_regions: nq regions
+ * under each of nshift offsets into out_qs, out_qe (int32[nshift * nq], shift-major); nctg is the caller's.
+ * igdc_shift_support_host_ov: shifted is int64[nshift * (nFiles + 1)], DEFINED; row j is the set moved by offsets[j], walked with
+ * the per-query code of igdc_support_host_ov (min_overlap NULL: no threshold); threads run over the rows as in igdc_permute_host.
+ * 0 on success; -1 for a refused argument -- the engine's refusals -- or when a tile could not be read (nothing written). */
+int igdc_shift_regions_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                            const int32_t *offsets, int64_t nshift, int32_t *out_qs, int32_t *out_qe);
+int igdc_shift_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *ctg_len, const int32_t *offsets, int64_t nshift, int32_t v, int rule, int64_t *shifted,
+                               const igd_hip_min_overlap *min_overlap);
 /* A genome file, lines `name<TAB>length`: len[c] = the length of contig c of the database (int32[nCtg]); lines of contigs the
  * database does not know are ignored, contigs the file does not name get 0.  0; -1 when the file cannot be opened; -2 for a
  * line of a known contig without a length or with one that is negative or above 2^31 - 1 (*bad_line, may be NULL, = its

@@ -571,6 +571,25 @@ int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, const int32_
               : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_shift_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                          int32_t nctg, const int32_t *offsets, int64_t nshift, int32_t *out_qs, int32_t *out_qe)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int32_t, const int32_t *,
+                        int64_t, int32_t *, int32_t *);
+    RESOLVE(fn_t, "igd_hip_shift_regions");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, nctg, offsets, nshift, out_qs, out_qe) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_shift_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                          const int32_t *offsets, int64_t nshift, int32_t v, int rule, int64_t *shifted,
+                          const igd_hip_min_overlap *min_overlap)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, const int32_t *, int64_t,
+                        int32_t, int, int64_t *, const igd_hip_min_overlap *);
+    RESOLVE(fn_t, "igd_hip_shift_support");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, offsets, nshift, v, rule, shifted, min_overlap) : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_permute_nearest_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
                                int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
                                int64_t *sum_dist, const igd_hip_workspace *ws)

@@ -1148,6 +1148,37 @@ int igdc_permute_regions_host(const int32_t *ichr, const int32_t *qs, const int3
     return igdc_permute_regions_host_ws(ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe, NULL);
 }
 
+/* the shift placement (include/igd_hip.h: THE SHIFT), on checked arguments: the set under each of nshift offsets */
+static void shift_regions_fill(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                               const int32_t *offsets, int64_t nshift, int32_t *out_qs, int32_t *out_qe)
+{
+    for (int64_t j = 0; j < nshift; j++) {
+        int32_t *os = out_qs + j * nq, *oe = out_qe + j * nq;
+        for (int64_t i = 0; i < nq; i++) {
+            os[i] = qs[i]; oe[i] = qe[i];
+            igd_hip_shift_place(offsets[j], ichr[i], ctg_len, nctg, &os[i], &oe[i]);
+        }
+    }
+}
+
+/* the refusals the two shift entries share with the engine's: the arrays, the number of shifts, every offset, the batch limit */
+static int shift_args_bad(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                          const int32_t *offsets, int64_t nshift)
+{
+    return nq < 0 || nctg < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (nctg > 0 && !ctg_len) || !offsets || nshift < 1 ||
+           nshift > IGD_HIP_SHIFT_MAX || igd_hip_shift_first_bad(offsets, nshift) >= 0 || nq > igd_hip_max_batch();
+}
+
+int igdc_shift_regions_host(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
+                            const int32_t *offsets, int64_t nshift, int32_t *out_qs, int32_t *out_qe)
+{
+    if (shift_args_bad(ichr, qs, qe, nq, ctg_len, nctg, offsets, nshift) || (nq > 0 && (!out_qs || !out_qe)) ||
+        (nq > 0 && nshift > (int64_t)INT32_MAX / nq))
+        return -1;
+    shift_regions_fill(ichr, qs, qe, nq, ctg_len, nctg, offsets, nshift, out_qs, out_qe);
+    return 0;
+}
+
 /* ---- the workspace table (include/igd_hip.h: THE WORKSPACE) ---------------------------------------------------------------
  * igdc_workspace_build: the segments through igdc_merge_host at gap 0 (one set; it needs a database only for the number of
  * contigs), the runs clipped to [0, ctg_len[c]], per contig ordered by length descending then start ascending, and summed.  The
@@ -1284,6 +1315,7 @@ typedef struct {
     int64_t nq, first, nrows;
     int mode; uint64_t seed;
     const igd_hip_workspace *ws;        /* the checked table of mode IGD_HIP_PERM_WORKSPACE, or NULL */
+    const int32_t *offsets;             /* the shift placement (igdc_shift_support_host_ov): row r > 0 is the set moved by offsets[r - 1]; or NULL */
     int32_t *ps, *pe;                   /* the permuted set */
     int k, T, failed;
 } perm_stripe;
@@ -1294,7 +1326,7 @@ static void stripe_init(perm_stripe *S, const igdc_db *db, const igdc_map *m, co
                         int32_t *ps, int k, int T)
 {
     S->db = db; S->m = m; S->ichr = ichr; S->qs = qs; S->qe = qe; S->ctg_len = ctg_len;
-    S->nq = nq; S->first = first; S->nrows = nrows; S->mode = mode; S->seed = seed; S->ws = ws;
+    S->nq = nq; S->first = first; S->nrows = nrows; S->mode = mode; S->seed = seed; S->ws = ws; S->offsets = NULL;
     S->ps = ps; S->pe = ps + nq;
     S->k = k; S->T = T; S->failed = 0;
 }
@@ -1304,7 +1336,8 @@ static void perm_rows(perm_stripe *S, perm_row_fn row, void *job)
     for (int64_t r = S->first + S->k; r < S->nrows && !S->failed; r += S->T) {
         const int32_t *s = S->qs, *e = S->qe;
         if (r > 0) {
-            perm_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->mode, S->seed, r - 1, 1, S->ps, S->pe, S->ws);
+            if (S->offsets) shift_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->offsets + (r - 1), 1, S->ps, S->pe);
+            else perm_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->mode, S->seed, r - 1, 1, S->ps, S->pe, S->ws);
             s = S->ps; e = S->pe;
         }
         if (row(job, r, s, e)) S->failed = 1;
@@ -1413,6 +1446,72 @@ int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ic
         memcpy(observed, obs, sizeof(int64_t) * (size_t)nC);
         for (int s = 0; s < 6; s++) if (out[s]) memcpy(out[s], a0 + s * nC, sizeof(int64_t) * (size_t)nC);
     }
+    free(w); free(pq);
+    return rc;
+}
+
+/* igdc_shift_support_host_ov's thread: rows 1 .. nshift of the stripe (row r is the set moved by offsets[r - 1]), each walked
+ * with the per-query code of igdc_support_host and written as row r - 1 of the call's own matrix */
+typedef struct {
+    perm_stripe s;
+    int32_t v; int rule;
+    int64_t *out, *last;                /* the call's matrix, nFiles + 1 words per row; the thread's stamps */
+    const igd_hip_min_overlap *mo;      /* an active minimum overlap, or NULL */
+} shift_job;
+
+static int shift_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
+{
+    shift_job *P = (shift_job *)job;
+    const int64_t nF = P->s.db->nFiles, nC = nF + 1;
+    int64_t *row = P->out + (r - 1) * nC;
+    memset(row, 0, sizeof(int64_t) * (size_t)nC);
+    memset(P->last, 0, sizeof(int64_t) * (size_t)nC);
+    host_job J;
+    job_init(&J, JOB_SUPPORT, P->s.db, P->s.m, P->s.ichr, s, e, 0, P->s.nq, P->v, P->rule);
+    J.hits = row; J.last = P->last; J.mo = P->mo;
+    host_run(&J);
+    if (J.io_failed) return 1;
+    row[nF] = J.total;
+    return 0;
+}
+static void *shift_run(void *arg)
+{
+    shift_job *P = (shift_job *)arg;
+    perm_rows(&P->s, shift_row, P);
+    return NULL;
+}
+
+int igdc_shift_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *ctg_len, const int32_t *offsets, int64_t nshift, int32_t v, int rule, int64_t *shifted,
+                               const igd_hip_min_overlap *min_overlap)
+{
+    const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
+    if (!igd_hip_min_overlap_valid(min_overlap) || !db || !m || !shifted || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) ||
+        shift_args_bad(ichr, qs, qe, nq, ctg_len, db->nCtg, offsets, nshift) || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0)
+        return -1;
+    const int64_t nF = db->nFiles, nC = nF + 1;
+    if (nq == 0 || nF == 0) {
+        memset(shifted, 0, sizeof(int64_t) * (size_t)(nshift * nC));
+        return 0;
+    }
+    int T = host_threads(nq * nshift);
+    if (T > nshift) T = (int)nshift;
+    /* the call's matrix, then per thread the stamps (nC words) and the shifted set (2 nq int32) */
+    int64_t *w = (int64_t *)calloc((size_t)(nshift + T) * (size_t)nC, sizeof(int64_t));
+    int32_t *pq = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 2 * (size_t)nq + 1));
+    int rc = w && pq ? 0 : -1;
+    shift_job job[HOST_MAX_THREADS];
+    for (int k = 0; k < T && rc == 0; k++) {
+        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, 0, 0, NULL, 1, nshift + 1, pq + (size_t)k * 2 * (size_t)nq, k, T);
+        job[k].s.offsets = offsets;
+        job[k].v = v; job[k].rule = rule; job[k].mo = mo;
+        job[k].out = w; job[k].last = w + (size_t)(nshift + k) * (size_t)nC;
+    }
+    if (rc == 0) {
+        run_threads(shift_run, job, sizeof job[0], T);
+        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
+    }
+    if (rc == 0) memcpy(shifted, w, sizeof(int64_t) * (size_t)(nshift * nC));
     free(w); free(pq);
     return rc;
 }

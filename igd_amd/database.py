@@ -624,6 +624,78 @@ def perm_summary(ps):
     return PermutationSummary(*out)
 
 
+ShiftSupport = collections.namedtuple("ShiftSupport", "shifted offsets")
+SHIFT_MAX = 4096                                     # IGD_HIP_SHIFT_MAX: offsets of one call
+SHIFT_MAX_OFFSET = 1 << 30                           # IGD_HIP_SHIFT_MAX_OFFSET
+
+
+def shift_offsets(window, step):
+    """int32 offsets -k * step .. k * step with k = window // step (what `igd search -Z window,step` uses): 2 k + 1 of them,
+    the middle one 0."""
+    window, step = int(window), int(step)
+    if window < 0 or step < 1 or window > SHIFT_MAX_OFFSET:
+        raise IgdError("shift_offsets: window %d, step %d: not 0 <= window <= %d with step >= 1" % (window, step, SHIFT_MAX_OFFSET))
+    k = window // step
+    if 2 * k + 1 > SHIFT_MAX:
+        raise IgdError("shift_offsets: %d shifts, not 1 .. %d" % (2 * k + 1, SHIFT_MAX))
+    return (np.arange(-k, k + 1, dtype=np.int64) * step).astype(np.int32)
+
+
+def _offsets(offsets, what):
+    """the offsets of a shift call as C-ordered int32: 1 .. SHIFT_MAX whole numbers within +-2^30 (the engine's two refusals, said
+    here because a conversion to int32 would wrap a larger one)"""
+    o = np.asarray(offsets)
+    if o.ndim != 1 or (o.size and o.dtype.kind not in "iu"):
+        raise IgdError("%s: offsets must be a list of whole numbers" % what)
+    if not 1 <= len(o) <= SHIFT_MAX:
+        raise IgdError("%s: %d shifts, not 1 .. %d" % (what, len(o), SHIFT_MAX))
+    bad = np.flatnonzero((o > SHIFT_MAX_OFFSET) | (o < -SHIFT_MAX_OFFSET))
+    if len(bad):
+        raise IgdError("%s: offset %d = %d is beyond +-%d" % (what, bad[0], int(o[bad[0]]), SHIFT_MAX_OFFSET))
+    return np.ascontiguousarray(o, dtype=np.int32)
+
+
+def shift_regions_host(ichr, qs, qe, ctg_len, offsets):
+    """A region list under rigid shifts on the host (igdc_shift_regions_host; no device is touched): (qs, qe) int32[nshift, nq]
+    as Database.shift_regions() defines them."""
+    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "shift_regions_host")
+    offsets = _offsets(offsets, "shift_regions_host")
+    oqs, oqe = np.empty((len(offsets), len(qs)), np.int32), np.empty((len(offsets), len(qs)), np.int32)
+    if N.cli().igdc_shift_regions_host(_ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len), _ptr(offsets), len(offsets),
+                                       _ptr(oqs), _ptr(oqe)) != 0:
+        raise IgdError("shift_regions_host: bad argument")
+    return oqs, oqe
+
+
+def shift_support_host(igd_path, ichr, qs, qe, ctg_len, offsets, v=0, rule=None, value_filter=None, min_overlap=None):
+    """The support of one region set under rigid shifts on the host (igdc_shift_support_host_ov: pread on the .igd, threads over
+    the shifts; no device is touched): a ShiftSupport as Database.shift_support() defines it."""
+    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "shift_support_host")
+    offsets = _offsets(offsets, "shift_support_host")
+    mo = _min_overlap(min_overlap, "shift_support_host")
+    with _HostDb(igd_path, "shift_support_host") as h:
+        _ctg_len_matches(ctg_len, h.nctg, "shift_support_host")
+        rule, vf = h.dispatch(v, rule, value_filter)
+        shifted = np.empty((len(offsets), h.nfiles + 1), np.int64)
+        if h.L.igdc_shift_support_host_ov(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), _ptr(offsets), len(offsets),
+                                          vf, rule, _ptr(shifted), None if mo is None else C.byref(mo)) != 0:
+            raise IgdError("shift_support_host: a refused argument (a region outside its contig, more regions than a batch), or a tile of %s "
+                           "could not be read" % igd_path)
+    return ShiftSupport(shifted, offsets)
+
+
+def local_zscore(ps, ss):
+    """float64[nshift, nfiles + 1]: every shifted support of a ShiftSupport placed in the null of a PermutationSupport of the same
+    set, z[j, f] = (shifted[j, f] - mean[f]) / sd[f] with mean and sd exactly as perm_summary() forms them; NaN where sd is 0
+    (or NaN: one permutation).  A peak at offset 0 means the association depends on the exact position."""
+    sm = perm_summary(ps)
+    sh = np.asarray(ss.shifted, dtype=np.int64)
+    if sh.ndim != 2 or sh.shape[1] != len(sm.mean):
+        raise IgdError("local_zscore: shifted must be int64[nshift, %d], the columns of the PermutationSupport" % len(sm.mean))
+    sd = np.where(sm.sd == 0, np.nan, sm.sd)
+    return (sh.astype(np.float64) - sm.mean[None, :]) / sd[None, :]
+
+
 def permute_nearest_host(igd_path, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, workspace=None):
     """Database.permutation_nearest() on the host (igdc_permute_nearest_host: pread on the .igd, threads over the permutations;
     no device is touched): a PermutationNearest."""
@@ -1410,6 +1482,44 @@ class Database:
         integers behind what `igd search -q path -P nperm -g genome_path` prints (with -W: mode="workspace" and workspace=)."""
         return self.permutation_support(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v, min_overlap=min_overlap,
                                         workspace=workspace)
+
+    def _shift_support(self, ichr, qs, qe, ctg_len, offsets, v=0, rule=None, value_filter=None, min_overlap=None):
+        """shift_support(ichr, qs, qe, ctg_len, offsets, v=0, rule=None, value_filter=None, min_overlap=None).  The support counts
+        of one region set under rigid shifts (igd_hip_shift_support; regioneR's localZScore).  The whole set is moved by each of
+        offsets (1 .. 4096 whole numbers within +-2^30, any order; shift_offsets() makes the usual ladder); a region that would
+        leave its contig is pushed back against the end, its width kept; regions on unknown contigs stay.  ctg_len as
+        permutation_support().  Returns ShiftSupport(shifted, offsets): shifted int64[nshift, nfiles + 1], row j what support()
+        counts for the set moved by offsets[j] (same v, rule, value_filter and min_overlap), the last column the regions with a
+        hit in any file.  The shifted regions never leave the device.  local_zscore() places the rows in the null of
+        permutation_support().  A region on a known contig that does not lie within its length raises IgdError."""
+        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "shift_support")
+        offsets = _offsets(offsets, "shift_support")
+        _ctg_len_matches(ctg_len, self.nctg, "shift_support")
+        rule, vf = _dispatch(self.gtype, v, rule, value_filter)
+        mo = _min_overlap(min_overlap, "shift_support")
+        shifted = np.empty((len(offsets), self.nfiles + 1), np.int64)
+        _chk(self._H.igd_hip_shift_support(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), _ptr(offsets), len(offsets),
+                                           vf, rule, _ptr(shifted), None if mo is None else C.byref(mo)), "igd_hip_shift_support")
+        return ShiftSupport(shifted, offsets)
+
+    shift_support = _forward(_shift_support)
+
+    def _shift_regions(self, ichr, qs, qe, ctg_len, offsets):
+        """shift_regions(ichr, qs, qe, ctg_len, offsets).  Kernel igd_shift_regions on host arrays (igd_hip_shift_regions): (qs,
+        qe) int32[nshift, nq], row j the regions moved by offsets[j].  ctg_len is the caller's, as for permute_regions()."""
+        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "shift_regions")
+        offsets = _offsets(offsets, "shift_regions")
+        oqs, oqe = np.empty((len(offsets), len(qs)), np.int32), np.empty((len(offsets), len(qs)), np.int32)
+        _chk(self._H.igd_hip_shift_regions(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), len(ctg_len), _ptr(offsets),
+                                           len(offsets), _ptr(oqs), _ptr(oqe)), "igd_hip_shift_regions")
+        return oqs, oqe
+
+    shift_regions = _forward(_shift_regions)
+
+    def shift_support_files(self, path, genome_path, offsets, v=0, min_overlap=None):
+        """The shift profile of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the integers
+        that `igd search -q path -g genome_path -Z W,STEP` prints for offsets = shift_offsets(W, STEP)."""
+        return self.shift_support(*self.read_queries(path), self.read_genome(genome_path), offsets, v, min_overlap=min_overlap)
 
     def permute_regions(self, ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular", workspace=None):
         """Kernel igd_permute_regions on host arrays (igd_hip_permute_regions): (qs, qe) int32[np_, nq], row k the regions

@@ -1036,6 +1036,57 @@ int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
                           int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
                           int64_t *n_dropped, const igd_hip_workspace *ws);
 
+/* Local z-score: the support of a region set under rigid shifts (regioneR's localZScore).  The whole set is moved by each of
+ * nshift offsets and counted again; the host places every count in the null the permutation entries above produced.
+ * THE SHIFT (the one definition: kernel igd_shift_regions, igdc_shift_regions_host and the tests' numpy reference agree on
+ * every integer).  A region (c, s, e) on a known contig, L = ctg_len[c] >= 1, 0 <= s <= e <= L, len = e - s, under offset d:
+ *     s' = min(max(s + d, 0), L - len) in signed 64 bits;  e' = s' + len
+ * -- a region that would leave its contig is pushed back against the end, its width kept: IGD_HIP_PERM_CIRCULAR's rule at the
+ * contig's end.  A region with c < 0 or c >= nctg passes through unchanged, and so does, in the generic entry alone, an invalid
+ * region on a known contig.  Offsets are int32 with |d| <= IGD_HIP_SHIFT_MAX_OFFSET (the bound of -N's window), 1 ..
+ * IGD_HIP_SHIFT_MAX of them per call, in any order, repeats allowed. */
+#define IGD_HIP_SHIFT_MAX 4096
+#define IGD_HIP_SHIFT_MAX_OFFSET ((int32_t)1 << 30)
+/* region (c, *s, *e) under offset d, in place */
+static inline IGD_HIP_HD_ void igd_hip_shift_place(int32_t d, int32_t c, const int32_t *ctg_len, int32_t nctg, int32_t *s, int32_t *e)
+{
+    if (c < 0 || c >= nctg) return;
+    const int64_t L = ctg_len[c], s0 = *s, len = (int64_t)*e - s0;
+    if (L < 1 || s0 < 0 || len < 0 || s0 + len > L) return;
+    int64_t t = s0 + (int64_t)d;
+    if (t < 0) t = 0;
+    if (t > L - len) t = L - len;
+    *s = (int32_t)t;
+    *e = (int32_t)(t + len);
+}
+/* the first offset beyond +-IGD_HIP_SHIFT_MAX_OFFSET; -1: none (host only) */
+static inline int64_t igd_hip_shift_first_bad(const int32_t *offsets, int64_t nshift)
+{
+    for (int64_t j = 0; j < nshift; j++)
+        if (offsets[j] > IGD_HIP_SHIFT_MAX_OFFSET || offsets[j] < -IGD_HIP_SHIFT_MAX_OFFSET) return j;
+    return -1;
+}
+/* igd_hip_shift_support: shifted is int64[nshift][nFiles + 1], DEFINED by the call.  Row j is exactly what igd_hip_support_sets_ov
+ * counts for the set shifted by offsets[j] (same v, rule and min_overlap; NULL: no threshold); column nFiles is the regions with a
+ * hit in any dataset, as in igd_hip_permute_support.  A row with offset 0 equals the support of the set as given; equal offsets
+ * give equal rows.  ctg_len is int32[number of contigs of db].  The regions and the offsets are uploaded once; the shifts go
+ * through the chunk driver of the permutation nulls, pc shifts per chunk with pc * nq <= igd_hip_max_batch() and pc * nFiles * 8
+ * <= the row budget of igd_hip_permute_support: kernel igd_shift_regions into the staging arrays, one row per shift through
+ * igd_sets_support, the rows copied into a buffer of the call; one wait at the end.  z-scores are the host's (igd_amd.local_zscore,
+ * `igd search -Z`): no floating point runs on the device.  IGD_HIP_ERR_ARG before any launch, nothing of the caller's written,
+ * checked in this order: min_overlap out of range; a missing argument or no such rule; nshift outside 1 .. IGD_HIP_SHIFT_MAX; an
+ * offset beyond +-2^30 (igd_hip_last_error names the first); nq > igd_hip_max_batch(); the first region on a known contig that
+ * breaks 0 <= s <= e <= L, L >= 1.  nq == 0 or nFiles == 0: all zeros, no device work.
+ * igd_hip_shift_regions: the kernel on host arrays, the twin of igd_hip_permute_regions -- out_qs, out_qe are int32[nshift * nq],
+ * shift-major; nctg is the caller's; chunked by igd_hip_max_batch(); the same refusals but the last (regions are not validated),
+ * and more than 2^31 - 1 outputs.
+ * Not done: the shift profile of the nearest distances and of the base pairs, several sets in one call, several devices. */
+int igd_hip_shift_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                          int32_t nctg, const int32_t *offsets, int64_t nshift, int32_t *out_qs, int32_t *out_qe);
+int igd_hip_shift_support(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                          const int32_t *offsets, int64_t nshift, int32_t v, int rule, int64_t *shifted,
+                          const igd_hip_min_overlap *min_overlap);
+
 /* Device-resident search: all pointers are device pointers on db's GPU; d_hits
  * (int64[nFiles]) is ADDED to; d_total (int64[1], may be NULL) is ADDED to.  Enqueues on
  * `stream` (a hipStream_t; NULL = the engine's own stream) and returns without waiting.
