@@ -12,7 +12,8 @@ __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "re
            "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace",
            "DatasetGroups", "build_groups", "read_groups_file", "GROUP_MAX", "ShiftSupport", "shift_offsets", "local_zscore"]
 # (igd_amd.group_support_host resolves below like the other host routes; it is not in __all__, whose `_host` names with regions are
-# the table of tests/test_database_args_host.py; so do igd_amd.shift_support_host and igd_amd.shift_regions_host)
+# the table of tests/test_database_args_host.py; so do igd_amd.shift_support_host, igd_amd.shift_regions_host
+# and igd_amd.resample_regions_host)
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -40,7 +41,8 @@ def __getattr__(name):
                 "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP",
                 "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace",
            "DatasetGroups", "build_groups", "read_groups_file", "group_support_host", "GROUP_MAX",
-                "ShiftSupport", "shift_offsets", "local_zscore", "shift_support_host", "shift_regions_host"):
+                "ShiftSupport", "shift_offsets", "local_zscore", "shift_support_host", "shift_regions_host",
+                "resample_regions_host"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

@@ -224,6 +224,14 @@ def hip():
                                             C.c_int64, C.c_void_p, C.c_void_p]
         L.igd_hip_shift_support.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                             C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
+        # the three nulls by resampling: db, ichr, qs, qe, nq, pool_ichr, pool_qs, pool_qe, npool, seed, nperm, then the entry's own
+        # arguments behind nperm; the generator alone: db, pool_ichr, pool_qs, pool_qe, npool, nq, seed, p0, np, out_ichr, out_qs, out_qe
+        rs = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64]
+        L.igd_hip_permute_support_rs.argtypes = rs + [C.c_int32, C.c_int] + [C.c_void_p] * 8
+        L.igd_hip_permute_nearest_rs.argtypes = rs + [C.c_int32, C.c_int32] + [C.c_void_p] * 3
+        L.igd_hip_permute_bp_rs.argtypes = rs + [C.c_int32, C.c_int] + [C.c_void_p] * 4
+        L.igd_hip_resample_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
+                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.igd_hip_membership_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int,
@@ -488,6 +496,15 @@ def _bind_core(L):
                                           C.c_void_p, C.c_void_p]
     L.igdc_shift_support_host_ov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                              C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
+    # the three nulls by resampling on the host: db, map, ichr, qs, qe, nq, pool_ichr, pool_qs, pool_qe, npool, seed, nperm, then the
+    # entry's own arguments behind nperm; the generator alone: pool_ichr, pool_qs, pool_qe, npool, nq, seed, p0, np, out_ichr, out_qs, out_qe
+    rs = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64,
+          C.c_int64]
+    L.igdc_permute_host_rs.argtypes = rs + [C.c_int32, C.c_int] + [C.c_void_p] * 8
+    L.igdc_permute_nearest_host_rs.argtypes = rs + [C.c_int32, C.c_int32] + [C.c_void_p] * 3
+    L.igdc_permute_bp_host_rs.argtypes = rs + [C.c_int32, C.c_int] + [C.c_void_p] * 4
+    L.igdc_resample_regions_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
     # db, path, len (int32[nCtg]), bad_line
     L.igdc_read_genome.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L

@@ -28,9 +28,17 @@ extern "C" int32_t igd_hip_permute_grid(int64_t n) { return items_grid(n, IGD_SE
 // it through run_perm_chunks with its offset table).  No public mode: perm_mode_ok refuses it for the three nulls.
 #define IGD_PERM_PLACE_SHIFT 3
 
-// a mode the call can run: the two free placements without a workspace, IGD_HIP_PERM_WORKSPACE with one
-static bool perm_mode_ok(int mode, const igd_hip_workspace *ws)
+// The pool of a resampling call (THE DRAW of include/igd_hip.h): host arrays of npool regions.  No pool: every other mode.
+struct PermPool {
+    const int32_t *ichr, *qs, *qe;
+    int64_t npool;
+};
+
+// a mode the call can run: the two free placements without a workspace, IGD_HIP_PERM_WORKSPACE with one, IGD_HIP_PERM_RESAMPLE
+// exactly when a pool is given and never with a workspace
+static bool perm_mode_ok(int mode, const igd_hip_workspace *ws, const PermPool *pool = nullptr)
 {
+    if (pool || mode == IGD_HIP_PERM_RESAMPLE) return pool && !ws && mode == IGD_HIP_PERM_RESAMPLE;
     return ws ? mode == IGD_HIP_PERM_WORKSPACE : (mode == IGD_HIP_PERM_CIRCULAR || mode == IGD_HIP_PERM_SHUFFLE);
 }
 
@@ -56,10 +64,15 @@ static bool perm_ws_refused(const char *who, const igd_hip_workspace *ws, const 
 // off its contig, a workspace table that is not valid for the database's contigs, the first region in no segment.  true, g_err
 // set, prefixed with `who`.  Each driver has its own check in front (min_overlap, the window); the support's bound on the sum of
 // squares runs BEHIND this function, so a call that also has one of the last three faults is now told of that fault instead.
+// With a pool (mode IGD_HIP_PERM_RESAMPLE) nothing is placed: no contig lengths are asked for and no region is validated; the
+// pool's size is held against the batch and against nq instead.
 static bool perm_args_refused(const char *who, const igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                              const int32_t *ctg_len, int mode, int64_t nperm, const igd_hip_workspace *ws, bool extraBad)
+                              const int32_t *ctg_len, int mode, int64_t nperm, const igd_hip_workspace *ws, bool extraBad,
+                              const PermPool *pool = nullptr)
 {
-    if (!db || nq < 0 || extraBad || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) || !perm_mode_ok(mode, ws)) {
+    const bool poolBad = pool && (pool->npool < 0 || (pool->npool > 0 && (!pool->ichr || !pool->qs || !pool->qe)));
+    if (!db || nq < 0 || extraBad || (nq > 0 && (!ichr || !qs || !qe)) || (!pool && !ctg_len && db->nCtg > 0) || poolBad ||
+        !perm_mode_ok(mode, ws, pool)) {
         snprintf(g_err, sizeof g_err, "%s: bad argument", who);
         return true;
     }
@@ -70,6 +83,14 @@ static bool perm_args_refused(const char *who, const igd_hip_db *db, const int32
     if (nq > max_batch()) {
         snprintf(g_err, sizeof g_err, "%s: %lld regions, more than %lld", who, (long long)nq, (long long)max_batch());
         return true;
+    }
+    if (pool) {
+        if (pool->npool > max_batch())
+            snprintf(g_err, sizeof g_err, "%s: a pool of %lld regions, more than %lld", who, (long long)pool->npool, (long long)max_batch());
+        else if (pool->npool < nq)
+            snprintf(g_err, sizeof g_err, "%s: %lld regions cannot be drawn without replacement from a pool of %lld", who, (long long)nq,
+                     (long long)pool->npool);
+        return pool->npool > max_batch() || pool->npool < nq;
     }
     const int64_t i = igd_hip_perm_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg);
     if (i >= 0) {
@@ -82,7 +103,8 @@ static bool perm_args_refused(const char *who, const igd_hip_db *db, const int32
 
 // THE PLACEMENT OF ONE CALL, written once for the two launch sites (run_perm_chunks, igd_hip_permute_regions_ws): the call's nq
 // regions and nctg contig lengths on the device (db->d_pmReg), the mode and, under IGD_HIP_PERM_WORKSPACE, the table (db->d_pmWs);
-// under IGD_PERM_PLACE_SHIFT the offsets, behind the contig lengths in db->d_pmReg.
+// under IGD_PERM_PLACE_SHIFT the offsets, behind the contig lengths in db->d_pmReg; under IGD_HIP_PERM_RESAMPLE the pool's three
+// arrays in the same place.
 struct PermPlace {
     const int32_t *rC, *rS, *rE, *rL;
     int64_t nq;
@@ -91,21 +113,35 @@ struct PermPlace {
     const int64_t *wOff;
     const int32_t *wStart, *wLen, *wPre;
     const int32_t *offs;
+    const int32_t *pC, *pS, *pE;
+    int64_t npool;
 };
 
+// the pool's three arrays to `at` (device, 3 * npool words) on the engine's stream, and into the placement
+static int perm_pool_upload(igd_hip_db *db, const PermPool &pool, int32_t *at, PermPlace *pl)
+{
+    const int64_t n = pool.npool;
+    pl->pC = at; pl->pS = at + n; pl->pE = at + 2 * n; pl->npool = n;
+    if (n == 0) return IGD_HIP_OK;
+    HIPCHK(hipMemcpyAsync(at, pool.ichr, (size_t)n * 4, hipMemcpyHostToDevice, db->stream));
+    HIPCHK(hipMemcpyAsync(at + n, pool.qs, (size_t)n * 4, hipMemcpyHostToDevice, db->stream));
+    HIPCHK(hipMemcpyAsync(at + 2 * n, pool.qe, (size_t)n * 4, hipMemcpyHostToDevice, db->stream));
+    return IGD_HIP_OK;
+}
+
 // both buffers grown, then on the engine's stream the table of a checked workspace (without one only the mode is kept) and the
-// regions with the contig lengths; offsets (nshift of them; NULL, 0 for the nulls) go up last
+// regions with the contig lengths; offsets (nshift of them; NULL, 0 for the nulls) or the pool of a resampling call go up last
 static int perm_place_upload(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
                              int32_t nctg, int mode, const igd_hip_workspace *ws, PermPlace *pl, const int32_t *offsets = nullptr,
-                             int64_t nshift = 0)
+                             int64_t nshift = 0, const PermPool *pool = nullptr)
 {
     const int64_t nc = ws ? ws->nctg : 0, ns = ws ? ws->nseg : 0;
     hipStream_t st = db->stream;
-    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg + nshift);
+    int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg + nshift + (pool ? 3 * pool->npool : 0));
     if (rc == IGD_HIP_OK && ws) rc = dev_grow(db, &db->d_pmWs, &db->pmWsCap, 2 * (nc + 1) + 3 * ns + nc + 1);
     if (rc != IGD_HIP_OK) return rc;
     int32_t *rC = db->d_pmReg, *rS = rC + nq, *rE = rS + nq, *rL = rE + nq;
-    *pl = PermPlace{rC, rS, rE, rL, nq, nctg, mode, nullptr, nullptr, nullptr, nullptr, nshift > 0 ? rL + nctg : nullptr};
+    *pl = PermPlace{rC, rS, rE, rL, nq, nctg, mode, nullptr, nullptr, nullptr, nullptr, nshift > 0 ? rL + nctg : nullptr, nullptr, nullptr, nullptr, 0};
     if (ws) {
         int64_t *dOff = (int64_t *)db->d_pmWs;
         int32_t *dStart = db->d_pmWs + 2 * (nc + 1), *dLen = dStart + ns, *dPre = dLen + ns;
@@ -122,15 +158,20 @@ static int perm_place_upload(igd_hip_db *db, const int32_t *ichr, const int32_t 
     HIPCHK(hipMemcpyAsync(rE, qe, (size_t)nq * 4, hipMemcpyHostToDevice, st));
     if (nctg > 0) HIPCHK(hipMemcpyAsync(rL, ctg_len, (size_t)nctg * 4, hipMemcpyHostToDevice, st));
     if (nshift > 0) HIPCHK(hipMemcpyAsync(rL + nctg, offsets, (size_t)nshift * 4, hipMemcpyHostToDevice, st));
+    if (pool) return perm_pool_upload(db, *pool, rL + nctg + nshift, pl);
     return IGD_HIP_OK;
 }
 
 // `total` outputs (permutations from p0 on, nq regions each) by the kernel of the call's placement; under IGD_PERM_PLACE_SHIFT
-// permutation p is the shift by offsets[p] and the seed is not read
+// permutation p is the shift by offsets[p] and the seed is not read; under IGD_HIP_PERM_RESAMPLE the outputs are pool regions, the
+// call's own are not read and oC is always written
 static int permute_launch(igd_hip_db *db, const PermPlace &pl, u64 seed, u64 p0, int64_t total, int32_t *oC, int32_t *oS, int32_t *oE)
 {
     const unsigned grid = (unsigned)igd_hip_permute_grid(total);
-    if (pl.mode == IGD_PERM_PLACE_SHIFT)
+    if (pl.mode == IGD_HIP_PERM_RESAMPLE)
+        igd_resample_regions<<<grid, IGD_SETS_WG, 0, db->stream>>>(pl.pC, pl.pS, pl.pE, (unsigned)pl.npool, (unsigned)pl.nq, seed, p0, (unsigned)total,
+                                                                 oC, oS, oE);
+    else if (pl.mode == IGD_PERM_PLACE_SHIFT)
         igd_shift_regions<<<grid, IGD_SETS_WG, 0, db->stream>>>(pl.rC, pl.rS, pl.rE, (unsigned)pl.nq, pl.rL, pl.nctg, pl.offs, (unsigned)p0,
                                                               (unsigned)total, oC, oS, oE);
     else if (pl.mode == IGD_HIP_PERM_WORKSPACE)
@@ -164,11 +205,12 @@ static std::vector<SetSlice> perm_row_slices(int64_t pc, int64_t nq, int64_t sli
 // generator's output in the staging arrays (r0 = 1 + p0); the call with r0 + rows == nperm + 1 is the last.  Everything is on the
 // engine's stream without a wait in between, unless count waits itself; ONE wait at the end, behind which the callers write
 // their results.  offsets (NULL for the three nulls): the table of mode IGD_PERM_PLACE_SHIFT, nperm entries -- "permutation" p
-// is then the set shifted by offsets[p], and the caller's count has nothing to do with the set as given.
+// is then the set shifted by offsets[p], and the caller's count has nothing to do with the set as given.  pool (NULL but for
+// mode IGD_HIP_PERM_RESAMPLE, which has no ctg_len): its regions go up behind the call's, and permutation p is a draw from it.
 template <typename Prepare, typename Count>
 static int run_perm_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
                            int mode, uint64_t seed, int64_t nperm, const igd_hip_workspace *ws, int64_t rowBytes, Prepare &&prepare,
-                           Count &&count, const int32_t *offsets = nullptr)
+                           Count &&count, const int32_t *offsets = nullptr, const PermPool *pool = nullptr)
 {
     HIPCHK(hipSetDevice(db->device));
     int64_t pc = max_batch() / nq;
@@ -180,7 +222,7 @@ static int run_perm_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *q
     int rc = prepare(pc, sliceLen, perRow);
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
     PermPlace pl;
-    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, db->nCtg, mode, ws, &pl, offsets, offsets ? nperm : 0);
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, pool ? 0 : db->nCtg, mode, ws, &pl, offsets, offsets ? nperm : 0, pool);
     if (rc == IGD_HIP_OK) rc = count(pl.rC, pl.rS, pl.rE, (int64_t)1, (int64_t)0);      // the set as given
     for (int64_t p0 = 0; rc == IGD_HIP_OK && p0 < nperm; p0 += pc) {
         const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
@@ -232,24 +274,25 @@ static void perm_copy_out(const int64_t *res, int64_t nC, int64_t *const out[7])
         if (out[a]) memcpy(out[a], res + a * nC, (size_t)nC * 8);
 }
 
-extern "C" int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule,
-                                          int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
-                                          int64_t *pmax, const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
+// the body of igd_hip_permute_support_ws and, with a pool and no ctg_len, of igd_hip_permute_support_rs
+static int permute_support_run(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                               int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
+                               const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws, const PermPool *pool)
 {
     if (!igd_hip_min_overlap_valid(min_overlap)) {
-        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: min_overlap (%d bp, %d ppm, %d ppm) out of range", (int)min_overlap->min_bp,
+        snprintf(g_err, sizeof g_err, "%s: min_overlap (%d bp, %d ppm, %d ppm) out of range", who, (int)min_overlap->min_bp,
                  (int)min_overlap->ppm_query, (int)min_overlap->ppm_record);
         return IGD_HIP_ERR_ARG;
     }
     const bool ov = igd_hip_min_overlap_active(min_overlap);
     const MinOv mo = min_ov_of(min_overlap);
-    if (perm_args_refused("igd_hip_permute_support", db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws,
-                          !observed || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)))
+    if (perm_args_refused(who, db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws,
+                          !observed || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT), pool))
         return IGD_HIP_ERR_ARG;
     if ((unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63) {
-        snprintf(g_err, sizeof g_err, "igd_hip_permute_support: %lld permutations of %lld regions: the sum of squares may pass 2^63",
-                 (long long)nperm, (long long)nq);
+        snprintf(g_err, sizeof g_err, "%s: %lld permutations of %lld regions: the sum of squares may pass 2^63", who, (long long)nperm,
+                 (long long)nq);
         return IGD_HIP_ERR_ARG;
     }
     const int64_t nF = db->nFiles, nC = nF + 1;
@@ -294,10 +337,30 @@ extern "C" int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, c
         if (r0 + rows == nperm + 1) HIPCHK(hipMemcpyAsync(res.data(), db->d_pmStat, (size_t)(7 * nC) * 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
-    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, nF * 8, prepare, count);
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, nF * 8, prepare, count, nullptr, pool);
     if (rc != IGD_HIP_OK) return rc;
     perm_copy_out(res.data(), nC, out);
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule,
+                                          int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
+                                          int64_t *pmax, const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
+{
+    return permute_support_run("igd_hip_permute_support", db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge,
+                               n_le, pmin, pmax, min_overlap, ws, nullptr);
+}
+
+extern "C" int igd_hip_permute_support_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                          const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool,
+                                          uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum,
+                                          int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
+                                          const igd_hip_min_overlap *min_overlap)
+{
+    const PermPool pool{pool_ichr, pool_qs, pool_qe, npool};
+    return permute_support_run("igd_hip_permute_support_rs", db, ichr, qs, qe, nq, nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, v, rule, observed,
+                               sum, sumsq, n_ge, n_le, pmin, pmax, min_overlap, nullptr, &pool);
 }
 
 extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -356,6 +419,49 @@ extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, cons
                                        int32_t *out_qs, int32_t *out_qe)
 {
     return igd_hip_permute_regions_ws(db, ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe, nullptr);
+}
+
+// the generator of the resampling null alone: draws [p0, p0 + np) of nq regions from the pool, chunked as igd_hip_permute_regions
+extern "C" int igd_hip_resample_regions(igd_hip_db *db, const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe,
+                                        int64_t npool, int64_t nq, uint64_t seed, int64_t p0, int64_t np, int32_t *out_ichr, int32_t *out_qs,
+                                        int32_t *out_qe)
+{
+    if (!db || nq < 0 || np < 0 || p0 < 0 || npool < 0 || (npool > 0 && (!pool_ichr || !pool_qs || !pool_qe)) ||
+        (nq > 0 && np > 0 && (!out_ichr || !out_qs || !out_qe)) || nq > max_batch() || npool > max_batch() ||
+        (nq > 0 && np > (int64_t)INT32_MAX / nq)) {
+        snprintf(g_err, sizeof g_err, "igd_hip_resample_regions: bad argument");
+        return IGD_HIP_ERR_ARG;
+    }
+    if (npool < nq) {
+        snprintf(g_err, sizeof g_err, "igd_hip_resample_regions: %lld regions cannot be drawn without replacement from a pool of %lld",
+                 (long long)nq, (long long)npool);
+        return IGD_HIP_ERR_ARG;
+    }
+    if (nq == 0 || np == 0) return IGD_HIP_OK;
+    const int64_t pc = max_batch() / nq < np ? max_batch() / nq : np;
+    std::vector<int32_t> h((size_t)(3 * np * nq));
+    int32_t *hc = h.data(), *hs = hc + np * nq, *he = hs + np * nq;
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = db->stream;
+    int rc = ensure_qstage(db, pc * nq);
+    if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * npool);
+    if (rc != IGD_HIP_OK) return rc;
+    PermPlace pl{nullptr, nullptr, nullptr, nullptr, nq, 0, IGD_HIP_PERM_RESAMPLE, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    const PermPool pool{pool_ichr, pool_qs, pool_qe, npool};
+    if ((rc = perm_pool_upload(db, pool, db->d_pmReg, &pl)) != IGD_HIP_OK) return rc;
+    for (int64_t a = 0; a < np; a += pc) {
+        const int64_t n = np - a < pc ? np - a : pc;
+        if ((rc = permute_launch(db, pl, (u64)seed, (u64)(p0 + a), n * nq, db->d_qc, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
+        HIPCHK(hipMemcpyAsync(hc + a * nq, db->d_qc, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hs + a * nq, db->d_qs, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(he + a * nq, db->d_qe, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    memcpy(out_ichr, hc, (size_t)(np * nq) * 4);
+    memcpy(out_qs, hs, (size_t)(np * nq) * 4);
+    memcpy(out_qe, he, (size_t)(np * nq) * 4);
+    return IGD_HIP_OK;
 }
 
 extern "C" int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t nrows, int64_t ncols, const int64_t *observed,

@@ -21,11 +21,13 @@ extern "C" int64_t igd_hip_merge_slices_per_row(int64_t pc, int64_t nq)
     return (nq + sliceLen - 1) / sliceLen;
 }
 
-extern "C" int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
-                                     int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp,
-                                     int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
+// the body of igd_hip_permute_bp_ws and, with a pool and no ctg_len, of igd_hip_permute_bp_rs (whose drawn rows drop what their own
+// regions make them drop; n_dropped stays row 0's)
+static int permute_bp_run(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp,
+                          int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws, const PermPool *pool)
 {
-    if (perm_args_refused("igd_hip_permute_bp", db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT))
+    if (perm_args_refused(who, db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT, pool))
         return IGD_HIP_ERR_ARG;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     if (nq == 0) {                                       // no region: no run, no base pair
@@ -89,7 +91,7 @@ extern "C" int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const 
         if (r0 == 0) HIPCHK(hipMemcpyAsync(hDrop, dDrop, 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
-    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, nF * 8, prepare, count);
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, nF * 8, prepare, count, nullptr, pool);
     if (rc != IGD_HIP_OK) return rc;
     if (inter)
         for (int64_t r = 0; r < R; r++) {
@@ -100,6 +102,24 @@ extern "C" int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const 
     if (n_merged) memcpy(n_merged, hRuns, (size_t)R * 8);
     if (n_dropped) *n_dropped = *hDrop;
     return IGD_HIP_OK;
+}
+
+extern "C" int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                                     int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp,
+                                     int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
+{
+    return permute_bp_run("igd_hip_permute_bp", db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, ws,
+                          nullptr);
+}
+
+extern "C" int igd_hip_permute_bp_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                     const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                                     int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
+                                     int64_t *n_dropped)
+{
+    const PermPool pool{pool_ichr, pool_qs, pool_qe, npool};
+    return permute_bp_run("igd_hip_permute_bp_rs", db, ichr, qs, qe, nq, nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, v, rule, inter, set_bp,
+                          n_merged, n_dropped, nullptr, &pool);
 }
 
 extern "C" int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,

@@ -1567,13 +1567,19 @@ static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int
  * fits in no segment of its contig end the run with a message (the latter names the line) and exit code EX_USAGE; regions that
  * do not lie inside the workspace as given are counted on stderr and the run goes on.  g_ws: the table of the run, or NULL. */
 static const igd_hip_workspace *g_ws = NULL;
+/* `-M resample -U universe.bed` draws every permuted set from the universe instead of placing it (include/igd_hip.h: THE DRAW;
+ * pmode is IGD_HIP_PERM_RESAMPLE then, -g and -W are refused): the universe is read as `-U` reads it everywhere, there is no genome
+ * file and no region is held against a contig's length, and the statistic's route is the _rs form; the three tables keep their
+ * layout.  A set larger than the universe ends the run with a message on stderr and exit code EX_USAGE; the set need not be a subset
+ * of the universe.  g_pool: the universe of the run, or NULL. */
+static const igdc_queries *g_pool = NULL;
 /* `-G` switches it to base pairs (permute_bp_table below); it takes no sum of squares on the device, so the guard on it does not apply. */
 static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int rule);
 /* `-Z W,STEP` prints the shift profile of the support instead (shift_table below): nshift > 0 offsets; nperm may be 0 then. */
 static void shift_table(const igdc_queries *q, const int32_t *len, const int32_t *offsets, int nshift, int64_t nperm, uint64_t seed, int pmode,
                         int32_t ev, int rule);
-static void permute_file(char *path, const char *genome, const char *wsName, int64_t nperm, uint64_t seed, int pmode, int32_t v, int32_t window,
-                         int gbp, const int32_t *offsets, int nshift)
+static void permute_file(char *path, const char *genome, const char *wsName, const char *uniName, int64_t nperm, uint64_t seed, int pmode,
+                         int32_t v, int32_t window, int gbp, const int32_t *offsets, int nshift)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
     const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
@@ -1581,7 +1587,7 @@ static void permute_file(char *path, const char *genome, const char *wsName, int
     const int32_t ev = q_dispatch(v, &rule);
     int32_t *len = (int32_t *)calloc((size_t)g_core->nCtg + 1, sizeof(int32_t));
     int64_t bad = 0;
-    const int grc = len ? igdc_read_genome(g_core, genome, len, &bad) : -1;
+    const int grc = !len ? -1 : uniName ? 0 : igdc_read_genome(g_core, genome, len, &bad);   /* (resampling: no genome file) */
     if (grc == -1) { printf("Cannot open genome file %s\n", genome); free(len); return; }
     if (grc != 0) {
         printf("Genome file %s, line %lld: not a name, a tab and a length of at most 2147483647\n", genome, (long long)bad);
@@ -1593,6 +1599,8 @@ static void permute_file(char *path, const char *genome, const char *wsName, int
     memset(&q, 0, sizeof q);
     int64_t no = 0, *lineOf = NULL, lineCap = 0;                             /* -W: the line of every accepted region */
     igd_hip_workspace *ws = NULL;
+    igdc_queries uq;                                                         /* -M resample: the universe */
+    memset(&uq, 0, sizeof uq);
     igdc_lines *r = igdc_lines_open(path);
     char *line;
     while (r && (line = igdc_lines_next(r, NULL)) != NULL) {
@@ -1602,6 +1610,10 @@ static void permute_file(char *path, const char *genome, const char *wsName, int
         if (!chrm) continue;
         const int32_t id = igdc_get_id(g_core, chrm);
         if (id < 0) continue;
+        if (uniName) {                                                       /* (nothing is placed: no region is held against a length) */
+            if (igdc_queries_push(&q, id, st, en) != 0) { fprintf(stderr, "igd: out of memory\n"); goto done; }
+            continue;
+        }
         if (len[id] < 1) {
             printf("%s, line %lld: contig %s is not in the genome file %s\n", path, (long long)no, g_core->cName[id], genome);
             goto done;
@@ -1639,6 +1651,25 @@ static void permute_file(char *path, const char *genome, const char *wsName, int
         if (outside > 0) fprintf(stderr, "%lld of %lld regions do not lie inside the workspace\n", (long long)outside, (long long)q.n);
         g_ws = ws;
     }
+    if (uniName) {
+        if (igdc_read_queries(g_core, uniName, 1, &uq) != 0 || uq.n == 0) {
+            printf("Cannot read universe file %s, or it holds no region\n", uniName);
+            goto done;
+        }
+        if (q.n > uq.n) {
+            fprintf(stderr, "Not supported: -M resample with a set of %lld regions, more than the %lld of the universe %s\n", (long long)q.n,
+                    (long long)uq.n, uniName);
+            g_usage_rc = 1;
+            goto done;
+        }
+        if (uq.n > igd_hip_max_batch()) {
+            fprintf(stderr, "Not supported: -M resample with a universe of %lld regions, more than %lld\n", (long long)uq.n,
+                    (long long)igd_hip_max_batch());
+            g_usage_rc = 1;
+            goto done;
+        }
+        g_pool = &uq;
+    }
     if (q.n > igd_hip_max_batch() ||
         (window < 0 && !gbp && (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63)) {
         printf("Not supported: -P %lld with %lld regions\n", (long long)nperm, (long long)q.n);
@@ -1654,11 +1685,15 @@ static void permute_file(char *path, const char *genome, const char *wsName, int
         int64_t *obs = st7, *sum = obs + nC, *ssq = sum + nC, *nge = ssq + nC, *nle = nge + nC, *mn = nle + nC, *mx = mn + nC;
         cli_route R;
         if (route_host(&R, q.n * (nperm + 1)))
-            route_host_end(&R, igdc_permute_host_ws(g_core, R.hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo, g_ws) == 0,
+            route_host_end(&R, (g_pool ? igdc_permute_host_rs(g_core, R.hm, q.ichr, q.qs, q.qe, q.n, g_pool->ichr, g_pool->qs, g_pool->qe, g_pool->n, seed,
+                                                              nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo)
+                                       : igdc_permute_host_ws(g_core, R.hm, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo, g_ws)) == 0,
                            "permutation null on the host (small files)");
         if (route_engine(&R, 1))
             route_engine_end(&R, "permutation null",
-                             igd_hip_permute_support_ws(R.dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo, g_ws),
+                             g_pool ? igd_hip_permute_support_rs(R.dev, q.ichr, q.qs, q.qe, q.n, g_pool->ichr, g_pool->qs, g_pool->qe, g_pool->n, seed, nperm, ev,
+                                                                 rule, obs, sum, ssq, nge, nle, mn, mx, g_mo)
+                                    : igd_hip_permute_support_ws(R.dev, q.ichr, q.qs, q.qe, q.n, len, pmode, seed, nperm, ev, rule, obs, sum, ssq, nge, nle, mn, mx, g_mo, g_ws),
                              "permutation null of the query file (H2D + permute, support and statistics kernels + D2H)");
         if (!g_fail_rc && igdc_perm_summary(obs, sum, ssq, nge, nle, nperm, nC, fl, fl + nC, fl + 2 * nC, fl + 3 * nC, fl + 4 * nC) == 0) {
             printf("index\tobserved\tmean\tsd\tz\tn_ge\tn_le\tnlog10_p_upper\tnlog10_p_lower\tFile\n");
@@ -1675,6 +1710,8 @@ done:
     if (r) igdc_lines_close(r);
     igdc_queries_free(&q);
     g_ws = NULL;
+    g_pool = NULL;
+    igdc_queries_free(&uq);
     igdc_workspace_free(ws);
     free(lineOf);
     free(len);
@@ -1757,6 +1794,11 @@ static int refused_shift(const char *why, const char *arg)                   /* 
 {
     fprintf(stderr, "Not supported: %s%s\n", why, arg ? arg : "");
     return EX_USAGE;
+}
+
+static int refused_resample(const char *why)                                 /* -M resample's refusals: stderr, nothing on stdout */
+{
+    return refused_shift(why, NULL);
 }
 
 /* ------------------------------- `igd search -q F -N <bp>` / `-Q <list> -N <bp>` ------- */
@@ -1981,11 +2023,15 @@ static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int
     double *wm = fl, *ws = wm + nC, *wz = ws + nC, *pu = wz + nC, *md = pu + nC, *dm = md + nC, *ds = dm + nC, *dz = ds + nC, *pl = dz + nC;
     cli_route Rt;
     if (route_host(&Rt, q->n * (nperm + 1)))
-        route_host_end(&Rt, igdc_permute_nearest_host_ws(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd, g_ws) == 0,
+        route_host_end(&Rt, (g_pool ? igdc_permute_nearest_host_rs(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, g_pool->ichr, g_pool->qs, g_pool->qe, g_pool->n,
+                                                                   seed, nperm, window, ev, nw, no, sd)
+                                    : igdc_permute_nearest_host_ws(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd, g_ws)) == 0,
                        "permutation null of the distances on the host (small files)");
     if (route_engine(&Rt, 1))
         route_engine_end(&Rt, "permutation null of the distances",
-                         igd_hip_permute_nearest_ws(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd, g_ws),
+                         g_pool ? igd_hip_permute_nearest_rs(Rt.dev, q->ichr, q->qs, q->qe, q->n, g_pool->ichr, g_pool->qs, g_pool->qe, g_pool->n, seed, nperm,
+                                                             window, ev, nw, no, sd)
+                                : igd_hip_permute_nearest_ws(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, window, ev, nw, no, sd, g_ws),
                          "permutation null of the distances (H2D + permute and fused nearest kernels + D2H)");
     if (!g_fail_rc && igdc_perm_nearest_summary(nw, sd, nperm, (int64_t)nC, wm, ws, wz, nge, pu, md, dm, ds, dz, ndef, nle, pl) == 0) {
         printf("index\tn_within\tmean_dist\twithin_mean\twithin_sd\twithin_z\tnlog10_p_within_upper\tdist_mean\tdist_sd\tdist_z\tn_def\tdist_n_le\t"
@@ -2027,11 +2073,15 @@ static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t 
     double *mu = fl, *sd = mu + nC, *z = sd + nC, *fold = z + nC, *pu = fold + nC, *pl = pu + nC, *jac = pl + nC, *jm = jac + nC, *js = jm + nC;
     cli_route Rt;
     if (route_host(&Rt, q->n * (nperm + 1)))
-        route_host_end(&Rt, igdc_permute_bp_host_ws(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd, g_ws) == 0 &&
+        route_host_end(&Rt, (g_pool ? igdc_permute_bp_host_rs(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, g_pool->ichr, g_pool->qs, g_pool->qe, g_pool->n, seed,
+                                                              nperm, ev, rule, inter, sbp, nm, nd)
+                                    : igdc_permute_bp_host_ws(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd, g_ws)) == 0 &&
                            igdc_dataset_bp_host(g_core, Rt.hm, ev, rule, fbp) == 0,
                        "permutation null of the base-pair overlap on the host (small files)");
     if (route_engine(&Rt, 1)) {
-        int rc = igd_hip_permute_bp_ws(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd, g_ws);
+        int rc = g_pool ? igd_hip_permute_bp_rs(Rt.dev, q->ichr, q->qs, q->qe, q->n, g_pool->ichr, g_pool->qs, g_pool->qe, g_pool->n, seed, nperm, ev, rule,
+                                                inter, sbp, nm, nd)
+                        : igd_hip_permute_bp_ws(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, ev, rule, inter, sbp, nm, nd, g_ws);
         if (rc == IGD_HIP_OK) rc = igd_hip_dataset_bp(Rt.dev, ev, rule, fbp);
         route_engine_end(&Rt, "permutation null of the base-pair overlap", rc,
                          "permutation null of the base-pair overlap (H2D + permute, merge, hand-over and coverage kernels + D2H)");
@@ -2081,6 +2131,9 @@ static int usage_search(void)
             "    -g <genome file>           with -P: the contig lengths, one name<TAB>length per line\n"
             "    -S <seed>  -M <mode>       with -P: the seed (default 0); circular (default: one rigid shift per contig) or\n"
             "                               shuffle (every region placed anew on its contig)\n"
+            "    -M resample -U <universe>  with -P, without -g: every permuted set is as many regions as the query file holds, drawn\n"
+            "                               without replacement from the universe file (contig, start and end as they stand);\n"
+            "                               with -D or -G the null of the distances or of the base pairs, tables as under -P\n"
             "    -O <bp>  -A <F>  -B <F>    minimum overlap of a counted (query region, record) pair: at least <bp> base pairs,\n"
             "                               the fraction F of the query region (-A), of the record (-B); F is a decimal in [0, 1]\n"
             "                               with at most six places.  With -q or -Q alone, -u, -U [-R] and -P\n"
@@ -2120,6 +2173,19 @@ static int parse_perm_count(const char *arg, long long *np)
     char *end = NULL;
     *np = strtoll(arg, &end, 10);
     return end != arg && !*end && *np >= 1 && *np <= (long long)IGD_HIP_PERM_MAX;
+}
+
+/* `-D <bp>`: the window of the distance null into *w; 0 with its one refusal line on `to` for anything but 0 .. 2^30 */
+static int parse_dist_window(const char *arg, FILE *to, int32_t *w)
+{
+    char *end = NULL;
+    const long long ww = strtoll(arg, &end, 10);
+    if (end == arg || *end || ww < 0 || ww > (long long)IGD_HIP_NEAREST_MAX_WINDOW) {
+        fprintf(to, "Not supported: -D %s (a window of 0 to %lld base pairs)\n", arg, (long long)IGD_HIP_NEAREST_MAX_WINDOW);
+        return 0;
+    }
+    *w = (int32_t)ww;
+    return 1;
 }
 
 /* `-M <mode>`: circular (also without -M) or shuffle; -1: neither */
@@ -2314,6 +2380,25 @@ int igd_search(int argc, char **argv)                                        /* 
         if ((nShift = parse_shifts(shiftArg, &shiftOff)) < 1)
             return refused_shift("-Z W,STEP needs 0 <= W <= 1073741824, STEP >= 1 and at most 4096 shifts, not ", shiftArg);
     }
+    /* -M resample: every refusal is a usage error.  It is the one -P that takes -U, so it is decided in front of the blocks of -G
+     * and -D below, which refuse -U and are skipped for it; -Z above has refused it already (its parse_perm_mode knows circular and
+     * shuffle only). */
+    const int resample = permArg && pmodeArg && strcmp(pmodeArg, "resample") == 0;
+    int32_t distW = -1;                                                       /* -D's window, here or in -D's own block below */
+    if (resample) {
+        const char *why = NULL;
+        if (!uniName) why = "-M resample without -U";
+        else if (genomeName || wsName) why = "-M resample together with -g or -W (the universe is the placement)";
+        else if (listName || ranks || restricted || grpName || shiftArg) why = "-M resample together with -Q, -R, -X, -K or -Z";
+        else if (uniq || bp || memb || cooc || full || other || jac || mapArg || nearArg || histArg || flankL || flankEdges)
+            why = "-M resample together with -u, -b, -w, -C, -f, -m, -s, -r, -J, -V, -N, -H, -L or -E";
+        else if (distArg && gbp) why = "-M resample together with both -D and -G";
+        else if ((distArg || gbp) && minov) why = "-M resample -D or -G together with -O, -A or -B";
+        else if (mode != 1) why = "-M resample without -q";
+        else if (!parse_perm_count(permArg, &np)) why = "-M resample with a number of permutations outside 1 to 1048576";
+        if (why) return refused_resample(why);
+        if (distArg && !parse_dist_window(distArg, stderr, &distW)) return EX_USAGE;
+    }
     if (grpName) {                                                            /* -K: every refusal is a usage error */
         const char *why = NULL;
         if (bp || memb || restricted || cooc || permArg || distArg || gbp || wsName || jac || mapArg || nearArg || histArg || flankL || flankEdges ||
@@ -2329,7 +2414,7 @@ int igd_search(int argc, char **argv)                                        /* 
         if (!permArg) return refused_usage("-W without -P");
         if (pmodeArg) return refused_usage("-W together with -M (the workspace is the placement)");
     }
-    if (gbp) {                                                                /* -G: every refusal is a usage error */
+    if (gbp && !resample) {                                                   /* -G: every refusal is a usage error */
         const char *why = NULL;
         if (!permArg) why = "-G without -P";
         else if (distArg || jac || minov || nearArg || histArg || flankL || flankEdges || mapArg || listName || uniq || bp || memb || uniName ||
@@ -2395,10 +2480,7 @@ int igd_search(int argc, char **argv)                                        /* 
             return EX_USAGE;
         }
     }
-    int32_t distW = -1;                                                       /* -D: every refusal is a usage error */
-    if (distArg) {
-        char *end = NULL;
-        const long long w = strtoll(distArg, &end, 10);
+    if (distArg && !resample) {                                               /* -D: every refusal is a usage error */
         const char *why = NULL;
         if (!permArg) why = "-D without -P";
         else if (nearArg || minov || listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)
@@ -2408,11 +2490,7 @@ int igd_search(int argc, char **argv)                                        /* 
         else if (!parse_perm_count(permArg, &np)) why = "-D with a number of permutations outside 1 to 1048576";
         else if (parse_perm_mode(pmodeArg) < 0) why = "-D with a -M that is neither circular nor shuffle";
         if (why) return refused_usage(why);
-        if (end == distArg || *end || w < 0 || w > (long long)IGD_HIP_NEAREST_MAX_WINDOW) {
-            printf("Not supported: -D %s (a window of 0 to %lld base pairs)\n", distArg, (long long)IGD_HIP_NEAREST_MAX_WINDOW);
-            return EX_USAGE;
-        }
-        distW = (int32_t)w;
+        if (!parse_dist_window(distArg, stdout, &distW)) return EX_USAGE;
     }
     int32_t nearW = 0;                                                        /* -N: the older wording, and exit code 0 */
     if (nearArg) {
@@ -2444,9 +2522,12 @@ int igd_search(int argc, char **argv)                                        /* 
     cli_paths P;
     memset(&P, 0, sizeof P);
     if (shiftArg) {
-        permute_file(qfName, genomeName, wsName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0,
+        permute_file(qfName, genomeName, wsName, NULL, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0,
                      wsName ? IGD_HIP_PERM_WORKSPACE : parse_perm_mode(pmodeArg), v, -1, 0, shiftOff, nShift);
         free(shiftOff);
+    } else if (resample) {
+        permute_file(qfName, NULL, NULL, uniName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, IGD_HIP_PERM_RESAMPLE, v, distW, gbp,
+                     NULL, 0);
     } else if (!permArg && (genomeName || seedArg || pmodeArg)) {
         printf("Not supported: -g, -S or -M without -P\n");
         return EX_OK;
@@ -2478,7 +2559,7 @@ int igd_search(int argc, char **argv)                                        /* 
             printf("Not supported: -M %s (circular or shuffle)\n", pmodeArg);
             return EX_OK;
         }
-        permute_file(qfName, genomeName, wsName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW, gbp, NULL, 0);
+        permute_file(qfName, genomeName, wsName, NULL, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW, gbp, NULL, 0);
     } else if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
         printf("Not supported: -C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r\n");
         return EX_OK;

@@ -360,6 +360,24 @@ int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int
 int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                             const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
                             int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws);
+/* The three nulls by resampling from a universe on the host (what igd_hip_permute_*_rs and igd_hip_resample_regions compute;
+ * include/igd_hip.h has THE DRAW, the outputs and the refusals).  igdc_resample_regions_host is kernel igd_resample_regions: draws
+ * [p0, p0 + np) of nq regions from the pool into out_ichr, out_qs, out_qe (int32[np * nq], draw-major).  The _rs forms are the _ws
+ * forms with a pool in the place of ctg_len, mode and workspace: row 0 is the set as given, a row r > 0 is filled by draw r - 1
+ * instead of the generator, and walked with the drawn contigs.  0 on success; -1 for a refused argument -- the engine's
+ * refusals -- or when a tile could not be read (nothing written). */
+int igdc_resample_regions_host(const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, int64_t nq,
+                               uint64_t seed, int64_t p0, int64_t np, int32_t *out_ichr, int32_t *out_qs, int32_t *out_qe);
+int igdc_permute_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                         int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le,
+                         int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap);
+int igdc_permute_nearest_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                 const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                                 int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist);
+int igdc_permute_bp_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                            const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                            int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped);
 /* The support of a region set under rigid shifts on the host (what igd_hip_shift_regions and igd_hip_shift_support compute;
  * include/igd_hip.h has THE SHIFT, the outputs and the refusals).  igdc_shift_regions_host is kernel igd_shift_regions: nq regions
  * under each of nshift offsets into out_qs, out_qe (int32[nshift * nq], shift-major); nctg is the caller's.

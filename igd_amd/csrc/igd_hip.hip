@@ -332,7 +332,7 @@ struct igd_hip_db {
     u64 *d_coCols, *d_coMat, *d_coA, *d_coB;
     int64_t coColsCap, coMatCap, coACap, coBCap;
     // perm_place_upload (host_permute.hpp), for run_perm_chunks -- the three permutation nulls -- and igd_hip_permute_regions: the
-    // call's regions and contig lengths (ichr, qs, qe, ctg_len), behind them the offsets of a shift call (host_shift.hpp).  igd_hip_permute_support / igd_hip_perm_stats: observed with the
+    // call's regions and contig lengths (ichr, qs, qe, ctg_len), behind them the offsets of a shift call (host_shift.hpp) or the pool of a resampling call.  igd_hip_permute_support / igd_hip_perm_stats: observed with the
     // six statistics (64-bit words)
     int32_t *d_pmReg;
     long long *d_pmStat;
@@ -413,6 +413,7 @@ struct igd_hip_db {
 #include "engine/permute_dev.hpp"     // igd_permute_regions, igd_perm_stats: shifted / shuffled region sets, column statistics of a row matrix -- permutation null
 #include "engine/permute_ws_dev.hpp"  // igd_permute_workspace: the same launch, regions placed inside a workspace by two binary searches in a resident table
 #include "engine/shift_dev.hpp"       // igd_shift_regions: the same launch, the set moved rigidly by each offset of a resident table -- local z-score
+#include "engine/resample_dev.hpp"    // igd_resample_regions: the same launch, each output a pool region drawn without replacement by a keyed bijection -- resampling null
 #include "engine/nearest_dev.hpp"     // igd_nearest_rows, igd_nearest_reduce, igd_nearest_hist: the same walk over a widened interval, one (signed) distance row per region -- nearest record per dataset
 #include "engine/flank_dev.hpp"       // igd_flank_rows, igd_flank_reldist: the same walk with two minima per region and dataset -- the nearest record on each side, the relative-distance histogram
 #include "engine/nearest_fused_dev.hpp" // igd_nearest_slices: the same walk and table, folded into per-slice LDS accumulators -- the set statistics without the rows

@@ -610,6 +610,51 @@ int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
     return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, ws) : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_resample_regions(igd_hip_db *db, const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool,
+                             int64_t nq, uint64_t seed, int64_t p0, int64_t np, int32_t *out_ichr, int32_t *out_qs, int32_t *out_qe)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, int64_t, uint64_t, int64_t, int64_t, int32_t *,
+                        int32_t *, int32_t *);
+    RESOLVE(fn_t, "igd_hip_resample_regions");
+    return fn ? fn(db, pool_ichr, pool_qs, pool_qe, npool, nq, seed, p0, np, out_ichr, out_qs, out_qe) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_support_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                               int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge,
+                               int64_t *n_le, int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, const int32_t *,
+                        const int32_t *, int64_t, uint64_t, int64_t, int32_t, int, int64_t *, int64_t *, int64_t *, int64_t *, int64_t *,
+                        int64_t *, int64_t *, const igd_hip_min_overlap *);
+    RESOLVE(fn_t, "igd_hip_permute_support_rs");
+    return fn ? fn(db, ichr, qs, qe, nq, pool_ichr, pool_qs, pool_qe, npool, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax,
+                   min_overlap)
+              : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_nearest_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                               int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, const int32_t *,
+                        const int32_t *, int64_t, uint64_t, int64_t, int32_t, int32_t, int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_permute_nearest_rs");
+    return fn ? fn(db, ichr, qs, qe, nq, pool_ichr, pool_qs, pool_qe, npool, seed, nperm, window, v, n_within, n_overlap, sum_dist)
+              : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_bp_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                          const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                          int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, const int32_t *,
+                        const int32_t *, int64_t, uint64_t, int64_t, int32_t, int, int64_t *, int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_permute_bp_rs");
+    return fn ? fn(db, ichr, qs, qe, nq, pool_ichr, pool_qs, pool_qe, npool, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped)
+              : IGD_HIP_ERR_DEVICE;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

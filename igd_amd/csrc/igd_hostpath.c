@@ -1179,6 +1179,42 @@ int igdc_shift_regions_host(const int32_t *ichr, const int32_t *qs, const int32_
     return 0;
 }
 
+/* The pool of a resampling call (include/igd_hip.h: THE DRAW) and the draws themselves, on checked arguments (nq <= npool): draw i
+ * of permutation p0 + p is pool region igd_hip_resample_index(base, i, npool), copied as it stands. */
+typedef struct { const int32_t *ichr, *qs, *qe; int64_t npool; } perm_pool;
+static void resample_regions_fill(const perm_pool *pool, int64_t nq, uint64_t seed, int64_t p0, int64_t np, int32_t *out_ichr,
+                                  int32_t *out_qs, int32_t *out_qe)
+{
+    const int h = igd_hip_resample_bits((uint64_t)pool->npool);
+    for (int64_t p = 0; p < np; p++) {
+        const uint64_t base = igd_hip_perm_base(seed, (uint64_t)(p0 + p));
+        for (int64_t i = 0; i < nq; i++) {
+            const uint64_t k = igd_hip_resample_walk(base, (uint64_t)i, (uint64_t)pool->npool, h);
+            out_ichr[p * nq + i] = pool->ichr[k];
+            out_qs[p * nq + i] = pool->qs[k];
+            out_qe[p * nq + i] = pool->qe[k];
+        }
+    }
+}
+
+/* the pool's own refusals, the engine's: the arrays, the batch limit, fewer regions than are drawn */
+static int pool_bad(const perm_pool *pool, int64_t nq)
+{
+    return pool->npool < 0 || (pool->npool > 0 && (!pool->ichr || !pool->qs || !pool->qe)) || pool->npool > igd_hip_max_batch() ||
+           pool->npool < nq;
+}
+
+int igdc_resample_regions_host(const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, int64_t nq,
+                               uint64_t seed, int64_t p0, int64_t np, int32_t *out_ichr, int32_t *out_qs, int32_t *out_qe)
+{
+    const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
+    if (nq < 0 || np < 0 || p0 < 0 || nq > igd_hip_max_batch() || pool_bad(&pool, nq) || (nq > 0 && np > 0 && (!out_ichr || !out_qs || !out_qe)) ||
+        (nq > 0 && np > (int64_t)INT32_MAX / nq))
+        return -1;
+    resample_regions_fill(&pool, nq, seed, p0, np, out_ichr, out_qs, out_qe);
+    return 0;
+}
+
 /* ---- the workspace table (include/igd_hip.h: THE WORKSPACE) ---------------------------------------------------------------
  * igdc_workspace_build: the segments through igdc_merge_host at gap 0 (one set; it needs a database only for the number of
  * contigs), the runs clipped to [0, ctg_len[c]], per contig ordered by length descending then start ascending, and summed.  The
@@ -1299,8 +1335,12 @@ int64_t igdc_permute_first_bad(const int32_t *ichr, const int32_t *qs, const int
  * number of permutations, the generator's bounds on the regions, and under a workspace a table that is valid for the database's
  * contigs and has a segment for every region on a known contig */
 static int perm_args_bad(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                         const int32_t *ctg_len, int mode, int64_t nperm, const igd_hip_workspace *ws)
+                         const int32_t *ctg_len, int mode, int64_t nperm, const igd_hip_workspace *ws, const perm_pool *pool)
 {
+    /* resampling: nothing is placed, so there are no contig lengths and no region is validated; the pool has its own bounds */
+    if (pool || mode == IGD_HIP_PERM_RESAMPLE)
+        return !pool || ws || mode != IGD_HIP_PERM_RESAMPLE || !db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || nperm < 1 ||
+               nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || pool_bad(pool, nq);
     return !db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) || !perm_mode_ok(mode, ws) ||
            nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 ||
            (ws && (!igd_hip_workspace_valid(ws, ctg_len, db->nCtg) || igdc_workspace_first_unplaceable(ws, ctg_len, ichr, qs, qe, nq) >= 0));
@@ -1316,7 +1356,9 @@ typedef struct {
     int mode; uint64_t seed;
     const igd_hip_workspace *ws;        /* the checked table of mode IGD_HIP_PERM_WORKSPACE, or NULL */
     const int32_t *offsets;             /* the shift placement (igdc_shift_support_host_ov): row r > 0 is the set moved by offsets[r - 1]; or NULL */
-    int32_t *ps, *pe;                   /* the permuted set */
+    const perm_pool *pool;              /* resampling (the _rs entries): row r > 0 is draw r - 1 from the pool, contigs into pc; or NULL */
+    int32_t *ps, *pe, *pc;              /* the permuted set; the drawn contigs (pool only) */
+    const int32_t *rowc;                /* the contigs of the row in hand: ichr, or pc for a draw */
     int k, T, failed;
 } perm_stripe;
 typedef int (*perm_row_fn)(void *job, int64_t r, const int32_t *s, const int32_t *e);
@@ -1327,6 +1369,7 @@ static void stripe_init(perm_stripe *S, const igdc_db *db, const igdc_map *m, co
 {
     S->db = db; S->m = m; S->ichr = ichr; S->qs = qs; S->qe = qe; S->ctg_len = ctg_len;
     S->nq = nq; S->first = first; S->nrows = nrows; S->mode = mode; S->seed = seed; S->ws = ws; S->offsets = NULL;
+    S->pool = NULL; S->pc = NULL; S->rowc = ichr;
     S->ps = ps; S->pe = ps + nq;
     S->k = k; S->T = T; S->failed = 0;
 }
@@ -1335,8 +1378,13 @@ static void perm_rows(perm_stripe *S, perm_row_fn row, void *job)
 {
     for (int64_t r = S->first + S->k; r < S->nrows && !S->failed; r += S->T) {
         const int32_t *s = S->qs, *e = S->qe;
+        S->rowc = S->ichr;
         if (r > 0) {
-            if (S->offsets) shift_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->offsets + (r - 1), 1, S->ps, S->pe);
+            if (S->pool) {
+                resample_regions_fill(S->pool, S->nq, S->seed, r - 1, 1, S->pc, S->ps, S->pe);
+                S->rowc = S->pc;
+            }
+            else if (S->offsets) shift_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->offsets + (r - 1), 1, S->ps, S->pe);
             else perm_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->mode, S->seed, r - 1, 1, S->ps, S->pe, S->ws);
             s = S->ps; e = S->pe;
         }
@@ -1363,7 +1411,7 @@ static int perm_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
     memset(P->row, 0, sizeof(int64_t) * (size_t)nC);
     memset(P->last, 0, sizeof(int64_t) * (size_t)nC);
     host_job J;
-    job_init(&J, JOB_SUPPORT, P->s.db, P->s.m, P->s.ichr, s, e, 0, P->s.nq, P->v, P->rule);
+    job_init(&J, JOB_SUPPORT, P->s.db, P->s.m, P->s.rowc, s, e, 0, P->s.nq, P->v, P->rule);
     J.hits = P->row; J.last = P->last; J.mo = P->mo;
     host_run(&J);
     if (J.io_failed) return 1;
@@ -1402,14 +1450,23 @@ int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ic
                                 min_overlap, NULL);
 }
 
-int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                         const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
-                         int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
-                         const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
+/* the contigs the threads of a resampling call draw into: nq words per thread (NULL without a pool; *bad when it cannot be had) */
+static int32_t *pool_contigs(const perm_pool *pool, int T, int64_t nq, int *bad)
+{
+    int32_t *pc = pool ? (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (size_t)nq + 1)) : NULL;
+    if (pool && !pc) *bad = -1;
+    return pc;
+}
+
+/* the body of igdc_permute_host_ws and, with a pool and no ctg_len, of igdc_permute_host_rs */
+static int permute_host_run(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                            const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                            int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
+                            const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws, const perm_pool *pool)
 {
     const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
     if (!igd_hip_min_overlap_valid(min_overlap) || !observed || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) ||
-        perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws) ||
+        perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, pool) ||
         (unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63)
         return -1;
     const int64_t nF = db->nFiles, nC = nF + 1;
@@ -1419,11 +1476,13 @@ int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ic
     int64_t *w = (int64_t *)calloc((size_t)T * 8 * (size_t)nC + (size_t)nC, sizeof(int64_t));
     int32_t *pq = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 2 * (size_t)nq + 1));
     int rc = w && pq ? 0 : -1;
+    int32_t *pcb = pool_contigs(pool, T, nq, &rc);
     int64_t *obs = w ? w + (size_t)T * 8 * (size_t)nC : NULL;
     if (rc == 0 && nq > 0) rc = igdc_support_host_ov(db, m, ichr, qs, qe, nq, v, rule, obs, &obs[nF], mo);
     perm_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
         stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 1, nperm + 1, pq + (size_t)k * 2 * (size_t)nq, k, T);
+        job[k].s.pool = pool; job[k].s.pc = pcb ? pcb + (size_t)k * (size_t)nq : NULL;
         job[k].v = v; job[k].rule = rule; job[k].observed = obs; job[k].mo = mo;
         job[k].acc = w + (size_t)k * 8 * (size_t)nC;
         job[k].row = job[k].acc + 6 * nC; job[k].last = job[k].row + nC;
@@ -1446,8 +1505,27 @@ int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ic
         memcpy(observed, obs, sizeof(int64_t) * (size_t)nC);
         for (int s = 0; s < 6; s++) if (out[s]) memcpy(out[s], a0 + s * nC, sizeof(int64_t) * (size_t)nC);
     }
-    free(w); free(pq);
+    free(w); free(pq); free(pcb);
     return rc;
+}
+
+int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
+                         int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
+                         const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
+{
+    return permute_host_run(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax,
+                            min_overlap, ws, NULL);
+}
+
+int igdc_permute_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                         const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                         int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le,
+                         int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap)
+{
+    const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
+    return permute_host_run(db, m, ichr, qs, qe, nq, NULL, IGD_HIP_PERM_RESAMPLE, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin,
+                            pmax, min_overlap, NULL, &pool);
 }
 
 /* igdc_shift_support_host_ov's thread: rows 1 .. nshift of the stripe (row r is the set moved by offsets[r - 1]), each walked
@@ -1467,7 +1545,7 @@ static int shift_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
     memset(row, 0, sizeof(int64_t) * (size_t)nC);
     memset(P->last, 0, sizeof(int64_t) * (size_t)nC);
     host_job J;
-    job_init(&J, JOB_SUPPORT, P->s.db, P->s.m, P->s.ichr, s, e, 0, P->s.nq, P->v, P->rule);
+    job_init(&J, JOB_SUPPORT, P->s.db, P->s.m, P->s.rowc, s, e, 0, P->s.nq, P->v, P->rule);
     J.hits = row; J.last = P->last; J.mo = P->mo;
     host_run(&J);
     if (J.io_failed) return 1;
@@ -1829,7 +1907,7 @@ static int pnear_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
     const int64_t nF = P->s.db->nFiles, nC = nF + 1;
     int64_t *nw = P->res + r * nC, *no = nw + P->s.nrows * nC, *sd = no + P->s.nrows * nC;
     for (int64_t i = 0; i < P->s.nq && !P->tb.failed; i++) {
-        const int32_t dm = one_region_nearest(P->s.db, P->s.m, &P->tb, P->s.ichr[i], s[i], e[i], P->window, P->v, P->use_v, P->row);
+        const int32_t dm = one_region_nearest(P->s.db, P->s.m, &P->tb, P->s.rowc[i], s[i], e[i], P->window, P->v, P->use_v, P->row);
         if (dm < 0) continue;                                          /* (no record within the window: the row is all -1) */
         for (int64_t f = 0; f < nC; f++) {
             const int32_t d = f < nF ? P->row[f] : dm;
@@ -1857,21 +1935,25 @@ int igdc_permute_nearest_host(const igdc_db *db, const igdc_map *m, const int32_
     return igdc_permute_nearest_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap, sum_dist, NULL);
 }
 
-int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                                 const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
-                                 int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws)
+/* the body of igdc_permute_nearest_host_ws and, with a pool and no ctg_len, of igdc_permute_nearest_host_rs */
+static int permute_nearest_host_run(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                    const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                                    int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws,
+                                    const perm_pool *pool)
 {
-    if (!igd_hip_nearest_window_valid(window) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws)) return -1;
+    if (!igd_hip_nearest_window_valid(window) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, pool)) return -1;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     int T = host_threads(nq * R > 0 ? nq * R : 1);
     if (T > R) T = (int)R;
     int64_t *res = (int64_t *)calloc((size_t)(3 * R * nC), sizeof(int64_t));
     int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (2 * (size_t)nq + (size_t)nF) + 1));
     int rc = res && w ? 0 : -1;
+    int32_t *pcb = pool_contigs(pool, T, nq, &rc);
     pnear_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
         int32_t *mine = w + (size_t)k * (2 * (size_t)nq + (size_t)nF);
         stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 0, R, mine, k, T);
+        job[k].s.pool = pool; job[k].s.pc = pcb ? pcb + (size_t)k * (size_t)nq : NULL;
         job[k].window = window; job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
         job[k].res = res; job[k].row = mine + 2 * nq;
     }
@@ -1883,8 +1965,24 @@ int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int
         int64_t *const out[3] = {n_within, n_overlap, sum_dist};
         for (int s = 0; s < 3; s++) if (out[s]) memcpy(out[s], res + (size_t)s * (size_t)(R * nC), sizeof(int64_t) * (size_t)(R * nC));
     }
-    free(res); free(w);
+    free(res); free(w); free(pcb);
     return rc;
+}
+
+int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                 const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
+                                 int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws)
+{
+    return permute_nearest_host_run(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap, sum_dist, ws, NULL);
+}
+
+int igdc_permute_nearest_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                 const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                                 int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
+{
+    const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
+    return permute_nearest_host_run(db, m, ichr, qs, qe, nq, NULL, IGD_HIP_PERM_RESAMPLE, seed, nperm, window, v, n_within, n_overlap, sum_dist,
+                                    NULL, &pool);
 }
 
 /* the summary of a null distribution of distance statistics; igd_core.h has the formulas */
@@ -2153,7 +2251,7 @@ static int pbp_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
     const igdc_db *db = P->s.db;
     const int64_t nF = db->nFiles, nq = P->s.nq, off[2] = {0, nq};
     int64_t moff[2], bp = 0;
-    if (igdc_merge_host(db, P->s.ichr, s, e, off, 1, 0, P->mr, P->mr + nq, P->mr + 2 * nq, moff, NULL, &P->dropped[r]) != 0) return 1;
+    if (igdc_merge_host(db, P->s.rowc, s, e, off, 1, 0, P->mr, P->mr + nq, P->mr + 2 * nq, moff, NULL, &P->dropped[r]) != 0) return 1;
     for (int64_t i = 0; i < moff[1]; i++) bp += (int64_t)P->mr[2 * nq + i] - (int64_t)P->mr[nq + i];
     P->set_bp[r] = bp;
     P->n_merged[r] = moff[1];
@@ -2174,21 +2272,24 @@ int igdc_permute_bp_host(const igdc_db *db, const igdc_map *m, const int32_t *ic
     return igdc_permute_bp_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, NULL);
 }
 
-int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                            const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
-                            int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
+/* the body of igdc_permute_bp_host_ws and, with a pool and no ctg_len, of igdc_permute_bp_host_rs */
+static int permute_bp_host_run(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
+                               int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws, const perm_pool *pool)
 {
-    if ((rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws)) return -1;
+    if ((rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, pool)) return -1;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
     int T = host_threads(nq * R > 0 ? nq * R : 1);
     if (T > R) T = (int)R;
     int64_t *res = (int64_t *)calloc((size_t)(R * nC + 3 * R), sizeof(int64_t));
     int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 5 * (size_t)nq + 1));
     int rc = res && w ? 0 : -1;
+    int32_t *pcb = pool_contigs(pool, T, nq, &rc);
     pbp_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
         int32_t *mine = w + (size_t)k * 5 * (size_t)nq;
         stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 0, R, mine, k, T);
+        job[k].s.pool = pool; job[k].s.pc = pcb ? pcb + (size_t)k * (size_t)nq : NULL;
         job[k].v = v; job[k].rule = rule; job[k].mr = mine + 2 * nq;
         job[k].inter = res; job[k].set_bp = res + R * nC; job[k].n_merged = job[k].set_bp + R; job[k].dropped = job[k].n_merged + R;
     }
@@ -2202,8 +2303,24 @@ int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t 
         if (n_merged) memcpy(n_merged, res + R * nC + R, sizeof(int64_t) * (size_t)R);
         if (n_dropped) *n_dropped = res[R * nC + 2 * R];
     }
-    free(res); free(w);
+    free(res); free(w); free(pcb);
     return rc;
+}
+
+int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                            const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
+                            int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
+{
+    return permute_bp_host_run(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, ws, NULL);
+}
+
+int igdc_permute_bp_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                            const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                            int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped)
+{
+    const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
+    return permute_bp_host_run(db, m, ichr, qs, qe, nq, NULL, IGD_HIP_PERM_RESAMPLE, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped,
+                               NULL, &pool);
 }
 
 /* the summary of a null distribution of base-pair overlaps; igd_core.h has the formulas */

@@ -569,6 +569,61 @@ def _perm_mode(mode, what, workspace=None):
     return PERM_MODES[mode]
 
 
+PERM_RESAMPLE = 4                                    # IGD_HIP_PERM_RESAMPLE: mode="resample" together with universe=
+
+
+def _perm_pool(mode, universe, ctg_len, workspace, what):
+    """None, or the pool of a resampling call as three C-ordered int32 arrays.  mode="resample" and universe= come together or not
+    at all, and with them neither contig lengths nor a workspace: nothing is placed (ValueError)."""
+    if (mode == "resample") != (universe is not None):
+        raise ValueError("%s: mode='resample' and universe= go together, not one without the other" % what)
+    if universe is None:
+        return None
+    if workspace is not None:
+        raise ValueError("%s: mode='resample' draws from the universe, it places nothing: there is no workspace= with it" % what)
+    if ctg_len is not None:
+        raise ValueError("%s: mode='resample' draws from the universe, it places nothing: ctg_len (genome_path) must be None" % what)
+    if len(universe) != 3:
+        raise ValueError("%s: universe must be (ichr, qs, qe)" % what)
+    return _regions(*universe, what, "universe regions")
+
+
+def _pool_args(pool):
+    return _ptr(pool[0]), _ptr(pool[1]), _ptr(pool[2]), len(pool[1])
+
+
+_Placement = collections.namedtuple("_Placement", "ichr qs qe ctg_len sfx mid tail refused keep")
+
+
+def _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, what):
+    """What the six entries of the three nulls share: the call's regions as C-ordered int32 and how its permuted sets are made.
+    sfx names the C entry -- "_ws": placed by mode, inside a workspace or not; "_rs": drawn from a universe (then ctg_len is None) --
+    mid is what that entry takes between nq and the seed, tail what it takes last, refused the host routes' words for what the
+    native call may have refused; keep holds the arrays behind mid's pointers."""
+    pool = _perm_pool(mode, universe, ctg_len, workspace, what)
+    if pool is not None:
+        ichr, qs, qe = _regions(ichr, qs, qe, what)
+        return _Placement(ichr, qs, qe, None, "_rs", _pool_args(pool), (), "%d regions from a universe of %d" % (len(qs), len(pool[1])), pool)
+    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, what)
+    pm = _perm_mode(mode, what, workspace)
+    return _Placement(ichr, qs, qe, ctg_len, "_ws", (_ptr(ctg_len), pm), (_ws_ptr(workspace),), "a region outside its contig or its workspace", workspace)
+
+
+def _placement_fits(P, nctg, what):
+    if P.ctg_len is not None:
+        _ctg_len_matches(P.ctg_len, nctg, what)
+
+
+def resample_regions_host(ichr, qs, qe, nq, p0, np_, seed=0):
+    """Draws [p0, p0 + np_) of nq regions without replacement from the pool (ichr, qs, qe) on the host
+    (igdc_resample_regions_host; no device is touched): (ichr, qs, qe) int32[np_, nq] as Database.resample_regions() defines them."""
+    pool = _regions(ichr, qs, qe, "resample_regions_host", "universe regions")
+    out = [np.empty((int(np_), int(nq)), np.int32) for _ in range(3)] if int(np_) >= 0 and int(nq) >= 0 else [np.empty(0, np.int32)] * 3
+    if N.cli().igdc_resample_regions_host(*_pool_args(pool), int(nq), _seed(seed), int(p0), int(np_), *[_ptr(a) for a in out]) != 0:
+        raise IgdError("resample_regions_host: bad argument (%d regions from a universe of %d)" % (int(nq), len(pool[1])))
+    return tuple(out)
+
+
 def _ws_ptr(workspace):
     return None if workspace is None else workspace.ptr
 
@@ -591,22 +646,19 @@ def permute_regions_host(ichr, qs, qe, ctg_len, p0, np_, seed=0, mode="circular"
 
 
 def permute_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, min_overlap=None,
-                 workspace=None):
+                 workspace=None, universe=None):
     """The permutation null of the support counts on the host (igdc_permute_host: pread on the .igd, threads over the
     permutations; no device is touched): a PermutationSupport as Database.permutation_support() defines it, min_overlap
-    included (igdc_permute_host_ov)."""
-    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_host")
-    pm = _perm_mode(mode, "permute_host", workspace)
+    included (igdc_permute_host_ov), and mode="resample" with universe= and ctg_len None (igdc_permute_host_rs)."""
+    P = _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, "permute_host")
     mo = _min_overlap(min_overlap, "permute_host")
     with _HostDb(igd_path, None) as h:
-        _ctg_len_matches(ctg_len, h.nctg, "permute_host")
+        _placement_fits(P, h.nctg, "permute_host")
         rule, vf = h.dispatch(v, rule, value_filter)
         out = [np.empty(h.nfiles + 1, np.int64) for _ in range(7)]
-        a = (h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed), int(nperm), vf, rule,
-             *[_ptr(x) for x in out])
-        if h.L.igdc_permute_host_ws(*a, None if mo is None else C.byref(mo), _ws_ptr(workspace)) != 0:
-            raise IgdError("permute_host: a refused argument (number of permutations, a region outside its contig or its workspace), or a tile of %s "
-                           "could not be read" % igd_path)
+        a = (h.core, h.m, _ptr(P.ichr), _ptr(P.qs), _ptr(P.qe), len(P.qs), *P.mid, _seed(seed), int(nperm), vf, rule, *[_ptr(x) for x in out])
+        if getattr(h.L, "igdc_permute_host" + P.sfx)(*a, None if mo is None else C.byref(mo), *P.tail) != 0:
+            raise IgdError("permute_host: a refused argument (number of permutations, %s), or a tile of %s could not be read" % (P.refused, igd_path))
     return PermutationSupport(*out, int(nperm))
 
 
@@ -696,19 +748,19 @@ def local_zscore(ps, ss):
     return (sh.astype(np.float64) - sm.mean[None, :]) / sd[None, :]
 
 
-def permute_nearest_host(igd_path, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, workspace=None):
+def permute_nearest_host(igd_path, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, workspace=None,
+                         universe=None):
     """Database.permutation_nearest() on the host (igdc_permute_nearest_host: pread on the .igd, threads over the permutations;
-    no device is touched): a PermutationNearest."""
-    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_nearest_host")
-    pm = _perm_mode(mode, "permute_nearest_host", workspace)
+    no device is touched): a PermutationNearest.  mode="resample" with universe= and ctg_len None: igdc_permute_nearest_host_rs."""
+    P = _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, "permute_nearest_host")
     with _HostDb(igd_path, "permute_nearest_host") as h:
-        _ctg_len_matches(ctg_len, h.nctg, "permute_nearest_host")
+        _placement_fits(P, h.nctg, "permute_nearest_host")
         out = [np.empty((max(int(nperm), 0) + 1, h.nfiles + 1), np.int64) for _ in range(3)]
-        if h.L.igdc_permute_nearest_host_ws(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed),
-                                            int(nperm), _window(window, "permute_nearest_host"), _value_filter(value_filter),
-                                            *[_ptr(a) for a in out], _ws_ptr(workspace)) != 0:
-            raise IgdError("permute_nearest_host: a refused argument (number of permutations, window, a region outside its contig or its workspace), or a "
-                           "tile of %s could not be read" % igd_path)
+        if getattr(h.L, "igdc_permute_nearest_host" + P.sfx)(h.core, h.m, _ptr(P.ichr), _ptr(P.qs), _ptr(P.qe), len(P.qs), *P.mid, _seed(seed),
+                                                             int(nperm), _window(window, "permute_nearest_host"), _value_filter(value_filter),
+                                                             *[_ptr(a) for a in out], *P.tail) != 0:
+            raise IgdError("permute_nearest_host: a refused argument (number of permutations, window, %s), or a tile of %s could not be read"
+                           % (P.refused, igd_path))
         return PermutationNearest(*out, int(window), int(nperm))
 
 
@@ -856,21 +908,20 @@ def _merge_cut(mc, ms, me, moff, cnt, dropped):
     return mc[:r], ms[:r], me[:r], moff, cnt[:r], dropped
 
 
-def permute_bp_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, workspace=None):
+def permute_bp_host(igd_path, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, workspace=None,
+                    universe=None):
     """Database.permutation_bp() on the host (igdc_permute_bp_host: pread on the .igd, threads over the permutations; no device
-    is touched): a PermutationBp."""
-    ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permute_bp_host")
-    pm = _perm_mode(mode, "permute_bp_host", workspace)
+    is touched): a PermutationBp.  mode="resample" with universe= and ctg_len None: igdc_permute_bp_host_rs."""
+    P = _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, "permute_bp_host")
     with _HostDb(igd_path, "permute_bp_host") as h:
-        _ctg_len_matches(ctg_len, h.nctg, "permute_bp_host")
+        _placement_fits(P, h.nctg, "permute_bp_host")
         rule, vf = h.dispatch(v, rule, value_filter)
         rows = max(int(nperm), 0) + 1
         inter, set_bp, n_merged = np.empty((rows, h.nfiles + 1), np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
         dropped, file_bp = np.zeros(1, np.int64), np.empty(h.nfiles + 1, np.int64)
-        if h.L.igdc_permute_bp_host_ws(h.core, h.m, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed),
-                                       int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged), _ptr(dropped), _ws_ptr(workspace)) != 0:
-            raise IgdError("permute_bp_host: a refused argument (number of permutations, a region outside its contig or its workspace), or a tile of %s "
-                           "could not be read" % igd_path)
+        if getattr(h.L, "igdc_permute_bp_host" + P.sfx)(h.core, h.m, _ptr(P.ichr), _ptr(P.qs), _ptr(P.qe), len(P.qs), *P.mid, _seed(seed), int(nperm),
+                                                        vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged), _ptr(dropped), *P.tail) != 0:
+            raise IgdError("permute_bp_host: a refused argument (number of permutations, %s), or a tile of %s could not be read" % (P.refused, igd_path))
         if h.L.igdc_dataset_bp_host(h.core, h.m, vf, rule, _ptr(file_bp)) != 0:
             raise IgdError("permute_bp_host: a tile of %s could not be read" % igd_path)
         return PermutationBp(inter, set_bp, n_merged, int(dropped[0]), file_bp, int(nperm))
@@ -1427,7 +1478,7 @@ class Database:
         return out
 
     def permutation_support(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None,
-                            min_overlap=None, workspace=None):
+                            min_overlap=None, workspace=None, universe=None):
         """Permutation null of the support counts of one region set (igd_hip_permute_support).  The set is moved nperm times
         -- mode "circular": one rigid shift per permutation and contig, a region that would cross the contig's end is pushed
         back against it; "shuffle": every region placed anew on its contig -- with the generator of include/igd_hip.h; every
@@ -1441,15 +1492,20 @@ class Database:
         mode "workspace" together with workspace= (a Workspace): every region is placed anew inside the segments of the
         workspace on its contig, every fitting start equally likely (igd_hip_permute_support_ws); a region that fits in no
         segment raises IgdError.  The same pair of arguments serves permutation_nearest(), permutation_bp() and
-        permute_regions()."""
-        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_support")
-        pm = _perm_mode(mode, "permutation_support", workspace)
-        _ctg_len_matches(ctg_len, self.nctg, "permutation_support")
+        permute_regions().
+        mode "resample" together with universe=(ichr, qs, qe) and ctg_len None (igd_hip_permute_support_rs; regioneR's
+        resampleRegions): every permuted set is len(qs) regions drawn without replacement from the universe, contigs, starts
+        and ends as they stand; nothing is placed, so there are no contig lengths and no workspace, and the set need not be
+        a subset of the universe.  Each permuted support is then hypergeometric.  A set larger than the universe raises
+        IgdError.  The same pair serves permutation_nearest() and permutation_bp()."""
+        P = _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, "permutation_support")
+        _placement_fits(P, self.nctg, "permutation_support")
         rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         out = [np.empty(self.nfiles + 1, np.int64) for _ in range(7)]
         mo = _min_overlap(min_overlap, "permutation_support")
-        a = (self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed), int(nperm), vf, rule, *[_ptr(x) for x in out])
-        _chk(self._H.igd_hip_permute_support_ws(*a, None if mo is None else C.byref(mo), _ws_ptr(workspace)), "igd_hip_permute_support")
+        a = (self.dev, _ptr(P.ichr), _ptr(P.qs), _ptr(P.qe), len(P.qs), *P.mid, _seed(seed), int(nperm), vf, rule, *[_ptr(x) for x in out])
+        _chk(getattr(self._H, "igd_hip_permute_support" + P.sfx)(*a, None if mo is None else C.byref(mo), *P.tail),
+             "igd_hip_permute_support" + P.sfx.replace("_ws", ""))
         return PermutationSupport(*out, int(nperm))
 
     def read_genome(self, path):
@@ -1477,11 +1533,35 @@ class Database:
             raise IgdError("read_workspace: the table of %s could not be built" % path)
         return Workspace(t, ctg_len)
 
-    def permutation_support_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0, min_overlap=None, workspace=None):
+    def _genome_or_universe(self, genome_path, universe_path):
+        """(ctg_len, universe) of a _files call: the lengths of a genome file, or -- mode "resample", genome_path None -- the regions
+        of a universe file, read as enrichment_files() reads one"""
+        return (None if genome_path is None else self.read_genome(genome_path),
+                None if universe_path is None else self.read_queries(universe_path))
+
+    def permutation_support_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0, min_overlap=None, workspace=None,
+                                  universe_path=None):
         """The permutation null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the
-        integers behind what `igd search -q path -P nperm -g genome_path` prints (with -W: mode="workspace" and workspace=)."""
-        return self.permutation_support(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v, min_overlap=min_overlap,
-                                        workspace=workspace)
+        integers behind what `igd search -q path -P nperm -g genome_path` prints (with -W: mode="workspace" and workspace=; with
+        -M resample -U universe_path: mode="resample", universe_path= and genome_path None)."""
+        ctg_len, uni = self._genome_or_universe(genome_path, universe_path)
+        return self.permutation_support(*self.read_queries(path), ctg_len, nperm, seed, mode, v, min_overlap=min_overlap,
+                                        workspace=workspace, universe=uni)
+
+    def _resample_regions(self, ichr, qs, qe, nq, p0, np_, seed=0):
+        """resample_regions(ichr, qs, qe, nq, p0, np_, seed=0).  Kernel igd_resample_regions on host arrays
+        (igd_hip_resample_regions): (ichr, qs, qe) int32[np_, nq], row k the nq regions of draw p0 + k from the pool (ichr, qs,
+        qe) -- pool region igd_hip_resample_index(base(seed, p0 + k), i, npool) for i = 0 .. nq - 1, distinct within a row.  nq
+        above the pool's size raises IgdError."""
+        pool = _regions(ichr, qs, qe, "resample_regions", "universe regions")
+        if int(np_) < 0 or int(nq) < 0:
+            raise IgdError("resample_regions: a negative size")
+        out = [np.empty((int(np_), int(nq)), np.int32) for _ in range(3)]
+        _chk(self._H.igd_hip_resample_regions(self.dev, *_pool_args(pool), int(nq), _seed(seed), int(p0), int(np_), *[_ptr(a) for a in out]),
+             "igd_hip_resample_regions")
+        return tuple(out)
+
+    resample_regions = _forward(_resample_regions)
 
     def _shift_support(self, ichr, qs, qe, ctg_len, offsets, v=0, rule=None, value_filter=None, min_overlap=None):
         """shift_support(ichr, qs, qe, ctg_len, offsets, v=0, rule=None, value_filter=None, min_overlap=None).  The support counts
@@ -1598,7 +1678,8 @@ class Database:
         """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets_fused()."""
         return self.nearest_sets_fused(*self._read_sets(paths), window, value_filter)
 
-    def permutation_nearest(self, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, out=None, workspace=None):
+    def permutation_nearest(self, ichr, qs, qe, ctg_len, nperm, window, seed=0, mode="circular", value_filter=None, out=None, workspace=None,
+                            universe=None):
         """Permutation null of the nearest-record distances of one region set (igd_hip_permute_nearest): "are my regions closer
         to dataset f than chance".  The set is moved nperm times as permutation_support() moves it (same generator, mode, seed
         and ctg_len) and every permuted set is measured as nearest_sets() measures a set.  Returns PermutationNearest(n_within,
@@ -1606,22 +1687,25 @@ class Database:
         p, the last column the any-dataset column.  The null distribution itself comes back -- the mean distance
         sum_dist / n_within is a ratio of two columns that both vary -- and perm_nearest_summary() places the observed row
         in it.  Neither the permuted regions nor any distance row leave the device.  out, when given, is a list of three
-        C-ordered int64[nperm + 1, nfiles + 1] that are overwritten (untouched when the call raises)."""
-        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_nearest")
-        pm = _perm_mode(mode, "permutation_nearest", workspace)
-        _ctg_len_matches(ctg_len, self.nctg, "permutation_nearest")
+        C-ordered int64[nperm + 1, nfiles + 1] that are overwritten (untouched when the call raises).  mode "resample" with
+        universe= and ctg_len None as permutation_support() takes them (igd_hip_permute_nearest_rs): "are my regions closer
+        to dataset f than other regions of the universe"."""
+        P = _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, "permutation_nearest")
+        _placement_fits(P, self.nctg, "permutation_nearest")
         out = _outs(out, 3, (max(int(nperm), 0) + 1, self.nfiles + 1), "permutation_nearest")
-        _chk(self._H.igd_hip_permute_nearest_ws(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm, _seed(seed), int(nperm),
-                                                _window(window, "permutation_nearest"), _value_filter(value_filter), *[_ptr(a) for a in out],
-                                                _ws_ptr(workspace)),
-             "igd_hip_permute_nearest")
+        _chk(getattr(self._H, "igd_hip_permute_nearest" + P.sfx)(self.dev, _ptr(P.ichr), _ptr(P.qs), _ptr(P.qe), len(P.qs), *P.mid, _seed(seed),
+                                                                 int(nperm), _window(window, "permutation_nearest"), _value_filter(value_filter),
+                                                                 *[_ptr(a) for a in out], *P.tail),
+             "igd_hip_permute_nearest" + P.sfx.replace("_ws", ""))
         return PermutationNearest(*out, int(window), int(nperm))
 
-    def permutation_nearest_files(self, path, genome_path, nperm, window, seed=0, mode="circular", value_filter=None, workspace=None):
+    def permutation_nearest_files(self, path, genome_path, nperm, window, seed=0, mode="circular", value_filter=None, workspace=None,
+                                  universe_path=None):
         """The null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the integers behind
-        what `igd search -q path -P nperm -g genome_path -D window` prints."""
-        return self.permutation_nearest(*self.read_queries(path), self.read_genome(genome_path), nperm, window, seed, mode, value_filter,
-                                        workspace=workspace)
+        what `igd search -q path -P nperm -g genome_path -D window` prints (mode="resample": universe_path=, genome_path None)."""
+        ctg_len, uni = self._genome_or_universe(genome_path, universe_path)
+        return self.permutation_nearest(*self.read_queries(path), ctg_len, nperm, window, seed, mode, value_filter,
+                                        workspace=workspace, universe=uni)
 
     def nearest_files(self, paths, window, value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the NearestSets of nearest_sets()."""
@@ -1776,31 +1860,34 @@ class Database:
                                           _ptr(js.set_bp), _ptr(js.file_bp), _ptr(js.n_merged), _ptr(js.n_dropped)), "igd_hip_jaccard_sets")
         return js
 
-    def permutation_bp(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, workspace=None):
+    def permutation_bp(self, ichr, qs, qe, ctg_len, nperm, seed=0, mode="circular", v=0, rule=None, value_filter=None, workspace=None,
+                       universe=None):
         """Permutation null of the base-pair overlap of one region set (igd_hip_permute_bp): "does my set share more base pairs
         with dataset f than chance".  The set is moved nperm times as permutation_support() moves it (same generator, mode,
         seed and ctg_len), and the set as given and every permuted set are treated as jaccard_sets() treats a set: merged at gap
         0, then covered.  Returns PermutationBp(inter int64[nperm + 1, nfiles + 1], set_bp, n_merged int64[nperm + 1], n_dropped,
         file_bp int64[nfiles + 1], nperm): row 0 the set as given, row p + 1 permutation p, the last column "any dataset";
         file_bp is dataset_bp().  Neither the permuted regions nor the merged runs leave the device.  perm_bp_summary() places
-        the observed row in the null distribution."""
-        ichr, qs, qe, ctg_len = _perm_regions(ichr, qs, qe, ctg_len, "permutation_bp")
-        pm = _perm_mode(mode, "permutation_bp", workspace)
-        _ctg_len_matches(ctg_len, self.nctg, "permutation_bp")
+        the observed row in the null distribution.  mode "resample" with universe= and ctg_len None as permutation_support()
+        takes them (igd_hip_permute_bp_rs); n_dropped is then that of the set as given, a draw drops what its own regions make
+        it drop."""
+        P = _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, "permutation_bp")
+        _placement_fits(P, self.nctg, "permutation_bp")
         rule, vf = _dispatch(self.gtype, v, rule, value_filter)
         rows = max(int(nperm), 0) + 1
         inter, set_bp, n_merged = np.empty((rows, self.nfiles + 1), np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
         dropped, file_bp = np.zeros(1, np.int64), np.empty(self.nfiles + 1, np.int64)
-        _chk(self._H.igd_hip_permute_bp_ws(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), len(qs), _ptr(ctg_len), pm,
-                                           _seed(seed), int(nperm), vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged),
-                                           _ptr(dropped), _ws_ptr(workspace)), "igd_hip_permute_bp")
+        _chk(getattr(self._H, "igd_hip_permute_bp" + P.sfx)(self.dev, _ptr(P.ichr), _ptr(P.qs), _ptr(P.qe), len(P.qs), *P.mid, _seed(seed), int(nperm),
+                                                            vf, rule, _ptr(inter), _ptr(set_bp), _ptr(n_merged), _ptr(dropped), *P.tail),
+             "igd_hip_permute_bp" + P.sfx.replace("_ws", ""))
         _chk(self._H.igd_hip_dataset_bp(self.dev, vf, rule, _ptr(file_bp)), "igd_hip_dataset_bp")
         return PermutationBp(inter, set_bp, n_merged, int(dropped[0]), file_bp, int(nperm))
 
-    def permutation_bp_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0, workspace=None):
+    def permutation_bp_files(self, path, genome_path, nperm, seed=0, mode="circular", v=0, workspace=None, universe_path=None):
         """The null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the integers behind
-        what `igd search -q path -P nperm -g genome_path -G` prints."""
-        return self.permutation_bp(*self.read_queries(path), self.read_genome(genome_path), nperm, seed, mode, v, workspace=workspace)
+        what `igd search -q path -P nperm -g genome_path -G` prints (mode="resample": universe_path=, genome_path None)."""
+        ctg_len, uni = self._genome_or_universe(genome_path, universe_path)
+        return self.permutation_bp(*self.read_queries(path), ctg_len, nperm, seed, mode, v, workspace=workspace, universe=uni)
 
     def jaccard_files(self, paths, v=0):
         """One region set per BED file (read as `igd search -q` reads it): the JaccardSets of jaccard_sets()."""

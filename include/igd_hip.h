@@ -873,6 +873,53 @@ static inline IGD_HIP_HD_ void igd_hip_perm_place(int mode, uint64_t base, int32
     *s = (int32_t)t;
     *e = (int32_t)(t + len);
 }
+/* THE DRAW (the one definition: kernel igd_resample_regions, igdc_resample_regions_host and the tests' numpy reference agree bit
+ * for bit).  A keyed bijection on [0, n), 1 <= n < 2^31: a four-round Feistel network on the smallest domain 2^(2h) >= n, walked
+ * until it is back below n (cycle walking).  Unsigned 64-bit arithmetic, G, mix64 and igd_hip_perm_base as above.
+ *     h      = the smallest integer >= 1 with 4^h >= n            (h <= 16; the domain 2^(2h) is below 4 n for n >= 2)
+ *     mask   = 2^h - 1
+ *     base   = igd_hip_perm_base(seed, p)
+ *     F(j,R) = mix64(base + (((j + 1) << 32) + R + 1) * G) & mask                 j = 0 .. 3
+ *     step(x): L = x >> h, R = x & mask;  four times, j = 0 .. 3: (L, R) <- (R, L ^ F(j, R));  return (L << h) | R
+ *     igd_hip_resample_index(base, i, n):  y = step(i);  while (y >= n) y = step(y);  return y      -- needs i < n
+ * IGD_HIP_PERM_RESAMPLE: draw i of permutation p is region igd_hip_resample_index(base(seed, p), i, npool) of a pool of npool
+ * regions, i = 0 .. nq - 1, copied as it stands -- contig, start and end; nq regions drawn WITHOUT replacement
+ * (regioneR::resampleRegions).  step is a bijection of the domain and i < n, so the walk returns to [0, n) and ends; it need not
+ * end for a start i >= n, so every entry refuses nq > npool before anything is launched.  A four-round network is not a uniform
+ * random permutation, least of all on tiny domains (n <= 4 has 2^(2h) = 4 points and at most 4^4 round-function tables); nothing
+ * is done about it. */
+#define IGD_HIP_PERM_RESAMPLE 4                      /* (3 is the engine's internal shift placement) */
+static inline IGD_HIP_HD_ int igd_hip_resample_bits(uint64_t n)
+{
+    int h = 1;
+    while (((uint64_t)1 << (2 * h)) < n) h++;
+    return h;
+}
+static inline IGD_HIP_HD_ uint64_t igd_hip_resample_step(uint64_t base, uint64_t x, int h)
+{
+    const uint64_t mask = ((uint64_t)1 << h) - 1;
+    uint64_t L = x >> h, R = x & mask;
+    for (uint64_t j = 0; j < 4; j++) {
+        const uint64_t f = igd_hip_perm_mix64(base + (((j + 1) << 32) + R + 1) * 0x9E3779B97F4A7C15ull) & mask;
+        const uint64_t t = L ^ f;
+        L = R;
+        R = t;
+    }
+    return (L << h) | R;
+}
+/* h = igd_hip_resample_bits(n), taken once by a caller with many draws from one pool */
+static inline IGD_HIP_HD_ uint64_t igd_hip_resample_walk(uint64_t base, uint64_t i, uint64_t n, int h)
+{
+    uint64_t y = igd_hip_resample_step(base, i, h);
+    while (y >= n) y = igd_hip_resample_step(base, y, h);
+    return y;
+}
+static inline IGD_HIP_HD_ uint64_t igd_hip_resample_index(uint64_t base, uint64_t i, uint64_t n)
+{
+    const int h = igd_hip_resample_bits(n);
+    const uint64_t y = igd_hip_resample_walk(base, i, n, h);
+    return y;
+}
 /* THE WORKSPACE (the one definition: kernel igd_permute_workspace, igdc_permute_regions_host_ws and the tests' numpy reference
  * agree bit for bit).  A workspace is a list of segments (c, a, b) on the contigs of the call: the stretches a region may be
  * placed in (GAT's workspace, regioneR's mask inverted, `bedtools shuffle -incl`).  It is merged at gap 0 by the rules of
@@ -1035,6 +1082,34 @@ int igd_hip_permute_nearest_ws(igd_hip_db *db, const int32_t *ichr, const int32_
 int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
                           int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
                           int64_t *n_dropped, const igd_hip_workspace *ws);
+/* The three nulls by RESAMPLING from a universe (THE DRAW above; kernel igd_resample_regions, the launch shape of
+ * igd_permute_regions with three gathered loads per output).  Row 0 is the call's own nq regions, the set as given, which need
+ * not come from the pool; row p + 1 is the nq pool regions of draw p, contigs included.  Nothing is placed, so there is no
+ * ctg_len and no region is validated: a region on an unknown contig overlaps nothing, as everywhere.  The pool (pool_ichr,
+ * pool_qs, pool_qe: int32[npool]) is uploaded once behind the call's regions; everything behind the generator is the entry's own
+ * chain, unchanged, with the chunk rule unchanged.  For the support each permuted value is hypergeometric: the null Fisher's test
+ * gives in closed form.  igd_hip_permute_bp_rs: n_dropped is that of the set as given; the draws' differ and are not reported.
+ * IGD_HIP_ERR_ARG before any launch, nothing of the caller's written, in this order: the entry's own first check (min_overlap, the
+ * window); a missing argument or no such rule; nperm outside 1 .. IGD_HIP_PERM_MAX; nq or npool above igd_hip_max_batch();
+ * npool < nq (igd_hip_last_error names both); the support's nperm * nq^2 >= 2^63.  nq == 0 or nFiles == 0: the all-zero results
+ * of the entries above, no device work.
+ * igd_hip_resample_regions: the generator alone, the twin of igd_hip_permute_regions -- draws [p0, p0 + np) of nq regions into
+ * out_ichr, out_qs, out_qe (int32[np * nq], draw-major); IGD_HIP_ERR_ARG for a missing array, a negative size, nq or npool above
+ * igd_hip_max_batch(), npool < nq or more than 2^31 - 1 outputs.
+ * Not done: strata of the pool (width- or GC-matched resampling), resampling for the shift profile, groups or set lists, several
+ * devices. */
+int igd_hip_resample_regions(igd_hip_db *db, const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool,
+                             int64_t nq, uint64_t seed, int64_t p0, int64_t np, int32_t *out_ichr, int32_t *out_qs, int32_t *out_qe);
+int igd_hip_permute_support_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                               int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge,
+                               int64_t *n_le, int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap);
+int igd_hip_permute_nearest_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                               const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                               int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist);
+int igd_hip_permute_bp_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                          const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                          int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped);
 
 /* Local z-score: the support of a region set under rigid shifts (regioneR's localZScore).  The whole set is moved by each of
  * nshift offsets and counted again; the host places every count in the null the permutation entries above produced.
