@@ -1548,6 +1548,40 @@ static void cooccur_file(char *path, int32_t v)
     free(cooc);
 }
 
+/* ------------------------------- the options of `igd search` ----------------------------- */
+/* What search_parse makes of argv, read by search_check and by the commands.  `given` has one bit per option (O_x; B(x)), and
+ * behind those the facts that the parse derives from the order and from the values (F_x; F(x)), so that a row of RULES can ask
+ * for either in one mask.  A valued option's bit says that a value was met, except -L and -r, which count bare too. */
+enum { O_f = 1, O_m, O_s, O_u, O_b, O_w, O_X, O_C, O_G, O_E, O_R, O_J, O_q, O_r, O_v, O_Q, O_U, O_P, O_g, O_S, O_M, O_O, O_A, O_B, O_N,
+       O_H, O_L, O_V, O_D, O_W, O_K, O_Z, O_o, O_COUNT,
+       F_q = O_COUNT, F_r, F_m, F_s,      /* the mode: the last of -q, -r, -m and -s (-s does not count after -r) */
+       F_PERSET,                          /* -u, -b and -w have their sets: mode -q, or -Q with no mode at all */
+       F_MINOV,                           /* -O, -A or -B */
+       F_RESAMPLE,                        /* -P and -M resample */
+       F_BAD_P, F_BAD_M, F_BAD_Z, F_BAD_D, F_BAD_N, F_BAD_V, F_BAD_L, F_BAD_H,       /* the value does not parse (-M: neither circular nor shuffle) */
+       F_L_BARE,                          /* -L without a value */
+       F_V_BLIND,                         /* -V with an op other than count on a database without values */
+       F_COUNT };
+_Static_assert(F_COUNT <= 64, "the options and facts of igd search share one 64-bit mask");
+#define B(x) (1ULL << O_##x)
+#define F(x) (1ULL << F_##x)
+
+typedef struct {
+    uint64_t given;
+    char *val[O_COUNT];                   /* the value of a valued option (-r: the contig), or NULL */
+    int mode, cmd;                        /* F_q, F_r, F_m, F_s or 0; the CMD_ that search_check chose */
+    /* every value parsed once */
+    int32_t v, qs, qe;                    /* -v; -r's start and end */
+    long long np;                         /* -P (0: none) */
+    uint64_t seed;                        /* -S */
+    int pmode;                            /* IGD_HIP_PERM_: -W's, -M resample's, or -M's */
+    int32_t distW, nearW, flankBins;      /* -D (-1: none), -N, -L */
+    int32_t histEdges[IGD_HIP_NEAREST_MAX_EDGES];
+    int histNe, mapOp;                    /* -H; -V's index in MAP_OPS */
+    int32_t *shiftOff;                    /* -Z: malloc'd offsets */
+    int nShift;
+} cli_opts;
+
 /* ------------------------------- `igd search -q F -P N -g genome` ------------------------ */
 /* Permutation null of the support counts of one query file: the regions are shifted along their contigs (-M circular, the
  * default: one offset per permutation and contig) or placed anew on them (-M shuffle) N times, seed -S (default 0); the
@@ -1578,10 +1612,15 @@ static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t 
 /* `-Z W,STEP` prints the shift profile of the support instead (shift_table below): nshift > 0 offsets; nperm may be 0 then. */
 static void shift_table(const igdc_queries *q, const int32_t *len, const int32_t *offsets, int nshift, int64_t nperm, uint64_t seed, int pmode,
                         int32_t ev, int rule);
-static void permute_file(char *path, const char *genome, const char *wsName, const char *uniName, int64_t nperm, uint64_t seed, int pmode,
-                         int32_t v, int32_t window, int gbp, const int32_t *offsets, int nshift)
+static void permute_file(const cli_opts *o)
 {
     if (!g_core || !cur_igd()) { engine(); return; }
+    char *path = o->val[O_q];
+    const char *genome = o->val[O_g], *wsName = o->val[O_W], *uniName = o->pmode == IGD_HIP_PERM_RESAMPLE ? o->val[O_U] : NULL;
+    const int64_t nperm = o->np;
+    const uint64_t seed = o->seed;
+    const int pmode = o->pmode, gbp = (o->given & B(G)) != 0;
+    const int32_t v = o->v, window = o->distW;
     const int32_t nfiles = IGD->nFiles, nC = nfiles + 1;
     int rule;
     const int32_t ev = q_dispatch(v, &rule);
@@ -1675,7 +1714,7 @@ static void permute_file(char *path, const char *genome, const char *wsName, con
         printf("Not supported: -P %lld with %lld regions\n", (long long)nperm, (long long)q.n);
         goto done;
     }
-    if (nshift > 0) shift_table(&q, len, offsets, nshift, nperm, seed, pmode, ev, rule);
+    if (o->nShift > 0) shift_table(&q, len, o->shiftOff, o->nShift, nperm, seed, pmode, ev, rule);
     else if (gbp) permute_bp_table(&q, len, nperm, seed, pmode, ev, rule);
     else if (window >= 0) permute_nearest_table(&q, len, nperm, seed, pmode, ev, window);
     else {
@@ -1788,17 +1827,6 @@ static int parse_shifts(const char *arg, int32_t **offsets)
     for (long long j = -k; j <= k; j++) o[j + k] = (int32_t)(j * step);
     *offsets = o;
     return (int)(2 * k + 1);
-}
-
-static int refused_shift(const char *why, const char *arg)                   /* -Z's refusals: stderr, nothing on stdout */
-{
-    fprintf(stderr, "Not supported: %s%s\n", why, arg ? arg : "");
-    return EX_USAGE;
-}
-
-static int refused_resample(const char *why)                                 /* -M resample's refusals: stderr, nothing on stdout */
-{
-    return refused_shift(why, NULL);
 }
 
 /* ------------------------------- `igd search -q F -N <bp>` / `-Q <list> -N <bp>` ------- */
@@ -2167,7 +2195,7 @@ static int usage_search(void)
     return EX_OK;
 }
 
-/* `-P <permutations>`: 1 when the argument is a whole number in 1 .. IGD_HIP_PERM_MAX; -D, -G and plain -P word their own refusals */
+/* `-P <permutations>`: 1 when the argument is a whole number in 1 .. IGD_HIP_PERM_MAX */
 static int parse_perm_count(const char *arg, long long *np)
 {
     char *end = NULL;
@@ -2175,15 +2203,12 @@ static int parse_perm_count(const char *arg, long long *np)
     return end != arg && !*end && *np >= 1 && *np <= (long long)IGD_HIP_PERM_MAX;
 }
 
-/* `-D <bp>`: the window of the distance null into *w; 0 with its one refusal line on `to` for anything but 0 .. 2^30 */
-static int parse_dist_window(const char *arg, FILE *to, int32_t *w)
+/* `-N <bp>`, `-D <bp>`: 1 with the window in *w when the argument is a whole number in 0 .. 2^30 */
+static int parse_window(const char *arg, int32_t *w)
 {
     char *end = NULL;
     const long long ww = strtoll(arg, &end, 10);
-    if (end == arg || *end || ww < 0 || ww > (long long)IGD_HIP_NEAREST_MAX_WINDOW) {
-        fprintf(to, "Not supported: -D %s (a window of 0 to %lld base pairs)\n", arg, (long long)IGD_HIP_NEAREST_MAX_WINDOW);
-        return 0;
-    }
+    if (end == arg || *end || ww < 0 || ww > (long long)IGD_HIP_NEAREST_MAX_WINDOW) return 0;
     *w = (int32_t)ww;
     return 1;
 }
@@ -2195,10 +2220,340 @@ static int parse_perm_mode(const char *arg)
     return strcmp(arg, "shuffle") == 0 ? IGD_HIP_PERM_SHUFFLE : -1;
 }
 
-static int refused_usage(const char *why)                                    /* the refusals of the newer options */
+/* `-O <bp>`, `-A <F>`, `-B <F>` (a minimum overlap per pair, see g_mo) into g_mo_val; 0 after the refusal of a missing or malformed value */
+static int parse_min_overlap(const char *a, const char *arg)
 {
-    printf("Not supported: %s\n", why);
-    return EX_USAGE;
+    char *end = NULL;
+    const long long bpv = a[1] == 'O' && arg ? strtoll(arg, &end, 10) : -1;
+    const int32_t ppm = a[1] != 'O' && arg ? parse_ppm(arg) : -1;
+    if (a[1] == 'O' ? (!end || end == arg || *end || bpv < 0 || bpv > INT32_MAX) : ppm < 0) {
+        printf("Not supported: %s %s (%s)\n", a, arg ? arg : "",
+               a[1] == 'O' ? "a number of base pairs, 0 to 2147483647" : "a decimal fraction in [0, 1] with at most six places");
+        return 0;
+    }
+    if (a[1] == 'O') g_mo_val.min_bp = (int32_t)bpv;
+    else if (a[1] == 'A') g_mo_val.ppm_query = ppm;
+    else g_mo_val.ppm_record = ppm;
+    return 1;
+}
+
+/* How an answer of the command line leaves: the older refusals on stdout with exit code 0, the newer ones as usage errors, those
+ * of -Z and -M resample on stderr with nothing on stdout.  In RULES the same column also holds what is no refusal: the groups file
+ * of -K is read at that place, or a command is taken. */
+enum { OLD = 1, NEW, ERR, GROUPS, CMD_PERMUTE, CMD_JACCARD, CMD_MAP, CMD_NEAREST, CMD_COOCCUR, CMD_ENRICH, CMD_FULL, CMD_MEMBERS, CMD_SUPPORT,
+       CMD_COUNT, CMD_REGION, CMD_HITMAP, CMD_SEQPARE, CMD_SETS, CMD_USAGE };
+#define NS "Not supported: "
+
+static int say(int how, const char *text, const char *arg, const char *tail)
+{
+    fprintf(how == ERR ? stderr : stdout, "%s%s%s\n", text, arg ? arg : "", tail ? tail : "");
+    return how == OLD ? EX_OK : EX_USAGE;
+}
+
+/* One row per option.  words: the words of its value.  STEP: the parse steps over the value; without it the value is looked at
+ * again as an option.  BARE: the option counts without its value too.  EAGER: parsed and refused where it stands
+ * (parse_min_overlap).  AFTER_R: does not set the mode after -r.  mode: the mode it sets.  miss, how: the answer to a missing
+ * value, given where it is met; none: the option is ignored then.  Words that are no row (-c among them) are ignored. */
+enum { STEP = 1, BARE = 2, EAGER = 4, AFTER_R = 8 };
+#define OPT(x, ...) {.name = "-" #x, .id = O_##x, .words = __VA_ARGS__}
+static const struct { const char *name; int id, words, flags, mode; const char *miss; int how; } OPTS[] = {
+    OPT(f, 0), OPT(u, 0), OPT(b, 0), OPT(w, 0), OPT(X, 0), OPT(C, 0), OPT(G, 0), OPT(E, 0), OPT(R, 0), OPT(J, 0),
+    OPT(m, 0, 0, F_m),
+    OPT(s, 0, AFTER_R, F_s),
+    OPT(q, 1, 0, F_q, "No query file.", OLD),
+    OPT(r, 3, BARE, F_r),
+    OPT(v, 1),
+    OPT(Q, 1),
+    OPT(o, 1),
+    OPT(U, 1, 0, 0, "No universe file.", OLD),
+    OPT(P, 1, 0, 0, "No number of permutations.", OLD),
+    OPT(g, 1, 0, 0, "No genome file.", OLD),
+    OPT(S, 1, 0, 0, "No seed.", OLD),
+    OPT(M, 1, 0, 0, "No mode.", OLD),
+    OPT(W, 1, 0, 0, NS "-W without a workspace file", NEW),
+    OPT(N, 1, STEP, 0, "No window.", OLD),                  /* (the window is not an option: "-N -5" is a refused window) */
+    OPT(H, 1, STEP, 0, NS "-H without a list of edges", NEW),
+    OPT(L, 1, STEP | BARE),
+    OPT(V, 1, STEP, 0, NS "-V without an op (count, sum, min, max or mean)", NEW),
+    OPT(D, 1, STEP, 0, NS "-D without a window", NEW),
+    OPT(K, 1, STEP, 0, NS "-K without a groups file", NEW),
+    OPT(Z, 1, STEP, 0, NS "-Z without W,STEP", ERR),
+    OPT(O, 1, STEP | EAGER), OPT(A, 1, STEP | EAGER), OPT(B, 1, STEP | EAGER),
+};
+
+/* argv into *o.  -1, or the exit code after the answer to a missing or (-O, -A, -B) refused value */
+static int search_parse(cli_opts *o, int argc, char **argv)                  /* :931-971 */
+{
+    for (int i = 3; i < argc; i++) {
+        size_t k = 0;
+        while (k < sizeof OPTS / sizeof *OPTS && strcmp(argv[i], OPTS[k].name) != 0) k++;
+        if (k == sizeof OPTS / sizeof *OPTS) continue;
+        const int id = OPTS[k].id, flags = OPTS[k].flags, have = i + OPTS[k].words < argc;
+        if (flags & EAGER) { if (!parse_min_overlap(argv[i], have ? argv[i + 1] : NULL)) return EX_USAGE; }
+        else if (!have && OPTS[k].miss) return say(OPTS[k].how, OPTS[k].miss, NULL, NULL);
+        else if (!have && !(flags & BARE)) continue;
+        o->given |= 1ULL << id;
+        if (!have) continue;
+        if (OPTS[k].words) o->val[id] = argv[i + 1];
+        if (id == O_r) { o->qs = atoi(argv[i + 2]); o->qe = atoi(argv[i + 3]); }
+        if (OPTS[k].mode && !((flags & AFTER_R) && o->mode == F_r)) o->mode = OPTS[k].mode;
+        if (flags & STEP) i += OPTS[k].words;
+    }
+    if (o->mode) o->given |= 1ULL << o->mode;
+    if (o->mode == F_q || (!o->mode && (o->given & B(Q)))) o->given |= F(PERSET);
+    if (o->given & (B(O) | B(A) | B(B))) o->given |= F(MINOV);
+    const char *a;
+    o->v = o->val[O_v] ? atoi(o->val[O_v]) : 0;
+    o->seed = o->val[O_S] ? (uint64_t)strtoull(o->val[O_S], NULL, 10) : 0;
+    if ((a = o->val[O_P]) && !parse_perm_count(a, &o->np)) { o->np = 0; o->given |= F(BAD_P); }
+    o->pmode = o->val[O_W] ? IGD_HIP_PERM_WORKSPACE : parse_perm_mode(o->val[O_M]);
+    if (parse_perm_mode(o->val[O_M]) < 0) o->given |= F(BAD_M);
+    if (o->val[O_P] && o->val[O_M] && strcmp(o->val[O_M], "resample") == 0) { o->given |= F(RESAMPLE); o->pmode = IGD_HIP_PERM_RESAMPLE; }
+    o->distW = -1;
+    if ((a = o->val[O_D]) && !parse_window(a, &o->distW)) o->given |= F(BAD_D);
+    if ((a = o->val[O_N]) && !parse_window(a, &o->nearW)) o->given |= F(BAD_N);
+    if ((a = o->val[O_L])) {
+        char *end = NULL;
+        const long long nb = strtoll(a, &end, 10);
+        if (a[0] < '0' || a[0] > '9' || *end || !igd_hip_flank_bins_valid(nb)) o->given |= F(BAD_L);
+        else o->flankBins = (int32_t)nb;
+    } else if (o->given & B(L)) o->given |= F(L_BARE);
+    if ((a = o->val[O_H]) && (o->histNe = parse_edges(a, o->histEdges)) < 1) o->given |= F(BAD_H);
+    o->mapOp = -1;
+    for (int k = 0; (a = o->val[O_V]) && k < 5; k++) if (strcmp(a, MAP_OPS[k]) == 0) o->mapOp = k;
+    if (a && o->mapOp < 0) o->given |= F(BAD_V);
+    if (a && o->mapOp > 0 && IGD->gType == 0) o->given |= F(V_BLIND);
+    if ((a = o->val[O_Z]) && (o->nShift = parse_shifts(a, &o->shiftOff)) < 1) o->given |= F(BAD_Z);
+    return -1;
+}
+
+/* What `igd search` answers, as ONE ordered list: the first row that applies is the answer.  A row applies when every option and
+ * fact of `all` is given, one of `any` (where there is an `any`) and none of `none`; so "-X together with .." rows keep their
+ * partners in `any`, "-X without .." rows in `none`.  The answer is a refusal -- the sentence as it is printed, with the value
+ * of option `arg` and `tail` behind it where the sentence quotes one -- or a command.  The order is the behaviour: where two
+ * refusals apply the earlier one answers (-J -P 5: -J's sentence, not -P's), and a command that stands ahead of a refusal wins
+ * over it (-q F -f -w -u prints every overlap).  The letters of a sentence stand in an order of their own; the mask beside it is what decides. */
+#define OTHER (B(m) | B(s) | B(r))
+#define QSET (F(q) | B(Q))                /* -q or -Q names the query sets */
+#define RULE(a, y, n, ...) {.all = (a), .any = (y), .none = (n), .how = __VA_ARGS__}
+static const struct { uint64_t all, any, none; int how; const char *text; int arg; const char *tail; } RULES[] = {
+    /* -Z: the shift profile */
+    RULE(B(Z), B(Q), 0, ERR, NS "-Z together with -Q"),
+    RULE(B(Z), B(u) | B(U) | B(b) | B(J) | B(w) | B(C) | B(N) | B(V) | B(K) | OTHER | B(f) | B(R) | B(X) | B(H) | B(L) | B(E), 0, ERR,
+     NS "-Z together with -u, -U, -b, -J, -w, -C, -N, -V, -K, -m, -s, -r, -f, -R, -X, -H, -L or -E"),
+    RULE(B(Z), B(D) | B(G), 0, ERR, NS "-Z together with -D or -G (the shift profile is the support's)"),
+    RULE(B(Z), 0, B(g), ERR, NS "-Z without -g"),
+    RULE(B(Z), 0, F(q), ERR, NS "-Z without -q"),
+    RULE(B(Z), B(S) | B(M) | B(W), B(P), ERR, NS "-Z with -S, -M or -W but without -P"),
+    RULE(B(Z) | B(W) | B(M), 0, 0, ERR, NS "-W together with -M (the workspace is the placement)"),
+    RULE(B(Z), F(BAD_P), 0, ERR, NS "-Z with a number of permutations outside 1 to 1048576"),
+    RULE(B(Z) | B(P), F(BAD_M), 0, ERR, NS "-Z with a -M that is neither circular nor shuffle"),
+    RULE(B(Z), F(BAD_Z), 0, ERR, NS "-Z W,STEP needs 0 <= W <= 1073741824, STEP >= 1 and at most 4096 shifts, not ", O_Z),
+    RULE(B(Z), 0, 0, CMD_PERMUTE),
+    /* -P -M resample: the one -P that takes -U, so it stands ahead of -G and -D, which refuse -U */
+    RULE(F(RESAMPLE), 0, B(U), ERR, NS "-M resample without -U"),
+    RULE(F(RESAMPLE), B(g) | B(W), 0, ERR, NS "-M resample together with -g or -W (the universe is the placement)"),
+    RULE(F(RESAMPLE), B(Q) | B(R) | B(X) | B(K) | B(Z), 0, ERR, NS "-M resample together with -Q, -R, -X, -K or -Z"),
+    RULE(F(RESAMPLE), B(u) | B(b) | B(w) | B(C) | B(f) | OTHER | B(J) | B(V) | B(N) | B(H) | B(L) | B(E), 0, ERR,
+     NS "-M resample together with -u, -b, -w, -C, -f, -m, -s, -r, -J, -V, -N, -H, -L or -E"),
+    RULE(F(RESAMPLE) | B(D) | B(G), 0, 0, ERR, NS "-M resample together with both -D and -G"),
+    RULE(F(RESAMPLE) | F(MINOV), B(D) | B(G), 0, ERR, NS "-M resample -D or -G together with -O, -A or -B"),
+    RULE(F(RESAMPLE), 0, F(q), ERR, NS "-M resample without -q"),
+    RULE(F(RESAMPLE), F(BAD_P), 0, ERR, NS "-M resample with a number of permutations outside 1 to 1048576"),
+    RULE(F(RESAMPLE), F(BAD_D), 0, ERR, NS "-D ", O_D, " (a window of 0 to 1073741824 base pairs)"),
+    RULE(F(RESAMPLE), 0, 0, CMD_PERMUTE),
+    /* -K: groups of datasets; the file is read, and refused for what it holds, once the options stand */
+    RULE(B(K), B(b) | B(w) | B(X) | B(C) | B(P) | B(D) | B(G) | B(W) | B(J) | B(V) | B(N) | B(H) | B(L) | B(E) | B(f) | OTHER, 0, NEW,
+     NS "-K together with -b, -w, -X, -C, -P, -D, -G, -W, -J, -V, -N, -H, -L, -E, -f, -m, -s or -r"),
+    RULE(B(K), 0, B(u) | B(U), NEW, NS "-K without -u or -U"),
+    RULE(B(K), 0, QSET, NEW, NS "-K without -q or -Q"),
+    RULE(B(K), 0, 0, GROUPS),
+    /* -W: a workspace */
+    RULE(B(W), 0, B(P), NEW, NS "-W without -P"),
+    RULE(B(W) | B(M), 0, 0, NEW, NS "-W together with -M (the workspace is the placement)"),
+    /* -G: the null of the base pairs */
+    RULE(B(G), 0, B(P), NEW, NS "-G without -P"),
+    RULE(B(G), B(D) | B(J) | F(MINOV) | B(N) | B(H) | B(L) | B(E) | B(V) | B(Q) | B(u) | B(b) | B(w) | B(U) | B(R) | B(X) | B(C) | B(f) | OTHER, 0, NEW,
+     NS "-G together with -D, -J, -O, -A, -B, -N, -H, -L, -E, -V, -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r"),
+    RULE(B(G), 0, B(g), NEW, NS "-G -P without -g"),
+    RULE(B(G), 0, F(q), NEW, NS "-G -P without -q"),
+    RULE(B(G), F(BAD_P), 0, NEW, NS "-G with a number of permutations outside 1 to 1048576"),
+    RULE(B(G), F(BAD_M), 0, NEW, NS "-G with a -M that is neither circular nor shuffle"),
+    /* -J: base-pair Jaccard */
+    RULE(B(J), B(u) | B(b) | B(w) | B(U) | B(R) | B(X) | B(C) | B(P) | B(D) | B(N) | B(H) | B(L) | B(E) | B(V) | B(f) | OTHER | F(MINOV), 0, NEW,
+     NS "-J together with -u, -b, -w, -U, -R, -X, -C, -P, -D, -N, -H, -L, -E, -V, -f, -m, -s, -r, -O, -A or -B"),
+    RULE(B(J), 0, QSET, NEW, NS "-J without -q or -Q"),
+    /* -V: values of the overlapping records */
+    RULE(B(V), B(u) | B(b) | B(w) | B(U) | B(R) | B(X) | B(C) | B(P) | B(D) | B(N) | B(f) | OTHER | F(MINOV), 0, NEW,
+     NS "-V together with -u, -b, -w, -U, -R, -X, -C, -P, -D, -N, -f, -m, -s, -r, -O, -A or -B"),
+    RULE(B(V), 0, QSET, NEW, NS "-V without -q or -Q"),
+    RULE(B(V), F(BAD_V), 0, NEW, NS "-V ", O_V, " (count, sum, min, max or mean)"),
+    RULE(B(V), F(V_BLIND), 0, NEW, NS "-V ", O_V, " on a database without values (gType 0); -V count works there"),
+    /* -L, -E: relative distances */
+    RULE(B(E), 0, B(L), NEW, NS "-E without -L"),
+    RULE(B(L), 0, B(N), NEW, NS "-L without -N"),
+    RULE(B(L), B(H) | B(P) | B(D) | F(MINOV), 0, NEW, NS "-L together with -H, -P, -D, -O, -A or -B"),
+    RULE(B(L), F(L_BARE), 0, NEW, NS "-L without a number of bins"),
+    RULE(B(L), F(BAD_L), 0, NEW, NS "-L ", O_L, " (1 to 64 bins)"),
+    /* -H: signed distances */
+    RULE(B(H), 0, B(N), NEW, NS "-H without -N"),
+    RULE(B(H), B(P) | B(D), 0, NEW, NS "-H together with -P or -D"),
+    RULE(B(H), F(BAD_H), 0, NEW, NS "-H ", O_H, " (1 to 63 ascending integer edges, each within int32, separated by commas)"),
+    /* -D: the null of the distances */
+    RULE(B(D), 0, B(P), NEW, NS "-D without -P"),
+    RULE(B(D), B(N) | F(MINOV) | B(Q) | B(u) | B(b) | B(w) | B(U) | B(R) | B(X) | B(C) | B(f) | OTHER, 0, NEW,
+     NS "-D together with -N, -O, -A, -B, -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r"),
+    RULE(B(D), 0, B(g), NEW, NS "-D -P without -g"),
+    RULE(B(D), 0, F(q), NEW, NS "-D -P without -q"),
+    RULE(B(D), F(BAD_P), 0, NEW, NS "-D with a number of permutations outside 1 to 1048576"),
+    RULE(B(D), F(BAD_M), 0, NEW, NS "-D with a -M that is neither circular nor shuffle"),
+    RULE(B(D), F(BAD_D), 0, NEW, NS "-D ", O_D, " (a window of 0 to 1073741824 base pairs)"),
+    /* -N: nearest records (the older wording, and exit code 0) */
+    RULE(B(N), B(u) | B(b) | B(w) | B(U) | B(R) | B(X) | B(C) | B(P) | B(f) | OTHER | F(MINOV), 0, OLD,
+     NS "-N together with -u, -b, -w, -U, -R, -X, -C, -P, -f, -m, -s, -r, -O, -A or -B"),
+    RULE(B(N), 0, QSET, OLD, NS "-N without -q or -Q"),
+    RULE(B(N), F(BAD_N), 0, OLD, NS "-N ", O_N, " (a window of 0 to 1073741824 base pairs)"),
+    /* -O, -A, -B: a minimum overlap */
+    RULE(F(MINOV), B(b) | B(w) | B(X) | B(C) | B(f) | OTHER, 0, NEW, NS "-O, -A or -B together with -b, -w, -X, -C, -f, -m, -s or -r, or without -q or -Q"),
+    RULE(F(MINOV), 0, QSET, NEW, NS "-O, -A or -B together with -b, -w, -X, -C, -f, -m, -s or -r, or without -q or -Q"),
+    /* the commands, and the older refusals between them */
+    RULE(0, B(g) | B(S) | B(M), B(P), OLD, NS "-g, -S or -M without -P"),
+    RULE(B(J), 0, 0, CMD_JACCARD),
+    RULE(B(V), 0, 0, CMD_MAP),
+    RULE(B(N), 0, 0, CMD_NEAREST),
+    RULE(B(P), B(Q) | B(u) | B(b) | B(w) | B(U) | B(R) | B(X) | B(C) | B(f) | OTHER, 0, OLD, NS "-P together with -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r"),
+    RULE(B(P), 0, B(g), OLD, NS "-P without -g"),
+    RULE(B(P), 0, F(q), OLD, NS "-P without -q"),
+    RULE(B(P), F(BAD_P), 0, OLD, NS "-P ", O_P, " (1 to 1048576 permutations)"),
+    RULE(B(P), F(BAD_M), 0, OLD, NS "-M ", O_M, " (circular or shuffle)"),
+    RULE(B(P), 0, 0, CMD_PERMUTE),
+    RULE(B(C), B(Q) | B(u) | B(b) | B(w) | B(U) | B(R) | B(X) | B(f) | OTHER, 0, OLD, NS "-C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r"),
+    RULE(B(C), 0, F(q), OLD, NS "-C without -q"),
+    RULE(B(C), 0, 0, CMD_COOCCUR),
+    RULE(B(R), 0, B(U), OLD, NS "-R without -U"),
+    RULE(B(X), 0, B(U), OLD, NS "-X without -U"),
+    RULE(B(U), B(b) | B(w) | B(f) | OTHER, 0, OLD, NS "-U together with -b, -w, -f, -m, -s or -r"),
+    RULE(B(U), QSET, 0, CMD_ENRICH),
+    RULE(B(f), 0, F(q) | F(r), OLD, "Not supported -f option"),
+    RULE(B(f), 0, 0, CMD_FULL),
+    RULE(F(PERSET) | B(w), B(u) | B(b), 0, OLD, NS "-w together with -u or -b"),
+    RULE(F(PERSET) | B(w), 0, 0, CMD_MEMBERS),
+    RULE(F(PERSET) | B(u) | B(b), 0, 0, OLD, NS "-b together with -u"),
+    RULE(F(PERSET), B(u) | B(b), 0, CMD_SUPPORT),
+    RULE(F(q), 0, 0, CMD_COUNT),
+    RULE(F(r), 0, 0, CMD_REGION),
+    RULE(F(m), 0, 0, CMD_HITMAP),
+    RULE(F(s), 0, 0, CMD_SEQPARE),
+    RULE(B(Q), 0, 0, CMD_SETS),                       /* only where the reference's own parse leaves nothing to do */
+    RULE(0, 0, 0, CMD_USAGE),
+};
+_Static_assert(IGD_HIP_PERM_MAX == 1048576 && IGD_HIP_NEAREST_MAX_WINDOW == 1073741824 && IGD_HIP_SHIFT_MAX_OFFSET == 1073741824 &&
+               IGD_HIP_SHIFT_MAX == 4096 && IGD_HIP_FLANK_MAX_BINS == 64 && IGD_HIP_NEAREST_MAX_EDGES == 63, "RULES spells these limits out");
+
+/* The first row of RULES that applies: the exit code after its refusal, or -1 with the command in o->cmd */
+static int search_check(cli_opts *o)
+{
+    for (size_t k = 0;; k++) {
+        if ((o->given & RULES[k].all) != RULES[k].all || (RULES[k].any && !(o->given & RULES[k].any)) || (o->given & RULES[k].none)) continue;
+        const int how = RULES[k].how;
+        if (how == GROUPS) {
+            const int rc = groups_read(o->val[O_K]);
+            if (rc) return rc;
+        } else if (how >= CMD_PERMUTE) {
+            o->cmd = how;
+            return -1;
+        } else return say(how, RULES[k].text, RULES[k].arg ? o->val[RULES[k].arg] : NULL, RULES[k].tail);
+    }
+}
+
+/* `-m`: the dataset x dataset hit map into the file `name` (-o; default Hitsmap) */
+static void hitmap_file(int32_t v, const char *name)                         /* :996-1022 */
+{
+    const int32_t nfiles = IGD->nFiles;
+    char out[64] = "";
+    if (name) strncpy(out, name, sizeof out - 1);
+    if (IGD->gType != 1) {
+        printf("igd: -m needs a database created with 16-byte records (gType 1)\n");
+        return;
+    }
+    uint32_t **hitmap = (uint32_t **)malloc(sizeof(uint32_t *) * (size_t)(nfiles + 1));
+    for (int32_t i = 0; i < nfiles; i++) hitmap[i] = (uint32_t *)calloc((size_t)nfiles + 1, sizeof(uint32_t));
+    if (v > 0) getMap_v(hitmap, v); else getMap(hitmap);
+    if (strlen(out) < 2) strcpy(out, "Hitsmap");
+    FILE *fo = g_fail_rc ? NULL : fopen(out, "w");
+    if (g_fail_rc) ;                                /* no matrix of zeros after an engine failure */
+    else if (!fo) printf("Can't open file %s\n", out);
+    else {
+        static char obuf[1 << 20];
+        setvbuf(fo, obuf, _IOFBF, sizeof obuf);
+        fprintf(fo, "%u\t%u\t%u\n", (unsigned)nfiles, (unsigned)nfiles, (unsigned)v);
+        for (int32_t i = 0; i < nfiles; i++) {
+            for (int32_t j = 0; j < nfiles; j++) fprintf(fo, "%u\t", hitmap[i][j]);
+            fprintf(fo, "\n");
+        }
+        fclose(fo);
+    }
+    for (int32_t i = 0; i < nfiles; i++) free(hitmap[i]);
+    free(hitmap);
+}
+
+/* The command that search_check chose */
+static void search_run(const cli_opts *o, int64_t *hits)
+{
+    const int32_t nfiles = IGD->nFiles, v = o->v;
+    char *qfName = o->val[O_q] ? o->val[O_q] : (char *)"", *chrm = o->val[O_r];
+    /* the query files of the per-set commands: -q's when it is the mode, else the -Q list's; opened by the command that reads them */
+    char *const oneFile = o->mode == F_q ? qfName : NULL, *const listName = o->val[O_Q];
+    cli_paths P;
+    memset(&P, 0, sizeof P);
+    int64_t total;
+    switch (o->cmd) {
+    case CMD_PERMUTE: permute_file(o); break;
+    case CMD_JACCARD: if (paths_open(&P, oneFile, listName)) jaccard_files(&P, v); break;
+    case CMD_MAP: if (paths_open(&P, oneFile, listName)) map_files(&P, v, o->mapOp); break;
+    case CMD_NEAREST:
+        if (!paths_open(&P, oneFile, listName)) break;
+        if (o->given & B(L)) flank_reldist_files(&P, v, o->nearW, o->given & B(E) ? IGD_HIP_FLANK_EDGES : IGD_HIP_FLANK_MIDPOINTS, o->flankBins);
+        else if (o->given & B(H)) nearest_hist_files(&P, v, o->nearW, o->histEdges, o->histNe);
+        else nearest_files(&P, v, o->nearW);
+        break;
+    case CMD_COOCCUR: cooccur_file(qfName, v); break;
+    case CMD_ENRICH: if (paths_open(&P, oneFile, listName)) enrich_files(&P, o->val[O_U], v, (o->given & B(R)) != 0, (o->given & B(X)) != 0); break;
+    case CMD_FULL:                                                            /* :975-995 */
+        if (o->mode == F_q) total = IGD->gType == 0 ? getOverlaps_f0(qfName) : getOverlaps_f1(qfName);
+        else total = IGD->gType == 0 ? get_overlaps_f0(chrm, o->qs, o->qe) : get_overlaps_f1(chrm, o->qs, o->qe);
+        if (!g_fail_rc) printf("Total overlaps: %lld\n", (long long)total);
+        break;
+    case CMD_MEMBERS: if (paths_open(&P, oneFile, listName)) membership_files(&P, v); break;
+    case CMD_SUPPORT: if (paths_open(&P, oneFile, listName)) support_files(&P, v, (o->given & B(b)) != 0); break;
+    case CMD_COUNT:                                                           /* :1023-1040 */
+        count_file(qfName, v, hits);
+        if (!g_fail_rc) print_hits_table(hits);
+        break;
+    case CMD_REGION:                                                          /* :1041-1053 */
+        if (IGD->gType == 0) get_overlaps0(chrm, o->qs, o->qe, hits);
+        else if (v > 0) get_overlaps_v(chrm, o->qs, o->qe, v, hits);
+        else get_overlaps(chrm, o->qs, o->qe, hits);
+        if (!g_fail_rc) printf("index\t number of regions\t number of hits\t File_name\n");
+        for (int32_t i = 0; i < nfiles && !g_fail_rc; i++)
+            printf("%i\t%i\t%lld\t%s\n", i, IGD->finfo[i].nr, (long long)hits[i], IGD->finfo[i].fileName);
+        break;
+    case CMD_HITMAP: hitmap_file(v, o->val[O_o]); break;
+    case CMD_SEQPARE:                                                         /* :1054-1061 */
+        if (IGD->gType != 1) printf("igd: -s needs a database created with 16-byte records (gType 1)\n");
+        else {
+            double *sm = (double *)malloc(sizeof(double) * (size_t)(nfiles + 1));
+            seqOverlaps(qfName, sm);
+            if (!g_fail_rc) printf("index\t number of regions\t similarity\t dataset name\n");
+            for (int32_t i = 0; i < nfiles && !g_fail_rc; i++)
+                printf("%i\t%i\t%10.6f\t%s\n", i, IGD->finfo[i].nr, sm[i], IGD->finfo[i].fileName);
+            free(sm);
+        }
+        break;
+    case CMD_SETS: if (paths_open(&P, oneFile, listName)) search_sets(&P, v, hits); break;
+    default: usage_search();
+    }
+    paths_close(&P);
 }
 
 int igd_search(int argc, char **argv)                                        /* :889-1079 */
@@ -2221,6 +2576,11 @@ int igd_search(int argc, char **argv)                                        /* 
     IGD = get_igdinfo(igdName);
     if (!IGD) return EX_OK;
     phase("header", &t0);
+    /* from here on every way out is the release below: refusal, usage, success and engine failure alike */
+    int rc = EX_OK;
+    int64_t *hits = NULL;
+    cli_opts o;
+    memset(&o, 0, sizeof o);
     char *tsv = igdc_index_path(igdName);
     {   /* fname = path without extension; the reference strcpy's into 64 bytes (:916-922) */
         size_t stem = strlen(tsv) - strlen("_index.tsv");
@@ -2230,445 +2590,40 @@ int igd_search(int argc, char **argv)                                        /* 
     }
     IGD->finfo = get_fileinfo(tsv, &IGD->nFiles);
     free(tsv);
-    if (!IGD->finfo) return EX_OK;
-    const int32_t nfiles = IGD->nFiles;
-    int64_t *hits = (int64_t *)calloc((size_t)nfiles + 1, sizeof(int64_t));
+    if (IGD->finfo) {
+        hits = (int64_t *)calloc((size_t)IGD->nFiles + 1, sizeof(int64_t));
+        g_mo_val.min_bp = g_mo_val.ppm_query = g_mo_val.ppm_record = 0;
+        groups_free();
+        if ((rc = search_parse(&o, argc, argv)) < 0) rc = search_check(&o);
+        if (rc < 0) {
+            if ((o.given & F(MINOV)) && igd_hip_min_overlap_active(&g_mo_val)) g_mo = &g_mo_val;  /* (all three zero: no threshold) */
+            fP = fopen(igdName, "rb");                                        /* :974 */
+            search_run(&o, hits);
+            /* the reference's exit code is always 0; an engine failure (message already on stderr) is the one
+             * thing this tool reports through it, instead of printing a table of zeros */
+            rc = g_fail_rc ? EX_UNAVAILABLE : g_usage_rc ? EX_USAGE : EX_OK;
+        }
+    }
 
-    int32_t v = 0, qs = 1, qe = 2;
-    g_mo_val.min_bp = g_mo_val.ppm_query = g_mo_val.ppm_record = 0;
-    g_mo = NULL;
-    int mode = -1, full = 0, uniq = 0, bp = 0, memb = 0, ranks = 0, restricted = 0, cooc = 0, other = 0, minov = 0;      /* other: -m, -s or -r was given (-U refuses them) */
-    char *chrm = NULL, *qfName = (char *)"", *listName = NULL, *uniName = NULL;
-    char *permArg = NULL, *genomeName = NULL, *seedArg = NULL, *pmodeArg = NULL;      /* -P, -g, -S, -M (see permute_file) */
-    char *nearArg = NULL;                                                             /* -N (see nearest_files) */
-    char *distArg = NULL;                                                             /* -D (see permute_nearest_table) */
-    char *wsName = NULL;                                                              /* -W (see g_ws) */
-    char *histArg = NULL;                                                             /* -H (see nearest_hist_files) */
-    char *binsArg = NULL;                                                             /* -L (see flank_reldist_files) */
-    int flankL = 0, flankEdges = 0;                                                   /* -L, -E given */
-    int jac = 0;                                                                      /* -J given (see jaccard_files) */
-    int gbp = 0;                                                                      /* -G given (see permute_bp_table) */
-    char *mapArg = NULL;                                                              /* -V (see map_files) */
-    char *grpName = NULL;                                                             /* -K (see groups_read) */
-    char *shiftArg = NULL;                                                            /* -Z (see shift_table) */
-    char out[64] = "";
+    /* release everything, in the shape get_igdinfo/get_fileinfo handed it out (:1066-1078), and leave the process as a first
+     * call finds it */
     groups_free();
-    for (int i = 3; i < argc; i++) {                                          /* :931-971 */
-        const char *a = argv[i];
-        if (strcmp(a, "-Q") == 0) {                   /* (not the reference's: a list of query files, see search_sets) */
-            if (i + 1 < argc) listName = argv[i + 1];
-        } else if (strcmp(a, "-q") == 0) {
-            if (i + 1 >= argc) { printf("No query file.\n"); return EX_OK; }
-            qfName = argv[i + 1];
-            mode = 1;
-        } else if (strcmp(a, "-r") == 0) {
-            if (i + 3 < argc) {
-                mode = 2;
-                chrm = argv[i + 1];
-                qs = atoi(argv[i + 2]);
-                qe = atoi(argv[i + 3]);
-            }
-        } else if (strcmp(a, "-v") == 0) {
-            if (i + 1 < argc) v = atoi(argv[i + 1]);
-        } else if (strcmp(a, "-m") == 0) {
-            mode = 0;
-        } else if (strcmp(a, "-s") == 0 && mode != 2) {
-            mode = 3;
-        } else if (strcmp(a, "-f") == 0) {
-            full = 1;
-        } else if (strcmp(a, "-u") == 0) {            /* (not the reference's: support counts, see support_files) */
-            uniq = 1;
-        } else if (strcmp(a, "-b") == 0) {            /* (not the reference's: covered base pairs, see support_files) */
-            bp = 1;
-        } else if (strcmp(a, "-J") == 0) {            /* (not the reference's: base-pair Jaccard, see jaccard_files) */
-            jac = 1;
-        } else if (strcmp(a, "-G") == 0) {            /* (not the reference's: -P on the base-pair overlap, see permute_bp_table) */
-            gbp = 1;
-        } else if (strcmp(a, "-w") == 0) {            /* (not the reference's: per-query membership, see membership_files) */
-            memb = 1;
-        } else if (strcmp(a, "-U") == 0) {            /* (not the reference's: enrichment against a universe, see enrich_files) */
-            if (i + 1 >= argc) { printf("No universe file.\n"); return EX_OK; }
-            uniName = argv[i + 1];
-        } else if (strcmp(a, "-R") == 0) {            /* (not the reference's: rank and q-value columns of -U, see enrich_files) */
-            ranks = 1;
-        } else if (strcmp(a, "-X") == 0) {            /* (not the reference's: -U on the sets restricted to the universe, see enrich_files) */
-            restricted = 1;
-        } else if (strcmp(a, "-C") == 0) {            /* (not the reference's: dataset co-occurrence, see cooccur_file) */
-            cooc = 1;
-        } else if (strcmp(a, "-P") == 0) {            /* (not the reference's: permutation null of the support, see permute_file) */
-            if (i + 1 >= argc) { printf("No number of permutations.\n"); return EX_OK; }
-            permArg = argv[i + 1];
-        } else if (strcmp(a, "-N") == 0) {            /* (not the reference's: nearest record per dataset within a window, see nearest_files) */
-            if (i + 1 >= argc) { printf("No window.\n"); return EX_OK; }
-            nearArg = argv[i + 1];
-            i++;                                      /* (the window is not an option: "-N -5" is a refused window) */
-        } else if (strcmp(a, "-H") == 0) {            /* (not the reference's: histogram of the signed distances of -N, see nearest_hist_files) */
-            if (i + 1 >= argc) { printf("Not supported: -H without a list of edges\n"); return EX_USAGE; }
-            histArg = argv[i + 1];
-            i++;                                      /* (the list is not an option: "-H -500,0,500" is a list) */
-        } else if (strcmp(a, "-L") == 0) {            /* (not the reference's: histogram of the relative distances of -N, see flank_reldist_files) */
-            flankL = 1;
-            if (i + 1 < argc) { binsArg = argv[i + 1]; i++; }
-        } else if (strcmp(a, "-E") == 0) {            /* (not the reference's: -L between edges) */
-            flankEdges = 1;
-        } else if (strcmp(a, "-V") == 0) {            /* (not the reference's: values of the overlapping records, see map_files) */
-            if (i + 1 >= argc) { printf("Not supported: -V without an op (count, sum, min, max or mean)\n"); return EX_USAGE; }
-            mapArg = argv[i + 1];
-            i++;                                      /* (the op is not an option) */
-        } else if (strcmp(a, "-D") == 0) {            /* (not the reference's: -P on the distances, see permute_nearest_table) */
-            if (i + 1 >= argc) { printf("Not supported: -D without a window\n"); return EX_USAGE; }
-            distArg = argv[i + 1];
-            i++;                                      /* (the window is not an option: "-D -5" is a refused window) */
-        } else if (strcmp(a, "-W") == 0) {            /* (not the reference's: -P inside a workspace, see g_ws) */
-            if (i + 1 >= argc) { printf("Not supported: -W without a workspace file\n"); return EX_USAGE; }
-            wsName = argv[i + 1];
-        } else if (strcmp(a, "-K") == 0) {            /* (not the reference's: -u and -U per group of datasets, see groups_read) */
-            if (i + 1 >= argc) { printf("Not supported: -K without a groups file\n"); return EX_USAGE; }
-            grpName = argv[i + 1];
-            i++;
-        } else if (strcmp(a, "-Z") == 0) {            /* (not the reference's: support under rigid shifts, see shift_table) */
-            if (i + 1 >= argc) return refused_shift("-Z without W,STEP", NULL);
-            shiftArg = argv[i + 1];
-            i++;
-        } else if (strcmp(a, "-g") == 0) {
-            if (i + 1 >= argc) { printf("No genome file.\n"); return EX_OK; }
-            genomeName = argv[i + 1];
-        } else if (strcmp(a, "-S") == 0) {
-            if (i + 1 >= argc) { printf("No seed.\n"); return EX_OK; }
-            seedArg = argv[i + 1];
-        } else if (strcmp(a, "-M") == 0) {
-            if (i + 1 >= argc) { printf("No mode.\n"); return EX_OK; }
-            pmodeArg = argv[i + 1];
-        } else if (strcmp(a, "-O") == 0 || strcmp(a, "-A") == 0 || strcmp(a, "-B") == 0) {
-            /* (not the reference's: a minimum overlap per pair, see g_mo) */
-            char *end = NULL;
-            const long long bpv = a[1] == 'O' && i + 1 < argc ? strtoll(argv[i + 1], &end, 10) : -1;
-            const int32_t ppm = a[1] != 'O' && i + 1 < argc ? parse_ppm(argv[i + 1]) : -1;
-            if (a[1] == 'O' ? (!end || end == argv[i + 1] || *end || bpv < 0 || bpv > INT32_MAX) : ppm < 0) {
-                printf("Not supported: %s %s (%s)\n", a, i + 1 < argc ? argv[i + 1] : "",
-                       a[1] == 'O' ? "a number of base pairs, 0 to 2147483647" : "a decimal fraction in [0, 1] with at most six places");
-                return EX_USAGE;
-            }
-            if (a[1] == 'O') g_mo_val.min_bp = (int32_t)bpv;
-            else if (a[1] == 'A') g_mo_val.ppm_query = ppm;
-            else g_mo_val.ppm_record = ppm;
-            minov = 1;
-            i++;
-        } else if (strcmp(a, "-o") == 0) {
-            if (i + 1 < argc) { strncpy(out, argv[i + 1], sizeof out - 1); out[sizeof out - 1] = '\0'; }
-        }
-        if (strcmp(a, "-m") == 0 || strcmp(a, "-s") == 0 || strcmp(a, "-r") == 0) other = 1;
-    }
-
-    long long np = 0;                                                         /* -P's count, once a block below has parsed it */
-    int32_t *shiftOff = NULL;                                                 /* -Z: every refusal is a usage error, worded on stderr */
-    int nShift = 0;
-    if (shiftArg) {
-        const char *why = NULL;
-        if (listName) why = "-Z together with -Q";
-        else if (uniq || uniName || bp || jac || memb || cooc || nearArg || mapArg || grpName || full || other || ranks || restricted || histArg ||
-                 flankL || flankEdges)
-            why = "-Z together with -u, -U, -b, -J, -w, -C, -N, -V, -K, -m, -s, -r, -f, -R, -X, -H, -L or -E";
-        else if (distArg || gbp) why = "-Z together with -D or -G (the shift profile is the support's)";
-        else if (!genomeName) why = "-Z without -g";
-        else if (mode != 1) why = "-Z without -q";
-        else if (!permArg && (seedArg || pmodeArg || wsName)) why = "-Z with -S, -M or -W but without -P";
-        else if (wsName && pmodeArg) why = "-W together with -M (the workspace is the placement)";
-        else if (permArg && !parse_perm_count(permArg, &np)) why = "-Z with a number of permutations outside 1 to 1048576";
-        else if (permArg && parse_perm_mode(pmodeArg) < 0) why = "-Z with a -M that is neither circular nor shuffle";
-        if (why) return refused_shift(why, NULL);
-        if ((nShift = parse_shifts(shiftArg, &shiftOff)) < 1)
-            return refused_shift("-Z W,STEP needs 0 <= W <= 1073741824, STEP >= 1 and at most 4096 shifts, not ", shiftArg);
-    }
-    /* -M resample: every refusal is a usage error.  It is the one -P that takes -U, so it is decided in front of the blocks of -G
-     * and -D below, which refuse -U and are skipped for it; -Z above has refused it already (its parse_perm_mode knows circular and
-     * shuffle only). */
-    const int resample = permArg && pmodeArg && strcmp(pmodeArg, "resample") == 0;
-    int32_t distW = -1;                                                       /* -D's window, here or in -D's own block below */
-    if (resample) {
-        const char *why = NULL;
-        if (!uniName) why = "-M resample without -U";
-        else if (genomeName || wsName) why = "-M resample together with -g or -W (the universe is the placement)";
-        else if (listName || ranks || restricted || grpName || shiftArg) why = "-M resample together with -Q, -R, -X, -K or -Z";
-        else if (uniq || bp || memb || cooc || full || other || jac || mapArg || nearArg || histArg || flankL || flankEdges)
-            why = "-M resample together with -u, -b, -w, -C, -f, -m, -s, -r, -J, -V, -N, -H, -L or -E";
-        else if (distArg && gbp) why = "-M resample together with both -D and -G";
-        else if ((distArg || gbp) && minov) why = "-M resample -D or -G together with -O, -A or -B";
-        else if (mode != 1) why = "-M resample without -q";
-        else if (!parse_perm_count(permArg, &np)) why = "-M resample with a number of permutations outside 1 to 1048576";
-        if (why) return refused_resample(why);
-        if (distArg && !parse_dist_window(distArg, stderr, &distW)) return EX_USAGE;
-    }
-    if (grpName) {                                                            /* -K: every refusal is a usage error */
-        const char *why = NULL;
-        if (bp || memb || restricted || cooc || permArg || distArg || gbp || wsName || jac || mapArg || nearArg || histArg || flankL || flankEdges ||
-            full || other)
-            why = "-K together with -b, -w, -X, -C, -P, -D, -G, -W, -J, -V, -N, -H, -L, -E, -f, -m, -s or -r";
-        else if (!uniq && !uniName) why = "-K without -u or -U";
-        else if (mode != 1 && !listName) why = "-K without -q or -Q";
-        if (why) return refused_usage(why);
-        const int rc = groups_read(grpName);
-        if (rc) return rc;
-    }
-    if (wsName) {                                                             /* -W: every refusal is a usage error */
-        if (!permArg) return refused_usage("-W without -P");
-        if (pmodeArg) return refused_usage("-W together with -M (the workspace is the placement)");
-    }
-    if (gbp && !resample) {                                                   /* -G: every refusal is a usage error */
-        const char *why = NULL;
-        if (!permArg) why = "-G without -P";
-        else if (distArg || jac || minov || nearArg || histArg || flankL || flankEdges || mapArg || listName || uniq || bp || memb || uniName ||
-                 ranks || restricted || cooc || full || other)
-            why = "-G together with -D, -J, -O, -A, -B, -N, -H, -L, -E, -V, -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r";
-        else if (!genomeName) why = "-G -P without -g";
-        else if (mode != 1) why = "-G -P without -q";
-        else if (!parse_perm_count(permArg, &np)) why = "-G with a number of permutations outside 1 to 1048576";
-        else if (parse_perm_mode(pmodeArg) < 0) why = "-G with a -M that is neither circular nor shuffle";
-        if (why) return refused_usage(why);
-    }
-    if (jac) {                                                                /* -J: every refusal is a usage error */
-        const char *why = NULL;
-        if (uniq || bp || memb || uniName || ranks || restricted || cooc || permArg || distArg || nearArg || histArg || flankL || flankEdges ||
-            mapArg || full || other || minov)
-            why = "-J together with -u, -b, -w, -U, -R, -X, -C, -P, -D, -N, -H, -L, -E, -V, -f, -m, -s, -r, -O, -A or -B";
-        else if (mode != 1 && !listName) why = "-J without -q or -Q";
-        if (why) return refused_usage(why);
-    }
-    int mapOp = -1;                                                           /* -V: every refusal is a usage error */
-    if (mapArg) {
-        for (int k = 0; k < 5; k++) if (strcmp(mapArg, MAP_OPS[k]) == 0) mapOp = k;
-        const char *why = NULL;
-        if (uniq || bp || memb || uniName || ranks || restricted || cooc || permArg || distArg || nearArg || full || other || minov)
-            why = "-V together with -u, -b, -w, -U, -R, -X, -C, -P, -D, -N, -f, -m, -s, -r, -O, -A or -B";
-        else if (mode != 1 && !listName) why = "-V without -q or -Q";
-        if (why) return refused_usage(why);
-        if (mapOp < 0) {
-            printf("Not supported: -V %s (count, sum, min, max or mean)\n", mapArg);
-            return EX_USAGE;
-        }
-        if (mapOp != 0 && IGD->gType == 0) {
-            printf("Not supported: -V %s on a database without values (gType 0); -V count works there\n", mapArg);
-            return EX_USAGE;
-        }
-    }
-    int32_t flankBins = 0;                                                    /* -L, -E: every refusal is a usage error */
-    if (flankL || flankEdges) {
-        char *end = NULL;
-        const long long nb = binsArg ? strtoll(binsArg, &end, 10) : 0;
-        const char *why = NULL;
-        if (!flankL) why = "-E without -L";
-        else if (!nearArg) why = "-L without -N";
-        else if (histArg || permArg || distArg || minov) why = "-L together with -H, -P, -D, -O, -A or -B";
-        else if (!binsArg) why = "-L without a number of bins";
-        if (why) return refused_usage(why);
-        if (binsArg[0] < '0' || binsArg[0] > '9' || *end || !igd_hip_flank_bins_valid(nb)) {
-            printf("Not supported: -L %s (1 to %d bins)\n", binsArg, (int)IGD_HIP_FLANK_MAX_BINS);
-            return EX_USAGE;
-        }
-        flankBins = (int32_t)nb;
-    }
-    int32_t histEdges[IGD_HIP_NEAREST_MAX_EDGES];                             /* -H: every refusal is a usage error */
-    int histNe = 0;
-    if (histArg) {
-        const char *why = NULL;
-        if (!nearArg) why = "-H without -N";
-        else if (permArg || distArg) why = "-H together with -P or -D";
-        if (why) return refused_usage(why);
-        if ((histNe = parse_edges(histArg, histEdges)) < 1) {
-            printf("Not supported: -H %s (1 to %d ascending integer edges, each within int32, separated by commas)\n", histArg,
-                   (int)IGD_HIP_NEAREST_MAX_EDGES);
-            return EX_USAGE;
-        }
-    }
-    if (distArg && !resample) {                                               /* -D: every refusal is a usage error */
-        const char *why = NULL;
-        if (!permArg) why = "-D without -P";
-        else if (nearArg || minov || listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)
-            why = "-D together with -N, -O, -A, -B, -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r";
-        else if (!genomeName) why = "-D -P without -g";
-        else if (mode != 1) why = "-D -P without -q";
-        else if (!parse_perm_count(permArg, &np)) why = "-D with a number of permutations outside 1 to 1048576";
-        else if (parse_perm_mode(pmodeArg) < 0) why = "-D with a -M that is neither circular nor shuffle";
-        if (why) return refused_usage(why);
-        if (!parse_dist_window(distArg, stdout, &distW)) return EX_USAGE;
-    }
-    int32_t nearW = 0;                                                        /* -N: the older wording, and exit code 0 */
-    if (nearArg) {
-        char *end = NULL;
-        const long long w = strtoll(nearArg, &end, 10);
-        if (uniq || bp || memb || uniName || ranks || restricted || cooc || permArg || full || other || minov) {
-            printf("Not supported: -N together with -u, -b, -w, -U, -R, -X, -C, -P, -f, -m, -s, -r, -O, -A or -B\n");
-            return EX_OK;
-        }
-        if (mode != 1 && !listName) {
-            printf("Not supported: -N without -q or -Q\n");
-            return EX_OK;
-        }
-        if (end == nearArg || *end || w < 0 || w > (long long)IGD_HIP_NEAREST_MAX_WINDOW) {
-            printf("Not supported: -N %s (a window of 0 to %lld base pairs)\n", nearArg, (long long)IGD_HIP_NEAREST_MAX_WINDOW);
-            return EX_OK;
-        }
-        nearW = (int32_t)w;
-    }
-    if (minov && (bp || memb || restricted || cooc || full || other || (mode != 1 && !listName))) {
-        printf("Not supported: -O, -A or -B together with -b, -w, -X, -C, -f, -m, -s or -r, or without -q or -Q\n");
-        return EX_USAGE;
-    }
-    if (minov && igd_hip_min_overlap_active(&g_mo_val)) g_mo = &g_mo_val;      /* (all three zero: no threshold) */
-    fP = fopen(igdName, "rb");                                                /* :974 */
-    /* the query files of the per-set commands: -q's when it was given, else the -Q list's; opened by the branch that runs one */
-    char *const oneFile = mode == 1 ? qfName : NULL;
-    const int perSet = mode == 1 || (mode < 0 && listName);                   /* -u, -b and -w: -Q counts only without -m, -s and -r */
-    cli_paths P;
-    memset(&P, 0, sizeof P);
-    if (shiftArg) {
-        permute_file(qfName, genomeName, wsName, NULL, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0,
-                     wsName ? IGD_HIP_PERM_WORKSPACE : parse_perm_mode(pmodeArg), v, -1, 0, shiftOff, nShift);
-        free(shiftOff);
-    } else if (resample) {
-        permute_file(qfName, NULL, NULL, uniName, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, IGD_HIP_PERM_RESAMPLE, v, distW, gbp,
-                     NULL, 0);
-    } else if (!permArg && (genomeName || seedArg || pmodeArg)) {
-        printf("Not supported: -g, -S or -M without -P\n");
-        return EX_OK;
-    } else if (jac) {
-        if (paths_open(&P, oneFile, listName)) jaccard_files(&P, v);
-    } else if (mapArg) {
-        if (paths_open(&P, oneFile, listName)) map_files(&P, v, mapOp);
-    } else if (nearArg) {
-        const int ok = paths_open(&P, oneFile, listName);
-        if (ok && flankL) flank_reldist_files(&P, v, nearW, flankEdges ? IGD_HIP_FLANK_EDGES : IGD_HIP_FLANK_MIDPOINTS, flankBins);
-        else if (ok && histArg) nearest_hist_files(&P, v, nearW, histEdges, histNe);
-        else if (ok) nearest_files(&P, v, nearW);
-    } else if (permArg && (listName || uniq || bp || memb || uniName || ranks || restricted || cooc || full || other)) {
-        printf("Not supported: -P together with -Q, -u, -b, -w, -U, -R, -X, -C, -f, -m, -s or -r\n");
-        return EX_OK;
-    } else if (permArg && !genomeName) {
-        printf("Not supported: -P without -g\n");
-        return EX_OK;
-    } else if (permArg && mode != 1) {
-        printf("Not supported: -P without -q\n");
-        return EX_OK;
-    } else if (permArg) {
-        const int pmode = wsName ? IGD_HIP_PERM_WORKSPACE : parse_perm_mode(pmodeArg);
-        if (!parse_perm_count(permArg, &np)) {
-            printf("Not supported: -P %s (1 to %lld permutations)\n", permArg, (long long)IGD_HIP_PERM_MAX);
-            return EX_OK;
-        }
-        if (pmode < 0) {
-            printf("Not supported: -M %s (circular or shuffle)\n", pmodeArg);
-            return EX_OK;
-        }
-        permute_file(qfName, genomeName, wsName, NULL, (int64_t)np, seedArg ? (uint64_t)strtoull(seedArg, NULL, 10) : 0, pmode, v, distW, gbp, NULL, 0);
-    } else if (cooc && (listName || uniq || bp || memb || uniName || ranks || restricted || full || other)) {
-        printf("Not supported: -C together with -Q, -u, -b, -w, -U, -R, -X, -f, -m, -s or -r\n");
-        return EX_OK;
-    } else if (cooc && mode != 1) {
-        printf("Not supported: -C without -q\n");
-        return EX_OK;
-    } else if (cooc) {
-        cooccur_file(qfName, v);
-    } else if (ranks && !uniName) {
-        printf("Not supported: -R without -U\n");
-        return EX_OK;
-    } else if (restricted && !uniName) {
-        printf("Not supported: -X without -U\n");
-        return EX_OK;
-    } else if (uniName && (bp || memb || full || other)) {
-        printf("Not supported: -U together with -b, -w, -f, -m, -s or -r\n");
-        return EX_OK;
-    } else if (uniName && (mode == 1 || listName)) {
-        if (paths_open(&P, oneFile, listName)) enrich_files(&P, uniName, v, ranks, restricted);
-    } else if (full) {                                                        /* :975-995 */
-        if (mode == 1) {
-            int64_t total = IGD->gType == 0 ? getOverlaps_f0(qfName) : getOverlaps_f1(qfName);
-            if (!g_fail_rc) printf("Total overlaps: %lld\n", (long long)total);
-        } else if (mode == 2) {
-            int64_t total = IGD->gType == 0 ? get_overlaps_f0(chrm, qs, qe) : get_overlaps_f1(chrm, qs, qe);
-            if (!g_fail_rc) printf("Total overlaps: %lld\n", (long long)total);
-        } else {
-            printf("Not supported -f option\n");
-            return EX_OK;
-        }
-    } else if (perSet && memb && (uniq || bp)) {
-        printf("Not supported: -w together with -u or -b\n");
-        return EX_OK;
-    } else if (perSet && memb) {
-        if (paths_open(&P, oneFile, listName)) membership_files(&P, v);
-    } else if (perSet && uniq && bp) {
-        printf("Not supported: -b together with -u\n");
-        return EX_OK;
-    } else if (perSet && (uniq || bp)) {
-        if (paths_open(&P, oneFile, listName)) support_files(&P, v, bp);
-    } else if (mode == 1) {                                                  /* :1023-1040 */
-        count_file(qfName, v, hits);
-        if (!g_fail_rc) print_hits_table(hits);
-    } else if (mode == 2) {                                                   /* :1041-1053 */
-        if (IGD->gType == 0) get_overlaps0(chrm, qs, qe, hits);
-        else if (v > 0) get_overlaps_v(chrm, qs, qe, v, hits);
-        else get_overlaps(chrm, qs, qe, hits);
-        if (!g_fail_rc) printf("index\t number of regions\t number of hits\t File_name\n");
-        for (int32_t i = 0; i < nfiles && !g_fail_rc; i++)
-            printf("%i\t%i\t%lld\t%s\n", i, IGD->finfo[i].nr, (long long)hits[i], IGD->finfo[i].fileName);
-    } else if (mode == 0) {                                                   /* :996-1022 */
-        if (IGD->gType != 1) {
-            printf("igd: -m needs a database created with 16-byte records (gType 1)\n");
-        } else {
-            uint32_t **hitmap = (uint32_t **)malloc(sizeof(uint32_t *) * (size_t)(nfiles + 1));
-            for (int32_t i = 0; i < nfiles; i++) hitmap[i] = (uint32_t *)calloc((size_t)nfiles + 1, sizeof(uint32_t));
-            if (v > 0) getMap_v(hitmap, v); else getMap(hitmap);
-            if (strlen(out) < 2) strcpy(out, "Hitsmap");
-            FILE *fo = g_fail_rc ? NULL : fopen(out, "w");
-            if (g_fail_rc) ;                                /* no matrix of zeros after an engine failure */
-            else if (!fo) printf("Can't open file %s\n", out);
-            else {
-                static char obuf[1 << 20];
-                setvbuf(fo, obuf, _IOFBF, sizeof obuf);
-                fprintf(fo, "%u\t%u\t%u\n", (unsigned)nfiles, (unsigned)nfiles, (unsigned)v);
-                for (int32_t i = 0; i < nfiles; i++) {
-                    for (int32_t j = 0; j < nfiles; j++) fprintf(fo, "%u\t", hitmap[i][j]);
-                    fprintf(fo, "\n");
-                }
-                fclose(fo);
-            }
-            for (int32_t i = 0; i < nfiles; i++) free(hitmap[i]);
-            free(hitmap);
-        }
-    } else if (mode == 3) {                                                   /* :1054-1061 */
-        if (IGD->gType != 1) printf("igd: -s needs a database created with 16-byte records (gType 1)\n");
-        else {
-            double *sm = (double *)malloc(sizeof(double) * (size_t)(nfiles + 1));
-            seqOverlaps(qfName, sm);
-            if (!g_fail_rc) printf("index\t number of regions\t similarity\t dataset name\n");
-            for (int32_t i = 0; i < nfiles && !g_fail_rc; i++)
-                printf("%i\t%i\t%10.6f\t%s\n", i, IGD->finfo[i].nr, sm[i], IGD->finfo[i].fileName);
-            free(sm);
-        }
-    } else if (listName) {                        /* only where the reference's own parse leaves nothing to do */
-        if (paths_open(&P, oneFile, listName)) search_sets(&P, v, hits);
-    } else {
-        free(hits);
-        return usage_search();
-    }
-    paths_close(&P);
-    groups_free();
-
-    /* release everything, in the shape get_igdinfo/get_fileinfo handed it out (:1066-1078) */
+    free(o.shiftOff);
+    free(hits);
     if (fP) { fclose(fP); fP = NULL; }
     free(IGD->nTile);
     for (int32_t c = 0; c < IGD->nCtg; c++) {
         free(IGD->nCnt[c]); free(IGD->tIdx[c]); free(IGD->cName[c]);
     }
-    for (int32_t i = 0; i < nfiles; i++) free(IGD->finfo[i].fileName);
+    for (int32_t i = 0; IGD->finfo && i < IGD->nFiles; i++) free(IGD->finfo[i].fileName);
     free(IGD->nCnt); free(IGD->tIdx); free(IGD->cName); free(IGD->finfo);
     free(IGD);
     IGD = NULL;
-    free(hits);
     if (g_core) { igdc_close(g_core); g_core = NULL; g_core_of = NULL; hc = NULL; }
     free(g_core_path); g_core_path = NULL;
-    /* the reference's exit code is always 0; an engine failure (message already on stderr) is the one
-     * thing this tool reports through it, instead of printing a table of zeros */
-    return g_fail_rc ? EX_UNAVAILABLE : g_usage_rc ? EX_USAGE : EX_OK;
+    g_mo = NULL; g_ws = NULL; g_pool = NULL;
+    g_usage_rc = 0;
+    return rc;
 }
 
 /* ---- create_igd*, src/igd_create.h:10-14 --------------------------------------------------- */
