@@ -10,10 +10,11 @@ __all__ = ["Database", "NativeMissing", "build", "fisher_host", "rank_host", "re
            "flanks_host", "flank_reldist_host", "reldist_summary", "FlankReldist", "FLANK_EDGES", "FLANK_MIDPOINTS", "FLANK_MAX_BINS",
            "merge_host", "dataset_bp_host", "jaccard_host", "jaccard_summary", "JaccardSets", "MERGE_MAX_GAP",
            "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace",
-           "DatasetGroups", "build_groups", "read_groups_file", "GROUP_MAX", "ShiftSupport", "shift_offsets", "local_zscore"]
+           "DatasetGroups", "build_groups", "read_groups_file", "GROUP_MAX", "ShiftSupport", "shift_offsets", "local_zscore",
+           "perm_map_summary", "PermutationMap"]
 # (igd_amd.group_support_host resolves below like the other host routes; it is not in __all__, whose `_host` names with regions are
 # the table of tests/test_database_args_host.py; so do igd_amd.shift_support_host, igd_amd.shift_regions_host
-# and igd_amd.resample_regions_host)
+# igd_amd.resample_regions_host and igd_amd.permute_map_host)
 # `from igd_amd import igd_py as iGD; iGD.igd_py()` mirrors the reference's `import igd_py as iGD`
 
 
@@ -42,7 +43,7 @@ def __getattr__(name):
                 "permute_bp_host", "perm_bp_summary", "PermutationBp", "Workspace", "build_workspace",
            "DatasetGroups", "build_groups", "read_groups_file", "group_support_host", "GROUP_MAX",
                 "ShiftSupport", "shift_offsets", "local_zscore", "shift_support_host", "shift_regions_host",
-                "resample_regions_host"):
+                "resample_regions_host", "permute_map_host", "perm_map_summary", "PermutationMap"):
         from . import database
         return getattr(database, name)
     raise AttributeError(name)

@@ -296,6 +296,17 @@ def hip():
                                       C.c_void_p]
         L.igd_hip_map_grid.argtypes = [C.c_int64]
         L.igd_hip_map_grid.restype = C.c_int32
+        # the fused route of the values and their permutation null: as igd_hip_map_sets / db, ichr, qs, qe, nq, ctg_len, mode, seed,
+        # nperm, op, v, n_hit, pairs, agg_sum [, ws] / the resampling form
+        L.igd_hip_map_sets_fused.argtypes = L.igd_hip_map_sets.argtypes
+        L.igd_hip_permute_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_uint64,
+                                          C.c_int64, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.igd_hip_permute_map_ws.argtypes = L.igd_hip_permute_map.argtypes + [C.c_void_p]
+        L.igd_hip_permute_map_rs.argtypes = rs + [C.c_int, C.c_int32] + [C.c_void_p] * 3
+        L.igd_hip_map_fused_max_files.argtypes = [C.c_int]
+        L.igd_hip_map_fused_max_files.restype = C.c_int32
+        L.igd_hip_map_fused_grid.argtypes = [C.c_int64]
+        L.igd_hip_map_fused_grid.restype = C.c_int32
         # the y of the reductions' grid: ncols (nFiles + 1 for the nearest family, nFiles for map), nslices
         L.igd_hip_reduce_grid_y.argtypes = [C.c_int64, C.c_int64]
         L.igd_hip_reduce_grid_y.restype = C.c_int32
@@ -505,6 +516,13 @@ def _bind_core(L):
     L.igdc_permute_bp_host_rs.argtypes = rs + [C.c_int32, C.c_int] + [C.c_void_p] * 4
     L.igdc_resample_regions_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
+    # permutation null of the values on the host: db, map, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, op, v, n_hit, pairs, agg_sum
+    # [, ws] / the resampling form / n_hit, pairs, agg_sum, nperm, ncols, over_pairs, the twelve outputs
+    L.igdc_permute_map_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                        C.c_uint64, C.c_int64, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.igdc_permute_map_host_ws.argtypes = L.igdc_permute_map_host.argtypes + [C.c_void_p]
+    L.igdc_permute_map_host_rs.argtypes = rs + [C.c_int, C.c_int32] + [C.c_void_p] * 3
+    L.igdc_perm_map_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 12
     # db, path, len (int32[nCtg]), bad_line
     L.igdc_read_genome.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
     return L

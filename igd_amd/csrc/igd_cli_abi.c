@@ -1553,7 +1553,7 @@ static void cooccur_file(char *path, int32_t v)
  * behind those the facts that the parse derives from the order and from the values (F_x; F(x)), so that a row of RULES can ask
  * for either in one mask.  A valued option's bit says that a value was met, except -L and -r, which count bare too. */
 enum { O_f = 1, O_m, O_s, O_u, O_b, O_w, O_X, O_C, O_G, O_E, O_R, O_J, O_q, O_r, O_v, O_Q, O_U, O_P, O_g, O_S, O_M, O_O, O_A, O_B, O_N,
-       O_H, O_L, O_V, O_D, O_W, O_K, O_Z, O_o, O_COUNT,
+       O_H, O_L, O_V, O_D, O_W, O_K, O_Z, O_o, O_I, O_COUNT,
        F_q = O_COUNT, F_r, F_m, F_s,      /* the mode: the last of -q, -r, -m and -s (-s does not count after -r) */
        F_PERSET,                          /* -u, -b and -w have their sets: mode -q, or -Q with no mode at all */
        F_MINOV,                           /* -O, -A or -B */
@@ -1561,6 +1561,7 @@ enum { O_f = 1, O_m, O_s, O_u, O_b, O_w, O_X, O_C, O_G, O_E, O_R, O_J, O_q, O_r,
        F_BAD_P, F_BAD_M, F_BAD_Z, F_BAD_D, F_BAD_N, F_BAD_V, F_BAD_L, F_BAD_H,       /* the value does not parse (-M: neither circular nor shuffle) */
        F_L_BARE,                          /* -L without a value */
        F_V_BLIND,                         /* -V with an op other than count on a database without values */
+       F_BAD_I, F_I_BLIND,                /* the same two facts of -I */
        F_COUNT };
 _Static_assert(F_COUNT <= 64, "the options and facts of igd search share one 64-bit mask");
 #define B(x) (1ULL << O_##x)
@@ -1577,7 +1578,7 @@ typedef struct {
     int pmode;                            /* IGD_HIP_PERM_: -W's, -M resample's, or -M's */
     int32_t distW, nearW, flankBins;      /* -D (-1: none), -N, -L */
     int32_t histEdges[IGD_HIP_NEAREST_MAX_EDGES];
-    int histNe, mapOp;                    /* -H; -V's index in MAP_OPS */
+    int histNe, mapOp, inOp;              /* -H; -V's and -I's index in MAP_OPS (-1: none) */
     int32_t *shiftOff;                    /* -Z: malloc'd offsets */
     int nShift;
 } cli_opts;
@@ -1609,6 +1610,8 @@ static const igd_hip_workspace *g_ws = NULL;
 static const igdc_queries *g_pool = NULL;
 /* `-G` switches it to base pairs (permute_bp_table below); it takes no sum of squares on the device, so the guard on it does not apply. */
 static void permute_bp_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int rule);
+/* `-I op` switches it to the values of the overlapping records (permute_map_table below); opName: the index in MAP_OPS. */
+static void permute_map_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int opName);
 /* `-Z W,STEP` prints the shift profile of the support instead (shift_table below): nshift > 0 offsets; nperm may be 0 then. */
 static void shift_table(const igdc_queries *q, const int32_t *len, const int32_t *offsets, int nshift, int64_t nperm, uint64_t seed, int pmode,
                         int32_t ev, int rule);
@@ -1710,12 +1713,13 @@ static void permute_file(const cli_opts *o)
         g_pool = &uq;
     }
     if (q.n > igd_hip_max_batch() ||
-        (window < 0 && !gbp && (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63)) {
+        (window < 0 && !gbp && o->inOp < 0 && (unsigned __int128)nperm * (unsigned __int128)q.n * (unsigned __int128)q.n >= (unsigned __int128)1 << 63)) {
         printf("Not supported: -P %lld with %lld regions\n", (long long)nperm, (long long)q.n);
         goto done;
     }
     if (o->nShift > 0) shift_table(&q, len, o->shiftOff, o->nShift, nperm, seed, pmode, ev, rule);
     else if (gbp) permute_bp_table(&q, len, nperm, seed, pmode, ev, rule);
+    else if (o->inOp >= 0) permute_map_table(&q, len, nperm, seed, pmode, ev, o->inOp);
     else if (window >= 0) permute_nearest_table(&q, len, nperm, seed, pmode, ev, window);
     else {
         int64_t *st7 = (int64_t *)calloc(7 * (size_t)nC, sizeof(int64_t));
@@ -2083,6 +2087,53 @@ static void permute_nearest_table(const igdc_queries *q, const int32_t *len, int
     free(st3); free(fl);
 }
 
+/* ------------------------------- `igd search -q F -P N -g genome -I <op>` -------------- */
+/* Permutation null of the values of the overlapping records (include/igd_hip.h: igd_hip_permute_map; igd_core.h:
+ * igdc_perm_map_summary has the columns): "are the scores of dataset f's records under my regions higher or lower than chance"
+ * (regioneR's meanInRegions).  -I is to -V what -D is to -N.  The statistic is -V's mean: of the per-region count, sum, minimum
+ * or maximum over the regions with a hit, or, for `mean`, of the values over the pairs (the rows of op SUM).  The header
+ *     index observed_n_hit observed_mean_<op> n_def mean sd z n_ge n_le mlog10p_ge mlog10p_le nhit_mean nhit_sd nhit_z File
+ * (tab-separated) and one line per dataset; floats as %.6f, NaN as NA.  -v keeps the records with value >= v, as everywhere;
+ * there is no tile rule.  Routing as -P: regions x (N + 1) against igdc_host_limit(). */
+static void permute_map_table(const igdc_queries *q, const int32_t *len, int64_t nperm, uint64_t seed, int pmode, int32_t ev, int opName)
+{
+    const int op = MAP_OP_OF[opName], perPair = opName == 4;
+    const int32_t nfiles = IGD->nFiles;
+    const size_t nC = (size_t)nfiles, R = (size_t)nperm + 1;
+    int64_t *st3 = (int64_t *)calloc(3 * R * nC + 3 * nC + 1, sizeof(int64_t));
+    double *fl = (double *)calloc(9 * nC + 1, sizeof(double));
+    if (!st3 || !fl) { fprintf(stderr, "igd: out of memory\n"); free(st3); free(fl); return; }
+    int64_t *nh = st3, *np = nh + R * nC, *sa = np + R * nC, *ndef = sa + R * nC, *nge = ndef + nC, *nle = nge + nC;
+    double *ob = fl, *mu = ob + nC, *sd = mu + nC, *z = sd + nC, *pu = z + nC, *pl = pu + nC, *hm = pl + nC, *hs = hm + nC, *hz = hs + nC;
+    cli_route Rt;
+    if (route_host(&Rt, q->n * (nperm + 1)))
+        route_host_end(&Rt, (g_pool ? igdc_permute_map_host_rs(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, g_pool->ichr, g_pool->qs, g_pool->qe, g_pool->n,
+                                                               seed, nperm, op, ev, nh, np, sa)
+                                    : igdc_permute_map_host_ws(g_core, Rt.hm, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, op, ev, nh, np, sa, g_ws)) == 0,
+                       "permutation null of the values on the host (small files)");
+    if (route_engine(&Rt, 1))
+        route_engine_end(&Rt, "permutation null of the values",
+                         g_pool ? igd_hip_permute_map_rs(Rt.dev, q->ichr, q->qs, q->qe, q->n, g_pool->ichr, g_pool->qs, g_pool->qe, g_pool->n, seed, nperm,
+                                                         op, ev, nh, np, sa)
+                                : igd_hip_permute_map_ws(Rt.dev, q->ichr, q->qs, q->qe, q->n, len, pmode, seed, nperm, op, ev, nh, np, sa, g_ws),
+                         "permutation null of the values (H2D + permute and fused map kernels + D2H)");
+    if (!g_fail_rc && igdc_perm_map_summary(nh, np, sa, nperm, (int64_t)nC, perPair, ob, ndef, mu, sd, z, nge, nle, pu, pl, hm, hs, hz) == 0) {
+        printf("index\tobserved_n_hit\tobserved_mean_%s\tn_def\tmean\tsd\tz\tn_ge\tn_le\tmlog10p_ge\tmlog10p_le\tnhit_mean\tnhit_sd\tnhit_z\tFile\n",
+               MAP_OPS[opName]);
+        for (int32_t i = 0; i < nfiles; i++) {
+            printf("%d\t%lld\t", (int)i, (long long)nh[i]);
+            print_na("%.6f", ob[i], "\t");
+            printf("%lld\t", (long long)ndef[i]);
+            print_na("%.6f", mu[i], "\t"); print_na("%.6f", sd[i], "\t"); print_na("%.6f", z[i], "\t");
+            printf("%lld\t%lld\t", (long long)nge[i], (long long)nle[i]);
+            print_na("%.6f", pu[i], "\t"); print_na("%.6f", pl[i], "\t");
+            print_na("%.6f", hm[i], "\t"); print_na("%.6f", hs[i], "\t"); print_na("%.6f", hz[i], "\t");
+            printf("%s\n", IGD->finfo[i].fileName);
+        }
+    }
+    free(st3); free(fl);
+}
+
 /* ------------------------------- `igd search -q F -P N -g genome -G` ------------------- */
 /* Permutation null of the base-pair overlap (include/igd_hip.h: igd_hip_permute_bp; igd_core.h: igdc_perm_bp_summary has the
  * columns): "does my region set share more base pairs with dataset f than chance".  -G is to -J what -D is to -N.  The header
@@ -2276,6 +2327,7 @@ static const struct { const char *name; int id, words, flags, mode; const char *
     OPT(L, 1, STEP | BARE),
     OPT(V, 1, STEP, 0, NS "-V without an op (count, sum, min, max or mean)", NEW),
     OPT(D, 1, STEP, 0, NS "-D without a window", NEW),
+    OPT(I, 1, STEP, 0, NS "-I without an op (count, sum, min, max or mean)", NEW),
     OPT(K, 1, STEP, 0, NS "-K without a groups file", NEW),
     OPT(Z, 1, STEP, 0, NS "-Z without W,STEP", ERR),
     OPT(O, 1, STEP | EAGER), OPT(A, 1, STEP | EAGER), OPT(B, 1, STEP | EAGER),
@@ -2323,6 +2375,10 @@ static int search_parse(cli_opts *o, int argc, char **argv)                  /* 
     for (int k = 0; (a = o->val[O_V]) && k < 5; k++) if (strcmp(a, MAP_OPS[k]) == 0) o->mapOp = k;
     if (a && o->mapOp < 0) o->given |= F(BAD_V);
     if (a && o->mapOp > 0 && IGD->gType == 0) o->given |= F(V_BLIND);
+    o->inOp = -1;
+    for (int k = 0; (a = o->val[O_I]) && k < 5; k++) if (strcmp(a, MAP_OPS[k]) == 0) o->inOp = k;
+    if (a && o->inOp < 0) o->given |= F(BAD_I);
+    if (a && o->inOp > 0 && IGD->gType == 0) o->given |= F(I_BLIND);
     if ((a = o->val[O_Z]) && (o->nShift = parse_shifts(a, &o->shiftOff)) < 1) o->given |= F(BAD_Z);
     return -1;
 }
@@ -2337,6 +2393,14 @@ static int search_parse(cli_opts *o, int argc, char **argv)                  /* 
 #define QSET (F(q) | B(Q))                /* -q or -Q names the query sets */
 #define RULE(a, y, n, ...) {.all = (a), .any = (y), .none = (n), .how = __VA_ARGS__}
 static const struct { uint64_t all, any, none; int how; const char *text; int arg; const char *tail; } RULES[] = {
+    /* -I: the null of the values.  A block of its own ahead of every older row, so that no older sentence and no older mask
+     * changes; behind it a command line with -I falls through to the rows of -M resample, -W and -P as they stand */
+    RULE(B(I), 0, B(P), NEW, NS "-I without -P"),
+    RULE(B(I), B(D) | B(G) | B(V) | B(N) | B(H) | B(L) | B(E) | B(J) | B(Z) | B(K) | B(Q) | B(u) | B(b) | B(w) | B(R) | B(X) | B(C) | B(f) | OTHER | F(MINOV),
+         0, NEW, NS "-I together with -D, -G, -V, -N, -H, -L, -E, -J, -Z, -K, -Q, -u, -b, -w, -R, -X, -C, -f, -m, -s, -r, -O, -A or -B"),
+    RULE(B(I) | B(U), 0, F(RESAMPLE), NEW, NS "-I with -U but without -M resample"),
+    RULE(B(I), F(BAD_I), 0, NEW, NS "-I ", O_I, " (count, sum, min, max or mean)"),
+    RULE(B(I), F(I_BLIND), 0, NEW, NS "-I ", O_I, " on a database without values (gType 0); -I count works there"),
     /* -Z: the shift profile */
     RULE(B(Z), B(Q), 0, ERR, NS "-Z together with -Q"),
     RULE(B(Z), B(u) | B(U) | B(b) | B(J) | B(w) | B(C) | B(N) | B(V) | B(K) | OTHER | B(f) | B(R) | B(X) | B(H) | B(L) | B(E), 0, ERR,

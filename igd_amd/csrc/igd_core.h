@@ -378,6 +378,35 @@ int igdc_permute_nearest_host_rs(const igdc_db *db, const igdc_map *m, const int
 int igdc_permute_bp_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                             const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
                             int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped);
+/* Permutation null of the overlapping records' values on the host (what igd_hip_permute_map, _ws and _rs compute;
+ * include/igd_hip.h): each output is int64[(nperm + 1) * nFiles] (may be NULL), row 0 the set as given, row p + 1 permutation p
+ * of igdc_permute_regions_host's generator (_rs: draw p of the pool) measured as igdc_map_sets_host measures a set; threads run
+ * over the rows.  0; -1 for a refused argument (an unknown op, a value op on a gType 0 database, then igdc_permute_nearest_host's
+ * but the window) or when a tile could not be read -- nothing is written then. */
+int igdc_permute_map_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs,
+                          int64_t *agg_sum);
+int igdc_permute_map_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                             const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit,
+                             int64_t *pairs, int64_t *agg_sum, const igd_hip_workspace *ws);
+int igdc_permute_map_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                             const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                             int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum);
+/* The summary of such a null distribution, per column f of ncols; n_hit, pairs and agg_sum are int64[(nperm + 1) * ncols].  The
+ * statistic of row r is m_r = a_r / d_r with a = agg_sum and d = n_hit (over_pairs = 0: mean_region) or d = pairs (over_pairs
+ * != 0: mean_pair, regioneR's meanInRegions over pairs); it is undefined where d_r = 0.  With P = nperm and row 0 the observed one:
+ *     statistic   observed = m_0 (NaN when d_0 = 0); n_def = #{p : d_p > 0}; mean and sd over m_p of those permutations, in
+ *                 doubles, two passes in permutation order (mean NaN when n_def = 0; sd divides by n_def - 1 and is NaN when
+ *                 n_def < 2: igdc_perm_nearest_summary's convention); z = (observed - mean) / sd, NaN when d_0 = 0 or the sd is 0
+ *                 or NaN; n_ge = #{p : d_p > 0 and m_p >= m_0}, n_le the same with <=, compared exactly as a_p d_0 against
+ *                 a_0 d_p in 128 bits (a tie counts in both), both 0 when d_0 = 0; nlog10_p_upper = -log10((n_ge + 1) /
+ *                 (n_def + 1)), nlog10_p_lower the same of n_le: NaN when d_0 = 0, 0 when n_def = 0
+ *     counts      nhit_mean, nhit_sd, nhit_z: igdc_perm_summary's formulas over the permuted n_hit
+ * n_def, n_ge and n_le are int64[ncols], the others double[ncols]; every output may be NULL.  Needs no database.  0, or -1 for a
+ * missing input or nperm < 1. */
+int igdc_perm_map_summary(const int64_t *n_hit, const int64_t *pairs, const int64_t *agg_sum, int64_t nperm, int64_t ncols, int over_pairs,
+                          double *observed, int64_t *n_def, double *mean, double *sd, double *z, int64_t *n_ge, int64_t *n_le,
+                          double *nlog10_p_upper, double *nlog10_p_lower, double *nhit_mean, double *nhit_sd, double *nhit_z);
 /* The support of a region set under rigid shifts on the host (what igd_hip_shift_regions and igd_hip_shift_support compute;
  * include/igd_hip.h has THE SHIFT, the outputs and the refusals).  igdc_shift_regions_host is kernel igd_shift_regions: nq regions
  * under each of nshift offsets into out_qs, out_qe (int32[nshift * nq], shift-major); nctg is the caller's.

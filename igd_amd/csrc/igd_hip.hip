@@ -418,6 +418,7 @@ struct igd_hip_db {
 #include "engine/flank_dev.hpp"       // igd_flank_rows, igd_flank_reldist: the same walk with two minima per region and dataset -- the nearest record on each side, the relative-distance histogram
 #include "engine/nearest_fused_dev.hpp" // igd_nearest_slices: the same walk and table, folded into per-slice LDS accumulators -- the set statistics without the rows
 #include "engine/map_dev.hpp"         // igd_map_rows, igd_map_reduce: the same walk with the value words, count and sum / min / max rows per region -- values of the overlapping records
+#include "engine/map_fused_dev.hpp"   // igd_map_slices: the same walk and tables, folded into per-slice LDS accumulators -- the set statistics of the values without the rows
 #include "engine/merge_dev.hpp"       // igd_merge_*: region sets merged as `bedtools merge` -- sort keys, segmented maximum scan of the ends, run heads and compaction
 #include "engine/permute_bp_dev.hpp"  // igd_merge_row_offsets, igd_merge_slices, igd_merge_row_bp: the merged runs handed to igd_sets_coverage on the device -- permutation null of base-pair overlap
 #include "engine/host_open.hpp"       // handles: allocation, close, pinned buffers, re-tiled copy, igd_hip_open
@@ -442,6 +443,7 @@ struct igd_hip_db {
 #include "engine/host_flank.hpp"      // igd_hip_flank / _dev / _reldist: the same two drivers with two rows per region
 #include "engine/host_permute_nearest.hpp" // igd_hip_nearest_sets_fused / igd_hip_permute_nearest: run_set_groups with one fused launch per chunk, the null distribution of the distance statistics
 #include "engine/host_map.hpp"        // igd_hip_map / _dev / _sets: the same two drivers, the set statistics stay resident
+#include "engine/host_permute_map.hpp" // igd_hip_map_sets_fused / igd_hip_permute_map: run_set_groups with one fused launch per chunk, the null distribution of the value statistics
 #include "engine/host_merge.hpp"      // igd_hip_merge_sets / _dev, igd_hip_dataset_bp, igd_hip_jaccard_sets: device merge, merged base pairs per dataset, the intersection table
 #include "engine/host_permute_bp.hpp" // igd_hip_permute_bp: chunks of permutations, merged and covered without a host copy in between
 #include "engine/host_selftest.hpp"   // TEST-ONLY: igd_hip_test_exclusive_scan / igd_hip_test_radix_sort_pairs: igd_sortscan.hpp on host arrays, guard bytes behind every device array

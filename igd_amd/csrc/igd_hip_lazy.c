@@ -655,6 +655,55 @@ int igd_hip_permute_bp_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
               : IGD_HIP_ERR_DEVICE;
 }
 
+int igd_hip_map_sets_fused(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                           int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, const int64_t *, int32_t, int, int32_t, int64_t *,
+                        int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_map_sets_fused");
+    return fn ? fn(db, ichr, qs, qe, set_off, nsets, op, v, n_hit, pairs, agg_sum) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_map(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                        int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
+{
+    return igd_hip_permute_map_ws(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, op, v, n_hit, pairs, agg_sum, NULL);
+}
+
+int igd_hip_permute_map_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                           int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum,
+                           const igd_hip_workspace *ws)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, int, uint64_t, int64_t,
+                        int, int32_t, int64_t *, int64_t *, int64_t *, const igd_hip_workspace *);
+    RESOLVE(fn_t, "igd_hip_permute_map_ws");
+    return fn ? fn(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, op, v, n_hit, pairs, agg_sum, ws) : IGD_HIP_ERR_DEVICE;
+}
+
+int igd_hip_permute_map_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                           const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                           int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
+{
+    typedef int (*fn_t)(igd_hip_db *, const int32_t *, const int32_t *, const int32_t *, int64_t, const int32_t *, const int32_t *,
+                        const int32_t *, int64_t, uint64_t, int64_t, int, int32_t, int64_t *, int64_t *, int64_t *);
+    RESOLVE(fn_t, "igd_hip_permute_map_rs");
+    return fn ? fn(db, ichr, qs, qe, nq, pool_ichr, pool_qs, pool_qe, npool, seed, nperm, op, v, n_hit, pairs, agg_sum) : IGD_HIP_ERR_DEVICE;
+}
+
+int32_t igd_hip_map_fused_max_files(int op)
+{
+    typedef int32_t (*fn_t)(int);
+    RESOLVE(fn_t, "igd_hip_map_fused_max_files");
+    return fn ? fn(op) : 0;
+}
+
+int32_t igd_hip_map_fused_grid(int64_t nslices)
+{
+    typedef int32_t (*fn_t)(int64_t);
+    RESOLVE(fn_t, "igd_hip_map_fused_grid");
+    return fn ? fn(nslices) : 0;
+}
+
 int igd_hip_enumerate_stream(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int64_t *qoff,
                              igd_hip_enum_sink sink, void *ctx, int64_t *total)
 {

@@ -2045,6 +2045,163 @@ int igdc_perm_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, 
     return 0;
 }
 
+/* ---- permutation null of the overlapping records' values (what igd_hip_permute_map computes) ------------------------------
+ * Row 0 is the set as given, row p + 1 permutation p of the generator or draw p of the pool (perm_rows); a row is
+ * igdc_map_sets_host's row computer over its regions (one_region_map) summed into the three statistics as map_sets_fold sums a
+ * region.  Each thread has its own permuted arrays, count and agg row and tile buffer; the rows are disjoint.  Everything is
+ * computed into a buffer and copied out at the end: -1 (a refused argument, a tile that could not be read) writes nothing. */
+typedef struct {
+    perm_stripe s;
+    int op; int32_t v; int use_v;
+    int64_t *res;           /* three matrices of nrows x nFiles */
+    int32_t *count;         /* one count row */
+    int64_t *agg;           /* one agg row (NULL under COUNT) */
+    tilebuf tb;
+} pmap_job;
+
+static int pmap_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
+{
+    pmap_job *P = (pmap_job *)job;
+    const int64_t nF = P->s.db->nFiles;
+    map_sets_ctx c = {P->s.db, P->s.m, NULL, NULL, NULL, P->op, P->v, P->count, P->agg, P->res, P->res + P->s.nrows * nF,
+                      P->res + 2 * P->s.nrows * nF};
+    for (int64_t i = 0; i < P->s.nq && !P->tb.failed; i++) {
+        one_region_map(P->s.db, P->s.m, &P->tb, P->s.rowc[i], s[i], e[i], P->op, P->v, P->use_v, P->count, P->agg);
+        if (!P->tb.failed) map_sets_fold(&c, (int32_t)r, 0);
+    }
+    return P->tb.failed;
+}
+static void *pmap_run(void *arg)
+{
+    pmap_job *P = (pmap_job *)arg;
+    tb_open(&P->tb);
+    perm_rows(&P->s, pmap_row, P);
+    tb_close(&P->tb);
+    return NULL;
+}
+
+/* the body of igdc_permute_map_host_ws and, with a pool and no ctg_len, of igdc_permute_map_host_rs */
+static int permute_map_host_run(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                                const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit,
+                                int64_t *pairs, int64_t *agg_sum, const igd_hip_workspace *ws, const perm_pool *pool)
+{
+    if (!db || !map_op_ok(db, op) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, pool)) return -1;
+    const int64_t nF = db->nFiles, R = nperm + 1;
+    int T = host_threads(nq * R > 0 ? nq * R : 1);
+    if (T > R) T = (int)R;
+    int64_t *res = (int64_t *)calloc((size_t)(3 * R * nF) + 1, sizeof(int64_t));
+    /* per thread: the permuted set (2 nq words), a count row (nF words) and an agg row (nF 64-bit words, 8-byte aligned in `a`) */
+    int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (2 * (size_t)nq + (size_t)nF) + 1));
+    int64_t *a = (int64_t *)malloc(sizeof(int64_t) * ((size_t)T * (size_t)nF + 1));
+    int rc = res && w && a ? 0 : -1;
+    int32_t *pcb = pool_contigs(pool, T, nq, &rc);
+    pmap_job job[HOST_MAX_THREADS];
+    for (int k = 0; k < T && rc == 0; k++) {
+        int32_t *mine = w + (size_t)k * (2 * (size_t)nq + (size_t)nF);
+        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 0, R, mine, k, T);
+        job[k].s.pool = pool; job[k].s.pc = pcb ? pcb + (size_t)k * (size_t)nq : NULL;
+        job[k].op = op; job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
+        job[k].res = res; job[k].count = mine + 2 * nq;
+        job[k].agg = a + (size_t)k * (size_t)nF;    /* (under COUNT it receives the counts: agg_sum IS pairs) */
+    }
+    if (rc == 0 && nq > 0 && nF > 0) {
+        run_threads(pmap_run, job, sizeof job[0], T);
+        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
+    }
+    if (rc == 0) {
+        int64_t *const out[3] = {n_hit, pairs, agg_sum};
+        for (int s = 0; s < 3; s++) if (out[s]) memcpy(out[s], res + (size_t)s * (size_t)(R * nF), sizeof(int64_t) * (size_t)(R * nF));
+    }
+    free(res); free(w); free(a); free(pcb);
+    return rc;
+}
+
+int igdc_permute_map_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                             const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit,
+                             int64_t *pairs, int64_t *agg_sum, const igd_hip_workspace *ws)
+{
+    return permute_map_host_run(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, op, v, n_hit, pairs, agg_sum, ws, NULL);
+}
+
+int igdc_permute_map_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs,
+                          int64_t *agg_sum)
+{
+    return igdc_permute_map_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, op, v, n_hit, pairs, agg_sum, NULL);
+}
+
+int igdc_permute_map_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                             const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                             int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
+{
+    const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
+    return permute_map_host_run(db, m, ichr, qs, qe, nq, NULL, IGD_HIP_PERM_RESAMPLE, seed, nperm, op, v, n_hit, pairs, agg_sum, NULL, &pool);
+}
+
+/* the summary of a null distribution of value statistics; igd_core.h has the formulas */
+int igdc_perm_map_summary(const int64_t *n_hit, const int64_t *pairs, const int64_t *agg_sum, int64_t nperm, int64_t ncols, int over_pairs,
+                          double *observed, int64_t *n_def, double *mean, double *sd, double *z, int64_t *n_ge, int64_t *n_le,
+                          double *nlog10_p_upper, double *nlog10_p_lower, double *nhit_mean, double *nhit_sd, double *nhit_z)
+{
+    const double P = (double)nperm, nan = __builtin_nan("");
+    const int64_t *den = over_pairs ? pairs : n_hit;
+    if (!sqrt || !log10 || nperm < 1 || ncols < 0 || (ncols > 0 && (!n_hit || !agg_sum || !den))) return -1;
+    for (int64_t f = 0; f < ncols; f++) {
+        /* the counts: igdc_perm_summary's formulas over the permuted n_hit */
+        __int128 sum = 0, sumsq = 0;
+        for (int64_t p = 1; p <= nperm; p++) {
+            const int64_t x = n_hit[p * ncols + f];
+            sum += x;
+            sumsq += (__int128)x * (__int128)x;
+        }
+        const double mu = (double)sum / P;
+        double s = nan;
+        if (nperm > 1) s = sqrt((double)((__int128)nperm * sumsq - sum * sum) / (P * (P - 1.0)));
+        if (nhit_mean) nhit_mean[f] = mu;
+        if (nhit_sd) nhit_sd[f] = s;
+        if (nhit_z) nhit_z[f] = (s != s || s == 0.0) ? nan : ((double)n_hit[f] - mu) / s;
+        /* the statistic: m_p = a_p / d_p over the permutations with d_p > 0, two passes in permutation order; m_p against m_0 is
+         * a_p d_0 against a_0 d_p, exact in 128 bits (both denominators are positive) */
+        const int64_t a0 = agg_sum[f], d0 = den[f];
+        const double m0 = d0 > 0 ? (double)a0 / (double)d0 : nan;
+        int64_t ndef = 0, nge = 0, nle = 0;
+        double acc = 0.0;
+        for (int64_t p = 1; p <= nperm; p++) {
+            const int64_t ap = agg_sum[p * ncols + f], dp = den[p * ncols + f];
+            if (dp <= 0) continue;
+            ndef++;
+            acc += (double)ap / (double)dp;
+            if (d0 > 0) {
+                const __int128 l = (__int128)ap * (__int128)d0, r = (__int128)a0 * (__int128)dp;
+                nge += l >= r;
+                nle += l <= r;
+            }
+        }
+        const double dmu = ndef > 0 ? acc / (double)ndef : nan;
+        double ds = nan;
+        if (ndef > 1) {
+            double ss = 0.0;
+            for (int64_t p = 1; p <= nperm; p++) {
+                const int64_t dp = den[p * ncols + f];
+                if (dp <= 0) continue;
+                const double t = (double)agg_sum[p * ncols + f] / (double)dp - dmu;
+                ss += t * t;
+            }
+            ds = sqrt(ss / (double)(ndef - 1));
+        }
+        if (observed) observed[f] = m0;
+        if (n_def) n_def[f] = ndef;
+        if (mean) mean[f] = dmu;
+        if (sd) sd[f] = ds;
+        if (z) z[f] = (d0 <= 0 || ds != ds || ds == 0.0) ? nan : (m0 - dmu) / ds;
+        if (n_ge) n_ge[f] = nge;
+        if (n_le) n_le[f] = nle;
+        if (nlog10_p_upper) nlog10_p_upper[f] = d0 > 0 ? 0.0 - log10((double)(nge + 1) / (double)(ndef + 1)) : nan;
+        if (nlog10_p_lower) nlog10_p_lower[f] = d0 > 0 ? 0.0 - log10((double)(nle + 1) / (double)(ndef + 1)) : nan;
+    }
+    return 0;
+}
+
 /* The handle flavours' batches (Python search_n / search_1, R search_nr / getOverlaps): on the host while the batch is
  * small and no engine is resident, otherwise on the engine, which is attached at the first batch that needs it -- the
  * moment the reference would do its first fseek/fread (src/igd_search.c:469-476); open_iGD reads the header only, like

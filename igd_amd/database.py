@@ -124,6 +124,9 @@ NearestSets = collections.namedtuple("NearestSets", "n_within n_overlap sum_dist
 PermutationNearest = collections.namedtuple("PermutationNearest", "n_within n_overlap sum_dist window nperm")
 MapSets = collections.namedtuple("MapSets", "n_hit pairs agg_sum op")
 MAP_OPS = {"count": 0, "sum": 1, "min": 2, "max": 3}             # IGD_HIP_MAP_COUNT, _SUM, _MIN, _MAX
+PermutationMap = collections.namedtuple("PermutationMap", "n_hit pairs agg_sum op nperm")
+PermutationMapSummary = collections.namedtuple(
+    "PermutationMapSummary", "observed_n_hit observed n_def mean sd z n_ge n_le nlog10_p_upper nlog10_p_lower nhit_mean nhit_sd nhit_z")
 PermutationBp = collections.namedtuple("PermutationBp", "inter set_bp n_merged n_dropped file_bp nperm")
 PermutationBpSummary = collections.namedtuple(
     "PermutationBpSummary", "observed mean sd z fold n_ge n_le nlog10_p_upper nlog10_p_lower jaccard jaccard_mean jaccard_sd jaccard_n_def "
@@ -1058,6 +1061,47 @@ def map_summary(ms):
     return mean_region, mean_pair
 
 
+def _perm_map_op(op, what):
+    """the op number whose rows a null of `op` runs: "mean" (agg_sum / pairs, regioneR's meanInRegions) runs the rows of op sum"""
+    if op != "mean" and op not in MAP_OPS:
+        raise IgdError("%s: op %r is none of count, sum, min, max, mean" % (what, op))
+    return MAP_OPS["sum" if op == "mean" else op]
+
+
+def permute_map_host(igd_path, ichr, qs, qe, ctg_len, nperm, op, seed=0, mode="circular", value_filter=None, workspace=None, universe=None):
+    """Database.permutation_map() on the host (igdc_permute_map_host: pread on the .igd, threads over the permutations; no
+    device is touched): a PermutationMap.  mode="resample" with universe= and ctg_len None: igdc_permute_map_host_rs."""
+    P = _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, "permute_map_host")
+    o = _perm_map_op(op, "permute_map_host")
+    with _HostDb(igd_path, "permute_map_host") as h:
+        _placement_fits(P, h.nctg, "permute_map_host")
+        out = [np.empty((max(int(nperm), 0) + 1, h.nfiles), np.int64) for _ in range(3)]
+        if getattr(h.L, "igdc_permute_map_host" + P.sfx)(h.core, h.m, _ptr(P.ichr), _ptr(P.qs), _ptr(P.qe), len(P.qs), *P.mid, _seed(seed),
+                                                         int(nperm), o, _value_filter(value_filter), *[_ptr(a) for a in out], *P.tail) != 0:
+            raise IgdError("permute_map_host: a refused argument (number of permutations, op %s on a database without values, %s), or a "
+                           "tile of %s could not be read" % (op, P.refused, igd_path))
+        return PermutationMap(*out, op, int(nperm))
+
+
+def perm_map_summary(pm):
+    """The summary of a PermutationMap (igdc_perm_map_summary; igd_core.h has the formulas): a PermutationMapSummary of arrays
+    [nfiles] -- float64, but observed_n_hit, n_def, n_ge and n_le, which are int64.  The statistic of a row is agg_sum / n_hit
+    (mean_region) for the ops count, sum, min and max and agg_sum / pairs for "mean" (regioneR's meanInRegions over pairs),
+    undefined where the divisor is 0: observed, the n_def permutations that have one, their mean and sd (ddof = 1), z, the
+    defined permutations whose statistic is >= / <= the observed one (compared exactly), -log10 of both one-sided p-values
+    (n + 1) / (n_def + 1); then mean, sd and z of the permuted n_hit.  NaN where undefined."""
+    nh, npairs, sa = (np.ascontiguousarray(x, dtype=np.int64) for x in (pm.n_hit, pm.pairs, pm.agg_sum))
+    if nh.ndim != 2 or nh.shape != npairs.shape or nh.shape != sa.shape or nh.shape[0] != int(pm.nperm) + 1:
+        raise IgdError("perm_map_summary: n_hit, pairs and agg_sum must be int64[nperm + 1, ncols]")
+    _perm_map_op(pm.op, "perm_map_summary")
+    n = nh.shape[1]
+    kinds = [np.float64, np.int64] + [np.float64] * 3 + [np.int64] * 2 + [np.float64] * 5
+    out = [np.empty(n, k) for k in kinds]
+    if N.cli().igdc_perm_map_summary(_ptr(nh), _ptr(npairs), _ptr(sa), int(pm.nperm), n, int(pm.op == "mean"), *[_ptr(x) for x in out]) != 0:
+        raise IgdError("perm_map_summary: bad argument")
+    return PermutationMapSummary(nh[0].copy(), *out)
+
+
 def _forward(f):
     """A public method that hands all its arguments to the private method f (its own name with an underscore in front) and
     carries f's docstring.  For the group entries: tests/test_gpu_database_args.py holds every public method whose signature
@@ -1923,6 +1967,55 @@ class Database:
     def map_files(self, paths, op, value_filter=None):
         """One region set per BED file (read as `igd search -q` reads it): the MapSets of map_sets()."""
         return self.map_sets(*self._read_sets(paths), op, value_filter)
+
+    def _map_sets_fused(self, ichr, qs, qe, set_off, op="sum", value_filter=None, out=None):
+        """map_sets_fused(ichr, qs, qe, set_off, op="sum", value_filter=None, out=None).  map_sets() through the fused kernel
+        (igd_hip_map_sets_fused, kernel igd_map_slices): the same MapSets, every integer, without count and agg rows in device
+        memory.  Databases with more files than igd_hip_map_fused_max_files(op) take map_sets()' route."""
+        ichr, qs, qe, set_off, nsets = _sets(ichr, qs, qe, set_off, "map_sets_fused")
+        o = _map_op(op, "map_sets_fused")
+        out = _outs(out, 3, (nsets, self.nfiles), "map_sets_fused")
+        _chk(self._H.igd_hip_map_sets_fused(self.dev, _ptr(ichr), _ptr(qs), _ptr(qe), _ptr(set_off), nsets, o, _value_filter(value_filter),
+                                            *[_ptr(a) for a in out]), "igd_hip_map_sets_fused")
+        return MapSets(*out, op)
+
+    map_sets_fused = _forward(_map_sets_fused)
+
+    def map_fused_files(self, paths, op, value_filter=None):
+        """One region set per BED file (read as `igd search -q` reads it): the MapSets of map_sets_fused()."""
+        return self.map_sets_fused(*self._read_sets(paths), op, value_filter)
+
+    def _permutation_map(self, ichr, qs, qe, ctg_len, nperm, op, seed=0, mode="circular", value_filter=None, out=None, workspace=None,
+                         universe=None):
+        """permutation_map(ichr, qs, qe, ctg_len, nperm, op, seed=0, mode="circular", value_filter=None, out=None, workspace=None,
+        universe=None).  Permutation null of the values of the records under one region set (igd_hip_permute_map): "are the scores
+        of dataset f's records under my regions higher or lower than chance" (regioneR's permTest with meanInRegions).  The set is
+        permuted nperm times by the generator of permutation_support() (same mode, seed and ctg_len) and every permuted set is
+        measured as map_sets() measures a set.  Returns PermutationMap(n_hit, pairs, agg_sum, op, nperm), each int64[nperm + 1,
+        nfiles]: row 0 is the set as given, row p + 1 permutation p.  op is "count", "sum", "min", "max" or "mean", which runs the
+        rows of "sum"; perm_map_summary() places the observed statistic -- agg_sum / n_hit, for "mean" agg_sum / pairs -- in its
+        null.  out, when given, is a list of three C-ordered int64[nperm + 1, nfiles] that are overwritten.  workspace= with
+        mode="workspace", and universe= with mode="resample" and ctg_len None, as permutation_support() takes them
+        (igd_hip_permute_map_ws, _rs)."""
+        P = _placement(ichr, qs, qe, ctg_len, mode, workspace, universe, "permutation_map")
+        _placement_fits(P, self.nctg, "permutation_map")
+        o = _perm_map_op(op, "permutation_map")
+        out = _outs(out, 3, (max(int(nperm), 0) + 1, self.nfiles), "permutation_map")
+        _chk(getattr(self._H, "igd_hip_permute_map" + P.sfx)(self.dev, _ptr(P.ichr), _ptr(P.qs), _ptr(P.qe), len(P.qs), *P.mid, _seed(seed),
+                                                             int(nperm), o, _value_filter(value_filter), *[_ptr(a) for a in out], *P.tail),
+             "igd_hip_permute_map" + P.sfx.replace("_ws", ""))
+        return PermutationMap(*out, op, int(nperm))
+
+    permutation_map = _forward(_permutation_map)
+
+    def permutation_map_files(self, path, genome_path, nperm, op, seed=0, mode="circular", value_filter=None, workspace=None,
+                              universe_path=None):
+        """The null of one BED file (read as `igd search -q` reads it) with the lengths of a genome file: the integers behind
+        what `igd search -q path -P nperm -g genome_path -I op` prints (with -W: mode="workspace" and workspace=; with -M resample
+        -U universe_path: mode="resample", universe_path= and genome_path None)."""
+        ctg_len, uni = self._genome_or_universe(genome_path, universe_path)
+        return self.permutation_map(*self.read_queries(path), ctg_len, nperm, op, seed, mode, value_filter, workspace=workspace,
+                                    universe=uni)
 
     def map_dev(self, d_ichr, d_qs, d_qe, nq, d_count, d_agg=None, op="sum", value_filter=None, stream=None):
         """Resident batch: arguments are device pointers (ints).  Asynchronous.  d_count (int32[nq * nfiles]) and d_agg

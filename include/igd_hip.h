@@ -1111,6 +1111,45 @@ int igd_hip_permute_bp_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs
                           const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
                           int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped);
 
+/* The set statistics of the overlapping records' values without the count and agg rows, and their permutation null: "are the
+ * scores of dataset f's records under my regions higher or lower than under the same regions placed at random" (regioneR's
+ * permTest with meanInRegions).  Kernel igd_map_slices: the walk and tables of igd_map_rows, folded per region into LDS
+ * accumulators of the slice; nothing per region reaches memory.  THE STATISTICS are igd_hip_map_sets' (counted, op, n_hit, pairs,
+ * agg_sum above), every integer the same.
+ * igd_hip_map_sets_fused: the contract, checks and outputs of igd_hip_map_sets.  Groups of whole sets within the row budget of
+ * igd_hip_support_sets, regions in chunks of igd_hip_max_batch(), no row workspace, one launch per chunk.
+ * igd_hip_permute_map (_ws: inside a workspace; _rs: resampled from a universe -- the placements of the three nulls above, with
+ * their arguments): each output is int64[nperm + 1][nFiles] (any may be NULL): row 0 the statistics of the set as given, row
+ * p + 1 those of permutation p of THE GENERATOR (resp. THE DRAW).  The null distribution itself comes back, as
+ * igd_hip_permute_nearest returns it: the statistics of interest are ratios of two columns that both vary per permutation --
+ *     mean_region = agg_sum / n_hit   (COUNT, SUM, MIN, MAX: the mean over the regions with a record of the region's aggregate)
+ *     mean_pair   = agg_sum / pairs   (SUM: the mean value of a counted record, meanInRegions over pairs)
+ * -- undefined where the denominator is 0 (igdc_perm_map_summary, igd_core.h).  Chunks of pc permutations, pc * nq <=
+ * igd_hip_max_batch() and 3 * pc * nFiles * 8 <= the row budget of igd_hip_permute_support (TEST-ONLY: IGD_HIP_PERM_ROW_BYTES);
+ * the slice table is built and uploaded once; per chunk the generator, a memset of the three matrices, igd_map_slices and an
+ * asynchronous copy of the chunk's rows, enqueued without a wait.
+ * IGD_HIP_ERR_ARG before any launch, nothing of the caller's written, in this order: an unknown op or a value op on a gType 0
+ * database (igd_hip_map's refusal); then the refusals of igd_hip_permute_nearest behind its window (resp. of the _ws and _rs
+ * entries).  nq == 0 or nFiles == 0: all zeros.  Blocking, one device.
+ * Databases with more than igd_hip_map_fused_max_files(op) files (163 840 B of LDS, the whole of a CU, over 28 (COUNT), 52 (MIN,
+ * MAX) or 68 (SUM) bytes per file: 5 851, 3 150, 2 409; 0 for an unknown op) take igd_map_rows + igd_map_reduce instead, in
+ * pieces within the row budget of igd_hip_map (there is no wide form of the fused kernel); the results are the same.
+ * igd_hip_map_fused_grid: workgroups the fused kernel is launched with for nslices slices (tests: a workgroup takes a second
+ * slice only past this number).
+ * Not done: several sets or a set list under the permutation, a minimum overlap, a per-permutation median, several devices. */
+int igd_hip_map_sets_fused(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, const int64_t *set_off, int32_t nsets,
+                           int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum);
+int igd_hip_permute_map(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                        int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum);
+int igd_hip_permute_map_ws(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
+                           int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum,
+                           const igd_hip_workspace *ws);
+int igd_hip_permute_map_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
+                           const int32_t *pool_ichr, const int32_t *pool_qs, const int32_t *pool_qe, int64_t npool, uint64_t seed,
+                           int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum);
+int32_t igd_hip_map_fused_max_files(int op);
+int32_t igd_hip_map_fused_grid(int64_t nslices);
+
 /* Local z-score: the support of a region set under rigid shifts (regioneR's localZScore).  The whole set is moved by each of
  * nshift offsets and counted again; the host places every count in the null the permutation entries above produced.
  * THE SHIFT (the one definition: kernel igd_shift_regions, igdc_shift_regions_host and the tests' numpy reference agree on
