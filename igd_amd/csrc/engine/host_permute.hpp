@@ -1,10 +1,13 @@
 // engine/host_permute.hpp -- part of igd_hip.hip (included there once; not a stand-alone header).
 // igd_hip_permute_support / igd_hip_permute_regions / igd_hip_perm_stats: the permutation null of region-set support
 // ------------------------------------------------------------------------------------------
-// What the three nulls (here, host_permute_nearest.hpp, host_permute_bp.hpp) share is written once, here: the refusals
-// (perm_args_refused), the upload of the call's regions, contig lengths and workspace table (perm_place_upload), the generator's
-// launch (permute_launch) and the chunk driver (run_perm_chunks).  A statistic adds the bytes of device rows one permutation
-// costs, the workspaces it grows, and what it counts from a chunk of rows.
+// What the nulls (here, host_permute_nearest.hpp, host_permute_map.hpp, host_permute_bp.hpp, host_shift.hpp) share is written
+// once, here.  ONE value, PermSpec, says how the rows of a call are made -- free placement, workspace, draw from a pool, rigid
+// shifts -- and is what every exported entry builds from its loose arguments and hands on: to the refusals (perm_args_refused),
+// to the upload of the call's regions, contig lengths, table, offsets or pool (perm_place_upload, which answers with the device
+// side of the same thing, PermPlace), and to the chunk driver (run_perm_chunks), which launches the generator (permute_launch)
+// per chunk.  A statistic adds the bytes of device rows one permutation costs, the workspaces it grows, and what it counts from a
+// chunk of rows.  The entries that return the generated regions themselves share perm_regions_home.
 // The support: the set as given is counted first, one row through igd_sets_support, copied on the device into `observed`
 // (db->d_pmStat holds observed and the six statistics, nFiles + 1 words each; word nFiles is the any-dataset column, the
 // kernel's nhit total).  Then the permutations in the driver's chunks, pc * nFiles * 8 <= perm_row_bytes() (the rows of
@@ -25,7 +28,7 @@ static int64_t perm_row_bytes(void)
 extern "C" int32_t igd_hip_permute_grid(int64_t n) { return items_grid(n, IGD_SETS_WG); }
 
 // The third placement kind, internal to the engine: the set moved rigidly by offsets[p] (igd_hip_shift_place; host_shift.hpp drives
-// it through run_perm_chunks with its offset table).  No public mode: perm_mode_ok refuses it for the three nulls.
+// it through run_perm_chunks with its offset table).  No public mode: igd_hip_perm_mode_ok refuses it for the nulls.
 #define IGD_PERM_PLACE_SHIFT 3
 
 // The pool of a resampling call (THE DRAW of include/igd_hip.h): host arrays of npool regions.  No pool: every other mode.
@@ -34,13 +37,16 @@ struct PermPool {
     int64_t npool;
 };
 
-// a mode the call can run: the two free placements without a workspace, IGD_HIP_PERM_WORKSPACE with one, IGD_HIP_PERM_RESAMPLE
-// exactly when a pool is given and never with a workspace
-static bool perm_mode_ok(int mode, const igd_hip_workspace *ws, const PermPool *pool = nullptr)
-{
-    if (pool || mode == IGD_HIP_PERM_RESAMPLE) return pool && !ws && mode == IGD_HIP_PERM_RESAMPLE;
-    return ws ? mode == IGD_HIP_PERM_WORKSPACE : (mode == IGD_HIP_PERM_CIRCULAR || mode == IGD_HIP_PERM_SHUFFLE);
-}
+// HOW THE ROWS OF ONE CALL ARE MADE, as the caller gave it (host pointers): nperm permutations, draws or shifts.  Exactly one of
+// ws (mode IGD_HIP_PERM_WORKSPACE), offsets (mode IGD_PERM_PLACE_SHIFT: nperm of them, the seed is not read) and pool (mode
+// IGD_HIP_PERM_RESAMPLE: no ctg_len) is set, or none (the two free placements).
+struct PermSpec {
+    const int32_t *ctg_len;
+    int mode; uint64_t seed; int64_t nperm;
+    const igd_hip_workspace *ws;
+    const int32_t *offsets;
+    const PermPool *pool;
+};
 
 // true, g_err set: the table is not valid for these contigs or -- drivers only, behind their own check of the regions -- a
 // region on a known contig fits in no segment
@@ -67,12 +73,12 @@ static bool perm_ws_refused(const char *who, const igd_hip_workspace *ws, const 
 // With a pool (mode IGD_HIP_PERM_RESAMPLE) nothing is placed: no contig lengths are asked for and no region is validated; the
 // pool's size is held against the batch and against nq instead.
 static bool perm_args_refused(const char *who, const igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                              const int32_t *ctg_len, int mode, int64_t nperm, const igd_hip_workspace *ws, bool extraBad,
-                              const PermPool *pool = nullptr)
+                              const PermSpec &sp, bool extraBad)
 {
+    const auto [ctg_len, mode, seed, nperm, ws, offsets, pool] = sp;
     const bool poolBad = pool && (pool->npool < 0 || (pool->npool > 0 && (!pool->ichr || !pool->qs || !pool->qe)));
     if (!db || nq < 0 || extraBad || (nq > 0 && (!ichr || !qs || !qe)) || (!pool && !ctg_len && db->nCtg > 0) || poolBad ||
-        !perm_mode_ok(mode, ws, pool)) {
+        !igd_hip_perm_mode_ok(mode, ws != nullptr, pool != nullptr)) {
         snprintf(g_err, sizeof g_err, "%s: bad argument", who);
         return true;
     }
@@ -130,11 +136,12 @@ static int perm_pool_upload(igd_hip_db *db, const PermPool &pool, int32_t *at, P
 }
 
 // both buffers grown, then on the engine's stream the table of a checked workspace (without one only the mode is kept) and the
-// regions with the contig lengths; offsets (nshift of them; NULL, 0 for the nulls) or the pool of a resampling call go up last
-static int perm_place_upload(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
-                             int32_t nctg, int mode, const igd_hip_workspace *ws, PermPlace *pl, const int32_t *offsets = nullptr,
-                             int64_t nshift = 0, const PermPool *pool = nullptr)
+// regions with the nctg contig lengths; the offsets of a shift call (sp.nperm of them) or the pool of a resampling call go up last
+static int perm_place_upload(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t nctg,
+                             const PermSpec &sp, PermPlace *pl)
 {
+    const auto [ctg_len, mode, seed, nperm, ws, offsets, pool] = sp;
+    const int64_t nshift = offsets ? nperm : 0;
     const int64_t nc = ws ? ws->nctg : 0, ns = ws ? ws->nseg : 0;
     hipStream_t st = db->stream;
     int rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * nq + nctg + nshift + (pool ? 3 * pool->npool : 0));
@@ -184,6 +191,30 @@ static int permute_launch(igd_hip_db *db, const PermPlace &pl, u64 seed, u64 p0,
     return IGD_HIP_OK;
 }
 
+// The generator alone, for the entries that return the regions themselves (igd_hip_permute_regions_ws, igd_hip_resample_regions,
+// igd_hip_shift_regions), behind their uploads and ensure_qstage(pc * nq): permutations [p0, p0 + np) of the placement, pc per
+// launch into the staging arrays, each chunk copied back behind its launch into home[] (the call's own buffers, np * nq words
+// each; contigs, starts, ends -- home[0] == nullptr: no contigs are generated); ONE wait, then the caller's arrays out[].
+static int perm_regions_home(igd_hip_db *db, const PermPlace &pl, u64 seed, int64_t p0, int64_t np, int64_t pc, int32_t *const home[3],
+                             int32_t *const out[3])
+{
+    const int64_t nq = pl.nq;
+    int32_t *const stage[3] = {home[0] ? db->d_qc : nullptr, db->d_qs, db->d_qe};
+    hipStream_t st = db->stream;
+    for (int64_t a = 0; a < np; a += pc) {
+        const int64_t n = np - a < pc ? np - a : pc;
+        const int rc = permute_launch(db, pl, seed, (u64)(p0 + a), n * nq, stage[0], stage[1], stage[2]);
+        if (rc != IGD_HIP_OK) return rc;
+        for (int i = 0; i < 3; i++)
+            if (home[i]) HIPCHK(hipMemcpyAsync(home[i] + a * nq, stage[i], (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < 3; i++)
+        if (home[i]) memcpy(out[i], home[i], (size_t)(np * nq) * 4);
+    return IGD_HIP_OK;
+}
+
 // the host slice table of a chunk of pc rows of nq staged regions: row r cut as igd_hip_support_sets cuts a set (the support, the
 // fused nearest kernel); a shorter chunk uses a prefix of it
 static std::vector<SetSlice> perm_row_slices(int64_t pc, int64_t nq, int64_t sliceLen)
@@ -204,14 +235,14 @@ static std::vector<SetSlice> perm_row_slices(int64_t pc, int64_t nq, int64_t sli
 // this call also uploads what every chunk reads, and adds what the statistic does once behind row 0), then per chunk the
 // generator's output in the staging arrays (r0 = 1 + p0); the call with r0 + rows == nperm + 1 is the last.  Everything is on the
 // engine's stream without a wait in between, unless count waits itself; ONE wait at the end, behind which the callers write
-// their results.  offsets (NULL for the three nulls): the table of mode IGD_PERM_PLACE_SHIFT, nperm entries -- "permutation" p
-// is then the set shifted by offsets[p], and the caller's count has nothing to do with the set as given.  pool (NULL but for
-// mode IGD_HIP_PERM_RESAMPLE, which has no ctg_len): its regions go up behind the call's, and permutation p is a draw from it.
+// their results.  sp.offsets: the table of mode IGD_PERM_PLACE_SHIFT, nperm entries -- "permutation" p is then the set shifted
+// by offsets[p], and the caller's count has nothing to do with the set as given.  sp.pool (mode IGD_HIP_PERM_RESAMPLE, which has
+// no ctg_len): its regions go up behind the call's, and permutation p is a draw from it.
 template <typename Prepare, typename Count>
-static int run_perm_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,
-                           int mode, uint64_t seed, int64_t nperm, const igd_hip_workspace *ws, int64_t rowBytes, Prepare &&prepare,
-                           Count &&count, const int32_t *offsets = nullptr, const PermPool *pool = nullptr)
+static int run_perm_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const PermSpec &sp,
+                           int64_t rowBytes, Prepare &&prepare, Count &&count)
 {
+    const int64_t nperm = sp.nperm;
     HIPCHK(hipSetDevice(db->device));
     int64_t pc = max_batch() / nq;
     const int64_t byRows = rowBytes > 0 ? perm_row_bytes() / rowBytes : pc;
@@ -222,11 +253,11 @@ static int run_perm_chunks(igd_hip_db *db, const int32_t *ichr, const int32_t *q
     int rc = prepare(pc, sliceLen, perRow);
     if (rc == IGD_HIP_OK) rc = ensure_qstage(db, pc * nq);
     PermPlace pl;
-    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, pool ? 0 : db->nCtg, mode, ws, &pl, offsets, offsets ? nperm : 0, pool);
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, sp.pool ? 0 : db->nCtg, sp, &pl);
     if (rc == IGD_HIP_OK) rc = count(pl.rC, pl.rS, pl.rE, (int64_t)1, (int64_t)0);      // the set as given
     for (int64_t p0 = 0; rc == IGD_HIP_OK && p0 < nperm; p0 += pc) {
         const int64_t n = nperm - p0 < pc ? nperm - p0 : pc;
-        rc = permute_launch(db, pl, (u64)seed, (u64)p0, n * nq, db->d_qc, db->d_qs, db->d_qe);
+        rc = permute_launch(db, pl, (u64)sp.seed, (u64)p0, n * nq, db->d_qc, db->d_qs, db->d_qe);
         if (rc == IGD_HIP_OK) rc = count(db->d_qc, db->d_qs, db->d_qe, n, 1 + p0);
     }
     if (rc != IGD_HIP_OK) return rc;
@@ -276,10 +307,10 @@ static void perm_copy_out(const int64_t *res, int64_t nC, int64_t *const out[7])
 
 // the body of igd_hip_permute_support_ws and, with a pool and no ctg_len, of igd_hip_permute_support_rs
 static int permute_support_run(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                               const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
-                               int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
-                               const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws, const PermPool *pool)
+                               const PermSpec &sp, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge,
+                               int64_t *n_le, int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap)
 {
+    const int64_t nperm = sp.nperm;
     if (!igd_hip_min_overlap_valid(min_overlap)) {
         snprintf(g_err, sizeof g_err, "%s: min_overlap (%d bp, %d ppm, %d ppm) out of range", who, (int)min_overlap->min_bp,
                  (int)min_overlap->ppm_query, (int)min_overlap->ppm_record);
@@ -287,8 +318,7 @@ static int permute_support_run(const char *who, igd_hip_db *db, const int32_t *i
     }
     const bool ov = igd_hip_min_overlap_active(min_overlap);
     const MinOv mo = min_ov_of(min_overlap);
-    if (perm_args_refused(who, db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws,
-                          !observed || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT), pool))
+    if (perm_args_refused(who, db, ichr, qs, qe, nq, sp, !observed || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)))
         return IGD_HIP_ERR_ARG;
     if ((unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63) {
         snprintf(g_err, sizeof g_err, "%s: %lld permutations of %lld regions: the sum of squares may pass 2^63", who, (long long)nperm,
@@ -337,7 +367,7 @@ static int permute_support_run(const char *who, igd_hip_db *db, const int32_t *i
         if (r0 + rows == nperm + 1) HIPCHK(hipMemcpyAsync(res.data(), db->d_pmStat, (size_t)(7 * nC) * 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
-    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, nF * 8, prepare, count, nullptr, pool);
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, sp, nF * 8, prepare, count);
     if (rc != IGD_HIP_OK) return rc;
     perm_copy_out(res.data(), nC, out);
     return IGD_HIP_OK;
@@ -348,8 +378,9 @@ extern "C" int igd_hip_permute_support_ws(igd_hip_db *db, const int32_t *ichr, c
                                           int64_t *observed, int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin,
                                           int64_t *pmax, const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
 {
-    return permute_support_run("igd_hip_permute_support", db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge,
-                               n_le, pmin, pmax, min_overlap, ws, nullptr);
+    const PermSpec sp{ctg_len, mode, seed, nperm, ws, nullptr, nullptr};
+    return permute_support_run("igd_hip_permute_support", db, ichr, qs, qe, nq, sp, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax,
+                               min_overlap);
 }
 
 extern "C" int igd_hip_permute_support_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -359,8 +390,9 @@ extern "C" int igd_hip_permute_support_rs(igd_hip_db *db, const int32_t *ichr, c
                                           const igd_hip_min_overlap *min_overlap)
 {
     const PermPool pool{pool_ichr, pool_qs, pool_qe, npool};
-    return permute_support_run("igd_hip_permute_support_rs", db, ichr, qs, qe, nq, nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, v, rule, observed,
-                               sum, sumsq, n_ge, n_le, pmin, pmax, min_overlap, nullptr, &pool);
+    const PermSpec sp{nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, nullptr, nullptr, &pool};
+    return permute_support_run("igd_hip_permute_support_rs", db, ichr, qs, qe, nq, sp, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax,
+                               min_overlap);
 }
 
 extern "C" int igd_hip_permute_support_ov(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -386,7 +418,7 @@ extern "C" int igd_hip_permute_regions_ws(igd_hip_db *db, const int32_t *ichr, c
                                           int32_t *out_qs, int32_t *out_qe, const igd_hip_workspace *ws)
 {
     if (!db || nq < 0 || np < 0 || p0 < 0 || nctg < 0 || (nctg > 0 && !ctg_len) || (nq > 0 && (!ichr || !qs || !qe)) ||
-        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || !perm_mode_ok(mode, ws) ||
+        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || !igd_hip_perm_mode_ok(mode, ws != nullptr, 0) ||
         nq > max_batch() || (nq > 0 && np > (int64_t)INT32_MAX / nq)) {
         snprintf(g_err, sizeof g_err, "igd_hip_permute_regions: bad argument");
         return IGD_HIP_ERR_ARG;
@@ -396,22 +428,12 @@ extern "C" int igd_hip_permute_regions_ws(igd_hip_db *db, const int32_t *ichr, c
     const int64_t pc = max_batch() / nq < np ? max_batch() / nq : np;
     std::vector<int32_t> hs((size_t)(np * nq)), he((size_t)(np * nq));
     HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
     int rc = ensure_qstage(db, pc * nq);
     PermPlace pl;
-    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, nctg, mode, ws, &pl);
+    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, nctg, PermSpec{ctg_len, mode, seed, np, ws, nullptr, nullptr}, &pl);
     if (rc != IGD_HIP_OK) return rc;
-    for (int64_t a = 0; a < np; a += pc) {
-        const int64_t n = np - a < pc ? np - a : pc;
-        if ((rc = permute_launch(db, pl, (u64)seed, (u64)(p0 + a), n * nq, nullptr, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemcpyAsync(hs.data() + a * nq, db->d_qs, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(he.data() + a * nq, db->d_qe, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    memcpy(out_qs, hs.data(), (size_t)(np * nq) * 4);
-    memcpy(out_qe, he.data(), (size_t)(np * nq) * 4);
-    return IGD_HIP_OK;
+    int32_t *const home[3] = {nullptr, hs.data(), he.data()}, *const out[3] = {nullptr, out_qs, out_qe};
+    return perm_regions_home(db, pl, (u64)seed, p0, np, pc, home, out);
 }
 
 extern "C" int igd_hip_permute_regions(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -442,26 +464,14 @@ extern "C" int igd_hip_resample_regions(igd_hip_db *db, const int32_t *pool_ichr
     std::vector<int32_t> h((size_t)(3 * np * nq));
     int32_t *hc = h.data(), *hs = hc + np * nq, *he = hs + np * nq;
     HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
     int rc = ensure_qstage(db, pc * nq);
     if (rc == IGD_HIP_OK) rc = dev_grow(db, &db->d_pmReg, &db->pmRegCap, 3 * npool);
     if (rc != IGD_HIP_OK) return rc;
     PermPlace pl{nullptr, nullptr, nullptr, nullptr, nq, 0, IGD_HIP_PERM_RESAMPLE, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     const PermPool pool{pool_ichr, pool_qs, pool_qe, npool};
     if ((rc = perm_pool_upload(db, pool, db->d_pmReg, &pl)) != IGD_HIP_OK) return rc;
-    for (int64_t a = 0; a < np; a += pc) {
-        const int64_t n = np - a < pc ? np - a : pc;
-        if ((rc = permute_launch(db, pl, (u64)seed, (u64)(p0 + a), n * nq, db->d_qc, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemcpyAsync(hc + a * nq, db->d_qc, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(hs + a * nq, db->d_qs, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(he + a * nq, db->d_qe, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    memcpy(out_ichr, hc, (size_t)(np * nq) * 4);
-    memcpy(out_qs, hs, (size_t)(np * nq) * 4);
-    memcpy(out_qe, he, (size_t)(np * nq) * 4);
-    return IGD_HIP_OK;
+    int32_t *const home[3] = {hc, hs, he}, *const out[3] = {out_ichr, out_qs, out_qe};
+    return perm_regions_home(db, pl, (u64)seed, p0, np, pc, home, out);
 }
 
 extern "C" int igd_hip_perm_stats(igd_hip_db *db, const int64_t *rows, int64_t nrows, int64_t ncols, const int64_t *observed,

@@ -24,12 +24,10 @@ extern "C" int64_t igd_hip_merge_slices_per_row(int64_t pc, int64_t nq)
 // the body of igd_hip_permute_bp_ws and, with a pool and no ctg_len, of igd_hip_permute_bp_rs (whose drawn rows drop what their own
 // regions make them drop; n_dropped stays row 0's)
 static int permute_bp_run(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                          const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp,
-                          int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws, const PermPool *pool)
+                          const PermSpec &sp, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped)
 {
-    if (perm_args_refused(who, db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT, pool))
-        return IGD_HIP_ERR_ARG;
-    const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
+    if (perm_args_refused(who, db, ichr, qs, qe, nq, sp, rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT)) return IGD_HIP_ERR_ARG;
+    const int64_t nF = db->nFiles, nC = nF + 1, R = sp.nperm + 1;
     if (nq == 0) {                                       // no region: no run, no base pair
         if (inter) memset(inter, 0, (size_t)R * (size_t)nC * 8);
         if (set_bp) memset(set_bp, 0, (size_t)R * 8);
@@ -91,7 +89,7 @@ static int permute_bp_run(const char *who, igd_hip_db *db, const int32_t *ichr, 
         if (r0 == 0) HIPCHK(hipMemcpyAsync(hDrop, dDrop, 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
-    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, nF * 8, prepare, count, nullptr, pool);
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, sp, nF * 8, prepare, count);
     if (rc != IGD_HIP_OK) return rc;
     if (inter)
         for (int64_t r = 0; r < R; r++) {
@@ -108,8 +106,8 @@ extern "C" int igd_hip_permute_bp_ws(igd_hip_db *db, const int32_t *ichr, const 
                                      int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp,
                                      int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
 {
-    return permute_bp_run("igd_hip_permute_bp", db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, ws,
-                          nullptr);
+    const PermSpec sp{ctg_len, mode, seed, nperm, ws, nullptr, nullptr};
+    return permute_bp_run("igd_hip_permute_bp", db, ichr, qs, qe, nq, sp, v, rule, inter, set_bp, n_merged, n_dropped);
 }
 
 extern "C" int igd_hip_permute_bp_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -118,8 +116,8 @@ extern "C" int igd_hip_permute_bp_rs(igd_hip_db *db, const int32_t *ichr, const 
                                      int64_t *n_dropped)
 {
     const PermPool pool{pool_ichr, pool_qs, pool_qe, npool};
-    return permute_bp_run("igd_hip_permute_bp_rs", db, ichr, qs, qe, nq, nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, v, rule, inter, set_bp,
-                          n_merged, n_dropped, nullptr, &pool);
+    const PermSpec sp{nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, nullptr, nullptr, &pool};
+    return permute_bp_run("igd_hip_permute_bp_rs", db, ichr, qs, qe, nq, sp, v, rule, inter, set_bp, n_merged, n_dropped);
 }
 
 extern "C" int igd_hip_permute_bp(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len,

@@ -109,12 +109,11 @@ static int map_rows_reduce(igd_hip_db *db, const int32_t *c, const int32_t *s, c
 
 // the body of igd_hip_permute_map_ws and, with a pool and no ctg_len, of igd_hip_permute_map_rs
 static int permute_map_run(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                           const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs,
-                           int64_t *agg_sum, const igd_hip_workspace *ws, const PermPool *pool)
+                           const PermSpec &sp, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
 {
     if (map_op_bad(who, db, op)) return IGD_HIP_ERR_ARG;
-    if (perm_args_refused(who, db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, false, pool)) return IGD_HIP_ERR_ARG;
-    const int64_t nF = db->nFiles, R = nperm + 1;
+    if (perm_args_refused(who, db, ichr, qs, qe, nq, sp, false)) return IGD_HIP_ERR_ARG;
+    const int64_t nF = db->nFiles, nperm = sp.nperm, R = nperm + 1;
     int64_t *const outs[3] = {n_hit, pairs, agg_sum};
     if (nq == 0 || nF == 0) {                            // every statistic is 0: no region, or no dataset
         for (int64_t *o : outs) if (o) memset(o, 0, (size_t)R * (size_t)nF * 8);
@@ -146,7 +145,7 @@ static int permute_map_run(const char *who, igd_hip_db *db, const int32_t *ichr,
             HIPCHK(hipMemcpyAsync(res.data() + (i * R + r0) * nF, db->d_grpStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
-    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, 3 * nF * 8, prepare, count, nullptr, pool);
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, sp, 3 * nF * 8, prepare, count);
     if (rc != IGD_HIP_OK) return rc;
     for (int i = 0; i < 3; i++)
         if (outs[i]) memcpy(outs[i], res.data() + (size_t)i * (size_t)(R * nF), (size_t)(R * nF) * 8);
@@ -157,7 +156,8 @@ extern "C" int igd_hip_permute_map_ws(igd_hip_db *db, const int32_t *ichr, const
                                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit,
                                       int64_t *pairs, int64_t *agg_sum, const igd_hip_workspace *ws)
 {
-    return permute_map_run("igd_hip_permute_map", db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, op, v, n_hit, pairs, agg_sum, ws, nullptr);
+    const PermSpec sp{ctg_len, mode, seed, nperm, ws, nullptr, nullptr};
+    return permute_map_run("igd_hip_permute_map", db, ichr, qs, qe, nq, sp, op, v, n_hit, pairs, agg_sum);
 }
 
 extern "C" int igd_hip_permute_map_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -165,8 +165,8 @@ extern "C" int igd_hip_permute_map_rs(igd_hip_db *db, const int32_t *ichr, const
                                       int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
 {
     const PermPool pool{pool_ichr, pool_qs, pool_qe, npool};
-    return permute_map_run("igd_hip_permute_map_rs", db, ichr, qs, qe, nq, nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, op, v, n_hit, pairs,
-                           agg_sum, nullptr, &pool);
+    const PermSpec sp{nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, nullptr, nullptr, &pool};
+    return permute_map_run("igd_hip_permute_map_rs", db, ichr, qs, qe, nq, sp, op, v, n_hit, pairs, agg_sum);
 }
 
 extern "C" int igd_hip_permute_map(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,

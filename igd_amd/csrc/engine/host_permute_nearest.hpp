@@ -100,12 +100,11 @@ static int nearest_rows_reduce(igd_hip_db *db, const int32_t *c, const int32_t *
 
 // the body of igd_hip_permute_nearest_ws and, with a pool and no ctg_len, of igd_hip_permute_nearest_rs
 static int permute_nearest_run(const char *who, igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                               const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v, int64_t *n_within,
-                               int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws, const PermPool *pool)
+                               const PermSpec &sp, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
 {
     if (nearest_window_bad(who, window)) return IGD_HIP_ERR_ARG;
-    if (perm_args_refused(who, db, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, false, pool)) return IGD_HIP_ERR_ARG;
-    const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
+    if (perm_args_refused(who, db, ichr, qs, qe, nq, sp, false)) return IGD_HIP_ERR_ARG;
+    const int64_t nF = db->nFiles, nC = nF + 1, nperm = sp.nperm, R = nperm + 1;
     int64_t *const outs[3] = {n_within, n_overlap, sum_dist};
     if (nq == 0 || nF == 0) {                            // every statistic is 0: no region, or no dataset to be near
         for (int64_t *o : outs) if (o) memset(o, 0, (size_t)R * (size_t)nC * 8);
@@ -137,7 +136,7 @@ static int permute_nearest_run(const char *who, igd_hip_db *db, const int32_t *i
             HIPCHK(hipMemcpyAsync(res.data() + (i * R + r0) * nC, db->d_grpStat + i * matWords, (size_t)matWords * 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
-    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, ws, 3 * nC * 8, prepare, count, nullptr, pool);
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, sp, 3 * nC * 8, prepare, count);
     if (rc != IGD_HIP_OK) return rc;
     for (int i = 0; i < 3; i++)
         if (outs[i]) memcpy(outs[i], res.data() + (size_t)i * (size_t)(R * nC), (size_t)(R * nC) * 8);
@@ -148,8 +147,8 @@ extern "C" int igd_hip_permute_nearest_ws(igd_hip_db *db, const int32_t *ichr, c
                                           const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
                                           int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws)
 {
-    return permute_nearest_run("igd_hip_permute_nearest", db, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap,
-                               sum_dist, ws, nullptr);
+    const PermSpec sp{ctg_len, mode, seed, nperm, ws, nullptr, nullptr};
+    return permute_nearest_run("igd_hip_permute_nearest", db, ichr, qs, qe, nq, sp, window, v, n_within, n_overlap, sum_dist);
 }
 
 extern "C" int igd_hip_permute_nearest_rs(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -158,8 +157,8 @@ extern "C" int igd_hip_permute_nearest_rs(igd_hip_db *db, const int32_t *ichr, c
                                           int64_t *sum_dist)
 {
     const PermPool pool{pool_ichr, pool_qs, pool_qe, npool};
-    return permute_nearest_run("igd_hip_permute_nearest_rs", db, ichr, qs, qe, nq, nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, window, v,
-                               n_within, n_overlap, sum_dist, nullptr, &pool);
+    const PermSpec sp{nullptr, IGD_HIP_PERM_RESAMPLE, seed, nperm, nullptr, nullptr, &pool};
+    return permute_nearest_run("igd_hip_permute_nearest_rs", db, ichr, qs, qe, nq, sp, window, v, n_within, n_overlap, sum_dist);
 }
 
 extern "C" int igd_hip_permute_nearest(igd_hip_db *db, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,

@@ -90,7 +90,8 @@ extern "C" int igd_hip_shift_support(igd_hip_db *db, const int32_t *ichr, const 
         HIPCHK(hipMemcpyAsync(totHome.data() + (r0 - 1), db->d_setTot, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
         return IGD_HIP_OK;
     };
-    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, ctg_len, IGD_PERM_PLACE_SHIFT, 0, nshift, nullptr, nF * 8, prepare, count, offsets);
+    const PermSpec sp{ctg_len, IGD_PERM_PLACE_SHIFT, 0, nshift, nullptr, offsets, nullptr};
+    const int rc = run_perm_chunks(db, ichr, qs, qe, nq, sp, nF * 8, prepare, count);
     if (rc != IGD_HIP_OK) return rc;
     for (int64_t j = 0; j < nshift; j++) {
         memcpy(shifted + j * nC, rowsHome.data() + j * nF, (size_t)nF * 8);
@@ -115,20 +116,11 @@ extern "C" int igd_hip_shift_regions(igd_hip_db *db, const int32_t *ichr, const 
     const int64_t pc = max_batch() / nq < nshift ? max_batch() / nq : nshift;
     std::vector<int32_t> hs((size_t)(nshift * nq)), he((size_t)(nshift * nq));
     HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = db->stream;
     int rc = ensure_qstage(db, pc * nq);
     PermPlace pl;
-    if (rc == IGD_HIP_OK) rc = perm_place_upload(db, ichr, qs, qe, nq, ctg_len, nctg, IGD_PERM_PLACE_SHIFT, nullptr, &pl, offsets, nshift);
+    if (rc == IGD_HIP_OK)
+        rc = perm_place_upload(db, ichr, qs, qe, nq, nctg, PermSpec{ctg_len, IGD_PERM_PLACE_SHIFT, 0, nshift, nullptr, offsets, nullptr}, &pl);
     if (rc != IGD_HIP_OK) return rc;
-    for (int64_t a = 0; a < nshift; a += pc) {
-        const int64_t n = nshift - a < pc ? nshift - a : pc;
-        if ((rc = permute_launch(db, pl, 0, (u64)a, n * nq, nullptr, db->d_qs, db->d_qe)) != IGD_HIP_OK) return rc;
-        HIPCHK(hipMemcpyAsync(hs.data() + a * nq, db->d_qs, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(he.data() + a * nq, db->d_qe, (size_t)(n * nq) * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    memcpy(out_qs, hs.data(), (size_t)(nshift * nq) * 4);
-    memcpy(out_qe, he.data(), (size_t)(nshift * nq) * 4);
-    return IGD_HIP_OK;
+    int32_t *const home[3] = {nullptr, hs.data(), he.data()}, *const out[3] = {nullptr, out_qs, out_qe};
+    return perm_regions_home(db, pl, 0, 0, nshift, pc, home, out);
 }

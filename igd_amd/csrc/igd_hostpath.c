@@ -1105,28 +1105,38 @@ int igdc_cooccur_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr,
     return rc;
 }
 
-/* Permutation null of region-set support on the host: what igd_hip_permute_support computes (include/igd_hip.h has the
- * generator and the definitions).  igdc_permute_regions_host is kernel igd_permute_regions, igdc_permute_host the whole test:
- * the set as given through igdc_support_host, then threads over the permutations (thread k takes p = k, k + T, ..), each with
- * its own permuted arrays, row and stamp array, walking a permuted set with the per-query code of igdc_support_host and
- * folding the row into its own statistics; the threads' statistics are combined at the end.  All outputs are DEFINED. */
-/* a mode the call can run: the two free placements without a workspace, IGD_HIP_PERM_WORKSPACE with one (a checked table) */
-static int perm_mode_ok(int mode, const igd_hip_workspace *ws)
-{
-    return ws ? mode == IGD_HIP_PERM_WORKSPACE : (mode == IGD_HIP_PERM_CIRCULAR || mode == IGD_HIP_PERM_SHUFFLE);
-}
+/* ---- the permutation nulls on the host: what the igd_hip_permute_* entries compute (include/igd_hip.h has the generator and
+ * the definitions) -----------------------------------------------------------------------------------------------------------
+ * Five statistics have one: support (igdc_permute_host*), support under rigid shifts (igdc_shift_support_host_ov), nearest
+ * distances, record values and base pairs (further down, each behind the statistic it permutes).  They share ONE value that says
+ * how a permuted row is made (perm_place, below) and ONE driver that shares the rows out over threads (stripe_drive); a statistic
+ * adds its refusals, its result buffer, its row function and the copy-out.  The generators alone are igdc_permute_regions_host
+ * (kernel igd_permute_regions), igdc_shift_regions_host and igdc_resample_regions_host.  All outputs are DEFINED. */
+/* THE PLACEMENT of a call.  Exactly one of four ways: mode CIRCULAR or SHUFFLE on the contigs (ws, offsets and pool NULL), mode
+ * WORKSPACE inside the checked table ws, a rigid shift by offsets[r - 1] (the shift entries; mode and seed unused), or mode
+ * RESAMPLE, a draw from pool (no ctg_len: nothing is placed).  Every exported entry builds one from its loose arguments in one
+ * line; everything below that takes the value. */
+typedef struct { const int32_t *ichr, *qs, *qe; int64_t npool; } perm_pool;
+typedef struct {
+    const int32_t *ctg_len;
+    int mode; uint64_t seed;
+    const igd_hip_workspace *ws;
+    const int32_t *offsets;
+    const perm_pool *pool;
+} perm_place;
 
-/* the placement itself, on checked arguments: what the threads of the three drivers call per permutation */
-static void perm_regions_fill(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, const int32_t *ctg_len, int32_t nctg,
-                              int mode, uint64_t seed, int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe, const igd_hip_workspace *ws)
+/* the generator's placement itself, on checked arguments: permutations p0 .. p0 + np - 1 of the set */
+static void perm_regions_fill(const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t nctg, const perm_place *pl,
+                              int64_t p0, int64_t np, int32_t *out_qs, int32_t *out_qe)
 {
+    const igd_hip_workspace *ws = pl->ws;
     for (int64_t p = 0; p < np; p++) {
-        const uint64_t base = igd_hip_perm_base(seed, (uint64_t)(p0 + p));
+        const uint64_t base = igd_hip_perm_base(pl->seed, (uint64_t)(p0 + p));
         int32_t *os = out_qs + p * nq, *oe = out_qe + p * nq;
         for (int64_t i = 0; i < nq; i++) {
             os[i] = qs[i]; oe[i] = qe[i];
-            if (ws) (void)igd_hip_perm_place_ws(base, ichr[i], i, ctg_len, nctg, ws->w_off, ws->w_start, ws->w_len, ws->w_pre, &os[i], &oe[i]);
-            else igd_hip_perm_place(mode, base, ichr[i], i, ctg_len, nctg, &os[i], &oe[i]);
+            if (ws) (void)igd_hip_perm_place_ws(base, ichr[i], i, pl->ctg_len, nctg, ws->w_off, ws->w_start, ws->w_len, ws->w_pre, &os[i], &oe[i]);
+            else igd_hip_perm_place(pl->mode, base, ichr[i], i, pl->ctg_len, nctg, &os[i], &oe[i]);
         }
     }
 }
@@ -1136,9 +1146,11 @@ int igdc_permute_regions_host_ws(const int32_t *ichr, const int32_t *qs, const i
                                  const igd_hip_workspace *ws)
 {
     if (nq < 0 || np < 0 || p0 < 0 || nctg < 0 || (nctg > 0 && !ctg_len) || (nq > 0 && (!ichr || !qs || !qe)) ||
-        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || !perm_mode_ok(mode, ws) || (ws && !igd_hip_workspace_valid(ws, ctg_len, nctg)))
+        (nq > 0 && np > 0 && (!out_qs || !out_qe)) || !igd_hip_perm_mode_ok(mode, ws != NULL, 0) ||
+        (ws && !igd_hip_workspace_valid(ws, ctg_len, nctg)))
         return -1;
-    perm_regions_fill(ichr, qs, qe, nq, ctg_len, nctg, mode, seed, p0, np, out_qs, out_qe, ws);
+    const perm_place pl = {ctg_len, mode, seed, ws, NULL, NULL};
+    perm_regions_fill(ichr, qs, qe, nq, nctg, &pl, p0, np, out_qs, out_qe);
     return 0;
 }
 
@@ -1181,7 +1193,6 @@ int igdc_shift_regions_host(const int32_t *ichr, const int32_t *qs, const int32_
 
 /* The pool of a resampling call (include/igd_hip.h: THE DRAW) and the draws themselves, on checked arguments (nq <= npool): draw i
  * of permutation p0 + p is pool region igd_hip_resample_index(base, i, npool), copied as it stands. */
-typedef struct { const int32_t *ichr, *qs, *qe; int64_t npool; } perm_pool;
 static void resample_regions_fill(const perm_pool *pool, int64_t nq, uint64_t seed, int64_t p0, int64_t np, int32_t *out_ichr,
                                   int32_t *out_qs, int32_t *out_qe)
 {
@@ -1331,65 +1342,96 @@ int64_t igdc_permute_first_bad(const int32_t *ichr, const int32_t *qs, const int
     return igd_hip_perm_first_bad(ichr, qs, qe, nq, ctg_len, nctg);
 }
 
-/* the refusals the three drivers share (each adds its own in front): the set and the contig lengths, a mode the call can run, the
+/* the refusals the nulls share (each adds its own in front): the set and the contig lengths, a mode the call can run, the
  * number of permutations, the generator's bounds on the regions, and under a workspace a table that is valid for the database's
  * contigs and has a segment for every region on a known contig */
 static int perm_args_bad(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                         const int32_t *ctg_len, int mode, int64_t nperm, const igd_hip_workspace *ws, const perm_pool *pool)
+                         int64_t nperm, const perm_place *pl)
 {
+    const int32_t *ctg_len = pl->ctg_len;
+    const igd_hip_workspace *ws = pl->ws;
     /* resampling: nothing is placed, so there are no contig lengths and no region is validated; the pool has its own bounds */
-    if (pool || mode == IGD_HIP_PERM_RESAMPLE)
-        return !pool || ws || mode != IGD_HIP_PERM_RESAMPLE || !db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || nperm < 1 ||
-               nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || pool_bad(pool, nq);
-    return !db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) || !perm_mode_ok(mode, ws) ||
+    if (pl->pool || pl->mode == IGD_HIP_PERM_RESAMPLE)
+        return !igd_hip_perm_mode_ok(pl->mode, ws != NULL, pl->pool != NULL) || !db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) ||
+               nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || pool_bad(pl->pool, nq);
+    return !db || !m || nq < 0 || (nq > 0 && (!ichr || !qs || !qe)) || (!ctg_len && db->nCtg > 0) || !igd_hip_perm_mode_ok(pl->mode, ws != NULL, 0) ||
            nperm < 1 || nperm > IGD_HIP_PERM_MAX || nq > igd_hip_max_batch() || igdc_permute_first_bad(ichr, qs, qe, nq, ctg_len, db->nCtg) >= 0 ||
            (ws && (!igd_hip_workspace_valid(ws, ctg_len, db->nCtg) || igdc_workspace_first_unplaceable(ws, ctg_len, ichr, qs, qe, nq) >= 0));
 }
 
-/* What a thread of the three drivers knows about the rows.  Row 0 is the set as given, row r > 0 permutation r - 1 of the
- * generator, filled into the thread's own arrays; thread k of T takes the rows first + k, first + k + T, .. below nrows and
- * hands each, with its arrays, to the driver's row function, until one answers nonzero (a tile that could not be read). */
+/* ---- THE null driver: the one place that shares the rows of a null out over threads ----------------------------------------
+ * Row 0 is the set as given, row r > 0 what the placement makes of it for r - 1 (permutation, draw or shift r - 1), filled into
+ * the thread's own arrays.  A statistic declares its thread's job with a perm_stripe as the FIRST member, asks stripe_threads
+ * how many there will be, sets its own fields of job[0 .. T) and calls stripe_drive, which gives every thread its arrays (the
+ * permuted set, `extra` words of the statistic's choosing, the drawn contigs under a pool) and a tile buffer, runs thread k of
+ * T over the rows first + k, first + k + T, .. below nrows, each handed to the statistic's row function until one answers
+ * nonzero (a tile that could not be read), and frees what it took.  Results, their copy-out, the statistic's own refusals and
+ * whether the threads run at all at an empty shape stay with the statistic. */
+typedef int (*perm_row_fn)(void *job, int64_t r, const int32_t *s, const int32_t *e);
 typedef struct {
     const igdc_db *db; const igdc_map *m;
-    const int32_t *ichr, *qs, *qe, *ctg_len;
+    const int32_t *ichr, *qs, *qe;
     int64_t nq, first, nrows;
-    int mode; uint64_t seed;
-    const igd_hip_workspace *ws;        /* the checked table of mode IGD_HIP_PERM_WORKSPACE, or NULL */
-    const int32_t *offsets;             /* the shift placement (igdc_shift_support_host_ov): row r > 0 is the set moved by offsets[r - 1]; or NULL */
-    const perm_pool *pool;              /* resampling (the _rs entries): row r > 0 is draw r - 1 from the pool, contigs into pc; or NULL */
-    int32_t *ps, *pe, *pc;              /* the permuted set; the drawn contigs (pool only) */
+    perm_place pl;
+    perm_row_fn row;
+    int32_t *ps, *pe, *pc, *extra;      /* the permuted set; the drawn contigs (pool only); the statistic's words */
     const int32_t *rowc;                /* the contigs of the row in hand: ichr, or pc for a draw */
+    tilebuf tb;                         /* for the row functions that walk tiles themselves */
     int k, T, failed;
 } perm_stripe;
-typedef int (*perm_row_fn)(void *job, int64_t r, const int32_t *s, const int32_t *e);
 
-static void stripe_init(perm_stripe *S, const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe,
-                        int64_t nq, const int32_t *ctg_len, int mode, uint64_t seed, const igd_hip_workspace *ws, int64_t first, int64_t nrows,
-                        int32_t *ps, int k, int T)
+static void *stripe_run(void *job)
 {
-    S->db = db; S->m = m; S->ichr = ichr; S->qs = qs; S->qe = qe; S->ctg_len = ctg_len;
-    S->nq = nq; S->first = first; S->nrows = nrows; S->mode = mode; S->seed = seed; S->ws = ws; S->offsets = NULL;
-    S->pool = NULL; S->pc = NULL; S->rowc = ichr;
-    S->ps = ps; S->pe = ps + nq;
-    S->k = k; S->T = T; S->failed = 0;
-}
-
-static void perm_rows(perm_stripe *S, perm_row_fn row, void *job)
-{
+    perm_stripe *S = (perm_stripe *)job;
+    tb_open(&S->tb);
     for (int64_t r = S->first + S->k; r < S->nrows && !S->failed; r += S->T) {
         const int32_t *s = S->qs, *e = S->qe;
         S->rowc = S->ichr;
         if (r > 0) {
-            if (S->pool) {
-                resample_regions_fill(S->pool, S->nq, S->seed, r - 1, 1, S->pc, S->ps, S->pe);
+            if (S->pl.pool) {
+                resample_regions_fill(S->pl.pool, S->nq, S->pl.seed, r - 1, 1, S->pc, S->ps, S->pe);
                 S->rowc = S->pc;
             }
-            else if (S->offsets) shift_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->offsets + (r - 1), 1, S->ps, S->pe);
-            else perm_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->ctg_len, S->db->nCtg, S->mode, S->seed, r - 1, 1, S->ps, S->pe, S->ws);
+            else if (S->pl.offsets) shift_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->pl.ctg_len, S->db->nCtg, S->pl.offsets + (r - 1), 1, S->ps, S->pe);
+            else perm_regions_fill(S->ichr, S->qs, S->qe, S->nq, S->db->nCtg, &S->pl, r - 1, 1, S->ps, S->pe);
             s = S->ps; e = S->pe;
         }
-        if (row(job, r, s, e)) S->failed = 1;
+        if (S->row(job, r, s, e)) S->failed = 1;
     }
+    tb_close(&S->tb);
+    return NULL;
+}
+
+/* the threads a null of `rows` permuted rows over nq regions is worth: never more than there are rows */
+static int stripe_threads(int64_t nq, int64_t rows)
+{
+    const int T = host_threads(nq * rows > 0 ? nq * rows : 1);
+    return T > rows ? (int)rows : T;
+}
+
+/* T jobs of `size` bytes at `jobs` (T from stripe_threads(nq, nrows - first)), each thread with 2 nq + extra words of its own.
+ * 0, or -1 when memory could not be had or a row function failed. */
+static int stripe_drive(void *jobs, size_t size, int T, int64_t extra, const igdc_db *db, const igdc_map *m, const int32_t *ichr,
+                        const int32_t *qs, const int32_t *qe, int64_t nq, const perm_place *pl, int64_t first, int64_t nrows, perm_row_fn row)
+{
+    const size_t per = 2 * (size_t)nq + (size_t)extra;
+    int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * per + 1));
+    int32_t *pc = pl->pool ? (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (size_t)nq + 1)) : NULL;
+    int rc = w && (pc || !pl->pool) ? 0 : -1;
+    for (int k = 0; k < T && rc == 0; k++) {
+        perm_stripe *S = (perm_stripe *)((char *)jobs + (size_t)k * size);
+        S->db = db; S->m = m; S->ichr = ichr; S->qs = qs; S->qe = qe;
+        S->nq = nq; S->first = first; S->nrows = nrows; S->pl = *pl; S->row = row;
+        S->ps = w + (size_t)k * per; S->pe = S->ps + nq; S->extra = S->pe + nq;
+        S->pc = pc ? pc + (size_t)k * (size_t)nq : NULL; S->rowc = ichr;
+        S->k = k; S->T = T; S->failed = 0;
+    }
+    if (rc == 0) {
+        run_threads(stripe_run, jobs, size, T);
+        for (int k = 0; k < T; k++) if (((perm_stripe *)((char *)jobs + (size_t)k * size))->failed) rc = -1;
+    }
+    free(w); free(pc);
+    return rc;
 }
 
 /* igdc_permute_host's thread: rows 1 .. nperm, each walked with the per-query code of igdc_support_host and folded into the
@@ -1427,12 +1469,6 @@ static int perm_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
     }
     return 0;
 }
-static void *perm_run(void *arg)
-{
-    perm_job *P = (perm_job *)arg;
-    perm_rows(&P->s, perm_row, P);
-    return NULL;
-}
 
 int igdc_permute_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                       const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
@@ -1450,48 +1486,31 @@ int igdc_permute_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ic
                                 min_overlap, NULL);
 }
 
-/* the contigs the threads of a resampling call draw into: nq words per thread (NULL without a pool; *bad when it cannot be had) */
-static int32_t *pool_contigs(const perm_pool *pool, int T, int64_t nq, int *bad)
-{
-    int32_t *pc = pool ? (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (size_t)nq + 1)) : NULL;
-    if (pool && !pc) *bad = -1;
-    return pc;
-}
-
-/* the body of igdc_permute_host_ws and, with a pool and no ctg_len, of igdc_permute_host_rs */
+/* the body of the igdc_permute_host entries: the set as given through igdc_support_host_ov, then rows 1 .. nperm */
 static int permute_host_run(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                            const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *observed,
-                            int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
-                            const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws, const perm_pool *pool)
+                            const perm_place *pl, int64_t nperm, int32_t v, int rule, int64_t *observed, int64_t *sum, int64_t *sumsq,
+                            int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap)
 {
     const igd_hip_min_overlap *mo = igd_hip_min_overlap_active(min_overlap) ? min_overlap : NULL;
     if (!igd_hip_min_overlap_valid(min_overlap) || !observed || (rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) ||
-        perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, pool) ||
+        perm_args_bad(db, m, ichr, qs, qe, nq, nperm, pl) ||
         (unsigned __int128)nperm * (unsigned __int128)nq * (unsigned __int128)nq >= (unsigned __int128)1 << 63)
         return -1;
     const int64_t nF = db->nFiles, nC = nF + 1;
-    int T = host_threads(nq * nperm > 0 ? nq * nperm : 1);
-    if (T > nperm) T = (int)nperm;
-    /* per thread: 6 statistics, row and stamps (8 nC words), the permuted set (2 nq int32); + the observed row */
+    const int T = stripe_threads(nq, nperm);
+    /* per thread: 6 statistics, row and stamps (8 nC words); + the observed row */
     int64_t *w = (int64_t *)calloc((size_t)T * 8 * (size_t)nC + (size_t)nC, sizeof(int64_t));
-    int32_t *pq = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 2 * (size_t)nq + 1));
-    int rc = w && pq ? 0 : -1;
-    int32_t *pcb = pool_contigs(pool, T, nq, &rc);
+    int rc = w ? 0 : -1;
     int64_t *obs = w ? w + (size_t)T * 8 * (size_t)nC : NULL;
     if (rc == 0 && nq > 0) rc = igdc_support_host_ov(db, m, ichr, qs, qe, nq, v, rule, obs, &obs[nF], mo);
     perm_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
-        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 1, nperm + 1, pq + (size_t)k * 2 * (size_t)nq, k, T);
-        job[k].s.pool = pool; job[k].s.pc = pcb ? pcb + (size_t)k * (size_t)nq : NULL;
         job[k].v = v; job[k].rule = rule; job[k].observed = obs; job[k].mo = mo;
         job[k].acc = w + (size_t)k * 8 * (size_t)nC;
         job[k].row = job[k].acc + 6 * nC; job[k].last = job[k].row + nC;
         for (int64_t f = 0; f < nC; f++) { job[k].acc[4 * nC + f] = INT64_MAX; job[k].acc[5 * nC + f] = INT64_MIN; }
     }
-    if (rc == 0) {
-        run_threads(perm_run, job, sizeof job[0], T);
-        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
-    }
+    if (rc == 0) rc = stripe_drive(job, sizeof job[0], T, 0, db, m, ichr, qs, qe, nq, pl, 1, nperm + 1, perm_row);
     if (rc == 0) {
         int64_t *a0 = job[0].acc;
         for (int k = 1; k < T; k++)
@@ -1505,7 +1524,7 @@ static int permute_host_run(const igdc_db *db, const igdc_map *m, const int32_t 
         memcpy(observed, obs, sizeof(int64_t) * (size_t)nC);
         for (int s = 0; s < 6; s++) if (out[s]) memcpy(out[s], a0 + s * nC, sizeof(int64_t) * (size_t)nC);
     }
-    free(w); free(pq); free(pcb);
+    free(w);
     return rc;
 }
 
@@ -1514,8 +1533,8 @@ int igdc_permute_host_ws(const igdc_db *db, const igdc_map *m, const int32_t *ic
                          int64_t *sum, int64_t *sumsq, int64_t *n_ge, int64_t *n_le, int64_t *pmin, int64_t *pmax,
                          const igd_hip_min_overlap *min_overlap, const igd_hip_workspace *ws)
 {
-    return permute_host_run(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax,
-                            min_overlap, ws, NULL);
+    const perm_place pl = {ctg_len, mode, seed, ws, NULL, NULL};
+    return permute_host_run(db, m, ichr, qs, qe, nq, &pl, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax, min_overlap);
 }
 
 int igdc_permute_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -1524,8 +1543,8 @@ int igdc_permute_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ic
                          int64_t *pmin, int64_t *pmax, const igd_hip_min_overlap *min_overlap)
 {
     const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
-    return permute_host_run(db, m, ichr, qs, qe, nq, NULL, IGD_HIP_PERM_RESAMPLE, seed, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin,
-                            pmax, min_overlap, NULL, &pool);
+    const perm_place pl = {NULL, IGD_HIP_PERM_RESAMPLE, seed, NULL, NULL, &pool};
+    return permute_host_run(db, m, ichr, qs, qe, nq, &pl, nperm, v, rule, observed, sum, sumsq, n_ge, n_le, pmin, pmax, min_overlap);
 }
 
 /* igdc_shift_support_host_ov's thread: rows 1 .. nshift of the stripe (row r is the set moved by offsets[r - 1]), each walked
@@ -1552,12 +1571,6 @@ static int shift_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
     row[nF] = J.total;
     return 0;
 }
-static void *shift_run(void *arg)
-{
-    shift_job *P = (shift_job *)arg;
-    perm_rows(&P->s, shift_row, P);
-    return NULL;
-}
 
 int igdc_shift_support_host_ov(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
                                const int32_t *ctg_len, const int32_t *offsets, int64_t nshift, int32_t v, int rule, int64_t *shifted,
@@ -1572,25 +1585,19 @@ int igdc_shift_support_host_ov(const igdc_db *db, const igdc_map *m, const int32
         memset(shifted, 0, sizeof(int64_t) * (size_t)(nshift * nC));
         return 0;
     }
-    int T = host_threads(nq * nshift);
-    if (T > nshift) T = (int)nshift;
-    /* the call's matrix, then per thread the stamps (nC words) and the shifted set (2 nq int32) */
+    const perm_place pl = {ctg_len, 0, 0, NULL, offsets, NULL};
+    const int T = stripe_threads(nq, nshift);
+    /* the call's matrix, then per thread the stamps (nC words) */
     int64_t *w = (int64_t *)calloc((size_t)(nshift + T) * (size_t)nC, sizeof(int64_t));
-    int32_t *pq = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 2 * (size_t)nq + 1));
-    int rc = w && pq ? 0 : -1;
+    int rc = w ? 0 : -1;
     shift_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
-        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, 0, 0, NULL, 1, nshift + 1, pq + (size_t)k * 2 * (size_t)nq, k, T);
-        job[k].s.offsets = offsets;
         job[k].v = v; job[k].rule = rule; job[k].mo = mo;
         job[k].out = w; job[k].last = w + (size_t)(nshift + k) * (size_t)nC;
     }
-    if (rc == 0) {
-        run_threads(shift_run, job, sizeof job[0], T);
-        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
-    }
+    if (rc == 0) rc = stripe_drive(job, sizeof job[0], T, 0, db, m, ichr, qs, qe, nq, &pl, 1, nshift + 1, shift_row);
     if (rc == 0) memcpy(shifted, w, sizeof(int64_t) * (size_t)(nshift * nC));
-    free(w); free(pq);
+    free(w);
     return rc;
 }
 
@@ -1889,7 +1896,7 @@ int igdc_map_summary(const int64_t *n_hit, const int64_t *pairs, const int64_t *
 }
 
 /* ---- permutation null of the nearest-record distances (what igd_hip_permute_nearest computes) ----------------------------
- * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator (perm_rows); a row is
+ * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator (stripe_run); a row is
  * igdc_nearest_sets_host's walk over its regions (one_region_nearest) summed into the three statistics.  Each thread has its
  * own permuted arrays, distance row and tile buffer; the rows are disjoint.  Everything is computed into a buffer and copied out
  * at the end: -1 (a refused argument, a tile that could not be read) writes nothing. */
@@ -1897,8 +1904,6 @@ typedef struct {
     perm_stripe s;
     int32_t window, v; int use_v;
     int64_t *res;           /* three matrices of nrows x (nFiles + 1) */
-    int32_t *row;           /* one distance row */
-    tilebuf tb;
 } pnear_job;
 
 static int pnear_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
@@ -1906,26 +1911,19 @@ static int pnear_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
     pnear_job *P = (pnear_job *)job;
     const int64_t nF = P->s.db->nFiles, nC = nF + 1;
     int64_t *nw = P->res + r * nC, *no = nw + P->s.nrows * nC, *sd = no + P->s.nrows * nC;
-    for (int64_t i = 0; i < P->s.nq && !P->tb.failed; i++) {
-        const int32_t dm = one_region_nearest(P->s.db, P->s.m, &P->tb, P->s.rowc[i], s[i], e[i], P->window, P->v, P->use_v, P->row);
+    int32_t *row = P->s.extra;                                             /* one distance row */
+    for (int64_t i = 0; i < P->s.nq && !P->s.tb.failed; i++) {
+        const int32_t dm = one_region_nearest(P->s.db, P->s.m, &P->s.tb, P->s.rowc[i], s[i], e[i], P->window, P->v, P->use_v, row);
         if (dm < 0) continue;                                          /* (no record within the window: the row is all -1) */
         for (int64_t f = 0; f < nC; f++) {
-            const int32_t d = f < nF ? P->row[f] : dm;
+            const int32_t d = f < nF ? row[f] : dm;
             if (d < 0) continue;
             nw[f]++;
             no[f] += d == 0;
             sd[f] += d;
         }
     }
-    return P->tb.failed;
-}
-static void *pnear_run(void *arg)
-{
-    pnear_job *P = (pnear_job *)arg;
-    tb_open(&P->tb);
-    perm_rows(&P->s, pnear_row, P);
-    tb_close(&P->tb);
-    return NULL;
+    return P->s.tb.failed;
 }
 
 int igdc_permute_nearest_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -1935,37 +1933,27 @@ int igdc_permute_nearest_host(const igdc_db *db, const igdc_map *m, const int32_
     return igdc_permute_nearest_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap, sum_dist, NULL);
 }
 
-/* the body of igdc_permute_nearest_host_ws and, with a pool and no ctg_len, of igdc_permute_nearest_host_rs */
+/* the body of the igdc_permute_nearest_host entries: per thread a distance row of nFiles words */
 static int permute_nearest_host_run(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                                    const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
-                                    int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws,
-                                    const perm_pool *pool)
+                                    const perm_place *pl, int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap,
+                                    int64_t *sum_dist)
 {
-    if (!igd_hip_nearest_window_valid(window) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, pool)) return -1;
+    if (!igd_hip_nearest_window_valid(window) || perm_args_bad(db, m, ichr, qs, qe, nq, nperm, pl)) return -1;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
-    int T = host_threads(nq * R > 0 ? nq * R : 1);
-    if (T > R) T = (int)R;
+    const int T = stripe_threads(nq, R);
     int64_t *res = (int64_t *)calloc((size_t)(3 * R * nC), sizeof(int64_t));
-    int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (2 * (size_t)nq + (size_t)nF) + 1));
-    int rc = res && w ? 0 : -1;
-    int32_t *pcb = pool_contigs(pool, T, nq, &rc);
+    int rc = res ? 0 : -1;
     pnear_job job[HOST_MAX_THREADS];
-    for (int k = 0; k < T && rc == 0; k++) {
-        int32_t *mine = w + (size_t)k * (2 * (size_t)nq + (size_t)nF);
-        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 0, R, mine, k, T);
-        job[k].s.pool = pool; job[k].s.pc = pcb ? pcb + (size_t)k * (size_t)nq : NULL;
+    for (int k = 0; k < T; k++) {
         job[k].window = window; job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
-        job[k].res = res; job[k].row = mine + 2 * nq;
+        job[k].res = res;
     }
-    if (rc == 0 && nq > 0 && nF > 0) {
-        run_threads(pnear_run, job, sizeof job[0], T);
-        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
-    }
+    if (rc == 0 && nq > 0 && nF > 0) rc = stripe_drive(job, sizeof job[0], T, nF, db, m, ichr, qs, qe, nq, pl, 0, R, pnear_row);
     if (rc == 0) {
         int64_t *const out[3] = {n_within, n_overlap, sum_dist};
         for (int s = 0; s < 3; s++) if (out[s]) memcpy(out[s], res + (size_t)s * (size_t)(R * nC), sizeof(int64_t) * (size_t)(R * nC));
     }
-    free(res); free(w); free(pcb);
+    free(res);
     return rc;
 }
 
@@ -1973,7 +1961,8 @@ int igdc_permute_nearest_host_ws(const igdc_db *db, const igdc_map *m, const int
                                  const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t window, int32_t v,
                                  int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist, const igd_hip_workspace *ws)
 {
-    return permute_nearest_host_run(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, window, v, n_within, n_overlap, sum_dist, ws, NULL);
+    const perm_place pl = {ctg_len, mode, seed, ws, NULL, NULL};
+    return permute_nearest_host_run(db, m, ichr, qs, qe, nq, &pl, nperm, window, v, n_within, n_overlap, sum_dist);
 }
 
 int igdc_permute_nearest_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -1981,8 +1970,8 @@ int igdc_permute_nearest_host_rs(const igdc_db *db, const igdc_map *m, const int
                                  int64_t nperm, int32_t window, int32_t v, int64_t *n_within, int64_t *n_overlap, int64_t *sum_dist)
 {
     const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
-    return permute_nearest_host_run(db, m, ichr, qs, qe, nq, NULL, IGD_HIP_PERM_RESAMPLE, seed, nperm, window, v, n_within, n_overlap, sum_dist,
-                                    NULL, &pool);
+    const perm_place pl = {NULL, IGD_HIP_PERM_RESAMPLE, seed, NULL, NULL, &pool};
+    return permute_nearest_host_run(db, m, ichr, qs, qe, nq, &pl, nperm, window, v, n_within, n_overlap, sum_dist);
 }
 
 /* the summary of a null distribution of distance statistics; igd_core.h has the formulas */
@@ -2046,7 +2035,7 @@ int igdc_perm_nearest_summary(const int64_t *n_within, const int64_t *sum_dist, 
 }
 
 /* ---- permutation null of the overlapping records' values (what igd_hip_permute_map computes) ------------------------------
- * Row 0 is the set as given, row p + 1 permutation p of the generator or draw p of the pool (perm_rows); a row is
+ * Row 0 is the set as given, row p + 1 permutation p of the generator or draw p of the pool (stripe_run); a row is
  * igdc_map_sets_host's row computer over its regions (one_region_map) summed into the three statistics as map_sets_fold sums a
  * region.  Each thread has its own permuted arrays, count and agg row and tile buffer; the rows are disjoint.  Everything is
  * computed into a buffer and copied out at the end: -1 (a refused argument, a tile that could not be read) writes nothing. */
@@ -2054,65 +2043,44 @@ typedef struct {
     perm_stripe s;
     int op; int32_t v; int use_v;
     int64_t *res;           /* three matrices of nrows x nFiles */
-    int32_t *count;         /* one count row */
-    int64_t *agg;           /* one agg row (NULL under COUNT) */
-    tilebuf tb;
+    int64_t *agg;           /* one agg row (under COUNT it receives the counts: agg_sum IS pairs) */
 } pmap_job;
 
 static int pmap_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
 {
     pmap_job *P = (pmap_job *)job;
     const int64_t nF = P->s.db->nFiles;
-    map_sets_ctx c = {P->s.db, P->s.m, NULL, NULL, NULL, P->op, P->v, P->count, P->agg, P->res, P->res + P->s.nrows * nF,
+    int32_t *count = P->s.extra;                                           /* one count row */
+    map_sets_ctx c = {P->s.db, P->s.m, NULL, NULL, NULL, P->op, P->v, count, P->agg, P->res, P->res + P->s.nrows * nF,
                       P->res + 2 * P->s.nrows * nF};
-    for (int64_t i = 0; i < P->s.nq && !P->tb.failed; i++) {
-        one_region_map(P->s.db, P->s.m, &P->tb, P->s.rowc[i], s[i], e[i], P->op, P->v, P->use_v, P->count, P->agg);
-        if (!P->tb.failed) map_sets_fold(&c, (int32_t)r, 0);
+    for (int64_t i = 0; i < P->s.nq && !P->s.tb.failed; i++) {
+        one_region_map(P->s.db, P->s.m, &P->s.tb, P->s.rowc[i], s[i], e[i], P->op, P->v, P->use_v, count, P->agg);
+        if (!P->s.tb.failed) map_sets_fold(&c, (int32_t)r, 0);
     }
-    return P->tb.failed;
-}
-static void *pmap_run(void *arg)
-{
-    pmap_job *P = (pmap_job *)arg;
-    tb_open(&P->tb);
-    perm_rows(&P->s, pmap_row, P);
-    tb_close(&P->tb);
-    return NULL;
+    return P->s.tb.failed;
 }
 
-/* the body of igdc_permute_map_host_ws and, with a pool and no ctg_len, of igdc_permute_map_host_rs */
+/* the body of the igdc_permute_map_host entries: per thread a count row of nFiles words and an agg row of nFiles 64-bit words */
 static int permute_map_host_run(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                                const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit,
-                                int64_t *pairs, int64_t *agg_sum, const igd_hip_workspace *ws, const perm_pool *pool)
+                                const perm_place *pl, int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
 {
-    if (!db || !map_op_ok(db, op) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, pool)) return -1;
+    if (!db || !map_op_ok(db, op) || perm_args_bad(db, m, ichr, qs, qe, nq, nperm, pl)) return -1;
     const int64_t nF = db->nFiles, R = nperm + 1;
-    int T = host_threads(nq * R > 0 ? nq * R : 1);
-    if (T > R) T = (int)R;
+    const int T = stripe_threads(nq, R);
     int64_t *res = (int64_t *)calloc((size_t)(3 * R * nF) + 1, sizeof(int64_t));
-    /* per thread: the permuted set (2 nq words), a count row (nF words) and an agg row (nF 64-bit words, 8-byte aligned in `a`) */
-    int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * (2 * (size_t)nq + (size_t)nF) + 1));
     int64_t *a = (int64_t *)malloc(sizeof(int64_t) * ((size_t)T * (size_t)nF + 1));
-    int rc = res && w && a ? 0 : -1;
-    int32_t *pcb = pool_contigs(pool, T, nq, &rc);
+    int rc = res && a ? 0 : -1;
     pmap_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
-        int32_t *mine = w + (size_t)k * (2 * (size_t)nq + (size_t)nF);
-        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 0, R, mine, k, T);
-        job[k].s.pool = pool; job[k].s.pc = pcb ? pcb + (size_t)k * (size_t)nq : NULL;
         job[k].op = op; job[k].v = v; job[k].use_v = v != IGD_HIP_NO_VALUE_FILTER && db->gType == 1;
-        job[k].res = res; job[k].count = mine + 2 * nq;
-        job[k].agg = a + (size_t)k * (size_t)nF;    /* (under COUNT it receives the counts: agg_sum IS pairs) */
+        job[k].res = res; job[k].agg = a + (size_t)k * (size_t)nF;
     }
-    if (rc == 0 && nq > 0 && nF > 0) {
-        run_threads(pmap_run, job, sizeof job[0], T);
-        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
-    }
+    if (rc == 0 && nq > 0 && nF > 0) rc = stripe_drive(job, sizeof job[0], T, nF, db, m, ichr, qs, qe, nq, pl, 0, R, pmap_row);
     if (rc == 0) {
         int64_t *const out[3] = {n_hit, pairs, agg_sum};
         for (int s = 0; s < 3; s++) if (out[s]) memcpy(out[s], res + (size_t)s * (size_t)(R * nF), sizeof(int64_t) * (size_t)(R * nF));
     }
-    free(res); free(w); free(a); free(pcb);
+    free(res); free(a);
     return rc;
 }
 
@@ -2120,7 +2088,8 @@ int igdc_permute_map_host_ws(const igdc_db *db, const igdc_map *m, const int32_t
                              const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int op, int32_t v, int64_t *n_hit,
                              int64_t *pairs, int64_t *agg_sum, const igd_hip_workspace *ws)
 {
-    return permute_map_host_run(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, op, v, n_hit, pairs, agg_sum, ws, NULL);
+    const perm_place pl = {ctg_len, mode, seed, ws, NULL, NULL};
+    return permute_map_host_run(db, m, ichr, qs, qe, nq, &pl, nperm, op, v, n_hit, pairs, agg_sum);
 }
 
 int igdc_permute_map_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -2135,7 +2104,8 @@ int igdc_permute_map_host_rs(const igdc_db *db, const igdc_map *m, const int32_t
                              int64_t nperm, int op, int32_t v, int64_t *n_hit, int64_t *pairs, int64_t *agg_sum)
 {
     const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
-    return permute_map_host_run(db, m, ichr, qs, qe, nq, NULL, IGD_HIP_PERM_RESAMPLE, seed, nperm, op, v, n_hit, pairs, agg_sum, NULL, &pool);
+    const perm_place pl = {NULL, IGD_HIP_PERM_RESAMPLE, seed, NULL, NULL, &pool};
+    return permute_map_host_run(db, m, ichr, qs, qe, nq, &pl, nperm, op, v, n_hit, pairs, agg_sum);
 }
 
 /* the summary of a null distribution of value statistics; igd_core.h has the formulas */
@@ -2391,7 +2361,7 @@ int igdc_jaccard_summary(const int64_t *inter, const int64_t *set_bp, const int6
 }
 
 /* ---- permutation null of the base-pair overlap (what igd_hip_permute_bp computes; include/igd_hip.h has the definitions) --
- * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator (perm_rows); a row is
+ * Row 0 is the set as given, row p + 1 permutation p of igdc_permute_regions_host's generator (stripe_run); a row is
  * igdc_jaccard_host's treatment of one set: igdc_merge_host at gap 0, then igdc_coverage_host over the runs.  Each thread has
  * its own permuted arrays and run arrays; the rows are disjoint.  Everything is computed into a buffer and copied out at the
  * end: -1 (a refused argument, a tile that could not be read) writes nothing. */
@@ -2399,7 +2369,6 @@ typedef struct {
     perm_stripe s;
     int32_t v; int rule;
     int64_t *inter, *set_bp, *n_merged, *dropped;   /* nrows x (nFiles + 1), nrows, nrows, nrows */
-    int32_t *mr;                                    /* the runs (3 x nq) */
 } pbp_job;
 
 static int pbp_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
@@ -2407,19 +2376,14 @@ static int pbp_row(void *job, int64_t r, const int32_t *s, const int32_t *e)
     pbp_job *P = (pbp_job *)job;
     const igdc_db *db = P->s.db;
     const int64_t nF = db->nFiles, nq = P->s.nq, off[2] = {0, nq};
+    int32_t *mr = P->s.extra;                                              /* the runs (3 x nq) */
     int64_t moff[2], bp = 0;
-    if (igdc_merge_host(db, P->s.rowc, s, e, off, 1, 0, P->mr, P->mr + nq, P->mr + 2 * nq, moff, NULL, &P->dropped[r]) != 0) return 1;
-    for (int64_t i = 0; i < moff[1]; i++) bp += (int64_t)P->mr[2 * nq + i] - (int64_t)P->mr[nq + i];
+    if (igdc_merge_host(db, P->s.rowc, s, e, off, 1, 0, mr, mr + nq, mr + 2 * nq, moff, NULL, &P->dropped[r]) != 0) return 1;
+    for (int64_t i = 0; i < moff[1]; i++) bp += (int64_t)mr[2 * nq + i] - (int64_t)mr[nq + i];
     P->set_bp[r] = bp;
     P->n_merged[r] = moff[1];
     int64_t *row = P->inter + r * (nF + 1);
-    return igdc_coverage_host(db, P->s.m, P->mr, P->mr + nq, P->mr + 2 * nq, moff[1], P->v, P->rule, row, row + nF) != 0;
-}
-static void *pbp_run(void *arg)
-{
-    pbp_job *P = (pbp_job *)arg;
-    perm_rows(&P->s, pbp_row, P);
-    return NULL;
+    return igdc_coverage_host(db, P->s.m, mr, mr + nq, mr + 2 * nq, moff[1], P->v, P->rule, row, row + nF) != 0;
 }
 
 int igdc_permute_bp_host(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -2429,38 +2393,29 @@ int igdc_permute_bp_host(const igdc_db *db, const igdc_map *m, const int32_t *ic
     return igdc_permute_bp_host_ws(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, NULL);
 }
 
-/* the body of igdc_permute_bp_host_ws and, with a pool and no ctg_len, of igdc_permute_bp_host_rs */
+/* the body of the igdc_permute_bp_host entries: per thread the runs of a row, 3 nq words */
 static int permute_bp_host_run(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
-                               const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
-                               int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws, const perm_pool *pool)
+                               const perm_place *pl, int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged,
+                               int64_t *n_dropped)
 {
-    if ((rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || perm_args_bad(db, m, ichr, qs, qe, nq, ctg_len, mode, nperm, ws, pool)) return -1;
+    if ((rule != IGD_HIP_RULE_NEST && rule != IGD_HIP_RULE_FLAT) || perm_args_bad(db, m, ichr, qs, qe, nq, nperm, pl)) return -1;
     const int64_t nF = db->nFiles, nC = nF + 1, R = nperm + 1;
-    int T = host_threads(nq * R > 0 ? nq * R : 1);
-    if (T > R) T = (int)R;
+    const int T = stripe_threads(nq, R);
     int64_t *res = (int64_t *)calloc((size_t)(R * nC + 3 * R), sizeof(int64_t));
-    int32_t *w = (int32_t *)malloc(sizeof(int32_t) * ((size_t)T * 5 * (size_t)nq + 1));
-    int rc = res && w ? 0 : -1;
-    int32_t *pcb = pool_contigs(pool, T, nq, &rc);
+    int rc = res ? 0 : -1;
     pbp_job job[HOST_MAX_THREADS];
     for (int k = 0; k < T && rc == 0; k++) {
-        int32_t *mine = w + (size_t)k * 5 * (size_t)nq;
-        stripe_init(&job[k].s, db, m, ichr, qs, qe, nq, ctg_len, mode, seed, ws, 0, R, mine, k, T);
-        job[k].s.pool = pool; job[k].s.pc = pcb ? pcb + (size_t)k * (size_t)nq : NULL;
-        job[k].v = v; job[k].rule = rule; job[k].mr = mine + 2 * nq;
+        job[k].v = v; job[k].rule = rule;
         job[k].inter = res; job[k].set_bp = res + R * nC; job[k].n_merged = job[k].set_bp + R; job[k].dropped = job[k].n_merged + R;
     }
-    if (rc == 0 && nq > 0) {
-        run_threads(pbp_run, job, sizeof job[0], T);
-        for (int k = 0; k < T; k++) if (job[k].s.failed) rc = -1;
-    }
+    if (rc == 0 && nq > 0) rc = stripe_drive(job, sizeof job[0], T, 3 * nq, db, m, ichr, qs, qe, nq, pl, 0, R, pbp_row);
     if (rc == 0) {
         if (inter) memcpy(inter, res, sizeof(int64_t) * (size_t)(R * nC));
         if (set_bp) memcpy(set_bp, res + R * nC, sizeof(int64_t) * (size_t)R);
         if (n_merged) memcpy(n_merged, res + R * nC + R, sizeof(int64_t) * (size_t)R);
         if (n_dropped) *n_dropped = res[R * nC + 2 * R];
     }
-    free(res); free(w); free(pcb);
+    free(res);
     return rc;
 }
 
@@ -2468,7 +2423,8 @@ int igdc_permute_bp_host_ws(const igdc_db *db, const igdc_map *m, const int32_t 
                             const int32_t *ctg_len, int mode, uint64_t seed, int64_t nperm, int32_t v, int rule, int64_t *inter,
                             int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped, const igd_hip_workspace *ws)
 {
-    return permute_bp_host_run(db, m, ichr, qs, qe, nq, ctg_len, mode, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped, ws, NULL);
+    const perm_place pl = {ctg_len, mode, seed, ws, NULL, NULL};
+    return permute_bp_host_run(db, m, ichr, qs, qe, nq, &pl, nperm, v, rule, inter, set_bp, n_merged, n_dropped);
 }
 
 int igdc_permute_bp_host_rs(const igdc_db *db, const igdc_map *m, const int32_t *ichr, const int32_t *qs, const int32_t *qe, int64_t nq,
@@ -2476,8 +2432,8 @@ int igdc_permute_bp_host_rs(const igdc_db *db, const igdc_map *m, const int32_t 
                             int64_t nperm, int32_t v, int rule, int64_t *inter, int64_t *set_bp, int64_t *n_merged, int64_t *n_dropped)
 {
     const perm_pool pool = {pool_ichr, pool_qs, pool_qe, npool};
-    return permute_bp_host_run(db, m, ichr, qs, qe, nq, NULL, IGD_HIP_PERM_RESAMPLE, seed, nperm, v, rule, inter, set_bp, n_merged, n_dropped,
-                               NULL, &pool);
+    const perm_place pl = {NULL, IGD_HIP_PERM_RESAMPLE, seed, NULL, NULL, &pool};
+    return permute_bp_host_run(db, m, ichr, qs, qe, nq, &pl, nperm, v, rule, inter, set_bp, n_merged, n_dropped);
 }
 
 /* the summary of a null distribution of base-pair overlaps; igd_core.h has the formulas */

@@ -972,6 +972,13 @@ static inline int igd_hip_workspace_valid(const igd_hip_workspace *ws, const int
     }
     return 1;
 }
+/* a mode the call can run (the engine and the host route ask here): the two free placements without a workspace,
+ * IGD_HIP_PERM_WORKSPACE with one, IGD_HIP_PERM_RESAMPLE exactly when a pool is given and never with a workspace */
+static inline int igd_hip_perm_mode_ok(int mode, int has_ws, int has_pool)
+{
+    if (has_pool || mode == IGD_HIP_PERM_RESAMPLE) return has_pool && !has_ws && mode == IGD_HIP_PERM_RESAMPLE;
+    return has_ws ? mode == IGD_HIP_PERM_WORKSPACE : (mode == IGD_HIP_PERM_CIRCULAR || mode == IGD_HIP_PERM_SHUFFLE);
+}
 /* region i = (c, *s, *e) under permutation p (base = igd_hip_perm_base(seed, p)) inside the workspace, in place; 1 when the
  * region is on a known contig, valid, and fits in no segment (it is left as it was), 0 otherwise */
 static inline IGD_HIP_HD_ int igd_hip_perm_place_ws(uint64_t base, int32_t c, int64_t i, const int32_t *ctg_len, int32_t nctg,

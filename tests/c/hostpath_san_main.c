@@ -19,7 +19,7 @@ static void mix(const void *p, size_t bytes)
 static int fails = 0;
 #define WANT(rc, call) do { if ((call) != (rc)) { fprintf(stderr, "line %d: %s did not answer %d\n", __LINE__, #call, rc); fails++; } } while (0)
 
-enum { NQ = 9000, NP = 600, NPERM = 30, NSETS = 6, LEN = 1 << 30 };
+enum { NQ = 9000, NP = 600, NPOOL = NP + 7, NPERM = 30, NSETS = 6, LEN = 1 << 30 };
 
 int main(int argc, char **argv)
 {
@@ -124,6 +124,31 @@ int main(int argc, char **argv)
         WANT(0, igdc_permute_bp_host_ws(db, m, ichr, ps, pe, NP, ctg_len, mode, 5, NPERM, 300, 1, a64, a64 + (NPERM + 1) * nC, a64 + (NPERM + 1) * nC + 64,
                                         &tot, w));
         MIX64((NPERM + 1) * nC);
+        WANT(0, igdc_permute_map_host_ws(db, m, ichr, ps, pe, NP, ctg_len, mode, 5, NPERM, mode + 1, 300, a64, a64 + (NPERM + 1) * nf,
+                                         a64 + 2 * (NPERM + 1) * nf, w));
+        MIX64(3 * (NPERM + 1) * nf);
+    }
+    /* the same four nulls by resampling: draws of NP regions from a pool a few regions larger (the first NPOOL regions above,
+     * unknown contigs and the inverted region included: a draw is copied as it stands), and the generator alone */
+    WANT(0, igdc_resample_regions_host(ichr, qs, qe, NPOOL, NP, 5, 0, 1, po, po + NP, po + 2 * NP)); mix(po, 12 * NP);
+    WANT(0, igdc_permute_host_rs(db, m, ichr, ps, pe, NP, ichr, qs, qe, NPOOL, 5, NPERM, IGD_HIP_NO_VALUE_FILTER, 1, a64, a64 + nC, a64 + 2 * nC,
+                                 a64 + 3 * nC, a64 + 4 * nC, a64 + 5 * nC, a64 + 6 * nC, &mo));
+    MIX64(7 * nC);
+    WANT(0, igdc_permute_nearest_host_rs(db, m, ichr, ps, pe, NP, ichr, qs, qe, NPOOL, 5, NPERM, 5000, 300, a64, a64 + (NPERM + 1) * nC,
+                                         a64 + 2 * (NPERM + 1) * nC));
+    MIX64(3 * (NPERM + 1) * nC);
+    WANT(0, igdc_permute_bp_host_rs(db, m, ichr, ps, pe, NP, ichr, qs, qe, NPOOL, 5, NPERM, IGD_HIP_NO_VALUE_FILTER, 0, a64, a64 + (NPERM + 1) * nC,
+                                    a64 + (NPERM + 1) * nC + 64, &tot));
+    MIX64((NPERM + 1) * nC + 128); mix(&tot, 8);
+    WANT(0, igdc_permute_map_host_rs(db, m, ichr, ps, pe, NP, ichr, qs, qe, NPOOL, 5, NPERM, IGD_HIP_MAP_SUM, IGD_HIP_NO_VALUE_FILTER, a64,
+                                     a64 + (NPERM + 1) * nf, a64 + 2 * (NPERM + 1) * nf));
+    MIX64(3 * (NPERM + 1) * nf);
+    /* the set under NPERM rigid shifts, to both sides and past the contig ends, and the shifted regions alone */
+    int32_t offsets[NPERM];
+    for (int j = 0; j < NPERM; j++) offsets[j] = (j - NPERM / 2) * 300000;
+    if (nctg > 0) {
+        WANT(0, igdc_shift_regions_host(ichr, ps, pe, NP, ctg_len, nctg, offsets, 2, po, po + 2 * NP)); mix(po, 16 * NP);
+        WANT(0, igdc_shift_support_host_ov(db, m, ichr, ps, pe, NP, ctg_len, offsets, NPERM, 300, 0, a64, &mo)); MIX64(NPERM * nC);
     }
 
     /* the file is cut under the open map: no tile can be read any more */
@@ -146,6 +171,9 @@ int main(int argc, char **argv)
         WANT(-1, igdc_permute_host(db, m, ichr, ps, pe, NP, ctg_len, 1, 5, NPERM, IGD_HIP_NO_VALUE_FILTER, 0, a64, NULL, NULL, NULL, NULL, NULL, NULL));
         WANT(-1, igdc_permute_nearest_host(db, m, ichr, ps, pe, NP, ctg_len, 1, 5, NPERM, 5000, IGD_HIP_NO_VALUE_FILTER, a64, NULL, NULL));
         WANT(-1, igdc_permute_bp_host(db, m, ichr, ps, pe, NP, ctg_len, 0, 5, NPERM, IGD_HIP_NO_VALUE_FILTER, 0, a64, NULL, NULL, NULL));
+        WANT(-1, igdc_permute_map_host_rs(db, m, ichr, ps, pe, NP, ichr, qs, qe, NPOOL, 5, NPERM, IGD_HIP_MAP_COUNT, IGD_HIP_NO_VALUE_FILTER, a64, NULL,
+                                          NULL));
+        WANT(-1, igdc_shift_support_host_ov(db, m, ichr, ps, pe, NP, ctg_len, offsets, NPERM, IGD_HIP_NO_VALUE_FILTER, 0, a64, NULL));
     }
 
     igdc_workspace_free(ws);

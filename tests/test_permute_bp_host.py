@@ -123,6 +123,19 @@ def test_host_equals_the_reference_on_the_four_database_shapes(case, workdir, ho
     assert varied and got.inter.sum() > 0 and got.n_dropped > 0, "fixture is vacuous"
 
 
+def test_one_region_and_fewer_rows_than_threads(workdir, host_threads):
+    """one region; two rows (one permutation) of 2100 regions on three threads: 4200 region rows are worth three threads, and only
+    two rows are there to share out"""
+    ldb, ctg_len, ichr, qs, qe = fixture_db(workdir, 1, 2100)
+    host_threads("3")
+    k = int(np.flatnonzero((ichr >= 0) & (ichr < len(ctg_len)) & (qe > qs))[0])
+    for mode in (PR.CIRCULAR, PR.SHUFFLE):
+        got = igd_amd.permute_bp_host(ldb.path, ichr[k:k + 1], qs[k:k + 1], qe[k:k + 1], ctg_len, 3, seed=4, mode=mode, rule=FLAT)
+        assert equal_null(got, PB.null(ldb, ichr[k:k + 1], qs[k:k + 1], qe[k:k + 1], ctg_len, 3, 4, mode, NOV, FLAT)) and got.n_merged.tolist() == [1] * 4
+        got = igd_amd.permute_bp_host(ldb.path, ichr, qs, qe, ctg_len, 1, seed=6, mode=mode, rule=FLAT)
+        assert equal_null(got, PB.null(ldb, ichr, qs, qe, ctg_len, 1, 6, mode, NOV, FLAT)) and got.inter.all(axis=1).any()
+
+
 # ---- refusals and empty calls -----------------------------------------------------------------------------------------------
 def test_refused_arguments_leave_the_outputs_as_they_were(workdir):
     ldb, ctg_len, ichr, qs, qe = fixture_db(workdir, 0, 20)

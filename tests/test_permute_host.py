@@ -168,6 +168,28 @@ def test_permute_host_equals_the_reference_statistics(case, tmp, host_threads):
         H.close()
 
 
+def test_one_region_and_fewer_rows_than_threads(tmp, host_threads):
+    """one region; one permutation of 4500 regions on three threads: 4500 region rows are worth three threads, and only one row
+    is there to share out"""
+    import igd_amd
+    rng = random.Random(77)
+    nbp, gtype, nfiles, nctg, span_tiles = NUMPY_DBS[1]
+    path, span = clustered_db(rng, tmp, "few", nbp, gtype, nfiles, nctg, span_tiles)
+    ctg_len = np.full(nctg, span + 2 * nbp, np.int32)
+    ichr, qs, qe = PR.random_regions(rng, ctg_len, 4500)
+    k = int(np.flatnonzero((ichr >= 0) & (ichr < nctg))[0])
+    host_threads("3")
+    H = HostDb(path)
+    try:
+        for mode in MODES:
+            for c, s, e, nperm in ((ichr[k:k + 1], qs[k:k + 1], qe[k:k + 1], 3), (ichr, qs, qe, 1)):
+                obs, rows = reference_rows(H, c, s, e, ctg_len, nperm, 8, mode, NOV, FLAT)
+                check_result(igd_amd.permute_host(path, c, s, e, ctg_len, nperm, 8, mode, rule=FLAT), obs, rows, (mode, nperm))
+            assert obs[:-1].any() and rows.any()
+    finally:
+        H.close()
+
+
 def test_permute_host_refuses_what_the_engine_refuses(tmp):
     import igd_amd
     from igd_amd.database import IgdError

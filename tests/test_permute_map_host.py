@@ -85,6 +85,23 @@ def test_host_equals_the_numpy_composition(op, mode, fx, host_threads):
     assert hit and moved, "fixture is vacuous"
 
 
+@pytest.mark.parametrize("mode", ["circular", "shuffle", "workspace", "resample"])
+def test_one_region_and_fewer_rows_than_threads(mode, fx, host_threads):
+    """the shapes at which a driver shared by the nulls goes wrong: one region; two rows (one permutation) of 2160 regions on three
+    threads -- 4320 region rows are worth three threads, and only two rows are there to share out; a pool as large as the set"""
+    host_threads("3")
+    ichr = fx["reg"][0]
+    k = int(np.flatnonzero((ichr >= 0) & (ichr < 2))[0])
+    check(fx, fx["ldb"], tuple(a[k:k + 1] for a in fx["reg"]), 3, "sum", 5, mode, None)
+    many = tuple(np.tile(a, 18) for a in fx["reg"])
+    wide = dict(fx, pool=tuple(np.tile(a, 6) for a in fx["pool"]))
+    got = check(wide, fx["ldb"], many, 1, "sum", 7, mode, 500)
+    assert got.n_hit.any()
+    if mode == "resample":
+        n = len(ichr)
+        check(dict(fx, pool=tuple(a[:n] for a in fx["pool"])), fx["ldb"], fx["reg"], 2, "max", 9, mode, None)
+
+
 @pytest.mark.parametrize("op", ALL_OPS)
 def test_the_placed_database(op, workdir, fx):
     """300 records of one file under one region, INT32_MIN and INT32_MAX under one region, three times INT32_MAX, -v 500 removing

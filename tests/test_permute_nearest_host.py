@@ -76,6 +76,21 @@ def test_host_equals_the_numpy_composition(case, workdir, host_threads):
     assert far, "fixture is vacuous: no permuted region lies at a distance"
 
 
+def test_one_region_and_fewer_rows_than_threads(workdir, host_threads):
+    """one region; two rows (one permutation) of 2100 regions on three threads: 4200 region rows are worth three threads, and only
+    two rows are there to share out"""
+    ldb, nbp, ctg_len, ichr, qs, qe = fixture_db(workdir, 1, 2100)
+    host_threads("3")
+    k = int(np.flatnonzero((ichr >= 0) & (ichr < len(ctg_len)))[0])
+    for mode in (PR.CIRCULAR, PR.SHUFFLE):
+        for c, s, e, nperm in ((ichr[k:k + 1], qs[k:k + 1], qe[k:k + 1], 3), (ichr, qs, qe, 1)):
+            want = PN.null(ldb, c, s, e, ctg_len, nperm, nbp, 9, mode, None)
+            got = igd_amd.permute_nearest_host(ldb.path, c, s, e, ctg_len, nperm, nbp, seed=9, mode=mode)
+            for g, w in zip(got[:3], want):
+                assert g.shape == (nperm + 1, ldb.nfiles + 1) and np.array_equal(g, w), (mode, nperm)
+        assert got.n_within[1].any()
+
+
 def test_refused_arguments_and_empty_calls(workdir):
     from igd_amd.database import IgdError
     ldb, nbp, ctg_len, ichr, qs, qe = fixture_db(workdir, 0, 20)

@@ -189,6 +189,27 @@ def test_no_region_and_one_permutation(nfx):
     assert not igd_amd.permute_host(nfx["path"], *none, None, 1, 0, "resample", universe=none).sum.any()
 
 
+def test_one_region_and_fewer_rows_than_threads(nfx, monkeypatch):
+    """one region; one draw of 4500 regions from a universe of exactly 4500 on three threads: the region rows are worth three
+    threads, and only one row (support) or two (the others, with the set as given) are there to share out"""
+    import igd_amd
+    monkeypatch.setenv("IGD_HOST_THREADS", "3")
+    pool = tuple(np.tile(a, 15) for a in nfx["pool"])
+    for reg, nperm in ((tuple(a[:1] for a in nfx["reg"]), 3), (tuple(np.tile(a, 113)[:4500] for a in nfx["reg"]), 1)):
+        assert nperm == 3 or len(reg[0]) == len(pool[0]) == 4500
+        sets = RR.resample_sets(reg, pool, nperm, 5)
+        got = igd_amd.permute_host(nfx["path"], *reg, None, nperm, 5, "resample", universe=pool)
+        for name, w in zip("observed sum sumsq n_ge n_le min max".split(), stats_of(support_rows(nfx["path"], sets))):
+            assert np.array_equal(getattr(got, name), w), (nperm, name)
+        want = igd_amd.nearest_sets_host(nfx["path"], *sets, 3000)
+        got = igd_amd.permute_nearest_host(nfx["path"], *reg, None, nperm, 3000, 5, "resample", universe=pool)
+        assert all(np.array_equal(getattr(got, n), getattr(want, n)) for n in ("n_within", "n_overlap", "sum_dist")), nperm
+        want = igd_amd.jaccard_host(nfx["path"], *sets)
+        got = igd_amd.permute_bp_host(nfx["path"], *reg, None, nperm, 5, "resample", universe=pool)
+        assert np.array_equal(got.inter, want.inter) and np.array_equal(got.set_bp, want.set_bp) and np.array_equal(got.n_merged, want.n_merged)
+    assert got.inter[1].any()
+
+
 HOST = [("permute_host", ()), ("permute_nearest_host", (100,)), ("permute_bp_host", ())]
 
 

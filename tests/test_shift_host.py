@@ -157,6 +157,19 @@ def test_threads_one_shift_no_region_and_unknown_contigs(sfx, monkeypatch):
     assert u.shape == (3, 41) and not u.any()
 
 
+def test_one_region_and_fewer_shifts_than_threads(sfx, monkeypatch):
+    """one region under every offset; one shift of 4600 regions on three threads: 4600 region rows are worth three threads, and
+    only one row is there to share out"""
+    import igd_amd
+    monkeypatch.setenv("IGD_HOST_THREADS", "3")
+    ichr, qs, qe = sfx["reg"]
+    k = int(np.flatnonzero((ichr >= 0) & (ichr < 3))[0])
+    for c, s, e, offs in ((ichr[k:k + 1], qs[k:k + 1], qe[k:k + 1], SUP_OFFSETS), (np.tile(ichr, 23), np.tile(qs, 23), np.tile(qe, 23), [STEP])):
+        want = reference_rows(sfx["path"], c, s, e, sfx["ctg_len"], np.asarray(offs, np.int32))
+        got = igd_amd.shift_support_host(sfx["path"], c, s, e, sfx["ctg_len"], offs).shifted
+        assert got.shape == want.shape and np.array_equal(got, want) and want.any()
+
+
 def test_shift_support_host_refuses_what_the_engine_refuses(sfx):
     import igd_amd
     from igd_amd.database import IgdError
